@@ -12,23 +12,25 @@ uniform random actions (scripts/overcooked_example.py:99-116 of the reference: `
 agent per step, sampling outside the timed call).  A step = one `mrl_step_with_actions` launch over
 the rank's world shard, actions already resident in HBM (a pre-sampled pool, cycled).  Worlds are
 independent, so ranks do not communicate inside the timed region of `value` (weak scaling, 32768
-worlds per GPU).  N > 1 also times the `obs_gather` leg of BASELINE.json configs[3]: the same step
+worlds per GPU).  N > 1 with --full also times the `obs_gather` leg of BASELINE.json configs[3]: the same step
 followed by the RCCL all-gather of the world-major observation shards (34 MB per rank per step).
 
 `MRL_BENCH_FORCE_DIST=1 python bench.py --gpus 1 ...` runs the N > 1 protocol at world_size 1 (it starts ONE
 rank under torch.distributed.run): process group over `nccl` (= RCCL), the fences' barrier, the max-over-ranks
-all_reduce / all_gather on device tensors and the obs_gather leg's all_gather_into_tensor all execute on the
+all_reduce / all_gather on device tensors and (--full) the obs_gather leg's all_gather_into_tensor all execute on the
 one GPU a test box has (tests/test_gpu_nccl.py); the headline extras are skipped in that mode.
 
-Timing: W warm-up steps, then blocks of exactly K steps, each bracketed by barrier +
-`torch.cuda.synchronize()` on both sides, max over ranks.  One block is the contract; when K steps
-are shorter than 50 ms (K = 20 is 0.2 ms here) the block is repeated and the MEDIAN block is
-reported (`timing.blocks` says how many), so that one scheduling hiccup is not the result.
-`timing.empty_block_ms` is what a block of no steps costs between the same two fences -- the bracket's
-share of a short block (at --steps 20 it is 6 % of the block on one GPU, more with the ranks' rendezvous
-in it); it is reported, never subtracted.
+Timing: W warm-up steps, then ONE block of exactly K steps between two fences (barrier + `torch.cuda.synchronize()`),
+max over ranks: `value` = worlds x ranks x K / block time, `ms_per_step` = block time / K.  `--dump-outputs DIR` then
+writes what the last of those steps handed its caller (below).  That is all a plain run does.
 
-Also on the line: `roofline` (algorithmic HBM bytes of the step kernel / its average launch duration,
+`--full` adds everything else the line has carried: when K steps are shorter than 50 ms the block is repeated and the
+MEDIAN block is reported (`timing.blocks` says how many), so that one scheduling hiccup is not the result;
+`timing.empty_block_ms` is what a block of no steps costs between the same two fences -- the bracket's share of a short
+block (at --steps 20 it is 6 % of the block on one GPU, more with the ranks' rendezvous in it); it is reported, never
+subtracted.  With N > 1 the `obs_gather` leg.  And:
+
+`roofline` (algorithmic HBM bytes of the step kernel / its average launch duration,
 HIP events on the launch stream over >= 300 back-to-back launches; spec and on-box measured peaks),
 `cpu_baseline` (the test-only CPU oracle in oracle/ on this host's cores, bounded sample), the
 reference harness's own two timed regions, `wrapped_n_step` (scripts/overcooked_example.py:104-106)
@@ -40,12 +42,18 @@ its kernel, average launch duration over >= 300 launches, algorithmic bytes per 
 and the 1 M-world Cartpole legs carry a `cpu_baseline` of their own (the oracle, ~2 s); `mappo_rollout_loop_32768` is
 configs[4] on one GPU (50 loop steps of tools/mappo_rollout_loop.py: the PyTorch policy's loop time and, beside it, what this
 engine owns of a loop step: `env_step_plus_buffer_insert_us`).  `build_hash` = `mrl_build_hash()` of the running library.
-With N > 1 the line also carries `expected` (and `obs_gather.expected`): what DESIGN.md section 6 predicted before any
-multi-GPU run existed.
+With N > 1 the line also carries `expected` (and, with --full, `obs_gather.expected`): what DESIGN.md section 6 predicted
+before any multi-GPU run existed.
 
 `roofline.traffic` (and `traffic` of the other legs) are HBM bytes per launch from rocprofv3 PMC passes, which
 cannot run inside this process: they come from profiles/step_traffic.json and are quoted only when that file's
 `csrc_sha16` equals the hash compiled into the running library (`mrl_build_hash()`, also on the line as `build_hash`), null otherwise.
+
+`--dump-outputs DIR` (rank 0's shard): after the first block of K timed steps -- so the state is that of W + K steps
+whatever --full adds after it -- DIR/observation.npy (the world-major observations, worlds x players x H x W x F),
+DIR/reward.npy (players x worlds) and DIR/done.npy (worlds), float32.  The actions come from a seeded generator, so the
+same arguments give the same arrays on every run; above DUMP_BYTES the three arrays hold the same fixed, seeded sample of
+worlds, in ascending world order.
 """
 import argparse
 import json
@@ -59,9 +67,10 @@ import time
 REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
 
-HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
+HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak
 MIN_BLOCK_SECONDS = 0.05
 MIN_ROOFLINE_LAUNCHES = 300
+DUMP_BYTES = 48 << 20  # --dump-outputs: at most this many bytes of float32 arrays
 
 
 def parse(argv=None):
@@ -72,6 +81,10 @@ def parse(argv=None):
     ap.add_argument("--worlds", type=int, default=32768, help="worlds per GPU")
     ap.add_argument("--layout", default="cramped_room")
     ap.add_argument("--horizon", type=int, default=400)
+    ap.add_argument("--full", action="store_true",
+                    help="also every figure beyond the headline: repeated short blocks, roofline, probes, the other legs and "
+                         "configurations, CPU baselines, the N > 1 gather leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float32)")
     ap.add_argument("--no-gather-leg", action="store_true", help="N > 1: skip the obs all-gather leg")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="N = 1: only the headline, roofline and cpu_baseline")
@@ -365,6 +378,25 @@ def other_configs(args, torch, local_rank, launches_us):
     return out
 
 
+def dump_outputs(sim, out_dir):
+    """--dump-outputs: what the headline's last step handed its caller -- observations (world-major), rewards, dones -- as
+    float32 .npy files; beyond DUMP_BYTES, the same seeded sample of worlds of all three, in ascending order."""
+    import numpy as np
+    import torch
+    obs = sim.observation_world_major_tensor().to_torch()   # (N, P, H, W, F) int8
+    reward = sim.reward_tensor().to_torch()                 # (P, N) int32
+    done = sim.done_tensor().to_torch()                     # (N,) int32
+    n = obs.shape[0]
+    per_world = 4 * (obs[0].numel() + reward.shape[0] + 1)
+    k = min(n, DUMP_BYTES // per_world)
+    if k < n:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(n, k, replace=False))).to(obs.device)
+        obs, reward, done = obs.index_select(0, idx), reward.index_select(1, idx), done.index_select(0, idx)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (("observation", obs), ("reward", reward), ("done", done)):
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.to(torch.float32).cpu().numpy())
+
+
 def run(args):
     import torch
     import torch.distributed as dist
@@ -446,9 +478,10 @@ def run(args):
         dist.all_gather(out, t)
         return [float(o.item()) for o in out]
 
-    def timed_blocks(one_step, steps, warmup, max_blocks=41):
-        """`warmup` untimed steps, then blocks of exactly `steps` steps, each between two fences; every
-        rank runs the same number of blocks (decided from the max-over-ranks time of the first)."""
+    def timed_blocks(one_step, steps, warmup, max_blocks=41, repeat=True, after_first=None):
+        """`warmup` untimed steps, then blocks of exactly `steps` steps, each between two fences; with `repeat` every
+        rank runs the same number of blocks (decided from the max-over-ranks time of the first), else one block.
+        `after_first` runs once after the first block, outside it."""
         for i in range(warmup):
             one_step(i)
         blocks, mine = [], []
@@ -463,23 +496,31 @@ def run(args):
             dt = time.perf_counter() - t0
             mine.append(dt)
             blocks.append(max_over_ranks(dt))
-            if k == 0 and blocks[0] < MIN_BLOCK_SECONDS:
+            if k == 0 and after_first is not None:
+                after_first()
+            if k == 0 and repeat and blocks[0] < MIN_BLOCK_SECONDS:
                 count = int(min(max_blocks, max(3, MIN_BLOCK_SECONDS / max(blocks[0], 1e-6)))) | 1  # odd: a true median
             k += 1
         return blocks, mine
 
     # ---------------- headline: one launch per step, no communication ----------------
-    blocks, mine = timed_blocks(lambda i: sim.step_with_actions(pool[i % args.pool]), args.steps, args.warmup)
+    dump = (lambda: dump_outputs(sim, args.dump_outputs)) if args.dump_outputs and rank == 0 else None
+    blocks, mine = timed_blocks(lambda i: sim.step_with_actions(pool[i % args.pool]), args.steps, args.warmup,
+                                repeat=args.full, after_first=dump)
     dt = statistics.median(blocks)
-    # what a block of NO steps costs between the same fences: the share of a short block (--steps 20) that is the contract's
-    # bracket, not the steps -- reported, never subtracted
-    empty_blocks, _ = timed_blocks(lambda i: None, 0, 0, max_blocks=9)
-    empty_block_ms = statistics.median(empty_blocks) * 1e3
     per_rank_ms = all_ranks(statistics.median(mine) / args.steps * 1e3)
+    timing = {"blocks": len(blocks), "block_ms": [b * 1e3 for b in blocks],
+              "reported": "median block" if args.full else "one block of --steps steps",
+              "per_rank_ms_per_step": per_rank_ms, "rank_min_ms_per_step": min(per_rank_ms), "rank_max_ms_per_step": max(per_rank_ms)}
+    if args.full:
+        # what a block of NO steps costs between the same fences: the share of a short block (--steps 20) that is the contract's
+        # bracket, not the steps -- reported, never subtracted
+        empty_blocks, _ = timed_blocks(lambda i: None, 0, 0, max_blocks=9)
+        timing["empty_block_ms"] = statistics.median(empty_blocks) * 1e3
 
     # ---------------- N > 1: the step followed by the all-gather of the observation shards ----------------
     gather = None
-    if use_dist and not args.no_gather_leg:
+    if use_dist and args.full and not args.no_gather_leg:
         gathered = torch.empty((world_size * n,) + tuple(obs.shape[1:]), dtype=obs.dtype, device=obs.device)
         gsteps, gwarm = (min(args.steps, 3), 1) if rehearse else (args.steps, min(args.warmup, 10))
 
@@ -515,11 +556,12 @@ def run(args):
         torch.cuda.synchronize()
         return ev0.elapsed_time(ev1) * 1e3 / launches
 
-    k_launch = max(args.steps, MIN_ROOFLINE_LAUNCHES)
-    kernel_us = launches_us(lambda i: sim.step_with_actions(pool[i % args.pool]), k_launch)
+    if args.full:
+        k_launch = max(args.steps, MIN_ROOFLINE_LAUNCHES)
+        kernel_us = launches_us(lambda i: sim.step_with_actions(pool[i % args.pool]), k_launch)
 
     extras = {}
-    solo = world_size == 1 and not use_dist
+    solo = world_size == 1 and not use_dist and args.full
     single = solo and not args.no_extras
     stream = torch.cuda.current_stream().cuda_stream
     peak_measured = None
@@ -637,22 +679,6 @@ def run(args):
         del big_pool
 
     if rank == 0:
-        # HBM bytes per launch from the PMC passes committed under profiles/ (rocprofv3 cannot run inside this
-        # process): quoted only for this workload, this kernel and this build of csrc/
-        traffic = measured_traffic(sim.kernel_name, f"overcooked {args.layout} {n}")
-        bytes_per_launch = sim.bytes_per_world_step * n
-        achieved = bytes_per_launch / (kernel_us * 1e-6) / 1e9
-        roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                    "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
-                    "kernel": sim.kernel_name, "kernel_us_avg": kernel_us, "bytes_per_world_step": sim.bytes_per_world_step,
-                    "bytes_per_launch": bytes_per_launch, "launches_timed": k_launch,
-                    "note": "peak = HBM spec; the 41 MB working set is rewritten in place every step and is smaller than the "
-                            "256 MiB Infinity Cache, so the spec peak is a nominal denominator here: see peak_measured and large_batch"}
-        if peak_measured:
-            roofline["peak_measured"] = peak_measured
-            roofline["frac_of_measured_write_through"] = achieved / peak_measured["write_through_GBps"]
-        if large:
-            roofline["large_batch"] = large
         out = {
             "metric": "env-steps/sec (whole node), Overcooked 32768 worlds, random policy",
             "value": n * world_size * args.steps / dt,
@@ -669,11 +695,27 @@ def run(args):
             "config": {"workload": f"Overcooked {args.layout}, {n} worlds per GPU, horizon {args.horizon}, "
                                    f"uniform random actions (pre-sampled pool of {args.pool}, resident in HBM)",
                        "worlds_per_gpu": n, "obs_gather": False},
-            "timing": {"blocks": len(blocks), "block_ms": [b * 1e3 for b in blocks], "reported": "median block", "empty_block_ms": empty_block_ms,
-                       "per_rank_ms_per_step": per_rank_ms, "rank_min_ms_per_step": min(per_rank_ms), "rank_max_ms_per_step": max(per_rank_ms)},
-            "roofline": roofline,
+            "timing": timing,
             "build_hash": _lib.build_hash(),  # mrl_build_hash(): the sources the running library was compiled from; `traffic` is keyed by it
         }
+        if args.full:
+            # HBM bytes per launch from the PMC passes committed under profiles/ (rocprofv3 cannot run inside this
+            # process): quoted only for this workload, this kernel and this build of csrc/
+            traffic = measured_traffic(sim.kernel_name, f"overcooked {args.layout} {n}")
+            bytes_per_launch = sim.bytes_per_world_step * n
+            achieved = bytes_per_launch / (kernel_us * 1e-6) / 1e9
+            roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                        "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
+                        "kernel": sim.kernel_name, "kernel_us_avg": kernel_us, "bytes_per_world_step": sim.bytes_per_world_step,
+                        "bytes_per_launch": bytes_per_launch, "launches_timed": k_launch,
+                        "note": "peak = HBM spec; the 41 MB working set is rewritten in place every step and is smaller than the "
+                                "256 MiB Infinity Cache, so the spec peak is a nominal denominator here: see peak_measured and large_batch"}
+            if peak_measured:
+                roofline["peak_measured"] = peak_measured
+                roofline["frac_of_measured_write_through"] = achieved / peak_measured["write_through_GBps"]
+            if large:
+                roofline["large_batch"] = large
+            out["roofline"] = roofline
         if use_dist:
             out["ranks"] = {"world_size": dist.get_world_size(), "backend": backend,
                             "rehearsal_on_one_gpu": bool(rehearse)}

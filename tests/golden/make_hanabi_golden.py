@@ -96,12 +96,17 @@ def main():
             for k in ("obs", "state", "mask", "active", "reward", "done"):
                 rec[k].append(getattr(orc, k).copy())
         out = os.path.join(HERE, f"hanabi_{name}.npz")
-        np.savez_compressed(out, actions=np.stack(rec["actions"]), obs=np.stack(rec["obs"]),
-                            state=np.stack(rec["state"]), mask=np.stack(rec["mask"]).astype(np.int8),
+        # the 0/1 observation and state rows go in bit-packed (tests/conftest.py:load_golden unpacks them): the full
+        # configuration's fixture stays well under 1 MiB
+        bits = {"obs": np.stack(rec["obs"]), "state": np.stack(rec["state"]), "first_obs": first["obs"],
+                "first_state": first["state"]}
+        packed = {}
+        for k, v in bits.items():
+            packed[k + "_bits"], packed[k + "_len"] = np.packbits(v, axis=-1), np.int64(v.shape[-1])
+        np.savez_compressed(out, actions=np.stack(rec["actions"]), mask=np.stack(rec["mask"]).astype(np.int8),
                             active=np.stack(rec["active"]).astype(np.int8), reward=np.stack(rec["reward"]),
-                            done=np.stack(rec["done"]).astype(np.int8), first_obs=first["obs"],
-                            first_state=first["state"], first_mask=first["mask"].astype(np.int8),
-                            first_active=first["active"].astype(np.int8))
+                            done=np.stack(rec["done"]).astype(np.int8), first_mask=first["mask"].astype(np.int8),
+                            first_active=first["active"].astype(np.int8), **packed)
         print(f"{name}: {checked} world-steps accepted by the reference checker "
               f"({rejected_overflow} rejected only with information tokens above the maximum, "
               f"{rejected_short} only with a short hand), "

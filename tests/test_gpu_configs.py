@@ -157,12 +157,12 @@ def test_two_rank_gather_equals_one_simulator(total, hip_lib, tmp_path):
 
 
 def test_bench_starts_its_own_ranks(hip_lib):
-    """`python bench.py --gpus 2 ...` without a launcher: rc 0 and ONE JSON line from rank 0 with the
+    """`python bench.py --gpus 2 --full ...` without a launcher: rc 0 and ONE JSON line from rank 0 with the
     no-communication `value` and the obs_gather leg (one-GPU rehearsal: both ranks on this card, gloo)."""
     env = dict(os.environ, MRL_BENCH_REHEARSE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    proc = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5"],
+    proc = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--full"],
                           env=env, capture_output=True, text=True, timeout=600)
     assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-4000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.strip()]
@@ -178,7 +178,7 @@ def test_bench_starts_its_own_ranks(hip_lib):
 
 
 def test_bench_line_carries_every_single_gpu_config(hip_lib):
-    """`python bench.py` (N = 1): besides the headline, `other_configs` holds the other BASELINE.json configurations one
+    """`python bench.py --full` (N = 1): besides the headline, `other_configs` holds the other BASELINE.json configurations one
     GPU can run -- each with kernel, launch duration over >= 300 launches, bytes per world-step and roofline fraction --
     and every `traffic` is either null or comes from PMC passes taken on exactly this build of csrc/."""
     from madrona_rl_envs_playground_amd import _lib
@@ -186,7 +186,7 @@ def test_bench_line_carries_every_single_gpu_config(hip_lib):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "MRL_BENCH_REHEARSE", "MRL_BENCH_FORCE_DIST"):
         env.pop(k, None)
     proc = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "20", "--warmup", "5", "--cpu-seconds", "2",
-                           "--large-worlds", "0", "--fused-steps", "100"], env=env, capture_output=True, text=True, timeout=600)
+                           "--large-worlds", "0", "--fused-steps", "100", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-4000:]
     out = json.loads([ln for ln in proc.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["n_gpus"] == 1 and out["steps"] == 20 and out["roofline"]["bound"] == "hbm" and out["cpu_baseline"]["kind"] == "port"
@@ -221,6 +221,39 @@ def test_bench_line_carries_every_single_gpu_config(hip_lib):
         assert all(t is None for t in quoted)
     else:
         assert out["roofline"]["traffic"] is not None and 0.9 < out["roofline"]["traffic"] / out["roofline"]["bytes_per_launch"] < 1.3
+
+
+def test_plain_bench_times_exactly_its_steps_and_dumps_the_same_outputs(hip_lib, tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR` without --full: one block of exactly K steps, the headline
+    keys and nothing measured beside them; the dumped float32 arrays (observations of a fixed sample of worlds, rewards,
+    dones) fit 64 MB and are the same on a second run with the same arguments."""
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "MRL_BENCH_REHEARSE", "MRL_BENCH_FORCE_DIST"):
+        env.pop(k, None)
+    dumps = []
+    for run in ("a", "b"):
+        out_dir = tmp_path / run
+        proc = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "7",
+                               "--dump-outputs", str(out_dir)], env=env, capture_output=True, text=True, timeout=600)
+        assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-4000:]
+        lines = [ln for ln in proc.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1 and lines[0].startswith("{"), proc.stdout
+        out = json.loads(lines[0])
+        assert out["steps"] == 30 and out["warmup"] == 7 and out["timing"]["blocks"] == 1
+        assert out["unit"] == "env-steps/s" and out["higher_is_better"] is True and out["dtype"] == "u8"
+        assert abs(out["value"] - 32768 / (out["ms_per_step"] * 1e-3)) < 1e-6 * out["value"]
+        assert abs(out["ms_per_step"] * 30 - out["timing"]["block_ms"][0]) < 1e-9 * out["timing"]["block_ms"][0] + 1e-12
+        assert not {"roofline", "cpu_baseline", "other_configs", "graph_replay"} & set(out)
+        arrays = {name: np.load(out_dir / f"{name}.npy") for name in ("observation", "reward", "done")}
+        assert sorted(os.listdir(out_dir)) == ["done.npy", "observation.npy", "reward.npy"]
+        assert all(a.dtype == np.float32 for a in arrays.values()) and sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        k = arrays["observation"].shape[0]
+        assert 0 < k <= 32768 and arrays["observation"].shape[1:] == (2, 4, 5, 26)
+        assert arrays["reward"].shape == (2, k) and arrays["done"].shape == (k,)
+        assert arrays["observation"].any() and set(np.unique(arrays["done"])) <= {0.0, 1.0}
+        dumps.append(arrays)
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
 
 
 @pytest.mark.parametrize("layout,in_place", [("cramped_room", True), ("counter_circuit", True), ("cramped_room", False)],

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN
+from conftest import GOLDEN, load_golden
 
 pytestmark = pytest.mark.gpu
 
@@ -93,7 +93,7 @@ def test_overcooked_ego_step_with_random_partner(hip_lib):
 @pytest.mark.parametrize("name", ["full", "small", "very_small"])
 def test_hanabi_checked_fixture_on_gpu(name, hip_lib):
     """The sequences accepted by the reference's checker (make_hanabi_golden.py)."""
-    z = np.load(os.path.join(GOLDEN, f"hanabi_{name}.npz"))
+    z = load_golden(f"hanabi_{name}.npz")
     cfg = dict(FULL_CONFIG) if name == "full" else (
         dict(colors=2, ranks=5, players=2, max_information_tokens=3, max_life_tokens=1) if name == "small"
         else dict(colors=1, ranks=5, players=2, max_information_tokens=3, max_life_tokens=1))

@@ -30,12 +30,12 @@ def _free_port():
 
 
 def test_bench_rank_protocol_over_nccl_at_world_size_one(hip_lib):
-    """`MRL_BENCH_FORCE_DIST=1 python bench.py --gpus 1`: one rank under torch.distributed.run, backend nccl; the
+    """`MRL_BENCH_FORCE_DIST=1 python bench.py --gpus 1 --full`: one rank under torch.distributed.run, backend nccl; the
     line carries `ranks.backend == "nccl"` and the obs_gather leg (all_gather_into_tensor on device memory)."""
     env = dict(os.environ, MRL_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "MRL_BENCH_REHEARSE"):
         env.pop(k, None)
-    proc = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "50", "--warmup", "5"],
+    proc = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "50", "--warmup", "5", "--full"],
                           env=env, capture_output=True, text=True, timeout=600)
     assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-4000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.strip()]

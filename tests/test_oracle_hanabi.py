@@ -5,12 +5,10 @@ on the full configuration) and the accepted sequences are committed as fixtures.
 Here: the oracle reproduces those fixtures, and the invariants are re-checked
 independently of the reference's code.  Card-knowledge / last-action sections,
 RNG draws and episode->seed mapping stay PARITY UNPINNED."""
-import os
-
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
+from conftest import load_golden
 from madrona_rl_envs_playground_amd import hanabi_spec
 
 CONFIGS = {
@@ -29,7 +27,7 @@ def test_sizes():
 
 @pytest.mark.parametrize("name", list(CONFIGS))
 def test_oracle_reproduces_checked_fixture(name, oracle_lib):
-    z = np.load(os.path.join(GOLDEN, f"hanabi_{name}.npz"))
+    z = load_golden(f"hanabi_{name}.npz")
     cfg = CONFIGS[name]
     n = z["actions"].shape[2]
     orc = oracle_lib.HanabiOracle(cfg, n)

@@ -16,11 +16,11 @@ if [[ $part == *a* ]]; then
 timeout -k 10 600 python3 tools/pmc_traffic.py $out/${tag}_traffic > $out/${tag}_traffic.log 2>&1
 cp $out/${tag}_traffic/step_traffic.json profiles/step_traffic.json
 echo "pmc traffic done"
-( time python bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err ) 2> $out/${tag}_bench_time.txt
+( time python bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err ) 2> $out/${tag}_bench_time.txt
 ( time python bench.py --gpus 1 --steps 20 --warmup 5 > $out/${tag}_bench_steps20.json 2>> $out/${tag}_bench.err ) 2>> $out/${tag}_bench_time.txt
 echo "bench done"; head -c 400 $out/${tag}_bench.json; echo; grep real $out/${tag}_bench_time.txt
-MRL_BENCH_FORCE_DIST=1 python bench.py --gpus 1 --steps 500 --warmup 20 > $out/${tag}_bench_nccl_world_size_1.json 2>> $out/${tag}_bench.err
-MRL_BENCH_REHEARSE=1 python bench.py --gpus 2 --steps 200 --warmup 20 > $out/${tag}_bench_rehearse2_one_gpu.json 2>> $out/${tag}_bench.err
+MRL_BENCH_FORCE_DIST=1 python bench.py --gpus 1 --steps 500 --warmup 20 --full > $out/${tag}_bench_nccl_world_size_1.json 2>> $out/${tag}_bench.err
+MRL_BENCH_REHEARSE=1 python bench.py --gpus 2 --steps 200 --warmup 20 --full > $out/${tag}_bench_rehearse2_one_gpu.json 2>> $out/${tag}_bench.err
 echo "rank protocol legs done"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_kt -o kt -- python3 $root/bench.py --steps 2000 --warmup 50 --no-extras --no-cpu-baseline > $out/${tag}_kt.log 2>&1
