@@ -295,7 +295,9 @@ __device__ void encode_agent(const HanabiParams &p, uint8_t *rec, uint32_t *enc,
         if (card && (uint32_t)rec[R_LM_INDEX] < kHand) v2 |= 1u << (kHand + rec[R_LM_INDEX]);
         put(enc, off_last + at, 2 * kHand, v2);
         if (card) {
-            const uint32_t id = (uint32_t)rec[R_LM_COLOR] * R + rec[R_LM_RANK];
+            // sim.cpp:262-263 in uint32 arithmetic of the signed bytes: after a colour hint c that follows a card
+            // move the rank is -1 and the bit c * R - 1 is set (a hint leaves the move type alone, see apply_action)
+            const uint32_t id = (uint32_t)((int32_t)(int8_t)rec[R_LM_COLOR] * (int32_t)R + (int32_t)(int8_t)rec[R_LM_RANK]);
             if (id < bpc) put(enc, off_last + at + 2 * kHand + id, 1, 1);
         }
         if (move == MV_PLAY)
@@ -482,7 +484,7 @@ __device__ __forceinline__ void encode_record_full_t(const uint32_t (&r)[kRecord
         uint32_t v2 = hint ? byte_at(r, R_LM_REVEAL) & 31u : 0u;
         v2 |= (card && lm_index < kHand) ? 1u << (kHand + lm_index) : 0u;
         orbits(hi, kRelLast + 18, 10, v2);
-        const uint32_t id = lm_color * kRk + lm_rank;
+        const uint32_t id = (uint32_t)((int32_t)(int8_t)lm_color * (int32_t)kRk + (int32_t)(int8_t)lm_rank);  // signed, as above
         orbits(hi, kRelLast + 28, 25, (card && id < kBpc) ? 1u << id : 0u);
         orbits(hi, kRelLast + 53, 2,
                move == MV_PLAY ? (byte_at(r, R_LM_SCORED) ? 1u : 0u) | (byte_at(r, R_LM_INFOTOK) ? 2u : 0u) : 0u);
@@ -674,6 +676,8 @@ __device__ void apply_action(const HanabiParams &p, uint8_t *rec, uint32_t uid)
         return;
     }
     uid -= 2 * kHand;
+    // A hint leaves R_LM_MOVE as it was: sim.cpp:696-792 never set lastmove.move, so the last-action section
+    // goes on encoding the world's last card move (MV_INVALID after a reset), gated by that move type (:158-290).
     uint8_t *ph = rec + R_HAND + HAND_BYTES * (actor ^ 1u);  // one partner: target_offset is always 1
     uint32_t *plaus = plaus_of(ph);
     const uint32_t psize = min((uint32_t)ph[H_SIZE], (uint32_t)kHand);
@@ -682,7 +686,6 @@ __device__ void apply_action(const HanabiParams &p, uint8_t *rec, uint32_t uid)
     uint32_t reveal = 0, newly = 0, hint = 0;
     if (uid < K) {
         const uint32_t col = uid;
-        rec[R_LM_MOVE] = MV_REVEAL_COLOR;
         rec[R_LM_COLOR] = (uint8_t)col;
         for (uint32_t i = 0; i < R; i++) hint |= 1u << (col * R + i);
         for (uint32_t i = 0; i < psize; i++) {
@@ -697,7 +700,6 @@ __device__ void apply_action(const HanabiParams &p, uint8_t *rec, uint32_t uid)
         }
     } else {
         const uint32_t rk = (uid - K) % R;
-        rec[R_LM_MOVE] = MV_REVEAL_RANK;
         rec[R_LM_RANK] = (uint8_t)rk;
         for (uint32_t i = 0; i < R; i++) hint |= 1u << (i * R + rk);
         for (uint32_t i = 0; i < psize; i++) {
@@ -826,7 +828,7 @@ __device__ void apply_action_full(uint8_t *rec, uint32_t uid)
     info -= hint_move ? 1u : 0u;
 
     // ---- write back ----
-    const uint32_t lm_move = is_card ? (play ? (uint32_t)MV_PLAY : (uint32_t)MV_DISCARD) : (by_color ? (uint32_t)MV_REVEAL_COLOR : (uint32_t)MV_REVEAL_RANK);
+    const uint32_t lm_move = is_card ? (play ? (uint32_t)MV_PLAY : (uint32_t)MV_DISCARD) : w21 >> 24;  // a hint keeps the move type (sim.cpp:696-792)
     const uint32_t lm_color = is_card ? col : (by_color ? val : 0xFFu);
     const uint32_t lm_rank = is_card ? rk : (by_color ? 0xFFu : val);
     rec32[19] = (uint32_t)fw_new;
@@ -1068,7 +1070,7 @@ __device__ __forceinline__ MovedFull move_world_full(const HanabiParams &p, uint
     m.next = actor ^ 1u;
 
     // ---- the record's words after the move ----
-    const uint32_t lm_move = is_card ? (play ? (uint32_t)MV_PLAY : (uint32_t)MV_DISCARD) : (by_color ? (uint32_t)MV_REVEAL_COLOR : (uint32_t)MV_REVEAL_RANK);
+    const uint32_t lm_move = is_card ? (play ? (uint32_t)MV_PLAY : (uint32_t)MV_DISCARD) : w21 >> 24;  // a hint keeps the move type (sim.cpp:696-792)
     const uint32_t lm_color = is_card ? col : (by_color ? val : 0xFFu);
     const uint32_t lm_rank = is_card ? rk : (by_color ? 0xFFu : val);
     const uint32_t deck_less = deck_size - 1u;

@@ -15,13 +15,14 @@
  *   - hint legality scans all five hand slots whatever the hand size, so the
  *     duplicate a left-shift leaves in the last slot counts (sim.cpp:416-417),
  *   - the rank hint's "newly revealed" test looks at known_color (sim.cpp:776),
- *   - no legality check on the action (sim.cpp:604).
+ *   - no legality check on the action (sim.cpp:604),
+ *   - a hint does not set lastmove.move (sim.cpp:696-792): the last-action section after a hint encodes
+ *     the move type of the world's last card move (none after a reset), not the hint.
  *
- * PARITY UNPINNED for: card-knowledge section, last-action section, the RNG
- * draw sequence and the episode->seed mapping -- the reference holds no second
- * implementation, golden vector or test for them (its checker skips them,
- * envs/hanabi_env.py:296,640-641).  Everything else is pinned by the invariants
- * that checker tests, restated in tests/test_oracle_hanabi.py.
+ * Pinned bit for bit, every section of both agents' rows, against the reference's
+ * own sim.cpp compiled unchanged against a Madrona stand-in (oracle/_ref,
+ * tests/test_ref_hanabi.py) and against fixtures recorded from it
+ * (tests/golden/hanabi_ref_*.npz).
  *
  * Episode order: as in cartpole_oracle.c (ascending world index).
  */
@@ -376,8 +377,11 @@ static void apply_action(orc_hanabi *s, uint32_t wi, const int32_t *actions)
         return;
     }
     uid -= hs;
+    /* Hints leave lm->move as it was: sim.cpp:696-792 set target, colour / rank and the masks but never
+     * lastmove.move, and encodeLastAction (:158-290) gates every sub-section on it.  After a hint the
+     * encoding is that of the last card move of the world (or of none, kInvalid, after a reset), with
+     * card index -1 and, for a colour hint c > 0 after a card move, the card bit c * ranks - 1 (rank -1). */
     if (uid < (np - 1) * colors) { /* reveal colour */
-        lm->move = MV_REVEAL_COLOR;
         int target_offset = 1 + (int)(uid / colors);
         g->information_tokens--;
         int partner = (actor + target_offset) % (int)np;
@@ -403,7 +407,6 @@ static void apply_action(orc_hanabi *s, uint32_t wi, const int32_t *actions)
     }
     uid -= (np - 1) * colors;
     { /* reveal rank */
-        lm->move = MV_REVEAL_RANK;
         int target_offset = 1 + (int)(uid / ranks);
         g->information_tokens--;
         int partner = (actor + target_offset) % (int)np;
@@ -449,11 +452,17 @@ static int score_and_check(orc_hanabi *s, uint32_t wi)
 
 orc_hanabi *orc_hanabi_create(const orc_hanabi_config *cfg, uint32_t num_worlds)
 {
+    return orc_hanabi_create_at(cfg, num_worlds, 0);
+}
+
+orc_hanabi *orc_hanabi_create_at(const orc_hanabi_config *cfg, uint32_t num_worlds, uint32_t first_episode)
+{
     if (!cfg || cfg->players != NPLAYERS || cfg->colors < 1 || cfg->colors > 5 || cfg->ranks < 2 || cfg->ranks > 5 ||
         cfg->max_information_tokens > 8 || cfg->max_life_tokens > 3)
         return NULL;
     orc_hanabi *s = (orc_hanabi *)calloc(1, sizeof(*s));
     s->n = num_worlds;
+    s->next_episode = first_episode;
     s->colors = cfg->colors;
     s->ranks = cfg->ranks;
     s->players = cfg->players;

@@ -16,13 +16,13 @@
  * Pinning (see DESIGN.md "Oracle"):
  *   Overcooked: pinned against the reference's own numpy implementation
  *               (envs/overcooked_reimplement.py) through tests/golden/overcooked_*.npz.
- *   Cartpole  : dynamics pinned against the float64 one-step check the reference
- *               uses (envs/cartpole_env.py:177-233, tolerance 1e-6) restated in
- *               tests; reset/RNG stream pinned by hand-computed known answers.
- *   Hanabi    : the reference holds no second implementation or golden vector
- *               in-tree -> card-knowledge / last-action / RNG sections are
- *               "parity unpinned"; the rest is pinned by the invariants the
- *               reference checker tests (envs/hanabi_env.py:478-657), restated in tests.
+ *   Cartpole, Hanabi, balance beam: bit-exact against the reference's own
+ *               sim.cpp compiled unchanged against a Madrona stand-in
+ *               (oracle/Makefile.ref -> oracle/_ref, tests/test_ref_*.py) and
+ *               against fixtures recorded from it (tests/golden/make_ref_golden.py);
+ *               Cartpole also within 1e-6 of the reference's float64 one-step check
+ *               (envs/cartpole_env.py:177-233), Hanabi also accepted by the
+ *               reference checker (envs/hanabi_env.py:478-657).
  */
 #ifndef MRL_ORACLE_H
 #define MRL_ORACLE_H
@@ -148,6 +148,8 @@ typedef struct orc_hanabi_config {
 typedef struct orc_hanabi orc_hanabi;
 
 orc_hanabi *orc_hanabi_create(const orc_hanabi_config *cfg, uint32_t num_worlds);
+/* as orc_hanabi_create, the first world starting episode first_episode (the counter wraps at 2^32) */
+orc_hanabi *orc_hanabi_create_at(const orc_hanabi_config *cfg, uint32_t num_worlds, uint32_t first_episode);
 void orc_hanabi_destroy(orc_hanabi *s);
 /* actions: (2, N) int32 */
 void orc_hanabi_step(orc_hanabi *s, const int32_t *actions, int num_threads);

@@ -103,6 +103,8 @@ def lib():
 
         L.orc_hanabi_create.restype = vp
         L.orc_hanabi_create.argtypes = [ctypes.POINTER(HanabiConfig), u32]
+        L.orc_hanabi_create_at.restype = vp
+        L.orc_hanabi_create_at.argtypes = [ctypes.POINTER(HanabiConfig), u32, u32]
         L.orc_hanabi_destroy.argtypes = [vp]
         L.orc_hanabi_step.argtypes = [vp, i32p, ctypes.c_int]
         for name, rt in (("obs", ctypes.POINTER(ctypes.c_uint8)), ("state", ctypes.POINTER(ctypes.c_uint8)),
@@ -302,13 +304,13 @@ class CartpoleOracle:
 
 
 class HanabiOracle:
-    def __init__(self, config, num_worlds, num_threads=1):
+    def __init__(self, config, num_worlds, num_threads=1, first_episode=0):
         self.L = lib()
         self.N = int(num_worlds)
         self.num_threads = num_threads
         cfg = HanabiConfig(int(config["colors"]), int(config["ranks"]), int(config["players"]),
                            int(config["max_information_tokens"]), int(config["max_life_tokens"]))
-        self.h = self.L.orc_hanabi_create(ctypes.byref(cfg), self.N)
+        self.h = self.L.orc_hanabi_create_at(ctypes.byref(cfg), self.N, int(first_episode) & 0xFFFFFFFF)
         if not self.h:
             raise ValueError("oracle rejected the Hanabi config")
         N = self.N

@@ -10,8 +10,8 @@ What the reference checker pins: one active agent that alternates, state prefix
 card conservation, legal-move mask, one-step token/firework/discard/reward/done
 simulation, pristine start state after done.  It does NOT look at the
 card-knowledge and last-action sections, the RNG draws or the episode->seed map
-(envs/hanabi_env.py:296,640-641): for those the fixtures are this repo's oracle
-output, i.e. PARITY UNPINNED by the reference.
+(envs/hanabi_env.py:296,640-641): those are pinned by the compiled reference
+instead (tests/test_ref_hanabi.py, tests/golden/make_ref_golden.py).
 
 Two cases the checker rejects by construction; such steps are counted and
 reported, not treated as oracle errors:

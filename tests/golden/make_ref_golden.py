@@ -1,0 +1,93 @@
+"""Writes tests/golden/hanabi_ref_{full,small,very_small}.npz and cartpole_ref.npz: action streams and what the reference's
+OWN sim.cpp computed for them, compiled unchanged against the Madrona stand-in (oracle/_ref, built by build() when the
+reference tree is present; oracle/ref.py).  Data only, packed the way tests/conftest.py:load_golden reads them, so that the
+oracle and the GPU stay pinned to the compiled reference where oracle/_ref is not built.
+
+Hanabi: moves drawn from the reference's own mask, a third of the worlds preferring hints (hints as first moves and after
+card moves), a third discarding when it may (the deck runs out), a third uniformly random.  Rows are stored up to the
+configuration's observation / state length (what the reference writes).  Cartpole: random pushes, state as float32.
+
+    python tests/golden/make_ref_golden.py
+"""
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+REPO = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, REPO)
+
+from madrona_rl_envs_playground_amd import hanabi_spec  # noqa: E402
+from oracle import ref  # noqa: E402
+
+CONFIGS = {
+    "full": (dict(colors=5, ranks=5, players=2, max_information_tokens=8, max_life_tokens=3), 48, 200),
+    "small": (dict(colors=2, ranks=5, players=2, max_information_tokens=3, max_life_tokens=1), 48, 150),
+    "very_small": (dict(colors=1, ranks=5, players=2, max_information_tokens=3, max_life_tokens=1), 32, 60),
+}
+
+
+def hanabi_moves(rng, mask, active):
+    n = mask.shape[1]
+    w = np.arange(n)
+    mover = (active[1] != 0).astype(np.int64)
+    legal = mask[mover, w] != 0
+    uid = np.arange(legal.shape[1])
+    pick = lambda allowed: np.where(allowed.any(-1), (rng.random(allowed.shape) * allowed).argmax(-1), -1)
+    a_any, a_hint, a_disc = pick(legal), pick(legal & (uid >= 10)), pick(legal & (uid < 5))
+    pol = w % 3
+    act = np.where((pol == 0) & (a_hint >= 0), a_hint, a_any)
+    act = np.where((pol == 1) & (a_disc >= 0), a_disc, act)
+    acts = np.zeros((2, n), np.int32)
+    acts[mover, w] = act
+    return acts
+
+
+def packed(name, v):
+    return {name + "_bits": np.packbits(v, axis=-1), name + "_len": np.int64(v.shape[-1])}
+
+
+def main():
+    for name, (cfg, n, steps) in CONFIGS.items():
+        no, ns = hanabi_spec.observation_size(cfg), hanabi_spec.state_size(cfg)
+        r = ref.RefHanabi(cfg, n)
+        rng = np.random.default_rng(2026)
+        first = dict(obs=r.obs[..., :no].copy(), state=r.state[..., :ns].copy(), mask=r.mask.copy(), active=r.active.copy())
+        rec = {k: [] for k in ("actions", "obs", "state", "mask", "active", "reward", "done")}
+        for _ in range(steps):
+            a = hanabi_moves(rng, r.mask, r.active)
+            r.step(a)
+            rec["actions"].append(a.astype(np.int8))
+            rec["obs"].append(r.obs[..., :no].copy())
+            rec["state"].append(r.state[..., :ns].copy())
+            for k in ("mask", "active", "reward", "done"):
+                rec[k].append(getattr(r, k).copy())
+        out = os.path.join(HERE, f"hanabi_ref_{name}.npz")
+        np.savez_compressed(out, actions=np.stack(rec["actions"]), mask=np.stack(rec["mask"]).astype(np.int8),
+                            active=np.stack(rec["active"]).astype(np.int8), reward=np.stack(rec["reward"]),
+                            done=np.stack(rec["done"]).astype(np.int8), first_mask=first["mask"].astype(np.int8),
+                            first_active=first["active"].astype(np.int8), episodes=np.int64(r.episodes),
+                            **packed("obs", np.stack(rec["obs"])), **packed("state", np.stack(rec["state"])),
+                            **packed("first_obs", first["obs"]), **packed("first_state", first["state"]))
+        print(f"{out}: {n} worlds x {steps} steps, {r.episodes} episodes, {os.path.getsize(out) / 1024:.0f} KiB")
+
+    n, steps = 64, 300
+    r = ref.RefCartpole(n)
+    rng = np.random.default_rng(2026)
+    first = r.state.copy()
+    acts, states, dones = [], [], []
+    for _ in range(steps):
+        a = rng.integers(0, 2, n).astype(np.int32)
+        r.step(a)
+        acts.append(a.astype(np.int8))
+        states.append(r.state.copy())
+        dones.append(r.done[:, 0].astype(np.int8))
+    out = os.path.join(HERE, "cartpole_ref.npz")
+    np.savez_compressed(out, first_state=first, actions=np.stack(acts), state=np.stack(states), done=np.stack(dones),
+                        episodes=np.int64(r.episodes))
+    print(f"{out}: {n} worlds x {steps} steps, {r.episodes} episodes, {os.path.getsize(out) / 1024:.0f} KiB")
+
+
+if __name__ == "__main__":
+    main()

@@ -58,6 +58,7 @@ class Game:
         self.info, self.life = MAX_INFO, MAX_LIFE
         self.mover, self.turns_to_play, self.score = 0, 2, 0
         self.last = dict(move=NONE, player=-1, target=-1, index=-1, colour=-1, rank=-1, reveal=0, scored=False, info_token=False)
+        self.made = NONE  # the kind of the last move made (what `last["move"]` is not after a hint)
 
     def draw(self):
         """drawDeck (sim.cpp:45-52): rand() = low 24 bits of an LCG step / 2^24 as float32 (rng.hpp:28-36); position =
@@ -75,7 +76,12 @@ class Game:
         if not self.deck:
             self.turns_to_play -= 1
         who = self.mover
-        self.last = dict(move=move, player=who, target=-1, index=-1, colour=-1, rank=-1, reveal=0, scored=False, info_token=False)
+        # sim.cpp:621-630 reset every lastmove field but the move type; only the discard and play branches set that
+        # (:642, :666), the hint branches (:696-792) never do: after a hint the last-action section (:158-289) still
+        # encodes the world's last card move (kInvalid, :492, before the first one), with card index and rank -1
+        kept = move if move in (PLAY, DISCARD) else self.last["move"]
+        self.last = dict(move=kept, player=who, target=-1, index=-1, colour=-1, rank=-1, reveal=0, scored=False, info_token=False)
+        self.made = move
         self.mover = (who + 1) % 2
         return who, self.hands[who]
 
@@ -183,6 +189,7 @@ class Game:
         v += [int(lm["move"] == REVEAL_RANK and i == lm["rank"]) for i in range(R)]
         v += [int(hint and (lm["reveal"] >> i) & 1) for i in range(HAND)]
         v += [int(card_move and i == lm["index"]) for i in range(HAND)]
+        # (:267 compares in uint32; as Python ints the same: a colour hint c after a card move has rank -1 -> entry c*R - 1)
         v += [int(card_move and i == lm["colour"] * R + lm["rank"]) for i in range(K * R)]
         v += [int(lm["move"] == PLAY and lm["scored"]), int(lm["move"] == PLAY and lm["info_token"])]
         # encodeCardKnowledge (:291-331): my own cards, then the partner's.  Every one of the 25 plausibility entries of a
@@ -225,7 +232,7 @@ def snapshot(g, uid, actor):
     """What the reference leaves visible after a move: the NEXT mover's fresh observation, state tail and legal moves."""
     me = g.mover
     return dict(uid=uid, actor=actor, mover=me, obs=g.observation(me)[:658], own=g.own_hand(me), state=g.state(me), legal=g.legal(me),
-                info=g.info, life=g.life, deck=len(g.deck), scored=g.last["scored"], info_token=g.last["info_token"], move=g.last["move"])
+                info=g.info, life=g.life, deck=len(g.deck), scored=g.last["scored"], info_token=g.last["info_token"], move=g.made)
 
 
 def script_card_moves(episode):

@@ -368,3 +368,82 @@ def test_current_device_is_restored(hip_lib):
     sim.step()
     assert torch.cuda.current_device() == before
     sim.close()
+
+
+def _glibc_sincos():
+    import ctypes
+    libm = ctypes.CDLL("libm.so.6")
+    for f in (libm.sinf, libm.cosf):
+        f.restype, f.argtypes = ctypes.c_float, [ctypes.c_float]
+    return libm.sinf, libm.cosf
+
+
+@pytest.mark.parametrize("n,steps", [(1024, 300), (300001, 30), (1 << 20, 15)], ids=["1024", "300001", "1M"])
+@pytest.mark.parametrize("variant", [1, 0], ids=["reference_typed", "default"])
+def test_step_vs_compiled_reference(variant, n, steps, hip_lib):
+    """One launch and two launches against the reference's own sim.cpp compiled unchanged against the Madrona stand-in
+    (oracle/_ref: g++ -ffp-contract=off, glibc sinf / cosf), one step at a time from a common state (re-synchronised from
+    the reference after every step, as test_lockstep_vs_oracle does from the oracle).
+
+    Measured on the MI355X (300001 worlds x 30 steps): with the reference's typing (cartpole.variant=1) 0.80 % of the
+    world-steps differ, and every one of them starts from a theta at which the device's sinf / cosf (ocml) and glibc's
+    differ -- 2.8 % of the visited thetas; the default arithmetic differs in 8.55 % of the world-steps.  Every difference
+    stayed within 2.4e-7."""
+    from madrona_rl_envs_playground_amd._lib import debug_knobs
+    from oracle import ref
+    ref.require()
+    sims = []
+    for fused in (1, 2):
+        with debug_knobs({"fused_step": fused, "cartpole.variant": variant}):
+            sims.append(make(n))
+    assert [s.kernel_name for s in sims] == ["mrl_cartpole_step_fused", "mrl_cartpole_step"]
+    r = ref.RefCartpole(n)
+    for s in sims:
+        assert np.array_equal(s.observation_tensor().to_torch().cpu().numpy().view(np.uint32), r.state.view(np.uint32))
+    sinf, cosf = _glibc_sincos()
+    rng = np.random.default_rng(n + variant)
+    compared = differing = resets = 0
+    for t in range(steps):
+        a = rng.integers(0, 2, n).astype(np.int32)
+        theta = r.state[:, 2].copy()
+        r.step(a)
+        ref_state, ref_done = r.state, r.done[:, 0]
+        for s in sims:
+            st = s.observation_tensor().to_torch()
+            s.action_tensor().to_torch().copy_(torch.from_numpy(a).cuda().view(n, 1))
+            s.step()
+            got = st.cpu().numpy()
+            done = s.reset_tensor().to_torch().cpu().numpy()[:, 0]
+            assert np.array_equal(done, ref_done), f"done flags, step {t}"  # none flipped in the measurement
+            if ref_done.any():
+                rs = ref_done == 1
+                resets += int(rs.sum())
+                assert np.array_equal(got[rs].view(np.uint32), ref_state[rs].view(np.uint32)), f"reset state, step {t}"
+                assert int(s.reset_count_tensor().to_torch().item()) == int(rs.sum())
+            live = ref_done == 0
+            diff = live & (got.view(np.uint32) != ref_state.view(np.uint32)).any(1)
+            compared += int(live.sum())
+            differing += int(diff.sum())
+            # the reference's own one-step bound, 1e-6 (envs/cartpole_env.py:277); in ulps: at most 4 at the scale of the
+            # state's magnitude (max(|value|, 1): the largest difference seen is 2 ulps of 1.0)
+            scale = np.spacing(np.maximum(np.abs(ref_state[live]), np.float32(1)))
+            assert (np.abs(got[live] - ref_state[live]) <= 4 * scale).all(), f"more than 4 ulps, step {t}"
+            if variant == 1 and diff.any():
+                # typed as the reference writes it, the device rounds every operation as the CPU does: a difference can
+                # only come from the math library.  sin / cos of the pre-step theta on the device (ocml, as the kernel's
+                # sinf / cosf) against glibc's, world by world
+                w = np.flatnonzero(diff)
+                th = torch.from_numpy(theta[w]).cuda()
+                dev_s, dev_c = torch.sin(th).cpu().numpy(), torch.cos(th).cpu().numpy()
+                host_s = np.array([sinf(float(x)) for x in theta[w]], np.float32)
+                host_c = np.array([cosf(float(x)) for x in theta[w]], np.float32)
+                unexplained = (dev_s == host_s) & (dev_c == host_c)
+                assert not unexplained.any(), f"step {t}: worlds {w[unexplained][:8].tolist()} differ with sinf and cosf equal"
+            st.copy_(torch.from_numpy(ref_state).cuda())
+    frac = differing / compared
+    print(f"cartpole variant {variant}, {n} worlds: {differing} of {compared} world-steps differ ({frac:.3%}), {resets} resets")
+    # ceilings above the measured 0.80 % / 8.55 %; ADVICE's "about 9 %" for the default arithmetic
+    assert frac <= (0.015 if variant == 1 else 0.10), frac
+    assert resets > 0
+    for s in sims:
+        s.close()

@@ -91,8 +91,9 @@ def test_overcooked_ego_step_with_random_partner(hip_lib):
 
 
 @pytest.mark.parametrize("name", ["full", "small", "very_small"])
-def test_hanabi_checked_fixture_on_gpu(name, hip_lib):
-    """The sequences accepted by the reference's checker (make_hanabi_golden.py)."""
+def test_hanabi_checked_fixture_on_gpu_hints_keep_last_move(name, hip_lib):
+    """The sequences accepted by the reference's checker (make_hanabi_golden.py), recorded with hints that leave the last
+    card move's type in the last-action section, as the reference's actionSystem does (sim.cpp:642,666)."""
     z = load_golden(f"hanabi_{name}.npz")
     cfg = dict(FULL_CONFIG) if name == "full" else (
         dict(colors=2, ranks=5, players=2, max_information_tokens=3, max_life_tokens=1) if name == "small"

@@ -288,12 +288,13 @@ def test_persistent_rollout_equals_stepwise(cfg, n, hip_lib):
 
 
 @pytest.mark.parametrize("script,n", [("script_card_moves", 200), ("script_empty_deck", 96), ("script_complete_a_firework", 300)])
-def test_known_answers_by_hand_on_gpu(script, n, hip_lib):
+def test_known_answers_by_hand_on_gpu_hints_keep_last_move(script, n, hip_lib):
     """tests/hanabi_by_hand.py -- scripted games worked out from the reference text, NOT from the oracle: a successful and a
     failed play, a discard, the knowledge reset of a redrawn slot, the shift-left of a hand on an empty deck, a completed
     firework with the ninth information token and its shifted encoding -- replayed
     through the HIP step: every entry of the mover's observation, the state's own-hand tail and the legal moves, for the
-    single-launch step and for the two-launch pair."""
+    single-launch step and for the two-launch pair.  After a hint the last-action section encodes the world's last card
+    move: a hint never sets lastmove.move (sim.cpp:642,666 are the only writes)."""
     import hanabi_by_hand as by_hand
     scripts = [getattr(by_hand, script)(w) for w in range(n)]
     for knob in (1, 2):
@@ -312,12 +313,24 @@ def test_known_answers_by_hand_on_gpu(script, n, hip_lib):
         sim.close()
 
 
-@pytest.mark.parametrize("policy,n,steps,reason", [("policy_score_then_lose", 600, 40, "life"), ("policy_run_out_the_deck", 300, 90, "turns")])
+@pytest.mark.parametrize("policy,n,steps,reason", [("policy_score_then_lose", 600, 40, "life")])
 def test_endings_and_next_episodes_by_hand_on_gpu(policy, n, steps, reason, hip_lib):
     """Whole games worked out by hand (tests/hanabi_by_hand.py, not the oracle), endings included: every step's reward and
     done -- the move that burns the last life token is paid minus the score --, and after an ending BOTH agents' rows of the
     world's next game, dealt from the episode index it gets when the step's finished worlds (several workgroups' worth) take
     the indices in ascending world order; through the single-launch step and through the two-launch pair."""
+    _endings_by_hand_on_gpu(policy, n, steps, reason)
+
+
+@pytest.mark.parametrize("policy,n,steps,reason", [("policy_run_out_the_deck", 300, 90, "turns")])
+def test_endings_and_next_episodes_by_hand_on_gpu_hints_keep_last_move(policy, n, steps, reason, hip_lib):
+    """As test_endings_and_next_episodes_by_hand_on_gpu, for the policy that hints whenever it cannot discard: after each of
+    those hints the last-action section encodes the world's last card move, as the reference does (a hint never sets
+    lastmove.move, sim.cpp:642,666 are the only writes)."""
+    _endings_by_hand_on_gpu(policy, n, steps, reason)
+
+
+def _endings_by_hand_on_gpu(policy, n, steps, reason):
     import hanabi_by_hand as by_hand
     for knob in (1, 2):
         with debug_knobs({"fused_step": knob}):
@@ -393,3 +406,111 @@ def test_steps_captured_in_a_hip_graph_after_prepare(n, fused, hip_lib):
     assert finished > 0
     eager.close()
     graphed.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# Against the reference's own sim.cpp, compiled unchanged against the Madrona stand-in (oracle/_ref, oracle/ref.py):
+# every HIP path directly, not through the oracle.  Moves come from the policies of tests/test_ref_hanabi.py (hints first,
+# burning the life tokens, running the deck out, completing a firework with a full information pool, random), read off
+# the HIP game records, so the rare paths -- the hint's kept move type above all -- are on the GPU too.
+# ---------------------------------------------------------------------------------------------
+def compare_ref(sim, r, tag, cfg):
+    no, ns = hanabi_spec.observation_size(cfg), hanabi_spec.state_size(cfg)
+    got_o = sim.observation_tensor().to_torch().cpu().numpy().astype(np.uint8)
+    got_s = sim.agent_state_tensor().to_torch().cpu().numpy().astype(np.uint8)
+    assert np.array_equal(got_o[..., :no], r.obs[..., :no]), f"obs {tag}"
+    assert np.array_equal(got_s[..., :ns], r.state[..., :ns]), f"state {tag}"
+    assert np.array_equal(sim.action_mask_tensor().to_torch().cpu().numpy(), r.mask), f"mask {tag}"
+    assert np.array_equal(sim.active_agent_tensor().to_torch().cpu().numpy(), r.active), f"active {tag}"
+    assert np.array_equal(sim.reward_tensor().to_torch().cpu().numpy(), r.reward), f"reward {tag}"
+    assert np.array_equal(sim.done_tensor().to_torch().cpu().numpy(), r.done), f"done {tag}"
+
+
+@pytest.mark.parametrize("cfg,n,steps,fused,heal", [(FULL, 65536, 40, 1, 0), (FULL, 9001, 150, 1, 0), (FULL, 9001, 150, 1, 3),
+                                                    (FULL, 9001, 150, 2, 0), (FULL, 65536, 40, 2, 0), (SMALL, 4097, 120, 1, 3),
+                                                    (VERY_SMALL, 3001, 60, 2, 0)],
+                         ids=["full_65536_one_launch", "full_9001_one_launch", "full_9001_one_launch_heal3",
+                              "full_9001_two_launches", "full_65536_two_launches", "small_4097_one_launch_heal3",
+                              "very_small_3001_two_launches"])
+def test_step_vs_compiled_reference(cfg, n, steps, fused, heal, hip_lib):
+    from oracle import ref
+    from test_ref_hanabi import choose
+    ref.require()
+    with debug_knobs({"fused_step": fused, "fused_heal_test": heal}):
+        sim = make(cfg, n)
+    assert sim.kernel_name == ("mrl_hanabi_step_fused" if fused == 1 else "mrl_hanabi_step")
+    r = ref.RefHanabi(cfg, n)
+    compare_ref(sim, r, "initial", cfg)
+    rng = np.random.default_rng(n + heal)
+    finished = 0
+    for t in range(steps):
+        a = choose(rng, cfg, r.mask, sim.game_tensor().to_torch().cpu().numpy())
+        r.step(a)
+        if fused == 1:
+            sim.action_tensor().to_torch().copy_(torch.from_numpy(a).cuda().view(2, n, 1))
+            sim.step()
+        else:
+            sim.step_phase1(torch.from_numpy(a).cuda().view(2, n, 1))
+            sim.step_phase2(None)
+        compare_ref(sim, r, f"step {t}", cfg)
+        finished += int(r.done.sum())
+    assert finished > 0
+    sim.close()
+
+
+@pytest.mark.parametrize("n,chunk,chunks", [(9001, 40, 3), (65536, 25, 1)], ids=["9001", "65536"])
+def test_persistent_rollout_vs_compiled_reference(n, chunk, chunks, hip_lib):
+    """mrl_rollout_random, `chunk` steps per call (the persistent rollout), against the reference fed the same moves: the
+    documented device policy (simulators.random_hanabi_action) replayed on the host from the reference's own masks."""
+    from madrona_rl_envs_playground_amd.simulators import random_hanabi_action
+    from oracle import ref
+    ref.require()
+    sim, r = make(FULL, n), ref.RefHanabi(FULL, n)
+    seed, world = 0x5EED0F, np.arange(n)
+    step = 0
+    for c in range(chunks):
+        for t in range(chunk):
+            mover = (r.active[1] != 0).astype(np.int64)
+            want = random_hanabi_action(seed, step + t, world, mover, r.mask[mover, world])
+            acts = np.zeros((2, n), np.int32)
+            acts[mover, world] = want
+            r.step(acts)
+        sim.rollout_random(chunk, seed=seed, first_step=step)
+        step += chunk
+        compare_ref(sim, r, f"after rollout call {c}", FULL)
+        got = sim.action_tensor().to_torch().cpu().numpy()[mover, world, 0]
+        assert np.array_equal(got, want), "last drawn actions"
+    sim.close()
+
+
+@pytest.mark.parametrize("name,cfg", [("full", FULL), ("small", SMALL), ("very_small", VERY_SMALL)], ids=["full", "small", "very_small"])
+@pytest.mark.parametrize("fused", [1, 2], ids=["one_launch", "two_launches"])
+def test_step_reproduces_compiled_reference_fixture(name, cfg, fused, hip_lib):
+    """tests/golden/hanabi_ref_<cfg>.npz (the reference's own sim.cpp, tests/golden/make_ref_golden.py) on the GPU."""
+    from conftest import load_golden
+    z = load_golden(f"hanabi_ref_{name}.npz")
+    no, ns = hanabi_spec.observation_size(cfg), hanabi_spec.state_size(cfg)
+    n = z["actions"].shape[2]
+    with debug_knobs({"fused_step": fused}):
+        sim = make(cfg, n)
+
+    def check(tag, obs, state, mask, active, reward=None, done=None):
+        assert np.array_equal(sim.observation_tensor().to_torch().cpu().numpy().astype(np.uint8)[..., :no], obs), f"obs {tag}"
+        assert np.array_equal(sim.agent_state_tensor().to_torch().cpu().numpy().astype(np.uint8)[..., :ns], state), f"state {tag}"
+        assert np.array_equal(sim.action_mask_tensor().to_torch().cpu().numpy(), mask), f"mask {tag}"
+        assert np.array_equal(sim.active_agent_tensor().to_torch().cpu().numpy(), active), f"active {tag}"
+        if reward is not None:
+            assert np.array_equal(sim.reward_tensor().to_torch().cpu().numpy(), reward), f"reward {tag}"
+            assert np.array_equal(sim.done_tensor().to_torch().cpu().numpy(), done), f"done {tag}"
+
+    check("initial", z["first_obs"], z["first_state"], z["first_mask"], z["first_active"])
+    for t in range(z["actions"].shape[0]):
+        a = torch.from_numpy(z["actions"][t].astype(np.int32)).cuda().view(2, n, 1)
+        if fused == 1:
+            sim.action_tensor().to_torch().copy_(a)
+            sim.step()
+        else:
+            sim.step_phase1(a)
+            sim.step_phase2(None)
+        check(f"step {t}", z["obs"][t], z["state"][t], z["mask"][t], z["active"][t], z["reward"][t], z["done"][t])
+    sim.close()

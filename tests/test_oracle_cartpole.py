@@ -95,3 +95,18 @@ def test_config0_plumbing_1024_worlds(oracle_lib):
         assert (np.abs(orc.state[:, 0]) <= 2.4 + 1e-3).all()  # finished worlds were re-seeded
     assert 20000 < total_done < 80000  # random policy: episodes of ~20 steps
     assert orc.episodes == n + total_done
+
+
+def test_oracle_reproduces_compiled_reference_fixture(oracle_lib):
+    """tests/golden/cartpole_ref.npz: the reference's own sim.cpp compiled against the Madrona stand-in
+    (tests/golden/make_ref_golden.py): reset states, episode order and the reference-typed arithmetic, bit for bit."""
+    from conftest import load_golden
+    z = load_golden("cartpole_ref.npz")
+    n = z["first_state"].shape[0]
+    orc = oracle_lib.CartpoleOracle(n)
+    assert np.array_equal(orc.state.view(np.uint32), z["first_state"].view(np.uint32))
+    for t in range(z["actions"].shape[0]):
+        orc.step(z["actions"][t].astype(np.int32))
+        assert np.array_equal(orc.state.view(np.uint32), z["state"][t].view(np.uint32)), f"state, step {t}"
+        assert np.array_equal(orc.done[:, 0], z["done"][t]), f"done, step {t}"
+    assert orc.episodes == int(z["episodes"])

@@ -203,11 +203,10 @@ def test_hint_known_answers_by_hand(oracle_lib):
         c = int(colour[w])
         shown = [int(card // 5 == c) for card in hand1[w]]     # reveal_bitmask, card 0 first
         want = np.zeros(55, np.int64)
-        want[1] = 1                                            # the mover sits one seat before the observer
-        want[2 + 2] = 1                                        # move type: play, discard, REVEAL COLOUR, reveal rank
-        want[6 + 0] = 1                                        # the hint went to the observer itself
-        want[8 + c] = 1                                        # colour one-hot; rank one-hot stays empty
-        want[18:23] = shown                                    # which of the target's cards were touched
+        want[1] = 1                                            # the mover sits one seat before the observer (sim.cpp:170-174)
+        # and nothing else: a hint never sets lastmove.move (only sim.cpp:642 and :666 do), so it is still kInvalid from
+        # resetWorld (:492); the move-type one-hot takes the default branch (:194) and the target, colour, rank, reveal
+        # (:197-249), card-index and card (:251-276) and scored / token (:278-284) entries are all gated on the move type
         assert o[w, L:L + 55].tolist() == want.tolist(), f"world {w}: last-action section"
         own = o[w, K:K + 175].reshape(5, 35)
         for j in range(5):
@@ -229,11 +228,7 @@ def test_hint_known_answers_by_hand(oracle_lib):
         shown0 = [int(card % 5 == r) for card in hand0[w]]
         shown1 = [int(card // 5 == c) for card in hand1[w]]
         want = np.zeros(55, np.int64)
-        want[1] = 1
-        want[2 + 3] = 1                                        # REVEAL RANK
-        want[6 + 0] = 1
-        want[13 + r] = 1                                       # rank one-hot
-        want[18:23] = shown0
+        want[1] = 1                                            # as after the colour hint: the move type is still kInvalid
         assert o[w, L:L + 55].tolist() == want.tolist(), f"world {w}: last-action section after the rank hint"
         own = o[w, K:K + 175].reshape(5, 35)
         for j in range(5):
@@ -247,6 +242,39 @@ def test_hint_known_answers_by_hand(oracle_lib):
             assert not other[j, 30:35].any()
     # information tokens: two hints spent (thermometer at 192..199 in the mover's observation)
     assert (orc.obs[0][:, 192:200].sum(-1) == 6).all()
+
+    # step 3: player 0 discards card 0; step 4: player 1 reveals the highest colour in player 0's new hand; step 5:
+    # player 0 reveals the rank of player 1's card 0.  The hints leave the discard's move type (sim.cpp:642) in place and
+    # reset everything else (:621-630), so the observer sees: the mover one seat before it, "discard", no card index,
+    # and the card one-hot at colour * ranks + rank compared in uint32 (:267): c * 5 - 1 after a colour hint c > 0
+    # (rank -1), nothing after a rank hint (colour -1)
+    acts[:] = 0
+    orc.step(acts)                                             # uid 0: discard card 0
+    assert (orc.active[1] == 1).all()
+    new_hand0 = orc.obs[1, :, :125].reshape(n, 5, 25).argmax(-1)
+    top = new_hand0.max(-1) // 5
+    acts[1] = 10 + top
+    orc.step(acts)
+    o = orc.obs[0].astype(np.int64)
+    assert (orc.active[0] == 1).all() and (orc.done == 0).all()
+    for w in range(n):
+        want = np.zeros(55, np.int64)
+        want[1] = 1
+        want[2 + 1] = 1                                        # still DISCARD
+        if top[w] > 0:
+            want[28 + 5 * int(top[w]) - 1] = 1
+        assert o[w, L:L + 55].tolist() == want.tolist(), f"world {w}: last-action section of a colour hint after a discard"
+    assert (top > 0).sum() > n // 2                            # most worlds carry the c * 5 - 1 entry
+    acts[:] = 0
+    acts[0] = 15 + orc.obs[0, :, :25].argmax(-1) % 5          # the rank of player 1's card 0, as player 0 sees it
+    orc.step(acts)
+    o = orc.obs[1].astype(np.int64)
+    assert (orc.active[1] == 1).all()
+    for w in range(n):
+        want = np.zeros(55, np.int64)
+        want[1] = 1
+        want[2 + 1] = 1
+        assert o[w, L:L + 55].tolist() == want.tolist(), f"world {w}: last-action section of a rank hint after a discard"
 
 
 # ---------------------------------------------------------------------------------------------
@@ -313,3 +341,24 @@ def test_endings_and_next_episodes_by_hand(policy, steps, reason, oracle_lib):
     io = (lambda acts: orc.step(acts)), (lambda: (orc.obs, orc.state, orc.mask, orc.active, orc.done, orc.reward))
     started, reasons = by_hand.run_policy_games(*io, n, getattr(by_hand, policy), steps)
     assert reasons == {reason} and started >= n
+
+
+@pytest.mark.parametrize("name", list(CONFIGS))
+def test_oracle_reproduces_compiled_reference_fixture(name, oracle_lib):
+    """tests/golden/hanabi_ref_<cfg>.npz: what the reference's own sim.cpp (compiled against the Madrona stand-in,
+    tests/golden/make_ref_golden.py) computed -- every section of both agents' rows, hint-heavy streams included; this keeps
+    the oracle pinned where oracle/_ref is not built."""
+    z = load_golden(f"hanabi_ref_{name}.npz")
+    cfg = CONFIGS[name]
+    no, ns = hanabi_spec.observation_size(cfg), hanabi_spec.state_size(cfg)
+    n = z["actions"].shape[2]
+    orc = oracle_lib.HanabiOracle(cfg, n)
+    assert np.array_equal(orc.obs[..., :no], z["first_obs"]) and np.array_equal(orc.state[..., :ns], z["first_state"])
+    assert np.array_equal(orc.mask, z["first_mask"]) and np.array_equal(orc.active, z["first_active"])
+    for t in range(z["actions"].shape[0]):
+        orc.step(z["actions"][t].astype(np.int32))
+        assert np.array_equal(orc.obs[..., :no], z["obs"][t]), f"obs, step {t}"
+        assert np.array_equal(orc.state[..., :ns], z["state"][t]), f"state, step {t}"
+        for k in ("mask", "active", "reward", "done"):
+            assert np.array_equal(getattr(orc, k), z[k][t]), f"{k}, step {t}"
+    assert orc.episodes == int(z["episodes"])
