@@ -428,6 +428,32 @@ int mrl_step_sequence(mrl_sim *sim, const int32_t *actions_dev, uint32_t num_ste
  * the worlds' state resident in LDS / registers; otherwise it is one launch per step. */
 int mrl_rollout_random(mrl_sim *sim, uint32_t num_steps, uint64_t seed, uint32_t first_step, void *hip_stream);
 
+/* Restart the worlds whose byte in mask_dev is nonzero (device pointer, N bytes; NULL = every world) as fresh
+ * episodes, now, on hip_stream.  No reference counterpart (the reference restarts a world only when its episode ends
+ * inside a step); EnvPool's reset(env_ids) is the same call.
+ *   What a reset world becomes: world i is bit-identical to world 0 of a newly built simulator of the same configuration
+ *     whose first episode has the index world i receives -- observations, Hanabi STATE / ACTION_MASK / ACTIVE_AGENT /
+ *     GAME, the Overcooked STATE_* tensors (and Simplecooked's STATE_DISHES_OUT), Cartpole STATE.  Overcooked and
+ *     Simplecooked have no episode index: timestep 0, no objects, players on their start cells facing north, empty hands.
+ *   Numbering (Hanabi, Cartpole, balance beam): the reset worlds take the episode indices counter, counter + 1, ... in
+ *     ascending world order and the counter advances by their number; later episode ends go on from there exactly as if
+ *     those worlds had finished in a step.  The call is the two-launch step's phase 2 run on the mask: it follows the
+ *     same double-buffered counter (host mode, or the device-side state after mrl_prepare_graph_capture).
+ *   Untouched: worlds outside the mask, in every tensor, and every per-step output -- DONE / RESET, REWARD, ACTION,
+ *     RESET_COUNT, SHARD_COUNT, SCAN_TIMEOUT.  A mask with no byte set changes nothing, the counter included.
+ *   Overcooked / Simplecooked observations go where the most recent step wrote: the simulator's tensor, the slot of
+ *     mrl_set_observation_output, or ring slot (k - 1) mod T; where no step has run since that destination was set, where
+ *     the next step will write.  A STAGED destination (off a 16-byte boundary) is refused with MRL_ERR_INVALID.
+ *   Refused with MRL_ERR_INVALID: a Hanabi, Cartpole or balance-beam simulator that has been through mrl_reseed_shard or
+ *     mrl_exchange_create (numbering across ranks would need an exchange between them); a capturing stream wherever
+ *     mrl_step refuses one (a reset captured after mrl_prepare_graph_capture replays correctly); a NULL handle.
+ *   It only enqueues work: no host synchronisation.  Every later mrl_step*, mrl_step_many, mrl_step_sequence,
+ *   mrl_rollout_random and graph replay continues from the reset state.  The caller keeps mask_dev valid until the work
+ *   has run.  Cost: one small launch that turns the mask into per-workgroup counts plus the re-seeding launch (counter
+ *   games); one launch with a wavefront per world that copies the fresh world over the masked ones (Overcooked,
+ *   Simplecooked).  DESIGN.md section 9. */
+int mrl_reset_worlds(mrl_sim *sim, const uint8_t *mask_dev_or_null, void *hip_stream);
+
 int mrl_tensor(mrl_sim *sim, int slot, mrl_tensor_desc *out);
 int mrl_game(const mrl_sim *sim);
 uint32_t mrl_num_worlds(const mrl_sim *sim);

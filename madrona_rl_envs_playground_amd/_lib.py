@@ -32,7 +32,7 @@ SYMBOLS = [
     "mrl_abi_version", "mrl_rollout_random", "mrl_step_sequence", "mrl_debug_set", "mrl_probe_stream",
     "mrl_scan_timed_out", "mrl_simplecooked_create", "mrl_launch_shape", "mrl_balance_create", "mrl_step_with_actions_i64",
     "mrl_step_phase2_gathered", "mrl_set_observation_output", "mrl_set_observation_ring", "mrl_prepare_graph_capture", "mrl_step_many",
-    "mrl_build_hash", "mrl_exchange_create", "mrl_exchange_connect", "mrl_step_exchanged",
+    "mrl_build_hash", "mrl_exchange_create", "mrl_exchange_connect", "mrl_step_exchanged", "mrl_reset_worlds",
 ]
 ABI_VERSION = 4  # MRL_ABI_VERSION of include/mrl_envs.h this binding was written against
 
@@ -159,6 +159,7 @@ def lib():
     L.mrl_reseed_shard.argtypes = [vp, u32, u32, vp]
     L.mrl_rollout_random.argtypes = [vp, u32, ctypes.c_uint64, u32, vp]
     L.mrl_step_sequence.argtypes = [vp, vp, u32, vp]
+    L.mrl_reset_worlds.argtypes = [vp, vp, vp]
     L.mrl_tensor.argtypes = [vp, i32, ctypes.POINTER(TensorDesc)]
     L.mrl_game.argtypes = [vp]
     L.mrl_num_worlds.argtypes = [vp]

@@ -21,6 +21,7 @@
 #include "common.hpp"
 #include "episode_scan.hpp"
 #include "random_policy.hpp"
+#include "world_reset.hpp"
 
 namespace {
 
@@ -460,6 +461,17 @@ struct BalanceSim final : mrl_sim {
         launch_reset(counter + parity, g, stream);
     }
     void phase2_exchanged(hipStream_t stream) override { launch_reset(counter + parity, mrl::polled_counts(exchange, alarm.alarm()), stream); }
+    // mrl_reset_worlds: phase 2 on the caller's mask, with a scratch RESET_COUNT (world_reset.hpp)
+    mrl::ResetScratch forced;
+    void reset_worlds(const uint8_t *mask_dev, hipStream_t stream) override
+    {
+        forced.build(mask_dev, num_worlds, grid, chunk, stream);
+        if (launch_state.device_mode) launch_state.advance(stream);
+        hipLaunchKernelGGL((mrl_balance_reset<false>), dim3(grid), dim3(kBlock), 0, stream, num_worlds, chunk, forced.words, obs, forced.block_counts,
+                           counter + parity, 0u, counter + (parity ^ 1u), forced.reset_count, mrl::GatheredCounts{}, launch_state.counter_args(counter));
+        MRL_HIP(hipGetLastError());
+        parity ^= 1u;
+    }
     void rollout_random(uint32_t num_steps, uint64_t seed, uint32_t first_step, hipStream_t stream) override
     {
         for (uint32_t k = 0; k < num_steps; k++) {
@@ -554,6 +566,7 @@ mrl_sim *mrl::create_balance(int gpu_id, uint32_t num_worlds)
         sim->counter = sim->arena.alloc<uint32_t>(2);
         sim->reset_count = sim->arena.alloc<uint32_t>(1);
         sim->shard_count = sim->arena.alloc<uint32_t>(1);
+        sim->forced.init(sim->arena, sim->grid, sim->chunk, N, true, false);
         sim->launch_state.init(sim->arena);
         sim->alarm.init(sim->arena);
         {

@@ -443,7 +443,24 @@ int mrl_reseed_shard(mrl_sim *sim, uint32_t world_offset, uint32_t num_worlds_to
 {
     if (int rc = mrl::need(sim)) return rc;
     mrl::DeviceGuard on(sim->device);
-    return guarded([&] { sim->reseed_shard(world_offset, num_worlds_total, (hipStream_t)hip_stream); });
+    return guarded([&] {
+        sim->reseed_shard(world_offset, num_worlds_total, (hipStream_t)hip_stream);
+        sim->reseeded = true;
+    });
+}
+
+int mrl_reset_worlds(mrl_sim *sim, const uint8_t *mask_dev_or_null, void *hip_stream)
+{
+    if (int rc = mrl::need_healthy(sim)) return rc;
+    if (int rc = mrl::need_not_capturing(sim, hip_stream, "mrl_reset_worlds")) return rc;
+    const bool numbered = sim->game == MRL_GAME_HANABI || sim->game == MRL_GAME_CARTPOLE || sim->game == MRL_GAME_BALANCE;
+    if (numbered && (sim->reseeded || sim->exchange.mine)) {
+        mrl::set_error("mrl_reset_worlds: this simulator is a shard of a larger batch (mrl_reseed_shard / mrl_exchange_create); "
+                       "numbering restarted episodes across ranks is not supported");
+        return MRL_ERR_INVALID;
+    }
+    mrl::DeviceGuard on(sim->device);
+    return guarded([&] { sim->reset_worlds(mask_dev_or_null, (hipStream_t)hip_stream); });
 }
 
 int mrl_step_sequence(mrl_sim *sim, const int32_t *actions_dev, uint32_t num_steps, void *hip_stream)

@@ -19,6 +19,7 @@
 #include "common.hpp"
 #include "episode_scan.hpp"
 #include "random_policy.hpp"
+#include "world_reset.hpp"
 
 #include <cstdlib>
 #include <type_traits>
@@ -872,6 +873,18 @@ struct CartpoleSim final : mrl_sim {
     }
     void phase2_exchanged(hipStream_t stream) override { launch_reset(counter + parity, mrl::polled_counts(exchange, alarm.alarm()), stream); }
 
+    // mrl_reset_worlds: phase 2 on the caller's mask, with a scratch RESET_COUNT (world_reset.hpp)
+    mrl::ResetScratch forced;
+    void reset_worlds(const uint8_t *mask, hipStream_t stream) override
+    {
+        forced.build(mask, num_worlds, grid, chunk, stream);
+        if (launch_state.device_mode) launch_state.advance(stream);
+        hipLaunchKernelGGL(mrl_cartpole_reset, dim3(grid), dim3(kBlock), 0, stream, num_worlds, chunk, state, forced.block_counts, forced.words,
+                           counter + parity, counter + (parity ^ 1u), forced.reset_count, mrl::GatheredCounts{}, launch_state.counter_args(counter));
+        MRL_HIP(hipGetLastError());
+        parity ^= 1u;
+    }
+
     void set_episode_counter(uint32_t next_episode, hipStream_t stream) override
     {
         if (launch_state.device_mode) {  // which half is current is only known on the device
@@ -959,6 +972,7 @@ mrl_sim *mrl::create_cartpole(int gpu_id, uint32_t num_worlds)
         sim->counter = sim->arena.alloc<uint32_t>(2);
         sim->reset_count = sim->arena.alloc<uint32_t>(1);
         sim->shard_count = sim->arena.alloc<uint32_t>(1);
+        sim->forced.init(sim->arena, sim->grid, sim->chunk, num_worlds, true, false);
         {
             const uint32_t blocks = (num_worlds + kUnroll * kBlock - 1) / (kUnroll * kBlock);
             if (blocks <= mrl::kMaxFusedBlocks) {

@@ -187,6 +187,7 @@ struct mrl_sim {
     int game = 0;
     int device = 0;
     uint32_t num_worlds = 0;
+    bool reseeded = false;  // mrl_reseed_shard was called: the worlds are a shard of a larger batch
     mrl::DeviceArena arena;
     mrl::ShardExchange exchange;
 
@@ -240,6 +241,8 @@ struct mrl_sim {
     virtual bool capturable() const { return true; }
     virtual void set_episode_counter(uint32_t, hipStream_t) {}
     virtual void reseed_shard(uint32_t, uint32_t, hipStream_t) {}
+    // mrl_reset_worlds: restart the worlds whose mask byte is nonzero (mask == nullptr: every world) now, on `stream`
+    virtual void reset_worlds(const uint8_t *, hipStream_t) { throw std::runtime_error("mrl_reset_worlds: this game cannot restart worlds"); }
     virtual bool tensor(int slot, mrl_tensor_desc *out) = 0;
     virtual const char *kernel_name() const = 0;
     virtual const char *rollout_kernel_name() const { return kernel_name(); }

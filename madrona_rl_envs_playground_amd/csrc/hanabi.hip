@@ -34,6 +34,7 @@
 #include "common.hpp"
 #include "episode_scan.hpp"
 #include "random_policy.hpp"
+#include "world_reset.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -2358,6 +2359,27 @@ struct HanabiSim final : mrl_sim {
     }
     void phase2_exchanged(hipStream_t stream) override { launch_reset(counter + parity, mrl::polled_counts(exchange, alarm.alarm()), stream); }
 
+    // mrl_reset_worlds: phase 2 on the caller's mask (read through p.done), with a scratch RESET_COUNT (world_reset.hpp)
+    mrl::ResetScratch forced;
+    void reset_worlds(const uint8_t *mask, hipStream_t stream) override
+    {
+        forced.build(mask, num_worlds, grid, params.chunk, stream);
+        HanabiParams q = params;
+        q.done = forced.flags;
+        q.block_counts = forced.block_counts;
+        if (launch_state.device_mode) launch_state.advance(stream);
+        const mrl::DeviceCounter dc = launch_state.counter_args(counter);
+        const uint32_t *base = counter + parity;
+        uint32_t *next = counter + (parity ^ 1u);
+        switch (variant) {
+        case 2: hipLaunchKernelGGL((mrl_hanabi_reset<false, 2>), dim3(grid), dim3(kBlock), 0, stream, q, base, 0u, next, forced.reset_count, mrl::GatheredCounts{}, dc); break;
+        case 1: hipLaunchKernelGGL((mrl_hanabi_reset<false, 1>), dim3(grid), dim3(kBlock), 0, stream, q, base, 0u, next, forced.reset_count, mrl::GatheredCounts{}, dc); break;
+        default: hipLaunchKernelGGL((mrl_hanabi_reset<false, 0>), dim3(grid), dim3(kBlock), 0, stream, q, base, 0u, next, forced.reset_count, mrl::GatheredCounts{}, dc); break;
+        }
+        MRL_HIP(hipGetLastError());
+        parity ^= 1u;
+    }
+
     void set_episode_counter(uint32_t next_episode, hipStream_t stream) override
     {
         if (launch_state.device_mode) {  // which half is current is only known on the device
@@ -2518,6 +2540,7 @@ mrl_sim *mrl::create_hanabi(const mrl_hanabi_config *cfg, int gpu_id, uint32_t n
         sim->agent_id = sim->arena.alloc<int32_t>((size_t)2 * N, false);
         sim->counter = sim->arena.alloc<uint32_t>(2);
         sim->reset_count = sim->arena.alloc<uint32_t>(1);
+        sim->forced.init(sim->arena, sim->grid, sim->params.chunk, N, false, true);
         sim->alarm.init(sim->arena);
         sim->launch_state.init(sim->arena);
         sim->status = sim->arena.alloc<unsigned long long>(sim->grid);

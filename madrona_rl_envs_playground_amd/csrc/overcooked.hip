@@ -46,6 +46,7 @@
 //   obs      [N][P][C][F] u8, F = 5P+16: one contiguous P*C*F block per world
 #include "common.hpp"
 #include "random_policy.hpp"
+#include "world_reset.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -2110,6 +2111,18 @@ struct OvercookedSim final : mrl_sim {
     {
         if (staged && dest) MRL_HIP(hipMemcpyAsync(dest, staging, observation_bytes(), hipMemcpyDeviceToDevice, stream));
     }
+
+    // mrl_reset_worlds: world 0 as construction left it, copied over the masked worlds (world_reset.hpp).  The observations go
+    // where the most recent step wrote -- before any step since the output was set, where the next step will write.
+    mrl::FreshWorldOwner fresh;
+    void reset_worlds(const uint8_t *mask, hipStream_t stream) override
+    {
+        if (staged)
+            throw std::runtime_error("mrl_reset_worlds: the observation output is a staged slot (off a 16-byte boundary); a reset writes "
+                                     "observations in place only -- use an aligned slot or the simulator's own tensor");
+        const uint64_t slot = ring_pos ? (ring_pos - 1) % ring_slots : 0;
+        fresh.launch(mask, num_worlds, ring_base + (size_t)slot * ring_stride, stream);
+    }
     // the slot(s) of the next `steps` steps: single-step launches get the slot as their `obs`, multi-step ones the first index
     uint8_t *take_slots(uint32_t steps, uint32_t *first)
     {
@@ -2707,6 +2720,9 @@ mrl_sim *mrl::create_overcooked(const mrl_overcooked_config *cfg, int gpu_id, ui
         // Sim::Sim (sim.cpp:556-659): reset state + first observation
         sim->launch(true, nullptr, 0);
         MRL_HIP(hipDeviceSynchronize());
+        sim->fresh.init(sim->arena,
+                        {{a.cell_obj, a.C}, {reinterpret_cast<uint32_t *>(a.players), 2 * a.P}, {reinterpret_cast<uint32_t *>(a.timestep), 1u}},
+                        sim->own_obs, a.block_bytes);
     } catch (...) {
         delete sim;
         throw;

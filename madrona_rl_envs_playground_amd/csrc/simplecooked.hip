@@ -33,6 +33,7 @@
 #include "common.hpp"
 #include "grid_common.hpp"
 #include "random_policy.hpp"
+#include "world_reset.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -854,6 +855,16 @@ struct SimplecookedSim final : mrl_sim {
     }
     bool staged = false;
     uint8_t *staging = nullptr;
+    // mrl_reset_worlds: see OvercookedSim::reset_worlds
+    mrl::FreshWorldOwner fresh;
+    void reset_worlds(const uint8_t *mask, hipStream_t stream) override
+    {
+        if (staged)
+            throw std::runtime_error("mrl_reset_worlds: the observation output is a staged slot (off a 16-byte boundary); a reset writes "
+                                     "observations in place only -- use an aligned slot or the simulator's own tensor");
+        const uint64_t slot = ring_pos ? (ring_pos - 1) % ring_slots : 0;
+        fresh.launch(mask, num_worlds, ring_base + (size_t)slot * ring_stride, stream);
+    }
     uint8_t *take_slots(uint32_t steps, uint32_t *first)
     {
         const uint32_t at = (uint32_t)(ring_pos % ring_slots);
@@ -1239,6 +1250,9 @@ mrl_sim *mrl::create_simplecooked(const mrl_overcooked_config *cfg, int gpu_id, 
         // Sim::Sim (sim.cpp:470-575): reset state + first observation
         sim->launch(true, a, 0);
         MRL_HIP(hipDeviceSynchronize());
+        sim->fresh.init(sim->arena,
+                        {{a.cell_obj, a.C}, {reinterpret_cast<uint32_t *>(a.players), 2 * a.P}, {reinterpret_cast<uint32_t *>(a.clock), 2u}},
+                        sim->own_obs, a.block_bytes);
     } catch (...) {
         delete sim;
         throw;

@@ -44,7 +44,11 @@ class CartpoleMadronaTorch(_CartpoleBase):
         return (self.to_torch(self.static_observations), self.to_torch(self.static_rewards),
                 self.to_torch(self.static_dones[:, 0]), self.infos)
 
-    def reset(self):
+    def reset(self, worlds=None):
+        """The current observations (the reference restarts nothing here).  ``worlds`` (extension): a (num_envs,) bool or
+        integer mask of worlds to restart first, as new episodes (``sim.reset_worlds``)."""
+        if worlds is not None:
+            self.sim.reset_worlds(worlds)
         return self.to_torch(self.static_observations)
 
 
@@ -55,5 +59,8 @@ class CartpoleMadronaNumpy(_CartpoleBase):
         return (self.static_observations.cpu().numpy(), self.static_rewards.cpu().numpy(),
                 self.static_dones[:, 0].cpu().numpy(), [{}] * self.num_envs)
 
-    def reset(self):
+    def reset(self, worlds=None):
+        """See ``CartpoleMadronaTorch.reset``."""
+        if worlds is not None:
+            self.sim.reset_worlds(worlds)
         return self.static_observations.cpu().numpy()

@@ -77,7 +77,10 @@ class OvercookedMultiLayout:
         torch.cuda.current_stream(self.device).wait_stream(side)
         self._graph = graph
 
-    def n_reset(self):
+    def n_reset(self, worlds=None):
+        if worlds is not None:
+            raise NotImplementedError("OvercookedMultiLayout cannot restart chosen worlds: call n_reset(worlds=...) on the layout's own env "
+                                      "(self.envs[i])")
         return [env.n_reset() for env in self.envs]
 
     def _results(self):

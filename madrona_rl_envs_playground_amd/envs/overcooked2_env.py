@@ -111,9 +111,12 @@ class OvercookedMadrona(VectorMultiAgentEnv):
             return obs, self.static_rewards, self.static_dones, self.infos
         return obs, self.to_torch(self.static_rewards), self.to_torch(self.static_dones), self.infos
 
-    def n_reset(self):
-        """Like the reference (overcooked2_env.py:111-112) this restarts nothing: worlds restart themselves at
-        the horizon inside ``step``."""
+    def n_reset(self, worlds=None):
+        """Like the reference (overcooked2_env.py:111-112) ``n_reset()`` restarts nothing: worlds restart themselves at
+        the horizon inside ``step``.  ``worlds`` (extension): a (num_envs,) bool or integer mask of worlds to restart now
+        (``sim.reset_worlds``; see ``overcooked_env.OvercookedMadrona.n_reset``)."""
+        if worlds is not None:
+            self.sim.reset_worlds(worlds)
         return self.get_obs()
 
     def close(self, **kwargs):

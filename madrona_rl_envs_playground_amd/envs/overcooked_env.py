@@ -113,9 +113,13 @@ class OvercookedMadrona(VectorMultiAgentEnv):
             return obs, self.static_rewards, self.static_dones, self.infos
         return obs, self.to_torch(self.static_rewards), self.to_torch(self.static_dones), self.infos
 
-    def n_reset(self):
-        """Like the reference (overcooked_env.py:115-116) this does not restart
-        anything: worlds restart themselves at the horizon inside ``step``."""
+    def n_reset(self, worlds=None):
+        """Like the reference (overcooked_env.py:115-116) ``n_reset()`` does not restart
+        anything: worlds restart themselves at the horizon inside ``step``.  ``worlds`` (extension): a (num_envs,) bool or
+        integer mask; those worlds restart now, at timestep 0 (``sim.reset_worlds``).  Their observations are written where
+        the last step wrote them (the ``out`` of ``n_step(out=...)``, if one was given)."""
+        if worlds is not None:
+            self.sim.reset_worlds(worlds)
         return self.get_obs()
 
     def close(self, **kwargs):

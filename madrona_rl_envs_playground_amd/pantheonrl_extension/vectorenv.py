@@ -171,11 +171,12 @@ class VectorMultiAgentEnv(ABC):
         self._update_players(rews, done)
         return self._obs[self.ego_ind], rews[self.ego_ind], done, info
 
-    def reset(self):
+    def reset(self, worlds=None):
         """Resample partners and return the ego player's current observation.
-        (Worlds restart on their own inside ``step``; see ``n_reset``.)"""
+        (Worlds restart on their own inside ``step``; see ``n_reset``.)  ``worlds`` (extension): a (num_envs,) bool or
+        integer mask handed to ``n_reset``, whose worlds then restart, so the new partner starts a new game there."""
         self.resample_partner()
-        self._obs = self.n_reset()
+        self._obs = self.n_reset() if worlds is None else self.n_reset(worlds)
         return self._obs[self.ego_ind]
 
     @abstractmethod
@@ -239,7 +240,11 @@ class MadronaEnv(VectorMultiAgentEnv):
         self.sim.step()
         return self._observations(), self.to_torch(self.static_rewards), self.to_torch(self.static_dones), self.infos
 
-    def n_reset(self):
+    def n_reset(self, worlds=None):
+        """The current observations; ``worlds`` (extension): a (num_envs,) bool or integer mask of worlds to restart
+        first, as new episodes (``sim.reset_worlds``)."""
+        if worlds is not None:
+            self.sim.reset_worlds(worlds)
         return self._observations()
 
 
@@ -303,7 +308,9 @@ class SyncVectorEnv(VectorMultiAgentEnv):
         return [VectorObservation(self.static_active_agents[p], self.static_observations[p], self.static_agent_states[p],
                                   self.static_action_masks[p]) for p in range(self.n_players)]
 
-    def n_reset(self):
+    def n_reset(self, worlds=None):
+        if worlds is not None:
+            raise NotImplementedError("SyncVectorEnv cannot restart chosen worlds: n_reset(worlds=...) is for the batched simulators")
         self.agents_tuples = []
         for world, env in enumerate(self.envs):
             agents, observations = env.n_reset()

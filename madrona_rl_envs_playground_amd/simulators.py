@@ -216,6 +216,32 @@ class _Simulator:
         _lib.check(self._L.mrl_rollout_random(self._handle, int(num_steps), int(seed) & (2 ** 64 - 1), int(first_step),
                                               stream))
 
+    def reset_worlds(self, mask=None):
+        """Restart the worlds whose ``mask`` entry is nonzero (``None``: every world) as fresh episodes, enqueued on torch's
+        current stream (``mrl_reset_worlds``).  ``mask``: (num_worlds,) of bool, uint8 or any integer type, on any device;
+        it is copied into a uint8 buffer on the simulator's device that the simulator keeps.  Hanabi, Cartpole and the
+        balance beam number the restarted episodes from their episode counter as if those worlds had finished in a step;
+        Overcooked and Simplecooked put them back into the start state.  DONE, REWARD and the other per-step outputs keep
+        the last step's values."""
+        stream = _stream_ptr(self.gpu_id)
+        if mask is None:
+            _lib.check(self._L.mrl_reset_worlds(self._handle, None, stream))
+            return
+        if not isinstance(mask, torch.Tensor):
+            mask = torch.as_tensor(mask)
+        if mask.dim() != 1 or mask.numel() != self.num_worlds:
+            raise ValueError(f"mask must have shape ({self.num_worlds},) (one entry per world), got {tuple(mask.shape)}")
+        if mask.dtype.is_floating_point or mask.dtype.is_complex:
+            raise ValueError(f"mask must be a bool or integer tensor, got {mask.dtype}")
+        if mask.dtype not in (torch.bool, torch.uint8):
+            mask = mask != 0
+        if getattr(self, "_reset_mask", None) is None:
+            self._reset_mask = torch.empty(self.num_worlds, dtype=torch.uint8, device=torch.device("cuda", self.gpu_id))
+        with torch.cuda.device(self.gpu_id):
+            self._reset_mask.copy_(mask, non_blocking=True)
+        self._reset_mask_source = mask  # a pinned host mask is still read by the copy after this returns
+        _lib.check(self._L.mrl_reset_worlds(self._handle, self._reset_mask.data_ptr(), stream))
+
     def step_phase1(self, actions=None):
         ptr = self._action_pointer(actions) if actions is not None else None
         stream = _stream_ptr(self.gpu_id)
