@@ -473,7 +473,7 @@ void mrl_destroy(mrl_sim *sim);
  * context manager does exactly that, also when the create throws.  Keys (with their meanings: csrc/capi.hip, kDebugKeys):
  * overcooked.wpw, overcooked.whole_max, overcooked.lds_max, overcooked.share_max_players, overcooked.share_private,
  * overcooked.no_share, overcooked.lds_pad, overcooked.no_fixed, overcooked.no_direct, overcooked.whole_store,
- * overcooked.store_policy, overcooked.wide_rollout, overcooked.groups, overcooked.shared_consts, overcooked.variant,
+ * overcooked.store_policy, overcooked.wide_rollout, overcooked.writeback, overcooked.groups, overcooked.shared_consts, overcooked.variant,
  * hanabi.variant, hanabi.pairing, hanabi.no_persistent, cartpole.no_persistent, cartpole.persistent_max, cartpole.variant, fused_step (0 the library's choice, 1 one launch,
  * 2 two launches), fused_heal_test, inject_scan_timeout, and (diagnostic build) ablate, stamps.  key == NULL forgets all of
  * them.  Unknown key: MRL_ERR_INVALID.  No reference counterpart (the reference has MADRONA_* environment variables for its
@@ -483,7 +483,9 @@ int mrl_debug_set(const char *key, int64_t value);
 /* Measurement aid for bench.py's roofline.peak_measured: one float4 stream over caller buffers on
  * device gpu_id, enqueued on hip_stream.  mode 0: copy src -> dst (reads + writes bytes each);
  * mode 1: fill dst, plain stores; mode 2: fill dst, write-through (sc1) stores like the step
- * kernels' observation stream.  bytes: multiple of 16, buffers 16-byte aligned.  No reference counterpart. */
+ * kernels' observation stream; modes 3 / 4: mode 2's bytes and stores in two passes inside one launch, first the aligned
+ * 64-byte (3) / 128-byte (4) blocks of a fixed pseudo-random quarter of the block indices, then the rest.
+ * bytes: multiple of 16, buffers 16-byte aligned.  No reference counterpart. */
 int mrl_probe_stream(void *dst_dev, const void *src_dev, uint64_t bytes, int mode, int gpu_id, void *hip_stream);
 
 /* message of the last failing call on this thread ("" if none) */

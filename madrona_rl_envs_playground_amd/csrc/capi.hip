@@ -28,6 +28,7 @@ static const char *const kDebugKeys[] = {
     "overcooked.whole_store",   // single-pass stream-out stores: 0 by slab size and group alignment (default), 1 write-through, 2 plain
     "overcooked.store_policy",  // multi-pass stream-out stores: 0 by slab size (default), 1 sc1 write-through, 2 plain, 3 nt
     "overcooked.wide_rollout",  // 1: the multi-step launches keep the single step's group size (default: twice as wide where it fits)
+    "overcooked.writeback",  // cell words the single step writes back: 0 by batch size and layout (default), 1 every word, 2 only the words that changed
     "overcooked.groups",     // groups of worlds a wave steps one after the other in the single step of the standard layouts: 0 by batch size, 1, 2
     "overcooked.shared_consts",  // 1: constants through the workgroup-shared LDS block + barrier even where a private copy would do
     "overcooked.variant",    // 0: the library's choice; 1: force the generic (lane = world) transition
@@ -176,6 +177,25 @@ __global__ void __launch_bounds__(256) mrl_probe_stream_kernel(f32x4 *__restrict
         }
     }
     for (; i < last; i += 256) dst[i] = kMode == 0 ? src[i] : fill;
+}
+
+// Modes 3 / 4: the bytes and stores of mode 2 in TWO passes inside one launch.  The first pass stores the aligned
+// kBlockBytes blocks (64 / 128) of a fixed pseudo-random quarter of the block indices, the second pass the rest -- what a
+// step kernel does when it sends the blocks that cannot change ahead of the others.  Asks whether two halves of a
+// 128-byte line that reach the L2 at different times cost more than the line written at once.
+template <int kBlockBytes>
+__global__ void __launch_bounds__(256) mrl_probe_stream_two_pass_kernel(f32x4 *__restrict__ dst, size_t chunks)
+{
+    const size_t per_block = (chunks + gridDim.x - 1) / gridDim.x;
+    const size_t first = (size_t)blockIdx.x * per_block, last = first + per_block < chunks ? first + per_block : chunks;
+    const f32x4 fill = {1.f, 2.f, 3.f, 4.f};
+    constexpr int kShift = kBlockBytes == 64 ? 2 : 3;  // 16-byte chunks per block
+    for (int pass = 0; pass < 2; pass++) {
+        for (size_t i = first + threadIdx.x; i < last; i += 256) {
+            const bool early = (((uint32_t)(i >> kShift) * 2654435761u) >> 30) == 0u;
+            if (early == (pass == 0)) asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(dst + i), "v"(fill) : "memory");
+        }
+    }
 }
 
 }  // namespace mrl
@@ -541,9 +561,9 @@ int mrl_debug_set(const char *key, int64_t value)
 
 int mrl_probe_stream(void *dst_dev, const void *src_dev, uint64_t bytes, int mode, int gpu_id, void *hip_stream)
 {
-    if (!dst_dev || (mode == 0 && !src_dev) || mode < 0 || mode > 2 || bytes < 16 || (bytes & 15u) ||
+    if (!dst_dev || (mode == 0 && !src_dev) || mode < 0 || mode > 4 || bytes < 16 || (bytes & 15u) ||
         (reinterpret_cast<uintptr_t>(dst_dev) & 15u) || (reinterpret_cast<uintptr_t>(src_dev) & 15u)) {
-        mrl::set_error("mrl_probe_stream: need 16-byte aligned device buffers, a multiple of 16 bytes and mode 0..2");
+        mrl::set_error("mrl_probe_stream: need 16-byte aligned device buffers, a multiple of 16 bytes and mode 0..4");
         return MRL_ERR_INVALID;
     }
     mrl::DeviceGuard on(gpu_id);
@@ -557,8 +577,12 @@ int mrl_probe_stream(void *dst_dev, const void *src_dev, uint64_t bytes, int mod
             hipLaunchKernelGGL((mrl::mrl_probe_stream_kernel<0>), dim3(grid), dim3(256), 0, stream, dst, src, chunks);
         else if (mode == 1)
             hipLaunchKernelGGL((mrl::mrl_probe_stream_kernel<1>), dim3(grid), dim3(256), 0, stream, dst, src, chunks);
-        else
+        else if (mode == 2)
             hipLaunchKernelGGL((mrl::mrl_probe_stream_kernel<2>), dim3(grid), dim3(256), 0, stream, dst, src, chunks);
+        else if (mode == 3)
+            hipLaunchKernelGGL((mrl::mrl_probe_stream_two_pass_kernel<64>), dim3(grid), dim3(256), 0, stream, dst, chunks);
+        else
+            hipLaunchKernelGGL((mrl::mrl_probe_stream_two_pass_kernel<128>), dim3(grid), dim3(256), 0, stream, dst, chunks);
         MRL_HIP(hipGetLastError());
     });
 }

@@ -947,7 +947,8 @@ __device__ __forceinline__ uint32_t load_action(const StepParams &p, size_t at)
 
 // `block`: the workgroup's index among those of THIS simulator (blockIdx.x, except under mrl_overcooked_step_many, where
 // one grid covers the workgroups of several simulators)
-template <bool kInit, int kP, bool kPlain = false>
+// kSparse: only the cell words that differ from what the launch loaded are written back (store_state below)
+template <bool kInit, int kP, bool kPlain = false, bool kSparse = false>
 __device__ __forceinline__ void step_body(const StepParams &p, const uint32_t block)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -1019,10 +1020,11 @@ __device__ __forceinline__ void step_body(const StepParams &p, const uint32_t bl
     // All global loads of the group are issued before the first one is consumed (explicitly
     // batched: a plain copy loop waits for each load before issuing the next, which measured
     // 2.1 us -- three to four dependent HBM/L2 latencies -- for a 1.2 KB slab).
+    // the first kBatch * 64 cell words of the group as loaded (kSparse keeps them to the end: store_state)
+    constexpr int kBatch = 4;
+    uint32_t cell_reg[kBatch] = {};
     if (!kInit) {
         const uint32_t *g_obj = p.cell_obj + (size_t)w0 * C;
-        constexpr int kBatch = 4;
-        uint32_t cell_reg[kBatch];
         // bounds-checked buffer loads: lanes beyond the group's slab read zero, no branch around any load (behind a
         // branch hipcc consumes a load on the spot, `s_waitcnt vmcnt(0)` before the others are even issued)
         const __amdgpu_buffer_rsrc_t r_obj = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(g_obj), 0, (int)(ncells * 4u), 0x00020000);
@@ -1139,7 +1141,23 @@ __device__ __forceinline__ void step_body(const StepParams &p, const uint32_t bl
             }
         }
 #else
-        for (uint32_t i = lane; i < ncells; i += kWave) g_obj[i] = s_obj[i];
+        // kSparse: a cell word goes back only if it differs from what THIS launch loaded from its address (about one
+        // word in nine does per world and step; exact whatever a caller did to the exported tensor between steps).  Words
+        // past the register batch (groups of more than 256 cells) are stored as they are.  The host picks the
+        // instantiation (overcooked.writeback; the measurements are in DESIGN.md 4.1).
+        if constexpr (kSparse && !kInit) {
+#pragma unroll
+            for (int k = 0; k < kBatch; k++) {
+                const uint32_t i = lane + (uint32_t)k * kWave;
+                if (i < ncells) {
+                    const uint32_t v = s_obj[i];
+                    if (v != cell_reg[k]) g_obj[i] = v;
+                }
+            }
+            for (uint32_t i = lane + kBatch * kWave; i < ncells; i += kWave) g_obj[i] = s_obj[i];
+        } else {
+            for (uint32_t i = lane; i < ncells; i += kWave) g_obj[i] = s_obj[i];
+        }
         if (active) {
             const uint32_t world = w0 + wl;
             p.players[(size_t)w0 * P + lane] = make_uint2(posori, held);
@@ -1525,10 +1543,10 @@ __global__ void __launch_bounds__(kBlock) mrl_overcooked_step_team(const StepPar
     team_body<kInit>(p);
 }
 
-template <bool kInit, int kP, bool kPlain = false>
+template <bool kInit, int kP, bool kPlain = false, bool kSparse = false>
 __global__ void __launch_bounds__(kBlock) mrl_overcooked_step(const StepParams p)
 {
-    step_body<kInit, kP, kPlain>(p, blockIdx.x);
+    step_body<kInit, kP, kPlain, kSparse>(p, blockIdx.x);
 }
 
 // Several simulators -- any mix of layouts, sizes and player counts -- stepped by ONE launch (mrl_step_many): the grid is
@@ -1657,12 +1675,12 @@ __device__ __forceinline__ void take_hot_args(StepParams &q, MRL_HOT_ARGS)
 }
 #define MRL_HOT_PASS hot_cell_obj, hot_players, hot_timestep, hot_actions, hot_consts, hot_terr_off, hot_num_worlds, hot_per_xcd
 
-template <int kC, int kW, int kWidth, int kPots, int kHold, bool kI64 = false, bool kPlain = false>
+template <int kC, int kW, int kWidth, int kPots, int kHold, bool kI64 = false, bool kPlain = false, bool kSparse = false>
 __global__ void __launch_bounds__(kBlock) mrl_overcooked_step_fixed(MRL_HOT_ARGS, const StepParams p)
 {
     StepParams q = fixed_params<kC, kW, kWidth, kPots, kHold>(p);
     take_hot_args<kI64>(q, MRL_HOT_PASS);
-    step_body<false, 2, kPlain>(q, blockIdx.x);
+    step_body<false, 2, kPlain, kSparse>(q, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1866,7 +1884,7 @@ __global__ void __launch_bounds__(kWavesPerBlock * kWave) mrl_overcooked_rollout
 // launches -- and with half as many waves per SIMD a wave's phases take half as long, so the first stores leave
 // earlier.  Same state and output arrays, same results.
 // ---------------------------------------------------------------------------------------------
-template <int kP, int kG, bool kPlain = false>
+template <int kP, int kG, bool kPlain = false, bool kSparse = false>
 __device__ __forceinline__ void groups_body(const StepParams &p)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -1995,7 +2013,19 @@ __device__ __forceinline__ void groups_body(const StepParams &p)
         if (g == 0) STAMP(5);
         // the group's state, rewards and flags: behind its stream-out, like the ordinary step
         uint32_t *g_obj = p.cell_obj + (size_t)w0 * C;
-        for (uint32_t i = lane; i < ncells; i += kWave) g_obj[i] = s_obj[i];
+        if constexpr (kSparse) {  // only the cell words that differ from what this launch loaded: see store_state of step_body
+#pragma unroll
+            for (int k = 0; k < kBatch; k++) {
+                const uint32_t i = lane + (uint32_t)k * kWave;
+                if (i < ncells) {
+                    const uint32_t v = s_obj[i];
+                    if (v != cell_reg[g][k]) g_obj[i] = v;
+                }
+            }
+            for (uint32_t i = lane + kBatch * kWave; i < ncells; i += kWave) g_obj[i] = s_obj[i];
+        } else {
+            for (uint32_t i = lane; i < ncells; i += kWave) g_obj[i] = s_obj[i];
+        }
         if (active) {
             const uint32_t world = w0 + wl;
             p.players[(size_t)w0 * P + lane] = make_uint2(posori, held);
@@ -2012,12 +2042,12 @@ __device__ __forceinline__ void groups_body(const StepParams &p)
     STAMP_REALTIME(14);
 }
 
-template <int kC, int kW, int kWidth, int kPots, int kHold, bool kI64, int kG, bool kPlain = false>
+template <int kC, int kW, int kWidth, int kPots, int kHold, bool kI64, int kG, bool kPlain = false, bool kSparse = false>
 __global__ void __launch_bounds__(kBlock) mrl_overcooked_step_groups_fixed(MRL_HOT_ARGS, const StepParams p)
 {
     StepParams q = fixed_params<kC, kW, kWidth, kPots, kHold>(p);
     take_hot_args<kI64>(q, MRL_HOT_PASS);
-    groups_body<2, kG, kPlain>(q);
+    groups_body<2, kG, kPlain, kSparse>(q);
 }
 
 // fallback for layouts without the single-pass encode: draw into the ACTION tensor, then an ordinary step
@@ -2530,10 +2560,28 @@ mrl_sim *mrl::create_overcooked(const mrl_overcooked_config *cfg, int gpu_id, ui
             return knob ? knob == 2 : (!whole_lines && (multi_step || slab > (256ull << 20)));
         };
         const bool plain = plain_for(wpw, false), plain_multi = plain_for(wpw, true);
+        // Cell words written back by the single step: only those that differ from what the launch loaded (kSparse), or all.
+        // Changed-only takes 0.2 us off the headline launch and 3-6 % off every one-group-per-wave launch measured, in and
+        // beyond the Infinity Cache -- except where a wave streams more than 8320 bytes of observations between its loads and
+        // its state stores AND the slab is beyond the cache (asymmetric_advantages at 131072 worlds: 62 -> 73 us): a partial
+        // line that has left the L2 by then is a read-modify-write in HBM.  The two-groups kernels gain from 131072 worlds
+        // on and lose 1 % at 32768 (coordination_ring 10.52 -> 10.62), so they switch with the slab size.
+        // profiles/r05_b_overcooked_changed_cells_ab.txt; mrl_debug_set overcooked.writeback: 0 = this rule, 1 = every word,
+        // 2 = changed words only.
+        const auto sparse_for = [&](bool two_groups) {
+            const int64_t knob = mrl::debug_get("overcooked.writeback", 0);
+            const uint64_t slab = (uint64_t)N * a.block_bytes;
+            if (knob) return knob == 2;
+            if (slab > (256ull << 20) && (uint64_t)wpw * a.block_bytes > 8320u) return false;
+            return two_groups ? slab > (128ull << 20) : true;
+        };
         {
             const bool pairs = a.P == 2 && !sim->generic;  // two-player layouts (all five standard ones) exchange through DPP instead of LDS
-            sim->generic_step = pairs ? (plain ? &mrl_overcooked_step<false, 2, true> : &mrl_overcooked_step<false, 2, false>)
-                                      : (plain ? &mrl_overcooked_step<false, 0, true> : &mrl_overcooked_step<false, 0, false>);
+            const bool sparse = sparse_for(false);
+            sim->generic_step = pairs ? (plain ? (sparse ? &mrl_overcooked_step<false, 2, true, true> : &mrl_overcooked_step<false, 2, true, false>)
+                                               : (sparse ? &mrl_overcooked_step<false, 2, false, true> : &mrl_overcooked_step<false, 2, false, false>))
+                                      : (plain ? (sparse ? &mrl_overcooked_step<false, 0, true, true> : &mrl_overcooked_step<false, 0, true, false>)
+                                               : (sparse ? &mrl_overcooked_step<false, 0, false, true> : &mrl_overcooked_step<false, 0, false, false>));
             sim->generic_rollout = pairs ? (plain_multi ? &mrl_overcooked_rollout<2, true> : &mrl_overcooked_rollout<2, false>)
                                          : (plain_multi ? &mrl_overcooked_rollout<0, true> : &mrl_overcooked_rollout<0, false>);
         }
@@ -2579,20 +2627,20 @@ mrl_sim *mrl::create_overcooked(const mrl_overcooked_config *cfg, int gpu_id, ui
                        a.off_cur == f.off_cur && a.off_flags == f.off_flags && a.off_terr == f.off_terr && a.off_list == f.off_list &&
                        a.off_tile == f.off_tile && a.lds_wave_stride == f.stride && !mrl::debug_get("overcooked.no_fixed", 0);
             };
+// the (store flavour, write-back flavour) instantiation of a specialised kernel
+#define MRL_PICK(plain_, sparse_, kernel_, ...)                                                                      \
+    ((plain_) ? ((sparse_) ? &kernel_<__VA_ARGS__, true, true> : &kernel_<__VA_ARGS__, true, false>)                \
+              : ((sparse_) ? &kernel_<__VA_ARGS__, false, true> : &kernel_<__VA_ARGS__, false, false>))
 #define MRL_FIXED(C_, WPW_, WIDTH_, POTS_, HOLD_)                                                                    \
     if (!sim->fixed_kernel && matches(C_, WPW_, WIDTH_, POTS_, HOLD_)) {                                            \
-        sim->fixed_kernel = plain ? &mrl_overcooked_step_fixed<C_, WPW_, WIDTH_, POTS_, HOLD_, false, true>         \
-                                  : &mrl_overcooked_step_fixed<C_, WPW_, WIDTH_, POTS_, HOLD_, false, false>;       \
-        sim->fixed_kernel_i64 = plain ? &mrl_overcooked_step_fixed<C_, WPW_, WIDTH_, POTS_, HOLD_, true, true>      \
-                                      : &mrl_overcooked_step_fixed<C_, WPW_, WIDTH_, POTS_, HOLD_, true, false>;    \
+        sim->fixed_kernel = MRL_PICK(plain, sparse_for(false), mrl_overcooked_step_fixed, C_, WPW_, WIDTH_, POTS_, HOLD_, false);  \
+        sim->fixed_kernel_i64 = MRL_PICK(plain, sparse_for(false), mrl_overcooked_step_fixed, C_, WPW_, WIDTH_, POTS_, HOLD_, true); \
         sim->fixed_rollout = plain_multi ? &mrl_overcooked_rollout_fixed<C_, WPW_, WIDTH_, POTS_, HOLD_, true>      \
                                          : &mrl_overcooked_rollout_fixed<C_, WPW_, WIDTH_, POTS_, HOLD_, false>;    \
         sim->fixed_name = "mrl_overcooked_step_fixed<" #C_ ", " #WPW_ ", " #WIDTH_ ", " #POTS_ ", " #HOLD_ ", false>";      \
         if (groups == 2) {                                                                                          \
-            sim->groups_kernel = plain ? &mrl_overcooked_step_groups_fixed<C_, WPW_, WIDTH_, POTS_, HOLD_, false, 2, true>     \
-                                       : &mrl_overcooked_step_groups_fixed<C_, WPW_, WIDTH_, POTS_, HOLD_, false, 2, false>;   \
-            sim->groups_kernel_i64 = plain ? &mrl_overcooked_step_groups_fixed<C_, WPW_, WIDTH_, POTS_, HOLD_, true, 2, true>  \
-                                           : &mrl_overcooked_step_groups_fixed<C_, WPW_, WIDTH_, POTS_, HOLD_, true, 2, false>; \
+            sim->groups_kernel = MRL_PICK(plain, sparse_for(true), mrl_overcooked_step_groups_fixed, C_, WPW_, WIDTH_, POTS_, HOLD_, false, 2);    \
+            sim->groups_kernel_i64 = MRL_PICK(plain, sparse_for(true), mrl_overcooked_step_groups_fixed, C_, WPW_, WIDTH_, POTS_, HOLD_, true, 2); \
             sim->groups_name = "mrl_overcooked_step_groups_fixed<" #C_ ", " #WPW_ ", " #WIDTH_ ", " #POTS_ ", " #HOLD_ ", false, 2>"; \
         }                                                                                                           \
     }
@@ -2620,6 +2668,7 @@ mrl_sim *mrl::create_overcooked(const mrl_overcooked_config *cfg, int gpu_id, ui
             MRL_FIXED(25, 4, 5, 2, 9)    // coordination_ring, forced_coordination
             MRL_FIXED(40, 4, 8, 2, 18)   // counter_circuit
 #undef MRL_FIXED
+#undef MRL_PICK
         }
         const uint32_t waves = a.share ? N * kWavesPerBlock : (N + wpw - 1) / wpw;
         const uint32_t blocks = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
