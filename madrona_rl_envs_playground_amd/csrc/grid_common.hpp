@@ -1,6 +1,7 @@
-// Device helpers shared by the grid-world kernels (overcooked2 / "Simplecooked" uses them; overcooked.hip
-// keeps its own copies of the older ones in its anonymous namespace).  Everything here is about ONE wave:
-// in-order LDS hand-offs, pair exchange through DPP, write-through streaming stores, packed byte tables.
+// Device helpers shared by the kitchen-grid kernels (overcooked.hip and simplecooked.hip; the host side of what the
+// two share is kitchen_host.hpp).  Everything here is about ONE wave: in-order LDS hand-offs, pair exchange through
+// DPP, write-through streaming stores, packed byte tables.  The terrain enum is NOT here: the two games number it
+// differently.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -13,14 +14,16 @@ constexpr int kWave = 64;
 
 enum : uint32_t { A_NORTH = 0, A_SOUTH = 1, A_EAST = 2, A_WEST = 3, A_STAY = 4, A_INTERACT = 5 };
 enum : uint32_t { O_NONE = 0, O_TOMATO, O_ONION, O_DISH, O_SOUP };
-constexpr uint32_t kItemNone = 0xFF000000u;  // name NONE, no ingredients, cooking_tick -1
+constexpr uint32_t kItemNone = 0xFF000000u;  // name NONE, no ingredients, cooking_tick -1 (overcooked_env/sim.hpp:59-64)
 constexpr uint32_t kMaxIngredients = 3;
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // Cross-lane hand-off through LDS inside ONE wave: DS instructions of a wave execute in issue order, so a
 // later ds_read sees an earlier ds_write of another lane without any wait; only the compiler must keep the
-// order.  (A wavefront-scope fence also does, but hipcc lowers it with s_waitcnt vmcnt(0).)
+// order -- a compiler-only barrier.  (A wavefront-scope release/acquire fence also does that, but hipcc lowers
+// it with s_waitcnt vmcnt(0): the wave then sits out the full latency of its state stores before it starts the
+// observation passes.)
 __device__ __forceinline__ void wave_lds_sync()
 {
     __builtin_amdgcn_wave_barrier();
@@ -34,8 +37,9 @@ __device__ __forceinline__ uint32_t lds_addr(const void *p)
 
 // Zero-fill of a 256-byte-granular LDS region with ds_write_addtid_b32 (LDS address = M0 + offset + 4 * lane, no
 // address register): 256 bytes per instruction at twice the rate of ds_write_b32 and 1.6x that of ds_write_b128
-// (MI355X_MICROARCH.md, LDS).  M0 is written and restored inside each statement (hipcc reserves it and does not
-// preserve it around asm).  `tile` is wave-uniform.
+// (MI355X_MICROARCH.md, LDS).  The tile is the hot LDS-write traffic of the step kernels: 16 waves per CU x 8.3 KB.
+// M0 is written and restored inside each statement (hipcc reserves it and does not preserve it around asm).
+// `tile` is wave-uniform.
 __device__ __forceinline__ void tile_zero_addtid(uint8_t *tile, uint32_t nbytes)
 {
     const uint32_t total = (nbytes + 255u) >> 8;  // 256-byte pieces
@@ -79,12 +83,18 @@ __device__ __forceinline__ uint32_t swap_pair(uint32_t v)
     return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true);
 }
 
-// 16-byte write-through (sc1) store through a buffer descriptor: the observation slab is written once and
-// not read by the kernel; write-through streams it out while the waves still work instead of leaving dirty
-// lines for the end-of-kernel write-back (measured in overcooked.hip).  Out-of-range offsets are dropped.
-// kPlain: ordinary stores -- for groups whose slab is not whole 128-byte lines, in the multi-step launches and wherever
-// the slab is larger than the Infinity Cache (two write-through halves of a line cost a read-modify-write each there;
-// the L2 merges ordinary ones: overcooked.hip, stream_store_rsrc).
+// 16-byte write-through (sc1) store through a buffer descriptor; out-of-range offsets are dropped.  The observation
+// slab (34 MB per launch at 32768 worlds of Overcooked's cramped_room) is written once and not read again by the
+// kernel, and it is larger than the L2s: with plain stores the dirty lines pile up in L2 and are written back in the
+// end-of-kernel release, which the next launch waits for; write-through (line not kept) streams them out while the
+// waves are still working.  Measured on MI355X, us per launch at 32768 worlds: plain 14.05, nt 13.44, sc1 11.78,
+// sc0 sc1 11.79.
+// kPlain: ordinary stores instead.  Write-through wins while the slab fits the 256 MiB Infinity Cache and whenever a
+// group's slab is whole 128-byte lines (cramped_room, counter_circuit); a group slab that is NOT (1300- or 2340-byte
+// worlds) ends in a line it shares with the next group's wave, and two write-through partial lines that must go out
+// to HBM cost a read-modify-write each: coordination_ring at 262144 worlds 121 us per step write-through, 71 us plain
+// (1 M worlds 534 / 305; asymmetric_advantages 210 / 133 and 894 / 570) -- the L2 merges the halves before it writes
+// back.  The host picks the instantiation (kitchen_host.hpp, plain_store).
 template <bool kPlain = false>
 __device__ __forceinline__ void stream_store_rsrc(__amdgpu_buffer_rsrc_t rsrc, uint32_t byte_offset, const uint4 &v)
 {
@@ -96,9 +106,10 @@ __device__ __forceinline__ void stream_store_rsrc(__amdgpu_buffer_rsrc_t rsrc, u
     __builtin_amdgcn_raw_buffer_store_b128(r, rsrc, (int)byte_offset, 0, kPlain ? 0 : 16);  // aux bit 4 = sc1
 }
 
-// Cell-index delta of a move: NORTH -W, SOUTH +W, EAST +1, WEST -1, STAY / INTERACT 0, packed as signed
-// bytes (byte k = direction k): one 64-bit shift instead of a compare ladder (which hipcc lowers to
-// exec-masked branch trees on divergent lanes).
+// Cell-index delta of a move (overcooked_env/sim.cpp:185-197): NORTH -W, SOUTH +W, EAST +1, WEST -1, STAY / INTERACT 0,
+// packed as signed bytes (byte k = direction k; |W| <= 85 since H >= 3 and H*W <= 255): one 64-bit shift instead of a
+// compare ladder -- hipcc lowers such ladders to exec-masked branch trees, which cost ~20 instructions each on
+// divergent lanes.
 __device__ __forceinline__ int32_t step_of(uint32_t dir, uint64_t deltas)
 {
     return (int32_t)(int8_t)(deltas >> (8u * dir));
@@ -115,7 +126,8 @@ __device__ __forceinline__ uint32_t recipe_of(uint32_t item)
 }
 __device__ __forceinline__ uint32_t count_of(uint32_t item) { return (((item >> 8) & 0xFF) + ((item >> 16) & 0xFF)) & 0xFF; }
 
-// 16-entry byte table held in four scalar registers
+// 16-entry byte table held in four scalar registers: one select and a 64-bit shift instead of an LDS round trip
+// (and no compare ladder, see step_of)
 __device__ __forceinline__ uint32_t lookup16(const uint32_t (&w)[4], uint32_t idx)
 {
     const uint64_t lo = (uint64_t)w[0] | ((uint64_t)w[1] << 32), hi = (uint64_t)w[2] | ((uint64_t)w[3] << 32);

@@ -45,6 +45,8 @@
 //   reward   [P][N]  i32, done [N] i32
 //   obs      [N][P][C][F] u8, F = 5P+16: one contiguous P*C*F block per world
 #include "common.hpp"
+#include "grid_common.hpp"
+#include "kitchen_host.hpp"
 #include "random_policy.hpp"
 #include "world_reset.hpp"
 
@@ -54,19 +56,14 @@
 
 namespace {
 
-constexpr int kWave = 64;
-#ifndef MRL_OVERCOOKED_WPB
-#define MRL_OVERCOOKED_WPB 4
-#endif
-constexpr int kWavesPerBlock = MRL_OVERCOOKED_WPB;
+using namespace mrl_grid;
+
+constexpr int kWavesPerBlock = 4;
 constexpr int kBlock = kWave * kWavesPerBlock;
 constexpr int kRowsPerPass = 128;  // observation rows assembled per LDS tile
 
-enum : uint32_t { A_NORTH = 0, A_SOUTH = 1, A_EAST = 2, A_WEST = 3, A_STAY = 4, A_INTERACT = 5 };
 enum : uint32_t { T_AIR = 0, T_POT, T_COUNTER, T_ONION_SRC, T_TOMATO_SRC, T_DISH_SRC, T_SERVING };
-enum : uint32_t { O_NONE = 0, O_TOMATO, O_ONION, O_DISH, O_SOUP };
-constexpr uint32_t kItemNone = 0xFF000000u;  // name NONE, tick -1 (sim.hpp:59-64)
-constexpr uint32_t kMaxIngredients = 3;
+static_assert(T_AIR == mrl_kitchen::kAir && T_POT == mrl_kitchen::kPot && T_COUNTER == mrl_kitchen::kCounter, "kitchen_host.hpp");
 
 // layout of the constant block (copied into LDS by every workgroup)
 constexpr uint32_t kConstTerrain = 0;    // 256 bytes
@@ -138,18 +135,6 @@ struct StepParams {
     uint32_t pair_exchange;  // mrl_step_many: two players and the pair-exchange (DPP) transition is this simulator's (not forced generic)
 };
 
-__device__ __forceinline__ void wave_lds_sync()
-{
-    // Cross-lane hand-off through LDS inside ONE wave: DS instructions of a wave are executed
-    // in issue order, so a later ds_read sees an earlier ds_write of another lane without any
-    // wait.  All that is needed is that the compiler keeps the order -- a compiler-only
-    // barrier.  (A wavefront-scope release/acquire fence also does that, but hipcc lowers it
-    // with s_waitcnt vmcnt(0): the wave then sits out the full latency of its state stores
-    // before it starts the observation passes.)
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");
-}
-
 // Storing a row's 16 viewer-independent bytes into the LDS tile.  Rows are F = 5P+16 bytes
 // apart, so these 16 bytes are in general not 16-byte aligned, and a DS store off its natural
 // alignment is replayed (cdna_hip_programming.md G17; measured here: one misaligned b128 per
@@ -157,10 +142,6 @@ __device__ __forceinline__ void wave_lds_sync()
 // naturally aligned pieces chosen by the (wave-uniform) alignment class of the address.
 // Written as asm so the compiler cannot fuse the pieces back into one misaligned b128.  LDS
 // operations of a wave execute in order, so later ds_reads of the same wave see these stores.
-__device__ __forceinline__ uint32_t lds_addr(const void *p)
-{
-    return (uint32_t)reinterpret_cast<uintptr_t>(p);  // low 32 bits of a shared pointer = LDS offset
-}
 
 __device__ __forceinline__ void lds_store_tail_a4(uint8_t *ptr, const uint4 &t)  // address % 4 == 0
 {
@@ -233,35 +214,16 @@ __device__ __forceinline__ void lds_store_tail(uint8_t *ptr, const uint4 &t, uin
     }
 }
 
-// 16-byte store of observation bytes.  The observation slab (34 MB per launch at 32768
-// worlds) is written once and not read again by this kernel, and it is larger than the L2s:
-// with plain stores the dirty lines pile up in L2 and are written back in the end-of-kernel
-// release, which the next launch waits for.  sc1 (write-through, line not kept) streams them
-// out while the waves are still working.  Measured on MI355X, us per launch at 32768 worlds:
-// plain 14.05, nt 13.44, sc1 11.78, sc0 sc1 11.79.  MRL_STORE_POLICY (0 plain, 1 nt, 2 sc1,
-// 3 sc0 sc1) exists to re-measure.
-#ifndef MRL_STORE_POLICY
-#define MRL_STORE_POLICY 2
-#endif
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+// 16-byte write-through store of observation bytes in the multi-pass stream-out (why write-through: grid_common.hpp,
+// stream_store_rsrc).  As asm: the flat-address form of the same store.
 __device__ __forceinline__ void stream_store(uint4 *dst, const uint4 &v)
 {
-#if MRL_STORE_POLICY == 0
-    *dst = v;
-#else
     u32x4 r;
     r.x = v.x;
     r.y = v.y;
     r.z = v.z;
     r.w = v.w;
-#if MRL_STORE_POLICY == 1
-    asm volatile("global_store_dwordx4 %0, %1, off nt" : : "v"(dst), "v"(r) : "memory");
-#elif MRL_STORE_POLICY == 2
     asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(dst), "v"(r) : "memory");
-#else
-    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" : : "v"(dst), "v"(r) : "memory");
-#endif
-#endif
 }
 
 __device__ __forceinline__ void nt_store(uint4 *dst, const uint4 &v)
@@ -274,35 +236,10 @@ __device__ __forceinline__ void nt_store(uint4 *dst, const uint4 &v)
     __builtin_nontemporal_store(r, reinterpret_cast<u32x4 *>(dst));
 }
 
-// Cell-index delta of a move (sim.cpp:185-197): NORTH -W, SOUTH +W, EAST +1, WEST -1, STAY and
-// INTERACT 0.  `deltas` packs them as signed bytes (|W| <= 85 since H >= 3 and H*W <= 255),
-// byte k = delta of direction k; one 64-bit shift instead of a compare ladder -- hipcc lowers
-// such ladders to exec-masked branch trees, which cost ~20 instructions each on divergent lanes.
-__device__ __forceinline__ int32_t step_of(uint32_t dir, uint64_t deltas)
-{
-    return (int32_t)(int8_t)(deltas >> (8u * dir));
-}
-
-__device__ __forceinline__ uint32_t recipe_of(uint32_t item)
-{
-    return ((kMaxIngredients + 1) * ((item >> 8) & 0xFF) + ((item >> 16) & 0xFF)) & 15u;
-}
-
-__device__ __forceinline__ uint32_t count_of(uint32_t item) { return (((item >> 8) & 0xFF) + ((item >> 16) & 0xFF)) & 0xFF; }
-
 // The counter/pot/source/serving interaction of one player (sim.cpp:208-358), shared by the
 // generic and the register-resident transition.  `there` is the object on the faced cell
 // (only meaningful for counters and pots), `need` its cooking time and `value` the delivery
 // value of the held soup; returns the player's new held item.
-// 16-entry byte table held in four scalar registers: one select and a 64-bit shift instead of
-// an LDS round trip (and no compare ladder, see step_of)
-__device__ __forceinline__ uint32_t lookup16(const uint32_t (&w)[4], uint32_t idx)
-{
-    const uint64_t lo = (uint64_t)w[0] | ((uint64_t)w[1] << 32), hi = (uint64_t)w[2] | ((uint64_t)w[3] << 32);
-    const uint64_t half = (idx & 8u) ? hi : lo;
-    return (uint32_t)(half >> ((idx & 7u) * 8u)) & 0xFFu;
-}
-
 __device__ __forceinline__ uint32_t interact(const StepParams &p, int32_t need, int32_t value, uint32_t terr, uint32_t held,
                                              uint32_t &there, int32_t &reward)
 {
@@ -374,13 +311,6 @@ __device__ __forceinline__ uint4 cell_tail(const StepParams &p, uint32_t terr, u
     t.z = soup_on | (soup_tom << 8) | (remaining << 16) | (ready << 24);
     t.w = dish | (onion << 8) | (tomato << 16) | ((urgent ? 1u : 0u) << 24);
     return t;
-}
-
-// Value of the neighbouring lane of a pair (lanes 2k and 2k+1 swap): DPP quad_perm [1,0,3,2], no LDS.
-// Called with all lanes enabled.
-__device__ __forceinline__ uint32_t swap_pair(uint32_t v)
-{
-    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true);
 }
 
 // The transition of a whole group at once: lane = (world wl of the group, player q), lane = wl*P + q
@@ -490,28 +420,6 @@ __device__ __forceinline__ void tick_pots(const StepParams &p, const uint8_t *s_
 {
     tick_pots_world(p, s_pots, s_obj + lane * p.C, lane < nw);
 }
-// Diagnostics (make diag -> diag/libmrl_envs_diag.so, never the shipped library): in-kernel stamps
-// for tools/stamps.py and phase ablation.  In the normal build these expand to nothing.
-// kPlain: ordinary stores instead of write-through ones.  Write-through wins while the slab fits the 256 MiB Infinity Cache
-// and whenever a group's slab is whole 128-byte lines (cramped_room, counter_circuit); a group slab that is NOT (1300- or
-// 2340-byte worlds) ends in a line it shares with the next group's wave, and two write-through partial lines that must go out
-// to HBM cost a read-modify-write each: coordination_ring at 262144 worlds 121 us per step write-through, 71 us plain
-// (1 M worlds 534 / 305; asymmetric_advantages 210 / 133 and 894 / 570) -- the L2 merges the halves before it writes back.
-// The host picks the instantiation (overcooked.whole_store: 0 by slab size and alignment, 1 write-through, 2 plain).
-template <bool kPlain = false>
-__device__ __forceinline__ void stream_store_rsrc(__amdgpu_buffer_rsrc_t rsrc, uint32_t byte_offset, const uint4 &v)
-{
-    u32x4 r;
-    r.x = v.x;
-    r.y = v.y;
-    r.z = v.z;
-    r.w = v.w;
-#ifndef MRL_WHOLE_STORE_AUX
-#define MRL_WHOLE_STORE_AUX 16
-#endif
-    __builtin_amdgcn_raw_buffer_store_b128(r, rsrc, (int)byte_offset, 0, kPlain ? 0 : MRL_WHOLE_STORE_AUX);  // aux bit 4 = sc1 (write-through)
-}
-
 // Single-pass encode of a group's observation slab (small layouts; see the call site).
 template <bool kPlain = false>
 __device__ __forceinline__ void observe_whole(const StepParams &p, const uint8_t *s_terrain, const uint32_t *s_obj,
@@ -788,11 +696,7 @@ __device__ __forceinline__ void observe_patch(const StepParams &p, const uint8_t
     // Same box, us per launch with / without (profiles/r04_ae_overcooked_line_rounds_ab.txt): coordination_ring 10.14-10.17 / 10.49-10.50,
     // forced_coordination 10.47 / 10.67, asymmetric_advantages 15.63-15.69 / 15.75-15.80; the aligned layouts are untouched (lshift = 0).
     // Not in the multi-step launches: their ordinary stores meet in the L2 anyway, and the extra round cost them 0.1 us per step.
-#ifndef MRL_NO_LINE_ROUNDS
     const uint32_t lshift = kRestore ? 0u : (uint32_t)(reinterpret_cast<uintptr_t>(gobs + head) >> 4) & 7u;
-#else
-    const uint32_t lshift = 0u;
-#endif
     // (signed chunk indices: a lane in front of the slab reads up to 112 bytes below the tile -- the wave's own state -- and its
     // store offset wraps to 0xFFFFFF90 and more, which the descriptor drops)
     int32_t b0 = -(int32_t)lshift;  // wave-uniform
@@ -877,46 +781,9 @@ __device__ __forceinline__ void tile_zero(const StepParams &p, uint32_t lane, ui
     const uint32_t nchunks = (nw * p.block_bytes + 31u) >> 4;  // covers any start misalignment
     for (uint32_t k = lane; k < nchunks; k += kWave) reinterpret_cast<uint4 *>(tile)[k] = make_uint4(0, 0, 0, 0);
 }
-// Zero-fill of a 256-byte-granular tile with ds_write_addtid_b32 (LDS address = M0 + offset + 4 * lane, no address
-// register): 256 bytes per instruction at twice the rate of ds_write_b32 and 1.6x that of ds_write_b128
-// (MI355X_MICROARCH.md, LDS).  The tile is the hot LDS-write traffic of the kernel: 16 waves per CU x 8.3 KB.
-// M0 is written and restored inside each statement (hipcc reserves it and does not preserve it around asm).
-__device__ __forceinline__ void tile_zero_addtid(uint8_t *tile, uint32_t nbytes)
-{
-    const uint32_t total = (nbytes + 255u) >> 8;  // 256-byte pieces
-    uint32_t base = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_addr(tile));
-    uint32_t keep;
-    const uint32_t zero = 0;
-    uint32_t done = 0;
-    for (; done + 8 <= total; done += 8, base += 2048) {
-        asm volatile("s_mov_b32 %0, m0\n\t"
-                     "s_mov_b32 m0, %1\n\t"
-                     "s_nop 0\n\t"
-                     "ds_write_addtid_b32 %2\n\t"
-                     "ds_write_addtid_b32 %2 offset:256\n\t"
-                     "ds_write_addtid_b32 %2 offset:512\n\t"
-                     "ds_write_addtid_b32 %2 offset:768\n\t"
-                     "ds_write_addtid_b32 %2 offset:1024\n\t"
-                     "ds_write_addtid_b32 %2 offset:1280\n\t"
-                     "ds_write_addtid_b32 %2 offset:1536\n\t"
-                     "ds_write_addtid_b32 %2 offset:1792\n\t"
-                     "s_mov_b32 m0, %0"
-                     : "=&s"(keep)
-                     : "s"(base), "v"(zero)
-                     : "memory");
-    }
-    for (; done < total; done += 1, base += 256) {
-        asm volatile("s_mov_b32 %0, m0\n\t"
-                     "s_mov_b32 m0, %1\n\t"
-                     "s_nop 0\n\t"
-                     "ds_write_addtid_b32 %2\n\t"
-                     "s_mov_b32 m0, %0"
-                     : "=&s"(keep)
-                     : "s"(base), "v"(zero)
-                     : "memory");
-    }
-}
 
+// Diagnostics (make diag -> diag/libmrl_envs_diag.so, never the shipped library): in-kernel stamps
+// for tools/stamps.py and phase ablation.  In the normal build these expand to nothing.
 #ifdef MRL_DIAG
 #define STAMP(k)                                                                                               \
     do {                                                                                                       \
@@ -1129,18 +996,7 @@ __device__ __forceinline__ void step_body(const StepParams &p, const uint32_t bl
     auto store_state = [&]() {
         if (p.share && wib != 0) return;  // the siblings computed the same state
         uint32_t *g_obj = p.cell_obj + (size_t)w0 * C;
-#ifdef MRL_STATE_SC1
-        for (uint32_t i = lane; i < ncells; i += kWave) asm volatile("global_store_dword %0, %1, off sc1" : : "v"(g_obj + i), "v"(s_obj[i]) : "memory");
-        if (active) {
-            const uint32_t world = w0 + wl;
-            asm volatile("global_store_dwordx2 %0, %1, off sc1" : : "v"(p.players + (size_t)w0 * P + lane), "v"(make_uint2(posori, held)) : "memory");
-            asm volatile("global_store_dword %0, %1, off sc1" : : "v"(p.reward + (size_t)q * N + world), "v"(reward_world) : "memory");
-            if (q == 0) {
-                asm volatile("global_store_dword %0, %1, off sc1" : : "v"(p.timestep + world), "v"(t) : "memory");
-                asm volatile("global_store_dword %0, %1, off sc1" : : "v"(p.done + world), "v"(kInit ? 0 : (int32_t)reset_now) : "memory");
-            }
-        }
-#else
+        // (Write-through sc1 stores here were tried: they move the same bytes and gained nothing.)
         // kSparse: a cell word goes back only if it differs from what THIS launch loaded from its address (about one
         // word in nine does per world and step; exact whatever a caller did to the exported tensor between steps).  Words
         // past the register batch (groups of more than 256 cells) are stored as they are.  The host picks the
@@ -1167,7 +1023,6 @@ __device__ __forceinline__ void step_body(const StepParams &p, const uint32_t bl
                 p.done[world] = kInit ? 0 : (int32_t)reset_now;
             }
         }
-#endif
     };
 
     STAMP(3);
@@ -2057,25 +1912,7 @@ __global__ void mrl_overcooked_draw_actions(int32_t *action, uint32_t players, u
     if (i < (size_t)players * n) action[i] = (int32_t)mrl_random_action(seed, step, (uint32_t)(i % n), (uint32_t)(i / n));
 }
 
-__global__ void fill_ids(int32_t *world_id, int32_t *row_id, uint32_t rows, uint32_t n)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < (size_t)rows * n) {
-        world_id[i] = (int32_t)(i % n);
-        row_id[i] = (int32_t)(i / n);
-    }
-}
-
-__global__ void fill_i32(int32_t *dst, int32_t value, size_t count)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) dst[i] = value;
-}
-
-struct OvercookedSim final : mrl_sim {
-    StepParams params{};
-    uint32_t H = 0;
-    uint32_t grid = 0, lds_bytes = 0;
+struct OvercookedSim final : mrl_kitchen::KitchenSim<StepParams> {
     bool generic = false;  // tests: two-player layouts through the any-player-count transition as well
     using StepKernel = void (*)(const StepParams);
     using RolloutKernel = void (*)(const StepParams, uint32_t, uint64_t, uint32_t, int32_t *, const int32_t *);
@@ -2088,78 +1925,23 @@ struct OvercookedSim final : mrl_sim {
     FixedKernel groups_kernel_i64 = nullptr;
     uint32_t groups_grid = 0;
     const char *groups_name = nullptr;
-    void (*fixed_rollout)(const StepParams, uint32_t, uint64_t, uint32_t, int32_t *, const int32_t *) = nullptr;
+    RolloutKernel fixed_rollout = nullptr;
     // the multi-step launches with twice as many worlds per wave (half as many waves: the state lives in LDS / registers for
     // the whole launch, so there is no load phase to hide behind other waves and fewer, fatter waves issue fewer instructions)
-    void (*wide_rollout)(const StepParams, uint32_t, uint64_t, uint32_t, int32_t *, const int32_t *) = nullptr;
+    RolloutKernel wide_rollout = nullptr;
     StepParams wide_params{};
     uint32_t wide_grid = 0, wide_lds = 0;
     const char *fixed_name = nullptr;
-    int32_t *action = nullptr, *active = nullptr, *mask = nullptr;
-    int32_t *world_id = nullptr, *agent_id = nullptr, *loc_world_id = nullptr, *loc_id = nullptr;
-    uint8_t *own_obs = nullptr;  // the OBS_WORLD_MAJOR buffer; params.obs points elsewhere while the output is redirected
+    uint8_t *pending_dest = nullptr;  // mrl_step_many: the slot of the step just launched
 
-    // The kernels take the slab's address from the launch arguments and never read it back, so writing a step's
-    // observations into a caller's slot (a rollout buffer) instead of the exported tensor is a different pointer in
-    // the same launch: same bytes, same stores.
-    uint64_t observation_bytes() const override { return (uint64_t)num_worlds * params.block_bytes; }
-    uint64_t set_observation_output(void *out) override
+    void ring_changed(uint8_t *obs, uint64_t stride, uint32_t slots) override
     {
-        set_observation_ring(out, 0, 1);
-        return observation_bytes();
-    }
-    // a ring of slots: the step number `ring_pos` since this call writes slot ring_pos % slots (host-side count: a
-    // launch captured in a HIP graph keeps the slot it was captured with)
-    uint8_t *ring_base = nullptr;
-    uint64_t ring_stride = 0;
-    uint32_t ring_slots = 1;
-    uint64_t ring_pos = 0;
-    // Slots that do not start on 16-byte boundaries (a dense (T, N, P, H, W, F) buffer whose N x P x H x W x F is not a
-    // multiple of 16: coordination_ring at 1001 worlds) are STAGED: the kernels stream a slab out in 16-byte chunks from a
-    // 16-byte aligned base, so the step writes a slab of the simulator's (`staging`, allocated at the first such call; the
-    // exported tensor stays untouched) and a device-to-device copy behind the launch moves it to the slot -- one more pass
-    // over the slab per step, and the multi-step launches run one launch per step.  Aligned slots cost nothing.
-    bool staged = false;
-    uint8_t *staging = nullptr, *pending_dest = nullptr;
-    void set_observation_ring(void *base, uint64_t stride_bytes, uint32_t slots) override
-    {
-        ring_base = base ? static_cast<uint8_t *>(base) : own_obs;
-        ring_stride = base ? stride_bytes : 0;
-        ring_slots = base && slots > 1 ? slots : 1;
-        ring_pos = 0;
-        staged = base && ((reinterpret_cast<uintptr_t>(base) & 15u) != 0 || (ring_slots > 1 && (ring_stride & 15u) != 0));
-        if (staged && !staging) staging = arena.alloc<uint8_t>(observation_bytes(), false);
         for (StepParams *q : {&params, &wide_params}) {
-            q->obs = staged ? staging : ring_base;
-            q->ring_stride = staged ? 0 : ring_stride;
-            q->ring_slots = staged ? 1 : ring_slots;
+            q->obs = obs;
+            q->ring_stride = stride;
+            q->ring_slots = slots;
             q->ring_first = 0;
         }
-    }
-    // staged slots: the slab just written -> the caller's slot, behind the launch on the same stream
-    void deliver(uint8_t *dest, hipStream_t stream)
-    {
-        if (staged && dest) MRL_HIP(hipMemcpyAsync(dest, staging, observation_bytes(), hipMemcpyDeviceToDevice, stream));
-    }
-
-    // mrl_reset_worlds: world 0 as construction left it, copied over the masked worlds (world_reset.hpp).  The observations go
-    // where the most recent step wrote -- before any step since the output was set, where the next step will write.
-    mrl::FreshWorldOwner fresh;
-    void reset_worlds(const uint8_t *mask, hipStream_t stream) override
-    {
-        if (staged)
-            throw std::runtime_error("mrl_reset_worlds: the observation output is a staged slot (off a 16-byte boundary); a reset writes "
-                                     "observations in place only -- use an aligned slot or the simulator's own tensor");
-        const uint64_t slot = ring_pos ? (ring_pos - 1) % ring_slots : 0;
-        fresh.launch(mask, num_worlds, ring_base + (size_t)slot * ring_stride, stream);
-    }
-    // the slot(s) of the next `steps` steps: single-step launches get the slot as their `obs`, multi-step ones the first index
-    uint8_t *take_slots(uint32_t steps, uint32_t *first)
-    {
-        const uint32_t at = (uint32_t)(ring_pos % ring_slots);
-        ring_pos += steps;
-        if (first) *first = at;
-        return ring_base + (size_t)at * ring_stride;
     }
 
     // this step's parameters as the generic step kernel takes them (mrl_step_many)
@@ -2168,7 +1950,7 @@ struct OvercookedSim final : mrl_sim {
         StepParams a = params;
         a.actions = actions ? actions : action;
         pending_dest = take_slots(1, nullptr);  // (staged: delivered by step_many_overcooked behind the shared launch)
-        a.obs = staged ? staging : pending_dest;
+        a.obs = step_obs(pending_dest);
         a.ring_slots = 1;
         a.per_xcd = grid >> 3;
         a.pair_exchange = (a.P == 2 && !generic) ? 1u : 0u;
@@ -2180,7 +1962,7 @@ struct OvercookedSim final : mrl_sim {
         StepParams a = params;
         a.actions = actions ? actions : action;
         uint8_t *const dest = init ? nullptr : take_slots(1, nullptr);
-        if (!init) a.obs = staged ? staging : dest;
+        if (!init) a.obs = step_obs(dest);
         a.ring_slots = 1;  // a single step writes exactly its `obs`
         a.per_xcd = ((!init && groups_kernel) ? groups_grid : grid) >> 3;
         const void *hot_actions = a.actions64 ? static_cast<const void *>(a.actions64) : static_cast<const void *>(a.actions);
@@ -2213,26 +1995,26 @@ struct OvercookedSim final : mrl_sim {
         params.actions64 = keep;
         return true;
     }
-    void phase2(const uint32_t *, hipStream_t) override {}
+    // all steps of a call in one launch, where the group's slab fits one LDS tile (rollout_body): actions drawn in the
+    // kernel (action_seq == nullptr) or read from the caller's sequence
+    bool launch_rollout(uint32_t num_steps, uint64_t seed, uint32_t first_step, const int32_t *action_seq, hipStream_t stream)
+    {
+        if (!params.whole || staged) return false;  // (staged slots: one launch + one copy per step)
+        take_slots(num_steps, &params.ring_first);
+        wide_params.ring_first = params.ring_first;
+        if (wide_rollout)
+            hipLaunchKernelGGL(wide_rollout, dim3(wide_grid), dim3(kBlock), wide_lds, stream, wide_params, num_steps, seed, first_step, action,
+                               action_seq);
+        else
+            hipLaunchKernelGGL(fixed_rollout ? fixed_rollout : generic_rollout, dim3(grid), dim3(kBlock), lds_bytes, stream, params, num_steps,
+                               seed, first_step, action, action_seq);
+        MRL_HIP(hipGetLastError());
+        return true;
+    }
 
     void rollout_random(uint32_t num_steps, uint64_t seed, uint32_t first_step, hipStream_t stream) override
     {
-        if (num_steps == 0) return;
-        if (params.whole && !staged) {
-            take_slots(num_steps, &params.ring_first);
-            wide_params.ring_first = params.ring_first;
-            if (wide_rollout)
-                hipLaunchKernelGGL(wide_rollout, dim3(wide_grid), dim3(kWavesPerBlock * kWave), wide_lds, stream, wide_params, num_steps,
-                                   seed, first_step, action, (const int32_t *)nullptr);
-            else if (fixed_rollout)
-                hipLaunchKernelGGL(fixed_rollout, dim3(grid), dim3(kWavesPerBlock * kWave), lds_bytes, stream, params, num_steps, seed,
-                                   first_step, action, (const int32_t *)nullptr);
-            else
-                hipLaunchKernelGGL(generic_rollout, dim3(grid), dim3(kWavesPerBlock * kWave), lds_bytes, stream, params, num_steps, seed,
-                                   first_step, action, (const int32_t *)nullptr);
-            MRL_HIP(hipGetLastError());
-            return;
-        }
+        if (num_steps == 0 || launch_rollout(num_steps, seed, first_step, nullptr, stream)) return;
         const size_t count = (size_t)params.P * num_worlds;
         for (uint32_t k = 0; k < num_steps; k++) {
             hipLaunchKernelGGL(mrl_overcooked_draw_actions, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream,
@@ -2243,76 +2025,24 @@ struct OvercookedSim final : mrl_sim {
 
     void step_sequence(const int32_t *actions, uint32_t num_steps, hipStream_t stream) override
     {
-        if (num_steps == 0) return;
-        if (params.whole && !staged) {
-            take_slots(num_steps, &params.ring_first);
-            wide_params.ring_first = params.ring_first;
-            if (wide_rollout)
-                hipLaunchKernelGGL(wide_rollout, dim3(wide_grid), dim3(kWavesPerBlock * kWave), wide_lds, stream, wide_params, num_steps,
-                                   0ull, 0u, action, actions);
-            else if (fixed_rollout)
-                hipLaunchKernelGGL(fixed_rollout, dim3(grid), dim3(kWavesPerBlock * kWave), lds_bytes, stream, params, num_steps, 0ull, 0u,
-                                   action, actions);
-            else
-                hipLaunchKernelGGL(generic_rollout, dim3(grid), dim3(kWavesPerBlock * kWave), lds_bytes, stream, params, num_steps, 0ull, 0u,
-                                   action, actions);
-            MRL_HIP(hipGetLastError());
-            return;
-        }
+        if (num_steps == 0 || launch_rollout(num_steps, 0, 0, actions, stream)) return;
         mrl_sim::step_sequence(actions, num_steps, stream);
-    }
-
-    void ensure_ids()
-    {
-        if (world_id) return;
-        const uint32_t P = params.P, N = num_worlds, rows = params.rows;
-        world_id = arena.alloc<int32_t>((size_t)P * N, false);
-        agent_id = arena.alloc<int32_t>((size_t)P * N, false);
-        loc_world_id = arena.alloc<int32_t>((size_t)rows * N, false);
-        loc_id = arena.alloc<int32_t>((size_t)rows * N, false);
-        const size_t a = (size_t)P * N, b = (size_t)rows * N;
-        hipLaunchKernelGGL(fill_ids, dim3((unsigned)((a + 255) / 256)), dim3(256), 0, 0, world_id, agent_id, P, N);
-        hipLaunchKernelGGL(fill_ids, dim3((unsigned)((b + 255) / 256)), dim3(256), 0, 0, loc_world_id, loc_id, rows, N);
-        MRL_HIP(hipGetLastError());
-        MRL_HIP(hipDeviceSynchronize());
     }
 
     bool tensor(int slot, mrl_tensor_desc *out) override
     {
-        const int64_t P = params.P, N = num_worlds, C = params.C, F = params.F, W = params.W;
         switch (slot) {
-        case MRL_OVERCOOKED_DONE: *out = mrl::make_desc(params.done, MRL_INT32, device, {N}); return true;
-        case MRL_OVERCOOKED_ACTIVE_AGENT: *out = mrl::make_desc(active, MRL_INT32, device, {P, N}); return true;
-        case MRL_OVERCOOKED_ACTION: *out = mrl::make_desc(action, MRL_INT32, device, {P, N, 1}); return true;
-        case MRL_OVERCOOKED_OBSERVATION:
-            *out = mrl::make_desc(own_obs, MRL_INT8, device, {P * C, N, F}, {F, P * C * F, 1});
-            return true;
-        case MRL_OVERCOOKED_ACTION_MASK: *out = mrl::make_desc(mask, MRL_INT32, device, {P, N, 6}); return true;
-        case MRL_OVERCOOKED_REWARD: *out = mrl::make_desc(params.reward, MRL_INT32, device, {P, N}); return true;
-        case MRL_OVERCOOKED_WORLD_ID: ensure_ids(); *out = mrl::make_desc(world_id, MRL_INT32, device, {P, N}); return true;
-        case MRL_OVERCOOKED_AGENT_ID: ensure_ids(); *out = mrl::make_desc(agent_id, MRL_INT32, device, {P, N}); return true;
-        case MRL_OVERCOOKED_LOCATION_WORLD_ID:
-            ensure_ids();
-            *out = mrl::make_desc(loc_world_id, MRL_INT32, device, {P * C, N});
-            return true;
-        case MRL_OVERCOOKED_LOCATION_ID: ensure_ids(); *out = mrl::make_desc(loc_id, MRL_INT32, device, {P * C, N}); return true;
-        case MRL_OVERCOOKED_OBS_WORLD_MAJOR:
-            *out = mrl::make_desc(own_obs, MRL_INT8, device, {N, P, (int64_t)H, W, F});
-            return true;
-        case MRL_OVERCOOKED_STATE_PLAYERS: *out = mrl::make_desc(params.players, MRL_UINT8, device, {N, P, 8}); return true;
-        case MRL_OVERCOOKED_STATE_OBJECTS: *out = mrl::make_desc(params.cell_obj, MRL_UINT8, device, {N, C, 4}); return true;
-        case MRL_OVERCOOKED_STATE_TIMESTEP: *out = mrl::make_desc(params.timestep, MRL_INT32, device, {N}); return true;
+        case MRL_OVERCOOKED_STATE_TIMESTEP: *out = mrl::make_desc(params.timestep, MRL_INT32, device, {(int64_t)num_worlds}); return true;
 #ifdef MRL_DIAG
         case 14:
             if (!params.stamps) return false;
             *out = mrl::make_desc(params.stamps, MRL_UINT8, device, {(int64_t)grid * kWavesPerBlock * 16 * 8});
             return true;
 #endif
-        default: return false;
+        default: return common_tensor(slot, out);
         }
     }
 
-    size_t action_elems() const override { return (size_t)params.P * num_worlds; }
     void launch_shape(uint32_t out[4]) const override
     {
         out[0] = groups_kernel ? groups_grid : grid;
@@ -2341,58 +2071,19 @@ struct OvercookedSim final : mrl_sim {
 
 mrl_sim *mrl::create_overcooked(const mrl_overcooked_config *cfg, int gpu_id, uint32_t num_worlds)
 {
-    if (!cfg || !cfg->terrain || !cfg->start_player_x || !cfg->start_player_y || !cfg->recipe_values ||
-        !cfg->recipe_times) {
-        set_error("overcooked: null config field");
-        throw HipError{MRL_ERR_INVALID};
-    }
-    const int64_t H = cfg->height, W = cfg->width, P = cfg->num_players;
-    if (H < 3 || W < 3 || H * W > 255) {
-        set_error("overcooked: height*width must be 9..255 (the reference stores the cell count in a uint8, "
-                  "src/overcooked_env/sim.hpp:86), got %lldx%lld",
-                  (long long)H, (long long)W);
-        throw HipError{MRL_ERR_INVALID};
-    }
-    if (P < 1 || P > 64) {
-        set_error("overcooked: num_players must be 1..64 (MAX_NUM_PLAYERS), got %lld", (long long)P);
-        throw HipError{MRL_ERR_INVALID};
-    }
-    if (num_worlds == 0) {
-        set_error("overcooked: num_worlds must be > 0");
-        throw HipError{MRL_ERR_INVALID};
-    }
-    const int64_t C = H * W;
-    alignas(4) uint8_t consts[kConstBytes];
-    memset(consts, 0, sizeof(consts));
-    uint32_t num_pots = 0;
-    for (int64_t c = 0; c < C; c++) {
-        const int64_t t = cfg->terrain[c];
-        if (t < 0 || t > 6) {
-            set_error("overcooked: terrain[%lld] = %lld is not a TerrainT value", (long long)c, (long long)t);
-            throw HipError{MRL_ERR_INVALID};
-        }
-        const int64_t x = c % W, y = c / W;
-        if (t == T_AIR && (x == 0 || y == 0 || x == W - 1 || y == H - 1)) {
-            set_error("overcooked: walkable cell on the grid border at (%lld,%lld); the step indexes neighbours "
-                      "without bounds checks (src/overcooked_env/sim.cpp:185-197)",
-                      (long long)x, (long long)y);
-            throw HipError{MRL_ERR_INVALID};
-        }
-        consts[kConstTerrain + c] = (uint8_t)t;
-        if (t == T_POT) consts[kConstPots + num_pots++] = (uint8_t)c;
-    }
+    const mrl_kitchen::Kitchen k = mrl_kitchen::read_config(
+        cfg, num_worlds,
+        {"overcooked", 255, "the reference stores the cell count in a uint8, src/overcooked_env/sim.hpp:86", 64, "MAX_NUM_PLAYERS",
+         "src/overcooked_env/sim.cpp:185-197"});
+    const int64_t H = k.H, W = k.W, P = k.P, C = k.C;
+    const uint32_t num_pots = k.num_pots;
+    alignas(4) uint8_t consts[kConstBytes] = {};
+    memcpy(consts + kConstTerrain, k.terrain, 256);
+    memcpy(consts + kConstPots, k.pots, 256);
+    memcpy(consts + kConstStart, k.start, 64);
     for (int r = 0; r < 16; r++) {
         consts[kConstTimes + r] = (uint8_t)cfg->recipe_times[r];
         consts[kConstValues + r] = (uint8_t)cfg->recipe_values[r];
-    }
-    for (int64_t q = 0; q < P; q++) {
-        const int64_t x = cfg->start_player_x[q], y = cfg->start_player_y[q];
-        if (x < 1 || y < 1 || x >= W - 1 || y >= H - 1) {
-            set_error("overcooked: start position of player %lld (%lld,%lld) is not an interior cell", (long long)q,
-                      (long long)x, (long long)y);
-            throw HipError{MRL_ERR_INVALID};
-        }
-        consts[kConstStart + q] = (uint8_t)(y * W + x);
     }
 
     bind_device(gpu_id);
@@ -2417,7 +2108,7 @@ mrl_sim *mrl::create_overcooked(const mrl_overcooked_config *cfg, int gpu_id, ui
         a.soup_pickup_rew = (uint8_t)cfg->soup_pickup_rew;
         a.horizon = cfg->horizon;
         a.num_pots = num_pots;
-        a.deltas = (uint64_t)(uint8_t)(int8_t)(-W) | ((uint64_t)(uint8_t)(int8_t)W << 8) | (1ull << 16) | (0xFFull << 24);
+        a.deltas = pack_deltas(W);
         memcpy(a.times_w, consts + kConstTimes, 16);
         memcpy(a.values_w, consts + kConstValues, 16);
         memcpy(&a.pots_w, consts + kConstPots, 4);
@@ -2512,53 +2203,13 @@ mrl_sim *mrl::create_overcooked(const mrl_overcooked_config *cfg, int gpu_id, ui
             wpw >>= 1;
         sim->lds_bytes = layout(wpw) + (uint32_t)mrl::debug_get("overcooked.lds_pad", 0);  // the pad: residency experiments
         // p.direct (patch_direct): holder cells = counters / pots next to a walkable cell; players must start on walkable cells
-        std::vector<uint32_t> holders;  // cell | is_pot << 8
-        for (int64_t c = 0; c < C; c++) {
-            const uint32_t t = consts[kConstTerrain + c];
-            if (t != T_COUNTER && t != T_POT) continue;
-            const int64_t x = c % W, y = c / W;
-            bool faced = false;
-            if (x > 0 && consts[kConstTerrain + c - 1] == T_AIR) faced = true;
-            if (x + 1 < W && consts[kConstTerrain + c + 1] == T_AIR) faced = true;
-            if (y > 0 && consts[kConstTerrain + c - W] == T_AIR) faced = true;
-            if (y + 1 < H && consts[kConstTerrain + c + W] == T_AIR) faced = true;
-            if (faced) holders.push_back((uint32_t)c | (t == T_POT ? 0x100u : 0u));
-        }
-        // table of a group of `gw` worlds: round 0 keeps lanes [0, gw * P) for the players
-        auto hold_table = [&](uint32_t gw) {
-            std::vector<uint32_t> tab;
-            const uint32_t free0 = (uint32_t)kWave - std::min<uint32_t>((uint32_t)kWave, gw * a.P);
-            uint32_t s = 0;
-            for (uint32_t l = 0; l < gw; l++)
-                for (const uint32_t h : holders) {
-                    const uint32_t c = h & 0xFFu;
-                    const uint32_t slot = s < free0 ? gw * a.P + s : (uint32_t)kWave + (s - free0);
-                    if (tab.size() <= slot) tab.resize(slot + 1, 0u);
-                    tab[slot] = (l * a.block_bytes + c * a.F) | ((l * a.C + c) << 16) | (1u << 30) | ((h >> 8) << 31);
-                    s++;
-                }
-            if (tab.empty()) tab.resize(1, 0u);
-            return tab;
-        };
-        {
-            bool starts_walkable = true;
-            for (int64_t q = 0; q < P; q++) starts_walkable = starts_walkable && consts[kConstTerrain + consts[kConstStart + q]] == T_AIR;
-            a.direct = (a.patch && starts_walkable && hold_table(a.wpw).size() <= (size_t)kHoldPerLane * kWave &&
-                        !mrl::debug_get("overcooked.no_direct", 0))
-                           ? 1u
-                           : 0u;
-        }
-        // Stores of the single-pass stream-out (stream_store_rsrc): write-through, except where the slab is larger than the
-        // Infinity Cache AND a group's slab is not whole 128-byte lines -- then ordinary stores, which the L2 merges
-        // (the multi-step launches rewrite the same lines step after step and do better with ordinary stores for such groups
-        // at every size: asymmetric_advantages 32768 worlds 10.6 -> 9.3 us per step, 65536 21.2 -> 18.6, coordination_ring
-        // 6.61 -> 6.44; the single step inside the cache does not: coordination_ring 10.5 vs 12.0, asymmetric_advantages 15.6 vs 17.3)
-        const auto plain_for = [&](uint32_t group_worlds, bool multi_step) {
-            const int64_t knob = mrl::debug_get("overcooked.whole_store", 0);  // 0 by slab size and alignment, 1 write-through, 2 plain
-            const uint64_t slab = (uint64_t)N * a.block_bytes;
-            const bool whole_lines = ((uint64_t)group_worlds * a.block_bytes) % 64u == 0;  // (64: Simplecooked random0's 8000-byte groups, half a 128-byte line off, do not care)
-            return knob ? knob == 2 : (!whole_lines && (multi_step || slab > (256ull << 20)));
-        };
+        const std::vector<uint32_t> holders = mrl_kitchen::holder_cells(k);
+        const auto hold_table = [&](uint32_t gw) { return mrl_kitchen::hold_table(k, holders, gw, a.F); };
+        a.direct = (a.patch && mrl_kitchen::starts_walkable(k) && hold_table(a.wpw).size() <= (size_t)kHoldPerLane * kWave &&
+                    !mrl::debug_get("overcooked.no_direct", 0))
+                       ? 1u
+                       : 0u;
+        const auto plain_for = [&](uint32_t group_worlds, bool multi_step) { return mrl_kitchen::plain_store(N, a.block_bytes, group_worlds, multi_step); };
         const bool plain = plain_for(wpw, false), plain_multi = plain_for(wpw, true);
         // Cell words written back by the single step: only those that differ from what the launch loaded (kSparse), or all.
         // Changed-only takes 0.2 us off the headline launch and 3-6 % off every one-group-per-wave launch measured, in and
@@ -2575,13 +2226,14 @@ mrl_sim *mrl::create_overcooked(const mrl_overcooked_config *cfg, int gpu_id, ui
             if (slab > (256ull << 20) && (uint64_t)wpw * a.block_bytes > 8320u) return false;
             return two_groups ? slab > (128ull << 20) : true;
         };
+// the (store flavour, write-back flavour) instantiation of a step kernel
+#define MRL_PICK(plain_, sparse_, kernel_, ...)                                                                      \
+    ((plain_) ? ((sparse_) ? &kernel_<__VA_ARGS__, true, true> : &kernel_<__VA_ARGS__, true, false>)                \
+              : ((sparse_) ? &kernel_<__VA_ARGS__, false, true> : &kernel_<__VA_ARGS__, false, false>))
         {
             const bool pairs = a.P == 2 && !sim->generic;  // two-player layouts (all five standard ones) exchange through DPP instead of LDS
             const bool sparse = sparse_for(false);
-            sim->generic_step = pairs ? (plain ? (sparse ? &mrl_overcooked_step<false, 2, true, true> : &mrl_overcooked_step<false, 2, true, false>)
-                                               : (sparse ? &mrl_overcooked_step<false, 2, false, true> : &mrl_overcooked_step<false, 2, false, false>))
-                                      : (plain ? (sparse ? &mrl_overcooked_step<false, 0, true, true> : &mrl_overcooked_step<false, 0, true, false>)
-                                               : (sparse ? &mrl_overcooked_step<false, 0, false, true> : &mrl_overcooked_step<false, 0, false, false>));
+            sim->generic_step = pairs ? MRL_PICK(plain, sparse, mrl_overcooked_step, false, 2) : MRL_PICK(plain, sparse, mrl_overcooked_step, false, 0);
             sim->generic_rollout = pairs ? (plain_multi ? &mrl_overcooked_rollout<2, true> : &mrl_overcooked_rollout<2, false>)
                                          : (plain_multi ? &mrl_overcooked_rollout<0, true> : &mrl_overcooked_rollout<0, false>);
         }
@@ -2627,10 +2279,6 @@ mrl_sim *mrl::create_overcooked(const mrl_overcooked_config *cfg, int gpu_id, ui
                        a.off_cur == f.off_cur && a.off_flags == f.off_flags && a.off_terr == f.off_terr && a.off_list == f.off_list &&
                        a.off_tile == f.off_tile && a.lds_wave_stride == f.stride && !mrl::debug_get("overcooked.no_fixed", 0);
             };
-// the (store flavour, write-back flavour) instantiation of a specialised kernel
-#define MRL_PICK(plain_, sparse_, kernel_, ...)                                                                      \
-    ((plain_) ? ((sparse_) ? &kernel_<__VA_ARGS__, true, true> : &kernel_<__VA_ARGS__, true, false>)                \
-              : ((sparse_) ? &kernel_<__VA_ARGS__, false, true> : &kernel_<__VA_ARGS__, false, false>))
 #define MRL_FIXED(C_, WPW_, WIDTH_, POTS_, HOLD_)                                                                    \
     if (!sim->fixed_kernel && matches(C_, WPW_, WIDTH_, POTS_, HOLD_)) {                                            \
         sim->fixed_kernel = MRL_PICK(plain, sparse_for(false), mrl_overcooked_step_fixed, C_, WPW_, WIDTH_, POTS_, HOLD_, false);  \
@@ -2661,7 +2309,6 @@ mrl_sim *mrl::create_overcooked(const mrl_overcooked_config *cfg, int gpu_id, ui
             const uint64_t wg_per_cu = std::min<uint64_t>(8, std::max<uint64_t>(1, (160u * 1024u) / std::max<uint32_t>(sim->lds_bytes, 1u)));
             const uint64_t waves_at_once = (uint64_t)cus * wg_per_cu * kWavesPerBlock;
             const int64_t groups = groups_knob ? groups_knob : (ngroups > waves_at_once + waves_at_once / 8 ? 2 : 1);
-            // the five standard layouts: cells, worlds per wave, grid width, pots
             // the five standard layouts: cells, worlds per wave, grid width, pots, holder cells
             MRL_FIXED(20, 8, 5, 1, 6)    // cramped_room
             MRL_FIXED(45, 4, 9, 2, 14)   // asymmetric_advantages
@@ -2682,43 +2329,24 @@ mrl_sim *mrl::create_overcooked(const mrl_overcooked_config *cfg, int gpu_id, ui
 #ifdef MRL_DIAG
         if (mrl::debug_get("stamps", 0)) a.stamps = sim->arena.alloc<unsigned long long>((size_t)sim->grid * kWavesPerBlock * 16);
 #endif
-        uint32_t *d_consts = sim->arena.alloc<uint32_t>(kConstBytes / 4, false);
-        MRL_HIP(hipMemcpy(d_consts, consts, kConstBytes, hipMemcpyHostToDevice));
-        a.consts = d_consts;
+        a.consts = mrl_kitchen::upload(sim->arena, reinterpret_cast<const uint32_t *>(consts), kConstBytes / 4);
         a.cell_obj = sim->arena.alloc<uint32_t>((size_t)N * C);
         a.players = sim->arena.alloc<uint2>((size_t)N * P);
         a.timestep = sim->arena.alloc<int32_t>(N);
         a.reward = sim->arena.alloc<int32_t>((size_t)N * P);
         a.done = sim->arena.alloc<int32_t>(N);
-        a.obs = sim->arena.alloc<uint8_t>((size_t)N * a.block_bytes, false);
-        sim->own_obs = a.obs;
-        sim->ring_base = a.obs;
-        a.ring_stride = 0;
-        a.ring_slots = 1;
-        a.ring_first = 0;
-        {
-            // per row of a group: where its terrain one-hot byte goes in the tile (channel 5P + t - 1, sim.cpp:642-645)
-            a.terr_entries = a.wpw * a.rows;
-            std::vector<uint16_t> off(a.terr_entries, 0);
-            if (a.patch)
-                for (uint32_t l = 0; l < a.wpw; l++)
-                    for (uint32_t v = 0; v < a.P; v++)
-                        for (uint32_t c = 0; c < a.C; c++) {
-                            const uint32_t t = consts[kConstTerrain + c];
-                            if (t != T_AIR) off[l * a.rows + v * a.C + c] = (uint16_t)(l * a.block_bytes + (v * a.C + c) * a.F + 5 * a.P + t - 1);
-                        }
-            uint16_t *d_off = sim->arena.alloc<uint16_t>(a.terr_entries, false);
-            MRL_HIP(hipMemcpy(d_off, off.data(), a.terr_entries * sizeof(uint16_t), hipMemcpyHostToDevice));
-            a.terr_off = d_off;
-        }
-        auto upload_hold = [&](StepParams &dst, uint32_t gw) {
+        sim->alloc_outputs();
+        // the tables of a group of `gw` worlds: per row, where its terrain one-hot byte goes in the tile (channel 5P + t - 1,
+        // sim.cpp:642-645; only the patching encode reads it), and the group's holder cells
+        const auto upload_tables = [&](StepParams &dst, uint32_t gw) {
+            dst.terr_entries = gw * a.rows;
+            dst.terr_off = mrl_kitchen::upload(sim->arena, a.patch ? mrl_kitchen::terrain_offsets(k, gw, a.F, 1u << T_AIR)
+                                                                   : std::vector<uint16_t>(dst.terr_entries, 0));
             const std::vector<uint32_t> tab = hold_table(gw);
-            uint32_t *d_tab = sim->arena.alloc<uint32_t>(tab.size(), false);
-            MRL_HIP(hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            dst.hold_tab = d_tab;
+            dst.hold_tab = mrl_kitchen::upload(sim->arena, tab);
             dst.hold_entries = (uint32_t)tab.size();
         };
-        upload_hold(a, a.wpw);
+        upload_tables(a, a.wpw);
         // Multi-step launches of the standard layouts: groups twice as wide where the table of terrain offsets and the
         // LDS of two workgroups per CU allow (measured in DESIGN.md 4.1; mrl_debug_set overcooked.wide_rollout 1 = never)
         if (sim->fixed_rollout && mrl::debug_get("overcooked.wide_rollout", 0) != 1) {
@@ -2743,29 +2371,12 @@ mrl_sim *mrl::create_overcooked(const mrl_overcooked_config *cfg, int gpu_id, ui
                 sim->wide_lds = kConstBytes + kWavesPerBlock * stride;
                 sim->wide_grid = (((wide_waves + kWavesPerBlock - 1) / kWavesPerBlock) + 7u) & ~7u;
                 sim->wide_params.per_xcd = sim->wide_grid >> 3;
-                std::vector<uint16_t> off((size_t)rw * a.rows, 0);
-                for (uint32_t l = 0; l < rw; l++)
-                    for (uint32_t v = 0; v < a.P; v++)
-                        for (uint32_t c = 0; c < a.C; c++) {
-                            const uint32_t t = consts[kConstTerrain + c];
-                            if (t != T_AIR) off[l * a.rows + v * a.C + c] = (uint16_t)(l * a.block_bytes + (v * a.C + c) * a.F + 5 * a.P + t - 1);
-                        }
-                uint16_t *d_off = sim->arena.alloc<uint16_t>(off.size(), false);
-                MRL_HIP(hipMemcpy(d_off, off.data(), off.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-                sim->wide_params.terr_off = d_off;
-                upload_hold(sim->wide_params, rw);
+                upload_tables(sim->wide_params, rw);
                 if (sim->wide_lds > 65536)
                     MRL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sim->wide_rollout), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                 (int)sim->wide_lds));
             }
         }
-        sim->action = sim->arena.alloc<int32_t>((size_t)N * P);
-        sim->active = sim->arena.alloc<int32_t>((size_t)N * P, false);
-        sim->mask = sim->arena.alloc<int32_t>((size_t)N * P * 6, false);
-        const size_t na = (size_t)N * P, nm = na * 6;
-        hipLaunchKernelGGL(fill_i32, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, 0, sim->active, 1, na);
-        hipLaunchKernelGGL(fill_i32, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, 0, sim->mask, 1, nm);
-        MRL_HIP(hipGetLastError());
         // Sim::Sim (sim.cpp:556-659): reset state + first observation
         sim->launch(true, nullptr, 0);
         MRL_HIP(hipDeviceSynchronize());

@@ -32,6 +32,7 @@
 //   obs [N][P][C][F] u8, one contiguous block per world.
 #include "common.hpp"
 #include "grid_common.hpp"
+#include "kitchen_host.hpp"
 #include "random_policy.hpp"
 #include "world_reset.hpp"
 
@@ -47,6 +48,7 @@ constexpr int kWavesPerBlock = 4;
 constexpr int kBlock = kWave * kWavesPerBlock;
 
 enum : uint32_t { T_AIR = 0, T_POT, T_COUNTER, T_ONION_SRC, T_DISH_SRC, T_SERVING, T_TOMATO_SRC };  // sim.hpp:40
+static_assert(T_AIR == mrl_kitchen::kAir && T_POT == mrl_kitchen::kPot && T_COUNTER == mrl_kitchen::kCounter, "kitchen_host.hpp");
 
 constexpr uint32_t kMaxCells = 100, kMaxPlayers = 2;  // MAX_SIZE, MAX_NUM_PLAYERS (sim.hpp:12-13)
 // constant block copied into LDS by every workgroup
@@ -812,81 +814,26 @@ __global__ void __launch_bounds__(kBlock) mrl_simplecooked_rollout_fixed(const S
     rollout_body<kPlain>(fixed_simple_params<kC, kW, kWidth, kPots, kHold>(p), num_steps, seed, first_step, action_seq);
 }
 
-__global__ void fill_ids(int32_t *world_id, int32_t *row_id, uint32_t rows, uint32_t n)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < (size_t)rows * n) {
-        world_id[i] = (int32_t)(i % n);
-        row_id[i] = (int32_t)(i / n);
-    }
-}
-
-__global__ void fill_i32(int32_t *dst, int32_t value, size_t count)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) dst[i] = value;
-}
-
-struct SimplecookedSim final : mrl_sim {
-    SimpleParams params{};
-    uint8_t *own_obs = nullptr;  // the OBS_WORLD_MAJOR buffer; params.obs points elsewhere while the output is redirected
-    uint64_t observation_bytes() const override { return (uint64_t)num_worlds * params.block_bytes; }
-    uint64_t set_observation_output(void *out) override  // see OvercookedSim::set_observation_output
+struct SimplecookedSim final : mrl_kitchen::KitchenSim<SimpleParams> {
+    void ring_changed(uint8_t *obs, uint64_t stride, uint32_t slots) override
     {
-        set_observation_ring(out, 0, 1);
-        return observation_bytes();
-    }
-    uint8_t *ring_base = nullptr;
-    uint64_t ring_stride = 0, ring_pos = 0;
-    uint32_t ring_slots = 1;
-    void set_observation_ring(void *base, uint64_t stride_bytes, uint32_t slots) override  // see OvercookedSim::set_observation_ring
-    {
-        ring_base = base ? static_cast<uint8_t *>(base) : own_obs;
-        ring_stride = base ? stride_bytes : 0;
-        ring_slots = base && slots > 1 ? slots : 1;
-        ring_pos = 0;
-        // slots off 16-byte boundaries are staged (OvercookedSim::set_observation_ring): a slab of the simulator's + one copy
-        staged = base && ((reinterpret_cast<uintptr_t>(base) & 15u) != 0 || (ring_slots > 1 && (ring_stride & 15u) != 0));
-        if (staged && !staging) staging = arena.alloc<uint8_t>(observation_bytes(), false);
-        params.obs = staged ? staging : ring_base;
-        params.ring_stride = staged ? 0 : ring_stride;
-        params.ring_slots = staged ? 1 : ring_slots;
+        params.obs = obs;
+        params.ring_stride = stride;
+        params.ring_slots = slots;
         params.ring_first = 0;
     }
-    bool staged = false;
-    uint8_t *staging = nullptr;
-    // mrl_reset_worlds: see OvercookedSim::reset_worlds
-    mrl::FreshWorldOwner fresh;
-    void reset_worlds(const uint8_t *mask, hipStream_t stream) override
-    {
-        if (staged)
-            throw std::runtime_error("mrl_reset_worlds: the observation output is a staged slot (off a 16-byte boundary); a reset writes "
-                                     "observations in place only -- use an aligned slot or the simulator's own tensor");
-        const uint64_t slot = ring_pos ? (ring_pos - 1) % ring_slots : 0;
-        fresh.launch(mask, num_worlds, ring_base + (size_t)slot * ring_stride, stream);
-    }
-    uint8_t *take_slots(uint32_t steps, uint32_t *first)
-    {
-        const uint32_t at = (uint32_t)(ring_pos % ring_slots);
-        ring_pos += steps;
-        if (first) *first = at;
-        return ring_base + (size_t)at * ring_stride;
-    }
-    uint32_t H = 0, grid = 0, lds_bytes = 0;
     using FixedKernel = void (*)(uint32_t *, uint2 *, int2 *, const void *, const uint32_t *, const uint16_t *, uint32_t, uint32_t, const SimpleParams);
     FixedKernel fixed_kernel[3] = {};  // mrl_simplecooked_step_fixed<...> per action source, when the parameters are exactly its
     void (*fixed_rollout)(const SimpleParams, uint32_t, uint64_t, uint32_t, const int32_t *) = nullptr;
     void (*generic_rollout)(const SimpleParams, uint32_t, uint64_t, uint32_t, const int32_t *) = nullptr;
     void (*generic_step)(const SimpleParams) = nullptr;  // mrl_simplecooked_step<false, P, store flavour>
     const char *fixed_name = nullptr;
-    int32_t *action = nullptr, *active = nullptr, *mask = nullptr;
-    int32_t *world_id = nullptr, *agent_id = nullptr, *loc_world_id = nullptr, *loc_id = nullptr;
 
     void launch(bool init, const SimpleParams &given, hipStream_t stream)
     {
         SimpleParams a = given;
         uint8_t *const dest = init ? nullptr : take_slots(1, nullptr);
-        if (!init) a.obs = staged ? staging : dest;
+        if (!init) a.obs = step_obs(dest);
         a.ring_slots = 1;  // a single step writes exactly its `obs`
         if (init) {
             if (a.P == 2)
@@ -902,7 +849,7 @@ struct SimplecookedSim final : mrl_sim {
             hipLaunchKernelGGL(generic_step, dim3(grid), dim3(kBlock), lds_bytes, stream, a);
         }
         MRL_HIP(hipGetLastError());
-        if (staged && dest) MRL_HIP(hipMemcpyAsync(dest, staging, observation_bytes(), hipMemcpyDeviceToDevice, stream));
+        deliver(dest, stream);
     }
 
     void phase1(const int32_t *actions, hipStream_t stream) override
@@ -911,7 +858,6 @@ struct SimplecookedSim final : mrl_sim {
         a.actions = actions ? actions : action;
         launch(false, a, stream);
     }
-    void phase2(const uint32_t *, hipStream_t) override {}
     bool step_i64(const long long *actions, hipStream_t stream) override
     {
         SimpleParams a = params;
@@ -960,54 +906,18 @@ struct SimplecookedSim final : mrl_sim {
         }
     }
 
-    void ensure_ids()
-    {
-        if (world_id) return;
-        const uint32_t P = params.P, N = num_worlds, rows = params.rows;
-        world_id = arena.alloc<int32_t>((size_t)P * N, false);
-        agent_id = arena.alloc<int32_t>((size_t)P * N, false);
-        loc_world_id = arena.alloc<int32_t>((size_t)rows * N, false);
-        loc_id = arena.alloc<int32_t>((size_t)rows * N, false);
-        const size_t a = (size_t)P * N, b = (size_t)rows * N;
-        hipLaunchKernelGGL(fill_ids, dim3((unsigned)((a + 255) / 256)), dim3(256), 0, 0, world_id, agent_id, P, N);
-        hipLaunchKernelGGL(fill_ids, dim3((unsigned)((b + 255) / 256)), dim3(256), 0, 0, loc_world_id, loc_id, rows, N);
-        MRL_HIP(hipGetLastError());
-        MRL_HIP(hipDeviceSynchronize());
-    }
-
     bool tensor(int slot, mrl_tensor_desc *out) override
     {
-        const int64_t P = params.P, N = num_worlds, C = params.C, F = params.F, W = params.W;
+        const int64_t N = num_worlds;
         switch (slot) {
-        case MRL_OVERCOOKED_DONE: *out = mrl::make_desc(params.done, MRL_INT32, device, {N}); return true;
-        case MRL_OVERCOOKED_ACTIVE_AGENT: *out = mrl::make_desc(active, MRL_INT32, device, {P, N}); return true;
-        case MRL_OVERCOOKED_ACTION: *out = mrl::make_desc(action, MRL_INT32, device, {P, N, 1}); return true;
-        case MRL_OVERCOOKED_OBSERVATION:
-            *out = mrl::make_desc(own_obs, MRL_INT8, device, {P * C, N, F}, {F, P * C * F, 1});
-            return true;
-        case MRL_OVERCOOKED_ACTION_MASK: *out = mrl::make_desc(mask, MRL_INT32, device, {P, N, 6}); return true;
-        case MRL_OVERCOOKED_REWARD: *out = mrl::make_desc(params.reward, MRL_INT32, device, {P, N}); return true;
-        case MRL_OVERCOOKED_WORLD_ID: ensure_ids(); *out = mrl::make_desc(world_id, MRL_INT32, device, {P, N}); return true;
-        case MRL_OVERCOOKED_AGENT_ID: ensure_ids(); *out = mrl::make_desc(agent_id, MRL_INT32, device, {P, N}); return true;
-        case MRL_OVERCOOKED_LOCATION_WORLD_ID:
-            ensure_ids();
-            *out = mrl::make_desc(loc_world_id, MRL_INT32, device, {P * C, N});
-            return true;
-        case MRL_OVERCOOKED_LOCATION_ID: ensure_ids(); *out = mrl::make_desc(loc_id, MRL_INT32, device, {P * C, N}); return true;
-        case MRL_OVERCOOKED_OBS_WORLD_MAJOR:
-            *out = mrl::make_desc(own_obs, MRL_INT8, device, {N, P, (int64_t)H, W, F});
-            return true;
-        case MRL_OVERCOOKED_STATE_PLAYERS: *out = mrl::make_desc(params.players, MRL_UINT8, device, {N, P, 8}); return true;
-        case MRL_OVERCOOKED_STATE_OBJECTS: *out = mrl::make_desc(params.cell_obj, MRL_UINT8, device, {N, C, 4}); return true;
         case MRL_OVERCOOKED_STATE_TIMESTEP: *out = mrl::make_desc(params.clock, MRL_INT32, device, {N}, {2}); return true;
         case MRL_SIMPLECOOKED_STATE_DISHES_OUT:
             *out = mrl::make_desc(reinterpret_cast<int32_t *>(params.clock) + 1, MRL_INT32, device, {N}, {2});
             return true;
-        default: return false;
+        default: return common_tensor(slot, out);
         }
     }
 
-    size_t action_elems() const override { return (size_t)params.P * num_worlds; }
     void launch_shape(uint32_t out[4]) const override
     {
         out[0] = grid;
@@ -1034,54 +944,13 @@ struct SimplecookedSim final : mrl_sim {
 
 mrl_sim *mrl::create_simplecooked(const mrl_overcooked_config *cfg, int gpu_id, uint32_t num_worlds)
 {
-    if (!cfg || !cfg->terrain || !cfg->start_player_x || !cfg->start_player_y || !cfg->recipe_values || !cfg->recipe_times) {
-        set_error("simplecooked: null config field");
-        throw HipError{MRL_ERR_INVALID};
-    }
-    const int64_t H = cfg->height, W = cfg->width, P = cfg->num_players;
-    if (H < 3 || W < 3 || H * W > (int64_t)kMaxCells) {
-        set_error("simplecooked: height*width must be 9..100 (MAX_SIZE, src/overcooked2_env/sim.hpp:12), got %lldx%lld", (long long)H,
-                  (long long)W);
-        throw HipError{MRL_ERR_INVALID};
-    }
-    if (P < 1 || P > (int64_t)kMaxPlayers) {
-        set_error("simplecooked: num_players must be 1..2 (MAX_NUM_PLAYERS, src/overcooked2_env/sim.hpp:13), got %lld", (long long)P);
-        throw HipError{MRL_ERR_INVALID};
-    }
-    if (num_worlds == 0) {
-        set_error("simplecooked: num_worlds must be > 0");
-        throw HipError{MRL_ERR_INVALID};
-    }
-    const int64_t C = H * W;
-    alignas(4) uint8_t consts[kConstBytes];
-    memset(consts, 0, sizeof(consts));
-    uint32_t num_pots = 0;
-    for (int64_t c = 0; c < C; c++) {
-        const int64_t t = cfg->terrain[c];
-        if (t < 0 || t > 6) {
-            set_error("simplecooked: terrain[%lld] = %lld is not a TerrainT value", (long long)c, (long long)t);
-            throw HipError{MRL_ERR_INVALID};
-        }
-        const int64_t x = c % W, y = c / W;
-        if (t == T_AIR && (x == 0 || y == 0 || x == W - 1 || y == H - 1)) {
-            set_error("simplecooked: walkable cell on the grid border at (%lld,%lld); the step indexes neighbours without bounds checks "
-                      "(src/overcooked2_env/sim.cpp:160-172)",
-                      (long long)x, (long long)y);
-            throw HipError{MRL_ERR_INVALID};
-        }
-        consts[kConstTerrain + c] = (uint8_t)t;
-        if (t == T_POT) consts[kConstPots + num_pots++] = (uint8_t)c;
-    }
-    uint32_t starts = 0;
-    for (int64_t q = 0; q < P; q++) {
-        const int64_t x = cfg->start_player_x[q], y = cfg->start_player_y[q];
-        if (x < 1 || y < 1 || x >= W - 1 || y >= H - 1) {
-            set_error("simplecooked: start position of player %lld (%lld,%lld) is not an interior cell", (long long)q, (long long)x,
-                      (long long)y);
-            throw HipError{MRL_ERR_INVALID};
-        }
-        starts |= (uint32_t)(y * W + x) << (8 * q);
-    }
+    const mrl_kitchen::Kitchen k = mrl_kitchen::read_config(cfg, num_worlds,
+                                                            {"simplecooked", kMaxCells, "MAX_SIZE, src/overcooked2_env/sim.hpp:12", kMaxPlayers,
+                                                             "MAX_NUM_PLAYERS, src/overcooked2_env/sim.hpp:13", "src/overcooked2_env/sim.cpp:160-172"});
+    const int64_t H = k.H, W = k.W, P = k.P, C = k.C;
+    alignas(4) uint8_t consts[kConstBytes] = {};
+    memcpy(consts + kConstTerrain, k.terrain, (size_t)C);
+    memcpy(consts + kConstPots, k.pots, k.num_pots);
 
     bind_device(gpu_id);
     auto *sim = new SimplecookedSim();
@@ -1105,8 +974,8 @@ mrl_sim *mrl::create_simplecooked(const mrl_overcooked_config *cfg, int gpu_id, 
         a.dish_rew = (uint8_t)cfg->dish_pickup_rew;
         a.soup_pickup_rew = (uint8_t)cfg->soup_pickup_rew;
         a.horizon = cfg->horizon;
-        a.num_pots = num_pots;
-        a.starts = starts;
+        a.num_pots = k.num_pots;
+        a.starts = (uint32_t)k.start[0] | (uint32_t)k.start[1] << 8;
         a.deltas = pack_deltas(W);
         for (int r = 0; r < 16; r++) {
             reinterpret_cast<uint8_t *>(a.times_w)[r] = (uint8_t)cfg->recipe_times[r];
@@ -1129,44 +998,14 @@ mrl_sim *mrl::create_simplecooked(const mrl_overcooked_config *cfg, int gpu_id, 
         a.lds_wave_stride = a.off_tile + (a.flat ? ((wpw * a.block_bytes + 255u) & ~255u) : up16(wpw * a.block_bytes)) + 48u;
         sim->lds_bytes = kConstBytes + kWavesPerBlock * a.lds_wave_stride;
         // direct encode (see SimpleParams): holder cells = counters / pots next to a walkable cell; players start on walkable cells
-        std::vector<uint32_t> holders;  // cell | is_pot << 8
-        for (int64_t c = 0; c < C; c++) {
-            const uint32_t t = consts[kConstTerrain + c];
-            if (t != T_COUNTER && t != T_POT) continue;
-            const int64_t x = c % W, y = c / W;
-            const bool faced = (x > 0 && consts[kConstTerrain + c - 1] == T_AIR) || (x + 1 < W && consts[kConstTerrain + c + 1] == T_AIR) ||
-                               (y > 0 && consts[kConstTerrain + c - W] == T_AIR) || (y + 1 < H && consts[kConstTerrain + c + W] == T_AIR);
-            if (faced) holders.push_back((uint32_t)c | (t == T_POT ? 0x100u : 0u));
-        }
-        std::vector<uint32_t> hold_tab;
-        {
-            const uint32_t free0 = (uint32_t)kWave - std::min<uint32_t>((uint32_t)kWave, wpw * a.P);
-            uint32_t k = 0;
-            for (uint32_t l = 0; l < wpw; l++)
-                for (const uint32_t h : holders) {
-                    const uint32_t c = h & 0xFFu;
-                    const uint32_t slot = k < free0 ? wpw * a.P + k : (uint32_t)kWave + (k - free0);
-                    if (hold_tab.size() <= slot) hold_tab.resize(slot + 1, 0u);
-                    hold_tab[slot] = (l * a.block_bytes + c * a.F) | ((l * a.C + c) << 16) | (1u << 30) | ((h >> 8) << 31);
-                    k++;
-                }
-            if (hold_tab.empty()) hold_tab.resize(1, 0u);
-            bool starts_walkable = true;
-            for (int64_t q = 0; q < P; q++) starts_walkable = starts_walkable && consts[kConstTerrain + ((starts >> (8 * q)) & 0xFFu)] == T_AIR;
-            a.direct = (a.P == 2 && a.flat && starts_walkable && hold_tab.size() <= (size_t)kHoldPerLane * kWave && wpw * a.block_bytes < 65536u &&
-                        !mrl::debug_get("overcooked.no_direct", 0))
-                           ? 1u
-                           : 0u;
-            a.hold_entries = (uint32_t)hold_tab.size();
-        }
-        // store flavour of the stream-out (grid_common.hpp, stream_store_rsrc): ordinary stores iff a group's slab is not whole
-        // 128-byte lines and either the launch is a multi-step one or the slab exceeds the 256 MiB Infinity Cache
-        const auto plain_for = [&](bool multi_step) {
-            const int64_t knob = mrl::debug_get("overcooked.whole_store", 0);  // 0 that rule, 1 write-through, 2 plain
-            const bool whole_lines = ((uint64_t)wpw * a.block_bytes) % 64u == 0;  // (64: Simplecooked random0's 8000-byte groups, half a 128-byte line off, do not care)
-            return knob ? knob == 2 : (!whole_lines && (multi_step || (uint64_t)N * a.block_bytes > (256ull << 20)));
-        };
-        const bool plain = plain_for(false), plain_multi = plain_for(true);
+        const std::vector<uint32_t> holders = mrl_kitchen::holder_cells(k);
+        const std::vector<uint32_t> hold_tab = mrl_kitchen::hold_table(k, holders, wpw, a.F);
+        a.direct = (a.P == 2 && a.flat && mrl_kitchen::starts_walkable(k) && hold_tab.size() <= (size_t)kHoldPerLane * kWave &&
+                    wpw * a.block_bytes < 65536u && !mrl::debug_get("overcooked.no_direct", 0))
+                       ? 1u
+                       : 0u;
+        a.hold_entries = (uint32_t)hold_tab.size();
+        const bool plain = mrl_kitchen::plain_store(N, a.block_bytes, wpw, false), plain_multi = mrl_kitchen::plain_store(N, a.block_bytes, wpw, true);
         sim->generic_step = a.P == 2 ? (plain ? &mrl_simplecooked_step<false, 2, true> : &mrl_simplecooked_step<false, 2, false>)
                                      : (plain ? &mrl_simplecooked_step<false, 1, true> : &mrl_simplecooked_step<false, 1, false>);
         sim->generic_rollout = plain_multi ? &mrl_simplecooked_rollout<true> : &mrl_simplecooked_rollout<false>;
@@ -1198,55 +1037,25 @@ mrl_sim *mrl::create_simplecooked(const mrl_overcooked_config *cfg, int gpu_id, 
         const uint32_t blocks = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
         sim->grid = (blocks + 7u) & ~7u;
         a.per_xcd = sim->grid >> 3;
+        a.hold_tab = mrl_kitchen::upload(sim->arena, hold_tab);
+        a.consts = mrl_kitchen::upload(sim->arena, reinterpret_cast<const uint32_t *>(consts), kConstBytes / 4);
         {
-            uint32_t *d_tab = sim->arena.alloc<uint32_t>(hold_tab.size(), false);
-            MRL_HIP(hipMemcpy(d_tab, hold_tab.data(), hold_tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            a.hold_tab = d_tab;
-        }
-
-        uint32_t *d_consts = sim->arena.alloc<uint32_t>(kConstBytes / 4, false);
-        MRL_HIP(hipMemcpy(d_consts, consts, kConstBytes, hipMemcpyHostToDevice));
-        a.consts = d_consts;
-        {
-            // per row of one world: where its terrain one-hot byte goes (channel 5P + t - 1, sim.cpp:553-558); the
-            // tomato source's falls on channel 5P+5, which observationSystem zeroes on every pass (sim.cpp:74)
-            std::vector<uint16_t> pos(a.rows, 0xFFFFu);
-            for (uint32_t v = 0; v < a.P; v++)
-                for (uint32_t c = 0; c < a.C; c++) {
-                    const uint32_t t = consts[kConstTerrain + c];
-                    if (t != T_AIR && t != T_TOMATO_SRC) pos[v * a.C + c] = (uint16_t)((v * a.C + c) * a.F + 5 * a.P + t - 1);
-                }
-            uint16_t *d_pos = sim->arena.alloc<uint16_t>(a.rows, false);
-            MRL_HIP(hipMemcpy(d_pos, pos.data(), a.rows * sizeof(uint16_t), hipMemcpyHostToDevice));
-            a.terr_pos = d_pos;
-            std::vector<uint16_t> off(a.terr_entries, 0);
-            for (uint32_t l = 0; l < a.wpw; l++)
-                for (uint32_t r = 0; r < a.rows; r++)
-                    if (pos[r] != 0xFFFFu) off[l * a.rows + r] = (uint16_t)(l * a.block_bytes + pos[r]);
-            uint16_t *d_off = sim->arena.alloc<uint16_t>(a.terr_entries, false);
-            MRL_HIP(hipMemcpy(d_off, off.data(), a.terr_entries * sizeof(uint16_t), hipMemcpyHostToDevice));
-            a.terr_off = d_off;
+            // per row: where its terrain one-hot byte goes (channel 5P + t - 1, sim.cpp:553-558); the tomato source's falls on
+            // channel 5P+5, which observationSystem zeroes on every pass (sim.cpp:74)
+            const uint32_t no_byte = 1u << T_AIR | 1u << T_TOMATO_SRC;
+            std::vector<uint16_t> pos = mrl_kitchen::terrain_offsets(k, 1, a.F, no_byte);  // of one world, none = 0xFFFF
+            std::replace(pos.begin(), pos.end(), (uint16_t)0, (uint16_t)0xFFFFu);
+            a.terr_pos = mrl_kitchen::upload(sim->arena, pos);
+            a.terr_off = mrl_kitchen::upload(sim->arena, mrl_kitchen::terrain_offsets(k, a.wpw, a.F, no_byte));  // of a group
         }
         a.cell_obj = sim->arena.alloc<uint32_t>((size_t)N * C);
         a.players = sim->arena.alloc<uint2>((size_t)N * P);
         a.clock = sim->arena.alloc<int2>(N);
         a.reward = sim->arena.alloc<int32_t>((size_t)N * P);
         a.done = sim->arena.alloc<int32_t>(N);
-        a.obs = sim->arena.alloc<uint8_t>((size_t)N * a.block_bytes, false);
-        sim->own_obs = a.obs;
-        sim->ring_base = a.obs;
-        a.ring_stride = 0;
-        a.ring_slots = 1;
-        a.ring_first = 0;
-        sim->action = sim->arena.alloc<int32_t>((size_t)N * P);
-        sim->active = sim->arena.alloc<int32_t>((size_t)N * P, false);
-        sim->mask = sim->arena.alloc<int32_t>((size_t)N * P * 6, false);
+        sim->alloc_outputs();
         a.actions = sim->action;
         a.action_out = sim->action;
-        const size_t na = (size_t)N * P, nm = na * 6;
-        hipLaunchKernelGGL(fill_i32, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, 0, sim->active, 1, na);
-        hipLaunchKernelGGL(fill_i32, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, 0, sim->mask, 1, nm);
-        MRL_HIP(hipGetLastError());
         // Sim::Sim (sim.cpp:470-575): reset state + first observation
         sim->launch(true, a, 0);
         MRL_HIP(hipDeviceSynchronize());

@@ -1,5 +1,6 @@
-// The kernels of mrl_reset_worlds (world_reset.hpp says how they are used).
-#include "world_reset.hpp"
+// The kernels of mrl_reset_worlds (world_reset.hpp says how they are used), and the two fill kernels behind the kitchen
+// simulators' constant tensors (kitchen_host.hpp).
+#include "kitchen_host.hpp"
 
 namespace {
 
@@ -43,7 +44,35 @@ __global__ void __launch_bounds__(256) mrl_cooked_reset(const uint8_t *__restric
     }
 }
 
+__global__ void mrl_fill_ids(int32_t *world_id, int32_t *row_id, uint32_t rows, uint32_t n)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < (size_t)rows * n) {
+        world_id[i] = (int32_t)(i % n);
+        row_id[i] = (int32_t)(i / n);
+    }
+}
+
+__global__ void mrl_fill_i32(int32_t *dst, int32_t value, size_t count)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) dst[i] = value;
+}
+
 }  // namespace
+
+void mrl::fill_ids(int32_t *world_id, int32_t *row_id, uint32_t rows, uint32_t n)
+{
+    const size_t count = (size_t)rows * n;
+    hipLaunchKernelGGL(mrl_fill_ids, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, 0, world_id, row_id, rows, n);
+    MRL_HIP(hipGetLastError());
+}
+
+void mrl::fill_i32(int32_t *dst, int32_t value, size_t count)
+{
+    hipLaunchKernelGGL(mrl_fill_i32, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, 0, dst, value, count);
+    MRL_HIP(hipGetLastError());
+}
 
 void mrl::ResetScratch::build(const uint8_t *mask_dev, uint32_t n, uint32_t grid, uint32_t chunk, hipStream_t stream) const
 {
