@@ -18,10 +18,8 @@
 //   mrl_step_phase1  mrl_balance_step : moves, history, reward, done flag, per-workgroup finished counts
 //   mrl_step_phase2  mrl_balance_reset: exclusive prefix over the counts, re-seed finished worlds
 // and mrl_step is the two in a row.
-#include "common.hpp"
-#include "episode_scan.hpp"
+#include "episode_host.hpp"
 #include "random_policy.hpp"
-#include "world_reset.hpp"
 
 namespace {
 
@@ -370,134 +368,47 @@ __global__ void __launch_bounds__(kBlock) mrl_balance_step_fused(uint32_t n, con
     }
 }
 
-__global__ void fill_balance_ids(int32_t *world_id, int32_t *agent_id, int32_t *active, int32_t *mask, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < 2 * n) {
-        world_id[i] = (int32_t)(i % n);
-        agent_id[i] = (int32_t)(i / n);
-        active[i] = 1;
-#pragma unroll
-        for (int k = 0; k < 4; k++) mask[(size_t)i * 4 + k] = 1;
-    }
-}
-
-struct BalanceSim final : mrl_sim {
-    uint32_t grid = 0, chunk = 0, parity = 0;
+struct BalanceSim final : mrl::EpisodeSim {
     int32_t *action = nullptr, *obs = nullptr, *done = nullptr, *world_id = nullptr, *agent_id = nullptr, *active = nullptr, *mask = nullptr;
     float *reward = nullptr;
-    uint32_t *block_counts = nullptr, *counter = nullptr, *reset_count = nullptr;
-    uint32_t *shard_count = nullptr;  // SHARD_COUNT: finished worlds of the last mrl_step_phase1
-    mrl::LaunchStateOwner launch_state;  // parity in device memory once a caller wants to capture steps (common.hpp)
-    mrl::AlarmOwner alarm;               // raised when the mailbox exchange of a sharded step waited in vain (mrl_step_exchanged)
-    bool scan_timed_out() const override { return alarm.raised(); }
-    bool capturable() const override { return launch_state.device_mode; }
-    void prepare_graph_capture(hipStream_t stream) override { launch_state.to_device(parity, epoch, stream); }
-    unsigned long long *finished_mask = nullptr;  // one bit per world: the done flags, as each wave's ballot
     // single-launch step (mrl_balance_step_fused)
     uint32_t *status = nullptr;                 // 32-bit status words, and per 256 workgroups their total (mrl::grouped_prefix)
     unsigned long long *group_total = nullptr;
-    mrl::HealTest heal;
-    uint32_t fused_grid = 0, epoch = 0;
-    bool fused_step = false;
+    uint32_t fused_grid = 0;
 
-    void launch_fused(const int32_t *actions, int32_t *action_out, uint64_t seed, uint32_t sample_step, hipStream_t stream,
-                      const mrl::FusedExchange &fx = mrl::FusedExchange{})
+    void launch_fused(const int32_t *actions, const Drawn &drawn, const mrl::FusedExchange &fx, const Counters &c, hipStream_t stream) override
     {
-        epoch += 1;
-        if (launch_state.device_mode) launch_state.advance(stream);
         hipLaunchKernelGGL(mrl_balance_step_fused, dim3(fused_grid), dim3(kBlock), 0, stream, num_worlds, actions ? actions : action, obs, reward,
-                           done, status, group_total, epoch, counter + parity, counter + (parity ^ 1u), reset_count, action_out, seed, sample_step,
-                           heal, launch_state.counter_args(counter), fx);
-        MRL_HIP(hipGetLastError());
-        parity ^= 1u;
+                           done, status, group_total, epoch, c.base, c.next, reset_count, drawn.action_out, drawn.seed, drawn.step, heal, c.device, fx);
     }
-    void step(const int32_t *actions, hipStream_t stream) override
-    {
-        if (fused_step)
-            launch_fused(actions, nullptr, 0, 0, stream);
-        else
-            mrl_sim::step(actions, stream);
-    }
-    // a shard's step with the other ranks' counts taken from the mailboxes inside the single launch (episode_scan.hpp)
-    void step_exchanged(const int32_t *actions, hipStream_t stream) override
-    {
-        if (fused_step)
-            launch_fused(actions, nullptr, 0, 0, stream, mrl::fused_exchange_of(exchange, alarm.alarm()));
-        else
-            mrl_sim::step_exchanged(actions, stream);
-    }
-
     void launch_step(const int32_t *actions, int32_t *action_out, uint64_t seed, uint32_t sample_step, hipStream_t stream)
     {
         hipLaunchKernelGGL(mrl_balance_step, dim3(grid), dim3(kBlock), 0, stream, num_worlds, chunk, actions ? actions : action, obs, reward,
-                           done, block_counts, finished_mask, action_out, seed, sample_step);
+                           done, block_counts, stepped.words, action_out, seed, sample_step);
         MRL_HIP(hipGetLastError());
     }
     void phase1(const int32_t *actions, hipStream_t stream) override { launch_step(actions, nullptr, 0, 0, stream); }
-    void launch_reset(const uint32_t *base, const mrl::GatheredCounts &gathered, hipStream_t stream, bool external_base = false)
+    void launch_reseed(const Finished &from, const mrl::GatheredCounts &gathered, const Counters &c, hipStream_t stream) override
     {
-        if (launch_state.device_mode) launch_state.advance(stream);
-        hipLaunchKernelGGL((mrl_balance_reset<false>), dim3(grid), dim3(kBlock), 0, stream, num_worlds, chunk, finished_mask, obs, block_counts, base,
-                           0u, counter + (parity ^ 1u), reset_count, gathered, launch_state.counter_args(counter, external_base));
-        MRL_HIP(hipGetLastError());
-        parity ^= 1u;
-    }
-    void publish_shard_count(hipStream_t stream) override
-    {
-        hipLaunchKernelGGL(mrl::sum_block_counts, dim3(1), dim3(256), 0, stream, block_counts, grid, shard_count, mrl::mail_of(exchange));
-        MRL_HIP(hipGetLastError());
-    }
-    void phase2(const uint32_t *episode_base_dev, hipStream_t stream) override
-    {
-        launch_reset(episode_base_dev ? episode_base_dev : counter + parity, mrl::GatheredCounts{}, stream, episode_base_dev != nullptr);
-    }
-    void phase2_gathered(const uint32_t *counts, uint32_t num_ranks, uint32_t rank, hipStream_t stream) override
-    {
-        mrl::GatheredCounts g;
-        g.counts = counts;
-        g.num_ranks = num_ranks;
-        g.rank = rank;
-        launch_reset(counter + parity, g, stream);
-    }
-    void phase2_exchanged(hipStream_t stream) override { launch_reset(counter + parity, mrl::polled_counts(exchange, alarm.alarm()), stream); }
-    // mrl_reset_worlds: phase 2 on the caller's mask, with a scratch RESET_COUNT (world_reset.hpp)
-    mrl::ResetScratch forced;
-    void reset_worlds(const uint8_t *mask_dev, hipStream_t stream) override
-    {
-        forced.build(mask_dev, num_worlds, grid, chunk, stream);
-        if (launch_state.device_mode) launch_state.advance(stream);
-        hipLaunchKernelGGL((mrl_balance_reset<false>), dim3(grid), dim3(kBlock), 0, stream, num_worlds, chunk, forced.words, obs, forced.block_counts,
-                           counter + parity, 0u, counter + (parity ^ 1u), forced.reset_count, mrl::GatheredCounts{}, launch_state.counter_args(counter));
-        MRL_HIP(hipGetLastError());
-        parity ^= 1u;
+        hipLaunchKernelGGL((mrl_balance_reset<false>), dim3(grid), dim3(kBlock), 0, stream, num_worlds, chunk, from.words, obs, from.block_counts,
+                           c.base, 0u, c.next, from.reset_count, gathered, c.device);
     }
     void rollout_random(uint32_t num_steps, uint64_t seed, uint32_t first_step, hipStream_t stream) override
     {
         for (uint32_t k = 0; k < num_steps; k++) {
-            if (fused_step) {
-                launch_fused(action, action, seed, first_step + k, stream);
+            if (fused) {
+                fused_step(action, Drawn{action, seed, first_step + k}, mrl::FusedExchange{}, stream);
             } else {
                 launch_step(action, action, seed, first_step + k, stream);
                 phase2(nullptr, stream);
             }
         }
     }
-    void set_episode_counter(uint32_t next_episode, hipStream_t stream) override
-    {
-        if (launch_state.device_mode) {  // which half is current is only known on the device
-            hipLaunchKernelGGL(mrl::set_current_counter, dim3(1), dim3(1), 0, stream, counter, launch_state.dev, next_episode);
-            MRL_HIP(hipGetLastError());
-        } else {
-            MRL_HIP(hipMemcpyAsync(counter + parity, &next_episode, sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-        }
-        MRL_HIP(hipStreamSynchronize(stream));
-    }
     void reseed_shard(uint32_t world_offset, uint32_t num_worlds_total, hipStream_t stream) override
     {
         const uint32_t *none = nullptr;
         uint32_t *no_out = nullptr;
-        hipLaunchKernelGGL((mrl_balance_reset<true>), dim3(grid), dim3(kBlock), 0, stream, num_worlds, chunk, finished_mask, obs, block_counts, none,
+        hipLaunchKernelGGL((mrl_balance_reset<true>), dim3(grid), dim3(kBlock), 0, stream, num_worlds, chunk, stepped.words, obs, block_counts, none,
                            world_offset, no_out, no_out, mrl::GatheredCounts{}, mrl::DeviceCounter{});
         MRL_HIP(hipGetLastError());
         MRL_HIP(hipMemsetAsync(done, 0, sizeof(int32_t) * num_worlds, stream));
@@ -523,7 +434,7 @@ struct BalanceSim final : mrl_sim {
         }
     }
     size_t action_elems() const override { return (size_t)2 * num_worlds; }
-    const char *kernel_name() const override { return fused_step ? "mrl_balance_step_fused" : "mrl_balance_step"; }
+    const char *kernel_name() const override { return fused ? "mrl_balance_step_fused" : "mrl_balance_step"; }
     // actions 8 + both agents' rows r/w 2 * 2 * 28 + reward 8 + done 4
     uint64_t bytes_per_world_step() const override { return 8 + 4 * kRow * 4 + 8 + 4; }
     void launch_shape(uint32_t out[4]) const override
@@ -548,10 +459,7 @@ mrl_sim *mrl::create_balance(int gpu_id, uint32_t num_worlds)
         sim->game = MRL_GAME_BALANCE;
         sim->device = gpu_id;
         sim->num_worlds = num_worlds;
-        const uint32_t groups = (num_worlds + kBlock - 1) / kBlock;
-        const uint32_t blocks = groups < mrl::kMaxScanBlocks ? groups : mrl::kMaxScanBlocks;
-        sim->chunk = ((groups + blocks - 1) / blocks) * kBlock;
-        sim->grid = (num_worlds + sim->chunk - 1) / sim->chunk;
+        sim->size_scan_grid(kBlock);
         const size_t N = num_worlds;
         sim->action = sim->arena.alloc<int32_t>(2 * N);
         sim->obs = sim->arena.alloc<int32_t>(2 * N * kRow);
@@ -561,12 +469,7 @@ mrl_sim *mrl::create_balance(int gpu_id, uint32_t num_worlds)
         sim->agent_id = sim->arena.alloc<int32_t>(2 * N, false);
         sim->active = sim->arena.alloc<int32_t>(2 * N, false);
         sim->mask = sim->arena.alloc<int32_t>(2 * N * 4, false);
-        sim->block_counts = sim->arena.alloc<uint32_t>(sim->grid);
-        sim->finished_mask = sim->arena.alloc<unsigned long long>(((size_t)sim->grid * sim->chunk + 63) / 64);
-        sim->counter = sim->arena.alloc<uint32_t>(2);
-        sim->reset_count = sim->arena.alloc<uint32_t>(1);
-        sim->shard_count = sim->arena.alloc<uint32_t>(1);
-        sim->forced.init(sim->arena, sim->grid, sim->chunk, N, true, false);
+        sim->alloc_episode(true, false);
         sim->launch_state.init(sim->arena);
         sim->alarm.init(sim->arena);
         {
@@ -575,14 +478,12 @@ mrl_sim *mrl::create_balance(int gpu_id, uint32_t num_worlds)
                 sim->fused_grid = blocks;
                 sim->status = sim->arena.alloc<uint32_t>(blocks);
                 sim->group_total = sim->arena.alloc<unsigned long long>((blocks + mrl::kGroup - 1) / mrl::kGroup);
-                sim->heal.mod = (uint32_t)mrl::debug_get("fused_heal_test", 0);
-                sim->heal.seen = sim->arena.alloc<uint32_t>(blocks);
-                sim->fused_step = mrl::debug_get("fused_step", 0) != 2;  // 0 / 1: one launch (every row written once), 2: the two-launch pair
             }
+            sim->read_step_knobs(sim->fused_grid != 0, sim->fused_grid);  // one launch: every row written once
         }
-        hipLaunchKernelGGL(fill_balance_ids, dim3((unsigned)((2 * N + 255) / 256)), dim3(256), 0, 0, sim->world_id, sim->agent_id, sim->active,
-                           sim->mask, num_worlds);
-        MRL_HIP(hipGetLastError());
+        mrl::fill_ids(sim->world_id, sim->agent_id, 2, num_worlds);
+        mrl::fill_i32(sim->active, 1, 2 * N);
+        mrl::fill_i32(sim->mask, 1, 2 * N * 4);
         sim->reseed_shard(0, num_worlds, 0);  // Sim::Sim (sim.cpp:173-202): world w starts as episode w
         MRL_HIP(hipDeviceSynchronize());
     } catch (...) {

@@ -16,10 +16,8 @@
 //     mrl_cartpole_step : dynamics + done flag + per-workgroup reset counts
 //     mrl_cartpole_reset: exclusive prefix over the counts, re-seed finished worlds
 // HBM traffic per world-step: action 4 + state r/w 32 + reward 4 + done 4 = 44 B.
-#include "common.hpp"
-#include "episode_scan.hpp"
+#include "episode_host.hpp"
 #include "random_policy.hpp"
-#include "world_reset.hpp"
 
 #include <cstdlib>
 #include <type_traits>
@@ -731,70 +729,30 @@ template <typename F> void with_variant(int variant, F &&f)
     }
 }
 
-struct CartpoleSim final : mrl_sim {
-    uint32_t grid = 0;
+struct CartpoleSim final : mrl::EpisodeSim {
     int variant = kDefaultVariant;  // arithmetic of the transition (mrl_debug_set cartpole.variant: 1 + Variant; 0 = the default)
     int32_t *action = nullptr, *done = nullptr, *world_id = nullptr;
     float4 *state = nullptr;
     float *reward = nullptr;
-    uint32_t *block_counts = nullptr;
-    unsigned long long *finished_mask = nullptr;  // one bit per world: the done flags, as each wave's ballot
-    uint32_t chunk = 0;  // worlds per workgroup
-    uint32_t *counter = nullptr;  // [2]: double-buffered episode counter, [parity] is current
-    uint32_t *reset_count = nullptr;
-    uint32_t *shard_count = nullptr;  // SHARD_COUNT: finished worlds of the last mrl_step_phase1
-    uint32_t parity = 0;
     // single-launch step (see mrl_cartpole_step_fused)
     uint32_t *status = nullptr;
     unsigned long long *group_total = nullptr;  // per 64 workgroups (see mrl_cartpole_step_fused)
-    mrl::AlarmOwner alarm;
-    mrl::HealTest heal;  // test hook of the healing look-back (mrl_debug_set fused_heal_test)
-    uint32_t fused_grid = 0, epoch = 0;
-    mrl::LaunchStateOwner launch_state;  // parity / epoch in device memory once a caller wants to capture steps (common.hpp)
-    bool capturable() const override { return launch_state.device_mode; }
-    void prepare_graph_capture(hipStream_t stream) override { launch_state.to_device(parity, epoch, stream); }
-    bool scan_timed_out() const override { return alarm.raised(); }
-
+    uint32_t fused_grid = 0;
 #ifdef MRL_DIAG
     unsigned long long *stamps = nullptr;
 #endif
-    bool fused_step = false;  // one launch with the self-healing in-kernel look-back (the default where the grid allows; mrl_debug_set fused_step 2: two launches)
 
-    void step(const int32_t *actions, hipStream_t stream) override
+    void launch_fused(const int32_t *actions, const Drawn &drawn, const mrl::FusedExchange &fx, const Counters &c, hipStream_t stream) override
     {
-        if (fused_grid == 0 || !fused_step) {
-            mrl_sim::step(actions, stream);
-            return;
-        }
-        launch_fused(actions ? actions : action, nullptr, 0, 0, stream);
-    }
-
-    void launch_fused(const int32_t *actions, int32_t *action_out, uint64_t seed, uint32_t sample_step, hipStream_t stream,
-                      const mrl::FusedExchange &fx = mrl::FusedExchange{})
-    {
-        epoch += 1;
-        if (launch_state.device_mode) launch_state.advance(stream);  // then parity / epoch come from device memory
         with_variant(variant, [&](auto v) {
             hipLaunchKernelGGL(mrl_cartpole_step_fused<decltype(v)::value>, dim3(fused_grid), dim3(kBlock), 0, stream, num_worlds,
-                               actions, state, reward, done, status, group_total, epoch, counter + parity, counter + (parity ^ 1u), reset_count,
-                               action_out, seed, sample_step, heal, launch_state.counter_args(counter), fx
+                               actions ? actions : action, state, reward, done, status, group_total, epoch, c.base, c.next, reset_count,
+                               drawn.action_out, drawn.seed, drawn.step, heal, c.device, fx
 #ifdef MRL_DIAG
                                , stamps
 #endif
             );
         });
-        MRL_HIP(hipGetLastError());
-        parity ^= 1u;
-    }
-
-    // a shard's step with the other ranks' counts taken from the mailboxes inside the single launch (episode_scan.hpp)
-    void step_exchanged(const int32_t *actions, hipStream_t stream) override
-    {
-        if (fused_grid == 0 || !fused_step) {
-            mrl_sim::step_exchanged(actions, stream);
-            return;
-        }
-        launch_fused(actions ? actions : action, nullptr, 0, 0, stream, mrl::fused_exchange_of(exchange, alarm.alarm()));
     }
 
     unsigned long long *ring = nullptr;
@@ -827,8 +785,8 @@ struct CartpoleSim final : mrl_sim {
             persistent_ok = false;
         }
         for (uint32_t k = 0; k < num_steps; k++) {
-            if (fused_grid && fused_step) {
-                launch_fused(action, action, seed, first_step + k, stream);
+            if (fused) {
+                fused_step(action, Drawn{action, seed, first_step + k}, mrl::FusedExchange{}, stream);
             } else {
                 hipLaunchKernelGGL(mrl_cartpole_draw_actions, dim3((num_worlds + kBlock - 1) / kBlock), dim3(kBlock), 0, stream,
                                    action, num_worlds, seed, first_step + k);
@@ -841,59 +799,15 @@ struct CartpoleSim final : mrl_sim {
     {
         with_variant(variant, [&](auto v) {
             hipLaunchKernelGGL(mrl_cartpole_step<decltype(v)::value>, dim3(grid), dim3(kBlock), 0, stream, num_worlds, chunk,
-                               actions ? actions : action, state, reward, done, block_counts, finished_mask);
+                               actions ? actions : action, state, reward, done, block_counts, stepped.words);
         });
         MRL_HIP(hipGetLastError());
     }
 
-    void launch_reset(const uint32_t *base, const mrl::GatheredCounts &gathered, hipStream_t stream, bool external_base = false)
+    void launch_reseed(const Finished &from, const mrl::GatheredCounts &gathered, const Counters &c, hipStream_t stream) override
     {
-        if (launch_state.device_mode) launch_state.advance(stream);
-        hipLaunchKernelGGL(mrl_cartpole_reset, dim3(grid), dim3(kBlock), 0, stream, num_worlds, chunk, state, block_counts,
-                           finished_mask, base, counter + (parity ^ 1u), reset_count, gathered, launch_state.counter_args(counter, external_base));
-        MRL_HIP(hipGetLastError());
-        parity ^= 1u;
-    }
-    void publish_shard_count(hipStream_t stream) override
-    {
-        hipLaunchKernelGGL(mrl::sum_block_counts, dim3(1), dim3(256), 0, stream, block_counts, grid, shard_count, mrl::mail_of(exchange));
-        MRL_HIP(hipGetLastError());
-    }
-    void phase2(const uint32_t *episode_base_dev, hipStream_t stream) override
-    {
-        launch_reset(episode_base_dev ? episode_base_dev : counter + parity, mrl::GatheredCounts{}, stream, episode_base_dev != nullptr);
-    }
-    void phase2_gathered(const uint32_t *counts, uint32_t num_ranks, uint32_t rank, hipStream_t stream) override
-    {
-        mrl::GatheredCounts g;
-        g.counts = counts;
-        g.num_ranks = num_ranks;
-        g.rank = rank;
-        launch_reset(counter + parity, g, stream);
-    }
-    void phase2_exchanged(hipStream_t stream) override { launch_reset(counter + parity, mrl::polled_counts(exchange, alarm.alarm()), stream); }
-
-    // mrl_reset_worlds: phase 2 on the caller's mask, with a scratch RESET_COUNT (world_reset.hpp)
-    mrl::ResetScratch forced;
-    void reset_worlds(const uint8_t *mask, hipStream_t stream) override
-    {
-        forced.build(mask, num_worlds, grid, chunk, stream);
-        if (launch_state.device_mode) launch_state.advance(stream);
-        hipLaunchKernelGGL(mrl_cartpole_reset, dim3(grid), dim3(kBlock), 0, stream, num_worlds, chunk, state, forced.block_counts, forced.words,
-                           counter + parity, counter + (parity ^ 1u), forced.reset_count, mrl::GatheredCounts{}, launch_state.counter_args(counter));
-        MRL_HIP(hipGetLastError());
-        parity ^= 1u;
-    }
-
-    void set_episode_counter(uint32_t next_episode, hipStream_t stream) override
-    {
-        if (launch_state.device_mode) {  // which half is current is only known on the device
-            hipLaunchKernelGGL(mrl::set_current_counter, dim3(1), dim3(1), 0, stream, counter, launch_state.dev, next_episode);
-            MRL_HIP(hipGetLastError());
-        } else {
-            MRL_HIP(hipMemcpyAsync(counter + parity, &next_episode, sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-        }
-        MRL_HIP(hipStreamSynchronize(stream));
+        hipLaunchKernelGGL(mrl_cartpole_reset, dim3(grid), dim3(kBlock), 0, stream, num_worlds, chunk, state, from.block_counts, from.words,
+                           c.base, c.next, from.reset_count, gathered, c.device);
     }
 
     void reseed_shard(uint32_t world_offset, uint32_t num_worlds_total, hipStream_t stream) override
@@ -929,7 +843,7 @@ struct CartpoleSim final : mrl_sim {
     }
 
     size_t action_elems() const override { return (size_t)num_worlds; }
-    const char *kernel_name() const override { return fused_grid && fused_step ? "mrl_cartpole_step_fused" : "mrl_cartpole_step"; }
+    const char *kernel_name() const override { return fused ? "mrl_cartpole_step_fused" : "mrl_cartpole_step"; }
     const char *rollout_kernel_name() const override { return persistent_ok && !launch_state.device_mode ? "mrl_cartpole_rollout" : kernel_name(); }
     uint64_t bytes_per_world_step() const override { return 44; }
 };
@@ -956,23 +870,13 @@ mrl_sim *mrl::create_cartpole(int gpu_id, uint32_t num_worlds)
             }
             sim->variant = knob == 0 ? kDefaultVariant : (int)knob - 1;
         }
-        {
-            const uint32_t groups = (num_worlds + kBlock - 1) / kBlock;
-            const uint32_t blocks = groups < mrl::kMaxScanBlocks ? groups : mrl::kMaxScanBlocks;
-            sim->chunk = ((groups + blocks - 1) / blocks) * kBlock;
-            sim->grid = (num_worlds + sim->chunk - 1) / sim->chunk;
-        }
+        sim->size_scan_grid(kBlock);
         sim->action = sim->arena.alloc<int32_t>(num_worlds);
         sim->done = sim->arena.alloc<int32_t>(num_worlds);
         sim->world_id = sim->arena.alloc<int32_t>(num_worlds);
         sim->state = sim->arena.alloc<float4>(num_worlds);
         sim->reward = sim->arena.alloc<float>(num_worlds);
-        sim->block_counts = sim->arena.alloc<uint32_t>(sim->grid);
-        sim->finished_mask = sim->arena.alloc<unsigned long long>(((size_t)sim->grid * sim->chunk + 63) / 64);
-        sim->counter = sim->arena.alloc<uint32_t>(2);
-        sim->reset_count = sim->arena.alloc<uint32_t>(1);
-        sim->shard_count = sim->arena.alloc<uint32_t>(1);
-        sim->forced.init(sim->arena, sim->grid, sim->chunk, num_worlds, true, false);
+        sim->alloc_episode(true, false);
         {
             const uint32_t blocks = (num_worlds + kUnroll * kBlock - 1) / (kUnroll * kBlock);
             if (blocks <= mrl::kMaxFusedBlocks) {
@@ -992,30 +896,22 @@ mrl_sim *mrl::create_cartpole(int gpu_id, uint32_t num_worlds)
             // two launches, actions from a pool of eight tensors: 4096 worlds 4.3 / 6.1, 100 000 5.1 / 6.6, 262 144 6.2 / 9.7,
             // 524 288 7.7 / 9.6, 1 M 10.7 / 12.3 (tools/cartpole_probe.py, profiles/r04_i_cartpole_probe.txt); round 3's
             // crossover was 4096 worlds.  Two launches remain for the sharded path and above 4 M worlds (kMaxFusedBlocks).
-            const int64_t knob = mrl::debug_get("fused_step", 0);
-            sim->fused_step = knob != 2;
-            sim->heal.mod = (uint32_t)mrl::debug_get("fused_heal_test", 0);
-            sim->heal.seen = sim->arena.alloc<uint32_t>(sim->fused_grid ? sim->fused_grid : 1);
+            sim->read_step_knobs(sim->fused_grid != 0, sim->fused_grid);
         }
         if (sim->fused_grid) {
-            int per_cu = 0, cus = 0;
+            bool resident = false;
             with_variant(sim->variant, [&](auto v) {
-                MRL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                    &per_cu, reinterpret_cast<const void *>(&mrl_cartpole_rollout<decltype(v)::value>), kBlock, 0));
+                resident = mrl::grid_resident(reinterpret_cast<const void *>(&mrl_cartpole_rollout<decltype(v)::value>), kBlock, sim->fused_grid, gpu_id);
             });
-            MRL_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, gpu_id));
-            // (the occupancy query can be one workgroup per CU too high, MI355X_MICROARCH.md "Residency and
-            // cooperative launch": keep one per CU in hand near the edge; the cooperative launch is the check)
-            const int usable = per_cu > 4 ? per_cu - 1 : per_cu;
             // Above kPersistentMaxWorlds one single-launch step per step is faster than the persistent launch (whose per-step
             // hand-off reads every workgroup's count, flat): tools/cartpole_rollout_probe.py; cartpole.persistent_max moves the limit
             const uint64_t persistent_max = (uint64_t)mrl::debug_get("cartpole.persistent_max", kPersistentMaxWorlds);
-            sim->persistent_ok = !mrl::debug_get("cartpole.no_persistent", 0) && (uint64_t)sim->fused_grid <= (uint64_t)usable * (uint64_t)cus &&
+            sim->persistent_ok = !mrl::debug_get("cartpole.no_persistent", 0) && resident &&
                                  (uint64_t)num_worlds <= persistent_max;
             sim->ring = sim->arena.alloc<unsigned long long>((size_t)kRing * sim->fused_grid);
         }
         sim->reseed_shard(0, num_worlds, 0);
-        if (mrl::debug_get("inject_scan_timeout", 0)) hipLaunchKernelGGL(mrl::raise_alarm_kernel, dim3(1), dim3(1), 0, 0, sim->alarm.alarm());
+        sim->inject_scan_timeout();
         MRL_HIP(hipDeviceSynchronize());
     } catch (...) {
         delete sim;

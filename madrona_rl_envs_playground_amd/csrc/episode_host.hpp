@@ -1,0 +1,191 @@
+// Host side of what the three games that number their episodes share (HanabiSim in hanabi.hip, CartpoleSim in
+// cartpole.hip, BalanceSim in balance.hip; the device side is episode_scan.hpp): the double-buffered episode counter and
+// the launch-to-launch state around it, the choice between the single-launch step and the two-launch pair, phase 2 in
+// its four forms and the forced reset, which are all the game's one re-seeding launch on different inputs.  Host-only code.
+#pragma once
+
+#include "common.hpp"
+#include "episode_scan.hpp"
+#include "world_reset.hpp"
+
+namespace mrl {
+
+// The grid both launches of the two-launch step run on: at most kMaxScanBlocks workgroups, each owning `chunk`
+// consecutive worlds, chunk a multiple of what one workgroup steps at a time.
+struct ScanGrid {
+    uint32_t chunk, grid;
+};
+inline ScanGrid scan_grid(uint32_t num_worlds, uint32_t worlds_per_workgroup)
+{
+    const uint32_t groups = (num_worlds + worlds_per_workgroup - 1) / worlds_per_workgroup;
+    const uint32_t blocks = groups < kMaxScanBlocks ? groups : kMaxScanBlocks;
+    const uint32_t chunk = ((groups + blocks - 1) / blocks) * worlds_per_workgroup;
+    return ScanGrid{chunk, (num_worlds + chunk - 1) / chunk};
+}
+
+// A persistent rollout kernel keeps every workgroup alive for the whole rollout and they wait for each other: does its
+// grid fit the GPU in one go?
+inline bool grid_resident(const void *kernel, int block_threads, uint32_t grid, int gpu_id)
+{
+    int per_cu = 0, cus = 0;
+    MRL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block_threads, 0));
+    MRL_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, gpu_id));
+    // (the occupancy query can be one workgroup per CU too high, MI355X_MICROARCH.md "Residency and
+    // cooperative launch": keep one per CU in hand near the edge; the cooperative launch is the check)
+    const int usable = per_cu > 4 ? per_cu - 1 : per_cu;
+    return (uint64_t)grid <= (uint64_t)usable * (uint64_t)cus;
+}
+
+struct EpisodeSim : mrl_sim {
+    uint32_t grid = 0, chunk = 0;  // of the two-launch step (scan_grid)
+    uint32_t *counter = nullptr;   // [2]: double-buffered episode counter, [parity] is current
+    uint32_t parity = 0, epoch = 0;  // epoch: tag of the single-launch step's status words
+    uint32_t *block_counts = nullptr, *reset_count = nullptr;
+    uint32_t *shard_count = nullptr;  // SHARD_COUNT: finished worlds of the last mrl_step_phase1
+    LaunchStateOwner launch_state;    // parity / epoch in device memory once a caller wants to capture steps (common.hpp)
+    AlarmOwner alarm;                 // raised when a bounded wait expired: a persistent rollout's, or the mailbox exchange's of a sharded step
+    HealTest heal;                    // test hook of the healing look-back (mrl_debug_set fused_heal_test)
+    bool fused = false;               // mrl_step is one launch with the in-kernel look-back, not the two-launch pair
+
+    // ---- what a game supplies ----
+    // Where a re-seeding launch finds the finished worlds -- mask words (Cartpole, balance beam) or flags (Hanabi), and their
+    // number per workgroup -- and where it leaves RESET_COUNT.  A game reads one of words / flags; the other is null.
+    struct Finished {
+        unsigned long long *words;
+        int32_t *flags;
+        uint32_t *block_counts;
+        uint32_t *reset_count;
+    };
+    // What a counted launch reads and writes: this step's first episode, where the next step's goes, and the same in device mode.
+    struct Counters {
+        const uint32_t *base;
+        uint32_t *next;
+        DeviceCounter device;
+    };
+    // the random policy drawn inside the step (mrl_rollout_random); action_out == nullptr: the caller's actions.  Cartpole and
+    // the balance beam only: Hanabi's policy travels in its HanabiParams and its launch_fused does not look at a Drawn
+    struct Drawn {
+        int32_t *action_out = nullptr;
+        uint64_t seed = 0;
+        uint32_t step = 0;
+    };
+    virtual void launch_fused(const int32_t *actions, const Drawn &drawn, const FusedExchange &fx, const Counters &c, hipStream_t stream) = 0;
+    virtual void launch_reseed(const Finished &from, const GatheredCounts &gathered, const Counters &c, hipStream_t stream) = 0;
+    Finished stepped{};  // what phase 1 leaves (alloc_episode; Hanabi sets its flags)
+
+    // One launch that takes episode numbers: the device copy of the state advanced first, the counter's halves as of before
+    // the flip.  (Graph replay depends on this order.)  launch(Counters)
+    template <typename Launch> void counted_launch(bool new_epoch, const uint32_t *external_base, hipStream_t stream, Launch &&launch)
+    {
+        if (new_epoch) epoch += 1;
+        if (launch_state.device_mode) launch_state.advance(stream);  // then parity / epoch come from device memory
+        launch(Counters{external_base ? external_base : counter + parity, counter + (parity ^ 1u),
+                        launch_state.counter_args(counter, external_base != nullptr)});
+        MRL_HIP(hipGetLastError());
+        parity ^= 1u;
+    }
+    void fused_step(const int32_t *actions, const Drawn &drawn, const FusedExchange &fx, hipStream_t stream)
+    {
+        counted_launch(true, nullptr, stream, [&](const Counters &c) { launch_fused(actions, drawn, fx, c, stream); });
+    }
+    void reseed(const Finished &from, const uint32_t *external_base, const GatheredCounts &gathered, hipStream_t stream)
+    {
+        counted_launch(false, external_base, stream, [&](const Counters &c) { launch_reseed(from, gathered, c, stream); });
+    }
+
+    void step(const int32_t *actions, hipStream_t stream) override
+    {
+        if (fused)
+            fused_step(actions, Drawn{}, FusedExchange{}, stream);
+        else
+            mrl_sim::step(actions, stream);
+    }
+    // a shard's step with the other ranks' counts taken from the mailboxes inside the single launch (episode_scan.hpp)
+    void step_exchanged(const int32_t *actions, hipStream_t stream) override
+    {
+        if (fused)
+            fused_step(actions, Drawn{}, fused_exchange_of(exchange, alarm.alarm()), stream);
+        else
+            mrl_sim::step_exchanged(actions, stream);
+    }
+    void publish_shard_count(hipStream_t stream) override
+    {
+        hipLaunchKernelGGL(sum_block_counts, dim3(1), dim3(256), 0, stream, block_counts, grid, shard_count, mail_of(exchange));
+        MRL_HIP(hipGetLastError());
+    }
+    void phase2(const uint32_t *episode_base_dev, hipStream_t stream) override { reseed(stepped, episode_base_dev, GatheredCounts{}, stream); }
+    void phase2_gathered(const uint32_t *counts, uint32_t num_ranks, uint32_t rank, hipStream_t stream) override
+    {
+        GatheredCounts g;
+        g.counts = counts;
+        g.num_ranks = num_ranks;
+        g.rank = rank;
+        reseed(stepped, nullptr, g, stream);
+    }
+    void phase2_exchanged(hipStream_t stream) override { reseed(stepped, nullptr, polled_counts(exchange, alarm.alarm()), stream); }
+    // mrl_reset_worlds: phase 2 on the caller's mask, with a scratch RESET_COUNT (world_reset.hpp)
+    ResetScratch forced;
+    void reset_worlds(const uint8_t *mask_dev, hipStream_t stream) override
+    {
+        forced.build(mask_dev, num_worlds, grid, chunk, stream);
+        reseed(Finished{forced.words, forced.flags, forced.block_counts, forced.reset_count}, nullptr, GatheredCounts{}, stream);
+    }
+
+    bool scan_timed_out() const override { return alarm.raised(); }
+    bool capturable() const override { return launch_state.device_mode; }
+    void prepare_graph_capture(hipStream_t stream) override { launch_state.to_device(parity, epoch, stream); }
+    void set_episode_counter(uint32_t next_episode, hipStream_t stream) override
+    {
+        if (launch_state.device_mode) {  // which half is current is only known on the device
+            hipLaunchKernelGGL(set_current_counter, dim3(1), dim3(1), 0, stream, counter, launch_state.dev, next_episode);
+            MRL_HIP(hipGetLastError());
+        } else {
+            MRL_HIP(hipMemcpyAsync(counter + parity, &next_episode, sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        }
+        MRL_HIP(hipStreamSynchronize(stream));
+    }
+
+    // ---- construction ----
+    // first: grid and chunk of the two-launch step (the game's own allocations depend on them)
+    void size_scan_grid(uint32_t worlds_per_workgroup)
+    {
+        const ScanGrid g = scan_grid(num_worlds, worlds_per_workgroup);
+        chunk = g.chunk;
+        grid = g.grid;
+    }
+    // Then what lives in device memory.  Every game makes these allocations BEHIND its per-world tensors and in exactly the
+    // sequence it used before this header existed, which is why the alarm and the launch state are left to the game
+    // (alarm.init, launch_state.init: the balance beam has them the other way round) and why what is already allocated is
+    // skipped here (Hanabi allocates block_counts and shard_count itself, right behind its DONE tensor).  Where these few
+    // words land decides the speed of a kernel that is otherwise the same: Cartpole's single-launch step at 1 M worlds,
+    // 9.1-9.2 us, ran 9.7-9.9 us with all of this allocated in front of the tensors, and 9.4-9.6 us with only the launch
+    // state and the alarm in front of its status words instead of behind them (profiles/episode_host_bench_ab.txt).
+    // alloc_episode: the counts, the step's own mask words (Cartpole, balance beam), the counter, the forced reset's scratch
+    // with mask words or flags, whichever the game's re-seeding launch reads
+    void alloc_episode(bool with_words, bool with_flags)
+    {
+        if (!block_counts) block_counts = arena.alloc<uint32_t>(grid);
+        if (with_words) stepped.words = arena.alloc<unsigned long long>(((size_t)grid * chunk + 63) / 64);
+        counter = arena.alloc<uint32_t>(2);
+        reset_count = arena.alloc<uint32_t>(1);
+        if (!shard_count) shard_count = arena.alloc<uint32_t>(1);
+        forced.init(arena, grid, chunk, num_worlds, with_words, with_flags);
+        stepped.block_counts = block_counts;
+        stepped.reset_count = reset_count;
+    }
+    // mrl_debug_set fused_step: 0 = the library's choice (one launch wherever the game has one for this batch: `exists`),
+    // 1 = one launch where possible, 2 = always two; fused_heal_test: see HealTest (one word per workgroup of the single launch)
+    void read_step_knobs(bool exists, uint32_t fused_blocks)
+    {
+        fused = exists && debug_get("fused_step", 0) != 2;
+        heal.mod = (uint32_t)debug_get("fused_heal_test", 0);
+        heal.seen = arena.alloc<uint32_t>(fused_blocks);
+    }
+    // test hook (mrl_debug_set inject_scan_timeout), for the games that export SCAN_TIMEOUT
+    void inject_scan_timeout()
+    {
+        if (debug_get("inject_scan_timeout", 0)) hipLaunchKernelGGL(raise_alarm_kernel, dim3(1), dim3(1), 0, 0, alarm.alarm());
+    }
+};
+
+}  // namespace mrl

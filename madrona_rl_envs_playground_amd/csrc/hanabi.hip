@@ -31,14 +31,13 @@
 //                         other ranks in between): mrl_hanabi_step = action + encode +
 //                         score/done + per-workgroup done counts, mrl_hanabi_reset = prefix
 //                         over the counts, re-deal, encode both agents.
-#include "common.hpp"
-#include "episode_scan.hpp"
+#include "episode_host.hpp"
 #include "random_policy.hpp"
-#include "world_reset.hpp"
 
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 namespace {
 
@@ -2193,74 +2192,75 @@ mrl_hanabi_rollout(const HanabiParams p0, unsigned long long *ring, uint32_t epo
     store_records(p, rollout_lds(smem, b_slot, 0), w0, nw, lane);
 }
 
-__global__ void fill_agent_ids(int32_t *world_id, int32_t *agent_id, uint32_t n)
+// runs f(std::integral_constant<int, kV>) for the code variant picked at creation (see encode_variant)
+template <typename F> void with_variant(int variant, F &&f)
 {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < 2 * n) {
-        world_id[i] = (int32_t)(i % n);
-        agent_id[i] = (int32_t)(i / n);
+    switch (variant) {
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    default: f(std::integral_constant<int, 0>{}); break;
     }
 }
 
-struct HanabiSim final : mrl_sim {
-    HanabiParams params{};
-    uint32_t grid = 0;
+struct HanabiSim final : mrl::EpisodeSim {
+    HanabiParams params{};  // (carries copies of block_counts, shard_count and chunk: the kernels read them there)
     int32_t *action = nullptr, *world_id = nullptr, *agent_id = nullptr;
-    uint32_t *counter = nullptr, *reset_count = nullptr;
-    uint32_t parity = 0;
     int variant = 0;  // code variant of the kernels (see encode_variant)
     // single-launch step (mrl_hanabi_step_fused)
     unsigned long long *status = nullptr;
-    mrl::AlarmOwner alarm;
-    mrl::HealTest heal;  // test hook of the healing look-back (mrl_debug_set fused_heal_test)
     uint32_t pair_stride = 4;  // phase A of the single-launch step by four leader waves (see the kernel); mrl_debug_set hanabi.pairing
-    uint32_t epoch = 0;
-    bool fused = false;
-    mrl::LaunchStateOwner launch_state;  // parity / epoch in device memory once a caller wants to capture steps (common.hpp)
-    bool scan_timed_out() const override { return alarm.raised(); }
-    bool capturable() const override { return launch_state.device_mode; }
-    void prepare_graph_capture(hipStream_t stream) override { launch_state.to_device(parity, epoch, stream); }
 
-    void step(const int32_t *actions, hipStream_t stream) override
-    {
-        if (!fused) {
-            mrl_sim::step(actions, stream);
-            return;
-        }
-        launch_fused(actions, stream, mrl::FusedExchange{});
-    }
-    // a shard's step with the other ranks' counts taken from the mailboxes inside the single launch (episode_scan.hpp)
-    void step_exchanged(const int32_t *actions, hipStream_t stream) override
-    {
-        if (!fused) {
-            mrl_sim::step_exchanged(actions, stream);
-            return;
-        }
-        launch_fused(actions, stream, mrl::fused_exchange_of(exchange, alarm.alarm()));
-    }
-    void launch_fused(const int32_t *actions, hipStream_t stream, const mrl::FusedExchange &fx)
+    // (the random policy of mrl_rollout_random travels in params: `drawn` is not looked at)
+    void launch_fused(const int32_t *actions, const Drawn &, const mrl::FusedExchange &fx, const Counters &c, hipStream_t stream) override
     {
         HanabiParams a = params;
         a.actions = actions ? actions : action;
-        epoch += 1;
-        const uint32_t *base = counter + parity;
-        uint32_t *next = counter + (parity ^ 1u);
-        if (launch_state.device_mode) launch_state.advance(stream);  // then parity / epoch come from device memory
-        const mrl::DeviceCounter dc = launch_state.counter_args(counter);
-        switch (variant) {
-        case 2: hipLaunchKernelGGL((mrl_hanabi_step_fused<2>), dim3(grid), dim3(kFusedBlock), 0, stream, a.records, a.actions, a.num_worlds, heal.mod, pair_stride, a, status, epoch, base, next, reset_count, heal.seen, dc, fx); break;
-        case 1: hipLaunchKernelGGL((mrl_hanabi_step_fused<1>), dim3(grid), dim3(kFusedBlock), 0, stream, a.records, a.actions, a.num_worlds, heal.mod, pair_stride, a, status, epoch, base, next, reset_count, heal.seen, dc, fx); break;
-        default: hipLaunchKernelGGL((mrl_hanabi_step_fused<0>), dim3(grid), dim3(kFusedBlock), 0, stream, a.records, a.actions, a.num_worlds, heal.mod, pair_stride, a, status, epoch, base, next, reset_count, heal.seen, dc, fx); break;
-        }
+        with_variant(variant, [&](auto v) {
+            hipLaunchKernelGGL((mrl_hanabi_step_fused<decltype(v)::value>), dim3(grid), dim3(kFusedBlock), 0, stream, a.records, a.actions,
+                               a.num_worlds, heal.mod, pair_stride, a, status, epoch, c.base, c.next, reset_count, heal.seen, c.device, fx);
+        });
+    }
+
+    void phase1(const int32_t *actions, hipStream_t stream) override
+    {
+        HanabiParams a = params;
+        a.actions = actions ? actions : action;
+        with_variant(variant, [&](auto v) {
+            hipLaunchKernelGGL((mrl_hanabi_step<decltype(v)::value>), dim3(grid), dim3(kBlock), 0, stream, a.records, a.actions, a.num_worlds,
+                               a.chunk, a);
+        });
         MRL_HIP(hipGetLastError());
-        parity ^= 1u;
+    }
+
+    // the flags are read through p.done, the counts through p.block_counts
+    void launch_reseed(const Finished &from, const mrl::GatheredCounts &gathered, const Counters &c, hipStream_t stream) override
+    {
+        HanabiParams q = params;
+        q.done = from.flags;
+        q.block_counts = from.block_counts;
+        with_variant(variant, [&](auto v) {
+            hipLaunchKernelGGL((mrl_hanabi_reset<false, decltype(v)::value>), dim3(grid), dim3(kBlock), 0, stream, q, c.base, 0u, c.next,
+                               from.reset_count, gathered, c.device);
+        });
+    }
+
+    void reseed_shard(uint32_t world_offset, uint32_t num_worlds_total, hipStream_t stream) override
+    {
+        const uint32_t *none = nullptr;
+        uint32_t *no_out = nullptr;
+        with_variant(variant, [&](auto v) {
+            hipLaunchKernelGGL((mrl_hanabi_reset<true, decltype(v)::value>), dim3(grid), dim3(kBlock), 0, stream, params, none, world_offset,
+                               no_out, no_out, mrl::GatheredCounts{}, mrl::DeviceCounter{});
+        });
+        MRL_HIP(hipGetLastError());
+        set_episode_counter(num_worlds_total, stream);
     }
 
     unsigned long long *ring = nullptr;
     uint32_t ring_epoch = 0;
     bool persistent_ok = false;  // the whole grid of mrl_hanabi_rollout is resident at once
 
-    template <int kV> bool launch_rollout(uint32_t num_steps, uint64_t seed, uint32_t first_step, hipStream_t stream)
+    bool launch_rollout(uint32_t num_steps, uint64_t seed, uint32_t first_step, hipStream_t stream)
     {
         HanabiParams a = params;
         a.sample = 1;
@@ -2272,8 +2272,11 @@ struct HanabiSim final : mrl_sim {
         uint32_t *next = counter + (parity ^ 1u);
         mrl::Alarm al = alarm.alarm();
         void *args[] = {&a, &ring, &epoch0, &num_steps, &first_step, &base, &next, &reset_count, &al};
-        const hipError_t err = hipLaunchCooperativeKernel(reinterpret_cast<const void *>(&mrl_hanabi_rollout<kV>), dim3(grid), dim3(kRolloutBlock),
-                                                          args, 0, stream);
+        hipError_t err = hipSuccess;
+        with_variant(variant, [&](auto v) {
+            err = hipLaunchCooperativeKernel(reinterpret_cast<const void *>(&mrl_hanabi_rollout<decltype(v)::value>), dim3(grid),
+                                             dim3(kRolloutBlock), args, 0, stream);
+        });
         if (err != hipSuccess) {
             (void)hipGetLastError();
             return false;
@@ -2287,13 +2290,7 @@ struct HanabiSim final : mrl_sim {
     {
         if (num_steps == 0) return;
         if (persistent_ok && !launch_state.device_mode) {  // (a cooperative launch cannot be captured; its counters live on the host)
-            bool launched;
-            switch (variant) {
-            case 2: launched = launch_rollout<2>(num_steps, seed, first_step, stream); break;
-            case 1: launched = launch_rollout<1>(num_steps, seed, first_step, stream); break;
-            default: launched = launch_rollout<0>(num_steps, seed, first_step, stream); break;
-            }
-            if (launched) return;
+            if (launch_rollout(num_steps, seed, first_step, stream)) return;
             persistent_ok = false;  // refused: one launch per step from now on (needs no co-residency)
         }
         const HanabiParams saved = params;
@@ -2305,103 +2302,6 @@ struct HanabiSim final : mrl_sim {
             step(nullptr, stream);
         }
         params = saved;
-    }
-
-    void phase1(const int32_t *actions, hipStream_t stream) override
-    {
-        HanabiParams a = params;
-        a.actions = actions ? actions : action;
-        switch (variant) {
-        case 2: hipLaunchKernelGGL((mrl_hanabi_step<2>), dim3(grid), dim3(kBlock), 0, stream, a.records, a.actions, a.num_worlds, a.chunk, a); break;
-        case 1: hipLaunchKernelGGL((mrl_hanabi_step<1>), dim3(grid), dim3(kBlock), 0, stream, a.records, a.actions, a.num_worlds, a.chunk, a); break;
-        default: hipLaunchKernelGGL((mrl_hanabi_step<0>), dim3(grid), dim3(kBlock), 0, stream, a.records, a.actions, a.num_worlds, a.chunk, a); break;
-        }
-        MRL_HIP(hipGetLastError());
-    }
-
-    void launch_reset(const uint32_t *base, const mrl::GatheredCounts &gathered, hipStream_t stream, bool external_base = false)
-    {
-        if (launch_state.device_mode) launch_state.advance(stream);
-        const mrl::DeviceCounter dc = launch_state.counter_args(counter, external_base);
-        switch (variant) {
-        case 2:
-            hipLaunchKernelGGL((mrl_hanabi_reset<false, 2>), dim3(grid), dim3(kBlock), 0, stream, params, base, 0u,
-                               counter + (parity ^ 1u), reset_count, gathered, dc);
-            break;
-        case 1:
-            hipLaunchKernelGGL((mrl_hanabi_reset<false, 1>), dim3(grid), dim3(kBlock), 0, stream, params, base, 0u,
-                               counter + (parity ^ 1u), reset_count, gathered, dc);
-            break;
-        default:
-            hipLaunchKernelGGL((mrl_hanabi_reset<false, 0>), dim3(grid), dim3(kBlock), 0, stream, params, base, 0u,
-                               counter + (parity ^ 1u), reset_count, gathered, dc);
-            break;
-        }
-        MRL_HIP(hipGetLastError());
-        parity ^= 1u;
-    }
-    void publish_shard_count(hipStream_t stream) override
-    {
-        hipLaunchKernelGGL(mrl::sum_block_counts, dim3(1), dim3(256), 0, stream, params.block_counts, grid, params.shard_count, mrl::mail_of(exchange));
-        MRL_HIP(hipGetLastError());
-    }
-    void phase2(const uint32_t *episode_base_dev, hipStream_t stream) override
-    {
-        launch_reset(episode_base_dev ? episode_base_dev : counter + parity, mrl::GatheredCounts{}, stream, episode_base_dev != nullptr);
-    }
-    void phase2_gathered(const uint32_t *counts, uint32_t num_ranks, uint32_t rank, hipStream_t stream) override
-    {
-        mrl::GatheredCounts g;
-        g.counts = counts;
-        g.num_ranks = num_ranks;
-        g.rank = rank;
-        launch_reset(counter + parity, g, stream);
-    }
-    void phase2_exchanged(hipStream_t stream) override { launch_reset(counter + parity, mrl::polled_counts(exchange, alarm.alarm()), stream); }
-
-    // mrl_reset_worlds: phase 2 on the caller's mask (read through p.done), with a scratch RESET_COUNT (world_reset.hpp)
-    mrl::ResetScratch forced;
-    void reset_worlds(const uint8_t *mask, hipStream_t stream) override
-    {
-        forced.build(mask, num_worlds, grid, params.chunk, stream);
-        HanabiParams q = params;
-        q.done = forced.flags;
-        q.block_counts = forced.block_counts;
-        if (launch_state.device_mode) launch_state.advance(stream);
-        const mrl::DeviceCounter dc = launch_state.counter_args(counter);
-        const uint32_t *base = counter + parity;
-        uint32_t *next = counter + (parity ^ 1u);
-        switch (variant) {
-        case 2: hipLaunchKernelGGL((mrl_hanabi_reset<false, 2>), dim3(grid), dim3(kBlock), 0, stream, q, base, 0u, next, forced.reset_count, mrl::GatheredCounts{}, dc); break;
-        case 1: hipLaunchKernelGGL((mrl_hanabi_reset<false, 1>), dim3(grid), dim3(kBlock), 0, stream, q, base, 0u, next, forced.reset_count, mrl::GatheredCounts{}, dc); break;
-        default: hipLaunchKernelGGL((mrl_hanabi_reset<false, 0>), dim3(grid), dim3(kBlock), 0, stream, q, base, 0u, next, forced.reset_count, mrl::GatheredCounts{}, dc); break;
-        }
-        MRL_HIP(hipGetLastError());
-        parity ^= 1u;
-    }
-
-    void set_episode_counter(uint32_t next_episode, hipStream_t stream) override
-    {
-        if (launch_state.device_mode) {  // which half is current is only known on the device
-            hipLaunchKernelGGL(mrl::set_current_counter, dim3(1), dim3(1), 0, stream, counter, launch_state.dev, next_episode);
-            MRL_HIP(hipGetLastError());
-        } else {
-            MRL_HIP(hipMemcpyAsync(counter + parity, &next_episode, sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-        }
-        MRL_HIP(hipStreamSynchronize(stream));
-    }
-
-    void reseed_shard(uint32_t world_offset, uint32_t num_worlds_total, hipStream_t stream) override
-    {
-        const uint32_t *none = nullptr;
-        uint32_t *no_out = nullptr;
-        switch (variant) {
-        case 2: hipLaunchKernelGGL((mrl_hanabi_reset<true, 2>), dim3(grid), dim3(kBlock), 0, stream, params, none, world_offset, no_out, no_out, mrl::GatheredCounts{}, mrl::DeviceCounter{}); break;
-        case 1: hipLaunchKernelGGL((mrl_hanabi_reset<true, 1>), dim3(grid), dim3(kBlock), 0, stream, params, none, world_offset, no_out, no_out, mrl::GatheredCounts{}, mrl::DeviceCounter{}); break;
-        default: hipLaunchKernelGGL((mrl_hanabi_reset<true, 0>), dim3(grid), dim3(kBlock), 0, stream, params, none, world_offset, no_out, no_out, mrl::GatheredCounts{}, mrl::DeviceCounter{}); break;
-        }
-        MRL_HIP(hipGetLastError());
-        set_episode_counter(num_worlds_total, stream);
     }
 
     bool tensor(int slot, mrl_tensor_desc *out) override
@@ -2429,7 +2329,7 @@ struct HanabiSim final : mrl_sim {
         case MRL_HANABI_GAME: *out = mrl::make_desc(params.records, MRL_UINT8, device, {N, kRecordBytes}); return true;
         case MRL_HANABI_RESET_COUNT: *out = mrl::make_desc(reset_count, MRL_UINT32, device, {1}); return true;
         case MRL_HANABI_SCAN_TIMEOUT: *out = mrl::make_desc(alarm.alarm().dev, MRL_UINT32, device, {1}); return true;
-        case MRL_HANABI_SHARD_COUNT: *out = mrl::make_desc(params.shard_count, MRL_UINT32, device, {1}); return true;
+        case MRL_HANABI_SHARD_COUNT: *out = mrl::make_desc(shard_count, MRL_UINT32, device, {1}); return true;
 #ifdef MRL_DIAG
         case 14:
             if (!params.stamps) return false;
@@ -2482,13 +2382,9 @@ mrl_sim *mrl::create_hanabi(const mrl_hanabi_config *cfg, int gpu_id, uint32_t n
         sim->game = MRL_GAME_HANABI;
         sim->device = gpu_id;
         sim->num_worlds = num_worlds;
-        {
-            const uint32_t groups = (num_worlds + kWorldsPerBlock - 1) / kWorldsPerBlock;
-            const uint32_t blocks = groups < mrl::kMaxScanBlocks ? groups : mrl::kMaxScanBlocks;
-            sim->params.chunk = ((groups + blocks - 1) / blocks) * kWorldsPerBlock;
-            sim->grid = (num_worlds + sim->params.chunk - 1) / sim->params.chunk;
-        }
+        sim->size_scan_grid(kWorldsPerBlock);
         HanabiParams &a = sim->params;
+        a.chunk = sim->chunk;
         const uint32_t K = cfg->colors, R = cfg->ranks, N = num_worlds;
         a.num_worlds = N;
         a.colors = K;
@@ -2529,8 +2425,8 @@ mrl_sim *mrl::create_hanabi(const mrl_hanabi_config *cfg, int gpu_id, uint32_t n
         a.active = sim->arena.alloc<int32_t>((size_t)2 * N);
         a.reward = sim->arena.alloc<float>((size_t)2 * N);
         a.done = sim->arena.alloc<int32_t>(N);
-        a.block_counts = sim->arena.alloc<uint32_t>(sim->grid);
-        a.shard_count = sim->arena.alloc<uint32_t>(1);
+        a.block_counts = sim->block_counts = sim->arena.alloc<uint32_t>(sim->grid);
+        a.shard_count = sim->shard_count = sim->arena.alloc<uint32_t>(1);
 #ifdef MRL_DIAG
         a.ablate = (uint32_t)mrl::debug_get("ablate", 0);
         a.stamps = mrl::debug_get("stamps", 0) ? sim->arena.alloc<unsigned long long>((size_t)sim->grid * kWavesPerBlock * 16) : nullptr;
@@ -2538,19 +2434,13 @@ mrl_sim *mrl::create_hanabi(const mrl_hanabi_config *cfg, int gpu_id, uint32_t n
         sim->action = sim->arena.alloc<int32_t>((size_t)2 * N);
         sim->world_id = sim->arena.alloc<int32_t>((size_t)2 * N, false);
         sim->agent_id = sim->arena.alloc<int32_t>((size_t)2 * N, false);
-        sim->counter = sim->arena.alloc<uint32_t>(2);
-        sim->reset_count = sim->arena.alloc<uint32_t>(1);
-        sim->forced.init(sim->arena, sim->grid, sim->params.chunk, N, false, true);
+        sim->alloc_episode(false, true);  // (block_counts and shard_count are there already)
+        sim->stepped.flags = a.done;
         sim->alarm.init(sim->arena);
         sim->launch_state.init(sim->arena);
         sim->status = sim->arena.alloc<unsigned long long>(sim->grid);
         {
-            // mrl_debug_set fused_step: 0 = the library's choice (one launch whenever a workgroup owns one sub-block),
-            // 1 = one launch where possible, 2 = always two
-            const int64_t knob = mrl::debug_get("fused_step", 0);
-            sim->fused = knob != 2 && sim->params.chunk == (uint32_t)kWorldsPerBlock;
-            sim->heal.mod = (uint32_t)mrl::debug_get("fused_heal_test", 0);
-            sim->heal.seen = sim->arena.alloc<uint32_t>(sim->grid);
+            sim->read_step_knobs(sim->chunk == (uint32_t)kWorldsPerBlock, sim->grid);  // one launch whenever a workgroup owns one sub-block
             const int64_t pairing = mrl::debug_get("hanabi.pairing", 4);  // 4: waves (w, w + 4), 1: (2k, 2k + 1), 0: no leaders
             sim->pair_stride = (pairing & 0xFF) == 1 ? 1u : (pairing & 0xFF) == 0 ? 0u : 4u;
             sim->pair_stride |= (uint32_t)(pairing & 0x100);  // experiment: see the kernel
@@ -2558,23 +2448,16 @@ mrl_sim *mrl::create_hanabi(const mrl_hanabi_config *cfg, int gpu_id, uint32_t n
         {
             // mrl_hanabi_rollout keeps every workgroup alive for the whole rollout and they wait for each
             // other: only usable when the grid fits the GPU in one go and each workgroup owns one sub-block
-            int per_cu = 0, cus = 0;
-            const void *fn = sim->variant == 2 ? reinterpret_cast<const void *>(&mrl_hanabi_rollout<2>)
-                             : sim->variant == 1 ? reinterpret_cast<const void *>(&mrl_hanabi_rollout<1>)
-                                                 : reinterpret_cast<const void *>(&mrl_hanabi_rollout<0>);
-            MRL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kRolloutBlock, 0));
-            MRL_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, gpu_id));
-            // (the occupancy query can be one workgroup per CU too high, MI355X_MICROARCH.md "Residency and
-            // cooperative launch": keep one per CU in hand near the edge; the cooperative launch is the check)
-            const int usable = per_cu > 4 ? per_cu - 1 : per_cu;
-            sim->persistent_ok = !mrl::debug_get("hanabi.no_persistent", 0) && sim->params.chunk == (uint32_t)kWorldsPerBlock &&
-                                 (uint64_t)sim->grid <= (uint64_t)usable * (uint64_t)cus;
+            bool resident = false;
+            with_variant(sim->variant, [&](auto v) {
+                resident = mrl::grid_resident(reinterpret_cast<const void *>(&mrl_hanabi_rollout<decltype(v)::value>), kRolloutBlock, sim->grid, gpu_id);
+            });
+            sim->persistent_ok = !mrl::debug_get("hanabi.no_persistent", 0) && sim->chunk == (uint32_t)kWorldsPerBlock && resident;
             sim->ring = sim->arena.alloc<unsigned long long>((size_t)kRing * sim->grid);
         }
-        hipLaunchKernelGGL(fill_agent_ids, dim3((2 * N + 255) / 256), dim3(256), 0, 0, sim->world_id, sim->agent_id, N);
-        MRL_HIP(hipGetLastError());
+        mrl::fill_ids(sim->world_id, sim->agent_id, 2, N);
         sim->reseed_shard(0, N, 0);
-        if (mrl::debug_get("inject_scan_timeout", 0)) hipLaunchKernelGGL(mrl::raise_alarm_kernel, dim3(1), dim3(1), 0, 0, sim->alarm.alarm());
+        sim->inject_scan_timeout();
         MRL_HIP(hipDeviceSynchronize());
     } catch (...) {
         delete sim;

@@ -19,6 +19,11 @@
 
 namespace mrl {
 
+// The fill kernels behind the simulators' constant tensors; on the null stream.  fill_ids: world_id[i] = i % n,
+// row_id[i] = i / n for i < rows * n.  (kitchen_host.hpp, which includes this header, still repeats the two declarations.)
+void fill_ids(int32_t *world_id, int32_t *row_id, uint32_t rows, uint32_t n);
+void fill_i32(int32_t *dst, int32_t value, size_t count);
+
 // Scratch of a forced reset in the counter games: the phase-2 inputs built from the mask, and the RESET_COUNT phase 2 writes.
 struct ResetScratch {
     unsigned long long *words = nullptr;
