@@ -63,7 +63,7 @@ enum {
 /* element types of exported tensors (madrona::py::Tensor::ElementType subset) */
 enum { MRL_INT8 = 0, MRL_UINT8 = 1, MRL_INT32 = 2, MRL_FLOAT32 = 3, MRL_UINT32 = 4 };
 
-enum { MRL_GAME_OVERCOOKED = 1, MRL_GAME_HANABI = 2, MRL_GAME_CARTPOLE = 3, MRL_GAME_SIMPLECOOKED = 4, MRL_GAME_BALANCE = 5 };
+enum { MRL_GAME_OVERCOOKED = 1, MRL_GAME_HANABI = 2, MRL_GAME_CARTPOLE = 3, MRL_GAME_SIMPLECOOKED = 4, MRL_GAME_BALANCE = 5, MRL_GAME_ACROBOT = 6 };
 
 typedef struct mrl_sim mrl_sim;
 
@@ -255,6 +255,41 @@ enum {
 int mrl_balance_create(int gpu_id, uint32_t num_worlds, mrl_sim **out);
 
 /* ------------------------------------------------------------------ */
+/* Acrobot  (reference: src/acrobat_env, its spelling of Acrobot-v1)    */
+/* ------------------------------------------------------------------ */
+
+/* Slots = ExportID (src/acrobat_env/sim.hpp:15-22); shapes as mgr.cpp's export calls:
+ *   RESET int32 (N,1); ACTION int32 (N,1), values 0/1/2 = torque -1/0/+1 (sim.hpp:28-35); STATE float32 (N,4) =
+ *   (theta1, theta2, omega1, omega2) (sim.hpp:37-49; the Python binding calls it observation_tensor); REWARD float32 (N,1);
+ *   WORLD_ID int32 (N,1); RESET_COUNT uint32 (1); SCAN_TIMEOUT uint32 (1); SHARD_COUNT uint32 (1) (all three as for
+ *   Cartpole); EPISODE_LENGTH int32 (N,1): steps of the world's current episode.
+ * One step = one RK4 step of sim.cpp:68-94 over [0, 0.2] (sim.cpp:116-145), angles wrapped into [-pi, pi], velocities clamped
+ *   to +-4 pi and +-9 pi (sim.cpp:180-183); RESET = (-cos theta1 - cos(theta1 + theta2) > 1) || (EPISODE_LENGTH > 500)
+ *   (sim.cpp:189-200).  A finished world is re-seeded from its new episode's index, four draws mapped to -0.1 + r * 0.2
+ *   (sim.cpp:45-66); world w starts as episode w and the counter at N; episodes are numbered in ascending world order.
+ * REWARD is -1 after every step, the terminating one included: sim.hpp:51-53 promises 0 there, sim.cpp:186 never writes it, and
+ *   the code is what is followed.  It is 0 before the first step.
+ * EPISODE_LENGTH is kept PER WORLD.  The reference keeps one length in the EpisodeManager all worlds share (init.hpp:9;
+ *   sim.cpp:52,169,199): every world increments it and any reset zeroes it, which is Acrobot-v1's truncation for N = 1 only (an
+ *   untouched episode ends at its 501st step).  Here every world behaves as the reference's N = 1 world does.
+ * mrl_rollout_random: action = (h * 3) >> 32 with the hash h of (seed, step, world, player 0) given there. */
+enum {
+    MRL_ACROBOT_RESET = 0,
+    MRL_ACROBOT_ACTION = 1,
+    MRL_ACROBOT_STATE = 2,
+    MRL_ACROBOT_REWARD = 3,
+    MRL_ACROBOT_WORLD_ID = 4,
+    MRL_ACROBOT_RESET_COUNT = 5,
+    MRL_ACROBOT_SCAN_TIMEOUT = 6, /* uint32 (1): see mrl_step */
+    MRL_ACROBOT_SHARD_COUNT = 7,
+    MRL_ACROBOT_EPISODE_LENGTH = 8
+};
+#define MRL_ACROBOT_MAX_STEPS 500 /* sim.cpp:199 */
+
+/* replaces AcrobatSimulator(exec_mode=CUDA, gpu_id, num_worlds) (src/acrobat_env/bindings.cpp) */
+int mrl_acrobot_create(int gpu_id, uint32_t num_worlds, mrl_sim **out);
+
+/* ------------------------------------------------------------------ */
 /* Common                                                               */
 /* ------------------------------------------------------------------ */
 
@@ -411,6 +446,7 @@ int mrl_step_sequence(mrl_sim *sim, const int32_t *actions_dev, uint32_t num_ste
  *   Overcooked  randint(high=6) per agent            scripts/overcooked_example.py:99-106
  *   Cartpole    randint(high=2)                      scripts/cartpole_example.py:53-87
  *   Simplecooked randint(high=6) per agent; Balance beam randint(high=4) per agent (their example scripts)
+ *   Acrobot     randint(high=3)                      (the reference ships no example script for it)
  *   Hanabi      argmax(rand * mask), i.e. a uniformly random legal move of the player
  *               to move                              scripts/hanabi_example.py:53-82
  * All draws come from one counter-based hash of (seed, step index k = first_step,
@@ -419,6 +455,7 @@ int mrl_step_sequence(mrl_sim *sim, const int32_t *actions_dev, uint32_t num_ste
  *     h ^= h>>16; h *= 0x7FEB352D; h ^= h>>15; h *= 0x846CA68B; h ^= h>>16;   (all mod 2^32)
  *   Overcooked  action = (h * 6) >> 32
  *   Cartpole    action = h >> 31                      (q = 0)
+ *   Acrobot     action = (h * 3) >> 32                (q = 0); one launch per step
  *   Hanabi      action = position of the j-th set bit of the mover's 20-bit legal-move
  *               mask, j = (h * popcount(mask)) >> 32  (q = the mover)
  * Every step writes its outputs exactly like mrl_step; afterwards the ACTION tensor holds
@@ -433,9 +470,10 @@ int mrl_rollout_random(mrl_sim *sim, uint32_t num_steps, uint64_t seed, uint32_t
  * inside a step); EnvPool's reset(env_ids) is the same call.
  *   What a reset world becomes: world i is bit-identical to world 0 of a newly built simulator of the same configuration
  *     whose first episode has the index world i receives -- observations, Hanabi STATE / ACTION_MASK / ACTIVE_AGENT /
- *     GAME, the Overcooked STATE_* tensors (and Simplecooked's STATE_DISHES_OUT), Cartpole STATE.  Overcooked and
+ *     GAME, the Overcooked STATE_* tensors (and Simplecooked's STATE_DISHES_OUT), Cartpole STATE, Acrobot STATE
+ *     with EPISODE_LENGTH 0.  Overcooked and
  *     Simplecooked have no episode index: timestep 0, no objects, players on their start cells facing north, empty hands.
- *   Numbering (Hanabi, Cartpole, balance beam): the reset worlds take the episode indices counter, counter + 1, ... in
+ *   Numbering (Hanabi, Cartpole, balance beam, Acrobot): the reset worlds take the episode indices counter, counter + 1, ... in
  *     ascending world order and the counter advances by their number; later episode ends go on from there exactly as if
  *     those worlds had finished in a step.  The call is the two-launch step's phase 2 run on the mask: it follows the
  *     same double-buffered counter (host mode, or the device-side state after mrl_prepare_graph_capture).
@@ -444,7 +482,7 @@ int mrl_rollout_random(mrl_sim *sim, uint32_t num_steps, uint64_t seed, uint32_t
  *   Overcooked / Simplecooked observations go where the most recent step wrote: the simulator's tensor, the slot of
  *     mrl_set_observation_output, or ring slot (k - 1) mod T; where no step has run since that destination was set, where
  *     the next step will write.  A STAGED destination (off a 16-byte boundary) is refused with MRL_ERR_INVALID.
- *   Refused with MRL_ERR_INVALID: a Hanabi, Cartpole or balance-beam simulator that has been through mrl_reseed_shard or
+ *   Refused with MRL_ERR_INVALID: a Hanabi, Cartpole, balance-beam or Acrobot simulator that has been through mrl_reseed_shard or
  *     mrl_exchange_create (numbering across ranks would need an exchange between them); a capturing stream wherever
  *     mrl_step refuses one (a reset captured after mrl_prepare_graph_capture replays correctly); a NULL handle.
  *   It only enqueues work: no host synchronisation.  Every later mrl_step*, mrl_step_many, mrl_step_sequence,

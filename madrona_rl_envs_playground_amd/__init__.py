@@ -1,8 +1,8 @@
 """MI355X-native batched RL-environment step engine (Overcooked, Hanabi,
-Cartpole) behind the API of willwng/madrona_rl_envs_playground.
+Cartpole, balance beam, Acrobot) behind the API of willwng/madrona_rl_envs_playground.
 
-    simulators            OvercookedSimulator / HanabiSimulator / CartpoleSimulator (+ madrona.ExecMode)
-    envs                  OvercookedMadrona, HanabiMadrona, CartpoleMadronaTorch/Numpy
+    simulators            OvercookedSimulator / HanabiSimulator / CartpoleSimulator / AcrobotSimulator ... (+ madrona.ExecMode)
+    envs                  OvercookedMadrona, HanabiMadrona, CartpoleMadronaTorch/Numpy, AcrobotMadronaTorch/Numpy
     pantheonrl_extension  VectorMultiAgentEnv, MadronaEnv, VectorObservation, VectorAgent
     layouts               Overcooked layout data + get_base_layout_params
     distributed           world sharding over the GPUs of a node, RCCL observation gather

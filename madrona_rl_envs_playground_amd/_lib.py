@@ -33,6 +33,7 @@ SYMBOLS = [
     "mrl_scan_timed_out", "mrl_simplecooked_create", "mrl_launch_shape", "mrl_balance_create", "mrl_step_with_actions_i64",
     "mrl_step_phase2_gathered", "mrl_set_observation_output", "mrl_set_observation_ring", "mrl_prepare_graph_capture", "mrl_step_many",
     "mrl_build_hash", "mrl_exchange_create", "mrl_exchange_connect", "mrl_step_exchanged", "mrl_reset_worlds",
+    "mrl_acrobot_create",
 ]
 ABI_VERSION = 4  # MRL_ABI_VERSION of include/mrl_envs.h this binding was written against
 
@@ -142,6 +143,7 @@ def lib():
     L.mrl_hanabi_create.argtypes = [ctypes.POINTER(HanabiConfig), i32, u32, ctypes.POINTER(vp)]
     L.mrl_cartpole_create.argtypes = [i32, u32, ctypes.POINTER(vp)]
     L.mrl_balance_create.argtypes = [i32, u32, ctypes.POINTER(vp)]
+    L.mrl_acrobot_create.argtypes = [i32, u32, ctypes.POINTER(vp)]
     L.mrl_step.argtypes = [vp, vp]
     L.mrl_step_with_actions.argtypes = [vp, vp, vp]
     L.mrl_step_with_actions_i64.argtypes = [vp, vp, vp]

@@ -254,6 +254,14 @@ int mrl_balance_create(int gpu_id, uint32_t num_worlds, mrl_sim **out)
     return guarded([&] { *out = mrl::create_balance(gpu_id, num_worlds); });
 }
 
+int mrl_acrobot_create(int gpu_id, uint32_t num_worlds, mrl_sim **out)
+{
+    if (!out) return MRL_ERR_INVALID;
+    *out = nullptr;
+    mrl::DeviceGuard on(gpu_id);  // the caller's current device is restored on return
+    return guarded([&] { *out = mrl::create_acrobot(gpu_id, num_worlds); });
+}
+
 int mrl_step(mrl_sim *sim, void *hip_stream)
 {
     if (int rc = mrl::need_healthy(sim)) return rc;
@@ -473,7 +481,8 @@ int mrl_reset_worlds(mrl_sim *sim, const uint8_t *mask_dev_or_null, void *hip_st
 {
     if (int rc = mrl::need_healthy(sim)) return rc;
     if (int rc = mrl::need_not_capturing(sim, hip_stream, "mrl_reset_worlds")) return rc;
-    const bool numbered = sim->game == MRL_GAME_HANABI || sim->game == MRL_GAME_CARTPOLE || sim->game == MRL_GAME_BALANCE;
+    const bool numbered = sim->game == MRL_GAME_HANABI || sim->game == MRL_GAME_CARTPOLE || sim->game == MRL_GAME_BALANCE ||
+                          sim->game == MRL_GAME_ACROBOT;
     if (numbered && (sim->reseeded || sim->exchange.mine)) {
         mrl::set_error("mrl_reset_worlds: this simulator is a shard of a larger batch (mrl_reseed_shard / mrl_exchange_create); "
                        "numbering restarted episodes across ranks is not supported");

@@ -6,6 +6,7 @@
     build.madrona_hanabi_example_python      -> HanabiSimulator       (src/hanabi_env/bindings.cpp:8-48)
     build.madrona_cartpole_example_python    -> CartpoleSimulator     (src/cartpole_env/bindings.cpp:8-31)
     build.madrona_balance_example_python     -> BalanceBeamSimulator  (src/balance_beam_env/bindings.cpp:8-34)
+    build.madrona_acrobat_example_python     -> AcrobotSimulator      (src/acrobat_env/bindings.cpp; alias AcrobatSimulator)
 
 Same constructor keywords, same method names; every ``*_tensor()`` returns an
 object whose ``to_torch()`` yields a persistent zero-copy ``torch.Tensor`` on the
@@ -124,6 +125,13 @@ def random_cartpole_action(seed, step, world):
     """Cartpole: the hash's top bit (player 0)."""
     import numpy as np
     return (random_hash(seed, step, world, np.zeros_like(np.asarray(world))) >> np.uint32(31)).astype(np.int32)
+
+
+def random_acrobot_action(seed, step, world):
+    """Acrobot: ``(hash * 3) >> 32`` for (step index, world, player 0)."""
+    import numpy as np
+    h = random_hash(seed, step, world, np.zeros_like(np.asarray(world)))
+    return ((h.astype(np.uint64) * np.uint64(3)) >> np.uint64(32)).astype(np.int32)
 
 
 def random_hanabi_action(seed, step, world, mover, legal_mask):
@@ -501,6 +509,30 @@ class CartpoleSimulator(_Simulator):
     def reset_count_tensor(self): return self._tensor(5)
     def scan_timeout_tensor(self): return self._tensor(6)
     def shard_count_tensor(self): return self._tensor(7)
+
+
+class AcrobotSimulator(_Simulator):
+    """Signature of src/acrobat_env/bindings.cpp (``AcrobatSimulator`` there).  ``observation_tensor`` is the raw state
+    (theta1, theta2, omega1, omega2); ``episode_length_tensor`` is this engine's per-world episode length (the reference
+    keeps one length for all worlds: include/mrl_envs.h)."""
+
+    def __init__(self, exec_mode, gpu_id, num_worlds, debug_compile=True):
+        super().__init__(exec_mode, gpu_id)
+        _lib.check(self._L.mrl_acrobot_create(int(gpu_id), int(num_worlds), ctypes.byref(self._handle)))
+        self._action_numel = int(num_worlds)
+
+    def reset_tensor(self): return self._tensor(0)
+    def action_tensor(self): return self._tensor(1)
+    def observation_tensor(self): return self._tensor(2)
+    def reward_tensor(self): return self._tensor(3)
+    def world_id_tensor(self): return self._tensor(4)
+    def reset_count_tensor(self): return self._tensor(5)
+    def scan_timeout_tensor(self): return self._tensor(6)
+    def shard_count_tensor(self): return self._tensor(7)
+    def episode_length_tensor(self): return self._tensor(8)
+
+
+AcrobatSimulator = AcrobotSimulator  # the reference's binding name
 
 
 class BalanceBeamSimulator(_Simulator):
