@@ -178,6 +178,24 @@ template <typename T> T *upload(mrl::DeviceArena &arena, const T *data, size_t c
 }
 template <typename T> T *upload(mrl::DeviceArena &arena, const std::vector<T> &v) { return upload(arena, v.data(), v.size()); }
 
+// A group's two tables in ONE allocation: the terrain offsets, then the holder table at a 4-byte aligned offset that depends
+// on the number of terrain entries alone -- a kernel compiled for one layout size reaches both through the one pointer it
+// is handed in registers (overcooked.hip, take_hot_args).
+constexpr uint32_t hold_tab_offset(uint32_t terr_entries) { return (terr_entries * 2u + 3u) & ~3u; }
+struct GroupTables {
+    const uint16_t *terr_off;
+    const uint32_t *hold_tab;
+};
+inline GroupTables upload_group_tables(mrl::DeviceArena &arena, const std::vector<uint16_t> &terr, const std::vector<uint32_t> &hold)
+{
+    const uint32_t at = hold_tab_offset((uint32_t)terr.size());
+    std::vector<uint8_t> both(at + hold.size() * sizeof(uint32_t), 0);
+    std::memcpy(both.data(), terr.data(), terr.size() * sizeof(uint16_t));
+    std::memcpy(both.data() + at, hold.data(), hold.size() * sizeof(uint32_t));
+    const uint8_t *d = upload(arena, both);
+    return {reinterpret_cast<const uint16_t *>(d), reinterpret_cast<const uint32_t *>(d + at)};
+}
+
 // What a kitchen simulator is around its step kernels.  Params is the game's kernel-argument struct; this code reads its
 // P, C, W, F, rows, block_bytes and the done / reward / players / cell_obj pointers, and never writes it: where a step
 // writes its observations reaches the game through ring_changed.

@@ -904,6 +904,7 @@ __device__ __forceinline__ void step_body(const StepParams &p, const uint32_t bl
         const uint32_t a_raw = load_action(p, a_at);
         t_loaded = p.timestep[min(w0 + wl, N - 1u)];
         if (p.patch) terrain_request(p, lane, tpos);
+        if (p.direct) hold_request(p, lane, hold);  // (the specialised kernels: no scalar load to wait for, see take_hot_args)
         // while the loads are in flight: the cell -> player map starts empty, the tile of the single-pass encode zeroed
         if (!p.direct)
             for (uint32_t i = lane; i < (p.wpw * C + 3u) >> 2; i += kWave) reinterpret_cast<uint32_t *>(s_cur)[i] = 0xFFFFFFFFu;
@@ -911,7 +912,6 @@ __device__ __forceinline__ void step_body(const StepParams &p, const uint32_t bl
             tile_zero_addtid(s_tile, nw * p.block_bytes + patch_mis);
         else if (p.whole)
             tile_zero(p, lane, s_tile, nw);
-        if (p.direct) hold_request(p, lane, hold);  // not among the preloaded arguments: asked for behind the fill
         STAMP(6);
 #pragma unroll
         for (int k = 0; k < kBatch; k++) {
@@ -929,13 +929,13 @@ __device__ __forceinline__ void step_body(const StepParams &p, const uint32_t bl
         }
     } else {
         if (p.patch) terrain_request(p, lane, tpos);
+        if (p.direct) hold_request(p, lane, hold);
         if (!p.direct)
             for (uint32_t i = lane; i < (p.wpw * C + 3u) >> 2; i += kWave) reinterpret_cast<uint32_t *>(s_cur)[i] = 0xFFFFFFFFu;
         if (p.patch)
             tile_zero_addtid(s_tile, nw * p.block_bytes + patch_mis);
         else if (p.whole)
             tile_zero(p, lane, s_tile, nw);
-        if (p.direct) hold_request(p, lane, hold);
     }
     if (p.patch) terrain_deliver(p, tpos, s_tile + patch_mis, nw);
     if (private_consts) {
@@ -990,9 +990,11 @@ __device__ __forceinline__ void step_body(const StepParams &p, const uint32_t bl
     wave_lds_sync();
 
     // ---------------- store: LDS -> HBM slab, rewards, flags ----------------
-    // The LAST thing a wave does: issued before the observation stream-out these stores sit in front
-    // of it in the wave's vmcnt order, and hipcc parks the wave on `s_waitcnt vmcnt(0)` -- a store
-    // round trip -- as soon as one of their address registers is reused.  Nothing waits for them here.
+    // The LAST thing a wave does.  Issued in front of the observation stream-out instead (player records, reward, clock
+    // and done behind the transition, the cell words behind patch_direct) they cost the headline launch 1.0 us, 7.83 ->
+    // 8.80, although hipcc then puts no `s_waitcnt vmcnt` between them and the first observation store: these are
+    // ordinary stores of partial lines, and in front of the stream they sit in front of it in the memory pipeline of
+    // every wave as well (profiles/r06_a_overcooked_front_order_ab.txt).  Nothing waits for them here.
     auto store_state = [&]() {
         if (p.share && wib != 0) return;  // the siblings computed the same state
         uint32_t *g_obj = p.cell_obj + (size_t)w0 * C;
@@ -1525,6 +1527,9 @@ __device__ __forceinline__ void take_hot_args(StepParams &q, MRL_HOT_ARGS)
     q.actions64 = kI64 ? static_cast<const long long *>(hot_actions) : nullptr;
     q.consts = hot_consts;
     q.terr_off = hot_terr_off;
+    // the holder table lies behind the terrain offsets in the same allocation (kitchen_host.hpp, upload_group_tables): with
+    // terr_entries a constant that is a constant offset from a preloaded pointer, and its load waits for no scalar load
+    q.hold_tab = reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(hot_terr_off) + mrl_kitchen::hold_tab_offset(q.terr_entries));
     q.num_worlds = hot_num_worlds;
     q.per_xcd = hot_per_xcd;
 }
@@ -1902,6 +1907,9 @@ __global__ void __launch_bounds__(kBlock) mrl_overcooked_step_groups_fixed(MRL_H
 {
     StepParams q = fixed_params<kC, kW, kWidth, kPots, kHold>(p);
     take_hot_args<kI64>(q, MRL_HOT_PASS);
+    // (this kernel keeps the struct's pointer: measured, its 32768-world launches lose 0.3-0.7 % with the constant offset,
+    // profiles/r06_a_overcooked_front_order_ab.txt)
+    q.hold_tab = p.hold_tab;
     groups_body<2, kG, kPlain, kSparse>(q);
 }
 
@@ -2340,10 +2348,11 @@ mrl_sim *mrl::create_overcooked(const mrl_overcooked_config *cfg, int gpu_id, ui
         // sim.cpp:642-645; only the patching encode reads it), and the group's holder cells
         const auto upload_tables = [&](StepParams &dst, uint32_t gw) {
             dst.terr_entries = gw * a.rows;
-            dst.terr_off = mrl_kitchen::upload(sim->arena, a.patch ? mrl_kitchen::terrain_offsets(k, gw, a.F, 1u << T_AIR)
-                                                                   : std::vector<uint16_t>(dst.terr_entries, 0));
             const std::vector<uint32_t> tab = hold_table(gw);
-            dst.hold_tab = mrl_kitchen::upload(sim->arena, tab);
+            const mrl_kitchen::GroupTables t = mrl_kitchen::upload_group_tables(
+                sim->arena, a.patch ? mrl_kitchen::terrain_offsets(k, gw, a.F, 1u << T_AIR) : std::vector<uint16_t>(dst.terr_entries, 0), tab);
+            dst.terr_off = t.terr_off;
+            dst.hold_tab = t.hold_tab;
             dst.hold_entries = (uint32_t)tab.size();
         };
         upload_tables(a, a.wpw);
