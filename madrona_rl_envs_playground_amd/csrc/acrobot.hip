@@ -16,7 +16,8 @@
 // Episode indices are taken in ascending world order within a step (see cartpole.hip):
 //   mrl_step             one launch (mrl_acrobot_step_fused, in-kernel look-back, episode_scan.hpp)
 //   mrl_step_phase1 / 2  mrl_acrobot_step : transition, done flag, ballot words, per-workgroup finished counts
-//                        mrl_acrobot_reset: exclusive prefix over the counts, re-seed finished worlds, zero their length
+//                        mrl::reseed_finished<AcrobotReseed>: exclusive prefix over the counts, re-seed finished worlds,
+//                        zero their length (episode_scan.hpp)
 // HBM traffic per world-step: action 4 + state r/w 32 + length r/w 8 + reward 4 + done 4 = 52 B.
 //
 // This is the one step in the tree that is bound by instruction issue, not by bytes: four derivative stages with four
@@ -33,6 +34,7 @@
 // -DMRL_ACROBOT_PLAIN builds the straightforward variant instead: sinf / cosf called where the reference calls them,
 // every expression typed and rounded as sim.cpp writes it, IEEE quotients (tools/acrobot_probe.py times one against the other).
 #include "episode_host.hpp"
+#include "episode_rng.hpp"
 #include "random_policy.hpp"
 
 namespace {
@@ -69,38 +71,19 @@ constexpr float kMaxVel1 = 4 * kPi, kMaxVel2 = 9 * kPi;     // sim.cpp:22-23
 constexpr float kGravity = 9.8f;
 constexpr int32_t kMaxSteps = MRL_ACROBOT_MAX_STEPS;
 
-__device__ __forceinline__ uint32_t seed_of(uint32_t episode)
-{
-    // rng.hpp:7-26
-    uint32_t v0 = episode, v1 = 0, sum = 0;
-#pragma unroll
-    for (int round = 0; round < 8; round++) {
-        sum += 0x9e3779b9u;
-        v0 += ((v1 << 4) + 0xa341316cu) ^ (v1 + sum) ^ ((v1 >> 5) + 0xc8013ea4u);
-        v1 += ((v0 << 4) + 0xad90777du) ^ (v0 + sum) ^ ((v0 >> 5) + 0x7e95761eu);
+// sim.cpp:59-65
+__device__ __forceinline__ float4 fresh_state(uint32_t episode) { return mrl::uniform4(episode, -0.1f, 0.1f - (-0.1f)); }
+
+// what the re-seeding launches store for a world that starts `episode` (mrl::reseed_finished, mrl::reseed_all)
+struct AcrobotReseed {
+    float4 *state;
+    int32_t *length;
+    __device__ __forceinline__ void operator()(uint32_t world, uint32_t episode) const
+    {
+        state[world] = fresh_state(episode);
+        length[world] = 0;  // sim.cpp:52
     }
-    return v0;
-}
-
-__device__ __forceinline__ float next_uniform(uint32_t &g)
-{
-    // rng.hpp:28-36
-    g = 1664525u * g + 1013904223u;
-    return (float)(g & 0x00FFFFFFu) / (float)0x01000000;
-}
-
-__device__ __forceinline__ float4 fresh_state(uint32_t episode)
-{
-    // sim.cpp:59-65
-    uint32_t g = seed_of(episode);
-    const float lo = -0.1f, span = 0.1f - (-0.1f);
-    float4 s;
-    s.x = lo + next_uniform(g) * span;
-    s.y = lo + next_uniform(g) * span;
-    s.z = lo + next_uniform(g) * span;
-    s.w = lo + next_uniform(g) * span;
-    return s;
-}
+};
 
 __device__ __forceinline__ float torque_of(int32_t action)
 {
@@ -370,72 +353,6 @@ __global__ void __launch_bounds__(kBlock, kWavesPerSimd) mrl_acrobot_step(uint32
     }
 }
 
-constexpr uint32_t kTripWords = 64;  // mask words (64 worlds each) the reset launch compacts per trip
-
-// The finished worlds of a trip are compacted into s_list in ascending world order (entry e is the e-th finished world:
-// episode base + running + e), then re-seeded one per thread on dense lanes; a re-seeded world's length starts at 0.
-__global__ void __launch_bounds__(kBlock) mrl_acrobot_reset(uint32_t n, uint32_t chunk, float4 *__restrict__ state,
-                                                            int32_t *__restrict__ length, const uint32_t *__restrict__ block_counts,
-                                                            const unsigned long long *__restrict__ finished_mask,
-                                                            const uint32_t *episode_base, uint32_t *next_counter,
-                                                            uint32_t *__restrict__ reset_count, const mrl::GatheredCounts gathered,
-                                                            const mrl::DeviceCounter device_counter)
-{
-    __shared__ uint32_t s_red[2 * kBlock / 64];
-    __shared__ unsigned long long s_word[kTripWords];
-    __shared__ uint32_t s_before[kTripWords];
-    __shared__ uint32_t s_total;
-    __shared__ uint16_t s_list[kTripWords * 64];
-    const bool last_block = blockIdx.x == gridDim.x - 1;
-    uint32_t unused_epoch = 0;
-    device_counter.apply(episode_base, next_counter, unused_epoch);  // (the launch state may live in device memory: common.hpp)
-    const uint32_t mine = block_counts[blockIdx.x];
-    const uint32_t first = blockIdx.x * chunk, last = min(n, first + chunk);
-    const uint32_t words = (last - first + 63u) >> 6;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    // the first trip's mask words are requested before the prefix is summed
-    unsigned long long word = threadIdx.x < min(words, kTripWords) ? finished_mask[(first >> 6) + threadIdx.x] : 0ull;
-    if (mine == 0 && !last_block) return;  // nothing finished here (uniform per workgroup)
-    uint32_t grand_total = 0;
-    uint32_t running = mrl::scan_prefix(block_counts, gridDim.x, blockIdx.x, s_red, last_block, &grand_total);
-    uint32_t base = *episode_base, all_ranks = grand_total;
-    const uint32_t counter_now = base;
-    if (gathered.counts) base += mrl::lower_ranks(gathered, &all_ranks);  // sharded batch: the ranks below come first
-    for (uint32_t w0 = 0; w0 < words; w0 += kTripWords) {  // uniform trip count
-        const uint32_t here = min(words - w0, kTripWords);
-        if (wave == 0) {
-            if (w0 > 0) word = lane < here ? finished_mask[(first >> 6) + w0 + lane] : 0ull;
-            const uint32_t c = (uint32_t)__popcll(word);
-            uint32_t x = c;
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t y = __shfl_up(x, off, 64);
-                x += lane >= (uint32_t)off ? y : 0u;
-            }
-            s_word[lane] = word;
-            s_before[lane] = x - c;
-            if (lane == 63) s_total = x;
-        }
-        __syncthreads();
-        const uint32_t total = s_total;
-        for (uint32_t k = wave; k < here; k += kBlock / 64) {  // one wave per word, lane = bit
-            const unsigned long long m = s_word[k];
-            if ((m >> lane) & 1ull) s_list[s_before[k] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)((k << 6) + lane);
-        }
-        __syncthreads();
-        for (uint32_t e = threadIdx.x; e < total; e += kBlock) {
-            const uint32_t w = first + (w0 << 6) + s_list[e];
-            state[w] = fresh_state(base + running + e);
-            length[w] = 0;  // sim.cpp:52
-        }
-        running += total;
-        __syncthreads();  // s_word / s_before / s_list are rewritten by the next trip
-    }
-    if (last_block && threadIdx.x == 0) {
-        *reset_count = grand_total;
-        *next_counter = gathered.counts ? counter_now + all_ranks : base + grand_total;
-    }
-}
-
 // How many of workgroup j's worlds finish in this step, worked out by ONE wave of another workgroup from j's inputs in HBM
 // (state, length, and the action or its draw): what the healing look-back of the single-launch step calls for a workgroup
 // whose own count has not appeared (episode_scan.hpp).  Unlike Cartpole's, the flag needs the whole transition.
@@ -571,24 +488,10 @@ __global__ void __launch_bounds__(kBlock, kWavesPerSimd) mrl_acrobot_step_fused(
     }
 }
 
-// construction / mrl_reseed_shard: world i of the shard is global world world_offset + i, in its first episode
-__global__ void mrl_acrobot_init(uint32_t n, uint32_t world_offset, float4 *state, int32_t *world_id)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        state[i] = fresh_state(world_offset + i);  // the constructor gives world i episode i (sim.cpp:233-234)
-        world_id[i] = (int32_t)i;
-    }
-}
-
 struct AcrobotSim final : mrl::EpisodeSim {
-    int32_t *action = nullptr, *done = nullptr, *world_id = nullptr, *length = nullptr;
+    int32_t *done = nullptr, *world_id = nullptr, *length = nullptr;
     float4 *state = nullptr;
     float *reward = nullptr;
-    // single-launch step (mrl_acrobot_step_fused)
-    uint32_t *status = nullptr;
-    unsigned long long *group_total = nullptr;  // per 256 workgroups (mrl::grouped_prefix)
-    uint32_t fused_grid = 0;
 
     void launch_fused(const int32_t *actions, const Drawn &drawn, const mrl::FusedExchange &fx, const Counters &c, hipStream_t stream) override
     {
@@ -596,7 +499,7 @@ struct AcrobotSim final : mrl::EpisodeSim {
                            length, reward, done, status, group_total, epoch, c.base, c.next, reset_count, drawn.action_out, drawn.seed,
                            drawn.step, heal, c.device, fx);
     }
-    void launch_step(const int32_t *actions, int32_t *action_out, uint64_t seed, uint32_t sample_step, hipStream_t stream)
+    void launch_step(const int32_t *actions, int32_t *action_out, uint64_t seed, uint32_t sample_step, hipStream_t stream) override
     {
         hipLaunchKernelGGL(mrl_acrobot_step, dim3(grid), dim3(kBlock), 0, stream, num_worlds, chunk, actions ? actions : action, state, length,
                            reward, done, block_counts, stepped.words, action_out, seed, sample_step);
@@ -605,25 +508,13 @@ struct AcrobotSim final : mrl::EpisodeSim {
     void phase1(const int32_t *actions, hipStream_t stream) override { launch_step(actions, nullptr, 0, 0, stream); }
     void launch_reseed(const Finished &from, const mrl::GatheredCounts &gathered, const Counters &c, hipStream_t stream) override
     {
-        hipLaunchKernelGGL(mrl_acrobot_reset, dim3(grid), dim3(kBlock), 0, stream, num_worlds, chunk, state, length, from.block_counts,
-                           from.words, c.base, c.next, from.reset_count, gathered, c.device);
-    }
-    // one launch per step (two without the single-launch step); the draws are made inside the step
-    void rollout_random(uint32_t num_steps, uint64_t seed, uint32_t first_step, hipStream_t stream) override
-    {
-        for (uint32_t k = 0; k < num_steps; k++) {
-            if (fused) {
-                fused_step(action, Drawn{action, seed, first_step + k}, mrl::FusedExchange{}, stream);
-            } else {
-                launch_step(action, action, seed, first_step + k, stream);
-                phase2(nullptr, stream);
-            }
-        }
+        hipLaunchKernelGGL((mrl::reseed_finished<kBlock, AcrobotReseed>), dim3(grid), dim3(kBlock), 0, stream, num_worlds, chunk,
+                           AcrobotReseed{state, length}, from.block_counts, from.words, c.base, c.next, from.reset_count, gathered, c.device);
     }
     void reseed_shard(uint32_t world_offset, uint32_t num_worlds_total, hipStream_t stream) override
     {
-        hipLaunchKernelGGL(mrl_acrobot_init, dim3((num_worlds + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, num_worlds, world_offset,
-                           state, world_id);
+        hipLaunchKernelGGL(mrl::reseed_all<AcrobotReseed>, dim3((num_worlds + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, num_worlds,
+                           world_offset, AcrobotReseed{state, length});
         MRL_HIP(hipGetLastError());
         MRL_HIP(hipMemsetAsync(length, 0, sizeof(int32_t) * num_worlds, stream));
         MRL_HIP(hipMemsetAsync(done, 0, sizeof(int32_t) * num_worlds, stream));
@@ -683,17 +574,11 @@ mrl_sim *mrl::create_acrobot(int gpu_id, uint32_t num_worlds)
         sim->state = sim->arena.alloc<float4>(num_worlds);
         sim->reward = sim->arena.alloc<float>(num_worlds);
         sim->alloc_episode(true, false);
-        {
-            const uint32_t blocks = (num_worlds + kGroupWorlds - 1) / kGroupWorlds;
-            if (blocks <= mrl::kMaxFusedBlocks) {
-                sim->fused_grid = blocks;
-                sim->status = sim->arena.alloc<uint32_t>(blocks);
-                sim->group_total = sim->arena.alloc<unsigned long long>((blocks + mrl::kGroup - 1) / mrl::kGroup);
-            }
-        }
+        sim->alloc_fused(kGroupWorlds);
         sim->alarm.init(sim->arena);
         sim->launch_state.init(sim->arena);
         sim->read_step_knobs(sim->fused_grid != 0, sim->fused_grid);  // one launch wherever it exists
+        mrl::fill_ids(sim->world_id, nullptr, 1, num_worlds);
         sim->reseed_shard(0, num_worlds, 0);  // Sim::Sim (sim.cpp:216-236): world w starts as episode w
         sim->inject_scan_timeout();
         MRL_HIP(hipDeviceSynchronize());

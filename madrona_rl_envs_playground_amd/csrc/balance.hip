@@ -16,35 +16,17 @@
 //
 // Episode indices are taken in ascending world order within a step (see cartpole.hip):
 //   mrl_step_phase1  mrl_balance_step : moves, history, reward, done flag, per-workgroup finished counts
-//   mrl_step_phase2  mrl_balance_reset: exclusive prefix over the counts, re-seed finished worlds
+//   mrl_step_phase2  mrl::reseed_finished<BalanceReseed>: exclusive prefix over the counts, re-seed finished worlds
+//                    (episode_scan.hpp)
 // and mrl_step is the two in a row.
 #include "episode_host.hpp"
+#include "episode_rng.hpp"
 #include "random_policy.hpp"
 
 namespace {
 
 constexpr int kBlock = 256;
 constexpr int kTime = 3, kSpaces = 5, kBuffer = 2, kRow = 2 * kTime + 1;  // sim.cpp:9-13, sim.hpp:8
-
-__device__ __forceinline__ uint32_t seed_of(uint32_t episode)
-{
-    // rng.hpp:7-26
-    uint32_t v0 = episode, v1 = 0, sum = 0;
-#pragma unroll
-    for (int round = 0; round < 8; round++) {
-        sum += 0x9e3779b9u;
-        v0 += ((v1 << 4) + 0xa341316cu) ^ (v1 + sum) ^ ((v1 >> 5) + 0xc8013ea4u);
-        v1 += ((v0 << 4) + 0xad90777du) ^ (v0 + sum) ^ ((v0 >> 5) + 0x7e95761eu);
-    }
-    return v0;
-}
-
-__device__ __forceinline__ float next_uniform(uint32_t &g)
-{
-    // rng.hpp:28-36
-    g = 1664525u * g + 1013904223u;
-    return (float)(g & 0x00FFFFFFu) / (float)0x01000000;
-}
 
 struct Row {
     int32_t x[kRow];  // x[0..5] history, x[6] = time left
@@ -69,9 +51,9 @@ __device__ __forceinline__ void store_row(int32_t *obs, uint32_t n, uint32_t age
 // resetWorld (sim.cpp:45-74): positions from the episode's generator, empty history
 __device__ __forceinline__ void fresh_rows(uint32_t episode, Row &r0, Row &r1)
 {
-    uint32_t g = seed_of(episode);
-    const int32_t loc0 = (int32_t)(kSpaces * next_uniform(g));
-    const int32_t loc1 = (int32_t)(kSpaces * next_uniform(g));
+    uint32_t g = mrl::seed_of(episode);
+    const int32_t loc0 = (int32_t)(kSpaces * mrl::next_uniform(g));
+    const int32_t loc1 = (int32_t)(kSpaces * mrl::next_uniform(g));
 #pragma unroll
     for (int k = 0; k < 2 * kTime; k++) r0.x[k] = r1.x[k] = 0;
     r0.x[0] = loc0 + kBuffer;
@@ -80,6 +62,19 @@ __device__ __forceinline__ void fresh_rows(uint32_t episode, Row &r0, Row &r1)
     r1.x[kTime] = loc0 + kBuffer;
     r0.x[2 * kTime] = r1.x[2 * kTime] = kTime - 1;
 }
+
+// what the re-seeding launches store for a world that starts `episode` (mrl::reseed_finished, mrl::reseed_all)
+struct BalanceReseed {
+    int32_t *obs;
+    uint32_t n;
+    __device__ __forceinline__ void operator()(uint32_t world, uint32_t episode) const
+    {
+        Row r0, r1;
+        fresh_rows(episode, r0, r1);
+        store_row(obs, n, 0, world, r0);
+        store_row(obs, n, 1, world, r1);
+    }
+};
 
 __device__ __forceinline__ int32_t move_of(int32_t choice)
 {
@@ -173,82 +168,6 @@ __global__ void __launch_bounds__(kBlock) mrl_balance_step(uint32_t n, uint32_t 
         uint32_t total = 0;
         for (uint32_t w = 0; w < kBlock / 64; w++) total += s_wave[w];
         block_counts[blockIdx.x] = total;
-    }
-}
-
-// kAll: (re)initialise every world as episode world_offset + world (construction / mrl_reseed_shard)
-constexpr uint32_t kTripWords = 64;  // mask words (64 worlds each) the reset launch compacts per trip
-template <bool kAll>
-__global__ void __launch_bounds__(kBlock) mrl_balance_reset(uint32_t n, uint32_t chunk, const unsigned long long *__restrict__ finished_mask,
-                                                            int32_t *__restrict__ obs, const uint32_t *__restrict__ block_counts,
-                                                            const uint32_t *episode_base, uint32_t world_offset,
-                                                            uint32_t *next_counter, uint32_t *__restrict__ reset_count,
-                                                            const mrl::GatheredCounts gathered, const mrl::DeviceCounter device_counter)
-{
-    __shared__ uint32_t s_red[2 * kBlock / 64];
-    __shared__ unsigned long long s_word[kTripWords];
-    __shared__ uint32_t s_before[kTripWords];
-    __shared__ uint32_t s_total;
-    __shared__ uint16_t s_list[kTripWords * 64];
-    const bool last_block = blockIdx.x == gridDim.x - 1;
-    const uint32_t first = blockIdx.x * chunk, last = min(n, first + chunk);
-    if (kAll) {
-        for (uint32_t w = first + threadIdx.x; w < last; w += kBlock) {
-            Row r0, r1;
-            fresh_rows(world_offset + w, r0, r1);
-            store_row(obs, n, 0, w, r0);
-            store_row(obs, n, 1, w, r1);
-        }
-        return;
-    }
-    const uint32_t words = (last - first + 63u) >> 6;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t unused_epoch = 0;
-    device_counter.apply(episode_base, next_counter, unused_epoch);  // (the launch state may live in device memory: common.hpp)
-    // the first trip's mask words are requested before the prefix is summed
-    unsigned long long word = threadIdx.x < min(words, kTripWords) ? finished_mask[(first >> 6) + threadIdx.x] : 0ull;
-    if (block_counts[blockIdx.x] == 0 && !last_block) return;  // nothing finished here (uniform per workgroup)
-    uint32_t grand_total = 0;
-    uint32_t running = mrl::scan_prefix(block_counts, gridDim.x, blockIdx.x, s_red, last_block, &grand_total);
-    uint32_t base = *episode_base, all_ranks = grand_total;
-    const uint32_t counter_now = base;
-    if (gathered.counts) base += mrl::lower_ranks(gathered, &all_ranks);  // sharded batch: the ranks below come first
-    // finished worlds of a trip are compacted into s_list in ascending world order (entry e is the e-th finished
-    // world: episode base + running + e), then re-seeded one per thread on dense lanes
-    for (uint32_t w0 = 0; w0 < words; w0 += kTripWords) {  // uniform trip count
-        const uint32_t here = min(words - w0, kTripWords);
-        if (wave == 0) {
-            if (w0 > 0) word = lane < here ? finished_mask[(first >> 6) + w0 + lane] : 0ull;
-            const uint32_t c = (uint32_t)__popcll(word);
-            uint32_t x = c;
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t y = __shfl_up(x, off, 64);
-                x += lane >= (uint32_t)off ? y : 0u;
-            }
-            s_word[lane] = word;
-            s_before[lane] = x - c;
-            if (lane == 63) s_total = x;
-        }
-        __syncthreads();
-        const uint32_t total = s_total;
-        for (uint32_t k = wave; k < here; k += kBlock / 64) {  // one wave per word, lane = bit
-            const unsigned long long m = s_word[k];
-            if ((m >> lane) & 1ull) s_list[s_before[k] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)((k << 6) + lane);
-        }
-        __syncthreads();
-        for (uint32_t e = threadIdx.x; e < total; e += kBlock) {
-            const uint32_t w = first + (w0 << 6) + s_list[e];
-            Row r0, r1;
-            fresh_rows(base + running + e, r0, r1);
-            store_row(obs, n, 0, w, r0);
-            store_row(obs, n, 1, w, r1);
-        }
-        running += total;
-        __syncthreads();  // s_word / s_before / s_list are rewritten by the next trip
-    }
-    if (last_block && threadIdx.x == 0) {
-        *reset_count = grand_total;
-        *next_counter = gathered.counts ? counter_now + all_ranks : base + grand_total;
     }
 }
 
@@ -369,19 +288,15 @@ __global__ void __launch_bounds__(kBlock) mrl_balance_step_fused(uint32_t n, con
 }
 
 struct BalanceSim final : mrl::EpisodeSim {
-    int32_t *action = nullptr, *obs = nullptr, *done = nullptr, *world_id = nullptr, *agent_id = nullptr, *active = nullptr, *mask = nullptr;
+    int32_t *obs = nullptr, *done = nullptr, *world_id = nullptr, *agent_id = nullptr, *active = nullptr, *mask = nullptr;
     float *reward = nullptr;
-    // single-launch step (mrl_balance_step_fused)
-    uint32_t *status = nullptr;                 // 32-bit status words, and per 256 workgroups their total (mrl::grouped_prefix)
-    unsigned long long *group_total = nullptr;
-    uint32_t fused_grid = 0;
 
     void launch_fused(const int32_t *actions, const Drawn &drawn, const mrl::FusedExchange &fx, const Counters &c, hipStream_t stream) override
     {
         hipLaunchKernelGGL(mrl_balance_step_fused, dim3(fused_grid), dim3(kBlock), 0, stream, num_worlds, actions ? actions : action, obs, reward,
                            done, status, group_total, epoch, c.base, c.next, reset_count, drawn.action_out, drawn.seed, drawn.step, heal, c.device, fx);
     }
-    void launch_step(const int32_t *actions, int32_t *action_out, uint64_t seed, uint32_t sample_step, hipStream_t stream)
+    void launch_step(const int32_t *actions, int32_t *action_out, uint64_t seed, uint32_t sample_step, hipStream_t stream) override
     {
         hipLaunchKernelGGL(mrl_balance_step, dim3(grid), dim3(kBlock), 0, stream, num_worlds, chunk, actions ? actions : action, obs, reward,
                            done, block_counts, stepped.words, action_out, seed, sample_step);
@@ -390,26 +305,13 @@ struct BalanceSim final : mrl::EpisodeSim {
     void phase1(const int32_t *actions, hipStream_t stream) override { launch_step(actions, nullptr, 0, 0, stream); }
     void launch_reseed(const Finished &from, const mrl::GatheredCounts &gathered, const Counters &c, hipStream_t stream) override
     {
-        hipLaunchKernelGGL((mrl_balance_reset<false>), dim3(grid), dim3(kBlock), 0, stream, num_worlds, chunk, from.words, obs, from.block_counts,
-                           c.base, 0u, c.next, from.reset_count, gathered, c.device);
-    }
-    void rollout_random(uint32_t num_steps, uint64_t seed, uint32_t first_step, hipStream_t stream) override
-    {
-        for (uint32_t k = 0; k < num_steps; k++) {
-            if (fused) {
-                fused_step(action, Drawn{action, seed, first_step + k}, mrl::FusedExchange{}, stream);
-            } else {
-                launch_step(action, action, seed, first_step + k, stream);
-                phase2(nullptr, stream);
-            }
-        }
+        hipLaunchKernelGGL((mrl::reseed_finished<kBlock, BalanceReseed>), dim3(grid), dim3(kBlock), 0, stream, num_worlds, chunk,
+                           BalanceReseed{obs, num_worlds}, from.block_counts, from.words, c.base, c.next, from.reset_count, gathered, c.device);
     }
     void reseed_shard(uint32_t world_offset, uint32_t num_worlds_total, hipStream_t stream) override
     {
-        const uint32_t *none = nullptr;
-        uint32_t *no_out = nullptr;
-        hipLaunchKernelGGL((mrl_balance_reset<true>), dim3(grid), dim3(kBlock), 0, stream, num_worlds, chunk, stepped.words, obs, block_counts, none,
-                           world_offset, no_out, no_out, mrl::GatheredCounts{}, mrl::DeviceCounter{});
+        hipLaunchKernelGGL(mrl::reseed_all<BalanceReseed>, dim3((num_worlds + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, num_worlds,
+                           world_offset, BalanceReseed{obs, num_worlds});
         MRL_HIP(hipGetLastError());
         MRL_HIP(hipMemsetAsync(done, 0, sizeof(int32_t) * num_worlds, stream));
         MRL_HIP(hipMemsetAsync(reward, 0, sizeof(float) * 2 * num_worlds, stream));
@@ -472,15 +374,8 @@ mrl_sim *mrl::create_balance(int gpu_id, uint32_t num_worlds)
         sim->alloc_episode(true, false);
         sim->launch_state.init(sim->arena);
         sim->alarm.init(sim->arena);
-        {
-            const uint32_t blocks = (num_worlds + kFusedWorlds * kBlock - 1) / (kFusedWorlds * kBlock);
-            if (blocks <= mrl::kMaxFusedBlocks) {
-                sim->fused_grid = blocks;
-                sim->status = sim->arena.alloc<uint32_t>(blocks);
-                sim->group_total = sim->arena.alloc<unsigned long long>((blocks + mrl::kGroup - 1) / mrl::kGroup);
-            }
-            sim->read_step_knobs(sim->fused_grid != 0, sim->fused_grid);  // one launch: every row written once
-        }
+        sim->alloc_fused(kFusedWorlds * kBlock);
+        sim->read_step_knobs(sim->fused_grid != 0, sim->fused_grid);  // one launch: every row written once
         mrl::fill_ids(sim->world_id, sim->agent_id, 2, num_worlds);
         mrl::fill_i32(sim->active, 1, 2 * N);
         mrl::fill_i32(sim->mask, 1, 2 * N * 4);

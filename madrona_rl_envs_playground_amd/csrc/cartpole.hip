@@ -14,9 +14,10 @@
 //   mrl_step             one launch (mrl_cartpole_step_fused, in-kernel prefix, episode_scan.hpp)
 //   mrl_step_phase1 / 2  two launches for sharded batches:
 //     mrl_cartpole_step : dynamics + done flag + per-workgroup reset counts
-//     mrl_cartpole_reset: exclusive prefix over the counts, re-seed finished worlds
+//     mrl::reseed_finished<CartpoleReseed>: exclusive prefix over the counts, re-seed finished worlds (episode_scan.hpp)
 // HBM traffic per world-step: action 4 + state r/w 32 + reward 4 + done 4 = 44 B.
 #include "episode_host.hpp"
+#include "episode_rng.hpp"
 #include "random_policy.hpp"
 
 #include <cstdlib>
@@ -38,38 +39,14 @@ constexpr int kBlock = 256;
 #define PI_D 3.141592653589793238463
 #define THETA_THRESHOLD (12 * 2 * PI_D / 360)
 
-__device__ __forceinline__ uint32_t seed_of(uint32_t episode)
-{
-    // rng.hpp:7-26
-    uint32_t v0 = episode, v1 = 0, sum = 0;
-#pragma unroll
-    for (int round = 0; round < 8; round++) {
-        sum += 0x9e3779b9u;
-        v0 += ((v1 << 4) + 0xa341316cu) ^ (v1 + sum) ^ ((v1 >> 5) + 0xc8013ea4u);
-        v1 += ((v0 << 4) + 0xad90777du) ^ (v0 + sum) ^ ((v0 >> 5) + 0x7e95761eu);
-    }
-    return v0;
-}
+// sim.cpp:55-65
+__device__ __forceinline__ float4 fresh_state(uint32_t episode) { return mrl::uniform4(episode, -0.05f, 0.05f - (-0.05f)); }
 
-__device__ __forceinline__ float next_uniform(uint32_t &g)
-{
-    // rng.hpp:28-36
-    g = 1664525u * g + 1013904223u;
-    return (float)(g & 0x00FFFFFFu) / (float)0x01000000;
-}
-
-__device__ __forceinline__ float4 fresh_state(uint32_t episode)
-{
-    // sim.cpp:55-65
-    uint32_t g = seed_of(episode);
-    const float lo = -0.05f, span = 0.05f - (-0.05f);
-    float4 s;
-    s.x = lo + next_uniform(g) * span;
-    s.y = lo + next_uniform(g) * span;
-    s.z = lo + next_uniform(g) * span;
-    s.w = lo + next_uniform(g) * span;
-    return s;
-}
+// what the re-seeding launches store for a world that starts `episode` (mrl::reseed_finished, mrl::reseed_all)
+struct CartpoleReseed {
+    float4 *state;
+    __device__ __forceinline__ void operator()(uint32_t world, uint32_t episode) const { state[world] = fresh_state(episode); }
+};
 
 // ---- the transition (sim.cpp:68-96), in four arithmetic variants (mrl_debug_set "cartpole.variant") ----
 // The reference mixes float state with double literals, so nearly every intermediate is a double and the three
@@ -279,71 +256,6 @@ __global__ void __launch_bounds__(kBlock) mrl_cartpole_step(uint32_t n, uint32_t
         uint32_t total = 0;
         for (uint32_t w = 0; w < kBlock / 64; w++) total += s_wave[w];
         block_counts[blockIdx.x] = total;
-    }
-}
-
-constexpr uint32_t kTripWords = 64;  // mask words (64 worlds each) the reset launch compacts per trip
-
-// The finished worlds of a trip are first compacted into s_list in ascending world order (entry e
-// is the e-th finished world, so its episode is base + running + e), then re-seeded one per
-// thread: the seed hash is ~150 dependent instructions, so it runs once on dense lanes rather
-// than once per mask word on the few lanes whose bit is set.
-__global__ void __launch_bounds__(kBlock) mrl_cartpole_reset(uint32_t n, uint32_t chunk, float4 *__restrict__ state,
-                                                             const uint32_t *__restrict__ block_counts,
-                                                             const unsigned long long *__restrict__ finished_mask,
-                                                             const uint32_t *episode_base, uint32_t *next_counter,
-                                                             uint32_t *__restrict__ reset_count, const mrl::GatheredCounts gathered,
-                                                             const mrl::DeviceCounter device_counter)
-{
-    __shared__ uint32_t s_red[2 * kBlock / 64];
-    __shared__ unsigned long long s_word[kTripWords];
-    __shared__ uint32_t s_before[kTripWords];
-    __shared__ uint32_t s_total;
-    __shared__ uint16_t s_list[kTripWords * 64];
-    const bool last_block = blockIdx.x == gridDim.x - 1;
-    uint32_t unused_epoch = 0;
-    device_counter.apply(episode_base, next_counter, unused_epoch);  // (the launch state may live in device memory: common.hpp)
-    const uint32_t mine = block_counts[blockIdx.x];
-    const uint32_t first = blockIdx.x * chunk, last = min(n, first + chunk);
-    const uint32_t words = (last - first + 63u) >> 6;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    // the first trip's mask words are requested before the prefix is summed
-    unsigned long long word = threadIdx.x < min(words, kTripWords) ? finished_mask[(first >> 6) + threadIdx.x] : 0ull;
-    if (mine == 0 && !last_block) return;  // nothing finished here (uniform per workgroup)
-    uint32_t grand_total = 0;
-    uint32_t running = mrl::scan_prefix(block_counts, gridDim.x, blockIdx.x, s_red, last_block, &grand_total);
-    uint32_t base = *episode_base, all_ranks = grand_total;
-    const uint32_t counter_now = base;
-    if (gathered.counts) base += mrl::lower_ranks(gathered, &all_ranks);  // sharded batch: the ranks below come first
-    for (uint32_t w0 = 0; w0 < words; w0 += kTripWords) {  // uniform trip count
-        const uint32_t here = min(words - w0, kTripWords);
-        if (wave == 0) {
-            if (w0 > 0) word = lane < here ? finished_mask[(first >> 6) + w0 + lane] : 0ull;
-            const uint32_t c = (uint32_t)__popcll(word);
-            uint32_t x = c;
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t y = __shfl_up(x, off, 64);
-                x += lane >= (uint32_t)off ? y : 0u;
-            }
-            s_word[lane] = word;
-            s_before[lane] = x - c;
-            if (lane == 63) s_total = x;
-        }
-        __syncthreads();
-        const uint32_t total = s_total;
-        for (uint32_t k = wave; k < here; k += kBlock / 64) {  // one wave per word, lane = bit
-            const unsigned long long m = s_word[k];
-            if ((m >> lane) & 1ull) s_list[s_before[k] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)((k << 6) + lane);
-        }
-        __syncthreads();
-        for (uint32_t e = threadIdx.x; e < total; e += kBlock)
-            state[first + (w0 << 6) + s_list[e]] = fresh_state(base + running + e);
-        running += total;
-        __syncthreads();  // s_word / s_before / s_list are rewritten by the next trip
-    }
-    if (last_block && threadIdx.x == 0) {
-        *reset_count = grand_total;
-        *next_counter = gathered.counts ? counter_now + all_ranks : base + grand_total;
     }
 }
 
@@ -709,15 +621,6 @@ __global__ void mrl_cartpole_draw_actions(int32_t *action, uint32_t n, uint64_t 
     if (i < n) action[i] = (int32_t)(mrl::policy_hash(seed, step, i, 0) >> 31);
 }
 
-__global__ void mrl_cartpole_init(uint32_t n, uint32_t world_offset, float4 *state, int32_t *world_id)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        state[i] = fresh_state(world_offset + i);  // the constructor gives world i episode i (sim.cpp:141)
-        world_id[i] = (int32_t)i;
-    }
-}
-
 // runs f(std::integral_constant<int, V>) for the arithmetic variant picked at creation
 template <typename F> void with_variant(int variant, F &&f)
 {
@@ -731,13 +634,9 @@ template <typename F> void with_variant(int variant, F &&f)
 
 struct CartpoleSim final : mrl::EpisodeSim {
     int variant = kDefaultVariant;  // arithmetic of the transition (mrl_debug_set cartpole.variant: 1 + Variant; 0 = the default)
-    int32_t *action = nullptr, *done = nullptr, *world_id = nullptr;
+    int32_t *done = nullptr, *world_id = nullptr;
     float4 *state = nullptr;
     float *reward = nullptr;
-    // single-launch step (see mrl_cartpole_step_fused)
-    uint32_t *status = nullptr;
-    unsigned long long *group_total = nullptr;  // per 64 workgroups (see mrl_cartpole_step_fused)
-    uint32_t fused_grid = 0;
 #ifdef MRL_DIAG
     unsigned long long *stamps = nullptr;
 #endif
@@ -806,14 +705,14 @@ struct CartpoleSim final : mrl::EpisodeSim {
 
     void launch_reseed(const Finished &from, const mrl::GatheredCounts &gathered, const Counters &c, hipStream_t stream) override
     {
-        hipLaunchKernelGGL(mrl_cartpole_reset, dim3(grid), dim3(kBlock), 0, stream, num_worlds, chunk, state, from.block_counts, from.words,
-                           c.base, c.next, from.reset_count, gathered, c.device);
+        hipLaunchKernelGGL((mrl::reseed_finished<kBlock, CartpoleReseed>), dim3(grid), dim3(kBlock), 0, stream, num_worlds, chunk,
+                           CartpoleReseed{state}, from.block_counts, from.words, c.base, c.next, from.reset_count, gathered, c.device);
     }
 
     void reseed_shard(uint32_t world_offset, uint32_t num_worlds_total, hipStream_t stream) override
     {
-        hipLaunchKernelGGL(mrl_cartpole_init, dim3((num_worlds + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, num_worlds,
-                           world_offset, state, world_id);
+        hipLaunchKernelGGL(mrl::reseed_all<CartpoleReseed>, dim3((num_worlds + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, num_worlds,
+                           world_offset, CartpoleReseed{state});  // the constructor gives world i episode i (sim.cpp:141)
         MRL_HIP(hipGetLastError());
         MRL_HIP(hipMemsetAsync(done, 0, sizeof(int32_t) * num_worlds, stream));
         MRL_HIP(hipMemsetAsync(reward, 0, sizeof(float) * num_worlds, stream));
@@ -877,17 +776,11 @@ mrl_sim *mrl::create_cartpole(int gpu_id, uint32_t num_worlds)
         sim->state = sim->arena.alloc<float4>(num_worlds);
         sim->reward = sim->arena.alloc<float>(num_worlds);
         sim->alloc_episode(true, false);
-        {
-            const uint32_t blocks = (num_worlds + kUnroll * kBlock - 1) / (kUnroll * kBlock);
-            if (blocks <= mrl::kMaxFusedBlocks) {
-                sim->fused_grid = blocks;
-                sim->status = sim->arena.alloc<uint32_t>(blocks);
-                sim->group_total = sim->arena.alloc<unsigned long long>((blocks + mrl::kGroup - 1) / mrl::kGroup);
+        sim->alloc_fused(kUnroll * kBlock);
 #ifdef MRL_DIAG
-                if (mrl::debug_get("stamps", 0)) sim->stamps = sim->arena.alloc<unsigned long long>((size_t)blocks * (kBlock / 64) * 8);
+        if (sim->fused_grid && mrl::debug_get("stamps", 0))
+            sim->stamps = sim->arena.alloc<unsigned long long>((size_t)sim->fused_grid * (kBlock / 64) * 8);
 #endif
-            }
-        }
         sim->alarm.init(sim->arena);
         sim->launch_state.init(sim->arena);
         {
@@ -910,6 +803,7 @@ mrl_sim *mrl::create_cartpole(int gpu_id, uint32_t num_worlds)
                                  (uint64_t)num_worlds <= persistent_max;
             sim->ring = sim->arena.alloc<unsigned long long>((size_t)kRing * sim->fused_grid);
         }
+        mrl::fill_ids(sim->world_id, nullptr, 1, num_worlds);
         sim->reseed_shard(0, num_worlds, 0);
         sim->inject_scan_timeout();
         MRL_HIP(hipDeviceSynchronize());

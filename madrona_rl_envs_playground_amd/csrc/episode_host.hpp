@@ -1,12 +1,16 @@
-// Host side of what the three games that number their episodes share (HanabiSim in hanabi.hip, CartpoleSim in
-// cartpole.hip, BalanceSim in balance.hip; the device side is episode_scan.hpp): the double-buffered episode counter and
-// the launch-to-launch state around it, the choice between the single-launch step and the two-launch pair, phase 2 in
-// its four forms and the forced reset, which are all the game's one re-seeding launch on different inputs.  Host-only code.
+// Host side of what the four games that number their episodes share (HanabiSim in hanabi.hip, CartpoleSim in
+// cartpole.hip, BalanceSim in balance.hip, AcrobotSim in acrobot.hip; the device side is episode_scan.hpp): the
+// double-buffered episode counter and the launch-to-launch state around it, the choice between the single-launch step and
+// the two-launch pair, phase 2 in its four forms and the forced reset, which are all the game's one re-seeding launch on
+// different inputs; for the three games with one lane per world also the status words of their single-launch step and
+// the random-policy rollout as one step per launch.  Host-only code.
 #pragma once
 
 #include "common.hpp"
 #include "episode_scan.hpp"
 #include "world_reset.hpp"
+
+#include <stdexcept>
 
 namespace mrl {
 
@@ -38,6 +42,7 @@ inline bool grid_resident(const void *kernel, int block_threads, uint32_t grid, 
 
 struct EpisodeSim : mrl_sim {
     uint32_t grid = 0, chunk = 0;  // of the two-launch step (scan_grid)
+    int32_t *action = nullptr;     // the ACTION tensor (allocated by the game, among its per-world tensors)
     uint32_t *counter = nullptr;   // [2]: double-buffered episode counter, [parity] is current
     uint32_t parity = 0, epoch = 0;  // epoch: tag of the single-launch step's status words
     uint32_t *block_counts = nullptr, *reset_count = nullptr;
@@ -46,6 +51,11 @@ struct EpisodeSim : mrl_sim {
     AlarmOwner alarm;                 // raised when a bounded wait expired: a persistent rollout's, or the mailbox exchange's of a sharded step
     HealTest heal;                    // test hook of the healing look-back (mrl_debug_set fused_heal_test)
     bool fused = false;               // mrl_step is one launch with the in-kernel look-back, not the two-launch pair
+    // single-launch step of Cartpole, the balance beam and Acrobot (alloc_fused): 32-bit status words and, per kGroup
+    // workgroups, their total (grouped_prefix); fused_grid == 0: the batch is too large for it.  Hanabi has 64-bit words of its own.
+    uint32_t *status = nullptr;
+    unsigned long long *group_total = nullptr;
+    uint32_t fused_grid = 0;
 
     // ---- what a game supplies ----
     // Where a re-seeding launch finds the finished worlds -- mask words (Cartpole, balance beam) or flags (Hanabi), and their
@@ -62,8 +72,8 @@ struct EpisodeSim : mrl_sim {
         uint32_t *next;
         DeviceCounter device;
     };
-    // the random policy drawn inside the step (mrl_rollout_random); action_out == nullptr: the caller's actions.  Cartpole and
-    // the balance beam only: Hanabi's policy travels in its HanabiParams and its launch_fused does not look at a Drawn
+    // the random policy drawn inside the step (mrl_rollout_random); action_out == nullptr: the caller's actions.  Not
+    // Hanabi: its policy travels in its HanabiParams and its launch_fused does not look at a Drawn
     struct Drawn {
         int32_t *action_out = nullptr;
         uint64_t seed = 0;
@@ -71,6 +81,12 @@ struct EpisodeSim : mrl_sim {
     };
     virtual void launch_fused(const int32_t *actions, const Drawn &drawn, const FusedExchange &fx, const Counters &c, hipStream_t stream) = 0;
     virtual void launch_reseed(const Finished &from, const GatheredCounts &gathered, const Counters &c, hipStream_t stream) = 0;
+    // phase 1 with the policy's draws made in the step kernel and written to action_out (nullptr: the caller's actions):
+    // the games whose two-launch step kernel can draw (balance beam, Acrobot), for rollout_random below
+    virtual void launch_step(const int32_t *, int32_t *, uint64_t, uint32_t, hipStream_t)
+    {
+        throw std::runtime_error("this game's step kernel draws no actions");
+    }
     Finished stepped{};  // what phase 1 leaves (alloc_episode; Hanabi sets its flags)
 
     // One launch that takes episode numbers: the device copy of the state advanced first, the counter's halves as of before
@@ -112,6 +128,19 @@ struct EpisodeSim : mrl_sim {
     {
         hipLaunchKernelGGL(sum_block_counts, dim3(1), dim3(256), 0, stream, block_counts, grid, shard_count, mail_of(exchange));
         MRL_HIP(hipGetLastError());
+    }
+    // mrl_rollout_random, one step per launch (two without the single-launch step); the draws are made inside the step.
+    // Cartpole and Hanabi, which have a persistent rollout kernel in front of this, override it.
+    void rollout_random(uint32_t num_steps, uint64_t seed, uint32_t first_step, hipStream_t stream) override
+    {
+        for (uint32_t k = 0; k < num_steps; k++) {
+            if (fused) {
+                fused_step(action, Drawn{action, seed, first_step + k}, FusedExchange{}, stream);
+            } else {
+                launch_step(action, action, seed, first_step + k, stream);
+                phase2(nullptr, stream);
+            }
+        }
     }
     void phase2(const uint32_t *episode_base_dev, hipStream_t stream) override { reseed(stepped, episode_base_dev, GatheredCounts{}, stream); }
     void phase2_gathered(const uint32_t *counts, uint32_t num_ranks, uint32_t rank, hipStream_t stream) override
@@ -172,6 +201,16 @@ struct EpisodeSim : mrl_sim {
         forced.init(arena, grid, chunk, num_worlds, with_words, with_flags);
         stepped.block_counts = block_counts;
         stepped.reset_count = reset_count;
+    }
+    // the single-launch step's status words, where the game's own block stood (see above: the sequence of allocations is the
+    // game's); nothing for a batch of more than kMaxFusedBlocks workgroups
+    void alloc_fused(uint32_t worlds_per_workgroup)
+    {
+        const uint32_t blocks = (num_worlds + worlds_per_workgroup - 1) / worlds_per_workgroup;
+        if (blocks > kMaxFusedBlocks) return;
+        fused_grid = blocks;
+        status = arena.alloc<uint32_t>(blocks);
+        group_total = arena.alloc<unsigned long long>((blocks + kGroup - 1) / kGroup);
     }
     // mrl_debug_set fused_step: 0 = the library's choice (one launch wherever the game has one for this batch: `exists`),
     // 1 = one launch where possible, 2 = always two; fused_heal_test: see HealTest (one word per workgroup of the single launch)

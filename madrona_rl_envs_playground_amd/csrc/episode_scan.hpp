@@ -1,4 +1,5 @@
-// Deterministic episode numbering for Hanabi and Cartpole.
+// Deterministic episode numbering for the games that seed a world from its episode's index: Hanabi, Cartpole, the balance
+// beam, Acrobot.
 //
 // The reference draws each new episode's index from one process-wide atomic
 // (src/hanabi_env/sim.cpp:449-451, src/cartpole_env/sim.cpp:51-53), i.e. in thread-arrival
@@ -249,6 +250,85 @@ __device__ __forceinline__ uint32_t scan_prefix(const uint32_t *block_counts, ui
     lds_barrier();
     if (grand_total) *grand_total = total;
     return prefix;
+}
+
+// ---- launch 2 of the two-launch step for the games whose phase 1 leaves ballot words (Cartpole, balance beam, Acrobot) ----
+// Also every gathered / exchanged phase 2 and mrl_reset_worlds (episode_host.hpp: all of them are this launch on different
+// inputs).  The kernel IS the template: a game supplies only `Reseed`, a trivially copyable struct passed by value whose
+// operator()(world, episode) const stores that world's next episode, and it is inlined into the last loop -- the shape the
+// three games' own copies had, so each instantiation compiles to the kernel it replaces (the other
+// direction, the common part as a callee inlined into per-game kernels, did not).
+//
+// The finished worlds of a trip are first compacted into s_list in ascending world order (entry e is the e-th finished
+// world, so its episode is base + running + e), then re-seeded one per thread: the seed hash is ~150 dependent
+// instructions, so it runs once on dense lanes rather than once per mask word on the few lanes whose bit is set.
+constexpr uint32_t kTripWords = 64;  // mask words (64 worlds each) compacted per trip
+
+template <int kBlock, typename Reseed>
+__global__ void __launch_bounds__(kBlock) reseed_finished(uint32_t n, uint32_t chunk, const Reseed reseed,
+                                                          const uint32_t *__restrict__ block_counts,
+                                                          const unsigned long long *__restrict__ finished_mask,
+                                                          const uint32_t *episode_base, uint32_t *next_counter,
+                                                          uint32_t *__restrict__ reset_count, const GatheredCounts gathered,
+                                                          const DeviceCounter device_counter)
+{
+    __shared__ uint32_t s_red[2 * kBlock / 64];
+    __shared__ unsigned long long s_word[kTripWords];
+    __shared__ uint32_t s_before[kTripWords];
+    __shared__ uint32_t s_total;
+    __shared__ uint16_t s_list[kTripWords * 64];
+    const bool last_block = blockIdx.x == gridDim.x - 1;
+    uint32_t unused_epoch = 0;
+    device_counter.apply(episode_base, next_counter, unused_epoch);  // (the launch state may live in device memory: common.hpp)
+    const uint32_t mine = block_counts[blockIdx.x];
+    const uint32_t first = blockIdx.x * chunk, last = min(n, first + chunk);
+    const uint32_t words = (last - first + 63u) >> 6;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    // the first trip's mask words are requested before the prefix is summed
+    unsigned long long word = threadIdx.x < min(words, kTripWords) ? finished_mask[(first >> 6) + threadIdx.x] : 0ull;
+    if (mine == 0 && !last_block) return;  // nothing finished here (uniform per workgroup)
+    uint32_t grand_total = 0;
+    uint32_t running = scan_prefix(block_counts, gridDim.x, blockIdx.x, s_red, last_block, &grand_total);
+    uint32_t base = *episode_base, all_ranks = grand_total;
+    const uint32_t counter_now = base;
+    if (gathered.counts) base += lower_ranks(gathered, &all_ranks);  // sharded batch: the ranks below come first
+    for (uint32_t w0 = 0; w0 < words; w0 += kTripWords) {  // uniform trip count
+        const uint32_t here = min(words - w0, kTripWords);
+        if (wave == 0) {
+            if (w0 > 0) word = lane < here ? finished_mask[(first >> 6) + w0 + lane] : 0ull;
+            const uint32_t c = (uint32_t)__popcll(word);
+            uint32_t x = c;
+            for (int off = 1; off < 64; off <<= 1) {
+                const uint32_t y = __shfl_up(x, off, 64);
+                x += lane >= (uint32_t)off ? y : 0u;
+            }
+            s_word[lane] = word;
+            s_before[lane] = x - c;
+            if (lane == 63) s_total = x;
+        }
+        __syncthreads();
+        const uint32_t total = s_total;
+        for (uint32_t k = wave; k < here; k += kBlock / 64) {  // one wave per word, lane = bit
+            const unsigned long long m = s_word[k];
+            if ((m >> lane) & 1ull) s_list[s_before[k] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)((k << 6) + lane);
+        }
+        __syncthreads();
+        for (uint32_t e = threadIdx.x; e < total; e += kBlock) reseed(first + (w0 << 6) + s_list[e], base + running + e);
+        running += total;
+        __syncthreads();  // s_word / s_before / s_list are rewritten by the next trip
+    }
+    if (last_block && threadIdx.x == 0) {
+        *reset_count = grand_total;
+        *next_counter = gathered.counts ? counter_now + all_ranks : base + grand_total;
+    }
+}
+
+// construction / mrl_reseed_shard: world i of the shard is global world world_offset + i, in its first episode (the
+// reference's constructors give world i episode i); launched with any block size over at least n threads
+template <typename Reseed> __global__ void reseed_all(uint32_t n, uint32_t world_offset, const Reseed reseed)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) reseed(i, world_offset + i);
 }
 
 // ---------------------------------------------------------------------------------------------

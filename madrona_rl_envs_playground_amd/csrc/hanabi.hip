@@ -32,6 +32,7 @@
 //                         score/done + per-workgroup done counts, mrl_hanabi_reset = prefix
 //                         over the counts, re-deal, encode both agents.
 #include "episode_host.hpp"
+#include "episode_rng.hpp"
 #include "random_policy.hpp"
 
 #include <algorithm>
@@ -175,27 +176,13 @@ __device__ __forceinline__ void wave_lds_sync()
     asm volatile("" ::: "memory");
 }
 
-__device__ __forceinline__ uint32_t seed_of(uint32_t episode)
-{
-    uint32_t v0 = episode, v1 = 0, sum = 0;
-#pragma unroll
-    for (int round = 0; round < 8; round++) {
-        sum += 0x9e3779b9u;
-        v0 += ((v1 << 4) + 0xa341316cu) ^ (v1 + sum) ^ ((v1 >> 5) + 0xc8013ea4u);
-        v1 += ((v0 << 4) + 0xad90777du) ^ (v0 + sum) ^ ((v0 >> 5) + 0x7e95761eu);
-    }
-    return v0;
-}
-
 __device__ __forceinline__ uint32_t &rng_of(uint8_t *rec) { return *reinterpret_cast<uint32_t *>(rec + R_RNG); }
 __device__ __forceinline__ uint32_t *plaus_of(uint8_t *hand) { return reinterpret_cast<uint32_t *>(hand + H_PLAUS); }
 
 // sim.cpp:45-52 (one float multiply, truncation)
 __device__ __forceinline__ uint32_t draw(uint8_t *rec)
 {
-    uint32_t &g = rng_of(rec);
-    g = 1664525u * g + 1013904223u;
-    const float r = (float)(g & 0x00FFFFFFu) / (float)0x01000000;
+    const float r = mrl::next_uniform(rng_of(rec));
     const uint32_t size = rec[R_DECK_SIZE];
     const int32_t at = (int32_t)((float)size * r);
     const uint8_t card = rec[R_DECK + at];
@@ -1145,7 +1132,7 @@ __device__ void deal_new_game(const HanabiParams &p, uint8_t *rec, uint32_t epis
     rec[R_LM_COLOR] = 0xFF;
     rec[R_LM_RANK] = 0xFF;
     rec[R_LM_DEALTO] = 0xFF;
-    uint32_t g = seed_of(episode);
+    uint32_t g = mrl::seed_of(episode);
     uint32_t size = p.deck_words[12] >> 16 & 0xFFu;  // byte 50
     const uint32_t all = ones(p.bpc);
     for (uint32_t a = 0; a < 2; a++) {
@@ -1153,8 +1140,7 @@ __device__ void deal_new_game(const HanabiParams &p, uint8_t *rec, uint32_t epis
 #pragma unroll
         for (uint32_t j = 0; j < kHand; j++) {
             // drawDeck (sim.cpp:45-52): one float multiply, truncation
-            g = 1664525u * g + 1013904223u;
-            const float r = (float)(g & 0x00FFFFFFu) / (float)0x01000000;
+            const float r = mrl::next_uniform(g);
             const int32_t at = (int32_t)((float)size * r);
             const uint8_t card = rec[R_DECK + at];
             rec[R_DECK + at] = rec[R_DECK + size - 1];
@@ -2204,10 +2190,10 @@ template <typename F> void with_variant(int variant, F &&f)
 
 struct HanabiSim final : mrl::EpisodeSim {
     HanabiParams params{};  // (carries copies of block_counts, shard_count and chunk: the kernels read them there)
-    int32_t *action = nullptr, *world_id = nullptr, *agent_id = nullptr;
+    int32_t *world_id = nullptr, *agent_id = nullptr;
     int variant = 0;  // code variant of the kernels (see encode_variant)
     // single-launch step (mrl_hanabi_step_fused)
-    unsigned long long *status = nullptr;
+    unsigned long long *wide_status = nullptr;  // 64-bit status words (mrl::wave_prefix_or_recount), not EpisodeSim's 32-bit ones
     uint32_t pair_stride = 4;  // phase A of the single-launch step by four leader waves (see the kernel); mrl_debug_set hanabi.pairing
 
     // (the random policy of mrl_rollout_random travels in params: `drawn` is not looked at)
@@ -2217,7 +2203,7 @@ struct HanabiSim final : mrl::EpisodeSim {
         a.actions = actions ? actions : action;
         with_variant(variant, [&](auto v) {
             hipLaunchKernelGGL((mrl_hanabi_step_fused<decltype(v)::value>), dim3(grid), dim3(kFusedBlock), 0, stream, a.records, a.actions,
-                               a.num_worlds, heal.mod, pair_stride, a, status, epoch, c.base, c.next, reset_count, heal.seen, c.device, fx);
+                               a.num_worlds, heal.mod, pair_stride, a, wide_status, epoch, c.base, c.next, reset_count, heal.seen, c.device, fx);
         });
     }
 
@@ -2438,7 +2424,7 @@ mrl_sim *mrl::create_hanabi(const mrl_hanabi_config *cfg, int gpu_id, uint32_t n
         sim->stepped.flags = a.done;
         sim->alarm.init(sim->arena);
         sim->launch_state.init(sim->arena);
-        sim->status = sim->arena.alloc<unsigned long long>(sim->grid);
+        sim->wide_status = sim->arena.alloc<unsigned long long>(sim->grid);
         {
             sim->read_step_knobs(sim->chunk == (uint32_t)kWorldsPerBlock, sim->grid);  // one launch whenever a workgroup owns one sub-block
             const int64_t pairing = mrl::debug_get("hanabi.pairing", 4);  // 4: waves (w, w + 4), 1: (2k, 2k + 1), 0: no leaders

@@ -1,5 +1,5 @@
-// The kernels of mrl_reset_worlds (world_reset.hpp says how they are used), and the two fill kernels behind the kitchen
-// simulators' constant tensors (kitchen_host.hpp).
+// The kernels of mrl_reset_worlds (world_reset.hpp says how they are used), and the two fill kernels behind the
+// simulators' constant tensors.
 #include "kitchen_host.hpp"
 
 namespace {
@@ -49,7 +49,7 @@ __global__ void mrl_fill_ids(int32_t *world_id, int32_t *row_id, uint32_t rows, 
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < (size_t)rows * n) {
         world_id[i] = (int32_t)(i % n);
-        row_id[i] = (int32_t)(i / n);
+        if (row_id) row_id[i] = (int32_t)(i / n);
     }
 }
 

@@ -20,7 +20,7 @@
 namespace mrl {
 
 // The fill kernels behind the simulators' constant tensors; on the null stream.  fill_ids: world_id[i] = i % n,
-// row_id[i] = i / n for i < rows * n.  (kitchen_host.hpp, which includes this header, still repeats the two declarations.)
+// row_id[i] = i / n for i < rows * n; row_id == nullptr: a game with one row (Cartpole, Acrobot).  (kitchen_host.hpp, which includes this header, still repeats the two declarations.)
 void fill_ids(int32_t *world_id, int32_t *row_id, uint32_t rows, uint32_t n);
 void fill_i32(int32_t *dst, int32_t value, size_t count);
 

@@ -134,12 +134,32 @@ def test_unknown_arithmetic_variant_is_refused(hip_lib):
             make(64)
 
 
-@pytest.mark.parametrize("n,pattern", [(300001, "all"), (300001, "dense_block"), (1 << 20, "sparse"), (777, "all")])
-def test_planted_terminations_take_episodes_in_world_order(n, pattern, hip_lib, oracle_lib):
-    """The reset launch ranks a workgroup's short list of finished worlds in LDS and falls back to
-    the done-flag walk when more than 256 worlds of one workgroup finish at once: plant both."""
+@pytest.mark.parametrize("n,pattern,fused_step", [
+    pytest.param(300001, "all", 0, id="300001-all"),
+    pytest.param(300001, "dense_block", 0, id="300001-dense_block"),
+    pytest.param(1 << 20, "sparse", 0, id="1048576-sparse"),
+    pytest.param(777, "all", 0, id="777-all"),
+    pytest.param(777, "all", 2, id="777-all-two_launches"),
+    pytest.param(300001, "all", 2, id="300001-all-two_launches"),
+    pytest.param(300001, "dense_block", 2, id="300001-dense_block-two_launches"),
+    pytest.param(4194305, "sparse", 0, id="4194305-sparse"),
+])
+def test_planted_terminations_take_episodes_in_world_order(n, pattern, fused_step, hip_lib, oracle_lib):
+    """Finished worlds take consecutive episodes in ascending world order, whichever kernel re-seeds them: plant every
+    world, one workgroup's whole chunk plus a sprinkle, and a sparse 3 %.
+
+    fused_step = 0 is the library's choice: up to 4096 workgroups of 1024 worlds the single launch, which re-seeds the
+    finished worlds of a wave from a list in LDS.  fused_step = 2 asks for the two-launch pair, whose second launch
+    (mrl::reseed_finished, csrc/episode_scan.hpp) compacts a workgroup's finished worlds from the step's ballot words,
+    64 words per trip.  4194305 worlds is the smallest batch without a single launch (4097 workgroups) and the smallest
+    whose chunk per workgroup of the two-launch grid -- 17 * 256 worlds = 68 mask words -- needs a second trip."""
+    from madrona_rl_envs_playground_amd._lib import debug_knobs
     rng = np.random.default_rng(5)
-    sim, orc = make(n), oracle_lib.CartpoleOracle(n, num_threads=8)
+    with debug_knobs({"fused_step": fused_step}):
+        sim = make(n)
+    if fused_step == 2 or n == 4194305:
+        assert sim.kernel_name == "mrl_cartpole_step"
+    orc = oracle_lib.CartpoleOracle(n, num_threads=8)
     st = sim.observation_tensor().to_torch()
     planted = orc.state.copy()
     if pattern == "all":
