@@ -62,6 +62,7 @@ enum {
 
 /* element types of exported tensors (madrona::py::Tensor::ElementType subset) */
 enum { MRL_INT8 = 0, MRL_UINT8 = 1, MRL_INT32 = 2, MRL_FLOAT32 = 3, MRL_UINT32 = 4 };
+#define MRL_FLOAT64 5 /* the TOTALS tensor of mrl_enable_episode_stats */
 
 enum { MRL_GAME_OVERCOOKED = 1, MRL_GAME_HANABI = 2, MRL_GAME_CARTPOLE = 3, MRL_GAME_SIMPLECOOKED = 4, MRL_GAME_BALANCE = 5, MRL_GAME_ACROBOT = 6 };
 
@@ -491,6 +492,49 @@ int mrl_rollout_random(mrl_sim *sim, uint32_t num_steps, uint64_t seed, uint32_t
  *   games); one launch with a wavefront per world that copies the fresh world over the masked ones (Overcooked,
  *   Simplecooked).  DESIGN.md section 9. */
 int mrl_reset_worlds(mrl_sim *sim, const uint8_t *mask_dev_or_null, void *hip_stream);
+
+/* Episode returns and lengths as a product of the step.  The reference's training scripts keep them by hand, in torch, after
+ * every step (scripts/cartpole_train_torch.py:223-226: ep_rewards += rewards; rewsum += sum(where(done, ep_rewards, 0));
+ * numfin += sum(done); ep_rewards *= 1 - done -- six or seven launches around a step of a few microseconds), and its
+ * environments never delivered the info["episode"] the commented-out lines beneath ask for.  No reference counterpart.
+ *   mrl_enable_episode_stats allocates and zeroes five tensors, for the rest of the simulator's life (like
+ *   mrl_prepare_graph_capture); a second call is a no-op.  MRL_ERR_INVALID for a NULL handle and on a capturing stream (the
+ *   call allocates; it also synchronises the stream).  The memory is an allocation of its own: no exported tensor moves.
+ *   Before the call the five slots answer MRL_ERR_SLOT and every entry point enqueues exactly what it did before.
+ * Slots, the same numbers for all six games.  P = players; REWARD's and DONE's own shapes are (P,N) / (N), or (N,1) / (N,1):
+ *   EPISODE_RETURN float32, REWARD's shape   sum of REWARD over the steps of the world's current episode since enabling
+ *   EPISODE_STEPS  int32,   DONE's shape     steps of the current episode since enabling
+ *   LAST_RETURN    float32, REWARD's shape   EPISODE_RETURN as it stood when the world last finished (0 before)
+ *   LAST_STEPS     int32,   DONE's shape     the same for EPISODE_STEPS
+ *   TOTALS         float64 (B, 2 + P), B = ceil(N / 1024): per block b of worlds [1024 b, 1024 b + 1024), since the last
+ *                  mrl_clear_episode_totals: episodes finished, their steps, their return per player.  The totals
+ *                  themselves are the column sums.
+ * After every completed step, for every world w:
+ *     ret[:, w] += float32(REWARD[:, w]);  steps[w] += 1                 (one IEEE float32 add per step and player)
+ *     if DONE[w]:  last_ret[:, w] = ret[:, w];  last_steps[w] = steps[w]
+ *                  TOTALS[w / 1024] += (1, steps[w], ret[:, w]);  ret[:, w] = 0;  steps[w] = 0
+ * TOTALS takes no atomics: block b is read and written by exactly one workgroup of a launch, which sums what its finished
+ * worlds contribute in a fixed order and touches the block only if one of its worlds finished -- the same bits from run to
+ * run, and no 1024 workgroups queueing on one word.
+ * A completed step is: mrl_step; mrl_step_with_actions and its _i64 form; every simulator of an mrl_step_many that has the
+ * statistics enabled; mrl_step_exchanged; each step of mrl_step_sequence and mrl_rollout_random; of the two-phase calls,
+ * phase 2 in any of its forms (Hanabi, Cartpole, balance beam, Acrobot) or phase 1 (Overcooked, Simplecooked, whose phase 2
+ * does nothing); every replay of a captured step.  The update is one more launch behind the step's own
+ * (mrl_episode_stats_update, 256 threads x 4 worlds), on the same stream; with statistics enabled mrl_step_sequence and
+ * mrl_rollout_random run one step per launch, each followed by it (K steps equal K single calls either way), and
+ * mrl_rollout_kernel_name says so.
+ * mrl_reset_worlds zeroes EPISODE_RETURN / EPISODE_STEPS of the masked worlds and nothing else of these tensors -- a forced
+ * restart is not a finished episode --, mrl_reseed_shard does the same for all worlds, mrl_clear_episode_totals zeroes TOTALS
+ * only (MRL_ERR_INVALID before mrl_enable_episode_stats).  Totals are per simulator: a sharded batch adds its ranks' up. */
+enum {
+    MRL_STATS_EPISODE_RETURN = 64,
+    MRL_STATS_EPISODE_STEPS = 65,
+    MRL_STATS_LAST_RETURN = 66,
+    MRL_STATS_LAST_STEPS = 67,
+    MRL_STATS_TOTALS = 68
+};
+int mrl_enable_episode_stats(mrl_sim *sim, void *hip_stream);
+int mrl_clear_episode_totals(mrl_sim *sim, void *hip_stream);
 
 int mrl_tensor(mrl_sim *sim, int slot, mrl_tensor_desc *out);
 int mrl_game(const mrl_sim *sim);

@@ -21,6 +21,9 @@ HEADER = os.path.join(os.path.dirname(_PKG), "include", "mrl_envs.h")
 
 MRL_OK, MRL_ERR_INVALID, MRL_ERR_DEVICE, MRL_ERR_SLOT = 0, 1, 2, 3
 MRL_INT8, MRL_UINT8, MRL_INT32, MRL_FLOAT32, MRL_UINT32 = 0, 1, 2, 3, 4
+MRL_FLOAT64 = 5
+# tensor slots of mrl_enable_episode_stats, the same for every game
+STATS_EPISODE_RETURN, STATS_EPISODE_STEPS, STATS_LAST_RETURN, STATS_LAST_STEPS, STATS_TOTALS = 64, 65, 66, 67, 68
 MAX_DIMS = 6
 MAX_RANKS, IPC_HANDLE_BYTES = 16, 64  # MRL_MAX_RANKS, MRL_IPC_HANDLE_BYTES
 
@@ -33,7 +36,7 @@ SYMBOLS = [
     "mrl_scan_timed_out", "mrl_simplecooked_create", "mrl_launch_shape", "mrl_balance_create", "mrl_step_with_actions_i64",
     "mrl_step_phase2_gathered", "mrl_set_observation_output", "mrl_set_observation_ring", "mrl_prepare_graph_capture", "mrl_step_many",
     "mrl_build_hash", "mrl_exchange_create", "mrl_exchange_connect", "mrl_step_exchanged", "mrl_reset_worlds",
-    "mrl_acrobot_create",
+    "mrl_acrobot_create", "mrl_enable_episode_stats", "mrl_clear_episode_totals",
 ]
 ABI_VERSION = 4  # MRL_ABI_VERSION of include/mrl_envs.h this binding was written against
 
@@ -162,6 +165,8 @@ def lib():
     L.mrl_rollout_random.argtypes = [vp, u32, ctypes.c_uint64, u32, vp]
     L.mrl_step_sequence.argtypes = [vp, vp, u32, vp]
     L.mrl_reset_worlds.argtypes = [vp, vp, vp]
+    L.mrl_enable_episode_stats.argtypes = [vp, vp]
+    L.mrl_clear_episode_totals.argtypes = [vp, vp]
     L.mrl_tensor.argtypes = [vp, i32, ctypes.POINTER(TensorDesc)]
     L.mrl_game.argtypes = [vp]
     L.mrl_num_worlds.argtypes = [vp]

@@ -386,6 +386,12 @@ __device__ __forceinline__ uint32_t recount_chunk(uint32_t n, const int32_t *act
 // length 0.  So a workgroup overwrites its state and length only after its count is globally visible, and whoever
 // recounts it before that reads the step's inputs.  (The drawn actions of a
 // rollout go out before the count: the recount draws them again from the hash and never reads ACTION.)
+// kStats (mrl_enable_episode_stats): the lane also keeps its four worlds' episode returns and step counts.  They are loaded
+// AFTER the transition, behind the first barrier -- its registers are what bounds this kernel, and the values are not needed
+// before the stores, two barriers later -- and thread 0 adds the workgroup's finished episodes to TOTALS block b behind the
+// last barrier (episode_stats.hpp).  171 VGPRs against 162, two waves per SIMD against three: DESIGN.md section 11 has the
+// measurement that keeps this form.  Without kStats the kernel is what it was.
+template <bool kStats>
 __global__ void __launch_bounds__(kBlock, kWavesPerSimd) mrl_acrobot_step_fused(uint32_t n, const int32_t *action,  // (no __restrict__: may be action_out)
                                                                  float4 *__restrict__ state, int32_t *__restrict__ length,
                                                                  float *__restrict__ reward, int32_t *__restrict__ done, uint32_t *status,
@@ -394,7 +400,8 @@ __global__ void __launch_bounds__(kBlock, kWavesPerSimd) mrl_acrobot_step_fused(
                                                                  uint32_t *__restrict__ reset_count, int32_t *action_out,
                                                                  uint64_t sample_seed, uint32_t sample_step, const mrl::HealTest heal,
                                                                  const mrl::DeviceCounter device_counter,
-                                                                 const mrl::FusedExchange fx)  // sharded batch: the other ranks' counts (episode_scan.hpp)
+                                                                 const mrl::FusedExchange fx,  // sharded batch: the other ranks' counts (episode_scan.hpp)
+                                                                 const mrl::StatsArg<kStats> stats)
 {
     __shared__ uint32_t s_wave[kWorlds][kBlock / 64];
     __shared__ uint32_t s_prefix, s_lower, s_all;
@@ -425,6 +432,16 @@ __global__ void __launch_bounds__(kBlock, kWavesPerSimd) mrl_acrobot_step_fused(
         if (lane == 0) s_wave[u][wave] = (uint32_t)__popcll(votes);
     }
     __syncthreads();
+    using Stats = mrl::StatsWorlds<1>;
+    [[maybe_unused]] Stats tally;
+    [[maybe_unused]] typename Stats::World running[kWorlds];
+    if constexpr (kStats) {  // (behind the barrier: not in flight during the transition)
+#pragma unroll
+        for (int u = 0; u < kWorlds; u++) {
+            const uint32_t w = first + u * kBlock + threadIdx.x;
+            running[u] = Stats::load(stats, w < last ? w : first);
+        }
+    }
     uint32_t block_total = 0;
 #pragma unroll
     for (int u = 0; u < kWorlds; u++)
@@ -469,10 +486,20 @@ __global__ void __launch_bounds__(kBlock, kWavesPerSimd) mrl_acrobot_step_fused(
             }
             reward[w] = -1.f;  // sim.cpp:186
             done[w] = over[u] ? 1 : 0;
+            if constexpr (kStats) tally.finish(stats, w, running[u], -1.f, over[u]);
         }
     }
     if (!needs_prefix) return;  // uniform per workgroup
+    [[maybe_unused]] double *s_sums = nullptr;
+    if constexpr (kStats) {
+        __shared__ double s_stats[kBlock / 64][2];
+        s_sums = &s_stats[0][0];
+        if (block_total != 0) tally.to_lds(s_sums, wave, lane);  // uniform per workgroup
+    }
     mrl::lds_barrier();
+    if constexpr (kStats) {
+        if (threadIdx.x == 0 && block_total != 0) Stats::add_totals(stats, s_sums, kBlock / 64, b, block_total);
+    }
     const uint32_t own_before = s_prefix, before = own_before + s_lower;
 #pragma unroll
     for (int u = 0; u < kWorlds; u++) {
@@ -495,9 +522,15 @@ struct AcrobotSim final : mrl::EpisodeSim {
 
     void launch_fused(const int32_t *actions, const Drawn &drawn, const mrl::FusedExchange &fx, const Counters &c, hipStream_t stream) override
     {
-        hipLaunchKernelGGL(mrl_acrobot_step_fused, dim3(fused_grid), dim3(kBlock), 0, stream, num_worlds, actions ? actions : action, state,
-                           length, reward, done, status, group_total, epoch, c.base, c.next, reset_count, drawn.action_out, drawn.seed,
-                           drawn.step, heal, c.device, fx);
+        if (stats_in_step())
+            hipLaunchKernelGGL(mrl_acrobot_step_fused<true>, dim3(fused_grid), dim3(kBlock), 0, stream, num_worlds, actions ? actions : action,
+                               state, length, reward, done, status, group_total, epoch, c.base, c.next, reset_count, drawn.action_out,
+                               drawn.seed, drawn.step, heal, c.device, fx, stats->lane());
+        else
+            hipLaunchKernelGGL(mrl_acrobot_step_fused<false>, dim3(fused_grid), dim3(kBlock), 0, stream, num_worlds, actions ? actions : action,
+                               state, length, reward, done, status, group_total, epoch, c.base, c.next, reset_count, drawn.action_out,
+                               drawn.seed, drawn.step, heal, c.device, fx, mrl::NoStats{});
+        stats_taken = stats_in_step();
     }
     void launch_step(const int32_t *actions, int32_t *action_out, uint64_t seed, uint32_t sample_step, hipStream_t stream) override
     {

@@ -197,6 +197,10 @@ __device__ __forceinline__ uint32_t recount_chunk(uint32_t n, const int32_t *act
     return count;
 }
 
+// kStats (mrl_enable_episode_stats): the lane also keeps its four worlds' episode returns (both players receive the same
+// reward) and step counts -- loaded with the rows, stored with reward and done -- and thread 0 adds the workgroup's
+// finished episodes to TOTALS block b behind one more LDS barrier (episode_stats.hpp).  Without it the kernel is what it was.
+template <bool kStats>
 __global__ void __launch_bounds__(kBlock) mrl_balance_step_fused(uint32_t n, const int32_t *action, int32_t *__restrict__ obs,
                                                                  float *__restrict__ reward, int32_t *__restrict__ done,
                                                                  uint32_t *status, unsigned long long *group_total, uint32_t epoch,
@@ -204,7 +208,8 @@ __global__ void __launch_bounds__(kBlock) mrl_balance_step_fused(uint32_t n, con
                                                                  uint32_t *next_counter, uint32_t *__restrict__ reset_count, int32_t *action_out,
                                                                  uint64_t sample_seed, uint32_t sample_step, const mrl::HealTest heal,
                                                                  const mrl::DeviceCounter device_counter,
-                                                                 const mrl::FusedExchange fx)  // sharded batch: the other ranks' counts (episode_scan.hpp)
+                                                                 const mrl::FusedExchange fx,  // sharded batch: the other ranks' counts (episode_scan.hpp)
+                                                                 const mrl::StatsArg<kStats> stats)
 {
     __shared__ uint32_t s_wave[kFusedWorlds][kBlock / 64];
     __shared__ uint32_t s_prefix, s_lower, s_all;
@@ -218,11 +223,15 @@ __global__ void __launch_bounds__(kBlock) mrl_balance_step_fused(uint32_t n, con
     float rew[kFusedWorlds];
     bool over[kFusedWorlds];
     uint32_t rank[kFusedWorlds];  // among the workgroup's finished worlds, in ascending world order (round u covers worlds first + 256 u ...)
+    using Stats = mrl::StatsWorlds<2>;
+    [[maybe_unused]] Stats tally;
+    [[maybe_unused]] typename Stats::World running[kFusedWorlds];
 #pragma unroll
     for (int u = 0; u < kFusedWorlds; u++) {
         const uint32_t w = first + u * kBlock + threadIdx.x, wc = w < last ? w : first;
         r0[u] = load_row(obs, n, 0, wc);
         r1[u] = load_row(obs, n, 1, wc);
+        if constexpr (kStats) running[u] = Stats::load(stats, wc);
         int32_t a0, a1;
         actions_of(action, n, wc, sampled, sample_seed, sample_step, a0, a1);
         if (sampled && w < last) {
@@ -279,6 +288,15 @@ __global__ void __launch_bounds__(kBlock) mrl_balance_step_fused(uint32_t n, con
             reward[w] = rew[u];
             reward[(size_t)n + w] = rew[u];
             done[w] = over[u] ? 1 : 0;
+            if constexpr (kStats) tally.finish(stats, w, running[u], rew[u], over[u]);
+        }
+    }
+    if constexpr (kStats) {
+        if (block_total != 0) {  // uniform per workgroup
+            __shared__ double s_stats[kBlock / 64][3];
+            tally.to_lds(&s_stats[0][0], wave, lane);
+            mrl::lds_barrier();
+            if (threadIdx.x == 0) Stats::add_totals(stats, &s_stats[0][0], kBlock / 64, b, block_total);
         }
     }
     if (last_block && threadIdx.x == 0) {
@@ -293,8 +311,15 @@ struct BalanceSim final : mrl::EpisodeSim {
 
     void launch_fused(const int32_t *actions, const Drawn &drawn, const mrl::FusedExchange &fx, const Counters &c, hipStream_t stream) override
     {
-        hipLaunchKernelGGL(mrl_balance_step_fused, dim3(fused_grid), dim3(kBlock), 0, stream, num_worlds, actions ? actions : action, obs, reward,
-                           done, status, group_total, epoch, c.base, c.next, reset_count, drawn.action_out, drawn.seed, drawn.step, heal, c.device, fx);
+        if (stats_in_step())
+            hipLaunchKernelGGL(mrl_balance_step_fused<true>, dim3(fused_grid), dim3(kBlock), 0, stream, num_worlds, actions ? actions : action, obs,
+                               reward, done, status, group_total, epoch, c.base, c.next, reset_count, drawn.action_out, drawn.seed, drawn.step, heal,
+                               c.device, fx, stats->lane());
+        else
+            hipLaunchKernelGGL(mrl_balance_step_fused<false>, dim3(fused_grid), dim3(kBlock), 0, stream, num_worlds, actions ? actions : action, obs,
+                               reward, done, status, group_total, epoch, c.base, c.next, reset_count, drawn.action_out, drawn.seed, drawn.step, heal,
+                               c.device, fx, mrl::NoStats{});
+        stats_taken = stats_in_step();
     }
     void launch_step(const int32_t *actions, int32_t *action_out, uint64_t seed, uint32_t sample_step, hipStream_t stream) override
     {

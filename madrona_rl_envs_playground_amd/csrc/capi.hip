@@ -1,6 +1,7 @@
 // extern "C" entry points of libmrl_envs.so (include/mrl_envs.h).
 #include "common.hpp"
 #include "episode_scan.hpp"
+#include "episode_stats.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -145,6 +146,27 @@ static int need_not_capturing(const mrl_sim *sim, void *hip_stream, const char *
     return MRL_ERR_INVALID;
 }
 
+static bool capturing(void *hip_stream)
+{
+    if (!hip_stream) return false;  // (asking about the NULL stream would itself break another stream's capture)
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing((hipStream_t)hip_stream, &status) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return status != hipStreamCaptureStatusNone;
+}
+
+// Behind every completed step (include/mrl_envs.h, mrl_enable_episode_stats): the general update launch, on the step's stream
+static void completed_step(mrl_sim *sim, hipStream_t stream)
+{
+    if (!sim->stats) return;
+    if (!sim->stats_taken) sim->stats->update(stream);
+    sim->stats_taken = false;
+}
+// the counter games complete a two-phase step with phase 2; the kitchen games, whose phase 2 does nothing, with phase 1
+static bool completes_in_phase1(const mrl_sim *sim) { return sim->game == MRL_GAME_OVERCOOKED || sim->game == MRL_GAME_SIMPLECOOKED; }
+
 // ---- roofline.peak_measured of bench.py: float4 streams over caller buffers ----
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 template <int kMode>
@@ -267,7 +289,10 @@ int mrl_step(mrl_sim *sim, void *hip_stream)
     if (int rc = mrl::need_healthy(sim)) return rc;
     if (int rc = mrl::need_not_capturing(sim, hip_stream, "mrl_step")) return rc;
     mrl::DeviceGuard on(sim->device);
-    return guarded([&] { sim->step(nullptr, (hipStream_t)hip_stream); });
+    return guarded([&] {
+        sim->step(nullptr, (hipStream_t)hip_stream);
+        mrl::completed_step(sim, (hipStream_t)hip_stream);
+    });
 }
 
 int mrl_step_with_actions(mrl_sim *sim, const int32_t *actions_dev, void *hip_stream)
@@ -275,7 +300,10 @@ int mrl_step_with_actions(mrl_sim *sim, const int32_t *actions_dev, void *hip_st
     if (int rc = mrl::need_healthy(sim)) return rc;
     if (int rc = mrl::need_not_capturing(sim, hip_stream, "mrl_step_with_actions")) return rc;
     mrl::DeviceGuard on(sim->device);
-    return guarded([&] { sim->step(actions_dev, (hipStream_t)hip_stream); });
+    return guarded([&] {
+        sim->step(actions_dev, (hipStream_t)hip_stream);
+        mrl::completed_step(sim, (hipStream_t)hip_stream);
+    });
 }
 
 int mrl_step_many(mrl_sim *const *sims, uint32_t count, const int32_t *const *actions_dev_or_null, void *hip_stream)
@@ -288,7 +316,10 @@ int mrl_step_many(mrl_sim *const *sims, uint32_t count, const int32_t *const *ac
         if (int rc = mrl::need_healthy(sims[k])) return rc;
     if (count == 0) return MRL_OK;
     mrl::DeviceGuard on(sims[0]->device);
-    return guarded([&] { mrl::step_many_overcooked(sims, count, actions_dev_or_null, (hipStream_t)hip_stream); });
+    return guarded([&] {
+        mrl::step_many_overcooked(sims, count, actions_dev_or_null, (hipStream_t)hip_stream);
+        for (uint32_t k = 0; k < count; k++) mrl::completed_step(sims[k], (hipStream_t)hip_stream);
+    });
 }
 
 int mrl_step_with_actions_i64(mrl_sim *sim, const int64_t *actions_dev, void *hip_stream)
@@ -304,6 +335,8 @@ int mrl_step_with_actions_i64(mrl_sim *sim, const int64_t *actions_dev, void *hi
         if (!sim->step_i64(reinterpret_cast<const long long *>(actions_dev), (hipStream_t)hip_stream)) {
             mrl::set_error("mrl_step_with_actions_i64: not available for game %d; convert to int32 and use mrl_step_with_actions", sim->game);
             rc = MRL_ERR_INVALID;
+        } else {
+            mrl::completed_step(sim, (hipStream_t)hip_stream);
         }
     });
     return g != MRL_OK ? g : rc;
@@ -317,6 +350,7 @@ int mrl_step_phase1(mrl_sim *sim, const int32_t *actions_dev_or_null, void *hip_
     return guarded([&] {
         sim->phase1(actions_dev_or_null, (hipStream_t)hip_stream);
         sim->publish_shard_count((hipStream_t)hip_stream);
+        if (mrl::completes_in_phase1(sim)) mrl::completed_step(sim, (hipStream_t)hip_stream);
     });
 }
 
@@ -325,7 +359,10 @@ int mrl_step_phase2(mrl_sim *sim, const uint32_t *episode_base_dev, void *hip_st
     if (int rc = mrl::need_healthy(sim)) return rc;
     if (int rc = mrl::need_not_capturing(sim, hip_stream, "mrl_step_phase2")) return rc;
     mrl::DeviceGuard on(sim->device);
-    return guarded([&] { sim->phase2(episode_base_dev, (hipStream_t)hip_stream); });
+    return guarded([&] {
+        sim->phase2(episode_base_dev, (hipStream_t)hip_stream);
+        if (!mrl::completes_in_phase1(sim)) mrl::completed_step(sim, (hipStream_t)hip_stream);
+    });
 }
 
 int mrl_step_phase2_gathered(mrl_sim *sim, const uint32_t *counts_dev, uint32_t num_ranks, uint32_t rank, void *hip_stream)
@@ -337,7 +374,10 @@ int mrl_step_phase2_gathered(mrl_sim *sim, const uint32_t *counts_dev, uint32_t 
         return MRL_ERR_INVALID;
     }
     mrl::DeviceGuard on(sim->device);
-    return guarded([&] { sim->phase2_gathered(counts_dev, num_ranks, rank, (hipStream_t)hip_stream); });
+    return guarded([&] {
+        sim->phase2_gathered(counts_dev, num_ranks, rank, (hipStream_t)hip_stream);
+        if (!mrl::completes_in_phase1(sim)) mrl::completed_step(sim, (hipStream_t)hip_stream);
+    });
 }
 
 int mrl_exchange_create(mrl_sim *sim, uint32_t num_ranks, uint32_t rank, uint8_t *ipc_handle_out)
@@ -417,6 +457,7 @@ int mrl_step_exchanged(mrl_sim *sim, const int32_t *actions_dev_or_null, void *h
             ~Done() { x.publishing = false; }
         } done{x};
         sim->step_exchanged(actions_dev_or_null, (hipStream_t)hip_stream);
+        mrl::completed_step(sim, (hipStream_t)hip_stream);
     });
 }
 
@@ -460,6 +501,39 @@ int mrl_prepare_graph_capture(mrl_sim *sim, void *hip_stream)
     return guarded([&] { sim->prepare_graph_capture((hipStream_t)hip_stream); });
 }
 
+int mrl_enable_episode_stats(mrl_sim *sim, void *hip_stream)
+{
+    if (int rc = mrl::need(sim)) return rc;
+    if (sim->stats) return MRL_OK;
+    if (mrl::capturing(hip_stream)) {
+        mrl::set_error("mrl_enable_episode_stats: the call allocates and cannot run on a capturing stream; enable the statistics "
+                       "before the capture");
+        return MRL_ERR_INVALID;
+    }
+    mrl::DeviceGuard on(sim->device);
+    return guarded([&] {
+        auto *stats = new mrl::EpisodeStats();
+        try {
+            stats->init(sim, (hipStream_t)hip_stream);
+        } catch (...) {
+            delete stats;
+            throw;
+        }
+        sim->stats = stats;
+    });
+}
+
+int mrl_clear_episode_totals(mrl_sim *sim, void *hip_stream)
+{
+    if (int rc = mrl::need(sim)) return rc;
+    if (!sim->stats) {
+        mrl::set_error("mrl_clear_episode_totals: call mrl_enable_episode_stats first");
+        return MRL_ERR_INVALID;
+    }
+    mrl::DeviceGuard on(sim->device);
+    return guarded([&] { sim->stats->clear_totals((hipStream_t)hip_stream); });
+}
+
 int mrl_set_episode_counter(mrl_sim *sim, uint32_t next_episode, void *hip_stream)
 {
     if (int rc = mrl::need(sim)) return rc;
@@ -474,6 +548,7 @@ int mrl_reseed_shard(mrl_sim *sim, uint32_t world_offset, uint32_t num_worlds_to
     return guarded([&] {
         sim->reseed_shard(world_offset, num_worlds_total, (hipStream_t)hip_stream);
         sim->reseeded = true;
+        if (sim->stats) sim->stats->clear_running(nullptr, (hipStream_t)hip_stream);
     });
 }
 
@@ -489,7 +564,11 @@ int mrl_reset_worlds(mrl_sim *sim, const uint8_t *mask_dev_or_null, void *hip_st
         return MRL_ERR_INVALID;
     }
     mrl::DeviceGuard on(sim->device);
-    return guarded([&] { sim->reset_worlds(mask_dev_or_null, (hipStream_t)hip_stream); });
+    return guarded([&] {
+        sim->reset_worlds(mask_dev_or_null, (hipStream_t)hip_stream);
+        // a forced restart is not a finished episode: the running values go, LAST_* and TOTALS stay
+        if (sim->stats) sim->stats->clear_running(mask_dev_or_null, (hipStream_t)hip_stream);
+    });
 }
 
 int mrl_step_sequence(mrl_sim *sim, const int32_t *actions_dev, uint32_t num_steps, void *hip_stream)
@@ -501,7 +580,17 @@ int mrl_step_sequence(mrl_sim *sim, const int32_t *actions_dev, uint32_t num_ste
         mrl::set_error("mrl_step_sequence: null action array");
         return MRL_ERR_INVALID;
     }
-    return guarded([&] { sim->step_sequence(actions_dev, num_steps, (hipStream_t)hip_stream); });
+    return guarded([&] {
+        if (!sim->stats) {
+            sim->step_sequence(actions_dev, num_steps, (hipStream_t)hip_stream);
+            return;
+        }
+        // K steps equal K single calls: with statistics each is a launch of its own with the update behind it
+        for (uint32_t k = 0; k < num_steps; k++) {
+            sim->step(actions_dev + (size_t)k * sim->action_elems(), (hipStream_t)hip_stream);
+            mrl::completed_step(sim, (hipStream_t)hip_stream);
+        }
+    });
 }
 
 int mrl_rollout_random(mrl_sim *sim, uint32_t num_steps, uint64_t seed, uint32_t first_step, void *hip_stream)
@@ -509,7 +598,16 @@ int mrl_rollout_random(mrl_sim *sim, uint32_t num_steps, uint64_t seed, uint32_t
     if (int rc = mrl::need_healthy(sim)) return rc;
     if (int rc = mrl::need_not_capturing(sim, hip_stream, "mrl_rollout_random")) return rc;
     mrl::DeviceGuard on(sim->device);
-    return guarded([&] { sim->rollout_random(num_steps, seed, first_step, (hipStream_t)hip_stream); });
+    return guarded([&] {
+        if (!sim->stats) {
+            sim->rollout_random(num_steps, seed, first_step, (hipStream_t)hip_stream);
+            return;
+        }
+        for (uint32_t k = 0; k < num_steps; k++) {
+            sim->rollout_random(1, seed, first_step + k, (hipStream_t)hip_stream);
+            mrl::completed_step(sim, (hipStream_t)hip_stream);
+        }
+    });
 }
 
 int mrl_tensor(mrl_sim *sim, int slot, mrl_tensor_desc *out)
@@ -520,7 +618,7 @@ int mrl_tensor(mrl_sim *sim, int slot, mrl_tensor_desc *out)
     int rc = MRL_OK;
     int g = guarded([&] {
         memset(out, 0, sizeof(*out));
-        if (!sim->tensor(slot, out)) {
+        if (!sim->tensor(slot, out) && !(sim->stats && sim->stats->tensor(slot, out))) {
             mrl::set_error("tensor slot %d is not exported by game %d", slot, sim->game);
             rc = MRL_ERR_SLOT;
         }

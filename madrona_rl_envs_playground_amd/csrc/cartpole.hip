@@ -294,7 +294,10 @@ __device__ __forceinline__ uint32_t recount_chunk(uint32_t n, const float4 *stat
 // of its 256 under a random policy -- are re-seeded by as many lanes in ONE pass over a list in LDS (the seed hash is
 // ~150 dependent instructions; per round it would run four times for three lanes each).
 // (the look-back has two levels: mrl::grouped_prefix, episode_scan.hpp)
-template <int V>
+// kStats (mrl_enable_episode_stats): the lane also keeps its four worlds' episode returns and step counts -- loaded behind
+// the actions, stored with reward and done -- and thread 0 adds the workgroup's finished episodes to TOTALS block b behind
+// the last barrier (episode_stats.hpp).  Without it the kernel is what it was.
+template <int V, bool kStats = false>
 __global__ void __launch_bounds__(kBlock) mrl_cartpole_step_fused(uint32_t n, const int32_t *action,  // (no __restrict__: may be action_out)
                                                                   float4 *__restrict__ state, float *__restrict__ reward,
                                                                   int32_t *__restrict__ done, uint32_t *status,
@@ -304,7 +307,8 @@ __global__ void __launch_bounds__(kBlock) mrl_cartpole_step_fused(uint32_t n, co
                                                                   uint32_t *__restrict__ reset_count,
                                                                   int32_t *action_out, uint64_t sample_seed, uint32_t sample_step,
                                                                   const mrl::HealTest heal, const mrl::DeviceCounter device_counter,
-                                                                  const mrl::FusedExchange fx  // sharded batch: the other ranks' counts (episode_scan.hpp)
+                                                                  const mrl::FusedExchange fx,  // sharded batch: the other ranks' counts (episode_scan.hpp)
+                                                                  const mrl::StatsArg<kStats> stats
 #ifdef MRL_DIAG
                                                                   , unsigned long long *stamps  // diagnostic build: s_memrealtime stamps per wave
 #endif
@@ -349,6 +353,16 @@ __global__ void __launch_bounds__(kBlock) mrl_cartpole_step_fused(uint32_t n, co
             if (i < last) action_out[i] = a[u];
         } else {
             a[u] = action[ic];
+        }
+    }
+    using Stats = mrl::StatsWorlds<1>;
+    [[maybe_unused]] Stats tally;
+    [[maybe_unused]] typename Stats::World running[kUnroll];
+    if constexpr (kStats) {
+#pragma unroll
+        for (int u = 0; u < kUnroll; u++) {
+            const uint32_t i = first + u * kBlock + threadIdx.x;
+            running[u] = Stats::load(stats, i < last ? i : first);
         }
     }
     // First the cheap half of the transition: new position and angle, hence the finished worlds -- one ballot per round
@@ -447,11 +461,21 @@ __global__ void __launch_bounds__(kBlock) mrl_cartpole_step_fused(uint32_t n, co
             reward[i] = 1.f;
             done[i] = over[u] ? 1 : 0;
 #endif
+            if constexpr (kStats) tally.finish(stats, i, running[u], 1.f, over[u]);
         }
     }
     CP_STAMP(6);
     if (!needs_prefix) return;
+    [[maybe_unused]] double *s_sums = nullptr;
+    if constexpr (kStats) {
+        __shared__ double s_stats[kBlock / 64][2];
+        s_sums = &s_stats[0][0];
+        if (block_total != 0) tally.to_lds(s_sums, wave, lane);  // uniform per workgroup
+    }
     mrl::lds_barrier();
+    if constexpr (kStats) {
+        if (threadIdx.x == 0 && block_total != 0) Stats::add_totals(stats, s_sums, kBlock / 64, b, block_total);
+    }
     const uint32_t prefix = s_prefix;
     for (uint32_t e = lane; e < wave_total; e += 64u) {  // this wave's finished worlds, one per lane
         const uint32_t entry = s_list[wave][e];
@@ -644,14 +668,24 @@ struct CartpoleSim final : mrl::EpisodeSim {
     void launch_fused(const int32_t *actions, const Drawn &drawn, const mrl::FusedExchange &fx, const Counters &c, hipStream_t stream) override
     {
         with_variant(variant, [&](auto v) {
-            hipLaunchKernelGGL(mrl_cartpole_step_fused<decltype(v)::value>, dim3(fused_grid), dim3(kBlock), 0, stream, num_worlds,
-                               actions ? actions : action, state, reward, done, status, group_total, epoch, c.base, c.next, reset_count,
-                               drawn.action_out, drawn.seed, drawn.step, heal, c.device, fx
+            if (stats_in_step())
+                hipLaunchKernelGGL((mrl_cartpole_step_fused<decltype(v)::value, true>), dim3(fused_grid), dim3(kBlock), 0, stream, num_worlds,
+                                   actions ? actions : action, state, reward, done, status, group_total, epoch, c.base, c.next, reset_count,
+                                   drawn.action_out, drawn.seed, drawn.step, heal, c.device, fx, stats->lane()
 #ifdef MRL_DIAG
-                               , stamps
+                                   , stamps
 #endif
-            );
+                );
+            else
+                hipLaunchKernelGGL((mrl_cartpole_step_fused<decltype(v)::value, false>), dim3(fused_grid), dim3(kBlock), 0, stream, num_worlds,
+                                   actions ? actions : action, state, reward, done, status, group_total, epoch, c.base, c.next, reset_count,
+                                   drawn.action_out, drawn.seed, drawn.step, heal, c.device, fx, mrl::NoStats{}
+#ifdef MRL_DIAG
+                                   , stamps
+#endif
+                );
         });
+        stats_taken = stats_in_step();
     }
 
     unsigned long long *ring = nullptr;
@@ -661,7 +695,8 @@ struct CartpoleSim final : mrl::EpisodeSim {
     void rollout_random(uint32_t num_steps, uint64_t seed, uint32_t first_step, hipStream_t stream) override
     {
         if (num_steps == 0) return;
-        if (persistent_ok && !launch_state.device_mode) {  // (a cooperative launch cannot be captured; its counters live on the host)
+        if (persistent_ok && !launch_state.device_mode && !stats) {  // (a cooperative launch cannot be captured; its counters live on the host;
+                                                                     // episode statistics are taken behind every step)
             // cooperative: the runtime checks the grid against what the device can hold at once and
             // refuses it otherwise -- then, and from then on, one launch per step
             uint32_t n = num_worlds, epoch0 = ring_epoch + 1u;
@@ -743,7 +778,7 @@ struct CartpoleSim final : mrl::EpisodeSim {
 
     size_t action_elems() const override { return (size_t)num_worlds; }
     const char *kernel_name() const override { return fused ? "mrl_cartpole_step_fused" : "mrl_cartpole_step"; }
-    const char *rollout_kernel_name() const override { return persistent_ok && !launch_state.device_mode ? "mrl_cartpole_rollout" : kernel_name(); }
+    const char *rollout_kernel_name() const override { return persistent_ok && !launch_state.device_mode && !stats ? "mrl_cartpole_rollout" : kernel_name(); }
     uint64_t bytes_per_world_step() const override { return 44; }
 };
 

@@ -182,6 +182,12 @@ struct ShardExchange {
 };
 }  // namespace mrl
 
+namespace mrl {
+// mrl_enable_episode_stats (episode_stats.hpp): the tensors of a simulator whose caller asked for them
+struct EpisodeStats;
+void episode_stats_destroy(EpisodeStats *stats);
+}  // namespace mrl
+
 // The opaque handle of the C ABI.
 struct mrl_sim {
     int game = 0;
@@ -190,8 +196,12 @@ struct mrl_sim {
     bool reseeded = false;  // mrl_reseed_shard was called: the worlds are a shard of a larger batch
     mrl::DeviceArena arena;
     mrl::ShardExchange exchange;
+    // nullptr until mrl_enable_episode_stats; capi.hip enqueues its update behind every completed step.  A simulator with
+    // stats runs its multi-step calls one step per launch (the persistent rollouts look at it)
+    mrl::EpisodeStats *stats = nullptr;
+    bool stats_taken = false;  // the step just enqueued kept the statistics in its own kernel: no update launch behind it
 
-    virtual ~mrl_sim() {}
+    virtual ~mrl_sim() { mrl::episode_stats_destroy(stats); }
     // actions == nullptr -> read the simulator's own ACTION tensor
     virtual void phase1(const int32_t *actions, hipStream_t stream) = 0;
     virtual void phase2(const uint32_t *episode_base_dev, hipStream_t stream) = 0;

@@ -8,6 +8,7 @@
 
 #include "common.hpp"
 #include "episode_scan.hpp"
+#include "episode_stats.hpp"
 #include "world_reset.hpp"
 
 #include <stdexcept>
@@ -88,6 +89,15 @@ struct EpisodeSim : mrl_sim {
         throw std::runtime_error("this game's step kernel draws no actions");
     }
     Finished stepped{};  // what phase 1 leaves (alloc_episode; Hanabi sets its flags)
+    // mrl_enable_episode_stats: the single-launch steps of Cartpole, Acrobot and the balance beam keep the statistics in
+    // their own kernel (their launch_fused asks this, launches the kStats instantiation and sets stats_taken); every other
+    // step is followed by the general update launch (capi.hip).  A measurement build without the in-kernel form, to
+    // compare the two: make EXTRA_CXXFLAGS=-DMRL_STATS_GENERAL_ONLY (tools/episode_stats_probe.py)
+#ifdef MRL_STATS_GENERAL_ONLY
+    bool stats_in_step() const { return false; }
+#else
+    bool stats_in_step() const { return stats != nullptr; }
+#endif
 
     // One launch that takes episode numbers: the device copy of the state advanced first, the counter's halves as of before
     // the flip.  (Graph replay depends on this order.)  launch(Counters)

@@ -2275,7 +2275,8 @@ struct HanabiSim final : mrl::EpisodeSim {
     void rollout_random(uint32_t num_steps, uint64_t seed, uint32_t first_step, hipStream_t stream) override
     {
         if (num_steps == 0) return;
-        if (persistent_ok && !launch_state.device_mode) {  // (a cooperative launch cannot be captured; its counters live on the host)
+        if (persistent_ok && !launch_state.device_mode && !stats) {  // (a cooperative launch cannot be captured; its counters live on the host;
+                                                                     // episode statistics are taken behind every step)
             if (launch_rollout(num_steps, seed, first_step, stream)) return;
             persistent_ok = false;  // refused: one launch per step from now on (needs no co-residency)
         }
@@ -2328,7 +2329,7 @@ struct HanabiSim final : mrl::EpisodeSim {
 
     size_t action_elems() const override { return (size_t)2 * num_worlds; }
     const char *kernel_name() const override { return fused ? "mrl_hanabi_step_fused" : "mrl_hanabi_step"; }
-    const char *rollout_kernel_name() const override { return persistent_ok && !launch_state.device_mode ? "mrl_hanabi_rollout" : kernel_name(); }
+    const char *rollout_kernel_name() const override { return persistent_ok && !launch_state.device_mode && !stats ? "mrl_hanabi_rollout" : kernel_name(); }
 
     uint64_t bytes_per_world_step() const override
     {

@@ -10,15 +10,16 @@ from math import pi
 import numpy as np
 import torch
 
-from ..simulators import AcrobotSimulator, ExecMode
+from ..simulators import AcrobotSimulator, ExecMode, RecordsEpisodeStatistics
 from ..spaces import Box, Discrete
 
 MAX_VEL_1 = 4 * pi
 MAX_VEL_2 = 9 * pi
 
 
-class _AcrobotBase:
-    def __init__(self, num_envs, gpu_id, debug_compile=True, use_cpu=False, use_env_cpu=False, observation="state"):
+class _AcrobotBase(RecordsEpisodeStatistics):
+    def __init__(self, num_envs, gpu_id, debug_compile=True, use_cpu=False, use_env_cpu=False, observation="state",
+                 record_episode_statistics=False):
         if observation not in ("state", "gym"):
             raise ValueError(f"observation must be 'state' or 'gym', got {observation!r}")
         self.observation = observation
@@ -37,6 +38,7 @@ class _AcrobotBase:
         self.static_rewards = self.sim.reward_tensor().to_torch()
         self.device = torch.device("cpu") if use_env_cpu else self.static_observations.device
         self.infos = [{}] * self.num_envs
+        self._record_episode_statistics(record_episode_statistics)
 
     def _observe(self):
         state = self.static_observations

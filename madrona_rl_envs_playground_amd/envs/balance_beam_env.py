@@ -16,11 +16,11 @@ SCALE = 0.2
 
 class BalanceMadronaTorch(MadronaEnv):
 
-    def __init__(self, num_envs, gpu_id, debug_compile=True, use_cpu=False, use_env_cpu=False):
+    def __init__(self, num_envs, gpu_id, debug_compile=True, use_cpu=False, use_env_cpu=False, record_episode_statistics=False):
         sim = BalanceBeamSimulator(exec_mode=ExecMode.CPU if use_cpu else ExecMode.CUDA, gpu_id=gpu_id,
                                    num_worlds=num_envs, debug_compile=debug_compile)
         device = torch.device("cpu") if use_env_cpu else None
-        super().__init__(num_envs, gpu_id, sim, env_device=device)
+        super().__init__(num_envs, gpu_id, sim, env_device=device, record_episode_statistics=record_episode_statistics)
         self.observation_space = MultiDiscrete([NUM_SPACES + 2 * BUFFER] * 2 * TIME + [TIME])
         self.action_space = Discrete(len(VALID_MOVES))
         self.share_observation_space = self.observation_space

@@ -7,15 +7,15 @@ from math import pi
 import numpy as np
 import torch
 
-from ..simulators import CartpoleSimulator, ExecMode
+from ..simulators import CartpoleSimulator, ExecMode, RecordsEpisodeStatistics
 from ..spaces import Box, Discrete
 
 X_THRESHOLD = 2.4
 THETA_THRESHOLD_RADIANS = 12 * 2 * pi / 360
 
 
-class _CartpoleBase:
-    def __init__(self, num_envs, gpu_id, debug_compile=True, use_cpu=False, use_env_cpu=False):
+class _CartpoleBase(RecordsEpisodeStatistics):
+    def __init__(self, num_envs, gpu_id, debug_compile=True, use_cpu=False, use_env_cpu=False, record_episode_statistics=False):
         high = np.array([X_THRESHOLD * 2, np.finfo(np.float32).max, THETA_THRESHOLD_RADIANS * 2,
                          np.finfo(np.float32).max], dtype=np.float32)
         self.num_envs = num_envs
@@ -29,6 +29,7 @@ class _CartpoleBase:
         self.static_rewards = self.sim.reward_tensor().to_torch()
         self.device = torch.device("cpu") if use_env_cpu else self.static_observations.device
         self.infos = [{}] * self.num_envs
+        self._record_episode_statistics(record_episode_statistics)
 
     def close(self, **kwargs):
         self.sim.close()

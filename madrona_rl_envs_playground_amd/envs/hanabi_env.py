@@ -22,7 +22,8 @@ config_choice = {"very_small": VERY_SMALL_CONFIG, "small": SMALL_CONFIG, "full":
 
 class HanabiMadrona(MadronaEnv):
 
-    def __init__(self, num_envs, gpu_id, debug_compile=True, config=None, use_cpu=False, use_env_cpu=False):
+    def __init__(self, num_envs, gpu_id, debug_compile=True, config=None, use_cpu=False, use_env_cpu=False,
+                 record_episode_statistics=False):
         self.config = config if config is not None else DEFAULT_CONFIG
         config = self.config
         sim = HanabiSimulator(exec_mode=ExecMode.CPU if use_cpu else ExecMode.CUDA, gpu_id=gpu_id,
@@ -37,7 +38,8 @@ class HanabiMadrona(MadronaEnv):
         self.share_observation_space = MultiBinary(state_size)
         device = torch.device("cpu") if use_env_cpu else None
         super().__init__(num_envs=num_envs, gpu_id=gpu_id, sim=sim, debug_compile=debug_compile, obs_size=obs_size,
-                         state_size=state_size, discrete_action_size=max_moves, env_device=device)
+                         state_size=state_size, discrete_action_size=max_moves, env_device=device,
+                         record_episode_statistics=record_episode_statistics)
 
     def close(self, **kwargs):
         self.sim.close()

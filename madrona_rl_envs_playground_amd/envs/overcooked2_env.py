@@ -12,16 +12,16 @@ import torch
 from ..layouts import get_simplecooked_layout_params as get_base_layout_params  # noqa: F401  (reference name)
 from ..pantheonrl_extension.vectorenv import VectorMultiAgentEnv
 from ..pantheonrl_extension.vectorobservation import VectorObservation
-from ..simulators import ExecMode, SimplecookedSimulator
+from ..simulators import ExecMode, RecordsEpisodeStatistics, SimplecookedSimulator
 from ..spaces import Discrete, MultiBinary
 
 NUM_ACTIONS = 6  # oldercooked_ai_py Action.ALL_ACTIONS
 
 
-class OvercookedMadrona(VectorMultiAgentEnv):
+class OvercookedMadrona(RecordsEpisodeStatistics, VectorMultiAgentEnv):
 
     def __init__(self, layout_name, num_envs, gpu_id, debug_compile=True, use_cpu=False, use_env_cpu=False,
-                 ego_agent_idx=0, horizon=200, num_players=None):
+                 ego_agent_idx=0, horizon=200, num_players=None, record_episode_statistics=False):
         self.layout_name = layout_name
         self.base_layout_params = get_base_layout_params(layout_name, horizon, max_num_players=num_players)
         self.width = self.base_layout_params["width"]
@@ -52,6 +52,7 @@ class OvercookedMadrona(VectorMultiAgentEnv):
         super().__init__(num_envs, device=env_device, n_players=self.num_players)
 
         self.infos = [{}] * self.num_envs
+        self._record_episode_statistics(record_episode_statistics)
         self.ego_ind = ego_agent_idx
         self.observation_space = self._setup_observation_space()
         self.share_observation_space = self.observation_space

@@ -17,6 +17,7 @@ from typing import Any, List, Optional
 import numpy as np
 import torch
 
+from ..simulators import RecordsEpisodeStatistics
 from .vectoragent import VectorAgent
 from .vectorobservation import VectorObservation
 
@@ -192,12 +193,12 @@ class VectorMultiAgentEnv(ABC):
         pass
 
 
-class MadronaEnv(VectorMultiAgentEnv):
+class MadronaEnv(RecordsEpisodeStatistics, VectorMultiAgentEnv):
     """Generic wrapper over a simulator exporting (players, worlds, ...) tensors;
     used by Hanabi (/root/reference/envs/hanabi_env.py:72-104)."""
 
     def __init__(self, num_envs, gpu_id, sim, debug_compile=True, obs_size=None, state_size=None,
-                 discrete_action_size=None, env_device=None):
+                 discrete_action_size=None, env_device=None, record_episode_statistics=False):
         self.sim = sim
         self.static_dones = sim.done_tensor().to_torch()
         self.static_active_agents = sim.active_agent_tensor().to_torch()
@@ -224,6 +225,7 @@ class MadronaEnv(VectorMultiAgentEnv):
             env_device = self.static_observations.device
         super().__init__(num_envs, device=env_device, n_players=self.static_observations.shape[0])
         self.infos = [{}] * self.num_envs
+        self._record_episode_statistics(record_episode_statistics)
 
     def to_torch(self, a):
         return a.to(self.device)

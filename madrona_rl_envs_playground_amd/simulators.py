@@ -56,6 +56,7 @@ _TORCH_DTYPE = {
     _lib.MRL_INT32: (torch.int32, "<i4", 4),
     _lib.MRL_FLOAT32: (torch.float32, "<f4", 4),
     _lib.MRL_UINT32: (torch.int32, "<i4", 4),  # torch has no general uint32; same bits
+    _lib.MRL_FLOAT64: (torch.float64, "<f8", 8),
 }
 
 
@@ -144,6 +145,49 @@ def random_hanabi_action(seed, step, world, mover, legal_mask):
     rank = np.cumsum(legal_mask, axis=-1) - 1                      # rank of each legal move among the legal ones
     pick = legal_mask & (rank == k[:, None].astype(np.int64))
     return np.where(count > 0, pick.argmax(-1), 0).astype(np.int32)
+
+
+def totals_of(totals):
+    """The column sums of a TOTALS tensor (float64, (blocks, 2 + players)) as ``episode_totals`` returns them."""
+    sums = totals.sum(dim=0).tolist()  # (the host waits here)
+    return {"episodes": int(round(sums[0])), "steps": int(round(sums[1])), "returns": [float(v) for v in sums[2:]]}
+
+
+class EpisodeStats:
+    """What ``env.episode_stats`` is for an env wrapper built with ``record_episode_statistics=True``: the five tensors of
+    ``mrl_enable_episode_stats`` as persistent torch views on the simulator's GPU."""
+
+    def __init__(self, sim):
+        sim.enable_episode_stats()
+        self.episode_return = sim.episode_return_tensor().to_torch()
+        self.episode_steps = sim.episode_steps_tensor().to_torch()
+        self.last_return = sim.last_episode_return_tensor().to_torch()
+        self.last_steps = sim.last_episode_steps_tensor().to_torch()
+        self.totals = sim.episode_totals_tensor().to_torch()
+
+
+class RecordsEpisodeStatistics:
+    """Mixin of the env wrappers (``self.sim`` is the simulator): the ``record_episode_statistics`` keyword.  ``infos`` stays
+    as it is -- per-world dicts would mean a host synchronisation per step; the numbers are tensors and one call."""
+
+    episode_stats = None
+
+    def _record_episode_statistics(self, record):
+        if record:
+            self.episode_stats = EpisodeStats(self.sim)
+
+    def _recording(self):
+        if self.episode_stats is None:
+            raise MrlError("this environment was built without record_episode_statistics=True")
+
+    def episode_totals(self):
+        """``sim.episode_totals()``: episodes finished since the last clear, their steps and returns (waits for the GPU)."""
+        self._recording()
+        return self.sim.episode_totals()
+
+    def clear_episode_totals(self):
+        self._recording()
+        self.sim.clear_episode_totals()
 
 
 class _Simulator:
@@ -329,6 +373,28 @@ class _Simulator:
                 ring.dtype not in (torch.int8, torch.uint8) or not ring[0].is_contiguous()):
             raise ValueError(f"ring must be an int8 tensor (T, N, P, H, W, F) on cuda:{self.gpu_id} with contiguous slots")
         _lib.check(self._L.mrl_set_observation_ring(self._handle, ring.data_ptr(), int(ring.stride(0)), int(ring.shape[0])))
+
+    # --- episode returns and lengths on the device (mrl_enable_episode_stats) ---
+    def enable_episode_stats(self):
+        """From now on every completed step also keeps the worlds' episode returns and lengths, on the device
+        (``mrl_enable_episode_stats``: five more tensors, for the rest of the simulator's life; a second call does nothing).
+        Call it outside a graph capture."""
+        _lib.check(self._L.mrl_enable_episode_stats(self._handle, _stream_ptr(self.gpu_id)))
+
+    def clear_episode_totals(self):
+        """Zeroes ``episode_totals_tensor()`` and nothing else (``mrl_clear_episode_totals``); enqueued, no host sync."""
+        _lib.check(self._L.mrl_clear_episode_totals(self._handle, _stream_ptr(self.gpu_id)))
+
+    def episode_return_tensor(self): return self._tensor(_lib.STATS_EPISODE_RETURN)  # float32, REWARD's shape
+    def episode_steps_tensor(self): return self._tensor(_lib.STATS_EPISODE_STEPS)  # int32, DONE's shape
+    def last_episode_return_tensor(self): return self._tensor(_lib.STATS_LAST_RETURN)
+    def last_episode_steps_tensor(self): return self._tensor(_lib.STATS_LAST_STEPS)
+    def episode_totals_tensor(self): return self._tensor(_lib.STATS_TOTALS)  # float64 (ceil(N / 1024), 2 + players)
+
+    def episode_totals(self):
+        """``{"episodes": int, "steps": int, "returns": [float] * players}`` of the episodes finished since the last
+        ``clear_episode_totals``: the column sums of ``episode_totals_tensor()``.  The one call here that waits for the GPU."""
+        return totals_of(self.episode_totals_tensor().to_torch())
 
     @property
     def scan_timed_out(self):
