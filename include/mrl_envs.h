@@ -536,6 +536,66 @@ enum {
 int mrl_enable_episode_stats(mrl_sim *sim, void *hip_stream);
 int mrl_clear_episode_totals(mrl_sim *sim, void *hip_stream);
 
+/* Policy rollouts on the device: the collection phase of PPO for Cartpole and Acrobot.  The reference's trainer runs, per
+ * step, two three-layer tanh MLPs (scripts/cartpole_train_torch.py:105-131, Agent), a Categorical sample, a log_prob and six
+ * buffer row copies in torch around the step (:204-218), then T sequential torch iterations for the advantages (:243-256).
+ * Here the first is ONE launch per step in front of the simulator's ordinary step (mrl_policy_act) and the second one launch
+ * (mrl_gae).  No reference counterpart as a call.
+ *   Policy: critic and actor are Linear(D, 64), tanh, Linear(64, 64), tanh, Linear(64, 1 or A).  params_dev is one flat float32
+ *     device array in the order of torch.nn.utils.parameters_to_vector(agent.parameters()) for that Agent: critic.0.weight
+ *     (64, D) row-major, critic.0.bias, critic.2.weight, critic.2.bias, critic.4.weight, critic.4.bias, then actor.0 ... actor.4;
+ *     mrl_mlp_policy_num_params floats.  The kernel reads it in place in every launch: between rollouts a trainer does its
+ *     optimizer step and one flat copy.  hidden must be 64; num_actions 2 (Cartpole) or 3 (Acrobot).
+ *   Observation: MRL_OBS_RAW, D = 4, is the STATE row; MRL_OBS_ACROBOT_GYM, D = 6, Acrobot only, is Gym's
+ *     [cos theta1, sin theta1, cos theta2, sin theta2, omega1, omega2] computed from it.
+ *   Buffers: dense device arrays, T = num_steps; obs / next_obs start on a 16-byte (D = 4) or 8-byte (D = 6) boundary.
+ *   Row k < T, world w, from the tensors as they stand in front of step k of the call:
+ *     obs[k,w,:] the observation; dones[k,w] = RESET[w] != 0 as 0.0 / 1.0 -- the previous step's flag, like `dones[step] =
+ *     next_done` (:207) --; values[k,w] the critic; actions[k,w] the draw, also written to ACTION[w]; logprobs[k,w]; and for
+ *     k > 0 rewards[k-1,w] = REWARD[w].  Then the step runs.  The closing launch (k = T) writes rewards[T-1], next_obs,
+ *     next_done and next_value (:244) and draws nothing.  num_steps == 0 writes the next_* arrays only.
+ *   Sampling, replayable on the host like mrl_rollout_random: h = the hash given there of (seed, first_step + k, w, player 0);
+ *     u = (h >> 8) * 2^-24 (exact in float32); m = max logit; e_a = exp(l_a - m); p_a = e_a / sum e; action = the number of a in
+ *     0..A-2 with u >= p_0 + ... + p_a; logprob = (l_action - m) - log(sum e); all in float32.  With MRL_POLICY_GREEDY in
+ *     flags the action is the first arg-max of the logits (evaluation); logprob is written all the same.
+ *   Arithmetic: every dot product starts from the bias and adds the inputs in ascending order with fused multiply-adds.
+ * mrl_rollout_policy enqueues T x (act, step) + the closing act and never synchronises: two launches per step (plus the
+ *   statistics update after mrl_enable_episode_stats, plus the advance launch after mrl_prepare_graph_capture).  The step is
+ *   mrl_step reading the ACTION tensor, so the call equals, row for row, T times "act on the current state, mrl_step", and
+ *   afterwards the simulator is exactly where T mrl_step_with_actions calls with actions[0..T-1] would have left it (and its
+ *   ACTION tensor holds actions[T-1]): episode numbering, statistics and SCAN_TIMEOUT behave as there.
+ *   MRL_ERR_INVALID: a game other than Cartpole or Acrobot; hidden != 64; num_actions other than the game's; an (obs_dim,
+ *   obs_mode) other than (4, RAW) or, for Acrobot, (6, ACROBOT_GYM); any NULL pointer; a misaligned obs / next_obs; a capturing
+ *   stream wherever mrl_step refuses one; a simulator that has been through mrl_exchange_create.  Capturing a rollout in a HIP
+ *   graph is not supported in any mode: the row index travels in kernel arguments.  The balance beam (two agents, integer
+ *   observations) and the other games are out of scope.
+ * mrl_gae is lines 247-256 with a lane per world, t = T-1 ... 0 in float32, one IEEE operation per operation of the script:
+ *     nnt = 1 - (t == T-1 ? next_done[w] : dones[t+1,w]);  nv = t == T-1 ? next_value[w] : values[t+1,w]
+ *     delta = rewards[t,w] + gamma * nv * nnt - values[t,w]
+ *     advantages[t,w] = last = delta + gl * nnt * last;  returns[t,w] = advantages[t,w] + values[t,w]
+ *   with gl = float32(double(gamma) * double(lambda)) (the script multiplies the two Python floats first).  All arrays (T, N)
+ *   dense on device gpu_id, next_* (N); it only enqueues.  MRL_ERR_INVALID for a NULL array.  DESIGN.md section 12. */
+enum { MRL_OBS_RAW = 0, MRL_OBS_ACROBOT_GYM = 1 };
+enum { MRL_POLICY_GREEDY = 1 };
+typedef struct mrl_mlp_policy {
+    const float *params_dev;
+    uint32_t obs_dim, hidden, num_actions, obs_mode, flags;
+} mrl_mlp_policy;
+typedef struct mrl_rollout_buffers { /* all device pointers, dense, T = num_steps */
+    float *obs;                      /* (T, N, D) */
+    int32_t *actions;                /* (T, N) */
+    float *logprobs, *values, *rewards, *dones; /* (T, N) */
+    float *next_obs;                 /* (N, D) */
+    float *next_value, *next_done;   /* (N) */
+    uint32_t num_steps;
+} mrl_rollout_buffers;
+uint64_t mrl_mlp_policy_num_params(uint32_t obs_dim, uint32_t hidden, uint32_t num_actions);
+int mrl_rollout_policy(mrl_sim *sim, const mrl_mlp_policy *policy, const mrl_rollout_buffers *buffers, uint64_t seed,
+                       uint32_t first_step, void *hip_stream);
+int mrl_gae(const float *rewards, const float *values, const float *dones, const float *next_value, const float *next_done,
+            uint32_t num_steps, uint32_t num_worlds, float gamma, float lambda, float *advantages, float *returns, int gpu_id,
+            void *hip_stream);
+
 int mrl_tensor(mrl_sim *sim, int slot, mrl_tensor_desc *out);
 int mrl_game(const mrl_sim *sim);
 uint32_t mrl_num_worlds(const mrl_sim *sim);

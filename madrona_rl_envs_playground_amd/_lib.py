@@ -26,6 +26,8 @@ MRL_FLOAT64 = 5
 STATS_EPISODE_RETURN, STATS_EPISODE_STEPS, STATS_LAST_RETURN, STATS_LAST_STEPS, STATS_TOTALS = 64, 65, 66, 67, 68
 MAX_DIMS = 6
 MAX_RANKS, IPC_HANDLE_BYTES = 16, 64  # MRL_MAX_RANKS, MRL_IPC_HANDLE_BYTES
+OBS_RAW, OBS_ACROBOT_GYM = 0, 1  # MRL_OBS_*: the observation mrl_rollout_policy forms from STATE
+POLICY_GREEDY = 1  # MRL_POLICY_GREEDY
 
 # every symbol include/mrl_envs.h declares
 SYMBOLS = [
@@ -36,7 +38,8 @@ SYMBOLS = [
     "mrl_scan_timed_out", "mrl_simplecooked_create", "mrl_launch_shape", "mrl_balance_create", "mrl_step_with_actions_i64",
     "mrl_step_phase2_gathered", "mrl_set_observation_output", "mrl_set_observation_ring", "mrl_prepare_graph_capture", "mrl_step_many",
     "mrl_build_hash", "mrl_exchange_create", "mrl_exchange_connect", "mrl_step_exchanged", "mrl_reset_worlds",
-    "mrl_acrobot_create", "mrl_enable_episode_stats", "mrl_clear_episode_totals",
+    "mrl_acrobot_create", "mrl_enable_episode_stats", "mrl_clear_episode_totals", "mrl_mlp_policy_num_params",
+    "mrl_rollout_policy", "mrl_gae",
 ]
 ABI_VERSION = 4  # MRL_ABI_VERSION of include/mrl_envs.h this binding was written against
 
@@ -59,6 +62,16 @@ class OvercookedConfig(ctypes.Structure):
 class HanabiConfig(ctypes.Structure):
     _fields_ = [("colors", ctypes.c_uint32), ("ranks", ctypes.c_uint32), ("players", ctypes.c_uint32),
                 ("max_information_tokens", ctypes.c_uint32), ("max_life_tokens", ctypes.c_uint32)]
+
+
+class MlpPolicyDesc(ctypes.Structure):  # mrl_mlp_policy
+    _fields_ = [("params_dev", ctypes.c_void_p), ("obs_dim", ctypes.c_uint32), ("hidden", ctypes.c_uint32),
+                ("num_actions", ctypes.c_uint32), ("obs_mode", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class RolloutBuffers(ctypes.Structure):  # mrl_rollout_buffers
+    _fields_ = [(name, ctypes.c_void_p) for name in ("obs", "actions", "logprobs", "values", "rewards", "dones", "next_obs",
+                                                     "next_value", "next_done")] + [("num_steps", ctypes.c_uint32)]
 
 
 class MrlError(RuntimeError):
@@ -167,6 +180,10 @@ def lib():
     L.mrl_reset_worlds.argtypes = [vp, vp, vp]
     L.mrl_enable_episode_stats.argtypes = [vp, vp]
     L.mrl_clear_episode_totals.argtypes = [vp, vp]
+    L.mrl_mlp_policy_num_params.argtypes = [u32, u32, u32]
+    L.mrl_mlp_policy_num_params.restype = ctypes.c_uint64
+    L.mrl_rollout_policy.argtypes = [vp, ctypes.POINTER(MlpPolicyDesc), ctypes.POINTER(RolloutBuffers), ctypes.c_uint64, u32, vp]
+    L.mrl_gae.argtypes = [vp, vp, vp, vp, vp, u32, u32, ctypes.c_float, ctypes.c_float, vp, vp, i32, vp]
     L.mrl_tensor.argtypes = [vp, i32, ctypes.POINTER(TensorDesc)]
     L.mrl_game.argtypes = [vp]
     L.mrl_num_worlds.argtypes = [vp]

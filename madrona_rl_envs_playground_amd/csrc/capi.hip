@@ -2,6 +2,7 @@
 #include "common.hpp"
 #include "episode_scan.hpp"
 #include "episode_stats.hpp"
+#include "policy_rollout.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -607,6 +608,100 @@ int mrl_rollout_random(mrl_sim *sim, uint32_t num_steps, uint64_t seed, uint32_t
             sim->rollout_random(1, seed, first_step + k, (hipStream_t)hip_stream);
             mrl::completed_step(sim, (hipStream_t)hip_stream);
         }
+    });
+}
+
+uint64_t mrl_mlp_policy_num_params(uint32_t obs_dim, uint32_t hidden, uint32_t num_actions)
+{
+    return mrl::mlp_net_params(obs_dim, hidden, 1) + mrl::mlp_net_params(obs_dim, hidden, num_actions);
+}
+
+int mrl_rollout_policy(mrl_sim *sim, const mrl_mlp_policy *policy, const mrl_rollout_buffers *buffers, uint64_t seed,
+                       uint32_t first_step, void *hip_stream)
+{
+    if (int rc = mrl::need_healthy(sim)) return rc;
+    if (int rc = mrl::need_not_capturing(sim, hip_stream, "mrl_rollout_policy")) return rc;
+    if (sim->game != MRL_GAME_CARTPOLE && sim->game != MRL_GAME_ACROBOT) {
+        mrl::set_error("mrl_rollout_policy: game %d has no policy rollout (Cartpole and Acrobot do)", sim->game);
+        return MRL_ERR_INVALID;
+    }
+    if (sim->exchange.mine) {
+        mrl::set_error("mrl_rollout_policy: this simulator is a rank of an exchanged batch (mrl_exchange_create); its step needs the other ranks");
+        return MRL_ERR_INVALID;
+    }
+    if (!policy || !buffers || !policy->params_dev) {
+        mrl::set_error("mrl_rollout_policy: null policy, parameter array or buffer description");
+        return MRL_ERR_INVALID;
+    }
+    const uint32_t actions = sim->game == MRL_GAME_CARTPOLE ? 2u : 3u;
+    const bool raw = policy->obs_dim == 4 && policy->obs_mode == MRL_OBS_RAW;
+    const bool gym = policy->obs_dim == 6 && policy->obs_mode == MRL_OBS_ACROBOT_GYM && sim->game == MRL_GAME_ACROBOT;
+    if (policy->hidden != mrl::kPolicyHidden || policy->num_actions != actions || !(raw || gym)) {
+        mrl::set_error("mrl_rollout_policy: need hidden = 64, num_actions = %u and (obs_dim, obs_mode) = (4, MRL_OBS_RAW)%s for game %d; got "
+                       "hidden %u, num_actions %u, obs_dim %u, obs_mode %u", actions,
+                       sim->game == MRL_GAME_ACROBOT ? " or (6, MRL_OBS_ACROBOT_GYM)" : "", sim->game, policy->hidden,
+                       policy->num_actions, policy->obs_dim, policy->obs_mode);
+        return MRL_ERR_INVALID;
+    }
+    const mrl_rollout_buffers &b = *buffers;
+    const uint32_t T = b.num_steps;
+    if (!b.next_obs || !b.next_value || !b.next_done ||
+        (T && (!b.obs || !b.actions || !b.logprobs || !b.values || !b.rewards || !b.dones))) {
+        mrl::set_error("mrl_rollout_policy: null rollout buffer");
+        return MRL_ERR_INVALID;
+    }
+    const uintptr_t row_align = policy->obs_dim == 4 ? 15u : 7u;  // the observation rows are stored 16 / 8 bytes at a time
+    if ((reinterpret_cast<uintptr_t>(b.obs) | reinterpret_cast<uintptr_t>(b.next_obs)) & row_align) {
+        mrl::set_error("mrl_rollout_policy: obs and next_obs must start on a %u-byte boundary", (unsigned)row_align + 1u);
+        return MRL_ERR_INVALID;
+    }
+    mrl::DeviceGuard on(sim->device);
+    return guarded([&] {
+        hipStream_t stream = (hipStream_t)hip_stream;
+        mrl_tensor_desc state{}, reset{}, reward{}, action{};
+        // (the slot numbers are the same for both games: MRL_CARTPOLE_* == MRL_ACROBOT_*)
+        if (!sim->tensor(MRL_CARTPOLE_STATE, &state) || !sim->tensor(MRL_CARTPOLE_RESET, &reset) ||
+            !sim->tensor(MRL_CARTPOLE_REWARD, &reward) || !sim->tensor(MRL_CARTPOLE_ACTION, &action))
+            throw std::runtime_error("mrl_rollout_policy: the simulator does not export STATE / RESET / REWARD / ACTION");
+        const size_t N = sim->num_worlds, D = policy->obs_dim;
+        mrl::PolicyActArgs args{};
+        args.params = policy->params_dev;
+        args.state = static_cast<const float *>(state.data);
+        args.reset = static_cast<const int32_t *>(reset.data);
+        args.reward = static_cast<const float *>(reward.data);
+        args.action_tensor = static_cast<int32_t *>(action.data);
+        args.seed = seed;
+        args.num_worlds = sim->num_worlds;
+        args.flags = policy->flags;
+        for (uint32_t k = 0; k <= T; k++) {
+            const bool closing = k == T;
+            args.obs_row = closing ? b.next_obs : b.obs + k * N * D;
+            args.done_row = closing ? b.next_done : b.dones + k * N;
+            args.value_row = closing ? b.next_value : b.values + k * N;
+            args.reward_row = k ? b.rewards + (k - 1) * N : nullptr;
+            args.action_row = closing ? nullptr : b.actions + k * N;
+            args.logprob_row = closing ? nullptr : b.logprobs + k * N;
+            args.step = first_step + k;
+            mrl::launch_policy_act(*policy, args, stream);
+            if (closing) break;
+            sim->step(nullptr, stream);
+            mrl::completed_step(sim, stream);
+        }
+    });
+}
+
+int mrl_gae(const float *rewards, const float *values, const float *dones, const float *next_value, const float *next_done,
+            uint32_t num_steps, uint32_t num_worlds, float gamma, float lambda, float *advantages, float *returns, int gpu_id,
+            void *hip_stream)
+{
+    if (!next_value || !next_done || (num_steps && (!rewards || !values || !dones || !advantages || !returns))) {
+        mrl::set_error("mrl_gae: null array");
+        return MRL_ERR_INVALID;
+    }
+    mrl::DeviceGuard on(gpu_id);
+    return guarded([&] {
+        mrl::launch_gae(rewards, values, dones, next_value, next_done, num_steps, num_worlds, gamma, lambda, advantages, returns,
+                        (hipStream_t)hip_stream);
     });
 }
 

@@ -68,6 +68,13 @@ class AcrobotMadronaTorch(_AcrobotBase):
             self.sim.reset_worlds(worlds)
         return self.to_torch(self._observe())
 
+    def rollout(self, policy, num_steps, seed=0, first_step=0, out=None, greedy=False):
+        """``num_steps`` steps under ``policy`` (``simulators.MlpPolicy``) collected on the device, observing what this
+        environment observes (``sim.rollout_policy``).  Returns a ``Rollout``."""
+        if policy.observation != self.observation:
+            raise ValueError(f"this environment observes {self.observation!r}, the policy {policy.observation!r}")
+        return self.sim.rollout_policy(policy, num_steps, seed=seed, first_step=first_step, out=out, greedy=greedy)
+
 
 class AcrobotMadronaNumpy(_AcrobotBase):
     def step(self, actions):

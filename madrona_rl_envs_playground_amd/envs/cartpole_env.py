@@ -52,6 +52,13 @@ class CartpoleMadronaTorch(_CartpoleBase):
             self.sim.reset_worlds(worlds)
         return self.to_torch(self.static_observations)
 
+    def rollout(self, policy, num_steps, seed=0, first_step=0, out=None, greedy=False):
+        """``num_steps`` steps under ``policy`` (``simulators.MlpPolicy``) collected on the device: the loop of
+        the reference's scripts/cartpole_train_torch.py:204-218 as ``sim.rollout_policy``.  Returns a ``Rollout``."""
+        if policy.observation != "state":
+            raise ValueError(f"this environment observes 'state', the policy {policy.observation!r}")
+        return self.sim.rollout_policy(policy, num_steps, seed=seed, first_step=first_step, out=out, greedy=greedy)
+
 
 class CartpoleMadronaNumpy(_CartpoleBase):
     def step(self, actions):

@@ -18,6 +18,7 @@ Everything is computed by libmrl_envs.so (HIP, gfx950).  ``ExecMode.CPU`` raises
 the reference's CPU TaskGraph executor is out of scope, and a
 silent CPU path would defeat the parity tests.
 """
+import collections
 import ctypes
 import enum
 
@@ -116,6 +117,14 @@ def random_hash(seed, step, world, player):
     return h.astype(np.uint32)
 
 
+def sample_u(seed, step, world):
+    """The uniform number behind ``rollout_policy``'s draw for (step index, world): ``(hash >> 8) * 2^-24`` with player 0,
+    a multiple of 2^-24 in [0, 1) and exact in float32 (``mrl_rollout_policy``).  float32 array."""
+    import numpy as np
+    h = random_hash(seed, step, world, np.zeros_like(np.asarray(world)))
+    return (h >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+
+
 def random_action(seed, step, world, player):
     """Overcooked: ``(hash * 6) >> 32`` for (step index, world, player)."""
     import numpy as np
@@ -145,6 +154,118 @@ def random_hanabi_action(seed, step, world, mover, legal_mask):
     rank = np.cumsum(legal_mask, axis=-1) - 1                      # rank of each legal move among the legal ones
     pick = legal_mask & (rank == k[:, None].astype(np.int64))
     return np.where(count > 0, pick.argmax(-1), 0).astype(np.int32)
+
+
+def _mlp(inputs, hidden, outputs):
+    nn = torch.nn
+    return nn.Sequential(nn.Linear(inputs, hidden), nn.Tanh(), nn.Linear(hidden, hidden), nn.Tanh(), nn.Linear(hidden, outputs))
+
+
+class MlpAgent(torch.nn.Module):
+    """What ``MlpPolicy.module()`` returns: the actor-critic of the reference's trainer (scripts/cartpole_train_torch.py:105-131,
+    ``Agent``) by shape and method names, for the update phase.  Initialisation is torch's default; the trainer's is its own."""
+
+    def __init__(self, obs_dim, num_actions, hidden=64):
+        super().__init__()
+        self.critic = _mlp(obs_dim, hidden, 1)
+        self.actor = _mlp(obs_dim, hidden, num_actions)
+
+    def get_value(self, x):
+        return self.critic(x)
+
+    def get_action_and_value(self, x, action=None):
+        dist = torch.distributions.Categorical(logits=self.actor(x))
+        if action is None:
+            action = dist.sample()
+        return action, dist.log_prob(action), dist.entropy(), self.critic(x)
+
+
+class MlpPolicy:
+    """The parameters ``rollout_policy`` runs: one flat float32 tensor ``params`` in the order of
+    ``parameters_to_vector(agent.parameters())`` for an agent with ``critic`` and ``actor`` =
+    ``Sequential(Linear(D, 64), Tanh, Linear(64, 64), Tanh, Linear(64, 1 or A))`` (``mrl_mlp_policy``).  The kernel reads the
+    tensor in place: between rollouts a trainer steps its optimizer and calls ``load_(agent)``.  ``observation``: "state"
+    (the simulator's STATE row, D = 4) or "gym" (Acrobot's six values, D = 6)."""
+
+    def __init__(self, obs_dim, num_actions, hidden=64, observation="state", device="cuda:0"):
+        if observation not in ("state", "gym"):
+            raise ValueError(f"observation must be 'state' or 'gym', got {observation!r}")
+        self.obs_dim, self.num_actions, self.hidden, self.observation = int(obs_dim), int(num_actions), int(hidden), observation
+        count = int(_lib.lib().mrl_mlp_policy_num_params(self.obs_dim, self.hidden, self.num_actions))
+        self.params = torch.zeros(count, dtype=torch.float32, device=torch.device(device))
+
+    @staticmethod
+    def _shape_of(agent):
+        """(obs_dim, num_actions, hidden) of an agent of the expected form; ValueError otherwise."""
+        nn = torch.nn
+        nets = []
+        for name in ("critic", "actor"):
+            net = getattr(agent, name, None)
+            if (not isinstance(net, nn.Sequential) or len(net) != 5 or not all(isinstance(net[i], nn.Linear) for i in (0, 2, 4)) or
+                    not all(isinstance(net[i], nn.Tanh) for i in (1, 3)) or any(net[i].bias is None for i in (0, 2, 4))):
+                raise ValueError(f"agent.{name} must be Sequential(Linear, Tanh, Linear, Tanh, Linear) with biases")
+            nets.append(net)
+        critic, actor = nets
+        d, h = critic[0].in_features, critic[0].out_features
+        for net, out in ((critic, 1), (actor, actor[4].out_features)):
+            shapes = [(net[i].in_features, net[i].out_features) for i in (0, 2, 4)]
+            if shapes != [(d, h), (h, h), (h, out)]:
+                raise ValueError(f"agent's layers are {shapes}, expected {[(d, h), (h, h), (h, out)]}")
+        return d, actor[4].out_features, h
+
+    @staticmethod
+    def _flat(agent):
+        return torch.cat([p.detach().reshape(-1) for net in (agent.critic, agent.actor) for p in net.parameters()])
+
+    @classmethod
+    def from_module(cls, agent, observation="state", device=None):
+        """A policy of ``agent``'s shape holding a copy of its parameters (``device``: default the agent's own)."""
+        d, a, h = cls._shape_of(agent)
+        policy = cls(d, a, h, observation, device if device is not None else agent.critic[0].weight.device)
+        return policy.load_(agent)
+
+    def load_(self, agent):
+        """One flat in-place copy of ``agent``'s parameters into ``params`` (the tensor the kernel reads does not move)."""
+        if self._shape_of(agent) != (self.obs_dim, self.num_actions, self.hidden):
+            raise ValueError(f"agent has (obs_dim, num_actions, hidden) = {self._shape_of(agent)}, this policy "
+                             f"{(self.obs_dim, self.num_actions, self.hidden)}")
+        with torch.no_grad():
+            self.params.copy_(self._flat(agent))
+        return self
+
+    def module(self):
+        """A new ``MlpAgent`` on ``params``' device with these parameters (a copy)."""
+        agent = MlpAgent(self.obs_dim, self.num_actions, self.hidden).to(self.params.device)
+        at = 0
+        with torch.no_grad():
+            for net in (agent.critic, agent.actor):
+                for p in net.parameters():
+                    p.copy_(self.params[at:at + p.numel()].view_as(p))
+                    at += p.numel()
+        return agent
+
+
+# what ``rollout_policy`` fills, the names of scripts/cartpole_train_torch.py:179-192: (T, N, D), (T, N) x 5, (N, D), (N), (N)
+Rollout = collections.namedtuple("Rollout", "obs actions logprobs values rewards dones next_obs next_value next_done")
+
+
+def gae(rollout, gamma, gae_lambda):
+    """``(advantages, returns)`` of a ``Rollout`` -- scripts/cartpole_train_torch.py:245-256 as one launch (``mrl_gae``), on
+    torch's current stream of the rollout's device."""
+    r = rollout
+    num_steps, num_worlds = r.rewards.shape
+    for t in (r.rewards, r.values, r.dones, r.next_value, r.next_done):
+        if not t.is_cuda or t.device != r.rewards.device or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("rollout tensors must be contiguous float32 tensors on one GPU")
+    if r.values.shape != r.rewards.shape or r.dones.shape != r.rewards.shape or r.next_value.numel() != num_worlds or \
+            r.next_done.numel() != num_worlds:
+        raise ValueError("rollout tensors must be (T, N), next_value and next_done (N)")
+    advantages, returns = torch.empty_like(r.rewards), torch.empty_like(r.rewards)
+    gpu = r.rewards.device.index
+    _lib.check(_lib.lib().mrl_gae(r.rewards.data_ptr(), r.values.data_ptr(), r.dones.data_ptr(), r.next_value.data_ptr(),
+                                  r.next_done.data_ptr(), num_steps, num_worlds, float(gamma), float(gae_lambda),
+                                  advantages.data_ptr(), returns.data_ptr(), gpu, _stream_ptr(gpu)))
+    return advantages, returns
 
 
 def totals_of(totals):
@@ -267,6 +388,39 @@ class _Simulator:
         stream = _stream_ptr(self.gpu_id)
         _lib.check(self._L.mrl_rollout_random(self._handle, int(num_steps), int(seed) & (2 ** 64 - 1), int(first_step),
                                               stream))
+
+    def rollout_policy(self, policy, num_steps, seed=0, first_step=0, out=None, greedy=False):
+        """``num_steps`` steps under ``policy`` (an ``MlpPolicy`` on this GPU) with the host out of the loop: observe, both
+        nets, draw, log-prob, value, step and record, two launches per step (``mrl_rollout_policy``; Cartpole and Acrobot).
+        Returns a ``Rollout`` of tensors on this GPU -- new ones, or ``out`` (an earlier call's result) filled again.  The
+        draw of (step index ``first_step + k``, world) uses ``sample_u``; ``greedy`` takes the first arg-max instead."""
+        if not isinstance(policy, MlpPolicy):
+            raise ValueError("policy must be an MlpPolicy")
+        p = policy.params
+        if not p.is_cuda or p.device.index != self.gpu_id or p.dtype != torch.float32 or not p.is_contiguous():
+            raise ValueError(f"policy.params must be a contiguous float32 tensor on cuda:{self.gpu_id} (the simulator's device)")
+        if p.numel() != int(self._L.mrl_mlp_policy_num_params(policy.obs_dim, policy.hidden, policy.num_actions)):
+            raise ValueError("policy.params does not have mrl_mlp_policy_num_params elements")
+        t, n, d = int(num_steps), self.num_worlds, policy.obs_dim
+        if t < 0:
+            raise ValueError("num_steps must not be negative")
+        f32, device = torch.float32, torch.device("cuda", self.gpu_id)
+        shapes = Rollout((t, n, d), (t, n), (t, n), (t, n), (t, n), (t, n), (n, d), (n,), (n,))
+        if out is None:
+            out = Rollout(*[torch.empty(shape, dtype=torch.int32 if name == "actions" else f32, device=device)
+                            for name, shape in zip(Rollout._fields, shapes)])
+        else:
+            for name, tensor, shape in zip(Rollout._fields, out, shapes):
+                if (not isinstance(tensor, torch.Tensor) or tensor.device != device or tuple(tensor.shape) != shape or
+                        tensor.dtype != (torch.int32 if name == "actions" else f32) or not tensor.is_contiguous()):
+                    raise ValueError(f"out.{name} must be a contiguous {shape} tensor on cuda:{self.gpu_id}")
+        desc = _lib.MlpPolicyDesc(p.data_ptr(), d, policy.hidden, policy.num_actions,
+                                  _lib.OBS_ACROBOT_GYM if policy.observation == "gym" else _lib.OBS_RAW,
+                                  _lib.POLICY_GREEDY if greedy else 0)
+        buffers = _lib.RolloutBuffers(*[tensor.data_ptr() for tensor in out], t)
+        _lib.check(self._L.mrl_rollout_policy(self._handle, ctypes.byref(desc), ctypes.byref(buffers),
+                                              int(seed) & (2 ** 64 - 1), int(first_step) & 0xFFFFFFFF, _stream_ptr(self.gpu_id)))
+        return out
 
     def reset_worlds(self, mask=None):
         """Restart the worlds whose ``mask`` entry is nonzero (``None``: every world) as fresh episodes, enqueued on torch's
