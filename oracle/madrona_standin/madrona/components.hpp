@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE ONLY -- minimal stand-in for the part of the Madrona engine the reference's
-// Hanabi, Cartpole and balance-beam sim.cpp files use.  Our own code: it holds no game logic.
+// Hanabi, Cartpole, balance-beam, Overcooked and Simplecooked sim.cpp files use.  Our own code: it holds no game logic.
 // Entities, the WorldID column and the Archetype tag.
 #pragma once
 

@@ -82,6 +82,16 @@ public:
         std::memset(mem, fill_, bytes);
         if (construct_) new (mem + kGuard) T;
         entities_[entity].push_back(Slot{type_id<T>(), (uint32_t)sizeof(T), mem});
+        if (by_type_.size() <= type_id<T>()) by_type_.resize(type_id<T>() + 1);
+        by_type_[type_id<T>()].push_back(entity);
+    }
+
+    // The entities that carry a T, in ascending creation order (what a node iterates instead of all entities).
+    template <typename T>
+    const std::vector<uint32_t> &entities_with()
+    {
+        if (by_type_.size() <= type_id<T>()) by_type_.resize(type_id<T>() + 1);
+        return by_type_[type_id<T>()];
     }
 
     template <typename T>
@@ -117,6 +127,7 @@ public:
         for (uint32_t e = 0; e < entities_.size(); e++)
             for (const Slot &s : entities_[e]) {
                 const size_t bytes = (2 * kGuard + s.size + 63) / 64 * 64;
+                if (clean(s.mem, kGuard) && clean(s.mem + kGuard + s.size, bytes - kGuard - s.size)) continue;
                 for (size_t b = 0; b < bytes; b++) {
                     if (b >= kGuard && b < kGuard + s.size) continue;
                     if (s.mem[b] == fill_) continue;
@@ -130,9 +141,16 @@ public:
     void *data = nullptr;  // the world's Sim object (CustomContext::data)
 
 private:
+    // whether all `bytes` bytes at p still hold the fill byte
+    bool clean(const unsigned char *p, size_t bytes) const
+    {
+        return bytes == 0 || (p[0] == fill_ && std::memcmp(p, p + 1, bytes - 1) == 0);
+    }
+
     uint8_t fill_;
     bool construct_;
     std::vector<std::vector<Slot>> entities_;
+    std::vector<std::vector<uint32_t>> by_type_;
     std::vector<void *> raw_;
 };
 

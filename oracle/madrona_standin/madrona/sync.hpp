@@ -1,4 +1,5 @@
-// TEST INFRASTRUCTURE ONLY -- Madrona stand-in: the episode counter's atomic.
+// TEST INFRASTRUCTURE ONLY -- Madrona stand-in: the episode counter's atomic (AtomicU32) and the generic
+// Atomic<T> the kitchen worlds keep in their components (rewards, flags, per-cell counters).
 #pragma once
 
 #include <atomic>
@@ -15,6 +16,21 @@ public:
 
 private:
     std::atomic<uint32_t> v_;
+};
+
+template <typename T>
+class Atomic {
+public:
+    Atomic() = default;  // as for raw column memory: the value is whatever the storage holds
+    Atomic(T v) : v_(v) {}
+    T load_relaxed() const { return __atomic_load_n(&v_, __ATOMIC_RELAXED); }
+    T load_acquire() const { return __atomic_load_n(&v_, __ATOMIC_ACQUIRE); }
+    void store_relaxed(T v) { __atomic_store_n(&v_, v, __ATOMIC_RELAXED); }
+    void store_release(T v) { __atomic_store_n(&v_, v, __ATOMIC_RELEASE); }
+    T fetch_add_relaxed(T d) { return __atomic_fetch_add(&v_, d, __ATOMIC_RELAXED); }
+
+private:
+    T v_;
 };
 
 }  // namespace madrona

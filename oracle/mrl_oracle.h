@@ -14,8 +14,12 @@
  *   Hanabi    : /root/reference/src/hanabi_env/sim.hpp:13-140, sim.cpp:45-897, rng.hpp:5-40
  *
  * Pinning (see DESIGN.md "Oracle"):
- *   Overcooked: pinned against the reference's own numpy implementation
- *               (envs/overcooked_reimplement.py) through tests/golden/overcooked_*.npz.
+ *   Overcooked, Simplecooked: pinned against the reference's own numpy implementations
+ *               (envs/overcooked_reimplement.py, envs/overcooked2_reimplement.py) through
+ *               tests/golden/{overcooked,simplecooked}_*.npz, and, like the next three, bit-exact
+ *               against the reference's own sim.cpp (tests/test_ref_overcooked.py,
+ *               tests/test_ref_simplecooked.py; one-player Simplecooked by the numpy twin only,
+ *               the C++ is undefined there).
  *   Cartpole, Hanabi, balance beam: bit-exact against the reference's own
  *               sim.cpp compiled unchanged against a Madrona stand-in
  *               (oracle/Makefile.ref -> oracle/_ref, tests/test_ref_*.py) and

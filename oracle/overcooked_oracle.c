@@ -14,7 +14,8 @@
  * Systems run per world in the dependency order of the graph, players in
  * ascending id (what one worker of the reference's CPU executor does).
  *
- * Pinned against envs/overcooked_reimplement.py via tests/golden/overcooked_*.npz.
+ * Pinned against envs/overcooked_reimplement.py via tests/golden/overcooked_*.npz, and bit for bit against the
+ * reference's own sim.cpp compiled unchanged (oracle/ref.py: RefOvercooked, tests/test_ref_overcooked.py).
  */
 #include "mrl_oracle.h"
 

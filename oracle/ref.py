@@ -1,7 +1,13 @@
-"""TEST INFRASTRUCTURE ONLY -- ctypes front end of oracle/_ref/libref_{hanabi,cartpole,balance}.so: the
-reference's own Hanabi, Cartpole and balance-beam sim.cpp, compiled unchanged against the Madrona stand-in
-(oracle/madrona_standin, oracle/ref_driver_*.cpp, oracle/Makefile.ref).  The classes mirror the oracle's
-(oracle/oracle.py) but copy their outputs out on every read.
+"""TEST INFRASTRUCTURE ONLY -- ctypes front end of oracle/_ref/libref_{hanabi,cartpole,balance,overcooked,
+simplecooked}.so: the reference's own sim.cpp of five games (Hanabi, Cartpole, the balance beam, Overcooked and
+Simplecooked), compiled unchanged against the Madrona stand-in (oracle/madrona_standin, oracle/ref_driver_*.cpp,
+oracle/Makefile.ref).  The classes mirror the oracle's (oracle/oracle.py) but copy their outputs out on every read.
+
+The kitchens take two more options, for what Madrona leaves open: ``graph_order`` (0: the task graph's nodes in
+insertion order, 1: a second topological order) and ``reverse_entities`` (a node visits its entities in descending
+creation order); see madrona_standin/madrona/taskgraph_builder.hpp.  A configuration the C++ cannot hold raises
+ValueError: Overcooked above 255 cells or 64 players, Simplecooked above 100 cells or with any player count but two
+(with one player its dish-pickup shaping reads a second agent that was never created).
 
 ``build(reference_dir)`` runs the recipe; ``require()`` is what a test calls first: it skips (with the
 reason) when oracle/_ref/BUILD_INFO is missing, i.e. the reference tree was never there to build from, and
@@ -18,10 +24,14 @@ from oracle.oracle import HANABI_MOVES, HANABI_OBS, HANABI_STATE, HanabiConfig
 _HERE = os.path.dirname(os.path.abspath(__file__))
 REF_DIR = os.path.join(_HERE, "_ref")
 BUILD_INFO = os.path.join(REF_DIR, "BUILD_INFO")
-GAMES = ("hanabi", "cartpole", "balance")
+GAMES = ("hanabi", "cartpole", "balance", "overcooked", "simplecooked")
+SOURCE_DIRS = ("hanabi_env", "cartpole_env", "balance_beam_env", "overcooked_env", "overcooked2_env")
 FILLS = (0x00, 0xA5)
 # guard-hit rows (world, entity, type code, offset, value); Hanabi type codes as ref_hanabi_guards numbers them
 GUARD_OBSERVATION, GUARD_STATE = 0, 1
+# ... and the kitchens' (ref_driver_kitchen.hpp)
+GUARD_LOCATION_OBSERVATION, GUARD_LOCATION_DATA, GUARD_PLAYER_STATE, GUARD_WORLD_STATE = 0, 1, 2, 3
+NUM_RECIPES = 16
 _libs = {}
 
 
@@ -33,11 +43,11 @@ def default_reference_dir():
 def reference_present(reference_dir=None):
     d = reference_dir or default_reference_dir()
     return all(os.path.isfile(os.path.join(d, "src", sub, "sim.cpp"))
-               for sub in ("hanabi_env", "cartpole_env", "balance_beam_env"))
+               for sub in SOURCE_DIRS)
 
 
 def build(reference_dir=None):
-    """Compile the three reference libraries and BUILD_INFO with oracle/Makefile.ref (g++)."""
+    """Compile the five reference libraries and BUILD_INFO with oracle/Makefile.ref (g++)."""
     d = os.path.abspath(reference_dir or default_reference_dir())
     proc = subprocess.run(["make", "-C", _HERE, "-f", "Makefile.ref", "REF=" + d], capture_output=True, text=True)
     if proc.returncode != 0:
@@ -46,7 +56,7 @@ def build(reference_dir=None):
 
 
 def require():
-    """Skip when _ref was never built (no BUILD_INFO); otherwise load all three libraries or fail."""
+    """Skip when _ref was never built (no BUILD_INFO); otherwise load all five libraries or fail."""
     if not os.path.isfile(BUILD_INFO):
         import pytest
         pytest.skip("oracle/_ref not built (no oracle/_ref/BUILD_INFO): build() found no reference tree to compile")
@@ -71,9 +81,14 @@ def lib(game):
         create.argtypes = [u32, u32, u32, ctypes.c_int]
         getattr(L, pre + "read").argtypes = [vp, f32p, f32p, i32p]
         L.ref_cartpole_set_state.argtypes = [vp, f32p]
-    else:
+    elif game == "balance":
         create.argtypes = [u32, u32, u32, ctypes.c_int]
         getattr(L, pre + "read").argtypes = [vp, i32p, i32p, i32p, f32p, i32p]
+    else:
+        create.argtypes = [ctypes.POINTER(ctypes.c_int64), u8p, u8p, u8p, u8p, u8p, u32, u32] + [ctypes.c_int] * 3
+        getattr(L, pre + "read").argtypes = [vp, u8p, i32p, i32p, u8p, u8p, i32p] + [i32p] * (game == "simplecooked")
+        getattr(L, pre + "node_order").restype = u32
+        getattr(L, pre + "node_order").argtypes = [vp, ctypes.c_int, ctypes.POINTER(u32), u32]
     getattr(L, pre + "destroy").argtypes = [vp]
     getattr(L, pre + "step").argtypes = [vp, i32p]
     getattr(L, pre + "episodes").restype = u32
@@ -194,3 +209,74 @@ class RefBalance(_Ref):
         self.L.ref_balance_read(self.h, _p(self.obs, ctypes.c_int32), _p(self.loc, ctypes.c_int32),
                                 _p(self.time, ctypes.c_int32), _p(self.reward, ctypes.c_float),
                                 _p(self.done, ctypes.c_int32))
+
+
+class _RefKitchen(_Ref):
+    """N worlds of a kitchen sim.cpp.  ``params``: the dict OvercookedOracle / SimplecookedOracle take.  The scalars go in
+    as int64 and the arrays as bytes (value & 255), since that is what the reference's Config holds."""
+    row_extra = None
+
+    def __init__(self, params, num_worlds, fill=0x00, construct=False, graph_order=0, reverse_entities=False):
+        self.L = lib(self.game)
+        self.params = params
+        self.N = N = int(num_worlds)
+        self.P, self.H, self.W = P, H, W = int(params["num_players"]), int(params["height"]), int(params["width"])
+        self.C, self.F = C, F = H * W, 5 * P + self.row_extra
+        self._act_shape = (P, N)
+        scalars = np.array([int(params[k]) for k in ("height", "width", "num_players", "placement_in_pot_rew",
+                                                      "dish_pickup_rew", "soup_pickup_rew", "horizon")], np.int64)
+
+        def as_bytes(key, count):
+            v = np.zeros(max(count, 1), np.uint8)
+            given = np.asarray(params[key], np.int64)[:count]
+            v[:len(given)] = given & 255
+            return v
+
+        arrays = [as_bytes("terrain", max(C, 0)), as_bytes("start_player_x", max(P, 0)), as_bytes("start_player_y", max(P, 0)),
+                  as_bytes("recipe_values", NUM_RECIPES), as_bytes("recipe_times", NUM_RECIPES)]
+        create = getattr(self.L, "ref_%s_create" % self.game)
+        h = create(_p(scalars, ctypes.c_int64), *[_p(a, ctypes.c_uint8) for a in arrays], N, fill, int(construct),
+                   int(graph_order), int(reverse_entities))
+        self._fin(h)
+        self.obs = np.zeros((N, P, C, F), np.uint8)
+        self.reward = np.zeros((P, N), np.int32)
+        self.done = np.zeros((N,), np.int32)
+        self.players = np.zeros((N, P, 6), np.uint8)
+        self.objects = np.zeros((N, C, 4), np.uint8)
+        self.timestep = np.zeros((N,), np.int32)
+        self._read()
+
+    def _out(self):
+        return [_p(self.obs, ctypes.c_uint8), _p(self.reward, ctypes.c_int32), _p(self.done, ctypes.c_int32),
+                _p(self.players, ctypes.c_uint8), _p(self.objects, ctypes.c_uint8), _p(self.timestep, ctypes.c_int32)]
+
+    def _read(self):
+        getattr(self.L, "ref_%s_read" % self.game)(self.h, *self._out())
+
+    def node_order(self, graph_order):
+        """The task graph's nodes, numbered as setupTasks adds them, in the order the stand-in runs them for graph_order."""
+        out = np.zeros(64, np.uint32)
+        n = int(getattr(self.L, "ref_%s_node_order" % self.game)(self.h, int(graph_order), _p(out, ctypes.c_uint32), 64))
+        return out[:n].tolist()
+
+    def dump(self):
+        """The internal state in the layout of the oracle's dump(): players (N, P, 6), objects (N, C, 4), timestep (N,)."""
+        return self.players.copy(), self.objects.copy(), self.timestep.copy()
+
+
+class RefOvercooked(_RefKitchen):
+    game = "overcooked"
+    row_extra = 16
+
+
+class RefSimplecooked(_RefKitchen):
+    game = "simplecooked"
+    row_extra = 10
+
+    def _out(self):
+        if not hasattr(self, "dishes_out"):
+            self.dishes_out = np.zeros((self.N,), np.int32)
+        return super()._out() + [_p(self.dishes_out, ctypes.c_int32)]
+
+    def dump(self):
+        return super().dump() + (self.dishes_out.copy(),)

@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE ONLY -- shared part of oracle/ref_driver_{hanabi,cartpole,balance}.cpp: N worlds of a
+// TEST INFRASTRUCTURE ONLY -- shared part of oracle/ref_driver_{hanabi,cartpole,balance,overcooked,simplecooked}.cpp: N worlds of a
 // reference sim.cpp built against the Madrona stand-in (oracle/madrona_standin), stepped through the task
 // graph its setupTasks builds.  No game logic here.
 //
@@ -46,7 +46,12 @@ struct Worlds {
         }
     }
 
-    void step() { graph.run(engines); }
+    // graph_order / reverse_entities: see madrona/taskgraph_builder.hpp; the defaults are insertion order and
+    // ascending entities
+    int graph_order = 0;
+    bool reverse_entities = false;
+
+    void step() { graph.run(engines, graph_order, reverse_entities); }
 
     ~Worlds()
     {

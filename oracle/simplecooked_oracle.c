@@ -21,7 +21,9 @@
  * player, sim.cpp:190-194) this follows its numpy twin (envs/overcooked2_reimplement.py:243-245:
  * never useful unless there are exactly two players).
  *
- * Pinned against envs/overcooked2_reimplement.py via tests/golden/simplecooked_*.npz.
+ * Pinned against envs/overcooked2_reimplement.py via tests/golden/simplecooked_*.npz, and with two players bit for bit
+ * against the reference's own sim.cpp compiled unchanged (oracle/ref.py: RefSimplecooked,
+ * tests/test_ref_simplecooked.py); with one player the C++ is undefined and the numpy twin alone decides.
  */
 #include "mrl_oracle.h"
 

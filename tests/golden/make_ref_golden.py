@@ -1,4 +1,5 @@
-"""Writes tests/golden/hanabi_ref_{full,small,very_small}.npz and cartpole_ref.npz: action streams and what the reference's
+"""Writes tests/golden/hanabi_ref_{full,small,very_small}.npz, cartpole_ref.npz and the kitchens' overcooked_ref_*.npz /
+simplecooked_ref_*.npz: action streams and what the reference's
 OWN sim.cpp computed for them, compiled unchanged against the Madrona stand-in (oracle/_ref, built by build() when the
 reference tree is present; oracle/ref.py).  Data only, packed the way tests/conftest.py:load_golden reads them, so that the
 oracle and the GPU stay pinned to the compiled reference where oracle/_ref is not built.
@@ -7,7 +8,12 @@ Hanabi: moves drawn from the reference's own mask, a third of the worlds preferr
 card moves), a third discarding when it may (the deck runs out), a third uniformly random.  Rows are stored up to the
 configuration's observation / state length (what the reference writes).  Cartpole: random pushes, state as float32.
 
-    python tests/golden/make_ref_golden.py
+Kitchens: the streams of tests/kitchen_ref.py:FIXTURES (half of the worlds follow a goal-directed cook stream where the
+layout has one, the others play at random); per step every viewer's observation rows (their 0/1 pattern packed, the count
+channels as bytes), reward and done, and the internal state after the last step.  overcooked_ref_limits.npz holds three
+streams side by side: recipe times 127 and 128 (the int8_t tick reaches 127 / wraps past it) and recipe values 300.
+
+    python tests/golden/make_ref_golden.py [kitchens]
 """
 import os
 import sys
@@ -17,6 +23,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, REPO)
+sys.path.insert(1, os.path.join(REPO, "tests"))
 
 from madrona_rl_envs_playground_amd import hanabi_spec  # noqa: E402
 from oracle import ref  # noqa: E402
@@ -48,7 +55,22 @@ def packed(name, v):
     return {name + "_bits": np.packbits(v, axis=-1), name + "_len": np.int64(v.shape[-1])}
 
 
+def kitchens():
+    import kitchen_ref as kr
+    for fixture in kr.FIXTURES:
+        make_ref = ref.RefOvercooked if kr.fixture_game(fixture) == "overcooked" else ref.RefSimplecooked
+        arrays, covs = kr.record_fixture(fixture, make_ref)
+        out = os.path.join(HERE, fixture + ".npz")
+        np.savez_compressed(out, **arrays)
+        print(f"{out}: {os.path.getsize(out) / 1024:.0f} KiB")
+        for prefix, cov in covs.items():
+            print(f"    {prefix or 'stream'}: {cov}")
+
+
 def main():
+    kitchens()
+    if sys.argv[1:] == ["kitchens"]:
+        return
     for name, (cfg, n, steps) in CONFIGS.items():
         no, ns = hanabi_spec.observation_size(cfg), hanabi_spec.state_size(cfg)
         r = ref.RefHanabi(cfg, n)

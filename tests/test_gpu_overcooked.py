@@ -33,7 +33,7 @@ def unpack_players(t):
     return np.stack([t[..., 0], t[..., 1], t[..., 4], t[..., 5], t[..., 6], t[..., 7]], axis=-1)
 
 
-@pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(GOLDEN, "overcooked_*.npz"))),
+@pytest.mark.parametrize("path", sorted(f for f in glob.glob(os.path.join(GOLDEN, "overcooked_*.npz")) if "_ref_" not in os.path.basename(f)),
                          ids=lambda p: os.path.basename(p)[11:-4])
 def test_golden_vectors(path, hip_lib):
     """Every world of a small batch replays the fixture's action stream and must
@@ -670,3 +670,91 @@ def test_multi_step_launches_fill_a_ring_of_slots(layout, n, dense, hip_lib):
         ringed.set_observation_ring(torch.zeros((2, own.numel() - 16), dtype=torch.int8, device="cuda"))
     ringed.close()
     twin.close()
+
+
+# ---- against the reference's own sim.cpp, compiled unchanged against the Madrona stand-in (oracle/ref.py): the comparand of
+# every HIP path directly, not through the oracle.  Streams, limits and what a run must have covered: tests/kitchen_ref.py. ----
+
+_FIXED_CRAMPED = "mrl_overcooked_step_fixed<20, 8, 5, 1, 6, false>"
+_WPW8, _WPW4 = {"overcooked.wpw": 8}, {"overcooked.wpw": 4}
+# The specialised kernels step 8 (cramped_room) or 4 worlds per wave, a group size the library picks by itself only for large
+# batches; `overcooked.wpw` asks for it at these small ones, whose last group is then ragged (67 = 8 * 8 + 3, 37 = 9 * 4 + 1).
+# id: (how, worlds, steps, knobs, kernel, steps per step_sequence launch or None)
+_REF_CASES = {
+    "specialised-1": (("layout", "cramped_room", 37, None), 1, 120, _WPW8, _FIXED_CRAMPED, None),
+    "specialised-67": (("layout", "cramped_room", 37, None), 67, 120, _WPW8, _FIXED_CRAMPED, None),
+    "any-player-path": (("layout", "cramped_room", 37, None), 67, 120, {**_WPW8, "overcooked.variant": 1}, "mrl_overcooked_step<false, 0>", None),
+    "generic": (("layout", "cramped_room", 37, None), 67, 120, {**_WPW8, "overcooked.no_fixed": 1}, "mrl_overcooked_step<false, 2>", None),
+    "generic-one-world-per-wave": (("layout", "cramped_room", 37, None), 67, 120, {"overcooked.no_fixed": 1}, "mrl_overcooked_step<false, 2>", None),
+    "searched-patch": (("layout", "counter_circuit", 50, None), 33, 120, {**_WPW4, "overcooked.no_direct": 1}, "mrl_overcooked_step<false, 2>", None),
+    "tomato-4-per-wave": (("layout", "asymmetric_advantages_tomato", 80, None), 37, 200, _WPW4, "mrl_overcooked_step_fixed<45, 4, 9, 2, 14, false>", None),
+    "three-players": (("layout", "multiplayer_schelling", 40, 3), 21, 120, {}, "mrl_overcooked_step_team<false>", None),
+    "waves-share-a-world": (("layout", "many_player_layout", 30, 2), 50, 70, {}, "mrl_overcooked_step_team<false>", None),
+    "8-viewers": (("layout", "many_player_layout", 30, 8), 9, 70, {}, "mrl_overcooked_step_team<false>", None),
+    "40-viewers": (("layout", "many_player_layout", 25, 40), 3, 60, {}, "mrl_overcooked_step_team<false>", None),
+    "one-player": (("layout", "cramped_room", 30, 1), 77, 100, {}, "mrl_overcooked_step<false, 0>", None),
+    "multi-step": (("layout", "cramped_room", 37, None), 67, 120, _WPW8, _FIXED_CRAMPED, 40),
+    "time-127": (("limit", "time", 127), 65, 600, _WPW8, _FIXED_CRAMPED, None),
+    "time-128": (("limit", "time", 128), 65, 600, _WPW8, _FIXED_CRAMPED, None),
+    "time-128-generic": (("limit", "time", 128), 65, 600, {**_WPW8, "overcooked.no_fixed": 1}, "mrl_overcooked_step<false, 2>", None),
+    "time-255": (("limit", "time", 255), 65, 600, _WPW8, _FIXED_CRAMPED, None),
+    "value-300": (("limit", "value", 300), 65, 200, _WPW8, _FIXED_CRAMPED, None),
+    "value-300-generic": (("limit", "value", 300), 65, 200, {**_WPW8, "overcooked.no_fixed": 1}, "mrl_overcooked_step<false, 2>", None),
+    "rewards-300": (("limit", "rewards", 293), 65, 200, _WPW8, _FIXED_CRAMPED, None),
+    "horizon-0": (("limit", "horizon", 0), 65, 200, _WPW8, _FIXED_CRAMPED, None),
+    "horizon-1": (("limit", "horizon", 1), 65, 200, _WPW8, _FIXED_CRAMPED, None),
+    "horizon-41": (("limit", "horizon", 41), 65, 200, _WPW8, _FIXED_CRAMPED, None),
+}
+
+
+@pytest.mark.parametrize("case", sorted(_REF_CASES))
+def test_step_vs_compiled_reference(case, hip_lib):
+    """Every Overcooked kernel family next to the compiled C++ itself: obs, reward and done after every step, players,
+    objects and timestep every 10 steps.  The kernel each case is there for is asserted by name; that the run ended an episode,
+    used a pot and -- in the type-limit cases -- reached the limit is read off the reference's own state."""
+    import kitchen_ref as kr
+    from oracle import ref
+    from madrona_rl_envs_playground_amd._lib import debug_knobs
+    ref.require()
+    how, n, steps, knobs, kernel, chunk = _REF_CASES[case]
+    params = kr.stream_params("overcooked", how)
+    with debug_knobs(knobs):
+        sim = make_sim(params, n)
+    assert sim.kernel_name == kernel, f"{case}: runs {sim.kernel_name} (launch shape {sim.launch_shape})"
+    assert knobs.get("overcooked.wpw", sim.launch_shape[3]) == sim.launch_shape[3]
+    acts = kr.case_actions("overcooked", how, n, steps, 0.45, zlib.crc32(case.encode()))
+    cov = kr.sim_against_reference("overcooked", sim, ref.RefOvercooked(params, n), acts, chunk=chunk, tag=case)
+    print(f"{case}: {sim.kernel_name}, launch shape {sim.launch_shape}; {cov}")
+    if how[0] == "limit":
+        kr.assert_limit_covered(how[1], how[2], params, cov)
+    else:
+        assert cov.episodes >= 1 and cov.pot_steps >= 1, cov
+    sim.close()
+
+
+@pytest.mark.parametrize("fixture,knobs,kernel", [
+    ("overcooked_ref_cramped_room", _WPW8, _FIXED_CRAMPED),
+    ("overcooked_ref_cramped_room", {}, "mrl_overcooked_step<false, 2>"),
+    ("overcooked_ref_tomato_mix", _WPW4, "mrl_overcooked_step_fixed<45, 4, 9, 2, 14, false>"),
+    ("overcooked_ref_many_player_8", {}, "mrl_overcooked_step_team<false>"),
+    ("overcooked_ref_limits", _WPW8, _FIXED_CRAMPED),
+    ("overcooked_ref_limits", {**_WPW8, "overcooked.no_fixed": 1}, "mrl_overcooked_step<false, 2>"),
+])
+def test_step_reproduces_compiled_reference_fixture(fixture, knobs, kernel, hip_lib):
+    """tests/golden/overcooked_ref_*.npz (the reference's own sim.cpp, tests/golden/make_ref_golden.py) on the GPU: needs no
+    reference build."""
+    import kitchen_ref as kr
+    from madrona_rl_envs_playground_amd._lib import debug_knobs
+    for prefix, params, s in kr.load_fixture(fixture):
+        T, P, n = s["actions"].shape
+        with debug_knobs(knobs):
+            sim = make_sim(params, n)
+        assert sim.kernel_name == kernel, f"{fixture}: runs {sim.kernel_name} (launch shape {sim.launch_shape})"
+        kr.assert_sim_equals("overcooked", sim, {"obs": s["first_obs"]}, f"{fixture} {prefix}before the first step", False, outputs=False)
+        for t in range(T):
+            sim.step_with_actions(torch.from_numpy(s["actions"][t]).cuda().view(P, n, 1))
+            want = {"obs": s["obs"][t], "reward": s["reward"][t], "done": s["done"][t]}
+            if t == T - 1:
+                want.update({k: s[k] for k in ("players", "objects", "timestep")})
+            kr.assert_sim_equals("overcooked", sim, want, f"{fixture} {prefix}step {t}", t == T - 1)
+        sim.close()

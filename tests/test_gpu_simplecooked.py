@@ -27,7 +27,7 @@ def unpack_players(t):
     return np.stack([t[..., 0], t[..., 1], t[..., 4], t[..., 5], t[..., 6], t[..., 7]], axis=-1)
 
 
-@pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(GOLDEN, "simplecooked_*.npz"))),
+@pytest.mark.parametrize("path", sorted(f for f in glob.glob(os.path.join(GOLDEN, "simplecooked_*.npz")) if "_ref_" not in os.path.basename(f)),
                          ids=lambda p: os.path.basename(p)[13:-4])
 def test_golden_vectors(path, hip_lib):
     """Reference numpy observations / rewards / dones; the one byte per tomato-source cell where the
@@ -410,3 +410,83 @@ def test_rollout_fills_a_ring_of_slots(hip_lib):
     assert torch.equal(own, before)
     ringed.close()
     twin.close()
+
+
+# ---- against the reference's own overcooked2_env sim.cpp, compiled unchanged against the Madrona stand-in (oracle/ref.py): the
+# comparand directly, not through the oracle.  Two players only: with one the C++ is undefined (tests/test_ref_simplecooked.py),
+# so the one-player kernels stay with the oracle cases above.  Streams, limits and coverage: tests/kitchen_ref.py. ----
+
+_FIXED_SIMPLE = "mrl_simplecooked_step_fixed<20, 8, 5, 1, 6, 0>"
+_GENERIC = "mrl_simplecooked_step<false, 2>"
+_WPW8, _WPW4 = {"overcooked.wpw": 8}, {"overcooked.wpw": 4}
+# `overcooked.wpw`: the group size of the specialised kernels, which the library picks by itself only for large batches
+# id: (how, worlds, steps, P(interact), knobs, kernel)
+_REF_CASES = {
+    "simple-1": (("layout", "simple", 37, None), 1, 120, 0.45, _WPW8, _FIXED_SIMPLE),
+    "simple-67": (("layout", "simple", 37, None), 67, 120, 0.45, _WPW8, _FIXED_SIMPLE),
+    "simple-1-generic": (("layout", "simple", 37, None), 1, 120, 0.45, {**_WPW8, "overcooked.no_fixed": 1}, _GENERIC),
+    "simple-67-generic": (("layout", "simple", 37, None), 67, 120, 0.45, {**_WPW8, "overcooked.no_fixed": 1}, _GENERIC),
+    "unident_s": (("layout", "unident_s", 60, None), 33, 150, 0.45, _WPW4, "mrl_simplecooked_step_fixed<45, 4, 9, 2, 14, 0>"),
+    "random3": (("layout", "random3", 50, None), 33, 120, 0.6, _WPW4, "mrl_simplecooked_step_fixed<40, 4, 8, 2, 18, 0>"),
+    "simple_tomato": (("layout", "simple_tomato", 80, None), 37, 200, 0.45, {}, _GENERIC),
+    "time-127": (("limit", "time", 127), 65, 600, 0.45, _WPW8, _FIXED_SIMPLE),
+    "time-128": (("limit", "time", 128), 65, 600, 0.45, _WPW8, _FIXED_SIMPLE),
+    "time-128-generic": (("limit", "time", 128), 65, 600, 0.45, {**_WPW8, "overcooked.no_fixed": 1}, _GENERIC),
+    "time-255": (("limit", "time", 255), 65, 600, 0.45, _WPW8, _FIXED_SIMPLE),
+    "value-300": (("limit", "value", 300), 65, 200, 0.45, _WPW8, _FIXED_SIMPLE),
+    "value-300-generic": (("limit", "value", 300), 65, 200, 0.45, {**_WPW8, "overcooked.no_fixed": 1}, _GENERIC),
+    "rewards-300": (("limit", "rewards", 287), 65, 200, 0.45, _WPW8, _FIXED_SIMPLE),
+    "horizon-0": (("limit", "horizon", 0), 65, 200, 0.45, _WPW8, _FIXED_SIMPLE),
+    "horizon-1": (("limit", "horizon", 1), 65, 200, 0.45, _WPW8, _FIXED_SIMPLE),
+    "horizon-41": (("limit", "horizon", 41), 65, 200, 0.45, _WPW8, _FIXED_SIMPLE),
+}
+
+
+@pytest.mark.parametrize("case", sorted(_REF_CASES))
+def test_step_vs_compiled_reference(case, hip_lib):
+    """The specialised and the generic Simplecooked kernels next to the compiled C++ itself: obs, reward and done after every
+    step, players, objects, timestep and num_dishes_out every 10 steps.  The kernel is asserted by name; that the run ended an
+    episode, used a pot and -- in the type-limit cases -- reached the limit is read off the reference's own state."""
+    import kitchen_ref as kr
+    from oracle import ref
+    from madrona_rl_envs_playground_amd._lib import debug_knobs
+    ref.require()
+    how, n, steps, p_interact, knobs, kernel = _REF_CASES[case]
+    params = kr.stream_params("simplecooked", how)
+    with debug_knobs(knobs):
+        sim = make_sim(params, n)
+    assert sim.kernel_name == kernel, f"{case}: runs {sim.kernel_name} (launch shape {sim.launch_shape})"
+    assert knobs.get("overcooked.wpw", sim.launch_shape[3]) == sim.launch_shape[3]
+    acts = kr.case_actions("simplecooked", how, n, steps, p_interact, zlib.crc32(case.encode()))
+    cov = kr.sim_against_reference("simplecooked", sim, ref.RefSimplecooked(params, n), acts, tag=case)
+    print(f"{case}: {sim.kernel_name}, launch shape {sim.launch_shape}; {cov}")
+    if how[0] == "limit":
+        kr.assert_limit_covered(how[1], how[2], params, cov)
+    else:
+        assert cov.episodes >= 1 and cov.pot_steps >= 1, cov
+    sim.close()
+
+
+@pytest.mark.parametrize("fixture,knobs,kernel", [
+    ("simplecooked_ref_simple", _WPW8, _FIXED_SIMPLE),
+    ("simplecooked_ref_simple", {}, _GENERIC),
+    ("simplecooked_ref_simple_tomato", {}, _GENERIC),
+])
+def test_step_reproduces_compiled_reference_fixture(fixture, knobs, kernel, hip_lib):
+    """tests/golden/simplecooked_ref_*.npz (the reference's own sim.cpp, tests/golden/make_ref_golden.py) on the GPU: needs no
+    reference build."""
+    import kitchen_ref as kr
+    from madrona_rl_envs_playground_amd._lib import debug_knobs
+    for prefix, params, s in kr.load_fixture(fixture):
+        T, P, n = s["actions"].shape
+        with debug_knobs(knobs):
+            sim = make_sim(params, n)
+        assert sim.kernel_name == kernel, f"{fixture}: runs {sim.kernel_name} (launch shape {sim.launch_shape})"
+        kr.assert_sim_equals("simplecooked", sim, {"obs": s["first_obs"]}, f"{fixture} {prefix}before the first step", False, outputs=False)
+        for t in range(T):
+            sim.step_with_actions(torch.from_numpy(s["actions"][t]).cuda().view(P, n, 1))
+            want = {"obs": s["obs"][t], "reward": s["reward"][t], "done": s["done"][t]}
+            if t == T - 1:
+                want.update({k: s[k] for k in ("players", "objects", "timestep", "dishes_out")})
+            kr.assert_sim_equals("simplecooked", sim, want, f"{fixture} {prefix}step {t}", t == T - 1)
+        sim.close()

@@ -10,7 +10,7 @@ import pytest
 
 from conftest import GOLDEN
 
-FIXTURES = sorted(glob.glob(os.path.join(GOLDEN, "overcooked_*.npz")))
+FIXTURES = sorted(f for f in glob.glob(os.path.join(GOLDEN, "overcooked_*.npz")) if "_ref_" not in os.path.basename(f))
 
 
 def test_fixtures_present():
