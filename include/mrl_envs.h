@@ -596,6 +596,61 @@ int mrl_gae(const float *rewards, const float *values, const float *dones, const
             uint32_t num_steps, uint32_t num_worlds, float gamma, float lambda, float *advantages, float *returns, int gpu_id,
             void *hip_stream);
 
+/* The update phase of PPO on the device: scripts/cartpole_train_torch.py:275-315 -- gather, both forward passes, the clipped
+ * losses, backward, clip_grad_norm_ and Adam.step() -- for the same actor-critic, on the flat parameter array the rollout
+ * kernel reads.  That array is the only copy of the weights; it is updated in place.  No reference counterpart as a call.
+ *   One call is K = num_minibatches steps in row order: row k gathers the B = minibatch_size samples indices[k, :] of the
+ *     batch (the script's b_* arrays, :259-264, S = T * N samples) and takes one Adam step.  A trainer passes the E * M rows of
+ *     its shuffles (:269-273); one that wants target_kl (:317-319) passes one epoch's rows per call and reads the stats.
+ *   Per sample, in float32, with c = clip_coef: logp = log_softmax(actor(x)); newlogprob = logp[a]; ratio = exp(newlogprob -
+ *     old); A = (adv - mean) / (std + 1e-8) over the row with MRL_PPO_NORM_ADV (torch's unbiased std), else adv; pg = max(-A
+ *     ratio, -A clamp(ratio, 1 - c, 1 + c)); with MRL_PPO_CLIP_VLOSS v_loss = 0.5 max((v - R)^2, (v_old + clamp(v - v_old, -c, c)
+ *     - R)^2), else 0.5 (v - R)^2; loss = mean(pg) - ent_coef mean(H) + vf_coef mean(v_loss).  The gradient is torch
+ *     autograd's for those lines (a tie of the two arguments of a max halves the gradient between them, as torch.max does).
+ *   Clipping: total = sqrt(sum g^2); g *= min(1, max_grad_norm / (total + 1e-6)); none for max_grad_norm <= 0.
+ *   Adam (torch.optim.Adam, single tensor, no amsgrad, no weight decay), t = opt->step + 1 + k: m = beta1 m + (1 - beta1) g;
+ *     v = beta2 v + (1 - beta2) g^2; p -= (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps); the two scalars are
+ *     formed in double on the host, as torch forms them in Python floats.  The caller adds K to its step count afterwards.
+ *   stats (K, 8), optional: 0 pg_loss, 1 v_loss (the 0.5 mean, as the script logs it), 2 entropy, 3 old_approx_kl, 4 approx_kl,
+ *     5 clipfrac, 6 total_norm before clipping, 7 loss.  grads (K, P), optional, P = mrl_mlp_policy_num_params: every row's
+ *     summed, unclipped gradient in parameter order (tests and diagnostics).
+ *   The call only enqueues on hip_stream of device gpu_id: it never synchronises or allocates.  Scratch is the caller's,
+ *     mrl_ppo_workspace_bytes (a pure host function) says how much; it need not be cleared and holds nothing between calls.
+ *     Launches: one for the rows' advantage statistics (MRL_PPO_NORM_ADV only) and three per row (gradient; sum of the
+ *     workgroups' partial vectors and of g^2; clip, Adam and stats).  No float atomics, no wait between workgroups: the
+ *     same inputs give the same bits on every run, and one call of K rows the same bits as K calls of one row.
+ *   Index values (0 <= indices[k, b] < batch->size) are the caller's duty: there is no device-side check to synchronise on.
+ *   shape->params_dev, obs_mode and flags are not read (the parameters are opt->params_dev; obs holds observations).
+ *   MRL_ERR_INVALID: a NULL among shape, opt, batch, indices, cfg, workspace, the optimizer's three arrays and the batch's six;
+ *     hidden != 64; (obs_dim, num_actions) other than (4, 2), (4, 3), (6, 3); minibatch_size < 2 with MRL_PPO_NORM_ADV;
+ *     minibatch_size == 0 or batch->size == 0; workspace_bytes below mrl_ppo_workspace_bytes; obs off a 16-byte (D = 4) or
+ *     8-byte (D = 6) boundary or workspace off a 16-byte one; a capturing stream (the step number travels in kernel
+ *     arguments).  num_minibatches == 0 enqueues nothing.  mrl_ppo_workspace_bytes refuses the same shapes and a NULL out.
+ *     DESIGN.md section 13. */
+enum { MRL_PPO_NORM_ADV = 1, MRL_PPO_CLIP_VLOSS = 2 };
+typedef struct mrl_ppo_config {
+    float clip_coef, ent_coef, vf_coef, max_grad_norm; /* max_grad_norm <= 0: no clipping */
+    float lr, beta1, beta2, eps;                        /* torch.optim.Adam, no amsgrad, no weight decay */
+    uint32_t flags;
+} mrl_ppo_config;
+typedef struct mrl_ppo_batch { /* the script's b_* arrays (:259-264), dense, device */
+    const float *obs;          /* (S, D); 16-byte (D = 4) / 8-byte (D = 6) aligned, as for rollouts */
+    const int32_t *actions;    /* (S) */
+    const float *logprobs, *advantages, *returns, *values; /* (S) */
+    uint32_t size;             /* S = T * N */
+} mrl_ppo_batch;
+typedef struct mrl_ppo_optimizer {
+    float *params_dev;           /* the tensor mrl_mlp_policy.params_dev points at; updated in place */
+    float *exp_avg, *exp_avg_sq; /* (P) each */
+    uint32_t step;               /* Adam steps taken BEFORE this call; row k uses step + 1 + k */
+} mrl_ppo_optimizer;
+int mrl_ppo_workspace_bytes(uint32_t obs_dim, uint32_t hidden, uint32_t num_actions, uint32_t minibatch_size,
+                            uint32_t num_minibatches, uint64_t *out);
+int mrl_ppo_update(const mrl_mlp_policy *shape, const mrl_ppo_optimizer *opt, const mrl_ppo_batch *batch,
+                   const int32_t *indices_dev /* (K, B) */, uint32_t num_minibatches /* K */, uint32_t minibatch_size /* B */,
+                   const mrl_ppo_config *cfg, void *workspace_dev, uint64_t workspace_bytes,
+                   float *stats_dev_or_null /* (K, 8) */, float *grads_dev_or_null /* (K, P) */, int gpu_id, void *hip_stream);
+
 int mrl_tensor(mrl_sim *sim, int slot, mrl_tensor_desc *out);
 int mrl_game(const mrl_sim *sim);
 uint32_t mrl_num_worlds(const mrl_sim *sim);

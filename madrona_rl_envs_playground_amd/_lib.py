@@ -28,6 +28,8 @@ MAX_DIMS = 6
 MAX_RANKS, IPC_HANDLE_BYTES = 16, 64  # MRL_MAX_RANKS, MRL_IPC_HANDLE_BYTES
 OBS_RAW, OBS_ACROBOT_GYM = 0, 1  # MRL_OBS_*: the observation mrl_rollout_policy forms from STATE
 POLICY_GREEDY = 1  # MRL_POLICY_GREEDY
+PPO_NORM_ADV, PPO_CLIP_VLOSS = 1, 2  # MRL_PPO_*
+PPO_STATS = ("pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac", "total_norm", "loss")  # a stats row
 
 # every symbol include/mrl_envs.h declares
 SYMBOLS = [
@@ -39,7 +41,7 @@ SYMBOLS = [
     "mrl_step_phase2_gathered", "mrl_set_observation_output", "mrl_set_observation_ring", "mrl_prepare_graph_capture", "mrl_step_many",
     "mrl_build_hash", "mrl_exchange_create", "mrl_exchange_connect", "mrl_step_exchanged", "mrl_reset_worlds",
     "mrl_acrobot_create", "mrl_enable_episode_stats", "mrl_clear_episode_totals", "mrl_mlp_policy_num_params",
-    "mrl_rollout_policy", "mrl_gae",
+    "mrl_rollout_policy", "mrl_gae", "mrl_ppo_workspace_bytes", "mrl_ppo_update",
 ]
 ABI_VERSION = 4  # MRL_ABI_VERSION of include/mrl_envs.h this binding was written against
 
@@ -72,6 +74,21 @@ class MlpPolicyDesc(ctypes.Structure):  # mrl_mlp_policy
 class RolloutBuffers(ctypes.Structure):  # mrl_rollout_buffers
     _fields_ = [(name, ctypes.c_void_p) for name in ("obs", "actions", "logprobs", "values", "rewards", "dones", "next_obs",
                                                      "next_value", "next_done")] + [("num_steps", ctypes.c_uint32)]
+
+
+class PpoConfig(ctypes.Structure):  # mrl_ppo_config
+    _fields_ = [(name, ctypes.c_float) for name in ("clip_coef", "ent_coef", "vf_coef", "max_grad_norm", "lr", "beta1", "beta2",
+                                                    "eps")] + [("flags", ctypes.c_uint32)]
+
+
+class PpoBatch(ctypes.Structure):  # mrl_ppo_batch
+    _fields_ = [(name, ctypes.c_void_p) for name in ("obs", "actions", "logprobs", "advantages", "returns", "values")] + \
+               [("size", ctypes.c_uint32)]
+
+
+class PpoOptimizerDesc(ctypes.Structure):  # mrl_ppo_optimizer
+    _fields_ = [("params_dev", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p),
+                ("step", ctypes.c_uint32)]
 
 
 class MrlError(RuntimeError):
@@ -184,6 +201,9 @@ def lib():
     L.mrl_mlp_policy_num_params.restype = ctypes.c_uint64
     L.mrl_rollout_policy.argtypes = [vp, ctypes.POINTER(MlpPolicyDesc), ctypes.POINTER(RolloutBuffers), ctypes.c_uint64, u32, vp]
     L.mrl_gae.argtypes = [vp, vp, vp, vp, vp, u32, u32, ctypes.c_float, ctypes.c_float, vp, vp, i32, vp]
+    L.mrl_ppo_workspace_bytes.argtypes = [u32, u32, u32, u32, u32, ctypes.POINTER(ctypes.c_uint64)]
+    L.mrl_ppo_update.argtypes = [ctypes.POINTER(MlpPolicyDesc), ctypes.POINTER(PpoOptimizerDesc), ctypes.POINTER(PpoBatch), vp, u32,
+                                 u32, ctypes.POINTER(PpoConfig), vp, ctypes.c_uint64, vp, vp, i32, vp]
     L.mrl_tensor.argtypes = [vp, i32, ctypes.POINTER(TensorDesc)]
     L.mrl_game.argtypes = [vp]
     L.mrl_num_worlds.argtypes = [vp]

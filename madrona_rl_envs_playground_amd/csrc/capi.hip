@@ -3,6 +3,7 @@
 #include "episode_scan.hpp"
 #include "episode_stats.hpp"
 #include "policy_rollout.hpp"
+#include "ppo_update.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -702,6 +703,73 @@ int mrl_gae(const float *rewards, const float *values, const float *dones, const
     return guarded([&] {
         mrl::launch_gae(rewards, values, dones, next_value, next_done, num_steps, num_worlds, gamma, lambda, advantages, returns,
                         (hipStream_t)hip_stream);
+    });
+}
+
+static bool ppo_shape_ok(uint32_t obs_dim, uint32_t hidden, uint32_t num_actions)
+{
+    return hidden == mrl::kPolicyHidden && ((obs_dim == 4 && (num_actions == 2 || num_actions == 3)) || (obs_dim == 6 && num_actions == 3));
+}
+
+int mrl_ppo_workspace_bytes(uint32_t obs_dim, uint32_t hidden, uint32_t num_actions, uint32_t minibatch_size,
+                            uint32_t num_minibatches, uint64_t *out)
+{
+    if (!out || !ppo_shape_ok(obs_dim, hidden, num_actions) || minibatch_size == 0) {
+        mrl::set_error("mrl_ppo_workspace_bytes: need an output pointer, hidden = 64, (obs_dim, num_actions) one of (4, 2), (4, 3), "
+                       "(6, 3) and minibatch_size > 0; got hidden %u, obs_dim %u, num_actions %u, minibatch_size %u", hidden, obs_dim,
+                       num_actions, minibatch_size);
+        return MRL_ERR_INVALID;
+    }
+    const uint64_t params = mrl_mlp_policy_num_params(obs_dim, hidden, num_actions);
+    *out = mrl::ppo_workspace(params, minibatch_size, num_minibatches).total * sizeof(float);
+    return MRL_OK;
+}
+
+int mrl_ppo_update(const mrl_mlp_policy *shape, const mrl_ppo_optimizer *opt, const mrl_ppo_batch *batch,
+                   const int32_t *indices_dev, uint32_t num_minibatches, uint32_t minibatch_size, const mrl_ppo_config *cfg,
+                   void *workspace_dev, uint64_t workspace_bytes, float *stats_dev_or_null, float *grads_dev_or_null, int gpu_id,
+                   void *hip_stream)
+{
+    if (!shape || !opt || !batch || !indices_dev || !cfg || !workspace_dev) {
+        mrl::set_error("mrl_ppo_update: null shape, optimizer, batch, index array, configuration or workspace");
+        return MRL_ERR_INVALID;
+    }
+    if (!opt->params_dev || !opt->exp_avg || !opt->exp_avg_sq || !batch->obs || !batch->actions || !batch->logprobs ||
+        !batch->advantages || !batch->returns || !batch->values) {
+        mrl::set_error("mrl_ppo_update: null parameter, moment or batch array");
+        return MRL_ERR_INVALID;
+    }
+    if (!ppo_shape_ok(shape->obs_dim, shape->hidden, shape->num_actions)) {
+        mrl::set_error("mrl_ppo_update: need hidden = 64 and (obs_dim, num_actions) one of (4, 2), (4, 3), (6, 3); got hidden %u, "
+                       "obs_dim %u, num_actions %u", shape->hidden, shape->obs_dim, shape->num_actions);
+        return MRL_ERR_INVALID;
+    }
+    if (minibatch_size == 0 || batch->size == 0 || (minibatch_size < 2 && (cfg->flags & MRL_PPO_NORM_ADV))) {
+        mrl::set_error("mrl_ppo_update: need minibatch_size > 0 (> 1 with MRL_PPO_NORM_ADV: the unbiased std of one sample does not "
+                       "exist) and a batch of at least one sample; got minibatch_size %u, batch size %u", minibatch_size, batch->size);
+        return MRL_ERR_INVALID;
+    }
+    const uint64_t params = mrl_mlp_policy_num_params(shape->obs_dim, shape->hidden, shape->num_actions);
+    const uint64_t need_bytes = mrl::ppo_workspace(params, minibatch_size, num_minibatches).total * sizeof(float);
+    if (workspace_bytes < need_bytes) {
+        mrl::set_error("mrl_ppo_update: workspace of %llu bytes, mrl_ppo_workspace_bytes asks for %llu", (unsigned long long)workspace_bytes,
+                       (unsigned long long)need_bytes);
+        return MRL_ERR_INVALID;
+    }
+    const uintptr_t row_align = shape->obs_dim == 4 ? 15u : 7u;  // the observation rows are loaded 16 / 8 bytes at a time
+    if ((reinterpret_cast<uintptr_t>(batch->obs) & row_align) || (reinterpret_cast<uintptr_t>(workspace_dev) & 15u)) {
+        mrl::set_error("mrl_ppo_update: obs must start on a %u-byte boundary and the workspace on a 16-byte one", (unsigned)row_align + 1u);
+        return MRL_ERR_INVALID;
+    }
+    if (mrl::capturing(hip_stream)) {
+        mrl::set_error("mrl_ppo_update: the Adam step number travels in kernel arguments, so the call cannot be captured in a HIP "
+                       "graph: a replay would repeat the same step's bias correction");
+        return MRL_ERR_INVALID;
+    }
+    mrl::DeviceGuard on(gpu_id);
+    return guarded([&] {
+        mrl::launch_ppo_update(*shape, *opt, *batch, indices_dev, num_minibatches, minibatch_size, *cfg,
+                               static_cast<float *>(workspace_dev), stats_dev_or_null, grads_dev_or_null, (hipStream_t)hip_stream);
     });
 }
 

@@ -268,6 +268,104 @@ def gae(rollout, gamma, gae_lambda):
     return advantages, returns
 
 
+class PpoOptimizer:
+    """Adam's state for ``ppo_update`` (``torch.optim.Adam(lr, betas, eps)`` without amsgrad or weight decay, as the reference's
+    trainer builds it, scripts/cartpole_train_torch.py:176): ``exp_avg`` and ``exp_avg_sq`` on ``policy.params``' device, the
+    number of steps taken (``step``) and the scratch ``mrl_ppo_update`` asks for, kept from call to call.  ``lr`` is an
+    ordinary attribute: assign to it to anneal (:199-202)."""
+
+    def __init__(self, policy, lr=2.5e-4, betas=(0.9, 0.999), eps=1e-5):
+        if not isinstance(policy, MlpPolicy):
+            raise ValueError("policy must be an MlpPolicy")
+        self.policy = policy
+        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.exp_avg = torch.zeros_like(policy.params)
+        self.exp_avg_sq = torch.zeros_like(policy.params)
+        self.step = 0
+        self._workspace = None
+
+    def workspace_bytes(self, minibatch_size, num_minibatches):
+        """``mrl_ppo_workspace_bytes`` for this policy's shape."""
+        p = self.policy
+        out = ctypes.c_uint64(0)
+        _lib.check(_lib.lib().mrl_ppo_workspace_bytes(p.obs_dim, p.hidden, p.num_actions, int(minibatch_size), int(num_minibatches),
+                                                      ctypes.byref(out)))
+        return int(out.value)
+
+    def workspace(self, minibatch_size, num_minibatches):
+        """A uint8 tensor of at least ``workspace_bytes`` on the parameters' device: the cached one while it is large enough."""
+        need = self.workspace_bytes(minibatch_size, num_minibatches)
+        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != self.policy.params.device:
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.policy.params.device)
+        return self._workspace
+
+
+def minibatch_indices(batch_size, num_minibatches, epochs, generator=None, device="cpu"):
+    """The rows ``ppo_update`` takes, (epochs * num_minibatches, batch_size // num_minibatches) int32 on ``device``: every epoch
+    is one ``torch.randperm(batch_size)`` cut into ``num_minibatches`` rows (scripts/cartpole_train_torch.py:267-273).
+    ``generator`` draws the permutations, on its own device."""
+    batch_size, num_minibatches, epochs = int(batch_size), int(num_minibatches), int(epochs)
+    if batch_size <= 0 or num_minibatches <= 0 or epochs < 0 or batch_size % num_minibatches:
+        raise ValueError("batch_size must be a positive multiple of num_minibatches, epochs not negative")
+    where = generator.device if generator is not None else torch.device(device)
+    rows = [torch.randperm(batch_size, generator=generator, device=where).to(device=device, dtype=torch.int32)
+            for _ in range(epochs)]
+    width = batch_size // num_minibatches
+    if not rows:
+        return torch.empty((0, width), dtype=torch.int32, device=device)
+    return torch.stack(rows).reshape(epochs * num_minibatches, width)
+
+
+PpoResult = collections.namedtuple("PpoResult", "stats grads")  # (K, 8) in the order of ``_lib.PPO_STATS`` / (K, P), or None
+
+
+def ppo_update(policy, optimizer, rollout, advantages, returns, indices, clip_coef=0.2, ent_coef=0.01, vf_coef=0.5,
+               max_grad_norm=0.5, norm_adv=True, clip_vloss=True, stats=True, grads=False):
+    """One Adam step per row of ``indices`` on the PPO loss of scripts/cartpole_train_torch.py:275-315, on the device
+    (``mrl_ppo_update``: three launches per row), enqueued on torch's current stream; it does not wait.  ``policy.params`` is
+    updated in place -- the next ``rollout_policy`` reads it as it stands, there is no ``load_`` --, ``optimizer.step`` grows
+    by the number of rows.  ``rollout`` is what ``rollout_policy`` returned (its obs, actions, logprobs and values, flattened
+    to T * N samples), ``advantages`` and ``returns`` what ``gae`` returned, ``indices`` (K, B) int32 sample numbers
+    (``minibatch_indices``).  Returns ``PpoResult(stats, grads)``: (K, 8) float32, columns ``_lib.PPO_STATS``, and (K, P) the
+    unclipped gradients, each None unless asked for."""
+    if not isinstance(policy, MlpPolicy) or not isinstance(optimizer, PpoOptimizer) or optimizer.policy is not policy:
+        raise ValueError("policy must be an MlpPolicy and optimizer the PpoOptimizer made for it")
+    p = policy.params
+    if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+        raise ValueError("policy.params must be a contiguous float32 tensor on a GPU")
+    device, f32 = p.device, torch.float32
+    count = rollout.values.numel()
+    wanted = (("policy.params", p, f32, p.numel()), ("optimizer.exp_avg", optimizer.exp_avg, f32, p.numel()),
+              ("optimizer.exp_avg_sq", optimizer.exp_avg_sq, f32, p.numel()), ("rollout.obs", rollout.obs, f32, count * policy.obs_dim),
+              ("rollout.actions", rollout.actions, torch.int32, count), ("rollout.logprobs", rollout.logprobs, f32, count),
+              ("rollout.values", rollout.values, f32, count), ("advantages", advantages, f32, count), ("returns", returns, f32, count),
+              ("indices", indices, torch.int32, None))
+    for name, tensor, dtype, numel in wanted:
+        if (not isinstance(tensor, torch.Tensor) or tensor.device != device or tensor.dtype != dtype or not tensor.is_contiguous() or
+                (numel is not None and tensor.numel() != numel)):
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor on {device}" + (f" of {numel} elements" if numel else ""))
+    if indices.dim() != 2:
+        raise ValueError("indices must be (rows, minibatch_size)")
+    rows, width = indices.shape
+    workspace = optimizer.workspace(width, rows) if width else None
+    out_stats = torch.empty((rows, len(_lib.PPO_STATS)), dtype=f32, device=device) if stats else None
+    out_grads = torch.empty((rows, p.numel()), dtype=f32, device=device) if grads else None
+    shape = _lib.MlpPolicyDesc(p.data_ptr(), policy.obs_dim, policy.hidden, policy.num_actions, 0, 0)
+    opt = _lib.PpoOptimizerDesc(p.data_ptr(), optimizer.exp_avg.data_ptr(), optimizer.exp_avg_sq.data_ptr(), optimizer.step)
+    batch = _lib.PpoBatch(rollout.obs.data_ptr(), rollout.actions.data_ptr(), rollout.logprobs.data_ptr(), advantages.data_ptr(),
+                          returns.data_ptr(), rollout.values.data_ptr(), count)
+    cfg = _lib.PpoConfig(clip_coef, ent_coef, vf_coef, max_grad_norm, optimizer.lr, optimizer.betas[0], optimizer.betas[1],
+                         optimizer.eps, (_lib.PPO_NORM_ADV if norm_adv else 0) | (_lib.PPO_CLIP_VLOSS if clip_vloss else 0))
+    gpu = device.index
+    _lib.check(_lib.lib().mrl_ppo_update(ctypes.byref(shape), ctypes.byref(opt), ctypes.byref(batch), indices.data_ptr(), rows, width,
+                                         ctypes.byref(cfg), workspace.data_ptr() if workspace is not None else None,
+                                         workspace.numel() if workspace is not None else 0,
+                                         out_stats.data_ptr() if stats else None, out_grads.data_ptr() if grads else None, gpu,
+                                         _stream_ptr(gpu)))
+    optimizer.step += rows
+    return PpoResult(out_stats, out_grads)
+
+
 def totals_of(totals):
     """The column sums of a TOTALS tensor (float64, (blocks, 2 + players)) as ``episode_totals`` returns them."""
     sums = totals.sum(dim=0).tolist()  # (the host waits here)
