@@ -651,6 +651,104 @@ int mrl_ppo_update(const mrl_mlp_policy *shape, const mrl_ppo_optimizer *opt, co
                    const mrl_ppo_config *cfg, void *workspace_dev, uint64_t workspace_bytes,
                    float *stats_dev_or_null /* (K, 8) */, float *grads_dev_or_null /* (K, P) */, int gpu_id, void *hip_stream);
 
+/* The collection phase of the reference's CleanPPOAgent (pantheonrl_extension/vectoragent.py:116-372) on the device, for
+ * Hanabi and the balance beam: the agent scripts/hanabi_train.py and scripts/balance_train.py build twice (ego and partner)
+ * around env.step.  Per environment step and agent the reference casts observation and state to float, runs two four-layer
+ * ReLU MLPs of width 512 for EVERY world, masks the logits, draws from a Categorical, writes about ten buffer rows
+ * (:352-371) and reads torch.any(dones) on the host (:207); before each update it walks T steps backwards with boolean-mask
+ * indexing (:230-262).  Here those are mrl_agent_act, mrl_agent_credit and mrl_gae_active; none of them synchronises.  The
+ * learning phase (:268-330) stays with the caller.  No reference counterpart as calls.  DESIGN.md section 14.
+ *   Policy (CleanRLNetwork, :66-113): critic = Linear(S, 512), ReLU, Linear(512, 512), ReLU, Linear(512, 512), ReLU,
+ *     Linear(512, 1); actor the same from D inputs to A outputs.  params_dev is one flat float32 device array in the order of
+ *     parameters_to_vector(agent.parameters()): critic.0.weight (512, S) row-major, critic.0.bias, ..., critic.6.bias, then
+ *     actor.0.weight, ...; mrl_wide_policy_num_params floats.  It is read in place in every call.  The width and the number of
+ *     layers are fixed; 1 <= A <= MRL_WIDE_MAX_ACTIONS; D and S from 1 up, at most the simulator's row widths.
+ *   mrl_agent_act acts for player `player` on the simulator's tensors as they stand: OBSERVATION, STATE (the balance beam's
+ *     state is its observation), ACTION_MASK and ACTIVE_AGENT are read in place, in their own element types and at their own
+ *     strides (the first D / S / A entries of a row); there is no float copy of the inputs.
+ *     Rows: only worlds with ACTIVE_AGENT[player, w] != 0 are computed (an integer compaction in front of the layers); the
+ *     others get action 0, log-prob 0 and value 0 -- the Hanabi step reads the mover's action only, and a trainer reads active
+ *     rows only.  MRL_AGENT_ALL_ROWS computes every world, as the reference does.
+ *     Arithmetic: every matrix layer runs on v_mfma_f32_32x32x2_f32 in exact float32; an output starts from 0 and adds the
+ *     inputs in ascending order, one fused multiply-add each (a K that is not a multiple of 2 is padded with zeros); the bias
+ *     is added to the finished sum, one more rounding.  (Unlike mrl_policy_act, whose chain starts from the bias: here the
+ *     output layers' products are a hundred times smaller than their bias, and 512 of them rounded at the bias's ulp put
+ *     the value 6 - 17 ulp from a float64 evaluation; bias last, it is within 3.)
+ *     Head, float32, per computed world: legal = ACTION_MASK != 0; m = max legal logit; e_a = exp(l_a - m), 0 for illegal a;
+ *     p_a = e_a / sum e (sum in ascending a); h = the hash of mrl_rollout_random of (seed, step, w, player); u = (h >> 8) * 2^-24;
+ *     action = the number of a in 0..A-2 with u >= p_0 + ... + p_a; if that action is illegal (rounding left the cumulative sum
+ *     below u) the last legal action; logprob = (l_action - m) - log(sum e).  MRL_POLICY_GREEDY: the first legal arg-max.  The
+ *     action goes to ACTION[player, w].  A world with no legal action (undefined in the reference: NaN) yields action 0 and
+ *     log-prob -inf.
+ *     Recording, record != NULL (:354-371), row `row` < num_steps of dense buffers: obs (T, N, D) and states (T, N, S) in the
+ *     inputs' own element types, action_masks (T, N, A) uint8 0/1, active (T, N) uint8, actions int32, logprobs, values,
+ *     dones (the agent's next_done as 0.0 / 1.0, which is then cleared), rewards (row set to 0) (T, N); last_active[w] = row
+ *     and new_game[w] = 0 where the world is active.  Inactive worlds get their obs / states / mask copies too.  logits, if
+ *     non-NULL, (N, MRL_WIDE_MAX_ACTIONS): the A unmasked logits of every computed world (tests and diagnostics).
+ *     MRL_AGENT_VALUE_ONLY (needs record): the critic alone; next_value[w] = its value (0 for a world not computed),
+ *     next_active[w] = ACTIVE_AGENT != 0; nothing else is written, no action is drawn.
+ *     workspace: mrl_agent_workspace_bytes(N) bytes of device memory, 16-byte aligned, the caller's; holds nothing between calls.
+ *     Launches: compaction, bookkeeping and copies, four layers (a grid over row tile x column slab x net), head.
+ *     MRL_ERR_INVALID: a game other than Hanabi or the balance beam; a NULL policy, parameter array or workspace; A > 64 or 0;
+ *     D / S / A wider than the simulator's rows; player out of range; row >= num_steps, num_worlds other than the simulator's or
+ *     a NULL buffer in a record; VALUE_ONLY without a record; a capturing stream wherever mrl_step refuses one (the row and the
+ *     step number travel in kernel arguments: a captured call would replay them); a simulator that has been through
+ *     mrl_exchange_create.
+ *   mrl_agent_credit is update() (:197-219) as one launch, dones = the DONE tensor (int32, N): running_rewards[w] += r;
+ *     rewards[last_active[w], w] += new_game[w] ? 0 : r; next_done[w] |= done; where done: the running return joins totals,
+ *     then running_rewards[w] = 0 and new_game[w] = 1.  totals is float64 (ceil(N / 1024), 4) = finished episodes, the sum of
+ *     their returns, their minimum, their maximum per block of 1024 worlds; the caller initialises it to (0, 0, +inf, -inf).
+ *     One workgroup owns a block and adds its worlds in a fixed order; no float atomics.  (The reference's indexed assignment,
+ *     self.rewards[self.last_active] += ..., selects whole ROWS and so also adds r[w] to column w of every row that is any
+ *     world's last_active; those extra cells belong to steps at which w was not the one to act or which w has since left behind
+ *     only if worlds get out of step with each other.  What is followed here is the documented intent, per world.)
+ *   mrl_gae_active is :231-262, a lane per world, t = T-1 ... 0, float32, the reference's operations in its order,
+ *     gl = float32(double(gamma) * double(lambda)):  boot = next_active[w]; nnt = boot ? 1 - next_done[w] : 0;
+ *     nv = boot ? next_value[w] : 0; last = 0.  At t, if active[t, w]: a world not yet bootstrapped computes delta = r[t,w] +
+ *     gamma * nv * nnt - v[t,w] (its nv and nnt are 0), advantages[t,w] = last = delta + gl * nnt * last, has active[t, w]
+ *     CLEARED (the row only carries the bootstrap) and is bootstrapped from there on, its nnt and nv still 0 (the reference
+ *     clears the flag through a view of the very mask it then indexes `nextnonterminal[mask] = ...` with, :245-261, so the row
+ *     that bootstraps a world hands nothing on: the next earlier active row of that world computes r - v again); a world that
+ *     was bootstrapped before t computes the same two lines and then sets nnt = 1 - dones[t,w], nv = v[t,w].  Everything else of
+ *     advantages is 0; returns = advantages + values.
+ *     One coupling between worlds exists in the reference and is kept: while any world of the batch is not yet bootstrapped
+ *     (`if not torch.all(bootstrapped)`, :248), only the worlds being bootstrapped at that t are computed -- an already
+ *     bootstrapped, active world keeps advantage 0 and its `last`, though its nnt and nv advance and its row stays active.
+ *     With first[w] = T if next_active[w], else the largest t with active[t,w], else -1, and t* = min over w of first[w] (one
+ *     integer-minimum launch in front, through record->first_step), that holds at every t >= t*.
+ *     MRL_ERR_INVALID: a NULL record, array or buffer. */
+enum { MRL_AGENT_ALL_ROWS = 2, MRL_AGENT_VALUE_ONLY = 4 }; /* flags of mrl_agent_act, beside MRL_POLICY_GREEDY */
+#define MRL_WIDE_HIDDEN 512
+#define MRL_WIDE_MAX_ACTIONS 64
+typedef struct mrl_wide_policy {
+    const float *params_dev;
+    uint32_t obs_dim, state_dim, num_actions; /* D, S, A */
+} mrl_wide_policy;
+typedef struct mrl_agent_record { /* all device pointers, dense; T = num_steps, N = num_worlds */
+    void *obs, *states;           /* (T, N, D), (T, N, S), the inputs' element types */
+    uint8_t *action_masks;        /* (T, N, A) */
+    uint8_t *active;              /* (T, N) */
+    int32_t *actions;             /* (T, N) */
+    float *logprobs, *values, *dones, *rewards; /* (T, N) */
+    int32_t *last_active;         /* (N) */
+    uint8_t *new_game, *next_done; /* (N) */
+    float *running_rewards;       /* (N) */
+    double *totals;               /* (ceil(N / 1024), 4) */
+    float *next_value;            /* (N), written by MRL_AGENT_VALUE_ONLY */
+    uint8_t *next_active;         /* (N), written by MRL_AGENT_VALUE_ONLY */
+    int32_t *first_step;          /* (1), scratch of mrl_gae_active */
+    float *logits;                /* (N, MRL_WIDE_MAX_ACTIONS) or NULL */
+    uint32_t num_steps, num_worlds;
+} mrl_agent_record;
+uint64_t mrl_wide_policy_num_params(uint32_t obs_dim, uint32_t state_dim, uint32_t num_actions);
+uint64_t mrl_agent_workspace_bytes(uint32_t num_worlds);
+int mrl_agent_act(mrl_sim *sim, uint32_t player, const mrl_wide_policy *policy, const mrl_agent_record *record_or_null,
+                  uint32_t row, uint64_t seed, uint32_t step, uint32_t flags, void *workspace_dev, void *hip_stream);
+int mrl_agent_credit(const mrl_agent_record *record, const float *rewards_dev, const int32_t *dones_dev, uint32_t num_worlds,
+                     int gpu_id, void *hip_stream);
+int mrl_gae_active(const mrl_agent_record *record, const float *next_value, const uint8_t *next_active, float gamma, float lambda,
+                   float *advantages, float *returns, int gpu_id, void *hip_stream);
+
 int mrl_tensor(mrl_sim *sim, int slot, mrl_tensor_desc *out);
 int mrl_game(const mrl_sim *sim);
 uint32_t mrl_num_worlds(const mrl_sim *sim);

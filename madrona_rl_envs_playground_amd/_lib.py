@@ -28,6 +28,8 @@ MAX_DIMS = 6
 MAX_RANKS, IPC_HANDLE_BYTES = 16, 64  # MRL_MAX_RANKS, MRL_IPC_HANDLE_BYTES
 OBS_RAW, OBS_ACROBOT_GYM = 0, 1  # MRL_OBS_*: the observation mrl_rollout_policy forms from STATE
 POLICY_GREEDY = 1  # MRL_POLICY_GREEDY
+AGENT_ALL_ROWS, AGENT_VALUE_ONLY = 2, 4  # MRL_AGENT_*: flags of mrl_agent_act beside POLICY_GREEDY
+WIDE_HIDDEN, WIDE_MAX_ACTIONS = 512, 64  # MRL_WIDE_*
 PPO_NORM_ADV, PPO_CLIP_VLOSS = 1, 2  # MRL_PPO_*
 PPO_STATS = ("pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac", "total_norm", "loss")  # a stats row
 
@@ -41,7 +43,8 @@ SYMBOLS = [
     "mrl_step_phase2_gathered", "mrl_set_observation_output", "mrl_set_observation_ring", "mrl_prepare_graph_capture", "mrl_step_many",
     "mrl_build_hash", "mrl_exchange_create", "mrl_exchange_connect", "mrl_step_exchanged", "mrl_reset_worlds",
     "mrl_acrobot_create", "mrl_enable_episode_stats", "mrl_clear_episode_totals", "mrl_mlp_policy_num_params",
-    "mrl_rollout_policy", "mrl_gae", "mrl_ppo_workspace_bytes", "mrl_ppo_update",
+    "mrl_rollout_policy", "mrl_gae", "mrl_ppo_workspace_bytes", "mrl_ppo_update", "mrl_wide_policy_num_params",
+    "mrl_agent_workspace_bytes", "mrl_agent_act", "mrl_agent_credit", "mrl_gae_active",
 ]
 ABI_VERSION = 4  # MRL_ABI_VERSION of include/mrl_envs.h this binding was written against
 
@@ -89,6 +92,20 @@ class PpoBatch(ctypes.Structure):  # mrl_ppo_batch
 class PpoOptimizerDesc(ctypes.Structure):  # mrl_ppo_optimizer
     _fields_ = [("params_dev", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p),
                 ("step", ctypes.c_uint32)]
+
+
+class WidePolicyDesc(ctypes.Structure):  # mrl_wide_policy
+    _fields_ = [("params_dev", ctypes.c_void_p), ("obs_dim", ctypes.c_uint32), ("state_dim", ctypes.c_uint32),
+                ("num_actions", ctypes.c_uint32)]
+
+
+AGENT_RECORD_BUFFERS = ("obs", "states", "action_masks", "active", "actions", "logprobs", "values", "dones", "rewards", "last_active",
+                        "new_game", "next_done", "running_rewards", "totals", "next_value", "next_active", "first_step", "logits")
+
+
+class AgentRecord(ctypes.Structure):  # mrl_agent_record
+    _fields_ = [(name, ctypes.c_void_p) for name in AGENT_RECORD_BUFFERS] + [("num_steps", ctypes.c_uint32),
+                                                                             ("num_worlds", ctypes.c_uint32)]
 
 
 class MrlError(RuntimeError):
@@ -204,6 +221,14 @@ def lib():
     L.mrl_ppo_workspace_bytes.argtypes = [u32, u32, u32, u32, u32, ctypes.POINTER(ctypes.c_uint64)]
     L.mrl_ppo_update.argtypes = [ctypes.POINTER(MlpPolicyDesc), ctypes.POINTER(PpoOptimizerDesc), ctypes.POINTER(PpoBatch), vp, u32,
                                  u32, ctypes.POINTER(PpoConfig), vp, ctypes.c_uint64, vp, vp, i32, vp]
+    L.mrl_wide_policy_num_params.argtypes = [u32, u32, u32]
+    L.mrl_wide_policy_num_params.restype = ctypes.c_uint64
+    L.mrl_agent_workspace_bytes.argtypes = [u32]
+    L.mrl_agent_workspace_bytes.restype = ctypes.c_uint64
+    L.mrl_agent_act.argtypes = [vp, u32, ctypes.POINTER(WidePolicyDesc), ctypes.POINTER(AgentRecord), u32, ctypes.c_uint64, u32, u32, vp,
+                                vp]
+    L.mrl_agent_credit.argtypes = [ctypes.POINTER(AgentRecord), vp, vp, u32, i32, vp]
+    L.mrl_gae_active.argtypes = [ctypes.POINTER(AgentRecord), vp, vp, ctypes.c_float, ctypes.c_float, vp, vp, i32, vp]
     L.mrl_tensor.argtypes = [vp, i32, ctypes.POINTER(TensorDesc)]
     L.mrl_game.argtypes = [vp]
     L.mrl_num_worlds.argtypes = [vp]

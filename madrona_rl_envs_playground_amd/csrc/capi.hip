@@ -4,6 +4,7 @@
 #include "episode_stats.hpp"
 #include "policy_rollout.hpp"
 #include "ppo_update.hpp"
+#include "wide_policy.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -770,6 +771,121 @@ int mrl_ppo_update(const mrl_mlp_policy *shape, const mrl_ppo_optimizer *opt, co
     return guarded([&] {
         mrl::launch_ppo_update(*shape, *opt, *batch, indices_dev, num_minibatches, minibatch_size, *cfg,
                                static_cast<float *>(workspace_dev), stats_dev_or_null, grads_dev_or_null, (hipStream_t)hip_stream);
+    });
+}
+
+uint64_t mrl_wide_policy_num_params(uint32_t obs_dim, uint32_t state_dim, uint32_t num_actions)
+{
+    return mrl::wide_net_params(state_dim, 1) + mrl::wide_net_params(obs_dim, num_actions);
+}
+
+uint64_t mrl_agent_workspace_bytes(uint32_t num_worlds) { return mrl::wide_workspace_bytes(num_worlds); }
+
+static bool agent_record_complete(const mrl_agent_record *r)
+{
+    return r->obs && r->states && r->action_masks && r->active && r->actions && r->logprobs && r->values && r->dones && r->rewards &&
+           r->last_active && r->new_game && r->next_done && r->running_rewards && r->totals && r->next_value && r->next_active &&
+           r->first_step;
+}
+
+// player p's (N, width) slice of a (P, N, width) tensor, or its (N) slice of a (P, N) one
+static mrl::WideInput agent_slice(const mrl_tensor_desc &d, uint32_t player)
+{
+    const int64_t bytes = d.dtype == MRL_INT8 || d.dtype == MRL_UINT8 ? 1 : 4;
+    mrl::WideInput in{};
+    in.data = static_cast<const char *>(d.data) + (int64_t)player * d.strides[0] * bytes;
+    in.row_stride = d.strides[1];
+    in.type = (uint32_t)d.dtype;
+    return in;
+}
+
+int mrl_agent_act(mrl_sim *sim, uint32_t player, const mrl_wide_policy *policy, const mrl_agent_record *record, uint32_t row,
+                  uint64_t seed, uint32_t step, uint32_t flags, void *workspace_dev, void *hip_stream)
+{
+    if (int rc = mrl::need_healthy(sim)) return rc;
+    if (int rc = mrl::need_not_capturing(sim, hip_stream, "mrl_agent_act")) return rc;
+    if (sim->game != MRL_GAME_HANABI && sim->game != MRL_GAME_BALANCE) {
+        mrl::set_error("mrl_agent_act: game %d has no wide-policy agent (Hanabi and the balance beam do)", sim->game);
+        return MRL_ERR_INVALID;
+    }
+    if (sim->exchange.mine) {
+        mrl::set_error("mrl_agent_act: this simulator is a rank of an exchanged batch (mrl_exchange_create); sharded simulators are out of scope");
+        return MRL_ERR_INVALID;
+    }
+    if (!policy || !policy->params_dev || !workspace_dev || (reinterpret_cast<uintptr_t>(workspace_dev) & 15u)) {
+        mrl::set_error("mrl_agent_act: null policy or parameter array, or a workspace that is null or off a 16-byte boundary");
+        return MRL_ERR_INVALID;
+    }
+    if (policy->num_actions == 0 || policy->num_actions > MRL_WIDE_MAX_ACTIONS || policy->obs_dim == 0 || policy->state_dim == 0) {
+        mrl::set_error("mrl_agent_act: need 1 <= num_actions <= %d and obs_dim, state_dim >= 1; got num_actions %u, obs_dim %u, state_dim %u",
+                       MRL_WIDE_MAX_ACTIONS, policy->num_actions, policy->obs_dim, policy->state_dim);
+        return MRL_ERR_INVALID;
+    }
+    if ((flags & MRL_AGENT_VALUE_ONLY) && !record) {
+        mrl::set_error("mrl_agent_act: MRL_AGENT_VALUE_ONLY writes next_value and next_active of a record; none was given");
+        return MRL_ERR_INVALID;
+    }
+    if (record && (!agent_record_complete(record) || record->num_worlds != sim->num_worlds ||
+                   (!(flags & MRL_AGENT_VALUE_ONLY) && row >= record->num_steps))) {
+        mrl::set_error("mrl_agent_act: the record needs every buffer but logits, num_worlds = %u (got %u) and row < num_steps (row %u of %u)",
+                       sim->num_worlds, record->num_worlds, row, record->num_steps);
+        return MRL_ERR_INVALID;
+    }
+    mrl::DeviceGuard on(sim->device);
+    int rc = MRL_OK;
+    int g = guarded([&] {
+        mrl_tensor_desc active{}, action{}, obs{}, mask{}, state{};
+        // (the slot numbers are the same for both games: MRL_HANABI_* == MRL_BALANCE_* up to REWARD; the balance beam's state is its observation)
+        if (!sim->tensor(MRL_HANABI_ACTIVE_AGENT, &active) || !sim->tensor(MRL_HANABI_ACTION, &action) ||
+            !sim->tensor(MRL_HANABI_OBSERVATION, &obs) || !sim->tensor(MRL_HANABI_ACTION_MASK, &mask) ||
+            !sim->tensor(sim->game == MRL_GAME_HANABI ? MRL_HANABI_STATE : MRL_BALANCE_OBSERVATION, &state))
+            throw std::runtime_error("mrl_agent_act: the simulator does not export ACTIVE_AGENT / ACTION / OBSERVATION / ACTION_MASK / STATE");
+        if (player >= (uint64_t)obs.shape[0] || policy->obs_dim > (uint64_t)obs.shape[2] || policy->state_dim > (uint64_t)state.shape[2] ||
+            policy->num_actions > (uint64_t)mask.shape[2]) {
+            mrl::set_error("mrl_agent_act: player %u of %lld; obs_dim %u, state_dim %u, num_actions %u against rows of %lld, %lld, %lld", player,
+                           (long long)obs.shape[0], policy->obs_dim, policy->state_dim, policy->num_actions, (long long)obs.shape[2],
+                           (long long)state.shape[2], (long long)mask.shape[2]);
+            rc = MRL_ERR_INVALID;
+            return;
+        }
+        if (obs.strides[2] != 1 || state.strides[2] != 1 || mask.strides[2] != 1 || action.dtype != MRL_INT32 || active.ndim != 2)
+            throw std::runtime_error("mrl_agent_act: unexpected tensor layout (rows must be dense, ACTION int32, ACTIVE_AGENT (P, N))");
+        mrl::AgentActArgs args{};
+        args.params = policy->params_dev;
+        args.obs = agent_slice(obs, player), args.state = agent_slice(state, player), args.mask = agent_slice(mask, player);
+        args.active = agent_slice(active, player);
+        args.action = static_cast<int32_t *>(action.data) + (int64_t)player * action.strides[0];
+        args.action_stride = action.strides[1];
+        args.D = policy->obs_dim, args.S = policy->state_dim, args.A = policy->num_actions;
+        args.num_worlds = sim->num_worlds, args.player = player;
+        args.record = record, args.row = row, args.step = step, args.flags = flags, args.seed = seed;
+        args.ws = mrl::wide_workspace(workspace_dev, sim->num_worlds);
+        mrl::launch_agent_act(args, (hipStream_t)hip_stream);
+    });
+    return g != MRL_OK ? g : rc;
+}
+
+int mrl_agent_credit(const mrl_agent_record *record, const float *rewards_dev, const int32_t *dones_dev, uint32_t num_worlds, int gpu_id,
+                     void *hip_stream)
+{
+    if (!record || !rewards_dev || !dones_dev || !agent_record_complete(record) || record->num_worlds != num_worlds) {
+        mrl::set_error("mrl_agent_credit: null record, buffer, reward or done array, or num_worlds other than the record's");
+        return MRL_ERR_INVALID;
+    }
+    mrl::DeviceGuard on(gpu_id);
+    return guarded([&] { mrl::launch_agent_credit(*record, rewards_dev, dones_dev, num_worlds, (hipStream_t)hip_stream); });
+}
+
+int mrl_gae_active(const mrl_agent_record *record, const float *next_value, const uint8_t *next_active, float gamma, float lambda,
+                   float *advantages, float *returns, int gpu_id, void *hip_stream)
+{
+    if (!record || !next_value || !next_active || !advantages || !returns || !agent_record_complete(record)) {
+        mrl::set_error("mrl_gae_active: null record, buffer or array");
+        return MRL_ERR_INVALID;
+    }
+    mrl::DeviceGuard on(gpu_id);
+    return guarded([&] {
+        mrl::launch_gae_active(*record, next_value, next_active, gamma, lambda, advantages, returns, (hipStream_t)hip_stream);
     });
 }
 

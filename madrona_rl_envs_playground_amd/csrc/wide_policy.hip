@@ -1,0 +1,497 @@
+// mrl_agent_act, mrl_agent_credit and mrl_gae_active: what the reference's CleanPPOAgent does around env.step for Hanabi and
+// the balance beam (pantheonrl_extension/vectoragent.py:197-262, :352-372), without the host in the loop
+// (include/mrl_envs.h).
+//
+// One act is seven launches on one stream:
+//   mrl_wide_rows      one workgroup turns ACTIVE_AGENT[player, :] into the ascending list of worlds to compute and its length
+//                      (an integer prefix sum: the same list on every run); with MRL_AGENT_ALL_ROWS the list is 0..N-1.
+//   mrl_agent_book     a lane per world: the per-world rows of the record, zeros for the worlds not computed; then the grid
+//                      copies the observation, state and mask rows in their own element types.
+//   mrl_wide_layer x4  out = act(bias + in W^T) for a 32-row x 128-column tile per workgroup, grid = (row tile, column slab,
+//                      net).  Each of the four wavefronts owns a 32 x 32 tile of v_mfma_f32_32x32x2_f32: lane (r, half) feeds
+//                      A[row r][k = 2 kk + half] and B[k][column r], so an output is 0, then fmaf over k ascending, and the
+//                      bias is added to the finished sum (a chain begun at the bias rounds every product at the bias's
+//                      ulp: DESIGN.md section 14).  The operands go through LDS in chunks of 64 k (rows 66 floats
+//                      apart: lane r reads bank 2 r + half, no conflict), the next chunk's global loads are issued before the current chunk's products.  Layer 1
+//                      reads the simulator's tensors themselves (int8 / int32, row-strided) through the world list; layers
+//                      2-4 read the previous layer's activations from the workspace, which stays in L2.
+//   mrl_agent_head     a lane per computed world: mask, soft-max, draw, log-prob; three passes over the world's <= 64 logits in
+//                      the workspace instead of an array in registers (a dynamically indexed array would go to scratch).
+// No float atomics, no workgroup waits on another, no scratch: the same inputs give the same bits on every run.
+#include "wide_policy.hpp"
+#include "random_policy.hpp"
+
+namespace mrl {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int kTileRows = 32, kTileCols = 128, kChunk = 64, kLd = 66, kLayerThreads = 256;
+constexpr int kStageA = kTileRows * kChunk / kLayerThreads;  // 8 elements of the input tile per thread and chunk
+constexpr int kStageB = kTileCols * kChunk / kLayerThreads;  // 32 of the weight tile
+
+__device__ __forceinline__ float wide_load(const void *p, uint32_t type, int64_t at)
+{
+    switch (type) {
+    case MRL_INT8: return (float)static_cast<const int8_t *>(p)[at];
+    case MRL_UINT8: return (float)static_cast<const uint8_t *>(p)[at];
+    case MRL_INT32: return (float)static_cast<const int32_t *>(p)[at];
+    case MRL_UINT32: return (float)static_cast<const uint32_t *>(p)[at];
+    default: return static_cast<const float *>(p)[at];
+    }
+}
+
+__device__ __forceinline__ bool wide_nonzero(const WideInput &in, int64_t at)
+{
+    switch (in.type) {
+    case MRL_INT8:
+    case MRL_UINT8: return static_cast<const uint8_t *>(in.data)[at] != 0;
+    case MRL_FLOAT32: return static_cast<const float *>(in.data)[at] != 0.0f;
+    default: return static_cast<const uint32_t *>(in.data)[at] != 0u;
+    }
+}
+
+// ---------------------------------------------------------------- the world list
+
+__global__ void __launch_bounds__(1024) mrl_wide_rows(WideInput active, uint32_t num_worlds, uint32_t all_rows,
+                                                      uint32_t *__restrict__ rows, uint32_t *__restrict__ count)
+{
+    __shared__ uint32_t wave_total[16];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    uint32_t base = 0;
+    for (uint32_t start = 0; start < num_worlds; start += 1024u) {
+        const uint32_t w = start + tid;
+        const bool take = w < num_worlds && (all_rows || wide_nonzero(active, (int64_t)w * active.row_stride));
+        const unsigned long long votes = __ballot(take);
+        const uint32_t before = __popcll(votes & ((1ull << lane) - 1ull));
+        if (lane == 0) wave_total[wave] = __popcll(votes);
+        __syncthreads();
+        uint32_t lower = 0, total = 0;
+#pragma unroll
+        for (uint32_t v = 0; v < 16; v++) {
+            const uint32_t c = wave_total[v];
+            lower += v < wave ? c : 0u;
+            total += c;
+        }
+        if (take) rows[base + lower + before] = w;  // base + lower + before < number of taken worlds <= num_worlds
+        base += total;
+        __syncthreads();
+    }
+    if (tid == 0) *count = base;
+}
+
+// ---------------------------------------------------------------- per-world rows of the record and the copies
+
+struct BookArgs {
+    WideInput obs, state, mask, active;
+    int32_t *action;
+    int64_t action_stride;
+    mrl_agent_record rec;
+    uint32_t has_record, row, flags, D, S, A, num_worlds;
+};
+
+template <typename T>
+__device__ __forceinline__ void copy_rows(T *__restrict__ dst, const WideInput &src, uint64_t num_worlds, uint32_t width)
+{
+    const uint64_t total = num_worlds * width, stride = (uint64_t)gridDim.x * blockDim.x;
+    const T *__restrict__ from = static_cast<const T *>(src.data);
+    for (uint64_t at = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; at < total; at += stride) {
+        const uint64_t w = at / width, k = at - w * width;
+        dst[at] = from[(int64_t)w * src.row_stride + (int64_t)k];
+    }
+}
+
+__device__ __forceinline__ uint32_t elem_bytes(uint32_t type) { return type == MRL_INT8 || type == MRL_UINT8 ? 1u : 4u; }
+
+__global__ void __launch_bounds__(256) mrl_agent_book(BookArgs a)
+{
+    const uint64_t N = a.num_worlds, stride = (uint64_t)gridDim.x * blockDim.x;
+    const bool value_only = a.flags & MRL_AGENT_VALUE_ONLY, all_rows = a.flags & MRL_AGENT_ALL_ROWS;
+    const mrl_agent_record &r = a.rec;
+    for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < N; w += stride) {
+        const bool active = wide_nonzero(a.active, (int64_t)w * a.active.row_stride);
+        const bool computed = active || all_rows;
+        if (value_only) {
+            r.next_active[w] = active ? 1 : 0;
+            if (!computed) r.next_value[w] = 0.0f;
+            continue;
+        }
+        if (!computed) a.action[(int64_t)w * a.action_stride] = 0;
+        if (!a.has_record) continue;
+        const uint64_t at = (uint64_t)a.row * N + w;
+        if (!computed) {
+            r.actions[at] = 0;
+            r.logprobs[at] = 0.0f;
+            r.values[at] = 0.0f;
+        }
+        r.active[at] = active ? 1 : 0;
+        r.dones[at] = r.next_done[w] ? 1.0f : 0.0f;
+        r.next_done[w] = 0;
+        r.rewards[at] = 0.0f;
+        if (active) {
+            r.last_active[w] = (int32_t)a.row;
+            r.new_game[w] = 0;
+        }
+    }
+    if (!a.has_record || value_only) return;
+    if (elem_bytes(a.obs.type) == 1)
+        copy_rows(static_cast<uint8_t *>(r.obs) + (uint64_t)a.row * N * a.D, a.obs, N, a.D);
+    else
+        copy_rows(static_cast<uint32_t *>(r.obs) + (uint64_t)a.row * N * a.D, a.obs, N, a.D);
+    if (elem_bytes(a.state.type) == 1)
+        copy_rows(static_cast<uint8_t *>(r.states) + (uint64_t)a.row * N * a.S, a.state, N, a.S);
+    else
+        copy_rows(static_cast<uint32_t *>(r.states) + (uint64_t)a.row * N * a.S, a.state, N, a.S);
+    uint8_t *__restrict__ masks = r.action_masks + (uint64_t)a.row * N * a.A;
+    for (uint64_t at = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; at < N * a.A; at += stride) {
+        const uint64_t w = at / a.A, k = at - w * a.A;
+        masks[at] = wide_nonzero(a.mask, (int64_t)w * a.mask.row_stride + (int64_t)k) ? 1 : 0;
+    }
+}
+
+// ---------------------------------------------------------------- one matrix layer
+
+struct WideLayerNet {
+    const void *in;       // (rows, K) at in_row_stride; layer 1: the simulator's tensor, indexed by world
+    const float *weight;  // (out_dim, K) row-major
+    const float *bias;
+    float *out;           // (rows, out_stride), indexed by position in the world list
+    int64_t in_row_stride;
+    uint32_t in_type, K, out_dim, out_stride;
+};
+struct WideLayerArgs {
+    WideLayerNet net[2];
+    const uint32_t *rows, *count;
+    uint32_t gather;  // the input rows are worlds (rows[j]) and not list positions (j)
+    uint32_t relu;
+};
+
+__device__ __forceinline__ void wide_fetch(const WideLayerNet &n, const int64_t (&arow)[kStageA], uint32_t col_first, uint32_t k,
+                                           float (&pa)[kStageA], float (&pb)[kStageB])
+{
+    const bool in_k = k < n.K;
+#pragma unroll
+    for (int i = 0; i < kStageA; i++) pa[i] = in_k && arow[i] >= 0 ? wide_load(n.in, n.in_type, arow[i] + k) : 0.0f;
+#pragma unroll
+    for (int i = 0; i < kStageB; i++) {
+        const uint32_t col = col_first + 4u * i;
+        pb[i] = in_k && col < n.out_dim ? n.weight[(size_t)col * n.K + k] : 0.0f;
+    }
+}
+
+__global__ void __launch_bounds__(kLayerThreads) mrl_wide_layer(WideLayerArgs a)
+{
+    const WideLayerNet &n = a.net[blockIdx.z];
+    const uint32_t count = *a.count;
+    const uint32_t row0 = blockIdx.x * kTileRows, col0 = blockIdx.y * kTileCols;
+    if (row0 >= count || col0 >= n.out_dim) return;  // (uniform over the workgroup)
+    __shared__ float tile_a[kTileRows * kLd];
+    __shared__ float tile_b[kTileCols * kLd];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, r = lane & 31u, half = lane >> 5;
+
+    // staging: this thread moves k = lane of every chunk for the input rows wave + 4 i and the weight rows wave + 4 i
+    int64_t arow[kStageA];
+#pragma unroll
+    for (int i = 0; i < kStageA; i++) {
+        const uint32_t j = row0 + wave + 4u * i;
+        arow[i] = j < count ? (int64_t)(a.gather ? a.rows[j] : j) * n.in_row_stride : -1;
+    }
+    float pa[kStageA], pb[kStageB];
+    wide_fetch(n, arow, col0 + wave, lane, pa, pb);
+
+    const uint32_t col = col0 + wave * 32u + r;
+    const bool live = col0 + wave * 32u < n.out_dim;  // this wavefront's 32 columns hold at least one output
+    const float bias = col < n.out_dim ? n.bias[col] : 0.0f;
+    f32x16 acc;
+#pragma unroll
+    for (int e = 0; e < 16; e++) acc[e] = 0.0f;
+
+    for (uint32_t k0 = 0; k0 < n.K; k0 += kChunk) {
+#pragma unroll
+        for (int i = 0; i < kStageA; i++) tile_a[(wave + 4u * i) * kLd + lane] = pa[i];
+#pragma unroll
+        for (int i = 0; i < kStageB; i++) tile_b[(wave + 4u * i) * kLd + lane] = pb[i];
+        __syncthreads();
+        if (k0 + kChunk < n.K) wide_fetch(n, arow, col0 + wave, k0 + kChunk + lane, pa, pb);
+        if (live) {
+            const uint32_t left = n.K - k0, steps = left >= (uint32_t)kChunk ? kChunk / 2 : (left + 1u) / 2u;  // an odd tail is padded with a zero
+            const float *__restrict__ pa_lds = tile_a + r * kLd + half;
+            const float *__restrict__ pb_lds = tile_b + (wave * 32u + r) * kLd + half;
+            for (uint32_t kk = 0; kk < steps; kk++)
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pa_lds[2 * kk], pb_lds[2 * kk], acc, 0, 0, 0);
+        }
+        __syncthreads();  // the next chunk overwrites what the products read
+    }
+    if (!live || col >= n.out_dim) return;
+#pragma unroll
+    for (int e = 0; e < 16; e++) {
+        const uint32_t j = row0 + (e & 3) + 8 * (e >> 2) + 4 * half;  // C/D map of the 32 x 32 tile
+        if (j >= count) continue;
+        const float v = acc[e] + bias;
+        n.out[(size_t)j * n.out_stride + col] = a.relu ? (v > 0.0f ? v : 0.0f) : v;
+    }
+}
+
+// ---------------------------------------------------------------- the head
+
+struct HeadArgs {
+    const uint32_t *rows, *count;
+    const float *logits, *value;  // (count, 64), (count)
+    WideInput mask;
+    int32_t *action;
+    int64_t action_stride;
+    mrl_agent_record rec;
+    uint32_t has_record, row, flags, A, num_worlds, player, step;
+    uint64_t seed;
+};
+
+__global__ void __launch_bounds__(64) mrl_agent_head(HeadArgs a)
+{
+    const uint32_t j = blockIdx.x * 64u + threadIdx.x;
+    if (j >= *a.count) return;
+    const uint32_t w = a.rows[j];
+    const uint64_t N = a.num_worlds, at = (uint64_t)a.row * N + w;
+    const mrl_agent_record &r = a.rec;
+    if (a.flags & MRL_AGENT_VALUE_ONLY) {
+        r.next_value[w] = a.value[j];
+        return;
+    }
+    const float *__restrict__ l = a.logits + (size_t)j * kWideMaxActions;
+    const int64_t mask_at = (int64_t)w * a.mask.row_stride;
+    const int A = (int)a.A;
+    float top = -INFINITY;
+    int first = -1, last_legal = -1;  // the first legal arg-max, the last legal action
+    for (int i = 0; i < A; i++) {
+        if (!wide_nonzero(a.mask, mask_at + i)) continue;
+        const float v = l[i];
+        if (first < 0 || v > top) {
+            top = v;
+            first = i;
+        }
+        last_legal = i;
+    }
+    int action = 0;
+    float logprob = -INFINITY;
+    if (first >= 0) {
+        float sum = 0.0f;
+        for (int i = 0; i < A; i++) sum += wide_nonzero(a.mask, mask_at + i) ? expf(l[i] - top) : 0.0f;
+        action = first;
+        if (!(a.flags & MRL_POLICY_GREEDY)) {
+            const float u = (float)(policy_hash(a.seed, a.step, w, a.player) >> 8) * 0x1p-24f;
+            float cdf = 0.0f;
+            action = 0;
+            for (int i = 0; i < A - 1; i++) {
+                cdf += (wide_nonzero(a.mask, mask_at + i) ? expf(l[i] - top) : 0.0f) / sum;
+                action += u >= cdf ? 1 : 0;
+            }
+            if (!wide_nonzero(a.mask, mask_at + action)) action = last_legal;
+        }
+        logprob = (l[action] - top) - logf(sum);
+    }
+    a.action[(int64_t)w * a.action_stride] = action;
+    if (!a.has_record) return;
+    r.actions[at] = action;
+    r.logprobs[at] = logprob;
+    r.values[at] = a.value[j];
+    if (r.logits)
+        for (int i = 0; i < A; i++) r.logits[(size_t)w * kWideMaxActions + i] = l[i];
+}
+
+void launch_agent_act(const AgentActArgs &g, hipStream_t stream)
+{
+    const uint32_t N = g.num_worlds;
+    if (N == 0) return;
+    const bool value_only = g.flags & MRL_AGENT_VALUE_ONLY;
+    hipLaunchKernelGGL(mrl_wide_rows, dim3(1), dim3(1024), 0, stream, g.active, N, g.flags & MRL_AGENT_ALL_ROWS ? 1u : 0u, g.ws.rows,
+                       g.ws.count);
+
+    BookArgs book{};
+    book.obs = g.obs, book.state = g.state, book.mask = g.mask, book.active = g.active;
+    book.action = g.action, book.action_stride = g.action_stride;
+    if (g.record) book.rec = *g.record;
+    book.has_record = g.record ? 1u : 0u;
+    book.row = g.row, book.flags = g.flags, book.D = g.D, book.S = g.S, book.A = g.A, book.num_worlds = N;
+    const uint64_t copied = g.record && !value_only ? (uint64_t)N * (g.S > g.D ? g.S : g.D) : N;
+    const uint32_t book_blocks = (uint32_t)((copied + 255) / 256 < 2048 ? (copied + 255) / 256 : 2048);
+    hipLaunchKernelGGL(mrl_agent_book, dim3(book_blocks), dim3(256), 0, stream, book);
+
+    // critic: parameters from 0; actor: behind them
+    const uint64_t H = kWideHidden;
+    const float *net_params[2] = {g.params, g.params + wide_net_params(g.S, 1)};
+    const WideInput first_in[2] = {g.state, g.obs};
+    const uint32_t first_k[2] = {g.S, g.D}, last_out[2] = {1u, g.A};
+    const uint32_t nets = value_only ? 1u : 2u, row_tiles = (N + kTileRows - 1) / kTileRows;
+    for (uint32_t layer = 0; layer < 4; layer++) {
+        WideLayerArgs la{};
+        la.rows = g.ws.rows, la.count = g.ws.count;
+        la.gather = layer == 0, la.relu = layer < 3;
+        for (uint32_t net = 0; net < nets; net++) {
+            WideLayerNet &n = la.net[net];
+            const float *p = net_params[net];
+            if (layer >= 1) p += (uint64_t)first_k[net] * H + H;
+            if (layer >= 2) p += H * H + H;
+            if (layer >= 3) p += H * H + H;
+            n.K = layer == 0 ? first_k[net] : kWideHidden;
+            n.out_dim = layer == 3 ? last_out[net] : kWideHidden;
+            n.weight = p;
+            n.bias = p + (uint64_t)n.out_dim * n.K;
+            if (layer == 0) {
+                n.in = first_in[net].data, n.in_row_stride = first_in[net].row_stride, n.in_type = first_in[net].type;
+            } else {
+                n.in = g.ws.hidden[(layer - 1) & 1u] + (uint64_t)net * N * H, n.in_row_stride = (int64_t)H, n.in_type = MRL_FLOAT32;
+            }
+            if (layer < 3) {
+                n.out = g.ws.hidden[layer & 1u] + (uint64_t)net * N * H, n.out_stride = kWideHidden;
+            } else if (net == 0) {
+                n.out = g.ws.value, n.out_stride = 1;
+            } else {
+                n.out = g.ws.logits, n.out_stride = kWideMaxActions;
+            }
+        }
+        const uint32_t slabs = layer == 3 ? 1u : kWideHidden / kTileCols;
+        hipLaunchKernelGGL(mrl_wide_layer, dim3(row_tiles, slabs, nets), dim3(kLayerThreads), 0, stream, la);
+    }
+
+    HeadArgs head{};
+    head.rows = g.ws.rows, head.count = g.ws.count, head.logits = g.ws.logits, head.value = g.ws.value;
+    head.mask = g.mask, head.action = g.action, head.action_stride = g.action_stride;
+    if (g.record) head.rec = *g.record;
+    head.has_record = g.record ? 1u : 0u;
+    head.row = g.row, head.flags = g.flags, head.A = g.A, head.num_worlds = N, head.player = g.player, head.step = g.step;
+    head.seed = g.seed;
+    hipLaunchKernelGGL(mrl_agent_head, dim3((N + 63) / 64), dim3(64), 0, stream, head);
+    MRL_HIP(hipGetLastError());
+}
+
+// ---------------------------------------------------------------- update(): reward bookkeeping
+
+// vectoragent.py:197-219 with a lane per world; workgroup b owns worlds [1024 b, 1024 b + 1024) and row b of the totals
+__global__ void __launch_bounds__(1024) mrl_agent_credit(mrl_agent_record r, const float *__restrict__ rewards,
+                                                         const int32_t *__restrict__ dones, uint32_t num_worlds)
+{
+    __shared__ double sum[1024];
+    __shared__ float low[1024], high[1024];
+    __shared__ uint32_t finished[1024];
+    const uint32_t tid = threadIdx.x, w = blockIdx.x * 1024u + tid;
+    double mine = 0.0;
+    float lo = INFINITY, hi = -INFINITY;
+    uint32_t fin = 0;
+    if (w < num_worlds) {
+        const float reward = rewards[w];
+        const bool done = dones[w] != 0;
+        const float running = r.running_rewards[w] + reward;
+        const uint32_t credited = (uint32_t)r.last_active[w];  // a row mrl_agent_act wrote, or the caller's initial 0
+        if (credited < r.num_steps) {
+            float *cell = r.rewards + (uint64_t)credited * num_worlds + w;
+            *cell = *cell + (r.new_game[w] ? 0.0f : reward);
+        }
+        if (done) {
+            r.next_done[w] = 1;
+            r.new_game[w] = 1;
+            mine = running, lo = hi = running, fin = 1;
+        }
+        r.running_rewards[w] = done ? 0.0f : running;
+    }
+    sum[tid] = mine, low[tid] = lo, high[tid] = hi, finished[tid] = fin;
+    __syncthreads();
+    for (uint32_t step = 512; step > 0; step >>= 1) {  // a fixed tree: the same bits on every run
+        if (tid < step) {
+            sum[tid] += sum[tid + step];
+            low[tid] = fminf(low[tid], low[tid + step]);
+            high[tid] = fmaxf(high[tid], high[tid + step]);
+            finished[tid] += finished[tid + step];
+        }
+        __syncthreads();
+    }
+    if (tid == 0 && finished[0]) {
+        double *t = r.totals + 4 * (size_t)blockIdx.x;
+        t[0] += (double)finished[0];
+        t[1] += sum[0];
+        t[2] = t[2] < (double)low[0] ? t[2] : (double)low[0];
+        t[3] = t[3] > (double)high[0] ? t[3] : (double)high[0];
+    }
+}
+
+void launch_agent_credit(const mrl_agent_record &record, const float *rewards, const int32_t *dones, uint32_t num_worlds,
+                         hipStream_t stream)
+{
+    if (num_worlds == 0) return;
+    hipLaunchKernelGGL(mrl_agent_credit, dim3((num_worlds + 1023) / 1024), dim3(1024), 0, stream, record, rewards, dones, num_worlds);
+    MRL_HIP(hipGetLastError());
+}
+
+// ---------------------------------------------------------------- activity-masked advantages
+
+// t* = min over worlds of first[w] (include/mrl_envs.h); *first_step was set to 0x7f7f7f7f in front of the launch
+__global__ void __launch_bounds__(256) mrl_gae_first(const uint8_t *__restrict__ active, const uint8_t *__restrict__ next_active,
+                                                     uint32_t num_steps, uint32_t num_worlds, int32_t *first_step)
+{
+    const uint32_t w = blockIdx.x * 256u + threadIdx.x;
+    int32_t first = 0x7f7f7f7f;
+    if (w < num_worlds) {
+        first = -1;
+        if (next_active[w]) {
+            first = (int32_t)num_steps;
+        } else {
+            for (uint32_t t = num_steps; t-- > 0;)
+                if (active[(uint64_t)t * num_worlds + w]) {
+                    first = (int32_t)t;
+                    break;
+                }
+        }
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const int32_t other = __shfl_xor(first, d);
+        first = other < first ? other : first;
+    }
+    if ((threadIdx.x & 63u) == 0) atomicMin(first_step, first);
+}
+
+__global__ void __launch_bounds__(256) mrl_gae_active(mrl_agent_record r, const float *__restrict__ next_value,
+                                                      const uint8_t *__restrict__ next_active, float gamma, float gamma_lambda,
+                                                      float *__restrict__ advantages, float *__restrict__ returns)
+{
+    const uint32_t w = blockIdx.x * 256u + threadIdx.x, N = r.num_worlds;
+    if (w >= N) return;
+    const int32_t coupled_from = *r.first_step;  // t*: at every t >= t* only the worlds being bootstrapped are computed
+    bool boot = next_active[w] != 0;
+    float nnt = boot ? 1.0f - (r.next_done[w] ? 1.0f : 0.0f) : 0.0f;
+    float nv = boot ? next_value[w] : 0.0f;
+    float last = 0.0f;
+    for (uint32_t t = r.num_steps; t-- > 0;) {
+        const uint64_t at = (uint64_t)t * N + w;
+        const float v = r.values[at];
+        float adv = 0.0f;
+        if (r.active[at]) {
+            if (!boot || (int32_t)t < coupled_from) {
+                const float delta = r.rewards[at] + gamma * nv * nnt - v;
+                adv = last = delta + gamma_lambda * nnt * last;
+            }
+            if (!boot) {  // the reference clears the flag through a view of the mask its last two lines index with: nnt and nv stay 0
+                r.active[at] = 0;
+                boot = true;
+            } else {
+                nnt = 1.0f - r.dones[at];
+                nv = v;
+            }
+        }
+        advantages[at] = adv;
+        returns[at] = adv + v;
+    }
+}
+
+void launch_gae_active(const mrl_agent_record &record, const float *next_value, const uint8_t *next_active, float gamma, float lambda,
+                       float *advantages, float *returns, hipStream_t stream)
+{
+    const uint32_t N = record.num_worlds;
+    if (N == 0) return;
+    const float gamma_lambda = (float)((double)gamma * (double)lambda);
+    MRL_HIP(hipMemsetAsync(record.first_step, 0x7f, sizeof(int32_t), stream));
+    hipLaunchKernelGGL(mrl_gae_first, dim3((N + 255) / 256), dim3(256), 0, stream, record.active, next_active, record.num_steps, N,
+                       record.first_step);
+    hipLaunchKernelGGL(mrl_gae_active, dim3((N + 255) / 256), dim3(256), 0, stream, record, next_value, next_active, gamma, gamma_lambda,
+                       advantages, returns);
+    MRL_HIP(hipGetLastError());
+}
+
+}  // namespace mrl

@@ -28,3 +28,186 @@ class RandomVectorAgent(VectorAgent):
 
     def update(self, rewards: torch.Tensor, dones: torch.Tensor) -> None:
         return None
+
+
+class CleanPPOAgent(VectorAgent):
+    """The reference's PPO agent for Hanabi and the balance beam (/root/reference/pantheonrl_extension/vectoragent.py:116-372;
+    built twice, ego and partner, by scripts/hanabi_train.py and scripts/balance_train.py) with its collection phase on the
+    device: ``get_action`` is ``mrl_agent_act`` on the simulator's own tensors, ``update`` is ``mrl_agent_credit``, and the
+    advantages at the update boundary are ``mrl_gae_active`` -- no host synchronisation per step.  The learning phase is the
+    reference's, in torch autograd, on ``policy.module()``, whose parameters are views of the flat tensor the kernels read.
+
+    Constructor arguments and defaults are the reference's; ``seed`` (extension) seeds the action draws and defaults to a value
+    derived from ``name``.  ``envs`` must be a ``MadronaEnv`` over a Hanabi or balance-beam simulator on the GPU (checked at the
+    first ``get_action``: ``TypeError`` otherwise; there is no torch fallback).  The agent's seat is ``player_num`` -- set by
+    ``env.add_partner_agent(agent, player_num)`` -- or, while that is ``None``, the env's ``ego_ind``.
+
+    Differences from the reference that a caller can see: the per-step ``torch.any(dones)`` is gone, so episode returns are read
+    once per update from device totals (``episode_stats``: count, mean, min and max over the episodes that finished since the last
+    update, where the reference averaged per-step means); worlds where this agent is not the one to act get action 0."""
+
+    def __init__(self, envs, name, device, num_updates, verbose=True, lr=2.5e-4, num_steps=128, anneal_lr=True, gamma=0.99,
+                 gae_lambda=0.95, num_minibatches=4, update_epochs=4, norm_adv=True, clip_coef=0.2, clip_vloss=True, ent_coef=0.01,
+                 vf_coef=0.5, max_grad_norm=0.5, target_kl=None, seed=None):
+        import time
+        import zlib
+
+        import numpy as np
+
+        from ..simulators import WideAgent, WidePolicy
+        self.envs, self.num_envs, self.name, self.device, self.verbose = envs, envs.num_envs, name, torch.device(device), verbose
+        self.lr, self.num_steps, self.anneal_lr, self.gamma, self.gae_lambda = lr, num_steps, anneal_lr, gamma, gae_lambda
+        self.num_minibatches, self.update_epochs, self.norm_adv = num_minibatches, update_epochs, norm_adv
+        self.clip_coef, self.clip_vloss, self.ent_coef, self.vf_coef = clip_coef, clip_vloss, ent_coef, vf_coef
+        self.max_grad_norm, self.target_kl = max_grad_norm, target_kl
+        self.batch_size = int(self.num_envs * self.num_steps)
+        self.minibatch_size = int(self.batch_size // self.num_minibatches)
+        self.seed = zlib.crc32(str(name).encode()) if seed is None else int(seed)
+        self.player_num = None
+
+        self.writer = None
+        if self.verbose:
+            try:
+                from torch.utils.tensorboard import SummaryWriter
+                self.writer = SummaryWriter(f"runs/{name}")
+            except ImportError:  # tensorboard is optional here
+                self.writer = None
+
+        obs_dim = int(np.prod(envs.observation_space.shape))
+        state_dim = int(np.prod(envs.share_observation_space.shape))
+        self.policy = WidePolicy.from_module(WideAgent(obs_dim, state_dim, envs.action_space.n, orthogonal=True), device=self.device)
+        self.agent = self.policy.module()
+        self.optimizer = torch.optim.Adam(self.agent.parameters(), lr=self.lr, eps=1e-5)
+
+        self._obs_dim, self._state_dim = obs_dim, state_dim
+        self._sim = self.record = None  # bound at the first get_action / update, where an unsupported env is refused
+
+        self.global_step, self.step, self.updates, self.num_updates = 0, 0, 1, num_updates
+        self._draws = 0
+        self.start_time = time.time()
+        self.episode_stats = {"episodes": 0, "mean": float("nan"), "min": float("nan"), "max": float("nan")}
+        self.last_losses = {}
+
+    def _attach(self):
+        self._sim = self._check_env()
+        envs = self.envs
+        from ..simulators import AgentRecord
+        self.record = AgentRecord(self.num_steps, self.num_envs, self._obs_dim, self._state_dim, envs.action_space.n,
+                                  envs.static_observations.dtype, envs.static_agent_states.dtype, self.device)
+
+    def _check_env(self):
+        from ..simulators import BalanceBeamSimulator, HanabiSimulator
+        from .vectorenv import MadronaEnv
+        envs = self.envs
+        sim = getattr(envs, "sim", None)
+        if not isinstance(envs, MadronaEnv) or not isinstance(sim, (HanabiSimulator, BalanceBeamSimulator)):
+            raise TypeError("CleanPPOAgent acts through mrl_agent_act: envs must be a MadronaEnv over a HanabiSimulator or a "
+                            f"BalanceBeamSimulator, got {type(envs).__name__} over {type(sim).__name__}; there is no torch fallback")
+        if envs.device.type != "cuda" or self.device.type != "cuda" or self.device.index not in (None, sim.gpu_id):
+            raise TypeError(f"CleanPPOAgent needs the env and the agent on the simulator's GPU (cuda:{sim.gpu_id}); got env device "
+                            f"{envs.device} and agent device {self.device}")
+        return sim
+
+    @property
+    def seat(self):
+        return self.envs.ego_ind if self.player_num is None else self.player_num
+
+    def update(self, rewards, dones):
+        from ..simulators import agent_credit
+        if self.record is None:
+            self._attach()
+        rewards = rewards.reshape(-1)
+        if rewards.dtype != torch.float32 or not rewards.is_contiguous():
+            rewards = rewards.to(torch.float32).contiguous()
+        dones = dones.reshape(-1)
+        if dones.dtype != torch.int32 or not dones.is_contiguous():
+            dones = dones.to(torch.int32).contiguous()
+        agent_credit(self.record, rewards, dones)
+        self.step += 1
+        self.global_step += 1
+
+    def get_action(self, obs, record=True):
+        from ..simulators import agent_act
+        if self.record is None:
+            self._attach()
+        if self.global_step > 0 and self.global_step % self.num_steps == 0 and record:
+            self.step = 0
+            self._learn()
+        agent_act(self._sim, self.seat, self.policy, self.record if record else None, row=self.step, seed=self.seed,
+                  step=self._draws, workspace=self.record.workspace)
+        self._draws += 1
+        return self.envs.static_actions[self.seat]
+
+    def _learn(self):
+        """The update boundary: bootstrap value, advantages (both on the device), then the reference's epochs (:268-330)."""
+        import numpy as np
+
+        from ..simulators import agent_act, gae_active
+        r = self.record
+        if self.anneal_lr:
+            self.optimizer.param_groups[0]["lr"] = (1.0 - (self.updates - 1.0) / self.num_updates) * self.lr
+        agent_act(self._sim, self.seat, self.policy, r, value_only=True)
+        advantages, returns = gae_active(r, self.gamma, self.gae_lambda)
+
+        active = r.active.bool()
+        b_obs, b_states = r.obs[active].float(), r.states[active].float()
+        b_masks, b_actions = r.action_masks[active].bool(), r.actions[active].long()
+        b_logprobs, b_values = r.logprobs[active], r.values[active]
+        b_advantages, b_returns = advantages[active], returns[active]
+        clipfracs = []
+        size = b_values.size(0)
+        v_loss = pg_loss = entropy_loss = old_approx_kl = approx_kl = torch.zeros((), device=self.device)
+        for _ in range(self.update_epochs if size > 1 else 0):
+            inds = torch.randperm(size, device=self.device)  # the reference trains on the whole batch per epoch (:280-283)
+            _, newlogprob, entropy, newvalue = self.agent.get_action_and_value(b_obs[inds], b_states[inds], b_masks[inds], b_actions[inds])
+            logratio = newlogprob - b_logprobs[inds]
+            ratio = logratio.exp()
+            with torch.no_grad():
+                old_approx_kl = (-logratio).mean()
+                approx_kl = ((ratio - 1) - logratio).mean()
+                clipfracs.append(((ratio - 1.0).abs() > self.clip_coef).float().mean())
+            adv = b_advantages[inds]
+            if self.norm_adv:
+                adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+            pg_loss = torch.max(-adv * ratio, -adv * torch.clamp(ratio, 1 - self.clip_coef, 1 + self.clip_coef)).mean()
+            newvalue = newvalue.view(-1)
+            if self.clip_vloss:
+                unclipped = (newvalue - b_returns[inds]) ** 2
+                clipped = b_values[inds] + torch.clamp(newvalue - b_values[inds], -self.clip_coef, self.clip_coef)
+                v_loss = 0.5 * torch.max(unclipped, (clipped - b_returns[inds]) ** 2).mean()
+            else:
+                v_loss = 0.5 * ((newvalue - b_returns[inds]) ** 2).mean()
+            entropy_loss = entropy.mean()
+            loss = pg_loss - self.ent_coef * entropy_loss + v_loss * self.vf_coef
+            self.optimizer.zero_grad()
+            loss.backward()
+            torch.nn.utils.clip_grad_norm_(self.agent.parameters(), self.max_grad_norm)
+            self.optimizer.step()
+            if self.target_kl is not None and approx_kl > self.target_kl:
+                break
+
+        # the one host read of the update: losses and the episode totals the credit launches kept
+        y_pred, y_true = b_values.cpu().numpy(), b_returns.cpu().numpy()
+        var_y = np.var(y_true) if size else 0.0
+        episodes, total, low, high = r.episode_totals()
+        r.clear_totals()
+        if episodes:
+            self.episode_stats = {"episodes": episodes, "mean": total / episodes, "min": low, "max": high}
+        self.last_losses = {
+            "value_loss": float(v_loss.detach()), "policy_loss": float(pg_loss.detach()), "entropy": float(entropy_loss.detach()),
+            "old_approx_kl": float(old_approx_kl), "approx_kl": float(approx_kl),
+            "clipfrac": float(torch.stack(clipfracs).mean()) if clipfracs else 0.0,
+            "explained_variance": float("nan") if var_y == 0 else float(1 - np.var(y_true - y_pred) / var_y),
+            "learning_rate": self.optimizer.param_groups[0]["lr"], "samples": size,
+        }
+        if self.writer is not None:
+            import time
+            if episodes:
+                self.writer.add_scalar("charts/episodic_return", total / episodes, self.global_step)
+                self.writer.add_scalar("charts/min_episodic_return", low, self.global_step)
+                self.writer.add_scalar("charts/max_episodic_return", high, self.global_step)
+            for key, value in self.last_losses.items():
+                group = "charts" if key == "learning_rate" else "losses"
+                self.writer.add_scalar(f"{group}/{key}", value, self.global_step)
+            self.writer.add_scalar("charts/SPS", int(self.global_step / (time.time() - self.start_time)), self.global_step)
+        self.updates += 1

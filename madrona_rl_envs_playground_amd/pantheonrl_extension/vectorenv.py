@@ -133,6 +133,8 @@ class VectorMultiAgentEnv(ABC):
     def add_partner_agent(self, agent: VectorAgent, player_num: int = 1) -> None:
         self._roster.ego_ind = self.ego_ind
         self._roster.add(agent, player_num)
+        if hasattr(agent, "player_num"):  # an agent that acts on the simulator's tensors itself needs to know its seat
+            agent.player_num = player_num
 
     def set_partnerid(self, agent_id: int, player_num: int = 1) -> None:
         self._roster.ego_ind = self.ego_ind

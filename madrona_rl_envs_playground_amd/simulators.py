@@ -245,6 +245,182 @@ class MlpPolicy:
         return agent
 
 
+def _wide_mlp(inputs, outputs, hidden=_lib.WIDE_HIDDEN):
+    nn = torch.nn
+    return nn.Sequential(nn.Linear(inputs, hidden), nn.ReLU(), nn.Linear(hidden, hidden), nn.ReLU(), nn.Linear(hidden, hidden), nn.ReLU(),
+                         nn.Linear(hidden, outputs))
+
+
+class WideAgent(torch.nn.Module):
+    """The actor-critic of the reference's ``CleanPPOAgent`` by shape and method names (pantheonrl_extension/vectoragent.py:66-113,
+    ``CleanRLNetwork``): critic from the S-wide state to one value, actor from the D-wide observation to A logits, three hidden
+    ReLU layers of width 512 each.  ``orthogonal=True`` initialises like the reference (orthogonal weights of gain sqrt 2, 0.01
+    for the two output layers, zero biases); otherwise torch's default."""
+
+    def __init__(self, obs_dim, state_dim, num_actions, orthogonal=False):
+        super().__init__()
+        self.critic = _wide_mlp(state_dim, 1)
+        self.actor = _wide_mlp(obs_dim, num_actions)
+        if orthogonal:
+            for net in (self.critic, self.actor):
+                for i in (0, 2, 4, 6):
+                    torch.nn.init.orthogonal_(net[i].weight, 0.01 if i == 6 else 2.0 ** 0.5)
+                    torch.nn.init.constant_(net[i].bias, 0.0)
+
+    def get_value(self, x):
+        return self.critic(x)
+
+    def get_action_and_value(self, x, state, action_mask, action=None):
+        logits = self.actor(x).masked_fill(torch.logical_not(action_mask), -float("inf"))
+        dist = torch.distributions.Categorical(logits=logits)
+        if action is None:
+            action = dist.sample()
+        return action, dist.log_prob(action), dist.entropy(), self.critic(state)
+
+
+class WidePolicy:
+    """The parameters ``mrl_agent_act`` runs: one flat float32 tensor ``params`` in the order of
+    ``parameters_to_vector(agent.parameters())`` for a ``WideAgent`` (``mrl_wide_policy``).  ``module()`` returns a ``WideAgent``
+    whose parameters are VIEWS into ``params``: a torch optimizer's in-place step on them is what the kernels read next, with no
+    copy in between (so there is no ``load_``)."""
+
+    def __init__(self, obs_dim, state_dim, num_actions, device="cuda:0"):
+        self.obs_dim, self.state_dim, self.num_actions = int(obs_dim), int(state_dim), int(num_actions)
+        if not 1 <= self.num_actions <= _lib.WIDE_MAX_ACTIONS or self.obs_dim < 1 or self.state_dim < 1:
+            raise ValueError(f"need 1 <= num_actions <= {_lib.WIDE_MAX_ACTIONS} and obs_dim, state_dim >= 1")
+        self.params = torch.zeros(self.num_params, dtype=torch.float32, device=torch.device(device))
+        self._module = None
+
+    @property
+    def num_params(self):
+        return int(_lib.lib().mrl_wide_policy_num_params(self.obs_dim, self.state_dim, self.num_actions))
+
+    @staticmethod
+    def _shape_of(agent):
+        """(obs_dim, state_dim, num_actions) of an agent of the expected form; ValueError otherwise."""
+        nn, h = torch.nn, _lib.WIDE_HIDDEN
+        for name in ("critic", "actor"):
+            net = getattr(agent, name, None)
+            if (not isinstance(net, nn.Sequential) or len(net) != 7 or not all(isinstance(net[i], nn.Linear) for i in (0, 2, 4, 6)) or
+                    not all(isinstance(net[i], nn.ReLU) for i in (1, 3, 5)) or any(net[i].bias is None for i in (0, 2, 4, 6))):
+                raise ValueError(f"agent.{name} must be Sequential(Linear, ReLU, Linear, ReLU, Linear, ReLU, Linear) with biases")
+            shapes = [(net[i].in_features, net[i].out_features) for i in (0, 2, 4, 6)]
+            if shapes != [(shapes[0][0], h), (h, h), (h, h), (h, shapes[3][1])]:
+                raise ValueError(f"agent.{name}'s layers are {shapes}; the hidden width must be {h}")
+        if agent.critic[6].out_features != 1:
+            raise ValueError("agent.critic must end in one value")
+        return agent.actor[0].in_features, agent.critic[0].in_features, agent.actor[6].out_features
+
+    @classmethod
+    def from_module(cls, agent, device=None):
+        """A policy of ``agent``'s shape holding a copy of its parameters (``device``: default the agent's own)."""
+        d, s, a = cls._shape_of(agent)
+        policy = cls(d, s, a, device if device is not None else agent.critic[0].weight.device)
+        with torch.no_grad():
+            policy.params.copy_(torch.cat([p.detach().reshape(-1) for net in (agent.critic, agent.actor) for p in net.parameters()]))
+        return policy
+
+    def module(self):
+        """The ``WideAgent`` whose parameters alias ``params`` (one object per policy)."""
+        if self._module is None:
+            agent = WideAgent(self.obs_dim, self.state_dim, self.num_actions)
+            at = 0
+            for p in agent.parameters():  # critic first, then actor: the order of the flat array
+                p.data = self.params[at:at + p.numel()].view(p.shape)
+                at += p.numel()
+            assert at == self.params.numel()
+            self._module = agent
+        return self._module
+
+    def desc(self):
+        return _lib.WidePolicyDesc(self.params.data_ptr(), self.obs_dim, self.state_dim, self.num_actions)
+
+
+class AgentRecord:
+    """The buffers of one ``CleanPPOAgent`` (``mrl_agent_record``): torch tensors by name plus the ctypes struct over them."""
+
+    def __init__(self, num_steps, num_worlds, obs_dim, state_dim, num_actions, obs_dtype, state_dtype, device, logits=False):
+        t, n = int(num_steps), int(num_worlds)
+        z = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=device)  # noqa: E731
+        self.num_steps, self.num_worlds = t, n
+        self.obs, self.states = z((t, n, obs_dim), obs_dtype), z((t, n, state_dim), state_dtype)
+        self.action_masks, self.active = z((t, n, num_actions), torch.uint8), z((t, n), torch.uint8)
+        self.actions = z((t, n), torch.int32)
+        self.logprobs, self.values, self.dones, self.rewards = (z((t, n), torch.float32) for _ in range(4))
+        self.last_active = z((n,), torch.int32)
+        self.new_game, self.next_done = z((n,), torch.uint8), z((n,), torch.uint8)
+        self.running_rewards = z((n,), torch.float32)
+        self.totals = z(((n + 1023) // 1024, 4), torch.float64)
+        self.next_value, self.next_active = z((n,), torch.float32), z((n,), torch.uint8)
+        self.first_step = z((1,), torch.int32)
+        self.logits = z((n, _lib.WIDE_MAX_ACTIONS), torch.float32) if logits else None
+        self.advantages, self.returns = z((t, n), torch.float32), z((t, n), torch.float32)
+        self.workspace = torch.empty(int(_lib.lib().mrl_agent_workspace_bytes(n)) if device.type == "cuda" else 0, dtype=torch.uint8,
+                                     device=device)
+        self.clear_totals()
+        self.struct = _lib.AgentRecord(*[getattr(self, name).data_ptr() if getattr(self, name) is not None else None
+                                         for name in _lib.AGENT_RECORD_BUFFERS], t, n)
+
+    def clear_totals(self):
+        self.totals[:, 0:2] = 0.0
+        self.totals[:, 2] = float("inf")
+        self.totals[:, 3] = -float("inf")
+
+    def episode_totals(self):
+        """(finished episodes, sum of their returns, minimum, maximum) since the last ``clear_totals`` -- one host read."""
+        t = self.totals.cpu()
+        return int(t[:, 0].sum()), float(t[:, 1].sum()), float(t[:, 2].min()), float(t[:, 3].max())
+
+
+def agent_act(sim, player, policy, record=None, row=0, seed=0, step=0, greedy=False, all_rows=False, value_only=False, workspace=None):
+    """``mrl_agent_act`` on torch's current stream of the simulator's device: player ``player`` of a Hanabi or balance-beam
+    simulator acts under ``policy`` (a ``WidePolicy``) on the simulator's tensors as they stand; with ``record`` (an
+    ``AgentRecord``) row ``row`` of its buffers is written.  ``workspace``: default the record's."""
+    if not isinstance(policy, WidePolicy):
+        raise ValueError("policy must be a WidePolicy")
+    p = policy.params
+    if not p.is_cuda or p.device.index != sim.gpu_id or p.dtype != torch.float32 or not p.is_contiguous() or p.numel() != policy.num_params:
+        raise ValueError(f"policy.params must be a contiguous float32 tensor of num_params elements on cuda:{sim.gpu_id}")
+    if workspace is None:
+        if record is None:
+            raise ValueError("give a workspace (uint8, mrl_agent_workspace_bytes) or a record")
+        workspace = record.workspace
+    flags = (_lib.POLICY_GREEDY if greedy else 0) | (_lib.AGENT_ALL_ROWS if all_rows else 0) | (_lib.AGENT_VALUE_ONLY if value_only else 0)
+    desc = policy.desc()
+    rc = sim._L.mrl_agent_act(sim._handle, int(player), ctypes.byref(desc), ctypes.byref(record.struct) if record is not None else None,
+                              int(row), int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF, flags, workspace.data_ptr(),
+                              _stream_ptr(sim.gpu_id))
+    if rc:
+        _lib.check(rc)
+
+
+def agent_credit(record, rewards, dones):
+    """``mrl_agent_credit``: ``rewards`` float32 (N), ``dones`` int32 (N), contiguous, on the record's GPU."""
+    device = record.rewards.device
+    for t, dtype in ((rewards, torch.float32), (dones, torch.int32)):
+        if t.device != device or t.dtype != dtype or not t.is_contiguous() or t.numel() != record.num_worlds:
+            raise ValueError("rewards / dones must be contiguous float32 / int32 tensors of num_worlds elements on the record's GPU")
+    rc = _lib.lib().mrl_agent_credit(ctypes.byref(record.struct), rewards.data_ptr(), dones.data_ptr(), record.num_worlds, device.index,
+                                     _stream_ptr(device.index))
+    if rc:
+        _lib.check(rc)
+
+
+def gae_active(record, gamma, gae_lambda, next_value=None, next_active=None):
+    """``mrl_gae_active`` over ``record``: fills and returns ``(record.advantages, record.returns)``; clears the ``active`` flag of the
+    rows that only carried a bootstrap.  ``next_value`` / ``next_active``: default the record's own (a VALUE_ONLY act wrote them)."""
+    nv = record.next_value if next_value is None else next_value
+    na = record.next_active if next_active is None else next_active
+    device = record.rewards.device
+    if nv.dtype != torch.float32 or na.dtype != torch.uint8 or nv.device != device or na.device != device or \
+            nv.numel() != record.num_worlds or na.numel() != record.num_worlds or not nv.is_contiguous() or not na.is_contiguous():
+        raise ValueError("next_value / next_active must be contiguous float32 / uint8 tensors of num_worlds elements on the record's GPU")
+    _lib.check(_lib.lib().mrl_gae_active(ctypes.byref(record.struct), nv.data_ptr(), na.data_ptr(), float(gamma), float(gae_lambda),
+                                         record.advantages.data_ptr(), record.returns.data_ptr(), device.index,
+                                         _stream_ptr(device.index)))
+    return record.advantages, record.returns
+
+
 # what ``rollout_policy`` fills, the names of scripts/cartpole_train_torch.py:179-192: (T, N, D), (T, N) x 5, (N, D), (N), (N)
 Rollout = collections.namedtuple("Rollout", "obs actions logprobs values rewards dones next_obs next_value next_done")
 

@@ -1,0 +1,220 @@
+"""CPU: the public surface of the device-side CleanPPOAgent collection phase (mrl_agent_act, mrl_agent_credit,
+mrl_gae_active; WidePolicy; CleanPPOAgent) and the yardsticks tests/test_gpu_wide_agent.py measures against: the float64 twin
+against torch float32, the draws of the GPU cases, and the reference's own advantage pass and reward bookkeeping
+(tests/golden/cleanppo_gae.npz, recorded from the reference's class by tests/golden/make_cleanppo_golden.py)."""
+import inspect
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+import torch
+from conftest import load_golden
+
+import wide_twin as twin
+
+NEW_SYMBOLS = ["mrl_wide_policy_num_params", "mrl_agent_workspace_bytes", "mrl_agent_act", "mrl_agent_credit", "mrl_gae_active"]
+
+
+def reference_shaped_network(d, s, a):
+    """a network of the reference's CleanRLNetwork shape, built here from torch alone"""
+    nn = torch.nn
+
+    def net(inputs, outputs):
+        return nn.Sequential(nn.Linear(inputs, 512), nn.ReLU(), nn.Linear(512, 512), nn.ReLU(), nn.Linear(512, 512), nn.ReLU(),
+                             nn.Linear(512, outputs))
+
+    module = nn.Module()
+    module.critic = net(s, 1)
+    module.actor = net(d, a)
+    return module
+
+
+def test_symbols(hip_lib):
+    from madrona_rl_envs_playground_amd import _lib
+    for name in NEW_SYMBOLS:
+        assert name in _lib.SYMBOLS
+        assert hasattr(hip_lib, name)
+    assert hip_lib.mrl_abi_version() == 4
+
+
+@pytest.mark.parametrize("d,s,a", [(7, 7, 4), (658, 783, 20), (1, 1, 1), (3, 9, 64)])
+def test_parameter_count_and_order(d, s, a, hip_lib):
+    from madrona_rl_envs_playground_amd.simulators import WidePolicy
+    torch.manual_seed(d)
+    network = reference_shaped_network(d, s, a)
+    vector = torch.nn.utils.parameters_to_vector(network.parameters()).detach()
+    assert hip_lib.mrl_wide_policy_num_params(d, s, a) == vector.numel()
+    policy = WidePolicy.from_module(network, device="cpu")
+    assert policy.num_params == vector.numel() and (policy.obs_dim, policy.state_dim, policy.num_actions) == (d, s, a)
+    assert torch.equal(policy.params, vector)
+    # the order by name: the critic's first weight leads, the actor's last bias ends
+    assert torch.equal(policy.params[:512 * s].view(512, s), network.critic[0].weight.detach())
+    assert torch.equal(policy.params[-a:], network.actor[6].bias.detach())
+    assert hip_lib.mrl_agent_workspace_bytes(33) >= 33 * (4 + 2 * 2 * 512 * 4 + 64 * 4 + 4)
+
+
+def test_policy_shape_refusals(hip_lib):
+    from madrona_rl_envs_playground_amd.simulators import WidePolicy
+    with pytest.raises(ValueError):
+        WidePolicy(7, 7, 65, device="cpu")
+    with pytest.raises(ValueError):
+        WidePolicy(0, 7, 4, device="cpu")
+    narrow = reference_shaped_network(7, 7, 4)
+    narrow.actor[2] = torch.nn.Linear(512, 256)
+    with pytest.raises(ValueError):
+        WidePolicy.from_module(narrow, device="cpu")
+    assert not hasattr(WidePolicy, "load_")
+
+
+def test_module_parameters_are_views_of_params(hip_lib):
+    from madrona_rl_envs_playground_amd.simulators import WidePolicy
+    torch.manual_seed(5)
+    policy = WidePolicy.from_module(reference_shaped_network(7, 9, 4), device="cpu")
+    module = policy.module()
+    assert policy.module() is module
+    storage = policy.params.untyped_storage().data_ptr()
+    at = policy.params.data_ptr()
+    for p in module.parameters():
+        assert p.untyped_storage().data_ptr() == storage and p.data_ptr() == at
+        at += 4 * p.numel()
+    assert at == policy.params.data_ptr() + 4 * policy.params.numel()
+    before = policy.params.clone()
+    optimizer = torch.optim.Adam(module.parameters(), lr=1e-2, eps=1e-5)
+    x = torch.ones(3, 7)
+    state = torch.ones(3, 9)
+    _, logp, _, value = module.get_action_and_value(x, state, torch.ones(3, 4, dtype=torch.bool), torch.zeros(3, dtype=torch.long))
+    (logp.sum() + value.sum()).backward()
+    optimizer.step()
+    assert not torch.equal(policy.params, before)  # the optimizer's in-place step is what the kernels read next
+    assert torch.equal(policy.params, torch.nn.utils.parameters_to_vector(module.parameters()).detach())
+
+
+def test_draws_lie_on_the_24_bit_grid():
+    u = twin.draws(12345, 7, 4096, 1)
+    assert np.all(u >= 0) and np.all(u < 1) and np.all(u * 2 ** 24 == np.floor(u * 2 ** 24))
+    assert np.array_equal(u.astype(np.float32).astype(np.float64), u)
+    assert not np.array_equal(u, twin.draws(12345, 7, 4096, 0)) and not np.array_equal(u, twin.draws(12345, 8, 4096, 1))
+
+
+@pytest.mark.parametrize("weights", sorted(twin.WEIGHTS))
+@pytest.mark.parametrize("game", ["balance", "hanabi_very_small", "hanabi_full"])
+def test_twin_against_torch_float32(game, weights):
+    """The twin and torch's float32 evaluation are the same function: their distance d is a float32 rounding distance (the
+    bound: K <= 783 terms of size <= |x w| each rounded to 2^-24 relative, four layers), and away from the boundaries they
+    choose the same actions."""
+    agent = twin.make_agent(game, weights)
+    inputs = twin.case_inputs(game, 65, twin.case_seed(game, 65, weights))
+    d_value, d_logp = twin.margins(agent, inputs)
+    print(f"{game} {weights}: d_value {d_value:.3e} d_logp {d_logp:.3e}")
+    assert 0 < d_value < 1e-4 and 0 < d_logp < 1e-3
+    u = twin.draws(1, 0, 65, 0)
+    out = twin.act(twin.flat(agent), inputs["obs"], inputs["state"], inputs["mask"], u)
+    _, lp32 = twin.torch_forward32(agent, inputs["obs"], inputs["state"], inputs["mask"])
+    cdf32 = np.cumsum(np.exp(lp32), axis=1)[:, :-1]
+    actions32 = (u[:, None] >= cdf32).sum(axis=1)
+    keep = ~twin.near_boundary(out["cdf"], u)
+    assert np.array_equal(actions32[keep], out["actions"][keep])
+    legal = inputs["mask"] != 0
+    assert legal[np.arange(65), out["actions"]].all() and legal[np.arange(65), out["greedy"]].all()
+    assert np.isneginf(out["logp"][~legal]).all()
+
+
+@pytest.mark.parametrize("weights", sorted(twin.WEIGHTS))
+@pytest.mark.parametrize("game,n", twin.CASES)
+def test_gpu_cases_draw_away_from_boundaries(game, n, weights):
+    """The rows a GPU action comparison may skip: at most 1 % of a case's rows lie within 1e-5 of a boundary."""
+    seed = twin.case_seed(game, n, weights)
+    agent = twin.make_agent(game, weights)
+    inputs = twin.case_inputs(game, n, seed)
+    u = twin.draws(seed, 0, n, 0)
+    near = twin.near_boundary(twin.act(twin.flat(agent), inputs["obs"], inputs["state"], inputs["mask"], u)["cdf"], u)
+    assert near.sum() <= 0.01 * n, f"{near.sum()} of {n} rows are near a boundary"
+
+
+FIXTURE_CASES = [(regime, n) for n in (5, 70) for regime in ("coupled", "together")]
+
+
+def fixture_case(regime, n):
+    g = load_golden("cleanppo_gae.npz")
+    return {k[len(f"{regime}_{n}_"):]: v for k, v in g.items() if k.startswith(f"{regime}_{n}_")}
+
+
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+@pytest.mark.parametrize("regime,n", FIXTURE_CASES)
+def test_advantage_pass_equals_the_reference_bit_for_bit(regime, n):
+    f = fixture_case(regime, n)
+    num_steps = f["before_active"].shape[0]
+    assert num_steps == 8
+    adv, ret, active = twin.gae_active(f["before_rewards"], f["before_values"], f["before_dones"], f["before_active"],
+                                       f["before_next_done"], f["next_value"], f["activity"][num_steps], float(f["gamma"]),
+                                       float(f["gae_lambda"]))
+    assert same_bits(adv, f["advantages"]) and same_bits(ret, f["returns"])
+    assert np.array_equal(active, f["active_after"])
+    # the fixture holds the regime it claims: the coupling acts below T - 1, or not at all
+    boot = f["activity"][num_steps]
+    first = np.where(boot, num_steps, np.where(f["before_active"].any(axis=0),
+                                               num_steps - 1 - f["before_active"][::-1].argmax(axis=0), -1))
+    if regime == "coupled":
+        assert 0 <= first.min() < num_steps - 1 and boot.any() and not boot.all()
+        skipped = f["before_active"] & f["active_after"] & (f["advantages"] == 0) & (np.arange(num_steps)[:, None] >= first.min())
+        assert skipped.any()  # an already bootstrapped, active world was left at 0
+        assert (f["before_active"] != f["active_after"]).any()
+    else:
+        assert first.min() == num_steps and np.array_equal(f["before_active"], f["active_after"])
+    assert f["dones_in"].any()  # episode ends
+
+
+@pytest.mark.parametrize("regime,n", FIXTURE_CASES)
+def test_credit_step_equals_the_reference(regime, n):
+    """The per-world arrays after every update() bit for bit, and the reward buffer in every cell (last_active[w], w).  The other
+    cells differ on purpose: the reference's indexed add selects whole rows (include/mrl_envs.h, mrl_agent_credit)."""
+    f = fixture_case(regime, n)
+    rec = twin.new_record(8, n)
+    worlds = np.arange(n)
+    for t in range(8):
+        twin.book(rec, t, f["activity"][t])
+        twin.credit(rec, f["rewards_in"][t], f["dones_in"][t])
+        assert same_bits(rec["running_rewards"], f["trace_running_rewards"][t])
+        for name in ("next_done", "new_game", "last_active"):
+            assert np.array_equal(rec[name].astype(np.int64), f["trace_" + name][t].astype(np.int64)), name
+        own = rec["last_active"]
+        assert same_bits(rec["rewards"][own, worlds], f["trace_rewards"][t][own, worlds])
+    assert same_bits(rec["dones"], f["before_dones"]) and np.array_equal(rec["active"] != 0, f["before_active"])
+    if regime == "together":
+        assert same_bits(rec["rewards"], f["before_rewards"])
+    finished = f["dones_in"].sum()
+    assert rec["totals"][:, 0].sum() == finished
+
+
+def reference_signature():
+    """names and defaults of the reference's CleanPPOAgent.__init__ (pantheonrl_extension/vectoragent.py:117-136)"""
+    return [("envs", None), ("name", None), ("device", None), ("num_updates", None), ("verbose", True), ("lr", 2.5e-4), ("num_steps", 128),
+            ("anneal_lr", True), ("gamma", 0.99), ("gae_lambda", 0.95), ("num_minibatches", 4), ("update_epochs", 4), ("norm_adv", True),
+            ("clip_coef", 0.2), ("clip_vloss", True), ("ent_coef", 0.01), ("vf_coef", 0.5), ("max_grad_norm", 0.5), ("target_kl", None)]
+
+
+def test_agent_signature_and_refusal_of_other_envs(hip_lib):
+    from madrona_rl_envs_playground_amd.pantheonrl_extension import CleanPPOAgent, VectorAgent
+    from madrona_rl_envs_playground_amd.pantheonrl_extension.vectorobservation import VectorObservation
+    parameters = list(inspect.signature(CleanPPOAgent.__init__).parameters.values())[1:]
+    for got, (name, default) in zip(parameters, reference_signature()):
+        assert got.name == name
+        assert got.default == default if name not in ("envs", "name", "device", "num_updates") else got.default is inspect.Parameter.empty
+    assert [p.name for p in parameters[len(reference_signature()):]] == ["seed"]
+    assert issubclass(CleanPPOAgent, VectorAgent)
+    space = SimpleNamespace(shape=(7,))
+    envs = SimpleNamespace(num_envs=3, observation_space=space, share_observation_space=space, action_space=SimpleNamespace(n=4, shape=()),
+                           ego_ind=0)
+    agent = CleanPPOAgent(envs, "stub", torch.device("cpu"), num_updates=1, verbose=False, num_steps=4)
+    assert agent.policy.params.numel() == hip_lib.mrl_wide_policy_num_params(7, 7, 4)
+    assert agent.seed == CleanPPOAgent(envs, "stub", torch.device("cpu"), num_updates=1, verbose=False).seed  # derived from the name
+    assert CleanPPOAgent(envs, "stub", "cpu", 1, verbose=False, seed=9).seed == 9
+    x = torch.zeros(3, 7)
+    with pytest.raises(TypeError, match="MadronaEnv"):
+        agent.get_action(VectorObservation(torch.ones(3, dtype=torch.bool), x, x, torch.ones(3, 4, dtype=torch.bool)))
+    with pytest.raises(TypeError, match="MadronaEnv"):
+        agent.update(torch.zeros(3), torch.zeros(3))

@@ -1,0 +1,228 @@
+"""Float64 numpy twin of the device-side wide-policy act (``mrl_agent_act``: forward pass, head, sampling), the same function in
+torch float32 -- whose distance from the twin sets the tests' margins --, the synthetic inputs the GPU tests write into a
+simulator's tensors, and float32 numpy restatements of ``mrl_agent_credit`` and ``mrl_gae_active`` that follow
+include/mrl_envs.h operation for operation.  Nothing here touches a GPU."""
+import numpy as np
+import torch
+
+from madrona_rl_envs_playground_amd import hanabi_spec
+from madrona_rl_envs_playground_amd.envs.hanabi_env import config_choice
+from madrona_rl_envs_playground_amd.simulators import WideAgent, random_hash
+
+H = 512
+SIZES = (1, 31, 33, 65, 257)
+AGENT_SEED = 11
+WEIGHTS = {"orthogonal": 1.0, "peaked": 300.0}  # the factor on the actor's output layer: 300 moves the probabilities far from uniform
+
+
+def dims(game):
+    """(D, S, A) of ``game``: "balance" or "hanabi_<config>" """
+    if game == "balance":
+        return 7, 7, 4
+    config = config_choice[game[len("hanabi_"):]]
+    return hanabi_spec.observation_size(config), hanabi_spec.state_size(config), hanabi_spec.num_moves(config)
+
+
+# every forward case of tests/test_gpu_wide_agent.py: (game, worlds); each runs with both weight sets
+CASES = [(game, n) for game in ("balance", "hanabi_very_small") for n in SIZES] + [("hanabi_full", 65)]
+
+
+def case_seed(game, n, weights):
+    """seed of the inputs and of the draws of one case"""
+    return 7919 * n + 104729 * sorted(WEIGHTS).index(weights) + {"balance": 1, "hanabi_very_small": 2, "hanabi_full": 3}[game]
+
+
+def make_agent(game, weights, seed=AGENT_SEED):
+    """A ``WideAgent`` of the game's shape, initialised as the reference's ``layer_init`` does under ``torch.manual_seed``;
+    the actor's output layer is multiplied by ``WEIGHTS[weights]``."""
+    d, s, a = dims(game)
+    torch.manual_seed(seed)
+    agent = WideAgent(d, s, a, orthogonal=True)
+    with torch.no_grad():
+        agent.actor[6].weight.mul_(WEIGHTS[weights])
+        for net in (agent.critic, agent.actor):  # (the reference's biases start at zero: move them, or a bias mix-up goes unseen)
+            for i in (0, 2, 4, 6):
+                net[i].bias.uniform_(-0.1, 0.1)
+    return agent
+
+
+def flat(agent):
+    return torch.nn.utils.parameters_to_vector(agent.parameters()).detach().numpy()
+
+
+def case_inputs(game, n, seed, player=0):
+    """What a forward test writes into the simulator's tensors for ``player``: ``state`` (n, S) and ``obs`` = its first D entries
+    (Hanabi's OBSERVATION is the head of the STATE row; the balance beam's state is its observation), ``mask`` (n, A) with at
+    least one legal action per world, ``active`` (n).  Hanabi values are 0 / 1, the balance beam's 0..8."""
+    d, s, a = dims(game)
+    rng = np.random.default_rng(seed)
+    if game == "balance":
+        state = rng.integers(0, 9, size=(n, s)).astype(np.int32)
+    else:
+        state = (rng.uniform(size=(n, s)) < 0.3).astype(np.int8)
+    mask = (rng.uniform(size=(n, a)) < 0.6).astype(np.int32)
+    mask[np.arange(n), rng.integers(0, a, size=n)] = 1
+    active = (rng.uniform(size=n) < 0.55).astype(np.int32)
+    active[0] = 1  # (N = 1 computes something)
+    return {"obs": state[:, :d], "state": state, "mask": mask, "active": active}
+
+
+def draws(seed, step, n, player):
+    """u of every world: ``(hash >> 8) * 2^-24`` of (seed, step, world, player), float64 (exact)"""
+    h = random_hash(seed, step, np.arange(n), np.full(n, player))
+    return (h >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
+
+
+def split(params, d, s, a):
+    p = np.asarray(params, np.float64)
+    at, nets = 0, {}
+    for name, first, out in (("critic", s, 1), ("actor", d, a)):
+        layers = []
+        for rows, cols in ((H, first), (H, H), (H, H), (out, H)):
+            w = p[at:at + rows * cols].reshape(rows, cols)
+            at += rows * cols
+            layers.append((w, p[at:at + rows]))
+            at += rows
+        nets[name] = layers
+    assert at == p.size
+    return nets
+
+
+def forward(params, obs, state, num_actions):
+    """values (n,), logits (n, A) in float64"""
+    obs, state = np.asarray(obs, np.float64), np.asarray(state, np.float64)
+    nets = split(params, obs.shape[1], state.shape[1], num_actions)
+    out = []
+    for name, x in (("critic", state), ("actor", obs)):
+        for k, (w, b) in enumerate(nets[name]):
+            x = x @ w.T + b
+            if k < 3:
+                x = np.maximum(x, 0.0)
+        out.append(x)
+    return out[0][:, 0], out[1]
+
+
+def act(params, obs, state, mask, u):
+    """The head of include/mrl_envs.h in float64.  ``values``; ``logits``; ``logp`` (n, A), -inf where illegal; ``cdf`` (n, A - 1) the
+    boundaries p_0 + ... + p_a; ``actions``; ``greedy`` the first legal arg-max."""
+    legal = np.asarray(mask) != 0
+    values, logits = forward(params, obs, state, legal.shape[1])
+    masked = np.where(legal, logits, -np.inf)
+    top = masked.max(axis=1, keepdims=True)
+    e = np.where(legal, np.exp(masked - top), 0.0)
+    total = e.sum(axis=1, keepdims=True)
+    cdf = np.cumsum(e / total, axis=1)[:, :-1]
+    actions = (np.asarray(u, np.float64)[:, None] >= cdf).sum(axis=1)
+    last_legal = legal.shape[1] - 1 - legal[:, ::-1].argmax(axis=1)
+    actions = np.where(legal[np.arange(len(legal)), actions], actions, last_legal).astype(np.int32)
+    return {"values": values, "logits": logits, "logp": (masked - top) - np.log(total), "cdf": cdf, "actions": actions,
+            "greedy": masked.argmax(axis=1).astype(np.int32)}
+
+
+def near_boundary(cdf, u, tol=1e-5):
+    """rows whose draw lies within ``tol`` of a boundary: the only ones whose action a float32 evaluation may decide otherwise"""
+    return (np.abs(np.asarray(u, np.float64)[:, None] - cdf) <= tol).any(axis=1)
+
+
+def torch_forward32(agent, obs, state, mask):
+    """torch's float32 CPU evaluation of ``agent``, as the reference calls it: values (n,), log-probabilities (n, A), float64 arrays"""
+    with torch.no_grad():
+        x = torch.from_numpy(np.ascontiguousarray(obs)).float()
+        s = torch.from_numpy(np.ascontiguousarray(state)).float()
+        legal = torch.from_numpy(np.asarray(mask) != 0)
+        logits = agent.actor(x).masked_fill(torch.logical_not(legal), -float("inf"))
+        return agent.critic(s)[:, 0].double().numpy(), torch.distributions.Categorical(logits=logits).logits.double().numpy()
+
+
+def margins(agent, inputs, actions=None):
+    """d per kind on one case's inputs: the largest distance between torch float32 and the twin over the rows, for the values
+    and for the log-probability of ``actions`` (default: every legal action)."""
+    v32, lp32 = torch_forward32(agent, inputs["obs"], inputs["state"], inputs["mask"])
+    twin = act(flat(agent), inputs["obs"], inputs["state"], inputs["mask"], np.zeros(len(v32)))
+    legal = inputs["mask"] != 0
+    if actions is None:
+        d_logp = np.abs(np.where(legal, lp32 - np.where(legal, twin["logp"], 0.0), 0.0)).max()
+    else:
+        rows = np.arange(len(v32))
+        d_logp = np.abs(lp32[rows, actions] - twin["logp"][rows, actions]).max()
+    return float(np.abs(v32 - twin["values"]).max()), float(d_logp)
+
+
+# ---------------------------------------------------------------- the record's bookkeeping, float32, operation for operation
+
+def new_record(num_steps, n):
+    f, z = np.float32, np.zeros
+    return {"active": z((num_steps, n), np.uint8), "dones": z((num_steps, n), f), "rewards": z((num_steps, n), f),
+            "last_active": z(n, np.int32), "new_game": z(n, np.uint8), "next_done": z(n, np.uint8), "running_rewards": z(n, f),
+            "totals": np.tile(np.array([0.0, 0.0, np.inf, -np.inf]), ((n + 1023) // 1024, 1))}
+
+
+def book(rec, row, active):
+    """the per-world part of a recorded ``mrl_agent_act``"""
+    active = np.asarray(active) != 0
+    rec["active"][row] = active
+    rec["dones"][row] = rec["next_done"].astype(np.float32)
+    rec["next_done"][:] = 0
+    rec["rewards"][row] = 0.0
+    rec["last_active"][active] = row
+    rec["new_game"][active] = 0
+
+
+def credit(rec, rewards, dones):
+    """``mrl_agent_credit``; returns the float32 returns of the episodes that finished"""
+    r, done = np.asarray(rewards, np.float32), np.asarray(dones) != 0
+    n = len(r)
+    running = rec["running_rewards"] + r
+    w = np.arange(n)
+    rec["rewards"][rec["last_active"], w] += np.where(rec["new_game"] != 0, np.float32(0.0), r)
+    rec["next_done"][done] = 1
+    rec["new_game"][done] = 1
+    for b in range((n + 1023) // 1024):
+        mine = done[1024 * b:1024 * b + 1024]
+        if mine.any():
+            finished = running[1024 * b:1024 * b + 1024][mine].astype(np.float64)
+            t = rec["totals"][b]
+            t[0] += len(finished)
+            t[1] += finished.sum()
+            t[2], t[3] = min(t[2], finished.min()), max(t[3], finished.max())
+    rec["running_rewards"] = np.where(done, np.float32(0.0), running).astype(np.float32)
+    return running[done]  # the returns of the episodes that finished, in world order
+
+
+def gae_active(rewards, values, dones, active, next_done, next_value, next_active, gamma, gae_lambda):
+    """``mrl_gae_active`` in float32: (advantages, returns, active afterwards)"""
+    f = np.float32
+    rewards, values, dones = (np.asarray(a, f) for a in (rewards, values, dones))
+    active = (np.asarray(active) != 0).copy()
+    num_steps, n = rewards.shape
+    gamma32, gl = f(gamma), f(float(gamma) * float(gae_lambda))
+    boot = np.asarray(next_active) != 0
+    first = np.where(boot, num_steps, np.where(active.any(axis=0), num_steps - 1 - active[::-1].argmax(axis=0), -1))
+    t_star = first.min()
+    adv = np.zeros((num_steps, n), f)
+    for w in range(n):
+        b = bool(boot[w])
+        nnt = f(1.0) - f(np.asarray(next_done)[w] != 0) if b else f(0.0)
+        nv = f(next_value[w]) if b else f(0.0)
+        last = f(0.0)
+        for t in reversed(range(num_steps)):
+            if not active[t, w]:
+                continue
+            if not b or t < t_star:
+                delta = rewards[t, w] + gamma32 * nv * nnt - values[t, w]
+                adv[t, w] = last = delta + gl * nnt * last
+            if not b:  # the row only carries the bootstrap; the reference's cleared flag also hides it from the two lines below
+                active[t, w] = False
+                b = True
+                continue
+            nnt = f(1.0) - dones[t, w]
+            nv = values[t, w]
+    return adv, adv + values, active
+
+
+def sum_margin(finished):
+    """d of a float64 total of float32 returns: a float32 running sum's distance from it (0 where float32 is exact)"""
+    finished = np.asarray(finished, np.float32)
+    if finished.size == 0:
+        return 0.0
+    return abs(float(np.cumsum(finished, dtype=np.float32)[-1]) - float(finished.astype(np.float64).sum()))
