@@ -490,3 +490,406 @@ def test_refusals(hip_lib):
         agent_act(sim, 0, policy, record, row=0)
     sim.close()
     clean.close()
+
+
+# ---------------------------------------------------------------- modes, sizes and head edges beside the default act
+#
+# Past one pass of the world list, MRL_AGENT_VALUE_ONLY, an act without a record, draws at the ends of the 2^-24 grid, a world
+# with no legal action, policies narrower than the simulator's rows, the workspace's bounds, a side stream.  Margins: d as
+# above, the largest over the sizes of a game at a weight set, here over CASES and LARGE_CASES together; bound 8 d.
+
+EVERY_BUFFER = RECORDED + ("running_rewards", "totals", "first_step", "next_value", "next_active", "advantages", "returns")
+
+
+def every_buffer(record):
+    return {name: cpu(getattr(record, name)) for name in EVERY_BUFFER if getattr(record, name) is not None}
+
+
+@functools.lru_cache(maxsize=None)
+def margins_of_every_size(game, weights):
+    agent = twin.make_agent(game, weights)
+    sizes = [n for g, n in twin.CASES if g == game] + [n for g, n, _, _ in twin.LARGE_CASES if g == game]
+    per_size = [twin.margins(agent, twin.case_inputs(game, n, twin.case_seed(game, n, weights))) for n in sizes]
+    return max(m[0] for m in per_size), max(m[1] for m in per_size)
+
+
+def world_list(workspace, n):
+    """the list of computed worlds an act left in its workspace and its length (the layout: csrc/wide_policy.hpp)"""
+    raw = workspace.cpu().numpy()
+    rows_bytes = (4 * n + 255) // 256 * 256 + 256
+    count = int(raw[rows_bytes - 256:rows_bytes - 252].copy().view(np.uint32)[0])
+    assert count <= n
+    return raw[:4 * n].copy().view(np.uint32)[:count], count
+
+
+def prepared_record(sim, game, num_steps, n, dims=None):
+    """a record whose per-world state is not the initial one, so that what an act writes and what it leaves alone both show"""
+    d, s, a = dims or twin.dims(game)
+    record = AgentRecord(num_steps, n, d, s, a, sim.observation_tensor().to_torch().dtype, sim.agent_state_tensor().to_torch().dtype, DEV,
+                         logits=True)
+    record.next_done[:] = torch.from_numpy((np.arange(n) % 3 == 0).astype(np.uint8)).to(DEV)
+    record.new_game.fill_(1)
+    record.rewards.fill_(5.0)
+    record.running_rewards.fill_(3.0)
+    return record
+
+
+@pytest.mark.parametrize("weights", WEIGHTS)
+@pytest.mark.parametrize("game,n,player,step", twin.LARGE_CASES)
+def test_more_than_one_pass_of_the_world_list(game, n, player, step, weights, hip_lib):
+    """Everything test_forward_pass_and_head and test_values_within_8_d_of_the_twin assert, past 1024 worlds and at a step other
+    than 0, and the world list itself.  An MI355X measures log-probs 0.97 - 1.30 d and values 1.15 - 1.82 d."""
+    seed = twin.case_seed(game, n, weights)
+    agent = twin.make_agent(game, weights)
+    policy = WidePolicy.from_module(agent, device=DEV)
+    inputs = twin.case_inputs(game, n, seed)
+    sim = make_sim(game, n)
+    write_inputs(sim, game, inputs, player)
+    runs = {}
+    for name, kwargs in (("default", {}), ("again", {}), ("all_rows", {"all_rows": True})):
+        record = prepared_record(sim, game, 2, n)
+        sim.action_tensor().to_torch().fill_(-7)
+        agent_act(sim, player, policy, record, row=1, seed=seed, step=step, **kwargs)
+        torch.cuda.synchronize()
+        runs[name] = record_arrays(record)
+        runs[name]["action_tensor"] = cpu(sim.action_tensor())
+        runs[name]["list"] = world_list(record.workspace, n)
+    sim.close()
+    u = twin.draws(seed, step, n, player)
+    want = twin.act(twin.flat(agent), inputs["obs"], inputs["state"], inputs["mask"], u)
+    got, every = runs["default"], runs["all_rows"]
+    active, legal, rows = inputs["active"] != 0, inputs["mask"] != 0, np.arange(n)
+    assert active[1024:].any() and not active[:1024].all()  # (the last pass adds to the list; the list is not every world)
+    # the world list: ascending, complete, its length beside it
+    listed, count = got["list"]
+    assert count == active.sum() and np.array_equal(listed, np.flatnonzero(active))
+    listed, count = every["list"]
+    assert count == n and np.array_equal(listed, rows)
+    d_value, d_logp = margins_of_every_size(game, weights)
+    actions = got["actions"][1]
+    assert legal[rows, actions][active].all() and legal[rows, every["actions"][1]].all()
+    err_logp = max(np.abs(got["logprobs"][1].astype(np.float64) - want["logp"][rows, actions])[active].max(),
+                   np.abs(every["logprobs"][1].astype(np.float64) - want["logp"][rows, every["actions"][1]]).max())
+    err_value = max(np.abs(got["values"][1] - want["values"])[active].max(), np.abs(every["values"][1] - want["values"]).max())
+    print(f"{game} n={n} {weights}: log-probs {err_logp / d_logp:.2f} d (d = {d_logp:.3e}), values {err_value / d_value:.2f} d "
+          f"(d = {d_value:.3e})")
+    assert err_logp <= 8 * d_logp
+    assert err_value <= 8 * d_value
+    near = twin.near_boundary(want["cdf"], u)
+    assert (active & ~near).sum() >= active.sum() - 0.01 * n
+    assert np.array_equal(actions[active & ~near], want["actions"][active & ~near])
+    assert np.array_equal(every["actions"][1][~near], want["actions"][~near])
+    for name in ("actions", "logprobs", "values"):
+        assert (got[name][1][~active] == 0).all(), name
+        same_bits(every[name][1][active], got[name][1][active], f"{name} of the active rows under ALL_ROWS")
+    same_bits(every["logits"][active], got["logits"][active], "logits")
+    for run in (got, every):
+        same_bits(run["action_tensor"][player, :, 0], run["actions"][1], "the ACTION tensor")
+        assert (run["action_tensor"][1 - player] == -7).all()
+        same_bits(run["obs"][1], inputs["obs"], "recorded obs")
+        same_bits(run["states"][1], inputs["state"], "recorded states")
+        same_bits(run["action_masks"][1], legal.astype(np.uint8), "recorded masks")
+        same_bits(run["active"][1], active.astype(np.uint8), "recorded active")
+        same_bits(run["dones"][1], (rows % 3 == 0).astype(np.float32), "dones = next_done")
+        assert not run["next_done"].any() and (run["rewards"][1] == 0).all() and (run["rewards"][0] == 5).all()
+        same_bits(run["last_active"], np.where(active, 1, 0).astype(np.int32), "last_active")
+        same_bits(run["new_game"], np.where(active, 0, 1).astype(np.uint8), "new_game")
+        assert not run["obs"][0].any() and not run["states"][0].any() and not run["action_masks"][0].any() and not run["active"][0].any()
+    for name in RECORDED:
+        same_bits(runs["again"][name], got[name], f"{name} of a second run")
+
+
+@pytest.mark.parametrize("game,n", [("hanabi_very_small", 65), ("balance", 33)])
+def test_value_only_writes_the_bootstrap_value_and_nothing_else(game, n, hip_lib):
+    weights, player, num_steps, step = "orthogonal", 1, 2, 5
+    seed = twin.case_seed(game, n, weights)
+    agent = twin.make_agent(game, weights)
+    policy = WidePolicy.from_module(agent, device=DEV)
+    earlier, inputs = twin.case_inputs(game, n, seed), twin.case_inputs(game, n, seed + 1)
+    active = inputs["active"] != 0
+    assert not np.array_equal(earlier["active"], inputs["active"]) and not np.array_equal(earlier["state"], inputs["state"])
+    sim = make_sim(game, n)
+    write_inputs(sim, game, earlier, player)
+    record = prepared_record(sim, game, num_steps, n)
+    sim.action_tensor().to_torch().fill_(-7)
+    agent_act(sim, player, policy, record, row=1, seed=seed, step=step)
+    record.next_done[:] = torch.from_numpy((np.arange(n) % 2 == 0).astype(np.uint8)).to(DEV)
+    record.next_value.fill_(9.0)
+    record.next_active.fill_(9)
+    torch.cuda.synchronize()
+    before, action_before = every_buffer(record), cpu(sim.action_tensor())
+    assert before["logits"].any() and before["next_done"].any() and (action_before[player] != -7).any()
+    write_inputs(sim, game, inputs, player)
+    results = {}
+    for all_rows in (False, True):
+        agent_act(sim, player, policy, record, row=num_steps, seed=seed, step=step, value_only=True, all_rows=all_rows)
+        torch.cuda.synchronize()
+        after = every_buffer(record)
+        for name in EVERY_BUFFER:
+            if name not in ("next_value", "next_active"):
+                same_bits(after[name], before[name], f"{name} across a VALUE_ONLY act (all_rows={all_rows})")
+        same_bits(cpu(sim.action_tensor()), action_before, "the ACTION tensor across a VALUE_ONLY act")
+        same_bits(after["next_active"], active.astype(np.uint8), "next_active")
+        results[all_rows] = after["next_value"]
+        record.next_value.fill_(9.0)
+        record.next_active.fill_(9)
+    # the same kernels on the same list: the values row of a recorded act on these inputs
+    recorded = {}
+    for all_rows in (False, True):
+        other = prepared_record(sim, game, num_steps, n)
+        agent_act(sim, player, policy, other, row=0, seed=seed, step=step, all_rows=all_rows)
+        torch.cuda.synchronize()
+        recorded[all_rows] = cpu(other.values)[0]
+    sim.close()
+    want = twin.forward(twin.flat(agent), inputs["obs"], inputs["state"], twin.dims(game)[2])[0]
+    d_value = margins_of_every_size(game, weights)[0]
+    same_bits(results[False][active], recorded[False][active], "next_value of the active worlds")
+    assert (results[False][~active] == 0).all() and active.any() and not active.all()
+    same_bits(results[True], recorded[True], "next_value under ALL_ROWS")
+    err = max(np.abs(results[False] - want)[active].max(), np.abs(results[True] - want).max())
+    print(f"{game} n={n} VALUE_ONLY: values {err / d_value:.2f} d (d = {d_value:.3e})")
+    assert err <= 8 * d_value
+
+
+@pytest.mark.parametrize("game,n", [("hanabi_very_small", 65), ("balance", 33)])
+def test_an_act_without_a_record(game, n, hip_lib):
+    """get_action(record=False), a partner in evaluation: the same actions as the recorded act, into the ACTION tensor alone"""
+    weights, player, step = "peaked", 0, 4
+    seed = twin.case_seed(game, n, weights)
+    policy = WidePolicy.from_module(twin.make_agent(game, weights), device=DEV)
+    inputs = twin.case_inputs(game, n, seed)
+    active = inputs["active"] != 0
+    sim = make_sim(game, n)
+    write_inputs(sim, game, inputs, player)
+    workspace = torch.empty(int(_lib.lib().mrl_agent_workspace_bytes(n)), dtype=torch.uint8, device=DEV)
+    for kwargs in ({}, {"all_rows": True}, {"greedy": True}):
+        record = prepared_record(sim, game, 1, n)
+        sim.action_tensor().to_torch().fill_(-7)
+        agent_act(sim, player, policy, record, row=0, seed=seed, step=step, **kwargs)
+        torch.cuda.synchronize()
+        recorded = cpu(record.actions)[0]
+        same_bits(cpu(sim.action_tensor())[player, :, 0], recorded, "the ACTION tensor of the recorded act")
+        sim.action_tensor().to_torch().fill_(-7)
+        agent_act(sim, player, policy, None, seed=seed, step=step, workspace=workspace, **kwargs)
+        torch.cuda.synchronize()
+        got = cpu(sim.action_tensor())
+        same_bits(got[player, :, 0], recorded, f"the actions without a record {kwargs}")
+        if "all_rows" not in kwargs:
+            assert (got[player, :, 0][~active] == 0).all()
+        assert recorded[active].any() and (got[1 - player] == -7).all()
+    sim.close()
+
+
+def test_draws_at_the_ends_of_the_grid(hip_lib):
+    """u = 1 - 2^-24 over a mask whose last four actions are illegal: the exact cumulative sum reaches 1 at the last legal action, a
+    float32 one may stay below u and count on into the illegal tail -- the head's last-legal fallback.  u = 0 over three
+    illegal leading actions: the empty boundaries are passed.  near_boundary flags these rows, so the general comparison skips
+    them; here the action is compared exactly."""
+    game, n, weights = twin.EDGE_GAME, twin.EDGE_N, "orthogonal"
+    agent = twin.make_agent(game, weights)
+    params = twin.flat(agent)
+    policy = WidePolicy.from_module(agent, device=DEV)
+    d_logp = margins_of_every_size(game, weights)[1]
+    sim = make_sim(game, n)
+    record = prepared_record(sim, game, 1, n)
+    fallback, worst = 0, 0.0
+    for kind, seed, player, world, variant, want in twin.edge_rows():
+        inputs = twin.edge_inputs(kind, seed, world, variant)
+        write_inputs(sim, game, inputs, player)
+        agent_act(sim, player, policy, record, row=0, seed=seed, step=0)
+        torch.cuda.synchronize()
+        action, logprob = int(cpu(record.actions)[0, world]), float(cpu(record.logprobs)[0, world])
+        assert action == want, (kind, seed, player, world, variant, action)
+        u = twin.draws(seed, 0, n, player)
+        out = twin.act(params, inputs["obs"], inputs["state"], inputs["mask"], u)
+        assert twin.near_boundary(out["cdf"], u)[world] and u[world] == twin.EDGE_U[kind]
+        worst = max(worst, abs(logprob - out["logp"][world, want]))
+        if kind == "top":  # would the device's own logits, summed in float32 without the fallback, have left the legal actions?
+            raw = twin.head32(cpu(record.logits)[world:world + 1], inputs["mask"][world:world + 1], u[world:world + 1])[0]
+            fallback += int(inputs["mask"][world, raw] == 0)
+    sim.close()
+    print(f"edge draws: log-probs {worst / d_logp:.2f} d (d = {d_logp:.3e}); the unguarded float32 count over the device's logits is "
+          f"illegal in {fallback} of 48 top-draw rows")
+    assert worst <= 8 * d_logp
+    assert fallback >= 1  # (else nothing here went through the fallback)
+
+
+@pytest.mark.parametrize("game,n", [("hanabi_very_small", 65), ("balance", 33)])
+def test_a_world_with_no_legal_action(game, n, hip_lib):
+    weights, player, step = "orthogonal", 1, 2
+    seed = twin.case_seed(game, n, weights)
+    agent = twin.make_agent(game, weights)
+    policy = WidePolicy.from_module(agent, device=DEV)
+    inputs = twin.case_inputs(game, n, seed)
+    active = inputs["active"] != 0
+    world = int(np.flatnonzero(active)[len(np.flatnonzero(active)) // 2])
+    assert 0 < world < n - 1
+    emptied = {**inputs, "mask": inputs["mask"].copy()}
+    emptied["mask"][world] = 0
+    sim = make_sim(game, n)
+    runs = {}
+    for name, case, kwargs in (("normal", inputs, {}), ("emptied", emptied, {}), ("greedy", emptied, {"greedy": True})):
+        write_inputs(sim, game, case, player)
+        record = prepared_record(sim, game, 1, n)
+        sim.action_tensor().to_torch().fill_(-7)
+        agent_act(sim, player, policy, record, row=0, seed=seed, step=step, **kwargs)
+        torch.cuda.synchronize()
+        runs[name] = record_arrays(record)
+        runs[name]["action_tensor"] = cpu(sim.action_tensor())
+    sim.close()
+    others = np.arange(n) != world
+    for name in ("actions", "logprobs", "values"):
+        same_bits(runs["emptied"][name][0][others], runs["normal"][name][0][others], f"{name} of the other worlds")
+    same_bits(runs["emptied"]["logits"], runs["normal"]["logits"], "logits")
+    same_bits(runs["emptied"]["action_tensor"][player, :, 0][others], runs["normal"]["action_tensor"][player, :, 0][others], "ACTION")
+    assert not runs["emptied"]["action_masks"][0][world].any() and runs["normal"]["action_masks"][0][world].any()
+    d_value = margins_of_every_size(game, weights)[0]
+    want = twin.forward(twin.flat(agent), inputs["obs"], inputs["state"], twin.dims(game)[2])[0][world]
+    for name in ("emptied", "greedy"):
+        run = runs[name]
+        assert run["actions"][0][world] == 0 and run["action_tensor"][player, world, 0] == 0, name
+        assert np.isneginf(run["logprobs"][0][world]), name
+        err = abs(float(run["values"][0][world]) - want)
+        print(f"{game} n={n} no legal action ({name}): value {err / d_value:.2f} d (d = {d_value:.3e})")
+        assert err <= 8 * d_value
+        assert np.isfinite(run["logprobs"][0][others]).all()
+
+
+@pytest.mark.parametrize("game,d,s,a", twin.NARROW_CASES)
+def test_policies_narrower_than_the_rows_with_exact_integers(game, d, s, a, hip_lib):
+    """D, S, A below the simulator's row widths: first layers of K = 1 (one padded product), 2, 65 (a chunk and an odd tail of
+    one), 64, 5, and a mask row whose stride is not A.  Integer weights as in test_operand_maps_with_exact_integers: logits and
+    values bit for bit.  A world whose legal actions all lie at A or beyond has no legal action.  In the A = 15 case two
+    outputs share weights and bias: GREEDY takes the lower index of the tie, the higher where the lower is masked off."""
+    n, player, seed, step = twin.NARROW_N, 1, 31, 6
+    tie = twin.TIE if a == 15 else None
+    layers = twin.integer_layers(d, s, a, tie=tie)
+    policy = WidePolicy(d, s, a, device=DEV)
+    policy.params.copy_(torch.from_numpy(twin.integer_params(layers)))
+    full = twin.case_inputs(game, n, 4242)
+    beyond = 5  # this world's only legal action is the simulator's last, which the policy does not have unless A is the row's width
+    full["mask"][beyond] = 0
+    full["mask"][beyond, -1] = 1
+    inputs = twin.narrow_inputs(full, d, s, a)
+    values, logits, bound = twin.integer_forward(layers, inputs["obs"], inputs["state"])
+    assert bound < 2 ** 24
+    legal, rows = inputs["mask"] != 0, np.arange(n)
+    none = ~legal.any(axis=1)
+    assert none[beyond] == (a < full["mask"].shape[1]) and not none.all()
+    sim = make_sim(game, n)
+    write_inputs(sim, game, full, player)
+    assert sim.action_mask_tensor().to_torch().shape[2] >= full["mask"].shape[1]
+    record = prepared_record(sim, game, 1, n, dims=(d, s, a))
+    sim.action_tensor().to_torch().fill_(-7)
+    agent_act(sim, player, policy, record, row=0, seed=seed, step=step, all_rows=True)
+    torch.cuda.synchronize()
+    got = record_arrays(record)
+    same_bits(got["logits"][:, :a], logits.astype(np.float32), "logits")
+    assert not got["logits"][:, a:].any()
+    same_bits(got["values"][0], values.astype(np.float32), "values")
+    same_bits(got["obs"][0], inputs["obs"], "recorded obs: the first D entries")
+    same_bits(got["states"][0], inputs["state"], "recorded states: the first S entries")
+    same_bits(got["action_masks"][0], legal.astype(np.uint8), "recorded masks: the first A entries")
+    same_bits(cpu(sim.action_tensor())[player, :, 0], got["actions"][0], "the ACTION tensor")
+    actions = got["actions"][0]
+    assert (actions[none] == 0).all() and np.isneginf(got["logprobs"][0][none]).all()
+    assert legal[rows, actions][~none].all() and np.isfinite(got["logprobs"][0][~none]).all()
+    u = twin.draws(seed, step, n, player)
+    want = twin.act(twin.integer_params(layers), inputs["obs"][~none], inputs["state"][~none], inputs["mask"][~none], u[~none])
+    keep = ~twin.near_boundary(want["cdf"], u[~none])
+    assert keep.sum() >= (~none).sum() - 1
+    assert np.array_equal(actions[~none][keep], want["actions"][keep])
+    if tie:
+        lo, hi = tie
+        # legal: what does not beat the tied pair; every third world loses the lower of the two, every third keeps its own mask
+        mask = full["mask"].copy()
+        for w in rows:
+            if w % 3 != 2:
+                mask[w, :a] = logits[w] <= logits[w, lo]
+                mask[w, lo] = w % 3 != 0
+        write_inputs(sim, game, {**full, "mask": mask}, player)
+        agent_act(sim, player, policy, record, row=0, seed=seed, step=step, all_rows=True, greedy=True)
+        torch.cuda.synchronize()
+        greedy, legal = cpu(record.actions)[0], mask[:, :a] != 0
+        first = np.where(legal, logits, -np.inf).argmax(axis=1)  # (numpy's arg-max is the first)
+        some = legal.any(axis=1)
+        assert np.array_equal(greedy[some], first[some]) and (greedy[~some] == 0).all()
+        both, lower_off = (rows % 3 == 1) & (first == lo), (rows % 3 == 0) & (first == hi)
+        assert both.sum() >= 5 and legal[both][:, hi].all() and lower_off.sum() >= 5 and not legal[lower_off][:, lo].any()
+    sim.close()
+
+
+@pytest.mark.parametrize("n", [33, 1025])
+def test_an_act_stays_inside_its_workspace(n, hip_lib):
+    """mrl_agent_workspace_bytes(N) bytes between two guards of 4096 bytes: the guards keep their fill, the results are those
+    of the record's own workspace."""
+    game, weights, player, step, guard = "hanabi_very_small", "orthogonal", 0, 1, 4096
+    seed = twin.case_seed(game, 33, weights) + n
+    policy = WidePolicy.from_module(twin.make_agent(game, weights), device=DEV)
+    sim = make_sim(game, n)
+    write_inputs(sim, game, twin.case_inputs(game, n, seed), player)
+    size = (int(_lib.lib().mrl_agent_workspace_bytes(n)) + 15) // 16 * 16
+    buffer = torch.full((guard + size + guard + 16,), 0xA5, dtype=torch.uint8, device=DEV)
+    first = guard + (-(buffer.data_ptr() + guard)) % 16
+    middle = buffer[first:first + size]
+    assert middle.data_ptr() % 16 == 0 and middle.numel() == size
+    results = {}
+    for name, workspace in (("own", None), ("guarded", middle)):
+        record = prepared_record(sim, game, 1, n)
+        sim.action_tensor().to_torch().fill_(-7)
+        agent_act(sim, player, policy, record, row=0, seed=seed, step=step, workspace=workspace)
+        agent_act(sim, player, policy, record, row=1, seed=seed, step=step, value_only=True, workspace=workspace)
+        torch.cuda.synchronize()
+        results[name] = every_buffer(record)
+        results[name]["action_tensor"] = cpu(sim.action_tensor())
+    sim.close()
+    whole = buffer.cpu().numpy()
+    assert (whole[first - guard:first] == 0xA5).all(), "the guard in front of the workspace was written"
+    assert (whole[first + size:first + size + guard] == 0xA5).all(), "the guard behind the workspace was written"
+    assert (whole[first:first + size] != 0xA5).any()
+    for name in results["own"]:
+        same_bits(results["guarded"][name], results["own"][name], f"{name} with a workspace of the caller's")
+    assert results["own"]["next_value"].any() and results["own"]["values"].any()
+
+
+def test_a_side_stream_gives_the_same_bits(hip_lib):
+    """a recorded act, a credit, the bootstrap value and the advantage pass under torch.cuda.stream(side)"""
+    game, n, weights, player, num_steps = "balance", 33, "orthogonal", 1, 2
+    seed = twin.case_seed(game, n, weights)
+    policy = WidePolicy.from_module(twin.make_agent(game, weights), device=DEV)
+    inputs = twin.case_inputs(game, n, seed)
+    rng = np.random.default_rng(8)
+    rewards = torch.from_numpy(rng.normal(size=n).astype(np.float32)).to(DEV)
+    dones = torch.from_numpy((rng.uniform(size=n) < 0.3).astype(np.int32)).to(DEV)
+    sim = make_sim(game, n)
+    # the closing observation is every world's: while a world is left without a bootstrap, the advantage pass computes only
+    # the worlds being bootstrapped (include/mrl_envs.h), and a world that never acts would leave every advantage at 0
+    closing = {**inputs, "active": np.ones(n, np.int32)}
+
+    def run():
+        write_inputs(sim, game, inputs, player)
+        record = prepared_record(sim, game, num_steps, n)
+        sim.action_tensor().to_torch().fill_(-7)
+        for t in range(num_steps):
+            agent_act(sim, player, policy, record, row=t, seed=seed, step=t)
+            agent_credit(record, rewards, dones)
+        write_inputs(sim, game, closing, player)
+        agent_act(sim, player, policy, record, row=num_steps, seed=seed, step=num_steps, value_only=True)
+        gae_active(record, 0.99, 0.95)
+        return record
+
+    on_default = run()
+    torch.cuda.synchronize()
+    want, want_action = every_buffer(on_default), cpu(sim.action_tensor())
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        on_side = run()
+    side.synchronize()
+    torch.cuda.synchronize()
+    got = every_buffer(on_side)
+    for name in want:
+        same_bits(got[name], want[name], f"{name} on a side stream")
+    same_bits(cpu(sim.action_tensor()), want_action, "the ACTION tensor on a side stream")
+    assert want["advantages"].any() and want["totals"][0, 0] > 0 and want["next_value"].any()
+    sim.close()

@@ -131,6 +131,79 @@ def test_gpu_cases_draw_away_from_boundaries(game, n, weights):
     assert near.sum() <= 0.01 * n, f"{near.sum()} of {n} rows are near a boundary"
 
 
+@pytest.mark.parametrize("weights", sorted(twin.WEIGHTS))
+@pytest.mark.parametrize("game,n,player,step", twin.LARGE_CASES)
+def test_large_gpu_cases_draw_away_from_boundaries(game, n, player, step, weights):
+    """The same cap for the cases past 1024 worlds, at the player and the step they run with."""
+    seed = twin.case_seed(game, n, weights)
+    agent = twin.make_agent(game, weights)
+    inputs = twin.case_inputs(game, n, seed)
+    u = twin.draws(seed, step, n, player)
+    assert not np.array_equal(u, twin.draws(seed, 0, n, player))  # (the step reaches the draw)
+    near = twin.near_boundary(twin.act(twin.flat(agent), inputs["obs"], inputs["state"], inputs["mask"], u)["cdf"], u)
+    print(f"{game} n={n} {weights}: {near.sum()} of {n} rows are near a boundary")
+    assert near.sum() <= 0.01 * n, f"{near.sum()} of {n} rows are near a boundary"
+
+
+@pytest.mark.parametrize("kind", sorted(twin.EDGE_DRAWS))
+def test_edge_draws_sit_at_the_ends_of_the_grid(kind):
+    assert len(twin.EDGE_DRAWS[kind]) == 6
+    for seed, player, world in twin.EDGE_DRAWS[kind]:
+        assert twin.draws(seed, 0, twin.EDGE_N, player)[world] == twin.EDGE_U[kind], (seed, player, world)
+    assert twin.EDGE_U["top"] == np.nextafter(np.float32(1.0), np.float32(0.0))  # the largest u there is
+
+
+def test_edge_rows_are_decided_by_the_ends_of_the_grid():
+    """What the GPU's edge-draw test rests on.  Top draws: the twin chooses the last legal action, with a probability far
+    above the grid's spacing (so the boundary below it is nowhere near u); the row is one the general comparison skips; and a
+    float32 cumulative sum without the fallback runs on into the illegal tail in some of the rows (which ones depends on the
+    rounding: evidence that the device takes the branch, not proof).  Zero draws: the three empty boundaries are passed
+    (0 >= 0) and the first legal action, 3, is chosen."""
+    agent = twin.make_agent(twin.EDGE_GAME, "orthogonal")
+    params = twin.flat(agent)
+    rows = twin.edge_rows()
+    assert [r[0] for r in rows].count("top") == 48 and [r[0] for r in rows].count("zero") == 6
+    illegal, lowest = 0, 1.0
+    for kind, seed, player, world, variant, want in rows:
+        inputs = twin.edge_inputs(kind, seed, world, variant)
+        legal = inputs["mask"] != 0
+        u = twin.draws(seed, 0, twin.EDGE_N, player)
+        out = twin.act(params, inputs["obs"], inputs["state"], inputs["mask"], u)
+        assert out["actions"][world] == want and legal[world, want], (kind, seed, variant)
+        if kind == "zero":
+            assert not legal[world, :3].any()
+            continue
+        assert want == np.flatnonzero(legal[world]).max() and not legal[world, want + 1:].any() and not legal[world, 0]
+        lowest = min(lowest, float(np.exp(out["logp"][world, want])))
+        assert twin.near_boundary(out["cdf"], u)[world]
+        raw = twin.head32(out["logits"].astype(np.float32)[world:world + 1], inputs["mask"][world:world + 1], u[world:world + 1])[0]
+        assert raw >= want
+        illegal += not legal[world, raw]
+    print(f"top draws: the raw float32 count is illegal in {illegal} of 48 rows; the last legal action's probability >= {lowest:.3f}")
+    assert lowest >= 1e-3
+    assert illegal >= 1
+
+
+@pytest.mark.parametrize("game,d,s,a", twin.NARROW_CASES)
+def test_narrow_integer_policies_are_exact_in_float32(game, d, s, a):
+    """The narrow-policy GPU cases compare bit for bit: every sum of absolute terms stays below 2^24, the logits are not all
+    alike, and in the tied case the tie is there and is the largest logit of some worlds."""
+    full = twin.dims(game)
+    assert d < full[0] and s < full[1] and a <= full[2]
+    tie = twin.TIE if a == 15 else None
+    layers = twin.integer_layers(d, s, a, tie=tie)
+    inputs = twin.narrow_inputs(twin.case_inputs(game, twin.NARROW_N, 4242), d, s, a)
+    values, logits, bound = twin.integer_forward(layers, inputs["obs"], inputs["state"])
+    assert bound < 2 ** 24
+    assert len(np.unique(logits)) > 1 and len(np.unique(values)) > 1
+    reference = twin.forward(twin.integer_params(layers), inputs["obs"], inputs["state"], a)
+    assert np.array_equal(reference[0], values) and np.array_equal(reference[1], logits)  # the flat order is the twin's
+    if tie:
+        lo, hi = tie
+        assert np.array_equal(logits[:, lo], logits[:, hi])
+        assert ((logits <= logits[:, [lo]]).sum(axis=1) > 2).any()
+
+
 FIXTURE_CASES = [(regime, n) for n in (5, 70) for regime in ("coupled", "together")]
 
 

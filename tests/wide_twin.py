@@ -27,6 +27,23 @@ def dims(game):
 CASES = [(game, n) for game in ("balance", "hanabi_very_small") for n in SIZES] + [("hanabi_full", 65)]
 
 
+# forward cases past one pass of the world list (1024 worlds): (game, worlds, player, step), each with both weight sets.  They
+# are not part of CASES: the margins of the cases above are a maximum over CASES and stay what they were.
+#   hanabi_very_small 2081 = 1024 + 1024 + 33: three passes, two carries, a ragged last pass
+#   hanabi_full 1025 = 1024 + 1: a last pass of one world; 1025 x 783 elements are past the bookkeeping kernel's 2048 workgroups
+#   balance 2081: the int32 inputs
+LARGE_CASES = [("hanabi_very_small", 2081, 1, 3), ("hanabi_full", 1025, 0, 3), ("balance", 2081, 1, 3)]
+
+# (seed, player, world) of hanabi_very_small, 65 worlds, step 0, whose draw sits at an end of the 2^-24 grid (found by search,
+# checked by tests/test_wide_agent_api.py through ``draws``)
+EDGE_GAME, EDGE_N, EDGE_VARIANTS = "hanabi_very_small", 65, 8
+EDGE_DRAWS = {
+    "top": [(17086, 1, 13), (98468, 1, 18), (176164, 0, 7), (296419, 0, 11), (680799, 1, 47), (830688, 0, 6)],  # u = 1 - 2^-24
+    "zero": [(8124, 1, 45), (455495, 1, 39), (543352, 0, 36), (570769, 1, 25), (659495, 1, 27), (1183274, 0, 17)],  # u = 0
+}
+EDGE_U = {"top": 1.0 - 2.0 ** -24, "zero": 0.0}
+
+
 def case_seed(game, n, weights):
     """seed of the inputs and of the draws of one case"""
     return 7919 * n + 104729 * sorted(WEIGHTS).index(weights) + {"balance": 1, "hanabi_very_small": 2, "hanabi_full": 3}[game]
@@ -65,6 +82,104 @@ def case_inputs(game, n, seed, player=0):
     active = (rng.uniform(size=n) < 0.55).astype(np.int32)
     active[0] = 1  # (N = 1 computes something)
     return {"obs": state[:, :d], "state": state, "mask": mask, "active": active}
+
+
+def narrow_inputs(inputs, d, s, a):
+    """what a policy of (d, s, a) reads of a case's inputs: the first d / s / a entries of the rows"""
+    return {"obs": inputs["obs"][:, :d], "state": inputs["state"][:, :s], "mask": inputs["mask"][:, :a], "active": inputs["active"]}
+
+
+def edge_inputs(kind, seed, world, variant=0):
+    """The inputs of one edge-draw row: ``case_inputs(EDGE_GAME, EDGE_N, 1000 * variant + seed)`` with ``world`` active and its
+    mask set so that the end of the grid decides.  "top": action 0 illegal, 1 .. A - 5 legal, the last four illegal -- the
+    exact cumulative sum reaches 1 at action A - 5 and u = 1 - 2^-24 asks for the last legal action, or, where float32
+    rounding leaves the sum below u, counts on into the illegal tail.  "zero": the first three actions illegal, action 3
+    legal -- u = 0 passes the three empty boundaries and stops at the first legal action."""
+    inputs = case_inputs(EDGE_GAME, EDGE_N, 1000 * variant + seed)
+    a = inputs["mask"].shape[1]
+    inputs["active"][world] = 1
+    if kind == "top":
+        inputs["mask"][world] = 0
+        inputs["mask"][world, 1:a - 4] = 1
+    else:
+        inputs["mask"][world, :3] = 0
+        inputs["mask"][world, 3] = 1
+    return inputs
+
+
+def edge_rows():
+    """every edge-draw row of the GPU test: (kind, seed, player, world, variant, the action the header asks for)"""
+    a = dims(EDGE_GAME)[2]
+    return [("top", seed, player, world, variant, a - 5) for seed, player, world in EDGE_DRAWS["top"] for variant in range(EDGE_VARIANTS)] + \
+        [("zero", seed, player, world, 0, 3) for seed, player, world in EDGE_DRAWS["zero"]]
+
+
+def head32(logits, mask, u):
+    """The head's cumulative sum restated in float32, WITHOUT its fallback: the raw count of boundaries at or below u.
+    e = the float64 exponential of the float32 difference, rounded once to float32 (a correctly rounded expf, independent of
+    any library's vectorised one); the sum, the divides and the running sum are float32, ascending."""
+    f = np.float32
+    legal = np.asarray(mask) != 0
+    logits = np.asarray(logits, f)[:, :legal.shape[1]]  # (a recorded row is MRL_WIDE_MAX_ACTIONS wide)
+    u = np.asarray(u, np.float64).astype(f)
+    n, a = legal.shape
+    count = np.zeros(n, np.int32)
+    for w in range(n):
+        if not legal[w].any():
+            continue
+        top = logits[w][legal[w]].max()
+        e = np.where(legal[w], np.exp((logits[w] - top).astype(np.float64)), 0.0).astype(f)
+        total, cdf = f(0.0), f(0.0)
+        for i in range(a):
+            total = f(total + e[i])
+        for i in range(a - 1):
+            cdf = f(cdf + f(e[i] / total))
+            count[w] += int(u[w] >= cdf)
+    return count
+
+
+# policies narrower than the simulator's rows: (game, D, S, A).  K = 1 is a single padded product, 2 one unpadded step, 65 a
+# chunk of 64 and an odd tail of one; A = 1, 15 and 3 read a mask row whose stride is not A.
+NARROW_CASES = [("hanabi_very_small", 1, 65, 1), ("hanabi_very_small", 2, 64, 15), ("hanabi_very_small", 65, 1, 16), ("balance", 5, 5, 3)]
+NARROW_N, TIE = 33, (4, 9)  # the two actor outputs of the A = 15 case that share weights and bias
+
+
+def integer_layers(d, s, a, seed=99, tie=None):
+    """Integer weights and biases of a (d, s, a) policy, the construction of ``test_operand_maps_with_exact_integers``: the first
+    layer dense in -2..2, the others one entry in 32, plus a pattern that is asymmetric in row and column.  With ``tie`` =
+    (lo, hi) the actor's output row hi is a copy of row lo.  {"critic" / "actor": [(w, b)] * 4} in int64."""
+    rng = np.random.default_rng(seed)
+    layers = {}
+    for name, first, out in (("critic", s, 1), ("actor", d, a)):
+        layers[name] = []
+        for k, (rows, cols) in enumerate(((H, first), (H, H), (H, H), (out, H))):
+            density = 1.0 if k == 0 else 1.0 / 32
+            w = (rng.integers(-2, 3, size=(rows, cols)) * (rng.uniform(size=(rows, cols)) < density)).astype(np.int64)
+            w += (np.arange(rows)[:, None] % 3 == 0) & (np.arange(cols)[None, :] % 7 == 0)
+            b = rng.integers(-3, 4, size=rows).astype(np.int64)
+            layers[name].append((w, b))
+    if tie:
+        w, b = layers["actor"][3]
+        w[tie[1]], b[tie[1]] = w[tie[0]], b[tie[0]]
+    return layers
+
+
+def integer_params(layers):
+    return np.concatenate([x.reshape(-1) for name in ("critic", "actor") for w, b in layers[name] for x in (w, b)]).astype(np.float32)
+
+
+def integer_forward(layers, obs, state):
+    """(values (n,), logits (n, A)) in int64, and the largest sum of absolute terms over every output of every layer: below
+    2^24 every partial sum is an integer float32 holds exactly, in whatever order it is taken"""
+    out, bound = {}, 0
+    for name, x in (("critic", np.asarray(state, np.int64)), ("actor", np.asarray(obs, np.int64))):
+        for k, (w, b) in enumerate(layers[name]):
+            bound = max(bound, int((np.abs(x) @ np.abs(w).T + np.abs(b)).max()))
+            x = x @ w.T + b
+            if k < 3:
+                x = np.maximum(x, 0)
+        out[name] = x
+    return out["critic"][:, 0], out["actor"], bound
 
 
 def draws(seed, step, n, player):
