@@ -749,6 +749,87 @@ int mrl_agent_credit(const mrl_agent_record *record, const float *rewards_dev, c
 int mrl_gae_active(const mrl_agent_record *record, const float *next_value, const uint8_t *next_active, float gamma, float lambda,
                    float *advantages, float *returns, int gpu_id, void *hip_stream);
 
+/* MAPPO's CNN actor-critic for Overcooked on the device: what the reference's rollout loop runs in torch around every step
+ * (train/MAPPO/main_player.py:211-261) -- for each seat an int8 -> float cast, a movedim, Conv2d, three Linear layers and a
+ * Categorical, twice (actor and critic: train/MAPPO/utils/cnn.py:26-42, r_actor_critic.py, utils/distributions.py:55-68, hidden_size
+ * 64 as the reference's Overcooked notebook sets it) -- as ONE launch per act, mrl_cnn_act, and a whole T-step collection as one
+ * call, mrl_rollout_cnn.  No reference counterpart as calls.  DESIGN.md section 15.
+ *   Networks, for a W x H kitchen with F = 5P + 16 channels and npos = (W - 2)(H - 2): Conv2d(F, 32, 3 x 3, valid), ReLU, flatten,
+ *     Linear(32 npos, 64), ReLU, Linear(64, 64), ReLU, then Linear(64, 6) (actor) or Linear(64, 1) (critic).  For Overcooked the
+ *     critic's input IS the seat's observation (share_observation_space = observation_space) and there is no action mask.
+ *     params_dev is one flat float32 device array: the actor's eight tensors, then the critic's eight, each in
+ *     parameters_to_vector order -- conv weight (32, F, 3, 3) and bias, fc1 weight (64, 32 npos) and bias, fc2 weight and bias, head
+ *     weight and bias; mrl_cnn_policy_num_params(W, H, F, hidden, A) floats (0 for hidden != 64 or A != 6 or W, H < 3).  It is read
+ *     in place in every call.  hidden must be 64; flags is 0 or MRL_POLICY_GREEDY, which both calls OR into their own flags
+ *     (mrl_rollout_cnn has no flags argument of its own).
+ *   Samples: (world n, seat p) for every seat whose bit is set in `players` (seats 0..31).  The kernel reads the int8 world-major
+ *     block (N, P, H, W, F) where the simulator's most recent step wrote its observations -- its own OBS_WORLD_MAJOR tensor, the
+ *     slot of mrl_set_observation_output, or ring slot (k - 1) mod T; where no step has run since that destination was set,
+ *     where the next step will write -- in place, converting on load: there is no float copy of the observations.
+ *   THE INDEX MAP: torch sees x[n, f, w, h] = obs[n, p, h, w, f], so for the conv weight Wc[c, f, i, j]
+ *       conv[n, c, ow, oh] = bc[c] + sum over (f, i, j) of Wc[c, f, i, j] * obs[n, p, oh + j, ow + i, f],  ow < W - 2, oh < H - 2,
+ *     and fc1's input index is c (W - 2)(H - 2) + ow (H - 2) + oh.
+ *   Arithmetic: mrl_agent_act's rule.  Every product runs on v_mfma_f32_32x32x2_f32 in exact float32; an output starts from 0 and
+ *     adds its products with one fused multiply-add each in ascending order of torch's flattened weight index (conv: k = 9 f + 3 i +
+ *     j; the linear layers: their input index; an odd K is padded with one zero product); the bias is added to the finished sum.
+ *     No float atomics, no order that depends on timing: the same inputs give the same bits on every run and on any stream.
+ *   Head, float32, A = 6: mrl_policy_act's rule above with the seat as the hash's player -- h = the hash of (seed, step, n, p);
+ *     u = (h >> 8) * 2^-24; m = max logit; e_a = exp(l_a - m); p_a = e_a / sum e; action = the number of a in 0..4 with u >= p_0 +
+ *     ... + p_a; logprob = (l_action - m) - log(sum e).  MRL_POLICY_GREEDY: the first arg-max (the reference's deterministic=True
+ *     is probs.argmax).  The action goes to ACTION[p, n].  Without a record only the actor runs.
+ *   Record (mrl_cnn_record), dense device arrays, T = num_steps: actions int32, logprobs, rewards, dones (T, N, P); values
+ *     (T + 1, N, P), row T the closing value; next_done (N, P); logits (T, N, P, 6), optional (tests and diagnostics); all float32
+ *     but actions.  An act at row k < T writes, for its seats, actions / logprobs / values / logits [k, n, p], dones[k, n, p] =
+ *     DONE[n] != 0 as 0.0 / 1.0 -- the flag as it stands in front of step k, mrl_policy_act's convention -- and, for k > 0,
+ *     rewards[k - 1, n, p] = (float)REWARD[p, n] (the same for every seat).  MRL_CNN_VALUE_ONLY needs row == T: the critic alone;
+ *     it writes values[T], rewards[T - 1] (T > 0) and next_done and touches neither ACTION nor any other row.  Flattened to N P
+ *     columns the arrays are what mrl_gae takes (next_value = values[T]).  Seats outside `players` keep every byte of their
+ *     ACTION row and of their record columns.
+ *   workspace: mrl_cnn_workspace_bytes(num_worlds, num_players) bytes of device memory on a 16-byte boundary, the caller's.  The
+ *     fused kernel keeps every intermediate in LDS and does not touch it today; the amount is fixed (256 bytes) and is part of
+ *     the call so that a later, larger tile need not change the ABI.
+ *   Launches: one -- a workgroup of four wavefronts per (tile of 32 samples, net).  The call only enqueues on hip_stream; it never
+ *     synchronises or allocates.
+ *   Limit: the workgroup's LDS image -- 32 observation rows of H W F bytes (+ 3, rounded up to an odd number of dwords), the conv
+ *     weights (32 rows of 9 F floats, padded to an odd count), 2 bytes per k, and the convolution's output, 32 rows of 32 npos + 1
+ *     floats -- must fit 160 KiB.  The five standard two-player layouts do (9 x 5: 154 464 bytes; 5 x 4: 72 032); a larger kitchen or
+ *     more players than that allows is refused, never computed wrongly.
+ *   MRL_ERR_INVALID: a simulator that is not Overcooked; hidden != 64; players == 0 or a bit >= P; a NULL policy, parameter array
+ *     or workspace, or a NULL buffer but logits in a record; row >= T without MRL_CNN_VALUE_ONLY, row != T with it, or it without a
+ *     record; workspace_bytes below mrl_cnn_workspace_bytes or a workspace off a 16-byte boundary; a shape beyond the limit; a
+ *     capturing stream (row and step travel in kernel arguments, as for the sibling calls); a flag bit other than
+ *     MRL_POLICY_GREEDY and MRL_CNN_VALUE_ONLY; a kitchen narrower or lower than 3; a simulator that has been through
+ *     mrl_exchange_create.
+ * mrl_rollout_cnn: obs_ring is int8 (T + 1, N, P, H, W, F), dense.  Slot 0 receives the current observations (one copy); for
+ *   k < T: mrl_cnn_act on slot k at row k with step number first_step + k, then the ordinary step (mrl_step reading the ACTION
+ *   tensor) writes slot k + 1 through the observation ring of mrl_set_observation_ring; then the closing MRL_CNN_VALUE_ONLY act on
+ *   slot T.  Afterwards the simulator's observation output is what it was before the call (destination and ring position), and
+ *   slot T is copied to where that output's most recent step wrote (one more device-to-device copy, T > 0): the simulator,
+ *   its observations included, is exactly where T mrl_step_with_actions calls with actions[0..T-1] would have left it, and the
+ *   next mrl_cnn_act or mrl_rollout_cnn reads the observations of the state it acts on -- two rollouts of T equal one of 2 T.  Seats outside `players`
+ *   step with whatever their ACTION rows hold.  A ring whose slots do not start on 16-byte boundaries is staged as
+ *   mrl_set_observation_ring says.  It takes no workspace (its acts need none).  Refusals: those of mrl_cnn_act, a NULL record or ring. */
+enum { MRL_CNN_VALUE_ONLY = 4 }; /* flag of mrl_cnn_act, beside MRL_POLICY_GREEDY */
+typedef struct mrl_cnn_policy {
+    const float *params_dev;
+    uint32_t hidden, flags;
+} mrl_cnn_policy;
+typedef struct mrl_cnn_record { /* all device pointers, dense; T = num_steps */
+    int32_t *actions;           /* (T, N, P) */
+    float *logprobs;            /* (T, N, P) */
+    float *values;              /* (T + 1, N, P) */
+    float *rewards, *dones;     /* (T, N, P) */
+    float *next_done;           /* (N, P) */
+    float *logits;              /* (T, N, P, 6) or NULL */
+    uint32_t num_steps;
+} mrl_cnn_record;
+uint64_t mrl_cnn_policy_num_params(uint32_t width, uint32_t height, uint32_t channels, uint32_t hidden, uint32_t num_actions);
+uint64_t mrl_cnn_workspace_bytes(uint32_t num_worlds, uint32_t num_players);
+int mrl_cnn_act(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, const mrl_cnn_record *record_or_null, uint32_t row,
+                uint64_t seed, uint32_t step, uint32_t flags, void *workspace_dev, uint64_t workspace_bytes, void *hip_stream);
+int mrl_rollout_cnn(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, const mrl_cnn_record *record, void *obs_ring_dev,
+                    uint64_t seed, uint32_t first_step, void *hip_stream);
+
 int mrl_tensor(mrl_sim *sim, int slot, mrl_tensor_desc *out);
 int mrl_game(const mrl_sim *sim);
 uint32_t mrl_num_worlds(const mrl_sim *sim);

@@ -31,6 +31,8 @@ POLICY_GREEDY = 1  # MRL_POLICY_GREEDY
 AGENT_ALL_ROWS, AGENT_VALUE_ONLY = 2, 4  # MRL_AGENT_*: flags of mrl_agent_act beside POLICY_GREEDY
 WIDE_HIDDEN, WIDE_MAX_ACTIONS = 512, 64  # MRL_WIDE_*
 PPO_NORM_ADV, PPO_CLIP_VLOSS = 1, 2  # MRL_PPO_*
+CNN_VALUE_ONLY = 4  # MRL_CNN_VALUE_ONLY: flag of mrl_cnn_act beside POLICY_GREEDY
+CNN_HIDDEN, CNN_ACTIONS = 64, 6  # the one shape mrl_cnn_act runs
 PPO_STATS = ("pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac", "total_norm", "loss")  # a stats row
 
 # every symbol include/mrl_envs.h declares
@@ -44,7 +46,8 @@ SYMBOLS = [
     "mrl_build_hash", "mrl_exchange_create", "mrl_exchange_connect", "mrl_step_exchanged", "mrl_reset_worlds",
     "mrl_acrobot_create", "mrl_enable_episode_stats", "mrl_clear_episode_totals", "mrl_mlp_policy_num_params",
     "mrl_rollout_policy", "mrl_gae", "mrl_ppo_workspace_bytes", "mrl_ppo_update", "mrl_wide_policy_num_params",
-    "mrl_agent_workspace_bytes", "mrl_agent_act", "mrl_agent_credit", "mrl_gae_active",
+    "mrl_agent_workspace_bytes", "mrl_agent_act", "mrl_agent_credit", "mrl_gae_active", "mrl_cnn_policy_num_params",
+    "mrl_cnn_workspace_bytes", "mrl_cnn_act", "mrl_rollout_cnn",
 ]
 ABI_VERSION = 4  # MRL_ABI_VERSION of include/mrl_envs.h this binding was written against
 
@@ -106,6 +109,17 @@ AGENT_RECORD_BUFFERS = ("obs", "states", "action_masks", "active", "actions", "l
 class AgentRecord(ctypes.Structure):  # mrl_agent_record
     _fields_ = [(name, ctypes.c_void_p) for name in AGENT_RECORD_BUFFERS] + [("num_steps", ctypes.c_uint32),
                                                                              ("num_worlds", ctypes.c_uint32)]
+
+
+class CnnPolicyDesc(ctypes.Structure):  # mrl_cnn_policy
+    _fields_ = [("params_dev", ctypes.c_void_p), ("hidden", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+CNN_RECORD_BUFFERS = ("actions", "logprobs", "values", "rewards", "dones", "next_done", "logits")
+
+
+class CnnRecordDesc(ctypes.Structure):  # mrl_cnn_record
+    _fields_ = [(name, ctypes.c_void_p) for name in CNN_RECORD_BUFFERS] + [("num_steps", ctypes.c_uint32)]
 
 
 class MrlError(RuntimeError):
@@ -229,6 +243,13 @@ def lib():
                                 vp]
     L.mrl_agent_credit.argtypes = [ctypes.POINTER(AgentRecord), vp, vp, u32, i32, vp]
     L.mrl_gae_active.argtypes = [ctypes.POINTER(AgentRecord), vp, vp, ctypes.c_float, ctypes.c_float, vp, vp, i32, vp]
+    L.mrl_cnn_policy_num_params.argtypes = [u32, u32, u32, u32, u32]
+    L.mrl_cnn_policy_num_params.restype = ctypes.c_uint64
+    L.mrl_cnn_workspace_bytes.argtypes = [u32, u32]
+    L.mrl_cnn_workspace_bytes.restype = ctypes.c_uint64
+    L.mrl_cnn_act.argtypes = [vp, u32, ctypes.POINTER(CnnPolicyDesc), ctypes.POINTER(CnnRecordDesc), u32, ctypes.c_uint64, u32, u32, vp,
+                              ctypes.c_uint64, vp]
+    L.mrl_rollout_cnn.argtypes = [vp, u32, ctypes.POINTER(CnnPolicyDesc), ctypes.POINTER(CnnRecordDesc), vp, ctypes.c_uint64, u32, vp]
     L.mrl_tensor.argtypes = [vp, i32, ctypes.POINTER(TensorDesc)]
     L.mrl_game.argtypes = [vp]
     L.mrl_num_worlds.argtypes = [vp]

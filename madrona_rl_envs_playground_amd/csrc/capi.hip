@@ -5,6 +5,7 @@
 #include "policy_rollout.hpp"
 #include "ppo_update.hpp"
 #include "wide_policy.hpp"
+#include "cnn_policy.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -886,6 +887,174 @@ int mrl_gae_active(const mrl_agent_record *record, const float *next_value, cons
     mrl::DeviceGuard on(gpu_id);
     return guarded([&] {
         mrl::launch_gae_active(*record, next_value, next_active, gamma, lambda, advantages, returns, (hipStream_t)hip_stream);
+    });
+}
+
+uint64_t mrl_cnn_policy_num_params(uint32_t width, uint32_t height, uint32_t channels, uint32_t hidden, uint32_t num_actions)
+{
+    if (hidden != mrl::kCnnHidden || num_actions != mrl::kCnnActions || width < 3 || height < 3 || channels == 0) return 0;
+    return mrl::cnn_net_params(width, height, channels, num_actions) + mrl::cnn_net_params(width, height, channels, 1);
+}
+
+uint64_t mrl_cnn_workspace_bytes(uint32_t num_worlds, uint32_t num_players) { return mrl::kCnnWorkspaceBytes; }
+
+// Everything mrl_cnn_act and mrl_rollout_cnn check alike; fills `args` but for the observation pointer, the rows and the step.
+static int cnn_prepare(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, const mrl_cnn_record *record, void *hip_stream,
+                       const char *what, mrl::CnnActArgs *args)
+{
+    if (int rc = mrl::need_healthy(sim)) return rc;
+    if (sim->game != MRL_GAME_OVERCOOKED) {
+        mrl::set_error("%s: game %d has no CNN policy (Overcooked does)", what, sim->game);
+        return MRL_ERR_INVALID;
+    }
+    if (sim->exchange.mine) {
+        mrl::set_error("%s: this simulator is a rank of an exchanged batch (mrl_exchange_create); sharded simulators are out of scope", what);
+        return MRL_ERR_INVALID;
+    }
+    if (mrl::capturing(hip_stream)) {
+        mrl::set_error("%s: the row and the step number travel in kernel arguments, a captured call would replay them", what);
+        return MRL_ERR_INVALID;
+    }
+    if (!policy || !policy->params_dev || policy->hidden != mrl::kCnnHidden || (policy->flags & ~(uint32_t)MRL_POLICY_GREEDY)) {
+        mrl::set_error("%s: null policy or parameter array, hidden other than 64, or policy flags other than MRL_POLICY_GREEDY", what);
+        return MRL_ERR_INVALID;
+    }
+    if (record && (!record->actions || !record->logprobs || !record->values || !record->rewards || !record->dones || !record->next_done)) {
+        mrl::set_error("%s: the record needs every buffer but logits", what);
+        return MRL_ERR_INVALID;
+    }
+    mrl_tensor_desc obs{}, done{}, reward{}, action{};
+    int rc = mrl::guarded([&] {
+        if (!sim->tensor(MRL_OVERCOOKED_OBS_WORLD_MAJOR, &obs) || !sim->tensor(MRL_OVERCOOKED_DONE, &done) ||
+            !sim->tensor(MRL_OVERCOOKED_REWARD, &reward) || !sim->tensor(MRL_OVERCOOKED_ACTION, &action))
+            throw std::runtime_error("the simulator does not export OBS_WORLD_MAJOR / DONE / REWARD / ACTION");
+    });
+    if (rc) return rc;
+    const uint32_t P = (uint32_t)obs.shape[1], H = (uint32_t)obs.shape[2], W = (uint32_t)obs.shape[3], F = (uint32_t)obs.shape[4];
+    if (W < 3 || H < 3) {
+        mrl::set_error("%s: a %u x %u kitchen has no 3 x 3 patch", what, W, H);
+        return MRL_ERR_INVALID;
+    }
+    if (players == 0 || (P < 32 && (players >> P) != 0)) {
+        mrl::set_error("%s: players = 0x%x must name at least one seat and none beyond the simulator's %u", what, players, P);
+        return MRL_ERR_INVALID;
+    }
+    const mrl::CnnLds lds = mrl::cnn_lds(W, H, F);
+    if (lds.total > mrl::kCnnLdsLimit) {
+        mrl::set_error("%s: a %u x %u kitchen with %u channels needs an LDS image of %u bytes per workgroup, the limit is %u", what, W, H, F,
+                       lds.total, mrl::kCnnLdsLimit);
+        return MRL_ERR_INVALID;
+    }
+    mrl::CnnActArgs &a = *args;
+    a = mrl::CnnActArgs{};
+    a.params = policy->params_dev;
+    a.done = static_cast<const int32_t *>(done.data);
+    a.reward = static_cast<const int32_t *>(reward.data);
+    a.action = static_cast<int32_t *>(action.data);
+    a.W = W, a.H = H, a.F = F, a.P = P, a.num_worlds = sim->num_worlds;
+    a.players = players, a.num_seats = (uint32_t)__builtin_popcount(players);
+    a.lds = lds;
+    return MRL_OK;
+}
+
+// the rows of `record` an act at `row` writes (value_only: the closing act at row T)
+static void cnn_rows(mrl::CnnActArgs &a, const mrl_cnn_record *record, uint32_t row, bool value_only)
+{
+    a.actions_row = nullptr, a.logprobs_row = a.values_row = a.rewards_row = a.dones_row = a.logits_row = nullptr;
+    a.nets = 1u;
+    if (!record) return;
+    const size_t cells = (size_t)a.num_worlds * a.P;
+    a.nets = value_only ? 2u : 3u;
+    a.values_row = record->values + row * cells;
+    a.rewards_row = row ? record->rewards + (row - 1) * cells : nullptr;
+    a.dones_row = value_only ? record->next_done : record->dones + row * cells;
+    if (value_only) return;
+    a.actions_row = record->actions + row * cells;
+    a.logprobs_row = record->logprobs + row * cells;
+    a.logits_row = record->logits ? record->logits + row * cells * mrl::kCnnActions : nullptr;
+}
+
+int mrl_cnn_act(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, const mrl_cnn_record *record, uint32_t row, uint64_t seed,
+                uint32_t step, uint32_t flags, void *workspace_dev, uint64_t workspace_bytes, void *hip_stream)
+{
+    mrl::CnnActArgs args{};
+    if (int rc = cnn_prepare(sim, players, policy, record, hip_stream, "mrl_cnn_act", &args)) return rc;
+    if (flags & ~(uint32_t)(MRL_POLICY_GREEDY | MRL_CNN_VALUE_ONLY)) {
+        mrl::set_error("mrl_cnn_act: flags 0x%x: only MRL_POLICY_GREEDY and MRL_CNN_VALUE_ONLY exist", flags);
+        return MRL_ERR_INVALID;
+    }
+    flags |= policy->flags;  // MRL_POLICY_GREEDY may travel with the policy (mrl_rollout_cnn has no flags of its own)
+    const bool value_only = flags & MRL_CNN_VALUE_ONLY;
+    if (value_only ? (!record || row != record->num_steps) : (record && row >= record->num_steps)) {
+        mrl::set_error("mrl_cnn_act: row %u of %u; MRL_CNN_VALUE_ONLY needs a record and row == num_steps, every other act row < num_steps", row,
+                       record ? record->num_steps : 0u);
+        return MRL_ERR_INVALID;
+    }
+    if (!workspace_dev || (reinterpret_cast<uintptr_t>(workspace_dev) & 15u) ||
+        workspace_bytes < mrl_cnn_workspace_bytes(sim->num_worlds, args.P)) {
+        mrl::set_error("mrl_cnn_act: the workspace is null, off a 16-byte boundary or smaller than mrl_cnn_workspace_bytes");
+        return MRL_ERR_INVALID;
+    }
+    mrl::DeviceGuard on(sim->device);
+    return mrl::guarded([&] {
+        args.obs = static_cast<const int8_t *>(sim->observation_source());
+        if (!args.obs) throw std::runtime_error("mrl_cnn_act: the simulator has no observation slab");
+        cnn_rows(args, record, row, value_only);
+        args.seed = seed, args.step = step, args.flags = flags;
+        mrl::launch_cnn_act(args, (hipStream_t)hip_stream);
+    });
+}
+
+int mrl_rollout_cnn(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, const mrl_cnn_record *record, void *obs_ring_dev,
+                    uint64_t seed, uint32_t first_step, void *hip_stream)
+{
+    mrl::CnnActArgs args{};
+    if (int rc = cnn_prepare(sim, players, policy, record, hip_stream, "mrl_rollout_cnn", &args)) return rc;
+    if (!record || !obs_ring_dev) {
+        mrl::set_error("mrl_rollout_cnn: null record or observation ring");
+        return MRL_ERR_INVALID;
+    }
+    mrl::DeviceGuard on(sim->device);
+    return mrl::guarded([&] {
+        hipStream_t stream = (hipStream_t)hip_stream;
+        const uint32_t T = record->num_steps;
+        const uint64_t slot_bytes = sim->observation_bytes();
+        uint8_t *ring = static_cast<uint8_t *>(obs_ring_dev);
+        const void *current = sim->observation_source();
+        if (!current || !slot_bytes) throw std::runtime_error("mrl_rollout_cnn: the simulator has no observation slab");
+        if (current != ring) MRL_HIP(hipMemcpyAsync(ring, current, slot_bytes, hipMemcpyDeviceToDevice, stream));
+        const mrl_sim::ObservationRing before = sim->observation_ring();
+        struct HandBack {  // also when a launch throws
+            mrl_sim *sim;
+            const mrl_sim::ObservationRing &ring;
+            bool armed;
+            ~HandBack()
+            {
+                if (armed) sim->restore_observation_ring(ring);
+            }
+        } hand_back{sim, before, T > 0};
+        if (T) sim->set_observation_ring(ring + slot_bytes, slot_bytes, T);  // step k writes slot k + 1
+        args.seed = seed;
+        for (uint32_t k = 0; k <= T; k++) {
+            const bool closing = k == T;
+            args.obs = reinterpret_cast<const int8_t *>(ring + (size_t)k * slot_bytes);
+            cnn_rows(args, record, k, closing);
+            args.step = first_step + k;
+            args.flags = policy->flags | (closing ? (uint32_t)MRL_CNN_VALUE_ONLY : 0u);
+            mrl::launch_cnn_act(args, stream);
+            if (closing) break;
+            sim->step(nullptr, stream);
+            mrl::completed_step(sim, stream);
+        }
+        if (T) {
+            // the output goes back to where it pointed, and that place receives slot T: the simulator's observations are then
+            // what T mrl_step_with_actions calls would have left there, and the next act or rollout reads them
+            hand_back.armed = false;
+            sim->restore_observation_ring(before);
+            void *home = const_cast<void *>(sim->observation_source());
+            const uint8_t *last = ring + (size_t)T * slot_bytes;
+            if (home != last) MRL_HIP(hipMemcpyAsync(home, last, slot_bytes, hipMemcpyDeviceToDevice, stream));
+        }
     });
 }
 

@@ -245,6 +245,17 @@ struct mrl_sim {
     virtual uint64_t observation_bytes() const { return 0; }
     // mrl_set_observation_ring: step number k after this call writes its slab to base + (k % num_slots) * stride_bytes
     virtual void set_observation_ring(void *, uint64_t, uint32_t) {}
+    // mrl_cnn_act / mrl_rollout_cnn (host only): where the observations the most recent step wrote lie -- before any step since
+    // the output was set, where the next step will write -- nullptr for a game without a redirectable slab; and the ring as
+    // it stands (base == nullptr: the simulator's own tensor), so that a call which borrows the output can hand it back.
+    struct ObservationRing {
+        void *base = nullptr;
+        uint64_t stride = 0, position = 0;
+        uint32_t slots = 1;
+    };
+    virtual const void *observation_source() const { return nullptr; }
+    virtual ObservationRing observation_ring() const { return {}; }
+    virtual void restore_observation_ring(const ObservationRing &) {}
     // mrl_prepare_graph_capture: from now on the launch-to-launch state lives in device memory (see LaunchState); games
     // without such state have nothing to do.  capturable(): may this simulator's launches be captured right now?
     virtual void prepare_graph_capture(hipStream_t) {}

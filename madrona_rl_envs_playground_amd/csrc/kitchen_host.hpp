@@ -243,6 +243,23 @@ template <class Params> struct KitchenSim : mrl_sim {
         else
             ring_changed(ring_base, ring_stride, ring_slots);
     }
+    const void *observation_source() const override
+    {
+        const uint64_t slot = ring_pos ? (ring_pos - 1) % ring_slots : 0;
+        return ring_base + (size_t)slot * ring_stride;
+    }
+    ObservationRing observation_ring() const override
+    {
+        ObservationRing ring;
+        ring.base = ring_base == own_obs ? nullptr : ring_base;
+        ring.stride = ring_stride, ring.slots = ring_slots, ring.position = ring_pos;
+        return ring;
+    }
+    void restore_observation_ring(const ObservationRing &ring) override
+    {
+        set_observation_ring(ring.base, ring.stride, ring.slots);
+        ring_pos = ring.position;
+    }
     // the slot(s) of the next `steps` steps: single-step launches get the slot as their `obs`, multi-step ones the first index
     uint8_t *take_slots(uint32_t steps, uint32_t *first)
     {

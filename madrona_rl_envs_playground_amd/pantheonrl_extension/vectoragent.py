@@ -30,6 +30,47 @@ class RandomVectorAgent(VectorAgent):
         return None
 
 
+class CnnPolicyAgent(VectorAgent):
+    """A player of ``OvercookedMadrona`` that acts under MAPPO's CNN policy on the device: ``get_action`` is ``mrl_cnn_act`` for this
+    agent's seat -- ``player_num``, set by ``env.add_partner_agent``, or, while that is ``None``, the env's ``ego_ind`` -- on the
+    simulator's own observations, and returns the view ``env.static_actions[seat]``.  ``policy``: a ``simulators.CnnPolicy``;
+    ``seed`` seeds the draws, whose step number counts this agent's calls.  ``update`` does nothing.  Any env other than an
+    ``OvercookedMadrona`` on the GPU is refused with a ``TypeError`` by the constructor: there is no torch fallback.  ``obs`` and
+    ``record`` of ``get_action`` are the ``VectorAgent`` protocol's; the kernel reads the simulator's observations itself and this
+    agent keeps no buffers."""
+
+    def __init__(self, envs, policy, seed=0, greedy=False):
+        self.envs, self.policy, self.seed, self.greedy = envs, policy, int(seed), bool(greedy)
+        self.player_num = None
+        self._draws = 0
+        self._sim = self._check_env()
+
+    def _check_env(self):
+        from ..envs.overcooked_env import OvercookedMadrona
+        from ..simulators import OvercookedSimulator, SimplecookedSimulator
+        envs = self.envs
+        sim = getattr(envs, "sim", None)
+        if not isinstance(envs, OvercookedMadrona) or not isinstance(sim, OvercookedSimulator) or isinstance(sim, SimplecookedSimulator):
+            raise TypeError("CnnPolicyAgent acts through mrl_cnn_act: envs must be an OvercookedMadrona, got "
+                            f"{type(envs).__name__} over {type(sim).__name__}; there is no torch fallback")
+        if envs.device.type != "cuda":
+            raise TypeError(f"CnnPolicyAgent needs the env on the simulator's GPU (cuda:{sim.gpu_id}); got env device {envs.device}")
+        return sim
+
+    @property
+    def seat(self):
+        return self.envs.ego_ind if self.player_num is None else self.player_num
+
+    def get_action(self, obs=None, record=True):
+        from ..simulators import cnn_act
+        cnn_act(self._sim, self.policy, 1 << self.seat, seed=self.seed, step=self._draws, greedy=self.greedy)
+        self._draws += 1
+        return self.envs.static_actions[self.seat]
+
+    def update(self, rewards, dones):
+        return None
+
+
 class CleanPPOAgent(VectorAgent):
     """The reference's PPO agent for Hanabi and the balance beam (/root/reference/pantheonrl_extension/vectoragent.py:116-372;
     built twice, ego and partner, by scripts/hanabi_train.py and scripts/balance_train.py) with its collection phase on the

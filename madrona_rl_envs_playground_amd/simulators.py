@@ -245,6 +245,201 @@ class MlpPolicy:
         return agent
 
 
+class _CnnLayer(torch.nn.Module):
+    """train/MAPPO/utils/cnn.py:11-42 for use_ReLU: ``cnn`` = Conv2d 3 x 3, ReLU, Flatten, Linear, ReLU, Linear, ReLU"""
+
+    def __init__(self, width, height, channels, hidden):
+        super().__init__()
+        nn = torch.nn
+        self.cnn = nn.Sequential(nn.Conv2d(channels, hidden // 2, kernel_size=3, stride=1), nn.ReLU(), nn.Flatten(),
+                                 nn.Linear(hidden // 2 * (width - 2) * (height - 2), hidden), nn.ReLU(), nn.Linear(hidden, hidden), nn.ReLU())
+
+    def forward(self, x):
+        return self.cnn(x.movedim(-1, -3))
+
+
+class _CnnBase(torch.nn.Module):
+    def __init__(self, width, height, channels, hidden):
+        super().__init__()
+        self.cnn = _CnnLayer(width, height, channels, hidden)
+
+    def forward(self, x):
+        return self.cnn(x)
+
+
+class _CategoricalHead(torch.nn.Module):
+    def __init__(self, hidden, num_actions):
+        super().__init__()
+        self.linear = torch.nn.Linear(hidden, num_actions)
+
+
+class _ActLayer(torch.nn.Module):
+    def __init__(self, hidden, num_actions):
+        super().__init__()
+        self.action_out = _CategoricalHead(hidden, num_actions)
+
+
+class _CnnActor(torch.nn.Module):
+    """``R_Actor``'s parameters by name for the CNN, non-recurrent configuration: ``base.cnn.cnn.0/3/5``, ``act.action_out.linear``"""
+
+    def __init__(self, width, height, channels, hidden, num_actions):
+        super().__init__()
+        self.base = _CnnBase(width, height, channels, hidden)
+        self.act = _ActLayer(hidden, num_actions)
+
+    def forward(self, obs):
+        return self.act.action_out.linear(self.base(obs))
+
+
+class _CnnCritic(torch.nn.Module):
+    """``R_Critic``'s parameters by name without PopArt: ``base.cnn.cnn.0/3/5``, ``v_out``"""
+
+    def __init__(self, width, height, channels, hidden):
+        super().__init__()
+        self.base = _CnnBase(width, height, channels, hidden)
+        self.v_out = torch.nn.Linear(hidden, 1)
+
+    def forward(self, state):
+        return self.v_out(self.base(state))
+
+
+class CnnActorCritic(torch.nn.Module):
+    """MAPPO's CNN actor-critic for Overcooked (train/MAPPO/utils/cnn.py:26-42, r_actor_critic.py, utils/distributions.py:55-68;
+    non-recurrent, no PopArt, ``hidden_size`` 64): ``actor`` and ``critic`` take the (N, W, H, F) observation as floats.  Their
+    state dicts have the reference's keys, so ``actor.load_state_dict`` / ``critic.load_state_dict`` take a reference checkpoint's
+    two files.  Initialisation is the reference's: orthogonal weights with the ReLU gain, 0.01 for the action head (``args.gain``),
+    1 for ``v_out`` (r_actor_critic.py:136-142), zero biases."""
+
+    def __init__(self, width, height, channels, hidden=64, num_actions=6):
+        super().__init__()
+        self.width, self.height, self.channels, self.hidden, self.num_actions = int(width), int(height), int(channels), int(hidden), int(num_actions)
+        self.actor = _CnnActor(self.width, self.height, self.channels, self.hidden, self.num_actions)
+        self.critic = _CnnCritic(self.width, self.height, self.channels, self.hidden)
+        relu_gain = torch.nn.init.calculate_gain("relu")
+        for net, head, head_gain in ((self.actor, self.actor.act.action_out.linear, 0.01), (self.critic, self.critic.v_out, 1.0)):
+            for i in (0, 3, 5):
+                torch.nn.init.orthogonal_(net.base.cnn.cnn[i].weight, gain=relu_gain)
+                torch.nn.init.constant_(net.base.cnn.cnn[i].bias, 0.0)
+            torch.nn.init.orthogonal_(head.weight, gain=head_gain)
+            torch.nn.init.constant_(head.bias, 0.0)
+
+    def get_value(self, state):
+        return self.critic(state)
+
+    def get_action_and_value(self, obs, action=None, deterministic=False):
+        dist = torch.distributions.Categorical(logits=self.actor(obs))
+        if action is None:
+            action = dist.probs.argmax(dim=-1) if deterministic else dist.sample()
+        return action, dist.log_prob(action), dist.entropy(), self.critic(obs)
+
+
+class CnnPolicy:
+    """The parameters ``mrl_cnn_act`` runs: one flat float32 tensor ``params``, the actor's eight tensors and then the critic's in
+    the order of ``parameters_to_vector(CnnActorCritic.parameters())`` (``mrl_cnn_policy``).  ``module()`` returns a
+    ``CnnActorCritic`` whose parameters are VIEWS into ``params``: an optimizer's in-place step on them is what the kernel reads
+    next, with no copy in between (so there is no ``load_``)."""
+
+    def __init__(self, width, height, channels, hidden=64, num_actions=6, device="cuda:0"):
+        self.width, self.height, self.channels, self.hidden, self.num_actions = int(width), int(height), int(channels), int(hidden), int(num_actions)
+        if self.num_params == 0:
+            raise ValueError(f"mrl_cnn_act runs hidden = {_lib.CNN_HIDDEN}, num_actions = {_lib.CNN_ACTIONS} and kitchens of at least 3 x 3")
+        self.params = torch.zeros(self.num_params, dtype=torch.float32, device=torch.device(device))
+        self._module = None
+
+    @property
+    def num_params(self):
+        return int(_lib.lib().mrl_cnn_policy_num_params(self.width, self.height, self.channels, self.hidden, self.num_actions))
+
+    @classmethod
+    def from_module(cls, module, device=None):
+        """A policy of ``module``'s shape (a ``CnnActorCritic``) holding a copy of its parameters (``device``: default its own)."""
+        if not isinstance(module, CnnActorCritic):
+            raise ValueError("module must be a CnnActorCritic")
+        own = next(module.parameters()).device
+        policy = cls(module.width, module.height, module.channels, module.hidden, module.num_actions, device if device is not None else own)
+        with torch.no_grad():
+            policy.params.copy_(torch.nn.utils.parameters_to_vector(module.parameters()).detach())
+        return policy
+
+    def module(self):
+        """The ``CnnActorCritic`` whose parameters alias ``params`` (one object per policy)."""
+        if self._module is None:
+            module = CnnActorCritic(self.width, self.height, self.channels, self.hidden, self.num_actions)
+            at = 0
+            for p in module.parameters():  # actor first, then critic: the order of the flat array
+                p.data = self.params[at:at + p.numel()].view(p.shape)
+                at += p.numel()
+            assert at == self.params.numel()
+            self._module = module
+        return self._module
+
+    def desc(self):
+        return _lib.CnnPolicyDesc(self.params.data_ptr(), self.hidden, 0)
+
+
+class CnnRecord:
+    """The buffers of ``mrl_cnn_act`` / ``mrl_rollout_cnn`` (``mrl_cnn_record``): torch tensors by name plus the ctypes struct over
+    them.  ``actions`` int32, ``logprobs``, ``rewards``, ``dones`` (T, N, P); ``values`` (T + 1, N, P), row T the closing value;
+    ``next_done`` (N, P); ``logits`` (T, N, P, 6) on request."""
+
+    def __init__(self, num_steps, num_worlds, num_players, device, logits=False):
+        t, n, p = int(num_steps), int(num_worlds), int(num_players)
+        z = lambda shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=device)  # noqa: E731
+        self.num_steps, self.num_worlds, self.num_players = t, n, p
+        self.actions = z((t, n, p), torch.int32)
+        self.logprobs, self.rewards, self.dones = z((t, n, p)), z((t, n, p)), z((t, n, p))
+        self.values, self.next_done = z((t + 1, n, p)), z((n, p))
+        self.logits = z((t, n, p, _lib.CNN_ACTIONS)) if logits else None
+        self.struct = _lib.CnnRecordDesc(*[getattr(self, name).data_ptr() if getattr(self, name) is not None else None
+                                           for name in _lib.CNN_RECORD_BUFFERS], t)
+
+    def rollout(self):
+        """The record as the ``Rollout`` that ``gae`` takes: views flattened to N * P columns, ``next_value`` = ``values[T]``."""
+        t, cols = self.num_steps, self.num_worlds * self.num_players
+        flat = lambda x: x.view(t, cols)  # noqa: E731
+        return Rollout(None, flat(self.actions), flat(self.logprobs), self.values[:t].view(t, cols), flat(self.rewards), flat(self.dones),
+                       None, self.values[t].view(cols), self.next_done.view(cols))
+
+
+def _cnn_call_args(sim, policy, players, record):
+    if not isinstance(policy, CnnPolicy):
+        raise ValueError("policy must be a CnnPolicy")
+    p = policy.params
+    if not p.is_cuda or p.device.index != sim.gpu_id or p.dtype != torch.float32 or not p.is_contiguous() or p.numel() != policy.num_params:
+        raise ValueError(f"policy.params must be a contiguous float32 tensor of num_params elements on cuda:{sim.gpu_id}")
+    shape = sim.observation_world_major_tensor().shape  # (N, P, H, W, F)
+    if (policy.height, policy.width, policy.channels) != tuple(shape[2:]):
+        raise ValueError(f"the policy is for a {policy.width} x {policy.height} kitchen with {policy.channels} channels, the simulator's "
+                         f"is {shape[3]} x {shape[2]} with {shape[4]}")
+    if record is not None and (not isinstance(record, CnnRecord) or record.num_worlds != shape[0] or record.num_players != shape[1] or
+                               record.actions.device != p.device):
+        raise ValueError(f"record must be a CnnRecord of {shape[0]} worlds and {shape[1]} players on cuda:{sim.gpu_id}")
+    mask = (1 << shape[1]) - 1 if players is None else players
+    if not isinstance(mask, int):
+        mask = sum(1 << int(seat) for seat in mask)
+    return mask & 0xFFFFFFFF if 0 <= mask < 2 ** 32 else 0xFFFFFFFF
+
+
+def cnn_act(sim, policy, players=None, record=None, row=0, seed=0, step=0, greedy=False, value_only=False, workspace=None):
+    """``mrl_cnn_act`` on torch's current stream of the simulator's device: the seats in ``players`` (a bit mask or an iterable of
+    seats; default all) of an Overcooked simulator act under ``policy`` (a ``CnnPolicy``) on the observations the simulator's
+    most recent step wrote, wherever that was; with ``record`` (a ``CnnRecord``) row ``row`` of its buffers is written.
+    ``value_only``: the closing act at row T.  ``workspace``: default one the simulator keeps."""
+    mask = _cnn_call_args(sim, policy, players, record)
+    if workspace is None:
+        workspace = getattr(sim, "_cnn_workspace", None)
+        if workspace is None:
+            size = int(sim._L.mrl_cnn_workspace_bytes(sim.num_worlds, sim.observation_world_major_tensor().shape[1]))
+            workspace = sim._cnn_workspace = torch.empty(size, dtype=torch.uint8, device=torch.device("cuda", sim.gpu_id))
+    flags = (_lib.POLICY_GREEDY if greedy else 0) | (_lib.CNN_VALUE_ONLY if value_only else 0)
+    desc = policy.desc()
+    rc = sim._L.mrl_cnn_act(sim._handle, mask, ctypes.byref(desc), ctypes.byref(record.struct) if record is not None else None, int(row),
+                            int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF, flags, workspace.data_ptr(), workspace.numel(),
+                            _stream_ptr(sim.gpu_id))
+    if rc:
+        _lib.check(rc)
+
+
 def _wide_mlp(inputs, outputs, hidden=_lib.WIDE_HIDDEN):
     nn = torch.nn
     return nn.Sequential(nn.Linear(inputs, hidden), nn.ReLU(), nn.Linear(hidden, hidden), nn.ReLU(), nn.Linear(hidden, hidden), nn.ReLU(),
@@ -695,6 +890,24 @@ class _Simulator:
         _lib.check(self._L.mrl_rollout_policy(self._handle, ctypes.byref(desc), ctypes.byref(buffers),
                                               int(seed) & (2 ** 64 - 1), int(first_step) & 0xFFFFFFFF, _stream_ptr(self.gpu_id)))
         return out
+
+    def rollout_cnn(self, policy, record, obs_ring, players=None, seed=0, first_step=0, greedy=False):
+        """``record.num_steps`` steps under ``policy`` (a ``CnnPolicy``) for the seats in ``players`` with the host out of the loop
+        (``mrl_rollout_cnn``; Overcooked): ``obs_ring`` is int8 (T + 1, N, P, H, W, F), contiguous; slot 0 receives the current
+        observations, the act of step k reads slot k and the step writes slot k + 1.  Afterwards the observation output is what
+        it was before and holds slot T, the observations of the state the simulator is in: the next act or rollout goes on from
+        there.  ``greedy`` travels in the policy descriptor's flags.  The draw of (step index ``first_step + k``, world, seat) is ``random_hash``'s."""
+        mask = _cnn_call_args(self, policy, players, record)
+        if record is None:
+            raise ValueError("rollout_cnn needs a CnnRecord")
+        want = (record.num_steps + 1,) + tuple(self.observation_world_major_tensor().shape)
+        if (not isinstance(obs_ring, torch.Tensor) or not obs_ring.is_cuda or obs_ring.device.index != self.gpu_id or
+                obs_ring.dtype not in (torch.int8, torch.uint8) or tuple(obs_ring.shape) != want or not obs_ring.is_contiguous()):
+            raise ValueError(f"obs_ring must be a contiguous int8 tensor of shape {want} on cuda:{self.gpu_id}")
+        desc = policy.desc()
+        desc.flags = _lib.POLICY_GREEDY if greedy else 0
+        _lib.check(self._L.mrl_rollout_cnn(self._handle, mask, ctypes.byref(desc), ctypes.byref(record.struct), obs_ring.data_ptr(),
+                                           int(seed) & (2 ** 64 - 1), int(first_step) & 0xFFFFFFFF, _stream_ptr(self.gpu_id)))
 
     def reset_worlds(self, mask=None):
         """Restart the worlds whose ``mask`` entry is nonzero (``None``: every world) as fresh episodes, enqueued on torch's
