@@ -303,8 +303,26 @@ class CartpoleOracle:
             pass
 
 
+def check_hanabi_config(config):
+    """ValueError for a game the reference's sim.cpp cannot hold: it takes any five numbers and then indexes out of bounds
+    (a negative deck size kills the process).  The limits are the HIP library's (mrl_hanabi_create): two players, 1..5
+    colours, 2..5 ranks, 1..8 information tokens, 1..3 life tokens, and a deck of at least zero cards once two hands of
+    five are dealt.  Decided here, before any compiled code sees the configuration."""
+    k, r, players = int(config["colors"]), int(config["ranks"]), int(config["players"])
+    info, life = int(config["max_information_tokens"]), int(config["max_life_tokens"])
+    if players != 2:
+        raise ValueError(f"hanabi: players must be 2, got {players}")
+    if not (1 <= k <= 5 and 2 <= r <= 5 and 1 <= info <= 8 and 1 <= life <= 3):
+        raise ValueError(f"hanabi: need 1..5 colors, 2..5 ranks, 1..8 information tokens, 1..3 life tokens, got "
+                         f"{k}, {r}, {info}, {life}")
+    deck = (4 + 2 * (r - 2)) * k - 10
+    if deck < 0:
+        raise ValueError(f"hanabi: {k} colors of {r} ranks are {deck + 10} cards, fewer than the two hands of five")
+
+
 class HanabiOracle:
     def __init__(self, config, num_worlds, num_threads=1, first_episode=0):
+        check_hanabi_config(config)
         self.L = lib()
         self.N = int(num_worlds)
         self.num_threads = num_threads

@@ -7,7 +7,8 @@ The kitchens take two more options, for what Madrona leaves open: ``graph_order`
 insertion order, 1: a second topological order) and ``reverse_entities`` (a node visits its entities in descending
 creation order); see madrona_standin/madrona/taskgraph_builder.hpp.  A configuration the C++ cannot hold raises
 ValueError: Overcooked above 255 cells or 64 players, Simplecooked above 100 cells or with any player count but two
-(with one player its dish-pickup shaping reads a second agent that was never created).
+(with one player its dish-pickup shaping reads a second agent that was never created), Hanabi outside the HIP library's
+ranges or with fewer than ten cards (oracle.check_hanabi_config: decided in Python, the C++ is never entered).
 
 ``build(reference_dir)`` runs the recipe; ``require()`` is what a test calls first: it skips (with the
 reason) when oracle/_ref/BUILD_INFO is missing, i.e. the reference tree was never there to build from, and
@@ -19,7 +20,7 @@ import subprocess
 
 import numpy as np
 
-from oracle.oracle import HANABI_MOVES, HANABI_OBS, HANABI_STATE, HanabiConfig
+from oracle.oracle import HANABI_MOVES, HANABI_OBS, HANABI_STATE, HanabiConfig, check_hanabi_config
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 REF_DIR = os.path.join(_HERE, "_ref")
@@ -147,6 +148,7 @@ class RefHanabi(_Ref):
     game = "hanabi"
 
     def __init__(self, config, num_worlds, first_episode=0, fill=0x00, construct=False):
+        check_hanabi_config(config)  # sim.cpp takes anything and indexes out of bounds with a negative deck
         self.L = lib(self.game)
         self.N = N = int(num_worlds)
         self._act_shape = (2, N)

@@ -1,4 +1,4 @@
-"""Writes tests/golden/hanabi_ref_{full,small,very_small}.npz, cartpole_ref.npz and the kitchens' overcooked_ref_*.npz /
+"""Writes tests/golden/hanabi_ref_{full,small,very_small,k5r3i8l3,k2r4i1l1,k4r5i5l2}.npz, cartpole_ref.npz and the kitchens' overcooked_ref_*.npz /
 simplecooked_ref_*.npz: action streams and what the reference's
 OWN sim.cpp computed for them, compiled unchanged against the Madrona stand-in (oracle/_ref, built by build() when the
 reference tree is present; oracle/ref.py).  Data only, packed the way tests/conftest.py:load_golden reads them, so that the
@@ -13,7 +13,7 @@ layout has one, the others play at random); per step every viewer's observation 
 channels as bytes), reward and done, and the internal state after the last step.  overcooked_ref_limits.npz holds three
 streams side by side: recipe times 127 and 128 (the int8_t tick reaches 127 / wraps past it) and recipe values 300.
 
-    python tests/golden/make_ref_golden.py [kitchens]
+    python tests/golden/make_ref_golden.py [kitchens | hanabi NAME...]
 """
 import os
 import sys
@@ -32,6 +32,11 @@ CONFIGS = {
     "full": (dict(colors=5, ranks=5, players=2, max_information_tokens=8, max_life_tokens=3), 48, 200),
     "small": (dict(colors=2, ranks=5, players=2, max_information_tokens=3, max_life_tokens=1), 48, 150),
     "very_small": (dict(colors=1, ranks=5, players=2, max_information_tokens=3, max_life_tokens=1), 32, 60),
+    # beyond the named games (tests/hanabi_configs.py): three ranks with K > R, four ranks with K < R, four colours of five;
+    # small's steps, and its worlds where the file stays no larger than small's (their rows are longer)
+    "k5r3i8l3": (dict(colors=5, ranks=3, players=2, max_information_tokens=8, max_life_tokens=3), 36, 150),
+    "k2r4i1l1": (dict(colors=2, ranks=4, players=2, max_information_tokens=1, max_life_tokens=1), 48, 150),
+    "k4r5i5l2": (dict(colors=4, ranks=5, players=2, max_information_tokens=5, max_life_tokens=2), 33, 150),
 }
 
 
@@ -68,10 +73,13 @@ def kitchens():
 
 
 def main():
-    kitchens()
+    if sys.argv[1:2] != ["hanabi"]:
+        kitchens()
     if sys.argv[1:] == ["kitchens"]:
         return
     for name, (cfg, n, steps) in CONFIGS.items():
+        if sys.argv[1:2] == ["hanabi"] and name not in sys.argv[2:]:
+            continue
         no, ns = hanabi_spec.observation_size(cfg), hanabi_spec.state_size(cfg)
         r = ref.RefHanabi(cfg, n)
         rng = np.random.default_rng(2026)
@@ -94,6 +102,8 @@ def main():
                             **packed("first_obs", first["obs"]), **packed("first_state", first["state"]))
         print(f"{out}: {n} worlds x {steps} steps, {r.episodes} episodes, {os.path.getsize(out) / 1024:.0f} KiB")
 
+    if sys.argv[1:2] == ["hanabi"]:
+        return
     n, steps = 64, 300
     r = ref.RefCartpole(n)
     rng = np.random.default_rng(2026)

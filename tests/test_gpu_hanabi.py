@@ -8,6 +8,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import hanabi_configs  # noqa: E402
 from madrona_rl_envs_playground_amd import hanabi_spec  # noqa: E402
 from madrona_rl_envs_playground_amd._lib import debug_knobs  # noqa: E402
 from madrona_rl_envs_playground_amd.simulators import ExecMode, HanabiSimulator  # noqa: E402
@@ -483,7 +484,9 @@ def test_persistent_rollout_vs_compiled_reference(n, chunk, chunks, hip_lib):
     sim.close()
 
 
-@pytest.mark.parametrize("name,cfg", [("full", FULL), ("small", SMALL), ("very_small", VERY_SMALL)], ids=["full", "small", "very_small"])
+@pytest.mark.parametrize("name,cfg", [("full", FULL), ("small", SMALL), ("very_small", VERY_SMALL)] +
+                         [(cid, hanabi_configs.BY_ID[cid]) for cid in ("k5r3i8l3", "k2r4i1l1", "k4r5i5l2")],
+                         ids=["full", "small", "very_small", "k5r3i8l3", "k2r4i1l1", "k4r5i5l2"])
 @pytest.mark.parametrize("fused", [1, 2], ids=["one_launch", "two_launches"])
 def test_step_reproduces_compiled_reference_fixture(name, cfg, fused, hip_lib):
     """tests/golden/hanabi_ref_<cfg>.npz (the reference's own sim.cpp, tests/golden/make_ref_golden.py) on the GPU."""

@@ -11,6 +11,8 @@ import pytest
 from conftest import load_golden
 from madrona_rl_envs_playground_amd import hanabi_spec
 
+import hanabi_configs
+
 CONFIGS = {
     "full": dict(colors=5, ranks=5, players=2, max_information_tokens=8, max_life_tokens=3),
     "small": dict(colors=2, ranks=5, players=2, max_information_tokens=3, max_life_tokens=1),
@@ -343,13 +345,16 @@ def test_endings_and_next_episodes_by_hand(policy, steps, reason, oracle_lib):
     assert reasons == {reason} and started >= n
 
 
-@pytest.mark.parametrize("name", list(CONFIGS))
+REF_FIXTURES = dict(CONFIGS, **{cid: hanabi_configs.BY_ID[cid] for cid in ("k5r3i8l3", "k2r4i1l1", "k4r5i5l2")})
+
+
+@pytest.mark.parametrize("name", list(REF_FIXTURES))
 def test_oracle_reproduces_compiled_reference_fixture(name, oracle_lib):
     """tests/golden/hanabi_ref_<cfg>.npz: what the reference's own sim.cpp (compiled against the Madrona stand-in,
     tests/golden/make_ref_golden.py) computed -- every section of both agents' rows, hint-heavy streams included; this keeps
     the oracle pinned where oracle/_ref is not built."""
     z = load_golden(f"hanabi_ref_{name}.npz")
-    cfg = CONFIGS[name]
+    cfg = REF_FIXTURES[name]
     no, ns = hanabi_spec.observation_size(cfg), hanabi_spec.state_size(cfg)
     n = z["actions"].shape[2]
     orc = oracle_lib.HanabiOracle(cfg, n)
@@ -362,3 +367,91 @@ def test_oracle_reproduces_compiled_reference_fixture(name, oracle_lib):
         for k in ("mask", "active", "reward", "done"):
             assert np.array_equal(getattr(orc, k), z[k][t]), f"{k}, step {t}"
     assert orc.episodes == int(z["episodes"])
+
+
+# ---------------------------------------------------------------------------------------------
+# Games beyond the three named ones (tests/hanabi_configs.py)
+# ---------------------------------------------------------------------------------------------
+def test_config_list_keeps_its_spread():
+    """What makes hanabi_configs.CONFIGS worth running, so that an edit cannot lose it."""
+    cfgs = hanabi_configs.CONFIGS
+    pairs = [(c["colors"], c["ranks"]) for c in cfgs]
+    decks = [hanabi_configs.deck_size(c) for c in cfgs]
+    assert len(cfgs) == 14 and len(set(hanabi_configs.IDS)) == 14 and all(c["players"] == 2 for c in cfgs)
+    assert hanabi_configs.IDS[0] == "k3r5i8l3"
+    assert {r for _, r in pairs} == {2, 3, 4, 5}                                      # every rank count
+    assert (3, 5) in pairs and (4, 5) in pairs                                         # variant 1 beyond 1, 2 and 5 colours
+    assert any(k > r for k, r in pairs) and any(k < r for k, r in pairs)
+    assert any(k == r != 5 for k, r in pairs)
+    assert 0 in decks and 2 in decks and max(decks) >= 20 and min(decks) >= 0
+    assert {1, 2, 8} <= {c["max_information_tokens"] for c in cfgs}
+    assert {c["max_life_tokens"] for c in cfgs} == {1, 2, 3}
+    assert {hanabi_configs.variant(c) for c in cfgs} == {0, 1}                         # 2 is the full game alone
+    assert hanabi_configs.variant(CONFIGS["full"]) == 2 and hanabi_configs.variant(CONFIGS["small"]) == 1
+    assert all(hanabi_configs.variant(c) == (1 if c["ranks"] == 5 else 0) for c in cfgs)
+    assert [hanabi_configs.deck_size(CONFIGS[k]) for k in ("full", "small", "very_small")] == [40, 10, 0]
+    # the refused pairs are exactly those of the accepted ranges that have fewer than ten cards
+    short = [(k, r) for k in range(1, 6) for r in range(2, 6) if hanabi_configs.deck_size(hanabi_configs.config(k, r, 3, 1)) < 0]
+    assert sorted(short) == sorted(hanabi_configs.DECKLESS) and not set(pairs) & set(short)
+    for c in cfgs:                                                                     # section sizes: rows fit the arrays
+        assert hanabi_spec.state_size(c) <= 783 and hanabi_spec.num_moves(c) == 10 + c["colors"] + c["ranks"]
+
+
+def _hanabi_classes(oracle_lib, with_ref):
+    classes = [oracle_lib.HanabiOracle]
+    if with_ref:
+        from oracle import ref
+        ref.require()
+        classes.append(ref.RefHanabi)
+    return classes
+
+
+@pytest.mark.parametrize("with_ref", [False, True], ids=["oracle", "compiled_reference"])
+def test_refuses_what_the_reference_cannot_hold(with_ref, oracle_lib):
+    """The reference's sim.cpp takes any five numbers; with fewer than ten cards its deck size is negative and it indexes
+    out of bounds (the process dies).  Both CPU front ends refuse in Python what the HIP library refuses, and hold the
+    smallest decks it accepts."""
+    for cls in _hanabi_classes(oracle_lib, with_ref):
+        for k, r in hanabi_configs.DECKLESS:
+            with pytest.raises(ValueError, match="fewer than the two hands"):
+                cls(hanabi_configs.config(k, r, 3, 1), 4)
+        good = dict(colors=3, ranks=3, players=2, max_information_tokens=4, max_life_tokens=2)
+        for field, low, high in (("colors", 0, 6), ("ranks", 1, 6), ("max_information_tokens", 0, 9), ("max_life_tokens", 0, 4)):
+            for v in (low, high):
+                with pytest.raises(ValueError, match="need 1..5 colors"):
+                    cls(dict(good, **{field: v}), 4)
+        for players in (1, 3):
+            with pytest.raises(ValueError, match="players must be 2"):
+                cls(dict(good, players=players), 4)
+        for (k, r), deck in (((1, 5), 0), ((2, 3), 2), ((3, 2), 2)):
+            cfg = hanabi_configs.config(k, r, 2, 1)
+            assert hanabi_configs.deck_size(cfg) == deck
+            n = 32
+            sim = cls(cfg, n)
+            assert sim.mask[0].any(-1).all() and (sim.active[0] == 1).all()
+            rng = np.random.default_rng(7)
+            ended = 0
+            for _ in range(12):
+                sim.step((rng.random(sim.mask.shape) * (sim.mask != 0)).argmax(-1).astype(np.int32))
+                assert (sim.active.sum(0) == 1).all()
+                ended += int(sim.done.sum())
+            assert ended > 0 and sim.episodes == n + ended
+            sim.close()
+
+
+@pytest.mark.parametrize("cid", hanabi_configs.IDS)
+def test_lockstep_walk_reaches_every_path(cid, oracle_lib):
+    """The CPU twin of test_gpu_hanabi_configs.py:test_lockstep_vs_oracle: the same walk (worlds, seed, steps, policies),
+    the oracle alone.  Every reachable rare path occurs and episodes end, so what the device is compared on there is
+    known to contain them."""
+    cfg = hanabi_configs.BY_ID[cid]
+    orc = oracle_lib.HanabiOracle(cfg, hanabi_configs.WALK_WORLDS, num_threads=4)
+    counts, ended = {}, 0
+    for _, rec, acts in hanabi_configs.walk(orc, cfg, hanabi_configs.WALK_STEPS[cid]):
+        for k, v in hanabi_configs.count_paths(cfg, rec, acts, orc.done).items():
+            counts[k] = counts.get(k, 0) + v
+        ended += int(orc.done.sum())
+    print(f"hanabi {cid} (variant {hanabi_configs.variant(cfg)}, deck {hanabi_configs.deck_size(cfg)}): {ended} episodes ended; paths: {counts}")
+    assert ended > 0
+    for k, v in counts.items():
+        assert v >= 1 or not hanabi_configs.reachable(cfg, k), f"{cid}: the walk never took the path '{k}' ({counts})"

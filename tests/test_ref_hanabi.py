@@ -17,105 +17,22 @@ from madrona_rl_envs_playground_amd import hanabi_spec
 from oracle import ref
 from oracle.oracle import HanabiOracle
 
+import hanabi_configs
+from hanabi_configs import choose, count_paths, reachable, tokens_after_move  # noqa: F401  (choose: test_gpu_hanabi.py imports it from here)
+
 CONFIGS = {
     "full": dict(colors=5, ranks=5, players=2, max_information_tokens=8, max_life_tokens=3),
     "small": dict(colors=2, ranks=5, players=2, max_information_tokens=3, max_life_tokens=1),
     "very_small": dict(colors=1, ranks=5, players=2, max_information_tokens=3, max_life_tokens=1),
 }
-MV_DISCARD, MV_PLAY, MV_INVALID = 0, 1, 4
-HAND = 5
 # very_small deals its 10 cards into the two hands: the deck is empty from the start and a game is two moves (sim.cpp:598-600,
-# 842), the first with the information pool full (no discard, :400).  These paths cannot occur there.
-UNREACHABLE_VERY_SMALL = ("hint after a discard", "firework completed at full tokens", "moves seen with tokens above the maximum")
-POLICIES = 5  # world w follows policy w % 5: random, hints first, burn, run out the deck, complete at full tokens
+# 842), the first with the information pool full (no discard, :400).  Three paths cannot occur there, nor in any other game
+# without a deck: hanabi_configs.UNREACHABLE_WITHOUT_A_DECK.
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _ref_built():
     ref.require()
-
-
-def _pick(rng, allowed):
-    """One uniformly drawn True column per row of `allowed` (N, 20); -1 where a row has none."""
-    score = rng.random(allowed.shape) * allowed
-    return np.where(allowed.any(-1), score.argmax(-1), -1)
-
-
-def choose(rng, cfg, mask, rec):
-    """The movers' actions (2, N) for the five policies, from the reference's mask and the game records."""
-    K, R, max_info = cfg["colors"], cfg["ranks"], cfg["max_information_tokens"]
-    n = rec.shape[0]
-    w = np.arange(n)
-    mover = rec[:, 83].astype(np.int64)
-    legal = mask[mover, w] != 0                                         # (N, 20)
-    uid = np.arange(20)
-    is_discard, is_play, is_hint = uid < HAND, (uid >= HAND) & (uid < 2 * HAND), (uid >= 2 * HAND) & (uid < 2 * HAND + K + R)
-    hand = rec[w[:, None], 100 + 36 * mover[:, None] + np.arange(HAND)].astype(np.int64)
-    size = rec[w, 105 + 36 * mover].astype(np.int64)
-    fw = rec[:, 76:81].astype(np.int64)
-    playable = (np.arange(HAND) < size[:, None]) & (fw[w[:, None], np.minimum(hand // R, 4)] == hand % R)
-    info = rec[:, 81].astype(np.int64)
-
-    a_random = _pick(rng, legal)
-    a_hint = _pick(rng, legal & is_hint)
-    a_discard = _pick(rng, legal & is_discard)
-    a_play_ok = _pick(rng, np.pad(playable, ((0, 0), (HAND, 20 - 2 * HAND))))
-    a_useless_discard = _pick(rng, legal & np.pad(~playable, ((0, 0), (0, 20 - HAND))))
-
-    pol = w % POLICIES
-    act = a_random.copy()
-    act = np.where((pol == 1) & (a_hint >= 0), a_hint, act)                        # hints whenever legal
-    act = np.where(pol == 2, HAND, act)                                            # play card 0: burns the life tokens
-    run = np.where(a_discard >= 0, a_discard, np.where(a_hint >= 0, a_hint, HAND))  # discard / hint: runs the deck out
-    act = np.where(pol == 3, run, act)
-    # play a playable card only with the information pool full, so that a completed firework brings the ninth token
-    full = info >= max_info
-    complete = np.where(full & (a_play_ok >= 0), a_play_ok,
-                        np.where(~full & (a_useless_discard >= 0), a_useless_discard,
-                                 np.where(~full & (a_discard >= 0), a_discard,
-                                          np.where(a_hint >= 0, a_hint, a_random))))
-    act = np.where(pol == 4, complete, act)
-    acts = np.zeros((2, n), np.int32)
-    acts[mover, w] = act
-    return acts
-
-
-def tokens_after_move(cfg, rec, acts):
-    """Information tokens once the move of `acts` is made, before checkDone may reset the world (sim.cpp:646, 676-678,
-    700, 749): a discard and a completed firework add one, a hint spends one."""
-    R = cfg["ranks"]
-    n = rec.shape[0]
-    w = np.arange(n)
-    mover = rec[:, 83].astype(np.int64)
-    uid = acts[mover, w].astype(np.int64)
-    card = rec[w, 100 + 36 * mover + np.clip(uid - HAND, 0, HAND - 1)].astype(np.int64)
-    play = (uid >= HAND) & (uid < 2 * HAND)
-    completes = play & (rec[w, 76 + np.minimum(card // R, 4)] == card % R) & (card % R == R - 1)
-    return rec[:, 81].astype(np.int64) + (uid < HAND) + completes - (uid >= 2 * HAND)
-
-
-def count_paths(cfg, rec, acts, done):
-    """Which rare paths the step from records `rec` with actions `acts` took, as counts."""
-    K, R, max_info = cfg["colors"], cfg["ranks"], cfg["max_information_tokens"]
-    n = rec.shape[0]
-    w = np.arange(n)
-    mover = rec[:, 83].astype(np.int64)
-    uid = acts[mover, w].astype(np.int64)
-    hint = uid >= 2 * HAND
-    play = (uid >= HAND) & (uid < 2 * HAND)
-    card = rec[w, 100 + 36 * mover + np.clip(uid - HAND, 0, HAND - 1)].astype(np.int64)
-    fw = rec[w, 76 + np.minimum(card // R, 4)].astype(np.int64)
-    scores = play & (fw == card % R)
-    last_move, last_player = rec[:, 87], rec[:, 88]
-    return {
-        "hint as an episode's first move": int((hint & (last_player == 0xFF)).sum()),
-        "hint after a play": int((hint & (last_move == MV_PLAY)).sum()),
-        "hint after a discard": int((hint & (last_move == MV_DISCARD)).sum()),
-        "last life token burnt": int((play & ~scores & (rec[:, 82] == 1) & (done != 0)).sum()),
-        "deck out, last round played": int(((rec[:, 50] == 0) & (rec[:, 84] == 1) & (done != 0)).sum()),
-        "firework completed at full tokens": int((scores & (card % R == R - 1) & (rec[:, 81] == max_info)).sum()),
-        "moves seen with tokens above the maximum": int((rec[:, 81] > max_info).sum()),
-    }
 
 
 def _assert_same(name, step, orc, refs, ob_n, st_n):
@@ -143,9 +60,10 @@ def _check_guards(name, cfg, ob_n, st_n, r, info_after):
     return len(g)
 
 
-@pytest.mark.parametrize("name,n,steps", [("full", 2000, 300), ("small", 1500, 250), ("very_small", 1000, 200)])
+@pytest.mark.parametrize("name,n,steps", [("full", 2000, 300), ("small", 1500, 250), ("very_small", 1000, 200)] +
+                         [(cid, 600, 200) for cid in hanabi_configs.IDS])
 def test_oracle_matches_compiled_reference(name, n, steps):
-    cfg = CONFIGS[name]
+    cfg = CONFIGS.get(name) or hanabi_configs.BY_ID[name]
     ob_n, st_n = hanabi_spec.observation_size(cfg), hanabi_spec.state_size(cfg)
     orc = HanabiOracle(cfg, n)
     refs = [ref.RefHanabi(cfg, n, fill=0x00, construct=False), ref.RefHanabi(cfg, n, fill=0xA5, construct=True)]
@@ -170,11 +88,13 @@ def test_oracle_matches_compiled_reference(name, n, steps):
     print(f"hanabi {name}: {compared} world-steps compared bit-exact, {orc.episodes} episodes, "
           f"{guard_bytes} overflow guard bytes; forced paths: {counts}")
     for k, v in counts.items():
-        if name == "very_small" and k in UNREACHABLE_VERY_SMALL:
+        if not reachable(cfg, k):
             continue
         assert v >= 1, f"{name}: the policies never took the path '{k}' ({counts})"
     if name == "full":
         assert guard_bytes >= 1, "the full configuration's documented one-byte overflow never happened"
+    else:
+        assert name in CONFIGS or guard_bytes == 0, f"{name}: {guard_bytes} guard bytes written"
 
 
 def test_episode_index_wraps():
