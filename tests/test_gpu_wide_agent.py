@@ -21,7 +21,6 @@ pytestmark = pytest.mark.gpu
 import wide_twin as twin  # noqa: E402
 from conftest import load_golden  # noqa: E402
 from madrona_rl_envs_playground_amd import _lib  # noqa: E402
-from madrona_rl_envs_playground_amd.envs.hanabi_env import config_choice  # noqa: E402
 from madrona_rl_envs_playground_amd.simulators import (AgentRecord, BalanceBeamSimulator, CartpoleSimulator, ExecMode,  # noqa: E402
                                                          HanabiSimulator, WidePolicy, agent_act, agent_credit, gae_active)
 
@@ -31,9 +30,10 @@ TENSORS = ("done_tensor", "active_agent_tensor", "observation_tensor", "agent_st
 
 
 def make_sim(game, n):
+    """"balance", a named Hanabi game, or "hanabi_<id>" of tests/hanabi_configs.py"""
     if game == "balance":
         return BalanceBeamSimulator(exec_mode=ExecMode.CUDA, gpu_id=0, num_worlds=n)
-    c = config_choice[game[len("hanabi_"):]]
+    c = twin.config_of(game)
     return HanabiSimulator(exec_mode=ExecMode.CUDA, gpu_id=0, num_worlds=n, colors=c["colors"], ranks=c["ranks"], players=c["players"],
                            max_information_tokens=c["max_information_tokens"], max_life_tokens=c["max_life_tokens"])
 
@@ -109,13 +109,11 @@ def margins(game, weights):
     return max(m[0] for m in per_size), max(m[1] for m in per_size)
 
 
-@pytest.mark.parametrize("weights", WEIGHTS)
-@pytest.mark.parametrize("game,n", twin.CASES)
-def test_forward_pass_and_head(game, n, weights, hip_lib):
+def check_forward_pass_and_head(game, n, weights, d_logp):
+    """The default act of one forward case against the twin and the inputs; ``d_logp``: the case's margin.  Returns the ratio."""
     c = forward_case(game, n, weights)
     got, want, inputs = c["runs"]["default"], c["twin"], c["inputs"]
     active, legal, rows = inputs["active"] != 0, inputs["mask"] != 0, np.arange(n)
-    d_logp = margins(game, weights)[1]
     actions = got["actions"][1]
     err_logp = np.abs(got["logprobs"][1].astype(np.float64) - want["logp"][rows, actions])[active].max()  # teacher-forced
     print(f"{game} n={n} {weights}: log-probs {err_logp / d_logp:.2f} d (d = {d_logp:.3e})")
@@ -143,6 +141,24 @@ def test_forward_pass_and_head(game, n, weights, hip_lib):
     # the same seed gives the same bits
     for name in RECORDED:
         same_bits(c["runs"]["again"][name], got[name], f"{name} of a second run")
+    return err_logp / d_logp
+
+
+@pytest.mark.parametrize("weights", WEIGHTS)
+@pytest.mark.parametrize("game,n", twin.CASES)
+def test_forward_pass_and_head(game, n, weights, hip_lib):
+    check_forward_pass_and_head(game, n, weights, margins(game, weights)[1])
+
+
+def check_values(game, n, weights, d_value):
+    """The critic's values of the active rows, and of every row under ALL_ROWS, within 8 ``d_value`` of the twin.  Returns the ratio."""
+    c = forward_case(game, n, weights)
+    active = c["inputs"]["active"] != 0
+    err = max(np.abs(c["runs"]["default"]["values"][1] - c["twin"]["values"])[active].max(),
+              np.abs(c["runs"]["all_rows"]["values"][1] - c["twin"]["values"]).max())
+    print(f"{game} n={n} {weights}: values {err / d_value:.2f} d (d = {d_value:.3e}, err = {err:.3e})")
+    assert err <= 8 * d_value
+    return err / d_value
 
 
 @pytest.mark.parametrize("weights", WEIGHTS)
@@ -153,26 +169,20 @@ def test_values_within_8_d_of_the_twin(game, n, weights, hip_lib):
     d is 4.5 - 9.3e-9, about one ulp of a value of 0.07: this is the test that tells where the bias is added.  A chain begun
     at the bias measured 6.2 - 16.8 d here (512 products of 2e-4 each rounded at the ulp of a bias of 0.07); with the bias
     added to the finished sum an MI355X measures 0.15 - 2.81 d."""
-    c = forward_case(game, n, weights)
-    active = c["inputs"]["active"] != 0
-    d_value = margins(game, weights)[0]
-    err = max(np.abs(c["runs"]["default"]["values"][1] - c["twin"]["values"])[active].max(),
-              np.abs(c["runs"]["all_rows"]["values"][1] - c["twin"]["values"]).max())
-    print(f"{game} n={n} {weights}: values {err / d_value:.2f} d (d = {d_value:.3e}, err = {err:.3e})")
-    assert err <= 8 * d_value
+    check_values(game, n, weights, margins(game, weights)[0])
 
 
-@pytest.mark.parametrize("weights", WEIGHTS)
-@pytest.mark.parametrize("game,n", twin.CASES)
-def test_all_rows_and_greedy(game, n, weights, hip_lib):
+def check_all_rows_and_greedy(game, n, weights, d_logp):
+    """ALL_ROWS and GREEDY of one forward case against its default act.  Returns the ratio of the log-probs under ALL_ROWS."""
     c = forward_case(game, n, weights)
     default, every, greedy, inputs = c["runs"]["default"], c["runs"]["all_rows"], c["runs"]["greedy"], c["inputs"]
     active, legal, rows = inputs["active"] != 0, inputs["mask"] != 0, np.arange(n)
     for name in ("actions", "logprobs", "values"):
         same_bits(every[name][1][active], default[name][1][active], f"{name} of the active rows under ALL_ROWS")
     same_bits(every["logits"][active], default["logits"][active], "logits")
-    d_logp = margins(game, weights)[1]
-    assert np.abs(every["logprobs"][1].astype(np.float64) - c["twin"]["logp"][rows, every["actions"][1]]).max() <= 8 * d_logp
+    err_logp = np.abs(every["logprobs"][1].astype(np.float64) - c["twin"]["logp"][rows, every["actions"][1]]).max()
+    print(f"{game} n={n} {weights}: log-probs under ALL_ROWS {err_logp / d_logp:.2f} d (d = {d_logp:.3e})")
+    assert err_logp <= 8 * d_logp
     assert legal[rows, every["actions"][1]].all()
     same_bits(every["active"][1], active.astype(np.uint8), "ALL_ROWS records the real flags")
     # GREEDY: the first legal arg-max of the device's own logits
@@ -180,44 +190,42 @@ def test_all_rows_and_greedy(game, n, weights, hip_lib):
     first = np.where(legal, greedy["logits"][:, :a], -np.inf).argmax(axis=1)
     assert np.array_equal(greedy["actions"][1][active], first[active])
     same_bits(greedy["values"][1], default["values"][1], "values under GREEDY")
+    return err_logp / d_logp
 
 
-def test_operand_maps_with_exact_integers(hip_lib):
-    """Integer weights and 0 / 1 inputs whose every partial sum is an integer below 2^24: float32 is exact whatever the order,
-    so a wrong lane map, a transposed tile or a dropped k shows as a wrong integer.  Logits and values are compared bit for bit."""
-    game, n, player = "hanabi_very_small", 65, 1
+@pytest.mark.parametrize("weights", WEIGHTS)
+@pytest.mark.parametrize("game,n", twin.CASES)
+def test_all_rows_and_greedy(game, n, weights, hip_lib):
+    check_all_rows_and_greedy(game, n, weights, margins(game, weights)[1])
+
+
+def check_operand_maps(game, n, player):
+    """Integer weights (``twin.integer_layers``) and 0 / 1 inputs whose every partial sum is an integer below 2^24: float32 is exact
+    whatever the order, so a wrong lane map, a transposed tile or a dropped k shows as a wrong integer.  Logits and values of
+    every row (ALL_ROWS) are compared bit for bit."""
     d, s, a = twin.dims(game)
-    rng = np.random.default_rng(99)
+    layers = twin.integer_layers(d, s, a)
     policy = WidePolicy(d, s, a, device=DEV)
-    layers, flat = {}, []
-    for name, first, out in (("critic", s, 1), ("actor", d, a)):
-        layers[name] = []
-        for k, (rows, cols) in enumerate(((512, first), (512, 512), (512, 512), (out, 512))):
-            density = 1.0 if k == 0 else 1.0 / 32
-            w = (rng.integers(-2, 3, size=(rows, cols)) * (rng.uniform(size=(rows, cols)) < density)).astype(np.int64)
-            w += (np.arange(rows)[:, None] % 3 == 0) & (np.arange(cols)[None, :] % 7 == 0)  # (asymmetric in row and column)
-            b = rng.integers(-3, 4, size=rows).astype(np.int64)
-            layers[name].append((w, b))
-            flat += [w.reshape(-1), b]
-    policy.params.copy_(torch.from_numpy(np.concatenate(flat).astype(np.float32)))
-    inputs = twin.case_inputs(game, n, 4242)
-    exact = {}
-    for name, x in (("critic", inputs["state"].astype(np.int64)), ("actor", inputs["obs"].astype(np.int64))):
-        for k, (w, b) in enumerate(layers[name]):
-            assert (np.abs(x) @ np.abs(w).T + np.abs(b)).max() < 2 ** 24
-            x = x @ w.T + b
-            if k < 3:
-                x = np.maximum(x, 0)
-        exact[name] = x
-    assert len(np.unique(exact["actor"])) > n and exact["actor"].std(axis=0).min() > 0 and exact["actor"].std(axis=1).min() > 0
+    policy.params.copy_(torch.from_numpy(twin.integer_params(layers)))
+    inputs = twin.case_inputs(game, n, twin.INTEGER_SEED)
+    values, logits, bound = twin.integer_forward(layers, inputs["obs"], inputs["state"])
+    assert bound < 2 ** 24
+    assert len(np.unique(logits)) > n and logits.std(axis=0).min() > 0 and logits.std(axis=1).min() > 0
     sim = make_sim(game, n)
     write_inputs(sim, game, inputs, player)
     record = new_record(sim, game, 1, logits=True)
     agent_act(sim, player, policy, record, row=0, seed=1, step=0, all_rows=True)
     torch.cuda.synchronize()
-    same_bits(cpu(record.logits)[:, :a], exact["actor"].astype(np.float32), "logits")
-    same_bits(cpu(record.values)[0], exact["critic"][:, 0].astype(np.float32), "values")
+    same_bits(cpu(record.logits)[:, :a], logits.astype(np.float32), "logits")
+    assert not cpu(record.logits)[:, a:].any()
+    same_bits(cpu(record.values)[0], values.astype(np.float32), "values")
     sim.close()
+
+
+def test_operand_maps_with_exact_integers(hip_lib):
+    """Integer weights and 0 / 1 inputs whose every partial sum is an integer below 2^24: float32 is exact whatever the order,
+    so a wrong lane map, a transposed tile or a dropped k shows as a wrong integer.  Logits and values are compared bit for bit."""
+    check_operand_maps("hanabi_very_small", 65, 1)
 
 
 def collect(game, n, num_steps, prepare=None, seed=77):
@@ -364,16 +372,21 @@ def test_gae_active_over_several_workgroups(coupled, hip_lib):
     same_bits(got[2] != 0, want[2], "active afterwards")
 
 
-def test_one_full_update(hip_lib):
+@pytest.mark.parametrize("game", ["hanabi_very_small", "hanabi_k5r4i8l3", "hanabi_k1r5i1l1"])
+def test_one_full_update(game, hip_lib):
+    """A rollout of ``CleanPPOAgent``, its update, and the act behind it.  k5r4i8l3: code variant 0, 542 / 642 wide, 19 actions;
+    k1r5i1l1: no deck, episodes of two moves."""
     from madrona_rl_envs_playground_amd.envs.hanabi_env import HanabiMadrona
     from madrona_rl_envs_playground_amd.pantheonrl_extension import CleanPPOAgent
-    n, num_steps, game = 33, 8, "hanabi_very_small"
+    n, num_steps = 33, 8
+    d, s, a = twin.dims(game)
     torch.manual_seed(0)
-    env = HanabiMadrona(n, 0, config=config_choice["very_small"])
+    env = HanabiMadrona(n, 0, config=twin.config_of(game))
     ego = CleanPPOAgent(env, "ego", DEV, num_updates=2, verbose=False, num_steps=num_steps, seed=5)
     partner = CleanPPOAgent(env.getDummyEnv(1), "partner", DEV, num_updates=2, verbose=False, num_steps=num_steps)
     env.add_partner_agent(partner, player_num=1)
     assert (ego.seat, partner.seat) == (0, 1) and ego.seed == 5 and partner.seed != 5
+    assert (ego.policy.obs_dim, ego.policy.state_dim, ego.policy.num_actions) == (d, s, a)
     obs = env.reset()
     for _ in range(num_steps):
         action = ego.get_action(obs)
@@ -382,6 +395,8 @@ def test_one_full_update(hip_lib):
         ego.update(reward, done)
     torch.cuda.synchronize()
     assert ego.global_step == num_steps and partner.global_step == num_steps and ego.updates == 1
+    assert ego.record.obs.shape == (num_steps, n, d) and ego.record.states.shape == (num_steps, n, s)
+    assert ego.record.action_masks.shape == (num_steps, n, a)
     before = ego.policy.params.clone()
     old_agent = twin.make_agent(game, "orthogonal")
     torch.nn.utils.vector_to_parameters(before.cpu(), old_agent.parameters())
@@ -391,6 +406,11 @@ def test_one_full_update(hip_lib):
     after = ego.policy.params
     assert not torch.equal(after, before) and torch.isfinite(after).all()
     assert torch.equal(after, torch.nn.utils.parameters_to_vector(ego.agent.parameters()))
+    at = after.data_ptr()
+    for p in ego.agent.parameters():  # views of policy.params: the optimizer's step is what the kernels read
+        assert p.untyped_storage().data_ptr() == after.untyped_storage().data_ptr() and p.data_ptr() == at
+        at += 4 * p.numel()
+    assert at == after.data_ptr() + 4 * after.numel()
     for key, value in ego.last_losses.items():
         assert np.isfinite(value) or key == "explained_variance", key
     assert ego.last_losses["samples"] > 1 and ego.last_losses["learning_rate"] == 2.5e-4
@@ -401,11 +421,20 @@ def test_one_full_update(hip_lib):
     new_agent = twin.make_agent(game, "orthogonal")
     torch.nn.utils.vector_to_parameters(after.cpu(), new_agent.parameters())
     values = cpu(r.values)[0]
-    new_twin = twin.forward(twin.flat(new_agent), inputs["obs"], inputs["state"], twin.dims(game)[2])[0]
-    old_twin = twin.forward(twin.flat(old_agent), inputs["obs"], inputs["state"], twin.dims(game)[2])[0]
-    # float32 rounding keeps the forward pass within K eps sum |x w| ~ 512 x 6e-8 x 0.1 = 3e-6 of the twin; four Adam steps of
-    # 2.5e-4 on every weight move a value by far more
-    assert np.abs(values - new_twin)[active].max() <= 1e-5 < 1e-4 <= np.abs(values - old_twin)[active].max()
+    new_twin = twin.forward(twin.flat(new_agent), inputs["obs"], inputs["state"], a)[0]
+    old_twin = twin.forward(twin.flat(old_agent), inputs["obs"], inputs["state"], a)[0]
+    err_new, err_old = np.abs(values - new_twin)[active].max(), np.abs(values - old_twin)[active].max()
+    if game == "hanabi_very_small":
+        # float32 rounding keeps the forward pass within K eps sum |x w| ~ 512 x 6e-8 x 0.1 = 3e-6 of the twin; four Adam steps of
+        # 2.5e-4 on every weight move a value by far more
+        assert err_new <= 1e-5 < 1e-4 <= err_old
+    else:
+        # d: torch float32 against the twin on the recorded rows, at the new parameters; 100 x 8 d is the margin of
+        # test_rollout_reads_the_updated_parameters
+        d_value = twin.margins(new_agent, {name: x[active] for name, x in inputs.items()})[0]
+        print(f"{game}: values of row 0 {err_new / d_value:.2f} d from the twin at the new parameters, {err_old / d_value:.0f} d from "
+              f"the twin at the old ones (d = {d_value:.3e})")
+        assert d_value > 0 and err_new <= 8 * d_value and err_old > 100 * 8 * d_value
     env.close()
 
 

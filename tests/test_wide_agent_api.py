@@ -10,6 +10,7 @@ import pytest
 import torch
 from conftest import load_golden
 
+import hanabi_configs
 import wide_twin as twin
 
 NEW_SYMBOLS = ["mrl_wide_policy_num_params", "mrl_agent_workspace_bytes", "mrl_agent_act", "mrl_agent_credit", "mrl_gae_active"]
@@ -97,7 +98,7 @@ def test_draws_lie_on_the_24_bit_grid():
 
 
 @pytest.mark.parametrize("weights", sorted(twin.WEIGHTS))
-@pytest.mark.parametrize("game", ["balance", "hanabi_very_small", "hanabi_full"])
+@pytest.mark.parametrize("game", ["balance", "hanabi_very_small", "hanabi_full"] + [game for game, _ in twin.CONFIG_CASES])
 def test_twin_against_torch_float32(game, weights):
     """The twin and torch's float32 evaluation are the same function: their distance d is a float32 rounding distance (the
     bound: K <= 783 terms of size <= |x w| each rounded to 2^-24 relative, four layers), and away from the boundaries they
@@ -120,15 +121,17 @@ def test_twin_against_torch_float32(game, weights):
 
 
 @pytest.mark.parametrize("weights", sorted(twin.WEIGHTS))
-@pytest.mark.parametrize("game,n", twin.CASES)
+@pytest.mark.parametrize("game,n", twin.CASES + twin.CONFIG_CASES)
 def test_gpu_cases_draw_away_from_boundaries(game, n, weights):
-    """The rows a GPU action comparison may skip: at most 1 % of a case's rows lie within 1e-5 of a boundary."""
+    """The rows a GPU action comparison may skip: at most 1 % of a case's rows lie within 1e-5 of a boundary -- with the draws of
+    the seat the GPU case acts as, n % 2, and for the named games with those of seat 0 as well."""
     seed = twin.case_seed(game, n, weights)
     agent = twin.make_agent(game, weights)
     inputs = twin.case_inputs(game, n, seed)
-    u = twin.draws(seed, 0, n, 0)
-    near = twin.near_boundary(twin.act(twin.flat(agent), inputs["obs"], inputs["state"], inputs["mask"], u)["cdf"], u)
-    assert near.sum() <= 0.01 * n, f"{near.sum()} of {n} rows are near a boundary"
+    for player in sorted({0, n % 2} if (game, n) in twin.CASES else {n % 2}):
+        u = twin.draws(seed, 0, n, player)
+        near = twin.near_boundary(twin.act(twin.flat(agent), inputs["obs"], inputs["state"], inputs["mask"], u)["cdf"], u)
+        assert near.sum() <= 0.01 * n, f"seat {player}: {near.sum()} of {n} rows are near a boundary"
 
 
 @pytest.mark.parametrize("weights", sorted(twin.WEIGHTS))
@@ -202,6 +205,113 @@ def test_narrow_integer_policies_are_exact_in_float32(game, d, s, a):
         lo, hi = tie
         assert np.array_equal(logits[:, lo], logits[:, hi])
         assert ((logits <= logits[:, [lo]]).sum(axis=1) > 2).any()
+
+
+# ---------------------------------------------------------------- every Hanabi configuration of tests/hanabi_configs.py
+
+# id: (D, S, A, code variant, deck); D = 21 K R + 11 K + 11 R + 12 + information + life, S = D + 5 K R, A = 10 + K + R
+CONFIG_TABLE = {
+    "k3r5i8l3": (426, 501, 18, 1, 20), "k4r5i5l2": (538, 638, 19, 1, 30), "k5r4i8l3": (542, 642, 19, 0, 30), "k5r3i8l3": (426, 501, 18, 0, 20),
+    "k5r2i8l3": (310, 360, 17, 0, 10), "k3r3i4l2": (273, 318, 16, 0, 8), "k2r4i1l1": (248, 288, 16, 0, 6), "k4r2i2l3": (251, 291, 16, 0, 6),
+    "k3r2i1l1": (195, 225, 15, 0, 2), "k2r3i8l3": (204, 234, 15, 0, 2), "k1r5i1l1": (185, 210, 16, 1, 0), "k4r4i7l2": (445, 525, 18, 0, 22),
+    "k5r5i1l3": (651, 776, 20, 1, 40), "k2r3i3l1": (197, 227, 15, 0, 2),
+}
+
+
+def test_config_table_and_its_spread():
+    """(D, S, A), variant and deck of every configuration as literals, and what the list brings to the act kernels -- asserted so
+    that an edit of ``hanabi_configs.CONFIGS`` cannot lose it."""
+    from madrona_rl_envs_playground_amd import hanabi_spec
+    assert list(CONFIG_TABLE) == hanabi_configs.IDS == [game[len("hanabi_"):] for game, _ in twin.CONFIG_CASES]
+    assert all(n == 65 for _, n in twin.CONFIG_CASES)
+    for cid, (d, s, a, variant, deck) in CONFIG_TABLE.items():
+        cfg = hanabi_configs.BY_ID[cid]
+        k, r = cfg["colors"], cfg["ranks"]
+        assert (hanabi_spec.observation_size(cfg), hanabi_spec.state_size(cfg), hanabi_spec.num_moves(cfg)) == (d, s, a) == twin.dims("hanabi_" + cid)
+        assert d == 21 * k * r + 11 * k + 11 * r + 12 + cfg["max_information_tokens"] + cfg["max_life_tokens"]
+        assert s == d + 5 * k * r and a == 10 + k + r
+        assert hanabi_configs.variant(cfg) == variant and hanabi_configs.deck_size(cfg) == deck
+    rows = list(CONFIG_TABLE.values())
+    assert {a for _, _, a, _, _ in rows} == set(range(15, 21))
+    assert [cid for cid, row in CONFIG_TABLE.items() if row[2] == 20] == ["k5r5i1l3"]  # A = 20 on a game that is not the full one
+    assert {variant for _, _, _, variant, _ in rows} == {0, 1}
+    tails = {w % 64 for d, s, _, _, _ in rows for w in (d, s)}  # the last k-chunk of a first layer
+    assert {2, 3, 5, 32, 62} <= tails
+    assert any(w % 2 for d, s, _, _, _ in rows for w in (d, s)) and any(d % 4 for d, _, _, _, _ in rows) and any(s % 4 for _, s, _, _, _ in rows)
+    assert {0, 2} <= {deck for _, _, _, _, deck in rows}
+    # the named games keep their seeds, the configurations get their own
+    assert [twin.case_seed(g, 65, "orthogonal") for g in ("balance", "hanabi_very_small", "hanabi_full")] == [514736, 514737, 514738]
+    assert twin.case_seed("hanabi_k3r5i8l3", 65, "orthogonal") == 7919 * 65 + 10
+    assert twin.case_seed("hanabi_k2r3i3l1", 65, "peaked") == 7919 * 65 + 104729 + 10 + 13
+
+
+@pytest.mark.parametrize("game,n", twin.CONFIG_CASES)
+def test_config_margins_pool_three_input_sets(game, n):
+    """d of a configuration is the largest of three sets' distances, each a float32 rounding distance of the size the named
+    games have."""
+    for weights in sorted(twin.WEIGHTS):
+        agent, seed = twin.make_agent(game, weights), twin.case_seed(game, n, weights)
+        per_set = [twin.margins(agent, twin.case_inputs(game, n, seed + 1000003 * k)) for k in range(3)]
+        d_value, d_logp = twin.config_margins(game, weights)
+        print(f"{game} {weights}: d_value {d_value:.3e} d_logp {d_logp:.3e}; per set {per_set}")
+        assert d_value == max(m[0] for m in per_set) and d_logp == max(m[1] for m in per_set)
+        assert 1e-9 < d_value < 5e-8 and 1e-7 < d_logp < 1e-5
+
+
+@pytest.mark.parametrize("game,n", twin.CONFIG_CASES)
+def test_integer_policies_of_every_configuration_are_exact_in_float32(game, n):
+    """The operand-map GPU cases compare bit for bit: every sum of absolute terms stays below 2^24 and the logits are not all alike."""
+    d, s, a = twin.dims(game)
+    layers = twin.integer_layers(d, s, a)
+    inputs = twin.case_inputs(game, n, twin.INTEGER_SEED)
+    values, logits, bound = twin.integer_forward(layers, inputs["obs"], inputs["state"])
+    print(f"{game}: the largest sum of absolute terms is {bound:.3e}")
+    assert bound < 2 ** 24
+    assert len(np.unique(logits)) > n and logits.std(axis=0).min() > 0 and logits.std(axis=1).min() > 0 and len(np.unique(values)) > 1
+    reference = twin.forward(twin.integer_params(layers), inputs["obs"], inputs["state"], a)
+    assert np.array_equal(reference[0], values) and np.array_equal(reference[1], logits)  # the flat order is the twin's
+
+
+# episodes ended in the committed walk of each configuration (65 worlds, 24 steps, twin.WALK_SEEDS)
+WALK_EPISODES = {"k1r5i1l1": 952, "k3r2i1l1": 407, "k2r4i1l1": 521, "k5r4i8l3": 93, "k4r5i5l2": 118, "k5r5i1l3": 177}
+
+
+@pytest.mark.parametrize("cid", sorted(twin.WALK_SEEDS))
+def test_config_walk_reaches_what_the_gpu_test_relies_on(cid, oracle_lib):
+    """Conditions on the closed loop of tests/test_gpu_wide_agent_configs.py, walked here by the oracle and the twin alone."""
+    assert sorted(twin.WALK_SEEDS) == sorted(WALK_EPISODES) and (twin.WALK_N, twin.WALK_STEPS) == (65, 24)
+    game = "hanabi_" + cid
+    d, s, a = twin.dims(game)
+    steps = twin.walked(cid)
+    assert len(steps) == twin.WALK_STEPS
+    near = rows = empty = ended = 0
+    chosen = np.zeros(a, np.int64)
+    d_value = d_logp = 0.0
+    for t, step in enumerate(steps):
+        assert not step["before"]["mask"][..., a:].any() and not step["after"]["mask"][..., a:].any(), f"step {t}: a legal move beyond {a}"
+        assert ((step["before"]["active"] != 0).sum(axis=0) == 1).all()  # one seat is the one to act
+        ended += int(step["after"]["done"].sum())
+        for p, seat in enumerate(step["seats"]):
+            active = seat["active"]
+            assert (step["actions"][p][~active] == 0).all()
+            if not active.any():
+                empty += 1
+                continue
+            legal = step["before"]["mask"][p][active, :a] != 0
+            assert legal[np.arange(active.sum()), seat["twin"]["actions"]].all()
+            assert np.array_equal(step["actions"][p][active], seat["twin"]["actions"])
+            rows += int(active.sum())
+            near += int(twin.near_boundary(seat["twin"]["cdf"], seat["u"]).sum())
+            chosen += np.bincount(seat["twin"]["actions"], minlength=a)
+            d_value, d_logp = max(d_value, seat["d"][0]), max(d_logp, seat["d"][1])
+    print(f"{cid}: {rows} active rows, {near} near a boundary, {ended} episodes ended, {empty} seat-steps without an active world, "
+          f"d_value {d_value:.3e} d_logp {d_logp:.3e}, actions chosen {chosen.tolist()}")
+    assert rows == twin.WALK_N * twin.WALK_STEPS
+    assert near == 0, f"{near} active rows lie within 1e-5 of a boundary: choose another seed"
+    assert (chosen > 0).all(), f"actions never chosen: {np.flatnonzero(chosen == 0).tolist()}"
+    assert empty >= 1 and not steps[0]["seats"][1]["active"].any()  # seat 1 at step 0: an act over an empty world list
+    assert ended >= max(50, WALK_EPISODES[cid] / 2)
+    assert 0 < d_value < 1e-4 and 0 < d_logp < 1e-3
 
 
 FIXTURE_CASES = [(regime, n) for n in (5, 70) for regime in ("coupled", "together")]

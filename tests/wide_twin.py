@@ -2,9 +2,12 @@
 torch float32 -- whose distance from the twin sets the tests' margins --, the synthetic inputs the GPU tests write into a
 simulator's tensors, and float32 numpy restatements of ``mrl_agent_credit`` and ``mrl_gae_active`` that follow
 include/mrl_envs.h operation for operation.  Nothing here touches a GPU."""
+import functools
+
 import numpy as np
 import torch
 
+import hanabi_configs
 from madrona_rl_envs_playground_amd import hanabi_spec
 from madrona_rl_envs_playground_amd.envs.hanabi_env import config_choice
 from madrona_rl_envs_playground_amd.simulators import WideAgent, random_hash
@@ -15,11 +18,17 @@ AGENT_SEED = 11
 WEIGHTS = {"orthogonal": 1.0, "peaked": 300.0}  # the factor on the actor's output layer: 300 moves the probabilities far from uniform
 
 
+def config_of(game):
+    """the configuration of "hanabi_<name>": one of the three named games, or an id of ``hanabi_configs.BY_ID``"""
+    name = game[len("hanabi_"):]
+    return config_choice[name] if name in config_choice else hanabi_configs.BY_ID[name]
+
+
 def dims(game):
     """(D, S, A) of ``game``: "balance" or "hanabi_<config>" """
     if game == "balance":
         return 7, 7, 4
-    config = config_choice[game[len("hanabi_"):]]
+    config = config_of(game)
     return hanabi_spec.observation_size(config), hanabi_spec.state_size(config), hanabi_spec.num_moves(config)
 
 
@@ -34,6 +43,11 @@ CASES = [(game, n) for game in ("balance", "hanabi_very_small") for n in SIZES] 
 #   balance 2081: the int32 inputs
 LARGE_CASES = [("hanabi_very_small", 2081, 1, 3), ("hanabi_full", 1025, 0, 3), ("balance", 2081, 1, 3)]
 
+# the forward cases of tests/test_gpu_wide_agent_configs.py: every configuration of tests/hanabi_configs.py at 65 worlds -- three
+# 32-row tiles with a last tile of one row, and a head workgroup of one lane --, each with both weight sets.  Not part of
+# CASES either; their margins are ``config_margins``, one configuration each.
+CONFIG_CASES = [("hanabi_" + cid, 65) for cid in hanabi_configs.IDS]
+
 # (seed, player, world) of hanabi_very_small, 65 worlds, step 0, whose draw sits at an end of the 2^-24 grid (found by search,
 # checked by tests/test_wide_agent_api.py through ``draws``)
 EDGE_GAME, EDGE_N, EDGE_VARIANTS = "hanabi_very_small", 65, 8
@@ -46,7 +60,9 @@ EDGE_U = {"top": 1.0 - 2.0 ** -24, "zero": 0.0}
 
 def case_seed(game, n, weights):
     """seed of the inputs and of the draws of one case"""
-    return 7919 * n + 104729 * sorted(WEIGHTS).index(weights) + {"balance": 1, "hanabi_very_small": 2, "hanabi_full": 3}[game]
+    named = {"balance": 1, "hanabi_very_small": 2, "hanabi_full": 3}
+    last = named[game] if game in named else 10 + hanabi_configs.IDS.index(game[len("hanabi_"):])
+    return 7919 * n + 104729 * sorted(WEIGHTS).index(weights) + last
 
 
 def make_agent(game, weights, seed=AGENT_SEED):
@@ -142,6 +158,9 @@ def head32(logits, mask, u):
 # chunk of 64 and an odd tail of one; A = 1, 15 and 3 read a mask row whose stride is not A.
 NARROW_CASES = [("hanabi_very_small", 1, 65, 1), ("hanabi_very_small", 2, 64, 15), ("hanabi_very_small", 65, 1, 16), ("balance", 5, 5, 3)]
 NARROW_N, TIE = 33, (4, 9)  # the two actor outputs of the A = 15 case that share weights and bias
+
+
+INTEGER_SEED = 4242  # of the ``case_inputs`` the integer-weight GPU cases run on
 
 
 def integer_layers(d, s, a, seed=99, tie=None):
@@ -261,6 +280,67 @@ def margins(agent, inputs, actions=None):
         rows = np.arange(len(v32))
         d_logp = np.abs(lp32[rows, actions] - twin["logp"][rows, actions]).max()
     return float(np.abs(v32 - twin["values"]).max()), float(d_logp)
+
+
+@functools.lru_cache(maxsize=None)
+def config_margins(game, weights):
+    """d of one configuration (a ``CONFIG_CASES`` game) at one weight set: the largest ``margins`` over three input sets of 65 rows,
+    ``case_inputs`` at the case's seed, at seed + 1000003 and at seed + 2000006.  One set's value distance is a single draw of
+    about one ulp of a value, hence the pool; the three agree within about 30 %."""
+    n = dict(CONFIG_CASES)[game]
+    agent, seed = make_agent(game, weights), case_seed(game, n, weights)
+    per_set = [margins(agent, case_inputs(game, n, seed + 1000003 * k)) for k in range(3)]
+    return max(m[0] for m in per_set), max(m[1] for m in per_set)
+
+
+# ---------------------------------------------------------------- a closed loop on the CPU: the oracle under the twin's actions
+#
+# What tests/test_gpu_wide_agent_configs.py collects on the device, walked here by the oracle and the twin alone.  WALK_SEEDS:
+# the walked configurations and the seed of their draws, chosen so that no active row of the walk lies within 1e-5 of a
+# boundary (tests/test_wide_agent_api.py asserts it: a row the device decided otherwise would send the trajectories apart).
+# Without a deck or with a deck of 2 most worlds end an episode every few moves; k5r4i8l3 is code variant 0 with A = 19,
+# k4r5i5l2 variant 1 with A = 19, k5r5i1l3 A = 20 on a game that is not the full one.
+WALK_N, WALK_STEPS = 65, 24
+WALK_SEEDS = {"k1r5i1l1": 79, "k3r2i1l1": 77, "k2r4i1l1": 77, "k5r4i8l3": 77, "k4r5i5l2": 79, "k5r5i1l3": 79}
+
+
+def config_walk(cid, n, steps, seed):
+    """Steps a ``HanabiOracle`` of configuration ``cid`` under the twin: seat p follows ``act`` with the parameters of
+    ``make_agent(game, sorted(WEIGHTS)[p], seed=21 + p)`` -- the policies of the device's collection -- on the oracle's own
+    ``obs[:, :D]``, ``state[:, :S]``, ``mask[:, :A]`` and ``active``, with the draws ``draws(seed, t, n, p)``.  Yields per step
+    {"before" / "after": the oracle's tensors around the step, "actions" (2, n) int32, 0 where a seat is not the one to act,
+    "seats": per seat {"active", "twin": ``act`` over the active rows, "u": their draws, "d": ``margins`` of torch float32 on
+    those rows at the actions chosen, None where no row is active}}."""
+    from oracle import oracle
+    oracle.build()
+    game = "hanabi_" + cid
+    d, s, a = dims(game)
+    agents = [make_agent(game, w, seed=21 + p) for p, w in enumerate(sorted(WEIGHTS))]
+    params = [flat(agent) for agent in agents]
+    orc = oracle.HanabiOracle(hanabi_configs.BY_ID[cid], n)
+
+    def tensors():
+        return {name: getattr(orc, name).copy() for name in ("obs", "state", "mask", "active", "reward", "done")}
+
+    for t in range(steps):
+        before = tensors()
+        actions, seats = np.zeros((2, n), np.int32), []
+        for p in range(2):
+            active = before["active"][p] != 0
+            inputs = {"obs": before["obs"][p][active, :d], "state": before["state"][p][active, :s], "mask": before["mask"][p][active, :a]}
+            u = draws(seed, t, n, p)[active]
+            out = act(params[p], inputs["obs"], inputs["state"], inputs["mask"], u)
+            actions[p, active] = out["actions"]
+            seats.append({"active": active, "twin": out, "u": u, "d": margins(agents[p], inputs, out["actions"]) if active.any() else None})
+        orc.step(actions)
+        yield {"before": before, "after": tensors(), "actions": actions, "seats": seats}
+    orc.close()
+
+
+@functools.lru_cache(maxsize=None)
+def walked(cid):
+    """the committed walk of ``cid``, walked once and shared: a list, one entry per step"""
+    return list(config_walk(cid, WALK_N, WALK_STEPS, WALK_SEEDS[cid]))
 
 
 # ---------------------------------------------------------------- the record's bookkeeping, float32, operation for operation
