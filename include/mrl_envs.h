@@ -830,6 +830,76 @@ int mrl_cnn_act(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, co
 int mrl_rollout_cnn(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, const mrl_cnn_record *record, void *obs_ring_dev,
                     uint64_t seed, uint32_t first_step, void *hip_stream);
 
+/* MAPPO's update for that actor-critic on the device: R_MAPPO.ppo_update (train/MAPPO/r_mappo.py:91-164, feed-forward networks, all
+ * active masks one) with ValueNorm (utils/valuenorm.py) -- gather, both forward passes, the clipped losses, backward, two
+ * clip_grad_norm_ and two Adam steps -- on the flat parameter array mrl_cnn_act reads, which is updated in place.  No reference
+ * counterpart as a call.  DESIGN.md section 16.
+ *   Samples: s = (t N + n) P + p is row t, world n, seat p of an mrl_cnn_record; its observation is the H W F bytes at s H W F of
+ *     batch->obs (the ring mrl_rollout_cnn filled: slot t is what the act of step t saw), read as int8 and converted on load.
+ *   One call is K = num_minibatches steps in row order; row k takes the B = minibatch_size samples indices[k, :].  An index >= S
+ *     is outside the contract; it is clamped to S - 1, so it stays memory-safe.
+ *   Per sample, float32, c = clip_param: logits -> max m, e_a = exp(l_a - m), p_a = e_a / sum e, logp_a = (l_a - m) - log(sum e)
+ *     (mrl_cnn_act's own expressions: on unchanged parameters logp[action] and v are the record's, bit for bit), H = -sum p logp;
+ *     ratio = exp(logp[action] - old); actor loss = -mean(min(ratio A, clamp(ratio, 1 - c, 1 + c) A)) - entropy_coef mean(H), A =
+ *     advantages[s] as given.  Critic: v_c = v_old + clamp(v - v_old, -c, c); target = (R - mean) / sqrt(var) of the ValueNorm
+ *     state AFTER this row's update (MRL_MAPPO_VALUENORM), else R; e = target - v, e_c = target - v_c; value_loss = mean(max(L(e),
+ *     L(e_c))) (MRL_MAPPO_CLIPPED_VALUE_LOSS) or mean(L(e)); L(e) = e^2 / 2, or with MRL_MAPPO_HUBER_LOSS the reference's
+ *     huber_loss (utils/util.py:46-50) as written: e^2 / 2 for |e| <= delta, delta (|e| - delta / 2) for e > delta and 0 for e <
+ *     -delta.  The critic differentiates value_loss_coef value_loss.  Gradients are autograd's: a tie of min / max halves the
+ *     gradient between the arguments, clamp passes it on the closed interval, ReLU passes none at a pre-activation of 0.
+ *   ValueNorm: value_norm_state = (running_mean, running_mean_sq, debiasing_term), 3 device floats.  Row k: m = mean of the row's
+ *     gathered returns, q = mean of their squares; each of the three becomes x * beta + (m | q | 1) * one_minus_beta; then mean =
+ *     running_mean / max(deb, epsilon), var = max(running_mean_sq / max(deb, epsilon) - mean^2, 0.01).  The K-row recurrence runs up
+ *     front (it depends on no parameter) and leaves the final state in value_norm_state.  Without the flag the state is not
+ *     touched and may be NULL.
+ *   Clip and Adam, per net (actor with lr, critic with critic_lr): total = sqrt(sum g^2) over the net's own tensors; with
+ *     MRL_MAPPO_MAX_GRAD_NORM g *= min(1, max_grad_norm / (total + 1e-6)); then mrl_ppo_update's Adam with t = opt->step + 1 + k.
+ *   stats (K, 8), optional: 0 value_loss, 1 critic_grad_norm, 2 policy_loss, 3 dist_entropy, 4 actor_grad_norm, 5 ratio (the mean
+ *     importance weight), 6 clipfrac (|ratio - 1| > c), 7 reserved (0).  grads (K, P), optional: each row's summed, unclipped
+ *     gradient in parameter order (actor, then critic).
+ *   Launches: two up front with MRL_MAPPO_VALUENORM, then three per row (gradient: a workgroup per (share of the row, net), tiles
+ *     of 32 samples, everything between the int8 rows and the weight gradients in LDS; ordered sum of the workgroups' partial
+ *     vectors; clip, Adam, stats).  At most 256 partial vectors per net, so mrl_mappo_workspace_bytes stops growing with B.  No
+ *     float atomics, no wait between workgroups: the same inputs give the same bits on every run, one call of K rows the bits of
+ *     K calls of one row.  The call only enqueues on hip_stream of device gpu_id.
+ *   MRL_ERR_INVALID, nothing changed: a NULL among policy, opt, batch, indices, cfg, workspace, the arrays of opt and batch, or
+ *     value_norm_state with MRL_MAPPO_VALUENORM; policy->params_dev != opt->params_dev; hidden != 64; a kitchen below 3 x 3 or
+ *     whose LDS image (mrl_cnn_act's with room for three more 32-row arrays in its first region, plus 256 bytes: DESIGN.md
+ *     section 16) does not fit 160 KiB; B == 0 or S == 0; a
+ *     workspace below mrl_mappo_workspace_bytes or off a 16-byte boundary; params, moments, float arrays or indices off a 4-byte
+ *     boundary; unknown flag bits; a capturing stream.  K == 0 enqueues nothing.  mrl_mappo_workspace_bytes refuses the same
+ *     shapes and a NULL out.  Not built: active masks, PopArt, recurrent networks, update_actor = False, weight decay. */
+enum { MRL_MAPPO_VALUENORM = 1, MRL_MAPPO_HUBER_LOSS = 2, MRL_MAPPO_CLIPPED_VALUE_LOSS = 4, MRL_MAPPO_MAX_GRAD_NORM = 8 };
+typedef struct mrl_mappo_policy {
+    const float *params_dev;     /* as mrl_cnn_policy */
+    uint32_t hidden, flags;      /* flags: not read */
+    uint32_t width, height, channels;
+} mrl_mappo_policy;
+typedef struct mrl_mappo_config {
+    float clip_param, entropy_coef, value_loss_coef, max_grad_norm, huber_delta;
+    float lr, critic_lr, beta1, beta2, opti_eps;             /* torch.optim.Adam, no amsgrad, no weight decay */
+    float valuenorm_beta, valuenorm_one_minus_beta, valuenorm_epsilon;
+    uint32_t flags;                                          /* MRL_MAPPO_* */
+} mrl_mappo_config;
+typedef struct mrl_mappo_batch {
+    const int8_t *obs;           /* (S, H, W, F) */
+    const int32_t *actions;      /* (S) */
+    const float *logprobs, *value_preds, *returns, *advantages; /* (S) */
+    uint32_t size;               /* S */
+} mrl_mappo_batch;
+typedef struct mrl_mappo_optimizer {
+    float *params_dev;           /* the tensor mrl_cnn_policy.params_dev points at; updated in place */
+    float *exp_avg, *exp_avg_sq; /* (P) each */
+    uint32_t step;               /* Adam steps taken BEFORE this call (both nets step together) */
+} mrl_mappo_optimizer;
+int mrl_mappo_workspace_bytes(uint32_t width, uint32_t height, uint32_t channels, uint32_t hidden, uint32_t minibatch_size,
+                              uint32_t num_minibatches, uint64_t *out);
+int mrl_mappo_update(const mrl_mappo_policy *policy, const mrl_mappo_optimizer *opt, const mrl_mappo_batch *batch,
+                     const int32_t *indices_dev /* (K, B) */, uint32_t num_minibatches /* K */, uint32_t minibatch_size /* B */,
+                     const mrl_mappo_config *cfg, float *value_norm_state_dev_or_null /* (3) */, void *workspace_dev,
+                     uint64_t workspace_bytes, float *stats_dev_or_null /* (K, 8) */, float *grads_dev_or_null /* (K, P) */,
+                     int gpu_id, void *hip_stream);
+
 int mrl_tensor(mrl_sim *sim, int slot, mrl_tensor_desc *out);
 int mrl_game(const mrl_sim *sim);
 uint32_t mrl_num_worlds(const mrl_sim *sim);

@@ -33,6 +33,8 @@ WIDE_HIDDEN, WIDE_MAX_ACTIONS = 512, 64  # MRL_WIDE_*
 PPO_NORM_ADV, PPO_CLIP_VLOSS = 1, 2  # MRL_PPO_*
 CNN_VALUE_ONLY = 4  # MRL_CNN_VALUE_ONLY: flag of mrl_cnn_act beside POLICY_GREEDY
 CNN_HIDDEN, CNN_ACTIONS = 64, 6  # the one shape mrl_cnn_act runs
+MAPPO_VALUENORM, MAPPO_HUBER_LOSS, MAPPO_CLIPPED_VALUE_LOSS, MAPPO_MAX_GRAD_NORM = 1, 2, 4, 8  # MRL_MAPPO_*
+MAPPO_STATS = ("value_loss", "critic_grad_norm", "policy_loss", "dist_entropy", "actor_grad_norm", "ratio", "clipfrac", "reserved")
 PPO_STATS = ("pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac", "total_norm", "loss")  # a stats row
 
 # every symbol include/mrl_envs.h declares
@@ -47,7 +49,7 @@ SYMBOLS = [
     "mrl_acrobot_create", "mrl_enable_episode_stats", "mrl_clear_episode_totals", "mrl_mlp_policy_num_params",
     "mrl_rollout_policy", "mrl_gae", "mrl_ppo_workspace_bytes", "mrl_ppo_update", "mrl_wide_policy_num_params",
     "mrl_agent_workspace_bytes", "mrl_agent_act", "mrl_agent_credit", "mrl_gae_active", "mrl_cnn_policy_num_params",
-    "mrl_cnn_workspace_bytes", "mrl_cnn_act", "mrl_rollout_cnn",
+    "mrl_cnn_workspace_bytes", "mrl_cnn_act", "mrl_rollout_cnn", "mrl_mappo_workspace_bytes", "mrl_mappo_update",
 ]
 ABI_VERSION = 4  # MRL_ABI_VERSION of include/mrl_envs.h this binding was written against
 
@@ -120,6 +122,27 @@ CNN_RECORD_BUFFERS = ("actions", "logprobs", "values", "rewards", "dones", "next
 
 class CnnRecordDesc(ctypes.Structure):  # mrl_cnn_record
     _fields_ = [(name, ctypes.c_void_p) for name in CNN_RECORD_BUFFERS] + [("num_steps", ctypes.c_uint32)]
+
+
+class MappoPolicyDesc(ctypes.Structure):  # mrl_mappo_policy
+    _fields_ = [("params_dev", ctypes.c_void_p), ("hidden", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("width", ctypes.c_uint32),
+                ("height", ctypes.c_uint32), ("channels", ctypes.c_uint32)]
+
+
+class MappoConfig(ctypes.Structure):  # mrl_mappo_config
+    _fields_ = [(name, ctypes.c_float) for name in ("clip_param", "entropy_coef", "value_loss_coef", "max_grad_norm", "huber_delta", "lr",
+                                                    "critic_lr", "beta1", "beta2", "opti_eps", "valuenorm_beta",
+                                                    "valuenorm_one_minus_beta", "valuenorm_epsilon")] + [("flags", ctypes.c_uint32)]
+
+
+class MappoBatch(ctypes.Structure):  # mrl_mappo_batch
+    _fields_ = [(name, ctypes.c_void_p) for name in ("obs", "actions", "logprobs", "value_preds", "returns", "advantages")] + \
+               [("size", ctypes.c_uint32)]
+
+
+class MappoOptimizerDesc(ctypes.Structure):  # mrl_mappo_optimizer
+    _fields_ = [("params_dev", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p),
+                ("step", ctypes.c_uint32)]
 
 
 class MrlError(RuntimeError):
@@ -249,6 +272,9 @@ def lib():
     L.mrl_cnn_workspace_bytes.restype = ctypes.c_uint64
     L.mrl_cnn_act.argtypes = [vp, u32, ctypes.POINTER(CnnPolicyDesc), ctypes.POINTER(CnnRecordDesc), u32, ctypes.c_uint64, u32, u32, vp,
                               ctypes.c_uint64, vp]
+    L.mrl_mappo_workspace_bytes.argtypes = [u32, u32, u32, u32, u32, u32, ctypes.POINTER(ctypes.c_uint64)]
+    L.mrl_mappo_update.argtypes = [ctypes.POINTER(MappoPolicyDesc), ctypes.POINTER(MappoOptimizerDesc), ctypes.POINTER(MappoBatch), vp,
+                                   u32, u32, ctypes.POINTER(MappoConfig), vp, vp, ctypes.c_uint64, vp, vp, i32, vp]
     L.mrl_rollout_cnn.argtypes = [vp, u32, ctypes.POINTER(CnnPolicyDesc), ctypes.POINTER(CnnRecordDesc), vp, ctypes.c_uint64, u32, vp]
     L.mrl_tensor.argtypes = [vp, i32, ctypes.POINTER(TensorDesc)]
     L.mrl_game.argtypes = [vp]

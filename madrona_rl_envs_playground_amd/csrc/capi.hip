@@ -6,6 +6,7 @@
 #include "ppo_update.hpp"
 #include "wide_policy.hpp"
 #include "cnn_policy.hpp"
+#include "cnn_update.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -1002,6 +1003,91 @@ int mrl_cnn_act(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, co
         cnn_rows(args, record, row, value_only);
         args.seed = seed, args.step = step, args.flags = flags;
         mrl::launch_cnn_act(args, (hipStream_t)hip_stream);
+    });
+}
+
+// what mrl_mappo_workspace_bytes and mrl_mappo_update refuse alike: nullptr when the shape can run, else why not
+static const char *mappo_shape_error(uint32_t width, uint32_t height, uint32_t channels, uint32_t hidden, uint32_t minibatch_size)
+{
+    if (hidden != mrl::kCnnHidden) return "hidden must be 64";
+    if (width < 3 || height < 3 || channels == 0) return "the kitchen must be at least 3 x 3 with at least one channel";
+    if ((uint64_t)width * height * channels > 65535u) return "the kitchen's LDS image does not fit one workgroup's 160 KiB";
+    if (mrl::cnn_update_lds(width, height, channels).total > mrl::kCnnLdsLimit) return "the kitchen's LDS image does not fit one workgroup's 160 KiB";
+    if (minibatch_size == 0) return "minibatch_size must be positive";
+    return nullptr;
+}
+
+int mrl_mappo_workspace_bytes(uint32_t width, uint32_t height, uint32_t channels, uint32_t hidden, uint32_t minibatch_size,
+                              uint32_t num_minibatches, uint64_t *out)
+{
+    const char *why = out ? mappo_shape_error(width, height, channels, hidden, minibatch_size) : "null output pointer";
+    if (why) {
+        mrl::set_error("mrl_mappo_workspace_bytes: %s (width %u, height %u, channels %u, hidden %u, minibatch_size %u)", why, width, height,
+                       channels, hidden, minibatch_size);
+        return MRL_ERR_INVALID;
+    }
+    *out = mrl::mappo_workspace(mrl::cnn_net_params(width, height, channels, mrl::kCnnActions), minibatch_size, num_minibatches).total *
+           sizeof(float);
+    return MRL_OK;
+}
+
+int mrl_mappo_update(const mrl_mappo_policy *policy, const mrl_mappo_optimizer *opt, const mrl_mappo_batch *batch,
+                     const int32_t *indices_dev, uint32_t num_minibatches, uint32_t minibatch_size, const mrl_mappo_config *cfg,
+                     float *value_norm_state, void *workspace_dev, uint64_t workspace_bytes, float *stats_dev_or_null,
+                     float *grads_dev_or_null, int gpu_id, void *hip_stream)
+{
+    if (!policy || !opt || !batch || (!indices_dev && num_minibatches) || !cfg || !workspace_dev) {  // (no rows: no index array)
+        mrl::set_error("mrl_mappo_update: null policy, optimizer, batch, index array, configuration or workspace");
+        return MRL_ERR_INVALID;
+    }
+    if (!policy->params_dev || !opt->params_dev || !opt->exp_avg || !opt->exp_avg_sq || !batch->obs || !batch->actions || !batch->logprobs ||
+        !batch->value_preds || !batch->returns || !batch->advantages) {
+        mrl::set_error("mrl_mappo_update: null parameter, moment or batch array");
+        return MRL_ERR_INVALID;
+    }
+    if (policy->params_dev != opt->params_dev) {
+        mrl::set_error("mrl_mappo_update: the policy's and the optimizer's params_dev must be the same array");
+        return MRL_ERR_INVALID;
+    }
+    if (cfg->flags & ~mrl::kMappoKnownFlags) {
+        mrl::set_error("mrl_mappo_update: flags 0x%x: only the four MRL_MAPPO_* bits exist", cfg->flags);
+        return MRL_ERR_INVALID;
+    }
+    if ((cfg->flags & MRL_MAPPO_VALUENORM) && !value_norm_state) {
+        mrl::set_error("mrl_mappo_update: MRL_MAPPO_VALUENORM needs value_norm_state");
+        return MRL_ERR_INVALID;
+    }
+    const char *why = mappo_shape_error(policy->width, policy->height, policy->channels, policy->hidden, minibatch_size);
+    if (why || batch->size == 0) {
+        mrl::set_error("mrl_mappo_update: %s (width %u, height %u, channels %u, hidden %u, minibatch_size %u, batch size %u)",
+                       why ? why : "the batch must hold at least one sample", policy->width, policy->height, policy->channels, policy->hidden,
+                       minibatch_size, batch->size);
+        return MRL_ERR_INVALID;
+    }
+    const uint64_t actor = mrl::cnn_net_params(policy->width, policy->height, policy->channels, mrl::kCnnActions);
+    const uint64_t need_bytes = mrl::mappo_workspace(actor, minibatch_size, num_minibatches).total * sizeof(float);
+    if (workspace_bytes < need_bytes) {
+        mrl::set_error("mrl_mappo_update: workspace of %llu bytes, mrl_mappo_workspace_bytes asks for %llu", (unsigned long long)workspace_bytes,
+                       (unsigned long long)need_bytes);
+        return MRL_ERR_INVALID;
+    }
+    const void *words[] = {opt->params_dev, opt->exp_avg, opt->exp_avg_sq, batch->actions, batch->logprobs, batch->value_preds, batch->returns,
+                           batch->advantages, indices_dev, value_norm_state, stats_dev_or_null, grads_dev_or_null};
+    uintptr_t low_bits = 0;
+    for (const void *p : words) low_bits |= reinterpret_cast<uintptr_t>(p) & 3u;
+    if (low_bits || (reinterpret_cast<uintptr_t>(workspace_dev) & 15u)) {
+        mrl::set_error("mrl_mappo_update: the float and int32 arrays must start on 4-byte boundaries and the workspace on a 16-byte one");
+        return MRL_ERR_INVALID;
+    }
+    if (mrl::capturing(hip_stream)) {
+        mrl::set_error("mrl_mappo_update: the Adam step number travels in kernel arguments, so the call cannot be captured in a HIP "
+                       "graph: a replay would repeat the same step's bias correction");
+        return MRL_ERR_INVALID;
+    }
+    mrl::DeviceGuard on(gpu_id);
+    return guarded([&] {
+        mrl::launch_mappo_update(*policy, *opt, *batch, indices_dev, num_minibatches, minibatch_size, *cfg, value_norm_state,
+                                 static_cast<float *>(workspace_dev), stats_dev_or_null, grads_dev_or_null, (hipStream_t)hip_stream);
     });
 }
 

@@ -1,0 +1,86 @@
+// MAPPO's update for the Overcooked CNN actor-critic on the device (C ABI: mrl_mappo_update, mrl_mappo_workspace_bytes in
+// include/mrl_envs.h).  The kernels live in cnn_update.hip; capi.hip validates the arguments.
+#pragma once
+
+#include "cnn_policy.hpp"
+
+namespace mrl {
+
+constexpr uint32_t kMappoMaxGroups = 256;  // workgroups per net, hence partial gradient vectors per net and row, however large B is
+constexpr uint32_t kMappoStats = 8;        // columns of a stats row
+constexpr uint32_t kMappoReduceThreads = 256;
+constexpr uint32_t kMappoKnownFlags = MRL_MAPPO_VALUENORM | MRL_MAPPO_HUBER_LOSS | MRL_MAPPO_CLIPPED_VALUE_LOSS | MRL_MAPPO_MAX_GRAD_NORM;
+
+// How the B samples of a row are shared out (ppo_shape's rule with this kernel's tile): workgroup g of `groups` owns samples
+// [g * share, min(B, (g + 1) * share)), share a whole number of tiles.  Every workgroup owns at least one sample.
+struct MappoShape {
+    uint32_t groups;
+    uint64_t share;
+};
+
+inline MappoShape mappo_shape(uint32_t minibatch_size)
+{
+    const uint64_t tiles = ((uint64_t)minibatch_size + kCnnTile - 1) / kCnnTile;
+    const uint64_t want = tiles < kMappoMaxGroups ? tiles : kMappoMaxGroups;
+    const uint64_t tiles_each = want ? (tiles + want - 1) / want : 1;
+    MappoShape s;
+    s.groups = (uint32_t)(tiles_each ? (tiles + tiles_each - 1) / tiles_each : 0);
+    s.share = tiles_each * kCnnTile;
+    return s;
+}
+
+// The gradient workgroup's LDS image: mrl_cnn_act's (cnn_lds) with region A at least large enough for what back-propagation
+// keeps beside the forward pass's chunk, h1, h2 and head outputs -- dL/d(head output) (32 x 8), dL/d(pre-activation of fc2) and
+// of fc1 (32 rows of 65 floats each) -- and, behind the activation image, the tile's sample numbers and row shifts (32 x 2
+// words).  The activation image doubles as dL/d(pre-activation of the convolution): it is overwritten in place once dW_fc1 has
+// been formed, and the observation rows are loaded a second time into region A for dW_conv.
+constexpr uint32_t kUpdDoutAt = kCnnFcBytes, kUpdDh2At = kUpdDoutAt + kCnnTile * 8 * 4, kUpdDh1At = kUpdDh2At + kCnnTile * kCnnFcLd * 4,
+                   kUpdFcBytes = kUpdDh1At + kCnnTile * kCnnFcLd * 4;
+struct CnnUpdateLds {
+    CnnLds fwd;        // act_at moved up where region A grew; every other field is cnn_lds's
+    uint32_t tail_at;  // sample numbers (32 words), then row shifts (32 words)
+    uint32_t total;
+};
+inline CnnUpdateLds cnn_update_lds(uint32_t W, uint32_t H, uint32_t F)
+{
+    CnnUpdateLds u{};
+    u.fwd = cnn_lds(W, H, F);
+    if (u.fwd.act_at < kUpdFcBytes) u.fwd.act_at = kUpdFcBytes;
+    u.tail_at = u.fwd.act_at + kCnnTile * u.fwd.act_ld * 4u;
+    u.fwd.total = u.tail_at;
+    u.total = u.tail_at + kCnnTile * 2u * 4u;
+    return u;
+}
+
+// The caller's scratch, in floats: every row's ValueNorm (mean, sqrt(var)) and (mean, mean of squares) of its returns; the
+// workgroups' partial gradient vectors (2 nets, groups, stride) and partial stats (2, groups, 8 doubles); the summed gradient
+// (2, stride); the reduce launch's per-block sums of g^2 (2, blocks).  stride = the actor's parameter count, padded.
+struct MappoWorkspace {
+    uint64_t row_norm, row_sums, partial_grads, partial_stats, grad, sumsq, total;
+    uint64_t stride, groups, blocks;
+};
+
+inline MappoWorkspace mappo_workspace(uint64_t actor_params, uint32_t minibatch_size, uint32_t num_minibatches)
+{
+    const auto pad = [](uint64_t n) { return (n + 3) & ~uint64_t(3); };  // every array on a 16-byte boundary
+    const uint64_t tiles = ((uint64_t)minibatch_size + kCnnTile - 1) / kCnnTile;
+    MappoWorkspace w;
+    w.groups = tiles < kMappoMaxGroups ? tiles : kMappoMaxGroups;  // room for min(tiles, cap); mappo_shape may use fewer
+    w.stride = pad(actor_params);
+    w.blocks = (w.stride + kMappoReduceThreads - 1) / kMappoReduceThreads;
+    w.row_norm = 0;
+    w.row_sums = w.row_norm + pad(2 * (uint64_t)num_minibatches);
+    w.partial_grads = w.row_sums + pad(2 * (uint64_t)num_minibatches);
+    w.partial_stats = w.partial_grads + 2 * w.groups * w.stride;
+    w.grad = w.partial_stats + pad(2 * 2 * w.groups * kMappoStats);
+    w.sumsq = w.grad + 2 * w.stride;
+    w.total = w.sumsq + pad(2 * w.blocks);
+    return w;
+}
+
+// K rows enqueued on `stream`; every argument has been validated (capi.hip, mrl_mappo_update).
+void launch_mappo_update(const mrl_mappo_policy &policy, const mrl_mappo_optimizer &opt, const mrl_mappo_batch &batch,
+                         const int32_t *indices, uint32_t num_minibatches, uint32_t minibatch_size, const mrl_mappo_config &cfg,
+                         float *value_norm_state, float *workspace, float *stats, float *grads, hipStream_t stream);
+
+}  // namespace mrl

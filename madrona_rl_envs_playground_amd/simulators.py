@@ -737,6 +737,159 @@ def ppo_update(policy, optimizer, rollout, advantages, returns, indices, clip_co
     return PpoResult(out_stats, out_grads)
 
 
+class ValueNorm:
+    """The reference's ``ValueNorm`` (train/MAPPO/utils/valuenorm.py, scalar values, ``per_element_update`` off) as the three
+    device floats ``mrl_mappo_update`` keeps up to date: ``state`` = (running_mean, running_mean_sq, debiasing_term).  The
+    methods are torch ops on device tensors with the reference's formulas; none of them waits for the device."""
+
+    def __init__(self, device, beta=0.99999, epsilon=1e-5):
+        self.beta, self.epsilon = float(beta), float(epsilon)
+        self.state = torch.zeros(3, dtype=torch.float32, device=torch.device(device))
+
+    def running_mean_var(self):
+        floor = self.state[2].clamp(min=self.epsilon)
+        mean = self.state[0] / floor
+        return mean, (self.state[1] / floor - mean ** 2).clamp(min=1e-2)
+
+    def update(self, x):
+        """One ``ValueNorm.update`` in torch, as the reference runs it (``mappo_update`` does this on the device per row)."""
+        x = x.to(torch.float32)
+        self.state[0].mul_(self.beta).add_(x.mean() * (1.0 - self.beta))
+        self.state[1].mul_(self.beta).add_((x ** 2).mean() * (1.0 - self.beta))
+        self.state[2].mul_(self.beta).add_(1.0 * (1.0 - self.beta))
+
+    def normalize(self, x):
+        mean, var = self.running_mean_var()
+        return (x.to(torch.float32) - mean) / torch.sqrt(var)
+
+    def denormalize(self, x):
+        mean, var = self.running_mean_var()
+        return x.to(torch.float32) * torch.sqrt(var) + mean
+
+
+class MappoOptimizer:
+    """The state of MAPPO's two Adam optimizers for a ``CnnPolicy`` (``R_MAPPOPolicy``: ``torch.optim.Adam(lr, eps=opti_eps,
+    weight_decay=0)`` for the actor and for the critic): ``exp_avg`` and ``exp_avg_sq`` over the whole flat tensor, the number
+    of steps both have taken (``step``) and the scratch ``mrl_mappo_update`` asks for, kept from call to call.  ``lr`` and
+    ``critic_lr`` are ordinary attributes: assign to them for the reference's ``lr_decay``."""
+
+    def __init__(self, policy, lr=5e-4, critic_lr=5e-4, betas=(0.9, 0.999), eps=1e-5):
+        if not isinstance(policy, CnnPolicy):
+            raise ValueError("policy must be a CnnPolicy")
+        self.policy = policy
+        self.lr, self.critic_lr, self.betas, self.eps = float(lr), float(critic_lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.exp_avg = torch.zeros_like(policy.params)
+        self.exp_avg_sq = torch.zeros_like(policy.params)
+        self.step = 0
+        self._workspace = None
+
+    def workspace_bytes(self, minibatch_size, num_minibatches):
+        """``mrl_mappo_workspace_bytes`` for this policy's shape."""
+        p = self.policy
+        out = ctypes.c_uint64(0)
+        _lib.check(_lib.lib().mrl_mappo_workspace_bytes(p.width, p.height, p.channels, p.hidden, int(minibatch_size), int(num_minibatches),
+                                                        ctypes.byref(out)))
+        return int(out.value)
+
+    def workspace(self, minibatch_size, num_minibatches):
+        """A uint8 tensor of at least ``workspace_bytes`` on the parameters' device: the cached one while it is large enough."""
+        need = self.workspace_bytes(minibatch_size, num_minibatches)
+        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != self.policy.params.device:
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.policy.params.device)
+        return self._workspace
+
+
+def mappo_advantages(record, value_norm=None, gamma=0.99, gae_lambda=0.95):
+    """``(advantages, returns)`` of a ``CnnRecord``, each (T, N, P), as ``R_MAPPO.train`` and ``SharedReplayBuffer.compute_returns``
+    form them (train/MAPPO/r_mappo.py:174-182, utils/shared_buffer.py:216-228 with ``use_gae``; every active mask one): the
+    record's values denormalised when a ``ValueNorm`` is given, ``gae`` on those (``mrl_gae``: the reference's recurrence with
+    ``masks[t + 1] = 1 - dones[t + 1]``), then ``(A - mean) / (std + 1e-5)`` over the whole buffer with torch's unbiased std.
+    ``returns`` are in the denormalised scale, as the reference's buffer holds them.  It runs once per update, so apart from
+    ``mrl_gae`` it is a handful of torch ops on the record's device; it does not wait."""
+    if not isinstance(record, CnnRecord):
+        raise ValueError("record must be a CnnRecord")
+    rollout = record.rollout()
+    if value_norm is not None:
+        t, cols = record.num_steps, record.num_worlds * record.num_players
+        values = value_norm.denormalize(record.values).contiguous()
+        rollout = rollout._replace(values=values[:t].view(t, cols), next_value=values[t].view(cols))
+    advantages, returns = gae(rollout, gamma, gae_lambda)
+    advantages = (advantages - advantages.mean()) / (advantages.std() + 1e-5)
+    shape = (record.num_steps, record.num_worlds, record.num_players)
+    return advantages.view(shape), returns.view(shape)
+
+
+MappoResult = collections.namedtuple("MappoResult", "stats grads")  # (K, 8) in the order of ``_lib.MAPPO_STATS`` / (K, P), or None
+
+
+def mappo_update(policy, optimizer, record, ring, advantages, returns, indices, value_norm=None, clip_param=0.2, entropy_coef=0.01,
+                 value_loss_coef=1.0, max_grad_norm=10.0, huber_delta=10.0, use_huber_loss=True, use_clipped_value_loss=True,
+                 use_max_grad_norm=True, stats=True, grads=False):
+    """One actor and one critic Adam step per row of ``indices`` on MAPPO's losses (``R_MAPPO.ppo_update``,
+    train/MAPPO/r_mappo.py:91-164, feed-forward networks), on the device (``mrl_mappo_update``: three launches per row),
+    enqueued on torch's current stream; it does not wait.  ``policy.params`` is updated in place -- the next ``rollout`` or
+    ``cnn_act`` reads it as it stands --, ``optimizer.step`` grows by the number of rows, and with ``value_norm`` (a
+    ``ValueNorm``: the reference's ``use_valuenorm``) its state takes one update per row.  ``record`` and ``ring`` are what
+    ``rollout_cnn`` filled: sample ``(t N + n) P + p`` is row t, world n, seat p, and its observation is ring slot t, read as
+    int8 in place.  ``advantages`` and ``returns`` (T, N, P) are ``mappo_advantages``'; ``indices`` (K, B) int32 sample
+    numbers (``minibatch_indices``).  The defaults are the reference's (train/config.py).  Returns ``MappoResult(stats,
+    grads)``: (K, 8) float32, columns ``_lib.MAPPO_STATS``, and (K, P) the unclipped gradients, each None unless asked for.
+    Not built: active masks, PopArt, recurrent policies, ``update_actor=False``, weight decay."""
+    if not isinstance(policy, CnnPolicy) or not isinstance(optimizer, MappoOptimizer) or optimizer.policy is not policy:
+        raise ValueError("policy must be a CnnPolicy and optimizer the MappoOptimizer made for it")
+    if not isinstance(record, CnnRecord):
+        raise ValueError("record must be a CnnRecord")
+    if value_norm is not None and not isinstance(value_norm, ValueNorm):
+        raise ValueError("value_norm must be a ValueNorm or None")
+    p = policy.params
+    if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous() or p.numel() != policy.num_params:
+        raise ValueError("policy.params must be a contiguous float32 tensor of num_params elements on a GPU")
+    device, f32 = p.device, torch.float32
+    count = record.num_steps * record.num_worlds * record.num_players
+    row_bytes = policy.width * policy.height * policy.channels
+    # views of the record's first T rows: contiguous, because the rows are the leading dimension
+    wanted = [("policy.params", p, f32, p.numel()), ("optimizer.exp_avg", optimizer.exp_avg, f32, p.numel()),
+              ("optimizer.exp_avg_sq", optimizer.exp_avg_sq, f32, p.numel()), ("record.actions", record.actions, torch.int32, count),
+              ("record.logprobs", record.logprobs, f32, count), ("record.values", record.values, f32, count + count // max(record.num_steps, 1)),
+              ("advantages", advantages, f32, count), ("returns", returns, f32, count), ("indices", indices, torch.int32, None)]
+    if value_norm is not None:
+        wanted.append(("value_norm.state", value_norm.state, f32, 3))
+    for name, tensor, dtype, numel in wanted:
+        if (not isinstance(tensor, torch.Tensor) or tensor.device != device or tensor.dtype != dtype or not tensor.is_contiguous() or
+                (numel is not None and tensor.numel() != numel)):
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor on {device}" + (f" of {numel} elements" if numel else ""))
+    if (not isinstance(ring, torch.Tensor) or ring.device != device or ring.dtype != torch.int8 or not ring.is_contiguous() or
+            ring.numel() < count * row_bytes):
+        raise ValueError(f"ring must be a contiguous torch.int8 tensor on {device} of at least {count * row_bytes} elements: (T + 1, N, P, "
+                         f"H, W, F) for the policy's {policy.width} x {policy.height} kitchen with {policy.channels} channels")
+    if indices.dim() != 2:
+        raise ValueError("indices must be (rows, minibatch_size)")
+    rows, width = indices.shape
+    workspace = optimizer.workspace(width, rows) if width else None
+    out_stats = torch.empty((rows, len(_lib.MAPPO_STATS)), dtype=f32, device=device) if stats else None
+    out_grads = torch.empty((rows, p.numel()), dtype=f32, device=device) if grads else None
+    shape = _lib.MappoPolicyDesc(p.data_ptr(), policy.hidden, 0, policy.width, policy.height, policy.channels)
+    opt = _lib.MappoOptimizerDesc(p.data_ptr(), optimizer.exp_avg.data_ptr(), optimizer.exp_avg_sq.data_ptr(), optimizer.step)
+    batch = _lib.MappoBatch(ring.data_ptr(), record.actions.data_ptr(), record.logprobs.data_ptr(), record.values.data_ptr(),
+                            returns.data_ptr(), advantages.data_ptr(), count)
+    beta = value_norm.beta if value_norm is not None else 0.99999
+    flags = ((_lib.MAPPO_VALUENORM if value_norm is not None else 0) | (_lib.MAPPO_HUBER_LOSS if use_huber_loss else 0) |
+             (_lib.MAPPO_CLIPPED_VALUE_LOSS if use_clipped_value_loss else 0) | (_lib.MAPPO_MAX_GRAD_NORM if use_max_grad_norm else 0))
+    # torch multiplies a float32 tensor by the Python floats beta and 1.0 - beta rounded to float32, each on its own
+    cfg = _lib.MappoConfig(clip_param, entropy_coef, value_loss_coef, max_grad_norm, huber_delta, optimizer.lr, optimizer.critic_lr,
+                           optimizer.betas[0], optimizer.betas[1], optimizer.eps, beta, 1.0 - beta,
+                           value_norm.epsilon if value_norm is not None else 1e-5, flags)
+    gpu = device.index
+    _lib.check(_lib.lib().mrl_mappo_update(ctypes.byref(shape), ctypes.byref(opt), ctypes.byref(batch), indices.data_ptr(), rows, width,
+                                           ctypes.byref(cfg), value_norm.state.data_ptr() if value_norm is not None else None,
+                                           workspace.data_ptr() if workspace is not None else None,
+                                           workspace.numel() if workspace is not None else 0,
+                                           out_stats.data_ptr() if stats else None, out_grads.data_ptr() if grads else None, gpu,
+                                           _stream_ptr(gpu)))
+    optimizer.step += rows
+    return MappoResult(out_stats, out_grads)
+
+
 def totals_of(totals):
     """The column sums of a TOTALS tensor (float64, (blocks, 2 + players)) as ``episode_totals`` returns them."""
     sums = totals.sum(dim=0).tolist()  # (the host waits here)
