@@ -709,6 +709,29 @@ int mrl_gae(const float *rewards, const float *values, const float *dones, const
     });
 }
 
+// what mrl_ppo_update and mrl_mappo_update (`what`) refuse alike, after their own checks: a workspace smaller than `sizer` asks
+// for, arrays or a workspace off their boundaries (`arrays_rule` says which arrays, `arrays_off` whether one of them is), and a
+// capturing stream
+static int update_refusal(const char *what, const char *sizer, uint64_t workspace_bytes, uint64_t need_bytes, const void *workspace_dev,
+                          bool arrays_off, const char *arrays_rule, void *hip_stream)
+{
+    if (workspace_bytes < need_bytes) {
+        mrl::set_error("%s: workspace of %llu bytes, %s asks for %llu", what, (unsigned long long)workspace_bytes, sizer,
+                       (unsigned long long)need_bytes);
+        return MRL_ERR_INVALID;
+    }
+    if (arrays_off || (reinterpret_cast<uintptr_t>(workspace_dev) & 15u)) {
+        mrl::set_error("%s: %s and the workspace on a 16-byte one", what, arrays_rule);
+        return MRL_ERR_INVALID;
+    }
+    if (mrl::capturing(hip_stream)) {
+        mrl::set_error("%s: the Adam step number travels in kernel arguments, so the call cannot be captured in a HIP graph: a replay "
+                       "would repeat the same step's bias correction", what);
+        return MRL_ERR_INVALID;
+    }
+    return MRL_OK;
+}
+
 static bool ppo_shape_ok(uint32_t obs_dim, uint32_t hidden, uint32_t num_actions)
 {
     return hidden == mrl::kPolicyHidden && ((obs_dim == 4 && (num_actions == 2 || num_actions == 3)) || (obs_dim == 6 && num_actions == 3));
@@ -754,21 +777,11 @@ int mrl_ppo_update(const mrl_mlp_policy *shape, const mrl_ppo_optimizer *opt, co
     }
     const uint64_t params = mrl_mlp_policy_num_params(shape->obs_dim, shape->hidden, shape->num_actions);
     const uint64_t need_bytes = mrl::ppo_workspace(params, minibatch_size, num_minibatches).total * sizeof(float);
-    if (workspace_bytes < need_bytes) {
-        mrl::set_error("mrl_ppo_update: workspace of %llu bytes, mrl_ppo_workspace_bytes asks for %llu", (unsigned long long)workspace_bytes,
-                       (unsigned long long)need_bytes);
-        return MRL_ERR_INVALID;
-    }
-    const uintptr_t row_align = shape->obs_dim == 4 ? 15u : 7u;  // the observation rows are loaded 16 / 8 bytes at a time
-    if ((reinterpret_cast<uintptr_t>(batch->obs) & row_align) || (reinterpret_cast<uintptr_t>(workspace_dev) & 15u)) {
-        mrl::set_error("mrl_ppo_update: obs must start on a %u-byte boundary and the workspace on a 16-byte one", (unsigned)row_align + 1u);
-        return MRL_ERR_INVALID;
-    }
-    if (mrl::capturing(hip_stream)) {
-        mrl::set_error("mrl_ppo_update: the Adam step number travels in kernel arguments, so the call cannot be captured in a HIP "
-                       "graph: a replay would repeat the same step's bias correction");
-        return MRL_ERR_INVALID;
-    }
+    const bool wide_rows = shape->obs_dim == 4;  // the observation rows are loaded 16 / 8 bytes at a time
+    if (int rc = update_refusal("mrl_ppo_update", "mrl_ppo_workspace_bytes", workspace_bytes, need_bytes, workspace_dev,
+                                reinterpret_cast<uintptr_t>(batch->obs) & (wide_rows ? 15u : 7u),
+                                wide_rows ? "obs must start on a 16-byte boundary" : "obs must start on a 8-byte boundary", hip_stream))
+        return rc;
     mrl::DeviceGuard on(gpu_id);
     return guarded([&] {
         mrl::launch_ppo_update(*shape, *opt, *batch, indices_dev, num_minibatches, minibatch_size, *cfg,
@@ -1066,24 +1079,13 @@ int mrl_mappo_update(const mrl_mappo_policy *policy, const mrl_mappo_optimizer *
     }
     const uint64_t actor = mrl::cnn_net_params(policy->width, policy->height, policy->channels, mrl::kCnnActions);
     const uint64_t need_bytes = mrl::mappo_workspace(actor, minibatch_size, num_minibatches).total * sizeof(float);
-    if (workspace_bytes < need_bytes) {
-        mrl::set_error("mrl_mappo_update: workspace of %llu bytes, mrl_mappo_workspace_bytes asks for %llu", (unsigned long long)workspace_bytes,
-                       (unsigned long long)need_bytes);
-        return MRL_ERR_INVALID;
-    }
     const void *words[] = {opt->params_dev, opt->exp_avg, opt->exp_avg_sq, batch->actions, batch->logprobs, batch->value_preds, batch->returns,
                            batch->advantages, indices_dev, value_norm_state, stats_dev_or_null, grads_dev_or_null};
     uintptr_t low_bits = 0;
     for (const void *p : words) low_bits |= reinterpret_cast<uintptr_t>(p) & 3u;
-    if (low_bits || (reinterpret_cast<uintptr_t>(workspace_dev) & 15u)) {
-        mrl::set_error("mrl_mappo_update: the float and int32 arrays must start on 4-byte boundaries and the workspace on a 16-byte one");
-        return MRL_ERR_INVALID;
-    }
-    if (mrl::capturing(hip_stream)) {
-        mrl::set_error("mrl_mappo_update: the Adam step number travels in kernel arguments, so the call cannot be captured in a HIP "
-                       "graph: a replay would repeat the same step's bias correction");
-        return MRL_ERR_INVALID;
-    }
+    if (int rc = update_refusal("mrl_mappo_update", "mrl_mappo_workspace_bytes", workspace_bytes, need_bytes, workspace_dev, low_bits,
+                                "the float and int32 arrays must start on 4-byte boundaries", hip_stream))
+        return rc;
     mrl::DeviceGuard on(gpu_id);
     return guarded([&] {
         mrl::launch_mappo_update(*policy, *opt, *batch, indices_dev, num_minibatches, minibatch_size, *cfg, value_norm_state,

@@ -22,8 +22,6 @@
 #include "cnn_forward.hpp"
 #include "random_policy.hpp"
 
-#include <atomic>
-
 namespace mrl {
 
 extern __shared__ __attribute__((aligned(16))) unsigned char cnn_lds_image[];
@@ -139,38 +137,12 @@ __global__ void __launch_bounds__(kCnnThreads) mrl_cnn_act(CnnActArgs a)
     const float l0 = outs[tid * 8u], l1 = outs[tid * 8u + 1], l2 = outs[tid * 8u + 2], l3 = outs[tid * 8u + 3], l4 = outs[tid * 8u + 4],
                 l5 = outs[tid * 8u + 5];
     const float l[kCnnActions] = {l0, l1, l2, l3, l4, l5};  // statically indexed below: stays in registers
-    float top = l[0];
-    int first = 0;  // the first arg-max
-#pragma unroll
-    for (int i = 1; i < (int)kCnnActions; i++) {
-        if (l[i] > top) {
-            top = l[i];
-            first = i;
-        }
-    }
-    float e[kCnnActions], sum = 0.0f;
-#pragma unroll
-    for (int i = 0; i < (int)kCnnActions; i++) {
-        e[i] = expf(l[i] - top);
-        sum += e[i];
-    }
-    int action = first;
-    if (!(a.flags & MRL_POLICY_GREEDY)) {
-        const float u = (float)(policy_hash(a.seed, a.step, world, seat) >> 8) * 0x1p-24f;
-        float cdf = 0.0f;
-        action = 0;
-#pragma unroll
-        for (int i = 0; i < (int)kCnnActions - 1; i++) {
-            cdf += e[i] / sum;
-            action += u >= cdf ? 1 : 0;
-        }
-    }
-    float chosen = l[0];
-#pragma unroll
-    for (int i = 1; i < (int)kCnnActions; i++) chosen = action == i ? l[i] : chosen;
+    int action;
+    float logprob;
+    categorical_sample<(int)kCnnActions>(l, policy_hash(a.seed, a.step, world, seat), a.flags & MRL_POLICY_GREEDY, action, logprob);
     a.action[agent] = action;
     if (a.actions_row) a.actions_row[cell] = action;
-    if (a.logprobs_row) a.logprobs_row[cell] = (chosen - top) - logf(sum);
+    if (a.logprobs_row) a.logprobs_row[cell] = logprob;
     if (a.logits_row) {
 #pragma unroll
         for (int i = 0; i < (int)kCnnActions; i++) a.logits_row[cell * kCnnActions + i] = l[i];
@@ -181,15 +153,7 @@ void launch_cnn_act(const CnnActArgs &args, hipStream_t stream)
 {
     const uint64_t total = (uint64_t)args.num_worlds * args.num_seats;
     if (total == 0 || args.nets == 0) return;
-    // more dynamic LDS than the default limit: the runtime is told once per device (a refusal shows in the launch that follows)
-    static std::atomic<bool> told[64];
-    int device = 0;
-    if (args.lds.total > 64u * 1024u && hipGetDevice(&device) == hipSuccess && device >= 0 && device < 64 && !told[device].load()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&mrl_cnn_act), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)kCnnLdsLimit) != hipSuccess)
-            (void)hipGetLastError();
-        told[device].store(true);
-    }
+    allow_large_dynamic_lds<&mrl_cnn_act>(args.lds.total);
     const dim3 grid((uint32_t)((total + kCnnTile - 1) / kCnnTile), args.nets == 3u ? 2u : 1u);
     hipLaunchKernelGGL(mrl_cnn_act, grid, dim3(kCnnThreads), args.lds.total, stream, args);
     MRL_HIP(hipGetLastError());

@@ -13,6 +13,8 @@
 
 #include "common.hpp"
 
+#include <atomic>
+
 namespace mrl {
 
 constexpr uint32_t kCnnHidden = 64, kCnnChannels = 32, kCnnActions = 6, kCnnTile = 32, kCnnThreads = 256, kCnnChunk = 64;
@@ -80,5 +82,20 @@ struct CnnActArgs {
 };
 
 void launch_cnn_act(const CnnActArgs &args, hipStream_t stream);
+
+// Before a launch of KERNEL with `bytes` of dynamic LDS: more than the default limit, and the runtime is told once per device
+// and kernel (a refusal shows in the launch that follows).
+template <auto KERNEL>
+inline void allow_large_dynamic_lds(uint32_t bytes)
+{
+    static std::atomic<bool> told[64];
+    int device = 0;
+    if (bytes > 64u * 1024u && hipGetDevice(&device) == hipSuccess && device >= 0 && device < 64 && !told[device].load()) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCnnLdsLimit) !=
+            hipSuccess)
+            (void)hipGetLastError();
+        told[device].store(true);
+    }
+}
 
 }  // namespace mrl

@@ -13,13 +13,13 @@
 //                     accumulators live in the workgroup's own partial vector in global memory: a tile's products start from
 //                     the value the same lane stored after the previous tile (0 for the first), so a sum over the share is ONE
 //                     chain of fused multiply-adds in sample order, and nothing but its owner ever touches the vector.
-//   mrl_mappo_reduce  adds the partial vectors in ascending workgroup order and forms per-block sums of g^2, per net.
-//   mrl_mappo_adam    per net: total norm, clip, Adam with the net's learning rate, and the net's columns of the stats row.
+//   mrl_grad_reduce   adds the partial vectors in ascending workgroup order and forms per-block sums of g^2, per net.
+//   mrl_clip_adam     per net: total norm, clip, Adam with the net's learning rate, and the net's columns of the stats row
+//                     (adam_step.hpp: the tail every update shares; each net is a segment).
 // No float atomics and no wait on another workgroup anywhere: the same inputs give the same bits on every run.
 #include "cnn_update.hpp"
 #include "cnn_forward.hpp"
 
-#include <atomic>
 #include <cmath>
 
 namespace mrl {
@@ -222,6 +222,8 @@ __global__ void __launch_bounds__(kCnnThreads) mrl_mappo_grad(MappoGradArgs a)
             if (at != 0xFFFFFFFFu && net == 0u) {
                 const float lg[kCnnActions] = {outs[tid * 8u], outs[tid * 8u + 1], outs[tid * 8u + 2], outs[tid * 8u + 3], outs[tid * 8u + 4],
                                                outs[tid * 8u + 5]};
+                // categorical_sample's soft-max (random_policy.hpp) with all six log-probs kept: logf as there, so that the new
+                // log-prob of the recorded action is the act's bit for bit
                 float top = lg[0];
 #pragma unroll
                 for (int i = 1; i < (int)kCnnActions; i++) top = lg[i] > top ? lg[i] : top;
@@ -434,21 +436,6 @@ __global__ void __launch_bounds__(kCnnThreads) mrl_mappo_grad(MappoGradArgs a)
     }
 }
 
-// a fixed tree over the workgroup's values; the result is in every thread
-template <int THREADS, typename T>
-__device__ __forceinline__ T block_sum(T v, T *scratch)
-{
-    __syncthreads();
-    scratch[threadIdx.x] = v;
-    __syncthreads();
-#pragma unroll
-    for (int width = THREADS / 2; width > 0; width /= 2) {
-        if ((int)threadIdx.x < width) scratch[threadIdx.x] += scratch[threadIdx.x + width];
-        __syncthreads();
-    }
-    return scratch[0];
-}
-
 // ValueNorm, first launch: the mean and the mean of squares of every row's gathered returns, one workgroup per row
 __global__ void __launch_bounds__(kStatThreads) mrl_mappo_row_sums(const float *__restrict__ returns, const int32_t *__restrict__ indices,
                                                                   uint32_t minibatch_size, uint32_t batch_size, float *__restrict__ row_sums)
@@ -490,74 +477,32 @@ __global__ void mrl_mappo_value_norm(const float *__restrict__ row_sums, uint32_
     state[2] = debias;
 }
 
-struct MappoReduceArgs {
-    const float *partial_grads;
-    float *grad, *grads_row, *sumsq;
-    uint64_t stride;
-    uint32_t groups, blocks, net_params[2], net_at[2];
-};
-
-__global__ void __launch_bounds__(kMappoReduceThreads) mrl_mappo_reduce(MappoReduceArgs a)
-{
-    __shared__ float scratch[kMappoReduceThreads];
-    const uint32_t net = blockIdx.y, p = blockIdx.x * kMappoReduceThreads + threadIdx.x;
-    const float *__restrict__ partial = a.partial_grads + (size_t)net * a.groups * a.stride;
-    float g = 0.0f;
-    if (p < a.net_params[net]) {
-        for (uint32_t w = 0; w < a.groups; w++) g += partial[(size_t)w * a.stride + p];
-        a.grad[(size_t)net * a.stride + p] = g;
-        if (a.grads_row) a.grads_row[a.net_at[net] + p] = g;
-    }
-    const float total = block_sum<(int)kMappoReduceThreads>(g * g, scratch);
-    if (threadIdx.x == 0) a.sumsq[net * a.blocks + blockIdx.x] = total;
-}
-
-struct MappoAdamArgs {
-    const float *grad, *sumsq;
+// The stats row's end, in mrl_clip_adam: the net's columns from its workgroups' four sums and its total norm
+struct MappoStatsRow {
     const double *partial_stats;
-    float *params, *exp_avg, *exp_avg_sq, *stats_row;
-    uint64_t stride;
-    uint32_t blocks, groups, minibatch_size, clip, net_params[2], net_at[2];
-    float max_grad_norm, step_size[2], bias2_sqrt, beta1, beta2, one_minus_beta1, one_minus_beta2, eps;
-};
+    float *row;  // nullptr: no stats
+    uint32_t groups, minibatch_size;
 
-// clip_grad_norm_ and torch.optim.Adam's single-tensor step, per net (mrl_ppo_adam's formulas); block 0 of each net writes the
-// net's columns of the stats row
-__global__ void __launch_bounds__(kMappoReduceThreads) mrl_mappo_adam(MappoAdamArgs a)
-{
-    const uint32_t net = blockIdx.y;
-    float squares = 0.0f;
-    for (uint32_t b = 0; b < a.blocks; b++) squares += a.sumsq[net * a.blocks + b];
-    const float total = sqrtf(squares);
-    const float scale = a.clip ? fminf(a.max_grad_norm / (total + 1e-6f), 1.0f) : 1.0f;
-    const uint32_t p = blockIdx.x * kMappoReduceThreads + threadIdx.x;
-    if (p < a.net_params[net]) {
-        const size_t at = (size_t)a.net_at[net] + p;
-        const float g = a.grad[(size_t)net * a.stride + p] * scale;
-        const float m = a.beta1 * a.exp_avg[at] + a.one_minus_beta1 * g;
-        const float v = a.beta2 * a.exp_avg_sq[at] + a.one_minus_beta2 * (g * g);
-        a.exp_avg[at] = m;
-        a.exp_avg_sq[at] = v;
-        a.params[at] -= a.step_size[net] * (m / (sqrtf(v) / a.bias2_sqrt + a.eps));
-    }
-    if (a.stats_row && blockIdx.x == 0 && threadIdx.x == 0) {
+    __device__ void operator()(uint32_t net, float total_norm) const
+    {
+        if (!row) return;
         double sum[4] = {0.0, 0.0, 0.0, 0.0};
-        for (uint32_t w = 0; w < a.groups; w++)
-            for (int c = 0; c < 4; c++) sum[c] += a.partial_stats[((size_t)net * a.groups + w) * kMappoStats + c];
-        const double count = (double)a.minibatch_size;
+        for (uint32_t w = 0; w < groups; w++)
+            for (int c = 0; c < 4; c++) sum[c] += partial_stats[((size_t)net * groups + w) * kMappoStats + c];
+        const double count = (double)minibatch_size;
         if (net) {
-            a.stats_row[0] = (float)(sum[0] / count);
-            a.stats_row[1] = total;
+            row[0] = (float)(sum[0] / count);
+            row[1] = total_norm;
         } else {
-            a.stats_row[2] = (float)(-(sum[0] / count));
-            a.stats_row[3] = (float)(sum[1] / count);
-            a.stats_row[4] = total;
-            a.stats_row[5] = (float)(sum[2] / count);
-            a.stats_row[6] = (float)(sum[3] / count);
-            a.stats_row[7] = 0.0f;
+            row[2] = (float)(-(sum[0] / count));
+            row[3] = (float)(sum[1] / count);
+            row[4] = total_norm;
+            row[5] = (float)(sum[2] / count);
+            row[6] = (float)(sum[3] / count);
+            row[7] = 0.0f;
         }
     }
-}
+};
 
 }  // namespace
 
@@ -568,7 +513,7 @@ void launch_mappo_update(const mrl_mappo_policy &policy, const mrl_mappo_optimiz
     if (num_minibatches == 0) return;
     const uint32_t W = policy.width, H = policy.height, F = policy.channels;
     const uint32_t actor = (uint32_t)cnn_net_params(W, H, F, kCnnActions), critic = (uint32_t)cnn_net_params(W, H, F, 1);
-    const MappoShape share = mappo_shape(minibatch_size);
+    const SampleShare share = share_samples(minibatch_size, kCnnTile, kMappoMaxGroups);
     const MappoWorkspace ws = mappo_workspace(actor, minibatch_size, num_minibatches);
     const CnnUpdateLds lds = cnn_update_lds(W, H, F);
     const bool norm = cfg.flags & MRL_MAPPO_VALUENORM;
@@ -580,15 +525,7 @@ void launch_mappo_update(const mrl_mappo_policy &policy, const mrl_mappo_optimiz
                            cfg.valuenorm_one_minus_beta, cfg.valuenorm_epsilon, value_norm_state, workspace + ws.row_norm);
         MRL_HIP(hipGetLastError());
     }
-    // more dynamic LDS than the default limit: the runtime is told once per device (a refusal shows in the launch that follows)
-    static std::atomic<bool> told[64];
-    int device = 0;
-    if (lds.total > 64u * 1024u && hipGetDevice(&device) == hipSuccess && device >= 0 && device < 64 && !told[device].load()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&mrl_mappo_grad), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)kCnnLdsLimit) != hipSuccess)
-            (void)hipGetLastError();
-        told[device].store(true);
-    }
+    allow_large_dynamic_lds<&mrl_mappo_grad>(lds.total);
     MappoGradArgs g{};
     g.fwd.params = opt.params_dev;
     g.fwd.W = W;
@@ -614,51 +551,30 @@ void launch_mappo_update(const mrl_mappo_policy &policy, const mrl_mappo_optimiz
     g.value_loss_coef = cfg.value_loss_coef;
     g.huber_delta = cfg.huber_delta;
     g.flags = cfg.flags;
-    MappoReduceArgs rd{};
-    rd.partial_grads = g.partial_grads;
-    rd.grad = workspace + ws.grad;
-    rd.sumsq = workspace + ws.sumsq;
-    rd.stride = ws.stride;
-    rd.groups = share.groups;
-    rd.blocks = (uint32_t)ws.blocks;
-    rd.net_params[0] = actor, rd.net_params[1] = critic;
-    rd.net_at[0] = 0, rd.net_at[1] = actor;
-    MappoAdamArgs ad{};
-    ad.grad = rd.grad;
-    ad.sumsq = rd.sumsq;
-    ad.partial_stats = g.partial_stats;
+    // two clip_grad_norm_ and two Adam steps: the actor's segment, then the critic's
+    AdamStepArgs ad = adam_step_args(cfg.beta1, cfg.beta2, cfg.opti_eps, cfg.flags & MRL_MAPPO_MAX_GRAD_NORM, cfg.max_grad_norm);
+    ad.partial_grads = g.partial_grads;
+    ad.grad = workspace + ws.grad;
+    ad.sumsq = workspace + ws.sumsq;
     ad.params = opt.params_dev;
     ad.exp_avg = opt.exp_avg;
     ad.exp_avg_sq = opt.exp_avg_sq;
     ad.stride = ws.stride;
-    ad.blocks = rd.blocks;
+    ad.segments = 2;
     ad.groups = share.groups;
-    ad.minibatch_size = minibatch_size;
-    ad.clip = cfg.flags & MRL_MAPPO_MAX_GRAD_NORM ? 1u : 0u;
-    ad.net_params[0] = actor, ad.net_params[1] = critic;
-    ad.net_at[0] = 0, ad.net_at[1] = actor;
-    ad.max_grad_norm = cfg.max_grad_norm;
-    ad.beta1 = cfg.beta1;
-    ad.beta2 = cfg.beta2;
-    ad.one_minus_beta1 = (float)(1.0 - (double)cfg.beta1);
-    ad.one_minus_beta2 = (float)(1.0 - (double)cfg.beta2);
-    ad.eps = cfg.opti_eps;
+    ad.blocks = (uint32_t)ws.blocks;
+    ad.num_params[0] = actor, ad.num_params[1] = critic;
+    ad.at[0] = 0, ad.at[1] = actor;
+    MappoStatsRow row{g.partial_stats, nullptr, share.groups, minibatch_size};
     for (uint32_t k = 0; k < num_minibatches; k++) {
         g.indices = indices + (size_t)k * minibatch_size;
         g.row_norm = norm ? workspace + ws.row_norm + 2 * (size_t)k : nullptr;
         hipLaunchKernelGGL(mrl_mappo_grad, dim3(share.groups, 2), dim3(kCnnThreads), lds.total, stream, g);
         MRL_HIP(hipGetLastError());
-        rd.grads_row = grads ? grads + (size_t)k * ((size_t)actor + critic) : nullptr;
-        hipLaunchKernelGGL(mrl_mappo_reduce, dim3(rd.blocks, 2), dim3(kMappoReduceThreads), 0, stream, rd);
-        MRL_HIP(hipGetLastError());
-        // torch's _single_tensor_adam forms these in Python floats: step_size = lr / (1 - beta1^t), sqrt(1 - beta2^t)
-        const double t = (double)opt.step + 1.0 + (double)k, bias1 = 1.0 - std::pow((double)cfg.beta1, t);
-        ad.step_size[0] = (float)((double)cfg.lr / bias1);
-        ad.step_size[1] = (float)((double)cfg.critic_lr / bias1);
-        ad.bias2_sqrt = (float)std::sqrt(1.0 - std::pow((double)cfg.beta2, t));
-        ad.stats_row = stats ? stats + (size_t)k * kMappoStats : nullptr;
-        hipLaunchKernelGGL(mrl_mappo_adam, dim3(rd.blocks, 2), dim3(kMappoReduceThreads), 0, stream, ad);
-        MRL_HIP(hipGetLastError());
+        ad.grads_row = grads ? grads + (size_t)k * ((size_t)actor + critic) : nullptr;
+        adam_set_step(ad, (double)opt.step + 1.0 + (double)k, {cfg.lr, cfg.critic_lr});
+        row.row = stats ? stats + (size_t)k * kMappoStats : nullptr;
+        launch_adam_step(ad, row, stream);
     }
 }
 

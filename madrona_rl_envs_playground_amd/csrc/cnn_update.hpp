@@ -2,32 +2,14 @@
 // include/mrl_envs.h).  The kernels live in cnn_update.hip; capi.hip validates the arguments.
 #pragma once
 
+#include "adam_step.hpp"
 #include "cnn_policy.hpp"
 
 namespace mrl {
 
 constexpr uint32_t kMappoMaxGroups = 256;  // workgroups per net, hence partial gradient vectors per net and row, however large B is
 constexpr uint32_t kMappoStats = 8;        // columns of a stats row
-constexpr uint32_t kMappoReduceThreads = 256;
 constexpr uint32_t kMappoKnownFlags = MRL_MAPPO_VALUENORM | MRL_MAPPO_HUBER_LOSS | MRL_MAPPO_CLIPPED_VALUE_LOSS | MRL_MAPPO_MAX_GRAD_NORM;
-
-// How the B samples of a row are shared out (ppo_shape's rule with this kernel's tile): workgroup g of `groups` owns samples
-// [g * share, min(B, (g + 1) * share)), share a whole number of tiles.  Every workgroup owns at least one sample.
-struct MappoShape {
-    uint32_t groups;
-    uint64_t share;
-};
-
-inline MappoShape mappo_shape(uint32_t minibatch_size)
-{
-    const uint64_t tiles = ((uint64_t)minibatch_size + kCnnTile - 1) / kCnnTile;
-    const uint64_t want = tiles < kMappoMaxGroups ? tiles : kMappoMaxGroups;
-    const uint64_t tiles_each = want ? (tiles + want - 1) / want : 1;
-    MappoShape s;
-    s.groups = (uint32_t)(tiles_each ? (tiles + tiles_each - 1) / tiles_each : 0);
-    s.share = tiles_each * kCnnTile;
-    return s;
-}
 
 // The gradient workgroup's LDS image: mrl_cnn_act's (cnn_lds) with region A at least large enough for what back-propagation
 // keeps beside the forward pass's chunk, h1, h2 and head outputs -- dL/d(head output) (32 x 8), dL/d(pre-activation of fc2) and
@@ -65,9 +47,9 @@ inline MappoWorkspace mappo_workspace(uint64_t actor_params, uint32_t minibatch_
     const auto pad = [](uint64_t n) { return (n + 3) & ~uint64_t(3); };  // every array on a 16-byte boundary
     const uint64_t tiles = ((uint64_t)minibatch_size + kCnnTile - 1) / kCnnTile;
     MappoWorkspace w;
-    w.groups = tiles < kMappoMaxGroups ? tiles : kMappoMaxGroups;  // room for min(tiles, cap); mappo_shape may use fewer
+    w.groups = tiles < kMappoMaxGroups ? tiles : kMappoMaxGroups;  // room for min(tiles, cap); share_samples may use fewer
     w.stride = pad(actor_params);
-    w.blocks = (w.stride + kMappoReduceThreads - 1) / kMappoReduceThreads;
+    w.blocks = (w.stride + kAdamThreads - 1) / kAdamThreads;
     w.row_norm = 0;
     w.row_sums = w.row_norm + pad(2 * (uint64_t)num_minibatches);
     w.partial_grads = w.row_sums + pad(2 * (uint64_t)num_minibatches);

@@ -85,38 +85,12 @@ __global__ void __launch_bounds__(kActThreads) mrl_policy_act(PolicyActArgs a)
     }
     float l[A];
     mlp_forward<D, A>(a.params + mlp_net_params(D, kH, 1), x, l);
-    float top = l[0];
-    int first = 0;  // the first arg-max
-#pragma unroll
-    for (int i = 1; i < A; i++) {
-        if (l[i] > top) {
-            top = l[i];
-            first = i;
-        }
-    }
-    float e[A], sum = 0.0f;
-#pragma unroll
-    for (int i = 0; i < A; i++) {
-        e[i] = expf(l[i] - top);
-        sum += e[i];
-    }
-    int action = first;
-    if (!(a.flags & MRL_POLICY_GREEDY)) {
-        const float u = (float)(policy_hash(a.seed, a.step, w, 0) >> 8) * 0x1p-24f;
-        float cdf = 0.0f;
-        action = 0;
-#pragma unroll
-        for (int i = 0; i < A - 1; i++) {
-            cdf += e[i] / sum;
-            action += u >= cdf ? 1 : 0;
-        }
-    }
-    float chosen = l[0];
-#pragma unroll
-    for (int i = 1; i < A; i++) chosen = action == i ? l[i] : chosen;
+    int action;
+    float logprob;
+    categorical_sample<A>(l, policy_hash(a.seed, a.step, w, 0), a.flags & MRL_POLICY_GREEDY, action, logprob);
     a.action_row[w] = action;
     a.action_tensor[w] = action;
-    a.logprob_row[w] = (chosen - top) - logf(sum);
+    a.logprob_row[w] = logprob;
 }
 
 void launch_policy_act(const mrl_mlp_policy &policy, const PolicyActArgs &args, hipStream_t stream)

@@ -10,8 +10,9 @@
 //                   in registers over the whole share and writes ONE partial gradient vector.  dW2 = sum_s d2(s) h1(s)^T,
 //                   the one 64 x 64 reduction across samples, runs on v_mfma_f32_32x32x2_f32 with k = samples: the
 //                   activations go through LDS as [unit][sample], which is the transpose the instruction wants.
-//   mrl_ppo_reduce  adds the partial vectors in ascending workgroup order and forms per-block sums of g^2.
-//   mrl_ppo_adam    total norm, clip, Adam and the stats row.
+//   mrl_grad_reduce adds the partial vectors in ascending workgroup order and forms per-block sums of g^2.
+//   mrl_clip_adam   total norm, clip, Adam and the stats row (adam_step.hpp: the tail every update shares; the whole
+//                   parameter array is one segment).
 // No float atomics and no wait on another workgroup anywhere: the same inputs give the same bits on every run.
 //
 // Arithmetic: every dot product and every sum that is not on the MFMA is fmaf or a plain add in a fixed order (the
@@ -70,6 +71,7 @@ template <int A>
 __device__ __forceinline__ void actor_head(const PpoGradArgs &a, uint32_t at, const float (&l)[A], float (&d3)[A], PpoHead &s)
 {
     const float count = (float)a.minibatch_size;
+    // categorical_sample's soft-max (random_policy.hpp), all A log-probs kept, the log of the sum in double (below)
     float top = l[0];
 #pragma unroll
     for (int i = 1; i < A; i++) top = fmaxf(top, l[i]);
@@ -320,21 +322,6 @@ __global__ void __launch_bounds__(kT) mrl_ppo_grad(PpoGradArgs a)
     else ppo_grad_net<D, A, true>(a, a.params + mlp_net_params(D, kH, 1), gout + mlp_net_params(D, kH, 1), sout, lds);
 }
 
-// a fixed tree over the workgroup's values; the result is in every thread
-template <int THREADS>
-__device__ __forceinline__ float block_sum(float v, float *scratch)
-{
-    __syncthreads();
-    scratch[threadIdx.x] = v;
-    __syncthreads();
-#pragma unroll
-    for (int width = THREADS / 2; width > 0; width /= 2) {
-        if ((int)threadIdx.x < width) scratch[threadIdx.x] += scratch[threadIdx.x + width];
-        __syncthreads();
-    }
-    return scratch[0];
-}
-
 // line 287's mean and std (torch's unbiased one) of every row's advantages, one workgroup per row
 __global__ void __launch_bounds__(kMeanThreads) mrl_ppo_mean_std(const float *__restrict__ advantages, const int32_t *__restrict__ indices,
                                                                 uint32_t minibatch_size, float *__restrict__ mean_std)
@@ -356,62 +343,31 @@ __global__ void __launch_bounds__(kMeanThreads) mrl_ppo_mean_std(const float *__
     }
 }
 
-__global__ void __launch_bounds__(kPpoReduceThreads) mrl_ppo_reduce(const float *__restrict__ partial_grads, uint32_t groups,
-                                                                    uint32_t num_params, float *__restrict__ grad,
-                                                                    float *__restrict__ grads_row, float *__restrict__ sumsq)
-{
-    __shared__ float scratch[kPpoReduceThreads];
-    const uint32_t p = blockIdx.x * kPpoReduceThreads + threadIdx.x;
-    float g = 0.0f;
-    if (p < num_params) {
-        for (uint32_t w = 0; w < groups; w++) g += partial_grads[(size_t)w * num_params + p];
-        grad[p] = g;
-        if (grads_row) grads_row[p] = g;
-    }
-    const float total = block_sum<(int)kPpoReduceThreads>(g * g, scratch);
-    if (threadIdx.x == 0) sumsq[blockIdx.x] = total;
-}
-
-struct PpoAdamArgs {
-    const float *grad, *sumsq;
+// The stats row's end, in mrl_clip_adam: eight columns from the workgroups' six sums and the total norm
+struct PpoStatsRow {
     const double *partial_stats;
-    float *params, *exp_avg, *exp_avg_sq, *stats_row;
-    uint32_t num_params, num_blocks, groups, minibatch_size;
-    float max_grad_norm, step_size, bias2_sqrt, beta1, beta2, one_minus_beta1, one_minus_beta2, eps, ent_coef, vf_coef;
-};
+    float *row;  // nullptr: no stats
+    uint32_t groups, minibatch_size;
+    float ent_coef, vf_coef;
 
-// clip_grad_norm_ (line 314) and torch.optim.Adam's single-tensor step (line 315); block 0 also writes the stats row
-__global__ void __launch_bounds__(kPpoReduceThreads) mrl_ppo_adam(PpoAdamArgs a)
-{
-    float squares = 0.0f;
-    for (uint32_t b = 0; b < a.num_blocks; b++) squares += a.sumsq[b];
-    const float total = sqrtf(squares);
-    const float scale = a.max_grad_norm > 0.0f ? fminf(a.max_grad_norm / (total + 1e-6f), 1.0f) : 1.0f;
-    const uint32_t p = blockIdx.x * kPpoReduceThreads + threadIdx.x;
-    if (p < a.num_params) {
-        const float g = a.grad[p] * scale;
-        const float m = a.beta1 * a.exp_avg[p] + a.one_minus_beta1 * g;
-        const float v = a.beta2 * a.exp_avg_sq[p] + a.one_minus_beta2 * (g * g);
-        a.exp_avg[p] = m;
-        a.exp_avg_sq[p] = v;
-        a.params[p] -= a.step_size * (m / (sqrtf(v) / a.bias2_sqrt + a.eps));
-    }
-    if (a.stats_row && blockIdx.x == 0 && threadIdx.x == 0) {
+    __device__ void operator()(uint32_t, float total_norm) const
+    {
+        if (!row) return;
         double sum[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        for (uint32_t w = 0; w < a.groups; w++)
-            for (int c = 0; c < 6; c++) sum[c] += a.partial_stats[(size_t)w * kPpoStats + c];
-        const double count = (double)a.minibatch_size;
+        for (uint32_t w = 0; w < groups; w++)
+            for (int c = 0; c < 6; c++) sum[c] += partial_stats[(size_t)w * kPpoStats + c];
+        const double count = (double)minibatch_size;
         const double pg = sum[0] / count, v_loss = 0.5 * (sum[1] / count), entropy = sum[2] / count;
-        a.stats_row[0] = (float)pg;
-        a.stats_row[1] = (float)v_loss;
-        a.stats_row[2] = (float)entropy;
-        a.stats_row[3] = (float)(sum[3] / count);
-        a.stats_row[4] = (float)(sum[4] / count);
-        a.stats_row[5] = (float)(sum[5] / count);
-        a.stats_row[6] = total;
-        a.stats_row[7] = (float)(pg - (double)a.ent_coef * entropy + v_loss * (double)a.vf_coef);
+        row[0] = (float)pg;
+        row[1] = (float)v_loss;
+        row[2] = (float)entropy;
+        row[3] = (float)(sum[3] / count);
+        row[4] = (float)(sum[4] / count);
+        row[5] = (float)(sum[5] / count);
+        row[6] = total_norm;
+        row[7] = (float)(pg - (double)ent_coef * entropy + v_loss * (double)vf_coef);
     }
-}
+};
 
 }  // namespace
 
@@ -421,9 +377,8 @@ void launch_ppo_update(const mrl_mlp_policy &shape, const mrl_ppo_optimizer &opt
 {
     const uint32_t D = shape.obs_dim, A = shape.num_actions;
     const uint32_t P = (uint32_t)(mlp_net_params(D, kH, 1) + mlp_net_params(D, kH, A));
-    const PpoShape share = ppo_shape(minibatch_size);
+    const SampleShare share = share_samples(minibatch_size, kPpoTile, kPpoMaxGroups);
     const PpoWorkspace ws = ppo_workspace(P, minibatch_size, num_minibatches);
-    const uint32_t blocks = (P + kPpoReduceThreads - 1) / kPpoReduceThreads;
     const bool norm = cfg.flags & MRL_PPO_NORM_ADV;
     if (norm && num_minibatches) {
         hipLaunchKernelGGL(mrl_ppo_mean_std, dim3(num_minibatches), dim3(kMeanThreads), 0, stream, batch.advantages, indices,
@@ -447,25 +402,20 @@ void launch_ppo_update(const mrl_mlp_policy &shape, const mrl_ppo_optimizer &opt
     g.ent_coef = cfg.ent_coef;
     g.vf_coef = cfg.vf_coef;
     g.flags = cfg.flags;
-    PpoAdamArgs ad{};
+    // clip_grad_norm_ (line 314) and torch.optim.Adam (line 315) over the whole parameter array
+    AdamStepArgs ad = adam_step_args(cfg.beta1, cfg.beta2, cfg.eps, cfg.max_grad_norm > 0.0f, cfg.max_grad_norm);
+    ad.partial_grads = g.partial_grads;
     ad.grad = workspace + ws.grad;
     ad.sumsq = workspace + ws.sumsq;
-    ad.partial_stats = g.partial_stats;
     ad.params = opt.params_dev;
     ad.exp_avg = opt.exp_avg;
     ad.exp_avg_sq = opt.exp_avg_sq;
-    ad.num_params = P;
-    ad.num_blocks = blocks;
+    ad.stride = P;
+    ad.segments = 1;
     ad.groups = share.groups;
-    ad.minibatch_size = minibatch_size;
-    ad.max_grad_norm = cfg.max_grad_norm;
-    ad.beta1 = cfg.beta1;
-    ad.beta2 = cfg.beta2;
-    ad.one_minus_beta1 = (float)(1.0 - (double)cfg.beta1);
-    ad.one_minus_beta2 = (float)(1.0 - (double)cfg.beta2);
-    ad.eps = cfg.eps;
-    ad.ent_coef = cfg.ent_coef;
-    ad.vf_coef = cfg.vf_coef;
+    ad.blocks = (P + kAdamThreads - 1) / kAdamThreads;
+    ad.num_params[0] = P;
+    PpoStatsRow row{g.partial_stats, nullptr, share.groups, minibatch_size, cfg.ent_coef, cfg.vf_coef};
     const dim3 grid(share.groups, 2);
     for (uint32_t k = 0; k < num_minibatches; k++) {
         g.indices = indices + (size_t)k * minibatch_size;
@@ -477,16 +427,10 @@ void launch_ppo_update(const mrl_mlp_policy &shape, const mrl_ppo_optimizer &opt
         else
             hipLaunchKernelGGL((mrl_ppo_grad<4, 2>), grid, dim3(kT), 0, stream, g);
         MRL_HIP(hipGetLastError());
-        hipLaunchKernelGGL(mrl_ppo_reduce, dim3(blocks), dim3(kPpoReduceThreads), 0, stream, g.partial_grads, share.groups, P,
-                           workspace + ws.grad, grads ? grads + (size_t)k * P : nullptr, workspace + ws.sumsq);
-        MRL_HIP(hipGetLastError());
-        // torch's _single_tensor_adam forms these in Python floats: step_size = lr / (1 - beta1^t), sqrt(1 - beta2^t)
-        const double t = (double)opt.step + 1.0 + (double)k;
-        ad.step_size = (float)((double)cfg.lr / (1.0 - std::pow((double)cfg.beta1, t)));
-        ad.bias2_sqrt = (float)std::sqrt(1.0 - std::pow((double)cfg.beta2, t));
-        ad.stats_row = stats ? stats + (size_t)k * kPpoStats : nullptr;
-        hipLaunchKernelGGL(mrl_ppo_adam, dim3(blocks), dim3(kPpoReduceThreads), 0, stream, ad);
-        MRL_HIP(hipGetLastError());
+        ad.grads_row = grads ? grads + (size_t)k * P : nullptr;
+        adam_set_step(ad, (double)opt.step + 1.0 + (double)k, {cfg.lr, cfg.lr});
+        row.row = stats ? stats + (size_t)k * kPpoStats : nullptr;
+        launch_adam_step(ad, row, stream);
     }
 }
 

@@ -2,6 +2,7 @@
 // The kernels live in ppo_update.hip; capi.hip validates the arguments and calls launch_ppo_update.  DESIGN.md section 13.
 #pragma once
 
+#include "adam_step.hpp"
 #include "policy_rollout.hpp"
 
 namespace mrl {
@@ -9,25 +10,6 @@ namespace mrl {
 constexpr uint32_t kPpoTile = 64;        // samples a gradient workgroup (one wavefront) takes at a time: a lane per sample
 constexpr uint32_t kPpoMaxGroups = 256;  // workgroups per net, hence partial gradient vectors per row, however large B is
 constexpr uint32_t kPpoStats = 8;        // columns of a stats row
-constexpr uint32_t kPpoReduceThreads = 256;
-
-// How the B samples of a row are shared out: workgroup g of `groups` owns samples [g * share, min(B, (g + 1) * share)),
-// share a whole number of tiles.  Every workgroup owns at least one sample.
-struct PpoShape {
-    uint32_t groups;
-    uint64_t share;
-};
-
-inline PpoShape ppo_shape(uint32_t minibatch_size)
-{
-    const uint64_t tiles = ((uint64_t)minibatch_size + kPpoTile - 1) / kPpoTile;
-    const uint64_t want = tiles < kPpoMaxGroups ? tiles : kPpoMaxGroups;
-    const uint64_t tiles_each = want ? (tiles + want - 1) / want : 1;
-    PpoShape s;
-    s.groups = (uint32_t)(tiles_each ? (tiles + tiles_each - 1) / tiles_each : 0);
-    s.share = tiles_each * kPpoTile;
-    return s;
-}
 
 // The caller's scratch, in floats: [mean, std + 1e-8] of every row's advantages; the workgroups' partial gradients
 // (groups, P) and partial stats (groups, 8), doubles; the summed gradient (P); the reduce launch's per-block sums of g^2.
@@ -38,7 +20,7 @@ struct PpoWorkspace {
 inline PpoWorkspace ppo_workspace(uint64_t num_params, uint32_t minibatch_size, uint32_t num_minibatches)
 {
     const auto pad = [](uint64_t n) { return (n + 3) & ~uint64_t(3); };  // every array on a 16-byte boundary
-    // room for min(tiles, cap) workgroups, which never shrinks as B grows; ppo_shape may use fewer (no empty workgroup)
+    // room for min(tiles, cap) workgroups, which never shrinks as B grows; share_samples may use fewer (no empty workgroup)
     const uint64_t tiles = ((uint64_t)minibatch_size + kPpoTile - 1) / kPpoTile;
     const uint64_t groups = tiles < kPpoMaxGroups ? tiles : kPpoMaxGroups;
     PpoWorkspace w;
@@ -47,7 +29,7 @@ inline PpoWorkspace ppo_workspace(uint64_t num_params, uint32_t minibatch_size, 
     w.partial_stats = w.partial_grads + pad(groups * num_params);
     w.grad = w.partial_stats + pad(2 * groups * kPpoStats);
     w.sumsq = w.grad + pad(num_params);
-    w.total = w.sumsq + pad((num_params + kPpoReduceThreads - 1) / kPpoReduceThreads);
+    w.total = w.sumsq + pad((num_params + kAdamThreads - 1) / kAdamThreads);
     return w;
 }
 

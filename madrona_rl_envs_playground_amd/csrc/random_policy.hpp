@@ -50,4 +50,42 @@ __device__ __forceinline__ uint32_t nth_set_bit(uint32_t mask, uint32_t k)
     return pos;
 }
 
+// The categorical head of the act kernels (mrl_policy_act, mrl_cnn_act): the first arg-max of the logits when greedy, else the
+// inverse-CDF draw from the 24 high bits of `hash` over the soft-max in ascending action order; logprob is the action's
+// log-soft-max, (l - top) - logf(sum of expf(l - top)).
+template <int A>
+__device__ __forceinline__ void categorical_sample(const float (&l)[A], uint32_t hash, bool greedy, int &action, float &logprob)
+{
+    float top = l[0];
+    int first = 0;  // the first arg-max
+#pragma unroll
+    for (int i = 1; i < A; i++) {
+        if (l[i] > top) {
+            top = l[i];
+            first = i;
+        }
+    }
+    float e[A], sum = 0.0f;
+#pragma unroll
+    for (int i = 0; i < A; i++) {
+        e[i] = expf(l[i] - top);
+        sum += e[i];
+    }
+    action = first;
+    if (!greedy) {
+        const float u = (float)(hash >> 8) * 0x1p-24f;
+        float cdf = 0.0f;
+        action = 0;
+#pragma unroll
+        for (int i = 0; i < A - 1; i++) {
+            cdf += e[i] / sum;
+            action += u >= cdf ? 1 : 0;
+        }
+    }
+    float chosen = l[0];
+#pragma unroll
+    for (int i = 1; i < A; i++) chosen = action == i ? l[i] : chosen;
+    logprob = (chosen - top) - logf(sum);
+}
+
 }  // namespace mrl

@@ -258,6 +258,7 @@ __global__ void __launch_bounds__(64) mrl_agent_head(HeadArgs a)
     const float *__restrict__ l = a.logits + (size_t)j * kWideMaxActions;
     const int64_t mask_at = (int64_t)w * a.mask.row_stride;
     const int A = (int)a.A;
+    // categorical_sample's rule (random_policy.hpp) over the legal actions only, A at run time, the logits read from memory
     float top = -INFINITY;
     int first = -1, last_legal = -1;  // the first legal arg-max, the last legal action
     for (int i = 0; i < A; i++) {

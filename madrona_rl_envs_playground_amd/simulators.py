@@ -639,7 +639,55 @@ def gae(rollout, gamma, gae_lambda):
     return advantages, returns
 
 
-class PpoOptimizer:
+class _AdamState:
+    """What ``PpoOptimizer`` and ``MappoOptimizer`` share: ``exp_avg`` and ``exp_avg_sq`` over ``policy.params``, ``step``,
+    ``betas``, ``eps`` and the cached scratch.  A subclass adds its learning rates and ``workspace_bytes``."""
+
+    def __init__(self, policy, betas, eps):
+        self.policy = policy
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        self.exp_avg = torch.zeros_like(policy.params)
+        self.exp_avg_sq = torch.zeros_like(policy.params)
+        self.step = 0
+        self._workspace = None
+
+    def workspace(self, minibatch_size, num_minibatches):
+        """A uint8 tensor of at least ``workspace_bytes`` on the parameters' device: the cached one while it is large enough."""
+        need = self.workspace_bytes(minibatch_size, num_minibatches)
+        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != self.policy.params.device:
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.policy.params.device)
+        return self._workspace
+
+
+def _require_tensors(wanted, device):
+    """``wanted``: (name, tensor, dtype, number of elements or None) each; raises unless every one is such a contiguous tensor on
+    ``device``."""
+    for name, tensor, dtype, numel in wanted:
+        if (not isinstance(tensor, torch.Tensor) or tensor.device != device or tensor.dtype != dtype or not tensor.is_contiguous() or
+                (numel is not None and tensor.numel() != numel)):
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor on {device}" + (f" of {numel} elements" if numel else ""))
+
+
+def _run_update(entry, head, indices, middle, optimizer, columns, result, stats, grads):
+    """The common end of ``ppo_update`` and ``mappo_update``: ``entry(*head, indices, rows, width, *middle, workspace, its bytes,
+    stats, grads, gpu, stream)`` with the optimizer's scratch and fresh ``(rows, columns)`` / ``(rows, P)`` outputs where asked
+    for; ``optimizer.step`` grows by the rows; returns ``result(stats, grads)``."""
+    if indices.dim() != 2:
+        raise ValueError("indices must be (rows, minibatch_size)")
+    rows, width = indices.shape
+    p = optimizer.policy.params
+    workspace = optimizer.workspace(width, rows) if width else None
+    out_stats = torch.empty((rows, columns), dtype=torch.float32, device=p.device) if stats else None
+    out_grads = torch.empty((rows, p.numel()), dtype=torch.float32, device=p.device) if grads else None
+    gpu = p.device.index
+    _lib.check(entry(*head, indices.data_ptr(), rows, width, *middle, workspace.data_ptr() if workspace is not None else None,
+                     workspace.numel() if workspace is not None else 0, out_stats.data_ptr() if stats else None,
+                     out_grads.data_ptr() if grads else None, gpu, _stream_ptr(gpu)))
+    optimizer.step += rows
+    return result(out_stats, out_grads)
+
+
+class PpoOptimizer(_AdamState):
     """Adam's state for ``ppo_update`` (``torch.optim.Adam(lr, betas, eps)`` without amsgrad or weight decay, as the reference's
     trainer builds it, scripts/cartpole_train_torch.py:176): ``exp_avg`` and ``exp_avg_sq`` on ``policy.params``' device, the
     number of steps taken (``step``) and the scratch ``mrl_ppo_update`` asks for, kept from call to call.  ``lr`` is an
@@ -648,12 +696,8 @@ class PpoOptimizer:
     def __init__(self, policy, lr=2.5e-4, betas=(0.9, 0.999), eps=1e-5):
         if not isinstance(policy, MlpPolicy):
             raise ValueError("policy must be an MlpPolicy")
-        self.policy = policy
-        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
-        self.exp_avg = torch.zeros_like(policy.params)
-        self.exp_avg_sq = torch.zeros_like(policy.params)
-        self.step = 0
-        self._workspace = None
+        super().__init__(policy, betas, eps)
+        self.lr = float(lr)
 
     def workspace_bytes(self, minibatch_size, num_minibatches):
         """``mrl_ppo_workspace_bytes`` for this policy's shape."""
@@ -662,13 +706,6 @@ class PpoOptimizer:
         _lib.check(_lib.lib().mrl_ppo_workspace_bytes(p.obs_dim, p.hidden, p.num_actions, int(minibatch_size), int(num_minibatches),
                                                       ctypes.byref(out)))
         return int(out.value)
-
-    def workspace(self, minibatch_size, num_minibatches):
-        """A uint8 tensor of at least ``workspace_bytes`` on the parameters' device: the cached one while it is large enough."""
-        need = self.workspace_bytes(minibatch_size, num_minibatches)
-        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != self.policy.params.device:
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.policy.params.device)
-        return self._workspace
 
 
 def minibatch_indices(batch_size, num_minibatches, epochs, generator=None, device="cpu"):
@@ -711,30 +748,15 @@ def ppo_update(policy, optimizer, rollout, advantages, returns, indices, clip_co
               ("rollout.actions", rollout.actions, torch.int32, count), ("rollout.logprobs", rollout.logprobs, f32, count),
               ("rollout.values", rollout.values, f32, count), ("advantages", advantages, f32, count), ("returns", returns, f32, count),
               ("indices", indices, torch.int32, None))
-    for name, tensor, dtype, numel in wanted:
-        if (not isinstance(tensor, torch.Tensor) or tensor.device != device or tensor.dtype != dtype or not tensor.is_contiguous() or
-                (numel is not None and tensor.numel() != numel)):
-            raise ValueError(f"{name} must be a contiguous {dtype} tensor on {device}" + (f" of {numel} elements" if numel else ""))
-    if indices.dim() != 2:
-        raise ValueError("indices must be (rows, minibatch_size)")
-    rows, width = indices.shape
-    workspace = optimizer.workspace(width, rows) if width else None
-    out_stats = torch.empty((rows, len(_lib.PPO_STATS)), dtype=f32, device=device) if stats else None
-    out_grads = torch.empty((rows, p.numel()), dtype=f32, device=device) if grads else None
+    _require_tensors(wanted, device)
     shape = _lib.MlpPolicyDesc(p.data_ptr(), policy.obs_dim, policy.hidden, policy.num_actions, 0, 0)
     opt = _lib.PpoOptimizerDesc(p.data_ptr(), optimizer.exp_avg.data_ptr(), optimizer.exp_avg_sq.data_ptr(), optimizer.step)
     batch = _lib.PpoBatch(rollout.obs.data_ptr(), rollout.actions.data_ptr(), rollout.logprobs.data_ptr(), advantages.data_ptr(),
                           returns.data_ptr(), rollout.values.data_ptr(), count)
     cfg = _lib.PpoConfig(clip_coef, ent_coef, vf_coef, max_grad_norm, optimizer.lr, optimizer.betas[0], optimizer.betas[1],
                          optimizer.eps, (_lib.PPO_NORM_ADV if norm_adv else 0) | (_lib.PPO_CLIP_VLOSS if clip_vloss else 0))
-    gpu = device.index
-    _lib.check(_lib.lib().mrl_ppo_update(ctypes.byref(shape), ctypes.byref(opt), ctypes.byref(batch), indices.data_ptr(), rows, width,
-                                         ctypes.byref(cfg), workspace.data_ptr() if workspace is not None else None,
-                                         workspace.numel() if workspace is not None else 0,
-                                         out_stats.data_ptr() if stats else None, out_grads.data_ptr() if grads else None, gpu,
-                                         _stream_ptr(gpu)))
-    optimizer.step += rows
-    return PpoResult(out_stats, out_grads)
+    return _run_update(_lib.lib().mrl_ppo_update, (ctypes.byref(shape), ctypes.byref(opt), ctypes.byref(batch)), indices,
+                       (ctypes.byref(cfg),), optimizer, len(_lib.PPO_STATS), PpoResult, stats, grads)
 
 
 class ValueNorm:
@@ -767,7 +789,7 @@ class ValueNorm:
         return x.to(torch.float32) * torch.sqrt(var) + mean
 
 
-class MappoOptimizer:
+class MappoOptimizer(_AdamState):
     """The state of MAPPO's two Adam optimizers for a ``CnnPolicy`` (``R_MAPPOPolicy``: ``torch.optim.Adam(lr, eps=opti_eps,
     weight_decay=0)`` for the actor and for the critic): ``exp_avg`` and ``exp_avg_sq`` over the whole flat tensor, the number
     of steps both have taken (``step``) and the scratch ``mrl_mappo_update`` asks for, kept from call to call.  ``lr`` and
@@ -776,12 +798,8 @@ class MappoOptimizer:
     def __init__(self, policy, lr=5e-4, critic_lr=5e-4, betas=(0.9, 0.999), eps=1e-5):
         if not isinstance(policy, CnnPolicy):
             raise ValueError("policy must be a CnnPolicy")
-        self.policy = policy
-        self.lr, self.critic_lr, self.betas, self.eps = float(lr), float(critic_lr), (float(betas[0]), float(betas[1])), float(eps)
-        self.exp_avg = torch.zeros_like(policy.params)
-        self.exp_avg_sq = torch.zeros_like(policy.params)
-        self.step = 0
-        self._workspace = None
+        super().__init__(policy, betas, eps)
+        self.lr, self.critic_lr = float(lr), float(critic_lr)
 
     def workspace_bytes(self, minibatch_size, num_minibatches):
         """``mrl_mappo_workspace_bytes`` for this policy's shape."""
@@ -790,13 +808,6 @@ class MappoOptimizer:
         _lib.check(_lib.lib().mrl_mappo_workspace_bytes(p.width, p.height, p.channels, p.hidden, int(minibatch_size), int(num_minibatches),
                                                         ctypes.byref(out)))
         return int(out.value)
-
-    def workspace(self, minibatch_size, num_minibatches):
-        """A uint8 tensor of at least ``workspace_bytes`` on the parameters' device: the cached one while it is large enough."""
-        need = self.workspace_bytes(minibatch_size, num_minibatches)
-        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != self.policy.params.device:
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.policy.params.device)
-        return self._workspace
 
 
 def mappo_advantages(record, value_norm=None, gamma=0.99, gae_lambda=0.95):
@@ -854,20 +865,11 @@ def mappo_update(policy, optimizer, record, ring, advantages, returns, indices, 
               ("advantages", advantages, f32, count), ("returns", returns, f32, count), ("indices", indices, torch.int32, None)]
     if value_norm is not None:
         wanted.append(("value_norm.state", value_norm.state, f32, 3))
-    for name, tensor, dtype, numel in wanted:
-        if (not isinstance(tensor, torch.Tensor) or tensor.device != device or tensor.dtype != dtype or not tensor.is_contiguous() or
-                (numel is not None and tensor.numel() != numel)):
-            raise ValueError(f"{name} must be a contiguous {dtype} tensor on {device}" + (f" of {numel} elements" if numel else ""))
+    _require_tensors(wanted, device)
     if (not isinstance(ring, torch.Tensor) or ring.device != device or ring.dtype != torch.int8 or not ring.is_contiguous() or
             ring.numel() < count * row_bytes):
         raise ValueError(f"ring must be a contiguous torch.int8 tensor on {device} of at least {count * row_bytes} elements: (T + 1, N, P, "
                          f"H, W, F) for the policy's {policy.width} x {policy.height} kitchen with {policy.channels} channels")
-    if indices.dim() != 2:
-        raise ValueError("indices must be (rows, minibatch_size)")
-    rows, width = indices.shape
-    workspace = optimizer.workspace(width, rows) if width else None
-    out_stats = torch.empty((rows, len(_lib.MAPPO_STATS)), dtype=f32, device=device) if stats else None
-    out_grads = torch.empty((rows, p.numel()), dtype=f32, device=device) if grads else None
     shape = _lib.MappoPolicyDesc(p.data_ptr(), policy.hidden, 0, policy.width, policy.height, policy.channels)
     opt = _lib.MappoOptimizerDesc(p.data_ptr(), optimizer.exp_avg.data_ptr(), optimizer.exp_avg_sq.data_ptr(), optimizer.step)
     batch = _lib.MappoBatch(ring.data_ptr(), record.actions.data_ptr(), record.logprobs.data_ptr(), record.values.data_ptr(),
@@ -879,15 +881,9 @@ def mappo_update(policy, optimizer, record, ring, advantages, returns, indices, 
     cfg = _lib.MappoConfig(clip_param, entropy_coef, value_loss_coef, max_grad_norm, huber_delta, optimizer.lr, optimizer.critic_lr,
                            optimizer.betas[0], optimizer.betas[1], optimizer.eps, beta, 1.0 - beta,
                            value_norm.epsilon if value_norm is not None else 1e-5, flags)
-    gpu = device.index
-    _lib.check(_lib.lib().mrl_mappo_update(ctypes.byref(shape), ctypes.byref(opt), ctypes.byref(batch), indices.data_ptr(), rows, width,
-                                           ctypes.byref(cfg), value_norm.state.data_ptr() if value_norm is not None else None,
-                                           workspace.data_ptr() if workspace is not None else None,
-                                           workspace.numel() if workspace is not None else 0,
-                                           out_stats.data_ptr() if stats else None, out_grads.data_ptr() if grads else None, gpu,
-                                           _stream_ptr(gpu)))
-    optimizer.step += rows
-    return MappoResult(out_stats, out_grads)
+    return _run_update(_lib.lib().mrl_mappo_update, (ctypes.byref(shape), ctypes.byref(opt), ctypes.byref(batch)), indices,
+                       (ctypes.byref(cfg), value_norm.state.data_ptr() if value_norm is not None else None), optimizer,
+                       len(_lib.MAPPO_STATS), MappoResult, stats, grads)
 
 
 def totals_of(totals):

@@ -14,6 +14,8 @@ import torch
 
 import cnn_twin
 from madrona_rl_envs_playground_amd.simulators import CnnActorCritic
+# (the tests reach these through this module)
+from update_twin import clip_adam, clip_adam_torch, distance, f32, make_indices, moments, saturation  # noqa: F401
 
 STATS = ("value_loss", "critic_grad_norm", "policy_loss", "dist_entropy", "actor_grad_norm", "ratio", "clipfrac")
 KINK = 1e-5    # no sample of a case may lie this close to a kink of the loss (in the twin)
@@ -24,10 +26,6 @@ DISTINCT = 257  # distinct samples the sizes beyond the workgroup cap repeat
 # deviation 2, so that one more update moves it by a part in 10^5 and the normalised targets stay where make_batch put them
 RETURN_MEAN, RETURN_STD = 0.5, 2.0
 STATE0 = (np.float32(RETURN_MEAN), np.float32(RETURN_STD ** 2 + RETURN_MEAN ** 2), np.float32(1.0))
-
-
-def f32(x):
-    return float(np.float32(x))
 
 
 class Config(collections.namedtuple("Config", "clip_param entropy_coef value_loss_coef max_grad_norm huber_delta lr critic_lr beta1 beta2 "
@@ -228,23 +226,6 @@ def row(params, layout, batch, mb_inds, cfg, state=(0.0, 0.0, 0.0), dtype=torch.
             "kink": float(np.min(kinks)), "branches": branches, "pre": pre}
 
 
-AdamCfg = collections.namedtuple("AdamCfg", "max_grad_norm lr beta1 beta2 eps")
-
-
-def clip_adam(params, exp_avg, exp_avg_sq, grad, step, max_grad_norm, lr, cfg):
-    """clip_grad_norm_ and one torch.optim.Adam step (single tensor, no amsgrad, no weight decay) over ONE net's slice in float64
-    numpy; ``step``: steps taken before; ``max_grad_norm`` None: no clipping.  Returns (total_norm, params, exp_avg, exp_avg_sq)."""
-    p, m, v, g = (np.asarray(a, np.float64) for a in (params, exp_avg, exp_avg_sq, grad))
-    total = float(np.sqrt(np.sum(g * g)))
-    if max_grad_norm is not None:
-        g = g * min(1.0, max_grad_norm / (total + 1e-6))
-    t = step + 1
-    m = cfg.beta1 * m + (1 - cfg.beta1) * g
-    v = cfg.beta2 * v + (1 - cfg.beta2) * g * g
-    p = p - (lr / (1 - cfg.beta1 ** t)) * m / (np.sqrt(v) / np.sqrt(1 - cfg.beta2 ** t) + cfg.eps)
-    return total, p, m, v
-
-
 def step_both(layout, params, exp_avg, exp_avg_sq, grad, step, cfg):
     """both nets' clip and Adam on the flat arrays: (actor_norm, critic_norm, params, exp_avg, exp_avg_sq)"""
     na = actor_size(layout)
@@ -252,28 +233,6 @@ def step_both(layout, params, exp_avg, exp_avg_sq, grad, step, cfg):
     out = [clip_adam(params[s], exp_avg[s], exp_avg_sq[s], grad[s], step, limit, lr, cfg)
            for s, lr in ((slice(0, na), cfg.lr), (slice(na, None), cfg.critic_lr))]
     return (out[0][0], out[1][0]) + tuple(np.concatenate([out[0][i], out[1][i]]) for i in (1, 2, 3))
-
-
-def clip_adam_torch(params, exp_avg, exp_avg_sq, grad, step, max_grad_norm, lr, cfg, dtype=torch.float64):
-    """The same through ``clip_grad_norm_`` and ``torch.optim.Adam`` themselves on one flat CPU tensor of ``dtype``"""
-    p = torch.nn.Parameter(torch.tensor(np.asarray(params, np.float64)).to(dtype))
-    p.grad = torch.tensor(np.asarray(grad, np.float64)).to(dtype)
-    total = float(torch.linalg.vector_norm(p.grad).item())
-    if max_grad_norm is not None:
-        total = float(torch.nn.utils.clip_grad_norm_([p], max_grad_norm).item())
-    opt = torch.optim.Adam([p], lr=lr, betas=(cfg.beta1, cfg.beta2), eps=cfg.eps)
-    opt.state[p] = {"step": torch.tensor(float(step)), "exp_avg": torch.tensor(np.asarray(exp_avg, np.float64)).to(dtype),
-                    "exp_avg_sq": torch.tensor(np.asarray(exp_avg_sq, np.float64)).to(dtype)}
-    opt.step()
-    state = opt.state[p]
-    return total, p.detach().double().numpy(), state["exp_avg"].double().numpy(), state["exp_avg_sq"].double().numpy()
-
-
-def moments(num_params, seed):
-    """Adam moments of a run in progress (float32): exp_avg of the size of a gradient, exp_avg_sq of its square."""
-    rng = np.random.default_rng(seed)
-    return (rng.normal(scale=1e-2, size=num_params).astype(np.float32),
-            (rng.normal(scale=1e-2, size=num_params) ** 2 + 1e-8).astype(np.float32))
 
 
 @functools.lru_cache(maxsize=None)
@@ -308,14 +267,6 @@ def make_batch(params, ring, seed, delta, valuenorm):
     return Batch(ring, actions, logprobs, values, returns, advantages)
 
 
-def make_indices(rows, width, size, seed):
-    """(rows, width) int32 sample numbers below ``size``, each row without repeats -- or, wider than the batch, drawn with them"""
-    rng = np.random.default_rng(seed + 1)
-    if width > size:
-        return rng.integers(0, size, size=(rows, width)).astype(np.int32)
-    return np.stack([rng.permutation(size)[:width] for _ in range(rows)]).astype(np.int32)
-
-
 def seed_of(case):
     layout, worlds, weights, inputs, width, variant = case
     derived = (cnn_twin.case_seed(layout, worlds, weights, inputs) + 7 * width + 13 * sorted(VARIANTS).index(variant))
@@ -344,10 +295,6 @@ def fixed_case(case, rows=1):
     return {"layout": layout, "worlds": worlds, "params": params, "batch": batch, "indices": indices, "cfg": cfg,
             "twin": row(params, layout, batch, indices[0], cfg, STATE0),
             "f32": row(params, layout, batch, indices[0], cfg, STATE0, dtype=torch.float32)}
-
-
-def distance(a, b):
-    return float(np.max(np.abs(np.asarray(a, np.float64) - np.asarray(b, np.float64))))
 
 
 def row_margins(twin_row, f32_row):
@@ -388,24 +335,6 @@ def stat_margins(weights, cases=None):
         for name in STATS:
             d[name] = max(d[name], own[name])
     return d
-
-
-def saturation(workspace_bytes):
-    """(tile, cap * tile): the gradient kernel's tile, read off ``workspace_bytes(B)`` as the largest B that still needs one
-    partial vector, and the largest B at which every workgroup still takes a single tile"""
-    base, tile = workspace_bytes(1), 1
-    while workspace_bytes(tile + 1) == base:
-        tile += 1
-        assert tile < 1 << 16
-    top = workspace_bytes((1 << 31) - 1)
-    low, high = 1, (1 << 31) - 1
-    while low < high:
-        mid = (low + high) // 2
-        if workspace_bytes(mid) == top:
-            high = mid
-        else:
-            low = mid + 1
-    return tile, low - 1 + tile
 
 
 def large_cases(tile, saturation_size):

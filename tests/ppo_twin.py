@@ -12,7 +12,10 @@ import numpy as np
 import torch
 
 import policy_twin
+import update_twin
 from madrona_rl_envs_playground_amd.simulators import MlpAgent
+# (the tests reach these through this module)
+from update_twin import distance, f32, make_indices, moments, tile_size  # noqa: F401
 
 STATS = ("pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac", "total_norm", "loss")
 KINK = 1e-5       # no sample of a fixed case may lie this close to a kink of the loss (in the twin)
@@ -41,10 +44,6 @@ SEEDS = {
     (6, 3, 1.0, 16389, "default"): 421024,
     (6, 3, 1.0, 32837, "default"): 236160,
 }
-
-
-def f32(x):
-    return float(np.float32(x))
 
 
 class Config(collections.namedtuple("Config", "clip_coef ent_coef vf_coef max_grad_norm lr beta1 beta2 eps norm_adv clip_vloss")):
@@ -156,40 +155,13 @@ def _num_actions(params, obs_dim):
 
 
 def clip_adam(params, exp_avg, exp_avg_sq, grad, step, cfg):
-    """clip_grad_norm_ (line 314) and one torch.optim.Adam step (line 315; single tensor, no amsgrad, no weight decay) in
-    float64 numpy; ``step`` is the number of steps taken before.  Returns (total_norm, params, exp_avg, exp_avg_sq)."""
-    p, m, v, g = (np.asarray(a, np.float64) for a in (params, exp_avg, exp_avg_sq, grad))
-    total = float(np.sqrt(np.sum(g * g)))
-    if cfg.max_grad_norm > 0:
-        g = g * min(1.0, cfg.max_grad_norm / (total + 1e-6))
-    t = step + 1
-    m = cfg.beta1 * m + (1 - cfg.beta1) * g
-    v = cfg.beta2 * v + (1 - cfg.beta2) * g * g
-    p = p - (cfg.lr / (1 - cfg.beta1 ** t)) * m / (np.sqrt(v) / np.sqrt(1 - cfg.beta2 ** t) + cfg.eps)
-    return total, p, m, v
+    """``update_twin.clip_adam`` (lines 314 and 315) as the trainer's flags put it: no clipping at ``max_grad_norm`` <= 0"""
+    return update_twin.clip_adam(params, exp_avg, exp_avg_sq, grad, step, cfg.max_grad_norm if cfg.max_grad_norm > 0 else None, cfg.lr, cfg)
 
 
 def clip_adam_torch(params, exp_avg, exp_avg_sq, grad, step, cfg, dtype):
-    """The same through ``clip_grad_norm_`` and ``torch.optim.Adam`` themselves on one flat CPU tensor of ``dtype``
-    (copies: the caller's arrays stay as they are)."""
-    p = torch.nn.Parameter(torch.tensor(np.asarray(params, np.float64)).to(dtype))
-    p.grad = torch.tensor(np.asarray(grad, np.float64)).to(dtype)
-    total = float(torch.linalg.vector_norm(p.grad).item())
-    if cfg.max_grad_norm > 0:
-        total = float(torch.nn.utils.clip_grad_norm_([p], cfg.max_grad_norm).item())
-    opt = torch.optim.Adam([p], lr=cfg.lr, betas=(cfg.beta1, cfg.beta2), eps=cfg.eps)
-    opt.state[p] = {"step": torch.tensor(float(step)), "exp_avg": torch.tensor(np.asarray(exp_avg, np.float64)).to(dtype),
-                    "exp_avg_sq": torch.tensor(np.asarray(exp_avg_sq, np.float64)).to(dtype)}
-    opt.step()
-    state = opt.state[p]
-    return total, p.detach().double().numpy(), state["exp_avg"].double().numpy(), state["exp_avg_sq"].double().numpy()
-
-
-def moments(num_params, seed):
-    """Adam moments of a run in progress (float32): exp_avg of the size of a gradient, exp_avg_sq of its square."""
-    rng = np.random.default_rng(seed)
-    return (rng.normal(scale=1e-2, size=num_params).astype(np.float32),
-            (rng.normal(scale=1e-2, size=num_params) ** 2 + 1e-8).astype(np.float32))
+    return update_twin.clip_adam_torch(params, exp_avg, exp_avg_sq, grad, step, cfg.max_grad_norm if cfg.max_grad_norm > 0 else None,
+                                       cfg.lr, cfg, dtype)
 
 
 def make_batch(params, obs_dim, num_actions, size, seed):
@@ -205,14 +177,6 @@ def make_batch(params, obs_dim, num_actions, size, seed):
     returns = (values + rng.normal(size=size)).astype(np.float32)
     advantages = rng.normal(scale=3.0, size=size).astype(np.float32)
     return Batch(obs, actions, logprobs, advantages, returns, values)
-
-
-def make_indices(rows, width, size, seed):
-    """(rows, width) int32 sample numbers below ``size``, each row without repeats -- or, wider than the batch, drawn with them"""
-    rng = np.random.default_rng(seed + 1)
-    if width > size:
-        return rng.integers(0, size, size=(rows, width)).astype(np.int32)
-    return np.stack([rng.permutation(size)[:width] for _ in range(rows)]).astype(np.int32)
 
 
 @functools.lru_cache(maxsize=None)
@@ -239,10 +203,6 @@ def fixed_case(case, rows=1, draw=0):
     cfg = VARIANTS[variant]
     return {"params": params, "batch": batch, "indices": indices, "cfg": cfg, "twin": row(params, batch, indices[0], cfg),
             "f32": row(params, batch, indices[0], cfg, torch.float32)}
-
-
-def distance(a, b):
-    return float(np.max(np.abs(np.asarray(a, np.float64) - np.asarray(b, np.float64))))
 
 
 def row_margins(twin_row, f32_row):
@@ -282,17 +242,8 @@ def stat_margins(case):
 
 
 def saturation(workspace_bytes):
-    """The cap on partial vectors times the tile: the largest B at which every workgroup still takes a single tile.
-    ``workspace_bytes(B)`` reaches its final value where the last of those tiles begins."""
-    top = workspace_bytes((1 << 31) - 1)
-    low, high = 1, (1 << 31) - 1
-    while low < high:
-        mid = (low + high) // 2
-        if workspace_bytes(mid) == top:
-            high = mid
-        else:
-            low = mid + 1
-    return low - 1 + tile_size(workspace_bytes)
+    """The cap on partial vectors times the tile: the largest B at which every workgroup still takes a single tile."""
+    return update_twin.saturation(workspace_bytes)[1]
 
 
 def large_sizes(tile_size, saturation_size):
@@ -319,13 +270,3 @@ def gpu_cases(tile_size):
             if variant != "default":
                 cases.append((d, a, 1.0, 257, variant))
     return cases
-
-
-def tile_size(workspace_bytes):
-    """The gradient kernel's tile, read off ``workspace_bytes(B)``: the largest B that still needs one partial vector."""
-    base = workspace_bytes(1)
-    width = 1
-    while workspace_bytes(width + 1) == base:
-        width += 1
-        assert width < 1 << 16
-    return width
