@@ -55,7 +55,6 @@ static_assert(kBlock * kWorlds == (int)kGroupWorlds && kBlock % 64 == 0 && kBloc
 #define MRL_ACROBOT_WAVES 1  // second argument of __launch_bounds__: the least waves per SIMD the compiler must make room for
 #endif
 constexpr int kWavesPerSimd = MRL_ACROBOT_WAVES;
-static_assert(kGroupWorlds <= 0xfffu, "a workgroup's finished count must fit the 12 bits of a status word (episode_scan.hpp)");
 
 #ifdef MRL_ACROBOT_PLAIN
 constexpr bool kPlain = true;
@@ -338,19 +337,12 @@ __global__ void __launch_bounds__(kBlock, kWavesPerSimd) mrl_acrobot_step(uint32
                 reward[i] = -1.f;  // sim.cpp:186
                 done[i] = over ? 1 : 0;
             }
-            const unsigned long long votes = __ballot(over);
-            const uint32_t word = (i - (threadIdx.x & 63u)) >> 6;  // wave-uniform
-            if ((threadIdx.x & 63u) == 0 && i < last) finished_mask[word] = votes;
-            finished += (uint32_t)__popcll(votes);
+            finished += mrl::note_finished(over, i, i < last, finished_mask);
         }
     }
-    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = finished;
+    mrl::post_wave_count(finished, s_wave);
     __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t total = 0;
-        for (uint32_t w = 0; w < kBlock / 64; w++) total += s_wave[w];
-        block_counts[blockIdx.x] = total;
-    }
+    mrl::store_block_count(s_wave, block_counts);
 }
 
 // How many of workgroup j's worlds finish in this step, worked out by ONE wave of another workgroup from j's inputs in HBM
@@ -377,15 +369,13 @@ __device__ __forceinline__ uint32_t recount_chunk(uint32_t n, const int32_t *act
 // The whole step in one launch (mrl_step / mrl_step_with_actions / mrl_rollout_random on one GPU): workgroup b owns worlds
 // [1024 b, 1024 b + 1024), four per thread, in registers from the load to the store.
 //
-// Order of events in a workgroup: loads (state, length, action or its draw) -> the WHOLE transition of its 1024 worlds,
-// because here the done flag is the end of the arithmetic (the height of the new pose, the new length) -> ballots, the
-// workgroup's count and every finished world's rank -> the count is PUBLISHED and the publishing wave waits for that store
-// to be acknowledged (s_waitcnt vmcnt(0), as in cartpole.hip) -> __syncthreads -> one wave looks back at the lower workgroups' counts (two levels, mrl::grouped_prefix; a
-// count that does not appear is recounted from that workgroup's inputs) while the other waves already store what needs
-// no prefix: state and length of the worlds that go on, reward, done -> the finished worlds follow as their next episodes,
-// length 0.  So a workgroup overwrites its state and length only after its count is globally visible, and whoever
-// recounts it before that reads the step's inputs.  (The drawn actions of a
-// rollout go out before the count: the recount draws them again from the hash and never reads ACTION.)
+// Order of events in a workgroup (the protocol and its shared helpers: DESIGN.md 4.6): loads (state, length, action or its
+// draw) -> the WHOLE transition of its 1024 worlds, because here the done flag is the end of the arithmetic (the height of
+// the new pose, the new length) -> votes, tally -> the count is PUBLISHED and the publishing wave waits for that store to
+// be acknowledged (s_waitcnt vmcnt(0), as in cartpole.hip) -> __syncthreads -> the first wave looks back while the other
+// waves already store what needs no prefix: state and length of the worlds that go on, reward, done -> the finished
+// worlds follow as their next episodes, length 0.  (The drawn actions of a rollout go out before the count: the recount
+// draws them again from the hash and never reads ACTION.)
 // kStats (mrl_enable_episode_stats): the lane also keeps its four worlds' episode returns and step counts.  They are loaded
 // AFTER the transition, behind the first barrier -- its registers are what bounds this kernel, and the values are not needed
 // before the stores, two barriers later -- and thread 0 adds the workgroup's finished episodes to TOTALS block b behind the
@@ -404,7 +394,7 @@ __global__ void __launch_bounds__(kBlock, kWavesPerSimd) mrl_acrobot_step_fused(
                                                                  const mrl::StatsArg<kStats> stats)
 {
     __shared__ uint32_t s_wave[kWorlds][kBlock / 64];
-    __shared__ uint32_t s_prefix, s_lower, s_all;
+    __shared__ mrl::EpisodeNumbers s_numbers;
     const uint32_t b = blockIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t first = b * kGroupWorlds, last = min(n, first + kGroupWorlds);
     const bool last_block = b == gridDim.x - 1, sampled = action_out != nullptr;
@@ -427,9 +417,7 @@ __global__ void __launch_bounds__(kBlock, kWavesPerSimd) mrl_acrobot_step_fused(
 #pragma unroll
     for (int u = 0; u < kWorlds; u++) {
         over[u] = over[u] && first + u * kBlock + threadIdx.x < last;
-        const unsigned long long votes = __ballot(over[u]);
-        rank[u] = (uint32_t)__popcll(votes & ((1ull << lane) - 1ull));
-        if (lane == 0) s_wave[u][wave] = (uint32_t)__popcll(votes);
+        rank[u] = mrl::cast_vote(over[u], s_wave[u]);
     }
     __syncthreads();
     using Stats = mrl::StatsWorlds<1>;
@@ -442,16 +430,7 @@ __global__ void __launch_bounds__(kBlock, kWavesPerSimd) mrl_acrobot_step_fused(
             running[u] = Stats::load(stats, w < last ? w : first);
         }
     }
-    uint32_t block_total = 0;
-#pragma unroll
-    for (int u = 0; u < kWorlds; u++)
-        for (uint32_t v = 0; v < kBlock / 64; v++) {
-            const uint32_t c = s_wave[u][v];
-            block_total += c;
-#pragma unroll
-            for (int u2 = 0; u2 < kWorlds; u2++)  // everything in front of (round u2, wave `wave`) in world order
-                rank[u2] += (u < u2 || (u == u2 && v < wave)) ? c : 0u;
-        }
+    const uint32_t block_total = mrl::tally_votes<kWorlds, kBlock>(s_wave, rank);
     if (threadIdx.x == 0) mrl::publish_count(status, b, epoch, block_total);
     // The count is globally visible before any wave of this workgroup changes a world: the publishing wave waits for ITS
     // store to be acknowledged in front of the barrier (the barrier alone makes no wave wait for its stores; only the drawn
@@ -459,21 +438,10 @@ __global__ void __launch_bounds__(kBlock, kWavesPerSimd) mrl_acrobot_step_fused(
     if (wave == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     const bool needs_prefix = block_total != 0 || last_block;
-    if (threadIdx.x < 64) {  // (a workgroup that closes a group of 256 looks back whatever its count)
-        const uint32_t before = mrl::grouped_prefix(status, group_total, b, epoch, block_total, needs_prefix, heal, [&](uint32_t j) {
+    if (threadIdx.x < 64)  // (a workgroup that closes a group of 256 looks back whatever its count)
+        mrl::fused_lookback(s_numbers, status, group_total, epoch, block_total, needs_prefix, heal, fx, [&](uint32_t j) {
             return recount_chunk(n, action, state, length, j, sampled, sample_seed, sample_step);
         });
-        uint32_t lower_ranks = 0, all_counts = before + block_total;
-        if (fx.mail.num_ranks && needs_prefix) {  // the last workgroup tells every rank the shard's total; the ranks below come first in the numbering
-            lower_ranks = mrl::fused_exchange(fx, last_block, before + block_total, fx.mail.rank);
-            if (last_block) all_counts = mrl::fused_exchange(fx, false, 0u, fx.mail.num_ranks);
-        }
-        if (threadIdx.x == 0 && needs_prefix) {
-            s_prefix = before;
-            s_lower = lower_ranks;
-            s_all = all_counts;
-        }
-    }
     // what does not need the prefix goes out while the first wave is still looking back (the other three are here right
     // after the barrier; the first wave's loads come before its stores: behind them they would sit out their acknowledgement)
 #pragma unroll
@@ -500,7 +468,7 @@ __global__ void __launch_bounds__(kBlock, kWavesPerSimd) mrl_acrobot_step_fused(
     if constexpr (kStats) {
         if (threadIdx.x == 0 && block_total != 0) Stats::add_totals(stats, s_sums, kBlock / 64, b, block_total);
     }
-    const uint32_t own_before = s_prefix, before = own_before + s_lower;
+    const uint32_t own_before = s_numbers.own_before, before = own_before + s_numbers.lower_ranks;
 #pragma unroll
     for (int u = 0; u < kWorlds; u++) {
         const uint32_t w = first + u * kBlock + threadIdx.x;
@@ -509,10 +477,7 @@ __global__ void __launch_bounds__(kBlock, kWavesPerSimd) mrl_acrobot_step_fused(
             length[w] = 0;
         }
     }
-    if (last_block && threadIdx.x == 0) {
-        *reset_count = own_before + block_total;
-        *next_counter = base + s_all;
-    }
+    if (last_block && threadIdx.x == 0) mrl::close_step(own_before, block_total, base, s_numbers.all_counts, reset_count, next_counter);
 }
 
 struct AcrobotSim final : mrl::EpisodeSim {
@@ -522,15 +487,9 @@ struct AcrobotSim final : mrl::EpisodeSim {
 
     void launch_fused(const int32_t *actions, const Drawn &drawn, const mrl::FusedExchange &fx, const Counters &c, hipStream_t stream) override
     {
-        if (stats_in_step())
-            hipLaunchKernelGGL(mrl_acrobot_step_fused<true>, dim3(fused_grid), dim3(kBlock), 0, stream, num_worlds, actions ? actions : action,
-                               state, length, reward, done, status, group_total, epoch, c.base, c.next, reset_count, drawn.action_out,
-                               drawn.seed, drawn.step, heal, c.device, fx, stats->lane());
-        else
-            hipLaunchKernelGGL(mrl_acrobot_step_fused<false>, dim3(fused_grid), dim3(kBlock), 0, stream, num_worlds, actions ? actions : action,
-                               state, length, reward, done, status, group_total, epoch, c.base, c.next, reset_count, drawn.action_out,
-                               drawn.seed, drawn.step, heal, c.device, fx, mrl::NoStats{});
-        stats_taken = stats_in_step();
+        single_launch(mrl_acrobot_step_fused<true>, mrl_acrobot_step_fused<false>, kBlock, stream, num_worlds, actions ? actions : action, state,
+                      length, reward, done, status, group_total, epoch, c.base, c.next, reset_count, drawn.action_out, drawn.seed, drawn.step, heal,
+                      c.device, fx)();
     }
     void launch_step(const int32_t *actions, int32_t *action_out, uint64_t seed, uint32_t sample_step, hipStream_t stream) override
     {
@@ -589,16 +548,7 @@ struct AcrobotSim final : mrl::EpisodeSim {
 
 mrl_sim *mrl::create_acrobot(int gpu_id, uint32_t num_worlds)
 {
-    if (num_worlds == 0) {
-        set_error("acrobot: num_worlds must be > 0");
-        throw HipError{MRL_ERR_INVALID};
-    }
-    bind_device(gpu_id);
-    auto *sim = new AcrobotSim();
-    try {
-        sim->game = MRL_GAME_ACROBOT;
-        sim->device = gpu_id;
-        sim->num_worlds = num_worlds;
+    return create_episode_sim<AcrobotSim>("acrobot", MRL_GAME_ACROBOT, gpu_id, num_worlds, [&](AcrobotSim *sim) {
         sim->size_scan_grid(kBlock);
         sim->action = sim->arena.alloc<int32_t>(num_worlds);
         sim->done = sim->arena.alloc<int32_t>(num_worlds);
@@ -614,10 +564,5 @@ mrl_sim *mrl::create_acrobot(int gpu_id, uint32_t num_worlds)
         mrl::fill_ids(sim->world_id, nullptr, 1, num_worlds);
         sim->reseed_shard(0, num_worlds, 0);  // Sim::Sim (sim.cpp:216-236): world w starts as episode w
         sim->inject_scan_timeout();
-        MRL_HIP(hipDeviceSynchronize());
-    } catch (...) {
-        delete sim;
-        throw;
-    }
-    return sim;
+    });
 }

@@ -158,26 +158,19 @@ __global__ void __launch_bounds__(kBlock) mrl_balance_step(uint32_t n, uint32_t 
         reward[(size_t)n + w] = rew;
         done[w] = over ? 1 : 0;
         }
-        const unsigned long long votes = __ballot(over);
-        if ((threadIdx.x & 63u) == 0 && w < last) finished_mask[w >> 6] = votes;
-        finished += (uint32_t)__popcll(votes);
+        finished += mrl::note_finished(over, w, w < last, finished_mask);
     }
-    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = finished;
+    mrl::post_wave_count(finished, s_wave);
     __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t total = 0;
-        for (uint32_t w = 0; w < kBlock / 64; w++) total += s_wave[w];
-        block_counts[blockIdx.x] = total;
-    }
+    mrl::store_block_count(s_wave, block_counts);
 }
 
 // The whole step in ONE launch (mrl_step on one GPU).  A third of the worlds finish in every step (episodes last at most
 // three), so the two-launch pair writes a third of the rows twice over -- stepped rows it then skips, fresh rows as 28-byte
 // pieces scattered by the re-seeding launch -- and that launch costs 15 us of the 36 at 1 M worlds.  Here workgroup b owns
 // worlds [1024 b, 1024 b + 1024), four per thread in registers; a finished world's rows are replaced by the fresh episode's
-// BEFORE they are stored, so every row is written exactly once, in the step's own coalesced stream.  Episode indices come
-// from the single-launch look-back of episode_scan.hpp (a count that does not appear is recounted from that workgroup's rows
-// and actions; rows are stored only behind the __syncthreads that makes the workgroup's own count globally visible).
+// BEFORE they are stored, so every row is written exactly once, in the step's own coalesced stream.  Episode indices: the
+// protocol of DESIGN.md 4.6 (rows are stored only behind the __syncthreads that makes the workgroup's own count globally visible).
 constexpr int kFusedWorlds = 4;  // worlds per thread
 __device__ __forceinline__ uint32_t recount_chunk(uint32_t n, const int32_t *action, const int32_t *obs, uint32_t j, bool sampled, uint64_t seed,
                                                    uint32_t step)
@@ -212,7 +205,7 @@ __global__ void __launch_bounds__(kBlock) mrl_balance_step_fused(uint32_t n, con
                                                                  const mrl::StatsArg<kStats> stats)
 {
     __shared__ uint32_t s_wave[kFusedWorlds][kBlock / 64];
-    __shared__ uint32_t s_prefix, s_lower, s_all;
+    __shared__ mrl::EpisodeNumbers s_numbers;
     const uint32_t b = blockIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t first = b * (kFusedWorlds * kBlock), last = min(n, first + kFusedWorlds * kBlock);
     const bool last_block = b == gridDim.x - 1, sampled = action_out != nullptr;
@@ -239,42 +232,20 @@ __global__ void __launch_bounds__(kBlock) mrl_balance_step_fused(uint32_t n, con
             action_out[(size_t)n + w] = a1;
         }
         over[u] = move_world(r0[u], r1[u], a0, a1, rew[u]) && w < last;
-        const unsigned long long votes = __ballot(over[u]);
-        rank[u] = (uint32_t)__popcll(votes & ((1ull << lane) - 1ull));
-        if (lane == 0) s_wave[u][wave] = (uint32_t)__popcll(votes);
+        rank[u] = mrl::cast_vote(over[u], s_wave[u]);
     }
     __syncthreads();
-    uint32_t block_total = 0;
-#pragma unroll
-    for (int u = 0; u < kFusedWorlds; u++)
-        for (uint32_t v = 0; v < kBlock / 64; v++) {
-            const uint32_t c = s_wave[u][v];
-            block_total += c;
-#pragma unroll
-            for (int u2 = 0; u2 < kFusedWorlds; u2++)  // everything in front of (round u2, wave `wave`) in world order
-                rank[u2] += (u < u2 || (u == u2 && v < wave)) ? c : 0u;
-        }
+    const uint32_t block_total = mrl::tally_votes<kFusedWorlds, kBlock>(s_wave, rank);
     if (threadIdx.x == 0) mrl::publish_count(status, b, epoch, block_total);
     __syncthreads();  // the count is globally visible (vmcnt(0) in front of the barrier) before any row of this workgroup changes
     const bool needs_prefix = block_total != 0 || last_block;
-    if (threadIdx.x < 64) {  // (two levels: mrl::grouped_prefix, episode_scan.hpp; a workgroup that closes a group looks back whatever its count)
-        const uint32_t before = mrl::grouped_prefix(status, group_total, b, epoch, block_total, needs_prefix, heal, [&](uint32_t j) {
+    if (threadIdx.x < 64)  // (a workgroup that closes a group of 256 looks back whatever its count)
+        mrl::fused_lookback(s_numbers, status, group_total, epoch, block_total, needs_prefix, heal, fx, [&](uint32_t j) {
             return recount_chunk(n, action, obs, j, sampled, sample_seed, sample_step);
         });
-        uint32_t lower_ranks = 0, all_counts = before + block_total;
-        if (fx.mail.num_ranks && needs_prefix) {  // the last workgroup tells every rank the shard's total; the ranks below come first in the numbering
-            lower_ranks = mrl::fused_exchange(fx, last_block, before + block_total, fx.mail.rank);
-            if (last_block) all_counts = mrl::fused_exchange(fx, false, 0u, fx.mail.num_ranks);
-        }
-        if (threadIdx.x == 0 && needs_prefix) {
-            s_prefix = before;
-            s_lower = lower_ranks;
-            s_all = all_counts;
-        }
-    }
     mrl::lds_barrier();
-    const uint32_t own_before = needs_prefix ? s_prefix : 0u;
-    const uint32_t before = own_before + (needs_prefix ? s_lower : 0u);
+    const uint32_t own_before = needs_prefix ? s_numbers.own_before : 0u;
+    const uint32_t before = own_before + (needs_prefix ? s_numbers.lower_ranks : 0u);
     // (Storing the rows of the worlds that go on while the look-back is under way, and the fresh rows behind it, was measured:
     // 32.6 against 30.4 us per step at 1 M worlds -- the 28-byte rows of neighbouring worlds share cache lines, and writing a
     // line in two passes costs more than the 2 us of waiting.)
@@ -299,10 +270,7 @@ __global__ void __launch_bounds__(kBlock) mrl_balance_step_fused(uint32_t n, con
             if (threadIdx.x == 0) Stats::add_totals(stats, &s_stats[0][0], kBlock / 64, b, block_total);
         }
     }
-    if (last_block && threadIdx.x == 0) {
-        *reset_count = own_before + block_total;
-        *next_counter = base + s_all;
-    }
+    if (last_block && threadIdx.x == 0) mrl::close_step(own_before, block_total, base, s_numbers.all_counts, reset_count, next_counter);
 }
 
 struct BalanceSim final : mrl::EpisodeSim {
@@ -311,15 +279,9 @@ struct BalanceSim final : mrl::EpisodeSim {
 
     void launch_fused(const int32_t *actions, const Drawn &drawn, const mrl::FusedExchange &fx, const Counters &c, hipStream_t stream) override
     {
-        if (stats_in_step())
-            hipLaunchKernelGGL(mrl_balance_step_fused<true>, dim3(fused_grid), dim3(kBlock), 0, stream, num_worlds, actions ? actions : action, obs,
-                               reward, done, status, group_total, epoch, c.base, c.next, reset_count, drawn.action_out, drawn.seed, drawn.step, heal,
-                               c.device, fx, stats->lane());
-        else
-            hipLaunchKernelGGL(mrl_balance_step_fused<false>, dim3(fused_grid), dim3(kBlock), 0, stream, num_worlds, actions ? actions : action, obs,
-                               reward, done, status, group_total, epoch, c.base, c.next, reset_count, drawn.action_out, drawn.seed, drawn.step, heal,
-                               c.device, fx, mrl::NoStats{});
-        stats_taken = stats_in_step();
+        single_launch(mrl_balance_step_fused<true>, mrl_balance_step_fused<false>, kBlock, stream, num_worlds, actions ? actions : action, obs,
+                      reward, done, status, group_total, epoch, c.base, c.next, reset_count, drawn.action_out, drawn.seed, drawn.step, heal, c.device,
+                      fx)();
     }
     void launch_step(const int32_t *actions, int32_t *action_out, uint64_t seed, uint32_t sample_step, hipStream_t stream) override
     {
@@ -376,16 +338,7 @@ struct BalanceSim final : mrl::EpisodeSim {
 
 mrl_sim *mrl::create_balance(int gpu_id, uint32_t num_worlds)
 {
-    if (num_worlds == 0) {
-        set_error("balance: num_worlds must be > 0");
-        throw HipError{MRL_ERR_INVALID};
-    }
-    bind_device(gpu_id);
-    auto *sim = new BalanceSim();
-    try {
-        sim->game = MRL_GAME_BALANCE;
-        sim->device = gpu_id;
-        sim->num_worlds = num_worlds;
+    return create_episode_sim<BalanceSim>("balance", MRL_GAME_BALANCE, gpu_id, num_worlds, [&](BalanceSim *sim) {
         sim->size_scan_grid(kBlock);
         const size_t N = num_worlds;
         sim->action = sim->arena.alloc<int32_t>(2 * N);
@@ -405,10 +358,5 @@ mrl_sim *mrl::create_balance(int gpu_id, uint32_t num_worlds)
         mrl::fill_i32(sim->active, 1, 2 * N);
         mrl::fill_i32(sim->mask, 1, 2 * N * 4);
         sim->reseed_shard(0, num_worlds, 0);  // Sim::Sim (sim.cpp:173-202): world w starts as episode w
-        MRL_HIP(hipDeviceSynchronize());
-    } catch (...) {
-        delete sim;
-        throw;
-    }
-    return sim;
+    });
 }

@@ -244,19 +244,12 @@ __global__ void __launch_bounds__(kBlock) mrl_cartpole_step(uint32_t n, uint32_t
                 reward[i] = 1.f;
                 done[i] = over ? 1 : 0;
             }
-            const unsigned long long votes = __ballot(over);
-            const uint32_t word = (i - (threadIdx.x & 63u)) >> 6;  // wave-uniform
-            if ((threadIdx.x & 63u) == 0 && i < last) finished_mask[word] = votes;
-            finished += (uint32_t)__popcll(votes);
+            finished += mrl::note_finished(over, i, i < last, finished_mask);
         }
     }
-    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = finished;
+    mrl::post_wave_count(finished, s_wave);
     __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t total = 0;
-        for (uint32_t w = 0; w < kBlock / 64; w++) total += s_wave[w];
-        block_counts[blockIdx.x] = total;
-    }
+    mrl::store_block_count(s_wave, block_counts);
 }
 
 // How many of workgroup j's worlds finish in this step, worked out by ONE wave of another workgroup from j's inputs in
@@ -280,10 +273,9 @@ __device__ __forceinline__ uint32_t recount_chunk(uint32_t n, const float4 *stat
 }
 
 // The whole step in one launch (mrl_step / mrl_step_with_actions on one GPU): workgroup b owns worlds [1024 b, 1024 b + 1024),
-// four per thread, all in registers from the first load to the last store.  Finished worlds get their episode index from
-// the single-launch look-back of episode_scan.hpp (a count that does not appear is recounted from that workgroup's
-// inputs: no workgroup ever depends on another one making progress) and are written once, already re-seeded; the
-// two-launch pair above stays for the sharded path, whose episode base comes from the other ranks between the phases.
+// four per thread, all in registers from the first load to the last store.  Finished worlds get their episode index by
+// the protocol of DESIGN.md 4.6 and are written once, already re-seeded; the two-launch pair above stays for the RCCL form
+// of the sharded path, whose episode base comes from the other ranks between the phases.
 //
 // Order of events in a workgroup (round 4): state loads, then action loads; new position and angle of its 1024 worlds (two
 // multiply-adds each) -> who finishes -> the count is PUBLISHED ~30 instructions after the state has arrived; the first wave
@@ -293,7 +285,6 @@ __device__ __forceinline__ uint32_t recount_chunk(uint32_t n, const float4 *stat
 // workgroup that does not see the count reads the state as the step's input).  The finished worlds of a wave -- a dozen
 // of its 256 under a random policy -- are re-seeded by as many lanes in ONE pass over a list in LDS (the seed hash is
 // ~150 dependent instructions; per round it would run four times for three lanes each).
-// (the look-back has two levels: mrl::grouped_prefix, episode_scan.hpp)
 // kStats (mrl_enable_episode_stats): the lane also keeps its four worlds' episode returns and step counts -- loaded behind
 // the actions, stored with reward and done -- and thread 0 adds the workgroup's finished episodes to TOTALS block b behind
 // the last barrier (episode_stats.hpp).  Without it the kernel is what it was.
@@ -329,7 +320,7 @@ __global__ void __launch_bounds__(kBlock) mrl_cartpole_step_fused(uint32_t n, co
     __builtin_amdgcn_s_setprio(3);
     // action_out != nullptr: the reference harness's randint(high=2) drawn here (random_policy.hpp)
     __shared__ uint32_t s_votes[kUnroll][kBlock / 64];
-    __shared__ uint32_t s_prefix, s_all_ranks;
+    __shared__ mrl::EpisodeNumbers s_numbers;
     __shared__ uint32_t s_list[kBlock / 64][kUnroll * 64];  // per wave: its finished worlds, (rank in the workgroup << 16) | local index
     const uint32_t b = blockIdx.x;
     const uint32_t first = b * (kUnroll * kBlock), last = min(n, first + kUnroll * kBlock);
@@ -382,6 +373,7 @@ __global__ void __launch_bounds__(kBlock) mrl_cartpole_step_fused(uint32_t n, co
     }
     CP_STAMP(1);
     mrl::lds_barrier();
+    static_assert(kUnroll * kBlock <= 0xfff, "a workgroup's finished count must fit the 12 bits of a status word (episode_scan.hpp)");
     uint32_t block_total = 0, wave_total = 0;
 #pragma unroll
     for (int u = 0; u < kUnroll; u++) {
@@ -417,23 +409,9 @@ __global__ void __launch_bounds__(kBlock) mrl_cartpole_step_fused(uint32_t n, co
     if (wave == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     mrl::lds_barrier();
     CP_STAMP(4);
-    if (wave == 0) {  // before its own stores: a load would sit out their acknowledgement
-        uint32_t before = mrl::grouped_prefix(status, group_total, b, epoch, block_total, needs_prefix, heal,
-                                              [&](uint32_t j) { return recount_chunk<V>(n, state, j); });
-        if (needs_prefix) {
-            if (fx.mail.num_ranks) {
-                // a shard of a larger batch: the last workgroup knows the shard's total and tells every rank; the ranks
-                // below this one come first in the numbering, and the counter moves on by the sum over all ranks
-                const uint32_t shard_total = before + block_total;  // (meaningful in the last workgroup)
-                before += mrl::fused_exchange(fx, last_block, shard_total, fx.mail.rank);
-                if (last_block) {
-                    const uint32_t all_ranks = mrl::fused_exchange(fx, false, 0u, fx.mail.num_ranks);
-                    if (lane == 0) s_all_ranks = all_ranks;
-                }
-            }
-            if (lane == 0) s_prefix = before;
-        }
-    }
+    if (wave == 0)  // before its own stores: a load would sit out their acknowledgement
+        mrl::fused_lookback(s_numbers, status, group_total, epoch, block_total, needs_prefix, heal, fx,
+                            [&](uint32_t j) { return recount_chunk<V>(n, state, j); });
     CP_STAMP(5);
     // everything that does not need the prefix goes out (the other three waves are here right after the barrier)
 #pragma unroll
@@ -476,25 +454,13 @@ __global__ void __launch_bounds__(kBlock) mrl_cartpole_step_fused(uint32_t n, co
     if constexpr (kStats) {
         if (threadIdx.x == 0 && block_total != 0) Stats::add_totals(stats, s_sums, kBlock / 64, b, block_total);
     }
-    const uint32_t prefix = s_prefix;
+    const uint32_t own_before = s_numbers.own_before, prefix = own_before + s_numbers.lower_ranks;
     for (uint32_t e = lane; e < wave_total; e += 64u) {  // this wave's finished worlds, one per lane
         const uint32_t entry = s_list[wave][e];
         state[first + (entry & 0xffffu)] = fresh_state(base + prefix + (entry >> 16));
     }
     CP_STAMP(7);
-    if (last_block && threadIdx.x == 0) {
-        if (fx.mail.num_ranks) {
-            // prefix includes the ranks below: this shard's own total is what its look-back and its own count add up to
-            uint32_t lower = 0;
-            for (uint32_t r = 0; r < fx.mail.rank; r++) lower += (uint32_t)fx.mine[(fx.mail.tag % mrl::kMailSlots) * MRL_MAX_RANKS + r];
-            *reset_count = prefix - lower + block_total;
-            *next_counter = base + s_all_ranks;
-        } else {
-            const uint32_t grand_total = prefix + block_total;  // the whole GPU's
-            *reset_count = grand_total;
-            *next_counter = base + grand_total;
-        }
-    }
+    if (last_block && threadIdx.x == 0) mrl::close_step(own_before, block_total, base, s_numbers.all_counts, reset_count, next_counter);
 }
 
 // mrl_rollout_random in ONE launch: the four worlds of a thread stay in registers for all steps;
@@ -668,24 +634,14 @@ struct CartpoleSim final : mrl::EpisodeSim {
     void launch_fused(const int32_t *actions, const Drawn &drawn, const mrl::FusedExchange &fx, const Counters &c, hipStream_t stream) override
     {
         with_variant(variant, [&](auto v) {
-            if (stats_in_step())
-                hipLaunchKernelGGL((mrl_cartpole_step_fused<decltype(v)::value, true>), dim3(fused_grid), dim3(kBlock), 0, stream, num_worlds,
-                                   actions ? actions : action, state, reward, done, status, group_total, epoch, c.base, c.next, reset_count,
-                                   drawn.action_out, drawn.seed, drawn.step, heal, c.device, fx, stats->lane()
+            single_launch(mrl_cartpole_step_fused<decltype(v)::value, true>, mrl_cartpole_step_fused<decltype(v)::value, false>, kBlock, stream,
+                          num_worlds, actions ? actions : action, state, reward, done, status, group_total, epoch, c.base, c.next, reset_count,
+                          drawn.action_out, drawn.seed, drawn.step, heal, c.device, fx)(
 #ifdef MRL_DIAG
-                                   , stamps
+                stamps  // (behind the statistics argument)
 #endif
-                );
-            else
-                hipLaunchKernelGGL((mrl_cartpole_step_fused<decltype(v)::value, false>), dim3(fused_grid), dim3(kBlock), 0, stream, num_worlds,
-                                   actions ? actions : action, state, reward, done, status, group_total, epoch, c.base, c.next, reset_count,
-                                   drawn.action_out, drawn.seed, drawn.step, heal, c.device, fx, mrl::NoStats{}
-#ifdef MRL_DIAG
-                                   , stamps
-#endif
-                );
+            );
         });
-        stats_taken = stats_in_step();
     }
 
     unsigned long long *ring = nullptr;
@@ -786,16 +742,7 @@ struct CartpoleSim final : mrl::EpisodeSim {
 
 mrl_sim *mrl::create_cartpole(int gpu_id, uint32_t num_worlds)
 {
-    if (num_worlds == 0) {
-        set_error("cartpole: num_worlds must be > 0");
-        throw HipError{MRL_ERR_INVALID};
-    }
-    bind_device(gpu_id);
-    auto *sim = new CartpoleSim();
-    try {
-        sim->game = MRL_GAME_CARTPOLE;
-        sim->device = gpu_id;
-        sim->num_worlds = num_worlds;
+    return create_episode_sim<CartpoleSim>("cartpole", MRL_GAME_CARTPOLE, gpu_id, num_worlds, [&](CartpoleSim *sim) {
         {
             const int64_t knob = mrl::debug_get("cartpole.variant", 0);  // 0: the default; 1 + Variant otherwise
             if (knob < 0 || knob > kNumVariants) {
@@ -841,10 +788,5 @@ mrl_sim *mrl::create_cartpole(int gpu_id, uint32_t num_worlds)
         mrl::fill_ids(sim->world_id, nullptr, 1, num_worlds);
         sim->reseed_shard(0, num_worlds, 0);
         sim->inject_scan_timeout();
-        MRL_HIP(hipDeviceSynchronize());
-    } catch (...) {
-        delete sim;
-        throw;
-    }
-    return sim;
+    });
 }

@@ -2,8 +2,9 @@
 // cartpole.hip, BalanceSim in balance.hip, AcrobotSim in acrobot.hip; the device side is episode_scan.hpp): the
 // double-buffered episode counter and the launch-to-launch state around it, the choice between the single-launch step and
 // the two-launch pair, phase 2 in its four forms and the forced reset, which are all the game's one re-seeding launch on
-// different inputs; for the three games with one lane per world also the status words of their single-launch step and
-// the random-policy rollout as one step per launch.  Host-only code.
+// different inputs; for the three games with one lane per world also the status words of their single-launch step, its
+// launch with or without in-kernel statistics (single_launch) and the random-policy rollout as one step per launch; and
+// the frame of the four mrl::create_* functions (create_episode_sim).  Host-only code.
 #pragma once
 
 #include "common.hpp"
@@ -114,6 +115,20 @@ struct EpisodeSim : mrl_sim {
     {
         counted_launch(true, nullptr, stream, [&](const Counters &c) { launch_fused(actions, drawn, fx, c, stream); });
     }
+    // What a lane-per-world game's launch_fused is: the kernel's instantiation with or without the in-kernel statistics on
+    // fused_grid, `lead...` being the kernel's arguments in front of the statistics argument, which is appended here.  The
+    // call returns the launch itself, to be called with whatever the kernel takes behind it (Cartpole's diagnostic stamps).
+    template <typename WithStats, typename Plain, typename... Lead>
+    auto single_launch(WithStats with_stats, Plain plain, uint32_t block, hipStream_t stream, Lead... lead)
+    {
+        return [=](auto... tail) {
+            if (stats_in_step())
+                hipLaunchKernelGGL(with_stats, dim3(fused_grid), dim3(block), 0, stream, lead..., stats->lane(), tail...);
+            else
+                hipLaunchKernelGGL(plain, dim3(fused_grid), dim3(block), 0, stream, lead..., NoStats{}, tail...);
+            stats_taken = stats_in_step();
+        };
+    }
     void reseed(const Finished &from, const uint32_t *external_base, const GatheredCounts &gathered, hipStream_t stream)
     {
         counted_launch(false, external_base, stream, [&](const Counters &c) { launch_reseed(from, gathered, c, stream); });
@@ -184,7 +199,7 @@ struct EpisodeSim : mrl_sim {
         MRL_HIP(hipStreamSynchronize(stream));
     }
 
-    // ---- construction ----
+    // ---- construction (create_episode_sim below is the frame; these are what a game's part of it calls) ----
     // first: grid and chunk of the two-launch step (the game's own allocations depend on them)
     void size_scan_grid(uint32_t worlds_per_workgroup)
     {
@@ -236,5 +251,28 @@ struct EpisodeSim : mrl_sim {
         if (debug_get("inject_scan_timeout", 0)) hipLaunchKernelGGL(raise_alarm_kernel, dim3(1), dim3(1), 0, 0, alarm.alarm());
     }
 };
+
+// mrl::create_<game> of the four games: refuses an empty batch, binds the device, and runs init(sim) -- the game's
+// allocations in the game's own sequence (see alloc_episode), its first episodes -- on a new Sim that does not outlive a throw.
+template <typename Sim, typename Init> mrl_sim *create_episode_sim(const char *name, int game, int gpu_id, uint32_t num_worlds, Init &&init)
+{
+    if (num_worlds == 0) {
+        set_error("%s: num_worlds must be > 0", name);
+        throw HipError{MRL_ERR_INVALID};
+    }
+    bind_device(gpu_id);
+    auto *sim = new Sim();
+    try {
+        sim->game = game;
+        sim->device = gpu_id;
+        sim->num_worlds = num_worlds;
+        init(sim);
+        MRL_HIP(hipDeviceSynchronize());
+    } catch (...) {
+        delete sim;
+        throw;
+    }
+    return sim;
+}
 
 }  // namespace mrl

@@ -1,5 +1,7 @@
 // Deterministic episode numbering for the games that seed a world from its episode's index: Hanabi, Cartpole, the balance
-// beam, Acrobot.
+// beam, Acrobot: the two-launch step's prefix and re-seeding launch, the single-launch step's status words and look-back,
+// and (last section) the count, look-back and numbering tail that the four single-launch kernels and the three phase-1
+// kernels share.  The host side is episode_host.hpp.
 //
 // The reference draws each new episode's index from one process-wide atomic
 // (src/hanabi_env/sim.cpp:449-451, src/cartpole_env/sim.cpp:51-53), i.e. in thread-arrival
@@ -555,6 +557,102 @@ __device__ __forceinline__ uint32_t grouped_prefix(const uint32_t *status, unsig
         return wave_sum(lookback_finish<kGroupWords>(status, g * kGroup, g * kGroup + kGroup, epoch, heal, words, recount));
     };
     return in_group + wave_sum(lookback_finish<1>(group_total, 0, group, epoch, HealTest{}, lower_groups, regroup));
+}
+
+// ---- count, look-back and numbering of a step, once for all games (the protocol and who does which step: DESIGN.md 4.6) ----
+// None of these holds a barrier, a wait for memory or a priority change: which barrier hands s_wave and the numbers
+// over, and where the publishing wave waits for its store, is measured per kernel and stays in the kernel's body.
+
+// One flag of a lane (wave-uniform call): the wave's count of set flags into its word of `s_round` -- s_wave[u] of the
+// lane's u-th world -- and, returned, the lane's rank among the wave's set flags.
+template <int kWaves> __device__ __forceinline__ uint32_t cast_vote(bool flag, uint32_t (&s_round)[kWaves])
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const unsigned long long votes = __ballot(flag);
+    const uint32_t rank = (uint32_t)__popcll(votes & ((1ull << lane) - 1ull));
+    if (lane == 0) s_round[threadIdx.x >> 6] = (uint32_t)__popcll(votes);
+    return rank;
+}
+// Behind the caller's barrier: the workgroup's total, and rank[u] (cast_vote's) becomes the flag's rank in the workgroup in
+// ascending world order -- round u covers worlds first + kBlock u ..., so everything of a lower round, and of a lower wave
+// in the same round, comes first.
+template <int K, int kBlock> __device__ __forceinline__ uint32_t tally_votes(const uint32_t (&s_wave)[K][kBlock / 64], uint32_t (&rank)[K])
+{
+    static_assert(K * kBlock <= 0xfff, "a workgroup's finished count must fit the 12 bits of a status word");
+    const uint32_t wave = threadIdx.x >> 6;
+    uint32_t block_total = 0;
+#pragma unroll
+    for (int u = 0; u < K; u++)
+        for (uint32_t v = 0; v < kBlock / 64; v++) {
+            const uint32_t c = s_wave[u][v];
+            block_total += c;
+#pragma unroll
+            for (int u2 = 0; u2 < K; u2++) rank[u2] += (u < u2 || (u == u2 && v < wave)) ? c : 0u;
+        }
+    return block_total;
+}
+
+// A finished world of rank r in its workgroup starts episode base + lower_ranks + own_before + r; the step leaves
+// RESET_COUNT = own_before + the last workgroup's count and the counter at base + all_counts.
+struct EpisodeNumbers {
+    uint32_t own_before;   // finished worlds of this GPU's lower workgroups
+    uint32_t lower_ranks;  // ... of the ranks below this one (0 unless the batch is sharded)
+    uint32_t all_counts;   // ... of all ranks (meaningful in the last workgroup)
+};
+
+// (wave-uniform call, behind the look-back) A shard of a larger batch: the last workgroup tells every rank the shard's
+// total; the ranks below come first in the numbering, and the counter moves on by the sum over all ranks.
+__device__ __forceinline__ EpisodeNumbers number_episodes(const FusedExchange &fx, bool last_block, bool needs_prefix, uint32_t before,
+                                                          uint32_t block_total)
+{
+    EpisodeNumbers e{before, 0u, before + block_total};
+    if (fx.mail.num_ranks && needs_prefix) {
+        e.lower_ranks = fused_exchange(fx, last_block, before + block_total, fx.mail.rank);
+        if (last_block) e.all_counts = fused_exchange(fx, false, 0u, fx.mail.num_ranks);
+    }
+    return e;
+}
+
+// The first wave of a workgroup that has published block_total: two-level look-back, exchange, and the numbers into the
+// caller's word of LDS for the other waves (nothing is written unless needs_prefix: nobody reads it then).
+template <typename Recount>
+__device__ __forceinline__ void fused_lookback(EpisodeNumbers &s_numbers, const uint32_t *status, unsigned long long *group_total, uint32_t epoch,
+                                               uint32_t block_total, bool needs_prefix, const HealTest &heal, const FusedExchange &fx,
+                                               Recount &&recount)
+{
+    const bool last_block = blockIdx.x == gridDim.x - 1;
+    const uint32_t before = grouped_prefix(status, group_total, blockIdx.x, epoch, block_total, needs_prefix, heal, recount);
+    const EpisodeNumbers e = number_episodes(fx, last_block, needs_prefix, before, block_total);
+    if ((threadIdx.x & 63u) == 0 && needs_prefix) s_numbers = e;
+}
+
+// the last workgroup, one thread
+__device__ __forceinline__ void close_step(uint32_t own_before, uint32_t block_total, uint32_t base, uint32_t all_counts, uint32_t *reset_count,
+                                           uint32_t *next_counter)
+{
+    *reset_count = own_before + block_total;
+    *next_counter = base + all_counts;
+}
+
+// The two-launch step's phase 1 (and mrl_reset_worlds' mask launch): a wave's 64 flags as one word of finished_mask
+// (world i = bit i % 64 of word i / 64; `store`: the wave's worlds exist and the words are wanted), their number returned;
+// at the end the waves' counts meet in s_wave and, behind the caller's barrier, thread 0 leaves their sum.
+__device__ __forceinline__ uint32_t note_finished(bool over, uint32_t i, bool store, unsigned long long *finished_mask)
+{
+    const unsigned long long votes = __ballot(over);
+    if ((threadIdx.x & 63u) == 0 && store) finished_mask[i >> 6] = votes;
+    return (uint32_t)__popcll(votes);
+}
+template <int kWaves> __device__ __forceinline__ void post_wave_count(uint32_t count, uint32_t (&s_wave)[kWaves])
+{
+    if ((threadIdx.x & 63u) == 0) s_wave[threadIdx.x >> 6] = count;
+}
+template <int kWaves> __device__ __forceinline__ void store_block_count(const uint32_t (&s_wave)[kWaves], uint32_t *block_counts)
+{
+    if (threadIdx.x != 0) return;
+    uint32_t total = 0;
+    for (uint32_t w = 0; w < kWaves; w++) total += s_wave[w];
+    block_counts[blockIdx.x] = total;
 }
 
 }  // namespace mrl

@@ -1802,19 +1802,10 @@ mrl_hanabi_step_fused(uint32_t *hot_records, const int32_t *hot_actions, uint32_
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (lane == 0) __hip_atomic_store(&s_ready, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         FSTAMP_SCAN(1);
-        uint32_t lower_ranks = 0, all_counts = before + block_total;
-        if (fx.mail.num_ranks) {
-            // a shard of a larger batch: the last workgroup tells every rank the shard's total; the ranks below come first in the
-            // numbering, and the counter moves on by the sum over all ranks
-            if (block_total != 0 || last_block) lower_ranks = mrl::fused_exchange(fx, last_block, before + block_total, fx.mail.rank);
-            if (last_block) all_counts = mrl::fused_exchange(fx, false, 0u, fx.mail.num_ranks);
-        }
-        if (last_block && lane == 0) {
-            *reset_count = before + block_total;
-            *next_counter = base + all_counts;
-        }
+        const mrl::EpisodeNumbers e = mrl::number_episodes(fx, last_block, block_total != 0 || last_block, before, block_total);  // (sharded batch)
+        if (last_block && lane == 0) mrl::close_step(before, block_total, base, e.all_counts, reset_count, next_counter);
         flag_wait(&s_encoded, leaders);  // the leaders have written their last bit vector: the finished worlds' slots are free
-        deal_finished_worlds<kV>(p, [&](uint32_t wv) { return wave_lds(smem, wv); }, s_fin, start_of, base + lower_ranks + before, lane);
+        deal_finished_worlds<kV>(p, [&](uint32_t wv) { return wave_lds(smem, wv); }, s_fin, start_of, base + e.lower_ranks + before, lane);
         if (lane == 0) __hip_atomic_store(&s_ready, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         FSTAMP_SCAN(2);
         return;
@@ -2359,16 +2350,7 @@ mrl_sim *mrl::create_hanabi(const mrl_hanabi_config *cfg, int gpu_id, uint32_t n
         set_error("hanabi: need 1..5 colors, 2..5 ranks, 1..8 information tokens, 1..3 life tokens");
         throw HipError{MRL_ERR_INVALID};
     }
-    if (num_worlds == 0) {
-        set_error("hanabi: num_worlds must be > 0");
-        throw HipError{MRL_ERR_INVALID};
-    }
-    bind_device(gpu_id);
-    auto *sim = new HanabiSim();
-    try {
-        sim->game = MRL_GAME_HANABI;
-        sim->device = gpu_id;
-        sim->num_worlds = num_worlds;
+    return create_episode_sim<HanabiSim>("hanabi", MRL_GAME_HANABI, gpu_id, num_worlds, [&](HanabiSim *sim) {
         sim->size_scan_grid(kWorldsPerBlock);
         HanabiParams &a = sim->params;
         a.chunk = sim->chunk;
@@ -2445,10 +2427,5 @@ mrl_sim *mrl::create_hanabi(const mrl_hanabi_config *cfg, int gpu_id, uint32_t n
         mrl::fill_ids(sim->world_id, sim->agent_id, 2, N);
         sim->reseed_shard(0, N, 0);
         sim->inject_scan_timeout();
-        MRL_HIP(hipDeviceSynchronize());
-    } catch (...) {
-        delete sim;
-        throw;
-    }
-    return sim;
+    });
 }

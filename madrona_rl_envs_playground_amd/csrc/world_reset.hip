@@ -1,5 +1,6 @@
 // The kernels of mrl_reset_worlds (world_reset.hpp says how they are used), and the two fill kernels behind the
 // simulators' constant tensors.
+#include "episode_scan.hpp"
 #include "kitchen_host.hpp"
 
 namespace {
@@ -12,19 +13,16 @@ __global__ void __launch_bounds__(256) mrl_reset_mask_counts(const uint8_t *__re
 {
     __shared__ uint32_t s_wave[4];
     const uint32_t first = blockIdx.x * chunk, last = min(n, first + chunk);
-    const uint32_t lane = threadIdx.x & 63u;
     uint32_t count = 0;  // wave-uniform
     for (uint32_t i0 = first; i0 < last; i0 += 256) {  // uniform trip count
         const uint32_t i = i0 + threadIdx.x;
         const bool on = i < last && (!mask || mask[i] != 0);
-        const unsigned long long votes = __ballot(on);
-        if (words && lane == 0 && i < last) words[i >> 6] = votes;
         if (flags && i < last) flags[i] = on ? 1 : 0;
-        count += (uint32_t)__popcll(votes);
+        count += mrl::note_finished(on, i, words && i < last, words);
     }
-    if (lane == 0) s_wave[threadIdx.x >> 6] = count;
+    mrl::post_wave_count(count, s_wave);
     __syncthreads();
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    mrl::store_block_count(s_wave, block_counts);
 }
 
 // One wavefront per world; a world outside the mask costs the load of its mask byte.

@@ -11,6 +11,7 @@ import os
 import socket
 import sys
 
+import numpy as np
 import pytest
 import torch
 import torch.multiprocessing as mp
@@ -20,6 +21,33 @@ from conftest import REPO
 pytestmark = pytest.mark.gpu
 
 HANABI = dict(colors=5, ranks=5, players=2, max_information_tokens=8, max_life_tokens=3)
+
+
+def _make(game):
+    """num_worlds -> simulator"""
+    from madrona_rl_envs_playground_amd.simulators import AcrobotSimulator, BalanceBeamSimulator, CartpoleSimulator, ExecMode, HanabiSimulator
+    if game == "hanabi":
+        return lambda k: HanabiSimulator(exec_mode=ExecMode.CUDA, gpu_id=0, num_worlds=k, **HANABI)
+    cls = {"cartpole": CartpoleSimulator, "balance": BalanceBeamSimulator, "acrobot": AcrobotSimulator}[game]
+    return lambda k: cls(ExecMode.CUDA, 0, k)
+
+
+# per game: (actions of the whole batch from the shared stream, the tensors compared at a snapshot with their world dimension)
+ACTIONS = {"cartpole": lambda n, gen: torch.randint(0, 2, (n, 1), dtype=torch.int32, generator=gen),
+           "balance": lambda n, gen: torch.randint(0, 4, (2, n, 1), dtype=torch.int32, generator=gen),
+           "acrobot": lambda n, gen: torch.randint(0, 3, (n, 1), dtype=torch.int32, generator=gen)}
+COMPARED = {"hanabi": (("game_tensor", 0),), "cartpole": (("observation_tensor", 0),),
+            "balance": (("observation_tensor", 1), ("done_tensor", 0)),
+            "acrobot": (("observation_tensor", 0), ("reset_tensor", 0), ("episode_length_tensor", 0))}
+
+
+def _plant_swing(sim, lo, n):
+    """Acrobot: worlds [lo, lo + n) of the batch start swinging (tests/golden/acrobot_ref.npz swing_state, row world % 2048),
+    so that episodes end within the test's steps"""
+    with np.load(os.path.join(REPO, "tests", "golden", "acrobot_ref.npz")) as gold:
+        states = gold["swing_state"][np.arange(lo, lo + n) % 2048]
+    sim.observation_tensor().to_torch().copy_(torch.from_numpy(np.ascontiguousarray(states, dtype=np.float32)))
+    sim.episode_length_tensor().to_torch().fill_(0)
 
 
 def _free_port():
@@ -91,15 +119,12 @@ def _mailbox_rank(rank, ws, port, game, total, steps, out_dir):
     sys.path.insert(0, REPO)
     import torch.distributed as dist
     from madrona_rl_envs_playground_amd.distributed import ShardedSimulator
-    from madrona_rl_envs_playground_amd.simulators import CartpoleSimulator, ExecMode, HanabiSimulator
     torch.cuda.set_device(0)
     dist.init_process_group("gloo", rank=rank, world_size=ws)
     try:
-        if game == "hanabi":
-            make = lambda k: HanabiSimulator(exec_mode=ExecMode.CUDA, gpu_id=0, num_worlds=k, **HANABI)  # noqa: E731
-        else:
-            make = lambda k: CartpoleSimulator(ExecMode.CUDA, 0, k)  # noqa: E731
-        sh = ShardedSimulator(make, total, exchange="mailbox")
+        sh = ShardedSimulator(_make(game), total, exchange="mailbox")
+        if game == "acrobot":
+            _plant_swing(sh.sim, sh.lo, sh.n)
         gen = torch.Generator().manual_seed(99)  # the same global random stream on both ranks
         snaps = []
         for t in range(steps):
@@ -108,16 +133,15 @@ def _mailbox_rank(rank, ws, port, game, total, steps, out_dir):
                 mask = sh.gather(sh.sim.action_mask_tensor().to_torch().contiguous(), world_dim=1).cpu()
                 a = (torch.rand(mask.shape, generator=gen) * mask).argmax(-1).to(torch.int32).unsqueeze(-1)
                 sh.step(a[:, sh.lo:sh.lo + sh.n].contiguous().cuda())
-                local = sh.sim.game_tensor().to_torch()
-                dim = 0
             else:
-                a = torch.randint(0, 2, (total, 1), dtype=torch.int32, generator=gen)
-                sh.step(a[sh.lo:sh.lo + sh.n].contiguous().cuda())
-                local = sh.sim.observation_tensor().to_torch()
-                dim = 0
+                a = ACTIONS[game](total, gen)
+                sh.step(a.narrow(a.dim() - 2, sh.lo, sh.n).contiguous().cuda())
             if t % 7 == 0 or t == steps - 1:
-                snaps.append(sh.gather(local, world_dim=dim).cpu())
-        assert int(sh.sim.scan_timeout_tensor().to_torch().item()) == 0
+                snaps.append([sh.gather(getattr(sh.sim, name)().to_torch(), world_dim=dim).cpu() for name, dim in COMPARED[game]])
+        if game == "balance":  # (it exports no SCAN_TIMEOUT slot)
+            assert not sh.sim.scan_timed_out
+        else:
+            assert int(sh.sim.scan_timeout_tensor().to_torch().item()) == 0
         if rank == 0:
             torch.save(snaps, os.path.join(out_dir, "snaps.pt"))
         torch.cuda.synchronize()
@@ -127,29 +151,30 @@ def _mailbox_rank(rank, ws, port, game, total, steps, out_dir):
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("game,total,steps", [("cartpole", 200001, 60), ("hanabi", 3000, 50)])
+@pytest.mark.parametrize("game,total,steps", [("cartpole", 200001, 60), ("hanabi", 3000, 50), ("balance", 4099, 12), ("acrobot", 4099, 24)])
 def test_two_processes_exchange_through_ipc_mailboxes(game, total, steps, hip_lib, tmp_path):
     """Two ranks, two processes, one GPU: every world of the sharded run holds what it holds in ONE simulator of the whole
-    batch fed the same actions -- so every finished world took the episode number the global order gives it."""
-    from madrona_rl_envs_playground_amd.simulators import CartpoleSimulator, ExecMode, HanabiSimulator
+    batch fed the same actions -- so every finished world took the episode number the global order gives it.  The balance
+    beam and Acrobot run shards of three workgroups with a ragged last one (4099 worlds: 2050 + 2049), so the upper rank's
+    other workgroups need both their own look-back and the lower rank's total; Acrobot starts from the swing states."""
     mp.start_processes(_mailbox_rank, args=(2, _free_port(), game, total, steps, str(tmp_path)), nprocs=2, join=True, start_method="spawn")
     snaps = torch.load(os.path.join(str(tmp_path), "snaps.pt"))
     gen = torch.Generator().manual_seed(99)
-    whole = (HanabiSimulator(exec_mode=ExecMode.CUDA, gpu_id=0, num_worlds=total, **HANABI) if game == "hanabi"
-             else CartpoleSimulator(ExecMode.CUDA, 0, total))
+    whole = _make(game)(total)
+    if game == "acrobot":
+        _plant_swing(whole, 0, total)
     k, finished = 0, 0
     for t in range(steps):
         if game == "hanabi":
             mask = whole.action_mask_tensor().to_torch().cpu()
             a = (torch.rand(mask.shape, generator=gen) * mask).argmax(-1).to(torch.int32).unsqueeze(-1)
             whole.step_with_actions(a.cuda())
-            now = whole.game_tensor().to_torch()
         else:
-            whole.step_with_actions(torch.randint(0, 2, (total, 1), dtype=torch.int32, generator=gen).cuda())
-            now = whole.observation_tensor().to_torch()
+            whole.step_with_actions(ACTIONS[game](total, gen).cuda())
         finished += int(whole.reset_count_tensor().to_torch().item())
         if t % 7 == 0 or t == steps - 1:
-            assert torch.equal(snaps[k], now.cpu()), f"{game}: the sharded batch differs from one simulator at step {t}"
+            for (name, _), sharded in zip(COMPARED[game], snaps[k]):
+                assert torch.equal(sharded, getattr(whole, name)().to_torch().cpu()), f"{game}: {name} of the sharded batch differs from one simulator at step {t}"
             k += 1
-    assert k == len(snaps) and finished > 100
+    assert k == len(snaps) and finished > 100 and not whole.scan_timed_out
     whole.close()
