@@ -657,7 +657,7 @@ int mrl_ppo_update(const mrl_mlp_policy *shape, const mrl_ppo_optimizer *opt, co
  * ReLU MLPs of width 512 for EVERY world, masks the logits, draws from a Categorical, writes about ten buffer rows
  * (:352-371) and reads torch.any(dones) on the host (:207); before each update it walks T steps backwards with boolean-mask
  * indexing (:230-262).  Here those are mrl_agent_act, mrl_agent_credit and mrl_gae_active; none of them synchronises.  The
- * learning phase (:268-330) stays with the caller.  No reference counterpart as calls.  DESIGN.md section 14.
+ * learning phase (:268-330) is mrl_agent_update, below.  No reference counterpart as calls.  DESIGN.md section 14.
  *   Policy (CleanRLNetwork, :66-113): critic = Linear(S, 512), ReLU, Linear(512, 512), ReLU, Linear(512, 512), ReLU,
  *     Linear(512, 1); actor the same from D inputs to A outputs.  params_dev is one flat float32 device array in the order of
  *     parameters_to_vector(agent.parameters()): critic.0.weight (512, S) row-major, critic.0.bias, ..., critic.6.bias, then
@@ -748,6 +748,54 @@ int mrl_agent_credit(const mrl_agent_record *record, const float *rewards_dev, c
                      int gpu_id, void *hip_stream);
 int mrl_gae_active(const mrl_agent_record *record, const float *next_value, const uint8_t *next_active, float gamma, float lambda,
                    float *advantages, float *returns, int gpu_id, void *hip_stream);
+
+/* The learning phase of CleanPPOAgent (pantheonrl_extension/vectoragent.py:268-330) on the device, for the wide policy above:
+ * boolean-mask indexing, float copies of the int8 rows, autograd over both nets, clip_grad_norm_ and Adam.step() become
+ * mrl_agent_update.  No reference counterpart as a call.  DESIGN.md section 17.
+ *   Samples: the cells (t, w) of the record with active[t, w] != 0, in ascending flat order t N + w (the order of the
+ *     reference's self.obs[self.active]); B of them.  The reference's per-epoch randperm (:281) only reorders a whole-batch
+ *     mean, so there is no permutation and no index argument.
+ *   One call is `epochs` epochs (:283-323).  Epoch k, float32: logits and values of the B samples are recomputed from rows
+ *     record->obs / record->states (element types obs_type / state_type, converted on load; no float copy) with
+ *     mrl_agent_act's own layer kernel, so on unchanged parameters they carry the record's bits; the masked soft-max, the
+ *     log-prob of the recorded action and the entropy use mrl_agent_act's expressions; ratio = exp(new - old).  With
+ *     MRL_PPO_NORM_ADV A = (adv - mean) / (std + 1e-8), mean and unbiased std over all B samples (summed in double, once per
+ *     call); the losses, their gradient rules for max / clamp, the clipping and Adam's step are mrl_ppo_update's (above), with
+ *     one clip over ALL parameters and t = opt->step + 1 + k; ReLU passes a gradient where the activation is > 0.
+ *     cfg->lr .. eps are Adam's.  opt->params_dev is the parameter array (policy->params_dev is not read).
+ *   Arithmetic of the backward pass: a weight gradient dW[c][k] = sum_j dY[j][c] X[j][k] and a bias gradient db[c] = sum_j
+ *     dY[j][c] start from 0 and add the samples in list order, one fused multiply-add each, on v_mfma_f32_32x32x2_f32 (the
+ *     sample pair is the instruction's k; an odd count is padded with a zero); an input gradient dX[j][k] = (X[j][k] > 0)
+ *     sum_c dY[j][c] W[c][k] adds c ascending the same way.  Every gradient entry is written once; there are no partial
+ *     vectors, no float atomics and no wait between workgroups: the same inputs give the same bits on every run, on any
+ *     stream, and one call of K epochs the bits of K calls of one (with opt->step advanced by the caller).
+ *   stats (epochs, 10), optional: mrl_ppo_update's eight columns, then 8 samples = B (exact: T N >= 2^24 is refused) and
+ *     9 status: 0 done; 1 B < 2 (the reference's .std() is NaN there); 2 B > capacity.  With status 1 or 2 no byte of the
+ *     parameters, the moments or grads changes and columns 0-7 are 0.  grads (epochs, P), optional: row k is epoch k's
+ *     unclipped gradient in parameter order.
+ *   A sample whose mask row has no legal action has log-prob -inf in the record; as in the reference the update then yields
+ *     NaN.  It cannot occur for an active seat of either game.
+ *   workspace: mrl_agent_update_workspace_bytes for `capacity` samples, 1 <= capacity <= T N, 16-byte aligned, the
+ *     caller's; it holds nothing between calls.  With n = capacity and P = mrl_wide_policy_num_params, pad = up to a
+ *     multiple of 256:  pad(4 n) + 256  +  2 * 6 * 2048 n  +  2 * 256 n  +  2 pad(4 n)  +  256  +  pad(64 ceil(n / 256))  +
+ *     2 pad(4 P)  +  pad(4 ceil(P / 256))  bytes: the sample list and its three words; activations and hidden gradients
+ *     (2 nets x 3 layers x n x 512 floats each); logits and d_logits; value and d_value; mean and std; partial stats; the
+ *     gradient, its copy and the blocks' sums of squares.  About 25 KB per sample.
+ *   The call only enqueues on hip_stream of device gpu_id: it never synchronises or allocates.  Every kernel reads B from a
+ *     device word; grids are sized for capacity and tiles past B leave at once.  Launches: the list, the advantages' moments
+ *     (MRL_PPO_NORM_ADV), and per epoch four forward layers, the loss head, three input-gradient layers, one weight-gradient
+ *     launch over all eight layers and the two of the optimiser tail.
+ *   MRL_ERR_INVALID: a NULL among policy, opt, record, cfg, advantages, returns, workspace, the optimizer's three arrays and
+ *     the record's obs, states, action_masks, active, actions, logprobs, values; num_actions outside 1..64; obs_dim or
+ *     state_dim 0; T N >= 2^24; capacity 0 or above T N; workspace_bytes too small; a workspace off a 16-byte boundary or a
+ *     float / int32 array off a 4-byte one; flag bits other than MRL_PPO_NORM_ADV | MRL_PPO_CLIP_VLOSS; an element type
+ *     other than MRL_INT8 .. MRL_UINT32; a capturing stream.  epochs == 0 enqueues nothing.
+ *     mrl_agent_update_workspace_bytes refuses the same shapes (capacity 0 or >= 2^24) and a NULL out. */
+int mrl_agent_update_workspace_bytes(uint32_t obs_dim, uint32_t state_dim, uint32_t num_actions, uint32_t capacity, uint64_t *out);
+int mrl_agent_update(const mrl_wide_policy *policy, const mrl_ppo_optimizer *opt, const mrl_agent_record *record,
+                     uint32_t obs_type, uint32_t state_type, const float *advantages, const float *returns /* (T, N) */,
+                     uint32_t epochs, const mrl_ppo_config *cfg, uint32_t capacity, void *workspace_dev, uint64_t workspace_bytes,
+                     float *stats_or_null /* (epochs, 10) */, float *grads_or_null /* (epochs, P) */, int gpu_id, void *hip_stream);
 
 /* MAPPO's CNN actor-critic for Overcooked on the device: what the reference's rollout loop runs in torch around every step
  * (train/MAPPO/main_player.py:211-261) -- for each seat an int8 -> float cast, a movedim, Conv2d, three Linear layers and a

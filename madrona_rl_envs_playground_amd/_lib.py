@@ -36,6 +36,7 @@ CNN_HIDDEN, CNN_ACTIONS = 64, 6  # the one shape mrl_cnn_act runs
 MAPPO_VALUENORM, MAPPO_HUBER_LOSS, MAPPO_CLIPPED_VALUE_LOSS, MAPPO_MAX_GRAD_NORM = 1, 2, 4, 8  # MRL_MAPPO_*
 MAPPO_STATS = ("value_loss", "critic_grad_norm", "policy_loss", "dist_entropy", "actor_grad_norm", "ratio", "clipfrac", "reserved")
 PPO_STATS = ("pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac", "total_norm", "loss")  # a stats row
+AGENT_UPDATE_STATS = PPO_STATS + ("samples", "status")  # a stats row of mrl_agent_update; status 0 done, 1 B < 2, 2 B > capacity
 
 # every symbol include/mrl_envs.h declares
 SYMBOLS = [
@@ -50,6 +51,7 @@ SYMBOLS = [
     "mrl_rollout_policy", "mrl_gae", "mrl_ppo_workspace_bytes", "mrl_ppo_update", "mrl_wide_policy_num_params",
     "mrl_agent_workspace_bytes", "mrl_agent_act", "mrl_agent_credit", "mrl_gae_active", "mrl_cnn_policy_num_params",
     "mrl_cnn_workspace_bytes", "mrl_cnn_act", "mrl_rollout_cnn", "mrl_mappo_workspace_bytes", "mrl_mappo_update",
+    "mrl_agent_update_workspace_bytes", "mrl_agent_update",
 ]
 ABI_VERSION = 4  # MRL_ABI_VERSION of include/mrl_envs.h this binding was written against
 
@@ -266,6 +268,9 @@ def lib():
                                 vp]
     L.mrl_agent_credit.argtypes = [ctypes.POINTER(AgentRecord), vp, vp, u32, i32, vp]
     L.mrl_gae_active.argtypes = [ctypes.POINTER(AgentRecord), vp, vp, ctypes.c_float, ctypes.c_float, vp, vp, i32, vp]
+    L.mrl_agent_update_workspace_bytes.argtypes = [u32, u32, u32, u32, ctypes.POINTER(ctypes.c_uint64)]
+    L.mrl_agent_update.argtypes = [ctypes.POINTER(WidePolicyDesc), ctypes.POINTER(PpoOptimizerDesc), ctypes.POINTER(AgentRecord), u32, u32,
+                                   vp, vp, u32, ctypes.POINTER(PpoConfig), u32, vp, ctypes.c_uint64, vp, vp, i32, vp]
     L.mrl_cnn_policy_num_params.argtypes = [u32, u32, u32, u32, u32]
     L.mrl_cnn_policy_num_params.restype = ctypes.c_uint64
     L.mrl_cnn_workspace_bytes.argtypes = [u32, u32]

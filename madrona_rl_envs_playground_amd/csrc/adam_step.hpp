@@ -52,6 +52,7 @@ struct AdamStepArgs {
     float *grad, *sumsq;         // [segment][stride], [segment][blocks]
     float *grads_row;            // the row's unclipped gradient in parameter order, or nullptr
     float *params, *exp_avg, *exp_avg_sq;
+    const uint32_t *skip;  // nullptr, or a device word: non-zero leaves grad, grads_row, the parameters and the moments as they are
     uint64_t stride;
     uint32_t segments, groups, blocks;      // blocks of kAdamThreads per segment, the same for both
     uint32_t clip;                          // 0: no clip_grad_norm_
@@ -90,6 +91,7 @@ template <int THREADS>
 __global__ void __launch_bounds__(THREADS) mrl_grad_reduce(AdamStepArgs a)
 {
     __shared__ float scratch[THREADS];
+    if (a.skip && *a.skip) return;  // (uniform over the grid)
     const uint32_t seg = blockIdx.y, p = blockIdx.x * THREADS + threadIdx.x;
     const float *__restrict__ partial = a.partial_grads + (size_t)seg * a.groups * a.stride;
     float g = 0.0f;
@@ -103,11 +105,15 @@ __global__ void __launch_bounds__(THREADS) mrl_grad_reduce(AdamStepArgs a)
 }
 
 // clip_grad_norm_ and torch.optim.Adam's single-tensor step, per segment.  Thread 0 of block 0 of each segment then calls
-// stats(segment, total norm), the algorithm's own end of the stats row.
+// stats(segment, total norm), the algorithm's own end of the stats row (with a non-zero skip word: stats(segment, 0) alone).
 template <typename STATS>
 __global__ void __launch_bounds__(kAdamThreads) mrl_clip_adam(AdamStepArgs a, STATS stats)
 {
     const uint32_t seg = blockIdx.y;
+    if (a.skip && *a.skip) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) stats(seg, 0.0f);
+        return;
+    }
     float squares = 0.0f;
     for (uint32_t b = 0; b < a.blocks; b++) squares += a.sumsq[seg * a.blocks + b];
     const float total = sqrtf(squares);

@@ -5,6 +5,7 @@
 #include "policy_rollout.hpp"
 #include "ppo_update.hpp"
 #include "wide_policy.hpp"
+#include "wide_update.hpp"
 #include "cnn_policy.hpp"
 #include "cnn_update.hpp"
 
@@ -902,6 +903,85 @@ int mrl_gae_active(const mrl_agent_record *record, const float *next_value, cons
     return guarded([&] {
         mrl::launch_gae_active(*record, next_value, next_active, gamma, lambda, advantages, returns, (hipStream_t)hip_stream);
     });
+}
+
+static const char *agent_update_shape_error(uint32_t obs_dim, uint32_t state_dim, uint32_t num_actions, uint32_t capacity)
+{
+    if (num_actions == 0 || num_actions > MRL_WIDE_MAX_ACTIONS || obs_dim == 0 || state_dim == 0)
+        return "need 1 <= num_actions <= 64 and obs_dim, state_dim >= 1";
+    if (capacity == 0 || capacity >= (1u << 24)) return "need 1 <= capacity < 2^24 (the sample count travels through a float)";
+    return nullptr;
+}
+
+int mrl_agent_update_workspace_bytes(uint32_t obs_dim, uint32_t state_dim, uint32_t num_actions, uint32_t capacity, uint64_t *out)
+{
+    const char *why = out ? agent_update_shape_error(obs_dim, state_dim, num_actions, capacity) : "need an output pointer";
+    if (why) {
+        mrl::set_error("mrl_agent_update_workspace_bytes: %s; got obs_dim %u, state_dim %u, num_actions %u, capacity %u", why, obs_dim,
+                       state_dim, num_actions, capacity);
+        return MRL_ERR_INVALID;
+    }
+    *out = mrl::update_workspace_bytes(capacity, mrl_wide_policy_num_params(obs_dim, state_dim, num_actions));
+    return MRL_OK;
+}
+
+int mrl_agent_update(const mrl_wide_policy *policy, const mrl_ppo_optimizer *opt, const mrl_agent_record *record, uint32_t obs_type,
+                     uint32_t state_type, const float *advantages, const float *returns, uint32_t epochs, const mrl_ppo_config *cfg,
+                     uint32_t capacity, void *workspace_dev, uint64_t workspace_bytes, float *stats_or_null, float *grads_or_null,
+                     int gpu_id, void *hip_stream)
+{
+    if (!policy || !opt || !record || !cfg || !advantages || !returns || !workspace_dev) {
+        mrl::set_error("mrl_agent_update: null policy, optimizer, record, configuration, advantages, returns or workspace");
+        return MRL_ERR_INVALID;
+    }
+    if (!opt->params_dev || !opt->exp_avg || !opt->exp_avg_sq || !record->obs || !record->states || !record->action_masks ||
+        !record->active || !record->actions || !record->logprobs || !record->values) {
+        mrl::set_error("mrl_agent_update: null parameter or moment array, or a record without obs, states, action_masks, active, "
+                       "actions, logprobs or values");
+        return MRL_ERR_INVALID;
+    }
+    const uint64_t cells = (uint64_t)record->num_steps * record->num_worlds;
+    if (cells >= (1u << 24)) {
+        mrl::set_error("mrl_agent_update: a record of %llu cells; the sample count travels through a float, so T N must stay below 2^24",
+                       (unsigned long long)cells);
+        return MRL_ERR_INVALID;
+    }
+    const char *why = agent_update_shape_error(policy->obs_dim, policy->state_dim, policy->num_actions, capacity);
+    if (why || capacity > cells) {
+        mrl::set_error("mrl_agent_update: %s; got obs_dim %u, state_dim %u, num_actions %u, capacity %u for a record of %llu cells",
+                       why ? why : "capacity must not exceed T N", policy->obs_dim, policy->state_dim, policy->num_actions, capacity,
+                       (unsigned long long)cells);
+        return MRL_ERR_INVALID;
+    }
+    if (cfg->flags & ~(uint32_t)(MRL_PPO_NORM_ADV | MRL_PPO_CLIP_VLOSS)) {
+        mrl::set_error("mrl_agent_update: unknown flag bits 0x%x", cfg->flags & ~(uint32_t)(MRL_PPO_NORM_ADV | MRL_PPO_CLIP_VLOSS));
+        return MRL_ERR_INVALID;
+    }
+    if (obs_type > MRL_UINT32 || state_type > MRL_UINT32) {
+        mrl::set_error("mrl_agent_update: element types must be MRL_INT8, MRL_UINT8, MRL_INT32, MRL_FLOAT32 or MRL_UINT32; got %u and %u",
+                       obs_type, state_type);
+        return MRL_ERR_INVALID;
+    }
+    uintptr_t floats = 0;
+    for (const void *p : {(const void *)opt->params_dev, (const void *)opt->exp_avg, (const void *)opt->exp_avg_sq,
+                          (const void *)record->logprobs, (const void *)record->values, (const void *)record->actions,
+                          (const void *)advantages, (const void *)returns, (const void *)stats_or_null, (const void *)grads_or_null})
+        floats |= reinterpret_cast<uintptr_t>(p);
+    if (obs_type != MRL_INT8 && obs_type != MRL_UINT8) floats |= reinterpret_cast<uintptr_t>(record->obs);
+    if (state_type != MRL_INT8 && state_type != MRL_UINT8) floats |= reinterpret_cast<uintptr_t>(record->states);
+    const uint64_t need_bytes = mrl::update_workspace_bytes(capacity, mrl_wide_policy_num_params(policy->obs_dim, policy->state_dim, policy->num_actions));
+    if (int rc = update_refusal("mrl_agent_update", "mrl_agent_update_workspace_bytes", workspace_bytes, need_bytes, workspace_dev,
+                                floats & 3u, "float and int32 arrays must start on a 4-byte boundary", hip_stream))
+        return rc;
+    if (epochs == 0) return MRL_OK;
+    mrl::AgentUpdateArgs args{};
+    args.policy = *policy, args.opt = *opt, args.record = *record, args.cfg = *cfg;
+    args.obs_type = obs_type, args.state_type = state_type;
+    args.advantages = advantages, args.returns = returns;
+    args.epochs = epochs, args.capacity = capacity;
+    args.workspace = workspace_dev, args.stats = stats_or_null, args.grads = grads_or_null;
+    mrl::DeviceGuard on(gpu_id);
+    return guarded([&] { mrl::launch_agent_update(args, (hipStream_t)hip_stream); });
 }
 
 uint64_t mrl_cnn_policy_num_params(uint32_t width, uint32_t height, uint32_t channels, uint32_t hidden, uint32_t num_actions)

@@ -18,6 +18,8 @@
 //   mrl_agent_head     a lane per computed world: mask, soft-max, draw, log-prob; three passes over the world's <= 64 logits in
 //                      the workspace instead of an array in registers (a dynamically indexed array would go to scratch).
 // No float atomics, no workgroup waits on another, no scratch: the same inputs give the same bits on every run.
+// The four layer launches are launch_wide_forward, which mrl_agent_update (wide_update.hip) also runs, over the record's rows:
+// the log-probs and values an update recomputes on unchanged parameters carry the record's bits.
 #include "wide_policy.hpp"
 #include "random_policy.hpp"
 
@@ -28,17 +30,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kTileRows = 32, kTileCols = 128, kChunk = 64, kLd = 66, kLayerThreads = 256;
 constexpr int kStageA = kTileRows * kChunk / kLayerThreads;  // 8 elements of the input tile per thread and chunk
 constexpr int kStageB = kTileCols * kChunk / kLayerThreads;  // 32 of the weight tile
-
-__device__ __forceinline__ float wide_load(const void *p, uint32_t type, int64_t at)
-{
-    switch (type) {
-    case MRL_INT8: return (float)static_cast<const int8_t *>(p)[at];
-    case MRL_UINT8: return (float)static_cast<const uint8_t *>(p)[at];
-    case MRL_INT32: return (float)static_cast<const int32_t *>(p)[at];
-    case MRL_UINT32: return (float)static_cast<const uint32_t *>(p)[at];
-    default: return static_cast<const float *>(p)[at];
-    }
-}
 
 __device__ __forceinline__ bool wide_nonzero(const WideInput &in, int64_t at)
 {
@@ -297,6 +288,47 @@ __global__ void __launch_bounds__(64) mrl_agent_head(HeadArgs a)
         for (int i = 0; i < A; i++) r.logits[(size_t)w * kWideMaxActions + i] = l[i];
 }
 
+void launch_wide_forward(const WideForwardArgs &g, hipStream_t stream)
+{
+    // critic: parameters from 0; actor: behind them
+    const uint64_t H = kWideHidden;
+    const float *net_params[2] = {g.params, g.params + wide_net_params(g.S, 1)};
+    const WideInput first_in[2] = {g.state, g.obs};
+    const uint32_t first_k[2] = {g.S, g.D}, last_out[2] = {1u, g.A};
+    const uint32_t row_tiles = (g.max_rows + kTileRows - 1) / kTileRows;
+    for (uint32_t layer = 0; layer < 4; layer++) {
+        WideLayerArgs la{};
+        la.rows = g.rows, la.count = g.count;
+        la.gather = layer == 0, la.relu = layer < 3;
+        for (uint32_t net = 0; net < g.nets; net++) {
+            WideLayerNet &n = la.net[net];
+            const float *p = net_params[net];
+            if (layer >= 1) p += (uint64_t)first_k[net] * H + H;
+            if (layer >= 2) p += H * H + H;
+            if (layer >= 3) p += H * H + H;
+            n.K = layer == 0 ? first_k[net] : kWideHidden;
+            n.out_dim = layer == 3 ? last_out[net] : kWideHidden;
+            n.weight = p;
+            n.bias = p + (uint64_t)n.out_dim * n.K;
+            if (layer == 0) {
+                n.in = first_in[net].data, n.in_row_stride = first_in[net].row_stride, n.in_type = first_in[net].type;
+            } else {
+                n.in = g.hidden[net][layer - 1], n.in_row_stride = (int64_t)H, n.in_type = MRL_FLOAT32;
+            }
+            if (layer < 3) {
+                n.out = g.hidden[net][layer], n.out_stride = kWideHidden;
+            } else if (net == 0) {
+                n.out = g.value, n.out_stride = 1;
+            } else {
+                n.out = g.logits, n.out_stride = kWideMaxActions;
+            }
+        }
+        const uint32_t slabs = layer == 3 ? 1u : kWideHidden / kTileCols;
+        hipLaunchKernelGGL(mrl_wide_layer, dim3(row_tiles, slabs, g.nets), dim3(kLayerThreads), 0, stream, la);
+    }
+    MRL_HIP(hipGetLastError());
+}
+
 void launch_agent_act(const AgentActArgs &g, hipStream_t stream)
 {
     const uint32_t N = g.num_worlds;
@@ -315,42 +347,14 @@ void launch_agent_act(const AgentActArgs &g, hipStream_t stream)
     const uint32_t book_blocks = (uint32_t)((copied + 255) / 256 < 2048 ? (copied + 255) / 256 : 2048);
     hipLaunchKernelGGL(mrl_agent_book, dim3(book_blocks), dim3(256), 0, stream, book);
 
-    // critic: parameters from 0; actor: behind them
-    const uint64_t H = kWideHidden;
-    const float *net_params[2] = {g.params, g.params + wide_net_params(g.S, 1)};
-    const WideInput first_in[2] = {g.state, g.obs};
-    const uint32_t first_k[2] = {g.S, g.D}, last_out[2] = {1u, g.A};
-    const uint32_t nets = value_only ? 1u : 2u, row_tiles = (N + kTileRows - 1) / kTileRows;
-    for (uint32_t layer = 0; layer < 4; layer++) {
-        WideLayerArgs la{};
-        la.rows = g.ws.rows, la.count = g.ws.count;
-        la.gather = layer == 0, la.relu = layer < 3;
-        for (uint32_t net = 0; net < nets; net++) {
-            WideLayerNet &n = la.net[net];
-            const float *p = net_params[net];
-            if (layer >= 1) p += (uint64_t)first_k[net] * H + H;
-            if (layer >= 2) p += H * H + H;
-            if (layer >= 3) p += H * H + H;
-            n.K = layer == 0 ? first_k[net] : kWideHidden;
-            n.out_dim = layer == 3 ? last_out[net] : kWideHidden;
-            n.weight = p;
-            n.bias = p + (uint64_t)n.out_dim * n.K;
-            if (layer == 0) {
-                n.in = first_in[net].data, n.in_row_stride = first_in[net].row_stride, n.in_type = first_in[net].type;
-            } else {
-                n.in = g.ws.hidden[(layer - 1) & 1u] + (uint64_t)net * N * H, n.in_row_stride = (int64_t)H, n.in_type = MRL_FLOAT32;
-            }
-            if (layer < 3) {
-                n.out = g.ws.hidden[layer & 1u] + (uint64_t)net * N * H, n.out_stride = kWideHidden;
-            } else if (net == 0) {
-                n.out = g.ws.value, n.out_stride = 1;
-            } else {
-                n.out = g.ws.logits, n.out_stride = kWideMaxActions;
-            }
-        }
-        const uint32_t slabs = layer == 3 ? 1u : kWideHidden / kTileCols;
-        hipLaunchKernelGGL(mrl_wide_layer, dim3(row_tiles, slabs, nets), dim3(kLayerThreads), 0, stream, la);
-    }
+    WideForwardArgs fwd{};
+    fwd.params = g.params, fwd.obs = g.obs, fwd.state = g.state;
+    fwd.D = g.D, fwd.S = g.S, fwd.A = g.A, fwd.max_rows = N, fwd.nets = value_only ? 1u : 2u;
+    fwd.rows = g.ws.rows, fwd.count = g.ws.count;
+    for (uint32_t net = 0; net < 2; net++)
+        for (uint32_t layer = 0; layer < 3; layer++) fwd.hidden[net][layer] = g.ws.hidden[layer & 1u] + (uint64_t)net * N * kWideHidden;
+    fwd.logits = g.ws.logits, fwd.value = g.ws.value;
+    launch_wide_forward(fwd, stream);
 
     HeadArgs head{};
     head.rows = g.ws.rows, head.count = g.ws.count, head.logits = g.ws.logits, head.value = g.ws.value;

@@ -49,6 +49,32 @@ struct WideInput {
     uint32_t type;       // MRL_INT8 ...
 };
 
+// an element of a simulator tensor or of a record row, converted on load
+__device__ __forceinline__ float wide_load(const void *p, uint32_t type, int64_t at)
+{
+    switch (type) {
+    case MRL_INT8: return (float)static_cast<const int8_t *>(p)[at];
+    case MRL_UINT8: return (float)static_cast<const uint8_t *>(p)[at];
+    case MRL_INT32: return (float)static_cast<const int32_t *>(p)[at];
+    case MRL_UINT32: return (float)static_cast<const uint32_t *>(p)[at];
+    default: return static_cast<const float *>(p)[at];
+    }
+}
+
+// The four mrl_wide_layer launches of one forward pass over the rows rows[0 .. *count): layer 1 gathers row rows[j] of `state`
+// (critic, net 0) and `obs` (actor, net 1), layer l writes hidden[net][l - 1], layer 4 writes value (j) and logits (j, 64).  The
+// grids are sized for max_rows; tiles past *count leave at once.  The act alternates between two buffers, so its hidden[net][2]
+// is its hidden[net][0]; the update (wide_update.hip) keeps all three, which its backward pass reads.
+struct WideForwardArgs {
+    const float *params;
+    WideInput obs, state;  // (rows, D), (rows, S)
+    uint32_t D, S, A, max_rows, nets;  // nets = 1: the critic alone
+    const uint32_t *rows, *count;
+    float *hidden[2][3];
+    float *logits, *value;
+};
+void launch_wide_forward(const WideForwardArgs &args, hipStream_t stream);
+
 struct AgentActArgs {
     const float *params;
     WideInput obs, state, mask;  // (N, D), (N, S), (N, A)

@@ -76,7 +76,12 @@ class CleanPPOAgent(VectorAgent):
     built twice, ego and partner, by scripts/hanabi_train.py and scripts/balance_train.py) with its collection phase on the
     device: ``get_action`` is ``mrl_agent_act`` on the simulator's own tensors, ``update`` is ``mrl_agent_credit``, and the
     advantages at the update boundary are ``mrl_gae_active`` -- no host synchronisation per step.  The learning phase is the
-    reference's, in torch autograd, on ``policy.module()``, whose parameters are views of the flat tensor the kernels read.
+    reference's, in torch autograd, on ``policy.module()``, whose parameters are views of the flat tensor the kernels read --
+    or, after ``agent.device_update = True`` (extension; an attribute and not a constructor argument, because the constructor
+    keeps the reference's signature), ``mrl_agent_update``: the epochs run on the device over the record as it stands (no
+    boolean-mask indexing, no float copies of the rows), ``optimizer`` is a ``simulators.WideOptimizer`` and the update waits
+    for the device once, to read the losses (once per epoch with ``target_kl``, the reference's own host read).  Assign it
+    before the first update: the assignment builds a new optimizer, whose moments start at zero.
 
     Constructor arguments and defaults are the reference's; ``seed`` (extension) seeds the action draws and defaults to a value
     derived from ``name``.  ``envs`` must be a ``MadronaEnv`` over a Hanabi or balance-beam simulator on the GPU (checked at the
@@ -119,6 +124,7 @@ class CleanPPOAgent(VectorAgent):
         self.policy = WidePolicy.from_module(WideAgent(obs_dim, state_dim, envs.action_space.n, orthogonal=True), device=self.device)
         self.agent = self.policy.module()
         self.optimizer = torch.optim.Adam(self.agent.parameters(), lr=self.lr, eps=1e-5)
+        self._device_update = False
 
         self._obs_dim, self._state_dim = obs_dim, state_dim
         self._sim = self.record = None  # bound at the first get_action / update, where an unsupported env is refused
@@ -128,6 +134,22 @@ class CleanPPOAgent(VectorAgent):
         self.start_time = time.time()
         self.episode_stats = {"episodes": 0, "mean": float("nan"), "min": float("nan"), "max": float("nan")}
         self.last_losses = {}
+
+    @property
+    def device_update(self):
+        """Whether the epochs run on the device (``mrl_agent_update``) and ``optimizer`` is a ``WideOptimizer``; False: torch's."""
+        return self._device_update
+
+    @device_update.setter
+    def device_update(self, on):
+        from ..simulators import WideOptimizer
+        if bool(on) == self._device_update:
+            return
+        self._device_update = bool(on)
+        if self._device_update:
+            self.optimizer = WideOptimizer(self.policy, lr=self.lr, eps=1e-5)
+        else:
+            self.optimizer = torch.optim.Adam(self.agent.parameters(), lr=self.lr, eps=1e-5)
 
     def _attach(self):
         self._sim = self._check_env()
@@ -180,16 +202,26 @@ class CleanPPOAgent(VectorAgent):
         return self.envs.static_actions[self.seat]
 
     def _learn(self):
-        """The update boundary: bootstrap value, advantages (both on the device), then the reference's epochs (:268-330)."""
-        import numpy as np
-
+        """The update boundary: bootstrap value, advantages (both on the device), then the epochs."""
         from ..simulators import agent_act, gae_active
         r = self.record
         if self.anneal_lr:
-            self.optimizer.param_groups[0]["lr"] = (1.0 - (self.updates - 1.0) / self.num_updates) * self.lr
+            lrnow = (1.0 - (self.updates - 1.0) / self.num_updates) * self.lr
+            if self.device_update:
+                self.optimizer.lr = lrnow
+            else:
+                self.optimizer.param_groups[0]["lr"] = lrnow
         agent_act(self._sim, self.seat, self.policy, r, value_only=True)
         advantages, returns = gae_active(r, self.gamma, self.gae_lambda)
+        if self.device_update:
+            self._learn_device(advantages, returns)
+        else:
+            self._learn_torch(advantages, returns)
 
+    def _learn_torch(self, advantages, returns):
+        """The reference's epochs (:268-330) in torch autograd on the module whose parameters alias ``policy.params``."""
+        import numpy as np
+        r = self.record
         active = r.active.bool()
         b_obs, b_states = r.obs[active].float(), r.states[active].float()
         b_masks, b_actions = r.action_masks[active].bool(), r.actions[active].long()
@@ -241,6 +273,53 @@ class CleanPPOAgent(VectorAgent):
             "explained_variance": float("nan") if var_y == 0 else float(1 - np.var(y_true - y_pred) / var_y),
             "learning_rate": self.optimizer.param_groups[0]["lr"], "samples": size,
         }
+        self._log_update(episodes, total, low, high)
+
+    def _learn_device(self, advantages, returns):
+        """The epochs as ``mrl_agent_update`` and the update's one host read: the stats rows, the explained variance's three
+        sums over the (T, N) arrays and the episode totals travel in one tensor."""
+        from .. import _lib
+        from ..simulators import agent_update
+        r, opt = self.record, self.optimizer
+        terms = dict(clip_coef=self.clip_coef, ent_coef=self.ent_coef, vf_coef=self.vf_coef, max_grad_norm=self.max_grad_norm,
+                     norm_adv=self.norm_adv, clip_vloss=self.clip_vloss)
+        col = {name: i for i, name in enumerate(_lib.AGENT_UPDATE_STATS)}
+        if self.target_kl is None:
+            rows = agent_update(self.policy, opt, r, advantages, returns, epochs=self.update_epochs, **terms).stats
+        else:
+            each = []
+            for _ in range(self.update_epochs):
+                each.append(agent_update(self.policy, opt, r, advantages, returns, epochs=1, **terms).stats)
+                status, approx_kl = (float(x) for x in each[-1][0, [col["status"], col["approx_kl"]]].cpu())
+                if status != 0 or approx_kl > self.target_kl:
+                    break
+            rows = torch.cat(each)
+        # np.var(y_true) and np.var(y_true - y_pred) over the active cells, as masked sums on the device
+        w = r.active.double()
+        n = w.sum()
+        y_true, diff = returns.double(), returns.double() - r.values.double()
+        var = [(((y - (y * w).sum() / n) ** 2) * w).sum() / n for y in (y_true, diff)]
+        packed = torch.cat([rows.double().reshape(-1), torch.stack([n] + var), r.totals.reshape(-1)]).cpu()
+        rows = packed[:rows.numel()].reshape(rows.shape)
+        size, var_y, var_diff = (float(x) for x in packed[rows.numel():rows.numel() + 3])
+        totals = packed[rows.numel() + 3:].reshape(r.totals.shape)
+        episodes, total, low, high = int(totals[:, 0].sum()), float(totals[:, 1].sum()), float(totals[:, 2].min()), float(totals[:, 3].max())
+        r.clear_totals()
+        if episodes:
+            self.episode_stats = {"episodes": episodes, "mean": total / episodes, "min": low, "max": high}
+        done = rows[rows[:, col["status"]] == 0]
+        opt.step -= len(rows) - len(done)  # agent_update counted every epoch; those with a status took no step
+        last = done[-1] if len(done) else torch.zeros(len(col), dtype=torch.float64)
+        self.last_losses = {
+            "value_loss": float(last[col["v_loss"]]), "policy_loss": float(last[col["pg_loss"]]), "entropy": float(last[col["entropy"]]),
+            "old_approx_kl": float(last[col["old_approx_kl"]]), "approx_kl": float(last[col["approx_kl"]]),
+            "clipfrac": float(done[:, col["clipfrac"]].mean()) if len(done) else 0.0,
+            "explained_variance": float("nan") if size == 0 or var_y == 0 else float(1 - var_diff / var_y),
+            "learning_rate": opt.lr, "samples": int(size),
+        }
+        self._log_update(episodes, total, low, high)
+
+    def _log_update(self, episodes, total, low, high):
         if self.writer is not None:
             import time
             if episodes:

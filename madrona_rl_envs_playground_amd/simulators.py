@@ -653,7 +653,9 @@ class _AdamState:
 
     def workspace(self, minibatch_size, num_minibatches):
         """A uint8 tensor of at least ``workspace_bytes`` on the parameters' device: the cached one while it is large enough."""
-        need = self.workspace_bytes(minibatch_size, num_minibatches)
+        return self._cached_workspace(self.workspace_bytes(minibatch_size, num_minibatches))
+
+    def _cached_workspace(self, need):
         if self._workspace is None or self._workspace.numel() < need or self._workspace.device != self.policy.params.device:
             self._workspace = torch.empty(need, dtype=torch.uint8, device=self.policy.params.device)
         return self._workspace
@@ -757,6 +759,87 @@ def ppo_update(policy, optimizer, rollout, advantages, returns, indices, clip_co
                          optimizer.eps, (_lib.PPO_NORM_ADV if norm_adv else 0) | (_lib.PPO_CLIP_VLOSS if clip_vloss else 0))
     return _run_update(_lib.lib().mrl_ppo_update, (ctypes.byref(shape), ctypes.byref(opt), ctypes.byref(batch)), indices,
                        (ctypes.byref(cfg),), optimizer, len(_lib.PPO_STATS), PpoResult, stats, grads)
+
+
+class WideOptimizer(_AdamState):
+    """Adam's state for ``agent_update`` (``torch.optim.Adam(lr, betas, eps)`` without amsgrad or weight decay, as the reference's
+    ``CleanPPOAgent`` builds it, pantheonrl_extension/vectoragent.py:170) over a ``WidePolicy``'s flat parameters: the two
+    moments, the number of steps taken and the cached scratch of ``mrl_agent_update``.  ``lr`` is an ordinary attribute:
+    assign to it to anneal (:225-228)."""
+
+    def __init__(self, policy, lr=2.5e-4, betas=(0.9, 0.999), eps=1e-5):
+        if not isinstance(policy, WidePolicy):
+            raise ValueError("policy must be a WidePolicy")
+        super().__init__(policy, betas, eps)
+        self.lr = float(lr)
+
+    def workspace_bytes(self, capacity):
+        """``mrl_agent_update_workspace_bytes`` for this policy's shape and ``capacity`` samples."""
+        p = self.policy
+        out = ctypes.c_uint64(0)
+        _lib.check(_lib.lib().mrl_agent_update_workspace_bytes(p.obs_dim, p.state_dim, p.num_actions, int(capacity), ctypes.byref(out)))
+        return int(out.value)
+
+    def workspace(self, capacity):
+        """The cached scratch, grown to ``workspace_bytes(capacity)`` where it is smaller."""
+        return self._cached_workspace(self.workspace_bytes(capacity))
+
+
+_WIDE_TYPES = {torch.int8: _lib.MRL_INT8, torch.uint8: _lib.MRL_UINT8, torch.int32: _lib.MRL_INT32, torch.float32: _lib.MRL_FLOAT32}
+
+
+def agent_update(policy, optimizer, record, advantages=None, returns=None, epochs=1, clip_coef=0.2, ent_coef=0.01, vf_coef=0.5,
+                 max_grad_norm=0.5, norm_adv=True, clip_vloss=True, capacity=None, stats=True, grads=False):
+    """``epochs`` whole-batch epochs of the reference's ``CleanPPOAgent`` update (pantheonrl_extension/vectoragent.py:283-323) on
+    the active cells of ``record`` (an ``AgentRecord``), on the device (``mrl_agent_update``), enqueued on torch's current
+    stream; it does not wait.  ``policy.params`` is updated in place.  ``advantages`` / ``returns``: (T, N) float32, default the
+    record's own (what ``gae_active`` filled).  ``capacity``: the largest number of samples the scratch is sized for, default
+    T * N; a batch with more active cells changes nothing and reports status 2, one with fewer than two status 1.  Returns
+    ``PpoResult(stats, grads)``: (epochs, 10) float32 in the order of ``_lib.AGENT_UPDATE_STATS`` and (epochs, P) unclipped
+    gradients, each None unless asked for.
+
+    ``optimizer.step`` grows by ``epochs`` in every call: learning whether the epochs ran (status 0) would take a host read, and
+    this function never waits.  A caller that reads the stats and finds a status other than 0 takes the epochs off again, as
+    ``CleanPPOAgent`` does."""
+    if not isinstance(policy, WidePolicy) or not isinstance(optimizer, WideOptimizer) or optimizer.policy is not policy:
+        raise ValueError("policy must be a WidePolicy and optimizer the WideOptimizer made for it")
+    if not isinstance(record, AgentRecord):
+        raise ValueError("record must be an AgentRecord")
+    p = policy.params
+    if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+        raise ValueError("policy.params must be a contiguous float32 tensor on a GPU")
+    advantages = record.advantages if advantages is None else advantages
+    returns = record.returns if returns is None else returns
+    device, f32 = p.device, torch.float32
+    cells = record.num_steps * record.num_worlds
+    if record.obs.dtype not in _WIDE_TYPES or record.states.dtype not in _WIDE_TYPES:
+        raise ValueError("record.obs / record.states must be int8, uint8, int32 or float32")
+    wanted = (("policy.params", p, f32, policy.num_params), ("optimizer.exp_avg", optimizer.exp_avg, f32, p.numel()),
+              ("optimizer.exp_avg_sq", optimizer.exp_avg_sq, f32, p.numel()),
+              ("record.obs", record.obs, record.obs.dtype, cells * policy.obs_dim),
+              ("record.states", record.states, record.states.dtype, cells * policy.state_dim),
+              ("record.action_masks", record.action_masks, torch.uint8, cells * policy.num_actions),
+              ("record.active", record.active, torch.uint8, cells), ("record.actions", record.actions, torch.int32, cells),
+              ("record.logprobs", record.logprobs, f32, cells), ("record.values", record.values, f32, cells),
+              ("advantages", advantages, f32, cells), ("returns", returns, f32, cells))
+    _require_tensors(wanted, device)
+    epochs = int(epochs)
+    capacity = cells if capacity is None else int(capacity)
+    workspace = optimizer.workspace(capacity)
+    out_stats = torch.empty((epochs, len(_lib.AGENT_UPDATE_STATS)), dtype=f32, device=device) if stats else None
+    out_grads = torch.empty((epochs, p.numel()), dtype=f32, device=device) if grads else None
+    desc = policy.desc()
+    opt = _lib.PpoOptimizerDesc(p.data_ptr(), optimizer.exp_avg.data_ptr(), optimizer.exp_avg_sq.data_ptr(), optimizer.step)
+    cfg = _lib.PpoConfig(clip_coef, ent_coef, vf_coef, max_grad_norm, optimizer.lr, optimizer.betas[0], optimizer.betas[1],
+                         optimizer.eps, (_lib.PPO_NORM_ADV if norm_adv else 0) | (_lib.PPO_CLIP_VLOSS if clip_vloss else 0))
+    gpu = device.index
+    _lib.check(_lib.lib().mrl_agent_update(ctypes.byref(desc), ctypes.byref(opt), ctypes.byref(record.struct),
+                                           _WIDE_TYPES[record.obs.dtype], _WIDE_TYPES[record.states.dtype], advantages.data_ptr(),
+                                           returns.data_ptr(), epochs, ctypes.byref(cfg), capacity, workspace.data_ptr(),
+                                           workspace.numel(), out_stats.data_ptr() if stats else None,
+                                           out_grads.data_ptr() if grads else None, gpu, _stream_ptr(gpu)))
+    optimizer.step += epochs
+    return PpoResult(out_stats, out_grads)
 
 
 class ValueNorm:

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """The loop of the reference's scripts/hanabi_train.py and scripts/balance_train.py -- two ``CleanPPOAgent``s, ego and partner,
 around ``env.step`` -- on this engine's calls: every ``get_action`` is ``mrl_agent_act`` on the simulator's tensors, every
-``update`` is ``mrl_agent_credit``, the advantages at an update boundary are ``mrl_gae_active``; the learning phase is torch's.
+``update`` is ``mrl_agent_credit``, the advantages at an update boundary are ``mrl_gae_active``; the learning phase is torch's,
+or with ``--device-update`` ``mrl_agent_update``.
 
     python tools/hanabi_train_device.py --game hanabi --config very_small --num-updates 20
-    python tools/hanabi_train_device.py --game balance
+    python tools/hanabi_train_device.py --game balance --device-update
 
 Hyper-parameter defaults are the two scripts' own (Hanabi: 1000 worlds, T = 128, lr 6.25e-5, gamma 0.999, clip 0.05; balance
 beam: 120 worlds, T = 60, lr 2.5e-4, gamma 0.99, clip 0.2; one minibatch, four epochs).  Prints one line per update: episodes
@@ -30,6 +31,7 @@ def main():
     parser.add_argument("--num-steps", type=int)
     parser.add_argument("--learning-rate", type=float)
     parser.add_argument("--seed", type=int, default=1)
+    parser.add_argument("--device-update", action="store_true", help="run the epochs on the device (mrl_agent_update), not in torch")
     parser.add_argument("--tensorboard", action="store_true", help="log to runs/ (if tensorboard is importable)")
     args = parser.parse_args()
 
@@ -52,6 +54,7 @@ def main():
                   num_minibatches=1, update_epochs=4, **hp)
     ego = CleanPPOAgent(envs=env, name=name + "_ego", seed=2 * args.seed, **common)
     partner = CleanPPOAgent(envs=env.getDummyEnv(1), name=name + "_partner", seed=2 * args.seed + 1, **common)
+    ego.device_update = partner.device_update = args.device_update
     env.add_partner_agent(partner)
 
     obs = env.reset()
