@@ -153,7 +153,11 @@ int mrl_overcooked_create(const mrl_overcooked_config *cfg, int gpu_id, uint32_t
  * TOMATO_SOURCE (sim.hpp:40); height*width <= 100 and num_players <= 2 (sim.hpp:12-13); rows are
  * F = 5P + 10 bytes (sim.hpp:121-123), so OBSERVATION is int8 (P*C, N, 5P+10) and OBS_WORLD_MAJOR
  * (N, P, H, W, 5P+10); dish_pickup_rew is paid (sim.cpp:241-246).  Slots: the MRL_OVERCOOKED_* ids
- * (ExportID is the same list, sim.hpp:22-37) plus STATE_DISHES_OUT int32 (N) = WorldState.num_dishes_out. */
+ * (ExportID is the same list, sim.hpp:22-37) plus STATE_DISHES_OUT int32 (N) = WorldState.num_dishes_out.
+ * mrl_cnn_act and mrl_rollout_cnn take a Simplecooked simulator as they take an Overcooked one -- they read OBS_WORLD_MAJOR, DONE,
+ * REWARD and ACTION under those same MRL_OVERCOOKED_* ids --, with one or two players: F = 5P + 10 is 15 or 20 channels, and the
+ * ring of mrl_rollout_cnn is what mrl_mappo_update reads.  This is the reference's own training configuration (MAPPO's CNN
+ * actor-critic on layout `simple`). */
 enum { MRL_SIMPLECOOKED_STATE_DISHES_OUT = 14 };
 int mrl_simplecooked_create(const mrl_overcooked_config *cfg, int gpu_id, uint32_t num_worlds, mrl_sim **out);
 
@@ -797,14 +801,14 @@ int mrl_agent_update(const mrl_wide_policy *policy, const mrl_ppo_optimizer *opt
                      uint32_t epochs, const mrl_ppo_config *cfg, uint32_t capacity, void *workspace_dev, uint64_t workspace_bytes,
                      float *stats_or_null /* (epochs, 10) */, float *grads_or_null /* (epochs, P) */, int gpu_id, void *hip_stream);
 
-/* MAPPO's CNN actor-critic for Overcooked on the device: what the reference's rollout loop runs in torch around every step
+/* MAPPO's CNN actor-critic for the two kitchens, Overcooked and Simplecooked, on the device: what the reference's rollout loop runs in torch around every step
  * (train/MAPPO/main_player.py:211-261) -- for each seat an int8 -> float cast, a movedim, Conv2d, three Linear layers and a
  * Categorical, twice (actor and critic: train/MAPPO/utils/cnn.py:26-42, r_actor_critic.py, utils/distributions.py:55-68, hidden_size
  * 64 as the reference's Overcooked notebook sets it) -- as ONE launch per act, mrl_cnn_act, and a whole T-step collection as one
  * call, mrl_rollout_cnn.  No reference counterpart as calls.  DESIGN.md section 15.
- *   Networks, for a W x H kitchen with F = 5P + 16 channels and npos = (W - 2)(H - 2): Conv2d(F, 32, 3 x 3, valid), ReLU, flatten,
- *     Linear(32 npos, 64), ReLU, Linear(64, 64), ReLU, then Linear(64, 6) (actor) or Linear(64, 1) (critic).  For Overcooked the
- *     critic's input IS the seat's observation (share_observation_space = observation_space) and there is no action mask.
+ *   Networks, for a W x H kitchen with F channels (Overcooked: 5P + 16; Simplecooked: 5P + 10, P = 1 or 2) and npos = (W - 2)(H - 2): Conv2d(F, 32, 3 x 3, valid), ReLU, flatten,
+ *     Linear(32 npos, 64), ReLU, Linear(64, 64), ReLU, then Linear(64, 6) (actor) or Linear(64, 1) (critic).  In both kitchens the
+ *     critic's input IS the seat's observation (share_observation_space = observation_space) and no action is masked (Simplecooked's mask is all ones).
  *     params_dev is one flat float32 device array: the actor's eight tensors, then the critic's eight, each in
  *     parameters_to_vector order -- conv weight (32, F, 3, 3) and bias, fc1 weight (64, 32 npos) and bias, fc2 weight and bias, head
  *     weight and bias; mrl_cnn_policy_num_params(W, H, F, hidden, A) floats (0 for hidden != 64 or A != 6 or W, H < 3).  It is read
@@ -819,7 +823,7 @@ int mrl_agent_update(const mrl_wide_policy *policy, const mrl_ppo_optimizer *opt
  *     and fc1's input index is c (W - 2)(H - 2) + ow (H - 2) + oh.
  *   Arithmetic: mrl_agent_act's rule.  Every product runs on v_mfma_f32_32x32x2_f32 in exact float32; an output starts from 0 and
  *     adds its products with one fused multiply-add each in ascending order of torch's flattened weight index (conv: k = 9 f + 3 i +
- *     j; the linear layers: their input index; an odd K is padded with one zero product); the bias is added to the finished sum.
+ *     j; the linear layers: their input index; an odd K -- the convolution's 9 F for an odd F, as one-player Simplecooked's 15 -- is padded with one zero product); the bias is added to the finished sum.
  *     No float atomics, no order that depends on timing: the same inputs give the same bits on every run and on any stream.
  *   Head, float32, A = 6: mrl_policy_act's rule above with the seat as the hash's player -- h = the hash of (seed, step, n, p);
  *     u = (h >> 8) * 2^-24; m = max logit; e_a = exp(l_a - m); p_a = e_a / sum e; action = the number of a in 0..4 with u >= p_0 +
@@ -836,13 +840,14 @@ int mrl_agent_update(const mrl_wide_policy *policy, const mrl_ppo_optimizer *opt
  *   workspace: mrl_cnn_workspace_bytes(num_worlds, num_players) bytes of device memory on a 16-byte boundary, the caller's.  The
  *     fused kernel keeps every intermediate in LDS and does not touch it today; the amount is fixed (256 bytes) and is part of
  *     the call so that a later, larger tile need not change the ABI.
- *   Launches: one -- a workgroup of four wavefronts per (tile of 32 samples, net).  The call only enqueues on hip_stream; it never
+ *   Launches: one -- a workgroup of four wavefronts per (tile of 32 samples, net); with one seat (P = 1, or one bit in `players`) a
+ *     tile is 32 worlds.  The call only enqueues on hip_stream; it never
  *     synchronises or allocates.
  *   Limit: the workgroup's LDS image -- 32 observation rows of H W F bytes (+ 3, rounded up to an odd number of dwords), the conv
  *     weights (32 rows of 9 F floats, padded to an odd count), 2 bytes per k, and the convolution's output, 32 rows of 32 npos + 1
- *     floats -- must fit 160 KiB.  The five standard two-player layouts do (9 x 5: 154 464 bytes; 5 x 4: 72 032); a larger kitchen or
+ *     floats -- must fit 160 KiB.  The five standard two-player layouts do (Overcooked 9 x 5: 154 464 bytes; 5 x 4: 72 032; Simplecooked's rows are shorter); a larger kitchen or
  *     more players than that allows is refused, never computed wrongly.
- *   MRL_ERR_INVALID: a simulator that is not Overcooked; hidden != 64; players == 0 or a bit >= P; a NULL policy, parameter array
+ *   MRL_ERR_INVALID: a simulator that is neither Overcooked nor Simplecooked; hidden != 64; players == 0 or a bit >= P; a NULL policy, parameter array
  *     or workspace, or a NULL buffer but logits in a record; row >= T without MRL_CNN_VALUE_ONLY, row != T with it, or it without a
  *     record; workspace_bytes below mrl_cnn_workspace_bytes or a workspace off a 16-byte boundary; a shape beyond the limit; a
  *     capturing stream (row and step travel in kernel arguments, as for the sibling calls); a flag bit other than
@@ -855,7 +860,7 @@ int mrl_agent_update(const mrl_wide_policy *policy, const mrl_ppo_optimizer *opt
  *   slot T is copied to where that output's most recent step wrote (one more device-to-device copy, T > 0): the simulator,
  *   its observations included, is exactly where T mrl_step_with_actions calls with actions[0..T-1] would have left it, and the
  *   next mrl_cnn_act or mrl_rollout_cnn reads the observations of the state it acts on -- two rollouts of T equal one of 2 T.  Seats outside `players`
- *   step with whatever their ACTION rows hold.  A ring whose slots do not start on 16-byte boundaries is staged as
+ *   step with whatever their ACTION rows hold.  Simplecooked: the same call, P = 1 included.  A ring whose slots do not start on 16-byte boundaries is staged as
  *   mrl_set_observation_ring says.  It takes no workspace (its acts need none).  Refusals: those of mrl_cnn_act, a NULL record or ring. */
 enum { MRL_CNN_VALUE_ONLY = 4 }; /* flag of mrl_cnn_act, beside MRL_POLICY_GREEDY */
 typedef struct mrl_cnn_policy {
@@ -881,7 +886,8 @@ int mrl_rollout_cnn(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy
 /* MAPPO's update for that actor-critic on the device: R_MAPPO.ppo_update (train/MAPPO/r_mappo.py:91-164, feed-forward networks, all
  * active masks one) with ValueNorm (utils/valuenorm.py) -- gather, both forward passes, the clipped losses, backward, two
  * clip_grad_norm_ and two Adam steps -- on the flat parameter array mrl_cnn_act reads, which is updated in place.  No reference
- * counterpart as a call.  DESIGN.md section 16.
+ * counterpart as a call.  DESIGN.md section 16.  The call sees no simulator: width, height and channels are the policy's, so a
+ * Simplecooked ring (channels = 5P + 10, P = 1 or 2) runs as an Overcooked one does.
  *   Samples: s = (t N + n) P + p is row t, world n, seat p of an mrl_cnn_record; its observation is the H W F bytes at s H W F of
  *     batch->obs (the ring mrl_rollout_cnn filled: slot t is what the act of step t saw), read as int8 and converted on load.
  *   One call is K = num_minibatches steps in row order; row k takes the B = minibatch_size samples indices[k, :].  An index >= S

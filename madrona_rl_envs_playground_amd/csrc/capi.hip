@@ -997,8 +997,10 @@ static int cnn_prepare(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *pol
                        const char *what, mrl::CnnActArgs *args)
 {
     if (int rc = mrl::need_healthy(sim)) return rc;
-    if (sim->game != MRL_GAME_OVERCOOKED) {
-        mrl::set_error("%s: game %d has no CNN policy (Overcooked does)", what, sim->game);
+    // the two kitchens export the same slab, flags and slot ids (Simplecooked's ExportID is Overcooked's list); the kernels take
+    // W, H, F and P at run time, so F = 5P + 10 and P = 1 need nothing of their own
+    if (sim->game != MRL_GAME_OVERCOOKED && sim->game != MRL_GAME_SIMPLECOOKED) {
+        mrl::set_error("%s: game %d has no CNN policy (Overcooked and Simplecooked do)", what, sim->game);
         return MRL_ERR_INVALID;
     }
     if (sim->exchange.mine) {

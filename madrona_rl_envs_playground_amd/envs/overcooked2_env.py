@@ -4,7 +4,8 @@
 Same constructor (horizon defaults to 200 here), attributes (``static_actions``, ``static_observations``,
 ``static_action_mask``, ``sim`` ...) and return shapes: ``get_obs`` gives, per player, an ``(N, W, H, 5P+10)``
 int8 view plus the all-ones ``(N, 6)`` action mask the reference attaches (overcooked2_env.py:55,96-99).  As in
-``overcooked_env.py`` here, the HIP kernel writes a world-major ``(N, P, H, W, F)`` block, so no scatter runs.
+``overcooked_env.py`` here, the HIP kernel writes a world-major ``(N, P, H, W, F)`` block, so no scatter runs.  ``act`` and
+``rollout`` (extensions) are those of ``overcooked_env.OvercookedMadrona``: MAPPO's CNN policy on the device, one or two players.
 """
 import numpy as np
 import torch
@@ -12,13 +13,13 @@ import torch
 from ..layouts import get_simplecooked_layout_params as get_base_layout_params  # noqa: F401  (reference name)
 from ..pantheonrl_extension.vectorenv import VectorMultiAgentEnv
 from ..pantheonrl_extension.vectorobservation import VectorObservation
-from ..simulators import ExecMode, RecordsEpisodeStatistics, SimplecookedSimulator
+from ..simulators import ActsWithCnnPolicy, ExecMode, RecordsEpisodeStatistics, SimplecookedSimulator
 from ..spaces import Discrete, MultiBinary
 
 NUM_ACTIONS = 6  # oldercooked_ai_py Action.ALL_ACTIONS
 
 
-class OvercookedMadrona(RecordsEpisodeStatistics, VectorMultiAgentEnv):
+class OvercookedMadrona(ActsWithCnnPolicy, RecordsEpisodeStatistics, VectorMultiAgentEnv):
 
     def __init__(self, layout_name, num_envs, gpu_id, debug_compile=True, use_cpu=False, use_env_cpu=False,
                  ego_agent_idx=0, horizon=200, num_players=None, record_episode_statistics=False):
@@ -111,6 +112,9 @@ class OvercookedMadrona(RecordsEpisodeStatistics, VectorMultiAgentEnv):
         if self._resident:
             return obs, self.static_rewards, self.static_dones, self.infos
         return obs, self.to_torch(self.static_rewards), self.to_torch(self.static_dones), self.infos
+
+    # act(policy, ...) and rollout(policy, num_steps, ...): simulators.ActsWithCnnPolicy, shared with envs/overcooked_env.py -- the
+    # reference's own training configuration (MAPPO's CNN actor-critic on this world) without the host in the loop
 
     def n_reset(self, worlds=None):
         """Like the reference (overcooked2_env.py:111-112) ``n_reset()`` restarts nothing: worlds restart themselves at

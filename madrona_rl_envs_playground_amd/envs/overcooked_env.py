@@ -13,13 +13,13 @@ import torch
 from ..layouts import get_base_layout_params  # noqa: F401  (re-export, reference location)
 from ..pantheonrl_extension.vectorenv import VectorMultiAgentEnv
 from ..pantheonrl_extension.vectorobservation import VectorObservation
-from ..simulators import ExecMode, OvercookedSimulator, RecordsEpisodeStatistics
+from ..simulators import ActsWithCnnPolicy, ExecMode, OvercookedSimulator, RecordsEpisodeStatistics
 from ..spaces import Discrete, MultiBinary
 
 NUM_ACTIONS = 6  # overcooked_ai_py Action.NUM_ACTIONS
 
 
-class OvercookedMadrona(RecordsEpisodeStatistics, VectorMultiAgentEnv):
+class OvercookedMadrona(ActsWithCnnPolicy, RecordsEpisodeStatistics, VectorMultiAgentEnv):
 
     def __init__(self, layout_name, num_envs, gpu_id, debug_compile=True, use_cpu=False, use_env_cpu=False,
                  ego_agent_idx=0, horizon=400, num_players=None, record_episode_statistics=False):
@@ -114,30 +114,7 @@ class OvercookedMadrona(RecordsEpisodeStatistics, VectorMultiAgentEnv):
             return obs, self.static_rewards, self.static_dones, self.infos
         return obs, self.to_torch(self.static_rewards), self.to_torch(self.static_dones), self.infos
 
-    def act(self, policy, players=None, record=None, row=0, seed=0, step=0, greedy=False):
-        """The seats in ``players`` (default all) act under ``policy`` (a ``simulators.CnnPolicy``) on the device, one launch
-        (``mrl_cnn_act``): the actions are in ``static_actions``, which is returned; with ``record`` (a ``CnnRecord``) row ``row``
-        also takes log-probs, values and the bookkeeping.  The observations read are those of the most recent step, also where
-        ``n_step(out=...)`` sent them."""
-        from ..simulators import cnn_act
-        cnn_act(self.sim, policy, players, record, row=row, seed=seed, step=step, greedy=greedy)
-        return self.static_actions
-
-    def rollout(self, policy, num_steps, seed=0, first_step=0, players=None, record=None, ring=None, greedy=False):
-        """``num_steps`` steps under ``policy`` without the host in the loop (``mrl_rollout_cnn``) -> (record, ring): a ``CnnRecord``
-        and the observation ring (T + 1, N, P, H, W, F) whose slot k is what the act of step k saw.  ``record`` / ``ring``: an
-        earlier call's, filled again.  Afterwards the observations of the state reached (slot T) are also where the simulator's output
-        pointed before the call -- ``static_world_major_observations`` unless ``n_step(out=...)`` redirected it -- so rollouts chain.  ``simulators.gae(record.rollout(), gamma, gae_lambda)`` gives the advantages."""
-        from ..simulators import CnnRecord
-        device = self.static_actions.device
-        if record is None:
-            record = CnnRecord(num_steps, self.num_envs, self.num_players, device)
-        if record.num_steps != int(num_steps):
-            raise ValueError(f"record holds {record.num_steps} steps, asked for {num_steps}")
-        if ring is None:
-            ring = torch.empty((int(num_steps) + 1,) + tuple(self.static_world_major_observations.shape), dtype=torch.int8, device=device)
-        self.sim.rollout_cnn(policy, record, ring, players=players, seed=seed, first_step=first_step, greedy=greedy)
-        return record, ring
+    # act(policy, ...) and rollout(policy, num_steps, ...): simulators.ActsWithCnnPolicy, shared with envs/overcooked2_env.py
 
     def n_reset(self, worlds=None):
         """Like the reference (overcooked_env.py:115-116) ``n_reset()`` does not restart

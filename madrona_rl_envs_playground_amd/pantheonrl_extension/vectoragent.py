@@ -31,11 +31,12 @@ class RandomVectorAgent(VectorAgent):
 
 
 class CnnPolicyAgent(VectorAgent):
-    """A player of ``OvercookedMadrona`` that acts under MAPPO's CNN policy on the device: ``get_action`` is ``mrl_cnn_act`` for this
+    """A player of either kitchen env (``envs.overcooked_env.OvercookedMadrona`` or the Simplecooked one of
+    ``envs.overcooked2_env``) that acts under MAPPO's CNN policy on the device: ``get_action`` is ``mrl_cnn_act`` for this
     agent's seat -- ``player_num``, set by ``env.add_partner_agent``, or, while that is ``None``, the env's ``ego_ind`` -- on the
     simulator's own observations, and returns the view ``env.static_actions[seat]``.  ``policy``: a ``simulators.CnnPolicy``;
-    ``seed`` seeds the draws, whose step number counts this agent's calls.  ``update`` does nothing.  Any env other than an
-    ``OvercookedMadrona`` on the GPU is refused with a ``TypeError`` by the constructor: there is no torch fallback.  ``obs`` and
+    ``seed`` seeds the draws, whose step number counts this agent's calls.  ``update`` does nothing.  Any env other than one of
+    those two on the GPU is refused with a ``TypeError`` by the constructor: there is no torch fallback.  ``obs`` and
     ``record`` of ``get_action`` are the ``VectorAgent`` protocol's; the kernel reads the simulator's observations itself and this
     agent keeps no buffers."""
 
@@ -46,12 +47,14 @@ class CnnPolicyAgent(VectorAgent):
         self._sim = self._check_env()
 
     def _check_env(self):
+        from ..envs.overcooked2_env import OvercookedMadrona as SimplecookedMadrona
         from ..envs.overcooked_env import OvercookedMadrona
-        from ..simulators import OvercookedSimulator, SimplecookedSimulator
+        from ..simulators import OvercookedSimulator
         envs = self.envs
-        sim = getattr(envs, "sim", None)
-        if not isinstance(envs, OvercookedMadrona) or not isinstance(sim, OvercookedSimulator) or isinstance(sim, SimplecookedSimulator):
-            raise TypeError("CnnPolicyAgent acts through mrl_cnn_act: envs must be an OvercookedMadrona, got "
+        sim = getattr(envs, "sim", None)  # (SimplecookedSimulator is an OvercookedSimulator)
+        if not isinstance(envs, (OvercookedMadrona, SimplecookedMadrona)) or not isinstance(sim, OvercookedSimulator):
+            raise TypeError("CnnPolicyAgent acts through mrl_cnn_act: envs must be an OvercookedMadrona of envs.overcooked_env or of "
+                            "envs.overcooked2_env (Simplecooked), got "
                             f"{type(envs).__name__} over {type(sim).__name__}; there is no torch fallback")
         if envs.device.type != "cuda":
             raise TypeError(f"CnnPolicyAgent needs the env on the simulator's GPU (cuda:{sim.gpu_id}); got env device {envs.device}")

@@ -304,7 +304,8 @@ class _CnnCritic(torch.nn.Module):
 
 
 class CnnActorCritic(torch.nn.Module):
-    """MAPPO's CNN actor-critic for Overcooked (train/MAPPO/utils/cnn.py:26-42, r_actor_critic.py, utils/distributions.py:55-68;
+    """MAPPO's CNN actor-critic for the two kitchens, Overcooked (``channels`` = 5P + 16) and Simplecooked (5P + 10, one or two
+    players) (train/MAPPO/utils/cnn.py:26-42, r_actor_critic.py, utils/distributions.py:55-68;
     non-recurrent, no PopArt, ``hidden_size`` 64): ``actor`` and ``critic`` take the (N, W, H, F) observation as floats.  Their
     state dicts have the reference's keys, so ``actor.load_state_dict`` / ``critic.load_state_dict`` take a reference checkpoint's
     two files.  Initialisation is the reference's: orthogonal weights with the ReLU gain, 0.01 for the action head (``args.gain``),
@@ -334,7 +335,7 @@ class CnnActorCritic(torch.nn.Module):
 
 
 class CnnPolicy:
-    """The parameters ``mrl_cnn_act`` runs: one flat float32 tensor ``params``, the actor's eight tensors and then the critic's in
+    """The parameters ``mrl_cnn_act`` runs on an Overcooked or a Simplecooked simulator of the policy's shape: one flat float32 tensor ``params``, the actor's eight tensors and then the critic's in
     the order of ``parameters_to_vector(CnnActorCritic.parameters())`` (``mrl_cnn_policy``).  ``module()`` returns a
     ``CnnActorCritic`` whose parameters are VIEWS into ``params``: an optimizer's in-place step on them is what the kernel reads
     next, with no copy in between (so there is no ``load_``)."""
@@ -410,7 +411,7 @@ def _cnn_call_args(sim, policy, players, record):
     shape = sim.observation_world_major_tensor().shape  # (N, P, H, W, F)
     if (policy.height, policy.width, policy.channels) != tuple(shape[2:]):
         raise ValueError(f"the policy is for a {policy.width} x {policy.height} kitchen with {policy.channels} channels, the simulator's "
-                         f"is {shape[3]} x {shape[2]} with {shape[4]}")
+                         f"is {shape[3]} x {shape[2]} with {shape[4]} (Overcooked: 5P + 16 channels, Simplecooked: 5P + 10)")
     if record is not None and (not isinstance(record, CnnRecord) or record.num_worlds != shape[0] or record.num_players != shape[1] or
                                record.actions.device != p.device):
         raise ValueError(f"record must be a CnnRecord of {shape[0]} worlds and {shape[1]} players on cuda:{sim.gpu_id}")
@@ -422,7 +423,7 @@ def _cnn_call_args(sim, policy, players, record):
 
 def cnn_act(sim, policy, players=None, record=None, row=0, seed=0, step=0, greedy=False, value_only=False, workspace=None):
     """``mrl_cnn_act`` on torch's current stream of the simulator's device: the seats in ``players`` (a bit mask or an iterable of
-    seats; default all) of an Overcooked simulator act under ``policy`` (a ``CnnPolicy``) on the observations the simulator's
+    seats; default all) of an Overcooked or Simplecooked simulator act under ``policy`` (a ``CnnPolicy``) on the observations the simulator's
     most recent step wrote, wherever that was; with ``record`` (a ``CnnRecord``) row ``row`` of its buffers is written.
     ``value_only``: the closing act at row T.  ``workspace``: default one the simulator keeps."""
     mask = _cnn_call_args(sim, policy, players, record)
@@ -894,7 +895,7 @@ class MappoOptimizer(_AdamState):
 
 
 def mappo_advantages(record, value_norm=None, gamma=0.99, gae_lambda=0.95):
-    """``(advantages, returns)`` of a ``CnnRecord``, each (T, N, P), as ``R_MAPPO.train`` and ``SharedReplayBuffer.compute_returns``
+    """``(advantages, returns)`` of a ``CnnRecord`` (Overcooked's or Simplecooked's, P = 1 included), each (T, N, P), as ``R_MAPPO.train`` and ``SharedReplayBuffer.compute_returns``
     form them (train/MAPPO/r_mappo.py:174-182, utils/shared_buffer.py:216-228 with ``use_gae``; every active mask one): the
     record's values denormalised when a ``ValueNorm`` is given, ``gae`` on those (``mrl_gae``: the reference's recurrence with
     ``masks[t + 1] = 1 - dones[t + 1]``), then ``(A - mean) / (std + 1e-5)`` over the whole buffer with torch's unbiased std.
@@ -924,7 +925,7 @@ def mappo_update(policy, optimizer, record, ring, advantages, returns, indices, 
     enqueued on torch's current stream; it does not wait.  ``policy.params`` is updated in place -- the next ``rollout`` or
     ``cnn_act`` reads it as it stands --, ``optimizer.step`` grows by the number of rows, and with ``value_norm`` (a
     ``ValueNorm``: the reference's ``use_valuenorm``) its state takes one update per row.  ``record`` and ``ring`` are what
-    ``rollout_cnn`` filled: sample ``(t N + n) P + p`` is row t, world n, seat p, and its observation is ring slot t, read as
+    ``rollout_cnn`` filled, of either kitchen (the call takes the shape from ``policy``): sample ``(t N + n) P + p`` is row t, world n, seat p, and its observation is ring slot t, read as
     int8 in place.  ``advantages`` and ``returns`` (T, N, P) are ``mappo_advantages``'; ``indices`` (K, B) int32 sample
     numbers (``minibatch_indices``).  The defaults are the reference's (train/config.py).  Returns ``MappoResult(stats,
     grads)``: (K, 8) float32, columns ``_lib.MAPPO_STATS``, and (K, P) the unclipped gradients, each None unless asked for.
@@ -1010,6 +1011,34 @@ class RecordsEpisodeStatistics:
     def clear_episode_totals(self):
         self._recording()
         self.sim.clear_episode_totals()
+
+
+class ActsWithCnnPolicy:
+    """Mixin of the two kitchen env wrappers (``envs/overcooked_env.py``, ``envs/overcooked2_env.py``; ``self.sim``, ``static_actions``,
+    ``static_world_major_observations``, ``num_envs`` and ``num_players`` are the wrapper's): MAPPO's CNN actor-critic on the device."""
+
+    def act(self, policy, players=None, record=None, row=0, seed=0, step=0, greedy=False):
+        """The seats in ``players`` (default all) act under ``policy`` (a ``simulators.CnnPolicy``) on the device, one launch
+        (``mrl_cnn_act``): the actions are in ``static_actions``, which is returned; with ``record`` (a ``CnnRecord``) row ``row``
+        also takes log-probs, values and the bookkeeping.  The observations read are those of the most recent step, also where
+        ``n_step(out=...)`` sent them."""
+        cnn_act(self.sim, policy, players, record, row=row, seed=seed, step=step, greedy=greedy)
+        return self.static_actions
+
+    def rollout(self, policy, num_steps, seed=0, first_step=0, players=None, record=None, ring=None, greedy=False):
+        """``num_steps`` steps under ``policy`` without the host in the loop (``mrl_rollout_cnn``) -> (record, ring): a ``CnnRecord``
+        and the observation ring (T + 1, N, P, H, W, F) whose slot k is what the act of step k saw.  ``record`` / ``ring``: an
+        earlier call's, filled again.  Afterwards the observations of the state reached (slot T) are also where the simulator's output
+        pointed before the call -- ``static_world_major_observations`` unless ``n_step(out=...)`` redirected it -- so rollouts chain.  ``simulators.gae(record.rollout(), gamma, gae_lambda)`` gives the advantages."""
+        device = self.static_actions.device
+        if record is None:
+            record = CnnRecord(num_steps, self.num_envs, self.num_players, device)
+        if record.num_steps != int(num_steps):
+            raise ValueError(f"record holds {record.num_steps} steps, asked for {num_steps}")
+        if ring is None:
+            ring = torch.empty((int(num_steps) + 1,) + tuple(self.static_world_major_observations.shape), dtype=torch.int8, device=device)
+        self.sim.rollout_cnn(policy, record, ring, players=players, seed=seed, first_step=first_step, greedy=greedy)
+        return record, ring
 
 
 class _Simulator:
@@ -1125,7 +1154,7 @@ class _Simulator:
 
     def rollout_cnn(self, policy, record, obs_ring, players=None, seed=0, first_step=0, greedy=False):
         """``record.num_steps`` steps under ``policy`` (a ``CnnPolicy``) for the seats in ``players`` with the host out of the loop
-        (``mrl_rollout_cnn``; Overcooked): ``obs_ring`` is int8 (T + 1, N, P, H, W, F), contiguous; slot 0 receives the current
+        (``mrl_rollout_cnn``; Overcooked and Simplecooked): ``obs_ring`` is int8 (T + 1, N, P, H, W, F), contiguous; slot 0 receives the current
         observations, the act of step k reads slot k and the step writes slot k + 1.  Afterwards the observation output is what
         it was before and holds slot T, the observations of the state the simulator is in: the next act or rollout goes on from
         there.  ``greedy`` travels in the policy descriptor's flags.  The draw of (step index ``first_step + k``, world, seat) is ``random_hash``'s."""
