@@ -954,6 +954,91 @@ int mrl_mappo_update(const mrl_mappo_policy *policy, const mrl_mappo_optimizer *
                      uint64_t workspace_bytes, float *stats_dev_or_null /* (K, 8) */, float *grads_dev_or_null /* (K, P) */,
                      int gpu_id, void *hip_stream);
 
+/* MAPPO's MLP actor-critic for the balance beam on the device: what the reference's trainer runs in torch for `balance`
+ * (train/trainer.py, train/env_utils.py:8-26; R_Actor / R_Critic pick MLPBase for a vector observation, train/MAPPO/
+ * r_actor_critic.py:33, utils/mlp.py) -- act, rollout and update, the counterparts of mrl_cnn_act, mrl_rollout_cnn and
+ * mrl_mappo_update.  No reference counterpart as calls.  DESIGN.md section 18.
+ *   Networks (use_feature_normalization, use_ReLU, use_orthogonal at their defaults; hidden_size 64; layer_N 1 or 2; D = 7 inputs;
+ *     A = 4 actions), per net: LayerNorm(7), Linear(7, 64), ReLU, LayerNorm(64), layer_N x [Linear(64, 64), ReLU, LayerNorm(64)],
+ *     then Linear(64, 4) (actor, Categorical) or Linear(64, 1) (critic).  LayerNorm is (x - mean) / sqrt(var + 1e-5) * weight + bias
+ *     with the biased variance over the row.  The critic's input IS the seat's observation (share_observation_space =
+ *     observation_space).  The balance beam's ACTION_MASK is all ones in every state (src/balance_beam_env/sim.cpp:197): the
+ *     kernels do not read it.
+ *   params_dev is one flat float32 device array, the actor's tensors and then the critic's, each in parameters_to_vector order:
+ *     base.feature_norm weight, bias (7, 7); base.mlp.fc1: Linear weight (64, 7), bias, LayerNorm weight, bias; base.mlp.fc_h:
+ *     Linear weight (64, 64), bias, LayerNorm weight, bias; base.mlp.fc2.i, i < layer_N: the same four; then the head's weight
+ *     (4, 64) or (1, 64) and bias.  mrl_mlpbase_policy_num_params(7, 64, layer_N, 4) floats: 27 361 for layer_N 2, 18 785 for 1 (0
+ *     for any other shape).  fc_h IS PART OF THE TENSOR AND OF NO COMPUTATION: the reference registers it and its forward never
+ *     uses it (mlp.py:20-27; fc2 are deep copies of it).  No kernel reads its 4 288 floats per net; its gradient is zero; its
+ *     parameter bits never change and its moments stay what they were (zero moments stay zero) -- the reference's Adam and
+ *     clip_grad_norm_ skip it because its grad is None.
+ *   Samples: (world n, seat p) for every seat whose bit is set in `players`.  The act reads OBSERVATION int32 (2, N, 7) in place,
+ *     converting on load.
+ *   Arithmetic, float32.  Linear: mrl_cnn_act's rule on v_mfma_f32_32x32x2_f32 -- an output starts from 0 and adds its products
+ *     with one fused multiply-add each in ascending input index, K = 7 padded with one zero product, the bias added to the
+ *     finished sum.  LayerNorm: a wavefront per row, lane j column j (lanes past the width add 0); a sum over the row is six
+ *     exchange steps, partners 32, 16, 8, 4, 2, 1 lanes apart, each lane adding its partner's partial sum to its own; mean = sum /
+ *     width, var = sum((x - mean)^2) / width, xhat = (x - mean) * (1 / sqrtf(var + 1e-5)), y = xhat * weight + bias (a product,
+ *     then a sum).  No float atomics, no order that depends on timing: the same inputs give the same bits on every run.
+ *   Head: mrl_cnn_act's with A = 4 -- h = the hash of (seed, step, n, p); u = (h >> 8) * 2^-24; the cumulative draw over the
+ *     soft-max; MRL_POLICY_GREEDY the first arg-max; the action goes to ACTION[p, n].  Without a record only the actor runs.
+ *   Record (mrl_mlpbase_record), dense device arrays, T = num_steps: mrl_cnn_record's arrays and row convention (logits (T, N, P,
+ *     4), optional; rewards[k - 1, n, p] = REWARD[p, n], float32 here) and obs int32 (T + 1, N, P, 7): row k receives the
+ *     observation rows the act at row k read, the closing MRL_MLPBASE_VALUE_ONLY act's at row T included.  Seats outside
+ *     `players` keep every byte of their ACTION row and of their record columns.
+ *   mrl_rollout_mlpbase: for k < T mrl_mlpbase_act at row k with step number first_step + k, then the ordinary step (mrl_step
+ *     reading the ACTION tensor); then the closing value-only act at row T.  No host in the loop; two rollouts of T equal one of
+ *     2 T.  Seats outside `players` step with whatever their ACTION rows hold.
+ *   mrl_mappo_mlp_update: mrl_mappo_update's samples (s = (t N + n) P + p; the observation is the seven int32 at 7 s of
+ *     batch->obs, the record's obs), losses, ValueNorm, clip, Adam, stats (K, 8), grads (K, P) and launch plan on this network:
+ *     two launches up front with MRL_MAPPO_VALUENORM, then three per row -- the gradient kernel (a workgroup per (share of the
+ *     row, net), tiles of 32 samples, everything between the observation row and the weight gradients in LDS: forward keeping
+ *     normalised rows, reciprocal standard deviations and ReLU signs, loss head, backward; LayerNorm backward dx = rstd (g -
+ *     mean(g) - xhat mean(g xhat)) with g = dy weight, dweight = sum dy xhat, dbias = sum dy; every Linear weight gradient on the
+ *     matrix instruction with the sample pair as k), the ordered sum of at most 256 partial vectors per net, and clip + Adam
+ *     per net.  On unchanged parameters the recomputed log-prob and value are the record's bit for bit.  Same inputs, same
+ *     bits; one call of K rows gives the bits of K calls of one row.
+ *   MRL_ERR_INVALID, nothing changed.  Act and rollout: a simulator that is not the balance beam, or one that has been through
+ *     mrl_exchange_create or mrl_prepare_graph_capture; a capturing stream; hidden != 64; layer_N not 1 or 2; players == 0 or a
+ *     bit >= 2; a NULL policy or parameter array; a NULL buffer but logits in a record; int32 or float arrays off a 4-byte
+ *     boundary; a flag bit other than MRL_POLICY_GREEDY and MRL_MLPBASE_VALUE_ONLY; row >= T without MRL_MLPBASE_VALUE_ONLY, row
+ *     != T with it, or it without a record; a NULL record for the rollout.  Update: mrl_mappo_update's refusals with the shape
+ *     check replaced by obs_dim != 7, hidden != 64, layer_N not 1 or 2, num_actions != 4; mrl_mappo_mlp_workspace_bytes refuses
+ *     the same shapes, B == 0 and a NULL out. */
+enum { MRL_MLPBASE_VALUE_ONLY = 4 }; /* flag of mrl_mlpbase_act, beside MRL_POLICY_GREEDY */
+typedef struct mrl_mlpbase_policy {
+    const float *params_dev;
+    uint32_t hidden, layer_N, flags; /* flags: 0 or MRL_POLICY_GREEDY (mrl_rollout_mlpbase has no flags argument of its own) */
+} mrl_mlpbase_policy;
+typedef struct mrl_mlpbase_record { /* all device pointers, dense; T = num_steps */
+    int32_t *actions;           /* (T, N, P) */
+    float *logprobs;            /* (T, N, P) */
+    float *values;              /* (T + 1, N, P) */
+    float *rewards, *dones;     /* (T, N, P) */
+    float *next_done;           /* (N, P) */
+    float *logits;              /* (T, N, P, 4) or NULL */
+    int32_t *obs;               /* (T + 1, N, P, 7) */
+    uint32_t num_steps;
+} mrl_mlpbase_record;
+typedef struct mrl_mappo_mlp_batch {
+    const int32_t *obs;          /* (S, 7) */
+    const int32_t *actions;      /* (S) */
+    const float *logprobs, *value_preds, *returns, *advantages; /* (S) */
+    uint32_t size;               /* S */
+} mrl_mappo_mlp_batch;
+uint64_t mrl_mlpbase_policy_num_params(uint32_t obs_dim, uint32_t hidden, uint32_t layer_N, uint32_t num_actions);
+int mrl_mlpbase_act(mrl_sim *sim, uint32_t players, const mrl_mlpbase_policy *policy, const mrl_mlpbase_record *record_or_null,
+                    uint32_t row, uint64_t seed, uint32_t step, uint32_t flags, void *hip_stream);
+int mrl_rollout_mlpbase(mrl_sim *sim, uint32_t players, const mrl_mlpbase_policy *policy, const mrl_mlpbase_record *record,
+                        uint64_t seed, uint32_t first_step, void *hip_stream);
+int mrl_mappo_mlp_workspace_bytes(uint32_t obs_dim, uint32_t hidden, uint32_t layer_N, uint32_t num_actions, uint32_t minibatch_size,
+                                  uint32_t num_minibatches, uint64_t *out);
+int mrl_mappo_mlp_update(const mrl_mlpbase_policy *policy, const mrl_mappo_optimizer *opt, const mrl_mappo_mlp_batch *batch,
+                         const int32_t *indices_dev /* (K, B) */, uint32_t num_minibatches /* K */, uint32_t minibatch_size /* B */,
+                         const mrl_mappo_config *cfg, float *value_norm_state_dev_or_null /* (3) */, void *workspace_dev,
+                         uint64_t workspace_bytes, float *stats_dev_or_null /* (K, 8) */, float *grads_dev_or_null /* (K, P) */,
+                         int gpu_id, void *hip_stream);
+
 int mrl_tensor(mrl_sim *sim, int slot, mrl_tensor_desc *out);
 int mrl_game(const mrl_sim *sim);
 uint32_t mrl_num_worlds(const mrl_sim *sim);

@@ -33,6 +33,8 @@ WIDE_HIDDEN, WIDE_MAX_ACTIONS = 512, 64  # MRL_WIDE_*
 PPO_NORM_ADV, PPO_CLIP_VLOSS = 1, 2  # MRL_PPO_*
 CNN_VALUE_ONLY = 4  # MRL_CNN_VALUE_ONLY: flag of mrl_cnn_act beside POLICY_GREEDY
 CNN_HIDDEN, CNN_ACTIONS = 64, 6  # the one shape mrl_cnn_act runs
+MLPBASE_VALUE_ONLY = 4  # MRL_MLPBASE_VALUE_ONLY: flag of mrl_mlpbase_act beside POLICY_GREEDY
+MLPBASE_HIDDEN, MLPBASE_OBS, MLPBASE_ACTIONS = 64, 7, 4  # the one shape mrl_mlpbase_act runs (layer_N 1 or 2)
 MAPPO_VALUENORM, MAPPO_HUBER_LOSS, MAPPO_CLIPPED_VALUE_LOSS, MAPPO_MAX_GRAD_NORM = 1, 2, 4, 8  # MRL_MAPPO_*
 MAPPO_STATS = ("value_loss", "critic_grad_norm", "policy_loss", "dist_entropy", "actor_grad_norm", "ratio", "clipfrac", "reserved")
 PPO_STATS = ("pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac", "total_norm", "loss")  # a stats row
@@ -51,7 +53,8 @@ SYMBOLS = [
     "mrl_rollout_policy", "mrl_gae", "mrl_ppo_workspace_bytes", "mrl_ppo_update", "mrl_wide_policy_num_params",
     "mrl_agent_workspace_bytes", "mrl_agent_act", "mrl_agent_credit", "mrl_gae_active", "mrl_cnn_policy_num_params",
     "mrl_cnn_workspace_bytes", "mrl_cnn_act", "mrl_rollout_cnn", "mrl_mappo_workspace_bytes", "mrl_mappo_update",
-    "mrl_agent_update_workspace_bytes", "mrl_agent_update",
+    "mrl_agent_update_workspace_bytes", "mrl_agent_update", "mrl_mlpbase_policy_num_params", "mrl_mlpbase_act",
+    "mrl_rollout_mlpbase", "mrl_mappo_mlp_workspace_bytes", "mrl_mappo_mlp_update",
 ]
 ABI_VERSION = 4  # MRL_ABI_VERSION of include/mrl_envs.h this binding was written against
 
@@ -145,6 +148,21 @@ class MappoBatch(ctypes.Structure):  # mrl_mappo_batch
 class MappoOptimizerDesc(ctypes.Structure):  # mrl_mappo_optimizer
     _fields_ = [("params_dev", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p),
                 ("step", ctypes.c_uint32)]
+
+
+class MlpBasePolicyDesc(ctypes.Structure):  # mrl_mlpbase_policy
+    _fields_ = [("params_dev", ctypes.c_void_p), ("hidden", ctypes.c_uint32), ("layer_N", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+MLPBASE_RECORD_BUFFERS = CNN_RECORD_BUFFERS + ("obs",)
+
+
+class MlpBaseRecordDesc(ctypes.Structure):  # mrl_mlpbase_record
+    _fields_ = [(name, ctypes.c_void_p) for name in MLPBASE_RECORD_BUFFERS] + [("num_steps", ctypes.c_uint32)]
+
+
+class MappoMlpBatch(ctypes.Structure):  # mrl_mappo_mlp_batch
+    _fields_ = MappoBatch._fields_
 
 
 class MrlError(RuntimeError):
@@ -281,6 +299,14 @@ def lib():
     L.mrl_mappo_update.argtypes = [ctypes.POINTER(MappoPolicyDesc), ctypes.POINTER(MappoOptimizerDesc), ctypes.POINTER(MappoBatch), vp,
                                    u32, u32, ctypes.POINTER(MappoConfig), vp, vp, ctypes.c_uint64, vp, vp, i32, vp]
     L.mrl_rollout_cnn.argtypes = [vp, u32, ctypes.POINTER(CnnPolicyDesc), ctypes.POINTER(CnnRecordDesc), vp, ctypes.c_uint64, u32, vp]
+    L.mrl_mlpbase_policy_num_params.argtypes = [u32, u32, u32, u32]
+    L.mrl_mlpbase_policy_num_params.restype = ctypes.c_uint64
+    L.mrl_mlpbase_act.argtypes = [vp, u32, ctypes.POINTER(MlpBasePolicyDesc), ctypes.POINTER(MlpBaseRecordDesc), u32, ctypes.c_uint64, u32,
+                                  u32, vp]
+    L.mrl_rollout_mlpbase.argtypes = [vp, u32, ctypes.POINTER(MlpBasePolicyDesc), ctypes.POINTER(MlpBaseRecordDesc), ctypes.c_uint64, u32, vp]
+    L.mrl_mappo_mlp_workspace_bytes.argtypes = [u32, u32, u32, u32, u32, u32, ctypes.POINTER(ctypes.c_uint64)]
+    L.mrl_mappo_mlp_update.argtypes = [ctypes.POINTER(MlpBasePolicyDesc), ctypes.POINTER(MappoOptimizerDesc), ctypes.POINTER(MappoMlpBatch),
+                                       vp, u32, u32, ctypes.POINTER(MappoConfig), vp, vp, ctypes.c_uint64, vp, vp, i32, vp]
     L.mrl_tensor.argtypes = [vp, i32, ctypes.POINTER(TensorDesc)]
     L.mrl_game.argtypes = [vp]
     L.mrl_num_worlds.argtypes = [vp]

@@ -8,6 +8,8 @@
 #include "wide_update.hpp"
 #include "cnn_policy.hpp"
 #include "cnn_update.hpp"
+#include "mlpbase_policy.hpp"
+#include "mlpbase_update.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -1225,6 +1227,220 @@ int mrl_rollout_cnn(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy
             const uint8_t *last = ring + (size_t)T * slot_bytes;
             if (home != last) MRL_HIP(hipMemcpyAsync(home, last, slot_bytes, hipMemcpyDeviceToDevice, stream));
         }
+    });
+}
+
+uint64_t mrl_mlpbase_policy_num_params(uint32_t obs_dim, uint32_t hidden, uint32_t layer_N, uint32_t num_actions)
+{
+    if (obs_dim != mrl::kMlpBaseObs || hidden != mrl::kMlpBaseHidden || layer_N < 1 || layer_N > mrl::kMlpBaseMaxLayerN ||
+        num_actions != mrl::kMlpBaseActions)
+        return 0;
+    return (uint64_t)mrl::mlpbase_net_params(layer_N, num_actions) + mrl::mlpbase_net_params(layer_N, 1);
+}
+
+// Everything mrl_mlpbase_act and mrl_rollout_mlpbase check alike; fills `args` but for the rows, the seed, the step and the flags.
+static int mlpbase_prepare(mrl_sim *sim, uint32_t players, const mrl_mlpbase_policy *policy, const mrl_mlpbase_record *record,
+                           void *hip_stream, const char *what, mrl::MlpBaseActArgs *args)
+{
+    if (int rc = mrl::need_healthy(sim)) return rc;
+    if (sim->game != MRL_GAME_BALANCE) {
+        mrl::set_error("%s: game %d has no MLPBase policy (the balance beam does)", what, sim->game);
+        return MRL_ERR_INVALID;
+    }
+    if (sim->exchange.mine || sim->capturable()) {
+        mrl::set_error("%s: this simulator has been through mrl_exchange_create or mrl_prepare_graph_capture; sharded and captured "
+                       "simulators are out of scope", what);
+        return MRL_ERR_INVALID;
+    }
+    if (mrl::capturing(hip_stream)) {
+        mrl::set_error("%s: the row and the step number travel in kernel arguments, a captured call would replay them", what);
+        return MRL_ERR_INVALID;
+    }
+    if (!policy || !policy->params_dev || policy->hidden != mrl::kMlpBaseHidden || policy->layer_N < 1 ||
+        policy->layer_N > mrl::kMlpBaseMaxLayerN || (policy->flags & ~(uint32_t)MRL_POLICY_GREEDY)) {
+        mrl::set_error("%s: null policy or parameter array, hidden other than 64, layer_N other than 1 or 2, or policy flags other than "
+                       "MRL_POLICY_GREEDY", what);
+        return MRL_ERR_INVALID;
+    }
+    if (record && (!record->actions || !record->logprobs || !record->values || !record->rewards || !record->dones || !record->next_done ||
+                   !record->obs)) {
+        mrl::set_error("%s: the record needs every buffer but logits", what);
+        return MRL_ERR_INVALID;
+    }
+    uintptr_t low_bits = reinterpret_cast<uintptr_t>(policy->params_dev);
+    if (record)
+        for (const void *p : {(const void *)record->actions, (const void *)record->logprobs, (const void *)record->values,
+                              (const void *)record->rewards, (const void *)record->dones, (const void *)record->next_done,
+                              (const void *)record->logits, (const void *)record->obs})
+            low_bits |= reinterpret_cast<uintptr_t>(p);
+    if (low_bits & 3u) {
+        mrl::set_error("%s: the parameter array and the record's arrays must start on 4-byte boundaries", what);
+        return MRL_ERR_INVALID;
+    }
+    mrl_tensor_desc obs{}, done{}, reward{}, action{};
+    int rc = mrl::guarded([&] {
+        if (!sim->tensor(MRL_BALANCE_OBSERVATION, &obs) || !sim->tensor(MRL_BALANCE_DONE, &done) || !sim->tensor(MRL_BALANCE_REWARD, &reward) ||
+            !sim->tensor(MRL_BALANCE_ACTION, &action))
+            throw std::runtime_error("the simulator does not export OBSERVATION / DONE / REWARD / ACTION");
+        if (obs.shape[2] != (int64_t)mrl::kMlpBaseObs || obs.dtype != MRL_INT32 || reward.dtype != MRL_FLOAT32 || action.dtype != MRL_INT32)
+            throw std::runtime_error("unexpected tensor layout (OBSERVATION int32 (P, N, 7), REWARD float32, ACTION int32)");
+    });
+    if (rc) return rc;
+    const uint32_t P = (uint32_t)obs.shape[0];
+    if (players == 0 || (P < 32 && (players >> P) != 0)) {
+        mrl::set_error("%s: players = 0x%x must name at least one seat and none beyond the simulator's %u", what, players, P);
+        return MRL_ERR_INVALID;
+    }
+    mrl::MlpBaseActArgs &a = *args;
+    a = mrl::MlpBaseActArgs{};
+    a.params = policy->params_dev;
+    a.obs = static_cast<const int32_t *>(obs.data);
+    a.done = static_cast<const int32_t *>(done.data);
+    a.reward = static_cast<const float *>(reward.data);
+    a.action = static_cast<int32_t *>(action.data);
+    a.P = P, a.num_worlds = sim->num_worlds;
+    a.players = players, a.num_seats = (uint32_t)__builtin_popcount(players);
+    a.layer_N = policy->layer_N;
+    return MRL_OK;
+}
+
+// the rows of `record` an act at `row` writes (value_only: the closing act at row T)
+static void mlpbase_rows(mrl::MlpBaseActArgs &a, const mrl_mlpbase_record *record, uint32_t row, bool value_only)
+{
+    a.actions_row = nullptr, a.obs_row = nullptr, a.logprobs_row = a.values_row = a.rewards_row = a.dones_row = a.logits_row = nullptr;
+    a.nets = 1u;
+    if (!record) return;
+    const size_t cells = (size_t)a.num_worlds * a.P;
+    a.nets = value_only ? 2u : 3u;
+    a.values_row = record->values + row * cells;
+    a.obs_row = record->obs + row * cells * mrl::kMlpBaseObs;
+    a.rewards_row = row ? record->rewards + (row - 1) * cells : nullptr;
+    a.dones_row = value_only ? record->next_done : record->dones + row * cells;
+    if (value_only) return;
+    a.actions_row = record->actions + row * cells;
+    a.logprobs_row = record->logprobs + row * cells;
+    a.logits_row = record->logits ? record->logits + row * cells * mrl::kMlpBaseActions : nullptr;
+}
+
+int mrl_mlpbase_act(mrl_sim *sim, uint32_t players, const mrl_mlpbase_policy *policy, const mrl_mlpbase_record *record, uint32_t row,
+                    uint64_t seed, uint32_t step, uint32_t flags, void *hip_stream)
+{
+    mrl::MlpBaseActArgs args{};
+    if (int rc = mlpbase_prepare(sim, players, policy, record, hip_stream, "mrl_mlpbase_act", &args)) return rc;
+    if (flags & ~(uint32_t)(MRL_POLICY_GREEDY | MRL_MLPBASE_VALUE_ONLY)) {
+        mrl::set_error("mrl_mlpbase_act: flags 0x%x: only MRL_POLICY_GREEDY and MRL_MLPBASE_VALUE_ONLY exist", flags);
+        return MRL_ERR_INVALID;
+    }
+    flags |= policy->flags;  // MRL_POLICY_GREEDY may travel with the policy (mrl_rollout_mlpbase has no flags of its own)
+    const bool value_only = flags & MRL_MLPBASE_VALUE_ONLY;
+    if (value_only ? (!record || row != record->num_steps) : (record && row >= record->num_steps)) {
+        mrl::set_error("mrl_mlpbase_act: row %u of %u; MRL_MLPBASE_VALUE_ONLY needs a record and row == num_steps, every other act row < "
+                       "num_steps", row, record ? record->num_steps : 0u);
+        return MRL_ERR_INVALID;
+    }
+    mrl::DeviceGuard on(sim->device);
+    return mrl::guarded([&] {
+        mlpbase_rows(args, record, row, value_only);
+        args.seed = seed, args.step = step, args.flags = flags;
+        mrl::launch_mlpbase_act(args, (hipStream_t)hip_stream);
+    });
+}
+
+int mrl_rollout_mlpbase(mrl_sim *sim, uint32_t players, const mrl_mlpbase_policy *policy, const mrl_mlpbase_record *record, uint64_t seed,
+                        uint32_t first_step, void *hip_stream)
+{
+    mrl::MlpBaseActArgs args{};
+    if (int rc = mlpbase_prepare(sim, players, policy, record, hip_stream, "mrl_rollout_mlpbase", &args)) return rc;
+    if (!record) {
+        mrl::set_error("mrl_rollout_mlpbase: null record");
+        return MRL_ERR_INVALID;
+    }
+    mrl::DeviceGuard on(sim->device);
+    return mrl::guarded([&] {
+        hipStream_t stream = (hipStream_t)hip_stream;
+        const uint32_t T = record->num_steps;
+        args.seed = seed;
+        for (uint32_t k = 0; k <= T; k++) {
+            const bool closing = k == T;
+            mlpbase_rows(args, record, k, closing);
+            args.step = first_step + k;
+            args.flags = policy->flags | (closing ? (uint32_t)MRL_MLPBASE_VALUE_ONLY : 0u);
+            mrl::launch_mlpbase_act(args, stream);
+            if (closing) break;
+            sim->step(nullptr, stream);
+            mrl::completed_step(sim, stream);
+        }
+    });
+}
+
+// what mrl_mappo_mlp_workspace_bytes and mrl_mappo_mlp_update refuse alike: nullptr when the shape can run, else why not
+static const char *mappo_mlp_shape_error(uint32_t obs_dim, uint32_t hidden, uint32_t layer_N, uint32_t num_actions, uint32_t minibatch_size)
+{
+    if (hidden != mrl::kMlpBaseHidden) return "hidden must be 64";
+    if (layer_N < 1 || layer_N > mrl::kMlpBaseMaxLayerN) return "layer_N must be 1 or 2";
+    if (obs_dim != mrl::kMlpBaseObs || num_actions != mrl::kMlpBaseActions) return "obs_dim must be 7 and num_actions 4";
+    if (minibatch_size == 0) return "minibatch_size must be positive";
+    return nullptr;
+}
+
+int mrl_mappo_mlp_workspace_bytes(uint32_t obs_dim, uint32_t hidden, uint32_t layer_N, uint32_t num_actions, uint32_t minibatch_size,
+                                  uint32_t num_minibatches, uint64_t *out)
+{
+    const char *why = out ? mappo_mlp_shape_error(obs_dim, hidden, layer_N, num_actions, minibatch_size) : "null output pointer";
+    if (why) {
+        mrl::set_error("mrl_mappo_mlp_workspace_bytes: %s (obs_dim %u, hidden %u, layer_N %u, num_actions %u, minibatch_size %u)", why, obs_dim,
+                       hidden, layer_N, num_actions, minibatch_size);
+        return MRL_ERR_INVALID;
+    }
+    *out = mrl::mappo_workspace(mrl::mlpbase_net_params(layer_N, num_actions), minibatch_size, num_minibatches).total * sizeof(float);
+    return MRL_OK;
+}
+
+int mrl_mappo_mlp_update(const mrl_mlpbase_policy *policy, const mrl_mappo_optimizer *opt, const mrl_mappo_mlp_batch *batch,
+                         const int32_t *indices_dev, uint32_t num_minibatches, uint32_t minibatch_size, const mrl_mappo_config *cfg,
+                         float *value_norm_state, void *workspace_dev, uint64_t workspace_bytes, float *stats_dev_or_null,
+                         float *grads_dev_or_null, int gpu_id, void *hip_stream)
+{
+    if (!policy || !opt || !batch || (!indices_dev && num_minibatches) || !cfg || !workspace_dev) {  // (no rows: no index array)
+        mrl::set_error("mrl_mappo_mlp_update: null policy, optimizer, batch, index array, configuration or workspace");
+        return MRL_ERR_INVALID;
+    }
+    if (!policy->params_dev || !opt->params_dev || !opt->exp_avg || !opt->exp_avg_sq || !batch->obs || !batch->actions || !batch->logprobs ||
+        !batch->value_preds || !batch->returns || !batch->advantages) {
+        mrl::set_error("mrl_mappo_mlp_update: null parameter, moment or batch array");
+        return MRL_ERR_INVALID;
+    }
+    if (policy->params_dev != opt->params_dev) {
+        mrl::set_error("mrl_mappo_mlp_update: the policy's and the optimizer's params_dev must be the same array");
+        return MRL_ERR_INVALID;
+    }
+    if (cfg->flags & ~mrl::kMappoKnownFlags) {
+        mrl::set_error("mrl_mappo_mlp_update: flags 0x%x: only the four MRL_MAPPO_* bits exist", cfg->flags);
+        return MRL_ERR_INVALID;
+    }
+    if ((cfg->flags & MRL_MAPPO_VALUENORM) && !value_norm_state) {
+        mrl::set_error("mrl_mappo_mlp_update: MRL_MAPPO_VALUENORM needs value_norm_state");
+        return MRL_ERR_INVALID;
+    }
+    const char *why = mappo_mlp_shape_error(mrl::kMlpBaseObs, policy->hidden, policy->layer_N, mrl::kMlpBaseActions, minibatch_size);
+    if (why || batch->size == 0) {
+        mrl::set_error("mrl_mappo_mlp_update: %s (hidden %u, layer_N %u, minibatch_size %u, batch size %u)",
+                       why ? why : "the batch must hold at least one sample", policy->hidden, policy->layer_N, minibatch_size, batch->size);
+        return MRL_ERR_INVALID;
+    }
+    const uint64_t actor = mrl::mlpbase_net_params(policy->layer_N, mrl::kMlpBaseActions);
+    const uint64_t need_bytes = mrl::mappo_workspace(actor, minibatch_size, num_minibatches).total * sizeof(float);
+    const void *words[] = {opt->params_dev, opt->exp_avg, opt->exp_avg_sq, batch->obs, batch->actions, batch->logprobs, batch->value_preds,
+                           batch->returns, batch->advantages, indices_dev, value_norm_state, stats_dev_or_null, grads_dev_or_null};
+    uintptr_t low_bits = 0;
+    for (const void *p : words) low_bits |= reinterpret_cast<uintptr_t>(p) & 3u;
+    if (int rc = update_refusal("mrl_mappo_mlp_update", "mrl_mappo_mlp_workspace_bytes", workspace_bytes, need_bytes, workspace_dev, low_bits,
+                                "the float and int32 arrays must start on 4-byte boundaries", hip_stream))
+        return rc;
+    mrl::DeviceGuard on(gpu_id);
+    return guarded([&] {
+        mrl::launch_mappo_mlp_update(policy->layer_N, *opt, *batch, indices_dev, num_minibatches, minibatch_size, *cfg, value_norm_state,
+                                     static_cast<float *>(workspace_dev), stats_dev_or_null, grads_dev_or_null, (hipStream_t)hip_stream);
     });
 }
 

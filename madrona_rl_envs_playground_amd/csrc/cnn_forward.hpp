@@ -53,7 +53,9 @@ __device__ __forceinline__ void cnn_fetch(const float *__restrict__ w, uint32_t 
     }
 }
 
-// out[row][col] = act(bias[col] + sum_k in[row][k] w[col][k]) for the tile's 32 rows; K even; ends behind a barrier
+// out[row][col] = act(bias[col] + sum_k in[row][k] w[col][k]) for the tile's 32 rows; ends behind a barrier.  K is the weight
+// rows' stride and the number of products; an odd K (the balance beam's 7 inputs) takes one more product, a zero weight times
+// in[row][K], which the caller keeps at 0.  An even K -- every layer of the kitchens -- runs the steps it always ran.
 __device__ __forceinline__ void cnn_fc_layer(const float *__restrict__ in, uint32_t in_ld, uint32_t K, const float *__restrict__ w,
                                              const float *__restrict__ bias, uint32_t out_dim, bool relu, float *__restrict__ chunk,
                                              float *__restrict__ out, uint32_t out_ld, uint32_t wave, uint32_t lane)
@@ -71,7 +73,7 @@ __device__ __forceinline__ void cnn_fc_layer(const float *__restrict__ in, uint3
         __syncthreads();
         if (k0 + kCnnChunk < K) cnn_fetch(w, K, out_dim, k0 + kCnnChunk + lane, wave, pb);
         if (compute) {
-            const uint32_t left = K - k0, steps = left >= kCnnChunk ? kCnnChunk / 2u : left / 2u;
+            const uint32_t left = K - k0, steps = left >= kCnnChunk ? kCnnChunk / 2u : (left + 1u) / 2u;
             const float *__restrict__ pa_lds = in + r * in_ld + k0 + half;
             const float *__restrict__ pb_lds = chunk + (wave * 32u + r) * kCnnFcLd + half;
             for (uint32_t s = 0; s < steps; s++) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pa_lds[2u * s], pb_lds[2u * s], acc, 0, 0, 0);

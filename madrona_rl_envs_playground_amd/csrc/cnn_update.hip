@@ -17,6 +17,8 @@
 //   mrl_clip_adam     per net: total norm, clip, Adam with the net's learning rate, and the net's columns of the stats row
 //                     (adam_step.hpp: the tail every update shares; each net is a segment).
 // No float atomics and no wait on another workgroup anywhere: the same inputs give the same bits on every run.
+// The per-sample loss head, the accumulator tiles and the stats row's end are mappo_loss.hpp's, shared with the balance beam's
+// update (mlpbase_update.hip); the ValueNorm launches are defined here and declared there.
 #include "cnn_update.hpp"
 #include "cnn_forward.hpp"
 
@@ -41,58 +43,8 @@ struct MappoGradArgs {
     double *partial_stats;   // (2, groups, 8)
     uint64_t share, stride;
     uint32_t minibatch_size, batch_size, groups, tail_at;
-    float clip_param, entropy_coef, value_loss_coef, huber_delta;
-    uint32_t flags;
+    MappoLoss loss;
 };
-
-// the value the compiler must take as new: keeps per-lane address arithmetic of the tile loop's body inside the loop (hoisted, the
-// addresses of every accumulator element of every phase would be live across the whole body and spill)
-__device__ __forceinline__ uint32_t opaque(uint32_t v)
-{
-    asm volatile("" : "+v"(v));
-    return v;
-}
-
-// the C/D map of the 32 x 32 tile: element e of lane (r, half) is row (e & 3) + 8 (e >> 2) + 4 half, column r
-__device__ __forceinline__ uint32_t tile_row(int e, uint32_t half) { return (e & 3) + 8 * (e >> 2) + 4 * half; }
-
-// the accumulator of C[row0 + row][col] as the previous tile left it in the partial vector (0 before the first tile)
-__device__ __forceinline__ f32x16 acc_load(const float *__restrict__ g, uint32_t ld, uint32_t rows, uint32_t col, bool col_ok, bool first,
-                                           uint32_t half)
-{
-    f32x16 acc;
-#pragma unroll
-    for (int e = 0; e < 16; e++) {
-        const uint32_t row = tile_row(e, half);
-        acc[e] = !first && col_ok && row < rows ? g[(size_t)row * ld + col] : 0.0f;
-    }
-    return acc;
-}
-
-__device__ __forceinline__ void acc_store(float *__restrict__ g, uint32_t ld, uint32_t rows, uint32_t col, bool col_ok, uint32_t half,
-                                          const f32x16 &acc)
-{
-#pragma unroll
-    for (int e = 0; e < 16; e++) {
-        const uint32_t row = tile_row(e, half);
-        if (col_ok && row < rows) g[(size_t)row * ld + col] = acc[e];
-    }
-}
-
-// the reference's huber_loss (utils/util.py:46-50) or mse_loss and its derivative in e
-__device__ __forceinline__ float value_term(float e, float delta, bool huber, float &slope)
-{
-    if (!huber || fabsf(e) <= delta) {
-        slope = e;
-        return e * e / 2.0f;
-    }
-    if (e > delta) {
-        slope = delta;
-        return delta * (fabsf(e) - delta / 2.0f);
-    }
-    slope = 0.0f;  // e < -delta: neither mask of huber_loss is set
-    return 0.0f;
-}
 
 // the tile's observation rows (mrl_cnn_act's loader with the row taken from the sample table), the patch offsets of k and, for
 // the forward pass, the conv weights
@@ -222,62 +174,9 @@ __global__ void __launch_bounds__(kCnnThreads) mrl_mappo_grad(MappoGradArgs a)
             if (at != 0xFFFFFFFFu && net == 0u) {
                 const float lg[kCnnActions] = {outs[tid * 8u], outs[tid * 8u + 1], outs[tid * 8u + 2], outs[tid * 8u + 3], outs[tid * 8u + 4],
                                                outs[tid * 8u + 5]};
-                // categorical_sample's soft-max (random_policy.hpp) with all six log-probs kept: logf as there, so that the new
-                // log-prob of the recorded action is the act's bit for bit
-                float top = lg[0];
-#pragma unroll
-                for (int i = 1; i < (int)kCnnActions; i++) top = lg[i] > top ? lg[i] : top;
-                float e[kCnnActions], sum = 0.0f;
-#pragma unroll
-                for (int i = 0; i < (int)kCnnActions; i++) {
-                    e[i] = expf(lg[i] - top);
-                    sum += e[i];
-                }
-                const float logsum = logf(sum);
-                const int action = a.actions[at];
-                float logp[kCnnActions], prob[kCnnActions], entropy = 0.0f, newlogprob = 0.0f;
-#pragma unroll
-                for (int i = 0; i < (int)kCnnActions; i++) {
-                    logp[i] = (lg[i] - top) - logsum;  // mrl_cnn_act's log-prob
-                    prob[i] = e[i] / sum;
-                    entropy = fmaf(-prob[i], logp[i], entropy);
-                    newlogprob = action == i ? logp[i] : newlogprob;
-                }
-                const float ratio = expf(newlogprob - a.logprobs[at]);
-                const float adv = a.advantages[at];
-                const float lo = 1.0f - a.clip_param, hi = 1.0f + a.clip_param;
-                const float surr1 = ratio * adv, surr2 = fminf(fmaxf(ratio, lo), hi) * adv;
-                // torch.min hands the gradient to the smaller argument and halves it on a tie; clamp passes it inside [lo, hi]
-                const float one = surr1 < surr2 ? 1.0f : (surr1 == surr2 ? 0.5f : 0.0f);
-                const float through = one + (ratio >= lo && ratio <= hi ? 1.0f - one : 0.0f);
-                const float g_logprob = (-adv * through) * ratio / count;
-                const float g_entropy = a.entropy_coef / count;  // of -entropy_coef * mean(H): dH/dl_i = -p_i (logp_i + H)
-#pragma unroll
-                for (int i = 0; i < (int)kCnnActions; i++)
-                    d[i] = fmaf(g_logprob, (action == i ? 1.0f : 0.0f) - prob[i], g_entropy * (prob[i] * (logp[i] + entropy)));
-                stat[0] += (double)fminf(surr1, surr2);
-                stat[1] += (double)entropy;
-                stat[2] += (double)ratio;
-                stat[3] += fabsf(ratio - 1.0f) > a.clip_param ? 1.0 : 0.0;
+                mappo_actor_sample<(int)kCnnActions>(lg, a.actions[at], a.logprobs[at], a.advantages[at], a.loss, count, d, stat);
             } else if (at != 0xFFFFFFFFu) {
-                const bool huber = a.flags & MRL_MAPPO_HUBER_LOSS;
-                const float v = outs[tid * 8u], old = a.value_preds[at];
-                float target = a.returns[at];
-                if (a.row_norm) target = (target - a.row_norm[0]) / a.row_norm[1];
-                float slope, slope_c;
-                const float plain = value_term(target - v, a.huber_delta, huber, slope);
-                float worst = plain, g = -slope;
-                if (a.flags & MRL_MAPPO_CLIPPED_VALUE_LOSS) {
-                    const float moved = v - old;
-                    const float near = old + fminf(fmaxf(moved, -a.clip_param), a.clip_param);
-                    const float clipped = value_term(target - near, a.huber_delta, huber, slope_c);
-                    const float one = plain > clipped ? 1.0f : (plain == clipped ? 0.5f : 0.0f);
-                    const bool inside = moved >= -a.clip_param && moved <= a.clip_param;
-                    worst = fmaxf(plain, clipped);
-                    g = one * -slope + (inside ? (1.0f - one) * -slope_c : 0.0f);
-                }
-                d[0] = a.value_loss_coef * g / count;
-                stat[0] += (double)worst;
+                d[0] = mappo_critic_sample(outs[tid * 8u], a.value_preds[at], a.returns[at], a.row_norm, a.loss, count, stat);
             }
 #pragma unroll
             for (int i = 0; i < (int)kCnnActions; i++) d_out[tid * 8u + i] = d[i];
@@ -477,34 +376,19 @@ __global__ void mrl_mappo_value_norm(const float *__restrict__ row_sums, uint32_
     state[2] = debias;
 }
 
-// The stats row's end, in mrl_clip_adam: the net's columns from its workgroups' four sums and its total norm
-struct MappoStatsRow {
-    const double *partial_stats;
-    float *row;  // nullptr: no stats
-    uint32_t groups, minibatch_size;
-
-    __device__ void operator()(uint32_t net, float total_norm) const
-    {
-        if (!row) return;
-        double sum[4] = {0.0, 0.0, 0.0, 0.0};
-        for (uint32_t w = 0; w < groups; w++)
-            for (int c = 0; c < 4; c++) sum[c] += partial_stats[((size_t)net * groups + w) * kMappoStats + c];
-        const double count = (double)minibatch_size;
-        if (net) {
-            row[0] = (float)(sum[0] / count);
-            row[1] = total_norm;
-        } else {
-            row[2] = (float)(-(sum[0] / count));
-            row[3] = (float)(sum[1] / count);
-            row[4] = total_norm;
-            row[5] = (float)(sum[2] / count);
-            row[6] = (float)(sum[3] / count);
-            row[7] = 0.0f;
-        }
-    }
-};
-
 }  // namespace
+
+void launch_mappo_value_norm(const float *returns, const int32_t *indices, uint32_t num_minibatches, uint32_t minibatch_size,
+                             uint32_t batch_size, const mrl_mappo_config &cfg, float *state, float *row_sums, float *row_norm,
+                             hipStream_t stream)
+{
+    hipLaunchKernelGGL(mrl_mappo_row_sums, dim3(num_minibatches), dim3(kStatThreads), 0, stream, returns, indices, minibatch_size, batch_size,
+                       row_sums);
+    MRL_HIP(hipGetLastError());
+    hipLaunchKernelGGL(mrl_mappo_value_norm, dim3(1), dim3(64), 0, stream, row_sums, num_minibatches, cfg.valuenorm_beta,
+                       cfg.valuenorm_one_minus_beta, cfg.valuenorm_epsilon, state, row_norm);
+    MRL_HIP(hipGetLastError());
+}
 
 void launch_mappo_update(const mrl_mappo_policy &policy, const mrl_mappo_optimizer &opt, const mrl_mappo_batch &batch,
                          const int32_t *indices, uint32_t num_minibatches, uint32_t minibatch_size, const mrl_mappo_config &cfg,
@@ -517,14 +401,9 @@ void launch_mappo_update(const mrl_mappo_policy &policy, const mrl_mappo_optimiz
     const MappoWorkspace ws = mappo_workspace(actor, minibatch_size, num_minibatches);
     const CnnUpdateLds lds = cnn_update_lds(W, H, F);
     const bool norm = cfg.flags & MRL_MAPPO_VALUENORM;
-    if (norm) {
-        hipLaunchKernelGGL(mrl_mappo_row_sums, dim3(num_minibatches), dim3(kStatThreads), 0, stream, batch.returns, indices, minibatch_size,
-                           batch.size, workspace + ws.row_sums);
-        MRL_HIP(hipGetLastError());
-        hipLaunchKernelGGL(mrl_mappo_value_norm, dim3(1), dim3(64), 0, stream, workspace + ws.row_sums, num_minibatches, cfg.valuenorm_beta,
-                           cfg.valuenorm_one_minus_beta, cfg.valuenorm_epsilon, value_norm_state, workspace + ws.row_norm);
-        MRL_HIP(hipGetLastError());
-    }
+    if (norm)
+        launch_mappo_value_norm(batch.returns, indices, num_minibatches, minibatch_size, batch.size, cfg, value_norm_state,
+                                workspace + ws.row_sums, workspace + ws.row_norm, stream);
     allow_large_dynamic_lds<&mrl_mappo_grad>(lds.total);
     MappoGradArgs g{};
     g.fwd.params = opt.params_dev;
@@ -546,11 +425,7 @@ void launch_mappo_update(const mrl_mappo_policy &policy, const mrl_mappo_optimiz
     g.batch_size = batch.size;
     g.groups = share.groups;
     g.tail_at = lds.tail_at;
-    g.clip_param = cfg.clip_param;
-    g.entropy_coef = cfg.entropy_coef;
-    g.value_loss_coef = cfg.value_loss_coef;
-    g.huber_delta = cfg.huber_delta;
-    g.flags = cfg.flags;
+    g.loss = MappoLoss{cfg.clip_param, cfg.entropy_coef, cfg.value_loss_coef, cfg.huber_delta, cfg.flags};
     // two clip_grad_norm_ and two Adam steps: the actor's segment, then the critic's
     AdamStepArgs ad = adam_step_args(cfg.beta1, cfg.beta2, cfg.opti_eps, cfg.flags & MRL_MAPPO_MAX_GRAD_NORM, cfg.max_grad_norm);
     ad.partial_grads = g.partial_grads;

@@ -2,14 +2,10 @@
 // include/mrl_envs.h).  The kernels live in cnn_update.hip; capi.hip validates the arguments.
 #pragma once
 
-#include "adam_step.hpp"
 #include "cnn_policy.hpp"
+#include "mappo_loss.hpp"
 
 namespace mrl {
-
-constexpr uint32_t kMappoMaxGroups = 256;  // workgroups per net, hence partial gradient vectors per net and row, however large B is
-constexpr uint32_t kMappoStats = 8;        // columns of a stats row
-constexpr uint32_t kMappoKnownFlags = MRL_MAPPO_VALUENORM | MRL_MAPPO_HUBER_LOSS | MRL_MAPPO_CLIPPED_VALUE_LOSS | MRL_MAPPO_MAX_GRAD_NORM;
 
 // The gradient workgroup's LDS image: mrl_cnn_act's (cnn_lds) with region A at least large enough for what back-propagation
 // keeps beside the forward pass's chunk, h1, h2 and head outputs -- dL/d(head output) (32 x 8), dL/d(pre-activation of fc2) and
@@ -32,32 +28,6 @@ inline CnnUpdateLds cnn_update_lds(uint32_t W, uint32_t H, uint32_t F)
     u.fwd.total = u.tail_at;
     u.total = u.tail_at + kCnnTile * 2u * 4u;
     return u;
-}
-
-// The caller's scratch, in floats: every row's ValueNorm (mean, sqrt(var)) and (mean, mean of squares) of its returns; the
-// workgroups' partial gradient vectors (2 nets, groups, stride) and partial stats (2, groups, 8 doubles); the summed gradient
-// (2, stride); the reduce launch's per-block sums of g^2 (2, blocks).  stride = the actor's parameter count, padded.
-struct MappoWorkspace {
-    uint64_t row_norm, row_sums, partial_grads, partial_stats, grad, sumsq, total;
-    uint64_t stride, groups, blocks;
-};
-
-inline MappoWorkspace mappo_workspace(uint64_t actor_params, uint32_t minibatch_size, uint32_t num_minibatches)
-{
-    const auto pad = [](uint64_t n) { return (n + 3) & ~uint64_t(3); };  // every array on a 16-byte boundary
-    const uint64_t tiles = ((uint64_t)minibatch_size + kCnnTile - 1) / kCnnTile;
-    MappoWorkspace w;
-    w.groups = tiles < kMappoMaxGroups ? tiles : kMappoMaxGroups;  // room for min(tiles, cap); share_samples may use fewer
-    w.stride = pad(actor_params);
-    w.blocks = (w.stride + kAdamThreads - 1) / kAdamThreads;
-    w.row_norm = 0;
-    w.row_sums = w.row_norm + pad(2 * (uint64_t)num_minibatches);
-    w.partial_grads = w.row_sums + pad(2 * (uint64_t)num_minibatches);
-    w.partial_stats = w.partial_grads + 2 * w.groups * w.stride;
-    w.grad = w.partial_stats + pad(2 * 2 * w.groups * kMappoStats);
-    w.sumsq = w.grad + 2 * w.stride;
-    w.total = w.sumsq + pad(2 * w.blocks);
-    return w;
 }
 
 // K rows enqueued on `stream`; every argument has been validated (capi.hip, mrl_mappo_update).

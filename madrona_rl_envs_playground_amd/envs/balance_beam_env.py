@@ -4,7 +4,7 @@ positions in 0..8 -- own and partner history, shifted by BUFFER -- and the steps
 import torch
 
 from ..pantheonrl_extension.vectorenv import MadronaEnv
-from ..simulators import BalanceBeamSimulator, ExecMode
+from ..simulators import ActsWithMlpBasePolicy, BalanceBeamSimulator, ExecMode
 from ..spaces import Discrete, MultiDiscrete
 
 NUM_SPACES = 5
@@ -14,7 +14,8 @@ TIME = 3
 SCALE = 0.2
 
 
-class BalanceMadronaTorch(MadronaEnv):
+class BalanceMadronaTorch(ActsWithMlpBasePolicy, MadronaEnv):
+    """``act`` and ``rollout`` (extensions, ``simulators.ActsWithMlpBasePolicy``): MAPPO's MLP actor-critic on the device."""
 
     def __init__(self, num_envs, gpu_id, debug_compile=True, use_cpu=False, use_env_cpu=False, record_episode_statistics=False):
         sim = BalanceBeamSimulator(exec_mode=ExecMode.CPU if use_cpu else ExecMode.CUDA, gpu_id=gpu_id,

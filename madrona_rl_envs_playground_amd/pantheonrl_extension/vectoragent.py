@@ -74,6 +74,46 @@ class CnnPolicyAgent(VectorAgent):
         return None
 
 
+class MlpBasePolicyAgent(VectorAgent):
+    """A player of ``envs.balance_beam_env.BalanceMadronaTorch`` that acts under MAPPO's MLP policy on the device -- what the
+    reference's ``CentralizedAgent`` does for the partner seat --, the counterpart of ``CnnPolicyAgent``: ``get_action`` is
+    ``mrl_mlpbase_act`` for this agent's seat (``player_num``, set by ``env.add_partner_agent``, or, while that is ``None``, the
+    env's ``ego_ind``) on the simulator's own observations, and returns the view ``env.static_actions[seat]``.  ``policy``: a
+    ``simulators.MlpBasePolicy``; ``seed`` seeds the draws, whose step number counts this agent's calls.  ``update`` does nothing.
+    Any other env, or one off the GPU, is refused with a ``TypeError`` by the constructor: there is no torch fallback."""
+
+    def __init__(self, envs, policy, seed=0, greedy=False):
+        self.envs, self.policy, self.seed, self.greedy = envs, policy, int(seed), bool(greedy)
+        self.player_num = None
+        self._draws = 0
+        self._sim = self._check_env()
+
+    def _check_env(self):
+        from ..envs.balance_beam_env import BalanceMadronaTorch
+        from ..simulators import BalanceBeamSimulator
+        envs = self.envs
+        sim = getattr(envs, "sim", None)
+        if not isinstance(envs, BalanceMadronaTorch) or not isinstance(sim, BalanceBeamSimulator):
+            raise TypeError("MlpBasePolicyAgent acts through mrl_mlpbase_act: envs must be a BalanceMadronaTorch, got "
+                            f"{type(envs).__name__} over {type(sim).__name__}; there is no torch fallback")
+        if envs.device.type != "cuda":
+            raise TypeError(f"MlpBasePolicyAgent needs the env on the simulator's GPU (cuda:{sim.gpu_id}); got env device {envs.device}")
+        return sim
+
+    @property
+    def seat(self):
+        return self.envs.ego_ind if self.player_num is None else self.player_num
+
+    def get_action(self, obs=None, record=True):
+        from ..simulators import mlpbase_act
+        mlpbase_act(self._sim, self.policy, 1 << self.seat, seed=self.seed, step=self._draws, greedy=self.greedy)
+        self._draws += 1
+        return self.envs.static_actions[self.seat]
+
+    def update(self, rewards, dones):
+        return None
+
+
 class CleanPPOAgent(VectorAgent):
     """The reference's PPO agent for Hanabi and the balance beam (/root/reference/pantheonrl_extension/vectoragent.py:116-372;
     built twice, ego and partner, by scripts/hanabi_train.py and scripts/balance_train.py) with its collection phase on the

@@ -19,6 +19,7 @@ the reference's CPU TaskGraph executor is out of scope, an
 silent CPU path would defeat the parity tests.
 """
 import collections
+import copy
 import ctypes
 import enum
 
@@ -437,6 +438,194 @@ def cnn_act(sim, policy, players=None, record=None, row=0, seed=0, step=0, greed
     rc = sim._L.mrl_cnn_act(sim._handle, mask, ctypes.byref(desc), ctypes.byref(record.struct) if record is not None else None, int(row),
                             int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF, flags, workspace.data_ptr(), workspace.numel(),
                             _stream_ptr(sim.gpu_id))
+    if rc:
+        _lib.check(rc)
+
+
+class _MlpLayer(torch.nn.Module):
+    """train/MAPPO/utils/mlp.py:6-27 for use_ReLU and use_orthogonal: ``fc1``, ``fc_h`` and ``fc2``, ``layer_N`` deep copies of
+    ``fc_h`` taken at construction.  ``forward`` never uses ``fc_h`` itself -- as in the reference, whose state dicts carry it."""
+
+    def __init__(self, obs_dim, hidden, layer_N):
+        super().__init__()
+        nn = torch.nn
+        gain = nn.init.calculate_gain("relu")
+
+        def linear(inputs, outputs):
+            layer = nn.Linear(inputs, outputs)
+            nn.init.orthogonal_(layer.weight.data, gain=gain)
+            nn.init.constant_(layer.bias.data, 0.0)
+            return layer
+
+        self._layer_N = int(layer_N)
+        self.fc1 = nn.Sequential(linear(obs_dim, hidden), nn.ReLU(), nn.LayerNorm(hidden))
+        self.fc_h = nn.Sequential(linear(hidden, hidden), nn.ReLU(), nn.LayerNorm(hidden))
+        self.fc2 = nn.ModuleList([copy.deepcopy(self.fc_h) for _ in range(self._layer_N)])
+
+    def forward(self, x):
+        x = self.fc1(x)
+        for i in range(self._layer_N):
+            x = self.fc2[i](x)
+        return x
+
+
+class _MlpBase(torch.nn.Module):
+    """``MLPBase`` with ``use_feature_normalization`` (mlp.py:31-58)"""
+
+    def __init__(self, obs_dim, hidden, layer_N):
+        super().__init__()
+        self.feature_norm = torch.nn.LayerNorm(obs_dim)
+        self.mlp = _MlpLayer(obs_dim, hidden, layer_N)
+
+    def forward(self, x):
+        return self.mlp(self.feature_norm(x))
+
+
+class _MlpBaseActor(torch.nn.Module):
+    """``R_Actor``'s parameters by name for a vector observation, non-recurrent: ``base.feature_norm``, ``base.mlp.fc1/fc_h/fc2``,
+    ``act.action_out.linear``"""
+
+    def __init__(self, obs_dim, hidden, layer_N, num_actions):
+        super().__init__()
+        self.base = _MlpBase(obs_dim, hidden, layer_N)
+        self.act = _ActLayer(hidden, num_actions)
+
+    def forward(self, obs):
+        return self.act.action_out.linear(self.base(obs))
+
+
+class _MlpBaseCritic(torch.nn.Module):
+    """``R_Critic``'s parameters by name without PopArt: ``base...``, ``v_out``"""
+
+    def __init__(self, obs_dim, hidden, layer_N):
+        super().__init__()
+        self.base = _MlpBase(obs_dim, hidden, layer_N)
+        self.v_out = torch.nn.Linear(hidden, 1)
+
+    def forward(self, state):
+        return self.v_out(self.base(state))
+
+
+class MlpBaseActorCritic(torch.nn.Module):
+    """MAPPO's MLP actor-critic for the balance beam (train/MAPPO/utils/mlp.py, r_actor_critic.py, utils/distributions.py:55-68;
+    ``use_feature_normalization``, ``use_ReLU`` and ``use_orthogonal`` at their defaults, non-recurrent, no PopArt): ``actor`` and
+    ``critic`` take the (n, 7) observation as floats.  Their state dicts have the reference's keys -- ``base.mlp.fc_h`` included,
+    which the reference registers and never uses --, so ``actor.load_state_dict`` / ``critic.load_state_dict`` take a reference
+    checkpoint's ``actor.pt`` / ``critic.pt``.  Initialisation is the reference's: orthogonal weights with the ReLU gain, 0.01 for
+    the action head (``args.gain``), 1 for ``v_out``, zero biases, LayerNorm at (1, 0).  The device path runs ``hidden`` 64 and
+    ``layer_N`` 1 or 2."""
+
+    def __init__(self, obs_dim=_lib.MLPBASE_OBS, num_actions=_lib.MLPBASE_ACTIONS, hidden=_lib.MLPBASE_HIDDEN, layer_N=2):
+        super().__init__()
+        self.obs_dim, self.num_actions, self.hidden, self.layer_N = int(obs_dim), int(num_actions), int(hidden), int(layer_N)
+        self.actor = _MlpBaseActor(self.obs_dim, self.hidden, self.layer_N, self.num_actions)
+        self.critic = _MlpBaseCritic(self.obs_dim, self.hidden, self.layer_N)
+        for head, head_gain in ((self.actor.act.action_out.linear, 0.01), (self.critic.v_out, 1.0)):
+            torch.nn.init.orthogonal_(head.weight, gain=head_gain)
+            torch.nn.init.constant_(head.bias, 0.0)
+
+    def get_value(self, state):
+        return self.critic(state)
+
+    def get_action_and_value(self, obs, action=None, deterministic=False):
+        dist = torch.distributions.Categorical(logits=self.actor(obs))
+        if action is None:
+            action = dist.probs.argmax(dim=-1) if deterministic else dist.sample()
+        return action, dist.log_prob(action), dist.entropy(), self.critic(obs)
+
+
+class MlpBasePolicy:
+    """The parameters ``mrl_mlpbase_act`` runs on a balance-beam simulator: one flat float32 tensor ``params``, the actor's tensors
+    and then the critic's in the order of ``parameters_to_vector(MlpBaseActorCritic.parameters())`` (``mrl_mlpbase_policy``; the
+    unused ``fc_h`` is part of it and is never read or changed by a kernel).  ``module()`` returns an ``MlpBaseActorCritic`` whose
+    parameters are VIEWS into ``params``: an in-place step on either side is what the other reads next (there is no ``load_``)."""
+
+    def __init__(self, obs_dim=_lib.MLPBASE_OBS, num_actions=_lib.MLPBASE_ACTIONS, hidden=_lib.MLPBASE_HIDDEN, layer_N=2, device="cuda:0"):
+        self.obs_dim, self.num_actions, self.hidden, self.layer_N = int(obs_dim), int(num_actions), int(hidden), int(layer_N)
+        if self.num_params == 0:
+            raise ValueError(f"mrl_mlpbase_act runs obs_dim = {_lib.MLPBASE_OBS}, num_actions = {_lib.MLPBASE_ACTIONS}, hidden = "
+                             f"{_lib.MLPBASE_HIDDEN} and layer_N 1 or 2; got {self.obs_dim}, {self.num_actions}, {self.hidden}, {self.layer_N}")
+        self.params = torch.zeros(self.num_params, dtype=torch.float32, device=torch.device(device))
+        self._module = None
+
+    @property
+    def num_params(self):
+        return int(_lib.lib().mrl_mlpbase_policy_num_params(self.obs_dim, self.hidden, self.layer_N, self.num_actions))
+
+    @classmethod
+    def from_module(cls, module, device=None):
+        """A policy of ``module``'s shape (an ``MlpBaseActorCritic``) holding a copy of its parameters (``device``: default its own)."""
+        if not isinstance(module, MlpBaseActorCritic):
+            raise ValueError("module must be an MlpBaseActorCritic")
+        own = next(module.parameters()).device
+        policy = cls(module.obs_dim, module.num_actions, module.hidden, module.layer_N, device if device is not None else own)
+        with torch.no_grad():
+            policy.params.copy_(torch.nn.utils.parameters_to_vector(module.parameters()).detach())
+        return policy
+
+    def module(self):
+        """The ``MlpBaseActorCritic`` whose parameters alias ``params`` (one object per policy)."""
+        if self._module is None:
+            module = MlpBaseActorCritic(self.obs_dim, self.num_actions, self.hidden, self.layer_N)
+            at = 0
+            for p in module.parameters():  # actor first, then critic: the order of the flat array
+                p.data = self.params[at:at + p.numel()].view(p.shape)
+                at += p.numel()
+            assert at == self.params.numel()
+            self._module = module
+        return self._module
+
+    def desc(self):
+        return _lib.MlpBasePolicyDesc(self.params.data_ptr(), self.hidden, self.layer_N, 0)
+
+
+class MlpBaseRecord:
+    """The buffers of ``mrl_mlpbase_act`` / ``mrl_rollout_mlpbase`` (``mrl_mlpbase_record``): ``CnnRecord``'s arrays and row
+    convention (``logits`` (T, N, P, 4) on request) and ``obs`` int32 (T + 1, N, P, 7), row k what the act at row k read."""
+
+    def __init__(self, num_steps, num_worlds, num_players, device, logits=False):
+        t, n, p = int(num_steps), int(num_worlds), int(num_players)
+        z = lambda shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=device)  # noqa: E731
+        self.num_steps, self.num_worlds, self.num_players = t, n, p
+        self.actions = z((t, n, p), torch.int32)
+        self.logprobs, self.rewards, self.dones = z((t, n, p)), z((t, n, p)), z((t, n, p))
+        self.values, self.next_done = z((t + 1, n, p)), z((n, p))
+        self.logits = z((t, n, p, _lib.MLPBASE_ACTIONS)) if logits else None
+        self.obs = z((t + 1, n, p, _lib.MLPBASE_OBS), torch.int32)
+        self.struct = _lib.MlpBaseRecordDesc(*[getattr(self, name).data_ptr() if getattr(self, name) is not None else None
+                                               for name in _lib.MLPBASE_RECORD_BUFFERS], t)
+
+    rollout = CnnRecord.rollout
+
+
+def _mlpbase_call_args(sim, policy, players, record):
+    if not isinstance(policy, MlpBasePolicy):
+        raise ValueError("policy must be an MlpBasePolicy")
+    if not isinstance(sim, BalanceBeamSimulator):
+        raise ValueError("mrl_mlpbase_act runs on a BalanceBeamSimulator")
+    p = policy.params
+    if not p.is_cuda or p.device.index != sim.gpu_id or p.dtype != torch.float32 or not p.is_contiguous() or p.numel() != policy.num_params:
+        raise ValueError(f"policy.params must be a contiguous float32 tensor of num_params elements on cuda:{sim.gpu_id}")
+    seats, worlds = sim.observation_tensor().shape[:2]  # (P, N, 7)
+    if record is not None and (not isinstance(record, MlpBaseRecord) or record.num_worlds != worlds or record.num_players != seats or
+                               record.actions.device != p.device):
+        raise ValueError(f"record must be an MlpBaseRecord of {worlds} worlds and {seats} players on cuda:{sim.gpu_id}")
+    mask = (1 << seats) - 1 if players is None else players
+    if not isinstance(mask, int):
+        mask = sum(1 << int(seat) for seat in mask)
+    return mask & 0xFFFFFFFF if 0 <= mask < 2 ** 32 else 0xFFFFFFFF
+
+
+def mlpbase_act(sim, policy, players=None, record=None, row=0, seed=0, step=0, greedy=False, value_only=False):
+    """``mrl_mlpbase_act`` on torch's current stream of the simulator's device: the seats in ``players`` (a bit mask or an iterable
+    of seats; default both) of a balance-beam simulator act under ``policy`` (an ``MlpBasePolicy``) on the simulator's own
+    OBSERVATION tensor; with ``record`` (an ``MlpBaseRecord``) row ``row`` of its buffers is written, the observation rows
+    included.  ``value_only``: the closing act at row T."""
+    mask = _mlpbase_call_args(sim, policy, players, record)
+    flags = (_lib.POLICY_GREEDY if greedy else 0) | (_lib.MLPBASE_VALUE_ONLY if value_only else 0)
+    desc = policy.desc()
+    rc = sim._L.mrl_mlpbase_act(sim._handle, mask, ctypes.byref(desc), ctypes.byref(record.struct) if record is not None else None,
+                                int(row), int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF, flags, _stream_ptr(sim.gpu_id))
     if rc:
         _lib.check(rc)
 
@@ -874,21 +1063,25 @@ class ValueNorm:
 
 
 class MappoOptimizer(_AdamState):
-    """The state of MAPPO's two Adam optimizers for a ``CnnPolicy`` (``R_MAPPOPolicy``: ``torch.optim.Adam(lr, eps=opti_eps,
+    """The state of MAPPO's two Adam optimizers for a ``CnnPolicy`` or an ``MlpBasePolicy`` (``R_MAPPOPolicy``: ``torch.optim.Adam(lr, eps=opti_eps,
     weight_decay=0)`` for the actor and for the critic): ``exp_avg`` and ``exp_avg_sq`` over the whole flat tensor, the number
     of steps both have taken (``step``) and the scratch ``mrl_mappo_update`` asks for, kept from call to call.  ``lr`` and
     ``critic_lr`` are ordinary attributes: assign to them for the reference's ``lr_decay``."""
 
     def __init__(self, policy, lr=5e-4, critic_lr=5e-4, betas=(0.9, 0.999), eps=1e-5):
-        if not isinstance(policy, CnnPolicy):
-            raise ValueError("policy must be a CnnPolicy")
+        if not isinstance(policy, (CnnPolicy, MlpBasePolicy)):
+            raise ValueError("policy must be a CnnPolicy or an MlpBasePolicy")
         super().__init__(policy, betas, eps)
         self.lr, self.critic_lr = float(lr), float(critic_lr)
 
     def workspace_bytes(self, minibatch_size, num_minibatches):
-        """``mrl_mappo_workspace_bytes`` for this policy's shape."""
+        """``mrl_mappo_workspace_bytes`` (``mrl_mappo_mlp_workspace_bytes`` for an ``MlpBasePolicy``) for this policy's shape."""
         p = self.policy
         out = ctypes.c_uint64(0)
+        if isinstance(p, MlpBasePolicy):
+            _lib.check(_lib.lib().mrl_mappo_mlp_workspace_bytes(p.obs_dim, p.hidden, p.layer_N, p.num_actions, int(minibatch_size),
+                                                                int(num_minibatches), ctypes.byref(out)))
+            return int(out.value)
         _lib.check(_lib.lib().mrl_mappo_workspace_bytes(p.width, p.height, p.channels, p.hidden, int(minibatch_size), int(num_minibatches),
                                                         ctypes.byref(out)))
         return int(out.value)
@@ -901,8 +1094,8 @@ def mappo_advantages(record, value_norm=None, gamma=0.99, gae_lambda=0.95):
     ``masks[t + 1] = 1 - dones[t + 1]``), then ``(A - mean) / (std + 1e-5)`` over the whole buffer with torch's unbiased std.
     ``returns`` are in the denormalised scale, as the reference's buffer holds them.  It runs once per update, so apart from
     ``mrl_gae`` it is a handful of torch ops on the record's device; it does not wait."""
-    if not isinstance(record, CnnRecord):
-        raise ValueError("record must be a CnnRecord")
+    if not isinstance(record, (CnnRecord, MlpBaseRecord)):
+        raise ValueError("record must be a CnnRecord or an MlpBaseRecord")
     rollout = record.rollout()
     if value_norm is not None:
         t, cols = record.num_steps, record.num_worlds * record.num_players
@@ -929,7 +1122,13 @@ def mappo_update(policy, optimizer, record, ring, advantages, returns, indices, 
     int8 in place.  ``advantages`` and ``returns`` (T, N, P) are ``mappo_advantages``'; ``indices`` (K, B) int32 sample
     numbers (``minibatch_indices``).  The defaults are the reference's (train/config.py).  Returns ``MappoResult(stats,
     grads)``: (K, 8) float32, columns ``_lib.MAPPO_STATS``, and (K, P) the unclipped gradients, each None unless asked for.
+    For an ``MlpBasePolicy`` (the balance beam; ``mrl_mappo_mlp_update``) ``record`` is an ``MlpBaseRecord``, the batch is its
+    ``obs`` and ``ring`` must be ``None``.
     Not built: active masks, PopArt, recurrent policies, ``update_actor=False``, weight decay."""
+    if isinstance(policy, MlpBasePolicy):
+        return _mappo_mlp_update(policy, optimizer, record, ring, advantages, returns, indices, value_norm, clip_param, entropy_coef,
+                                 value_loss_coef, max_grad_norm, huber_delta, use_huber_loss, use_clipped_value_loss, use_max_grad_norm,
+                                 stats, grads)
     if not isinstance(policy, CnnPolicy) or not isinstance(optimizer, MappoOptimizer) or optimizer.policy is not policy:
         raise ValueError("policy must be a CnnPolicy and optimizer the MappoOptimizer made for it")
     if not isinstance(record, CnnRecord):
@@ -966,6 +1165,46 @@ def mappo_update(policy, optimizer, record, ring, advantages, returns, indices, 
                            optimizer.betas[0], optimizer.betas[1], optimizer.eps, beta, 1.0 - beta,
                            value_norm.epsilon if value_norm is not None else 1e-5, flags)
     return _run_update(_lib.lib().mrl_mappo_update, (ctypes.byref(shape), ctypes.byref(opt), ctypes.byref(batch)), indices,
+                       (ctypes.byref(cfg), value_norm.state.data_ptr() if value_norm is not None else None), optimizer,
+                       len(_lib.MAPPO_STATS), MappoResult, stats, grads)
+
+
+def _mappo_mlp_update(policy, optimizer, record, ring, advantages, returns, indices, value_norm, clip_param, entropy_coef, value_loss_coef,
+                      max_grad_norm, huber_delta, use_huber_loss, use_clipped_value_loss, use_max_grad_norm, stats, grads):
+    """``mappo_update`` for an ``MlpBasePolicy``: the same checks and configuration, the batch's observations are ``record.obs``"""
+    if not isinstance(optimizer, MappoOptimizer) or optimizer.policy is not policy:
+        raise ValueError("optimizer must be the MappoOptimizer made for the policy")
+    if not isinstance(record, MlpBaseRecord):
+        raise ValueError("record must be an MlpBaseRecord")
+    if ring is not None:
+        raise ValueError("an MlpBasePolicy's batch is record.obs: ring must be None")
+    if value_norm is not None and not isinstance(value_norm, ValueNorm):
+        raise ValueError("value_norm must be a ValueNorm or None")
+    p = policy.params
+    if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous() or p.numel() != policy.num_params:
+        raise ValueError("policy.params must be a contiguous float32 tensor of num_params elements on a GPU")
+    device, f32 = p.device, torch.float32
+    count = record.num_steps * record.num_worlds * record.num_players
+    per_row = count // max(record.num_steps, 1)
+    wanted = [("policy.params", p, f32, p.numel()), ("optimizer.exp_avg", optimizer.exp_avg, f32, p.numel()),
+              ("optimizer.exp_avg_sq", optimizer.exp_avg_sq, f32, p.numel()), ("record.actions", record.actions, torch.int32, count),
+              ("record.logprobs", record.logprobs, f32, count), ("record.values", record.values, f32, count + per_row),
+              ("record.obs", record.obs, torch.int32, (count + per_row) * policy.obs_dim),
+              ("advantages", advantages, f32, count), ("returns", returns, f32, count), ("indices", indices, torch.int32, None)]
+    if value_norm is not None:
+        wanted.append(("value_norm.state", value_norm.state, f32, 3))
+    _require_tensors(wanted, device)
+    shape = policy.desc()
+    opt = _lib.MappoOptimizerDesc(p.data_ptr(), optimizer.exp_avg.data_ptr(), optimizer.exp_avg_sq.data_ptr(), optimizer.step)
+    batch = _lib.MappoMlpBatch(record.obs.data_ptr(), record.actions.data_ptr(), record.logprobs.data_ptr(), record.values.data_ptr(),
+                               returns.data_ptr(), advantages.data_ptr(), count)
+    beta = value_norm.beta if value_norm is not None else 0.99999
+    flags = ((_lib.MAPPO_VALUENORM if value_norm is not None else 0) | (_lib.MAPPO_HUBER_LOSS if use_huber_loss else 0) |
+             (_lib.MAPPO_CLIPPED_VALUE_LOSS if use_clipped_value_loss else 0) | (_lib.MAPPO_MAX_GRAD_NORM if use_max_grad_norm else 0))
+    cfg = _lib.MappoConfig(clip_param, entropy_coef, value_loss_coef, max_grad_norm, huber_delta, optimizer.lr, optimizer.critic_lr,
+                           optimizer.betas[0], optimizer.betas[1], optimizer.eps, beta, 1.0 - beta,
+                           value_norm.epsilon if value_norm is not None else 1e-5, flags)
+    return _run_update(_lib.lib().mrl_mappo_mlp_update, (ctypes.byref(shape), ctypes.byref(opt), ctypes.byref(batch)), indices,
                        (ctypes.byref(cfg), value_norm.state.data_ptr() if value_norm is not None else None), optimizer,
                        len(_lib.MAPPO_STATS), MappoResult, stats, grads)
 
@@ -1039,6 +1278,29 @@ class ActsWithCnnPolicy:
             ring = torch.empty((int(num_steps) + 1,) + tuple(self.static_world_major_observations.shape), dtype=torch.int8, device=device)
         self.sim.rollout_cnn(policy, record, ring, players=players, seed=seed, first_step=first_step, greedy=greedy)
         return record, ring
+
+
+class ActsWithMlpBasePolicy:
+    """Mixin of the balance-beam env wrapper (``envs/balance_beam_env.py``; ``self.sim``, ``static_actions``, ``num_envs`` and
+    ``n_players`` are the wrapper's): MAPPO's MLP actor-critic on the device."""
+
+    def act(self, policy, players=None, record=None, row=0, seed=0, step=0, greedy=False):
+        """The seats in ``players`` (default both) act under ``policy`` (a ``simulators.MlpBasePolicy``) on the device, one launch
+        (``mrl_mlpbase_act``): the actions are in ``static_actions``, which is returned; with ``record`` (an ``MlpBaseRecord``)
+        row ``row`` also takes log-probs, values, the observation rows and the bookkeeping."""
+        mlpbase_act(self.sim, policy, players, record, row=row, seed=seed, step=step, greedy=greedy)
+        return self.static_actions
+
+    def rollout(self, policy, num_steps, seed=0, first_step=0, players=None, record=None, greedy=False):
+        """``num_steps`` steps under ``policy`` without the host in the loop (``mrl_rollout_mlpbase``) -> an ``MlpBaseRecord``
+        whose ``obs[k]`` is what the act of step k saw.  ``record``: an earlier call's, filled again.  Rollouts chain: the next one
+        acts on the state this one reached.  ``simulators.mappo_advantages(record)`` gives the advantages."""
+        if record is None:
+            record = MlpBaseRecord(num_steps, self.num_envs, self.n_players, self.static_actions.device)
+        if record.num_steps != int(num_steps):
+            raise ValueError(f"record holds {record.num_steps} steps, asked for {num_steps}")
+        self.sim.rollout_mlpbase(policy, record, players=players, seed=seed, first_step=first_step, greedy=greedy)
+        return record
 
 
 class _Simulator:
@@ -1169,6 +1431,19 @@ class _Simulator:
         desc.flags = _lib.POLICY_GREEDY if greedy else 0
         _lib.check(self._L.mrl_rollout_cnn(self._handle, mask, ctypes.byref(desc), ctypes.byref(record.struct), obs_ring.data_ptr(),
                                            int(seed) & (2 ** 64 - 1), int(first_step) & 0xFFFFFFFF, _stream_ptr(self.gpu_id)))
+
+    def rollout_mlpbase(self, policy, record, players=None, seed=0, first_step=0, greedy=False):
+        """``record.num_steps`` steps under ``policy`` (an ``MlpBasePolicy``) for the seats in ``players`` with the host out of the
+        loop (``mrl_rollout_mlpbase``; the balance beam): the act of step k reads OBSERVATION in place and copies its rows into
+        ``record.obs[k]``, the closing value-only act fills row T.  ``greedy`` travels in the policy descriptor's flags.  The draw
+        of (step index ``first_step + k``, world, seat) is ``random_hash``'s."""
+        mask = _mlpbase_call_args(self, policy, players, record)
+        if record is None:
+            raise ValueError("rollout_mlpbase needs an MlpBaseRecord")
+        desc = policy.desc()
+        desc.flags = _lib.POLICY_GREEDY if greedy else 0
+        _lib.check(self._L.mrl_rollout_mlpbase(self._handle, mask, ctypes.byref(desc), ctypes.byref(record.struct),
+                                               int(seed) & (2 ** 64 - 1), int(first_step) & 0xFFFFFFFF, _stream_ptr(self.gpu_id)))
 
     def reset_worlds(self, mask=None):
         """Restart the worlds whose ``mask`` entry is nonzero (``None``: every world) as fresh episodes, enqueued on torch's
