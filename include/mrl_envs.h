@@ -883,6 +883,78 @@ int mrl_cnn_act(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, co
 int mrl_rollout_cnn(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, const mrl_cnn_record *record, void *obs_ring_dev,
                     uint64_t seed, uint32_t first_step, void *hip_stream);
 
+/* A population of partners: a BANK of K CNN policies of one shape and a policy per (world, seat) cell, so that one batch of worlds
+ * plays against many partners at once and a world's partner can change when its episode ends -- what the reference's
+ * VectorMultiAgentEnv.add_partner_agent promises per episode and its vectorised reset can only do for the whole batch
+ * (pantheonrl_extension/vectorenv.py:89-98, 202-210).  No reference counterpart as calls.  DESIGN.md section 19.
+ *   Bank (mrl_cnn_bank): params_dev is a float32 device array of K = num_policies rows, `stride` floats apart (stride >=
+ *     mrl_cnn_policy_num_params); row k is exactly an mrl_cnn_policy's params_dev, so mrl_cnn_act, mrl_mappo_update and the bank act
+ *     read and write the same floats.  1 <= K <= 256.  hidden and flags as in mrl_cnn_policy.
+ *   Assignment: ids, int32 (N, P), device memory, the caller's.  ids[n, p] = k >= 0: seat p of world n acts under row k.  -1 (any
+ *     negative value): the cell is not acted -- its ACTION entry and its record cells keep every byte.  A value >= K is outside
+ *     the contract: the cell is treated as -1 and, where its seat is in `players`, counted in the workspace's out_of_range word.
+ *     A cell is acted when its seat's bit is set in `players` AND its id is valid.
+ *   mrl_cnn_act_bank is the plan and the act, on hip_stream: two launches up to M = N P = 2048 cells (the plan is one workgroup),
+ *     four beyond (the plan is then count, scan and place, the first and the last with a workgroup per 1024 cells; no workgroup
+ *     waits for another inside a kernel).
+ *     The plan writes the workspace, uint32 words, with Kp = K rounded up to a multiple of 4 and max_tiles = ceil(M / 32) + K:
+ *         [0] tiles   [1] acted   [2] out_of_range   [3] 0
+ *         [4, 4 + Kp)                          count[k], the acted cells of policy k
+ *         [4 + Kp, 4 + 2 Kp)                   start[k], where policy k's list begins in `lists`
+ *         [4 + 2 Kp, 4 + 2 Kp + 4 max_tiles)   the tile table, four words per tile: policy, first, rows (1..32), 0
+ *         the next M words (rounded up to a multiple of 4): lists -- the cells s = n P + p of policy 0, then of policy 1, ...,
+ *         each policy's in ascending s; tile t is lists[first, first + rows)
+ *         then ceil(M / 1024) rows of Kp + 4 words, the plan's own: per chunk of 1024 cells what lies in front of it (M > 2048 only)
+ *     mrl_cnn_bank_workspace_bytes(N, P, K) = 4 (4 + 2 Kp + 4 max_tiles + M rounded up to 4 + ceil(M / 1024) (Kp + 4)) (0 for K = 0
+ *     or K > 256).  Every acted
+ *     cell is in exactly one list, its own policy's; a tile holds one policy's cells; tiles = sum over k of ceil(count[k] / 32)
+ *     <= ceil(M / 32) + K.  Words behind `tiles` entries of the table and behind `acted` entries of the lists are not written.
+ *     The act is mrl_cnn_act's kernel body over those tiles: the same LDS image, the same products in the same order, the
+ *     same hash of (seed, step, n, p), the same head and flags, the same observation source (the simulator's tensor, a redirected
+ *     slot or a ring slot), with the tile's rows taken from the list and the parameters from params_dev + policy * stride.  A
+ *     sample's arithmetic reads its own rows and the tile's common weights only, so every output is bit for bit what
+ *     mrl_cnn_act gives that cell under that policy, whatever else shares the tile and whatever the order of the lists.  The
+ *     grid is sized for the bound; workgroups past `tiles` leave at once.  Record rows are written for acted cells only; values,
+ *     rewards and dones come from the critic of the cell's own policy.  ids_row, (N, P) int32 or NULL, receives the ids as this
+ *     act used them: k for an acted cell, -1 for every other.
+ *   Refusals (MRL_ERR_INVALID, nothing enqueued): those of mrl_cnn_act; K = 0 or K > 256; stride below
+ *     mrl_cnn_policy_num_params; NULL ids; a workspace below mrl_cnn_bank_workspace_bytes or off a 16-byte boundary.
+ * mrl_cnn_bank_resample: one launch, a lane per world.  Where DONE[n] != 0 (the world has just restarted itself):
+ *     episodes[n] += 1, and every seat p of `players` with ids[n, p] >= 0 takes a new id from [first_id[p], first_id[p] +
+ *     num_ids[p]) -- MRL_CNN_RESAMPLE_ROBIN: first + (id - first + 1) mod num (uint32 arithmetic); MRL_CNN_RESAMPLE_RANDOM: first +
+ *     (((h >> 8) * num) >> 24) with h the hash of (seed, episodes[n] after the increment, n, p), exact in 32 bits for num <= 256.
+ *     Nothing else changes: other worlds, seats outside `players`, negative cells.  first_id and num_ids are HOST arrays, one
+ *     entry per seat of the simulator (entries of seats outside `players` are not read).  Refused: a NULL pointer, a mode other
+ *     than the two, num_ids = 0 or first_id + num_ids > 256 for a seat of `players`, `players` as for mrl_cnn_act.
+ * mrl_rollout_cnn_bank: mrl_rollout_cnn's loop with the bank act -- for k < T: the bank act on ring slot k at row k (ids_record
+ *     row k, when given, receives that act's ids_row), the ordinary step, then, with a resample, mrl_cnn_bank_resample; then the
+ *     closing MRL_CNN_VALUE_ONLY bank act at row T (ids_record row T).  No host wait inside.  The ring, the hand-back of the
+ *     observation output and the copy of slot T are mrl_rollout_cnn's: two rollouts of T equal one of 2 T, ids and episodes
+ *     included.  With resample NULL neither ids nor episodes change (episodes may then be NULL).  Refusals: those of
+ *     mrl_cnn_act_bank and mrl_cnn_bank_resample, a NULL record or ring, NULL episodes with a resample. */
+enum { MRL_CNN_RESAMPLE_ROBIN = 1, MRL_CNN_RESAMPLE_RANDOM = 2 };
+typedef struct mrl_cnn_bank {
+    const float *params_dev;    /* (num_policies, stride) */
+    uint32_t num_policies;
+    uint64_t stride;            /* floats between rows */
+    uint32_t hidden, flags;
+} mrl_cnn_bank;
+typedef struct mrl_cnn_resample {
+    uint32_t mode;                          /* MRL_CNN_RESAMPLE_ROBIN or MRL_CNN_RESAMPLE_RANDOM */
+    const uint32_t *first_id, *num_ids;     /* host, one per seat */
+    uint64_t seed;
+} mrl_cnn_resample;
+uint64_t mrl_cnn_bank_workspace_bytes(uint32_t num_worlds, uint32_t num_players, uint32_t num_policies);
+int mrl_cnn_act_bank(mrl_sim *sim, uint32_t players, const mrl_cnn_bank *bank, const int32_t *ids_dev, const mrl_cnn_record *record_or_null,
+                     int32_t *ids_row_or_null, uint32_t row, uint64_t seed, uint32_t step, uint32_t flags, void *workspace_dev,
+                     uint64_t workspace_bytes, void *hip_stream);
+int mrl_cnn_bank_resample(mrl_sim *sim, uint32_t players, const mrl_cnn_resample *resample, int32_t *ids_dev, int32_t *episodes_dev,
+                          void *hip_stream);
+int mrl_rollout_cnn_bank(mrl_sim *sim, uint32_t players, const mrl_cnn_bank *bank, int32_t *ids_dev, int32_t *episodes_dev,
+                         const mrl_cnn_resample *resample_or_null, const mrl_cnn_record *record, int32_t *ids_record_or_null,
+                         void *obs_ring_dev, uint64_t seed, uint32_t first_step, void *workspace_dev, uint64_t workspace_bytes,
+                         void *hip_stream);
+
 /* MAPPO's update for that actor-critic on the device: R_MAPPO.ppo_update (train/MAPPO/r_mappo.py:91-164, feed-forward networks, all
  * active masks one) with ValueNorm (utils/valuenorm.py) -- gather, both forward passes, the clipped losses, backward, two
  * clip_grad_norm_ and two Adam steps -- on the flat parameter array mrl_cnn_act reads, which is updated in place.  No reference

@@ -33,6 +33,8 @@ WIDE_HIDDEN, WIDE_MAX_ACTIONS = 512, 64  # MRL_WIDE_*
 PPO_NORM_ADV, PPO_CLIP_VLOSS = 1, 2  # MRL_PPO_*
 CNN_VALUE_ONLY = 4  # MRL_CNN_VALUE_ONLY: flag of mrl_cnn_act beside POLICY_GREEDY
 CNN_HIDDEN, CNN_ACTIONS = 64, 6  # the one shape mrl_cnn_act runs
+CNN_BANK_MAX_POLICIES = 256  # the rows an mrl_cnn_bank may hold
+CNN_RESAMPLE_ROBIN, CNN_RESAMPLE_RANDOM = 1, 2  # MRL_CNN_RESAMPLE_*
 MLPBASE_VALUE_ONLY = 4  # MRL_MLPBASE_VALUE_ONLY: flag of mrl_mlpbase_act beside POLICY_GREEDY
 MLPBASE_HIDDEN, MLPBASE_OBS, MLPBASE_ACTIONS = 64, 7, 4  # the one shape mrl_mlpbase_act runs (layer_N 1 or 2)
 MAPPO_VALUENORM, MAPPO_HUBER_LOSS, MAPPO_CLIPPED_VALUE_LOSS, MAPPO_MAX_GRAD_NORM = 1, 2, 4, 8  # MRL_MAPPO_*
@@ -54,7 +56,8 @@ SYMBOLS = [
     "mrl_agent_workspace_bytes", "mrl_agent_act", "mrl_agent_credit", "mrl_gae_active", "mrl_cnn_policy_num_params",
     "mrl_cnn_workspace_bytes", "mrl_cnn_act", "mrl_rollout_cnn", "mrl_mappo_workspace_bytes", "mrl_mappo_update",
     "mrl_agent_update_workspace_bytes", "mrl_agent_update", "mrl_mlpbase_policy_num_params", "mrl_mlpbase_act",
-    "mrl_rollout_mlpbase", "mrl_mappo_mlp_workspace_bytes", "mrl_mappo_mlp_update",
+    "mrl_rollout_mlpbase", "mrl_mappo_mlp_workspace_bytes", "mrl_mappo_mlp_update", "mrl_cnn_bank_workspace_bytes",
+    "mrl_cnn_act_bank", "mrl_cnn_bank_resample", "mrl_rollout_cnn_bank",
 ]
 ABI_VERSION = 4  # MRL_ABI_VERSION of include/mrl_envs.h this binding was written against
 
@@ -127,6 +130,16 @@ CNN_RECORD_BUFFERS = ("actions", "logprobs", "values", "rewards", "dones", "next
 
 class CnnRecordDesc(ctypes.Structure):  # mrl_cnn_record
     _fields_ = [(name, ctypes.c_void_p) for name in CNN_RECORD_BUFFERS] + [("num_steps", ctypes.c_uint32)]
+
+
+class CnnBankDesc(ctypes.Structure):  # mrl_cnn_bank
+    _fields_ = [("params_dev", ctypes.c_void_p), ("num_policies", ctypes.c_uint32), ("stride", ctypes.c_uint64), ("hidden", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32)]
+
+
+class CnnResampleDesc(ctypes.Structure):  # mrl_cnn_resample
+    _fields_ = [("mode", ctypes.c_uint32), ("first_id", ctypes.POINTER(ctypes.c_uint32)), ("num_ids", ctypes.POINTER(ctypes.c_uint32)),
+                ("seed", ctypes.c_uint64)]
 
 
 class MappoPolicyDesc(ctypes.Structure):  # mrl_mappo_policy
@@ -299,6 +312,13 @@ def lib():
     L.mrl_mappo_update.argtypes = [ctypes.POINTER(MappoPolicyDesc), ctypes.POINTER(MappoOptimizerDesc), ctypes.POINTER(MappoBatch), vp,
                                    u32, u32, ctypes.POINTER(MappoConfig), vp, vp, ctypes.c_uint64, vp, vp, i32, vp]
     L.mrl_rollout_cnn.argtypes = [vp, u32, ctypes.POINTER(CnnPolicyDesc), ctypes.POINTER(CnnRecordDesc), vp, ctypes.c_uint64, u32, vp]
+    L.mrl_cnn_bank_workspace_bytes.argtypes = [u32, u32, u32]
+    L.mrl_cnn_bank_workspace_bytes.restype = ctypes.c_uint64
+    L.mrl_cnn_act_bank.argtypes = [vp, u32, ctypes.POINTER(CnnBankDesc), vp, ctypes.POINTER(CnnRecordDesc), vp, u32, ctypes.c_uint64, u32, u32,
+                                   vp, ctypes.c_uint64, vp]
+    L.mrl_cnn_bank_resample.argtypes = [vp, u32, ctypes.POINTER(CnnResampleDesc), vp, vp, vp]
+    L.mrl_rollout_cnn_bank.argtypes = [vp, u32, ctypes.POINTER(CnnBankDesc), vp, vp, ctypes.POINTER(CnnResampleDesc),
+                                       ctypes.POINTER(CnnRecordDesc), vp, vp, ctypes.c_uint64, u32, vp, ctypes.c_uint64, vp]
     L.mrl_mlpbase_policy_num_params.argtypes = [u32, u32, u32, u32]
     L.mrl_mlpbase_policy_num_params.restype = ctypes.c_uint64
     L.mrl_mlpbase_act.argtypes = [vp, u32, ctypes.POINTER(MlpBasePolicyDesc), ctypes.POINTER(MlpBaseRecordDesc), u32, ctypes.c_uint64, u32,

@@ -7,6 +7,7 @@
 #include "wide_policy.hpp"
 #include "wide_update.hpp"
 #include "cnn_policy.hpp"
+#include "cnn_bank.hpp"
 #include "cnn_update.hpp"
 #include "mlpbase_policy.hpp"
 #include "mlpbase_update.hpp"
@@ -1177,23 +1178,19 @@ int mrl_mappo_update(const mrl_mappo_policy *policy, const mrl_mappo_optimizer *
     });
 }
 
-int mrl_rollout_cnn(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, const mrl_cnn_record *record, void *obs_ring_dev,
-                    uint64_t seed, uint32_t first_step, void *hip_stream)
+// The loop of mrl_rollout_cnn and mrl_rollout_cnn_bank: act(k, slot k, closing) for k = 0..T with the ordinary step and
+// after_step(k) behind every act but the closing one, the simulator writing slot k + 1 through the observation ring.
+extern "C++" {
+template <class Act, class AfterStep>
+static int cnn_rollout_loop(mrl_sim *sim, const char *what, uint32_t T, void *obs_ring_dev, void *hip_stream, Act act, AfterStep after_step)
 {
-    mrl::CnnActArgs args{};
-    if (int rc = cnn_prepare(sim, players, policy, record, hip_stream, "mrl_rollout_cnn", &args)) return rc;
-    if (!record || !obs_ring_dev) {
-        mrl::set_error("mrl_rollout_cnn: null record or observation ring");
-        return MRL_ERR_INVALID;
-    }
     mrl::DeviceGuard on(sim->device);
     return mrl::guarded([&] {
         hipStream_t stream = (hipStream_t)hip_stream;
-        const uint32_t T = record->num_steps;
         const uint64_t slot_bytes = sim->observation_bytes();
         uint8_t *ring = static_cast<uint8_t *>(obs_ring_dev);
         const void *current = sim->observation_source();
-        if (!current || !slot_bytes) throw std::runtime_error("mrl_rollout_cnn: the simulator has no observation slab");
+        if (!current || !slot_bytes) throw std::runtime_error(std::string(what) + ": the simulator has no observation slab");
         if (current != ring) MRL_HIP(hipMemcpyAsync(ring, current, slot_bytes, hipMemcpyDeviceToDevice, stream));
         const mrl_sim::ObservationRing before = sim->observation_ring();
         struct HandBack {  // also when a launch throws
@@ -1206,17 +1203,13 @@ int mrl_rollout_cnn(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy
             }
         } hand_back{sim, before, T > 0};
         if (T) sim->set_observation_ring(ring + slot_bytes, slot_bytes, T);  // step k writes slot k + 1
-        args.seed = seed;
         for (uint32_t k = 0; k <= T; k++) {
             const bool closing = k == T;
-            args.obs = reinterpret_cast<const int8_t *>(ring + (size_t)k * slot_bytes);
-            cnn_rows(args, record, k, closing);
-            args.step = first_step + k;
-            args.flags = policy->flags | (closing ? (uint32_t)MRL_CNN_VALUE_ONLY : 0u);
-            mrl::launch_cnn_act(args, stream);
+            act(k, reinterpret_cast<const int8_t *>(ring + (size_t)k * slot_bytes), closing, stream);
             if (closing) break;
             sim->step(nullptr, stream);
             mrl::completed_step(sim, stream);
+            after_step(k, stream);
         }
         if (T) {
             // the output goes back to where it pointed, and that place receives slot T: the simulator's observations are then
@@ -1228,6 +1221,197 @@ int mrl_rollout_cnn(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy
             if (home != last) MRL_HIP(hipMemcpyAsync(home, last, slot_bytes, hipMemcpyDeviceToDevice, stream));
         }
     });
+}
+}  // extern "C++"
+
+int mrl_rollout_cnn(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, const mrl_cnn_record *record, void *obs_ring_dev,
+                    uint64_t seed, uint32_t first_step, void *hip_stream)
+{
+    mrl::CnnActArgs args{};
+    if (int rc = cnn_prepare(sim, players, policy, record, hip_stream, "mrl_rollout_cnn", &args)) return rc;
+    if (!record || !obs_ring_dev) {
+        mrl::set_error("mrl_rollout_cnn: null record or observation ring");
+        return MRL_ERR_INVALID;
+    }
+    args.seed = seed;
+    return cnn_rollout_loop(
+        sim, "mrl_rollout_cnn", record->num_steps, obs_ring_dev, hip_stream,
+        [&](uint32_t k, const int8_t *obs, bool closing, hipStream_t stream) {
+            args.obs = obs;
+            cnn_rows(args, record, k, closing);
+            args.step = first_step + k;
+            args.flags = policy->flags | (closing ? (uint32_t)MRL_CNN_VALUE_ONLY : 0u);
+            mrl::launch_cnn_act(args, stream);
+        },
+        [](uint32_t, hipStream_t) {});
+}
+
+uint64_t mrl_cnn_bank_workspace_bytes(uint32_t num_worlds, uint32_t num_players, uint32_t num_policies)
+{
+    if (num_policies == 0 || num_policies > mrl::kCnnBankMaxPolicies) return 0;
+    return mrl::cnn_bank_layout(num_worlds, num_players, num_policies).words * sizeof(uint32_t);
+}
+
+// Everything mrl_cnn_act_bank and mrl_rollout_cnn_bank check alike (cnn_prepare's checks and the bank's own); fills `args` but
+// for the observation pointer, the rows, the ids row, the seed, the step and the flags.
+static int cnn_bank_prepare(mrl_sim *sim, uint32_t players, const mrl_cnn_bank *bank, const int32_t *ids_dev, const mrl_cnn_record *record,
+                            void *workspace_dev, uint64_t workspace_bytes, void *hip_stream, const char *what, mrl::CnnBankArgs *args)
+{
+    if (!bank) {
+        mrl::set_error("%s: null bank", what);
+        return MRL_ERR_INVALID;
+    }
+    const mrl_cnn_policy row0{bank->params_dev, bank->hidden, bank->flags};
+    if (int rc = cnn_prepare(sim, players, &row0, record, hip_stream, what, &args->act)) return rc;
+    const mrl::CnnActArgs &a = args->act;
+    if (bank->num_policies == 0 || bank->num_policies > mrl::kCnnBankMaxPolicies) {
+        mrl::set_error("%s: a bank holds 1 to %u policies, not %u", what, mrl::kCnnBankMaxPolicies, bank->num_policies);
+        return MRL_ERR_INVALID;
+    }
+    const uint64_t num_params = mrl_cnn_policy_num_params(a.W, a.H, a.F, mrl::kCnnHidden, mrl::kCnnActions);
+    if (bank->stride < num_params) {
+        mrl::set_error("%s: the bank's stride of %llu floats is below the policy's %llu parameters", what, (unsigned long long)bank->stride,
+                       (unsigned long long)num_params);
+        return MRL_ERR_INVALID;
+    }
+    if (!ids_dev || (reinterpret_cast<uintptr_t>(ids_dev) & 3u)) {
+        mrl::set_error("%s: ids is null or off a 4-byte boundary", what);
+        return MRL_ERR_INVALID;
+    }
+    if ((uint64_t)a.num_worlds * a.P > 0x7fffffffull) {
+        mrl::set_error("%s: %u worlds of %u seats are more cells than the plan numbers", what, a.num_worlds, a.P);
+        return MRL_ERR_INVALID;
+    }
+    if (!workspace_dev || (reinterpret_cast<uintptr_t>(workspace_dev) & 15u) ||
+        workspace_bytes < mrl_cnn_bank_workspace_bytes(a.num_worlds, a.P, bank->num_policies)) {
+        mrl::set_error("%s: the workspace is null, off a 16-byte boundary or smaller than mrl_cnn_bank_workspace_bytes", what);
+        return MRL_ERR_INVALID;
+    }
+    args->ids = ids_dev, args->ids_row = nullptr;
+    args->workspace = static_cast<uint32_t *>(workspace_dev);
+    args->stride = bank->stride, args->num_policies = bank->num_policies;
+    return MRL_OK;
+}
+
+int mrl_cnn_act_bank(mrl_sim *sim, uint32_t players, const mrl_cnn_bank *bank, const int32_t *ids_dev, const mrl_cnn_record *record,
+                     int32_t *ids_row, uint32_t row, uint64_t seed, uint32_t step, uint32_t flags, void *workspace_dev,
+                     uint64_t workspace_bytes, void *hip_stream)
+{
+    mrl::CnnBankArgs args{};
+    if (int rc = cnn_bank_prepare(sim, players, bank, ids_dev, record, workspace_dev, workspace_bytes, hip_stream, "mrl_cnn_act_bank", &args))
+        return rc;
+    if (flags & ~(uint32_t)(MRL_POLICY_GREEDY | MRL_CNN_VALUE_ONLY)) {
+        mrl::set_error("mrl_cnn_act_bank: flags 0x%x: only MRL_POLICY_GREEDY and MRL_CNN_VALUE_ONLY exist", flags);
+        return MRL_ERR_INVALID;
+    }
+    flags |= bank->flags;
+    const bool value_only = flags & MRL_CNN_VALUE_ONLY;
+    if (value_only ? (!record || row != record->num_steps) : (record && row >= record->num_steps)) {
+        mrl::set_error("mrl_cnn_act_bank: row %u of %u; MRL_CNN_VALUE_ONLY needs a record and row == num_steps, every other act row < num_steps",
+                       row, record ? record->num_steps : 0u);
+        return MRL_ERR_INVALID;
+    }
+    mrl::DeviceGuard on(sim->device);
+    return mrl::guarded([&] {
+        args.act.obs = static_cast<const int8_t *>(sim->observation_source());
+        if (!args.act.obs) throw std::runtime_error("mrl_cnn_act_bank: the simulator has no observation slab");
+        cnn_rows(args.act, record, row, value_only);
+        args.act.seed = seed, args.act.step = step, args.act.flags = flags;
+        args.ids_row = ids_row;
+        mrl::launch_cnn_act_bank(args, (hipStream_t)hip_stream);
+    });
+}
+
+// what mrl_cnn_bank_resample and mrl_rollout_cnn_bank check of a resample; fills `args` but for ids and episodes
+static int cnn_resample_prepare(mrl_sim *sim, uint32_t players, const mrl_cnn_resample *resample, const char *what, mrl::CnnResampleArgs *args)
+{
+    if (int rc = mrl::need_healthy(sim)) return rc;
+    if (sim->game != MRL_GAME_OVERCOOKED && sim->game != MRL_GAME_SIMPLECOOKED) {
+        mrl::set_error("%s: game %d has no CNN policy (Overcooked and Simplecooked do)", what, sim->game);
+        return MRL_ERR_INVALID;
+    }
+    if (!resample || !resample->first_id || !resample->num_ids ||
+        (resample->mode != MRL_CNN_RESAMPLE_ROBIN && resample->mode != MRL_CNN_RESAMPLE_RANDOM)) {
+        mrl::set_error("%s: null resample, first_id or num_ids, or a mode other than MRL_CNN_RESAMPLE_ROBIN and MRL_CNN_RESAMPLE_RANDOM", what);
+        return MRL_ERR_INVALID;
+    }
+    mrl_tensor_desc obs{}, done{};
+    int rc = mrl::guarded([&] {
+        if (!sim->tensor(MRL_OVERCOOKED_OBS_WORLD_MAJOR, &obs) || !sim->tensor(MRL_OVERCOOKED_DONE, &done))
+            throw std::runtime_error("the simulator does not export OBS_WORLD_MAJOR / DONE");
+    });
+    if (rc) return rc;
+    const uint32_t P = (uint32_t)obs.shape[1];
+    if (players == 0 || P > 32 || (P < 32 && (players >> P) != 0)) {
+        mrl::set_error("%s: players = 0x%x must name at least one seat and none beyond the simulator's %u", what, players, P);
+        return MRL_ERR_INVALID;
+    }
+    mrl::CnnResampleArgs &a = *args;
+    a = mrl::CnnResampleArgs{};
+    for (uint32_t p = 0; p < P; p++) {
+        if (!((players >> p) & 1u)) continue;
+        const uint32_t first = resample->first_id[p], num = resample->num_ids[p];
+        if (num == 0 || first > mrl::kCnnBankMaxPolicies || num > mrl::kCnnBankMaxPolicies || first + num > mrl::kCnnBankMaxPolicies) {
+            mrl::set_error("%s: seat %u draws from [%u, %u + %u): a range is 1 to 256 ids and ends at 256 at the latest", what, p, first, first, num);
+            return MRL_ERR_INVALID;
+        }
+        a.first[p] = (uint16_t)first, a.num[p] = (uint16_t)num;
+    }
+    a.done = static_cast<const int32_t *>(done.data);
+    a.seed = resample->seed;
+    a.num_worlds = sim->num_worlds, a.P = P, a.players = players, a.mode = resample->mode;
+    return MRL_OK;
+}
+
+int mrl_cnn_bank_resample(mrl_sim *sim, uint32_t players, const mrl_cnn_resample *resample, int32_t *ids_dev, int32_t *episodes_dev,
+                          void *hip_stream)
+{
+    mrl::CnnResampleArgs args{};
+    if (int rc = cnn_resample_prepare(sim, players, resample, "mrl_cnn_bank_resample", &args)) return rc;
+    if (!ids_dev || !episodes_dev || ((reinterpret_cast<uintptr_t>(ids_dev) | reinterpret_cast<uintptr_t>(episodes_dev)) & 3u)) {
+        mrl::set_error("mrl_cnn_bank_resample: ids or episodes is null or off a 4-byte boundary");
+        return MRL_ERR_INVALID;
+    }
+    args.ids = ids_dev, args.episodes = episodes_dev;
+    mrl::DeviceGuard on(sim->device);
+    return mrl::guarded([&] { mrl::launch_cnn_bank_resample(args, (hipStream_t)hip_stream); });
+}
+
+int mrl_rollout_cnn_bank(mrl_sim *sim, uint32_t players, const mrl_cnn_bank *bank, int32_t *ids_dev, int32_t *episodes_dev,
+                         const mrl_cnn_resample *resample, const mrl_cnn_record *record, int32_t *ids_record, void *obs_ring_dev, uint64_t seed,
+                         uint32_t first_step, void *workspace_dev, uint64_t workspace_bytes, void *hip_stream)
+{
+    mrl::CnnBankArgs args{};
+    if (int rc = cnn_bank_prepare(sim, players, bank, ids_dev, record, workspace_dev, workspace_bytes, hip_stream, "mrl_rollout_cnn_bank", &args))
+        return rc;
+    if (!record || !obs_ring_dev) {
+        mrl::set_error("mrl_rollout_cnn_bank: null record or observation ring");
+        return MRL_ERR_INVALID;
+    }
+    mrl::CnnResampleArgs again{};
+    if (resample) {
+        if (int rc = cnn_resample_prepare(sim, players, resample, "mrl_rollout_cnn_bank", &again)) return rc;
+        if (!episodes_dev || (reinterpret_cast<uintptr_t>(episodes_dev) & 3u)) {
+            mrl::set_error("mrl_rollout_cnn_bank: a resample needs episodes, on a 4-byte boundary");
+            return MRL_ERR_INVALID;
+        }
+        again.ids = ids_dev, again.episodes = episodes_dev;
+    }
+    args.act.seed = seed;
+    const size_t cells = (size_t)args.act.num_worlds * args.act.P;
+    return cnn_rollout_loop(
+        sim, "mrl_rollout_cnn_bank", record->num_steps, obs_ring_dev, hip_stream,
+        [&](uint32_t k, const int8_t *obs, bool closing, hipStream_t stream) {
+            args.act.obs = obs;
+            cnn_rows(args.act, record, k, closing);
+            args.act.step = first_step + k;
+            args.act.flags = bank->flags | (closing ? (uint32_t)MRL_CNN_VALUE_ONLY : 0u);
+            args.ids_row = ids_record ? ids_record + (size_t)k * cells : nullptr;
+            mrl::launch_cnn_act_bank(args, stream);
+        },
+        [&](uint32_t, hipStream_t stream) {
+            if (resample) mrl::launch_cnn_bank_resample(again, stream);
+        });
 }
 
 uint64_t mrl_mlpbase_policy_num_params(uint32_t obs_dim, uint32_t hidden, uint32_t layer_N, uint32_t num_actions)

@@ -53,11 +53,11 @@ class CnnPolicyAgent(VectorAgent):
         envs = self.envs
         sim = getattr(envs, "sim", None)  # (SimplecookedSimulator is an OvercookedSimulator)
         if not isinstance(envs, (OvercookedMadrona, SimplecookedMadrona)) or not isinstance(sim, OvercookedSimulator):
-            raise TypeError("CnnPolicyAgent acts through mrl_cnn_act: envs must be an OvercookedMadrona of envs.overcooked_env or of "
+            raise TypeError(f"{type(self).__name__} acts through mrl_cnn_act: envs must be an OvercookedMadrona of envs.overcooked_env or of "
                             "envs.overcooked2_env (Simplecooked), got "
                             f"{type(envs).__name__} over {type(sim).__name__}; there is no torch fallback")
         if envs.device.type != "cuda":
-            raise TypeError(f"CnnPolicyAgent needs the env on the simulator's GPU (cuda:{sim.gpu_id}); got env device {envs.device}")
+            raise TypeError(f"{type(self).__name__} needs the env on the simulator's GPU (cuda:{sim.gpu_id}); got env device {envs.device}")
         return sim
 
     @property
@@ -72,6 +72,60 @@ class CnnPolicyAgent(VectorAgent):
 
     def update(self, rewards, dones):
         return None
+
+
+class CnnPopulationAgent(CnnPolicyAgent):
+    """A partner seat of either kitchen env played by a POPULATION: every world has its own member of ``bank`` (a
+    ``simulators.CnnPolicyBank``) and draws a new one when its episode ends -- the per-episode partner sampling that
+    ``add_partner_agent``'s docstring describes, per world instead of for the whole batch.  World n starts with
+    ``members[n % len(members)]`` (``members``: rows of the bank, default all); ``get_action`` is ``cnn_act_bank`` for this agent's
+    seat; ``update(rewards, dones)`` is ``cnn_resample``: where the simulator's DONE is set the world's count in ``episodes`` goes up
+    and its member is replaced, ``resample`` "robin" the next of ``members``, "random" one of them by ``random_hash(seed, episode,
+    world, seat)``, ``None`` never (``members`` must then be ``range(first, first + num)``, the range the device call draws from).
+    ``ids`` (N, P) int32 -- -1 in every other seat's column -- and ``episodes`` (N) int32 live on the device and exist from the
+    first call on.  ``CnnPolicyAgent``'s refusals, and no torch fallback."""
+
+    def __init__(self, envs, bank, members=None, resample="robin", seed=0, greedy=False):
+        from ..simulators import CNN_RESAMPLE_MODES, CnnPolicyBank
+        if not isinstance(bank, CnnPolicyBank):
+            raise TypeError("CnnPopulationAgent acts through mrl_cnn_act_bank: bank must be a simulators.CnnPolicyBank")
+        super().__init__(envs, None, seed=seed, greedy=greedy)
+        self.bank = bank
+        self.members = list(range(bank.num_policies)) if members is None else [int(k) for k in members]
+        if not self.members or any(not 0 <= k < bank.num_policies for k in self.members):
+            raise ValueError(f"members must name rows 0..{bank.num_policies - 1} of the bank")
+        if resample is not None and resample not in CNN_RESAMPLE_MODES:
+            raise ValueError(f"resample must be one of {sorted(CNN_RESAMPLE_MODES)} or None, got {resample!r}")
+        if resample is not None and self.members != list(range(self.members[0], self.members[0] + len(self.members))):
+            raise ValueError("with a resample, members must be consecutive rows of the bank: the device draws from a range")
+        self.resample = resample
+        self.ids = self.episodes = None
+        self._resample = None
+
+    def _attach(self):
+        from ..simulators import CnnResample
+        envs, device = self.envs, self.envs.static_actions.device
+        n, p = envs.num_envs, envs.num_players
+        self.ids = torch.full((n, p), -1, dtype=torch.int32, device=device)
+        self.ids[:, self.seat] = torch.tensor(self.members, dtype=torch.int32, device=device)[torch.arange(n, device=device) % len(self.members)]
+        self.episodes = torch.zeros(n, dtype=torch.int32, device=device)
+        if self.resample is not None:
+            self._resample = CnnResample(self.resample, self.members[0], len(self.members), p, self.seed)
+
+    def get_action(self, obs=None, record=True):
+        from ..simulators import cnn_act_bank
+        if self.ids is None:
+            self._attach()
+        cnn_act_bank(self._sim, self.bank, self.ids, 1 << self.seat, seed=self.seed, step=self._draws, greedy=self.greedy)
+        self._draws += 1
+        return self.envs.static_actions[self.seat]
+
+    def update(self, rewards, dones):
+        from ..simulators import cnn_resample
+        if self.ids is None:
+            self._attach()
+        if self._resample is not None:
+            cnn_resample(self._sim, self.ids, self.episodes, self._resample, None, None, players=1 << self.seat)
 
 
 class MlpBasePolicyAgent(VectorAgent):

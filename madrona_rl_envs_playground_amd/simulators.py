@@ -416,7 +416,12 @@ def _cnn_call_args(sim, policy, players, record):
     if record is not None and (not isinstance(record, CnnRecord) or record.num_worlds != shape[0] or record.num_players != shape[1] or
                                record.actions.device != p.device):
         raise ValueError(f"record must be a CnnRecord of {shape[0]} worlds and {shape[1]} players on cuda:{sim.gpu_id}")
-    mask = (1 << shape[1]) - 1 if players is None else players
+    return _seat_mask(players, shape[1])
+
+
+def _seat_mask(players, num_players):
+    """``players`` (None: every seat; a bit mask; an iterable of seats) as the C ABI's mask"""
+    mask = (1 << num_players) - 1 if players is None else players
     if not isinstance(mask, int):
         mask = sum(1 << int(seat) for seat in mask)
     return mask & 0xFFFFFFFF if 0 <= mask < 2 ** 32 else 0xFFFFFFFF
@@ -440,6 +445,202 @@ def cnn_act(sim, policy, players=None, record=None, row=0, seed=0, step=0, greed
                             _stream_ptr(sim.gpu_id))
     if rc:
         _lib.check(rc)
+
+
+class CnnPolicyBank:
+    """K ``CnnPolicy`` of one shape in one dense float32 tensor ``params`` (K, num_params) (``mrl_cnn_bank``): row k is exactly
+    what a ``CnnPolicy``'s ``params`` is.  ``policy(k)`` is a ``CnnPolicy`` whose ``params`` IS row k, a contiguous view, so
+    ``cnn_act``, ``MappoOptimizer``, ``mappo_update`` and ``.module()`` work on a member unchanged and training a member is what the
+    next ``cnn_act_bank`` reads.  1 <= K <= 256."""
+
+    def __init__(self, width, height, channels, num_policies, hidden=64, num_actions=6, device="cuda:0"):
+        self.width, self.height, self.channels, self.hidden, self.num_actions = int(width), int(height), int(channels), int(hidden), int(num_actions)
+        self.num_policies = int(num_policies)
+        if not 1 <= self.num_policies <= _lib.CNN_BANK_MAX_POLICIES:
+            raise ValueError(f"a bank holds 1 to {_lib.CNN_BANK_MAX_POLICIES} policies, not {num_policies}")
+        self.num_params = int(_lib.lib().mrl_cnn_policy_num_params(self.width, self.height, self.channels, self.hidden, self.num_actions))
+        if self.num_params == 0:
+            raise ValueError(f"mrl_cnn_act runs hidden = {_lib.CNN_HIDDEN}, num_actions = {_lib.CNN_ACTIONS} and kitchens of at least 3 x 3")
+        self.params = torch.zeros((self.num_policies, self.num_params), dtype=torch.float32, device=torch.device(device))
+        self._members = {}
+
+    def __len__(self):
+        return self.num_policies
+
+    def policy(self, k):
+        """The ``CnnPolicy`` whose ``params`` is row ``k`` of the bank (one object per row)."""
+        k = int(k)
+        if not 0 <= k < self.num_policies:
+            raise IndexError(f"the bank holds policies 0..{self.num_policies - 1}, not {k}")
+        member = self._members.get(k)
+        if member is None:
+            member = CnnPolicy.__new__(CnnPolicy)
+            member.width, member.height, member.channels, member.hidden, member.num_actions = (self.width, self.height, self.channels,
+                                                                                               self.hidden, self.num_actions)
+            member.params = self.params[k]
+            member._module = None
+            self._members[k] = member
+        return member
+
+    @classmethod
+    def from_policies(cls, policies, device=None):
+        """A bank holding copies of ``policies`` (``CnnPolicy`` of one shape), in that order (``device``: default the first one's)."""
+        policies = list(policies)
+        if not policies or not all(isinstance(p, CnnPolicy) for p in policies):
+            raise ValueError("from_policies takes a non-empty list of CnnPolicy")
+        first = policies[0]
+        shape = (first.width, first.height, first.channels, first.hidden, first.num_actions)
+        if any((p.width, p.height, p.channels, p.hidden, p.num_actions) != shape for p in policies):
+            raise ValueError("the policies of a bank must have one shape")
+        bank = cls(*shape[:3], len(policies), shape[3], shape[4], device if device is not None else first.params.device)
+        with torch.no_grad():
+            for k, p in enumerate(policies):
+                bank.params[k].copy_(p.params)
+        return bank
+
+    def desc(self):
+        return _lib.CnnBankDesc(self.params.data_ptr(), self.num_policies, self.params.stride(0), self.hidden, 0)
+
+
+def _cnn_bank_call_args(sim, bank, ids, players, record):
+    if not isinstance(bank, CnnPolicyBank):
+        raise ValueError("bank must be a CnnPolicyBank")
+    p = bank.params
+    if (not p.is_cuda or p.device.index != sim.gpu_id or p.dtype != torch.float32 or not p.is_contiguous() or
+            tuple(p.shape) != (bank.num_policies, bank.num_params)):
+        raise ValueError(f"bank.params must be a contiguous float32 tensor (num_policies, num_params) on cuda:{sim.gpu_id}")
+    mask = _cnn_call_args(sim, bank.policy(0), players, record)
+    shape = tuple(sim.observation_world_major_tensor().shape[:2])
+    _check_ids(sim, ids, shape, "ids")
+    return mask
+
+
+def _check_ids(sim, tensor, shape, name):
+    if (not isinstance(tensor, torch.Tensor) or not tensor.is_cuda or tensor.device.index != sim.gpu_id or tensor.dtype != torch.int32 or
+            tuple(tensor.shape) != tuple(shape) or not tensor.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous int32 tensor of shape {tuple(shape)} on cuda:{sim.gpu_id}")
+
+
+def _cnn_bank_workspace(sim, bank):
+    size = int(sim._L.mrl_cnn_bank_workspace_bytes(sim.num_worlds, sim.observation_world_major_tensor().shape[1], bank.num_policies))
+    workspace = getattr(sim, "_cnn_bank_workspace", None)
+    if workspace is None or workspace.numel() < size:
+        workspace = sim._cnn_bank_workspace = torch.empty(size, dtype=torch.uint8, device=torch.device("cuda", sim.gpu_id))
+    return workspace
+
+
+def cnn_act_bank(sim, bank, ids, players=None, record=None, ids_row=None, row=0, seed=0, step=0, greedy=False, value_only=False,
+                 workspace=None):
+    """``mrl_cnn_act_bank`` on torch's current stream: seat p of world n acts under row ``ids[n, p]`` of ``bank`` (a
+    ``CnnPolicyBank``) where p is in ``players`` and the id is valid; a cell at -1 keeps its ACTION entry and its record cells.
+    The plan, which sorts the cells by policy into tiles of one policy each (one launch up to 2048 cells, three beyond), then
+    ``cnn_act``'s kernel body over those tiles: every output is bit for bit ``cnn_act``'s under the cell's policy.  ``ids``: int32 (N, P) on the device;
+    ``ids_row``: int32 (N, P) that receives the ids as this act used them (-1 where it did not act).  The other arguments are
+    ``cnn_act``'s.  ``workspace``: default one the simulator keeps (``mrl_cnn_bank_workspace_bytes``; its words are in
+    include/mrl_envs.h)."""
+    mask = _cnn_bank_call_args(sim, bank, ids, players, record)
+    if ids_row is not None:
+        _check_ids(sim, ids_row, ids.shape, "ids_row")
+    if workspace is None:
+        workspace = _cnn_bank_workspace(sim, bank)
+    flags = (_lib.POLICY_GREEDY if greedy else 0) | (_lib.CNN_VALUE_ONLY if value_only else 0)
+    desc = bank.desc()
+    rc = sim._L.mrl_cnn_act_bank(sim._handle, mask, ctypes.byref(desc), ids.data_ptr(), ctypes.byref(record.struct) if record is not None else None,
+                                 ids_row.data_ptr() if ids_row is not None else None, int(row), int(seed) & (2 ** 64 - 1),
+                                 int(step) & 0xFFFFFFFF, flags, workspace.data_ptr(), workspace.numel(), _stream_ptr(sim.gpu_id))
+    if rc:
+        _lib.check(rc)
+
+
+CNN_RESAMPLE_MODES = {"robin": _lib.CNN_RESAMPLE_ROBIN, "random": _lib.CNN_RESAMPLE_RANDOM}
+
+
+class CnnResample:
+    """How finished worlds draw their next policies (``mrl_cnn_resample``): ``mode`` "robin" or "random"; ``first_id`` and
+    ``num_ids`` an int or one per seat -- seat p draws from ``[first_id[p], first_id[p] + num_ids[p])``; ``seed`` for "random"."""
+
+    def __init__(self, mode, first_id, num_ids, num_players, seed=0):
+        if mode not in CNN_RESAMPLE_MODES and mode not in CNN_RESAMPLE_MODES.values():
+            raise ValueError(f"mode must be one of {sorted(CNN_RESAMPLE_MODES)}, got {mode!r}")
+        self.mode = CNN_RESAMPLE_MODES.get(mode, mode)
+        per_seat = lambda v: [int(v)] * int(num_players) if isinstance(v, int) else [int(x) for x in v]  # noqa: E731
+        self.first_id, self.num_ids = per_seat(first_id), per_seat(num_ids)
+        if len(self.first_id) != int(num_players) or len(self.num_ids) != int(num_players):
+            raise ValueError(f"first_id and num_ids take an int or one entry per seat ({num_players})")
+        if any(f < 0 or n < 0 for f, n in zip(self.first_id, self.num_ids)):
+            raise ValueError("first_id and num_ids must not be negative")
+        self.seed = int(seed)
+        self._first = (ctypes.c_uint32 * len(self.first_id))(*self.first_id)
+        self._num = (ctypes.c_uint32 * len(self.num_ids))(*self.num_ids)
+        self.struct = _lib.CnnResampleDesc(self.mode, self._first, self._num, self.seed & (2 ** 64 - 1))
+
+
+def resample_twin(ids, episodes, done, mode, first_id, num_ids, players, seed=0):
+    """``mrl_cnn_bank_resample`` in numpy, in place on ``ids`` (N, P) int32 and ``episodes`` (N) int32; ``done`` (N)."""
+    import numpy as np
+    n_players = ids.shape[1]
+    finished = np.flatnonzero(np.asarray(done) != 0)
+    episodes[finished] += 1
+    for p in range(n_players):
+        if not (players >> p) & 1:
+            continue
+        rows = finished[ids[finished, p] >= 0]
+        first, num = np.uint32(first_id[p]), np.uint32(num_ids[p])
+        old = ids[rows, p].astype(np.uint32)
+        if CNN_RESAMPLE_MODES.get(mode, mode) == _lib.CNN_RESAMPLE_ROBIN:
+            new = first + (old - first + np.uint32(1)) % num
+        else:
+            h = random_hash(seed, episodes[rows].astype(np.uint32), rows.astype(np.uint32), np.full(rows.shape, p, dtype=np.uint32))
+            new = first + (((h >> np.uint32(8)).astype(np.uint64) * np.uint64(num)) >> np.uint64(24)).astype(np.uint32)
+        ids[rows, p] = new.astype(np.int32)
+
+
+def cnn_resample(sim, ids, episodes, mode, first_id, num_ids, players=None, seed=0):
+    """``mrl_cnn_bank_resample`` on torch's current stream: where DONE[n] != 0 -- the world has just restarted itself --
+    ``episodes[n]`` goes up by one and every seat p of ``players`` with ``ids[n, p] >= 0`` takes its next policy from
+    ``[first_id[p], first_id[p] + num_ids[p])``: "robin" the next one round the range, "random" by ``random_hash(seed, episodes[n],
+    n, p)`` (``resample_twin`` is the same in numpy).  ``mode`` may also be a ``CnnResample``, which then carries the rest."""
+    shape = tuple(sim.observation_world_major_tensor().shape[:2])
+    _check_ids(sim, ids, shape, "ids")
+    _check_ids(sim, episodes, shape[:1], "episodes")
+    resample = mode if isinstance(mode, CnnResample) else CnnResample(mode, first_id, num_ids, shape[1], seed)
+    _lib.check(sim._L.mrl_cnn_bank_resample(sim._handle, _seat_mask(players, shape[1]), ctypes.byref(resample.struct), ids.data_ptr(),
+                                            episodes.data_ptr(), _stream_ptr(sim.gpu_id)))
+
+
+CrossPlayResult = collections.namedtuple("CrossPlayResult", "mean_return episodes")  # each (Ka, Kb), on the device
+
+
+def cross_play(env, bank, members_a=None, members_b=None, greedy=True, seed=0):
+    """The cross-play matrix of ``bank``'s members on one batch of worlds: world n plays pair n mod (Ka Kb), seat 0 under
+    ``members_a[pair // Kb]`` and seat 1 under ``members_b[pair % Kb]`` (default every row of the bank).  All worlds are restarted, one
+    horizon of (``cnn_act_bank``, step) follows, no host wait inside, and the last-episode return
+    of ``enable_episode_stats`` (the team's, as seat 0 received it) is averaged per pair.  ``env``: a two-player kitchen env
+    wrapper on the GPU.  Returns ``CrossPlayResult(mean_return, episodes)``, float64 and int64 (Ka, Kb) on the device;
+    ``episodes`` is the number of worlds that played the pair."""
+    sim = env.sim
+    n, p = tuple(sim.observation_world_major_tensor().shape[:2])
+    if p != 2:
+        raise ValueError(f"cross_play pairs seat 0 with seat 1: the env has {p} seats")
+    a = list(range(bank.num_policies)) if members_a is None else [int(k) for k in members_a]
+    b = list(range(bank.num_policies)) if members_b is None else [int(k) for k in members_b]
+    if not a or not b or any(not 0 <= k < bank.num_policies for k in a + b):
+        raise ValueError(f"members must name rows 0..{bank.num_policies - 1} of the bank")
+    pairs = len(a) * len(b)
+    if n < pairs:
+        raise ValueError(f"{n} worlds cannot play {len(a)} x {len(b)} pairs")
+    device = torch.device("cuda", sim.gpu_id)
+    pair = torch.arange(n, device=device) % pairs
+    ids = torch.stack([torch.tensor(a, device=device)[pair // len(b)], torch.tensor(b, device=device)[pair % len(b)]], dim=1).to(torch.int32).contiguous()
+    sim.enable_episode_stats()
+    sim.reset_worlds(None)
+    for t in range(int(env.horizon)):
+        cnn_act_bank(sim, bank, ids, seed=seed, step=t, greedy=greedy)
+        sim.step()
+    last = sim.last_episode_return_tensor().to_torch().reshape(p, n)[0].to(torch.float64)
+    count = torch.zeros(pairs, dtype=torch.int64, device=device).index_add_(0, pair, torch.ones_like(pair))
+    total = torch.zeros(pairs, dtype=torch.float64, device=device).index_add_(0, pair, last)
+    return CrossPlayResult((total / count).view(len(a), len(b)), count.view(len(a), len(b)))
 
 
 class _MlpLayer(torch.nn.Module):
@@ -1087,24 +1288,36 @@ class MappoOptimizer(_AdamState):
         return int(out.value)
 
 
-def mappo_advantages(record, value_norm=None, gamma=0.99, gae_lambda=0.95):
+def mappo_advantages(record, value_norm=None, gamma=0.99, gae_lambda=0.95, seats=None):
     """``(advantages, returns)`` of a ``CnnRecord`` (Overcooked's or Simplecooked's, P = 1 included), each (T, N, P), as ``R_MAPPO.train`` and ``SharedReplayBuffer.compute_returns``
     form them (train/MAPPO/r_mappo.py:174-182, utils/shared_buffer.py:216-228 with ``use_gae``; every active mask one): the
     record's values denormalised when a ``ValueNorm`` is given, ``gae`` on those (``mrl_gae``: the reference's recurrence with
     ``masks[t + 1] = 1 - dones[t + 1]``), then ``(A - mean) / (std + 1e-5)`` over the whole buffer with torch's unbiased std.
     ``returns`` are in the denormalised scale, as the reference's buffer holds them.  It runs once per update, so apart from
-    ``mrl_gae`` it is a handful of torch ops on the record's device; it does not wait."""
+    ``mrl_gae`` it is a handful of torch ops on the record's device; it does not wait.
+    ``seats`` (default ``None``: as above): a list of seats; the mean and the std are then taken over those seats' columns only and
+    only those columns are normalised -- the others keep their raw GAE advantages.  That is what an ego trained against frozen
+    partners of a ``CnnPolicyBank`` needs: the partners' columns hold values of other critics."""
     if not isinstance(record, (CnnRecord, MlpBaseRecord)):
         raise ValueError("record must be a CnnRecord or an MlpBaseRecord")
+    if seats is not None:
+        seats = sorted({int(seat) for seat in seats})
+        if not seats or seats[0] < 0 or seats[-1] >= record.num_players:
+            raise ValueError(f"seats must name some of the record's seats 0..{record.num_players - 1}")
     rollout = record.rollout()
     if value_norm is not None:
         t, cols = record.num_steps, record.num_worlds * record.num_players
         values = value_norm.denormalize(record.values).contiguous()
         rollout = rollout._replace(values=values[:t].view(t, cols), next_value=values[t].view(cols))
     advantages, returns = gae(rollout, gamma, gae_lambda)
-    advantages = (advantages - advantages.mean()) / (advantages.std() + 1e-5)
     shape = (record.num_steps, record.num_worlds, record.num_players)
-    return advantages.view(shape), returns.view(shape)
+    if seats is None:
+        advantages = (advantages - advantages.mean()) / (advantages.std() + 1e-5)
+        return advantages.view(shape), returns.view(shape)
+    advantages = advantages.view(shape).clone()
+    own = advantages[:, :, seats]
+    advantages[:, :, seats] = (own - own.mean()) / (own.std() + 1e-5)
+    return advantages, returns.view(shape)
 
 
 MappoResult = collections.namedtuple("MappoResult", "stats grads")  # (K, 8) in the order of ``_lib.MAPPO_STATS`` / (K, P), or None
@@ -1279,6 +1492,36 @@ class ActsWithCnnPolicy:
         self.sim.rollout_cnn(policy, record, ring, players=players, seed=seed, first_step=first_step, greedy=greedy)
         return record, ring
 
+    def act_bank(self, bank, ids, players=None, record=None, ids_row=None, row=0, seed=0, step=0, greedy=False):
+        """``act`` with a policy per (world, seat) cell: seat p of world n acts under row ``ids[n, p]`` of ``bank`` (a
+        ``simulators.CnnPolicyBank``), cells at -1 keep their actions (``mrl_cnn_act_bank``: the plan and the act, every output bit for bit
+        ``act``'s under the cell's policy).  ``ids``: int32 (N, P) on the device.  Returns ``static_actions``."""
+        cnn_act_bank(self.sim, bank, ids, players, record, ids_row, row=row, seed=seed, step=step, greedy=greedy)
+        return self.static_actions
+
+    def rollout_bank(self, bank, ids, num_steps, episodes=None, resample=None, seed=0, first_step=0, players=None, record=None, ring=None,
+                     ids_record=None, greedy=False):
+        """``rollout`` under a bank (``mrl_rollout_cnn_bank``) -> (record, ring, ids_record): ``ids_record`` int32 (T + 1, N, P) holds
+        the ids each act used (-1 where it did not act).  ``resample`` (a ``simulators.CnnResample``) runs behind every step: worlds
+        that have just restarted draw their next policies into ``ids`` and count in ``episodes`` (int32 (N), made when ``None`` and
+        then kept by the env as ``bank_episodes``)."""
+        device = self.static_actions.device
+        if record is None:
+            record = CnnRecord(num_steps, self.num_envs, self.num_players, device)
+        if record.num_steps != int(num_steps):
+            raise ValueError(f"record holds {record.num_steps} steps, asked for {num_steps}")
+        if ring is None:
+            ring = torch.empty((int(num_steps) + 1,) + tuple(self.static_world_major_observations.shape), dtype=torch.int8, device=device)
+        if ids_record is None:
+            ids_record = torch.empty((int(num_steps) + 1, self.num_envs, self.num_players), dtype=torch.int32, device=device)
+        if episodes is None and resample is not None:
+            episodes = getattr(self, "bank_episodes", None)
+            if episodes is None:
+                episodes = self.bank_episodes = torch.zeros(self.num_envs, dtype=torch.int32, device=device)
+        self.sim.rollout_cnn_bank(bank, ids, record, ring, episodes=episodes, resample=resample, ids_record=ids_record, players=players,
+                                  seed=seed, first_step=first_step, greedy=greedy)
+        return record, ring, ids_record
+
 
 class ActsWithMlpBasePolicy:
     """Mixin of the balance-beam env wrapper (``envs/balance_beam_env.py``; ``self.sim``, ``static_actions``, ``num_envs`` and
@@ -1431,6 +1674,38 @@ class _Simulator:
         desc.flags = _lib.POLICY_GREEDY if greedy else 0
         _lib.check(self._L.mrl_rollout_cnn(self._handle, mask, ctypes.byref(desc), ctypes.byref(record.struct), obs_ring.data_ptr(),
                                            int(seed) & (2 ** 64 - 1), int(first_step) & 0xFFFFFFFF, _stream_ptr(self.gpu_id)))
+
+    def rollout_cnn_bank(self, bank, ids, record, obs_ring, episodes=None, resample=None, ids_record=None, players=None, seed=0,
+                         first_step=0, greedy=False, workspace=None):
+        """``rollout_cnn`` with ``cnn_act_bank`` in place of ``cnn_act`` (``mrl_rollout_cnn_bank``): ``ids`` int32 (N, P) assigns a
+        row of ``bank`` (a ``CnnPolicyBank``) to every cell; with ``resample`` (a ``CnnResample``) ``cnn_resample`` runs behind every
+        step on ``ids`` and ``episodes`` (int32 (N)); ``ids_record`` int32 (T + 1, N, P) receives the ids each act used.  No host
+        wait inside; two rollouts of T equal one of 2 T, ``ids`` and ``episodes`` included."""
+        mask = _cnn_bank_call_args(self, bank, ids, players, record)
+        if record is None:
+            raise ValueError("rollout_cnn_bank needs a CnnRecord")
+        cells = tuple(self.observation_world_major_tensor().shape)
+        want = (record.num_steps + 1,) + cells
+        if (not isinstance(obs_ring, torch.Tensor) or not obs_ring.is_cuda or obs_ring.device.index != self.gpu_id or
+                obs_ring.dtype not in (torch.int8, torch.uint8) or tuple(obs_ring.shape) != want or not obs_ring.is_contiguous()):
+            raise ValueError(f"obs_ring must be a contiguous int8 tensor of shape {want} on cuda:{self.gpu_id}")
+        if ids_record is not None:
+            _check_ids(self, ids_record, (record.num_steps + 1,) + cells[:2], "ids_record")
+        if resample is not None and not isinstance(resample, CnnResample):
+            raise ValueError("resample must be a CnnResample or None")
+        if episodes is not None:
+            _check_ids(self, episodes, cells[:1], "episodes")
+        elif resample is not None:
+            raise ValueError("a resample needs episodes, an int32 tensor (num_worlds,)")
+        if workspace is None:
+            workspace = _cnn_bank_workspace(self, bank)
+        desc = bank.desc()
+        desc.flags = _lib.POLICY_GREEDY if greedy else 0
+        _lib.check(self._L.mrl_rollout_cnn_bank(
+            self._handle, mask, ctypes.byref(desc), ids.data_ptr(), episodes.data_ptr() if episodes is not None else None,
+            ctypes.byref(resample.struct) if resample is not None else None, ctypes.byref(record.struct),
+            ids_record.data_ptr() if ids_record is not None else None, obs_ring.data_ptr(), int(seed) & (2 ** 64 - 1),
+            int(first_step) & 0xFFFFFFFF, workspace.data_ptr(), workspace.numel(), _stream_ptr(self.gpu_id)))
 
     def rollout_mlpbase(self, policy, record, players=None, seed=0, first_step=0, greedy=False):
         """``record.num_steps`` steps under ``policy`` (an ``MlpBasePolicy``) for the seats in ``players`` with the host out of the
