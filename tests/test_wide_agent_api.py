@@ -314,6 +314,57 @@ def test_config_walk_reaches_what_the_gpu_test_relies_on(cid, oracle_lib):
     assert 0 < d_value < 1e-4 and 0 < d_logp < 1e-3
 
 
+@pytest.mark.parametrize("game,n,seed", twin.LIVE_CASES)
+def test_live_walk_reaches_what_the_gpu_test_relies_on(game, n, seed, oracle_lib):
+    """Conditions on the closed loop of tests/test_gpu_wide_agent_live.py, walked here by the oracle and the twin alone (the
+    device's own walk differs from this one only behind a row it decided otherwise, and asserts the near-boundary cap again):
+    few rows near a boundary, episodes that end in several 1024-world blocks of the totals in the same step, world lists whose
+    length changes from step to step and lies on either side of one pass of 1024, no tie among a row's largest logits (so the
+    first-arg-max rule of GREEDY decides nothing), and an advantage pass that is coupled across its workgroups."""
+    assert [(g, m) for g, m, _ in twin.LIVE_CASES] == [(g, 2081) for g in ("hanabi_k1r5i1l1", "hanabi_k5r4i8l3", "hanabi_k2r4i1l1", "balance")]
+    assert twin.LIVE_STEPS == 12 and twin.NEAR_CAP == 0.001
+    d, s, a = twin.dims(game)
+    blocks = range(0, n, 1024)
+    near = rows = ended = ties = 0
+    together = one_idle = False
+    counts, either_side = [[], []], False
+    activity = np.zeros((2, twin.LIVE_STEPS, n), bool)
+    for t, step in enumerate(twin.twin_walk(game, n, twin.LIVE_STEPS, seed)):
+        done = step["after"]["done"] != 0
+        per_block = [int(done[b:b + 1024].sum()) for b in blocks]
+        ended += int(done.sum())
+        together |= sum(c > 0 for c in per_block) >= 2
+        one_idle |= min(per_block) == 0 < max(per_block)
+        for p, seat in enumerate(step["seats"]):
+            active = activity[p, t] = seat["active"]
+            assert (step["actions"][p][~active] == 0).all()
+            counts[p].append(int(active.sum()))
+            if not active.any():
+                continue
+            either_side |= counts[p][-1] > 1024 and bool(active[:1024].any() and active[1024:].any())
+            legal = step["before"]["mask"][p][active, :a] != 0
+            assert legal[np.arange(active.sum()), seat["twin"]["actions"]].all()
+            rows += counts[p][-1]
+            near += int(twin.near_boundary(seat["twin"]["cdf"], seat["u"]).sum())
+            top = np.sort(np.where(legal, seat["twin"]["logits"], -np.inf), axis=1)[:, -2:]
+            ties += int((top[:, 0] == top[:, 1]).sum())
+            assert 0 < seat["d"][0] < 1e-4 and 0 < seat["d"][1] < 1e-3
+    coupled = [twin.coupled_across_workgroups(activity[p], step["after"]["active"][p]) for p in range(2)]
+    print(f"{game}: {rows} active rows, {near} near a boundary, {ended} episodes ended, list lengths {counts}, coupled advantage pass "
+          f"of the seats {coupled}")
+    assert near <= twin.NEAR_CAP * rows, f"{near} of {rows} active rows lie within 1e-5 of a boundary: choose another seed"
+    assert together, "no step ends episodes in two blocks of the totals at once"
+    assert ended >= 50
+    assert ties == 0, f"{ties} rows whose two largest legal logits tie"
+    if game == "balance":
+        assert counts == [[n] * twin.LIVE_STEPS] * 2 and coupled == [False, False]  # every row of both seats: nothing to wait for
+        return
+    assert any(len(set(c)) >= 3 and max(c) > 1024 > min(c) for c in counts) and either_side
+    assert any(coupled), "t* never lies below a workgroup's own least row"
+    if game == "hanabi_k5r4i8l3":
+        assert one_idle, "no step in which one block ends episodes and another ends none"
+
+
 FIXTURE_CASES = [(regime, n) for n in (5, 70) for regime in ("coupled", "together")]
 
 

@@ -1,7 +1,8 @@
 """Float64 numpy twin of the device-side wide-policy act (``mrl_agent_act``: forward pass, head, sampling), the same function in
 torch float32 -- whose distance from the twin sets the tests' margins --, the synthetic inputs the GPU tests write into a
-simulator's tensors, and float32 numpy restatements of ``mrl_agent_credit`` and ``mrl_gae_active`` that follow
-include/mrl_envs.h operation for operation.  Nothing here touches a GPU."""
+simulator's tensors, the closed loops the CPU oracle walks under the twin (``twin_step``, which also judges the device's own walk
+step by step), and float32 numpy restatements of ``mrl_agent_credit`` and ``mrl_gae_active`` that follow include/mrl_envs.h
+operation for operation.  Nothing here touches a GPU."""
 import functools
 
 import numpy as np
@@ -268,11 +269,13 @@ def torch_forward32(agent, obs, state, mask):
         return agent.critic(s)[:, 0].double().numpy(), torch.distributions.Categorical(logits=logits).logits.double().numpy()
 
 
-def margins(agent, inputs, actions=None):
+def margins(agent, inputs, actions=None, twin=None):
     """d per kind on one case's inputs: the largest distance between torch float32 and the twin over the rows, for the values
-    and for the log-probability of ``actions`` (default: every legal action)."""
+    and for the log-probability of ``actions`` (default: every legal action).  ``twin``: what ``act`` gave on these inputs with
+    the agent's parameters, where the caller has it already (its values and log-probabilities do not depend on the draws)."""
     v32, lp32 = torch_forward32(agent, inputs["obs"], inputs["state"], inputs["mask"])
-    twin = act(flat(agent), inputs["obs"], inputs["state"], inputs["mask"], np.zeros(len(v32)))
+    if twin is None:
+        twin = act(flat(agent), inputs["obs"], inputs["state"], inputs["mask"], np.zeros(len(v32)))
     legal = inputs["mask"] != 0
     if actions is None:
         d_logp = np.abs(np.where(legal, lp32 - np.where(legal, twin["logp"], 0.0), 0.0)).max()
@@ -304,43 +307,105 @@ WALK_N, WALK_STEPS = 65, 24
 WALK_SEEDS = {"k1r5i1l1": 79, "k3r2i1l1": 77, "k2r4i1l1": 77, "k5r4i8l3": 77, "k4r5i5l2": 79, "k5r5i1l3": 79}
 
 
-def config_walk(cid, n, steps, seed):
-    """Steps a ``HanabiOracle`` of configuration ``cid`` under the twin: seat p follows ``act`` with the parameters of
-    ``make_agent(game, sorted(WEIGHTS)[p], seed=21 + p)`` -- the policies of the device's collection -- on the oracle's own
-    ``obs[:, :D]``, ``state[:, :S]``, ``mask[:, :A]`` and ``active``, with the draws ``draws(seed, t, n, p)``.  Yields per step
-    {"before" / "after": the oracle's tensors around the step, "actions" (2, n) int32, 0 where a seat is not the one to act,
-    "seats": per seat {"active", "twin": ``act`` over the active rows, "u": their draws, "d": ``margins`` of torch float32 on
-    those rows at the actions chosen, None where no row is active}}."""
+def walk_agents(game):
+    """the two seats' policies of a closed loop, the device's collection included: ``make_agent(game, sorted(WEIGHTS)[p], seed=21 + p)``"""
+    return [make_agent(game, w, seed=21 + p) for p, w in enumerate(sorted(WEIGHTS))]
+
+
+def oracle_tensors(game, orc):
+    """Copies of what both seats read of an oracle and of what its last step left: "obs", "state", "mask", "active", "reward",
+    "done".  The balance beam's state is its observation, its four actions are always legal and both seats act in every world."""
+    if game == "balance":
+        n = orc.N
+        return {"obs": orc.obs.copy(), "state": orc.obs.copy(), "mask": np.ones((2, n, 4), np.int32), "active": np.ones((2, n), np.int32),
+                "reward": orc.reward.copy(), "done": orc.done.copy()}
+    return {name: getattr(orc, name).copy() for name in ("obs", "state", "mask", "active", "reward", "done")}
+
+
+def twin_step(game, agents, tensors, seed, t, actions=None):
+    """One step's decisions of both seats, by the twin: seat p follows ``act`` with the parameters of ``agents[p]`` on the first D,
+    S and A entries of the active rows of ``tensors`` ("obs", "state", "mask", "active" of both seats, (2, n, ...)), with the
+    draws ``draws(seed, t, n, p)``.  Per seat {"active", "twin": ``act`` over the active rows, "u": their draws, "d": ``margins`` of
+    torch float32 on those rows at ``actions[p]`` (2, n) -- default: at the actions the twin chose --, None where no row is
+    active}."""
+    d, s, a = dims(game)
+    n = tensors["active"].shape[1]
+    seats = []
+    for p in range(2):
+        active = tensors["active"][p] != 0
+        inputs = {"obs": tensors["obs"][p][active, :d], "state": tensors["state"][p][active, :s], "mask": tensors["mask"][p][active, :a]}
+        u = draws(seed, t, n, p)[active]
+        out = act(flat(agents[p]), inputs["obs"], inputs["state"], inputs["mask"], u)
+        at = out["actions"] if actions is None else np.asarray(actions)[p][active]
+        seats.append({"active": active, "twin": out, "u": u, "d": margins(agents[p], inputs, at, twin=out) if active.any() else None})
+    return seats
+
+
+def twin_walk(game, n, steps, seed):
+    """Steps the oracle of ``game`` ("balance" or "hanabi_<configuration id>") under the twin: ``twin_step`` with ``walk_agents`` on the
+    oracle's own tensors.  Yields per step {"before" / "after": ``oracle_tensors`` around the step, "actions" (2, n) int32, 0 where
+    a seat is not the one to act, "seats": what ``twin_step`` gave}."""
     from oracle import oracle
     oracle.build()
-    game = "hanabi_" + cid
-    d, s, a = dims(game)
-    agents = [make_agent(game, w, seed=21 + p) for p, w in enumerate(sorted(WEIGHTS))]
-    params = [flat(agent) for agent in agents]
-    orc = oracle.HanabiOracle(hanabi_configs.BY_ID[cid], n)
-
-    def tensors():
-        return {name: getattr(orc, name).copy() for name in ("obs", "state", "mask", "active", "reward", "done")}
-
+    agents = walk_agents(game)
+    orc = oracle.BalanceOracle(n) if game == "balance" else oracle.HanabiOracle(config_of(game), n)
     for t in range(steps):
-        before = tensors()
-        actions, seats = np.zeros((2, n), np.int32), []
-        for p in range(2):
-            active = before["active"][p] != 0
-            inputs = {"obs": before["obs"][p][active, :d], "state": before["state"][p][active, :s], "mask": before["mask"][p][active, :a]}
-            u = draws(seed, t, n, p)[active]
-            out = act(params[p], inputs["obs"], inputs["state"], inputs["mask"], u)
-            actions[p, active] = out["actions"]
-            seats.append({"active": active, "twin": out, "u": u, "d": margins(agents[p], inputs, out["actions"]) if active.any() else None})
+        before = oracle_tensors(game, orc)
+        seats = twin_step(game, agents, before, seed, t)
+        actions = np.zeros((2, n), np.int32)
+        for p, seat in enumerate(seats):
+            actions[p, seat["active"]] = seat["twin"]["actions"]
         orc.step(actions)
-        yield {"before": before, "after": tensors(), "actions": actions, "seats": seats}
+        yield {"before": before, "after": oracle_tensors(game, orc), "actions": actions, "seats": seats}
     orc.close()
+
+
+def config_walk(cid, n, steps, seed):
+    """``twin_walk`` of the Hanabi configuration ``cid``: the policies of the device's collection on the oracle's own
+    ``obs[:, :D]``, ``state[:, :S]``, ``mask[:, :A]`` and ``active``"""
+    return twin_walk("hanabi_" + cid, n, steps, seed)
 
 
 @functools.lru_cache(maxsize=None)
 def walked(cid):
     """the committed walk of ``cid``, walked once and shared: a list, one entry per step"""
     return list(config_walk(cid, WALK_N, WALK_STEPS, WALK_SEEDS[cid]))
+
+
+# ---------------------------------------------------------------- the closed loop past 1024 worlds, judged step by step
+#
+# (game, worlds, seed of the draws) of tests/test_gpu_wide_agent_live.py.  2081 = 1024 + 1024 + 33: three passes of the world
+# list, three blocks of episode totals with a short last one, nine 256-world workgroups of the Hanabi step and of the
+# advantage pass with a last one of 33 worlds.  Among 2081 x 12 rows some lie within 1e-5 of a boundary whatever the seed, so
+# the loop is teacher-forced: the oracle is fed the device's actions and ``twin_step`` judges every step on the oracle's
+# tensors; a near-boundary row decided otherwise then changes the trajectory that is judged, not the verdict.
+# tests/test_wide_agent_api.py asserts on the CPU what the cases are here for:
+#   hanabi_k1r5i1l1   episodes of two moves: every block ends hundreds of episodes in every step
+#   hanabi_k5r4i8l3   code variant 0, 19 actions; steps without an ended episode, then steps in which blocks 0 and 1 end some and
+#                     block 2 none; list lengths between a few dozen and some two thousand
+#   hanabi_k2r4i1l1   list lengths around 1024, on either side of it
+#   balance           every world in step, both seats active in every row, K = 7
+LIVE_STEPS = 12
+LIVE_CASES = [("hanabi_k1r5i1l1", 2081, 79), ("hanabi_k5r4i8l3", 2081, 77), ("hanabi_k2r4i1l1", 2081, 77), ("balance", 2081, 77)]
+NEAR_CAP = 0.001  # the share of a walk's active rows that may lie within 1e-5 of a boundary
+
+
+def coupled_across_workgroups(active, next_active, group=256):
+    """Whether the advantage pass over a record's ``active`` (T, n) and ``next_active`` (n) is coupled across workgroups of ``group``
+    worlds: t* -- the least, over the worlds, of T where a world is bootstrapped and of its last active row where not -- lies
+    below T - 1, and some bootstrapped world is active at a row t >= t* that the least of its own workgroup alone lies above.
+    A t* taken per workgroup computes that row; the batch's t* leaves it at 0."""
+    active, boot = np.asarray(active) != 0, np.asarray(next_active) != 0
+    num_steps, n = active.shape
+    first = np.where(boot, num_steps, np.where(active.any(axis=0), num_steps - 1 - active[::-1].argmax(axis=0), -1))
+    t_star = int(first.min())
+    if not 0 <= t_star < num_steps - 1:
+        return False
+    for start in range(0, n, group):
+        own = int(first[start:start + group].min())
+        if own > t_star and (active[t_star:own, start:start + group] & boot[start:start + group]).any():
+            return True
+    return False
 
 
 # ---------------------------------------------------------------- the record's bookkeeping, float32, operation for operation
