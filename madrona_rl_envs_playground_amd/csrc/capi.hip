@@ -13,6 +13,7 @@
 #include "mlpbase_update.hpp"
 
 #include <algorithm>
+#include <cstdio>
 #include <cstring>
 #include <exception>
 #include <map>
@@ -995,69 +996,57 @@ uint64_t mrl_cnn_policy_num_params(uint32_t width, uint32_t height, uint32_t cha
 
 uint64_t mrl_cnn_workspace_bytes(uint32_t num_worlds, uint32_t num_players) { return mrl::kCnnWorkspaceBytes; }
 
-// Everything mrl_cnn_act and mrl_rollout_cnn check alike; fills `args` but for the observation pointer, the rows and the step.
-static int cnn_prepare(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, const mrl_cnn_record *record, void *hip_stream,
-                       const char *what, mrl::CnnActArgs *args)
+// What the acts and rollouts of MAPPO's two actor-critics (`what`: the entry point) check and fill alike, whatever the network.
+static_assert(MRL_CNN_VALUE_ONLY == MRL_MLPBASE_VALUE_ONLY, "one closing-act bit for both networks");
+
+// Behind the caller's own checks of the simulator's health and game: `out_of_scope` is why the network does not run on this
+// simulator (a rank of an exchanged batch, say) or nullptr, and the stream must not be capturing.
+static int act_scope_refusal(const char *what, const char *out_of_scope, void *hip_stream)
 {
-    if (int rc = mrl::need_healthy(sim)) return rc;
-    // the two kitchens export the same slab, flags and slot ids (Simplecooked's ExportID is Overcooked's list); the kernels take
-    // W, H, F and P at run time, so F = 5P + 10 and P = 1 need nothing of their own
-    if (sim->game != MRL_GAME_OVERCOOKED && sim->game != MRL_GAME_SIMPLECOOKED) {
-        mrl::set_error("%s: game %d has no CNN policy (Overcooked and Simplecooked do)", what, sim->game);
-        return MRL_ERR_INVALID;
-    }
-    if (sim->exchange.mine) {
-        mrl::set_error("%s: this simulator is a rank of an exchanged batch (mrl_exchange_create); sharded simulators are out of scope", what);
+    if (out_of_scope) {
+        mrl::set_error("%s: %s", what, out_of_scope);
         return MRL_ERR_INVALID;
     }
     if (mrl::capturing(hip_stream)) {
         mrl::set_error("%s: the row and the step number travel in kernel arguments, a captured call would replay them", what);
         return MRL_ERR_INVALID;
     }
-    if (!policy || !policy->params_dev || policy->hidden != mrl::kCnnHidden || (policy->flags & ~(uint32_t)MRL_POLICY_GREEDY)) {
-        mrl::set_error("%s: null policy or parameter array, hidden other than 64, or policy flags other than MRL_POLICY_GREEDY", what);
-        return MRL_ERR_INVALID;
-    }
-    if (record && (!record->actions || !record->logprobs || !record->values || !record->rewards || !record->dones || !record->next_done)) {
-        mrl::set_error("%s: the record needs every buffer but logits", what);
-        return MRL_ERR_INVALID;
-    }
-    mrl_tensor_desc obs{}, done{}, reward{}, action{};
-    int rc = mrl::guarded([&] {
-        if (!sim->tensor(MRL_OVERCOOKED_OBS_WORLD_MAJOR, &obs) || !sim->tensor(MRL_OVERCOOKED_DONE, &done) ||
-            !sim->tensor(MRL_OVERCOOKED_REWARD, &reward) || !sim->tensor(MRL_OVERCOOKED_ACTION, &action))
-            throw std::runtime_error("the simulator does not export OBS_WORLD_MAJOR / DONE / REWARD / ACTION");
-    });
-    if (rc) return rc;
-    const uint32_t P = (uint32_t)obs.shape[1], H = (uint32_t)obs.shape[2], W = (uint32_t)obs.shape[3], F = (uint32_t)obs.shape[4];
-    if (W < 3 || H < 3) {
-        mrl::set_error("%s: a %u x %u kitchen has no 3 x 3 patch", what, W, H);
-        return MRL_ERR_INVALID;
-    }
-    if (players == 0 || (P < 32 && (players >> P) != 0)) {
-        mrl::set_error("%s: players = 0x%x must name at least one seat and none beyond the simulator's %u", what, players, P);
-        return MRL_ERR_INVALID;
-    }
-    const mrl::CnnLds lds = mrl::cnn_lds(W, H, F);
-    if (lds.total > mrl::kCnnLdsLimit) {
-        mrl::set_error("%s: a %u x %u kitchen with %u channels needs an LDS image of %u bytes per workgroup, the limit is %u", what, W, H, F,
-                       lds.total, mrl::kCnnLdsLimit);
-        return MRL_ERR_INVALID;
-    }
-    mrl::CnnActArgs &a = *args;
-    a = mrl::CnnActArgs{};
-    a.params = policy->params_dev;
-    a.done = static_cast<const int32_t *>(done.data);
-    a.reward = static_cast<const int32_t *>(reward.data);
-    a.action = static_cast<int32_t *>(action.data);
-    a.W = W, a.H = H, a.F = F, a.P = P, a.num_worlds = sim->num_worlds;
-    a.players = players, a.num_seats = (uint32_t)__builtin_popcount(players);
-    a.lds = lds;
     return MRL_OK;
 }
 
-// the rows of `record` an act at `row` writes (value_only: the closing act at row T)
-static void cnn_rows(mrl::CnnActArgs &a, const mrl_cnn_record *record, uint32_t row, bool value_only)
+extern "C++" {
+// the record's buffers every act writes; `own`: the network's own buffers are there too
+template <class Record>
+static int act_record_refusal(const char *what, const Record *record, bool own)
+{
+    if (record && (!record->actions || !record->logprobs || !record->values || !record->rewards || !record->dones || !record->next_done || !own)) {
+        mrl::set_error("%s: the record needs every buffer but logits", what);
+        return MRL_ERR_INVALID;
+    }
+    return MRL_OK;
+}
+
+// An act's own flags (`only`: the name of its closing-act bit, for the message) and its row: the policy's flags join in, the
+// closing act needs a record and row == num_steps, every other act row < num_steps.
+template <class Record>
+static int act_row_refusal(const char *what, const char *only, uint32_t &flags, uint32_t policy_flags, const Record *record, uint32_t row)
+{
+    if (flags & ~(uint32_t)(MRL_POLICY_GREEDY | MRL_CNN_VALUE_ONLY)) {
+        mrl::set_error("%s: flags 0x%x: only MRL_POLICY_GREEDY and %s exist", what, flags, only);
+        return MRL_ERR_INVALID;
+    }
+    flags |= policy_flags;  // MRL_POLICY_GREEDY may travel with the policy (the rollouts have no flags of their own)
+    if (flags & MRL_CNN_VALUE_ONLY ? (!record || row != record->num_steps) : (record && row >= record->num_steps)) {
+        mrl::set_error("%s: row %u of %u; %s needs a record and row == num_steps, every other act row < num_steps", what, row,
+                       record ? record->num_steps : 0u, only);
+        return MRL_ERR_INVALID;
+    }
+    return MRL_OK;
+}
+
+// the rows of `record` an act at `row` writes (value_only: the closing act at row T); `actions`: the width of a row of logits
+template <class Record>
+static void record_rows(mrl::ActArgs &a, const Record *record, uint32_t row, bool value_only, uint32_t actions)
 {
     a.actions_row = nullptr, a.logprobs_row = a.values_row = a.rewards_row = a.dones_row = a.logits_row = nullptr;
     a.nets = 1u;
@@ -1070,7 +1059,69 @@ static void cnn_rows(mrl::CnnActArgs &a, const mrl_cnn_record *record, uint32_t 
     if (value_only) return;
     a.actions_row = record->actions + row * cells;
     a.logprobs_row = record->logprobs + row * cells;
-    a.logits_row = record->logits ? record->logits + row * cells * mrl::kCnnActions : nullptr;
+    a.logits_row = record->logits ? record->logits + row * cells * actions : nullptr;
+}
+}  // extern "C++"
+
+// the seat mask against the simulator's P seats, then the part of the arguments every act carries
+static int act_seats(mrl::ActArgs &a, const char *what, mrl_sim *sim, uint32_t players, uint32_t P, const mrl_tensor_desc &done,
+                     const mrl_tensor_desc &action)
+{
+    if (players == 0 || (P < 32 && (players >> P) != 0)) {
+        mrl::set_error("%s: players = 0x%x must name at least one seat and none beyond the simulator's %u", what, players, P);
+        return MRL_ERR_INVALID;
+    }
+    a.done = static_cast<const int32_t *>(done.data);
+    a.action = static_cast<int32_t *>(action.data);
+    a.P = P, a.num_worlds = sim->num_worlds;
+    a.players = players, a.num_seats = (uint32_t)__builtin_popcount(players);
+    return MRL_OK;
+}
+
+// Everything mrl_cnn_act and mrl_rollout_cnn check alike; fills `args` but for the observation pointer, the rows and the step.
+static int cnn_prepare(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, const mrl_cnn_record *record, void *hip_stream,
+                       const char *what, mrl::CnnActArgs *args)
+{
+    // the two kitchens export the same slab, flags and slot ids (Simplecooked's ExportID is Overcooked's list); the kernels take
+    // W, H, F and P at run time, so F = 5P + 10 and P = 1 need nothing of their own
+    if (int rc = mrl::need_healthy(sim)) return rc;
+    if (sim->game != MRL_GAME_OVERCOOKED && sim->game != MRL_GAME_SIMPLECOOKED) {
+        mrl::set_error("%s: game %d has no CNN policy (Overcooked and Simplecooked do)", what, sim->game);
+        return MRL_ERR_INVALID;
+    }
+    const char *sharded = "this simulator is a rank of an exchanged batch (mrl_exchange_create); sharded simulators are out of scope";
+    if (int rc = act_scope_refusal(what, sim->exchange.mine ? sharded : nullptr, hip_stream)) return rc;
+    if (!policy || !policy->params_dev || policy->hidden != mrl::kCnnHidden || (policy->flags & ~(uint32_t)MRL_POLICY_GREEDY)) {
+        mrl::set_error("%s: null policy or parameter array, hidden other than 64, or policy flags other than MRL_POLICY_GREEDY", what);
+        return MRL_ERR_INVALID;
+    }
+    if (int rc = act_record_refusal(what, record, true)) return rc;
+    mrl_tensor_desc obs{}, done{}, reward{}, action{};
+    int rc = mrl::guarded([&] {
+        if (!sim->tensor(MRL_OVERCOOKED_OBS_WORLD_MAJOR, &obs) || !sim->tensor(MRL_OVERCOOKED_DONE, &done) ||
+            !sim->tensor(MRL_OVERCOOKED_REWARD, &reward) || !sim->tensor(MRL_OVERCOOKED_ACTION, &action))
+            throw std::runtime_error("the simulator does not export OBS_WORLD_MAJOR / DONE / REWARD / ACTION");
+    });
+    if (rc) return rc;
+    const uint32_t P = (uint32_t)obs.shape[1], H = (uint32_t)obs.shape[2], W = (uint32_t)obs.shape[3], F = (uint32_t)obs.shape[4];
+    if (W < 3 || H < 3) {
+        mrl::set_error("%s: a %u x %u kitchen has no 3 x 3 patch", what, W, H);
+        return MRL_ERR_INVALID;
+    }
+    mrl::CnnActArgs &a = *args;
+    a = mrl::CnnActArgs{};
+    if (int rc = act_seats(a, what, sim, players, P, done, action)) return rc;
+    const mrl::CnnLds lds = mrl::cnn_lds(W, H, F);
+    if (lds.total > mrl::kCnnLdsLimit) {
+        mrl::set_error("%s: a %u x %u kitchen with %u channels needs an LDS image of %u bytes per workgroup, the limit is %u", what, W, H, F,
+                       lds.total, mrl::kCnnLdsLimit);
+        return MRL_ERR_INVALID;
+    }
+    a.params = policy->params_dev;
+    a.reward = static_cast<const int32_t *>(reward.data);
+    a.W = W, a.H = H, a.F = F;
+    a.lds = lds;
+    return MRL_OK;
 }
 
 int mrl_cnn_act(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, const mrl_cnn_record *record, uint32_t row, uint64_t seed,
@@ -1078,17 +1129,8 @@ int mrl_cnn_act(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, co
 {
     mrl::CnnActArgs args{};
     if (int rc = cnn_prepare(sim, players, policy, record, hip_stream, "mrl_cnn_act", &args)) return rc;
-    if (flags & ~(uint32_t)(MRL_POLICY_GREEDY | MRL_CNN_VALUE_ONLY)) {
-        mrl::set_error("mrl_cnn_act: flags 0x%x: only MRL_POLICY_GREEDY and MRL_CNN_VALUE_ONLY exist", flags);
-        return MRL_ERR_INVALID;
-    }
-    flags |= policy->flags;  // MRL_POLICY_GREEDY may travel with the policy (mrl_rollout_cnn has no flags of its own)
+    if (int rc = act_row_refusal("mrl_cnn_act", "MRL_CNN_VALUE_ONLY", flags, policy->flags, record, row)) return rc;
     const bool value_only = flags & MRL_CNN_VALUE_ONLY;
-    if (value_only ? (!record || row != record->num_steps) : (record && row >= record->num_steps)) {
-        mrl::set_error("mrl_cnn_act: row %u of %u; MRL_CNN_VALUE_ONLY needs a record and row == num_steps, every other act row < num_steps", row,
-                       record ? record->num_steps : 0u);
-        return MRL_ERR_INVALID;
-    }
     if (!workspace_dev || (reinterpret_cast<uintptr_t>(workspace_dev) & 15u) ||
         workspace_bytes < mrl_cnn_workspace_bytes(sim->num_worlds, args.P)) {
         mrl::set_error("mrl_cnn_act: the workspace is null, off a 16-byte boundary or smaller than mrl_cnn_workspace_bytes");
@@ -1098,7 +1140,7 @@ int mrl_cnn_act(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, co
     return mrl::guarded([&] {
         args.obs = static_cast<const int8_t *>(sim->observation_source());
         if (!args.obs) throw std::runtime_error("mrl_cnn_act: the simulator has no observation slab");
-        cnn_rows(args, record, row, value_only);
+        record_rows(args, record, row, value_only, mrl::kCnnActions);
         args.seed = seed, args.step = step, args.flags = flags;
         mrl::launch_cnn_act(args, (hipStream_t)hip_stream);
     });
@@ -1129,47 +1171,70 @@ int mrl_mappo_workspace_bytes(uint32_t width, uint32_t height, uint32_t channels
     return MRL_OK;
 }
 
+// What mrl_mappo_update and mrl_mappo_mlp_update (`what`; `sizer`: its workspace function) refuse alike.  The network's own part
+// comes from the caller once the pointers are known to be there: shape(described) returns why the shape cannot run, or nullptr,
+// and describes the shape for the message; actor_params() is the actor's parameter count; obs_words: the batch's observations
+// are 4-byte words, to be checked with the other arrays.
+extern "C++" {
+template <class Policy, class Batch, class Shape, class ActorParams>
+static int mappo_update_refusal(const char *what, const char *sizer, const Policy *policy, const mrl_mappo_optimizer *opt, const Batch *batch,
+                                const int32_t *indices_dev, uint32_t num_minibatches, uint32_t minibatch_size, const mrl_mappo_config *cfg,
+                                float *value_norm_state, void *workspace_dev, uint64_t workspace_bytes, float *stats_dev_or_null,
+                                float *grads_dev_or_null, void *hip_stream, bool obs_words, Shape shape, ActorParams actor_params)
+{
+    if (!policy || !opt || !batch || (!indices_dev && num_minibatches) || !cfg || !workspace_dev) {  // (no rows: no index array)
+        mrl::set_error("%s: null policy, optimizer, batch, index array, configuration or workspace", what);
+        return MRL_ERR_INVALID;
+    }
+    if (!policy->params_dev || !opt->params_dev || !opt->exp_avg || !opt->exp_avg_sq || !batch->obs || !batch->actions || !batch->logprobs ||
+        !batch->value_preds || !batch->returns || !batch->advantages) {
+        mrl::set_error("%s: null parameter, moment or batch array", what);
+        return MRL_ERR_INVALID;
+    }
+    if (policy->params_dev != opt->params_dev) {
+        mrl::set_error("%s: the policy's and the optimizer's params_dev must be the same array", what);
+        return MRL_ERR_INVALID;
+    }
+    if (cfg->flags & ~mrl::kMappoKnownFlags) {
+        mrl::set_error("%s: flags 0x%x: only the four MRL_MAPPO_* bits exist", what, cfg->flags);
+        return MRL_ERR_INVALID;
+    }
+    if ((cfg->flags & MRL_MAPPO_VALUENORM) && !value_norm_state) {
+        mrl::set_error("%s: MRL_MAPPO_VALUENORM needs value_norm_state", what);
+        return MRL_ERR_INVALID;
+    }
+    char described[96];
+    const char *why = shape(described, sizeof described);
+    if (why || batch->size == 0) {
+        mrl::set_error("%s: %s (%s, minibatch_size %u, batch size %u)", what, why ? why : "the batch must hold at least one sample", described,
+                       minibatch_size, batch->size);
+        return MRL_ERR_INVALID;
+    }
+    const uint64_t need_bytes = mrl::mappo_workspace(actor_params(), minibatch_size, num_minibatches).total * sizeof(float);
+    const void *words[] = {opt->params_dev, opt->exp_avg, opt->exp_avg_sq, obs_words ? batch->obs : nullptr, batch->actions, batch->logprobs,
+                           batch->value_preds, batch->returns, batch->advantages, indices_dev, value_norm_state, stats_dev_or_null,
+                           grads_dev_or_null};
+    uintptr_t low_bits = 0;
+    for (const void *p : words) low_bits |= reinterpret_cast<uintptr_t>(p) & 3u;
+    return update_refusal(what, sizer, workspace_bytes, need_bytes, workspace_dev, low_bits,
+                          "the float and int32 arrays must start on 4-byte boundaries", hip_stream);
+}
+}  // extern "C++"
+
 int mrl_mappo_update(const mrl_mappo_policy *policy, const mrl_mappo_optimizer *opt, const mrl_mappo_batch *batch,
                      const int32_t *indices_dev, uint32_t num_minibatches, uint32_t minibatch_size, const mrl_mappo_config *cfg,
                      float *value_norm_state, void *workspace_dev, uint64_t workspace_bytes, float *stats_dev_or_null,
                      float *grads_dev_or_null, int gpu_id, void *hip_stream)
 {
-    if (!policy || !opt || !batch || (!indices_dev && num_minibatches) || !cfg || !workspace_dev) {  // (no rows: no index array)
-        mrl::set_error("mrl_mappo_update: null policy, optimizer, batch, index array, configuration or workspace");
-        return MRL_ERR_INVALID;
-    }
-    if (!policy->params_dev || !opt->params_dev || !opt->exp_avg || !opt->exp_avg_sq || !batch->obs || !batch->actions || !batch->logprobs ||
-        !batch->value_preds || !batch->returns || !batch->advantages) {
-        mrl::set_error("mrl_mappo_update: null parameter, moment or batch array");
-        return MRL_ERR_INVALID;
-    }
-    if (policy->params_dev != opt->params_dev) {
-        mrl::set_error("mrl_mappo_update: the policy's and the optimizer's params_dev must be the same array");
-        return MRL_ERR_INVALID;
-    }
-    if (cfg->flags & ~mrl::kMappoKnownFlags) {
-        mrl::set_error("mrl_mappo_update: flags 0x%x: only the four MRL_MAPPO_* bits exist", cfg->flags);
-        return MRL_ERR_INVALID;
-    }
-    if ((cfg->flags & MRL_MAPPO_VALUENORM) && !value_norm_state) {
-        mrl::set_error("mrl_mappo_update: MRL_MAPPO_VALUENORM needs value_norm_state");
-        return MRL_ERR_INVALID;
-    }
-    const char *why = mappo_shape_error(policy->width, policy->height, policy->channels, policy->hidden, minibatch_size);
-    if (why || batch->size == 0) {
-        mrl::set_error("mrl_mappo_update: %s (width %u, height %u, channels %u, hidden %u, minibatch_size %u, batch size %u)",
-                       why ? why : "the batch must hold at least one sample", policy->width, policy->height, policy->channels, policy->hidden,
-                       minibatch_size, batch->size);
-        return MRL_ERR_INVALID;
-    }
-    const uint64_t actor = mrl::cnn_net_params(policy->width, policy->height, policy->channels, mrl::kCnnActions);
-    const uint64_t need_bytes = mrl::mappo_workspace(actor, minibatch_size, num_minibatches).total * sizeof(float);
-    const void *words[] = {opt->params_dev, opt->exp_avg, opt->exp_avg_sq, batch->actions, batch->logprobs, batch->value_preds, batch->returns,
-                           batch->advantages, indices_dev, value_norm_state, stats_dev_or_null, grads_dev_or_null};
-    uintptr_t low_bits = 0;
-    for (const void *p : words) low_bits |= reinterpret_cast<uintptr_t>(p) & 3u;
-    if (int rc = update_refusal("mrl_mappo_update", "mrl_mappo_workspace_bytes", workspace_bytes, need_bytes, workspace_dev, low_bits,
-                                "the float and int32 arrays must start on 4-byte boundaries", hip_stream))
+    if (int rc = mappo_update_refusal(
+            "mrl_mappo_update", "mrl_mappo_workspace_bytes", policy, opt, batch, indices_dev, num_minibatches, minibatch_size, cfg, value_norm_state,
+            workspace_dev, workspace_bytes, stats_dev_or_null, grads_dev_or_null, hip_stream, false,
+            [&](char *described, size_t room) {
+                snprintf(described, room, "width %u, height %u, channels %u, hidden %u", policy->width, policy->height, policy->channels,
+                         policy->hidden);
+                return mappo_shape_error(policy->width, policy->height, policy->channels, policy->hidden, minibatch_size);
+            },
+            [&] { return mrl::cnn_net_params(policy->width, policy->height, policy->channels, mrl::kCnnActions); }))
         return rc;
     mrl::DeviceGuard on(gpu_id);
     return guarded([&] {
@@ -1238,7 +1303,7 @@ int mrl_rollout_cnn(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy
         sim, "mrl_rollout_cnn", record->num_steps, obs_ring_dev, hip_stream,
         [&](uint32_t k, const int8_t *obs, bool closing, hipStream_t stream) {
             args.obs = obs;
-            cnn_rows(args, record, k, closing);
+            record_rows(args, record, k, closing, mrl::kCnnActions);
             args.step = first_step + k;
             args.flags = policy->flags | (closing ? (uint32_t)MRL_CNN_VALUE_ONLY : 0u);
             mrl::launch_cnn_act(args, stream);
@@ -1300,22 +1365,13 @@ int mrl_cnn_act_bank(mrl_sim *sim, uint32_t players, const mrl_cnn_bank *bank, c
     mrl::CnnBankArgs args{};
     if (int rc = cnn_bank_prepare(sim, players, bank, ids_dev, record, workspace_dev, workspace_bytes, hip_stream, "mrl_cnn_act_bank", &args))
         return rc;
-    if (flags & ~(uint32_t)(MRL_POLICY_GREEDY | MRL_CNN_VALUE_ONLY)) {
-        mrl::set_error("mrl_cnn_act_bank: flags 0x%x: only MRL_POLICY_GREEDY and MRL_CNN_VALUE_ONLY exist", flags);
-        return MRL_ERR_INVALID;
-    }
-    flags |= bank->flags;
+    if (int rc = act_row_refusal("mrl_cnn_act_bank", "MRL_CNN_VALUE_ONLY", flags, bank->flags, record, row)) return rc;
     const bool value_only = flags & MRL_CNN_VALUE_ONLY;
-    if (value_only ? (!record || row != record->num_steps) : (record && row >= record->num_steps)) {
-        mrl::set_error("mrl_cnn_act_bank: row %u of %u; MRL_CNN_VALUE_ONLY needs a record and row == num_steps, every other act row < num_steps",
-                       row, record ? record->num_steps : 0u);
-        return MRL_ERR_INVALID;
-    }
     mrl::DeviceGuard on(sim->device);
     return mrl::guarded([&] {
         args.act.obs = static_cast<const int8_t *>(sim->observation_source());
         if (!args.act.obs) throw std::runtime_error("mrl_cnn_act_bank: the simulator has no observation slab");
-        cnn_rows(args.act, record, row, value_only);
+        record_rows(args.act, record, row, value_only, mrl::kCnnActions);
         args.act.seed = seed, args.act.step = step, args.act.flags = flags;
         args.ids_row = ids_row;
         mrl::launch_cnn_act_bank(args, (hipStream_t)hip_stream);
@@ -1403,7 +1459,7 @@ int mrl_rollout_cnn_bank(mrl_sim *sim, uint32_t players, const mrl_cnn_bank *ban
         sim, "mrl_rollout_cnn_bank", record->num_steps, obs_ring_dev, hip_stream,
         [&](uint32_t k, const int8_t *obs, bool closing, hipStream_t stream) {
             args.act.obs = obs;
-            cnn_rows(args.act, record, k, closing);
+            record_rows(args.act, record, k, closing, mrl::kCnnActions);
             args.act.step = first_step + k;
             args.act.flags = bank->flags | (closing ? (uint32_t)MRL_CNN_VALUE_ONLY : 0u);
             args.ids_row = ids_record ? ids_record + (size_t)k * cells : nullptr;
@@ -1431,26 +1487,16 @@ static int mlpbase_prepare(mrl_sim *sim, uint32_t players, const mrl_mlpbase_pol
         mrl::set_error("%s: game %d has no MLPBase policy (the balance beam does)", what, sim->game);
         return MRL_ERR_INVALID;
     }
-    if (sim->exchange.mine || sim->capturable()) {
-        mrl::set_error("%s: this simulator has been through mrl_exchange_create or mrl_prepare_graph_capture; sharded and captured "
-                       "simulators are out of scope", what);
-        return MRL_ERR_INVALID;
-    }
-    if (mrl::capturing(hip_stream)) {
-        mrl::set_error("%s: the row and the step number travel in kernel arguments, a captured call would replay them", what);
-        return MRL_ERR_INVALID;
-    }
+    const char *prepared = "this simulator has been through mrl_exchange_create or mrl_prepare_graph_capture; sharded and captured "
+                           "simulators are out of scope";
+    if (int rc = act_scope_refusal(what, sim->exchange.mine || sim->capturable() ? prepared : nullptr, hip_stream)) return rc;
     if (!policy || !policy->params_dev || policy->hidden != mrl::kMlpBaseHidden || policy->layer_N < 1 ||
         policy->layer_N > mrl::kMlpBaseMaxLayerN || (policy->flags & ~(uint32_t)MRL_POLICY_GREEDY)) {
         mrl::set_error("%s: null policy or parameter array, hidden other than 64, layer_N other than 1 or 2, or policy flags other than "
                        "MRL_POLICY_GREEDY", what);
         return MRL_ERR_INVALID;
     }
-    if (record && (!record->actions || !record->logprobs || !record->values || !record->rewards || !record->dones || !record->next_done ||
-                   !record->obs)) {
-        mrl::set_error("%s: the record needs every buffer but logits", what);
-        return MRL_ERR_INVALID;
-    }
+    if (int rc = act_record_refusal(what, record, record && record->obs)) return rc;
     uintptr_t low_bits = reinterpret_cast<uintptr_t>(policy->params_dev);
     if (record)
         for (const void *p : {(const void *)record->actions, (const void *)record->logprobs, (const void *)record->values,
@@ -1470,40 +1516,21 @@ static int mlpbase_prepare(mrl_sim *sim, uint32_t players, const mrl_mlpbase_pol
             throw std::runtime_error("unexpected tensor layout (OBSERVATION int32 (P, N, 7), REWARD float32, ACTION int32)");
     });
     if (rc) return rc;
-    const uint32_t P = (uint32_t)obs.shape[0];
-    if (players == 0 || (P < 32 && (players >> P) != 0)) {
-        mrl::set_error("%s: players = 0x%x must name at least one seat and none beyond the simulator's %u", what, players, P);
-        return MRL_ERR_INVALID;
-    }
     mrl::MlpBaseActArgs &a = *args;
     a = mrl::MlpBaseActArgs{};
+    if (int rc = act_seats(a, what, sim, players, (uint32_t)obs.shape[0], done, action)) return rc;
     a.params = policy->params_dev;
     a.obs = static_cast<const int32_t *>(obs.data);
-    a.done = static_cast<const int32_t *>(done.data);
     a.reward = static_cast<const float *>(reward.data);
-    a.action = static_cast<int32_t *>(action.data);
-    a.P = P, a.num_worlds = sim->num_worlds;
-    a.players = players, a.num_seats = (uint32_t)__builtin_popcount(players);
     a.layer_N = policy->layer_N;
     return MRL_OK;
 }
 
-// the rows of `record` an act at `row` writes (value_only: the closing act at row T)
+// the rows of `record` an act at `row` writes: record_rows', and the row of observations every act copies
 static void mlpbase_rows(mrl::MlpBaseActArgs &a, const mrl_mlpbase_record *record, uint32_t row, bool value_only)
 {
-    a.actions_row = nullptr, a.obs_row = nullptr, a.logprobs_row = a.values_row = a.rewards_row = a.dones_row = a.logits_row = nullptr;
-    a.nets = 1u;
-    if (!record) return;
-    const size_t cells = (size_t)a.num_worlds * a.P;
-    a.nets = value_only ? 2u : 3u;
-    a.values_row = record->values + row * cells;
-    a.obs_row = record->obs + row * cells * mrl::kMlpBaseObs;
-    a.rewards_row = row ? record->rewards + (row - 1) * cells : nullptr;
-    a.dones_row = value_only ? record->next_done : record->dones + row * cells;
-    if (value_only) return;
-    a.actions_row = record->actions + row * cells;
-    a.logprobs_row = record->logprobs + row * cells;
-    a.logits_row = record->logits ? record->logits + row * cells * mrl::kMlpBaseActions : nullptr;
+    record_rows(a, record, row, value_only, mrl::kMlpBaseActions);
+    a.obs_row = record ? record->obs + row * (size_t)a.num_worlds * a.P * mrl::kMlpBaseObs : nullptr;
 }
 
 int mrl_mlpbase_act(mrl_sim *sim, uint32_t players, const mrl_mlpbase_policy *policy, const mrl_mlpbase_record *record, uint32_t row,
@@ -1511,17 +1538,8 @@ int mrl_mlpbase_act(mrl_sim *sim, uint32_t players, const mrl_mlpbase_policy *po
 {
     mrl::MlpBaseActArgs args{};
     if (int rc = mlpbase_prepare(sim, players, policy, record, hip_stream, "mrl_mlpbase_act", &args)) return rc;
-    if (flags & ~(uint32_t)(MRL_POLICY_GREEDY | MRL_MLPBASE_VALUE_ONLY)) {
-        mrl::set_error("mrl_mlpbase_act: flags 0x%x: only MRL_POLICY_GREEDY and MRL_MLPBASE_VALUE_ONLY exist", flags);
-        return MRL_ERR_INVALID;
-    }
-    flags |= policy->flags;  // MRL_POLICY_GREEDY may travel with the policy (mrl_rollout_mlpbase has no flags of its own)
+    if (int rc = act_row_refusal("mrl_mlpbase_act", "MRL_MLPBASE_VALUE_ONLY", flags, policy->flags, record, row)) return rc;
     const bool value_only = flags & MRL_MLPBASE_VALUE_ONLY;
-    if (value_only ? (!record || row != record->num_steps) : (record && row >= record->num_steps)) {
-        mrl::set_error("mrl_mlpbase_act: row %u of %u; MRL_MLPBASE_VALUE_ONLY needs a record and row == num_steps, every other act row < "
-                       "num_steps", row, record ? record->num_steps : 0u);
-        return MRL_ERR_INVALID;
-    }
     mrl::DeviceGuard on(sim->device);
     return mrl::guarded([&] {
         mlpbase_rows(args, record, row, value_only);
@@ -1585,41 +1603,14 @@ int mrl_mappo_mlp_update(const mrl_mlpbase_policy *policy, const mrl_mappo_optim
                          float *value_norm_state, void *workspace_dev, uint64_t workspace_bytes, float *stats_dev_or_null,
                          float *grads_dev_or_null, int gpu_id, void *hip_stream)
 {
-    if (!policy || !opt || !batch || (!indices_dev && num_minibatches) || !cfg || !workspace_dev) {  // (no rows: no index array)
-        mrl::set_error("mrl_mappo_mlp_update: null policy, optimizer, batch, index array, configuration or workspace");
-        return MRL_ERR_INVALID;
-    }
-    if (!policy->params_dev || !opt->params_dev || !opt->exp_avg || !opt->exp_avg_sq || !batch->obs || !batch->actions || !batch->logprobs ||
-        !batch->value_preds || !batch->returns || !batch->advantages) {
-        mrl::set_error("mrl_mappo_mlp_update: null parameter, moment or batch array");
-        return MRL_ERR_INVALID;
-    }
-    if (policy->params_dev != opt->params_dev) {
-        mrl::set_error("mrl_mappo_mlp_update: the policy's and the optimizer's params_dev must be the same array");
-        return MRL_ERR_INVALID;
-    }
-    if (cfg->flags & ~mrl::kMappoKnownFlags) {
-        mrl::set_error("mrl_mappo_mlp_update: flags 0x%x: only the four MRL_MAPPO_* bits exist", cfg->flags);
-        return MRL_ERR_INVALID;
-    }
-    if ((cfg->flags & MRL_MAPPO_VALUENORM) && !value_norm_state) {
-        mrl::set_error("mrl_mappo_mlp_update: MRL_MAPPO_VALUENORM needs value_norm_state");
-        return MRL_ERR_INVALID;
-    }
-    const char *why = mappo_mlp_shape_error(mrl::kMlpBaseObs, policy->hidden, policy->layer_N, mrl::kMlpBaseActions, minibatch_size);
-    if (why || batch->size == 0) {
-        mrl::set_error("mrl_mappo_mlp_update: %s (hidden %u, layer_N %u, minibatch_size %u, batch size %u)",
-                       why ? why : "the batch must hold at least one sample", policy->hidden, policy->layer_N, minibatch_size, batch->size);
-        return MRL_ERR_INVALID;
-    }
-    const uint64_t actor = mrl::mlpbase_net_params(policy->layer_N, mrl::kMlpBaseActions);
-    const uint64_t need_bytes = mrl::mappo_workspace(actor, minibatch_size, num_minibatches).total * sizeof(float);
-    const void *words[] = {opt->params_dev, opt->exp_avg, opt->exp_avg_sq, batch->obs, batch->actions, batch->logprobs, batch->value_preds,
-                           batch->returns, batch->advantages, indices_dev, value_norm_state, stats_dev_or_null, grads_dev_or_null};
-    uintptr_t low_bits = 0;
-    for (const void *p : words) low_bits |= reinterpret_cast<uintptr_t>(p) & 3u;
-    if (int rc = update_refusal("mrl_mappo_mlp_update", "mrl_mappo_mlp_workspace_bytes", workspace_bytes, need_bytes, workspace_dev, low_bits,
-                                "the float and int32 arrays must start on 4-byte boundaries", hip_stream))
+    if (int rc = mappo_update_refusal(
+            "mrl_mappo_mlp_update", "mrl_mappo_mlp_workspace_bytes", policy, opt, batch, indices_dev, num_minibatches, minibatch_size, cfg,
+            value_norm_state, workspace_dev, workspace_bytes, stats_dev_or_null, grads_dev_or_null, hip_stream, true,
+            [&](char *described, size_t room) {
+                snprintf(described, room, "hidden %u, layer_N %u", policy->hidden, policy->layer_N);
+                return mappo_mlp_shape_error(mrl::kMlpBaseObs, policy->hidden, policy->layer_N, mrl::kMlpBaseActions, minibatch_size);
+            },
+            [&] { return (uint64_t)mrl::mlpbase_net_params(policy->layer_N, mrl::kMlpBaseActions); }))
         return rc;
     mrl::DeviceGuard on(gpu_id);
     return guarded([&] {

@@ -9,6 +9,59 @@ namespace mrl {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// A tile's 32 observation rows into LDS, whole dwords from the 4-byte boundary at or below each row's start: LDS row rr holds the
+// row's bytes from byte `shift` on, and the first and the last dword are put together from the row's own bytes only.
+// row_address(rr) is the row's first byte, or nullptr for a row the tile does not have (zeros).  With `shifts`, shifts[rr]
+// receives the row's shift.  Then the patch offset of every k and, with_weights, the conv weights, rows conv_ld floats apart and
+// a zero behind an odd K.  The caller puts a barrier behind it.
+template <class RowAddress>
+__device__ __forceinline__ void cnn_load_tile(const CnnActArgs &a, unsigned char *lds, const RowAddress &row_address, uint32_t *shifts,
+                                              const float *__restrict__ conv_w, bool with_weights)
+{
+    const CnnLds &l = a.lds;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t S = a.W * a.H * a.F, k1 = l.k1;
+    uint32_t *obs_words = reinterpret_cast<uint32_t *>(lds);
+    for (uint32_t rr = wave; rr < kCnnTile; rr += 4u) {
+        uint32_t *__restrict__ dst = obs_words + rr * (l.obs_ld / 4u);
+        const uint8_t *__restrict__ row = row_address(rr);
+        if (!row) {
+            for (uint32_t d = lane; d < (S + 3u) / 4u; d += 64u) dst[d] = 0u;
+            if (shifts && lane == 0) shifts[rr] = 0u;
+            continue;
+        }
+        const uint32_t shift = (uint32_t)(reinterpret_cast<uintptr_t>(row) & 3u), words = (shift + S + 3u) / 4u;
+        if (shifts && lane == 0) shifts[rr] = shift;
+        for (uint32_t d = lane; d < words; d += 64u) {
+            const int32_t g = (int32_t)(4u * d) - (int32_t)shift;  // the dword's first byte, counted from the row's start
+            uint32_t v = 0u;
+            if (g >= 0 && (uint32_t)g + 4u <= S) {
+                v = *reinterpret_cast<const uint32_t *>(row + g);
+            } else {
+#pragma unroll
+                for (int b = 0; b < 4; b++) {
+                    const int32_t at = g + b;
+                    if (at >= 0 && (uint32_t)at < S) v |= (uint32_t)row[at] << (8 * b);
+                }
+            }
+            dst[d] = v;
+        }
+    }
+    if (with_weights) {
+        float *w_lds = reinterpret_cast<float *>(lds + l.conv_w_at);
+        for (uint32_t e = tid; e < kCnnChannels * k1; e += kCnnThreads) {
+            const uint32_t c = e / k1, k = e - c * k1;
+            w_lds[c * l.conv_ld + k] = conv_w[e];
+        }
+        if (k1 != l.k1_padded && tid < kCnnChannels) w_lds[tid * l.conv_ld + k1] = 0.0f;
+    }
+    uint16_t *koff = reinterpret_cast<uint16_t *>(lds + l.koff_at);
+    for (uint32_t k = tid; k < l.k1_padded; k += kCnnThreads) {
+        const uint32_t f = k / 9u, ij = k - 9u * f, i = ij / 3u, j = ij - 3u * i;
+        koff[k] = k < k1 ? (uint16_t)((j * a.W + i) * a.F + f) : (uint16_t)0;
+    }
+}
+
 template <int NP>
 __device__ __forceinline__ void cnn_conv_pass(const CnnActArgs &a, const int8_t *__restrict__ my_obs, const float *__restrict__ my_w,
                                               const uint16_t *__restrict__ koff, float *__restrict__ act, float bias, uint32_t p0,
@@ -40,6 +93,28 @@ __device__ __forceinline__ void cnn_conv_pass(const CnnActArgs &a, const int8_t 
             const float v = acc[q][e] + bias;
             out[row * a.lds.act_ld] = v > 0.0f ? v : 0.0f;
         }
+    }
+}
+
+// The convolution of a tile cnn_load_tile left in LDS, into the activation image: wave w takes positions w, w + 4, ..., three at a
+// time.  `shift`: where the row of this lane's sample r begins in its LDS row.  The caller puts a barrier behind it.
+__device__ __forceinline__ void cnn_conv_tile(const CnnActArgs &a, unsigned char *lds, uint32_t shift, const float *__restrict__ conv_b,
+                                              uint32_t wave, uint32_t r, uint32_t half)
+{
+    const int8_t *__restrict__ my_obs = reinterpret_cast<const int8_t *>(lds) + r * a.lds.obs_ld + shift;
+    const float *__restrict__ my_w = reinterpret_cast<const float *>(lds + a.lds.conv_w_at) + r * a.lds.conv_ld;
+    const uint16_t *koff = reinterpret_cast<const uint16_t *>(lds + a.lds.koff_at);
+    float *act = reinterpret_cast<float *>(lds + a.lds.act_at);
+    const float bias = conv_b[r];
+    const uint32_t npos = a.lds.npos;
+    for (uint32_t p0 = wave; p0 < npos; p0 += 12u) {
+        const uint32_t count = (npos - p0 + 3u) / 4u;  // positions p0, p0 + 4, p0 + 8 that exist
+        if (count >= 3u)
+            cnn_conv_pass<3>(a, my_obs, my_w, koff, act, bias, p0, r, half);
+        else if (count == 2u)
+            cnn_conv_pass<2>(a, my_obs, my_w, koff, act, bias, p0, r, half);
+        else
+            cnn_conv_pass<1>(a, my_obs, my_w, koff, act, bias, p0, r, half);
     }
 }
 

@@ -22,22 +22,13 @@
 
 namespace mrl {
 
-// sample s of the call -> (world, seat): seat = the (s % num_seats)-th set bit of the mask
-__device__ __forceinline__ void cnn_sample(const CnnActArgs &a, uint32_t s, uint32_t &world, uint32_t &seat)
-{
-    world = s / a.num_seats;
-    uint32_t idx = s - world * a.num_seats, mask = a.players;
-    for (; idx > 0; idx--) mask &= mask - 1u;
-    seat = (uint32_t)__ffs((int)mask) - 1u;
-}
-
 // tile t of the call holds samples 32 t .. 32 t + 31 (cnn_act_body's map)
 struct CnnPlainMap {
     uint32_t tile0, total;
     __device__ __forceinline__ bool sample(const CnnActArgs &a, uint32_t row, uint32_t &world, uint32_t &seat) const
     {
         if (tile0 + row >= total) return false;
-        cnn_sample(a, tile0 + row, world, seat);
+        seat_sample(a.players, a.num_seats, tile0 + row, world, seat);
         return true;
     }
 };

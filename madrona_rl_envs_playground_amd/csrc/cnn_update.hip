@@ -17,10 +17,13 @@
 //   mrl_clip_adam     per net: total norm, clip, Adam with the net's learning rate, and the net's columns of the stats row
 //                     (adam_step.hpp: the tail every update shares; each net is a segment).
 // No float atomics and no wait on another workgroup anywhere: the same inputs give the same bits on every run.
-// The per-sample loss head, the accumulator tiles and the stats row's end are mappo_loss.hpp's, shared with the balance beam's
-// update (mlpbase_update.hip); the ValueNorm launches are defined here and declared there.
+// The per-sample losses, the accumulator tiles and the stats row's end are mappo_loss.hpp's; the sample table, the loss head, the
+// backward pass of the head and of fc2, the bias-column sums, the stats' tail and the host's row loop are mappo_grad.hpp's: both
+// shared with the balance beam's update (mlpbase_update.hip).  What is left here is what a convolution net has of its own.  The
+// ValueNorm launches are defined here and declared in mappo_loss.hpp.
 #include "cnn_update.hpp"
 #include "cnn_forward.hpp"
+#include "mappo_grad.hpp"
 
 #include <cmath>
 
@@ -30,74 +33,20 @@ namespace {
 
 constexpr uint32_t kStatThreads = 1024;
 
+static_assert(kCnnHidden == kMappoHidden && kCnnThreads == kMappoThreads && kCnnTile == kMappoTile && kCnnFcLd == kMappoLd,
+              "mappo_grad.hpp's functions are written for this net's width, workgroup, tile and LDS row stride");
+
 extern __shared__ __attribute__((aligned(16))) unsigned char upd_lds_image[];
 
 struct MappoGradArgs {
+    MappoGradCommon common;
     CnnActArgs fwd;  // W, H, F and the LDS image of the forward pass; params
-    const int8_t *obs;
-    const int32_t *actions;
-    const float *logprobs, *value_preds, *returns, *advantages;
-    const int32_t *indices;  // this row's B sample numbers
-    const float *row_norm;   // this row's ValueNorm (mean, sqrt(var)); nullptr without MRL_MAPPO_VALUENORM
-    float *partial_grads;    // (2, groups, stride)
-    double *partial_stats;   // (2, groups, 8)
-    uint64_t share, stride;
-    uint32_t minibatch_size, batch_size, groups, tail_at;
-    MappoLoss loss;
+    uint32_t tail_at;
 };
-
-// the tile's observation rows (mrl_cnn_act's loader with the row taken from the sample table), the patch offsets of k and, for
-// the forward pass, the conv weights
-__device__ __forceinline__ void load_rows(const MappoGradArgs &a, unsigned char *lds, const uint32_t *sample, uint32_t *shifts,
-                                          const float *__restrict__ conv_w, bool with_weights)
-{
-    const CnnLds &l = a.fwd.lds;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t S = a.fwd.W * a.fwd.H * a.fwd.F, k1 = l.k1;
-    uint32_t *obs_words = reinterpret_cast<uint32_t *>(lds);
-    for (uint32_t rr = wave; rr < kCnnTile; rr += 4u) {
-        uint32_t *__restrict__ dst = obs_words + rr * (l.obs_ld / 4u);
-        const uint32_t s = sample[rr];
-        if (s == 0xFFFFFFFFu) {
-            for (uint32_t d = lane; d < (S + 3u) / 4u; d += 64u) dst[d] = 0u;
-            if (lane == 0) shifts[rr] = 0u;
-            continue;
-        }
-        const uint8_t *__restrict__ row = reinterpret_cast<const uint8_t *>(a.obs) + (size_t)s * S;
-        const uint32_t shift = (uint32_t)(reinterpret_cast<uintptr_t>(row) & 3u), words = (shift + S + 3u) / 4u;
-        if (lane == 0) shifts[rr] = shift;
-        for (uint32_t d = lane; d < words; d += 64u) {
-            const int32_t g = (int32_t)(4u * d) - (int32_t)shift;  // the dword's first byte, counted from the row's start
-            uint32_t v = 0u;
-            if (g >= 0 && (uint32_t)g + 4u <= S) {
-                v = *reinterpret_cast<const uint32_t *>(row + g);
-            } else {
-#pragma unroll
-                for (int b = 0; b < 4; b++) {
-                    const int32_t at = g + b;
-                    if (at >= 0 && (uint32_t)at < S) v |= (uint32_t)row[at] << (8 * b);
-                }
-            }
-            dst[d] = v;
-        }
-    }
-    if (with_weights) {
-        float *w_lds = reinterpret_cast<float *>(lds + l.conv_w_at);
-        for (uint32_t e = tid; e < kCnnChannels * k1; e += kCnnThreads) {
-            const uint32_t c = e / k1, k = e - c * k1;
-            w_lds[c * l.conv_ld + k] = conv_w[e];
-        }
-        if (k1 != l.k1_padded && tid < kCnnChannels) w_lds[tid * l.conv_ld + k1] = 0.0f;
-    }
-    uint16_t *koff = reinterpret_cast<uint16_t *>(lds + l.koff_at);
-    for (uint32_t k = tid; k < l.k1_padded; k += kCnnThreads) {
-        const uint32_t f = k / 9u, ij = k - 9u * f, i = ij / 3u, j = ij - 3u * i;
-        koff[k] = k < k1 ? (uint16_t)((j * a.fwd.W + i) * a.fwd.F + f) : (uint16_t)0;
-    }
-}
 
 __global__ void __launch_bounds__(kCnnThreads) mrl_mappo_grad(MappoGradArgs a)
 {
+    const MappoGradCommon &c = a.common;
     const CnnActArgs &f = a.fwd;
     const CnnLds &l = f.lds;
     const uint32_t net = blockIdx.y;  // 0 the actor, 1 the critic
@@ -110,15 +59,14 @@ __global__ void __launch_bounds__(kCnnThreads) mrl_mappo_grad(MappoGradArgs a)
     const float *__restrict__ fc2_w = fc1_b + kCnnHidden, *__restrict__ fc2_b = fc2_w + kCnnHidden * kCnnHidden;
     const float *__restrict__ head_w = fc2_b + kCnnHidden, *__restrict__ head_b = head_w + out_dim * kCnnHidden;
     // this workgroup's partial vector, in the net's parameter order
-    float *__restrict__ g_conv_w = a.partial_grads + ((size_t)net * a.groups + blockIdx.x) * a.stride;
+    float *__restrict__ g_conv_w = c.partial_grads + ((size_t)net * c.groups + blockIdx.x) * c.stride;
     float *__restrict__ g_conv_b = g_conv_w + (size_t)kCnnChannels * k1;
     float *__restrict__ g_fc1_w = g_conv_b + kCnnChannels, *__restrict__ g_fc1_b = g_fc1_w + (size_t)kCnnHidden * K2;
     float *__restrict__ g_fc2_w = g_fc1_b + kCnnHidden, *__restrict__ g_fc2_b = g_fc2_w + kCnnHidden * kCnnHidden;
     float *__restrict__ g_head_w = g_fc2_b + kCnnHidden, *__restrict__ g_head_b = g_head_w + out_dim * kCnnHidden;
 
     unsigned char *lds = upd_lds_image;
-    float *w_lds = reinterpret_cast<float *>(lds + l.conv_w_at);
-    uint16_t *koff = reinterpret_cast<uint16_t *>(lds + l.koff_at);
+    const uint16_t *koff = reinterpret_cast<const uint16_t *>(lds + l.koff_at);
     float *act = reinterpret_cast<float *>(lds + l.act_at);
     uint32_t *sample = reinterpret_cast<uint32_t *>(lds + a.tail_at), *shifts = sample + kCnnTile;
     float *chunk = reinterpret_cast<float *>(lds + kCnnChunkAt);
@@ -127,119 +75,41 @@ __global__ void __launch_bounds__(kCnnThreads) mrl_mappo_grad(MappoGradArgs a)
     float *d_out = reinterpret_cast<float *>(lds + kUpdDoutAt), *d_h2 = reinterpret_cast<float *>(lds + kUpdDh2At);
     float *d_h1 = reinterpret_cast<float *>(lds + kUpdDh1At);
 
-    const uint64_t begin = blockIdx.x * a.share;
-    const uint64_t end = begin + a.share < a.minibatch_size ? begin + a.share : a.minibatch_size;
-    const float count = (float)a.minibatch_size;
+    const uint64_t begin = blockIdx.x * c.share;
+    const uint64_t end = begin + c.share < c.minibatch_size ? begin + c.share : c.minibatch_size;
+    const float count = (float)c.minibatch_size;
+    // a row of the tile in the batch, or nullptr where the tile has no such row
+    const auto row_address = [&](uint32_t rr) -> const uint8_t * {
+        const uint32_t s = sample[rr];
+        return s == kMappoAbsent ? nullptr : static_cast<const uint8_t *>(c.obs) + (size_t)s * (f.W * f.H * f.F);
+    };
     double stat[4] = {0.0, 0.0, 0.0, 0.0};  // lanes 0..31 of wave 0: this lane's samples
 
     for (uint64_t base = begin; base < end; base += kCnnTile) {
         const bool first = base == begin;
         const uint32_t tid = opaque(tid0), lane = tid & 63u, wave = tid >> 6, r = lane & 31u, half = lane >> 5;
-        // ---- the tile's samples; a lane past the end runs on a zero observation with zero upstream gradient
-        if (tid < kCnnTile) {
-            uint32_t s = 0xFFFFFFFFu;
-            if (base + tid < end) {
-                s = (uint32_t)a.indices[base + tid];
-                s = s < a.batch_size ? s : a.batch_size - 1u;  // outside the contract, but memory-safe
-            }
-            sample[tid] = s;
-        }
+        mappo_tile_samples(c, sample, base, end, tid);
         __syncthreads();
-        load_rows(a, lds, sample, shifts, conv_w, true);
+        cnn_load_tile(f, lds, row_address, shifts, conv_w, true);
         __syncthreads();
         // ---- the forward pass of mrl_cnn_act
-        {
-            const int8_t *__restrict__ my_obs = reinterpret_cast<const int8_t *>(lds) + r * l.obs_ld + shifts[r];
-            const float *__restrict__ my_w = w_lds + r * l.conv_ld;
-            const float bias = conv_b[r];
-            for (uint32_t p0 = wave; p0 < npos; p0 += 12u) {
-                const uint32_t n = (npos - p0 + 3u) / 4u;  // positions p0, p0 + 4, p0 + 8 that exist
-                if (n >= 3u)
-                    cnn_conv_pass<3>(f, my_obs, my_w, koff, act, bias, p0, r, half);
-                else if (n == 2u)
-                    cnn_conv_pass<2>(f, my_obs, my_w, koff, act, bias, p0, r, half);
-                else
-                    cnn_conv_pass<1>(f, my_obs, my_w, koff, act, bias, p0, r, half);
-            }
-        }
+        cnn_conv_tile(f, lds, shifts[r], conv_b, wave, r, half);
         __syncthreads();  // the activation image is complete; the convolution's operands are dead
         cnn_fc_layer(act, act_ld, K2, fc1_w, fc1_b, kCnnHidden, true, chunk, h1, kCnnFcLd, wave, lane);
         cnn_fc_layer(h1, kCnnFcLd, kCnnHidden, fc2_w, fc2_b, kCnnHidden, true, chunk, h2, kCnnFcLd, wave, lane);
         cnn_fc_layer(h2, kCnnFcLd, kCnnHidden, head_w, head_b, out_dim, false, chunk, outs, 8u, wave, lane);
 
-        // ---- the loss head, a lane per sample: d_out = dLoss / d(head output)
-        if (tid < kCnnTile) {
-            float d[kCnnActions] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-            const uint32_t at = sample[tid];
-            if (at != 0xFFFFFFFFu && net == 0u) {
-                const float lg[kCnnActions] = {outs[tid * 8u], outs[tid * 8u + 1], outs[tid * 8u + 2], outs[tid * 8u + 3], outs[tid * 8u + 4],
-                                               outs[tid * 8u + 5]};
-                mappo_actor_sample<(int)kCnnActions>(lg, a.actions[at], a.logprobs[at], a.advantages[at], a.loss, count, d, stat);
-            } else if (at != 0xFFFFFFFFu) {
-                d[0] = mappo_critic_sample(outs[tid * 8u], a.value_preds[at], a.returns[at], a.row_norm, a.loss, count, stat);
-            }
-#pragma unroll
-            for (int i = 0; i < (int)kCnnActions; i++) d_out[tid * 8u + i] = d[i];
-            d_out[tid * 8u + 6] = d_out[tid * 8u + 7] = 0.0f;
-        }
+        mappo_loss_head<(int)kCnnActions>(c, net, sample, outs, d_out, count, stat, tid);
         __syncthreads();
-
-        // ---- head: dW_head = d_out^T h2 (rows: outputs, k: samples) on waves 0 and 1, a 32-column slab each; db_head; d_h2
-        if (wave < 2u) {
-            const uint32_t col = 32u * wave + r;
-            f32x16 acc = acc_load(g_head_w, kCnnHidden, out_dim, col, true, first, half);
-#pragma unroll 4
-            for (uint32_t kk = 0; kk < kCnnTile / 2u; kk++) {
-                const uint32_t s = 2u * kk + half;
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(r < out_dim ? d_out[s * 8u + r] : 0.0f, h2[s * kCnnFcLd + col], acc, 0, 0, 0);
-            }
-            acc_store(g_head_w, kCnnHidden, out_dim, col, true, half, acc);
-        } else if (wave == 2u && lane < out_dim) {
-            float sum = first ? 0.0f : g_head_b[lane];
-            for (uint32_t s = 0; s < kCnnTile; s++) sum += d_out[s * 8u + lane];
-            g_head_b[lane] = sum;
-        }
-        for (uint32_t idx = tid; idx < kCnnTile * kCnnHidden; idx += kCnnThreads) {
-            const uint32_t s = idx >> 6, j = idx & 63u;
-            float sum = 0.0f;
-            for (uint32_t o = 0; o < out_dim; o++) sum = fmaf(head_w[o * kCnnHidden + j], d_out[s * 8u + o], sum);
-            d_h2[s * kCnnFcLd + j] = h2[s * kCnnFcLd + j] > 0.0f ? sum : 0.0f;
-        }
+        // ---- head: dW_head, db_head and d_h2 behind fc2's ReLU
+        mappo_head_backward<true>(head_w, g_head_w, g_head_b, out_dim, d_out, h2, d_h2, h2, kCnnFcLd, first, tid);
         __syncthreads();
-
-        // ---- fc2: dW_fc2 = d_h2^T h1, one 32 x 32 block per wave, k = samples
-        {
-            const uint32_t jt = wave >> 1, it = wave & 1u, col = 32u * it + r;
-            float *__restrict__ g = g_fc2_w + (size_t)32u * jt * kCnnHidden;
-            f32x16 acc = acc_load(g, kCnnHidden, 32u, col, true, first, half);
-#pragma unroll 4
-            for (uint32_t kk = 0; kk < kCnnTile / 2u; kk++) {
-                const uint32_t s = 2u * kk + half;
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(d_h2[s * kCnnFcLd + 32u * jt + r], h1[s * kCnnFcLd + col], acc, 0, 0, 0);
-            }
-            acc_store(g, kCnnHidden, 32u, col, true, half, acc);
-        }
-        // d_h1[sample][i] = (h1 > 0) sum_j d_h2[sample][j] W_fc2[j][i]: rows samples, k = units of fc2; waves 0 and 1
-        if (wave < 2u) {
-            const uint32_t col = 32u * wave + r;
-            f32x16 acc;
-#pragma unroll
-            for (int e = 0; e < 16; e++) acc[e] = 0.0f;
-#pragma unroll 4
-            for (uint32_t kk = 0; kk < kCnnHidden / 2u; kk++) {
-                const uint32_t j = 2u * kk + half;
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(d_h2[r * kCnnFcLd + j], fc2_w[j * kCnnHidden + col], acc, 0, 0, 0);
-            }
-#pragma unroll
-            for (int e = 0; e < 16; e++) {
-                const uint32_t row = tile_row(e, half);
-                d_h1[row * kCnnFcLd + col] = h1[row * kCnnFcLd + col] > 0.0f ? acc[e] : 0.0f;
-            }
-        } else if (wave == 2u) {
-            float sum = first ? 0.0f : g_fc2_b[lane];
-            for (uint32_t s = 0; s < kCnnTile; s++) sum += d_h2[s * kCnnFcLd + lane];
-            g_fc2_b[lane] = sum;
-        }
+        // ---- fc2: dW_fc2 = d_h2^T h1; d_h1 behind fc1's ReLU on waves 0 and 1; db_fc2
+        mappo_dw_block(g_fc2_w, d_h2, h1, kCnnFcLd, first, wave, r, half);
+        if (wave < 2u)
+            mappo_d_in<true>(d_h2, fc2_w, d_h1, h1, kCnnFcLd, wave, r, half);
+        else if (wave == 2u)
+            column_sum(g_fc2_b, first, d_h2, nullptr, kCnnFcLd, 0u, lane);
         __syncthreads();
 
         // ---- fc1: dW_fc1 = d_h1^T act (64 x 32 npos) while act is intact: wave w takes the column slabs w, w + 4, ..., both row
@@ -259,11 +129,7 @@ __global__ void __launch_bounds__(kCnnThreads) mrl_mappo_grad(MappoGradArgs a)
             acc_store(g0, K2, 32u, col, true, half, acc0);
             acc_store(g1, K2, 32u, col, true, half, acc1);
         }
-        if (wave == 3u) {
-            float sum = first ? 0.0f : g_fc1_b[lane];
-            for (uint32_t s = 0; s < kCnnTile; s++) sum += d_h1[s * kCnnFcLd + lane];
-            g_fc1_b[lane] = sum;
-        }
+        if (wave == 3u) column_sum(g_fc1_b, first, d_h1, nullptr, kCnnFcLd, 0u, lane);
         __syncthreads();
         // act in place becomes dL/d(conv pre-activation) = (act > 0) sum_j d_h1[sample][j] W_fc1[j][.]: rows samples, k = units
 #pragma unroll 1
@@ -287,7 +153,7 @@ __global__ void __launch_bounds__(kCnnThreads) mrl_mappo_grad(MappoGradArgs a)
 
         // ---- convolution: the observation rows again (out of L2), then dW_conv[c][k] = sum over (position, sample) of
         // d_conv[sample][c][position] * patch[sample][position][k]: rows channels, columns k in slabs of 32, wave w takes slabs w, w + 4
-        load_rows(a, lds, sample, shifts, conv_w, false);
+        cnn_load_tile(f, lds, row_address, shifts, conv_w, false);
         __syncthreads();
         {
             const uint32_t hh = f.H - 2u, slabs = (k1 + 31u) / 32u;
@@ -319,20 +185,7 @@ __global__ void __launch_bounds__(kCnnThreads) mrl_mappo_grad(MappoGradArgs a)
         __syncthreads();  // the next tile overwrites what the loops above read
     }
 
-    // ---- the stats' sums: lanes in ascending order
-    const uint32_t tid = tid0;
-    double *sums = reinterpret_cast<double *>(lds);
-    if (tid < kCnnTile) {
-#pragma unroll
-        for (int c = 0; c < 4; c++) sums[c * kCnnTile + tid] = stat[c];
-    }
-    __syncthreads();
-    if (tid < kMappoStats) {
-        double sum = 0.0;
-        if (tid < 4u)
-            for (uint32_t s = 0; s < kCnnTile; s++) sum += sums[tid * kCnnTile + s];
-        a.partial_stats[((size_t)net * a.groups + blockIdx.x) * kMappoStats + tid] = sum;
-    }
+    mappo_stats_tail(c, net, reinterpret_cast<double *>(lds), stat, tid0);
 }
 
 // ValueNorm, first launch: the mean and the mean of squares of every row's gathered returns, one workgroup per row
@@ -396,14 +249,7 @@ void launch_mappo_update(const mrl_mappo_policy &policy, const mrl_mappo_optimiz
 {
     if (num_minibatches == 0) return;
     const uint32_t W = policy.width, H = policy.height, F = policy.channels;
-    const uint32_t actor = (uint32_t)cnn_net_params(W, H, F, kCnnActions), critic = (uint32_t)cnn_net_params(W, H, F, 1);
-    const SampleShare share = share_samples(minibatch_size, kCnnTile, kMappoMaxGroups);
-    const MappoWorkspace ws = mappo_workspace(actor, minibatch_size, num_minibatches);
     const CnnUpdateLds lds = cnn_update_lds(W, H, F);
-    const bool norm = cfg.flags & MRL_MAPPO_VALUENORM;
-    if (norm)
-        launch_mappo_value_norm(batch.returns, indices, num_minibatches, minibatch_size, batch.size, cfg, value_norm_state,
-                                workspace + ws.row_sums, workspace + ws.row_norm, stream);
     allow_large_dynamic_lds<&mrl_mappo_grad>(lds.total);
     MappoGradArgs g{};
     g.fwd.params = opt.params_dev;
@@ -411,46 +257,12 @@ void launch_mappo_update(const mrl_mappo_policy &policy, const mrl_mappo_optimiz
     g.fwd.H = H;
     g.fwd.F = F;
     g.fwd.lds = lds.fwd;
-    g.obs = batch.obs;
-    g.actions = batch.actions;
-    g.logprobs = batch.logprobs;
-    g.value_preds = batch.value_preds;
-    g.returns = batch.returns;
-    g.advantages = batch.advantages;
-    g.partial_grads = workspace + ws.partial_grads;
-    g.partial_stats = reinterpret_cast<double *>(workspace + ws.partial_stats);
-    g.share = share.share;
-    g.stride = ws.stride;
-    g.minibatch_size = minibatch_size;
-    g.batch_size = batch.size;
-    g.groups = share.groups;
     g.tail_at = lds.tail_at;
-    g.loss = MappoLoss{cfg.clip_param, cfg.entropy_coef, cfg.value_loss_coef, cfg.huber_delta, cfg.flags};
-    // two clip_grad_norm_ and two Adam steps: the actor's segment, then the critic's
-    AdamStepArgs ad = adam_step_args(cfg.beta1, cfg.beta2, cfg.opti_eps, cfg.flags & MRL_MAPPO_MAX_GRAD_NORM, cfg.max_grad_norm);
-    ad.partial_grads = g.partial_grads;
-    ad.grad = workspace + ws.grad;
-    ad.sumsq = workspace + ws.sumsq;
-    ad.params = opt.params_dev;
-    ad.exp_avg = opt.exp_avg;
-    ad.exp_avg_sq = opt.exp_avg_sq;
-    ad.stride = ws.stride;
-    ad.segments = 2;
-    ad.groups = share.groups;
-    ad.blocks = (uint32_t)ws.blocks;
-    ad.num_params[0] = actor, ad.num_params[1] = critic;
-    ad.at[0] = 0, ad.at[1] = actor;
-    MappoStatsRow row{g.partial_stats, nullptr, share.groups, minibatch_size};
-    for (uint32_t k = 0; k < num_minibatches; k++) {
-        g.indices = indices + (size_t)k * minibatch_size;
-        g.row_norm = norm ? workspace + ws.row_norm + 2 * (size_t)k : nullptr;
-        hipLaunchKernelGGL(mrl_mappo_grad, dim3(share.groups, 2), dim3(kCnnThreads), lds.total, stream, g);
-        MRL_HIP(hipGetLastError());
-        ad.grads_row = grads ? grads + (size_t)k * ((size_t)actor + critic) : nullptr;
-        adam_set_step(ad, (double)opt.step + 1.0 + (double)k, {cfg.lr, cfg.critic_lr});
-        row.row = stats ? stats + (size_t)k * kMappoStats : nullptr;
-        launch_adam_step(ad, row, stream);
-    }
+    mappo_update_rows((uint32_t)cnn_net_params(W, H, F, kCnnActions), (uint32_t)cnn_net_params(W, H, F, 1), opt, batch, indices, num_minibatches,
+                      minibatch_size, cfg, value_norm_state, workspace, stats, grads, stream, [&](const MappoGradCommon &common, uint32_t groups) {
+                          g.common = common;
+                          hipLaunchKernelGGL(mrl_mappo_grad, dim3(groups, 2), dim3(kCnnThreads), lds.total, stream, g);
+                      });
 }
 
 }  // namespace mrl

@@ -1,7 +1,8 @@
 // What MAPPO's two device updates share (cnn_update.hip for the kitchens' CNN actor-critic, mlpbase_update.hip for the balance
 // beam's MLPBase one; DESIGN.md sections 16 and 18): the per-sample loss head of R_MAPPO.ppo_update (train/MAPPO/r_mappo.py:91-164),
 // the accumulator tile of a weight gradient that lives in the workgroup's partial vector, the ValueNorm recurrence up front and the
-// stats row's end.  The networks differ, the losses do not: one definition, so the two updates cannot drift apart.
+// stats row's end.  The networks differ, the losses do not: one definition, so the two updates cannot drift apart.  The steps of a
+// tile that use these -- sample table, loss head, the backward pass of the head and of a 64 x 64 layer -- are in mappo_grad.hpp.
 #pragma once
 
 #include "adam_step.hpp"

@@ -74,13 +74,4 @@ __device__ __forceinline__ void mlpbase_forward(const float *__restrict__ net, u
     cnn_fc_layer(in, in_ld, kMlpBaseHidden, head_w, head_w + out_dim * kMlpBaseHidden, out_dim, false, chunk, outs, 8u, wave, lane);
 }
 
-// sample s of an act -> (world, seat): seat = the (s % num_seats)-th set bit of the mask
-__device__ __forceinline__ void mlpbase_sample(uint32_t players, uint32_t num_seats, uint32_t s, uint32_t &world, uint32_t &seat)
-{
-    world = s / num_seats;
-    uint32_t idx = s - world * num_seats, mask = players;
-    for (; idx > 0; idx--) mask &= mask - 1u;
-    seat = (uint32_t)__ffs((int)mask) - 1u;
-}
-
 }  // namespace mrl

@@ -14,7 +14,6 @@
 // No float atomics, no workgroup waits on another, no scratch: the same inputs give the same bits on every run.
 #include "mlpbase_policy.hpp"
 #include "mlpbase_forward.hpp"
-#include "random_policy.hpp"
 
 namespace mrl {
 
@@ -22,7 +21,7 @@ extern __shared__ __attribute__((aligned(16))) unsigned char mlpbase_lds_image[]
 
 __global__ void __launch_bounds__(kMlpBaseThreads) mrl_mlpbase_act(MlpBaseActArgs a)
 {
-    const uint32_t net = a.nets == 3u ? blockIdx.y : a.nets >> 1;  // 0 the actor, 1 the critic
+    const uint32_t net = act_net(a);
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t total = a.num_worlds * a.num_seats, tile0 = blockIdx.x * kMlpBaseTile;
     const uint32_t out_dim = net ? 1u : kMlpBaseActions;
@@ -36,7 +35,7 @@ __global__ void __launch_bounds__(kMlpBaseThreads) mrl_mlpbase_act(MlpBaseActArg
         float v = 0.0f;
         if (s < total && k < kMlpBaseObs) {
             uint32_t world, seat;
-            mlpbase_sample(a.players, a.num_seats, s, world, seat);
+            seat_sample(a.players, a.num_seats, s, world, seat);
             const int32_t word = a.obs[((size_t)seat * a.num_worlds + world) * kMlpBaseObs + k];
             v = (float)word;
             if (copies) a.obs_row[((size_t)world * a.P + seat) * kMlpBaseObs + k] = word;
@@ -46,29 +45,10 @@ __global__ void __launch_bounds__(kMlpBaseThreads) mrl_mlpbase_act(MlpBaseActArg
     __syncthreads();
     mlpbase_forward(params, a.layer_N, out_dim, lds, wave, lane);
 
-    const float *outs = lds + kMlpOutAt;
     if (tid >= kMlpBaseTile || tile0 + tid >= total) return;
     uint32_t world, seat;
-    mlpbase_sample(a.players, a.num_seats, tile0 + tid, world, seat);
-    const size_t cell = (size_t)world * a.P + seat, agent = (size_t)seat * a.num_worlds + world;
-    if (net) {
-        if (a.values_row) a.values_row[cell] = outs[tid * 8u];
-        if (a.dones_row) a.dones_row[cell] = a.done[world] != 0 ? 1.0f : 0.0f;
-        if (a.rewards_row) a.rewards_row[cell] = a.reward[agent];
-        return;
-    }
-    const float l0 = outs[tid * 8u], l1 = outs[tid * 8u + 1], l2 = outs[tid * 8u + 2], l3 = outs[tid * 8u + 3];
-    const float l[kMlpBaseActions] = {l0, l1, l2, l3};  // statically indexed below: stays in registers
-    int action;
-    float logprob;
-    categorical_sample<(int)kMlpBaseActions>(l, policy_hash(a.seed, a.step, world, seat), a.flags & MRL_POLICY_GREEDY, action, logprob);
-    a.action[agent] = action;
-    if (a.actions_row) a.actions_row[cell] = action;
-    if (a.logprobs_row) a.logprobs_row[cell] = logprob;
-    if (a.logits_row) {
-#pragma unroll
-        for (int i = 0; i < (int)kMlpBaseActions; i++) a.logits_row[cell * kMlpBaseActions + i] = l[i];
-    }
+    seat_sample(a.players, a.num_seats, tile0 + tid, world, seat);
+    act_tail<(int)kMlpBaseActions>(a, lds + kMlpOutAt, net, tid, world, seat, a.reward);
 }
 
 void launch_mlpbase_act(const MlpBaseActArgs &args, hipStream_t stream)

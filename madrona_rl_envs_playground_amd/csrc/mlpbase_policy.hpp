@@ -15,6 +15,7 @@
 // per net are part of the tensor, no kernel reads them, and their gradient is zero.
 #pragma once
 
+#include "act_record.hpp"
 #include "common.hpp"
 
 namespace mrl {
@@ -55,24 +56,12 @@ constexpr uint32_t kMlpChunkAt = 0, kMlpIn0At = kMlpChunkAt + kMlpBaseHidden * k
                    kMlpYAt = kMlpXhatAt + kMlpMaxLayers * kMlpBaseTile * kMlpLd, kMlpFwdFloats = kMlpYAt + kMlpMaxLayers * kMlpBaseTile * kMlpLd;
 static_assert((kMlpMaskAt & 1u) == 0, "the ReLU masks are 64-bit words");
 
-struct MlpBaseActArgs {
+struct MlpBaseActArgs : ActArgs {
     const float *params;       // actor's tensors, then the critic's
     const int32_t *obs;        // OBSERVATION (P, N, 7)
-    const int32_t *done;       // DONE (N)
     const float *reward;       // REWARD (P, N)
-    int32_t *action;           // ACTION (P, N)
-    // the record's rows for this call (nullptr: not written)
-    int32_t *actions_row;                   // (N, P)
-    float *logprobs_row, *values_row;       // (N, P)
-    float *rewards_row, *dones_row;         // (N, P): rewards[row - 1]; dones[row] or next_done
-    float *logits_row;                      // (N, P, 4)
-    int32_t *obs_row;                       // (N, P, 7)
-    uint32_t P, num_worlds;
-    uint32_t players, num_seats;            // the seat mask and its popcount
-    uint32_t step, flags;
-    uint32_t nets;                          // bit 0: the actor runs, bit 1: the critic runs
+    int32_t *obs_row;          // the record's (N, P, 7) row for this call (nullptr: not written)
     uint32_t layer_N;
-    uint64_t seed;
 };
 
 void launch_mlpbase_act(const MlpBaseActArgs &args, hipStream_t stream);

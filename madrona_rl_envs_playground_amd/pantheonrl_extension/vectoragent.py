@@ -30,7 +30,32 @@ class RandomVectorAgent(VectorAgent):
         return None
 
 
-class CnnPolicyAgent(VectorAgent):
+class _DevicePolicyAgent(VectorAgent):
+    """What the agents that act under a MAPPO policy on the device share: the seat -- ``player_num``, set by
+    ``env.add_partner_agent``, or, while that is ``None``, the env's ``ego_ind`` --, the count of draws that numbers the steps and
+    an ``update`` that does nothing.  A subclass has ``_check_env()``, which returns the env's simulator or raises ``TypeError``,
+    and ``_act(mask)``, its one launch for the seats in ``mask``."""
+
+    def __init__(self, envs, policy, seed=0, greedy=False):
+        self.envs, self.policy, self.seed, self.greedy = envs, policy, int(seed), bool(greedy)
+        self.player_num = None
+        self._draws = 0
+        self._sim = self._check_env()
+
+    @property
+    def seat(self):
+        return self.envs.ego_ind if self.player_num is None else self.player_num
+
+    def get_action(self, obs=None, record=True):
+        self._act(1 << self.seat)
+        self._draws += 1
+        return self.envs.static_actions[self.seat]
+
+    def update(self, rewards, dones):
+        return None
+
+
+class CnnPolicyAgent(_DevicePolicyAgent):
     """A player of either kitchen env (``envs.overcooked_env.OvercookedMadrona`` or the Simplecooked one of
     ``envs.overcooked2_env``) that acts under MAPPO's CNN policy on the device: ``get_action`` is ``mrl_cnn_act`` for this
     agent's seat -- ``player_num``, set by ``env.add_partner_agent``, or, while that is ``None``, the env's ``ego_ind`` -- on the
@@ -39,12 +64,6 @@ class CnnPolicyAgent(VectorAgent):
     those two on the GPU is refused with a ``TypeError`` by the constructor: there is no torch fallback.  ``obs`` and
     ``record`` of ``get_action`` are the ``VectorAgent`` protocol's; the kernel reads the simulator's observations itself and this
     agent keeps no buffers."""
-
-    def __init__(self, envs, policy, seed=0, greedy=False):
-        self.envs, self.policy, self.seed, self.greedy = envs, policy, int(seed), bool(greedy)
-        self.player_num = None
-        self._draws = 0
-        self._sim = self._check_env()
 
     def _check_env(self):
         from ..envs.overcooked2_env import OvercookedMadrona as SimplecookedMadrona
@@ -60,18 +79,9 @@ class CnnPolicyAgent(VectorAgent):
             raise TypeError(f"{type(self).__name__} needs the env on the simulator's GPU (cuda:{sim.gpu_id}); got env device {envs.device}")
         return sim
 
-    @property
-    def seat(self):
-        return self.envs.ego_ind if self.player_num is None else self.player_num
-
-    def get_action(self, obs=None, record=True):
+    def _act(self, mask):
         from ..simulators import cnn_act
-        cnn_act(self._sim, self.policy, 1 << self.seat, seed=self.seed, step=self._draws, greedy=self.greedy)
-        self._draws += 1
-        return self.envs.static_actions[self.seat]
-
-    def update(self, rewards, dones):
-        return None
+        cnn_act(self._sim, self.policy, mask, seed=self.seed, step=self._draws, greedy=self.greedy)
 
 
 class CnnPopulationAgent(CnnPolicyAgent):
@@ -112,13 +122,11 @@ class CnnPopulationAgent(CnnPolicyAgent):
         if self.resample is not None:
             self._resample = CnnResample(self.resample, self.members[0], len(self.members), p, self.seed)
 
-    def get_action(self, obs=None, record=True):
+    def _act(self, mask):
         from ..simulators import cnn_act_bank
         if self.ids is None:
             self._attach()
-        cnn_act_bank(self._sim, self.bank, self.ids, 1 << self.seat, seed=self.seed, step=self._draws, greedy=self.greedy)
-        self._draws += 1
-        return self.envs.static_actions[self.seat]
+        cnn_act_bank(self._sim, self.bank, self.ids, mask, seed=self.seed, step=self._draws, greedy=self.greedy)
 
     def update(self, rewards, dones):
         from ..simulators import cnn_resample
@@ -128,19 +136,13 @@ class CnnPopulationAgent(CnnPolicyAgent):
             cnn_resample(self._sim, self.ids, self.episodes, self._resample, None, None, players=1 << self.seat)
 
 
-class MlpBasePolicyAgent(VectorAgent):
+class MlpBasePolicyAgent(_DevicePolicyAgent):
     """A player of ``envs.balance_beam_env.BalanceMadronaTorch`` that acts under MAPPO's MLP policy on the device -- what the
     reference's ``CentralizedAgent`` does for the partner seat --, the counterpart of ``CnnPolicyAgent``: ``get_action`` is
     ``mrl_mlpbase_act`` for this agent's seat (``player_num``, set by ``env.add_partner_agent``, or, while that is ``None``, the
     env's ``ego_ind``) on the simulator's own observations, and returns the view ``env.static_actions[seat]``.  ``policy``: a
     ``simulators.MlpBasePolicy``; ``seed`` seeds the draws, whose step number counts this agent's calls.  ``update`` does nothing.
     Any other env, or one off the GPU, is refused with a ``TypeError`` by the constructor: there is no torch fallback."""
-
-    def __init__(self, envs, policy, seed=0, greedy=False):
-        self.envs, self.policy, self.seed, self.greedy = envs, policy, int(seed), bool(greedy)
-        self.player_num = None
-        self._draws = 0
-        self._sim = self._check_env()
 
     def _check_env(self):
         from ..envs.balance_beam_env import BalanceMadronaTorch
@@ -154,18 +156,9 @@ class MlpBasePolicyAgent(VectorAgent):
             raise TypeError(f"MlpBasePolicyAgent needs the env on the simulator's GPU (cuda:{sim.gpu_id}); got env device {envs.device}")
         return sim
 
-    @property
-    def seat(self):
-        return self.envs.ego_ind if self.player_num is None else self.player_num
-
-    def get_action(self, obs=None, record=True):
+    def _act(self, mask):
         from ..simulators import mlpbase_act
-        mlpbase_act(self._sim, self.policy, 1 << self.seat, seed=self.seed, step=self._draws, greedy=self.greedy)
-        self._draws += 1
-        return self.envs.static_actions[self.seat]
-
-    def update(self, rewards, dones):
-        return None
+        mlpbase_act(self._sim, self.policy, mask, seed=self.seed, step=self._draws, greedy=self.greedy)
 
 
 class CleanPPOAgent(VectorAgent):

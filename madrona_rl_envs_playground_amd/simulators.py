@@ -335,38 +335,43 @@ class CnnActorCritic(torch.nn.Module):
         return action, dist.log_prob(action), dist.entropy(), self.critic(obs)
 
 
-class CnnPolicy:
-    """The parameters ``mrl_cnn_act`` runs on an Overcooked or a Simplecooked simulator of the policy's shape: one flat float32 tensor ``params``, the actor's eight tensors and then the critic's in
-    the order of ``parameters_to_vector(CnnActorCritic.parameters())`` (``mrl_cnn_policy``).  ``module()`` returns a
-    ``CnnActorCritic`` whose parameters are VIEWS into ``params``: an optimizer's in-place step on them is what the kernel reads
-    next, with no copy in between (so there is no ``load_``)."""
+class _FlatPolicy:
+    """What ``CnnPolicy`` and ``MlpBasePolicy`` share: one flat float32 tensor ``params``, the actor's tensors and then the critic's in
+    the order of ``parameters_to_vector`` of the policy's torch module, and that module with its parameters as VIEWS into ``params``.
+    A subclass names its module class (``_module_class``, ``_module_name`` for messages), the shape fields that are both its own
+    constructor's and the module's leading arguments (``_shape``), its ``num_params`` and what ``mappo_update`` needs of it:
+    ``_mappo_workspace_bytes``, ``_mappo_check`` and ``_mappo_batch``."""
 
-    def __init__(self, width, height, channels, hidden=64, num_actions=6, device="cuda:0"):
-        self.width, self.height, self.channels, self.hidden, self.num_actions = int(width), int(height), int(channels), int(hidden), int(num_actions)
+    def _allocate(self, device, supported):
         if self.num_params == 0:
-            raise ValueError(f"mrl_cnn_act runs hidden = {_lib.CNN_HIDDEN}, num_actions = {_lib.CNN_ACTIONS} and kitchens of at least 3 x 3")
+            raise ValueError(supported)
         self.params = torch.zeros(self.num_params, dtype=torch.float32, device=torch.device(device))
         self._module = None
 
-    @property
-    def num_params(self):
-        return int(_lib.lib().mrl_cnn_policy_num_params(self.width, self.height, self.channels, self.hidden, self.num_actions))
+    def _check_params(self, gpu_id=None):
+        """``params`` is what the kernels take (``gpu_id``: on that device; default any GPU)"""
+        p = self.params
+        if (not p.is_cuda or (gpu_id is not None and p.device.index != gpu_id) or p.dtype != torch.float32 or not p.is_contiguous() or
+                p.numel() != self.num_params):
+            where = "a GPU" if gpu_id is None else f"cuda:{gpu_id}"
+            raise ValueError(f"policy.params must be a contiguous float32 tensor of num_params elements on {where}")
+        return p
 
     @classmethod
     def from_module(cls, module, device=None):
-        """A policy of ``module``'s shape (a ``CnnActorCritic``) holding a copy of its parameters (``device``: default its own)."""
-        if not isinstance(module, CnnActorCritic):
-            raise ValueError("module must be a CnnActorCritic")
+        """A policy of ``module``'s shape holding a copy of its parameters (``device``: default its own)."""
+        if not isinstance(module, cls._module_class):
+            raise ValueError(f"module must be {cls._module_name}")
         own = next(module.parameters()).device
-        policy = cls(module.width, module.height, module.channels, module.hidden, module.num_actions, device if device is not None else own)
+        policy = cls(*[getattr(module, name) for name in cls._shape], device if device is not None else own)
         with torch.no_grad():
             policy.params.copy_(torch.nn.utils.parameters_to_vector(module.parameters()).detach())
         return policy
 
     def module(self):
-        """The ``CnnActorCritic`` whose parameters alias ``params`` (one object per policy)."""
+        """The torch module whose parameters alias ``params`` (one object per policy)."""
         if self._module is None:
-            module = CnnActorCritic(self.width, self.height, self.channels, self.hidden, self.num_actions)
+            module = self._module_class(*[getattr(self, name) for name in self._shape])
             at = 0
             for p in module.parameters():  # actor first, then critic: the order of the flat array
                 p.data = self.params[at:at + p.numel()].view(p.shape)
@@ -375,14 +380,49 @@ class CnnPolicy:
             self._module = module
         return self._module
 
+
+class CnnPolicy(_FlatPolicy):
+    """The parameters ``mrl_cnn_act`` runs on an Overcooked or a Simplecooked simulator of the policy's shape: one flat float32 tensor ``params``, the actor's eight tensors and then the critic's in
+    the order of ``parameters_to_vector(CnnActorCritic.parameters())`` (``mrl_cnn_policy``).  ``module()`` returns a
+    ``CnnActorCritic`` whose parameters are VIEWS into ``params``: an optimizer's in-place step on them is what the kernel reads
+    next, with no copy in between (so there is no ``load_``)."""
+
+    _module_class, _module_name, _shape = CnnActorCritic, "a CnnActorCritic", ("width", "height", "channels", "hidden", "num_actions")
+
+    def __init__(self, width, height, channels, hidden=64, num_actions=6, device="cuda:0"):
+        self.width, self.height, self.channels, self.hidden, self.num_actions = int(width), int(height), int(channels), int(hidden), int(num_actions)
+        self._allocate(device, f"mrl_cnn_act runs hidden = {_lib.CNN_HIDDEN}, num_actions = {_lib.CNN_ACTIONS} and kitchens of at least 3 x 3")
+
+    @property
+    def num_params(self):
+        return int(_lib.lib().mrl_cnn_policy_num_params(self.width, self.height, self.channels, self.hidden, self.num_actions))
+
     def desc(self):
         return _lib.CnnPolicyDesc(self.params.data_ptr(), self.hidden, 0)
 
+    # what MappoOptimizer and mappo_update ask of a policy
+    def _mappo_workspace_bytes(self, minibatch_size, num_minibatches, out):
+        return _lib.lib().mrl_mappo_workspace_bytes(self.width, self.height, self.channels, self.hidden, minibatch_size, num_minibatches, out)
 
-class CnnRecord:
-    """The buffers of ``mrl_cnn_act`` / ``mrl_rollout_cnn`` (``mrl_cnn_record``): torch tensors by name plus the ctypes struct over
-    them.  ``actions`` int32, ``logprobs``, ``rewards``, ``dones`` (T, N, P); ``values`` (T + 1, N, P), row T the closing value;
-    ``next_done`` (N, P); ``logits`` (T, N, P, 6) on request."""
+    def _mappo_check(self, record, ring):
+        if not isinstance(record, CnnRecord):
+            raise ValueError("record must be a CnnRecord")
+
+    def _mappo_batch(self, record, ring, count):
+        """-> (entry point, policy struct, batch struct's type, the batch's observations): the record's ring"""
+        row_bytes = self.width * self.height * self.channels
+        if (not isinstance(ring, torch.Tensor) or ring.device != self.params.device or ring.dtype != torch.int8 or not ring.is_contiguous() or
+                ring.numel() < count * row_bytes):
+            raise ValueError(f"ring must be a contiguous torch.int8 tensor on {self.params.device} of at least {count * row_bytes} elements: "
+                             f"(T + 1, N, P, H, W, F) for the policy's {self.width} x {self.height} kitchen with {self.channels} channels")
+        shape = _lib.MappoPolicyDesc(self.params.data_ptr(), self.hidden, 0, self.width, self.height, self.channels)
+        return _lib.lib().mrl_mappo_update, shape, _lib.MappoBatch, ring
+
+
+class _MappoRecord:
+    """The buffers ``CnnRecord`` and ``MlpBaseRecord`` share: torch tensors by name plus the ctypes struct over them.  ``actions``
+    int32, ``logprobs``, ``rewards``, ``dones`` (T, N, P); ``values`` (T + 1, N, P), row T the closing value; ``next_done`` (N, P);
+    ``logits`` (T, N, P, actions) on request.  A subclass names its struct, the struct's buffers and the width of ``logits``."""
 
     def __init__(self, num_steps, num_worlds, num_players, device, logits=False):
         t, n, p = int(num_steps), int(num_worlds), int(num_players)
@@ -391,9 +431,12 @@ class CnnRecord:
         self.actions = z((t, n, p), torch.int32)
         self.logprobs, self.rewards, self.dones = z((t, n, p)), z((t, n, p)), z((t, n, p))
         self.values, self.next_done = z((t + 1, n, p)), z((n, p))
-        self.logits = z((t, n, p, _lib.CNN_ACTIONS)) if logits else None
-        self.struct = _lib.CnnRecordDesc(*[getattr(self, name).data_ptr() if getattr(self, name) is not None else None
-                                           for name in _lib.CNN_RECORD_BUFFERS], t)
+        self.logits = z((t, n, p, self._actions)) if logits else None
+        self._own_buffers(z, t, n, p)
+        self.struct = self._struct(*[getattr(self, name).data_ptr() if getattr(self, name) is not None else None for name in self._buffers], t)
+
+    def _own_buffers(self, z, t, n, p):
+        pass
 
     def rollout(self):
         """The record as the ``Rollout`` that ``gae`` takes: views flattened to N * P columns, ``next_value`` = ``values[T]``."""
@@ -402,13 +445,28 @@ class CnnRecord:
         return Rollout(None, flat(self.actions), flat(self.logprobs), self.values[:t].view(t, cols), flat(self.rewards), flat(self.dones),
                        None, self.values[t].view(cols), self.next_done.view(cols))
 
+    @classmethod
+    def _for_rollout(cls, record, num_steps, num_worlds, num_players, device):
+        """``record``, or a new one when it is None, for a rollout of ``num_steps`` steps"""
+        if record is None:
+            record = cls(num_steps, num_worlds, num_players, device)
+        if record.num_steps != int(num_steps):
+            raise ValueError(f"record holds {record.num_steps} steps, asked for {num_steps}")
+        return record
+
+
+class CnnRecord(_MappoRecord):
+    """The buffers of ``mrl_cnn_act`` / ``mrl_rollout_cnn`` (``mrl_cnn_record``): torch tensors by name plus the ctypes struct over
+    them.  ``actions`` int32, ``logprobs``, ``rewards``, ``dones`` (T, N, P); ``values`` (T + 1, N, P), row T the closing value;
+    ``next_done`` (N, P); ``logits`` (T, N, P, 6) on request."""
+
+    _struct, _buffers, _actions = _lib.CnnRecordDesc, _lib.CNN_RECORD_BUFFERS, _lib.CNN_ACTIONS
+
 
 def _cnn_call_args(sim, policy, players, record):
     if not isinstance(policy, CnnPolicy):
         raise ValueError("policy must be a CnnPolicy")
-    p = policy.params
-    if not p.is_cuda or p.device.index != sim.gpu_id or p.dtype != torch.float32 or not p.is_contiguous() or p.numel() != policy.num_params:
-        raise ValueError(f"policy.params must be a contiguous float32 tensor of num_params elements on cuda:{sim.gpu_id}")
+    p = policy._check_params(sim.gpu_id)
     shape = sim.observation_world_major_tensor().shape  # (N, P, H, W, F)
     if (policy.height, policy.width, policy.channels) != tuple(shape[2:]):
         raise ValueError(f"the policy is for a {policy.width} x {policy.height} kitchen with {policy.channels} channels, the simulator's "
@@ -735,68 +793,52 @@ class MlpBaseActorCritic(torch.nn.Module):
         return action, dist.log_prob(action), dist.entropy(), self.critic(obs)
 
 
-class MlpBasePolicy:
+class MlpBasePolicy(_FlatPolicy):
     """The parameters ``mrl_mlpbase_act`` runs on a balance-beam simulator: one flat float32 tensor ``params``, the actor's tensors
     and then the critic's in the order of ``parameters_to_vector(MlpBaseActorCritic.parameters())`` (``mrl_mlpbase_policy``; the
     unused ``fc_h`` is part of it and is never read or changed by a kernel).  ``module()`` returns an ``MlpBaseActorCritic`` whose
     parameters are VIEWS into ``params``: an in-place step on either side is what the other reads next (there is no ``load_``)."""
 
+    _module_class, _module_name, _shape = MlpBaseActorCritic, "an MlpBaseActorCritic", ("obs_dim", "num_actions", "hidden", "layer_N")
+
     def __init__(self, obs_dim=_lib.MLPBASE_OBS, num_actions=_lib.MLPBASE_ACTIONS, hidden=_lib.MLPBASE_HIDDEN, layer_N=2, device="cuda:0"):
         self.obs_dim, self.num_actions, self.hidden, self.layer_N = int(obs_dim), int(num_actions), int(hidden), int(layer_N)
-        if self.num_params == 0:
-            raise ValueError(f"mrl_mlpbase_act runs obs_dim = {_lib.MLPBASE_OBS}, num_actions = {_lib.MLPBASE_ACTIONS}, hidden = "
-                             f"{_lib.MLPBASE_HIDDEN} and layer_N 1 or 2; got {self.obs_dim}, {self.num_actions}, {self.hidden}, {self.layer_N}")
-        self.params = torch.zeros(self.num_params, dtype=torch.float32, device=torch.device(device))
-        self._module = None
+        self._allocate(device, f"mrl_mlpbase_act runs obs_dim = {_lib.MLPBASE_OBS}, num_actions = {_lib.MLPBASE_ACTIONS}, hidden = "
+                               f"{_lib.MLPBASE_HIDDEN} and layer_N 1 or 2; got {self.obs_dim}, {self.num_actions}, {self.hidden}, {self.layer_N}")
 
     @property
     def num_params(self):
         return int(_lib.lib().mrl_mlpbase_policy_num_params(self.obs_dim, self.hidden, self.layer_N, self.num_actions))
 
-    @classmethod
-    def from_module(cls, module, device=None):
-        """A policy of ``module``'s shape (an ``MlpBaseActorCritic``) holding a copy of its parameters (``device``: default its own)."""
-        if not isinstance(module, MlpBaseActorCritic):
-            raise ValueError("module must be an MlpBaseActorCritic")
-        own = next(module.parameters()).device
-        policy = cls(module.obs_dim, module.num_actions, module.hidden, module.layer_N, device if device is not None else own)
-        with torch.no_grad():
-            policy.params.copy_(torch.nn.utils.parameters_to_vector(module.parameters()).detach())
-        return policy
-
-    def module(self):
-        """The ``MlpBaseActorCritic`` whose parameters alias ``params`` (one object per policy)."""
-        if self._module is None:
-            module = MlpBaseActorCritic(self.obs_dim, self.num_actions, self.hidden, self.layer_N)
-            at = 0
-            for p in module.parameters():  # actor first, then critic: the order of the flat array
-                p.data = self.params[at:at + p.numel()].view(p.shape)
-                at += p.numel()
-            assert at == self.params.numel()
-            self._module = module
-        return self._module
-
     def desc(self):
         return _lib.MlpBasePolicyDesc(self.params.data_ptr(), self.hidden, self.layer_N, 0)
 
+    # what MappoOptimizer and mappo_update ask of a policy
+    def _mappo_workspace_bytes(self, minibatch_size, num_minibatches, out):
+        return _lib.lib().mrl_mappo_mlp_workspace_bytes(self.obs_dim, self.hidden, self.layer_N, self.num_actions, minibatch_size,
+                                                        num_minibatches, out)
 
-class MlpBaseRecord:
+    def _mappo_check(self, record, ring):
+        if not isinstance(record, MlpBaseRecord):
+            raise ValueError("record must be an MlpBaseRecord")
+        if ring is not None:
+            raise ValueError("an MlpBasePolicy's batch is record.obs: ring must be None")
+
+    def _mappo_batch(self, record, ring, count):
+        """-> (entry point, policy struct, batch struct's type, the batch's observations): the record's ``obs``"""
+        rows = count + count // max(record.num_steps, 1)
+        _require_tensors([("record.obs", record.obs, torch.int32, rows * self.obs_dim)], self.params.device)
+        return _lib.lib().mrl_mappo_mlp_update, self.desc(), _lib.MappoMlpBatch, record.obs
+
+
+class MlpBaseRecord(_MappoRecord):
     """The buffers of ``mrl_mlpbase_act`` / ``mrl_rollout_mlpbase`` (``mrl_mlpbase_record``): ``CnnRecord``'s arrays and row
     convention (``logits`` (T, N, P, 4) on request) and ``obs`` int32 (T + 1, N, P, 7), row k what the act at row k read."""
 
-    def __init__(self, num_steps, num_worlds, num_players, device, logits=False):
-        t, n, p = int(num_steps), int(num_worlds), int(num_players)
-        z = lambda shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=device)  # noqa: E731
-        self.num_steps, self.num_worlds, self.num_players = t, n, p
-        self.actions = z((t, n, p), torch.int32)
-        self.logprobs, self.rewards, self.dones = z((t, n, p)), z((t, n, p)), z((t, n, p))
-        self.values, self.next_done = z((t + 1, n, p)), z((n, p))
-        self.logits = z((t, n, p, _lib.MLPBASE_ACTIONS)) if logits else None
-        self.obs = z((t + 1, n, p, _lib.MLPBASE_OBS), torch.int32)
-        self.struct = _lib.MlpBaseRecordDesc(*[getattr(self, name).data_ptr() if getattr(self, name) is not None else None
-                                               for name in _lib.MLPBASE_RECORD_BUFFERS], t)
+    _struct, _buffers, _actions = _lib.MlpBaseRecordDesc, _lib.MLPBASE_RECORD_BUFFERS, _lib.MLPBASE_ACTIONS
 
-    rollout = CnnRecord.rollout
+    def _own_buffers(self, z, t, n, p):
+        self.obs = z((t + 1, n, p, _lib.MLPBASE_OBS), torch.int32)
 
 
 def _mlpbase_call_args(sim, policy, players, record):
@@ -804,17 +846,12 @@ def _mlpbase_call_args(sim, policy, players, record):
         raise ValueError("policy must be an MlpBasePolicy")
     if not isinstance(sim, BalanceBeamSimulator):
         raise ValueError("mrl_mlpbase_act runs on a BalanceBeamSimulator")
-    p = policy.params
-    if not p.is_cuda or p.device.index != sim.gpu_id or p.dtype != torch.float32 or not p.is_contiguous() or p.numel() != policy.num_params:
-        raise ValueError(f"policy.params must be a contiguous float32 tensor of num_params elements on cuda:{sim.gpu_id}")
+    p = policy._check_params(sim.gpu_id)
     seats, worlds = sim.observation_tensor().shape[:2]  # (P, N, 7)
     if record is not None and (not isinstance(record, MlpBaseRecord) or record.num_worlds != worlds or record.num_players != seats or
                                record.actions.device != p.device):
         raise ValueError(f"record must be an MlpBaseRecord of {worlds} worlds and {seats} players on cuda:{sim.gpu_id}")
-    mask = (1 << seats) - 1 if players is None else players
-    if not isinstance(mask, int):
-        mask = sum(1 << int(seat) for seat in mask)
-    return mask & 0xFFFFFFFF if 0 <= mask < 2 ** 32 else 0xFFFFFFFF
+    return _seat_mask(players, seats)
 
 
 def mlpbase_act(sim, policy, players=None, record=None, row=0, seed=0, step=0, greedy=False, value_only=False):
@@ -1277,14 +1314,8 @@ class MappoOptimizer(_AdamState):
 
     def workspace_bytes(self, minibatch_size, num_minibatches):
         """``mrl_mappo_workspace_bytes`` (``mrl_mappo_mlp_workspace_bytes`` for an ``MlpBasePolicy``) for this policy's shape."""
-        p = self.policy
         out = ctypes.c_uint64(0)
-        if isinstance(p, MlpBasePolicy):
-            _lib.check(_lib.lib().mrl_mappo_mlp_workspace_bytes(p.obs_dim, p.hidden, p.layer_N, p.num_actions, int(minibatch_size),
-                                                                int(num_minibatches), ctypes.byref(out)))
-            return int(out.value)
-        _lib.check(_lib.lib().mrl_mappo_workspace_bytes(p.width, p.height, p.channels, p.hidden, int(minibatch_size), int(num_minibatches),
-                                                        ctypes.byref(out)))
+        _lib.check(self.policy._mappo_workspace_bytes(int(minibatch_size), int(num_minibatches), ctypes.byref(out)))
         return int(out.value)
 
 
@@ -1298,7 +1329,7 @@ def mappo_advantages(record, value_norm=None, gamma=0.99, gae_lambda=0.95, seats
     ``seats`` (default ``None``: as above): a list of seats; the mean and the std are then taken over those seats' columns only and
     only those columns are normalised -- the others keep their raw GAE advantages.  That is what an ego trained against frozen
     partners of a ``CnnPolicyBank`` needs: the partners' columns hold values of other critics."""
-    if not isinstance(record, (CnnRecord, MlpBaseRecord)):
+    if not isinstance(record, _MappoRecord):
         raise ValueError("record must be a CnnRecord or an MlpBaseRecord")
     if seats is not None:
         seats = sorted({int(seat) for seat in seats})
@@ -1338,22 +1369,14 @@ def mappo_update(policy, optimizer, record, ring, advantages, returns, indices, 
     For an ``MlpBasePolicy`` (the balance beam; ``mrl_mappo_mlp_update``) ``record`` is an ``MlpBaseRecord``, the batch is its
     ``obs`` and ``ring`` must be ``None``.
     Not built: active masks, PopArt, recurrent policies, ``update_actor=False``, weight decay."""
-    if isinstance(policy, MlpBasePolicy):
-        return _mappo_mlp_update(policy, optimizer, record, ring, advantages, returns, indices, value_norm, clip_param, entropy_coef,
-                                 value_loss_coef, max_grad_norm, huber_delta, use_huber_loss, use_clipped_value_loss, use_max_grad_norm,
-                                 stats, grads)
-    if not isinstance(policy, CnnPolicy) or not isinstance(optimizer, MappoOptimizer) or optimizer.policy is not policy:
-        raise ValueError("policy must be a CnnPolicy and optimizer the MappoOptimizer made for it")
-    if not isinstance(record, CnnRecord):
-        raise ValueError("record must be a CnnRecord")
+    if not isinstance(policy, (CnnPolicy, MlpBasePolicy)) or not isinstance(optimizer, MappoOptimizer) or optimizer.policy is not policy:
+        raise ValueError("policy must be a CnnPolicy or an MlpBasePolicy and optimizer the MappoOptimizer made for it")
+    policy._mappo_check(record, ring)  # the record is the policy's kind, and so is the ring
     if value_norm is not None and not isinstance(value_norm, ValueNorm):
         raise ValueError("value_norm must be a ValueNorm or None")
-    p = policy.params
-    if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous() or p.numel() != policy.num_params:
-        raise ValueError("policy.params must be a contiguous float32 tensor of num_params elements on a GPU")
+    p = policy._check_params()
     device, f32 = p.device, torch.float32
     count = record.num_steps * record.num_worlds * record.num_players
-    row_bytes = policy.width * policy.height * policy.channels
     # views of the record's first T rows: contiguous, because the rows are the leading dimension
     wanted = [("policy.params", p, f32, p.numel()), ("optimizer.exp_avg", optimizer.exp_avg, f32, p.numel()),
               ("optimizer.exp_avg_sq", optimizer.exp_avg_sq, f32, p.numel()), ("record.actions", record.actions, torch.int32, count),
@@ -1362,14 +1385,10 @@ def mappo_update(policy, optimizer, record, ring, advantages, returns, indices, 
     if value_norm is not None:
         wanted.append(("value_norm.state", value_norm.state, f32, 3))
     _require_tensors(wanted, device)
-    if (not isinstance(ring, torch.Tensor) or ring.device != device or ring.dtype != torch.int8 or not ring.is_contiguous() or
-            ring.numel() < count * row_bytes):
-        raise ValueError(f"ring must be a contiguous torch.int8 tensor on {device} of at least {count * row_bytes} elements: (T + 1, N, P, "
-                         f"H, W, F) for the policy's {policy.width} x {policy.height} kitchen with {policy.channels} channels")
-    shape = _lib.MappoPolicyDesc(p.data_ptr(), policy.hidden, 0, policy.width, policy.height, policy.channels)
+    entry, shape, batch_type, obs = policy._mappo_batch(record, ring, count)  # the policy's own entry point and batch
     opt = _lib.MappoOptimizerDesc(p.data_ptr(), optimizer.exp_avg.data_ptr(), optimizer.exp_avg_sq.data_ptr(), optimizer.step)
-    batch = _lib.MappoBatch(ring.data_ptr(), record.actions.data_ptr(), record.logprobs.data_ptr(), record.values.data_ptr(),
-                            returns.data_ptr(), advantages.data_ptr(), count)
+    batch = batch_type(obs.data_ptr(), record.actions.data_ptr(), record.logprobs.data_ptr(), record.values.data_ptr(), returns.data_ptr(),
+                       advantages.data_ptr(), count)
     beta = value_norm.beta if value_norm is not None else 0.99999
     flags = ((_lib.MAPPO_VALUENORM if value_norm is not None else 0) | (_lib.MAPPO_HUBER_LOSS if use_huber_loss else 0) |
              (_lib.MAPPO_CLIPPED_VALUE_LOSS if use_clipped_value_loss else 0) | (_lib.MAPPO_MAX_GRAD_NORM if use_max_grad_norm else 0))
@@ -1377,47 +1396,7 @@ def mappo_update(policy, optimizer, record, ring, advantages, returns, indices, 
     cfg = _lib.MappoConfig(clip_param, entropy_coef, value_loss_coef, max_grad_norm, huber_delta, optimizer.lr, optimizer.critic_lr,
                            optimizer.betas[0], optimizer.betas[1], optimizer.eps, beta, 1.0 - beta,
                            value_norm.epsilon if value_norm is not None else 1e-5, flags)
-    return _run_update(_lib.lib().mrl_mappo_update, (ctypes.byref(shape), ctypes.byref(opt), ctypes.byref(batch)), indices,
-                       (ctypes.byref(cfg), value_norm.state.data_ptr() if value_norm is not None else None), optimizer,
-                       len(_lib.MAPPO_STATS), MappoResult, stats, grads)
-
-
-def _mappo_mlp_update(policy, optimizer, record, ring, advantages, returns, indices, value_norm, clip_param, entropy_coef, value_loss_coef,
-                      max_grad_norm, huber_delta, use_huber_loss, use_clipped_value_loss, use_max_grad_norm, stats, grads):
-    """``mappo_update`` for an ``MlpBasePolicy``: the same checks and configuration, the batch's observations are ``record.obs``"""
-    if not isinstance(optimizer, MappoOptimizer) or optimizer.policy is not policy:
-        raise ValueError("optimizer must be the MappoOptimizer made for the policy")
-    if not isinstance(record, MlpBaseRecord):
-        raise ValueError("record must be an MlpBaseRecord")
-    if ring is not None:
-        raise ValueError("an MlpBasePolicy's batch is record.obs: ring must be None")
-    if value_norm is not None and not isinstance(value_norm, ValueNorm):
-        raise ValueError("value_norm must be a ValueNorm or None")
-    p = policy.params
-    if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous() or p.numel() != policy.num_params:
-        raise ValueError("policy.params must be a contiguous float32 tensor of num_params elements on a GPU")
-    device, f32 = p.device, torch.float32
-    count = record.num_steps * record.num_worlds * record.num_players
-    per_row = count // max(record.num_steps, 1)
-    wanted = [("policy.params", p, f32, p.numel()), ("optimizer.exp_avg", optimizer.exp_avg, f32, p.numel()),
-              ("optimizer.exp_avg_sq", optimizer.exp_avg_sq, f32, p.numel()), ("record.actions", record.actions, torch.int32, count),
-              ("record.logprobs", record.logprobs, f32, count), ("record.values", record.values, f32, count + per_row),
-              ("record.obs", record.obs, torch.int32, (count + per_row) * policy.obs_dim),
-              ("advantages", advantages, f32, count), ("returns", returns, f32, count), ("indices", indices, torch.int32, None)]
-    if value_norm is not None:
-        wanted.append(("value_norm.state", value_norm.state, f32, 3))
-    _require_tensors(wanted, device)
-    shape = policy.desc()
-    opt = _lib.MappoOptimizerDesc(p.data_ptr(), optimizer.exp_avg.data_ptr(), optimizer.exp_avg_sq.data_ptr(), optimizer.step)
-    batch = _lib.MappoMlpBatch(record.obs.data_ptr(), record.actions.data_ptr(), record.logprobs.data_ptr(), record.values.data_ptr(),
-                               returns.data_ptr(), advantages.data_ptr(), count)
-    beta = value_norm.beta if value_norm is not None else 0.99999
-    flags = ((_lib.MAPPO_VALUENORM if value_norm is not None else 0) | (_lib.MAPPO_HUBER_LOSS if use_huber_loss else 0) |
-             (_lib.MAPPO_CLIPPED_VALUE_LOSS if use_clipped_value_loss else 0) | (_lib.MAPPO_MAX_GRAD_NORM if use_max_grad_norm else 0))
-    cfg = _lib.MappoConfig(clip_param, entropy_coef, value_loss_coef, max_grad_norm, huber_delta, optimizer.lr, optimizer.critic_lr,
-                           optimizer.betas[0], optimizer.betas[1], optimizer.eps, beta, 1.0 - beta,
-                           value_norm.epsilon if value_norm is not None else 1e-5, flags)
-    return _run_update(_lib.lib().mrl_mappo_mlp_update, (ctypes.byref(shape), ctypes.byref(opt), ctypes.byref(batch)), indices,
+    return _run_update(entry, (ctypes.byref(shape), ctypes.byref(opt), ctypes.byref(batch)), indices,
                        (ctypes.byref(cfg), value_norm.state.data_ptr() if value_norm is not None else None), optimizer,
                        len(_lib.MAPPO_STATS), MappoResult, stats, grads)
 
@@ -1483,10 +1462,7 @@ class ActsWithCnnPolicy:
         earlier call's, filled again.  Afterwards the observations of the state reached (slot T) are also where the simulator's output
         pointed before the call -- ``static_world_major_observations`` unless ``n_step(out=...)`` redirected it -- so rollouts chain.  ``simulators.gae(record.rollout(), gamma, gae_lambda)`` gives the advantages."""
         device = self.static_actions.device
-        if record is None:
-            record = CnnRecord(num_steps, self.num_envs, self.num_players, device)
-        if record.num_steps != int(num_steps):
-            raise ValueError(f"record holds {record.num_steps} steps, asked for {num_steps}")
+        record = CnnRecord._for_rollout(record, num_steps, self.num_envs, self.num_players, device)
         if ring is None:
             ring = torch.empty((int(num_steps) + 1,) + tuple(self.static_world_major_observations.shape), dtype=torch.int8, device=device)
         self.sim.rollout_cnn(policy, record, ring, players=players, seed=seed, first_step=first_step, greedy=greedy)
@@ -1506,10 +1482,7 @@ class ActsWithCnnPolicy:
         that have just restarted draw their next policies into ``ids`` and count in ``episodes`` (int32 (N), made when ``None`` and
         then kept by the env as ``bank_episodes``)."""
         device = self.static_actions.device
-        if record is None:
-            record = CnnRecord(num_steps, self.num_envs, self.num_players, device)
-        if record.num_steps != int(num_steps):
-            raise ValueError(f"record holds {record.num_steps} steps, asked for {num_steps}")
+        record = CnnRecord._for_rollout(record, num_steps, self.num_envs, self.num_players, device)
         if ring is None:
             ring = torch.empty((int(num_steps) + 1,) + tuple(self.static_world_major_observations.shape), dtype=torch.int8, device=device)
         if ids_record is None:
@@ -1538,10 +1511,7 @@ class ActsWithMlpBasePolicy:
         """``num_steps`` steps under ``policy`` without the host in the loop (``mrl_rollout_mlpbase``) -> an ``MlpBaseRecord``
         whose ``obs[k]`` is what the act of step k saw.  ``record``: an earlier call's, filled again.  Rollouts chain: the next one
         acts on the state this one reached.  ``simulators.mappo_advantages(record)`` gives the advantages."""
-        if record is None:
-            record = MlpBaseRecord(num_steps, self.num_envs, self.n_players, self.static_actions.device)
-        if record.num_steps != int(num_steps):
-            raise ValueError(f"record holds {record.num_steps} steps, asked for {num_steps}")
+        record = MlpBaseRecord._for_rollout(record, num_steps, self.num_envs, self.n_players, self.static_actions.device)
         self.sim.rollout_mlpbase(policy, record, players=players, seed=seed, first_step=first_step, greedy=greedy)
         return record
 
