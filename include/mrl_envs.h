@@ -1105,11 +1105,63 @@ int mrl_rollout_mlpbase(mrl_sim *sim, uint32_t players, const mrl_mlpbase_policy
                         uint64_t seed, uint32_t first_step, void *hip_stream);
 int mrl_mappo_mlp_workspace_bytes(uint32_t obs_dim, uint32_t hidden, uint32_t layer_N, uint32_t num_actions, uint32_t minibatch_size,
                                   uint32_t num_minibatches, uint64_t *out);
+
 int mrl_mappo_mlp_update(const mrl_mlpbase_policy *policy, const mrl_mappo_optimizer *opt, const mrl_mappo_mlp_batch *batch,
                          const int32_t *indices_dev /* (K, B) */, uint32_t num_minibatches /* K */, uint32_t minibatch_size /* B */,
                          const mrl_mappo_config *cfg, float *value_norm_state_dev_or_null /* (3) */, void *workspace_dev,
                          uint64_t workspace_bytes, float *stats_dev_or_null /* (K, 8) */, float *grads_dev_or_null /* (K, P) */,
                          int gpu_id, void *hip_stream);
+
+/* A population of partners on the balance beam: a BANK of K MLPBase policies of one shape and a policy per (world, seat) cell,
+ * the counterpart of mrl_cnn_bank and its calls above for the world where cross-play between trained conventions is the thing
+ * measured (the reference's --seed_skip and --pop_size).  No reference counterpart as calls.  DESIGN.md section 20.
+ *   Bank (mrl_mlpbase_bank): params_dev is a float32 device array of K = num_policies rows, `stride` floats apart (stride >=
+ *     mrl_mlpbase_policy_num_params(7, 64, layer_N, 4)); row k is exactly an mrl_mlpbase_policy's params_dev, so mrl_mlpbase_act,
+ *     mrl_mappo_mlp_update and the bank act read and write the same floats.  1 <= K <= 256.  hidden, layer_N and flags as in
+ *     mrl_mlpbase_policy: one layer_N for the whole bank.
+ *   Assignment: ids, int32 (N, P), device memory, the caller's, with mrl_cnn_act_bank's contract.  ids[n, p] = k >= 0: seat p of
+ *     world n acts under row k.  -1 (any negative value): the cell is not acted -- its ACTION entry and its record cells,
+ *     record.obs included, keep every byte.  A value >= K is outside the contract: the cell is treated as -1 and, where its seat
+ *     is in `players`, counted in the workspace's out_of_range word [2].  A cell is acted when its seat's bit is set in `players`
+ *     AND its id is valid.
+ *   mrl_mlpbase_act_bank is the plan and the act, on hip_stream: two launches up to M = N P = 2048 cells, four beyond.  The plan
+ *     is mrl_cnn_act_bank's own -- the same kernels, the same tile size of 32 and the same workspace words, described there -- and
+ *     the workspace is mrl_cnn_bank_workspace_bytes(N, 2, K) bytes (mrl_mlpbase_bank_workspace_bytes(N, K) is that number).  The
+ *     act is mrl_mlpbase_act's kernel body over the plan's tiles: the same LDS image, the same products in the same order, the
+ *     same LayerNorm sums, the same hash of (seed, step, n, p), the same head and flags, the same OBSERVATION tensor read in
+ *     place, with the tile's rows taken from the list and the parameters from params_dev + policy * stride.  A sample's arithmetic
+ *     reads its own rows and the tile's common weights only, so every output is bit for bit what mrl_mlpbase_act gives that cell
+ *     under that policy, whatever else shares the tile.  The grid is sized for the bound ceil(N seats / 32) + K; workgroups past
+ *     `tiles` leave at once.  Record rows, the observation rows included, are written for acted cells only; values, rewards and
+ *     dones come from the critic of the cell's own policy.  ids_row, (N, P) int32 or NULL, receives the ids as this act used
+ *     them: k for an acted cell, -1 for every other.  No float atomics, no workgroup waits on another, no scratch.
+ *   Refusals (MRL_ERR_INVALID, nothing enqueued): those of mrl_mlpbase_act; K = 0 or K > 256; stride below
+ *     mrl_mlpbase_policy_num_params; NULL ids; ids or ids_row off a 4-byte boundary; a workspace below
+ *     mrl_cnn_bank_workspace_bytes(N, 2, K) or off a 16-byte boundary.
+ * mrl_mlpbase_bank_resample: mrl_cnn_bank_resample on a balance-beam simulator -- the same kernel, which reads DONE, the ids and
+ *     the episodes only, the same mrl_cnn_resample descriptor, draws and refusals (`players` as for mrl_mlpbase_act); any other
+ *     simulator is refused.
+ * mrl_rollout_mlpbase_bank: mrl_rollout_mlpbase's loop with the bank act -- for k < T: the bank act at row k with step number
+ *     first_step + k (ids_record row k, when given, receives that act's ids_row), the ordinary step, then, with a resample,
+ *     mrl_mlpbase_bank_resample; then the closing MRL_MLPBASE_VALUE_ONLY bank act at row T (ids_record row T).  ids_record is
+ *     int32 (T + 1, N, P).  No host wait inside; two rollouts of T equal one of 2 T, ids and episodes included.  With resample
+ *     NULL neither ids nor episodes change (episodes may then be NULL).  Refusals: those of mrl_mlpbase_act_bank and
+ *     mrl_mlpbase_bank_resample, a NULL record, NULL episodes with a resample. */
+typedef struct mrl_mlpbase_bank {
+    const float *params_dev;    /* (num_policies, stride) */
+    uint32_t num_policies;
+    uint64_t stride;            /* floats between rows */
+    uint32_t hidden, layer_N, flags;
+} mrl_mlpbase_bank;
+uint64_t mrl_mlpbase_bank_workspace_bytes(uint32_t num_worlds, uint32_t num_policies);
+int mrl_mlpbase_act_bank(mrl_sim *sim, uint32_t players, const mrl_mlpbase_bank *bank, const int32_t *ids_dev,
+                         const mrl_mlpbase_record *record_or_null, int32_t *ids_row_or_null, uint32_t row, uint64_t seed, uint32_t step,
+                         uint32_t flags, void *workspace_dev, uint64_t workspace_bytes, void *hip_stream);
+int mrl_mlpbase_bank_resample(mrl_sim *sim, uint32_t players, const mrl_cnn_resample *resample, int32_t *ids_dev, int32_t *episodes_dev,
+                              void *hip_stream);
+int mrl_rollout_mlpbase_bank(mrl_sim *sim, uint32_t players, const mrl_mlpbase_bank *bank, int32_t *ids_dev, int32_t *episodes_dev,
+                             const mrl_cnn_resample *resample_or_null, const mrl_mlpbase_record *record, int32_t *ids_record_or_null,
+                             uint64_t seed, uint32_t first_step, void *workspace_dev, uint64_t workspace_bytes, void *hip_stream);
 
 int mrl_tensor(mrl_sim *sim, int slot, mrl_tensor_desc *out);
 int mrl_game(const mrl_sim *sim);

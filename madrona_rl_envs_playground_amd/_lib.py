@@ -57,7 +57,8 @@ SYMBOLS = [
     "mrl_cnn_workspace_bytes", "mrl_cnn_act", "mrl_rollout_cnn", "mrl_mappo_workspace_bytes", "mrl_mappo_update",
     "mrl_agent_update_workspace_bytes", "mrl_agent_update", "mrl_mlpbase_policy_num_params", "mrl_mlpbase_act",
     "mrl_rollout_mlpbase", "mrl_mappo_mlp_workspace_bytes", "mrl_mappo_mlp_update", "mrl_cnn_bank_workspace_bytes",
-    "mrl_cnn_act_bank", "mrl_cnn_bank_resample", "mrl_rollout_cnn_bank",
+    "mrl_cnn_act_bank", "mrl_cnn_bank_resample", "mrl_rollout_cnn_bank", "mrl_mlpbase_bank_workspace_bytes", "mrl_mlpbase_act_bank",
+    "mrl_mlpbase_bank_resample", "mrl_rollout_mlpbase_bank",
 ]
 ABI_VERSION = 4  # MRL_ABI_VERSION of include/mrl_envs.h this binding was written against
 
@@ -172,6 +173,11 @@ MLPBASE_RECORD_BUFFERS = CNN_RECORD_BUFFERS + ("obs",)
 
 class MlpBaseRecordDesc(ctypes.Structure):  # mrl_mlpbase_record
     _fields_ = [(name, ctypes.c_void_p) for name in MLPBASE_RECORD_BUFFERS] + [("num_steps", ctypes.c_uint32)]
+
+
+class MlpBaseBankDesc(ctypes.Structure):  # mrl_mlpbase_bank
+    _fields_ = [("params_dev", ctypes.c_void_p), ("num_policies", ctypes.c_uint32), ("stride", ctypes.c_uint64), ("hidden", ctypes.c_uint32),
+                ("layer_N", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
 
 
 class MappoMlpBatch(ctypes.Structure):  # mrl_mappo_mlp_batch
@@ -324,6 +330,13 @@ def lib():
     L.mrl_mlpbase_act.argtypes = [vp, u32, ctypes.POINTER(MlpBasePolicyDesc), ctypes.POINTER(MlpBaseRecordDesc), u32, ctypes.c_uint64, u32,
                                   u32, vp]
     L.mrl_rollout_mlpbase.argtypes = [vp, u32, ctypes.POINTER(MlpBasePolicyDesc), ctypes.POINTER(MlpBaseRecordDesc), ctypes.c_uint64, u32, vp]
+    L.mrl_mlpbase_bank_workspace_bytes.argtypes = [u32, u32]
+    L.mrl_mlpbase_bank_workspace_bytes.restype = ctypes.c_uint64
+    L.mrl_mlpbase_act_bank.argtypes = [vp, u32, ctypes.POINTER(MlpBaseBankDesc), vp, ctypes.POINTER(MlpBaseRecordDesc), vp, u32, ctypes.c_uint64,
+                                       u32, u32, vp, ctypes.c_uint64, vp]
+    L.mrl_mlpbase_bank_resample.argtypes = [vp, u32, ctypes.POINTER(CnnResampleDesc), vp, vp, vp]
+    L.mrl_rollout_mlpbase_bank.argtypes = [vp, u32, ctypes.POINTER(MlpBaseBankDesc), vp, vp, ctypes.POINTER(CnnResampleDesc),
+                                           ctypes.POINTER(MlpBaseRecordDesc), vp, ctypes.c_uint64, u32, vp, ctypes.c_uint64, vp]
     L.mrl_mappo_mlp_workspace_bytes.argtypes = [u32, u32, u32, u32, u32, u32, ctypes.POINTER(ctypes.c_uint64)]
     L.mrl_mappo_mlp_update.argtypes = [ctypes.POINTER(MlpBasePolicyDesc), ctypes.POINTER(MappoOptimizerDesc), ctypes.POINTER(MappoMlpBatch),
                                        vp, u32, u32, ctypes.POINTER(MappoConfig), vp, vp, ctypes.c_uint64, vp, vp, i32, vp]

@@ -1,5 +1,5 @@
 // What the act kernels of MAPPO's two actor-critics share (mrl_cnn_act and mrl_cnn_act_bank through cnn_act_body.hpp,
-// mrl_mlpbase_act in mlpbase_policy.hip; DESIGN.md sections 15, 18 and 19): the arguments every act carries whatever its network,
+// mrl_mlpbase_act and mrl_mlpbase_act_bank through mlpbase_act_body.hpp; DESIGN.md sections 15, 18, 19 and 20): the arguments every act carries whatever its network,
 // the map from a sample of the call to its (world, seat), and the tail that turns the head's outputs into the record's rows.
 #pragma once
 

@@ -1,0 +1,68 @@
+// The plan of a bank act, shared by the banks of both of MAPPO's actor-critics (mrl_cnn_act_bank in cnn_bank.hip,
+// mrl_mlpbase_act_bank in mlpbase_bank.hip; DESIGN.md sections 19 and 20): the acted cells of every policy gathered into that
+// policy's sample list, the lists cut into tiles of at most 32 samples.  The kernels live in bank_plan.hip.
+//
+// THE WORKSPACE, in uint32 words (include/mrl_envs.h repeats this: a test reads it back).  M = N P cells, Kp = K rounded up to a
+// multiple of 4, max_tiles = ceil(M / 32) + K:
+//     [0] tiles   [1] acted   [2] out_of_range   [3] 0
+//     [4, 4 + Kp)                     count[k]: the acted cells of policy k
+//     [4 + Kp, 4 + 2 Kp)              start[k]: where policy k's list begins in `lists` (the exclusive prefix of count)
+//     [4 + 2 Kp, 4 + 2 Kp + 4 max_tiles)   the tile table, four words per tile: policy, first (an index into lists), rows, 0
+//     then M rounded up to a multiple of 4: lists, samples s = n P + p, every policy's in ascending s
+//     then ceil(M / 1024) rows of Kp + 4 words: the plan's own (per chunk of 1024 cells, the cells of every policy in front of
+//     the chunk and the chunk's ids beyond the bank; written only when M > 2048)
+#pragma once
+
+#include "common.hpp"
+
+namespace mrl {
+
+constexpr uint32_t kBankMaxPolicies = 256, kBankPlanThreads = 1024;
+constexpr uint32_t kBankPlanSingle = 2048;  // up to this many cells one workgroup plans; beyond, a workgroup per 1024 cells
+constexpr uint32_t kBankTile = 32;          // the samples of a tile: both nets' act kernels run tiles of 32
+
+struct BankLayout {
+    uint64_t count_at, start_at, table_at, lists_at, chunks_at, words;  // word offsets
+    uint64_t max_tiles, chunk_ld;
+};
+constexpr BankLayout bank_layout(uint64_t num_worlds, uint64_t num_players, uint64_t num_policies)
+{
+    const uint64_t M = num_worlds * num_players, Kp = (num_policies + 3u) & ~(uint64_t)3u, max_tiles = (M + kBankTile - 1) / kBankTile + num_policies;
+    const uint64_t lists_at = 4 + 2 * Kp + 4 * max_tiles, chunks_at = lists_at + ((M + 3u) & ~(uint64_t)3u);
+    const uint64_t chunks = (M + kBankPlanThreads - 1) / kBankPlanThreads, chunk_ld = Kp + 4;
+    return BankLayout{4, 4 + Kp, 4 + 2 * Kp, lists_at, chunks_at, chunks_at + chunks * chunk_ld, max_tiles, chunk_ld};
+}
+
+struct BankPlanArgs {
+    const int32_t *ids;      // (N, P)
+    int32_t *ids_row;        // (N, P) or nullptr: k where the cell is acted, -1 elsewhere
+    uint32_t *workspace;     // the layout above
+    uint32_t cells, P, players, num_policies;
+    BankLayout at;
+};
+
+// the plan on `stream`: one launch up to kBankPlanSingle cells, three beyond
+void launch_bank_plan(const BankPlanArgs &args, hipStream_t stream);
+
+// a tile of the plan as an act body's map: rows of one policy's list (Args: the act's arguments, for P)
+struct BankTileMap {
+    const uint32_t *list;
+    uint32_t rows;
+    __device__ __forceinline__ bool has(uint32_t row) const { return row < rows; }
+    template <class Args>
+    __device__ __forceinline__ void locate(const Args &a, uint32_t row, uint32_t &world, uint32_t &seat) const
+    {
+        const uint32_t s = list[row];
+        world = s / a.P;
+        seat = s - world * a.P;
+    }
+    template <class Args>
+    __device__ __forceinline__ bool sample(const Args &a, uint32_t row, uint32_t &world, uint32_t &seat) const
+    {
+        if (!has(row)) return false;
+        locate(a, row, world, seat);
+        return true;
+    }
+};
+
+}  // namespace mrl

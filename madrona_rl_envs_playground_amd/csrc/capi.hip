@@ -10,6 +10,7 @@
 #include "cnn_bank.hpp"
 #include "cnn_update.hpp"
 #include "mlpbase_policy.hpp"
+#include "mlpbase_bank.hpp"
 #include "mlpbase_update.hpp"
 
 #include <algorithm>
@@ -1313,8 +1314,38 @@ int mrl_rollout_cnn(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy
 
 uint64_t mrl_cnn_bank_workspace_bytes(uint32_t num_worlds, uint32_t num_players, uint32_t num_policies)
 {
-    if (num_policies == 0 || num_policies > mrl::kCnnBankMaxPolicies) return 0;
-    return mrl::cnn_bank_layout(num_worlds, num_players, num_policies).words * sizeof(uint32_t);
+    if (num_policies == 0 || num_policies > mrl::kBankMaxPolicies) return 0;
+    return mrl::bank_layout(num_worlds, num_players, num_policies).words * sizeof(uint32_t);
+}
+
+// What the bank acts of both networks refuse alike behind their own network's checks: the bank's size and stride (`num_params`: the
+// floats of one policy), the ids and the plan's workspace, for the simulator of `a`.
+static int bank_refusal(const char *what, const mrl::ActArgs &a, uint32_t num_policies, uint64_t stride, uint64_t num_params,
+                        const int32_t *ids_dev, void *workspace_dev, uint64_t workspace_bytes)
+{
+    if (num_policies == 0 || num_policies > mrl::kBankMaxPolicies) {
+        mrl::set_error("%s: a bank holds 1 to %u policies, not %u", what, mrl::kBankMaxPolicies, num_policies);
+        return MRL_ERR_INVALID;
+    }
+    if (stride < num_params) {
+        mrl::set_error("%s: the bank's stride of %llu floats is below the policy's %llu parameters", what, (unsigned long long)stride,
+                       (unsigned long long)num_params);
+        return MRL_ERR_INVALID;
+    }
+    if (!ids_dev || (reinterpret_cast<uintptr_t>(ids_dev) & 3u)) {
+        mrl::set_error("%s: ids is null or off a 4-byte boundary", what);
+        return MRL_ERR_INVALID;
+    }
+    if ((uint64_t)a.num_worlds * a.P > 0x7fffffffull) {
+        mrl::set_error("%s: %u worlds of %u seats are more cells than the plan numbers", what, a.num_worlds, a.P);
+        return MRL_ERR_INVALID;
+    }
+    if (!workspace_dev || (reinterpret_cast<uintptr_t>(workspace_dev) & 15u) ||
+        workspace_bytes < mrl_cnn_bank_workspace_bytes(a.num_worlds, a.P, num_policies)) {
+        mrl::set_error("%s: the workspace is null, off a 16-byte boundary or smaller than mrl_cnn_bank_workspace_bytes", what);
+        return MRL_ERR_INVALID;
+    }
+    return MRL_OK;
 }
 
 // Everything mrl_cnn_act_bank and mrl_rollout_cnn_bank check alike (cnn_prepare's checks and the bank's own); fills `args` but
@@ -1329,29 +1360,8 @@ static int cnn_bank_prepare(mrl_sim *sim, uint32_t players, const mrl_cnn_bank *
     const mrl_cnn_policy row0{bank->params_dev, bank->hidden, bank->flags};
     if (int rc = cnn_prepare(sim, players, &row0, record, hip_stream, what, &args->act)) return rc;
     const mrl::CnnActArgs &a = args->act;
-    if (bank->num_policies == 0 || bank->num_policies > mrl::kCnnBankMaxPolicies) {
-        mrl::set_error("%s: a bank holds 1 to %u policies, not %u", what, mrl::kCnnBankMaxPolicies, bank->num_policies);
-        return MRL_ERR_INVALID;
-    }
     const uint64_t num_params = mrl_cnn_policy_num_params(a.W, a.H, a.F, mrl::kCnnHidden, mrl::kCnnActions);
-    if (bank->stride < num_params) {
-        mrl::set_error("%s: the bank's stride of %llu floats is below the policy's %llu parameters", what, (unsigned long long)bank->stride,
-                       (unsigned long long)num_params);
-        return MRL_ERR_INVALID;
-    }
-    if (!ids_dev || (reinterpret_cast<uintptr_t>(ids_dev) & 3u)) {
-        mrl::set_error("%s: ids is null or off a 4-byte boundary", what);
-        return MRL_ERR_INVALID;
-    }
-    if ((uint64_t)a.num_worlds * a.P > 0x7fffffffull) {
-        mrl::set_error("%s: %u worlds of %u seats are more cells than the plan numbers", what, a.num_worlds, a.P);
-        return MRL_ERR_INVALID;
-    }
-    if (!workspace_dev || (reinterpret_cast<uintptr_t>(workspace_dev) & 15u) ||
-        workspace_bytes < mrl_cnn_bank_workspace_bytes(a.num_worlds, a.P, bank->num_policies)) {
-        mrl::set_error("%s: the workspace is null, off a 16-byte boundary or smaller than mrl_cnn_bank_workspace_bytes", what);
-        return MRL_ERR_INVALID;
-    }
+    if (int rc = bank_refusal(what, a, bank->num_policies, bank->stride, num_params, ids_dev, workspace_dev, workspace_bytes)) return rc;
     args->ids = ids_dev, args->ids_row = nullptr;
     args->workspace = static_cast<uint32_t *>(workspace_dev);
     args->stride = bank->stride, args->num_policies = bank->num_policies;
@@ -1378,26 +1388,22 @@ int mrl_cnn_act_bank(mrl_sim *sim, uint32_t players, const mrl_cnn_bank *bank, c
     });
 }
 
-// what mrl_cnn_bank_resample and mrl_rollout_cnn_bank check of a resample; fills `args` but for ids and episodes
-static int cnn_resample_prepare(mrl_sim *sim, uint32_t players, const mrl_cnn_resample *resample, const char *what, mrl::CnnResampleArgs *args)
+// the descriptor of a resample, whichever network's bank it serves
+static int resample_desc_refusal(const mrl_cnn_resample *resample, const char *what)
 {
-    if (int rc = mrl::need_healthy(sim)) return rc;
-    if (sim->game != MRL_GAME_OVERCOOKED && sim->game != MRL_GAME_SIMPLECOOKED) {
-        mrl::set_error("%s: game %d has no CNN policy (Overcooked and Simplecooked do)", what, sim->game);
-        return MRL_ERR_INVALID;
-    }
     if (!resample || !resample->first_id || !resample->num_ids ||
         (resample->mode != MRL_CNN_RESAMPLE_ROBIN && resample->mode != MRL_CNN_RESAMPLE_RANDOM)) {
         mrl::set_error("%s: null resample, first_id or num_ids, or a mode other than MRL_CNN_RESAMPLE_ROBIN and MRL_CNN_RESAMPLE_RANDOM", what);
         return MRL_ERR_INVALID;
     }
-    mrl_tensor_desc obs{}, done{};
-    int rc = mrl::guarded([&] {
-        if (!sim->tensor(MRL_OVERCOOKED_OBS_WORLD_MAJOR, &obs) || !sim->tensor(MRL_OVERCOOKED_DONE, &done))
-            throw std::runtime_error("the simulator does not export OBS_WORLD_MAJOR / DONE");
-    });
-    if (rc) return rc;
-    const uint32_t P = (uint32_t)obs.shape[1];
+    return MRL_OK;
+}
+
+// the seat mask and the seats' ranges of a resample on a simulator of P seats whose DONE is `done`; fills `args` but for ids and
+// episodes
+static int resample_fill(mrl_sim *sim, uint32_t players, uint32_t P, const mrl_tensor_desc &done, const mrl_cnn_resample *resample,
+                         const char *what, mrl::CnnResampleArgs *args)
+{
     if (players == 0 || P > 32 || (P < 32 && (players >> P) != 0)) {
         mrl::set_error("%s: players = 0x%x must name at least one seat and none beyond the simulator's %u", what, players, P);
         return MRL_ERR_INVALID;
@@ -1407,7 +1413,7 @@ static int cnn_resample_prepare(mrl_sim *sim, uint32_t players, const mrl_cnn_re
     for (uint32_t p = 0; p < P; p++) {
         if (!((players >> p) & 1u)) continue;
         const uint32_t first = resample->first_id[p], num = resample->num_ids[p];
-        if (num == 0 || first > mrl::kCnnBankMaxPolicies || num > mrl::kCnnBankMaxPolicies || first + num > mrl::kCnnBankMaxPolicies) {
+        if (num == 0 || first > mrl::kBankMaxPolicies || num > mrl::kBankMaxPolicies || first + num > mrl::kBankMaxPolicies) {
             mrl::set_error("%s: seat %u draws from [%u, %u + %u): a range is 1 to 256 ids and ends at 256 at the latest", what, p, first, first, num);
             return MRL_ERR_INVALID;
         }
@@ -1417,6 +1423,24 @@ static int cnn_resample_prepare(mrl_sim *sim, uint32_t players, const mrl_cnn_re
     a.seed = resample->seed;
     a.num_worlds = sim->num_worlds, a.P = P, a.players = players, a.mode = resample->mode;
     return MRL_OK;
+}
+
+// what mrl_cnn_bank_resample and mrl_rollout_cnn_bank check of a resample; fills `args` but for ids and episodes
+static int cnn_resample_prepare(mrl_sim *sim, uint32_t players, const mrl_cnn_resample *resample, const char *what, mrl::CnnResampleArgs *args)
+{
+    if (int rc = mrl::need_healthy(sim)) return rc;
+    if (sim->game != MRL_GAME_OVERCOOKED && sim->game != MRL_GAME_SIMPLECOOKED) {
+        mrl::set_error("%s: game %d has no CNN policy (Overcooked and Simplecooked do)", what, sim->game);
+        return MRL_ERR_INVALID;
+    }
+    if (int rc = resample_desc_refusal(resample, what)) return rc;
+    mrl_tensor_desc obs{}, done{};
+    int rc = mrl::guarded([&] {
+        if (!sim->tensor(MRL_OVERCOOKED_OBS_WORLD_MAJOR, &obs) || !sim->tensor(MRL_OVERCOOKED_DONE, &done))
+            throw std::runtime_error("the simulator does not export OBS_WORLD_MAJOR / DONE");
+    });
+    if (rc) return rc;
+    return resample_fill(sim, players, (uint32_t)obs.shape[1], done, resample, what, args);
 }
 
 int mrl_cnn_bank_resample(mrl_sim *sim, uint32_t players, const mrl_cnn_resample *resample, int32_t *ids_dev, int32_t *episodes_dev,
@@ -1571,6 +1595,134 @@ int mrl_rollout_mlpbase(mrl_sim *sim, uint32_t players, const mrl_mlpbase_policy
             if (closing) break;
             sim->step(nullptr, stream);
             mrl::completed_step(sim, stream);
+        }
+    });
+}
+
+// Everything mrl_mlpbase_act_bank and mrl_rollout_mlpbase_bank check alike (mlpbase_prepare's checks and the bank's own); fills
+// `args` but for the rows, the ids row, the seed, the step and the flags.
+static int mlpbase_bank_prepare(mrl_sim *sim, uint32_t players, const mrl_mlpbase_bank *bank, const int32_t *ids_dev,
+                                const mrl_mlpbase_record *record, void *workspace_dev, uint64_t workspace_bytes, void *hip_stream,
+                                const char *what, mrl::MlpBaseBankArgs *args)
+{
+    if (!bank) {
+        mrl::set_error("%s: null bank", what);
+        return MRL_ERR_INVALID;
+    }
+    const mrl_mlpbase_policy row0{bank->params_dev, bank->hidden, bank->layer_N, bank->flags};
+    if (int rc = mlpbase_prepare(sim, players, &row0, record, hip_stream, what, &args->act)) return rc;
+    const mrl::MlpBaseActArgs &a = args->act;
+    const uint64_t num_params = mrl_mlpbase_policy_num_params(mrl::kMlpBaseObs, mrl::kMlpBaseHidden, bank->layer_N, mrl::kMlpBaseActions);
+    if (int rc = bank_refusal(what, a, bank->num_policies, bank->stride, num_params, ids_dev, workspace_dev, workspace_bytes)) return rc;
+    args->ids = ids_dev, args->ids_row = nullptr;
+    args->workspace = static_cast<uint32_t *>(workspace_dev);
+    args->stride = bank->stride, args->num_policies = bank->num_policies;
+    return MRL_OK;
+}
+
+uint64_t mrl_mlpbase_bank_workspace_bytes(uint32_t num_worlds, uint32_t num_policies)
+{
+    return mrl_cnn_bank_workspace_bytes(num_worlds, 2, num_policies);  // the balance beam seats two
+}
+
+int mrl_mlpbase_act_bank(mrl_sim *sim, uint32_t players, const mrl_mlpbase_bank *bank, const int32_t *ids_dev,
+                         const mrl_mlpbase_record *record, int32_t *ids_row, uint32_t row, uint64_t seed, uint32_t step, uint32_t flags,
+                         void *workspace_dev, uint64_t workspace_bytes, void *hip_stream)
+{
+    mrl::MlpBaseBankArgs args{};
+    if (int rc = mlpbase_bank_prepare(sim, players, bank, ids_dev, record, workspace_dev, workspace_bytes, hip_stream, "mrl_mlpbase_act_bank",
+                                      &args))
+        return rc;
+    if (int rc = act_row_refusal("mrl_mlpbase_act_bank", "MRL_MLPBASE_VALUE_ONLY", flags, bank->flags, record, row)) return rc;
+    if (reinterpret_cast<uintptr_t>(ids_row) & 3u) {
+        mrl::set_error("mrl_mlpbase_act_bank: ids_row is off a 4-byte boundary");
+        return MRL_ERR_INVALID;
+    }
+    const bool value_only = flags & MRL_MLPBASE_VALUE_ONLY;
+    mrl::DeviceGuard on(sim->device);
+    return mrl::guarded([&] {
+        mlpbase_rows(args.act, record, row, value_only);
+        args.act.seed = seed, args.act.step = step, args.act.flags = flags;
+        args.ids_row = ids_row;
+        mrl::launch_mlpbase_act_bank(args, (hipStream_t)hip_stream);
+    });
+}
+
+// what mrl_mlpbase_bank_resample and mrl_rollout_mlpbase_bank check of a resample; fills `args` but for ids and episodes
+static int mlpbase_resample_prepare(mrl_sim *sim, uint32_t players, const mrl_cnn_resample *resample, const char *what,
+                                    mrl::CnnResampleArgs *args)
+{
+    if (int rc = mrl::need_healthy(sim)) return rc;
+    if (sim->game != MRL_GAME_BALANCE) {
+        mrl::set_error("%s: game %d has no MLPBase policy (the balance beam does)", what, sim->game);
+        return MRL_ERR_INVALID;
+    }
+    if (int rc = resample_desc_refusal(resample, what)) return rc;
+    mrl_tensor_desc obs{}, done{};
+    int rc = mrl::guarded([&] {
+        if (!sim->tensor(MRL_BALANCE_OBSERVATION, &obs) || !sim->tensor(MRL_BALANCE_DONE, &done))
+            throw std::runtime_error("the simulator does not export OBSERVATION / DONE");
+    });
+    if (rc) return rc;
+    return resample_fill(sim, players, (uint32_t)obs.shape[0], done, resample, what, args);
+}
+
+int mrl_mlpbase_bank_resample(mrl_sim *sim, uint32_t players, const mrl_cnn_resample *resample, int32_t *ids_dev, int32_t *episodes_dev,
+                              void *hip_stream)
+{
+    mrl::CnnResampleArgs args{};
+    if (int rc = mlpbase_resample_prepare(sim, players, resample, "mrl_mlpbase_bank_resample", &args)) return rc;
+    if (!ids_dev || !episodes_dev || ((reinterpret_cast<uintptr_t>(ids_dev) | reinterpret_cast<uintptr_t>(episodes_dev)) & 3u)) {
+        mrl::set_error("mrl_mlpbase_bank_resample: ids or episodes is null or off a 4-byte boundary");
+        return MRL_ERR_INVALID;
+    }
+    args.ids = ids_dev, args.episodes = episodes_dev;
+    mrl::DeviceGuard on(sim->device);
+    return mrl::guarded([&] { mrl::launch_cnn_bank_resample(args, (hipStream_t)hip_stream); });
+}
+
+int mrl_rollout_mlpbase_bank(mrl_sim *sim, uint32_t players, const mrl_mlpbase_bank *bank, int32_t *ids_dev, int32_t *episodes_dev,
+                             const mrl_cnn_resample *resample, const mrl_mlpbase_record *record, int32_t *ids_record, uint64_t seed,
+                             uint32_t first_step, void *workspace_dev, uint64_t workspace_bytes, void *hip_stream)
+{
+    mrl::MlpBaseBankArgs args{};
+    if (int rc = mlpbase_bank_prepare(sim, players, bank, ids_dev, record, workspace_dev, workspace_bytes, hip_stream,
+                                      "mrl_rollout_mlpbase_bank", &args))
+        return rc;
+    if (!record) {
+        mrl::set_error("mrl_rollout_mlpbase_bank: null record");
+        return MRL_ERR_INVALID;
+    }
+    if (reinterpret_cast<uintptr_t>(ids_record) & 3u) {
+        mrl::set_error("mrl_rollout_mlpbase_bank: ids_record is off a 4-byte boundary");
+        return MRL_ERR_INVALID;
+    }
+    mrl::CnnResampleArgs again{};
+    if (resample) {
+        if (int rc = mlpbase_resample_prepare(sim, players, resample, "mrl_rollout_mlpbase_bank", &again)) return rc;
+        if (!episodes_dev || (reinterpret_cast<uintptr_t>(episodes_dev) & 3u)) {
+            mrl::set_error("mrl_rollout_mlpbase_bank: a resample needs episodes, on a 4-byte boundary");
+            return MRL_ERR_INVALID;
+        }
+        again.ids = ids_dev, again.episodes = episodes_dev;
+    }
+    mrl::DeviceGuard on(sim->device);
+    return mrl::guarded([&] {
+        hipStream_t stream = (hipStream_t)hip_stream;
+        const uint32_t T = record->num_steps;
+        const size_t cells = (size_t)args.act.num_worlds * args.act.P;
+        args.act.seed = seed;
+        for (uint32_t k = 0; k <= T; k++) {
+            const bool closing = k == T;
+            mlpbase_rows(args.act, record, k, closing);
+            args.act.step = first_step + k;
+            args.act.flags = bank->flags | (closing ? (uint32_t)MRL_MLPBASE_VALUE_ONLY : 0u);
+            args.ids_row = ids_record ? ids_record + (size_t)k * cells : nullptr;
+            mrl::launch_mlpbase_act_bank(args, stream);
+            if (closing) break;
+            sim->step(nullptr, stream);
+            mrl::completed_step(sim, stream);
+            if (resample) mrl::launch_cnn_bank_resample(again, stream);
         }
     });
 }

@@ -12,43 +12,23 @@
 //                 act) copies the observation rows into the record.
 // The balance beam's ACTION_MASK is all ones in every state (src/balance_beam_env/sim.cpp:197); the kernel does not read it.
 // No float atomics, no workgroup waits on another, no scratch: the same inputs give the same bits on every run.
-#include "mlpbase_policy.hpp"
-#include "mlpbase_forward.hpp"
+#include "mlpbase_act_body.hpp"
 
 namespace mrl {
 
-extern __shared__ __attribute__((aligned(16))) unsigned char mlpbase_lds_image[];
+// tile t of the call holds samples 32 t .. 32 t + 31 (mlpbase_act_body's map)
+struct MlpBasePlainMap {
+    uint32_t tile0, total;
+    __device__ __forceinline__ bool has(uint32_t row) const { return tile0 + row < total; }
+    __device__ __forceinline__ void locate(const MlpBaseActArgs &a, uint32_t row, uint32_t &world, uint32_t &seat) const
+    {
+        seat_sample(a.players, a.num_seats, tile0 + row, world, seat);
+    }
+};
 
 __global__ void __launch_bounds__(kMlpBaseThreads) mrl_mlpbase_act(MlpBaseActArgs a)
 {
-    const uint32_t net = act_net(a);
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t total = a.num_worlds * a.num_seats, tile0 = blockIdx.x * kMlpBaseTile;
-    const uint32_t out_dim = net ? 1u : kMlpBaseActions;
-    const float *__restrict__ params = a.params + (net ? mlpbase_net_params(a.layer_N, kMlpBaseActions) : 0u);
-    float *lds = reinterpret_cast<float *>(mlpbase_lds_image);
-
-    {
-        // the tile's observation rows: thread (row, k), k < 8; column 7 is never read as an input
-        const bool copies = a.obs_row && net == (a.nets == 2u ? 1u : 0u);
-        const uint32_t rr = tid >> 3, k = tid & 7u, s = tile0 + rr;
-        float v = 0.0f;
-        if (s < total && k < kMlpBaseObs) {
-            uint32_t world, seat;
-            seat_sample(a.players, a.num_seats, s, world, seat);
-            const int32_t word = a.obs[((size_t)seat * a.num_worlds + world) * kMlpBaseObs + k];
-            v = (float)word;
-            if (copies) a.obs_row[((size_t)world * a.P + seat) * kMlpBaseObs + k] = word;
-        }
-        lds[kMlpXhat0At + rr * kMlpLd0 + k] = v;
-    }
-    __syncthreads();
-    mlpbase_forward(params, a.layer_N, out_dim, lds, wave, lane);
-
-    if (tid >= kMlpBaseTile || tile0 + tid >= total) return;
-    uint32_t world, seat;
-    seat_sample(a.players, a.num_seats, tile0 + tid, world, seat);
-    act_tail<(int)kMlpBaseActions>(a, lds + kMlpOutAt, net, tid, world, seat, a.reward);
+    mlpbase_act_body(a, MlpBasePlainMap{blockIdx.x * kMlpBaseTile, a.num_worlds * a.num_seats}, a.params);
 }
 
 void launch_mlpbase_act(const MlpBaseActArgs &args, hipStream_t stream)

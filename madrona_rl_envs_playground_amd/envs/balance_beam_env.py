@@ -15,7 +15,8 @@ SCALE = 0.2
 
 
 class BalanceMadronaTorch(ActsWithMlpBasePolicy, MadronaEnv):
-    """``act`` and ``rollout`` (extensions, ``simulators.ActsWithMlpBasePolicy``): MAPPO's MLP actor-critic on the device."""
+    """``act``, ``rollout``, ``act_bank`` and ``rollout_bank`` (extensions, ``simulators.ActsWithMlpBasePolicy``): MAPPO's MLP
+    actor-critic on the device, under one policy or under a bank's member per (world, seat)."""
 
     def __init__(self, num_envs, gpu_id, debug_compile=True, use_cpu=False, use_env_cpu=False, record_episode_statistics=False):
         sim = BalanceBeamSimulator(exec_mode=ExecMode.CPU if use_cpu else ExecMode.CUDA, gpu_id=gpu_id,

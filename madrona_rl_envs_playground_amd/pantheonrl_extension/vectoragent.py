@@ -55,6 +55,51 @@ class _DevicePolicyAgent(VectorAgent):
         return None
 
 
+class _PopulationSeat:
+    """What the population agents of the two networks share, mixed in FRONT of their single-policy agent: the members, the
+    resample, ``ids`` and ``episodes`` on the device, ``get_action`` as the bank act and ``update`` as the resample.  A subclass
+    names its bank class (``_bank_class``, of ``simulators``) and entry point (``_entry``, for messages), and has ``_num_seats()``
+    and ``_bank_calls()`` -> (the bank act, the resample)."""
+
+    def __init__(self, envs, bank, members=None, resample="robin", seed=0, greedy=False):
+        from .. import simulators
+        if not isinstance(bank, getattr(simulators, self._bank_class)):
+            raise TypeError(f"{type(self).__name__} acts through {self._entry}: bank must be a simulators.{self._bank_class}")
+        super().__init__(envs, None, seed=seed, greedy=greedy)
+        self.bank = bank
+        self.members = list(range(bank.num_policies)) if members is None else [int(k) for k in members]
+        if not self.members or any(not 0 <= k < bank.num_policies for k in self.members):
+            raise ValueError(f"members must name rows 0..{bank.num_policies - 1} of the bank")
+        if resample is not None and resample not in simulators.CNN_RESAMPLE_MODES:
+            raise ValueError(f"resample must be one of {sorted(simulators.CNN_RESAMPLE_MODES)} or None, got {resample!r}")
+        if resample is not None and self.members != list(range(self.members[0], self.members[0] + len(self.members))):
+            raise ValueError("with a resample, members must be consecutive rows of the bank: the device draws from a range")
+        self.resample = resample
+        self.ids = self.episodes = None
+        self._resample = None
+
+    def _attach(self):
+        from ..simulators import CnnResample
+        envs, device = self.envs, self.envs.static_actions.device
+        n, p = envs.num_envs, self._num_seats()
+        self.ids = torch.full((n, p), -1, dtype=torch.int32, device=device)
+        self.ids[:, self.seat] = torch.tensor(self.members, dtype=torch.int32, device=device)[torch.arange(n, device=device) % len(self.members)]
+        self.episodes = torch.zeros(n, dtype=torch.int32, device=device)
+        if self.resample is not None:
+            self._resample = CnnResample(self.resample, self.members[0], len(self.members), p, self.seed)
+
+    def _act(self, mask):
+        if self.ids is None:
+            self._attach()
+        self._bank_calls()[0](self._sim, self.bank, self.ids, mask, seed=self.seed, step=self._draws, greedy=self.greedy)
+
+    def update(self, rewards, dones):
+        if self.ids is None:
+            self._attach()
+        if self._resample is not None:
+            self._bank_calls()[1](self._sim, self.ids, self.episodes, self._resample, None, None, players=1 << self.seat)
+
+
 class CnnPolicyAgent(_DevicePolicyAgent):
     """A player of either kitchen env (``envs.overcooked_env.OvercookedMadrona`` or the Simplecooked one of
     ``envs.overcooked2_env``) that acts under MAPPO's CNN policy on the device: ``get_action`` is ``mrl_cnn_act`` for this
@@ -84,7 +129,7 @@ class CnnPolicyAgent(_DevicePolicyAgent):
         cnn_act(self._sim, self.policy, mask, seed=self.seed, step=self._draws, greedy=self.greedy)
 
 
-class CnnPopulationAgent(CnnPolicyAgent):
+class CnnPopulationAgent(_PopulationSeat, CnnPolicyAgent):
     """A partner seat of either kitchen env played by a POPULATION: every world has its own member of ``bank`` (a
     ``simulators.CnnPolicyBank``) and draws a new one when its episode ends -- the per-episode partner sampling that
     ``add_partner_agent``'s docstring describes, per world instead of for the whole batch.  World n starts with
@@ -95,45 +140,14 @@ class CnnPopulationAgent(CnnPolicyAgent):
     ``ids`` (N, P) int32 -- -1 in every other seat's column -- and ``episodes`` (N) int32 live on the device and exist from the
     first call on.  ``CnnPolicyAgent``'s refusals, and no torch fallback."""
 
-    def __init__(self, envs, bank, members=None, resample="robin", seed=0, greedy=False):
-        from ..simulators import CNN_RESAMPLE_MODES, CnnPolicyBank
-        if not isinstance(bank, CnnPolicyBank):
-            raise TypeError("CnnPopulationAgent acts through mrl_cnn_act_bank: bank must be a simulators.CnnPolicyBank")
-        super().__init__(envs, None, seed=seed, greedy=greedy)
-        self.bank = bank
-        self.members = list(range(bank.num_policies)) if members is None else [int(k) for k in members]
-        if not self.members or any(not 0 <= k < bank.num_policies for k in self.members):
-            raise ValueError(f"members must name rows 0..{bank.num_policies - 1} of the bank")
-        if resample is not None and resample not in CNN_RESAMPLE_MODES:
-            raise ValueError(f"resample must be one of {sorted(CNN_RESAMPLE_MODES)} or None, got {resample!r}")
-        if resample is not None and self.members != list(range(self.members[0], self.members[0] + len(self.members))):
-            raise ValueError("with a resample, members must be consecutive rows of the bank: the device draws from a range")
-        self.resample = resample
-        self.ids = self.episodes = None
-        self._resample = None
+    _bank_class, _entry = "CnnPolicyBank", "mrl_cnn_act_bank"
 
-    def _attach(self):
-        from ..simulators import CnnResample
-        envs, device = self.envs, self.envs.static_actions.device
-        n, p = envs.num_envs, envs.num_players
-        self.ids = torch.full((n, p), -1, dtype=torch.int32, device=device)
-        self.ids[:, self.seat] = torch.tensor(self.members, dtype=torch.int32, device=device)[torch.arange(n, device=device) % len(self.members)]
-        self.episodes = torch.zeros(n, dtype=torch.int32, device=device)
-        if self.resample is not None:
-            self._resample = CnnResample(self.resample, self.members[0], len(self.members), p, self.seed)
+    def _num_seats(self):
+        return self.envs.num_players
 
-    def _act(self, mask):
-        from ..simulators import cnn_act_bank
-        if self.ids is None:
-            self._attach()
-        cnn_act_bank(self._sim, self.bank, self.ids, mask, seed=self.seed, step=self._draws, greedy=self.greedy)
-
-    def update(self, rewards, dones):
-        from ..simulators import cnn_resample
-        if self.ids is None:
-            self._attach()
-        if self._resample is not None:
-            cnn_resample(self._sim, self.ids, self.episodes, self._resample, None, None, players=1 << self.seat)
+    def _bank_calls(self):
+        from ..simulators import cnn_act_bank, cnn_resample
+        return cnn_act_bank, cnn_resample
 
 
 class MlpBasePolicyAgent(_DevicePolicyAgent):
@@ -150,15 +164,36 @@ class MlpBasePolicyAgent(_DevicePolicyAgent):
         envs = self.envs
         sim = getattr(envs, "sim", None)
         if not isinstance(envs, BalanceMadronaTorch) or not isinstance(sim, BalanceBeamSimulator):
-            raise TypeError("MlpBasePolicyAgent acts through mrl_mlpbase_act: envs must be a BalanceMadronaTorch, got "
+            raise TypeError(f"{type(self).__name__} acts through mrl_mlpbase_act: envs must be a BalanceMadronaTorch, got "
                             f"{type(envs).__name__} over {type(sim).__name__}; there is no torch fallback")
         if envs.device.type != "cuda":
-            raise TypeError(f"MlpBasePolicyAgent needs the env on the simulator's GPU (cuda:{sim.gpu_id}); got env device {envs.device}")
+            raise TypeError(f"{type(self).__name__} needs the env on the simulator's GPU (cuda:{sim.gpu_id}); got env device {envs.device}")
         return sim
 
     def _act(self, mask):
         from ..simulators import mlpbase_act
         mlpbase_act(self._sim, self.policy, mask, seed=self.seed, step=self._draws, greedy=self.greedy)
+
+
+class MlpBasePopulationAgent(_PopulationSeat, MlpBasePolicyAgent):
+    """A partner seat of ``envs.balance_beam_env.BalanceMadronaTorch`` played by a POPULATION, the counterpart of
+    ``CnnPopulationAgent``: every world has its own member of ``bank`` (a ``simulators.MlpBasePolicyBank``) and draws a new one
+    when its episode ends.  World n starts with ``members[n % len(members)]`` (``members``: rows of the bank, default all);
+    ``get_action`` is ``mlpbase_act_bank`` for this agent's seat; ``update(rewards, dones)`` is ``mlpbase_resample``: where the
+    simulator's DONE is set the world's count in ``episodes`` goes up and its member is replaced, ``resample`` "robin" the next of
+    ``members``, "random" one of them by ``random_hash(seed, episode, world, seat)``, ``None`` never (with a resample ``members``
+    must be ``range(first, first + num)``, the range the device call draws from).  ``ids`` (N, P) int32 -- -1 in the other seat's
+    column -- and ``episodes`` (N) int32 live on the device and exist from the first call on.  ``MlpBasePolicyAgent``'s refusals:
+    any other env gets a ``TypeError``, and there is no torch fallback."""
+
+    _bank_class, _entry = "MlpBasePolicyBank", "mrl_mlpbase_act_bank"
+
+    def _num_seats(self):
+        return self.envs.n_players
+
+    def _bank_calls(self):
+        from ..simulators import mlpbase_act_bank, mlpbase_resample
+        return mlpbase_act_bank, mlpbase_resample
 
 
 class CleanPPOAgent(VectorAgent):

@@ -669,13 +669,24 @@ def cnn_resample(sim, ids, episodes, mode, first_id, num_ids, players=None, seed
 CrossPlayResult = collections.namedtuple("CrossPlayResult", "mean_return episodes")  # each (Ka, Kb), on the device
 
 
-def cross_play(env, bank, members_a=None, members_b=None, greedy=True, seed=0):
+def cross_play(env, bank, members_a=None, members_b=None, greedy=True, seed=0, steps=None):
     """The cross-play matrix of ``bank``'s members on one batch of worlds: world n plays pair n mod (Ka Kb), seat 0 under
     ``members_a[pair // Kb]`` and seat 1 under ``members_b[pair % Kb]`` (default every row of the bank).  All worlds are restarted, one
     horizon of (``cnn_act_bank``, step) follows, no host wait inside, and the last-episode return
     of ``enable_episode_stats`` (the team's, as seat 0 received it) is averaged per pair.  ``env``: a two-player kitchen env
     wrapper on the GPU.  Returns ``CrossPlayResult(mean_return, episodes)``, float64 and int64 (Ka, Kb) on the device;
-    ``episodes`` is the number of worlds that played the pair."""
+    ``episodes`` is the number of worlds that played the pair.
+
+    With an ``MlpBasePolicyBank`` ``env`` is a ``BalanceMadronaTorch`` on the GPU and ``steps`` (default 12, four times the beam's TIME of
+    three: six episodes where nobody leaves the line) times (``mlpbase_act_bank``, step) follow the restart.  The beam's episodes have no fixed length, so every episode a
+    world finishes within ``steps`` counts: behind each step the last-episode return of the worlds whose DONE is set is added to
+    per-world float64 sums and counts (elementwise, no host wait), which are reduced per pair at the end -- the returns are
+    float32, so the sums are exact whatever the order.  ``episodes`` is then the number of finished episodes per pair.  ``steps``
+    is the beam's alone: the kitchens play one horizon."""
+    if isinstance(bank, MlpBasePolicyBank):
+        return _cross_play_beam(env, bank, members_a, members_b, greedy, seed, steps)
+    if steps is not None:
+        raise ValueError("steps is the balance beam's: a kitchen's cross-play lasts one horizon")
     sim = env.sim
     n, p = tuple(sim.observation_world_major_tensor().shape[:2])
     if p != 2:
@@ -866,6 +877,166 @@ def mlpbase_act(sim, policy, players=None, record=None, row=0, seed=0, step=0, g
                                 int(row), int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF, flags, _stream_ptr(sim.gpu_id))
     if rc:
         _lib.check(rc)
+
+
+class MlpBasePolicyBank:
+    """K ``MlpBasePolicy`` of one shape in one dense float32 tensor ``params`` (K, num_params) (``mrl_mlpbase_bank``), the
+    counterpart of ``CnnPolicyBank`` for the balance beam: row k is exactly what an ``MlpBasePolicy``'s ``params`` is.
+    ``policy(k)`` is an ``MlpBasePolicy`` whose ``params`` IS row k, a contiguous view, so ``mlpbase_act``, ``MappoOptimizer``,
+    ``mappo_update`` and ``.module()`` work on a member unchanged and training a member is what the next ``mlpbase_act_bank``
+    reads.  1 <= K <= 256; one ``layer_N`` for the whole bank."""
+
+    def __init__(self, num_policies, layer_N=2, obs_dim=_lib.MLPBASE_OBS, num_actions=_lib.MLPBASE_ACTIONS, hidden=_lib.MLPBASE_HIDDEN,
+                 device="cuda:0"):
+        self.obs_dim, self.num_actions, self.hidden, self.layer_N = int(obs_dim), int(num_actions), int(hidden), int(layer_N)
+        self.num_policies = int(num_policies)
+        if not 1 <= self.num_policies <= _lib.CNN_BANK_MAX_POLICIES:
+            raise ValueError(f"a bank holds 1 to {_lib.CNN_BANK_MAX_POLICIES} policies, not {num_policies}")
+        self.num_params = int(_lib.lib().mrl_mlpbase_policy_num_params(self.obs_dim, self.hidden, self.layer_N, self.num_actions))
+        if self.num_params == 0:
+            raise ValueError(f"mrl_mlpbase_act runs obs_dim = {_lib.MLPBASE_OBS}, num_actions = {_lib.MLPBASE_ACTIONS}, hidden = "
+                             f"{_lib.MLPBASE_HIDDEN} and layer_N 1 or 2; got {self.obs_dim}, {self.num_actions}, {self.hidden}, {self.layer_N}")
+        self.params = torch.zeros((self.num_policies, self.num_params), dtype=torch.float32, device=torch.device(device))
+        self._members = {}
+
+    def __len__(self):
+        return self.num_policies
+
+    def policy(self, k):
+        """The ``MlpBasePolicy`` whose ``params`` is row ``k`` of the bank (one object per row)."""
+        k = int(k)
+        if not 0 <= k < self.num_policies:
+            raise IndexError(f"the bank holds policies 0..{self.num_policies - 1}, not {k}")
+        member = self._members.get(k)
+        if member is None:
+            member = MlpBasePolicy.__new__(MlpBasePolicy)
+            member.obs_dim, member.num_actions, member.hidden, member.layer_N = self.obs_dim, self.num_actions, self.hidden, self.layer_N
+            member.params = self.params[k]
+            member._module = None
+            self._members[k] = member
+        return member
+
+    @classmethod
+    def from_policies(cls, policies, device=None):
+        """A bank holding copies of ``policies`` (``MlpBasePolicy`` of one shape), in that order (``device``: default the first one's)."""
+        policies = list(policies)
+        if not policies or not all(isinstance(p, MlpBasePolicy) for p in policies):
+            raise ValueError("from_policies takes a non-empty list of MlpBasePolicy")
+        first = policies[0]
+        shape = (first.obs_dim, first.num_actions, first.hidden, first.layer_N)
+        if any((p.obs_dim, p.num_actions, p.hidden, p.layer_N) != shape for p in policies):
+            raise ValueError("the policies of a bank must have one shape")
+        bank = cls(len(policies), first.layer_N, first.obs_dim, first.num_actions, first.hidden, device if device is not None else first.params.device)
+        with torch.no_grad():
+            for k, p in enumerate(policies):
+                bank.params[k].copy_(p.params)
+        return bank
+
+    def desc(self):
+        return _lib.MlpBaseBankDesc(self.params.data_ptr(), self.num_policies, self.params.stride(0), self.hidden, self.layer_N, 0)
+
+
+def _mlpbase_bank_call_args(sim, bank, ids, players, record):
+    if not isinstance(bank, MlpBasePolicyBank):
+        raise ValueError("bank must be an MlpBasePolicyBank")
+    if not isinstance(sim, BalanceBeamSimulator):
+        raise ValueError("mrl_mlpbase_act_bank runs on a BalanceBeamSimulator")
+    p = bank.params
+    if (not p.is_cuda or p.device.index != sim.gpu_id or p.dtype != torch.float32 or not p.is_contiguous() or
+            tuple(p.shape) != (bank.num_policies, bank.num_params)):
+        raise ValueError(f"bank.params must be a contiguous float32 tensor (num_policies, num_params) on cuda:{sim.gpu_id}")
+    mask = _mlpbase_call_args(sim, bank.policy(0), players, record)
+    seats, worlds = sim.observation_tensor().shape[:2]  # (P, N, 7)
+    _check_ids(sim, ids, (worlds, seats), "ids")
+    return mask
+
+
+def _mlpbase_bank_workspace(sim, bank):
+    size = int(sim._L.mrl_mlpbase_bank_workspace_bytes(sim.num_worlds, bank.num_policies))
+    workspace = getattr(sim, "_mlpbase_bank_workspace", None)
+    if workspace is None or workspace.numel() < size:
+        workspace = sim._mlpbase_bank_workspace = torch.empty(size, dtype=torch.uint8, device=torch.device("cuda", sim.gpu_id))
+    return workspace
+
+
+def mlpbase_act_bank(sim, bank, ids, players=None, record=None, ids_row=None, row=0, seed=0, step=0, greedy=False, value_only=False,
+                     workspace=None):
+    """``mrl_mlpbase_act_bank`` on torch's current stream: seat p of world n of a balance-beam simulator acts under row
+    ``ids[n, p]`` of ``bank`` (an ``MlpBasePolicyBank``) where p is in ``players`` and the id is valid; a cell at -1 keeps its
+    ACTION entry and its record cells, ``record.obs`` included.  The plan (``cnn_act_bank``'s own), then ``mlpbase_act``'s kernel
+    body over its tiles: every output is bit for bit ``mlpbase_act``'s under the cell's policy.  ``ids``: int32 (N, P) on the
+    device; ``ids_row``: int32 (N, P) that receives the ids as this act used them (-1 where it did not act).  The other arguments
+    are ``mlpbase_act``'s.  ``workspace``: default one the simulator keeps (``mrl_mlpbase_bank_workspace_bytes``, which is
+    ``mrl_cnn_bank_workspace_bytes(N, 2, K)``; its words are in include/mrl_envs.h)."""
+    mask = _mlpbase_bank_call_args(sim, bank, ids, players, record)
+    if ids_row is not None:
+        _check_ids(sim, ids_row, ids.shape, "ids_row")
+    if workspace is None:
+        workspace = _mlpbase_bank_workspace(sim, bank)
+    flags = (_lib.POLICY_GREEDY if greedy else 0) | (_lib.MLPBASE_VALUE_ONLY if value_only else 0)
+    desc = bank.desc()
+    rc = sim._L.mrl_mlpbase_act_bank(sim._handle, mask, ctypes.byref(desc), ids.data_ptr(),
+                                     ctypes.byref(record.struct) if record is not None else None,
+                                     ids_row.data_ptr() if ids_row is not None else None, int(row), int(seed) & (2 ** 64 - 1),
+                                     int(step) & 0xFFFFFFFF, flags, workspace.data_ptr(), workspace.numel(), _stream_ptr(sim.gpu_id))
+    if rc:
+        _lib.check(rc)
+
+
+BankResample = CnnResample  # the descriptor serves both networks' banks
+
+
+def mlpbase_resample(sim, ids, episodes, mode, first_id=None, num_ids=None, players=None, seed=0):
+    """``mrl_mlpbase_bank_resample`` on torch's current stream: ``cnn_resample`` on a balance-beam simulator -- the same kernel,
+    draws and arguments (``resample_twin`` is the same in numpy).  ``mode`` may also be a ``CnnResample`` (``BankResample``), which
+    then carries the rest."""
+    if not isinstance(sim, BalanceBeamSimulator):
+        raise ValueError("mrl_mlpbase_bank_resample runs on a BalanceBeamSimulator")
+    seats, worlds = sim.observation_tensor().shape[:2]
+    _check_ids(sim, ids, (worlds, seats), "ids")
+    _check_ids(sim, episodes, (worlds,), "episodes")
+    resample = mode if isinstance(mode, CnnResample) else CnnResample(mode, first_id, num_ids, seats, seed)
+    _lib.check(sim._L.mrl_mlpbase_bank_resample(sim._handle, _seat_mask(players, seats), ctypes.byref(resample.struct), ids.data_ptr(),
+                                                episodes.data_ptr(), _stream_ptr(sim.gpu_id)))
+
+
+BEAM_TIME = 3  # src/balance_beam_env/sim.cpp: an observation holds TIME positions per seat, an episode is at most TIME - 1 moves
+
+
+def _cross_play_beam(env, bank, members_a, members_b, greedy, seed, steps):
+    """``cross_play`` for an ``MlpBasePolicyBank`` on the balance beam"""
+    sim = env.sim
+    if not isinstance(sim, BalanceBeamSimulator):
+        raise ValueError("an MlpBasePolicyBank plays on the balance beam: env.sim must be a BalanceBeamSimulator")
+    p, n = tuple(sim.observation_tensor().shape[:2])
+    a = list(range(bank.num_policies)) if members_a is None else [int(k) for k in members_a]
+    b = list(range(bank.num_policies)) if members_b is None else [int(k) for k in members_b]
+    if not a or not b or any(not 0 <= k < bank.num_policies for k in a + b):
+        raise ValueError(f"members must name rows 0..{bank.num_policies - 1} of the bank")
+    pairs = len(a) * len(b)
+    if n < pairs:
+        raise ValueError(f"{n} worlds cannot play {len(a)} x {len(b)} pairs")
+    steps = 4 * BEAM_TIME if steps is None else int(steps)
+    if steps < 1:
+        raise ValueError("steps must be positive")
+    device = torch.device("cuda", sim.gpu_id)
+    pair = torch.arange(n, device=device) % pairs
+    ids = torch.stack([torch.tensor(a, device=device)[pair // len(b)], torch.tensor(b, device=device)[pair % len(b)]], dim=1).to(torch.int32).contiguous()
+    sim.enable_episode_stats()
+    sim.reset_worlds(None)
+    done = sim.done_tensor().to_torch().reshape(n)
+    last = sim.last_episode_return_tensor().to_torch().reshape(p, n)[0]  # the team's return, as seat 0 received it
+    total = torch.zeros(n, dtype=torch.float64, device=device)
+    finished = torch.zeros(n, dtype=torch.int64, device=device)
+    for t in range(steps):
+        mlpbase_act_bank(sim, bank, ids, seed=seed, step=t, greedy=greedy)
+        sim.step()
+        over = done != 0
+        total += torch.where(over, last.to(torch.float64), torch.zeros_like(total))  # float32 returns: the float64 sums are exact
+        finished += over
+    count = torch.zeros(pairs, dtype=torch.int64, device=device).index_add_(0, pair, finished)
+    summed = torch.zeros(pairs, dtype=torch.float64, device=device).index_add_(0, pair, total)
+    return CrossPlayResult((summed / count).view(len(a), len(b)), count.view(len(a), len(b)))
 
 
 def _wide_mlp(inputs, outputs, hidden=_lib.WIDE_HIDDEN):
@@ -1498,7 +1669,7 @@ class ActsWithCnnPolicy:
 
 class ActsWithMlpBasePolicy:
     """Mixin of the balance-beam env wrapper (``envs/balance_beam_env.py``; ``self.sim``, ``static_actions``, ``num_envs`` and
-    ``n_players`` are the wrapper's): MAPPO's MLP actor-critic on the device."""
+    ``n_players`` are the wrapper's): MAPPO's MLP actor-critic on the device, one policy for the batch or a bank's member per cell."""
 
     def act(self, policy, players=None, record=None, row=0, seed=0, step=0, greedy=False):
         """The seats in ``players`` (default both) act under ``policy`` (a ``simulators.MlpBasePolicy``) on the device, one launch
@@ -1514,6 +1685,31 @@ class ActsWithMlpBasePolicy:
         record = MlpBaseRecord._for_rollout(record, num_steps, self.num_envs, self.n_players, self.static_actions.device)
         self.sim.rollout_mlpbase(policy, record, players=players, seed=seed, first_step=first_step, greedy=greedy)
         return record
+
+    def act_bank(self, bank, ids, players=None, record=None, ids_row=None, row=0, seed=0, step=0, greedy=False):
+        """``act`` with a policy per (world, seat) cell: seat p of world n acts under row ``ids[n, p]`` of ``bank`` (a
+        ``simulators.MlpBasePolicyBank``), cells at -1 keep their actions (``mrl_mlpbase_act_bank``: the plan and the act, every
+        output bit for bit ``act``'s under the cell's policy).  ``ids``: int32 (N, P) on the device.  Returns ``static_actions``."""
+        mlpbase_act_bank(self.sim, bank, ids, players, record, ids_row, row=row, seed=seed, step=step, greedy=greedy)
+        return self.static_actions
+
+    def rollout_bank(self, bank, ids, num_steps, episodes=None, resample=None, seed=0, first_step=0, players=None, record=None,
+                     ids_record=None, greedy=False):
+        """``rollout`` under a bank (``mrl_rollout_mlpbase_bank``) -> (record, ids_record): ``ids_record`` int32 (T + 1, N, P) holds
+        the ids each act used (-1 where it did not act).  ``resample`` (a ``simulators.CnnResample``) runs behind every step: worlds
+        that have just restarted draw their next policies into ``ids`` and count in ``episodes`` (int32 (N), made when ``None`` and
+        then kept by the env as ``bank_episodes``)."""
+        device = self.static_actions.device
+        record = MlpBaseRecord._for_rollout(record, num_steps, self.num_envs, self.n_players, device)
+        if ids_record is None:
+            ids_record = torch.empty((int(num_steps) + 1, self.num_envs, self.n_players), dtype=torch.int32, device=device)
+        if episodes is None and resample is not None:
+            episodes = getattr(self, "bank_episodes", None)
+            if episodes is None:
+                episodes = self.bank_episodes = torch.zeros(self.num_envs, dtype=torch.int32, device=device)
+        self.sim.rollout_mlpbase_bank(bank, ids, record, episodes=episodes, resample=resample, ids_record=ids_record, players=players,
+                                      seed=seed, first_step=first_step, greedy=greedy)
+        return record, ids_record
 
 
 class _Simulator:
@@ -1689,6 +1885,34 @@ class _Simulator:
         desc.flags = _lib.POLICY_GREEDY if greedy else 0
         _lib.check(self._L.mrl_rollout_mlpbase(self._handle, mask, ctypes.byref(desc), ctypes.byref(record.struct),
                                                int(seed) & (2 ** 64 - 1), int(first_step) & 0xFFFFFFFF, _stream_ptr(self.gpu_id)))
+
+    def rollout_mlpbase_bank(self, bank, ids, record, episodes=None, resample=None, ids_record=None, players=None, seed=0, first_step=0,
+                             greedy=False, workspace=None):
+        """``rollout_mlpbase`` with ``mlpbase_act_bank`` in place of ``mlpbase_act`` (``mrl_rollout_mlpbase_bank``): ``ids`` int32
+        (N, P) assigns a row of ``bank`` (an ``MlpBasePolicyBank``) to every cell; with ``resample`` (a ``CnnResample``)
+        ``mlpbase_resample`` runs behind every step on ``ids`` and ``episodes`` (int32 (N)); ``ids_record`` int32 (T + 1, N, P)
+        receives the ids each act used.  No host wait inside; two rollouts of T equal one of 2 T, ``ids`` and ``episodes`` included."""
+        mask = _mlpbase_bank_call_args(self, bank, ids, players, record)
+        if record is None:
+            raise ValueError("rollout_mlpbase_bank needs an MlpBaseRecord")
+        cells = tuple(ids.shape)
+        if ids_record is not None:
+            _check_ids(self, ids_record, (record.num_steps + 1,) + cells, "ids_record")
+        if resample is not None and not isinstance(resample, CnnResample):
+            raise ValueError("resample must be a CnnResample or None")
+        if episodes is not None:
+            _check_ids(self, episodes, cells[:1], "episodes")
+        elif resample is not None:
+            raise ValueError("a resample needs episodes, an int32 tensor (num_worlds,)")
+        if workspace is None:
+            workspace = _mlpbase_bank_workspace(self, bank)
+        desc = bank.desc()
+        desc.flags = _lib.POLICY_GREEDY if greedy else 0
+        _lib.check(self._L.mrl_rollout_mlpbase_bank(
+            self._handle, mask, ctypes.byref(desc), ids.data_ptr(), episodes.data_ptr() if episodes is not None else None,
+            ctypes.byref(resample.struct) if resample is not None else None, ctypes.byref(record.struct),
+            ids_record.data_ptr() if ids_record is not None else None, int(seed) & (2 ** 64 - 1), int(first_step) & 0xFFFFFFFF,
+            workspace.data_ptr(), workspace.numel(), _stream_ptr(self.gpu_id)))
 
     def reset_worlds(self, mask=None):
         """Restart the worlds whose ``mask`` entry is nonzero (``None``: every world) as fresh episodes, enqueued on torch's

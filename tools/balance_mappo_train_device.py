@@ -52,11 +52,13 @@ def evaluate(env, policy, seed=0):
 
 def train(num_envs, num_steps, updates, seed, lr=5e-4, critic_lr=5e-4, lr_decay=False, gamma=0.99, gae_lambda=0.95, ppo_epoch=15,
           num_mini_batch=1, clip_param=0.2, entropy_coef=0.01, value_loss_coef=1.0, max_grad_norm=10.0, huber_delta=10.0, layer_N=2,
-          log=None, evaluation=None, final=None):
+          log=None, evaluation=None, final=None, policy=None):
     """``updates`` iterations of collect, advantages, update with the reference's defaults (train/config.py).  One dict per
     update: the learning rates, the mean of every stat over the update's rows (``train_info``), the episodes finished during the
     update with their mean return, and ``optimizer_step``.  ``evaluation``: a dict that takes ``evaluate``'s histogram under
-    "returns" after the last update.  ``final``: a dict that takes the final parameters (a CPU tensor) under "params"."""
+    "returns" after the last update.  ``final``: a dict that takes the final parameters (a CPU tensor) under "params".  ``policy``: an
+    ``MlpBasePolicy`` of ``layer_N`` to train in place from the parameters it holds -- a member of an ``MlpBasePolicyBank``, say --
+    instead of a fresh one initialised under ``seed``."""
     import torch
     from madrona_rl_envs_playground_amd import _lib
     from madrona_rl_envs_playground_amd.simulators import (MappoOptimizer, MlpBaseActorCritic, MlpBasePolicy, ValueNorm, mappo_advantages,
@@ -64,8 +66,11 @@ def train(num_envs, num_steps, updates, seed, lr=5e-4, critic_lr=5e-4, lr_decay=
     env = make_env(num_envs)
     device = torch.device("cuda", 0)
     players = env.n_players
-    torch.manual_seed(seed)
-    policy = MlpBasePolicy.from_module(MlpBaseActorCritic(layer_N=layer_N), device=device)
+    if policy is None:
+        torch.manual_seed(seed)
+        policy = MlpBasePolicy.from_module(MlpBaseActorCritic(layer_N=layer_N), device=device)
+    elif policy.layer_N != layer_N:
+        raise ValueError(f"the policy has layer_N {policy.layer_N}, asked for {layer_N}")
     optimizer = MappoOptimizer(policy, lr=lr, critic_lr=critic_lr)
     value_norm = ValueNorm(device)
     shuffles = torch.Generator(device=device).manual_seed(seed)
