@@ -1163,6 +1163,60 @@ int mrl_rollout_mlpbase_bank(mrl_sim *sim, uint32_t players, const mrl_mlpbase_b
                              const mrl_cnn_resample *resample_or_null, const mrl_mlpbase_record *record, int32_t *ids_record_or_null,
                              uint64_t seed, uint32_t first_step, void *workspace_dev, uint64_t workspace_bytes, void *hip_stream);
 
+/* A population of partners for Hanabi and the balance beam under the wide policy: a BANK of K policies of mrl_agent_act's shape
+ * and a policy per world for the seat that acts -- add_partner_agent's "randomly samples" a partner "at the start of every
+ * episode" (pantheonrl_extension/vectorenv.py:89-98), per world.  No reference counterpart as calls.  DESIGN.md section 21.
+ *   Bank (mrl_wide_bank): params_dev is a float32 device array of K = num_policies rows, `stride` floats apart (stride >=
+ *     mrl_wide_policy_num_params(obs_dim, state_dim, num_actions)); row k is exactly an mrl_wide_policy's params_dev, so
+ *     mrl_agent_act, mrl_agent_update and the bank act read and write the same floats.  1 <= K <= 256.
+ *   Assignment: ids, int32 (N, P), device memory, the caller's; the call reads column `player`.  A world is COMPUTED when
+ *     ACTIVE_AGENT[player, n] != 0, or always with MRL_AGENT_ALL_ROWS.  ids[n, player] = k, 0 <= k < K: a computed world acts
+ *     under row k; one that is not computed gets action 0, exactly as mrl_agent_act writes it.  -1 (any negative value): the
+ *     world's ACTION entry and its ids_row entry keep every byte.  A value >= K is outside the contract: the world is treated as
+ *     -1 and counted in the workspace's out_of_range word, computed or not.
+ *   mrl_agent_act_bank, on hip_stream: the effective ids (eff[n] = ids[n, player] where the world is computed or the id is not
+ *     valid, -1 elsewhere; this launch also writes the action 0 of the worlds not computed), the plan over eff -- mrl_cnn_act_bank's
+ *     own kernels with one seat and N cells, one launch up to 2048 worlds and three beyond --, four layer launches and the head.
+ *     A layer launch is mrl_agent_act's layer kernel body over the plan's tiles: workgroup (t, slab, net) takes entry t of the tile
+ *     table, its rows are list positions first .. first + rows (layer 1 gathers the worlds through the lists), its weights and
+ *     bias are the layer's inside row `policy` of the bank; the grid's x extent is max_tiles = ceil(N / 32) + K and workgroups past
+ *     `tiles` leave at once.  The head is mrl_agent_act's over list positions [0, acted): the same masks, the same draw
+ *     policy_hash(seed, step, world, player).  Every world's logits, value and action are bit for bit what mrl_agent_act gives that
+ *     world under row k alone.  flags: MRL_POLICY_GREEDY, MRL_AGENT_ALL_ROWS.  There is no record: population partners are
+ *     frozen, and a learner trains a member through mrl_agent_act on its row.  ids_row, (N) int32 or NULL: k where the world
+ *     acted under row k, -1 where it has a valid id and is not computed, untouched elsewhere.  No float atomics, no workgroup
+ *     waits on another, no scratch: the same inputs give the same bits on every run.
+ *   Workspace: mrl_agent_bank_workspace_bytes(N, K) bytes of device memory, 16-byte aligned, the caller's; holds nothing between
+ *     calls.  With W = mrl_agent_workspace_bytes(N) and E = 4 N rounded up to a multiple of 256:
+ *       [0, W)          mrl_agent_act's workspace, whose layout is: the world list (unused here), 4 N bytes rounded up to 256, plus
+ *                       a 256-byte slot; two activation buffers of (2, N, 512) floats; the logits (N, 64) floats; the values (N)
+ *                       floats, rounded up to 256 bytes.  Logits and values are indexed by POSITION IN THE PLAN'S LISTS.
+ *       [W, W + E)      eff, int32 (N)
+ *       [W + E, ...)    the plan's words exactly as mrl_cnn_act_bank describes them for M = N cells of one seat: [0] tiles, [1]
+ *                       acted, [2] out_of_range, count[], start[], the tile table (policy, first, rows, 0), lists (worlds, every
+ *                       policy's ascending), the chunk rows; mrl_cnn_bank_workspace_bytes(N, 1, K) bytes.
+ *   Refusals (MRL_ERR_INVALID, nothing enqueued): those of mrl_agent_act (another game, an exchanged simulator, a capturing
+ *     stream, a player beyond the seats); a NULL bank or parameter array; obs_dim, state_dim or num_actions of 0 or beyond
+ *     the simulator's rows, num_actions above 64 (mrl_agent_act's rule: the rows of a Hanabi simulator are as wide as the full
+ *     game's whatever its configuration, and a policy reads the head of a row); K = 0 or K > 256; stride below mrl_wide_policy_num_params; NULL ids; ids or ids_row off a 4-byte boundary; a
+ *     workspace that is NULL, off a 16-byte boundary or below mrl_agent_bank_workspace_bytes; MRL_AGENT_VALUE_ONLY; unknown flags.
+ * mrl_agent_bank_workspace_bytes: writes the size to *out; MRL_ERR_INVALID for K = 0, K > 256 or a NULL out.
+ * mrl_agent_bank_resample: mrl_cnn_bank_resample on a Hanabi or balance-beam simulator -- the same kernel, which reads DONE, the
+ *     ids and the episodes only, the same mrl_cnn_resample descriptor, draws and refusals; `players` is a mask of seats; any other
+ *     simulator is refused. */
+typedef struct mrl_wide_bank {
+    const float *params_dev;    /* (num_policies, stride) */
+    uint32_t num_policies;
+    uint64_t stride;            /* floats between rows */
+    uint32_t obs_dim, state_dim, num_actions;
+} mrl_wide_bank;
+int mrl_agent_bank_workspace_bytes(uint32_t num_worlds, uint32_t num_policies, uint64_t *out);
+int mrl_agent_act_bank(mrl_sim *sim, uint32_t player, const mrl_wide_bank *bank, const int32_t *ids_dev /* (N, P) */,
+                       int32_t *ids_row_or_null /* (N) */, uint64_t seed, uint32_t step, uint32_t flags, void *workspace_dev,
+                       uint64_t workspace_bytes, void *hip_stream);
+int mrl_agent_bank_resample(mrl_sim *sim, uint32_t players, const mrl_cnn_resample *resample, int32_t *ids_dev, int32_t *episodes_dev,
+                            void *hip_stream);
+
 int mrl_tensor(mrl_sim *sim, int slot, mrl_tensor_desc *out);
 int mrl_game(const mrl_sim *sim);
 uint32_t mrl_num_worlds(const mrl_sim *sim);

@@ -58,7 +58,8 @@ SYMBOLS = [
     "mrl_agent_update_workspace_bytes", "mrl_agent_update", "mrl_mlpbase_policy_num_params", "mrl_mlpbase_act",
     "mrl_rollout_mlpbase", "mrl_mappo_mlp_workspace_bytes", "mrl_mappo_mlp_update", "mrl_cnn_bank_workspace_bytes",
     "mrl_cnn_act_bank", "mrl_cnn_bank_resample", "mrl_rollout_cnn_bank", "mrl_mlpbase_bank_workspace_bytes", "mrl_mlpbase_act_bank",
-    "mrl_mlpbase_bank_resample", "mrl_rollout_mlpbase_bank",
+    "mrl_mlpbase_bank_resample", "mrl_rollout_mlpbase_bank", "mrl_agent_bank_workspace_bytes", "mrl_agent_act_bank",
+    "mrl_agent_bank_resample",
 ]
 ABI_VERSION = 4  # MRL_ABI_VERSION of include/mrl_envs.h this binding was written against
 
@@ -178,6 +179,11 @@ class MlpBaseRecordDesc(ctypes.Structure):  # mrl_mlpbase_record
 class MlpBaseBankDesc(ctypes.Structure):  # mrl_mlpbase_bank
     _fields_ = [("params_dev", ctypes.c_void_p), ("num_policies", ctypes.c_uint32), ("stride", ctypes.c_uint64), ("hidden", ctypes.c_uint32),
                 ("layer_N", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class WideBankDesc(ctypes.Structure):  # mrl_wide_bank
+    _fields_ = [("params_dev", ctypes.c_void_p), ("num_policies", ctypes.c_uint32), ("stride", ctypes.c_uint64), ("obs_dim", ctypes.c_uint32),
+                ("state_dim", ctypes.c_uint32), ("num_actions", ctypes.c_uint32)]
 
 
 class MappoMlpBatch(ctypes.Structure):  # mrl_mappo_mlp_batch
@@ -337,6 +343,9 @@ def lib():
     L.mrl_mlpbase_bank_resample.argtypes = [vp, u32, ctypes.POINTER(CnnResampleDesc), vp, vp, vp]
     L.mrl_rollout_mlpbase_bank.argtypes = [vp, u32, ctypes.POINTER(MlpBaseBankDesc), vp, vp, ctypes.POINTER(CnnResampleDesc),
                                            ctypes.POINTER(MlpBaseRecordDesc), vp, ctypes.c_uint64, u32, vp, ctypes.c_uint64, vp]
+    L.mrl_agent_bank_workspace_bytes.argtypes = [u32, u32, ctypes.POINTER(ctypes.c_uint64)]
+    L.mrl_agent_act_bank.argtypes = [vp, u32, ctypes.POINTER(WideBankDesc), vp, vp, ctypes.c_uint64, u32, u32, vp, ctypes.c_uint64, vp]
+    L.mrl_agent_bank_resample.argtypes = [vp, u32, ctypes.POINTER(CnnResampleDesc), vp, vp, vp]
     L.mrl_mappo_mlp_workspace_bytes.argtypes = [u32, u32, u32, u32, u32, u32, ctypes.POINTER(ctypes.c_uint64)]
     L.mrl_mappo_mlp_update.argtypes = [ctypes.POINTER(MlpBasePolicyDesc), ctypes.POINTER(MappoOptimizerDesc), ctypes.POINTER(MappoMlpBatch),
                                        vp, u32, u32, ctypes.POINTER(MappoConfig), vp, vp, ctypes.c_uint64, vp, vp, i32, vp]

@@ -5,6 +5,7 @@
 #include "policy_rollout.hpp"
 #include "ppo_update.hpp"
 #include "wide_policy.hpp"
+#include "wide_bank.hpp"
 #include "wide_update.hpp"
 #include "cnn_policy.hpp"
 #include "cnn_bank.hpp"
@@ -820,28 +821,69 @@ static mrl::WideInput agent_slice(const mrl_tensor_desc &d, uint32_t player)
     return in;
 }
 
-int mrl_agent_act(mrl_sim *sim, uint32_t player, const mrl_wide_policy *policy, const mrl_agent_record *record, uint32_t row,
-                  uint64_t seed, uint32_t step, uint32_t flags, void *workspace_dev, void *hip_stream)
+// Everything mrl_agent_act and mrl_agent_act_bank check alike of the simulator, the seat and the policy's shape (`policy`: for the
+// bank its row 0); fills `args` but for the record, the row, the step, the flags, the seed and the workspace; *seats: the
+// simulator's seats.
+static int agent_prepare(mrl_sim *sim, uint32_t player, const mrl_wide_policy *policy, void *workspace_dev, void *hip_stream, const char *what,
+                         mrl::AgentActArgs *out, uint32_t *seats = nullptr)
 {
     if (int rc = mrl::need_healthy(sim)) return rc;
-    if (int rc = mrl::need_not_capturing(sim, hip_stream, "mrl_agent_act")) return rc;
+    if (int rc = mrl::need_not_capturing(sim, hip_stream, what)) return rc;
     if (sim->game != MRL_GAME_HANABI && sim->game != MRL_GAME_BALANCE) {
-        mrl::set_error("mrl_agent_act: game %d has no wide-policy agent (Hanabi and the balance beam do)", sim->game);
+        mrl::set_error("%s: game %d has no wide-policy agent (Hanabi and the balance beam do)", what, sim->game);
         return MRL_ERR_INVALID;
     }
     if (sim->exchange.mine) {
-        mrl::set_error("mrl_agent_act: this simulator is a rank of an exchanged batch (mrl_exchange_create); sharded simulators are out of scope");
+        mrl::set_error("%s: this simulator is a rank of an exchanged batch (mrl_exchange_create); sharded simulators are out of scope", what);
         return MRL_ERR_INVALID;
     }
     if (!policy || !policy->params_dev || !workspace_dev || (reinterpret_cast<uintptr_t>(workspace_dev) & 15u)) {
-        mrl::set_error("mrl_agent_act: null policy or parameter array, or a workspace that is null or off a 16-byte boundary");
+        mrl::set_error("%s: null policy or parameter array, or a workspace that is null or off a 16-byte boundary", what);
         return MRL_ERR_INVALID;
     }
     if (policy->num_actions == 0 || policy->num_actions > MRL_WIDE_MAX_ACTIONS || policy->obs_dim == 0 || policy->state_dim == 0) {
-        mrl::set_error("mrl_agent_act: need 1 <= num_actions <= %d and obs_dim, state_dim >= 1; got num_actions %u, obs_dim %u, state_dim %u",
+        mrl::set_error("%s: need 1 <= num_actions <= %d and obs_dim, state_dim >= 1; got num_actions %u, obs_dim %u, state_dim %u", what,
                        MRL_WIDE_MAX_ACTIONS, policy->num_actions, policy->obs_dim, policy->state_dim);
         return MRL_ERR_INVALID;
     }
+    mrl::DeviceGuard on(sim->device);
+    int rc = MRL_OK;
+    int g = guarded([&] {
+        mrl_tensor_desc active{}, action{}, obs{}, mask{}, state{};
+        // (the slot numbers are the same for both games: MRL_HANABI_* == MRL_BALANCE_* up to REWARD; the balance beam's state is its observation)
+        if (!sim->tensor(MRL_HANABI_ACTIVE_AGENT, &active) || !sim->tensor(MRL_HANABI_ACTION, &action) ||
+            !sim->tensor(MRL_HANABI_OBSERVATION, &obs) || !sim->tensor(MRL_HANABI_ACTION_MASK, &mask) ||
+            !sim->tensor(sim->game == MRL_GAME_HANABI ? MRL_HANABI_STATE : MRL_BALANCE_OBSERVATION, &state))
+            throw std::runtime_error(std::string(what) + ": the simulator does not export ACTIVE_AGENT / ACTION / OBSERVATION / ACTION_MASK / STATE");
+        if (player >= (uint64_t)obs.shape[0] || policy->obs_dim > (uint64_t)obs.shape[2] || policy->state_dim > (uint64_t)state.shape[2] ||
+            policy->num_actions > (uint64_t)mask.shape[2]) {
+            mrl::set_error("%s: player %u of %lld; obs_dim %u, state_dim %u, num_actions %u against rows of %lld, %lld, %lld", what, player,
+                           (long long)obs.shape[0], policy->obs_dim, policy->state_dim, policy->num_actions, (long long)obs.shape[2],
+                           (long long)state.shape[2], (long long)mask.shape[2]);
+            rc = MRL_ERR_INVALID;
+            return;
+        }
+        if (obs.strides[2] != 1 || state.strides[2] != 1 || mask.strides[2] != 1 || action.dtype != MRL_INT32 || active.ndim != 2)
+            throw std::runtime_error(std::string(what) + ": unexpected tensor layout (rows must be dense, ACTION int32, ACTIVE_AGENT (P, N))");
+        mrl::AgentActArgs &args = *out;
+        args = mrl::AgentActArgs{};
+        args.params = policy->params_dev;
+        args.obs = agent_slice(obs, player), args.state = agent_slice(state, player), args.mask = agent_slice(mask, player);
+        args.active = agent_slice(active, player);
+        args.action = static_cast<int32_t *>(action.data) + (int64_t)player * action.strides[0];
+        args.action_stride = action.strides[1];
+        args.D = policy->obs_dim, args.S = policy->state_dim, args.A = policy->num_actions;
+        args.num_worlds = sim->num_worlds, args.player = player;
+        if (seats) *seats = (uint32_t)obs.shape[0];
+    });
+    return g != MRL_OK ? g : rc;
+}
+
+int mrl_agent_act(mrl_sim *sim, uint32_t player, const mrl_wide_policy *policy, const mrl_agent_record *record, uint32_t row,
+                  uint64_t seed, uint32_t step, uint32_t flags, void *workspace_dev, void *hip_stream)
+{
+    mrl::AgentActArgs args{};
+    if (int rc = agent_prepare(sim, player, policy, workspace_dev, hip_stream, "mrl_agent_act", &args)) return rc;
     if ((flags & MRL_AGENT_VALUE_ONLY) && !record) {
         mrl::set_error("mrl_agent_act: MRL_AGENT_VALUE_ONLY writes next_value and next_active of a record; none was given");
         return MRL_ERR_INVALID;
@@ -853,37 +895,11 @@ int mrl_agent_act(mrl_sim *sim, uint32_t player, const mrl_wide_policy *policy, 
         return MRL_ERR_INVALID;
     }
     mrl::DeviceGuard on(sim->device);
-    int rc = MRL_OK;
-    int g = guarded([&] {
-        mrl_tensor_desc active{}, action{}, obs{}, mask{}, state{};
-        // (the slot numbers are the same for both games: MRL_HANABI_* == MRL_BALANCE_* up to REWARD; the balance beam's state is its observation)
-        if (!sim->tensor(MRL_HANABI_ACTIVE_AGENT, &active) || !sim->tensor(MRL_HANABI_ACTION, &action) ||
-            !sim->tensor(MRL_HANABI_OBSERVATION, &obs) || !sim->tensor(MRL_HANABI_ACTION_MASK, &mask) ||
-            !sim->tensor(sim->game == MRL_GAME_HANABI ? MRL_HANABI_STATE : MRL_BALANCE_OBSERVATION, &state))
-            throw std::runtime_error("mrl_agent_act: the simulator does not export ACTIVE_AGENT / ACTION / OBSERVATION / ACTION_MASK / STATE");
-        if (player >= (uint64_t)obs.shape[0] || policy->obs_dim > (uint64_t)obs.shape[2] || policy->state_dim > (uint64_t)state.shape[2] ||
-            policy->num_actions > (uint64_t)mask.shape[2]) {
-            mrl::set_error("mrl_agent_act: player %u of %lld; obs_dim %u, state_dim %u, num_actions %u against rows of %lld, %lld, %lld", player,
-                           (long long)obs.shape[0], policy->obs_dim, policy->state_dim, policy->num_actions, (long long)obs.shape[2],
-                           (long long)state.shape[2], (long long)mask.shape[2]);
-            rc = MRL_ERR_INVALID;
-            return;
-        }
-        if (obs.strides[2] != 1 || state.strides[2] != 1 || mask.strides[2] != 1 || action.dtype != MRL_INT32 || active.ndim != 2)
-            throw std::runtime_error("mrl_agent_act: unexpected tensor layout (rows must be dense, ACTION int32, ACTIVE_AGENT (P, N))");
-        mrl::AgentActArgs args{};
-        args.params = policy->params_dev;
-        args.obs = agent_slice(obs, player), args.state = agent_slice(state, player), args.mask = agent_slice(mask, player);
-        args.active = agent_slice(active, player);
-        args.action = static_cast<int32_t *>(action.data) + (int64_t)player * action.strides[0];
-        args.action_stride = action.strides[1];
-        args.D = policy->obs_dim, args.S = policy->state_dim, args.A = policy->num_actions;
-        args.num_worlds = sim->num_worlds, args.player = player;
+    return guarded([&] {
         args.record = record, args.row = row, args.step = step, args.flags = flags, args.seed = seed;
         args.ws = mrl::wide_workspace(workspace_dev, sim->num_worlds);
         mrl::launch_agent_act(args, (hipStream_t)hip_stream);
     });
-    return g != MRL_OK ? g : rc;
 }
 
 int mrl_agent_credit(const mrl_agent_record *record, const float *rewards_dev, const int32_t *dones_dev, uint32_t num_worlds, int gpu_id,
@@ -1725,6 +1741,94 @@ int mrl_rollout_mlpbase_bank(mrl_sim *sim, uint32_t players, const mrl_mlpbase_b
             if (resample) mrl::launch_cnn_bank_resample(again, stream);
         }
     });
+}
+
+int mrl_agent_bank_workspace_bytes(uint32_t num_worlds, uint32_t num_policies, uint64_t *out)
+{
+    if (!out || num_policies == 0 || num_policies > mrl::kBankMaxPolicies) {
+        mrl::set_error("mrl_agent_bank_workspace_bytes: null output pointer, or a bank of %u policies (a bank holds 1 to %u)", num_policies,
+                       mrl::kBankMaxPolicies);
+        return MRL_ERR_INVALID;
+    }
+    *out = mrl::wide_bank_workspace_bytes(num_worlds, num_policies);
+    return MRL_OK;
+}
+
+int mrl_agent_act_bank(mrl_sim *sim, uint32_t player, const mrl_wide_bank *bank, const int32_t *ids_dev, int32_t *ids_row, uint64_t seed,
+                       uint32_t step, uint32_t flags, void *workspace_dev, uint64_t workspace_bytes, void *hip_stream)
+{
+    const char *what = "mrl_agent_act_bank";
+    if (!bank) {
+        mrl::set_error("%s: null bank", what);
+        return MRL_ERR_INVALID;
+    }
+    const mrl_wide_policy row0{bank->params_dev, bank->obs_dim, bank->state_dim, bank->num_actions};
+    mrl::WideBankArgs args{};
+    if (int rc = agent_prepare(sim, player, &row0, workspace_dev, hip_stream, what, &args.act, &args.P)) return rc;
+    if (flags & ~(uint32_t)(MRL_POLICY_GREEDY | MRL_AGENT_ALL_ROWS)) {
+        mrl::set_error("%s: flags 0x%x; the bank act takes MRL_POLICY_GREEDY and MRL_AGENT_ALL_ROWS (there is no record, so no "
+                       "MRL_AGENT_VALUE_ONLY: train a member through mrl_agent_act on its row)", what, flags);
+        return MRL_ERR_INVALID;
+    }
+    const uint32_t K = bank->num_policies, N = sim->num_worlds;
+    if (K == 0 || K > mrl::kBankMaxPolicies) {
+        mrl::set_error("%s: a bank holds 1 to %u policies, not %u", what, mrl::kBankMaxPolicies, K);
+        return MRL_ERR_INVALID;
+    }
+    const uint64_t num_params = mrl_wide_policy_num_params(bank->obs_dim, bank->state_dim, bank->num_actions);
+    if (bank->stride < num_params) {
+        mrl::set_error("%s: the bank's stride of %llu floats is below the policy's %llu parameters", what, (unsigned long long)bank->stride,
+                       (unsigned long long)num_params);
+        return MRL_ERR_INVALID;
+    }
+    if (!ids_dev || ((reinterpret_cast<uintptr_t>(ids_dev) | reinterpret_cast<uintptr_t>(ids_row)) & 3u)) {
+        mrl::set_error("%s: ids is null, or ids or ids_row is off a 4-byte boundary", what);
+        return MRL_ERR_INVALID;
+    }
+    if (workspace_bytes < mrl::wide_bank_workspace_bytes(N, K)) {
+        mrl::set_error("%s: the workspace of %llu bytes is smaller than mrl_agent_bank_workspace_bytes = %llu", what,
+                       (unsigned long long)workspace_bytes, (unsigned long long)mrl::wide_bank_workspace_bytes(N, K));
+        return MRL_ERR_INVALID;
+    }
+    mrl::DeviceGuard on(sim->device);
+    return guarded([&] {
+        char *base = static_cast<char *>(workspace_dev);
+        args.act.record = nullptr, args.act.row = 0, args.act.step = step, args.act.flags = flags, args.act.seed = seed;
+        args.act.ws = mrl::wide_workspace(base, N);
+        args.eff = reinterpret_cast<int32_t *>(base + mrl::wide_workspace_bytes(N));
+        args.plan = reinterpret_cast<uint32_t *>(base + mrl::wide_workspace_bytes(N) + mrl::wide_bank_eff_bytes(N));
+        args.ids = ids_dev, args.ids_row = ids_row;
+        args.stride = bank->stride, args.num_policies = K;
+        mrl::launch_agent_act_bank(args, (hipStream_t)hip_stream);
+    });
+}
+
+int mrl_agent_bank_resample(mrl_sim *sim, uint32_t players, const mrl_cnn_resample *resample, int32_t *ids_dev, int32_t *episodes_dev,
+                            void *hip_stream)
+{
+    const char *what = "mrl_agent_bank_resample";
+    if (int rc = mrl::need_healthy(sim)) return rc;
+    if (sim->game != MRL_GAME_HANABI && sim->game != MRL_GAME_BALANCE) {
+        mrl::set_error("%s: game %d has no wide-policy agent (Hanabi and the balance beam do)", what, sim->game);
+        return MRL_ERR_INVALID;
+    }
+    if (int rc = resample_desc_refusal(resample, what)) return rc;
+    mrl_tensor_desc obs{}, done{};
+    int rc = mrl::guarded([&] {
+        // (the slot numbers are the same for both games)
+        if (!sim->tensor(MRL_HANABI_OBSERVATION, &obs) || !sim->tensor(MRL_HANABI_DONE, &done))
+            throw std::runtime_error("the simulator does not export OBSERVATION / DONE");
+    });
+    if (rc) return rc;
+    mrl::CnnResampleArgs args{};
+    if (int rc2 = resample_fill(sim, players, (uint32_t)obs.shape[0], done, resample, what, &args)) return rc2;
+    if (!ids_dev || !episodes_dev || ((reinterpret_cast<uintptr_t>(ids_dev) | reinterpret_cast<uintptr_t>(episodes_dev)) & 3u)) {
+        mrl::set_error("%s: ids or episodes is null or off a 4-byte boundary", what);
+        return MRL_ERR_INVALID;
+    }
+    args.ids = ids_dev, args.episodes = episodes_dev;
+    mrl::DeviceGuard on(sim->device);
+    return mrl::guarded([&] { mrl::launch_cnn_bank_resample(args, (hipStream_t)hip_stream); });
 }
 
 // what mrl_mappo_mlp_workspace_bytes and mrl_mappo_mlp_update refuse alike: nullptr when the shape can run, else why not

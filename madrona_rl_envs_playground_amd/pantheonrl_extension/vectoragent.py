@@ -196,6 +196,65 @@ class MlpBasePopulationAgent(_PopulationSeat, MlpBasePolicyAgent):
         return mlpbase_act_bank, mlpbase_resample
 
 
+class WidePolicyAgent(_DevicePolicyAgent):
+    """A FROZEN player of a Hanabi or balance-beam env under the wide policy -- ``CleanPPOAgent``'s two 512-wide networks -- on the
+    device: ``get_action`` is ``mrl_agent_act`` without a record for this agent's seat (``player_num``, set by
+    ``env.add_partner_agent``, or, while that is ``None``, the env's ``ego_ind``) on the simulator's own tensors, and returns the
+    view ``env.static_actions[seat]``; worlds where it is not this seat's turn get action 0.  ``policy``: a
+    ``simulators.WidePolicy``; ``seed`` seeds the draws, whose step number counts this agent's calls.  ``update`` does nothing: a
+    partner that learns is a ``CleanPPOAgent``.  The agent owns its workspace.  ``envs`` must be a ``MadronaEnv`` over a Hanabi or
+    balance-beam simulator on the GPU: ``TypeError`` otherwise, from the constructor; there is no torch fallback."""
+
+    _entry = "mrl_agent_act"
+
+    def _check_env(self):
+        from ..simulators import BalanceBeamSimulator, HanabiSimulator
+        from .vectorenv import MadronaEnv
+        envs = self.envs
+        sim = getattr(envs, "sim", None)
+        if not isinstance(envs, MadronaEnv) or not isinstance(sim, (HanabiSimulator, BalanceBeamSimulator)):
+            raise TypeError(f"{type(self).__name__} acts through {self._entry}: envs must be a MadronaEnv over a HanabiSimulator or a "
+                            f"BalanceBeamSimulator, got {type(envs).__name__} over {type(sim).__name__}; there is no torch fallback")
+        if envs.device.type != "cuda":
+            raise TypeError(f"{type(self).__name__} needs the env on the simulator's GPU (cuda:{sim.gpu_id}); got env device {envs.device}")
+        self._workspace = None
+        return sim
+
+    def _act(self, mask):
+        from .. import _lib
+        from ..simulators import agent_act
+        if self._workspace is None:
+            self._workspace = torch.empty(int(_lib.lib().mrl_agent_workspace_bytes(self._sim.num_worlds)), dtype=torch.uint8,
+                                          device=self.envs.static_actions.device)
+        agent_act(self._sim, self.seat, self.policy, seed=self.seed, step=self._draws, greedy=self.greedy, workspace=self._workspace)
+
+
+class WidePopulationAgent(_PopulationSeat, WidePolicyAgent):
+    """A partner seat of a Hanabi or balance-beam env played by a POPULATION under the wide policy, the counterpart of
+    ``CnnPopulationAgent`` and ``MlpBasePopulationAgent``: every world has its own member of ``bank`` (a
+    ``simulators.WidePolicyBank``) and draws a new one when its episode ends -- ``add_partner_agent``'s per-episode partner
+    sampling, per world.  World n starts with ``members[n % len(members)]`` (``members``: rows of the bank, default all);
+    ``get_action`` is ``agent_act_bank`` for this agent's seat; ``update(rewards, dones)`` is ``wide_resample``: where the
+    simulator's DONE is set the world's count in ``episodes`` goes up and its member is replaced, ``resample`` "robin" the next of
+    ``members``, "random" one of them by ``random_hash(seed, episode, world, seat)``, ``None`` never (with a resample ``members``
+    must be ``range(first, first + num)``, the range the device call draws from).  ``ids`` (N, P) int32 -- -1 in the other seat's
+    column -- and ``episodes`` (N) int32 live on the device and exist from the first call on.  The members are frozen here; train
+    one through ``bank.policy(k)``.  ``WidePolicyAgent``'s refusals, and no torch fallback."""
+
+    _bank_class, _entry = "WidePolicyBank", "mrl_agent_act_bank"
+
+    def _num_seats(self):
+        return self.envs.n_players
+
+    def _bank_calls(self):
+        from ..simulators import agent_act_bank, wide_resample
+
+        def act(sim, bank, ids, mask, seed, step, greedy):
+            agent_act_bank(sim, self.seat, bank, ids, seed=seed, step=step, greedy=greedy)
+
+        return act, wide_resample
+
+
 class CleanPPOAgent(VectorAgent):
     """The reference's PPO agent for Hanabi and the balance beam (/root/reference/pantheonrl_extension/vectoragent.py:116-372;
     built twice, ego and partner, by scripts/hanabi_train.py and scripts/balance_train.py) with its collection phase on the
@@ -275,6 +334,18 @@ class CleanPPOAgent(VectorAgent):
             self.optimizer = WideOptimizer(self.policy, lr=self.lr, eps=1e-5)
         else:
             self.optimizer = torch.optim.Adam(self.agent.parameters(), lr=self.lr, eps=1e-5)
+
+    def use_policy(self, policy):
+        """(extension) Learn ``policy`` -- a ``simulators.WidePolicy`` of this agent's shape, for example a member of a
+        ``WidePolicyBank`` -- in place from now on, instead of the policy the constructor made.  The optimizer starts anew."""
+        from ..simulators import WidePolicy
+        mine = self.policy
+        if not isinstance(policy, WidePolicy) or (policy.obs_dim, policy.state_dim, policy.num_actions) != (mine.obs_dim, mine.state_dim,
+                                                                                                           mine.num_actions):
+            raise ValueError(f"policy must be a WidePolicy of shape ({mine.obs_dim}, {mine.state_dim}, {mine.num_actions})")
+        self.policy, self.agent = policy, policy.module()
+        on, self._device_update = self._device_update, not self._device_update
+        self.device_update = on  # the setter builds the optimizer of that kind over the new parameters
 
     def _attach(self):
         self._sim = self._check_env()

@@ -681,10 +681,16 @@ def cross_play(env, bank, members_a=None, members_b=None, greedy=True, seed=0, s
     three: six episodes where nobody leaves the line) times (``mlpbase_act_bank``, step) follow the restart.  The beam's episodes have no fixed length, so every episode a
     world finishes within ``steps`` counts: behind each step the last-episode return of the worlds whose DONE is set is added to
     per-world float64 sums and counts (elementwise, no host wait), which are reduced per pair at the end -- the returns are
-    float32, so the sums are exact whatever the order.  ``episodes`` is then the number of finished episodes per pair.  ``steps``
-    is the beam's alone: the kitchens play one horizon."""
+    float32, so the sums are exact whatever the order.  ``episodes`` is then the number of finished episodes per pair.
+
+    With a ``WidePolicyBank`` ``env`` is a ``HanabiMadrona`` or a ``BalanceMadronaTorch`` on the GPU and a step is
+    ``agent_act_bank`` for seat 0, the same for seat 1, then the simulator's step; the episodes are counted as on the beam.  A game
+    of Hanabi has no length to derive a default from: ``steps`` must be given there (on the beam it defaults to 12).  The kitchens
+    play one horizon and take no ``steps``."""
     if isinstance(bank, MlpBasePolicyBank):
         return _cross_play_beam(env, bank, members_a, members_b, greedy, seed, steps)
+    if isinstance(bank, WidePolicyBank):
+        return _cross_play_wide(env, bank, members_a, members_b, greedy, seed, steps)
     if steps is not None:
         raise ValueError("steps is the balance beam's: a kitchen's cross-play lasts one horizon")
     sim = env.sim
@@ -1003,12 +1009,13 @@ def mlpbase_resample(sim, ids, episodes, mode, first_id=None, num_ids=None, play
 BEAM_TIME = 3  # src/balance_beam_env/sim.cpp: an observation holds TIME positions per seat, an episode is at most TIME - 1 moves
 
 
-def _cross_play_beam(env, bank, members_a, members_b, greedy, seed, steps):
-    """``cross_play`` for an ``MlpBasePolicyBank`` on the balance beam"""
-    sim = env.sim
-    if not isinstance(sim, BalanceBeamSimulator):
-        raise ValueError("an MlpBasePolicyBank plays on the balance beam: env.sim must be a BalanceBeamSimulator")
+def _cross_play_counted(sim, bank, members_a, members_b, steps, act):
+    """What ``cross_play`` shares between the games whose episodes have no fixed length (``sim``: P = 2 seats, DONE (N),
+    the last-episode return (P, N)): the pairs, the restart, ``steps`` times (``act(ids, t)``, step, count) and the per-pair
+    reduction.  ``act`` enqueues step t's acts of both seats under ``ids`` (N, 2)."""
     p, n = tuple(sim.observation_tensor().shape[:2])
+    if p != 2:
+        raise ValueError(f"cross_play pairs seat 0 with seat 1: the env has {p} seats")
     a = list(range(bank.num_policies)) if members_a is None else [int(k) for k in members_a]
     b = list(range(bank.num_policies)) if members_b is None else [int(k) for k in members_b]
     if not a or not b or any(not 0 <= k < bank.num_policies for k in a + b):
@@ -1016,7 +1023,7 @@ def _cross_play_beam(env, bank, members_a, members_b, greedy, seed, steps):
     pairs = len(a) * len(b)
     if n < pairs:
         raise ValueError(f"{n} worlds cannot play {len(a)} x {len(b)} pairs")
-    steps = 4 * BEAM_TIME if steps is None else int(steps)
+    steps = int(steps)
     if steps < 1:
         raise ValueError("steps must be positive")
     device = torch.device("cuda", sim.gpu_id)
@@ -1029,7 +1036,7 @@ def _cross_play_beam(env, bank, members_a, members_b, greedy, seed, steps):
     total = torch.zeros(n, dtype=torch.float64, device=device)
     finished = torch.zeros(n, dtype=torch.int64, device=device)
     for t in range(steps):
-        mlpbase_act_bank(sim, bank, ids, seed=seed, step=t, greedy=greedy)
+        act(ids, t)
         sim.step()
         over = done != 0
         total += torch.where(over, last.to(torch.float64), torch.zeros_like(total))  # float32 returns: the float64 sums are exact
@@ -1037,6 +1044,33 @@ def _cross_play_beam(env, bank, members_a, members_b, greedy, seed, steps):
     count = torch.zeros(pairs, dtype=torch.int64, device=device).index_add_(0, pair, finished)
     summed = torch.zeros(pairs, dtype=torch.float64, device=device).index_add_(0, pair, total)
     return CrossPlayResult((summed / count).view(len(a), len(b)), count.view(len(a), len(b)))
+
+
+def _cross_play_beam(env, bank, members_a, members_b, greedy, seed, steps):
+    """``cross_play`` for an ``MlpBasePolicyBank`` on the balance beam"""
+    sim = env.sim
+    if not isinstance(sim, BalanceBeamSimulator):
+        raise ValueError("an MlpBasePolicyBank plays on the balance beam: env.sim must be a BalanceBeamSimulator")
+    return _cross_play_counted(sim, bank, members_a, members_b, 4 * BEAM_TIME if steps is None else steps,
+                               lambda ids, t: mlpbase_act_bank(sim, bank, ids, seed=seed, step=t, greedy=greedy))
+
+
+def _cross_play_wide(env, bank, members_a, members_b, greedy, seed, steps):
+    """``cross_play`` for a ``WidePolicyBank`` on Hanabi or the balance beam"""
+    sim = getattr(env, "sim", None)
+    if not isinstance(sim, (HanabiSimulator, BalanceBeamSimulator)):
+        raise ValueError("a WidePolicyBank plays Hanabi or the balance beam: env.sim must be a HanabiSimulator or a BalanceBeamSimulator, "
+                         f"got {type(sim).__name__}")
+    if steps is None:
+        if isinstance(sim, HanabiSimulator):
+            raise ValueError("steps has no default for Hanabi: a game has no fixed length; give the number of steps to play")
+        steps = 4 * BEAM_TIME
+
+    def act(ids, t):
+        agent_act_bank(sim, 0, bank, ids, seed=seed, step=t, greedy=greedy)
+        agent_act_bank(sim, 1, bank, ids, seed=seed, step=t, greedy=greedy)
+
+    return _cross_play_counted(sim, bank, members_a, members_b, steps, act)
 
 
 def _wide_mlp(inputs, outputs, hidden=_lib.WIDE_HIDDEN):
@@ -1186,6 +1220,127 @@ def agent_act(sim, player, policy, record=None, row=0, seed=0, step=0, greedy=Fa
                               _stream_ptr(sim.gpu_id))
     if rc:
         _lib.check(rc)
+
+
+class WidePolicyBank:
+    """K ``WidePolicy`` of one shape in one dense float32 tensor ``params`` (K, num_params) (``mrl_wide_bank``), the counterpart of
+    ``CnnPolicyBank`` and ``MlpBasePolicyBank`` for Hanabi and the balance beam: row k is exactly what a ``WidePolicy``'s ``params``
+    is.  ``policy(k)`` is a ``WidePolicy`` whose ``params`` IS row k, a contiguous view, so ``agent_act``, ``WideOptimizer`` /
+    ``agent_update``, ``.module()`` and a torch optimizer work on a member unchanged, and training a member is what the next
+    ``agent_act_bank`` reads.  1 <= K <= 256."""
+
+    def __init__(self, obs_dim, state_dim, num_actions, num_policies, device="cuda:0"):
+        self.obs_dim, self.state_dim, self.num_actions = int(obs_dim), int(state_dim), int(num_actions)
+        self.num_policies = int(num_policies)
+        if not 1 <= self.num_policies <= _lib.CNN_BANK_MAX_POLICIES:
+            raise ValueError(f"a bank holds 1 to {_lib.CNN_BANK_MAX_POLICIES} policies, not {num_policies}")
+        if not 1 <= self.num_actions <= _lib.WIDE_MAX_ACTIONS or self.obs_dim < 1 or self.state_dim < 1:
+            raise ValueError(f"need 1 <= num_actions <= {_lib.WIDE_MAX_ACTIONS} and obs_dim, state_dim >= 1")
+        self.num_params = int(_lib.lib().mrl_wide_policy_num_params(self.obs_dim, self.state_dim, self.num_actions))
+        self.params = torch.zeros((self.num_policies, self.num_params), dtype=torch.float32, device=torch.device(device))
+        self._members = {}
+
+    def __len__(self):
+        return self.num_policies
+
+    def policy(self, k):
+        """The ``WidePolicy`` whose ``params`` is row ``k`` of the bank (one object per row)."""
+        k = int(k)
+        if not 0 <= k < self.num_policies:
+            raise IndexError(f"the bank holds policies 0..{self.num_policies - 1}, not {k}")
+        member = self._members.get(k)
+        if member is None:
+            member = WidePolicy.__new__(WidePolicy)
+            member.obs_dim, member.state_dim, member.num_actions = self.obs_dim, self.state_dim, self.num_actions
+            member.params = self.params[k]
+            member._module = None
+            self._members[k] = member
+        return member
+
+    @classmethod
+    def from_policies(cls, policies, device=None):
+        """A bank holding copies of ``policies`` (``WidePolicy`` of one shape), in that order (``device``: default the first one's)."""
+        policies = list(policies)
+        if not policies or not all(isinstance(p, WidePolicy) for p in policies):
+            raise ValueError("from_policies takes a non-empty list of WidePolicy")
+        first = policies[0]
+        shape = (first.obs_dim, first.state_dim, first.num_actions)
+        if any((p.obs_dim, p.state_dim, p.num_actions) != shape for p in policies):
+            raise ValueError("the policies of a bank must have one shape")
+        bank = cls(*shape, len(policies), device if device is not None else first.params.device)
+        with torch.no_grad():
+            for k, p in enumerate(policies):
+                bank.params[k].copy_(p.params)
+        return bank
+
+    def desc(self):
+        return _lib.WideBankDesc(self.params.data_ptr(), self.num_policies, self.params.stride(0), self.obs_dim, self.state_dim,
+                                 self.num_actions)
+
+
+def _wide_seats(sim, what):
+    """(seats, worlds) of a Hanabi or balance-beam simulator; any other is refused"""
+    if not isinstance(sim, (HanabiSimulator, BalanceBeamSimulator)):
+        raise ValueError(f"{what} runs on a HanabiSimulator or a BalanceBeamSimulator, not on a {type(sim).__name__}")
+    return tuple(sim.observation_tensor().shape[:2])
+
+
+def agent_bank_workspace_bytes(num_worlds, num_policies):
+    """``mrl_agent_bank_workspace_bytes``"""
+    out = ctypes.c_uint64(0)
+    _lib.check(_lib.lib().mrl_agent_bank_workspace_bytes(int(num_worlds), int(num_policies), ctypes.byref(out)))
+    return int(out.value)
+
+
+def _wide_bank_workspace(sim, bank):
+    size = agent_bank_workspace_bytes(sim.num_worlds, bank.num_policies)
+    cache = sim.__dict__.setdefault("_wide_bank_workspaces", {})
+    workspace = cache.get(id(bank))
+    if workspace is None or workspace[0] is not bank or workspace[1].numel() < size:
+        workspace = cache[id(bank)] = (bank, torch.empty(size, dtype=torch.uint8, device=torch.device("cuda", sim.gpu_id)))
+    return workspace[1]
+
+
+def agent_act_bank(sim, player, bank, ids, ids_row=None, seed=0, step=0, greedy=False, all_rows=False, workspace=None):
+    """``mrl_agent_act_bank`` on torch's current stream: seat ``player`` of world n of a Hanabi or balance-beam simulator acts under
+    row ``ids[n, player]`` of ``bank`` (a ``WidePolicyBank``) where the world is computed -- where it is ``player``'s turn, or
+    everywhere with ``all_rows`` -- and gets action 0 where it is not, as ``agent_act`` writes it; a world at -1 keeps its ACTION
+    entry.  The effective ids, the plan (``cnn_act_bank``'s own, over one seat), ``agent_act``'s layer kernel over the plan's tiles
+    and its head: every world's logits, value and action are bit for bit ``agent_act``'s under the world's policy.  There is no
+    record: a learner trains ``bank.policy(k)`` through ``agent_act``.  ``ids``: int32 (N, P) on the device; ``ids_row``: int32 (N)
+    that receives k where the world acted under row k and -1 where it has a valid id and is not computed.  ``workspace``: default
+    one the simulator keeps per bank (``mrl_agent_bank_workspace_bytes``; its layout is in include/mrl_envs.h)."""
+    if not isinstance(bank, WidePolicyBank):
+        raise ValueError("bank must be a WidePolicyBank")
+    seats, worlds = _wide_seats(sim, "mrl_agent_act_bank")
+    p = bank.params
+    if (not p.is_cuda or p.device.index != sim.gpu_id or p.dtype != torch.float32 or not p.is_contiguous() or
+            tuple(p.shape) != (bank.num_policies, bank.num_params)):
+        raise ValueError(f"bank.params must be a contiguous float32 tensor (num_policies, num_params) on cuda:{sim.gpu_id}")
+    _check_ids(sim, ids, (worlds, seats), "ids")
+    if ids_row is not None:
+        _check_ids(sim, ids_row, (worlds,), "ids_row")
+    if workspace is None:
+        workspace = _wide_bank_workspace(sim, bank)
+    flags = (_lib.POLICY_GREEDY if greedy else 0) | (_lib.AGENT_ALL_ROWS if all_rows else 0)
+    desc = bank.desc()
+    rc = sim._L.mrl_agent_act_bank(sim._handle, int(player), ctypes.byref(desc), ids.data_ptr(),
+                                   ids_row.data_ptr() if ids_row is not None else None, int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF,
+                                   flags, workspace.data_ptr(), workspace.numel(), _stream_ptr(sim.gpu_id))
+    if rc:
+        _lib.check(rc)
+
+
+def wide_resample(sim, ids, episodes, mode, first_id=None, num_ids=None, players=None, seed=0):
+    """``mrl_agent_bank_resample`` on torch's current stream: ``cnn_resample`` on a Hanabi or balance-beam simulator -- the same
+    kernel, draws and arguments (``resample_twin`` is the same in numpy).  ``mode`` may also be a ``CnnResample``
+    (``BankResample``), which then carries the rest."""
+    seats, worlds = _wide_seats(sim, "mrl_agent_bank_resample")
+    _check_ids(sim, ids, (worlds, seats), "ids")
+    _check_ids(sim, episodes, (worlds,), "episodes")
+    resample = mode if isinstance(mode, CnnResample) else CnnResample(mode, first_id, num_ids, seats, seed)
+    _lib.check(sim._L.mrl_agent_bank_resample(sim._handle, _seat_mask(players, seats), ctypes.byref(resample.struct), ids.data_ptr(),
+                                              episodes.data_ptr(), _stream_ptr(sim.gpu_id)))
 
 
 def agent_credit(record, rewards, dones):

@@ -1,0 +1,181 @@
+"""CPU: the surface of the wide policy's bank (``mrl_agent_act_bank``, ``mrl_agent_bank_resample``,
+``mrl_agent_bank_workspace_bytes``) that needs no GPU -- symbols, struct layout, the documented workspace layout, the refusals that
+are raised before any launch, and the aliasing of a bank's members."""
+import ctypes
+import re
+
+import pytest
+import torch
+
+from madrona_rl_envs_playground_amd import _lib, simulators
+from madrona_rl_envs_playground_amd.envs.cartpole_env import CartpoleMadronaTorch
+from madrona_rl_envs_playground_amd.pantheonrl_extension import WidePolicyAgent, WidePopulationAgent
+from madrona_rl_envs_playground_amd.simulators import (MlpBasePolicyBank, WideAgent, WideOptimizer, WidePolicy, WidePolicyBank,
+                                                         agent_act_bank, agent_bank_workspace_bytes, cross_play, wide_resample)
+
+NEW = ("mrl_agent_bank_workspace_bytes", "mrl_agent_act_bank", "mrl_agent_bank_resample")
+
+
+def test_symbols_abi_and_struct_layout(hip_lib):
+    header = open(_lib.HEADER).read()
+    for name in NEW:
+        assert name in _lib.SYMBOLS and re.search(rf"\b{name}\(", header)
+        getattr(hip_lib, name)
+    assert re.search(r"#define MRL_ABI_VERSION 4\b", header) and int(hip_lib.mrl_abi_version()) == 4  # additive: the version stays
+    assert re.search(r"typedef struct mrl_wide_bank \{", header)
+    # mrl_wide_bank { const float *; uint32_t; uint64_t; uint32_t, uint32_t, uint32_t }: 8 + 4 (+ 4) + 8 + 12 (+ 4)
+    assert [f[0] for f in _lib.WideBankDesc._fields_] == ["params_dev", "num_policies", "stride", "obs_dim", "state_dim", "num_actions"]
+    assert ctypes.sizeof(_lib.WideBankDesc) == 40 and _lib.WideBankDesc.stride.offset == 16
+    assert (_lib.WideBankDesc.obs_dim.offset, _lib.WideBankDesc.state_dim.offset, _lib.WideBankDesc.num_actions.offset) == (24, 28, 32)
+
+
+def up(x, to):
+    return (x + to - 1) // to * to
+
+
+def plan_words(n, k):
+    """bank_plan.hpp's words for n cells of one seat and k policies, as include/mrl_envs.h documents them"""
+    kp, max_tiles = up(k, 4), (n + 31) // 32 + k
+    return 4 + 2 * kp + 4 * max_tiles + up(n, 4) + (n + 1023) // 1024 * (kp + 4)
+
+
+@pytest.mark.parametrize("n", [1, 33, 2049])
+@pytest.mark.parametrize("k", [1, 5, 256])
+def test_workspace_is_the_documented_layout(n, k, hip_lib):
+    """mrl_agent_act's workspace -- the world list and its slot, two activation buffers (2, N, 512), the logits (N, 64), the
+    values -- then eff (N int32, to 256 bytes), then the plan's words"""
+    act = up(4 * n, 256) + 256 + 2 * (2 * n * 512 * 4) + n * 64 * 4 + up(4 * n, 256)
+    assert int(hip_lib.mrl_agent_workspace_bytes(n)) == act
+    assert int(hip_lib.mrl_cnn_bank_workspace_bytes(n, 1, k)) == 4 * plan_words(n, k)
+    got = agent_bank_workspace_bytes(n, k)
+    assert got == act + up(4 * n, 256) + 4 * plan_words(n, k) and got % 16 == 0
+
+
+def test_refusals_without_a_device(hip_lib):
+    out = ctypes.c_uint64(7)
+    for k in (0, 257):
+        assert hip_lib.mrl_agent_bank_workspace_bytes(33, k, ctypes.byref(out)) != 0 and out.value == 7
+        with pytest.raises(_lib.MrlError):
+            agent_bank_workspace_bytes(33, k)
+    assert hip_lib.mrl_agent_bank_workspace_bytes(33, 1, None) != 0
+    # no simulator: every call is refused before it looks at anything else
+    bank = _lib.WideBankDesc(None, 1, 0, 7, 7, 4)
+    first, num = (ctypes.c_uint32 * 2)(0, 0), (ctypes.c_uint32 * 2)(1, 1)
+    resample = _lib.CnnResampleDesc(1, first, num, 0)
+    assert hip_lib.mrl_agent_act_bank(None, 0, ctypes.byref(bank), None, None, 0, 0, 0, None, 0, None) != 0
+    assert hip_lib.mrl_agent_bank_resample(None, 3, ctypes.byref(resample), None, None, None) != 0
+    for k in (0, 257, -1):
+        with pytest.raises(ValueError):
+            WidePolicyBank(7, 7, 4, k, device="cpu")
+    for shape in ((7, 7, 0), (7, 7, 65), (0, 7, 4), (7, 0, 4)):
+        with pytest.raises(ValueError):
+            WidePolicyBank(*shape, 2, device="cpu")
+    with pytest.raises(ValueError):
+        WidePolicyBank.from_policies([])
+    with pytest.raises(ValueError, match="one shape"):
+        WidePolicyBank.from_policies([WidePolicy(7, 7, 4, device="cpu"), WidePolicy(7, 8, 4, device="cpu")])
+    with pytest.raises(ValueError):
+        WidePolicyBank.from_policies([object()])
+    bank = WidePolicyBank(7, 7, 4, 3, device="cpu")
+    for k in (-1, 3):
+        with pytest.raises(IndexError):
+            bank.policy(k)
+
+    class NotAWideGame:
+        gpu_id = 0
+
+    ids = torch.zeros((3, 2), dtype=torch.int32)
+    with pytest.raises(ValueError, match="HanabiSimulator or a BalanceBeamSimulator"):
+        agent_act_bank(NotAWideGame(), 0, bank, ids)
+    with pytest.raises(ValueError, match="WidePolicyBank"):
+        agent_act_bank(NotAWideGame(), 0, bank.policy(0), ids)
+    with pytest.raises(ValueError, match="HanabiSimulator or a BalanceBeamSimulator"):
+        wide_resample(NotAWideGame(), ids, torch.zeros(3, dtype=torch.int32), "robin", 0, 3)
+
+
+def test_cross_play_refuses_a_kitchen(hip_lib):
+    """dispatched on the bank's type, refused on the env's: a wide bank does not play a kitchen"""
+    bank = WidePolicyBank(7, 7, 4, 2, device="cpu")
+    kitchen_sim = simulators.OvercookedSimulator.__new__(simulators.OvercookedSimulator)  # (never created: no device is touched)
+    kitchen_sim._handle = None
+
+    class KitchenEnv:
+        sim = kitchen_sim
+        horizon = 4
+
+    with pytest.raises(ValueError, match="Hanabi or the balance beam"):
+        cross_play(KitchenEnv(), bank, steps=4)
+    with pytest.raises(ValueError, match="Hanabi or the balance beam"):
+        cross_play(KitchenEnv(), bank)
+    # and the beam's own bank is still refused on the env, by the beam's branch
+    with pytest.raises(ValueError, match="BalanceBeamSimulator"):
+        cross_play(KitchenEnv(), MlpBasePolicyBank(2, device="cpu"))
+
+
+def test_agents_refuse_other_envs(hip_lib):
+    bank = WidePolicyBank(4, 4, 2, 3, device="cpu")
+    cartpole = CartpoleMadronaTorch.__new__(CartpoleMadronaTorch)  # a Cartpole env that was never started: no device is touched
+    for envs in (cartpole, object()):
+        with pytest.raises(TypeError, match="MadronaEnv"):
+            WidePolicyAgent(envs, bank.policy(0))
+        with pytest.raises(TypeError, match="MadronaEnv"):
+            WidePopulationAgent(envs, bank)
+    with pytest.raises(TypeError, match="WidePolicyBank"):
+        WidePopulationAgent(cartpole, object())
+    with pytest.raises(TypeError, match="WidePolicyBank"):
+        WidePopulationAgent(cartpole, MlpBasePolicyBank(2, device="cpu"))  # the other network's bank
+
+
+def test_population_agent_checks_its_members(hip_lib, monkeypatch):
+    """the checks of the members run behind the env's: give the agent an env it accepts"""
+    bank = WidePolicyBank(4, 4, 2, 5, device="cpu")
+    monkeypatch.setattr(WidePopulationAgent, "_check_env", lambda self: None)
+    envs = object()
+    with pytest.raises(ValueError, match="consecutive"):
+        WidePopulationAgent(envs, bank, members=[0, 2, 3], resample="robin")
+    with pytest.raises(ValueError, match="consecutive"):
+        WidePopulationAgent(envs, bank, members=[2, 1], resample="random")
+    assert WidePopulationAgent(envs, bank, members=[0, 2, 3], resample=None).members == [0, 2, 3]
+    assert WidePopulationAgent(envs, bank, members=[1, 2, 3]).resample == "robin"
+    for members in ([], [5], [-1]):
+        with pytest.raises(ValueError, match="members"):
+            WidePopulationAgent(envs, bank, members=members)
+    with pytest.raises(ValueError, match="resample"):
+        WidePopulationAgent(envs, bank, resample="sometimes")
+
+
+def test_members_are_views_of_the_bank(hip_lib):
+    sources = []
+    for seed in (1, 2, 3):
+        torch.manual_seed(seed)
+        sources.append(WidePolicy.from_module(WideAgent(9, 11, 5), device="cpu"))
+    bank = WidePolicyBank.from_policies(sources)
+    assert bank.params.shape == (3, sources[0].num_params) and bank.params.is_contiguous() and len(bank) == 3
+    assert bank.num_params == int(hip_lib.mrl_wide_policy_num_params(9, 11, 5))
+    desc = bank.desc()
+    assert desc.params_dev == bank.params.data_ptr() and desc.num_policies == 3 and desc.stride == bank.num_params
+    assert (desc.obs_dim, desc.state_dim, desc.num_actions) == (9, 11, 5)
+    for k in range(3):
+        member = bank.policy(k)
+        assert member is bank.policy(k) and isinstance(member, WidePolicy)
+        assert member.params.data_ptr() == bank.params[k].data_ptr() == bank.params.data_ptr() + 4 * k * bank.num_params
+        assert member.params.is_contiguous() and member.num_params == bank.num_params == member.params.numel()
+        assert torch.equal(member.params, sources[k].params) and member.params.data_ptr() != sources[k].params.data_ptr()
+        assert member.desc().params_dev == member.params.data_ptr()
+        assert (member.desc().obs_dim, member.desc().state_dim, member.desc().num_actions) == (9, 11, 5)
+    # a member's module and optimizers are the stand-alone policy's: parameters alias the row, a step on them moves the bank
+    module = bank.policy(1).module()
+    assert isinstance(module, WideAgent) and module is bank.policy(1).module()
+    at = bank.params[1].data_ptr()
+    for p in module.parameters():
+        assert p.data_ptr() == at
+        at += 4 * p.numel()
+    assert at == bank.params[2].data_ptr()
+    before = bank.params.clone()
+    optimizer = torch.optim.SGD(module.parameters(), lr=0.5)
+    x = torch.ones(2, 9)
+    module.actor(x).sum().backward()
+    optimizer.step()
+    assert not torch.equal(bank.params[1], before[1])
+    assert torch.equal(bank.params[0], before[0]) and torch.equal(bank.params[2], before[2])
+    assert WideOptimizer(bank.policy(1)).policy is bank.policy(1)
