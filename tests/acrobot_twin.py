@@ -33,18 +33,25 @@ def wrap(x):
     return np.where(x < -PI_F, x + two_pi * np.ceil((-PI_F - x) / two_pi), x)
 
 
-def step(state, action):
-    """state (n, 4), action (n,) in {0, 1, 2} -> (next state (n, 4) float64, height (n,), raw velocities (n, 2))."""
+def step(state, action, detail=False):
+    """state (n, 4), action (n,) in {0, 1, 2} -> (next state (n, 4) float64, height (n,), raw velocities (n, 2)); with
+    ``detail`` also the new angles before the wrap (n, 2) and the largest |angle| any of the four stages evaluates (n,)."""
     y0 = np.asarray(state, np.float64)
     a = np.asarray(action, np.float64) - 1.0
     k1 = derivs(y0, a)
-    k2 = derivs(y0 + k1 * DT2, a)
-    k3 = derivs(y0 + k2 * DT2, a)
-    k4 = derivs(y0 + k3 * DT, a)
+    y1 = y0 + k1 * DT2
+    k2 = derivs(y1, a)
+    y2 = y0 + k2 * DT2
+    k3 = derivs(y2, a)
+    y3 = y0 + k3 * DT
+    k4 = derivs(y3, a)
     n = y0 + (k1 + 2.0 * k2 + 2.0 * k3 + k4) * DT6
     out = np.stack([wrap(n[:, 0]), wrap(n[:, 1]), np.clip(n[:, 2], -MAX_VEL_1, MAX_VEL_1),
                     np.clip(n[:, 3], -MAX_VEL_2, MAX_VEL_2)], axis=1)
     height = -np.cos(out[:, 0]) - np.cos(out[:, 1] + out[:, 0])
+    if detail:
+        reach = np.abs(np.stack([y0[:, :2], y1[:, :2], y2[:, :2], y3[:, :2]])).max(axis=(0, 2))
+        return out, height, n[:, 2:4], n[:, 0:2], reach
     return out, height, n[:, 2:4]
 
 

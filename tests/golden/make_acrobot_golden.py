@@ -1,5 +1,5 @@
-"""TEST INFRASTRUCTURE ONLY -- writes tests/golden/acrobot_ref.npz: what the reference's own Acrobot sim.cpp computes,
-as data.  The reference file is compiled unchanged (tests/golden/acrobot_ref_driver.cpp includes it; the Madrona
+"""TEST INFRASTRUCTURE ONLY -- writes tests/golden/acrobot_ref.npz and acrobot_far_ref.npz: what the reference's own Acrobot
+sim.cpp computes, as data.  The reference file is compiled unchanged (tests/golden/acrobot_ref_driver.cpp includes it; the Madrona
 stand-in is oracle/madrona_standin with tests/golden/acrobot_standin in front for <madrona/math.hpp>) into a
 temporary directory; nothing of it is kept.
 
@@ -19,6 +19,21 @@ before every teacher-forced step, so its truncation never fires.  Arrays:
 
 Dropped before the sets are cut to size: every transition whose twin height -cos t1 - cos(t1 + t2) lies within 1e-3 of 1
 (the clamp set: within 0.2, and the twin must agree on the flag and overshoot the bound by 0.5).  *_dropped counts them.
+
+acrobot_far_ref.npz (generate_far): four sets of 512 one-step transitions from angles FAR outside [-pi, pi], which a caller
+may write into STATE and which take the step kernel's out-of-range paths (csrc/acrobot.hip: wrap_fast's second select,
+the per-world fallback to step_plain, wrap_plain's bounded loops and its one-piece wrap).  Velocities and actions as in
+`swing`; by draw index mod 3 theta1, theta2 or both are far, sign random, the other angle uniform in [-pi, pi]:
+
+    turns2  far |theta| in [10.5, 12]          the new angle is two turns off: within what the fast path wraps
+    turns3  far |theta| in [5 pi + 1, 120]     stage angles within the fast range, the new angle 3 .. 20 turns off
+    beyond  far |theta| in [130, 395]          stage angles beyond the fast range, at most 64 turns off
+    piece   far |theta| in [420, 2000]         more than 64 turns off: the reference loops on, the kernel wraps in one piece
+
+Same arrays per set as above (state, action, next, done, next64, tol, dropped), the band 1e-3 (piece: 1e-2: the reference is
+3.7e-3 from its twin there).  A draw must also lie ON its set's path by the float64 twin with a margin (on_path below:
+tests/test_ref_acrobot.py asserts the same of the stored inputs); *_offpath counts the draws that did not, e.g. a far
+angle of 10.5 whose velocity of -6 takes it below 3 pi.
 """
 import ctypes
 import os
@@ -34,10 +49,15 @@ sys.path.insert(0, os.path.join(REPO, "tests"))
 import acrobot_twin as twin  # noqa: E402
 
 OUT = os.path.join(HERE, "acrobot_ref.npz")
+OUT_FAR = os.path.join(HERE, "acrobot_far_ref.npz")
 FLAGS = ["-O2", "-fPIC", "-ffp-contract=off", "-std=c++17"]
 BATCH = 500
 FRESH, SET, CLAMP = 8192, 2048, 64
 BAND = 1e-3
+FAR_SET = 512
+FAR = (("turns2", 10.5, 12.0, 1e-3), ("turns3", 5 * np.pi + 1, 120.0, 1e-3), ("beyond", 130.0, 395.0, 1e-3), ("piece", 420.0, 2000.0, 1e-2))
+FAST_RANGE = 128.0                                  # csrc/acrobot.hip: kFastRange
+LOOP_END = twin.PI_F + 64 * 2 * twin.PI_F           # the largest value wrap_plain's 64 trips bring back into [-pi, pi]
 
 
 def default_reference_dir():
@@ -174,6 +194,57 @@ def finish_set(name, states, actions, nxt, done, out):
     out[name + "_next64"], out[name + "_tol"], out[name + "_dropped"] = n64, 4.0 * err, np.int64(dropped)
 
 
+def on_path(name, states, actions):
+    """which transitions take the path their set is named after, by the twin and with a margin: |new far angle| before the
+    wrap and the largest |stage angle| (the kernel's `reach`)"""
+    _, _, _, raw, reach = twin.step(states, actions, detail=True)
+    far = np.abs(np.asarray(states, np.float64)[:, :2]) > twin.PI_F
+    new = np.abs(raw)
+    lowest, highest = np.where(far, new, np.inf).min(axis=1), np.where(far, new, 0.0).max(axis=1)
+    if name == "turns2":
+        return (lowest > 3 * twin.PI_F + 0.05) & (highest < 5 * twin.PI_F - 0.05) & (reach < FAST_RANGE - 1)
+    if name == "turns3":
+        return (lowest > 5 * twin.PI_F + 0.05) & (reach < FAST_RANGE - 1)
+    if name == "beyond":
+        return (reach > FAST_RANGE + 1) & (highest < LOOP_END - 1)
+    return lowest > LOOP_END + 1
+
+
+def finish_far_set(name, count, band, states, actions, nxt, done, out):
+    """finish_set for a far set: drop what lies at the threshold (within `band`) or off the set's path, cut to `count`"""
+    n64, height, _ = twin.step(states, actions)
+    off_band, path = np.abs(height - 1.0) > band, on_path(name, states, actions)
+    assert ((height > 1.0) == (done != 0))[off_band].all(), name + ": the reference and its twin disagree on a done flag off the threshold"
+    idx = np.flatnonzero(off_band & path)[:count]
+    assert len(idx) == count, name + ": too few transitions left"
+    used = slice(0, idx[-1] + 1)
+    dropped, offpath = int((~off_band[used]).sum()), int((off_band & ~path)[used].sum())
+    states, actions, nxt, done, n64 = states[idx], actions[idx], nxt[idx], done[idx], n64[idx]
+    live = done == 0
+    err = twin.distance(nxt[live], n64[live]).max(axis=0)
+    out[name + "_state"], out[name + "_action"], out[name + "_next"], out[name + "_done"] = states, actions, nxt, done
+    out[name + "_next64"], out[name + "_tol"] = n64, 4.0 * err
+    out[name + "_dropped"], out[name + "_offpath"] = np.int64(dropped), np.int64(offpath)
+
+
+def generate_far(lib):
+    out = {}
+    for k, (name, lo, hi, band) in enumerate(FAR):
+        rng = np.random.default_rng(20250301 + k)
+        n = FAR_SET + 128
+        states = np.stack([rng.uniform(-np.pi, np.pi, n), rng.uniform(-np.pi, np.pi, n), rng.uniform(-3, 3, n),
+                           rng.uniform(-6, 6, n)], axis=1)
+        far = rng.choice([-1.0, 1.0], (n, 2)) * rng.uniform(lo, hi, (n, 2))
+        pattern = np.arange(n) % 3  # theta1 only, theta2 only, both
+        states[:, 0] = np.where(pattern != 1, far[:, 0], states[:, 0])
+        states[:, 1] = np.where(pattern != 0, far[:, 1], states[:, 1])
+        states = states.astype(np.float32)
+        actions = rng.integers(0, 3, n).astype(np.int32)
+        nxt, done = one_step(lib, states, actions)
+        finish_far_set(name, FAR_SET, band, states, actions, nxt, done, out)
+    return out
+
+
 def generate(lib):
     out = {}
     out["fresh"] = fresh_states(lib, 0, FRESH)
@@ -235,8 +306,14 @@ def generate(lib):
 def main():
     reference_dir = sys.argv[1] if len(sys.argv) > 1 else None
     with tempfile.TemporaryDirectory() as tmp:
-        out = generate(build_driver(tmp, reference_dir))
+        lib = build_driver(tmp, reference_dir)
+        out, far = generate(lib), generate_far(lib)
     np.savez_compressed(OUT, **out)
+    np.savez_compressed(OUT_FAR, **far)
+    for name, _, _, _ in FAR:
+        print(name, "tol", far[name + "_tol"], "dropped", int(far[name + "_dropped"]), "off path", int(far[name + "_offpath"]),
+              "done", int(far[name + "_done"].sum()))
+    print("->", OUT_FAR, os.path.getsize(OUT_FAR), "bytes")
     for name in ("reach", "swing"):
         print(name, "tol", out[name + "_tol"], "dropped", int(out[name + "_dropped"]), "done", int(out[name + "_done"].sum()))
     print("clamp: done", int(out["clamp_done"].sum()), "clamped components", int(out["clamp_mask"].sum()))

@@ -1,7 +1,8 @@
 """CPU: tests/golden/acrobot_ref.npz IS what the reference's own Acrobot sim.cpp computes (regenerated here from the
 reference tree when there is one, compiled unchanged: tests/golden/make_acrobot_golden.py), the float64 twin
 (tests/acrobot_twin.py) is as close to it as the fixture's tolerance says, and the reference's truncation is the per-world
-one of this engine at N = 1 only."""
+one of this engine at N = 1 only.  The same for tests/golden/acrobot_far_ref.npz, the transitions from far angles, whose
+inputs must also lie on the kernel paths they are named after."""
 import importlib.util
 import os
 import shutil
@@ -76,6 +77,87 @@ def test_twin_is_within_a_quarter_of_the_tolerance(golden):
         assert (err.max(axis=0) >= golden[name + "_tol"] / 4 * (1 - 1e-6)).all(), "the tolerance is the measured one"
     nxt, height, _ = twin.step(golden["clamp_state"], golden["clamp_action"])
     assert np.array_equal(height > 1.0, golden["clamp_done"] != 0)
+
+
+@pytest.fixture(scope="module")
+def far():
+    return load_golden("acrobot_far_ref.npz")
+
+
+FAR_SETS = [name for name, _, _, _ in gen.FAR]
+LOOP_END = twin.PI_F + 64 * 2 * twin.PI_F  # what the 64 trips of the kernel's wrap_plain still bring back into [-pi, pi]
+
+
+def test_far_fixture_is_what_the_reference_computes(ref_lib, far):
+    """acrobot_far_ref.npz, regenerated from the reference tree: the reference's arrays bit for bit, the twin's at 1e-9"""
+    fresh = gen.generate_far(ref_lib)
+    assert sorted(fresh) == sorted(far)
+    for key, want in far.items():
+        got = np.asarray(fresh[key])
+        assert got.shape == want.shape and got.dtype == want.dtype, key
+        if key.endswith(("_next64", "_tol")):
+            assert np.allclose(got, want, rtol=1e-9, atol=1e-15), key
+        else:
+            assert got.tobytes() == np.asarray(want).tobytes(), key
+
+
+@pytest.mark.parametrize("name", FAR_SETS)
+def test_far_twin_is_within_a_quarter_of_the_tolerance(name, far):
+    """as test_twin_is_within_a_quarter_of_the_tolerance: the twin reproduces tol / 4 as the largest distance, nothing left
+    out, and agrees on every done flag outside the set's band"""
+    band = dict((n, b) for n, _, _, b in gen.FAR)[name]
+    assert far[name + "_state"].shape == (512, 4) and far[name + "_state"].dtype == np.float32
+    assert far[name + "_next"].shape == (512, 4) and far[name + "_next64"].dtype == np.float64
+    nxt, height, _ = twin.step(far[name + "_state"], far[name + "_action"])
+    assert (np.abs(height - 1.0) > band).all()
+    assert np.array_equal(height > 1.0, far[name + "_done"] != 0)
+    assert np.allclose(nxt, far[name + "_next64"], rtol=1e-9, atol=1e-15)
+    live = far[name + "_done"] == 0
+    err = twin.distance(far[name + "_next"][live], nxt[live])
+    assert (err <= far[name + "_tol"] / 4 * (1 + 1e-6)).all()
+    assert (err.max(axis=0) >= far[name + "_tol"] / 4 * (1 - 1e-6)).all(), "the tolerance is the measured one"
+    assert (np.abs(far[name + "_next"][live][:, :2]) <= np.float32(np.pi)).all(), "the reference wrapped every live angle"
+    assert 0.05 < (~live).mean() < 0.30, "between 5 % and 30 % of the set finishes"
+    print(f"acrobot far {name}: reference to twin {far[name + '_tol'] / 4}, {int((~live).sum())} finished, "
+          f"{int(far[name + '_dropped'])} dropped at the threshold, {int(far[name + '_offpath'])} off the path")
+
+
+@pytest.mark.parametrize("name", FAR_SETS)
+def test_far_inputs_reach_their_path(name, far):
+    """What makes a set take its path through csrc/acrobot.hip is a property of its INPUTS, asserted from the twin with a
+    margin far above any float32 rounding of these angles (1.2e-4 at 2000): the new angle before the wrap against 3 pi,
+    5 pi (wrap_fast brings back two turns) and pi + 64 * 2 pi (wrap_plain's loops), and the largest stage angle against
+    kFastRange = 128."""
+    state, action = far[name + "_state"], far[name + "_action"]
+    lo, hi = dict((n, (a, b)) for n, a, b, _ in gen.FAR)[name]
+    is_far = np.abs(state[:, :2].astype(np.float64)) > twin.PI_F
+    assert is_far.any(axis=1).all()
+    assert ((np.abs(state[:, :2])[is_far] >= np.float32(lo)) & (np.abs(state[:, :2])[is_far] <= np.float32(hi))).all()
+    assert (np.abs(state[:, 2]) <= 3).all() and (np.abs(state[:, 3]) <= 6).all()
+    _, _, _, raw, reach = twin.step(state, action, detail=True)
+    assert (reach >= np.abs(state[:, :2]).max(axis=1)).all()
+    new = np.abs(raw)[is_far]                       # every far angle's new value
+    wide = np.repeat(reach, is_far.sum(axis=1))     # and its world's reach
+    if name == "turns2":
+        assert ((new > 3 * twin.PI_F + 0.05) & (new < 5 * twin.PI_F - 0.05)).all() and (wide < 127).all()
+    elif name == "turns3":
+        assert (new > 5 * twin.PI_F + 0.05).all() and (wide < 127).all()
+    elif name == "beyond":
+        assert (wide > 129).all() and (new < LOOP_END - 1).all()
+    else:
+        assert (new > LOOP_END + 1).all()
+    assert (np.abs(raw)[~is_far] < 3 * twin.PI_F - 0.05).all()  # the other angle: at most one turn off
+    assert np.array_equal(gen.on_path(name, state, action), np.ones(512, bool))
+    # theta1 only, theta2 only, both; every action; both signs
+    patterns = set(map(tuple, is_far.tolist()))
+    assert patterns == {(True, False), (False, True), (True, True)}
+    assert min((is_far == p).all(axis=1).sum() for p in patterns) > 100
+    assert set(np.unique(action)) == {0, 1, 2}
+    assert (state[:, :2][is_far] > 0).any() and (state[:, :2][is_far] < 0).any()
+
+
+def test_far_fixture_size():
+    assert os.path.getsize(os.path.join(GOLDEN, "acrobot_far_ref.npz")) < 256 * 1024
 
 
 def test_reference_truncation_at_one_world(ref_lib, golden):
