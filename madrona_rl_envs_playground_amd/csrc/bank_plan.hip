@@ -1,5 +1,4 @@
-// The plan of a bank act (bank_plan.hpp has the workspace layout; DESIGN.md sections 19 and 20), one copy for the banks of both
-// networks.
+// Every bank's plan of an act and, at the end, every bank's resample (bank_plan.hpp has the workspace; DESIGN.md sections 19 to 21).
 //
 // A cell s = n P + p is acted when seat p is in `players` and 0 <= ids[s] < K.  Pass one counts the acted cells of every policy,
 // chunks of 1024 cells at a time (a wave finds its distinct ids with ballots, one integer LDS add per id and wave); the counts
@@ -10,6 +9,7 @@
 // workgroup adds the chunks up and writes the table (mrl_bank_plan_scan), a workgroup per chunk places (mrl_bank_plan_place).
 // No workgroup waits for another inside a kernel.  Integer atomics in LDS only, no float atomics, no scratch.
 #include "bank_plan.hpp"
+#include "random_policy.hpp"
 
 namespace mrl {
 
@@ -219,6 +219,33 @@ void launch_bank_plan(const BankPlanArgs &plan, hipStream_t stream)
     hipLaunchKernelGGL(mrl_bank_plan_scan, dim3(1), dim3(kBankPlanThreads), 0, stream, plan, chunks);
     MRL_HIP(hipGetLastError());
     hipLaunchKernelGGL(mrl_bank_plan_place, dim3(chunks), dim3(kBankPlanThreads), 0, stream, plan);
+    MRL_HIP(hipGetLastError());
+}
+
+__global__ void __launch_bounds__(256) mrl_cnn_bank_resample_kernel(CnnResampleArgs a)
+{
+    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= a.num_worlds || a.done[n] == 0) return;
+    const uint32_t episode = (uint32_t)a.episodes[n] + 1u;
+    a.episodes[n] = (int32_t)episode;
+    for (uint32_t p = 0; p < a.P; p++) {
+        if (!((a.players >> p) & 1u)) continue;
+        const int32_t id = a.ids[(size_t)n * a.P + p];
+        if (id < 0) continue;
+        const uint32_t first = a.first[p], num = a.num[p];
+        uint32_t next;
+        if (a.mode == MRL_CNN_RESAMPLE_ROBIN)
+            next = first + ((uint32_t)id - first + 1u) % num;
+        else
+            next = first + (((policy_hash(a.seed, episode, n, p) >> 8) * num) >> 24);  // 24 bits times num <= 256: no overflow
+        a.ids[(size_t)n * a.P + p] = (int32_t)next;
+    }
+}
+
+void launch_cnn_bank_resample(const CnnResampleArgs &args, hipStream_t stream)
+{
+    if (args.num_worlds == 0) return;
+    hipLaunchKernelGGL(mrl_cnn_bank_resample_kernel, dim3((args.num_worlds + 255u) / 256u), dim3(256), 0, stream, args);
     MRL_HIP(hipGetLastError());
 }
 

@@ -1,6 +1,6 @@
-// The plan of a bank act, shared by the banks of both of MAPPO's actor-critics (mrl_cnn_act_bank in cnn_bank.hip,
-// mrl_mlpbase_act_bank in mlpbase_bank.hip; DESIGN.md sections 19 and 20): the acted cells of every policy gathered into that
-// policy's sample list, the lists cut into tiles of at most 32 samples.  The kernels live in bank_plan.hip.
+// What the three policy banks share below capi.hip (cnn_bank.hip, mlpbase_bank.hip, wide_bank.hip; DESIGN.md sections 19 to 21):
+// the plan of a bank act -- the acted cells of every policy gathered into that policy's sample list, the lists cut into tiles of at
+// most 32 samples --, the MAPPO banks' arguments and launcher, the tile table's reader and the resample.  Kernels: bank_plan.hip.
 //
 // THE WORKSPACE, in uint32 words (include/mrl_envs.h repeats this: a test reads it back).  M = N P cells, Kp = K rounded up to a
 // multiple of 4, max_tiles = ceil(M / 32) + K:
@@ -44,6 +44,37 @@ struct BankPlanArgs {
 // the plan on `stream`: one launch up to kBankPlanSingle cells, three beyond
 void launch_bank_plan(const BankPlanArgs &args, hipStream_t stream);
 
+// The bank's part of the arguments of mrl_cnn_act_bank and mrl_mlpbase_act_bank, behind the network's own act arguments
+struct BankActArgs {
+    const int32_t *ids;      // (N, P)
+    int32_t *ids_row;        // (N, P) or nullptr: k where the cell was acted, -1 elsewhere
+    uint32_t *workspace;     // the layout above
+    uint64_t stride;         // floats between two rows of the bank
+    uint32_t num_policies;
+};
+
+// A MAPPO bank act (`args`: an ActArgs `act` and `bank`) on `stream`: the plan, then KERNEL(args, layout) over the plan's tiles.
+// acted <= N * num_seats, so tiles <= ceil(N num_seats / 32) + K <= at.max_tiles: every workgroup's entry read lies in the table.
+template <auto KERNEL, class Args>
+inline void launch_act_bank(const Args &args, uint32_t threads, uint32_t lds_bytes, hipStream_t stream)
+{
+    const auto &a = args.act;
+    const BankActArgs &b = args.bank;
+    if ((uint64_t)a.num_worlds * a.P == 0 || a.nets == 0) return;
+    const BankLayout at = bank_layout(a.num_worlds, a.P, b.num_policies);
+    launch_bank_plan(BankPlanArgs{b.ids, b.ids_row, b.workspace, a.num_worlds * a.P, a.P, a.players, b.num_policies, at}, stream);
+    const uint64_t bound = ((uint64_t)a.num_worlds * a.num_seats + kBankTile - 1) / kBankTile + b.num_policies;
+    hipLaunchKernelGGL(KERNEL, dim3((uint32_t)bound, a.nets == 3u ? 2u : 1u), dim3(threads), lds_bytes, stream, args, at);
+    MRL_HIP(hipGetLastError());
+}
+
+// whether workgroup x has a tile, and its entry of the tile table (policy, first, rows, 0): inside the table whatever x, a tile's only then
+__device__ __forceinline__ bool bank_has_tile(const uint32_t *__restrict__ ws, uint32_t x) { return x < ws[0]; }
+__device__ __forceinline__ const uint32_t *bank_entry(const uint32_t *__restrict__ ws, uint64_t table_at, uint32_t x)
+{
+    return ws + table_at + 4u * (size_t)x;
+}
+
 // a tile of the plan as an act body's map: rows of one policy's list (Args: the act's arguments, for P)
 struct BankTileMap {
     const uint32_t *list;
@@ -64,5 +95,17 @@ struct BankTileMap {
         return true;
     }
 };
+
+// the resample of every bank, mrl_cnn_bank_resample_kernel: it reads DONE, the ids and the episodes only
+struct CnnResampleArgs {
+    const int32_t *done;     // DONE (N)
+    int32_t *ids;            // (N, P)
+    int32_t *episodes;       // (N)
+    uint64_t seed;
+    uint32_t num_worlds, P, players, mode;
+    uint16_t first[32], num[32];  // per seat
+};
+
+void launch_cnn_bank_resample(const CnnResampleArgs &args, hipStream_t stream);
 
 }  // namespace mrl

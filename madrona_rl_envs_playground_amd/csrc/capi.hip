@@ -179,6 +179,60 @@ static void completed_step(mrl_sim *sim, hipStream_t stream)
 // the counter games complete a two-phase step with phase 2; the kitchen games, whose phase 2 does nothing, with phase 1
 static bool completes_in_phase1(const mrl_sim *sim) { return sim->game == MRL_GAME_OVERCOOKED || sim->game == MRL_GAME_SIMPLECOOKED; }
 
+// The loop of every MAPPO rollout, on `stream` of the simulator's device: act(k, closing) for k = 0..T with the ordinary step, its
+// statistics and after_step() behind every act but the closing one.
+template <class Act, class AfterStep>
+static void rollout_loop(mrl_sim *sim, uint32_t T, hipStream_t stream, Act act, AfterStep after_step)
+{
+    for (uint32_t k = 0; k <= T; k++) {
+        const bool closing = k == T;
+        act(k, closing);
+        if (closing) break;
+        sim->step(nullptr, stream);
+        completed_step(sim, stream);
+        after_step();
+    }
+}
+
+// mrl_rollout_cnn and mrl_rollout_cnn_bank: rollout_loop with the simulator writing slot k + 1 of the observation ring in step k;
+// act(k, slot k, closing) reads its slot.
+template <class Act, class AfterStep>
+static int cnn_rollout_loop(mrl_sim *sim, const char *what, uint32_t T, void *obs_ring_dev, void *hip_stream, Act act, AfterStep after_step)
+{
+    DeviceGuard on(sim->device);
+    return guarded([&] {
+        hipStream_t stream = (hipStream_t)hip_stream;
+        const uint64_t slot_bytes = sim->observation_bytes();
+        uint8_t *ring = static_cast<uint8_t *>(obs_ring_dev);
+        const void *current = sim->observation_source();
+        if (!current || !slot_bytes) throw std::runtime_error(std::string(what) + ": the simulator has no observation slab");
+        if (current != ring) MRL_HIP(hipMemcpyAsync(ring, current, slot_bytes, hipMemcpyDeviceToDevice, stream));
+        const mrl_sim::ObservationRing before = sim->observation_ring();
+        struct HandBack {  // also when a launch throws
+            mrl_sim *sim;
+            const mrl_sim::ObservationRing &ring;
+            bool armed;
+            ~HandBack()
+            {
+                if (armed) sim->restore_observation_ring(ring);
+            }
+        } hand_back{sim, before, T > 0};
+        if (T) sim->set_observation_ring(ring + slot_bytes, slot_bytes, T);  // step k writes slot k + 1
+        rollout_loop(
+            sim, T, stream, [&](uint32_t k, bool closing) { act(k, reinterpret_cast<const int8_t *>(ring + (size_t)k * slot_bytes), closing); },
+            after_step);
+        if (T) {
+            // the output goes back to where it pointed, and that place receives slot T: the simulator's observations are then
+            // what T mrl_step_with_actions calls would have left there, and the next act or rollout reads them
+            hand_back.armed = false;
+            sim->restore_observation_ring(before);
+            void *home = const_cast<void *>(sim->observation_source());
+            const uint8_t *last = ring + (size_t)T * slot_bytes;
+            if (home != last) MRL_HIP(hipMemcpyAsync(home, last, slot_bytes, hipMemcpyDeviceToDevice, stream));
+        }
+    });
+}
+
 // ---- roofline.peak_measured of bench.py: float4 streams over caller buffers ----
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 template <int kMode>
@@ -230,6 +284,57 @@ __global__ void __launch_bounds__(256) mrl_probe_stream_two_pass_kernel(f32x4 *_
             if (early == (pass == 0)) asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(dst + i), "v"(fill) : "memory");
         }
     }
+}
+
+// What every bank act refuses behind its own network's checks: the bank's size and stride (`num_params`: the floats of one
+// policy), the ids, the cells of a call (`seats` per world; the plan numbers them) and the workspace of `need_bytes`, which is
+// what `sizer` returns.
+static int bank_refusal(const char *what, uint32_t num_worlds, uint32_t seats, uint32_t num_policies, uint64_t stride, uint64_t num_params,
+                        const int32_t *ids_dev, void *workspace_dev, uint64_t workspace_bytes, uint64_t need_bytes, const char *sizer)
+{
+    if (num_policies == 0 || num_policies > mrl::kBankMaxPolicies) {
+        mrl::set_error("%s: a bank holds 1 to %u policies, not %u", what, mrl::kBankMaxPolicies, num_policies);
+        return MRL_ERR_INVALID;
+    }
+    if (stride < num_params) {
+        mrl::set_error("%s: the bank's stride of %llu floats is below the policy's %llu parameters", what, (unsigned long long)stride,
+                       (unsigned long long)num_params);
+        return MRL_ERR_INVALID;
+    }
+    if (!ids_dev || (reinterpret_cast<uintptr_t>(ids_dev) & 3u)) {
+        mrl::set_error("%s: ids is null or off a 4-byte boundary", what);
+        return MRL_ERR_INVALID;
+    }
+    if ((uint64_t)num_worlds * seats > 0x7fffffffull) {
+        mrl::set_error("%s: %u worlds of %u seats are more cells than the plan numbers", what, num_worlds, seats);
+        return MRL_ERR_INVALID;
+    }
+    if (!workspace_dev || (reinterpret_cast<uintptr_t>(workspace_dev) & 15u) || workspace_bytes < need_bytes) {
+        mrl::set_error("%s: the workspace is null, off a 16-byte boundary or smaller than %s = %llu bytes", what, sizer,
+                       (unsigned long long)need_bytes);
+        return MRL_ERR_INVALID;
+    }
+    return MRL_OK;
+}
+
+// Everything the act and the rollout of a MAPPO bank (CnnBankArgs, MlpBaseBankArgs) check alike: prepare(), the network's own
+// checks with row 0 of the bank as the policy, which fills args->act; then bank_refusal with num_params(), the floats of one
+// policy, and `sizer`, the name of the entry point's own workspace function.  Fills args->bank but for the ids row.
+template <class Bank, class Args, class Prepare, class NumParams>
+static int bank_prepare(const char *what, const char *sizer, const Bank *bank, const int32_t *ids_dev, void *workspace_dev, uint64_t workspace_bytes, Args *args,
+                        Prepare prepare, NumParams num_params)
+{
+    if (!bank) {
+        set_error("%s: null bank", what);
+        return MRL_ERR_INVALID;
+    }
+    if (int rc = prepare()) return rc;
+    const ActArgs &a = args->act;
+    if (int rc = bank_refusal(what, a.num_worlds, a.P, bank->num_policies, bank->stride, num_params(), ids_dev, workspace_dev, workspace_bytes,
+                              mrl_cnn_bank_workspace_bytes(a.num_worlds, a.P, bank->num_policies), sizer))
+        return rc;
+    args->bank = BankActArgs{ids_dev, nullptr, static_cast<uint32_t *>(workspace_dev), bank->stride, bank->num_policies};
+    return MRL_OK;
 }
 
 }  // namespace mrl
@@ -1260,52 +1365,6 @@ int mrl_mappo_update(const mrl_mappo_policy *policy, const mrl_mappo_optimizer *
     });
 }
 
-// The loop of mrl_rollout_cnn and mrl_rollout_cnn_bank: act(k, slot k, closing) for k = 0..T with the ordinary step and
-// after_step(k) behind every act but the closing one, the simulator writing slot k + 1 through the observation ring.
-extern "C++" {
-template <class Act, class AfterStep>
-static int cnn_rollout_loop(mrl_sim *sim, const char *what, uint32_t T, void *obs_ring_dev, void *hip_stream, Act act, AfterStep after_step)
-{
-    mrl::DeviceGuard on(sim->device);
-    return mrl::guarded([&] {
-        hipStream_t stream = (hipStream_t)hip_stream;
-        const uint64_t slot_bytes = sim->observation_bytes();
-        uint8_t *ring = static_cast<uint8_t *>(obs_ring_dev);
-        const void *current = sim->observation_source();
-        if (!current || !slot_bytes) throw std::runtime_error(std::string(what) + ": the simulator has no observation slab");
-        if (current != ring) MRL_HIP(hipMemcpyAsync(ring, current, slot_bytes, hipMemcpyDeviceToDevice, stream));
-        const mrl_sim::ObservationRing before = sim->observation_ring();
-        struct HandBack {  // also when a launch throws
-            mrl_sim *sim;
-            const mrl_sim::ObservationRing &ring;
-            bool armed;
-            ~HandBack()
-            {
-                if (armed) sim->restore_observation_ring(ring);
-            }
-        } hand_back{sim, before, T > 0};
-        if (T) sim->set_observation_ring(ring + slot_bytes, slot_bytes, T);  // step k writes slot k + 1
-        for (uint32_t k = 0; k <= T; k++) {
-            const bool closing = k == T;
-            act(k, reinterpret_cast<const int8_t *>(ring + (size_t)k * slot_bytes), closing, stream);
-            if (closing) break;
-            sim->step(nullptr, stream);
-            mrl::completed_step(sim, stream);
-            after_step(k, stream);
-        }
-        if (T) {
-            // the output goes back to where it pointed, and that place receives slot T: the simulator's observations are then
-            // what T mrl_step_with_actions calls would have left there, and the next act or rollout reads them
-            hand_back.armed = false;
-            sim->restore_observation_ring(before);
-            void *home = const_cast<void *>(sim->observation_source());
-            const uint8_t *last = ring + (size_t)T * slot_bytes;
-            if (home != last) MRL_HIP(hipMemcpyAsync(home, last, slot_bytes, hipMemcpyDeviceToDevice, stream));
-        }
-    });
-}
-}  // extern "C++"
-
 int mrl_rollout_cnn(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, const mrl_cnn_record *record, void *obs_ring_dev,
                     uint64_t seed, uint32_t first_step, void *hip_stream)
 {
@@ -1316,92 +1375,24 @@ int mrl_rollout_cnn(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy
         return MRL_ERR_INVALID;
     }
     args.seed = seed;
-    return cnn_rollout_loop(
+    return mrl::cnn_rollout_loop(
         sim, "mrl_rollout_cnn", record->num_steps, obs_ring_dev, hip_stream,
-        [&](uint32_t k, const int8_t *obs, bool closing, hipStream_t stream) {
+        [&](uint32_t k, const int8_t *obs, bool closing) {
             args.obs = obs;
             record_rows(args, record, k, closing, mrl::kCnnActions);
             args.step = first_step + k;
             args.flags = policy->flags | (closing ? (uint32_t)MRL_CNN_VALUE_ONLY : 0u);
-            mrl::launch_cnn_act(args, stream);
+            mrl::launch_cnn_act(args, (hipStream_t)hip_stream);
         },
-        [](uint32_t, hipStream_t) {});
+        [] {});
 }
+
+// ---- the policy banks: what the three networks' banks (CNN, MLPBase, wide) check, fill and launch alike ----
 
 uint64_t mrl_cnn_bank_workspace_bytes(uint32_t num_worlds, uint32_t num_players, uint32_t num_policies)
 {
     if (num_policies == 0 || num_policies > mrl::kBankMaxPolicies) return 0;
     return mrl::bank_layout(num_worlds, num_players, num_policies).words * sizeof(uint32_t);
-}
-
-// What the bank acts of both networks refuse alike behind their own network's checks: the bank's size and stride (`num_params`: the
-// floats of one policy), the ids and the plan's workspace, for the simulator of `a`.
-static int bank_refusal(const char *what, const mrl::ActArgs &a, uint32_t num_policies, uint64_t stride, uint64_t num_params,
-                        const int32_t *ids_dev, void *workspace_dev, uint64_t workspace_bytes)
-{
-    if (num_policies == 0 || num_policies > mrl::kBankMaxPolicies) {
-        mrl::set_error("%s: a bank holds 1 to %u policies, not %u", what, mrl::kBankMaxPolicies, num_policies);
-        return MRL_ERR_INVALID;
-    }
-    if (stride < num_params) {
-        mrl::set_error("%s: the bank's stride of %llu floats is below the policy's %llu parameters", what, (unsigned long long)stride,
-                       (unsigned long long)num_params);
-        return MRL_ERR_INVALID;
-    }
-    if (!ids_dev || (reinterpret_cast<uintptr_t>(ids_dev) & 3u)) {
-        mrl::set_error("%s: ids is null or off a 4-byte boundary", what);
-        return MRL_ERR_INVALID;
-    }
-    if ((uint64_t)a.num_worlds * a.P > 0x7fffffffull) {
-        mrl::set_error("%s: %u worlds of %u seats are more cells than the plan numbers", what, a.num_worlds, a.P);
-        return MRL_ERR_INVALID;
-    }
-    if (!workspace_dev || (reinterpret_cast<uintptr_t>(workspace_dev) & 15u) ||
-        workspace_bytes < mrl_cnn_bank_workspace_bytes(a.num_worlds, a.P, num_policies)) {
-        mrl::set_error("%s: the workspace is null, off a 16-byte boundary or smaller than mrl_cnn_bank_workspace_bytes", what);
-        return MRL_ERR_INVALID;
-    }
-    return MRL_OK;
-}
-
-// Everything mrl_cnn_act_bank and mrl_rollout_cnn_bank check alike (cnn_prepare's checks and the bank's own); fills `args` but
-// for the observation pointer, the rows, the ids row, the seed, the step and the flags.
-static int cnn_bank_prepare(mrl_sim *sim, uint32_t players, const mrl_cnn_bank *bank, const int32_t *ids_dev, const mrl_cnn_record *record,
-                            void *workspace_dev, uint64_t workspace_bytes, void *hip_stream, const char *what, mrl::CnnBankArgs *args)
-{
-    if (!bank) {
-        mrl::set_error("%s: null bank", what);
-        return MRL_ERR_INVALID;
-    }
-    const mrl_cnn_policy row0{bank->params_dev, bank->hidden, bank->flags};
-    if (int rc = cnn_prepare(sim, players, &row0, record, hip_stream, what, &args->act)) return rc;
-    const mrl::CnnActArgs &a = args->act;
-    const uint64_t num_params = mrl_cnn_policy_num_params(a.W, a.H, a.F, mrl::kCnnHidden, mrl::kCnnActions);
-    if (int rc = bank_refusal(what, a, bank->num_policies, bank->stride, num_params, ids_dev, workspace_dev, workspace_bytes)) return rc;
-    args->ids = ids_dev, args->ids_row = nullptr;
-    args->workspace = static_cast<uint32_t *>(workspace_dev);
-    args->stride = bank->stride, args->num_policies = bank->num_policies;
-    return MRL_OK;
-}
-
-int mrl_cnn_act_bank(mrl_sim *sim, uint32_t players, const mrl_cnn_bank *bank, const int32_t *ids_dev, const mrl_cnn_record *record,
-                     int32_t *ids_row, uint32_t row, uint64_t seed, uint32_t step, uint32_t flags, void *workspace_dev,
-                     uint64_t workspace_bytes, void *hip_stream)
-{
-    mrl::CnnBankArgs args{};
-    if (int rc = cnn_bank_prepare(sim, players, bank, ids_dev, record, workspace_dev, workspace_bytes, hip_stream, "mrl_cnn_act_bank", &args))
-        return rc;
-    if (int rc = act_row_refusal("mrl_cnn_act_bank", "MRL_CNN_VALUE_ONLY", flags, bank->flags, record, row)) return rc;
-    const bool value_only = flags & MRL_CNN_VALUE_ONLY;
-    mrl::DeviceGuard on(sim->device);
-    return mrl::guarded([&] {
-        args.act.obs = static_cast<const int8_t *>(sim->observation_source());
-        if (!args.act.obs) throw std::runtime_error("mrl_cnn_act_bank: the simulator has no observation slab");
-        record_rows(args.act, record, row, value_only, mrl::kCnnActions);
-        args.act.seed = seed, args.act.step = step, args.act.flags = flags;
-        args.ids_row = ids_row;
-        mrl::launch_cnn_act_bank(args, (hipStream_t)hip_stream);
-    });
 }
 
 // the descriptor of a resample, whichever network's bank it serves
@@ -1441,72 +1432,137 @@ static int resample_fill(mrl_sim *sim, uint32_t players, uint32_t P, const mrl_t
     return MRL_OK;
 }
 
-// what mrl_cnn_bank_resample and mrl_rollout_cnn_bank check of a resample; fills `args` but for ids and episodes
-static int cnn_resample_prepare(mrl_sim *sim, uint32_t players, const mrl_cnn_resample *resample, const char *what, mrl::CnnResampleArgs *args)
+// A network family as a resample sees it: its games, a bit per MRL_GAME_* (`has`: what any other game is told), the slot of an
+// observation tensor and the axis of its shape that holds the seats, the slot of DONE (`tensors`: the two by name).
+struct BankFamily {
+    uint32_t games;
+    const char *has;
+    int obs_slot, seat_axis, done_slot;
+    const char *tensors;
+};
+static const BankFamily kCnnFamily{1u << MRL_GAME_OVERCOOKED | 1u << MRL_GAME_SIMPLECOOKED, "no CNN policy (Overcooked and Simplecooked do)",
+                                   MRL_OVERCOOKED_OBS_WORLD_MAJOR, 1, MRL_OVERCOOKED_DONE, "OBS_WORLD_MAJOR / DONE"};
+static const BankFamily kMlpBaseFamily{1u << MRL_GAME_BALANCE, "no MLPBase policy (the balance beam does)",
+                                       MRL_BALANCE_OBSERVATION, 0, MRL_BALANCE_DONE, "OBSERVATION / DONE"};
+// (the slot numbers are the same for both games)
+static const BankFamily kWideFamily{1u << MRL_GAME_HANABI | 1u << MRL_GAME_BALANCE, "no wide-policy agent (Hanabi and the balance beam do)",
+                                    MRL_HANABI_OBSERVATION, 0, MRL_HANABI_DONE, "OBSERVATION / DONE"};
+
+// What mrl_*_bank_resample and the bank rollouts check of a resample on a simulator of `family`; fills `args`.
+static int bank_resample_prepare(mrl_sim *sim, const BankFamily &family, uint32_t players, const mrl_cnn_resample *resample, int32_t *ids_dev,
+                                 int32_t *episodes_dev, const char *what, mrl::CnnResampleArgs *args)
 {
     if (int rc = mrl::need_healthy(sim)) return rc;
-    if (sim->game != MRL_GAME_OVERCOOKED && sim->game != MRL_GAME_SIMPLECOOKED) {
-        mrl::set_error("%s: game %d has no CNN policy (Overcooked and Simplecooked do)", what, sim->game);
+    if ((uint32_t)sim->game > 31u || !((family.games >> sim->game) & 1u)) {
+        mrl::set_error("%s: game %d has %s", what, sim->game, family.has);
         return MRL_ERR_INVALID;
     }
     if (int rc = resample_desc_refusal(resample, what)) return rc;
     mrl_tensor_desc obs{}, done{};
     int rc = mrl::guarded([&] {
-        if (!sim->tensor(MRL_OVERCOOKED_OBS_WORLD_MAJOR, &obs) || !sim->tensor(MRL_OVERCOOKED_DONE, &done))
-            throw std::runtime_error("the simulator does not export OBS_WORLD_MAJOR / DONE");
+        if (!sim->tensor(family.obs_slot, &obs) || !sim->tensor(family.done_slot, &done))
+            throw std::runtime_error(std::string("the simulator does not export ") + family.tensors);
     });
     if (rc) return rc;
-    return resample_fill(sim, players, (uint32_t)obs.shape[1], done, resample, what, args);
+    if (int rc2 = resample_fill(sim, players, (uint32_t)obs.shape[family.seat_axis], done, resample, what, args)) return rc2;
+    if (!ids_dev || !episodes_dev || ((reinterpret_cast<uintptr_t>(ids_dev) | reinterpret_cast<uintptr_t>(episodes_dev)) & 3u)) {
+        mrl::set_error("%s: a resample's ids or episodes is null or off a 4-byte boundary", what);
+        return MRL_ERR_INVALID;
+    }
+    args->ids = ids_dev, args->episodes = episodes_dev;
+    return MRL_OK;
+}
+
+// the three public resamples behind their family
+static int bank_resample(mrl_sim *sim, const BankFamily &family, uint32_t players, const mrl_cnn_resample *resample, int32_t *ids_dev,
+                         int32_t *episodes_dev, void *hip_stream, const char *what)
+{
+    mrl::CnnResampleArgs args{};
+    if (int rc = bank_resample_prepare(sim, family, players, resample, ids_dev, episodes_dev, what, &args)) return rc;
+    mrl::DeviceGuard on(sim->device);
+    return mrl::guarded([&] { mrl::launch_cnn_bank_resample(args, (hipStream_t)hip_stream); });
 }
 
 int mrl_cnn_bank_resample(mrl_sim *sim, uint32_t players, const mrl_cnn_resample *resample, int32_t *ids_dev, int32_t *episodes_dev,
                           void *hip_stream)
 {
-    mrl::CnnResampleArgs args{};
-    if (int rc = cnn_resample_prepare(sim, players, resample, "mrl_cnn_bank_resample", &args)) return rc;
-    if (!ids_dev || !episodes_dev || ((reinterpret_cast<uintptr_t>(ids_dev) | reinterpret_cast<uintptr_t>(episodes_dev)) & 3u)) {
-        mrl::set_error("mrl_cnn_bank_resample: ids or episodes is null or off a 4-byte boundary");
-        return MRL_ERR_INVALID;
-    }
-    args.ids = ids_dev, args.episodes = episodes_dev;
+    return bank_resample(sim, kCnnFamily, players, resample, ids_dev, episodes_dev, hip_stream, "mrl_cnn_bank_resample");
+}
+
+int mrl_mlpbase_bank_resample(mrl_sim *sim, uint32_t players, const mrl_cnn_resample *resample, int32_t *ids_dev, int32_t *episodes_dev,
+                              void *hip_stream)
+{
+    return bank_resample(sim, kMlpBaseFamily, players, resample, ids_dev, episodes_dev, hip_stream, "mrl_mlpbase_bank_resample");
+}
+
+int mrl_agent_bank_resample(mrl_sim *sim, uint32_t players, const mrl_cnn_resample *resample, int32_t *ids_dev, int32_t *episodes_dev,
+                            void *hip_stream)
+{
+    return bank_resample(sim, kWideFamily, players, resample, ids_dev, episodes_dev, hip_stream, "mrl_agent_bank_resample");
+}
+
+// Everything mrl_cnn_act_bank and mrl_rollout_cnn_bank check alike (cnn_prepare's checks and the bank's own); fills `args` but
+// for the observation pointer, the rows, the ids row, the seed, the step and the flags.
+static int cnn_bank_prepare(mrl_sim *sim, uint32_t players, const mrl_cnn_bank *bank, const int32_t *ids_dev, const mrl_cnn_record *record,
+                            void *workspace_dev, uint64_t workspace_bytes, void *hip_stream, const char *what, mrl::CnnBankArgs *args)
+{
+    return mrl::bank_prepare(
+        what, "mrl_cnn_bank_workspace_bytes", bank, ids_dev, workspace_dev, workspace_bytes, args,
+        [&] {
+            const mrl_cnn_policy row0{bank->params_dev, bank->hidden, bank->flags};
+            return cnn_prepare(sim, players, &row0, record, hip_stream, what, &args->act);
+        },
+        [&] { return mrl_cnn_policy_num_params(args->act.W, args->act.H, args->act.F, mrl::kCnnHidden, mrl::kCnnActions); });
+}
+
+int mrl_cnn_act_bank(mrl_sim *sim, uint32_t players, const mrl_cnn_bank *bank, const int32_t *ids_dev, const mrl_cnn_record *record,
+                     int32_t *ids_row, uint32_t row, uint64_t seed, uint32_t step, uint32_t flags, void *workspace_dev,
+                     uint64_t workspace_bytes, void *hip_stream)
+{
+    mrl::CnnBankArgs args{};
+    if (int rc = cnn_bank_prepare(sim, players, bank, ids_dev, record, workspace_dev, workspace_bytes, hip_stream, "mrl_cnn_act_bank", &args))
+        return rc;
+    if (int rc = act_row_refusal("mrl_cnn_act_bank", "MRL_CNN_VALUE_ONLY", flags, bank->flags, record, row)) return rc;
+    const bool value_only = flags & MRL_CNN_VALUE_ONLY;
     mrl::DeviceGuard on(sim->device);
-    return mrl::guarded([&] { mrl::launch_cnn_bank_resample(args, (hipStream_t)hip_stream); });
+    return mrl::guarded([&] {
+        args.act.obs = static_cast<const int8_t *>(sim->observation_source());
+        if (!args.act.obs) throw std::runtime_error("mrl_cnn_act_bank: the simulator has no observation slab");
+        record_rows(args.act, record, row, value_only, mrl::kCnnActions);
+        args.act.seed = seed, args.act.step = step, args.act.flags = flags;
+        args.bank.ids_row = ids_row;
+        mrl::launch_cnn_act_bank(args, (hipStream_t)hip_stream);
+    });
 }
 
 int mrl_rollout_cnn_bank(mrl_sim *sim, uint32_t players, const mrl_cnn_bank *bank, int32_t *ids_dev, int32_t *episodes_dev,
                          const mrl_cnn_resample *resample, const mrl_cnn_record *record, int32_t *ids_record, void *obs_ring_dev, uint64_t seed,
                          uint32_t first_step, void *workspace_dev, uint64_t workspace_bytes, void *hip_stream)
 {
+    const char *what = "mrl_rollout_cnn_bank";
     mrl::CnnBankArgs args{};
-    if (int rc = cnn_bank_prepare(sim, players, bank, ids_dev, record, workspace_dev, workspace_bytes, hip_stream, "mrl_rollout_cnn_bank", &args))
-        return rc;
+    if (int rc = cnn_bank_prepare(sim, players, bank, ids_dev, record, workspace_dev, workspace_bytes, hip_stream, what, &args)) return rc;
     if (!record || !obs_ring_dev) {
-        mrl::set_error("mrl_rollout_cnn_bank: null record or observation ring");
+        mrl::set_error("%s: null record or observation ring", what);
         return MRL_ERR_INVALID;
     }
     mrl::CnnResampleArgs again{};
-    if (resample) {
-        if (int rc = cnn_resample_prepare(sim, players, resample, "mrl_rollout_cnn_bank", &again)) return rc;
-        if (!episodes_dev || (reinterpret_cast<uintptr_t>(episodes_dev) & 3u)) {
-            mrl::set_error("mrl_rollout_cnn_bank: a resample needs episodes, on a 4-byte boundary");
-            return MRL_ERR_INVALID;
-        }
-        again.ids = ids_dev, again.episodes = episodes_dev;
-    }
+    if (resample)
+        if (int rc = bank_resample_prepare(sim, kCnnFamily, players, resample, ids_dev, episodes_dev, what, &again)) return rc;
     args.act.seed = seed;
     const size_t cells = (size_t)args.act.num_worlds * args.act.P;
-    return cnn_rollout_loop(
-        sim, "mrl_rollout_cnn_bank", record->num_steps, obs_ring_dev, hip_stream,
-        [&](uint32_t k, const int8_t *obs, bool closing, hipStream_t stream) {
+    return mrl::cnn_rollout_loop(
+        sim, what, record->num_steps, obs_ring_dev, hip_stream,
+        [&](uint32_t k, const int8_t *obs, bool closing) {
             args.act.obs = obs;
             record_rows(args.act, record, k, closing, mrl::kCnnActions);
             args.act.step = first_step + k;
             args.act.flags = bank->flags | (closing ? (uint32_t)MRL_CNN_VALUE_ONLY : 0u);
-            args.ids_row = ids_record ? ids_record + (size_t)k * cells : nullptr;
-            mrl::launch_cnn_act_bank(args, stream);
+            args.bank.ids_row = ids_record ? ids_record + (size_t)k * cells : nullptr;
+            mrl::launch_cnn_act_bank(args, (hipStream_t)hip_stream);
         },
-        [&](uint32_t, hipStream_t stream) {
-            if (resample) mrl::launch_cnn_bank_resample(again, stream);
+        [&] {
+            if (resample) mrl::launch_cnn_bank_resample(again, (hipStream_t)hip_stream);
         });
 }
 
@@ -1597,21 +1653,18 @@ int mrl_rollout_mlpbase(mrl_sim *sim, uint32_t players, const mrl_mlpbase_policy
         mrl::set_error("mrl_rollout_mlpbase: null record");
         return MRL_ERR_INVALID;
     }
+    args.seed = seed;
     mrl::DeviceGuard on(sim->device);
     return mrl::guarded([&] {
-        hipStream_t stream = (hipStream_t)hip_stream;
-        const uint32_t T = record->num_steps;
-        args.seed = seed;
-        for (uint32_t k = 0; k <= T; k++) {
-            const bool closing = k == T;
-            mlpbase_rows(args, record, k, closing);
-            args.step = first_step + k;
-            args.flags = policy->flags | (closing ? (uint32_t)MRL_MLPBASE_VALUE_ONLY : 0u);
-            mrl::launch_mlpbase_act(args, stream);
-            if (closing) break;
-            sim->step(nullptr, stream);
-            mrl::completed_step(sim, stream);
-        }
+        mrl::rollout_loop(
+            sim, record->num_steps, (hipStream_t)hip_stream,
+            [&](uint32_t k, bool closing) {
+                mlpbase_rows(args, record, k, closing);
+                args.step = first_step + k;
+                args.flags = policy->flags | (closing ? (uint32_t)MRL_MLPBASE_VALUE_ONLY : 0u);
+                mrl::launch_mlpbase_act(args, (hipStream_t)hip_stream);
+            },
+            [] {});
     });
 }
 
@@ -1621,19 +1674,13 @@ static int mlpbase_bank_prepare(mrl_sim *sim, uint32_t players, const mrl_mlpbas
                                 const mrl_mlpbase_record *record, void *workspace_dev, uint64_t workspace_bytes, void *hip_stream,
                                 const char *what, mrl::MlpBaseBankArgs *args)
 {
-    if (!bank) {
-        mrl::set_error("%s: null bank", what);
-        return MRL_ERR_INVALID;
-    }
-    const mrl_mlpbase_policy row0{bank->params_dev, bank->hidden, bank->layer_N, bank->flags};
-    if (int rc = mlpbase_prepare(sim, players, &row0, record, hip_stream, what, &args->act)) return rc;
-    const mrl::MlpBaseActArgs &a = args->act;
-    const uint64_t num_params = mrl_mlpbase_policy_num_params(mrl::kMlpBaseObs, mrl::kMlpBaseHidden, bank->layer_N, mrl::kMlpBaseActions);
-    if (int rc = bank_refusal(what, a, bank->num_policies, bank->stride, num_params, ids_dev, workspace_dev, workspace_bytes)) return rc;
-    args->ids = ids_dev, args->ids_row = nullptr;
-    args->workspace = static_cast<uint32_t *>(workspace_dev);
-    args->stride = bank->stride, args->num_policies = bank->num_policies;
-    return MRL_OK;
+    return mrl::bank_prepare(
+        what, "mrl_mlpbase_bank_workspace_bytes", bank, ids_dev, workspace_dev, workspace_bytes, args,
+        [&] {
+            const mrl_mlpbase_policy row0{bank->params_dev, bank->hidden, bank->layer_N, bank->flags};
+            return mlpbase_prepare(sim, players, &row0, record, hip_stream, what, &args->act);
+        },
+        [&] { return mrl_mlpbase_policy_num_params(mrl::kMlpBaseObs, mrl::kMlpBaseHidden, bank->layer_N, mrl::kMlpBaseActions); });
 }
 
 uint64_t mrl_mlpbase_bank_workspace_bytes(uint32_t num_worlds, uint32_t num_policies)
@@ -1659,87 +1706,45 @@ int mrl_mlpbase_act_bank(mrl_sim *sim, uint32_t players, const mrl_mlpbase_bank 
     return mrl::guarded([&] {
         mlpbase_rows(args.act, record, row, value_only);
         args.act.seed = seed, args.act.step = step, args.act.flags = flags;
-        args.ids_row = ids_row;
+        args.bank.ids_row = ids_row;
         mrl::launch_mlpbase_act_bank(args, (hipStream_t)hip_stream);
     });
-}
-
-// what mrl_mlpbase_bank_resample and mrl_rollout_mlpbase_bank check of a resample; fills `args` but for ids and episodes
-static int mlpbase_resample_prepare(mrl_sim *sim, uint32_t players, const mrl_cnn_resample *resample, const char *what,
-                                    mrl::CnnResampleArgs *args)
-{
-    if (int rc = mrl::need_healthy(sim)) return rc;
-    if (sim->game != MRL_GAME_BALANCE) {
-        mrl::set_error("%s: game %d has no MLPBase policy (the balance beam does)", what, sim->game);
-        return MRL_ERR_INVALID;
-    }
-    if (int rc = resample_desc_refusal(resample, what)) return rc;
-    mrl_tensor_desc obs{}, done{};
-    int rc = mrl::guarded([&] {
-        if (!sim->tensor(MRL_BALANCE_OBSERVATION, &obs) || !sim->tensor(MRL_BALANCE_DONE, &done))
-            throw std::runtime_error("the simulator does not export OBSERVATION / DONE");
-    });
-    if (rc) return rc;
-    return resample_fill(sim, players, (uint32_t)obs.shape[0], done, resample, what, args);
-}
-
-int mrl_mlpbase_bank_resample(mrl_sim *sim, uint32_t players, const mrl_cnn_resample *resample, int32_t *ids_dev, int32_t *episodes_dev,
-                              void *hip_stream)
-{
-    mrl::CnnResampleArgs args{};
-    if (int rc = mlpbase_resample_prepare(sim, players, resample, "mrl_mlpbase_bank_resample", &args)) return rc;
-    if (!ids_dev || !episodes_dev || ((reinterpret_cast<uintptr_t>(ids_dev) | reinterpret_cast<uintptr_t>(episodes_dev)) & 3u)) {
-        mrl::set_error("mrl_mlpbase_bank_resample: ids or episodes is null or off a 4-byte boundary");
-        return MRL_ERR_INVALID;
-    }
-    args.ids = ids_dev, args.episodes = episodes_dev;
-    mrl::DeviceGuard on(sim->device);
-    return mrl::guarded([&] { mrl::launch_cnn_bank_resample(args, (hipStream_t)hip_stream); });
 }
 
 int mrl_rollout_mlpbase_bank(mrl_sim *sim, uint32_t players, const mrl_mlpbase_bank *bank, int32_t *ids_dev, int32_t *episodes_dev,
                              const mrl_cnn_resample *resample, const mrl_mlpbase_record *record, int32_t *ids_record, uint64_t seed,
                              uint32_t first_step, void *workspace_dev, uint64_t workspace_bytes, void *hip_stream)
 {
+    const char *what = "mrl_rollout_mlpbase_bank";
     mrl::MlpBaseBankArgs args{};
-    if (int rc = mlpbase_bank_prepare(sim, players, bank, ids_dev, record, workspace_dev, workspace_bytes, hip_stream,
-                                      "mrl_rollout_mlpbase_bank", &args))
-        return rc;
+    if (int rc = mlpbase_bank_prepare(sim, players, bank, ids_dev, record, workspace_dev, workspace_bytes, hip_stream, what, &args)) return rc;
     if (!record) {
-        mrl::set_error("mrl_rollout_mlpbase_bank: null record");
+        mrl::set_error("%s: null record", what);
         return MRL_ERR_INVALID;
     }
     if (reinterpret_cast<uintptr_t>(ids_record) & 3u) {
-        mrl::set_error("mrl_rollout_mlpbase_bank: ids_record is off a 4-byte boundary");
+        mrl::set_error("%s: ids_record is off a 4-byte boundary", what);
         return MRL_ERR_INVALID;
     }
     mrl::CnnResampleArgs again{};
-    if (resample) {
-        if (int rc = mlpbase_resample_prepare(sim, players, resample, "mrl_rollout_mlpbase_bank", &again)) return rc;
-        if (!episodes_dev || (reinterpret_cast<uintptr_t>(episodes_dev) & 3u)) {
-            mrl::set_error("mrl_rollout_mlpbase_bank: a resample needs episodes, on a 4-byte boundary");
-            return MRL_ERR_INVALID;
-        }
-        again.ids = ids_dev, again.episodes = episodes_dev;
-    }
+    if (resample)
+        if (int rc = bank_resample_prepare(sim, kMlpBaseFamily, players, resample, ids_dev, episodes_dev, what, &again)) return rc;
+    args.act.seed = seed;
+    const size_t cells = (size_t)args.act.num_worlds * args.act.P;
     mrl::DeviceGuard on(sim->device);
     return mrl::guarded([&] {
-        hipStream_t stream = (hipStream_t)hip_stream;
-        const uint32_t T = record->num_steps;
-        const size_t cells = (size_t)args.act.num_worlds * args.act.P;
-        args.act.seed = seed;
-        for (uint32_t k = 0; k <= T; k++) {
-            const bool closing = k == T;
-            mlpbase_rows(args.act, record, k, closing);
-            args.act.step = first_step + k;
-            args.act.flags = bank->flags | (closing ? (uint32_t)MRL_MLPBASE_VALUE_ONLY : 0u);
-            args.ids_row = ids_record ? ids_record + (size_t)k * cells : nullptr;
-            mrl::launch_mlpbase_act_bank(args, stream);
-            if (closing) break;
-            sim->step(nullptr, stream);
-            mrl::completed_step(sim, stream);
-            if (resample) mrl::launch_cnn_bank_resample(again, stream);
-        }
+        mrl::rollout_loop(
+            sim, record->num_steps, (hipStream_t)hip_stream,
+            [&](uint32_t k, bool closing) {
+                mlpbase_rows(args.act, record, k, closing);
+                args.act.step = first_step + k;
+                args.act.flags = bank->flags | (closing ? (uint32_t)MRL_MLPBASE_VALUE_ONLY : 0u);
+                args.bank.ids_row = ids_record ? ids_record + (size_t)k * cells : nullptr;
+                mrl::launch_mlpbase_act_bank(args, (hipStream_t)hip_stream);
+            },
+            [&] {
+                if (resample) mrl::launch_cnn_bank_resample(again, (hipStream_t)hip_stream);
+            });
     });
 }
 
@@ -1771,23 +1776,13 @@ int mrl_agent_act_bank(mrl_sim *sim, uint32_t player, const mrl_wide_bank *bank,
         return MRL_ERR_INVALID;
     }
     const uint32_t K = bank->num_policies, N = sim->num_worlds;
-    if (K == 0 || K > mrl::kBankMaxPolicies) {
-        mrl::set_error("%s: a bank holds 1 to %u policies, not %u", what, mrl::kBankMaxPolicies, K);
-        return MRL_ERR_INVALID;
-    }
-    const uint64_t num_params = mrl_wide_policy_num_params(bank->obs_dim, bank->state_dim, bank->num_actions);
-    if (bank->stride < num_params) {
-        mrl::set_error("%s: the bank's stride of %llu floats is below the policy's %llu parameters", what, (unsigned long long)bank->stride,
-                       (unsigned long long)num_params);
-        return MRL_ERR_INVALID;
-    }
-    if (!ids_dev || ((reinterpret_cast<uintptr_t>(ids_dev) | reinterpret_cast<uintptr_t>(ids_row)) & 3u)) {
-        mrl::set_error("%s: ids is null, or ids or ids_row is off a 4-byte boundary", what);
-        return MRL_ERR_INVALID;
-    }
-    if (workspace_bytes < mrl::wide_bank_workspace_bytes(N, K)) {
-        mrl::set_error("%s: the workspace of %llu bytes is smaller than mrl_agent_bank_workspace_bytes = %llu", what,
-                       (unsigned long long)workspace_bytes, (unsigned long long)mrl::wide_bank_workspace_bytes(N, K));
+    // (one seat acts in a call: N cells)
+    if (int rc = mrl::bank_refusal(what, N, 1, K, bank->stride, mrl_wide_policy_num_params(bank->obs_dim, bank->state_dim, bank->num_actions),
+                                   ids_dev, workspace_dev, workspace_bytes, mrl::wide_bank_workspace_bytes(N, K),
+                                   "mrl_agent_bank_workspace_bytes"))
+        return rc;
+    if (reinterpret_cast<uintptr_t>(ids_row) & 3u) {
+        mrl::set_error("%s: ids_row is off a 4-byte boundary", what);
         return MRL_ERR_INVALID;
     }
     mrl::DeviceGuard on(sim->device);
@@ -1801,34 +1796,6 @@ int mrl_agent_act_bank(mrl_sim *sim, uint32_t player, const mrl_wide_bank *bank,
         args.stride = bank->stride, args.num_policies = K;
         mrl::launch_agent_act_bank(args, (hipStream_t)hip_stream);
     });
-}
-
-int mrl_agent_bank_resample(mrl_sim *sim, uint32_t players, const mrl_cnn_resample *resample, int32_t *ids_dev, int32_t *episodes_dev,
-                            void *hip_stream)
-{
-    const char *what = "mrl_agent_bank_resample";
-    if (int rc = mrl::need_healthy(sim)) return rc;
-    if (sim->game != MRL_GAME_HANABI && sim->game != MRL_GAME_BALANCE) {
-        mrl::set_error("%s: game %d has no wide-policy agent (Hanabi and the balance beam do)", what, sim->game);
-        return MRL_ERR_INVALID;
-    }
-    if (int rc = resample_desc_refusal(resample, what)) return rc;
-    mrl_tensor_desc obs{}, done{};
-    int rc = mrl::guarded([&] {
-        // (the slot numbers are the same for both games)
-        if (!sim->tensor(MRL_HANABI_OBSERVATION, &obs) || !sim->tensor(MRL_HANABI_DONE, &done))
-            throw std::runtime_error("the simulator does not export OBSERVATION / DONE");
-    });
-    if (rc) return rc;
-    mrl::CnnResampleArgs args{};
-    if (int rc2 = resample_fill(sim, players, (uint32_t)obs.shape[0], done, resample, what, &args)) return rc2;
-    if (!ids_dev || !episodes_dev || ((reinterpret_cast<uintptr_t>(ids_dev) | reinterpret_cast<uintptr_t>(episodes_dev)) & 3u)) {
-        mrl::set_error("%s: ids or episodes is null or off a 4-byte boundary", what);
-        return MRL_ERR_INVALID;
-    }
-    args.ids = ids_dev, args.episodes = episodes_dev;
-    mrl::DeviceGuard on(sim->device);
-    return mrl::guarded([&] { mrl::launch_cnn_bank_resample(args, (hipStream_t)hip_stream); });
 }
 
 // what mrl_mappo_mlp_workspace_bytes and mrl_mappo_mlp_update refuse alike: nullptr when the shape can run, else why not

@@ -36,14 +36,14 @@ __global__ void __launch_bounds__(256) mrl_wide_bank_ids(WideInput active, const
     }
 }
 
-// The plan's table as the layer kernel's map: workgroup x takes entry x -- (policy, first, rows, 0) -- and has no tile when x >=
-// tiles (the grid is sized for max_tiles, the table too, so the entry read lies inside the workspace whatever it holds).
+// The plan's table as the layer kernel's map: workgroup x takes bank_entry's entry x -- (policy, first, rows, 0) -- and has no tile
+// when x >= tiles (the grid is sized for max_tiles, the table too, so the entry read lies inside the workspace whatever it holds).
 struct WideBankTiles {
     const uint32_t *plan;  // bank_plan.hpp's words
     uint64_t table_at;     // word offset of the tile table
     uint64_t stride;       // floats between two rows of the bank
-    __device__ __forceinline__ const uint32_t *entry() const { return plan + table_at + 4u * (size_t)blockIdx.x; }
-    __device__ __forceinline__ uint32_t end(const WideLayerArgs &) const { return blockIdx.x < plan[0] ? entry()[1] + entry()[2] : 0u; }
+    __device__ __forceinline__ const uint32_t *entry() const { return bank_entry(plan, table_at, blockIdx.x); }
+    __device__ __forceinline__ uint32_t end(const WideLayerArgs &) const { return bank_has_tile(plan, blockIdx.x) ? entry()[1] + entry()[2] : 0u; }
     __device__ __forceinline__ uint32_t first() const { return entry()[1]; }
     __device__ __forceinline__ size_t shift() const { return (size_t)entry()[0] * stride; }
 };

@@ -1,11 +1,11 @@
 // A bank of K wide policies (CleanPPOAgent's two 512-wide four-layer MLPs) and a policy per world for one seat of Hanabi or the
 // balance beam (C ABI: mrl_agent_act_bank, mrl_agent_bank_resample, mrl_agent_bank_workspace_bytes in include/mrl_envs.h;
-// DESIGN.md section 21).  The kernels live in wide_bank.hip; capi.hip validates.
+// DESIGN.md section 21).  The kernels live in wide_bank.hip; capi.hip validates, with every bank's bank_refusal and bank_resample.
 //
 // An act is the effective ids (ids[n, player] where the world is computed, -1 elsewhere), the plan over them (bank_plan.hpp: the
 // other banks' own, with P = 1 and N cells), mrl_wide_layer's body (wide_layer_body.hpp) over the plan's tiles, four launches,
-// each tile under its own policy's row of the bank, and mrl_agent_head's body over the list positions [0, acted).  The resample
-// is the CNN bank's kernel (cnn_bank.hpp), which reads DONE, the ids and the episodes only.
+// each tile (bank_entry's entry) under its own policy's row of the bank, and mrl_agent_head's body over the list positions
+// [0, acted).  The resample is every bank's kernel (bank_plan.hpp), which reads DONE, the ids and the episodes only.
 //
 // THE WORKSPACE (include/mrl_envs.h repeats this: a test reads it back): mrl_agent_act's workspace first, wide_workspace_bytes(N)
 // bytes, of which the activations, the logits and the values are used, indexed by position in the plan's lists; then eff, N int32

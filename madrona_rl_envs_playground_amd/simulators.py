@@ -505,20 +505,18 @@ def cnn_act(sim, policy, players=None, record=None, row=0, seed=0, step=0, greed
         _lib.check(rc)
 
 
-class CnnPolicyBank:
-    """K ``CnnPolicy`` of one shape in one dense float32 tensor ``params`` (K, num_params) (``mrl_cnn_bank``): row k is exactly
-    what a ``CnnPolicy``'s ``params`` is.  ``policy(k)`` is a ``CnnPolicy`` whose ``params`` IS row k, a contiguous view, so
-    ``cnn_act``, ``MappoOptimizer``, ``mappo_update`` and ``.module()`` work on a member unchanged and training a member is what the
-    next ``cnn_act_bank`` reads.  1 <= K <= 256."""
+class _PolicyBank:
+    """What ``CnnPolicyBank``, ``MlpBasePolicyBank`` and ``WidePolicyBank`` share: K policies of one shape in one dense float32
+    tensor ``params`` (K, num_params) whose row k is exactly a member's ``params``, and the members as views of their rows.  A
+    subclass names its member class (``_member_class``) and the shape fields (``_shape``) that are the member's attributes and its
+    own constructor's keywords; its constructor sets them and hands over to this one; ``_count_params`` gives the floats of one
+    policy and refuses a shape the kernels do not run."""
 
-    def __init__(self, width, height, channels, num_policies, hidden=64, num_actions=6, device="cuda:0"):
-        self.width, self.height, self.channels, self.hidden, self.num_actions = int(width), int(height), int(channels), int(hidden), int(num_actions)
+    def __init__(self, num_policies, device):
         self.num_policies = int(num_policies)
         if not 1 <= self.num_policies <= _lib.CNN_BANK_MAX_POLICIES:
             raise ValueError(f"a bank holds 1 to {_lib.CNN_BANK_MAX_POLICIES} policies, not {num_policies}")
-        self.num_params = int(_lib.lib().mrl_cnn_policy_num_params(self.width, self.height, self.channels, self.hidden, self.num_actions))
-        if self.num_params == 0:
-            raise ValueError(f"mrl_cnn_act runs hidden = {_lib.CNN_HIDDEN}, num_actions = {_lib.CNN_ACTIONS} and kitchens of at least 3 x 3")
+        self.num_params = self._count_params()
         self.params = torch.zeros((self.num_policies, self.num_params), dtype=torch.float32, device=torch.device(device))
         self._members = {}
 
@@ -526,15 +524,15 @@ class CnnPolicyBank:
         return self.num_policies
 
     def policy(self, k):
-        """The ``CnnPolicy`` whose ``params`` is row ``k`` of the bank (one object per row)."""
+        """The member (a ``_member_class``) whose ``params`` is row ``k`` of the bank (one object per row)."""
         k = int(k)
         if not 0 <= k < self.num_policies:
             raise IndexError(f"the bank holds policies 0..{self.num_policies - 1}, not {k}")
         member = self._members.get(k)
         if member is None:
-            member = CnnPolicy.__new__(CnnPolicy)
-            member.width, member.height, member.channels, member.hidden, member.num_actions = (self.width, self.height, self.channels,
-                                                                                               self.hidden, self.num_actions)
+            member = self._member_class.__new__(self._member_class)
+            for name in self._shape:
+                setattr(member, name, getattr(self, name))
             member.params = self.params[k]
             member._module = None
             self._members[k] = member
@@ -542,19 +540,44 @@ class CnnPolicyBank:
 
     @classmethod
     def from_policies(cls, policies, device=None):
-        """A bank holding copies of ``policies`` (``CnnPolicy`` of one shape), in that order (``device``: default the first one's)."""
+        """A bank holding copies of ``policies`` (``_member_class`` of one shape), in that order (``device``: default the first one's)."""
         policies = list(policies)
-        if not policies or not all(isinstance(p, CnnPolicy) for p in policies):
-            raise ValueError("from_policies takes a non-empty list of CnnPolicy")
-        first = policies[0]
-        shape = (first.width, first.height, first.channels, first.hidden, first.num_actions)
-        if any((p.width, p.height, p.channels, p.hidden, p.num_actions) != shape for p in policies):
+        if not policies or not all(isinstance(p, cls._member_class) for p in policies):
+            raise ValueError(f"from_policies takes a non-empty list of {cls._member_class.__name__}")
+        shape = {name: getattr(policies[0], name) for name in cls._shape}
+        if any(getattr(p, name) != value for p in policies for name, value in shape.items()):
             raise ValueError("the policies of a bank must have one shape")
-        bank = cls(*shape[:3], len(policies), shape[3], shape[4], device if device is not None else first.params.device)
+        bank = cls(num_policies=len(policies), device=device if device is not None else policies[0].params.device, **shape)
         with torch.no_grad():
             for k, p in enumerate(policies):
                 bank.params[k].copy_(p.params)
         return bank
+
+    def _check_params(self, gpu_id):
+        """``params`` is what the bank kernels take on device ``gpu_id``"""
+        p = self.params
+        if (not p.is_cuda or p.device.index != gpu_id or p.dtype != torch.float32 or not p.is_contiguous() or
+                tuple(p.shape) != (self.num_policies, self.num_params)):
+            raise ValueError(f"bank.params must be a contiguous float32 tensor (num_policies, num_params) on cuda:{gpu_id}")
+
+
+class CnnPolicyBank(_PolicyBank):
+    """K ``CnnPolicy`` of one shape in one dense float32 tensor ``params`` (K, num_params) (``mrl_cnn_bank``): row k is exactly
+    what a ``CnnPolicy``'s ``params`` is.  ``policy(k)`` is a ``CnnPolicy`` whose ``params`` IS row k, a contiguous view, so
+    ``cnn_act``, ``MappoOptimizer``, ``mappo_update`` and ``.module()`` work on a member unchanged and training a member is what the
+    next ``cnn_act_bank`` reads.  1 <= K <= 256."""
+
+    _member_class, _shape = CnnPolicy, CnnPolicy._shape
+
+    def __init__(self, width, height, channels, num_policies, hidden=64, num_actions=6, device="cuda:0"):
+        self.width, self.height, self.channels, self.hidden, self.num_actions = int(width), int(height), int(channels), int(hidden), int(num_actions)
+        super().__init__(num_policies, device)
+
+    def _count_params(self):
+        count = int(_lib.lib().mrl_cnn_policy_num_params(self.width, self.height, self.channels, self.hidden, self.num_actions))
+        if count == 0:
+            raise ValueError(f"mrl_cnn_act runs hidden = {_lib.CNN_HIDDEN}, num_actions = {_lib.CNN_ACTIONS} and kitchens of at least 3 x 3")
+        return count
 
     def desc(self):
         return _lib.CnnBankDesc(self.params.data_ptr(), self.num_policies, self.params.stride(0), self.hidden, 0)
@@ -563,10 +586,7 @@ class CnnPolicyBank:
 def _cnn_bank_call_args(sim, bank, ids, players, record):
     if not isinstance(bank, CnnPolicyBank):
         raise ValueError("bank must be a CnnPolicyBank")
-    p = bank.params
-    if (not p.is_cuda or p.device.index != sim.gpu_id or p.dtype != torch.float32 or not p.is_contiguous() or
-            tuple(p.shape) != (bank.num_policies, bank.num_params)):
-        raise ValueError(f"bank.params must be a contiguous float32 tensor (num_policies, num_params) on cuda:{sim.gpu_id}")
+    bank._check_params(sim.gpu_id)
     mask = _cnn_call_args(sim, bank.policy(0), players, record)
     shape = tuple(sim.observation_world_major_tensor().shape[:2])
     _check_ids(sim, ids, shape, "ids")
@@ -579,12 +599,18 @@ def _check_ids(sim, tensor, shape, name):
         raise ValueError(f"{name} must be a contiguous int32 tensor of shape {tuple(shape)} on cuda:{sim.gpu_id}")
 
 
-def _cnn_bank_workspace(sim, bank):
-    size = int(sim._L.mrl_cnn_bank_workspace_bytes(sim.num_worlds, sim.observation_world_major_tensor().shape[1], bank.num_policies))
-    workspace = getattr(sim, "_cnn_bank_workspace", None)
+def _bank_workspace(sim, attribute, size):
+    """the plan's workspace a MAPPO bank act takes by default: one the simulator keeps as ``attribute``, of at least ``size`` bytes"""
+    workspace = getattr(sim, attribute, None)
     if workspace is None or workspace.numel() < size:
-        workspace = sim._cnn_bank_workspace = torch.empty(size, dtype=torch.uint8, device=torch.device("cuda", sim.gpu_id))
+        workspace = torch.empty(int(size), dtype=torch.uint8, device=torch.device("cuda", sim.gpu_id))
+        setattr(sim, attribute, workspace)
     return workspace
+
+
+def _cnn_bank_workspace(sim, bank):
+    seats = sim.observation_world_major_tensor().shape[1]
+    return _bank_workspace(sim, "_cnn_bank_workspace", sim._L.mrl_cnn_bank_workspace_bytes(sim.num_worlds, seats, bank.num_policies))
 
 
 def cnn_act_bank(sim, bank, ids, players=None, record=None, ids_row=None, row=0, seed=0, step=0, greedy=False, value_only=False,
@@ -653,17 +679,25 @@ def resample_twin(ids, episodes, done, mode, first_id, num_ids, players, seed=0)
         ids[rows, p] = new.astype(np.int32)
 
 
+def _bank_resample(sim, entry_point, worlds, seats, ids, episodes, mode, first_id, num_ids, players, seed):
+    """The three resamples behind their own check of the simulator: ``entry_point`` of the library on ``ids`` (worlds, seats) and
+    ``episodes`` (worlds)."""
+    _check_ids(sim, ids, (worlds, seats), "ids")
+    _check_ids(sim, episodes, (worlds,), "episodes")
+    resample = mode if isinstance(mode, CnnResample) else CnnResample(mode, first_id, num_ids, seats, seed)
+    _lib.check(getattr(sim._L, entry_point)(sim._handle, _seat_mask(players, seats), ctypes.byref(resample.struct), ids.data_ptr(),
+                                            episodes.data_ptr(), _stream_ptr(sim.gpu_id)))
+
+
 def cnn_resample(sim, ids, episodes, mode, first_id, num_ids, players=None, seed=0):
     """``mrl_cnn_bank_resample`` on torch's current stream: where DONE[n] != 0 -- the world has just restarted itself --
     ``episodes[n]`` goes up by one and every seat p of ``players`` with ``ids[n, p] >= 0`` takes its next policy from
     ``[first_id[p], first_id[p] + num_ids[p])``: "robin" the next one round the range, "random" by ``random_hash(seed, episodes[n],
     n, p)`` (``resample_twin`` is the same in numpy).  ``mode`` may also be a ``CnnResample``, which then carries the rest."""
-    shape = tuple(sim.observation_world_major_tensor().shape[:2])
-    _check_ids(sim, ids, shape, "ids")
-    _check_ids(sim, episodes, shape[:1], "episodes")
-    resample = mode if isinstance(mode, CnnResample) else CnnResample(mode, first_id, num_ids, shape[1], seed)
-    _lib.check(sim._L.mrl_cnn_bank_resample(sim._handle, _seat_mask(players, shape[1]), ctypes.byref(resample.struct), ids.data_ptr(),
-                                            episodes.data_ptr(), _stream_ptr(sim.gpu_id)))
+    if not isinstance(sim, OvercookedSimulator):  # (a SimplecookedSimulator is one)
+        raise ValueError(f"mrl_cnn_bank_resample runs on an OvercookedSimulator or a SimplecookedSimulator, not on a {type(sim).__name__}")
+    worlds, seats = sim.observation_world_major_tensor().shape[:2]
+    _bank_resample(sim, "mrl_cnn_bank_resample", worlds, seats, ids, episodes, mode, first_id, num_ids, players, seed)
 
 
 CrossPlayResult = collections.namedtuple("CrossPlayResult", "mean_return episodes")  # each (Ka, Kb), on the device
@@ -695,6 +729,19 @@ def cross_play(env, bank, members_a=None, members_b=None, greedy=True, seed=0, s
         raise ValueError("steps is the balance beam's: a kitchen's cross-play lasts one horizon")
     sim = env.sim
     n, p = tuple(sim.observation_world_major_tensor().shape[:2])
+    ka, kb, pair, ids = _cross_play_pairs(sim, bank, members_a, members_b, n, p)
+    sim.enable_episode_stats()
+    sim.reset_worlds(None)
+    for t in range(int(env.horizon)):
+        cnn_act_bank(sim, bank, ids, seed=seed, step=t, greedy=greedy)
+        sim.step()
+    last = sim.last_episode_return_tensor().to_torch().reshape(p, n)[0].to(torch.float64)
+    return _cross_play_result(ka, kb, pair, last, torch.ones_like(pair))
+
+
+def _cross_play_pairs(sim, bank, members_a, members_b, n, p):
+    """What every ``cross_play`` sets up alike on ``n`` worlds of ``p`` seats: the members of both seats (default every row of the
+    bank) and the worlds' pairs -> (Ka, Kb, ``pair`` (N): n mod (Ka Kb), ``ids`` int32 (N, 2): the rows world n plays under)."""
     if p != 2:
         raise ValueError(f"cross_play pairs seat 0 with seat 1: the env has {p} seats")
     a = list(range(bank.num_policies)) if members_a is None else [int(k) for k in members_a]
@@ -707,15 +754,14 @@ def cross_play(env, bank, members_a=None, members_b=None, greedy=True, seed=0, s
     device = torch.device("cuda", sim.gpu_id)
     pair = torch.arange(n, device=device) % pairs
     ids = torch.stack([torch.tensor(a, device=device)[pair // len(b)], torch.tensor(b, device=device)[pair % len(b)]], dim=1).to(torch.int32).contiguous()
-    sim.enable_episode_stats()
-    sim.reset_worlds(None)
-    for t in range(int(env.horizon)):
-        cnn_act_bank(sim, bank, ids, seed=seed, step=t, greedy=greedy)
-        sim.step()
-    last = sim.last_episode_return_tensor().to_torch().reshape(p, n)[0].to(torch.float64)
-    count = torch.zeros(pairs, dtype=torch.int64, device=device).index_add_(0, pair, torch.ones_like(pair))
-    total = torch.zeros(pairs, dtype=torch.float64, device=device).index_add_(0, pair, last)
-    return CrossPlayResult((total / count).view(len(a), len(b)), count.view(len(a), len(b)))
+    return len(a), len(b), pair, ids
+
+
+def _cross_play_result(ka, kb, pair, total, finished):
+    """the worlds' float64 return sums and int64 episode counts reduced per pair -> ``CrossPlayResult``"""
+    count = torch.zeros(ka * kb, dtype=torch.int64, device=pair.device).index_add_(0, pair, finished)
+    summed = torch.zeros(ka * kb, dtype=torch.float64, device=pair.device).index_add_(0, pair, total)
+    return CrossPlayResult((summed / count).view(ka, kb), count.view(ka, kb))
 
 
 class _MlpLayer(torch.nn.Module):
@@ -885,58 +931,26 @@ def mlpbase_act(sim, policy, players=None, record=None, row=0, seed=0, step=0, g
         _lib.check(rc)
 
 
-class MlpBasePolicyBank:
+class MlpBasePolicyBank(_PolicyBank):
     """K ``MlpBasePolicy`` of one shape in one dense float32 tensor ``params`` (K, num_params) (``mrl_mlpbase_bank``), the
     counterpart of ``CnnPolicyBank`` for the balance beam: row k is exactly what an ``MlpBasePolicy``'s ``params`` is.
     ``policy(k)`` is an ``MlpBasePolicy`` whose ``params`` IS row k, a contiguous view, so ``mlpbase_act``, ``MappoOptimizer``,
     ``mappo_update`` and ``.module()`` work on a member unchanged and training a member is what the next ``mlpbase_act_bank``
     reads.  1 <= K <= 256; one ``layer_N`` for the whole bank."""
 
+    _member_class, _shape = MlpBasePolicy, MlpBasePolicy._shape
+
     def __init__(self, num_policies, layer_N=2, obs_dim=_lib.MLPBASE_OBS, num_actions=_lib.MLPBASE_ACTIONS, hidden=_lib.MLPBASE_HIDDEN,
                  device="cuda:0"):
         self.obs_dim, self.num_actions, self.hidden, self.layer_N = int(obs_dim), int(num_actions), int(hidden), int(layer_N)
-        self.num_policies = int(num_policies)
-        if not 1 <= self.num_policies <= _lib.CNN_BANK_MAX_POLICIES:
-            raise ValueError(f"a bank holds 1 to {_lib.CNN_BANK_MAX_POLICIES} policies, not {num_policies}")
-        self.num_params = int(_lib.lib().mrl_mlpbase_policy_num_params(self.obs_dim, self.hidden, self.layer_N, self.num_actions))
-        if self.num_params == 0:
+        super().__init__(num_policies, device)
+
+    def _count_params(self):
+        count = int(_lib.lib().mrl_mlpbase_policy_num_params(self.obs_dim, self.hidden, self.layer_N, self.num_actions))
+        if count == 0:
             raise ValueError(f"mrl_mlpbase_act runs obs_dim = {_lib.MLPBASE_OBS}, num_actions = {_lib.MLPBASE_ACTIONS}, hidden = "
                              f"{_lib.MLPBASE_HIDDEN} and layer_N 1 or 2; got {self.obs_dim}, {self.num_actions}, {self.hidden}, {self.layer_N}")
-        self.params = torch.zeros((self.num_policies, self.num_params), dtype=torch.float32, device=torch.device(device))
-        self._members = {}
-
-    def __len__(self):
-        return self.num_policies
-
-    def policy(self, k):
-        """The ``MlpBasePolicy`` whose ``params`` is row ``k`` of the bank (one object per row)."""
-        k = int(k)
-        if not 0 <= k < self.num_policies:
-            raise IndexError(f"the bank holds policies 0..{self.num_policies - 1}, not {k}")
-        member = self._members.get(k)
-        if member is None:
-            member = MlpBasePolicy.__new__(MlpBasePolicy)
-            member.obs_dim, member.num_actions, member.hidden, member.layer_N = self.obs_dim, self.num_actions, self.hidden, self.layer_N
-            member.params = self.params[k]
-            member._module = None
-            self._members[k] = member
-        return member
-
-    @classmethod
-    def from_policies(cls, policies, device=None):
-        """A bank holding copies of ``policies`` (``MlpBasePolicy`` of one shape), in that order (``device``: default the first one's)."""
-        policies = list(policies)
-        if not policies or not all(isinstance(p, MlpBasePolicy) for p in policies):
-            raise ValueError("from_policies takes a non-empty list of MlpBasePolicy")
-        first = policies[0]
-        shape = (first.obs_dim, first.num_actions, first.hidden, first.layer_N)
-        if any((p.obs_dim, p.num_actions, p.hidden, p.layer_N) != shape for p in policies):
-            raise ValueError("the policies of a bank must have one shape")
-        bank = cls(len(policies), first.layer_N, first.obs_dim, first.num_actions, first.hidden, device if device is not None else first.params.device)
-        with torch.no_grad():
-            for k, p in enumerate(policies):
-                bank.params[k].copy_(p.params)
-        return bank
+        return count
 
     def desc(self):
         return _lib.MlpBaseBankDesc(self.params.data_ptr(), self.num_policies, self.params.stride(0), self.hidden, self.layer_N, 0)
@@ -947,10 +961,7 @@ def _mlpbase_bank_call_args(sim, bank, ids, players, record):
         raise ValueError("bank must be an MlpBasePolicyBank")
     if not isinstance(sim, BalanceBeamSimulator):
         raise ValueError("mrl_mlpbase_act_bank runs on a BalanceBeamSimulator")
-    p = bank.params
-    if (not p.is_cuda or p.device.index != sim.gpu_id or p.dtype != torch.float32 or not p.is_contiguous() or
-            tuple(p.shape) != (bank.num_policies, bank.num_params)):
-        raise ValueError(f"bank.params must be a contiguous float32 tensor (num_policies, num_params) on cuda:{sim.gpu_id}")
+    bank._check_params(sim.gpu_id)
     mask = _mlpbase_call_args(sim, bank.policy(0), players, record)
     seats, worlds = sim.observation_tensor().shape[:2]  # (P, N, 7)
     _check_ids(sim, ids, (worlds, seats), "ids")
@@ -958,11 +969,7 @@ def _mlpbase_bank_call_args(sim, bank, ids, players, record):
 
 
 def _mlpbase_bank_workspace(sim, bank):
-    size = int(sim._L.mrl_mlpbase_bank_workspace_bytes(sim.num_worlds, bank.num_policies))
-    workspace = getattr(sim, "_mlpbase_bank_workspace", None)
-    if workspace is None or workspace.numel() < size:
-        workspace = sim._mlpbase_bank_workspace = torch.empty(size, dtype=torch.uint8, device=torch.device("cuda", sim.gpu_id))
-    return workspace
+    return _bank_workspace(sim, "_mlpbase_bank_workspace", sim._L.mrl_mlpbase_bank_workspace_bytes(sim.num_worlds, bank.num_policies))
 
 
 def mlpbase_act_bank(sim, bank, ids, players=None, record=None, ids_row=None, row=0, seed=0, step=0, greedy=False, value_only=False,
@@ -999,11 +1006,7 @@ def mlpbase_resample(sim, ids, episodes, mode, first_id=None, num_ids=None, play
     if not isinstance(sim, BalanceBeamSimulator):
         raise ValueError("mrl_mlpbase_bank_resample runs on a BalanceBeamSimulator")
     seats, worlds = sim.observation_tensor().shape[:2]
-    _check_ids(sim, ids, (worlds, seats), "ids")
-    _check_ids(sim, episodes, (worlds,), "episodes")
-    resample = mode if isinstance(mode, CnnResample) else CnnResample(mode, first_id, num_ids, seats, seed)
-    _lib.check(sim._L.mrl_mlpbase_bank_resample(sim._handle, _seat_mask(players, seats), ctypes.byref(resample.struct), ids.data_ptr(),
-                                                episodes.data_ptr(), _stream_ptr(sim.gpu_id)))
+    _bank_resample(sim, "mrl_mlpbase_bank_resample", worlds, seats, ids, episodes, mode, first_id, num_ids, players, seed)
 
 
 BEAM_TIME = 3  # src/balance_beam_env/sim.cpp: an observation holds TIME positions per seat, an episode is at most TIME - 1 moves
@@ -1014,21 +1017,11 @@ def _cross_play_counted(sim, bank, members_a, members_b, steps, act):
     the last-episode return (P, N)): the pairs, the restart, ``steps`` times (``act(ids, t)``, step, count) and the per-pair
     reduction.  ``act`` enqueues step t's acts of both seats under ``ids`` (N, 2)."""
     p, n = tuple(sim.observation_tensor().shape[:2])
-    if p != 2:
-        raise ValueError(f"cross_play pairs seat 0 with seat 1: the env has {p} seats")
-    a = list(range(bank.num_policies)) if members_a is None else [int(k) for k in members_a]
-    b = list(range(bank.num_policies)) if members_b is None else [int(k) for k in members_b]
-    if not a or not b or any(not 0 <= k < bank.num_policies for k in a + b):
-        raise ValueError(f"members must name rows 0..{bank.num_policies - 1} of the bank")
-    pairs = len(a) * len(b)
-    if n < pairs:
-        raise ValueError(f"{n} worlds cannot play {len(a)} x {len(b)} pairs")
+    ka, kb, pair, ids = _cross_play_pairs(sim, bank, members_a, members_b, n, p)
     steps = int(steps)
     if steps < 1:
         raise ValueError("steps must be positive")
-    device = torch.device("cuda", sim.gpu_id)
-    pair = torch.arange(n, device=device) % pairs
-    ids = torch.stack([torch.tensor(a, device=device)[pair // len(b)], torch.tensor(b, device=device)[pair % len(b)]], dim=1).to(torch.int32).contiguous()
+    device = pair.device
     sim.enable_episode_stats()
     sim.reset_worlds(None)
     done = sim.done_tensor().to_torch().reshape(n)
@@ -1041,9 +1034,7 @@ def _cross_play_counted(sim, bank, members_a, members_b, steps, act):
         over = done != 0
         total += torch.where(over, last.to(torch.float64), torch.zeros_like(total))  # float32 returns: the float64 sums are exact
         finished += over
-    count = torch.zeros(pairs, dtype=torch.int64, device=device).index_add_(0, pair, finished)
-    summed = torch.zeros(pairs, dtype=torch.float64, device=device).index_add_(0, pair, total)
-    return CrossPlayResult((summed / count).view(len(a), len(b)), count.view(len(a), len(b)))
+    return _cross_play_result(ka, kb, pair, total, finished)
 
 
 def _cross_play_beam(env, bank, members_a, members_b, greedy, seed, steps):
@@ -1222,56 +1213,23 @@ def agent_act(sim, player, policy, record=None, row=0, seed=0, step=0, greedy=Fa
         _lib.check(rc)
 
 
-class WidePolicyBank:
+class WidePolicyBank(_PolicyBank):
     """K ``WidePolicy`` of one shape in one dense float32 tensor ``params`` (K, num_params) (``mrl_wide_bank``), the counterpart of
     ``CnnPolicyBank`` and ``MlpBasePolicyBank`` for Hanabi and the balance beam: row k is exactly what a ``WidePolicy``'s ``params``
     is.  ``policy(k)`` is a ``WidePolicy`` whose ``params`` IS row k, a contiguous view, so ``agent_act``, ``WideOptimizer`` /
     ``agent_update``, ``.module()`` and a torch optimizer work on a member unchanged, and training a member is what the next
     ``agent_act_bank`` reads.  1 <= K <= 256."""
 
+    _member_class, _shape = WidePolicy, ("obs_dim", "state_dim", "num_actions")
+
     def __init__(self, obs_dim, state_dim, num_actions, num_policies, device="cuda:0"):
         self.obs_dim, self.state_dim, self.num_actions = int(obs_dim), int(state_dim), int(num_actions)
-        self.num_policies = int(num_policies)
-        if not 1 <= self.num_policies <= _lib.CNN_BANK_MAX_POLICIES:
-            raise ValueError(f"a bank holds 1 to {_lib.CNN_BANK_MAX_POLICIES} policies, not {num_policies}")
+        super().__init__(num_policies, device)
+
+    def _count_params(self):
         if not 1 <= self.num_actions <= _lib.WIDE_MAX_ACTIONS or self.obs_dim < 1 or self.state_dim < 1:
             raise ValueError(f"need 1 <= num_actions <= {_lib.WIDE_MAX_ACTIONS} and obs_dim, state_dim >= 1")
-        self.num_params = int(_lib.lib().mrl_wide_policy_num_params(self.obs_dim, self.state_dim, self.num_actions))
-        self.params = torch.zeros((self.num_policies, self.num_params), dtype=torch.float32, device=torch.device(device))
-        self._members = {}
-
-    def __len__(self):
-        return self.num_policies
-
-    def policy(self, k):
-        """The ``WidePolicy`` whose ``params`` is row ``k`` of the bank (one object per row)."""
-        k = int(k)
-        if not 0 <= k < self.num_policies:
-            raise IndexError(f"the bank holds policies 0..{self.num_policies - 1}, not {k}")
-        member = self._members.get(k)
-        if member is None:
-            member = WidePolicy.__new__(WidePolicy)
-            member.obs_dim, member.state_dim, member.num_actions = self.obs_dim, self.state_dim, self.num_actions
-            member.params = self.params[k]
-            member._module = None
-            self._members[k] = member
-        return member
-
-    @classmethod
-    def from_policies(cls, policies, device=None):
-        """A bank holding copies of ``policies`` (``WidePolicy`` of one shape), in that order (``device``: default the first one's)."""
-        policies = list(policies)
-        if not policies or not all(isinstance(p, WidePolicy) for p in policies):
-            raise ValueError("from_policies takes a non-empty list of WidePolicy")
-        first = policies[0]
-        shape = (first.obs_dim, first.state_dim, first.num_actions)
-        if any((p.obs_dim, p.state_dim, p.num_actions) != shape for p in policies):
-            raise ValueError("the policies of a bank must have one shape")
-        bank = cls(*shape, len(policies), device if device is not None else first.params.device)
-        with torch.no_grad():
-            for k, p in enumerate(policies):
-                bank.params[k].copy_(p.params)
-        return bank
+        return int(_lib.lib().mrl_wide_policy_num_params(self.obs_dim, self.state_dim, self.num_actions))
 
     def desc(self):
         return _lib.WideBankDesc(self.params.data_ptr(), self.num_policies, self.params.stride(0), self.obs_dim, self.state_dim,
@@ -1293,6 +1251,9 @@ def agent_bank_workspace_bytes(num_worlds, num_policies):
 
 
 def _wide_bank_workspace(sim, bank):
+    """The default workspace of ``agent_act_bank``, one per (simulator, bank): the act itself does not need that -- a call rewrites
+    everything it reads of the workspace -- but two banks that act on one simulator from two streams (a population per seat) then
+    never share a buffer, which one workspace per simulator, as the MAPPO banks keep it, would make them do."""
     size = agent_bank_workspace_bytes(sim.num_worlds, bank.num_policies)
     cache = sim.__dict__.setdefault("_wide_bank_workspaces", {})
     workspace = cache.get(id(bank))
@@ -1313,10 +1274,7 @@ def agent_act_bank(sim, player, bank, ids, ids_row=None, seed=0, step=0, greedy=
     if not isinstance(bank, WidePolicyBank):
         raise ValueError("bank must be a WidePolicyBank")
     seats, worlds = _wide_seats(sim, "mrl_agent_act_bank")
-    p = bank.params
-    if (not p.is_cuda or p.device.index != sim.gpu_id or p.dtype != torch.float32 or not p.is_contiguous() or
-            tuple(p.shape) != (bank.num_policies, bank.num_params)):
-        raise ValueError(f"bank.params must be a contiguous float32 tensor (num_policies, num_params) on cuda:{sim.gpu_id}")
+    bank._check_params(sim.gpu_id)
     _check_ids(sim, ids, (worlds, seats), "ids")
     if ids_row is not None:
         _check_ids(sim, ids_row, (worlds,), "ids_row")
@@ -1336,11 +1294,7 @@ def wide_resample(sim, ids, episodes, mode, first_id=None, num_ids=None, players
     kernel, draws and arguments (``resample_twin`` is the same in numpy).  ``mode`` may also be a ``CnnResample``
     (``BankResample``), which then carries the rest."""
     seats, worlds = _wide_seats(sim, "mrl_agent_bank_resample")
-    _check_ids(sim, ids, (worlds, seats), "ids")
-    _check_ids(sim, episodes, (worlds,), "episodes")
-    resample = mode if isinstance(mode, CnnResample) else CnnResample(mode, first_id, num_ids, seats, seed)
-    _lib.check(sim._L.mrl_agent_bank_resample(sim._handle, _seat_mask(players, seats), ctypes.byref(resample.struct), ids.data_ptr(),
-                                              episodes.data_ptr(), _stream_ptr(sim.gpu_id)))
+    _bank_resample(sim, "mrl_agent_bank_resample", worlds, seats, ids, episodes, mode, first_id, num_ids, players, seed)
 
 
 def agent_credit(record, rewards, dones):
@@ -1770,6 +1724,32 @@ class RecordsEpisodeStatistics:
         self.sim.clear_episode_totals()
 
 
+def _bank_rollout_buffers(env, num_steps, seats, ids_record, episodes, resample):
+    """What the two env mixins' ``rollout_bank`` set up alike -> (``ids_record``, made when ``None``; ``episodes``, with a
+    ``resample`` and ``None`` the env's ``bank_episodes``, made once and kept)"""
+    device = env.static_actions.device
+    if ids_record is None:
+        ids_record = torch.empty((int(num_steps) + 1, env.num_envs, seats), dtype=torch.int32, device=device)
+    if episodes is None and resample is not None:
+        episodes = getattr(env, "bank_episodes", None)
+        if episodes is None:
+            episodes = env.bank_episodes = torch.zeros(env.num_envs, dtype=torch.int32, device=device)
+    return ids_record, episodes
+
+
+def _check_bank_rollout(sim, record, cells, ids_record, resample, episodes):
+    """What ``rollout_cnn_bank`` and ``rollout_mlpbase_bank`` check alike for ``cells`` = (N, P): ``ids_record`` (T + 1, N, P), the
+    ``resample`` and its ``episodes`` (N)"""
+    if ids_record is not None:
+        _check_ids(sim, ids_record, (record.num_steps + 1,) + tuple(cells), "ids_record")
+    if resample is not None and not isinstance(resample, CnnResample):
+        raise ValueError("resample must be a CnnResample or None")
+    if episodes is not None:
+        _check_ids(sim, episodes, tuple(cells[:1]), "episodes")
+    elif resample is not None:
+        raise ValueError("a resample needs episodes, an int32 tensor (num_worlds,)")
+
+
 class ActsWithCnnPolicy:
     """Mixin of the two kitchen env wrappers (``envs/overcooked_env.py``, ``envs/overcooked2_env.py``; ``self.sim``, ``static_actions``,
     ``static_world_major_observations``, ``num_envs`` and ``num_players`` are the wrapper's): MAPPO's CNN actor-critic on the device."""
@@ -1811,12 +1791,7 @@ class ActsWithCnnPolicy:
         record = CnnRecord._for_rollout(record, num_steps, self.num_envs, self.num_players, device)
         if ring is None:
             ring = torch.empty((int(num_steps) + 1,) + tuple(self.static_world_major_observations.shape), dtype=torch.int8, device=device)
-        if ids_record is None:
-            ids_record = torch.empty((int(num_steps) + 1, self.num_envs, self.num_players), dtype=torch.int32, device=device)
-        if episodes is None and resample is not None:
-            episodes = getattr(self, "bank_episodes", None)
-            if episodes is None:
-                episodes = self.bank_episodes = torch.zeros(self.num_envs, dtype=torch.int32, device=device)
+        ids_record, episodes = _bank_rollout_buffers(self, num_steps, self.num_players, ids_record, episodes, resample)
         self.sim.rollout_cnn_bank(bank, ids, record, ring, episodes=episodes, resample=resample, ids_record=ids_record, players=players,
                                   seed=seed, first_step=first_step, greedy=greedy)
         return record, ring, ids_record
@@ -1854,14 +1829,8 @@ class ActsWithMlpBasePolicy:
         the ids each act used (-1 where it did not act).  ``resample`` (a ``simulators.CnnResample``) runs behind every step: worlds
         that have just restarted draw their next policies into ``ids`` and count in ``episodes`` (int32 (N), made when ``None`` and
         then kept by the env as ``bank_episodes``)."""
-        device = self.static_actions.device
-        record = MlpBaseRecord._for_rollout(record, num_steps, self.num_envs, self.n_players, device)
-        if ids_record is None:
-            ids_record = torch.empty((int(num_steps) + 1, self.num_envs, self.n_players), dtype=torch.int32, device=device)
-        if episodes is None and resample is not None:
-            episodes = getattr(self, "bank_episodes", None)
-            if episodes is None:
-                episodes = self.bank_episodes = torch.zeros(self.num_envs, dtype=torch.int32, device=device)
+        record = MlpBaseRecord._for_rollout(record, num_steps, self.num_envs, self.n_players, self.static_actions.device)
+        ids_record, episodes = _bank_rollout_buffers(self, num_steps, self.n_players, ids_record, episodes, resample)
         self.sim.rollout_mlpbase_bank(bank, ids, record, episodes=episodes, resample=resample, ids_record=ids_record, players=players,
                                       seed=seed, first_step=first_step, greedy=greedy)
         return record, ids_record
@@ -2010,14 +1979,7 @@ class _Simulator:
         if (not isinstance(obs_ring, torch.Tensor) or not obs_ring.is_cuda or obs_ring.device.index != self.gpu_id or
                 obs_ring.dtype not in (torch.int8, torch.uint8) or tuple(obs_ring.shape) != want or not obs_ring.is_contiguous()):
             raise ValueError(f"obs_ring must be a contiguous int8 tensor of shape {want} on cuda:{self.gpu_id}")
-        if ids_record is not None:
-            _check_ids(self, ids_record, (record.num_steps + 1,) + cells[:2], "ids_record")
-        if resample is not None and not isinstance(resample, CnnResample):
-            raise ValueError("resample must be a CnnResample or None")
-        if episodes is not None:
-            _check_ids(self, episodes, cells[:1], "episodes")
-        elif resample is not None:
-            raise ValueError("a resample needs episodes, an int32 tensor (num_worlds,)")
+        _check_bank_rollout(self, record, cells[:2], ids_record, resample, episodes)
         if workspace is None:
             workspace = _cnn_bank_workspace(self, bank)
         desc = bank.desc()
@@ -2050,15 +2012,7 @@ class _Simulator:
         mask = _mlpbase_bank_call_args(self, bank, ids, players, record)
         if record is None:
             raise ValueError("rollout_mlpbase_bank needs an MlpBaseRecord")
-        cells = tuple(ids.shape)
-        if ids_record is not None:
-            _check_ids(self, ids_record, (record.num_steps + 1,) + cells, "ids_record")
-        if resample is not None and not isinstance(resample, CnnResample):
-            raise ValueError("resample must be a CnnResample or None")
-        if episodes is not None:
-            _check_ids(self, episodes, cells[:1], "episodes")
-        elif resample is not None:
-            raise ValueError("a resample needs episodes, an int32 tensor (num_worlds,)")
+        _check_bank_rollout(self, record, ids.shape, ids_record, resample, episodes)
         if workspace is None:
             workspace = _mlpbase_bank_workspace(self, bank)
         desc = bank.desc()

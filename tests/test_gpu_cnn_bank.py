@@ -14,6 +14,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import cnn_twin as twin  # noqa: E402
+from bank_cases import assert_plan_read_back, cpu, same_bits  # noqa: E402
 from madrona_rl_envs_playground_amd import _lib, layouts  # noqa: E402
 from madrona_rl_envs_playground_amd.envs import OvercookedMadrona  # noqa: E402
 from madrona_rl_envs_playground_amd.pantheonrl_extension import CnnPopulationAgent  # noqa: E402
@@ -26,15 +27,6 @@ from madrona_rl_envs_playground_amd.simulators import (CartpoleSimulator, CnnAct
 DEV = torch.device("cuda", 0)
 RECORDED = ("actions", "logprobs", "values", "rewards", "dones", "next_done", "logits")
 MARK, ACTION_MARK = -77, -7
-
-
-def cpu(t):
-    return (t.to_torch() if hasattr(t, "to_torch") else t).cpu().numpy().copy()
-
-
-def same_bits(a, b, what):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), f"{what} differs"
 
 
 def record_arrays(record):
@@ -97,13 +89,6 @@ def one_act(sim, act, n, p):
     out = record_arrays(record)
     out["action_tensor"] = cpu(sim.action_tensor())
     return out
-
-
-def workspace_layout(n, p, k):
-    cells, kp = n * p, (k + 3) // 4 * 4
-    max_tiles = (cells + 31) // 32 + k
-    table = 4 + 2 * kp
-    return {"count": 4, "start": 4 + kp, "table": table, "lists": table + 4 * max_tiles, "max_tiles": max_tiles}
 
 
 # ---------------------------------------------------------------- 1: a bank of one is the plain act
@@ -233,35 +218,7 @@ def test_mixed_assignment_equals_plain_acts_selected_by_id(key, hip_lib):
 @pytest.mark.parametrize("key", sorted(MIXED))
 def test_plan_read_back(key, hip_lib):
     c = mixed_case(key)
-    n, p, k, ids, size = c["n"], c["p"], c["k"], c["ids"], c["size"]
-    assert (c["block"][:256] == 0xA5).all() and (c["block"][256 + size:] == 0xA5).all()  # the guard bytes
-    words = c["block"][256:256 + size].view(np.uint32)
-    at = workspace_layout(n, p, k)
-    acted = acted_mask(c)
-    tiles, n_acted, out_of_range = (int(x) for x in words[:3])
-    assert n_acted == acted.sum() and out_of_range == 1
-    counts = words[at["count"]:at["count"] + k]
-    starts = words[at["start"]:at["start"] + k]
-    flat_ids, flat_acted = ids.reshape(-1), acted.reshape(-1)
-    assert np.array_equal(counts, [(flat_acted & (flat_ids == j)).sum() for j in range(k)])
-    assert np.array_equal(starts, np.concatenate([[0], np.cumsum(counts)[:-1]]))
-    assert tiles == sum((int(cnt) + 31) // 32 for cnt in counts) <= (n * p + 31) // 32 + k == at["max_tiles"]
-    lists = words[at["lists"]:at["lists"] + n_acted]
-    # every acted cell once, in its own policy's list, ascending
-    assert np.array_equal(np.sort(lists), np.flatnonzero(flat_acted))
-    for j in range(k):
-        mine = lists[starts[j]:starts[j] + counts[j]]
-        assert np.array_equal(mine, np.flatnonzero(flat_acted & (flat_ids == j)))
-    # tiles: one policy each, consecutive pieces of that policy's list, 32 rows but for the last
-    table = words[at["table"]:at["table"] + 4 * tiles].reshape(tiles, 4)
-    covered = np.zeros(n_acted, dtype=np.int32)
-    for policy, first, rows, zero in table:
-        assert 1 <= rows <= 32 and zero == 0 and policy < k
-        assert starts[policy] <= first and first + rows <= starts[policy] + counts[policy]
-        assert (flat_ids[lists[first:first + rows]] == policy).all()
-        covered[first:first + rows] += 1
-    assert (covered == 1).all()
-    assert np.array_equal(np.bincount(table[:, 0], minlength=k), [(int(cnt) + 31) // 32 for cnt in counts])
+    assert_plan_read_back(c["block"], c["size"], c["n"], c["p"], c["k"], c["ids"], acted_mask(c), out_of_range=1)
 
 
 # ---------------------------------------------------------------- 4: the resample against its twin

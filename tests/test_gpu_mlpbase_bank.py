@@ -15,6 +15,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from bank_cases import assert_plan_read_back, cpu, same_bits  # noqa: E402
 from madrona_rl_envs_playground_amd import _lib  # noqa: E402
 from madrona_rl_envs_playground_amd.envs.balance_beam_env import BalanceMadronaTorch  # noqa: E402
 from madrona_rl_envs_playground_amd.pantheonrl_extension import MlpBasePopulationAgent  # noqa: E402
@@ -22,21 +23,12 @@ from madrona_rl_envs_playground_amd.simulators import (BalanceBeamSimulator, Ban
                                                          MappoOptimizer, MlpBaseActorCritic, MlpBasePolicy, MlpBasePolicyBank,
                                                          MlpBaseRecord, ValueNorm, cross_play, gae, mappo_advantages, mappo_update,
                                                          minibatch_indices, mlpbase_act, mlpbase_act_bank, mlpbase_resample,
-                                                         resample_twin)
+                                                         resample_twin, wide_resample)
 
 DEV = torch.device("cuda", 0)
 RECORDED = _lib.MLPBASE_RECORD_BUFFERS  # actions, logprobs, values, rewards, dones, next_done, logits, obs
 MARK, ACTION_MARK = -77, -7
 P = 2
-
-
-def cpu(t):
-    return (t.to_torch() if hasattr(t, "to_torch") else t).cpu().numpy().copy()
-
-
-def same_bits(a, b, what):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), f"{what} differs"
 
 
 def record_arrays(record):
@@ -95,13 +87,6 @@ def one_act(sim, act, record):
     out = record_arrays(record) if record is not None else {}
     out["action_tensor"] = cpu(sim.action_tensor())
     return out
-
-
-def workspace_layout(n, p, k):
-    cells, kp = n * p, (k + 3) // 4 * 4
-    max_tiles = (cells + 31) // 32 + k
-    table = 4 + 2 * kp
-    return {"count": 4, "start": 4 + kp, "table": table, "lists": table + 4 * max_tiles, "max_tiles": max_tiles}
 
 
 # ---------------------------------------------------------------- 1: a bank of one is the plain act
@@ -263,57 +248,46 @@ def test_mixed_assignment_equals_plain_acts_selected_by_id(key, hip_lib):
 @pytest.mark.parametrize("key", sorted(MIXED))
 def test_plan_read_back(key, hip_lib):
     c = mixed_case(key)
-    n, k, ids, size = c["n"], c["k"], c["ids"], c["size"]
-    assert (c["block"][:256] == 0xA5).all() and (c["block"][256 + size:] == 0xA5).all()  # the guard bytes
-    words = c["block"][256:256 + size].view(np.uint32)
-    at = workspace_layout(n, P, k)
-    acted = acted_mask(c)
-    tiles, n_acted, out_of_range = (int(x) for x in words[:3])
-    assert n_acted == acted.sum() and out_of_range == MIXED[key][5] and words[3] == 0
-    counts = words[at["count"]:at["count"] + k]
-    starts = words[at["start"]:at["start"] + k]
-    flat_ids, flat_acted = ids.reshape(-1), acted.reshape(-1)
-    assert np.array_equal(counts, np.bincount(flat_ids[flat_acted], minlength=k))
-    assert np.array_equal(starts, np.concatenate([[0], np.cumsum(counts)[:-1]]))
-    assert tiles == sum((int(cnt) + 31) // 32 for cnt in counts) <= (n * P + 31) // 32 + k == at["max_tiles"]
-    lists = words[at["lists"]:at["lists"] + n_acted]
-    # every acted cell once, in its own policy's list, ascending
-    assert np.array_equal(np.sort(lists), np.flatnonzero(flat_acted))
-    for j in range(k):
-        mine = lists[starts[j]:starts[j] + counts[j]]
-        assert np.array_equal(mine, np.flatnonzero(flat_acted & (flat_ids == j)))
-    # tiles: one policy each, consecutive pieces of that policy's list, 32 rows but for the last
-    table = words[at["table"]:at["table"] + 4 * tiles].reshape(tiles, 4)
-    covered = np.zeros(n_acted, dtype=np.int32)
-    for policy, first, rows, zero in table:
-        assert 1 <= rows <= 32 and zero == 0 and policy < k
-        assert starts[policy] <= first and first + rows <= starts[policy] + counts[policy]
-        assert (flat_ids[lists[first:first + rows]] == policy).all()
-        covered[first:first + rows] += 1
-    assert (covered == 1).all()
-    assert np.array_equal(np.bincount(table[:, 0], minlength=k), [(int(cnt) + 31) // 32 for cnt in counts])
+    assert_plan_read_back(c["block"], c["size"], c["n"], P, c["k"], c["ids"], acted_mask(c), out_of_range=MIXED[key][5])
 
 
 # ---------------------------------------------------------------- 6: the resample against its twin
+
+def resample_start(n):
+    """what both resample tests start from -> (rng, first, num, ids (N, 2) with a fifth of the cells at -1)"""
+    rng = np.random.default_rng(3)
+    first, num = [1, 3], [3, 1]  # seat 0 draws from {1, 2, 3}, seat 1 from {3}: a range of one
+    ids_host = np.stack([rng.integers(1, 4, size=n), np.full(n, 3)], axis=1).astype(np.int32)
+    ids_host[rng.uniform(size=(n, 2)) < 0.2] = -1
+    return rng, first, num, ids_host
+
+
+def resample_schedule(sim, n, rng):
+    """The steps both resample tests run: eight times random actions and a step, yielding t behind each for the caller's resample."""
+    late = torch.arange(n, device=DEV) % 3 == 0  # these worlds restart after step 2: their episodes are out of step with the others'
+    for t in range(8):
+        sim.action_tensor().to_torch().copy_(torch.from_numpy(rng.integers(0, 4, size=(2, n, 1)).astype(np.int32)).to(DEV))
+        sim.step()
+        if t == 1:
+            sim.reset_worlds(late)
+        yield t
+
+
+def assert_mixed_done(seen, n, want_episodes):
+    """``seen``: the worlds with DONE set behind each step"""
+    assert 0 < min(x for x in seen if x) < n and (want_episodes > 40).all()  # DONE is a mix: some, not all, worlds finish at a time
+
 
 @pytest.mark.parametrize("players", [0b11, 0b01])
 @pytest.mark.parametrize("mode", ["robin", "random"])
 def test_resample_against_the_twin(mode, players, hip_lib):
     n = 33
     sim = make_sim(n)
-    rng = np.random.default_rng(3)
-    first, num = [1, 3], [3, 1]  # seat 0 draws from {1, 2, 3}, seat 1 from {3}: a range of one
-    ids_host = np.stack([rng.integers(1, 4, size=n), np.full(n, 3)], axis=1).astype(np.int32)
-    ids_host[rng.uniform(size=(n, 2)) < 0.2] = -1
+    rng, first, num, ids_host = resample_start(n)
     ids, episodes = torch.from_numpy(ids_host).to(DEV), torch.full((n,), 40, dtype=torch.int32, device=DEV)
     want_ids, want_episodes = ids_host.copy(), np.full(n, 40, np.int32)
-    late = torch.arange(n, device=DEV) % 3 == 0  # these worlds restart after step 2: their episodes are out of step with the others'
     seen = []
-    for t in range(8):
-        sim.action_tensor().to_torch().copy_(torch.from_numpy(rng.integers(0, 4, size=(2, n, 1)).astype(np.int32)).to(DEV))
-        sim.step()
-        if t == 1:
-            sim.reset_worlds(late)
+    for t in resample_schedule(sim, n, rng):
         mlpbase_resample(sim, ids, episodes, mode, first, num, players=players, seed=11)
         torch.cuda.synchronize()
         done = cpu(sim.done_tensor()).reshape(-1)
@@ -329,7 +303,7 @@ def test_resample_against_the_twin(mode, players, hip_lib):
             assert (moved[:, 0] == ((done != 0) & (before[:, 0] >= 0))).all()
         live = want_ids[:, 0] >= 0
         assert ((want_ids[live, 0] >= 1) & (want_ids[live, 0] <= 3)).all()
-    assert 0 < min(x for x in seen if x) < n and (want_episodes > 40).all()  # DONE is a mix: some, not all, worlds finish at a time
+    assert_mixed_done(seen, n, want_episodes)
     assert (want_ids < 0).sum() == (ids_host < 0).sum()
     # the descriptor may carry everything, under either name
     assert BankResample is CnnResample
@@ -337,6 +311,35 @@ def test_resample_against_the_twin(mode, players, hip_lib):
     torch.cuda.synchronize()
     resample_twin(want_ids, want_episodes, cpu(sim.done_tensor()).reshape(-1), mode, first, num, players, seed=11)
     same_bits(cpu(ids), want_ids, "through a descriptor: ids")
+    sim.close()
+
+
+@pytest.mark.parametrize("players", [0b11, 0b01])
+@pytest.mark.parametrize("mode", ["robin", "random"])
+def test_both_families_resample_the_beam_alike(mode, players, hip_lib):
+    """The resamples of the three families are one path behind the family's own check of the game.  The balance beam is the one
+    game two families play: ``mlpbase_resample`` and ``wide_resample`` from equal ids and episodes, behind the same steps, leave the
+    same bytes, and these are ``resample_twin``'s.  The steps, the late reset and the demand on DONE are those of
+    ``test_resample_against_the_twin``: neither "nobody finished" nor "everybody finished" passes."""
+    n = 33
+    sim = make_sim(n)
+    rng, first, num, ids_host = resample_start(n)
+    copies = {resample: (torch.from_numpy(ids_host).to(DEV), torch.full((n,), 40, dtype=torch.int32, device=DEV))
+              for resample in (mlpbase_resample, wide_resample)}
+    want_ids, want_episodes = ids_host.copy(), np.full(n, 40, np.int32)
+    seen = []
+    for t in resample_schedule(sim, n, rng):
+        for resample, (ids, episodes) in copies.items():
+            resample(sim, ids, episodes, mode, first, num, players=players, seed=11)
+        torch.cuda.synchronize()
+        done = cpu(sim.done_tensor()).reshape(-1)
+        seen.append(int((done != 0).sum()))
+        resample_twin(want_ids, want_episodes, done, mode, first, num, players, seed=11)
+        for resample, (ids, episodes) in copies.items():
+            same_bits(cpu(ids), want_ids, f"{resample.__name__}, {mode}, step {t}: ids")
+            same_bits(cpu(episodes), want_episodes, f"{resample.__name__}, {mode}, step {t}: episodes")
+    assert_mixed_done(seen, n, want_episodes)
+    assert (want_ids != ids_host).any() and (want_ids < 0).sum() == (ids_host < 0).sum()
     sim.close()
 
 

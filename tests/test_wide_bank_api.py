@@ -93,6 +93,41 @@ def test_refusals_without_a_device(hip_lib):
         wide_resample(NotAWideGame(), ids, torch.zeros(3, dtype=torch.int32), "robin", 0, 3)
 
 
+def test_the_three_resamples_refuse_the_same_arguments(hip_lib):
+    """``cnn_resample``, ``mlpbase_resample`` and ``wide_resample`` are one function behind their own check of the simulator: each
+    refuses a simulator of another game, ``ids`` of the wrong shape and ``episodes`` of the wrong dtype, before the library is
+    called (the simulators here were never created: no device is touched)"""
+    class Kitchen(simulators.OvercookedSimulator):
+        def __init__(self):
+            self.gpu_id = 0
+
+        def observation_world_major_tensor(self):
+            return torch.zeros((3, 2, 4, 5, 26), dtype=torch.int8)  # (N, P, H, W, F)
+
+    class Beam(simulators.BalanceBeamSimulator):
+        def __init__(self):
+            self.gpu_id = 0
+
+        def observation_tensor(self):
+            return torch.zeros((2, 3, 7), dtype=torch.int32)  # (P, N, 7)
+
+    cartpole = simulators.CartpoleSimulator.__new__(simulators.CartpoleSimulator)
+    ids, episodes = torch.zeros((3, 2), dtype=torch.int32), torch.zeros(3, dtype=torch.int32)
+    for resample, own in ((simulators.cnn_resample, Kitchen()), (simulators.mlpbase_resample, Beam()), (wide_resample, Beam())):
+        with pytest.raises(ValueError, match="Simulator"):
+            resample(cartpole, ids, episodes, "robin", 0, 3)
+        with pytest.raises(ValueError, match=r"ids must be a contiguous int32 tensor of shape \(3, 2\)"):
+            resample(own, torch.zeros((2, 3), dtype=torch.int32), episodes, "robin", 0, 3)
+        with pytest.raises(ValueError, match="must be a contiguous int32 tensor"):
+            resample(own, ids, torch.zeros(3, dtype=torch.int64), "robin", 0, 3)
+    with pytest.raises(ValueError, match="OvercookedSimulator"):
+        simulators.cnn_resample(Beam(), ids, episodes, "robin", 0, 3)
+    with pytest.raises(ValueError, match="BalanceBeamSimulator"):
+        simulators.mlpbase_resample(Kitchen(), ids, episodes, "robin", 0, 3)
+    with pytest.raises(ValueError, match="HanabiSimulator or a BalanceBeamSimulator"):
+        wide_resample(Kitchen(), ids, episodes, "robin", 0, 3)
+
+
 def test_cross_play_refuses_a_kitchen(hip_lib):
     """dispatched on the bank's type, refused on the env's: a wide bank does not play a kitchen"""
     bank = WidePolicyBank(7, 7, 4, 2, device="cpu")
