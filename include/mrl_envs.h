@@ -1163,6 +1163,64 @@ int mrl_rollout_mlpbase_bank(mrl_sim *sim, uint32_t players, const mrl_mlpbase_b
                              const mrl_cnn_resample *resample_or_null, const mrl_mlpbase_record *record, int32_t *ids_record_or_null,
                              uint64_t seed, uint32_t first_step, void *workspace_dev, uint64_t workspace_bytes, void *hip_stream);
 
+/* Training every member of a bank in one call: mrl_mappo_update and mrl_mappo_mlp_update with a member dimension, so that the
+ * record one bank rollout wrote -- every cell under its own policy -- trains the whole population in the launches one policy
+ * takes.  No reference counterpart as calls (the reference trains a population one run per seed).  DESIGN.md section 22.
+ *   Bank (mrl_mappo_bank_optimizer): params_dev, exp_avg and exp_avg_sq are float32 device arrays of K = num_policies rows,
+ *     row_bytes BYTES apart (one stride for all three; a multiple of 4, at least 4 P with P the policy's parameter count; a dense
+ *     (K, P) tensor has row_bytes = 4 P).  Row k of params_dev is exactly what mrl_cnn_bank / mrl_mlpbase_bank call row k, and
+ *     rows k of the three arrays are an mrl_mappo_optimizer's arrays: a member can also be stepped alone by the plain call.  1 <=
+ *     K <= 256.  step: the Adam steps every member has taken before this call, one number for the bank.  The call trains the M =
+ *     num_members consecutive rows first_member, ..., first_member + M - 1; no other row of any array is read or written.
+ *     policy->params_dev must be opt->params_dev, the bank's first row, whatever first_member is.
+ *   Arrays with a member dimension, member z = 0 .. M - 1 being bank row first_member + z:
+ *         indices           (M, R, B) int32: row r of member z takes the samples indices[z, r, :]; R = num_minibatches and B =
+ *                           minibatch_size are the same for every member
+ *         value_norm_state  (K, 3) float32 or NULL: row k is bank row k's ValueNorm state (indexed by bank row, as the moments are)
+ *         stats             (M, R, 8) or NULL;  grads (M, R, P) or NULL
+ *         workspace         M times the plain call's: member z uses the bytes [z w, (z + 1) w), w = mrl_mappo_workspace_bytes (or
+ *                           mrl_mappo_mlp_workspace_bytes) for the same shape, B and R, laid out as the plain call lays them out.
+ *                           mrl_mappo_bank_workspace_bytes and mrl_mappo_mlp_bank_workspace_bytes return M w; like w it stops
+ *                           growing with B at 256 partial vectors per net.
+ *     The batch (the record's arrays, the observations, advantages, returns) and cfg -- both learning rates included -- are
+ *     shared by all members.
+ *   What a member computes: exactly the plain call on (its row of the bank and of the moments, step, its row of the ValueNorm
+ *     state, indices[z], the shared batch and cfg) -- the same tiles, the same share of samples per workgroup (a function of B
+ *     alone), the same chains of sums, its own two clip_grad_norm_ norms -- so bank row first_member + z, both moment rows, the
+ *     ValueNorm row, stats[z] and grads[z] are bit for bit what that plain call leaves.  Members read nothing of each other.
+ *   Launches: two up front with MRL_MAPPO_VALUENORM, then three per row, 2 + 3 R whatever M is: every kernel of the plain call
+ *     with the member as a third grid dimension.  No float atomics, no wait between workgroups, no scratch memory: same inputs,
+ *     same bits; one call of R rows gives the bits of R calls of one row.
+ *   MRL_ERR_INVALID, nothing enqueued and nothing changed: everything the plain call refuses (with "opt's arrays" read as the
+ *     bank's); num_members == 0; first_member + num_members > num_policies; num_policies == 0 or > 256; row_bytes below 4 P or
+ *     not a multiple of 4; a workspace below M w or off a 16-byte boundary.  R == 0 enqueues nothing.  The workspace functions
+ *     refuse the plain ones' shapes, num_members == 0 or > 256 and a NULL out.
+ *   Not built: members with different B, learning rates or step counts; member sets that are not consecutive rows; the wide
+ *     policy's bank. */
+typedef struct mrl_mappo_bank_optimizer {
+    float *params_dev;           /* (K, row_bytes / 4): the bank's params_dev; updated in place */
+    float *exp_avg, *exp_avg_sq; /* (K, row_bytes / 4) each */
+    uint64_t row_bytes;          /* bytes between rows of all three */
+    uint32_t num_policies;       /* K */
+    uint32_t first_member, num_members;
+    uint32_t step;               /* Adam steps taken BEFORE this call, by every member */
+} mrl_mappo_bank_optimizer;
+int mrl_mappo_bank_workspace_bytes(uint32_t width, uint32_t height, uint32_t channels, uint32_t hidden, uint32_t minibatch_size,
+                                   uint32_t num_minibatches, uint32_t num_members, uint64_t *out);
+int mrl_mappo_bank_update(const mrl_mappo_policy *policy, const mrl_mappo_bank_optimizer *opt, const mrl_mappo_batch *batch,
+                          const int32_t *indices_dev /* (M, R, B) */, uint32_t num_minibatches /* R */, uint32_t minibatch_size /* B */,
+                          const mrl_mappo_config *cfg, float *value_norm_state_dev_or_null /* (K, 3) */, void *workspace_dev,
+                          uint64_t workspace_bytes, float *stats_dev_or_null /* (M, R, 8) */, float *grads_dev_or_null /* (M, R, P) */,
+                          int gpu_id, void *hip_stream);
+int mrl_mappo_mlp_bank_workspace_bytes(uint32_t obs_dim, uint32_t hidden, uint32_t layer_N, uint32_t num_actions, uint32_t minibatch_size,
+                                       uint32_t num_minibatches, uint32_t num_members, uint64_t *out);
+int mrl_mappo_mlp_bank_update(const mrl_mlpbase_policy *policy, const mrl_mappo_bank_optimizer *opt, const mrl_mappo_mlp_batch *batch,
+                              const int32_t *indices_dev /* (M, R, B) */, uint32_t num_minibatches /* R */,
+                              uint32_t minibatch_size /* B */, const mrl_mappo_config *cfg,
+                              float *value_norm_state_dev_or_null /* (K, 3) */, void *workspace_dev, uint64_t workspace_bytes,
+                              float *stats_dev_or_null /* (M, R, 8) */, float *grads_dev_or_null /* (M, R, P) */, int gpu_id,
+                              void *hip_stream);
+
 /* A population of partners for Hanabi and the balance beam under the wide policy: a BANK of K policies of mrl_agent_act's shape
  * and a policy per world for the seat that acts -- add_partner_agent's "randomly samples" a partner "at the start of every
  * episode" (pantheonrl_extension/vectorenv.py:89-98), per world.  No reference counterpart as calls.  DESIGN.md section 21.

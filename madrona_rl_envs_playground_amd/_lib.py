@@ -59,7 +59,8 @@ SYMBOLS = [
     "mrl_rollout_mlpbase", "mrl_mappo_mlp_workspace_bytes", "mrl_mappo_mlp_update", "mrl_cnn_bank_workspace_bytes",
     "mrl_cnn_act_bank", "mrl_cnn_bank_resample", "mrl_rollout_cnn_bank", "mrl_mlpbase_bank_workspace_bytes", "mrl_mlpbase_act_bank",
     "mrl_mlpbase_bank_resample", "mrl_rollout_mlpbase_bank", "mrl_agent_bank_workspace_bytes", "mrl_agent_act_bank",
-    "mrl_agent_bank_resample",
+    "mrl_agent_bank_resample", "mrl_mappo_bank_workspace_bytes", "mrl_mappo_bank_update", "mrl_mappo_mlp_bank_workspace_bytes",
+    "mrl_mappo_mlp_bank_update",
 ]
 ABI_VERSION = 4  # MRL_ABI_VERSION of include/mrl_envs.h this binding was written against
 
@@ -163,6 +164,12 @@ class MappoBatch(ctypes.Structure):  # mrl_mappo_batch
 class MappoOptimizerDesc(ctypes.Structure):  # mrl_mappo_optimizer
     _fields_ = [("params_dev", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p),
                 ("step", ctypes.c_uint32)]
+
+
+class MappoBankOptimizerDesc(ctypes.Structure):  # mrl_mappo_bank_optimizer
+    _fields_ = [("params_dev", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p),
+                ("row_bytes", ctypes.c_uint64), ("num_policies", ctypes.c_uint32), ("first_member", ctypes.c_uint32),
+                ("num_members", ctypes.c_uint32), ("step", ctypes.c_uint32)]
 
 
 class MlpBasePolicyDesc(ctypes.Structure):  # mrl_mlpbase_policy
@@ -347,6 +354,13 @@ def lib():
     L.mrl_agent_act_bank.argtypes = [vp, u32, ctypes.POINTER(WideBankDesc), vp, vp, ctypes.c_uint64, u32, u32, vp, ctypes.c_uint64, vp]
     L.mrl_agent_bank_resample.argtypes = [vp, u32, ctypes.POINTER(CnnResampleDesc), vp, vp, vp]
     L.mrl_mappo_mlp_workspace_bytes.argtypes = [u32, u32, u32, u32, u32, u32, ctypes.POINTER(ctypes.c_uint64)]
+    L.mrl_mappo_bank_workspace_bytes.argtypes = [u32, u32, u32, u32, u32, u32, u32, ctypes.POINTER(ctypes.c_uint64)]
+    L.mrl_mappo_mlp_bank_workspace_bytes.argtypes = [u32, u32, u32, u32, u32, u32, u32, ctypes.POINTER(ctypes.c_uint64)]
+    L.mrl_mappo_bank_update.argtypes = [ctypes.POINTER(MappoPolicyDesc), ctypes.POINTER(MappoBankOptimizerDesc), ctypes.POINTER(MappoBatch),
+                                        vp, u32, u32, ctypes.POINTER(MappoConfig), vp, vp, ctypes.c_uint64, vp, vp, i32, vp]
+    L.mrl_mappo_mlp_bank_update.argtypes = [ctypes.POINTER(MlpBasePolicyDesc), ctypes.POINTER(MappoBankOptimizerDesc),
+                                            ctypes.POINTER(MappoMlpBatch), vp, u32, u32, ctypes.POINTER(MappoConfig), vp, vp,
+                                            ctypes.c_uint64, vp, vp, i32, vp]
     L.mrl_mappo_mlp_update.argtypes = [ctypes.POINTER(MlpBasePolicyDesc), ctypes.POINTER(MappoOptimizerDesc), ctypes.POINTER(MappoMlpBatch),
                                        vp, u32, u32, ctypes.POINTER(MappoConfig), vp, vp, ctypes.c_uint64, vp, vp, i32, vp]
     L.mrl_tensor.argtypes = [vp, i32, ctypes.POINTER(TensorDesc)]

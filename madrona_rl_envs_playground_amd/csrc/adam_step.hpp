@@ -1,7 +1,10 @@
 // The second half of every device update (ppo_update.hip, cnn_update.hip; DESIGN.md section 13, "The optimiser tail"): the
 // workgroups' partial gradient vectors become one gradient, clip_grad_norm_ and torch.optim.Adam's single-tensor step, TWO
 // launches after the algorithm's own gradient kernel.  The parameters are up to two SEGMENTS (blockIdx.y), each with its own
-// norm, clip and learning rate: PPO's two nets are one segment, MAPPO's actor and critic one each.
+// norm, clip and learning rate: PPO's two nets are one segment, MAPPO's actor and critic one each.  A bank update (DESIGN.md
+// section 22) steps several MEMBERS in the same two launches (blockIdx.z), each on its own arrays a fixed number of floats behind
+// the previous member's: the MEMBERS = true instances of the two kernels.  The MEMBERS = false instances, which every other
+// update launches, read neither blockIdx.z nor the strides and compile to the instructions the kernels had without members.
 // No float atomics and no wait on another workgroup: the same inputs give the same bits on every run.
 #pragma once
 
@@ -60,6 +63,9 @@ struct AdamStepArgs {
     uint32_t at[kAdamSegments];             // ... and where they start in params, exp_avg, exp_avg_sq and grads_row
     float step_size[kAdamSegments];
     float max_grad_norm, bias2_sqrt, beta1, beta2, one_minus_beta1, one_minus_beta2, eps;
+    // MEMBERS only -- floats from a member's arrays to the next member's: the scratch (partial_grads, grad, sumsq), the bank's
+    // rows (params, exp_avg, exp_avg_sq), grads_row.  (Last, so that every other field is where it was.)
+    uint64_t member_scratch, member_params, member_grads_row;
 };
 
 // what does not change from row to row; the caller adds the arrays and the segments
@@ -85,28 +91,37 @@ inline void adam_set_step(AdamStepArgs &a, double t, const float (&lr)[kAdamSegm
     a.bias2_sqrt = (float)std::sqrt(1.0 - std::pow((double)a.beta2, t));
 }
 
+// member blockIdx.z's array behind the first member's (MEMBERS), or the array itself: the kernels below never write to their
+// argument struct, which would send all of it to scratch memory
+template <bool MEMBERS, typename T>
+__device__ __forceinline__ T *member_array(T *first, uint64_t stride)
+{
+    return MEMBERS ? first + (size_t)blockIdx.z * stride : first;
+}
+
 // adds the partial vectors in ascending workgroup order and forms per-block sums of g^2.  (A template, as mrl_clip_adam has to
 // be one: the header is compiled into more than one object.)
-template <int THREADS>
+template <int THREADS, bool MEMBERS = false>
 __global__ void __launch_bounds__(THREADS) mrl_grad_reduce(AdamStepArgs a)
 {
     __shared__ float scratch[THREADS];
     if (a.skip && *a.skip) return;  // (uniform over the grid)
     const uint32_t seg = blockIdx.y, p = blockIdx.x * THREADS + threadIdx.x;
-    const float *__restrict__ partial = a.partial_grads + (size_t)seg * a.groups * a.stride;
+    const float *__restrict__ partial = member_array<MEMBERS>(a.partial_grads, a.member_scratch) + (size_t)seg * a.groups * a.stride;
     float g = 0.0f;
     if (p < a.num_params[seg]) {
         for (uint32_t w = 0; w < a.groups; w++) g += partial[(size_t)w * a.stride + p];
-        a.grad[(size_t)seg * a.stride + p] = g;
-        if (a.grads_row) a.grads_row[a.at[seg] + p] = g;
+        member_array<MEMBERS>(a.grad, a.member_scratch)[(size_t)seg * a.stride + p] = g;
+        if (a.grads_row) member_array<MEMBERS>(a.grads_row, a.member_grads_row)[a.at[seg] + p] = g;
     }
     const float total = block_sum<THREADS>(g * g, scratch);  // (a block past the segment's end adds 0 to its norm)
-    if (threadIdx.x == 0) a.sumsq[seg * a.blocks + blockIdx.x] = total;
+    if (threadIdx.x == 0) member_array<MEMBERS>(a.sumsq, a.member_scratch)[seg * a.blocks + blockIdx.x] = total;
 }
 
 // clip_grad_norm_ and torch.optim.Adam's single-tensor step, per segment.  Thread 0 of block 0 of each segment then calls
-// stats(segment, total norm), the algorithm's own end of the stats row (with a non-zero skip word: stats(segment, 0) alone).
-template <typename STATS>
+// stats(segment, total norm), the algorithm's own end of the stats row (with a non-zero skip word: stats(segment, 0) alone); a
+// functor that serves several members reads blockIdx.z itself.
+template <typename STATS, bool MEMBERS = false>
 __global__ void __launch_bounds__(kAdamThreads) mrl_clip_adam(AdamStepArgs a, STATS stats)
 {
     const uint32_t seg = blockIdx.y;
@@ -115,18 +130,19 @@ __global__ void __launch_bounds__(kAdamThreads) mrl_clip_adam(AdamStepArgs a, ST
         return;
     }
     float squares = 0.0f;
-    for (uint32_t b = 0; b < a.blocks; b++) squares += a.sumsq[seg * a.blocks + b];
+    for (uint32_t b = 0; b < a.blocks; b++) squares += member_array<MEMBERS>(a.sumsq, a.member_scratch)[seg * a.blocks + b];
     const float total = sqrtf(squares);
     const float scale = a.clip ? fminf(a.max_grad_norm / (total + 1e-6f), 1.0f) : 1.0f;
     const uint32_t p = blockIdx.x * kAdamThreads + threadIdx.x;
     if (p < a.num_params[seg]) {
         const size_t at = (size_t)a.at[seg] + p;
-        const float g = a.grad[(size_t)seg * a.stride + p] * scale;
-        const float m = a.beta1 * a.exp_avg[at] + a.one_minus_beta1 * g;
-        const float v = a.beta2 * a.exp_avg_sq[at] + a.one_minus_beta2 * (g * g);
-        a.exp_avg[at] = m;
-        a.exp_avg_sq[at] = v;
-        a.params[at] -= a.step_size[seg] * (m / (sqrtf(v) / a.bias2_sqrt + a.eps));
+        float *exp_avg = member_array<MEMBERS>(a.exp_avg, a.member_params), *exp_avg_sq = member_array<MEMBERS>(a.exp_avg_sq, a.member_params);
+        const float g = member_array<MEMBERS>(a.grad, a.member_scratch)[(size_t)seg * a.stride + p] * scale;
+        const float m = a.beta1 * exp_avg[at] + a.one_minus_beta1 * g;
+        const float v = a.beta2 * exp_avg_sq[at] + a.one_minus_beta2 * (g * g);
+        exp_avg[at] = m;
+        exp_avg_sq[at] = v;
+        member_array<MEMBERS>(a.params, a.member_params)[at] -= a.step_size[seg] * (m / (sqrtf(v) / a.bias2_sqrt + a.eps));
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) stats(seg, total);
 }
@@ -139,6 +155,17 @@ inline void launch_adam_step(const AdamStepArgs &a, const STATS &stats, hipStrea
     hipLaunchKernelGGL(mrl_grad_reduce<(int)kAdamThreads>, grid, dim3(kAdamThreads), 0, stream, a);
     MRL_HIP(hipGetLastError());
     hipLaunchKernelGGL(mrl_clip_adam<STATS>, grid, dim3(kAdamThreads), 0, stream, a, stats);
+    MRL_HIP(hipGetLastError());
+}
+
+// the same two launches for `members` members of a bank (a's member strides set; `stats` reads blockIdx.z itself)
+template <typename STATS>
+inline void launch_adam_step_members(const AdamStepArgs &a, const STATS &stats, uint32_t members, hipStream_t stream)
+{
+    const dim3 grid(a.blocks, a.segments, members);
+    hipLaunchKernelGGL((mrl_grad_reduce<(int)kAdamThreads, true>), grid, dim3(kAdamThreads), 0, stream, a);
+    MRL_HIP(hipGetLastError());
+    hipLaunchKernelGGL((mrl_clip_adam<STATS, true>), grid, dim3(kAdamThreads), 0, stream, a, stats);
     MRL_HIP(hipGetLastError());
 }
 

@@ -1296,13 +1296,14 @@ int mrl_mappo_workspace_bytes(uint32_t width, uint32_t height, uint32_t channels
 // What mrl_mappo_update and mrl_mappo_mlp_update (`what`; `sizer`: its workspace function) refuse alike.  The network's own part
 // comes from the caller once the pointers are known to be there: shape(described) returns why the shape cannot run, or nullptr,
 // and describes the shape for the message; actor_params() is the actor's parameter count; obs_words: the batch's observations
-// are 4-byte words, to be checked with the other arrays.
+// are 4-byte words, to be checked with the other arrays.  members: the workspace must hold that many plain ones (the bank updates).
 extern "C++" {
 template <class Policy, class Batch, class Shape, class ActorParams>
 static int mappo_update_refusal(const char *what, const char *sizer, const Policy *policy, const mrl_mappo_optimizer *opt, const Batch *batch,
                                 const int32_t *indices_dev, uint32_t num_minibatches, uint32_t minibatch_size, const mrl_mappo_config *cfg,
                                 float *value_norm_state, void *workspace_dev, uint64_t workspace_bytes, float *stats_dev_or_null,
-                                float *grads_dev_or_null, void *hip_stream, bool obs_words, Shape shape, ActorParams actor_params)
+                                float *grads_dev_or_null, void *hip_stream, bool obs_words, Shape shape, ActorParams actor_params,
+                                uint32_t members = 1)
 {
     if (!policy || !opt || !batch || (!indices_dev && num_minibatches) || !cfg || !workspace_dev) {  // (no rows: no index array)
         mrl::set_error("%s: null policy, optimizer, batch, index array, configuration or workspace", what);
@@ -1332,7 +1333,7 @@ static int mappo_update_refusal(const char *what, const char *sizer, const Polic
                        minibatch_size, batch->size);
         return MRL_ERR_INVALID;
     }
-    const uint64_t need_bytes = mrl::mappo_workspace(actor_params(), minibatch_size, num_minibatches).total * sizeof(float);
+    const uint64_t need_bytes = members * mrl::mappo_workspace(actor_params(), minibatch_size, num_minibatches).total * sizeof(float);
     const void *words[] = {opt->params_dev, opt->exp_avg, opt->exp_avg_sq, obs_words ? batch->obs : nullptr, batch->actions, batch->logprobs,
                            batch->value_preds, batch->returns, batch->advantages, indices_dev, value_norm_state, stats_dev_or_null,
                            grads_dev_or_null};
@@ -1340,6 +1341,38 @@ static int mappo_update_refusal(const char *what, const char *sizer, const Polic
     for (const void *p : words) low_bits |= reinterpret_cast<uintptr_t>(p) & 3u;
     return update_refusal(what, sizer, workspace_bytes, need_bytes, workspace_dev, low_bits,
                           "the float and int32 arrays must start on 4-byte boundaries", hip_stream);
+}
+
+// What mrl_mappo_bank_update and mrl_mappo_mlp_bank_update (`what`) refuse of the bank itself, `num_params` being one policy's
+// parameter count; the plain calls' refusals follow on `first`, the bank's arrays as an mrl_mappo_optimizer.
+static int mappo_bank_refusal(const char *what, const mrl_mappo_bank_optimizer *opt, uint64_t num_params, mrl_mappo_optimizer *first)
+{
+    if (!opt) {
+        mrl::set_error("%s: null optimizer", what);
+        return MRL_ERR_INVALID;
+    }
+    if (opt->num_policies == 0 || opt->num_policies > mrl::kBankMaxPolicies || opt->num_members == 0 ||
+        (uint64_t)opt->first_member + opt->num_members > opt->num_policies) {
+        mrl::set_error("%s: members [%u, %u + %u) of a bank of %u policies: a bank holds 1 to %u and the call trains at least one of them", what,
+                       opt->first_member, opt->first_member, opt->num_members, opt->num_policies, mrl::kBankMaxPolicies);
+        return MRL_ERR_INVALID;
+    }
+    if ((opt->row_bytes & 3u) || opt->row_bytes / 4u < num_params) {
+        mrl::set_error("%s: row_bytes %llu: the bank's rows must lie a multiple of 4 bytes and at least %llu floats apart", what,
+                       (unsigned long long)opt->row_bytes, (unsigned long long)num_params);
+        return MRL_ERR_INVALID;
+    }
+    *first = mrl_mappo_optimizer{opt->params_dev, opt->exp_avg, opt->exp_avg_sq, opt->step};
+    return MRL_OK;
+}
+
+// the first trained member's rows of the bank's arrays, the ValueNorm state included, and the member dimension of the launches
+static mrl::MappoMembers mappo_bank_members(const mrl_mappo_bank_optimizer &opt, mrl_mappo_optimizer *first, float **value_norm_state)
+{
+    const uint64_t stride = opt.row_bytes / 4u, at = opt.first_member * stride;
+    first->params_dev += at, first->exp_avg += at, first->exp_avg_sq += at;
+    if (*value_norm_state) *value_norm_state += 3u * opt.first_member;
+    return mrl::MappoMembers{opt.num_members, stride};
 }
 }  // extern "C++"
 
@@ -1362,6 +1395,45 @@ int mrl_mappo_update(const mrl_mappo_policy *policy, const mrl_mappo_optimizer *
     return guarded([&] {
         mrl::launch_mappo_update(*policy, *opt, *batch, indices_dev, num_minibatches, minibatch_size, *cfg, value_norm_state,
                                  static_cast<float *>(workspace_dev), stats_dev_or_null, grads_dev_or_null, (hipStream_t)hip_stream);
+    });
+}
+
+int mrl_mappo_bank_workspace_bytes(uint32_t width, uint32_t height, uint32_t channels, uint32_t hidden, uint32_t minibatch_size,
+                                   uint32_t num_minibatches, uint32_t num_members, uint64_t *out)
+{
+    if (num_members == 0 || num_members > mrl::kBankMaxPolicies) {
+        mrl::set_error("mrl_mappo_bank_workspace_bytes: %u members: a call trains 1 to %u", num_members, mrl::kBankMaxPolicies);
+        return MRL_ERR_INVALID;
+    }
+    if (int rc = mrl_mappo_workspace_bytes(width, height, channels, hidden, minibatch_size, num_minibatches, out)) return rc;
+    *out *= num_members;
+    return MRL_OK;
+}
+
+int mrl_mappo_bank_update(const mrl_mappo_policy *policy, const mrl_mappo_bank_optimizer *opt, const mrl_mappo_batch *batch,
+                          const int32_t *indices_dev, uint32_t num_minibatches, uint32_t minibatch_size, const mrl_mappo_config *cfg,
+                          float *value_norm_state, void *workspace_dev, uint64_t workspace_bytes, float *stats_dev_or_null,
+                          float *grads_dev_or_null, int gpu_id, void *hip_stream)
+{
+    const char *what = "mrl_mappo_bank_update";
+    mrl_mappo_optimizer first{};
+    const uint64_t num_params = policy ? mrl_cnn_policy_num_params(policy->width, policy->height, policy->channels, policy->hidden, mrl::kCnnActions) : 0;
+    if (int rc = mappo_bank_refusal(what, opt, num_params, &first)) return rc;
+    if (int rc = mappo_update_refusal(
+            what, "mrl_mappo_bank_workspace_bytes", policy, &first, batch, indices_dev, num_minibatches, minibatch_size, cfg, value_norm_state,
+            workspace_dev, workspace_bytes, stats_dev_or_null, grads_dev_or_null, hip_stream, false,
+            [&](char *described, size_t room) {
+                snprintf(described, room, "width %u, height %u, channels %u, hidden %u", policy->width, policy->height, policy->channels,
+                         policy->hidden);
+                return mappo_shape_error(policy->width, policy->height, policy->channels, policy->hidden, minibatch_size);
+            },
+            [&] { return mrl::cnn_net_params(policy->width, policy->height, policy->channels, mrl::kCnnActions); }, opt->num_members))
+        return rc;
+    const mrl::MappoMembers members = mappo_bank_members(*opt, &first, &value_norm_state);
+    mrl::DeviceGuard on(gpu_id);
+    return guarded([&] {
+        mrl::launch_mappo_update(*policy, first, *batch, indices_dev, num_minibatches, minibatch_size, *cfg, value_norm_state,
+                                 static_cast<float *>(workspace_dev), stats_dev_or_null, grads_dev_or_null, (hipStream_t)hip_stream, members);
     });
 }
 
@@ -1839,6 +1911,44 @@ int mrl_mappo_mlp_update(const mrl_mlpbase_policy *policy, const mrl_mappo_optim
     return guarded([&] {
         mrl::launch_mappo_mlp_update(policy->layer_N, *opt, *batch, indices_dev, num_minibatches, minibatch_size, *cfg, value_norm_state,
                                      static_cast<float *>(workspace_dev), stats_dev_or_null, grads_dev_or_null, (hipStream_t)hip_stream);
+    });
+}
+
+int mrl_mappo_mlp_bank_workspace_bytes(uint32_t obs_dim, uint32_t hidden, uint32_t layer_N, uint32_t num_actions, uint32_t minibatch_size,
+                                       uint32_t num_minibatches, uint32_t num_members, uint64_t *out)
+{
+    if (num_members == 0 || num_members > mrl::kBankMaxPolicies) {
+        mrl::set_error("mrl_mappo_mlp_bank_workspace_bytes: %u members: a call trains 1 to %u", num_members, mrl::kBankMaxPolicies);
+        return MRL_ERR_INVALID;
+    }
+    if (int rc = mrl_mappo_mlp_workspace_bytes(obs_dim, hidden, layer_N, num_actions, minibatch_size, num_minibatches, out)) return rc;
+    *out *= num_members;
+    return MRL_OK;
+}
+
+int mrl_mappo_mlp_bank_update(const mrl_mlpbase_policy *policy, const mrl_mappo_bank_optimizer *opt, const mrl_mappo_mlp_batch *batch,
+                              const int32_t *indices_dev, uint32_t num_minibatches, uint32_t minibatch_size, const mrl_mappo_config *cfg,
+                              float *value_norm_state, void *workspace_dev, uint64_t workspace_bytes, float *stats_dev_or_null,
+                              float *grads_dev_or_null, int gpu_id, void *hip_stream)
+{
+    const char *what = "mrl_mappo_mlp_bank_update";
+    mrl_mappo_optimizer first{};
+    const uint64_t num_params = policy ? mrl_mlpbase_policy_num_params(mrl::kMlpBaseObs, policy->hidden, policy->layer_N, mrl::kMlpBaseActions) : 0;
+    if (int rc = mappo_bank_refusal(what, opt, num_params, &first)) return rc;
+    if (int rc = mappo_update_refusal(
+            what, "mrl_mappo_mlp_bank_workspace_bytes", policy, &first, batch, indices_dev, num_minibatches, minibatch_size, cfg, value_norm_state,
+            workspace_dev, workspace_bytes, stats_dev_or_null, grads_dev_or_null, hip_stream, true,
+            [&](char *described, size_t room) {
+                snprintf(described, room, "hidden %u, layer_N %u", policy->hidden, policy->layer_N);
+                return mappo_mlp_shape_error(mrl::kMlpBaseObs, policy->hidden, policy->layer_N, mrl::kMlpBaseActions, minibatch_size);
+            },
+            [&] { return (uint64_t)mrl::mlpbase_net_params(policy->layer_N, mrl::kMlpBaseActions); }, opt->num_members))
+        return rc;
+    const mrl::MappoMembers members = mappo_bank_members(*opt, &first, &value_norm_state);
+    mrl::DeviceGuard on(gpu_id);
+    return guarded([&] {
+        mrl::launch_mappo_mlp_update(policy->layer_N, first, *batch, indices_dev, num_minibatches, minibatch_size, *cfg, value_norm_state,
+                                     static_cast<float *>(workspace_dev), stats_dev_or_null, grads_dev_or_null, (hipStream_t)hip_stream, members);
     });
 }
 

@@ -16,6 +16,9 @@
 //   mrl_grad_reduce   adds the partial vectors in ascending workgroup order and forms per-block sums of g^2, per net.
 //   mrl_clip_adam     per net: total norm, clip, Adam with the net's learning rate, and the net's columns of the stats row
 //                     (adam_step.hpp: the tail every update shares; each net is a segment).
+// mrl_mappo_bank_update is the same launches with a third grid dimension, the member of the bank: a
+// member's workgroups read its own parameters, indices and ValueNorm rows and write its own partial vectors (the kernels'
+// MEMBERS = true instances; the plain update runs the MEMBERS = false ones, which are the kernels as they were).
 // No float atomics and no wait on another workgroup anywhere: the same inputs give the same bits on every run.
 // The per-sample losses, the accumulator tiles and the stats row's end are mappo_loss.hpp's; the sample table, the loss head, the
 // backward pass of the head and of fc2, the bias-column sums, the stats' tail and the host's row loop are mappo_grad.hpp's: both
@@ -42,18 +45,22 @@ struct MappoGradArgs {
     MappoGradCommon common;
     CnnActArgs fwd;  // W, H, F and the LDS image of the forward pass; params
     uint32_t tail_at;
+    MappoMemberStrides members;  // MEMBERS only
 };
 
+// MEMBERS: member blockIdx.z of a bank update, on its own parameters, indices, ValueNorm rows and partial vectors
+template <bool MEMBERS>
 __global__ void __launch_bounds__(kCnnThreads) mrl_mappo_grad(MappoGradArgs a)
 {
-    const MappoGradCommon &c = a.common;
+    const MappoGradCommon own = MEMBERS ? mappo_member_view(a.common, a.members) : MappoGradCommon{};
+    const MappoGradCommon &c = MEMBERS ? own : a.common;
     const CnnActArgs &f = a.fwd;
     const CnnLds &l = f.lds;
     const uint32_t net = blockIdx.y;  // 0 the actor, 1 the critic
     const uint32_t tid0 = threadIdx.x;
     const uint32_t k1 = l.k1, npos = l.npos, K2 = kCnnChannels * npos, out_dim = net ? 1u : kCnnActions, act_ld = l.act_ld;
     const size_t net_at = net ? cnn_net_params(f.W, f.H, f.F, kCnnActions) : 0;
-    const float *__restrict__ conv_w = f.params + net_at;
+    const float *__restrict__ conv_w = f.params + (MEMBERS ? (size_t)blockIdx.z * a.members.params : 0) + net_at;
     const float *__restrict__ conv_b = conv_w + (size_t)kCnnChannels * k1;
     const float *__restrict__ fc1_w = conv_b + kCnnChannels, *__restrict__ fc1_b = fc1_w + (size_t)kCnnHidden * K2;
     const float *__restrict__ fc2_w = fc1_b + kCnnHidden, *__restrict__ fc2_b = fc2_w + kCnnHidden * kCnnHidden;
@@ -188,12 +195,15 @@ __global__ void __launch_bounds__(kCnnThreads) mrl_mappo_grad(MappoGradArgs a)
     mappo_stats_tail(c, net, reinterpret_cast<double *>(lds), stat, tid0);
 }
 
-// ValueNorm, first launch: the mean and the mean of squares of every row's gathered returns, one workgroup per row
+// ValueNorm, first launch: the mean and the mean of squares of every row's gathered returns, one workgroup per (row, member);
+// a member's row_sums lie member_scratch floats behind the previous member's
 __global__ void __launch_bounds__(kStatThreads) mrl_mappo_row_sums(const float *__restrict__ returns, const int32_t *__restrict__ indices,
-                                                                  uint32_t minibatch_size, uint32_t batch_size, float *__restrict__ row_sums)
+                                                                  uint32_t minibatch_size, uint32_t batch_size, float *__restrict__ row_sums,
+                                                                  uint64_t member_scratch)
 {
     __shared__ double scratch[kStatThreads];
-    const int32_t *row = indices + (size_t)blockIdx.x * minibatch_size;
+    const int32_t *row = indices + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * minibatch_size;
+    row_sums += (size_t)blockIdx.y * member_scratch;
     double sum = 0.0, squares = 0.0;
     for (uint64_t b = threadIdx.x; b < minibatch_size; b += kStatThreads) {  // (64 bits: B may be within 1024 of 2^32)
         uint32_t s = (uint32_t)row[b];
@@ -209,11 +219,15 @@ __global__ void __launch_bounds__(kStatThreads) mrl_mappo_row_sums(const float *
     }
 }
 
-// ValueNorm, second launch: utils/valuenorm.py's update and running_mean_var over the K rows, one thread, float32 as torch's
+// ValueNorm, second launch: utils/valuenorm.py's update and running_mean_var over the K rows, one thread per member (a
+// workgroup each), float32 as torch's; member blockIdx.x has state row blockIdx.x of (members, 3)
 __global__ void mrl_mappo_value_norm(const float *__restrict__ row_sums, uint32_t rows, float beta, float one_minus_beta, float epsilon,
-                                     float *__restrict__ state, float *__restrict__ row_norm)
+                                     float *__restrict__ state, float *__restrict__ row_norm, uint64_t member_scratch)
 {
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    if (threadIdx.x != 0) return;
+    row_sums += (size_t)blockIdx.x * member_scratch;
+    row_norm += (size_t)blockIdx.x * member_scratch;
+    state += 3u * blockIdx.x;
     float mean = state[0], mean_sq = state[1], debias = state[2];
     for (uint32_t k = 0; k < rows; k++) {
         mean = mean * beta + row_sums[2 * k] * one_minus_beta;
@@ -233,24 +247,26 @@ __global__ void mrl_mappo_value_norm(const float *__restrict__ row_sums, uint32_
 
 void launch_mappo_value_norm(const float *returns, const int32_t *indices, uint32_t num_minibatches, uint32_t minibatch_size,
                              uint32_t batch_size, const mrl_mappo_config &cfg, float *state, float *row_sums, float *row_norm,
-                             hipStream_t stream)
+                             hipStream_t stream, uint32_t members, uint64_t member_scratch)
 {
-    hipLaunchKernelGGL(mrl_mappo_row_sums, dim3(num_minibatches), dim3(kStatThreads), 0, stream, returns, indices, minibatch_size, batch_size,
-                       row_sums);
+    hipLaunchKernelGGL(mrl_mappo_row_sums, dim3(num_minibatches, members), dim3(kStatThreads), 0, stream, returns, indices, minibatch_size,
+                       batch_size, row_sums, member_scratch);
     MRL_HIP(hipGetLastError());
-    hipLaunchKernelGGL(mrl_mappo_value_norm, dim3(1), dim3(64), 0, stream, row_sums, num_minibatches, cfg.valuenorm_beta,
-                       cfg.valuenorm_one_minus_beta, cfg.valuenorm_epsilon, state, row_norm);
+    hipLaunchKernelGGL(mrl_mappo_value_norm, dim3(members), dim3(64), 0, stream, row_sums, num_minibatches, cfg.valuenorm_beta,
+                       cfg.valuenorm_one_minus_beta, cfg.valuenorm_epsilon, state, row_norm, member_scratch);
     MRL_HIP(hipGetLastError());
 }
 
 void launch_mappo_update(const mrl_mappo_policy &policy, const mrl_mappo_optimizer &opt, const mrl_mappo_batch &batch,
                          const int32_t *indices, uint32_t num_minibatches, uint32_t minibatch_size, const mrl_mappo_config &cfg,
-                         float *value_norm_state, float *workspace, float *stats, float *grads, hipStream_t stream)
+                         float *value_norm_state, float *workspace, float *stats, float *grads, hipStream_t stream,
+                         const MappoMembers &members)
 {
     if (num_minibatches == 0) return;
     const uint32_t W = policy.width, H = policy.height, F = policy.channels;
     const CnnUpdateLds lds = cnn_update_lds(W, H, F);
-    allow_large_dynamic_lds<&mrl_mappo_grad>(lds.total);
+    allow_large_dynamic_lds<&mrl_mappo_grad<false>>(lds.total);
+    allow_large_dynamic_lds<&mrl_mappo_grad<true>>(lds.total);
     MappoGradArgs g{};
     g.fwd.params = opt.params_dev;
     g.fwd.W = W;
@@ -259,9 +275,14 @@ void launch_mappo_update(const mrl_mappo_policy &policy, const mrl_mappo_optimiz
     g.fwd.lds = lds.fwd;
     g.tail_at = lds.tail_at;
     mappo_update_rows((uint32_t)cnn_net_params(W, H, F, kCnnActions), (uint32_t)cnn_net_params(W, H, F, 1), opt, batch, indices, num_minibatches,
-                      minibatch_size, cfg, value_norm_state, workspace, stats, grads, stream, [&](const MappoGradCommon &common, uint32_t groups) {
+                      minibatch_size, cfg, value_norm_state, workspace, stats, grads, stream, members,
+                      [&](const MappoGradCommon &common, uint32_t groups, const MappoMemberStrides &strides, uint32_t count) {
                           g.common = common;
-                          hipLaunchKernelGGL(mrl_mappo_grad, dim3(groups, 2), dim3(kCnnThreads), lds.total, stream, g);
+                          g.members = strides;
+                          if (count == 1)
+                              hipLaunchKernelGGL(mrl_mappo_grad<false>, dim3(groups, 2), dim3(kCnnThreads), lds.total, stream, g);
+                          else
+                              hipLaunchKernelGGL(mrl_mappo_grad<true>, dim3(groups, 2, count), dim3(kCnnThreads), lds.total, stream, g);
                       });
 }
 

@@ -30,9 +30,11 @@ inline CnnUpdateLds cnn_update_lds(uint32_t W, uint32_t H, uint32_t F)
     return u;
 }
 
-// K rows enqueued on `stream`; every argument has been validated (capi.hip, mrl_mappo_update).
+// K rows enqueued on `stream`; every argument has been validated (capi.hip, mrl_mappo_update).  With `members`
+// (mrl_mappo_bank_update) opt, indices, value_norm_state, workspace, stats and grads are the first member's.
 void launch_mappo_update(const mrl_mappo_policy &policy, const mrl_mappo_optimizer &opt, const mrl_mappo_batch &batch,
                          const int32_t *indices, uint32_t num_minibatches, uint32_t minibatch_size, const mrl_mappo_config &cfg,
-                         float *value_norm_state, float *workspace, float *stats, float *grads, hipStream_t stream);
+                         float *value_norm_state, float *workspace, float *stats, float *grads, hipStream_t stream,
+                         const MappoMembers &members = kMappoOneMember);
 
 }  // namespace mrl

@@ -28,6 +28,27 @@ struct MappoGradCommon {
     MappoLoss loss;
 };
 
+// A bank update (MappoMembers, mappo_loss.hpp) runs each gradient kernel's MEMBERS = true instance with the member as
+// blockIdx.z: floats (words) from a member's arrays to the next member's -- the parameters, the row of indices, the scratch
+// (row_norm, partial_grads, partial_stats).  The last field of a kernel's arguments; the MEMBERS = false instance, which the
+// plain update launches, does not read it and compiles to the instructions the kernel had without members.
+struct MappoMemberStrides {
+    uint64_t params, indices, scratch;
+};
+
+// the arguments as member blockIdx.z sees them: its own indices, row_norm and partial vectors (uniform over the workgroup; the
+// caller adds the parameters' stride to its parameter pointer)
+__device__ __forceinline__ MappoGradCommon mappo_member_view(const MappoGradCommon &a, const MappoMemberStrides &m)
+{
+    MappoGradCommon c = a;
+    const size_t z = blockIdx.z;
+    c.indices += z * m.indices;
+    if (c.row_norm) c.row_norm += z * m.scratch;
+    c.partial_grads += z * m.scratch;
+    c.partial_stats += z * (m.scratch / 2u);  // (the scratch is a whole number of 16-byte units)
+    return c;
+}
+
 // the tile's samples; a lane past the end runs on a zero observation with zero upstream gradient.  The caller's barrier follows.
 __device__ __forceinline__ void mappo_tile_samples(const MappoGradCommon &a, uint32_t *sample, uint64_t base, uint64_t end, uint32_t tid)
 {
@@ -159,18 +180,22 @@ __device__ __forceinline__ void mappo_stats_tail(const MappoGradCommon &a, uint3
 
 // The host side of an update of K rows, enqueued on `stream`: ValueNorm's recurrence up front, then per row the net's gradient
 // launch -- launch_grad(common arguments, workgroups per net) -- and the optimiser tail with two segments, the actor's `actor`
-// parameters and then the critic's `critic` (two clip_grad_norm_ and two Adam steps).
+// parameters and then the critic's `critic` (two clip_grad_norm_ and two Adam steps).  `members` (MappoMembers): every launch
+// serves that many members at once (blockIdx.z), opt, indices, value_norm_state, workspace, stats and grads being the first
+// member's; launch_grad(common arguments, workgroups per net, the members' strides, their count) then launches the MEMBERS instance.
 template <class Batch, class LaunchGrad>
 inline void mappo_update_rows(uint32_t actor, uint32_t critic, const mrl_mappo_optimizer &opt, const Batch &batch, const int32_t *indices,
                               uint32_t num_minibatches, uint32_t minibatch_size, const mrl_mappo_config &cfg, float *value_norm_state,
-                              float *workspace, float *stats, float *grads, hipStream_t stream, LaunchGrad launch_grad)
+                              float *workspace, float *stats, float *grads, hipStream_t stream, const MappoMembers &members,
+                              LaunchGrad launch_grad)
 {
     const SampleShare share = share_samples(minibatch_size, kMappoTile, kMappoMaxGroups);
     const MappoWorkspace ws = mappo_workspace(actor, minibatch_size, num_minibatches);
-    const bool norm = cfg.flags & MRL_MAPPO_VALUENORM;
+    const bool norm = cfg.flags & MRL_MAPPO_VALUENORM, one = members.count == 1;
+    const uint64_t member_scratch = one ? 0 : ws.total, member_rows = one ? 0 : num_minibatches;
     if (norm)
         launch_mappo_value_norm(batch.returns, indices, num_minibatches, minibatch_size, batch.size, cfg, value_norm_state,
-                                workspace + ws.row_sums, workspace + ws.row_norm, stream);
+                                workspace + ws.row_sums, workspace + ws.row_norm, stream, members.count, member_scratch);
     MappoGradCommon g{};
     g.obs = batch.obs;
     g.actions = batch.actions;
@@ -182,6 +207,7 @@ inline void mappo_update_rows(uint32_t actor, uint32_t critic, const mrl_mappo_o
     g.partial_stats = reinterpret_cast<double *>(workspace + ws.partial_stats);
     g.share = share.share;
     g.stride = ws.stride;
+    const MappoMemberStrides strides{one ? 0 : members.params_stride, member_rows * minibatch_size, member_scratch};
     g.minibatch_size = minibatch_size;
     g.batch_size = batch.size;
     g.groups = share.groups;
@@ -194,21 +220,28 @@ inline void mappo_update_rows(uint32_t actor, uint32_t critic, const mrl_mappo_o
     ad.exp_avg = opt.exp_avg;
     ad.exp_avg_sq = opt.exp_avg_sq;
     ad.stride = ws.stride;
+    ad.member_scratch = member_scratch;
+    ad.member_params = strides.params;
+    ad.member_grads_row = member_rows * ((uint64_t)actor + critic);
     ad.segments = 2;
     ad.groups = share.groups;
     ad.blocks = (uint32_t)ws.blocks;
     ad.num_params[0] = actor, ad.num_params[1] = critic;
     ad.at[0] = 0, ad.at[1] = actor;
-    MappoStatsRow row{g.partial_stats, nullptr, share.groups, minibatch_size};
+    MappoBankStatsRow rows{{g.partial_stats, nullptr, share.groups, minibatch_size}, member_scratch / 2, member_rows * kMappoStats};
+    MappoStatsRow &row = rows.first;
     for (uint32_t k = 0; k < num_minibatches; k++) {
         g.indices = indices + (size_t)k * minibatch_size;
         g.row_norm = norm ? workspace + ws.row_norm + 2 * (size_t)k : nullptr;
-        launch_grad(g, share.groups);
+        launch_grad(g, share.groups, strides, members.count);
         MRL_HIP(hipGetLastError());
         ad.grads_row = grads ? grads + (size_t)k * ((size_t)actor + critic) : nullptr;
         adam_set_step(ad, (double)opt.step + 1.0 + (double)k, {cfg.lr, cfg.critic_lr});
         row.row = stats ? stats + (size_t)k * kMappoStats : nullptr;
-        launch_adam_step(ad, row, stream);
+        if (one)
+            launch_adam_step(ad, row, stream);
+        else
+            launch_adam_step_members(ad, rows, members.count, stream);
     }
 }
 

@@ -164,6 +164,21 @@ struct MappoStatsRow {
     }
 };
 
+// MappoStatsRow for member blockIdx.z of a bank update: the first member's, moved member_partial doubles / member_row floats per member
+struct MappoBankStatsRow {
+    MappoStatsRow first;
+    uint64_t member_partial, member_row;
+
+    __device__ void operator()(uint32_t net, float total_norm) const
+    {
+        if (!first.row) return;
+        MappoStatsRow own = first;
+        own.partial_stats += (size_t)blockIdx.z * member_partial;
+        own.row += (size_t)blockIdx.z * member_row;
+        own(net, total_norm);
+    }
+};
+
 // The caller's scratch, in floats: every row's ValueNorm (mean, sqrt(var)) and (mean, mean of squares) of its returns; the
 // workgroups' partial gradient vectors (2 nets, groups, stride) and partial stats (2, groups, 8 doubles); the summed gradient
 // (2, stride); the reduce launch's per-block sums of g^2 (2, blocks).  stride = the actor's parameter count, padded.
@@ -190,10 +205,21 @@ inline MappoWorkspace mappo_workspace(uint64_t actor_params, uint32_t minibatch_
     return w;
 }
 
+// The members of a policy bank that one update call trains (mrl_mappo_bank_update, mrl_mappo_mlp_bank_update; DESIGN.md section
+// 22): `count` consecutive bank rows, params_stride floats apart in the parameters and in both moments.  Every array a member has
+// of its own follows the previous member's: indices (M, K, B), the ValueNorm state (M, 3), stats (M, K, 8), grads (M, K, P) and
+// the workspace, M times mappo_workspace().total floats.  The plain calls train one member.
+struct MappoMembers {
+    uint32_t count;
+    uint64_t params_stride;
+};
+constexpr MappoMembers kMappoOneMember{1, 0};
+
 // ValueNorm's K-row recurrence, two launches up front (cnn_update.hip): every row's (mean, sqrt(var)) into row_norm (K, 2), the
-// final state into `state`; row_sums (K, 2) is scratch.
+// final state into `state`; row_sums (K, 2) is scratch.  With `members` members each runs its own recurrence on its own rows of
+// indices and its own state; row_sums and row_norm of a member lie member_scratch floats behind the previous member's.
 void launch_mappo_value_norm(const float *returns, const int32_t *indices, uint32_t num_minibatches, uint32_t minibatch_size,
                              uint32_t batch_size, const mrl_mappo_config &cfg, float *state, float *row_sums, float *row_norm,
-                             hipStream_t stream);
+                             hipStream_t stream, uint32_t members = 1, uint64_t member_scratch = 0);
 
 }  // namespace mrl

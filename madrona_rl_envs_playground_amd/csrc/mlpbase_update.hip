@@ -17,6 +17,9 @@
 //                     sum over the share is ONE chain in sample order and nothing but its owner touches the vector.  The fc_h
 //                     segment of the vector (registered by the reference, used by no forward pass) is written as zeros.
 //   mrl_grad_reduce, mrl_clip_adam  the optimiser tail (adam_step.hpp), a segment per net.
+// mrl_mappo_mlp_bank_update is the same launches with a third grid dimension, the member of the bank: a
+// member's workgroups read its own parameters, indices and ValueNorm rows and write its own partial vectors (the kernels'
+// MEMBERS = true instances; the plain update runs the MEMBERS = false ones, which are the kernels as they were).
 // The sample table, the loss head, the head's and a Linear(64, 64)'s backward pass, the column sums, the stats' tail and the host's
 // row loop are mappo_grad.hpp's, shared with mrl_mappo_grad; what is left here is what a LayerNorm MLP has of its own.
 // No float atomics and no wait on another workgroup anywhere: the same inputs give the same bits on every run.
@@ -37,15 +40,19 @@ struct MappoMlpGradArgs {
     MappoGradCommon common;  // obs: int32 (S, 7)
     const float *params;
     uint32_t layer_N;
+    MappoMemberStrides members;  // MEMBERS only
 };
 
+// MEMBERS: member blockIdx.z of a bank update, on its own parameters, indices, ValueNorm rows and partial vectors
+template <bool MEMBERS>
 __global__ void __launch_bounds__(kMlpBaseThreads) mrl_mappo_mlp_grad(MappoMlpGradArgs a)
 {
-    const MappoGradCommon &c = a.common;
+    const MappoGradCommon own = MEMBERS ? mappo_member_view(a.common, a.members) : MappoGradCommon{};
+    const MappoGradCommon &c = MEMBERS ? own : a.common;
     const uint32_t net = blockIdx.y;  // 0 the actor, 1 the critic
     const uint32_t tid0 = threadIdx.x, layer_N = a.layer_N, out_dim = net ? 1u : kMlpBaseActions;
     const uint32_t net_at = net ? mlpbase_net_params(layer_N, kMlpBaseActions) : 0u;
-    const float *__restrict__ params = a.params + net_at;
+    const float *__restrict__ params = a.params + (MEMBERS ? (size_t)blockIdx.z * a.members.params : 0) + net_at;
     // this workgroup's partial vector, in the net's parameter order
     float *__restrict__ grads = c.partial_grads + ((size_t)net * c.groups + blockIdx.x) * c.stride;
     const float *__restrict__ head_w = params + mlpbase_head_at(layer_N);
@@ -156,18 +163,24 @@ __global__ void __launch_bounds__(kMlpBaseThreads) mrl_mappo_mlp_grad(MappoMlpGr
 
 void launch_mappo_mlp_update(uint32_t layer_N, const mrl_mappo_optimizer &opt, const mrl_mappo_mlp_batch &batch, const int32_t *indices,
                              uint32_t num_minibatches, uint32_t minibatch_size, const mrl_mappo_config &cfg, float *value_norm_state,
-                             float *workspace, float *stats, float *grads, hipStream_t stream)
+                             float *workspace, float *stats, float *grads, hipStream_t stream, const MappoMembers &members)
 {
     if (num_minibatches == 0) return;
     constexpr uint32_t lds_bytes = kMlpUpdFloats * 4u;
-    allow_large_dynamic_lds<&mrl_mappo_mlp_grad>(lds_bytes);
+    allow_large_dynamic_lds<&mrl_mappo_mlp_grad<false>>(lds_bytes);
+    allow_large_dynamic_lds<&mrl_mappo_mlp_grad<true>>(lds_bytes);
     MappoMlpGradArgs g{};
     g.params = opt.params_dev;
     g.layer_N = layer_N;
     mappo_update_rows(mlpbase_net_params(layer_N, kMlpBaseActions), mlpbase_net_params(layer_N, 1), opt, batch, indices, num_minibatches,
-                      minibatch_size, cfg, value_norm_state, workspace, stats, grads, stream, [&](const MappoGradCommon &common, uint32_t groups) {
+                      minibatch_size, cfg, value_norm_state, workspace, stats, grads, stream, members,
+                      [&](const MappoGradCommon &common, uint32_t groups, const MappoMemberStrides &strides, uint32_t count) {
                           g.common = common;
-                          hipLaunchKernelGGL(mrl_mappo_mlp_grad, dim3(groups, 2), dim3(kMlpBaseThreads), lds_bytes, stream, g);
+                          g.members = strides;
+                          if (count == 1)
+                              hipLaunchKernelGGL(mrl_mappo_mlp_grad<false>, dim3(groups, 2), dim3(kMlpBaseThreads), lds_bytes, stream, g);
+                          else
+                              hipLaunchKernelGGL(mrl_mappo_mlp_grad<true>, dim3(groups, 2, count), dim3(kMlpBaseThreads), lds_bytes, stream, g);
                       });
 }
 

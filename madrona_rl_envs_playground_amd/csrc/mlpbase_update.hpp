@@ -15,9 +15,10 @@ namespace mrl {
 constexpr uint32_t kMlpDoutAt = kMlpFwdFloats, kMlpDyAt = kMlpDoutAt + kMlpBaseTile * 8, kMlpDzAt = kMlpDyAt + kMlpBaseTile * kMlpLd,
                    kMlpSampleAt = kMlpDzAt + kMlpBaseTile * kMlpLd, kMlpUpdFloats = kMlpSampleAt + kMlpBaseTile;
 
-// K rows enqueued on `stream`; every argument has been validated (capi.hip, mrl_mappo_mlp_update).
+// K rows enqueued on `stream`; every argument has been validated (capi.hip, mrl_mappo_mlp_update).  With `members`
+// (mrl_mappo_mlp_bank_update) opt, indices, value_norm_state, workspace, stats and grads are the first member's.
 void launch_mappo_mlp_update(uint32_t layer_N, const mrl_mappo_optimizer &opt, const mrl_mappo_mlp_batch &batch, const int32_t *indices,
                              uint32_t num_minibatches, uint32_t minibatch_size, const mrl_mappo_config &cfg, float *value_norm_state,
-                             float *workspace, float *stats, float *grads, hipStream_t stream);
+                             float *workspace, float *stats, float *grads, hipStream_t stream, const MappoMembers &members = kMappoOneMember);
 
 }  // namespace mrl
