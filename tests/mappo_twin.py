@@ -345,18 +345,25 @@ def large_cases(tile, saturation_size):
 
 # ---------------------------------------------------------------- the exact-integer construction (critic only)
 
-def integer_case(layout, width=64, seed=3):
+def integer_case(layout, width=64, seed=3, d3=None, indices=None):
     """A critic whose every activation, upstream gradient and weight gradient is an integer below 2^24 in whatever order it is
     summed: cnn_twin's integer weights and observations, ValueNorm, huber and value clipping off, B a power of two, returns =
     v + B * m for small integers m, value_loss_coef 1: dL/dv = (v - R) / B = -m.  Returns the flat float32 parameters, the batch,
-    the index row and the critic's gradient (int64, flat, in parameter order) by numpy integer arithmetic."""
+    the index row and the critic's gradient (int64, flat, in parameter order) by numpy integer arithmetic.
+
+    ``d3`` (width,) int64: another upstream gradient dL/dv per sample of the index row, in whatever integer unit the caller
+    holds it -- the gradient and the bound come back in that unit, and the batch's returns, which state the default one, are the
+    caller's to replace (tests/kink_cases.py).  ``indices`` (width,): another index row than the drawn one.  "values": every
+    sample's v (int64)."""
     w, h, p, f = shape_of(layout)
     layers = cnn_twin.integer_layers(layout)
     params = cnn_twin.integer_params(layers)
     rng = np.random.default_rng(seed)
     ring = cnn_twin.rows_of(np.concatenate([cnn_twin.integer_observations(layout, N, seed + t) for t in range(2)]))
     size = len(ring)
-    indices = rng.permutation(size)[:width].astype(np.int32)
+    drawn = rng.permutation(size)[:width].astype(np.int32)
+    indices = drawn if indices is None else np.asarray(indices, np.int32)
+    assert indices.shape == (width,)
     values, _, bound = cnn_twin.integer_forward(layers, ring)
     m = rng.integers(-2, 3, size=size)
     returns = values + width * m
@@ -373,7 +380,7 @@ def integer_case(layout, width=64, seed=3):
     a1 = np.maximum(z1, 0)
     z2 = a1 @ w2.T + b2
     a2 = np.maximum(z2, 0)
-    d3 = -m[indices.astype(np.int64)][:, None]  # (n, 1)
+    d3 = (-m[indices.astype(np.int64)] if d3 is None else np.asarray(d3, np.int64).reshape(width))[:, None]  # (n, 1)
     g_w3, g_b3 = d3.T @ a2, d3.sum(axis=0)
     d2 = (d3 @ w3) * (z2 > 0)
     g_w2, g_b2 = d2.T @ a1, d2.sum(axis=0)
@@ -387,5 +394,5 @@ def integer_case(layout, width=64, seed=3):
                 int((np.abs(d2).T @ np.abs(a1)).max()), int((np.abs(d3).T @ np.abs(a2)).max()), int((np.abs(d1) @ np.abs(w1)).max()),
                 int((np.abs(d2) @ np.abs(w2)).max()))
     return {"params": params, "batch": batch, "indices": indices[None, :], "grad": np.concatenate([g.reshape(-1) for g in pieces]),
-            "bound": bound, "matrices": {"conv": g_wc.reshape(32, -1), "fc1": g_w1, "fc2": g_w2},
+            "bound": bound, "matrices": {"conv": g_wc.reshape(32, -1), "fc1": g_w1, "fc2": g_w2}, "values": values,
             "cfg": Config(valuenorm=False, huber=False, clipped_value=False)}

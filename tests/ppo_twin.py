@@ -270,3 +270,32 @@ def gpu_cases(tile_size):
             if variant != "default":
                 cases.append((d, a, 1.0, 257, variant))
     return cases
+
+
+# ---------------------------------------------------------------- the exact construction (critic only)
+
+def integer_case(count, d3=None, seed=3):
+    """The construction of ``test_matrix_core_operand_maps_with_exact_integers`` (tests/test_gpu_ppo_update.py) with the upstream
+    gradient as an argument: a first layer that saturates tanh (h1 in {-1, 0, 1}), a second layer of zeros (h2 = 0, v = 0 exactly,
+    d2[j] = W3[j] d3), W3[j] = j - 20, an actor of zeros.  ``d3`` (count,) int64: dL/dv per sample in whatever integer unit the
+    caller holds it; by default -r for drawn integers r, which returns of 2 count r give with vf_coef 0.5 and no value clipping.
+    Returns {"params", "batch" (old values 0), "dW2" (64, 64) and "db2" (64,) int64 in d3's unit, "bound": the largest sum of
+    absolute terms, "slices": where dW2 and db2 lie in the flat gradient}; with a ``d3`` the returns and old values are the
+    caller's to replace (tests/kink_cases.py)."""
+    d, a, h = 4, 2, policy_twin.H
+    rng = np.random.default_rng(seed)
+    patterns = np.array([[(i + 1) // 3 ** k % 3 - 1 for k in range(d)] for i in range(h)], np.int64)  # 64 different rows of -1 / 0 / 1
+    obs = rng.choice([-1, 1], size=(count, d)).astype(np.int64)
+    r = rng.integers(-3, 4, size=count).astype(np.int64)
+    d3 = -r if d3 is None else np.asarray(d3, np.int64).reshape(count)
+    w3 = np.arange(h, dtype=np.int64) - 20
+    critic = np.concatenate([(64.0 * patterns).reshape(-1), np.zeros(h), np.zeros(h * h), np.zeros(h), w3.astype(np.float64), np.zeros(1)])
+    params = np.concatenate([critic, np.zeros(initial_params(d, a, 1.0).size - critic.size)]).astype(np.float32)
+    batch = Batch(obs.astype(np.float32), np.zeros(count, np.int32), np.full(count, np.log(0.5), np.float32), np.zeros(count, np.float32),
+                  (2.0 * count * r).astype(np.float32), np.zeros(count, np.float32))
+    h1 = np.sign(patterns @ obs.T)          # (unit of layer 1, sample)
+    d2 = w3[:, None] * d3[None, :]          # (unit of layer 2, sample)
+    at = d * h + h
+    return {"params": params, "batch": batch, "dW2": d2 @ h1.T, "db2": d2.sum(axis=1),
+            "bound": int(max((np.abs(d2) @ np.abs(h1).T).max(), np.abs(d2).sum(axis=1).max())),
+            "slices": (slice(at, at + h * h), slice(at + h * h, at + h * h + h))}

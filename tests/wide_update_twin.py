@@ -323,11 +323,15 @@ def stat_margins(weights, flags=()):
 
 # ---------------------------------------------------------------- exact integers, critic only
 
-def integer_case(size, seed=wide_twin.INTEGER_SEED):
+def integer_case(size, seed=wide_twin.INTEGER_SEED, d3=None):
     """``wide_twin.integer_layers`` weights on hanabi_very_small inputs, integer returns, ``size`` samples all active in a (1, size)
     record: with NORM_ADV and CLIP_VLOSS off and vf_coef = 1 the critic's gradient is d_value = (v - R) / B times integers.  B is
     a power of two, so every product and partial sum is an integer over B that float32 holds exactly while the sums of absolute
-    terms stay below 2^24.  Returns (params float32, record, expected critic gradient float64, the bound)."""
+    terms stay below 2^24.  Returns (params float32, record, expected critic gradient float64, the bound).
+
+    ``d3`` (size,) int64: another B dL/dv per sample, in whatever integer unit the caller holds it -- the expected gradient and
+    the bound come back in that unit, and the record's returns and old values (the samples' own v), which state the default
+    one, are the caller's to replace (tests/kink_cases.py)."""
     game = "hanabi_very_small"
     d, s, a = wide_twin.dims(game)
     layers = wide_twin.integer_layers(d, s, a)
@@ -342,7 +346,7 @@ def integer_case(size, seed=wide_twin.INTEGER_SEED):
     x = [np.asarray(inputs["state"], np.int64)]
     for k, (w, b) in enumerate(layers["critic"][:3]):
         x.append(np.maximum(x[-1] @ w.T + b, 0))
-    dy = (values - returns)[:, None]
+    dy = ((values - returns) if d3 is None else np.asarray(d3, np.int64).reshape(size))[:, None]
     grads = [None] * 4
     for k in (3, 2, 1, 0):
         w, _ = layers["critic"][k]
