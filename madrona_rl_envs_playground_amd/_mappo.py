@@ -247,7 +247,7 @@ def _kitchen_cells(sim, policy=None):
 
 class _Family:
     """What differs between MAPPO's two networks on the act and rollout side, stated once per network (``_CNN``, ``_MLPBASE``) as
-    ``BankFamily`` states it in capi.hip and the policies' ``_mappo_*`` hooks state it for the update.  ``name`` gives the four
+    ``BankFamily`` states it in capi_internal.hpp and the policies' ``_mappo_*`` hooks state it for the update.  ``name`` gives the four
     entry points (``act``, ``act_bank``, ``rollout``, ``rollout_bank``: ``mrl_<name>_act`` ... ``mrl_rollout_<name>_bank``), ``article``
     the nouns of the messages.  ``game``: the marker an act demands of the simulator, ``None`` where it asks only for the shape.
     ``cells(sim, policy=None)`` -> (worlds, seats), after the network's own shape check when there is a policy.  ``act_workspace``:

@@ -1,4 +1,4 @@
-// What the three policy banks share below capi.hip (cnn_bank.hip, mlpbase_bank.hip, wide_bank.hip; DESIGN.md sections 19 to 21):
+// What the three policy banks share below the C API (capi_bank.hip; cnn_bank.hip, mlpbase_bank.hip, wide_bank.hip; DESIGN.md sections 19 to 21):
 // the plan of a bank act -- the acted cells of every policy gathered into that policy's sample list, the lists cut into tiles of at
 // most 32 samples --, the MAPPO banks' arguments and launcher, the tile table's reader and the resample.  Kernels: bank_plan.hip.
 //

@@ -1,5 +1,5 @@
 // A bank of K CNN policies and a policy per (world, seat) cell (C ABI: mrl_cnn_act_bank, mrl_cnn_bank_resample,
-// mrl_rollout_cnn_bank in include/mrl_envs.h).  The kernel lives in cnn_bank.hip; capi.hip validates, with
+// mrl_rollout_cnn_bank in include/mrl_envs.h).  The kernel lives in cnn_bank.hip; capi_mappo.hip validates, with
 // the helpers every bank shares (bank_refusal, bank_prepare, bank_resample, rollout_loop).
 //
 // An act is two launches: the plan (bank_plan.hpp, one copy for every bank, with the workspace layout, BankActArgs, bank_entry and

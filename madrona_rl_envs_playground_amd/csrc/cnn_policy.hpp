@@ -1,5 +1,5 @@
 // MAPPO's CNN actor-critic for Overcooked on the device (C ABI: mrl_cnn_act, mrl_rollout_cnn in include/mrl_envs.h; DESIGN.md
-// section 15).  The kernel lives in cnn_policy.hip; capi.hip validates the arguments and collects the simulator's tensors.
+// section 15).  The kernel lives in cnn_policy.hip; capi_mappo.hip validates the arguments and collects the simulator's tensors.
 //
 // THE INDEX MAP.  The simulator writes obs[n, p, y, x, f] (world-major, int8, y < H, x < W).  The reference hands the network
 // the view (N, W, H, F) and moves the channels forward, so torch sees x[n, f, w, h] = obs[n, p, h, w, f]: the convolution's

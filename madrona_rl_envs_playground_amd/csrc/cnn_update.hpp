@@ -1,5 +1,5 @@
 // MAPPO's update for the Overcooked CNN actor-critic on the device (C ABI: mrl_mappo_update, mrl_mappo_workspace_bytes in
-// include/mrl_envs.h).  The kernels live in cnn_update.hip; capi.hip validates the arguments.
+// include/mrl_envs.h).  The kernels live in cnn_update.hip; capi_mappo.hip validates the arguments.
 #pragma once
 
 #include "cnn_policy.hpp"
@@ -30,7 +30,7 @@ inline CnnUpdateLds cnn_update_lds(uint32_t W, uint32_t H, uint32_t F)
     return u;
 }
 
-// K rows enqueued on `stream`; every argument has been validated (capi.hip, mrl_mappo_update).  With `members`
+// K rows enqueued on `stream`; every argument has been validated (capi_mappo.hip, mrl_mappo_update).  With `members`
 // (mrl_mappo_bank_update) opt, indices, value_norm_state, workspace, stats and grads are the first member's.
 void launch_mappo_update(const mrl_mappo_policy &policy, const mrl_mappo_optimizer &opt, const mrl_mappo_batch &batch,
                          const int32_t *indices, uint32_t num_minibatches, uint32_t minibatch_size, const mrl_mappo_config &cfg,

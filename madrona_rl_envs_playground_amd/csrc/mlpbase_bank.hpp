@@ -1,6 +1,6 @@
 // A bank of K MLPBase policies and a policy per (world, seat) cell of the balance beam (C ABI: mrl_mlpbase_act_bank,
 // mrl_mlpbase_bank_resample, mrl_rollout_mlpbase_bank in include/mrl_envs.h).  The kernel lives in
-// mlpbase_bank.hip; capi.hip validates, with every bank's helpers (bank_refusal, bank_prepare, bank_resample, rollout_loop).
+// mlpbase_bank.hip; capi_mappo.hip validates, with every bank's helpers (capi_bank.hip, capi_internal.hpp).
 //
 // An act is the plan (bank_plan.hpp: every bank's, one copy, the same workspace words) and mrl_mlpbase_act's body
 // (mlpbase_act_body.hpp) over the plan's tiles, each under its own policy's row of the bank.  The resample is bank_plan.hpp's too.

@@ -1,6 +1,6 @@
 // MAPPO's MLP actor-critic for the balance beam on the device (C ABI: mrl_mlpbase_act, mrl_rollout_mlpbase in
 // include/mrl_envs.h).  The kernel lives in mlpbase_policy.hip, the forward pass in mlpbase_forward.hpp;
-// capi.hip validates the arguments and collects the simulator's tensors.
+// capi_mappo.hip validates the arguments and collects the simulator's tensors.
 //
 // THE NETWORK (train/MAPPO/utils/mlp.py with use_feature_normalization, use_ReLU, use_orthogonal; hidden_size 64), per net:
 //     LayerNorm(7) -> Linear(7, 64) -> ReLU -> LayerNorm(64) -> layer_N x [Linear(64, 64) -> ReLU -> LayerNorm(64)] -> head

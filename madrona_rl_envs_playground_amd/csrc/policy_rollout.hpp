@@ -1,5 +1,5 @@
 // Policy rollouts on the device for Cartpole and Acrobot (C ABI: mrl_rollout_policy, mrl_gae in include/mrl_envs.h).
-// The kernels live in policy_rollout.hip; capi.hip drives them around the simulator's ordinary step.
+// The kernels live in policy_rollout.hip; capi_ppo.hip drives them around the simulator's ordinary step.
 #pragma once
 
 #include "common.hpp"

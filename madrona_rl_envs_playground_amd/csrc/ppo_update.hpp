@@ -1,5 +1,5 @@
 // The update phase of PPO on the device (C ABI: mrl_ppo_update, mrl_ppo_workspace_bytes in include/mrl_envs.h).
-// The kernels live in ppo_update.hip; capi.hip validates the arguments and calls launch_ppo_update.  DESIGN.md section 13.
+// The kernels live in ppo_update.hip; capi_ppo.hip validates the arguments and calls launch_ppo_update.  DESIGN.md section 13.
 #pragma once
 
 #include "adam_step.hpp"
@@ -33,7 +33,7 @@ inline PpoWorkspace ppo_workspace(uint64_t num_params, uint32_t minibatch_size, 
     return w;
 }
 
-// K rows enqueued on `stream`; every argument has been validated (capi.hip, mrl_ppo_update).
+// K rows enqueued on `stream`; every argument has been validated (capi_ppo.hip, mrl_ppo_update).
 void launch_ppo_update(const mrl_mlp_policy &shape, const mrl_ppo_optimizer &opt, const mrl_ppo_batch &batch,
                        const int32_t *indices, uint32_t num_minibatches, uint32_t minibatch_size, const mrl_ppo_config &cfg,
                        float *workspace, float *stats, float *grads, hipStream_t stream);

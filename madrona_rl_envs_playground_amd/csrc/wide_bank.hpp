@@ -1,6 +1,6 @@
 // A bank of K wide policies (CleanPPOAgent's two 512-wide four-layer MLPs) and a policy per world for one seat of Hanabi or the
 // balance beam (C ABI: mrl_agent_act_bank, mrl_agent_bank_resample, mrl_agent_bank_workspace_bytes in include/mrl_envs.h;
-// DESIGN.md section 21).  The kernels live in wide_bank.hip; capi.hip validates, with every bank's bank_refusal and bank_resample.
+// DESIGN.md section 21).  The kernels live in wide_bank.hip; capi_wide.hip validates, with every bank's bank_refusal and bank_resample.
 //
 // An act is the effective ids (ids[n, player] where the world is computed, -1 elsewhere), the plan over them (bank_plan.hpp: the
 // other banks' own, with P = 1 and N cells), mrl_wide_layer's body (wide_layer_body.hpp) over the plan's tiles, four launches,

@@ -1,6 +1,6 @@
 // The collection phase of CleanPPOAgent on the device for Hanabi and the balance beam (C ABI: mrl_agent_act,
 // mrl_agent_credit, mrl_gae_active in include/mrl_envs.h).  The kernels live in wide_policy.hip;
-// capi.hip validates the arguments and collects the simulator's tensors.
+// capi_wide.hip validates the arguments and collects the simulator's tensors.
 #pragma once
 
 #include "common.hpp"
