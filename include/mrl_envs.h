@@ -540,7 +540,8 @@ enum {
 int mrl_enable_episode_stats(mrl_sim *sim, void *hip_stream);
 int mrl_clear_episode_totals(mrl_sim *sim, void *hip_stream);
 
-/* Policy rollouts on the device: the collection phase of PPO for Cartpole and Acrobot.  The reference's trainer runs, per
+/* Policy rollouts on the device: the collection phase of PPO for Cartpole and Acrobot, and for the single-agent trainer of
+ * the balance beam (its own paragraph below).  The reference's trainer runs, per
  * step, two three-layer tanh MLPs (scripts/cartpole_train_torch.py:105-131, Agent), a Categorical sample, a log_prob and six
  * buffer row copies in torch around the step (:204-218), then T sequential torch iterations for the advantages (:243-256).
  * Here the first is ONE launch per step in front of the simulator's ordinary step (mrl_policy_act) and the second one launch
@@ -549,10 +550,12 @@ int mrl_clear_episode_totals(mrl_sim *sim, void *hip_stream);
  *     device array in the order of torch.nn.utils.parameters_to_vector(agent.parameters()) for that Agent: critic.0.weight
  *     (64, D) row-major, critic.0.bias, critic.2.weight, critic.2.bias, critic.4.weight, critic.4.bias, then actor.0 ... actor.4;
  *     mrl_mlp_policy_num_params floats.  The kernel reads it in place in every launch: between rollouts a trainer does its
- *     optimizer step and one flat copy.  hidden must be 64; num_actions 2 (Cartpole) or 3 (Acrobot).
+ *     optimizer step and one flat copy.  hidden must be 64; num_actions 2 (Cartpole), 3 (Acrobot) or 4 (the beam).
  *   Observation: MRL_OBS_RAW, D = 4, is the STATE row; MRL_OBS_ACROBOT_GYM, D = 6, Acrobot only, is Gym's
  *     [cos theta1, sin theta1, cos theta2, sin theta2, omega1, omega2] computed from it.
- *   Buffers: dense device arrays, T = num_steps; obs / next_obs start on a 16-byte (D = 4) or 8-byte (D = 6) boundary.
+ *     MRL_OBS_BALANCE, D = 7, the balance beam only, is seat 0's int32 OBSERVATION row as floats (below).
+ *   Buffers: dense device arrays, T = num_steps; obs / next_obs start on a 16-byte (D = 4), 8-byte (D = 6) or 4-byte (D = 7)
+ *     boundary.
  *   Row k < T, world w, from the tensors as they stand in front of step k of the call:
  *     obs[k,w,:] the observation; dones[k,w] = RESET[w] != 0 as 0.0 / 1.0 -- the previous step's flag, like `dones[step] =
  *     next_done` (:207) --; values[k,w] the critic; actions[k,w] the draw, also written to ACTION[w]; logprobs[k,w]; and for
@@ -568,18 +571,28 @@ int mrl_clear_episode_totals(mrl_sim *sim, void *hip_stream);
  *   mrl_step reading the ACTION tensor, so the call equals, row for row, T times "act on the current state, mrl_step", and
  *   afterwards the simulator is exactly where T mrl_step_with_actions calls with actions[0..T-1] would have left it (and its
  *   ACTION tensor holds actions[T-1]): episode numbering, statistics and SCAN_TIMEOUT behave as there.
- *   MRL_ERR_INVALID: a game other than Cartpole or Acrobot; hidden != 64; num_actions other than the game's; an (obs_dim,
+ *   MRL_ERR_INVALID: a game other than Cartpole, Acrobot or the balance beam (below); hidden != 64; num_actions other than the game's; an (obs_dim,
  *   obs_mode) other than (4, RAW) or, for Acrobot, (6, ACROBOT_GYM); any NULL pointer; a misaligned obs / next_obs; a capturing
  *   stream wherever mrl_step refuses one; a simulator that has been through mrl_exchange_create.  Capturing a rollout in a HIP
- *   graph is not supported in any mode: the row index travels in kernel arguments.  The balance beam (two agents, integer
- *   observations) and the other games are out of scope.
+ *   graph is not supported in any mode: the row index travels in kernel arguments.
+ *   The balance beam (scripts/balance_train_single.py: the same agent, 7 -> 64 -> 64 -> {4, 1}, as the ego of a two-seat game
+ *   whose partner moves uniformly at random): hidden 64, obs_dim 7, num_actions 4, MRL_OBS_BALANCE.  Per world w the launch
+ *   reads x = OBSERVATION[0,w,0..6] (int32 values 0..8 and 0..2, exact as floats) and writes obs[k,w,:] = x, dones[k,w] =
+ *   DONE[w] != 0, rewards[k-1,w] = REWARD[0,w] (the ego's, as VectorMultiAgentEnv.step returns it), values, actions and
+ *   logprobs as above, the ego's action also to ACTION[0,w,0] -- and, in the same launch, the partner's move ACTION[1,w,0] =
+ *   (h1 * 4) >> 32 with h1 the hash of (seed, first_step + k, w, player 1): mrl_rollout_random's draw for that seat.  The
+ *   closing launch draws nothing and leaves both seats' ACTION alone; MRL_POLICY_GREEDY changes the ego's choice only.
+ *   Afterwards the simulator is where T mrl_step_with_actions calls with [actions[k], those partner moves] would have left it,
+ *   and ACTION holds the last row of both seats.  MRL_ERR_INVALID for any other shape or mode on a beam, MRL_OBS_BALANCE on
+ *   another game, a beam that has been through mrl_exchange_create, and a capturing stream in every mode.  A caller-supplied or
+ *   learned partner is what mrl_rollout_mlpbase and the banks are for.  The other games are out of scope.  DESIGN.md section 25.
  * mrl_gae is lines 247-256 with a lane per world, t = T-1 ... 0 in float32, one IEEE operation per operation of the script:
  *     nnt = 1 - (t == T-1 ? next_done[w] : dones[t+1,w]);  nv = t == T-1 ? next_value[w] : values[t+1,w]
  *     delta = rewards[t,w] + gamma * nv * nnt - values[t,w]
  *     advantages[t,w] = last = delta + gl * nnt * last;  returns[t,w] = advantages[t,w] + values[t,w]
  *   with gl = float32(double(gamma) * double(lambda)) (the script multiplies the two Python floats first).  All arrays (T, N)
  *   dense on device gpu_id, next_* (N); it only enqueues.  MRL_ERR_INVALID for a NULL array.  DESIGN.md section 12. */
-enum { MRL_OBS_RAW = 0, MRL_OBS_ACROBOT_GYM = 1 };
+enum { MRL_OBS_RAW = 0, MRL_OBS_ACROBOT_GYM = 1, MRL_OBS_BALANCE = 2 };
 enum { MRL_POLICY_GREEDY = 1 };
 typedef struct mrl_mlp_policy {
     const float *params_dev;
@@ -626,11 +639,13 @@ int mrl_gae(const float *rewards, const float *values, const float *dones, const
  *   Index values (0 <= indices[k, b] < batch->size) are the caller's duty: there is no device-side check to synchronise on.
  *   shape->params_dev, obs_mode and flags are not read (the parameters are opt->params_dev; obs holds observations).
  *   MRL_ERR_INVALID: a NULL among shape, opt, batch, indices, cfg, workspace, the optimizer's three arrays and the batch's six;
- *     hidden != 64; (obs_dim, num_actions) other than (4, 2), (4, 3), (6, 3); minibatch_size < 2 with MRL_PPO_NORM_ADV;
- *     minibatch_size == 0 or batch->size == 0; workspace_bytes below mrl_ppo_workspace_bytes; obs off a 16-byte (D = 4) or
- *     8-byte (D = 6) boundary or workspace off a 16-byte one; a capturing stream (the step number travels in kernel
- *     arguments).  num_minibatches == 0 enqueues nothing.  mrl_ppo_workspace_bytes refuses the same shapes and a NULL out.
- *     DESIGN.md section 13. */
+ *     hidden != 64; (obs_dim, num_actions) other than (4, 2), (4, 3), (6, 3) and the balance beam's (7, 4); minibatch_size < 2
+ *     with MRL_PPO_NORM_ADV; minibatch_size == 0 or batch->size == 0; workspace_bytes below mrl_ppo_workspace_bytes; obs off a
+ *     16-byte (D = 4), 8-byte (D = 6) or 4-byte (D = 7: rows of 28 bytes, loaded float by float) boundary or workspace off a
+ *     16-byte one; a capturing stream (the step number travels in kernel arguments).  num_minibatches == 0 enqueues nothing.
+ *     mrl_ppo_workspace_bytes refuses the same shapes and a NULL out.  The words of a shape refusal: a call with neither
+ *     obs_dim 7 nor num_actions 4 is told "(4, 2), (4, 3), (6, 3)", the float-state games' shapes, as before the beam had one;
+ *     a call with either is told all four.  DESIGN.md sections 13 and 25. */
 enum { MRL_PPO_NORM_ADV = 1, MRL_PPO_CLIP_VLOSS = 2 };
 typedef struct mrl_ppo_config {
     float clip_coef, ent_coef, vf_coef, max_grad_norm; /* max_grad_norm <= 0: no clipping */
@@ -638,7 +653,7 @@ typedef struct mrl_ppo_config {
     uint32_t flags;
 } mrl_ppo_config;
 typedef struct mrl_ppo_batch { /* the script's b_* arrays (:259-264), dense, device */
-    const float *obs;          /* (S, D); 16-byte (D = 4) / 8-byte (D = 6) aligned, as for rollouts */
+    const float *obs;          /* (S, D); 16-byte (D = 4) / 8-byte (D = 6) / 4-byte (D = 7, the beam) aligned, as for rollouts */
     const int32_t *actions;    /* (S) */
     const float *logprobs, *advantages, *returns, *values; /* (S) */
     uint32_t size;             /* S = T * N */

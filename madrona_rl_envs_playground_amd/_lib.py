@@ -27,6 +27,7 @@ STATS_EPISODE_RETURN, STATS_EPISODE_STEPS, STATS_LAST_RETURN, STATS_LAST_STEPS, 
 MAX_DIMS = 6
 MAX_RANKS, IPC_HANDLE_BYTES = 16, 64  # MRL_MAX_RANKS, MRL_IPC_HANDLE_BYTES
 OBS_RAW, OBS_ACROBOT_GYM = 0, 1  # MRL_OBS_*: the observation mrl_rollout_policy forms from STATE
+OBS_BALANCE = 2  # MRL_OBS_BALANCE: the balance beam's seat-0 OBSERVATION row
 POLICY_GREEDY = 1  # MRL_POLICY_GREEDY
 AGENT_ALL_ROWS, AGENT_VALUE_ONLY = 2, 4  # MRL_AGENT_*: flags of mrl_agent_act beside POLICY_GREEDY
 WIDE_HIDDEN, WIDE_MAX_ACTIONS = 512, 64  # MRL_WIDE_*

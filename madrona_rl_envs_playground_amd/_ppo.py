@@ -70,12 +70,18 @@ class MlpPolicy:
     ``parameters_to_vector(agent.parameters())`` for an agent with ``critic`` and ``actor`` =
     ``Sequential(Linear(D, 64), Tanh, Linear(64, 64), Tanh, Linear(64, 1 or A))`` (``mrl_mlp_policy``).  The kernel reads the
     tensor in place: between rollouts a trainer steps its optimizer and calls ``load_(agent)``.  ``observation``: "state"
-    (the simulator's STATE row, D = 4) or "gym" (Acrobot's six values, D = 6)."""
+    (the simulator's STATE row, D = 4), "gym" (Acrobot's six values, D = 6) or "beam" (the balance beam's seat-0 row, D = 7
+    with 4 actions and nothing else: the agent of scripts/balance_train_single.py)."""
+
+    _OBS_MODES = {"state": _lib.OBS_RAW, "gym": _lib.OBS_ACROBOT_GYM, "beam": _lib.OBS_BALANCE}
 
     def __init__(self, obs_dim, num_actions, hidden=64, observation="state", device="cuda:0"):
-        if observation not in ("state", "gym"):
-            raise ValueError(f"observation must be 'state' or 'gym', got {observation!r}")
+        if observation not in self._OBS_MODES:
+            raise ValueError(f"observation must be 'state', 'gym' or 'beam', got {observation!r}")
         self.obs_dim, self.num_actions, self.hidden, self.observation = int(obs_dim), int(num_actions), int(hidden), observation
+        if observation == "beam" and (self.obs_dim, self.num_actions, self.hidden) != (7, 4, 64):
+            raise ValueError(f"observation 'beam' takes obs_dim 7, num_actions 4 and hidden 64, got "
+                             f"{(self.obs_dim, self.num_actions, self.hidden)}")
         count = int(_lib.lib().mrl_mlp_policy_num_params(self.obs_dim, self.hidden, self.num_actions))
         self.params = torch.zeros(count, dtype=torch.float32, device=torch.device(device))
 
@@ -260,9 +266,11 @@ class _PolicyRollout:
 
     def rollout_policy(self, policy, num_steps, seed=0, first_step=0, out=None, greedy=False):
         """``num_steps`` steps under ``policy`` (an ``MlpPolicy`` on this GPU) with the host out of the loop: observe, both
-        nets, draw, log-prob, value, step and record, two launches per step (``mrl_rollout_policy``; Cartpole and Acrobot).
-        Returns a ``Rollout`` of tensors on this GPU -- new ones, or ``out`` (an earlier call's result) filled again.  The
-        draw of (step index ``first_step + k``, world) uses ``sample_u``; ``greedy`` takes the first arg-max instead."""
+        nets, draw, log-prob, value, step and record, two launches per step (``mrl_rollout_policy``; Cartpole, Acrobot and,
+        for a policy that observes "beam", the balance beam).  Returns a ``Rollout`` of tensors on this GPU -- new ones, or
+        ``out`` (an earlier call's result) filled again.  The draw of (step index ``first_step + k``, world) uses
+        ``sample_u``; ``greedy`` takes the first arg-max instead.  On the beam the policy plays seat 0 and seat 1 moves at
+        random in the same launch: ``random_balance_action(seed, first_step + k, world, 1)``, whatever ``greedy`` says."""
         if not isinstance(policy, MlpPolicy):
             raise ValueError("policy must be an MlpPolicy")
         p = policy.params
@@ -283,8 +291,7 @@ class _PolicyRollout:
                 if (not isinstance(tensor, torch.Tensor) or tensor.device != device or tuple(tensor.shape) != shape or
                         tensor.dtype != (torch.int32 if name == "actions" else f32) or not tensor.is_contiguous()):
                     raise ValueError(f"out.{name} must be a contiguous {shape} tensor on cuda:{self.gpu_id}")
-        desc = _lib.MlpPolicyDesc(p.data_ptr(), d, policy.hidden, policy.num_actions,
-                                  _lib.OBS_ACROBOT_GYM if policy.observation == "gym" else _lib.OBS_RAW,
+        desc = _lib.MlpPolicyDesc(p.data_ptr(), d, policy.hidden, policy.num_actions, MlpPolicy._OBS_MODES[policy.observation],
                                   _lib.POLICY_GREEDY if greedy else 0)
         buffers = _lib.RolloutBuffers(*[tensor.data_ptr() for tensor in out], t)
         _lib.check(self._L.mrl_rollout_policy(self._handle, ctypes.byref(desc), ctypes.byref(buffers),

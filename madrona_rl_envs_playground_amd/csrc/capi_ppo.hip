@@ -1,4 +1,4 @@
-// The C API of the MLP learner (include/mrl_envs.h): the policy rollout of Cartpole and Acrobot, GAE and the PPO update, and the
+// The C API of the MLP learner (include/mrl_envs.h): the policy rollout of Cartpole, Acrobot and the balance beam, GAE and the PPO update, and the
 // tail every update's refusals share (update_refusal, capi_internal.hpp).
 #include "capi_internal.hpp"
 #include "policy_rollout.hpp"
@@ -46,22 +46,34 @@ int mrl_rollout_policy(mrl_sim *sim, const mrl_mlp_policy *policy, const mrl_rol
 {
     if (int rc = mrl::need_healthy(sim)) return rc;
     if (int rc = mrl::need_not_capturing(sim, hip_stream, "mrl_rollout_policy")) return rc;
-    if (sim->game != MRL_GAME_CARTPOLE && sim->game != MRL_GAME_ACROBOT) {
-        mrl::set_error("mrl_rollout_policy: game %d has no policy rollout (Cartpole and Acrobot do)", sim->game);
+    const bool beam = sim->game == MRL_GAME_BALANCE;
+    if (sim->game != MRL_GAME_CARTPOLE && sim->game != MRL_GAME_ACROBOT && !beam) {
+        mrl::set_error("mrl_rollout_policy: game %d has no policy rollout (Cartpole, Acrobot and the balance beam do)", sim->game);
         return MRL_ERR_INVALID;
     }
     if (sim->exchange.mine) {
         mrl::set_error("mrl_rollout_policy: this simulator is a rank of an exchanged batch (mrl_exchange_create); its step needs the other ranks");
         return MRL_ERR_INVALID;
     }
+    if (beam && mrl::capturing(hip_stream)) {  // (after mrl_prepare_graph_capture mrl_step would let the capture pass)
+        mrl::set_error("mrl_rollout_policy: the row index travels in kernel arguments, so a rollout cannot be captured in a HIP graph");
+        return MRL_ERR_INVALID;
+    }
     if (!policy || !buffers || !policy->params_dev) {
         mrl::set_error("mrl_rollout_policy: null policy, parameter array or buffer description");
+        return MRL_ERR_INVALID;
+    }
+    if (beam && (policy->hidden != mrl::kPolicyHidden || policy->obs_dim != 7 || policy->num_actions != 4 ||
+                 policy->obs_mode != MRL_OBS_BALANCE)) {
+        mrl::set_error("mrl_rollout_policy: the balance beam takes hidden = 64, obs_dim = 7, num_actions = 4, MRL_OBS_BALANCE; (4, RAW) and "
+                       "(6, ACROBOT_GYM) are the shapes of Cartpole and Acrobot; got hidden %u, num_actions %u, obs_dim %u, obs_mode %u",
+                       policy->hidden, policy->num_actions, policy->obs_dim, policy->obs_mode);
         return MRL_ERR_INVALID;
     }
     const uint32_t actions = sim->game == MRL_GAME_CARTPOLE ? 2u : 3u;
     const bool raw = policy->obs_dim == 4 && policy->obs_mode == MRL_OBS_RAW;
     const bool gym = policy->obs_dim == 6 && policy->obs_mode == MRL_OBS_ACROBOT_GYM && sim->game == MRL_GAME_ACROBOT;
-    if (policy->hidden != mrl::kPolicyHidden || policy->num_actions != actions || !(raw || gym)) {
+    if (!beam && (policy->hidden != mrl::kPolicyHidden || policy->num_actions != actions || !(raw || gym))) {
         mrl::set_error("mrl_rollout_policy: need hidden = 64, num_actions = %u and (obs_dim, obs_mode) = (4, MRL_OBS_RAW)%s for game %d; got "
                        "hidden %u, num_actions %u, obs_dim %u, obs_mode %u", actions,
                        sim->game == MRL_GAME_ACROBOT ? " or (6, MRL_OBS_ACROBOT_GYM)" : "", sim->game, policy->hidden,
@@ -75,7 +87,8 @@ int mrl_rollout_policy(mrl_sim *sim, const mrl_mlp_policy *policy, const mrl_rol
         mrl::set_error("mrl_rollout_policy: null rollout buffer");
         return MRL_ERR_INVALID;
     }
-    const uintptr_t row_align = policy->obs_dim == 4 ? 15u : 7u;  // the observation rows are stored 16 / 8 bytes at a time
+    // the observation rows are stored 16 / 8 bytes at a time, the beam's seven floats one by one
+    const uintptr_t row_align = policy->obs_dim == 4 ? 15u : policy->obs_dim == 6 ? 7u : 3u;
     if ((reinterpret_cast<uintptr_t>(b.obs) | reinterpret_cast<uintptr_t>(b.next_obs)) & row_align) {
         mrl::set_error("mrl_rollout_policy: obs and next_obs must start on a %u-byte boundary", (unsigned)row_align + 1u);
         return MRL_ERR_INVALID;
@@ -84,14 +97,27 @@ int mrl_rollout_policy(mrl_sim *sim, const mrl_mlp_policy *policy, const mrl_rol
     return guarded([&] {
         hipStream_t stream = (hipStream_t)hip_stream;
         mrl_tensor_desc state{}, reset{}, reward{}, action{};
-        // (the slot numbers are the same for both games: MRL_CARTPOLE_* == MRL_ACROBOT_*)
-        if (!sim->tensor(MRL_CARTPOLE_STATE, &state) || !sim->tensor(MRL_CARTPOLE_RESET, &reset) ||
-            !sim->tensor(MRL_CARTPOLE_REWARD, &reward) || !sim->tensor(MRL_CARTPOLE_ACTION, &action))
-            throw std::runtime_error("mrl_rollout_policy: the simulator does not export STATE / RESET / REWARD / ACTION");
         const size_t N = sim->num_worlds, D = policy->obs_dim;
         mrl::PolicyActArgs args{};
+        if (beam) {
+            // seat 0 is the ego: the first N rows of OBSERVATION (2, N, 7), REWARD (2, N) and ACTION (2, N, 1); DONE is (N)
+            if (!sim->tensor(MRL_BALANCE_OBSERVATION, &state) || !sim->tensor(MRL_BALANCE_DONE, &reset) ||
+                !sim->tensor(MRL_BALANCE_REWARD, &reward) || !sim->tensor(MRL_BALANCE_ACTION, &action))
+                throw std::runtime_error("mrl_rollout_policy: the simulator does not export OBSERVATION / DONE / REWARD / ACTION");
+            if (state.dtype != MRL_INT32 || state.shape[0] != 2 || state.shape[2] != 7 || reward.dtype != MRL_FLOAT32 ||
+                action.dtype != MRL_INT32 || reset.dtype != MRL_INT32)
+                throw std::runtime_error("mrl_rollout_policy: unexpected tensor layout (OBSERVATION int32 (2, N, 7), REWARD float32, "
+                                         "ACTION and DONE int32)");
+            args.obs_i32 = static_cast<const int32_t *>(state.data);
+            args.partner_action = static_cast<int32_t *>(action.data) + N;
+        } else {
+            // (the slot numbers are the same for both games: MRL_CARTPOLE_* == MRL_ACROBOT_*)
+            if (!sim->tensor(MRL_CARTPOLE_STATE, &state) || !sim->tensor(MRL_CARTPOLE_RESET, &reset) ||
+                !sim->tensor(MRL_CARTPOLE_REWARD, &reward) || !sim->tensor(MRL_CARTPOLE_ACTION, &action))
+                throw std::runtime_error("mrl_rollout_policy: the simulator does not export STATE / RESET / REWARD / ACTION");
+            args.state = static_cast<const float *>(state.data);
+        }
         args.params = policy->params_dev;
-        args.state = static_cast<const float *>(state.data);
         args.reset = static_cast<const int32_t *>(reset.data);
         args.reward = static_cast<const float *>(reward.data);
         args.action_tensor = static_cast<int32_t *>(action.data);
@@ -132,16 +158,25 @@ int mrl_gae(const float *rewards, const float *values, const float *dones, const
 
 static bool ppo_shape_ok(uint32_t obs_dim, uint32_t hidden, uint32_t num_actions)
 {
-    return hidden == mrl::kPolicyHidden && ((obs_dim == 4 && (num_actions == 2 || num_actions == 3)) || (obs_dim == 6 && num_actions == 3));
+    return hidden == mrl::kPolicyHidden && ((obs_dim == 4 && (num_actions == 2 || num_actions == 3)) || (obs_dim == 6 && num_actions == 3) ||
+                                            (obs_dim == 7 && num_actions == 4));
+}
+
+// The shapes a refusal lists.  A call that has nothing of the balance beam's shape is told the float-state games' three, in the
+// words these refusals have always had; one with obs_dim 7 or num_actions 4, which could not be mistaken before the beam had a
+// shape here, is told all four.
+static const char *ppo_shapes(uint32_t obs_dim, uint32_t num_actions)
+{
+    return obs_dim == 7 || num_actions == 4 ? "(4, 2), (4, 3), (6, 3), (7, 4)" : "(4, 2), (4, 3), (6, 3)";
 }
 
 int mrl_ppo_workspace_bytes(uint32_t obs_dim, uint32_t hidden, uint32_t num_actions, uint32_t minibatch_size,
                             uint32_t num_minibatches, uint64_t *out)
 {
     if (!out || !ppo_shape_ok(obs_dim, hidden, num_actions) || minibatch_size == 0) {
-        mrl::set_error("mrl_ppo_workspace_bytes: need an output pointer, hidden = 64, (obs_dim, num_actions) one of (4, 2), (4, 3), "
-                       "(6, 3) and minibatch_size > 0; got hidden %u, obs_dim %u, num_actions %u, minibatch_size %u", hidden, obs_dim,
-                       num_actions, minibatch_size);
+        mrl::set_error("mrl_ppo_workspace_bytes: need an output pointer, hidden = 64, (obs_dim, num_actions) one of %s and "
+                       "minibatch_size > 0; got hidden %u, obs_dim %u, num_actions %u, minibatch_size %u", ppo_shapes(obs_dim, num_actions),
+                       hidden, obs_dim, num_actions, minibatch_size);
         return MRL_ERR_INVALID;
     }
     const uint64_t params = mrl_mlp_policy_num_params(obs_dim, hidden, num_actions);
@@ -164,8 +199,8 @@ int mrl_ppo_update(const mrl_mlp_policy *shape, const mrl_ppo_optimizer *opt, co
         return MRL_ERR_INVALID;
     }
     if (!ppo_shape_ok(shape->obs_dim, shape->hidden, shape->num_actions)) {
-        mrl::set_error("mrl_ppo_update: need hidden = 64 and (obs_dim, num_actions) one of (4, 2), (4, 3), (6, 3); got hidden %u, "
-                       "obs_dim %u, num_actions %u", shape->hidden, shape->obs_dim, shape->num_actions);
+        mrl::set_error("mrl_ppo_update: need hidden = 64 and (obs_dim, num_actions) one of %s; got hidden %u, obs_dim %u, num_actions %u",
+                       ppo_shapes(shape->obs_dim, shape->num_actions), shape->hidden, shape->obs_dim, shape->num_actions);
         return MRL_ERR_INVALID;
     }
     if (minibatch_size == 0 || batch->size == 0 || (minibatch_size < 2 && (cfg->flags & MRL_PPO_NORM_ADV))) {
@@ -175,10 +210,13 @@ int mrl_ppo_update(const mrl_mlp_policy *shape, const mrl_ppo_optimizer *opt, co
     }
     const uint64_t params = mrl_mlp_policy_num_params(shape->obs_dim, shape->hidden, shape->num_actions);
     const uint64_t need_bytes = mrl::ppo_workspace(params, minibatch_size, num_minibatches).total * sizeof(float);
-    const bool wide_rows = shape->obs_dim == 4;  // the observation rows are loaded 16 / 8 bytes at a time
+    // the observation rows are loaded 16 / 8 bytes at a time, the beam's seven floats one by one
+    const uint32_t D = shape->obs_dim;
+    const char *rule = D == 4 ? "obs must start on a 16-byte boundary"
+                     : D == 6 ? "obs must start on a 8-byte boundary"
+                              : "obs must start on a 4-byte boundary for (7, 4) (16 bytes for (4, 2) and (4, 3), 8 for (6, 3))";
     if (int rc = update_refusal("mrl_ppo_update", "mrl_ppo_workspace_bytes", workspace_bytes, need_bytes, workspace_dev,
-                                reinterpret_cast<uintptr_t>(batch->obs) & (wide_rows ? 15u : 7u),
-                                wide_rows ? "obs must start on a 16-byte boundary" : "obs must start on a 8-byte boundary", hip_stream))
+                                reinterpret_cast<uintptr_t>(batch->obs) & (D == 4 ? 15u : D == 6 ? 7u : 3u), rule, hip_stream))
         return rc;
     mrl::DeviceGuard on(gpu_id);
     return guarded([&] {

@@ -9,6 +9,10 @@
 // actor are independent, so they run in different workgroups (blockIdx.y): at 1024 worlds that halves the dependent
 // chain, at large batches it costs one more 16-byte read of the state per world.
 //
+// The balance beam (MRL_OBS_BALANCE, D = 7, A = 4) is the same launch on seat 0's int32 observation row; its actor workgroups
+// also write the other seat's uniformly random move, so the step behind the launch finds both seats' actions (DESIGN.md
+// section 25).
+//
 // Arithmetic: every dot product is bias first, then fmaf over the inputs in ascending order (the Makefile compiles with
 // -ffp-contract=off, so nothing else is fused); tanhf / expf / logf / sinf / cosf are the accurate library versions.
 #include "policy_rollout.hpp"
@@ -53,25 +57,38 @@ __global__ void __launch_bounds__(kActThreads) mrl_policy_act(PolicyActArgs a)
 {
     const uint32_t w = blockIdx.x * kActThreads + threadIdx.x;
     if (w >= a.num_worlds) return;
-    const float4 s = reinterpret_cast<const float4 *>(a.state)[w];
     float x[D];
-    if (MODE == MRL_OBS_ACROBOT_GYM) {  // envs/acrobot_env.py:_observe
-        x[0] = cosf(s.x);
-        x[1] = sinf(s.x);
-        x[2] = cosf(s.y);
-        x[3] = sinf(s.y);
-        x[D - 2] = s.z;
-        x[D - 1] = s.w;
+    if constexpr (MODE == MRL_OBS_BALANCE) {
+        // Seat 0's int32 row.  Rows lie 28 bytes apart, so nothing wider than a dword is aligned: every lane reads its own
+        // seven dwords (the seven loads of a wavefront touch the same 1792 bytes, every cache line of them in full) and
+        // the critic's workgroup stores them the same way.  The values are 0..8 and 0..2: the conversion is exact.
+        const int32_t *__restrict__ in = a.obs_i32 + (size_t)w * D;
+#pragma unroll
+        for (int i = 0; i < D; i++) x[i] = (float)in[i];
     } else {
-        x[0] = s.x;
-        x[1] = s.y;
-        x[2] = s.z;
-        x[3] = s.w;
+        const float4 s = reinterpret_cast<const float4 *>(a.state)[w];
+        if (MODE == MRL_OBS_ACROBOT_GYM) {  // envs/acrobot_env.py:_observe
+            x[0] = cosf(s.x);
+            x[1] = sinf(s.x);
+            x[2] = cosf(s.y);
+            x[3] = sinf(s.y);
+            x[D - 2] = s.z;
+            x[D - 1] = s.w;
+        } else {
+            x[0] = s.x;
+            x[1] = s.y;
+            x[2] = s.z;
+            x[3] = s.w;
+        }
     }
     if (blockIdx.y == 0) {  // critic, and everything that is copied
         float v[1];
         mlp_forward<D, 1>(a.params, x, v);
-        if (D == 4) {
+        if (D % 2) {
+            float *__restrict__ row = a.obs_row + (size_t)w * D;
+#pragma unroll
+            for (int i = 0; i < D; i++) row[i] = x[i];
+        } else if (D == 4) {
             reinterpret_cast<float4 *>(a.obs_row)[w] = make_float4(x[0], x[1], x[2], x[3]);
         } else {
             float2 *row = reinterpret_cast<float2 *>(a.obs_row) + (size_t)w * (D / 2);
@@ -91,12 +108,16 @@ __global__ void __launch_bounds__(kActThreads) mrl_policy_act(PolicyActArgs a)
     a.action_row[w] = action;
     a.action_tensor[w] = action;
     a.logprob_row[w] = logprob;
+    // the beam's other seat moves uniformly at random whatever the ego's flags: mrl_rollout_random's draw of (step, w, player 1)
+    if constexpr (MODE == MRL_OBS_BALANCE) a.partner_action[w] = (int32_t)scale(policy_hash(a.seed, a.step, w, 1), A);
 }
 
 void launch_policy_act(const mrl_mlp_policy &policy, const PolicyActArgs &args, hipStream_t stream)
 {
     const dim3 grid((args.num_worlds + kActThreads - 1) / kActThreads, args.action_row ? 2 : 1);
-    if (policy.obs_mode == MRL_OBS_ACROBOT_GYM)
+    if (policy.obs_mode == MRL_OBS_BALANCE)
+        hipLaunchKernelGGL((mrl_policy_act<7, 4, MRL_OBS_BALANCE>), grid, dim3(kActThreads), 0, stream, args);
+    else if (policy.obs_mode == MRL_OBS_ACROBOT_GYM)
         hipLaunchKernelGGL((mrl_policy_act<6, 3, MRL_OBS_ACROBOT_GYM>), grid, dim3(kActThreads), 0, stream, args);
     else if (policy.num_actions == 3)
         hipLaunchKernelGGL((mrl_policy_act<4, 3, MRL_OBS_RAW>), grid, dim3(kActThreads), 0, stream, args);

@@ -1,5 +1,5 @@
-// mrl_ppo_update: the update phase of PPO for the Cartpole / Acrobot actor-critic without torch in the loop
-// (include/mrl_envs.h, mrl_ppo_update).
+// mrl_ppo_update: the update phase of PPO for the Cartpole / Acrobot actor-critic, and for the same agent on the balance beam
+// (D = 7, A = 4), without torch in the loop (include/mrl_envs.h, mrl_ppo_update; DESIGN.md sections 13 and 25).
 //
 // The reference's trainer runs, per minibatch, a gather, two forward passes, Categorical, the clipped losses, backward(),
 // clip_grad_norm_ and Adam.step() in torch (scripts/cartpole_train_torch.py:275-315).  Here one row is THREE launches,
@@ -29,7 +29,7 @@ namespace {
 constexpr int kH = (int)kPolicyHidden;
 constexpr int kT = (int)kPpoTile;
 constexpr int kLd = kT + 1;  // row stride of the [unit][sample] images: a column and a row both spread over all banks
-constexpr int kMaxD = 6, kMaxOut = 3;
+constexpr int kMaxD = 7, kMaxOut = 4;  // the balance beam's shape
 constexpr int kMeanThreads = 1024;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -50,12 +50,16 @@ struct PpoGradArgs {
     uint32_t flags;
 };
 
+// XD and XOUT size the two small images per instance: Cartpole's and Acrobot's three instances share (6, 3), as before the beam
+// brought (7, 4), so their LDS offsets, and with them their instruction streams, are what they were.
+template <int XD, int XOUT>
 struct PpoLds {
+    static_assert(XD <= kMaxD && XOUT <= kMaxOut, "a shape beyond the largest one launch_ppo_update dispatches on");
     alignas(16) float h1[kH * kLd];  // first hidden layer, [unit][sample]; at the end the lanes' stat sums (as double)
     float h2[kH * kLd];  // second hidden layer; later d1 = dL/d(pre-activation of layer 1)
     float d2[kH * kLd];  // dL/d(pre-activation of layer 2)
-    float x[kMaxD * kT];
-    float d3[kMaxOut * kT];  // dL/d(output)
+    float x[XD * kT];
+    float d3[XOUT * kT];  // dL/d(output)
 };
 
 // What a lane adds up over its samples for the stats row: the actor uses 0 pg, 2 entropy, 3 -logratio, 4 (ratio - 1) -
@@ -135,9 +139,9 @@ __device__ __forceinline__ void critic_head(const PpoGradArgs &a, uint32_t at, c
 }
 
 // One net over this workgroup's share.  p: the net's parameters; gout: its part of this workgroup's partial vector.
-template <int D, int OUT, bool ACTOR>
+template <int D, int OUT, bool ACTOR, class Lds>
 __device__ __forceinline__ void ppo_grad_net(const PpoGradArgs &a, const float *__restrict__ p, float *__restrict__ gout,
-                                             double *__restrict__ sout, PpoLds &lds)
+                                             double *__restrict__ sout, Lds &lds)
 {
     const float *__restrict__ w1 = p, *__restrict__ b1 = w1 + kH * D;
     const float *__restrict__ w2 = b1 + kH, *__restrict__ b2 = w2 + kH * kH;
@@ -170,7 +174,11 @@ __device__ __forceinline__ void ppo_grad_net(const PpoGradArgs &a, const float *
 #pragma unroll
         for (int d = 0; d < D; d++) x[d] = 0.0f;
         if (live) {
-            if (D == 4) {
+            if (D % 2) {  // an odd row length: rows lie D * 4 bytes apart, so only a dword is aligned
+                const float *__restrict__ row = a.obs + (size_t)at * D;
+#pragma unroll
+                for (int d = 0; d < D; d++) x[d] = row[d];
+            } else if (D == 4) {
                 const float4 o = reinterpret_cast<const float4 *>(a.obs)[at];
                 x[0] = o.x, x[1] = o.y, x[2] = o.z, x[3] = o.w;
             } else {
@@ -315,7 +323,7 @@ __device__ __forceinline__ void ppo_grad_net(const PpoGradArgs &a, const float *
 template <int D, int A>
 __global__ void __launch_bounds__(kT) mrl_ppo_grad(PpoGradArgs a)
 {
-    __shared__ PpoLds lds;
+    __shared__ PpoLds<(D > 6 ? D : 6), (A > 3 ? A : 3)> lds;
     float *gout = a.partial_grads + (size_t)blockIdx.x * a.num_params;
     double *sout = a.partial_stats + (size_t)blockIdx.x * kPpoStats;
     if (blockIdx.y == 0) ppo_grad_net<D, 1, false>(a, a.params, gout, sout, lds);
@@ -420,7 +428,9 @@ void launch_ppo_update(const mrl_mlp_policy &shape, const mrl_ppo_optimizer &opt
     for (uint32_t k = 0; k < num_minibatches; k++) {
         g.indices = indices + (size_t)k * minibatch_size;
         g.mean_std = norm ? workspace + ws.mean_std + 2 * (size_t)k : nullptr;
-        if (D == 6)
+        if (D == 7)
+            hipLaunchKernelGGL((mrl_ppo_grad<7, 4>), grid, dim3(kT), 0, stream, g);
+        else if (D == 6)
             hipLaunchKernelGGL((mrl_ppo_grad<6, 3>), grid, dim3(kT), 0, stream, g);
         else if (A == 3)
             hipLaunchKernelGGL((mrl_ppo_grad<4, 3>), grid, dim3(kT), 0, stream, g);
