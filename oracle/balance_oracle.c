@@ -53,10 +53,11 @@ static void reset_world(orc_balance *s, uint32_t w)
     }
 }
 
-orc_balance *orc_balance_create(uint32_t num_worlds)
+orc_balance *orc_balance_create_at(uint32_t num_worlds, uint32_t first_episode)
 {
     orc_balance *s = (orc_balance *)calloc(1, sizeof(*s));
     s->n = num_worlds;
+    s->next_episode = first_episode;
     s->loc = (int32_t *)calloc((size_t)2 * num_worlds, sizeof(int32_t));
     s->time = (int32_t *)calloc(num_worlds, sizeof(int32_t));
     s->obs = (int32_t *)calloc((size_t)2 * num_worlds * B_ROW, sizeof(int32_t));
@@ -65,6 +66,8 @@ orc_balance *orc_balance_create(uint32_t num_worlds)
     for (uint32_t w = 0; w < num_worlds; w++) reset_world(s, w);
     return s;
 }
+
+orc_balance *orc_balance_create(uint32_t num_worlds) { return orc_balance_create_at(num_worlds, 0); }
 
 void orc_balance_destroy(orc_balance *s)
 {

@@ -79,10 +79,11 @@ static void reset_world(orc_cartpole *s, uint32_t wi, uint32_t episode)
     s->rng[wi] = g;
 }
 
-orc_cartpole *orc_cartpole_create(uint32_t num_worlds)
+orc_cartpole *orc_cartpole_create_at(uint32_t num_worlds, uint32_t first_episode)
 {
     orc_cartpole *s = (orc_cartpole *)calloc(1, sizeof(*s));
     s->n = num_worlds;
+    s->next_episode = first_episode;
     s->state = (float *)calloc((size_t)num_worlds * 4, sizeof(float));
     s->reward = (float *)calloc(num_worlds, sizeof(float));
     s->done = (int32_t *)calloc(num_worlds, sizeof(int32_t));
@@ -90,6 +91,8 @@ orc_cartpole *orc_cartpole_create(uint32_t num_worlds)
     for (uint32_t wi = 0; wi < num_worlds; wi++) reset_world(s, wi, s->next_episode++);
     return s;
 }
+
+orc_cartpole *orc_cartpole_create(uint32_t num_worlds) { return orc_cartpole_create_at(num_worlds, 0); }
 
 void orc_cartpole_destroy(orc_cartpole *s)
 {

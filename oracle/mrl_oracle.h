@@ -107,6 +107,8 @@ void orc_simplecooked_dump(const orc_simplecooked *s, uint8_t *players, uint8_t 
 typedef struct orc_cartpole orc_cartpole;
 
 orc_cartpole *orc_cartpole_create(uint32_t num_worlds);
+/* as orc_cartpole_create, the first world starting episode first_episode (the counter wraps at 2^32) */
+orc_cartpole *orc_cartpole_create_at(uint32_t num_worlds, uint32_t first_episode);
 void orc_cartpole_destroy(orc_cartpole *s);
 /* actions: (N, 1) int32.  Episode indices are handed out in ascending world
  * order within a step (what a one-thread executor does). */
@@ -123,6 +125,8 @@ uint32_t orc_cartpole_episodes(const orc_cartpole *s);
 typedef struct orc_balance orc_balance;
 
 orc_balance *orc_balance_create(uint32_t num_worlds);
+/* as orc_balance_create, the first world starting episode first_episode (the counter wraps at 2^32) */
+orc_balance *orc_balance_create_at(uint32_t num_worlds, uint32_t first_episode);
 void orc_balance_destroy(orc_balance *s);
 /* actions: (2, N) int32, 0..3 = moves -2, -1, +1, +2.  Worlds are stepped in order (episode indices). */
 void orc_balance_step(orc_balance *s, const int32_t *actions);

@@ -76,6 +76,8 @@ def lib():
 
         L.orc_balance_create.restype = vp
         L.orc_balance_create.argtypes = [u32]
+        L.orc_balance_create_at.restype = vp
+        L.orc_balance_create_at.argtypes = [u32, u32]
         L.orc_balance_destroy.argtypes = [vp]
         L.orc_balance_step.argtypes = [vp, i32p]
         for name, rt in (("obs", i32p), ("loc", i32p), ("time", i32p), ("reward", ctypes.POINTER(ctypes.c_float)), ("done", i32p)):
@@ -86,6 +88,8 @@ def lib():
 
         L.orc_cartpole_create.restype = vp
         L.orc_cartpole_create.argtypes = [u32]
+        L.orc_cartpole_create_at.restype = vp
+        L.orc_cartpole_create_at.argtypes = [u32, u32]
         L.orc_cartpole_destroy.argtypes = [vp]
         L.orc_cartpole_step.argtypes = [vp, i32p, ctypes.c_int]
         L.orc_cartpole_state.restype = ctypes.POINTER(ctypes.c_float)
@@ -237,10 +241,10 @@ class SimplecookedOracle:
 class BalanceOracle:
     """N worlds of the reference's balance-beam step on the CPU (worlds in order: episode numbering)."""
 
-    def __init__(self, num_worlds):
+    def __init__(self, num_worlds, first_episode=0):
         self.L = lib()
         self.N = int(num_worlds)
-        self.h = self.L.orc_balance_create(self.N)
+        self.h = self.L.orc_balance_create_at(self.N, int(first_episode) & 0xFFFFFFFF)
         self.obs = _view(self.L.orc_balance_obs(self.h), (2, self.N, 7), np.int32)
         self.loc = _view(self.L.orc_balance_loc(self.h), (2, self.N), np.int32)
         self.time = _view(self.L.orc_balance_time(self.h), (self.N,), np.int32)
@@ -274,11 +278,11 @@ class BalanceOracle:
 
 
 class CartpoleOracle:
-    def __init__(self, num_worlds, num_threads=1):
+    def __init__(self, num_worlds, num_threads=1, first_episode=0):
         self.L = lib()
         self.N = int(num_worlds)
         self.num_threads = num_threads
-        self.h = self.L.orc_cartpole_create(self.N)
+        self.h = self.L.orc_cartpole_create_at(self.N, int(first_episode) & 0xFFFFFFFF)
         self.state = _view(self.L.orc_cartpole_state(self.h), (self.N, 4), np.float32)
         self.reward = _view(self.L.orc_cartpole_reward(self.h), (self.N, 1), np.float32)
         self.done = _view(self.L.orc_cartpole_done(self.h), (self.N, 1), np.int32)
