@@ -586,6 +586,18 @@ int mrl_clear_episode_totals(mrl_sim *sim, void *hip_stream);
  *   and ACTION holds the last row of both seats.  MRL_ERR_INVALID for any other shape or mode on a beam, MRL_OBS_BALANCE on
  *   another game, a beam that has been through mrl_exchange_create, and a capturing stream in every mode.  A caller-supplied or
  *   learned partner is what mrl_rollout_mlpbase and the banks are for.  The other games are out of scope.  DESIGN.md section 25.
+ *   A bank of policies (K seeds of one agent on one batch): policy->num_members = K > 0.  The field lies in
+ *   what used to be the struct's four bytes of tail padding, so sizeof and every other offset are what they were, and 0 -- what
+ *   every caller that zero-fills the struct passes -- is the behaviour above, bit for bit.  With K > 0 the simulator's N worlds
+ *   are K members of W = N / K worlds: member k owns worlds [k W, (k + 1) W) and acts under the parameters that start k P floats
+ *   behind params_dev, P = mrl_mlp_policy_num_params.  The bank is DENSE, there is no stride; P is odd for (4, 2) and (7, 4), 9155 and
+ *   9669, so a row is only 4-byte aligned, which is all the kernel asks of any shape.  One launch per step serves all members ((ceil(W / 64), nets,
+ *   K) workgroups).  Contract: for every world w of member k, every cell the call writes -- obs, dones, values, actions,
+ *   logprobs, rewards, next_obs, next_value, next_done, ACTION[w] and on the beam ACTION[1,w] -- is bit for bit what the plain
+ *   mrl_rollout_policy writes for world w under policy k alone on the same simulator state.  The draws are those of world w IN THE
+ *   BATCH OF N (the hash of (seed, first_step + k, w, player) with w = k W + j), and the episode numbers are the batch's: they are
+ *   not those of a simulator that holds the member's W worlds alone.  Everything the plain call refuses is refused in the same
+ *   words; then, MRL_ERR_INVALID: K > 65535 (the member travels in the launch grid's third dimension), K > N, and N % K != 0.
  * mrl_gae is lines 247-256 with a lane per world, t = T-1 ... 0 in float32, one IEEE operation per operation of the script:
  *     nnt = 1 - (t == T-1 ? next_done[w] : dones[t+1,w]);  nv = t == T-1 ? next_value[w] : values[t+1,w]
  *     delta = rewards[t,w] + gamma * nv * nnt - values[t,w]
@@ -597,6 +609,7 @@ enum { MRL_POLICY_GREEDY = 1 };
 typedef struct mrl_mlp_policy {
     const float *params_dev;
     uint32_t obs_dim, hidden, num_actions, obs_mode, flags;
+    uint32_t num_members; /* 0: one policy.  K > 0: a bank, params_dev is (K, P) dense (below).  In what was tail padding. */
 } mrl_mlp_policy;
 typedef struct mrl_rollout_buffers { /* all device pointers, dense, T = num_steps */
     float *obs;                      /* (T, N, D) */
@@ -645,7 +658,18 @@ int mrl_gae(const float *rewards, const float *values, const float *dones, const
  *     16-byte one; a capturing stream (the step number travels in kernel arguments).  num_minibatches == 0 enqueues nothing.
  *     mrl_ppo_workspace_bytes refuses the same shapes and a NULL out.  The words of a shape refusal: a call with neither
  *     obs_dim 7 nor num_actions 4 is told "(4, 2), (4, 3), (6, 3)", the float-state games' shapes, as before the beam had one;
- *     a call with either is told all four.  DESIGN.md sections 13 and 25. */
+ *     a call with either is told all four.  DESIGN.md sections 13 and 25.
+ *   A bank update: opt->num_members = M > 0, a field in what used to be the struct's tail padding; 0 is the
+ *     call above, bit for bit.  opt->params_dev, exp_avg and exp_avg_sq point at the first trained member's row and M dense rows
+ *     of P floats follow in each (a caller trains members first .. first + M - 1 of a bank by offsetting the three pointers; P is
+ *     odd for (4, 2) and (7, 4), so a row is only 4-byte aligned).  indices is (M, K, B), stats (M, K, 8), grads (M, K, P); the workspace is M times
+ *     mrl_ppo_workspace_bytes and member m uses slice m.  The batch, the configuration -- learning rate, betas, loss options -- and
+ *     step are shared by all members.  The launches are those of the plain call with the member in the grid's third dimension:
+ *     1 + 3 K whatever M is.  Contract: for every trained member the parameter row, both moment rows, the stats and the grads are
+ *     bit for bit what the plain mrl_ppo_update leaves for that member alone with indices[m] on the same batch; rows of the bank
+ *     that are not trained keep every bit; one call of K rows equals K calls of one row.  MRL_ERR_INVALID, after the checks above
+ *     in their order: M > 65535; the workspace refusal asks for M times the plain size.  mrl_agent_update, which takes the same
+ *     struct, refuses num_members != 0. */
 enum { MRL_PPO_NORM_ADV = 1, MRL_PPO_CLIP_VLOSS = 2 };
 typedef struct mrl_ppo_config {
     float clip_coef, ent_coef, vf_coef, max_grad_norm; /* max_grad_norm <= 0: no clipping */
@@ -662,6 +686,7 @@ typedef struct mrl_ppo_optimizer {
     float *params_dev;           /* the tensor mrl_mlp_policy.params_dev points at; updated in place */
     float *exp_avg, *exp_avg_sq; /* (P) each */
     uint32_t step;               /* Adam steps taken BEFORE this call; row k uses step + 1 + k */
+    uint32_t num_members;        /* 0: one policy.  M > 0: mrl_ppo_update steps M dense rows (above).  In what was tail padding. */
 } mrl_ppo_optimizer;
 int mrl_ppo_workspace_bytes(uint32_t obs_dim, uint32_t hidden, uint32_t num_actions, uint32_t minibatch_size,
                             uint32_t num_minibatches, uint64_t *out);

@@ -88,7 +88,8 @@ class HanabiConfig(ctypes.Structure):
 
 class MlpPolicyDesc(ctypes.Structure):  # mrl_mlp_policy
     _fields_ = [("params_dev", ctypes.c_void_p), ("obs_dim", ctypes.c_uint32), ("hidden", ctypes.c_uint32),
-                ("num_actions", ctypes.c_uint32), ("obs_mode", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+                ("num_actions", ctypes.c_uint32), ("obs_mode", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("num_members", ctypes.c_uint32)]  # in what was tail padding; 0, which ctypes fills in, is one policy
 
 
 class RolloutBuffers(ctypes.Structure):  # mrl_rollout_buffers
@@ -108,7 +109,7 @@ class PpoBatch(ctypes.Structure):  # mrl_ppo_batch
 
 class PpoOptimizerDesc(ctypes.Structure):  # mrl_ppo_optimizer
     _fields_ = [("params_dev", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p),
-                ("step", ctypes.c_uint32)]
+                ("step", ctypes.c_uint32), ("num_members", ctypes.c_uint32)]  # the same: 0 is one policy
 
 
 class WidePolicyDesc(ctypes.Structure):  # mrl_wide_policy

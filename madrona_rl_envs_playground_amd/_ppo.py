@@ -1,8 +1,9 @@
-"""PPO for the small MLP actor-critic of Cartpole and Acrobot -- the policy, its rollout on the device, GAE and the update -- and
-what the other learners take from it: ``Rollout``, ``gae``, ``_AdamState``, ``_run_update``, ``PpoResult`` and the two helpers that
-read an agent made of ``Sequential(Linear, activation, ...)``.  Every name here is also ``simulators``'.
+"""PPO for the small MLP actor-critic of Cartpole and Acrobot -- the policy, its rollout on the device, GAE and the update, for one
+policy and for the K members of an ``MlpPolicyBank`` on one batch -- and what the other learners take from it: ``Rollout``,
+``gae``, ``_AdamState``, ``_run_update``, ``PpoResult`` and the two helpers that read an agent made of ``Sequential(Linear,
+activation, ...)``.  Every name here is also ``simulators``'.
 
-May import: _lib, _device, torch.
+May import: _lib, _device, _bank, torch.
 """
 import collections
 import ctypes
@@ -10,6 +11,7 @@ import ctypes
 import torch
 
 from . import _lib
+from ._bank import _PolicyBank
 from ._device import _require_tensors, _stream_ptr
 
 
@@ -125,6 +127,40 @@ class MlpPolicy:
         return agent
 
 
+class MlpPolicyBank(_PolicyBank):
+    """K ``MlpPolicy`` of one shape in one dense float32 tensor ``params`` (K, P), P = ``mrl_mlp_policy_num_params``: K seeds of the
+    small PPO agent.  ``policy(k)`` is an ``MlpPolicy`` whose ``params`` IS row k, a contiguous view, so ``rollout_policy``,
+    ``PpoOptimizer`` and ``ppo_update`` work on a member unchanged and in place.  On a simulator of N = K W worlds member k owns
+    worlds ``[k W, (k + 1) W)``: ``rollout_policy_bank`` lets every world act under its member's policy in one launch per step,
+    ``ppo_update_bank`` steps every member in one call.  1 <= K <= 256; ``observation`` is ``MlpPolicy``'s."""
+
+    _member_class, _shape = MlpPolicy, ("obs_dim", "num_actions", "hidden", "observation")
+
+    def __init__(self, obs_dim, num_actions, num_policies, hidden=64, observation="state", device="cuda:0"):
+        self.obs_dim, self.num_actions, self.hidden, self.observation = int(obs_dim), int(num_actions), int(hidden), observation
+        super().__init__(num_policies, device)
+
+    def _count_params(self):
+        # (an MlpPolicy on no device refuses, in its own words, an observation it does not know and a beam of another shape)
+        return MlpPolicy(self.obs_dim, self.num_actions, self.hidden, self.observation, device="meta").params.numel()
+
+    @classmethod
+    def from_modules(cls, agents, observation="state", device=None):
+        """A bank holding copies of the parameters of ``agents`` (``MlpPolicy.from_module``'s form, all of one shape), in that
+        order (``device``: default the first agent's)."""
+        agents = list(agents)
+        if not agents:
+            raise ValueError("from_modules takes a non-empty list of agents")
+        shapes = [MlpPolicy._shape_of(agent) for agent in agents]
+        if any(shape != shapes[0] for shape in shapes):
+            raise ValueError(f"the agents of a bank must have one shape, got (obs_dim, num_actions, hidden) = {sorted(set(shapes))}")
+        d, a, h = shapes[0]
+        bank = cls(d, a, len(agents), h, observation, device if device is not None else agents[0].critic[0].weight.device)
+        for k, agent in enumerate(agents):
+            bank.policy(k).load_(agent)
+        return bank
+
+
 # what ``rollout_policy`` fills, the names of scripts/cartpole_train_torch.py:179-192: (T, N, D), (T, N) x 5, (N, D), (N), (N)
 Rollout = collections.namedtuple("Rollout", "obs actions logprobs values rewards dones next_obs next_value next_done")
 
@@ -226,6 +262,64 @@ def minibatch_indices(batch_size, num_minibatches, epochs, generator=None, devic
     return torch.stack(rows).reshape(epochs * num_minibatches, width)
 
 
+class PpoBankOptimizer(_AdamState):
+    """``PpoOptimizer`` for every member of an ``MlpPolicyBank`` at once: ``exp_avg`` and ``exp_avg_sq`` (K, P), row k the moments
+    of bank row k, ONE ``step`` -- every member has taken the same number of Adam steps -- and one ``lr`` (assignable).
+    ``member(k)`` is a ``PpoOptimizer`` for ``bank.policy(k)`` whose moments are VIEWS of row k and whose ``step`` is this one's
+    at the time of the call: the plain ``ppo_update`` steps that member alone (the bank's ``step`` does not follow)."""
+
+    def __init__(self, bank, lr=2.5e-4, betas=(0.9, 0.999), eps=1e-5):
+        if not isinstance(bank, MlpPolicyBank):
+            raise ValueError("bank must be an MlpPolicyBank")
+        super().__init__(bank, betas, eps)  # (the moments take bank.params' shape)
+        self.bank = bank
+        self.lr = float(lr)
+
+    def member(self, k):
+        member = PpoOptimizer(self.bank.policy(k), self.lr, self.betas, self.eps)
+        member.exp_avg, member.exp_avg_sq, member.step = self.exp_avg[int(k)], self.exp_avg_sq[int(k)], self.step
+        return member
+
+    def workspace_bytes(self, minibatch_size, num_minibatches, num_members=1):
+        """``num_members`` times ``mrl_ppo_workspace_bytes`` for the bank's shape: a slice per member trained in one call."""
+        b = self.bank
+        out = ctypes.c_uint64(0)
+        _lib.check(_lib.lib().mrl_ppo_workspace_bytes(b.obs_dim, b.hidden, b.num_actions, int(minibatch_size), int(num_minibatches),
+                                                      ctypes.byref(out)))
+        return int(out.value) * int(num_members)
+
+    def workspace(self, minibatch_size, num_minibatches, num_members=1):
+        return self._cached_workspace(self.workspace_bytes(minibatch_size, num_minibatches, num_members))
+
+
+def member_minibatch_indices(num_steps, num_worlds, num_members, num_minibatches, epochs, generator=None, device="cpu"):
+    """The rows ``ppo_update_bank`` takes for a rollout of ``num_steps`` on ``num_worlds`` = N worlds shared by ``num_members`` = K
+    members: int32 (K, epochs * num_minibatches, T W // num_minibatches) on ``device``, W = N // K.  Per member and epoch it is
+    one ``torch.randperm(T W)`` -- member 0's epochs first, then member 1's -- cut into ``num_minibatches`` rows; entry q of a
+    permutation stands for step ``q // W`` of the member's world ``q % W`` and becomes the flat sample number ``t N + k W + j``.
+    Every epoch of member k therefore holds exactly member k's samples, each once.  ``generator``: one generator, or a sequence
+    of K, member k's own."""
+    t, n, k, mb, epochs = int(num_steps), int(num_worlds), int(num_members), int(num_minibatches), int(epochs)
+    if t <= 0 or n <= 0 or k <= 0 or n % k:
+        raise ValueError(f"num_worlds ({num_worlds}) must be a positive multiple of num_members ({num_members}), num_steps positive")
+    w = n // k
+    if mb <= 0 or epochs < 0 or (t * w) % mb:
+        raise ValueError(f"a member's {t * w} samples (T W) must be a positive multiple of num_minibatches ({num_minibatches}), "
+                         f"epochs not negative")
+    if t * n >= 2 ** 31:
+        raise ValueError("the sample numbers are int32: T N must stay below 2^31")
+    generators = list(generator) if isinstance(generator, (list, tuple)) else [generator] * k
+    if len(generators) != k:
+        raise ValueError(f"generator must be one generator or one per member ({k})")
+    out = torch.empty((k, epochs, t * w), dtype=torch.int32, device=device)
+    for member, g in enumerate(generators):
+        where = g.device if g is not None else torch.device(device)
+        for epoch in range(epochs):
+            q = torch.randperm(t * w, generator=g, device=where).to(device)
+            out[member, epoch] = (q // w) * n + member * w + q % w
+    return out.reshape(k, epochs * mb, (t * w) // mb)
+
+
 PpoResult = collections.namedtuple("PpoResult", "stats grads")  # (K, 8) in the order of ``_lib.PPO_STATS`` / (K, P), or None
 
 
@@ -243,22 +337,73 @@ def ppo_update(policy, optimizer, rollout, advantages, returns, indices, clip_co
     p = policy.params
     if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
         raise ValueError("policy.params must be a contiguous float32 tensor on a GPU")
-    device, f32 = p.device, torch.float32
+    head, cfg = _ppo_structs(policy, "policy.params", p, optimizer.exp_avg, optimizer.exp_avg_sq, optimizer, 0, rollout, advantages,
+                             returns, indices, clip_coef, ent_coef, vf_coef, max_grad_norm, norm_adv, clip_vloss)
+    return _run_update(_lib.lib().mrl_ppo_update, tuple(ctypes.byref(struct) for struct in head), indices, (ctypes.byref(cfg),),
+                       optimizer, len(_lib.PPO_STATS), PpoResult, stats, grads)
+
+
+def _ppo_structs(shape, name, params, exp_avg, exp_avg_sq, optimizer, members, rollout, advantages, returns, indices, clip_coef, ent_coef,
+                 vf_coef, max_grad_norm, norm_adv, clip_vloss):
+    """What ``ppo_update`` and ``ppo_update_bank`` check and build alike -> ((shape, optimizer, batch), configuration) structs of
+    ``mrl_ppo_update``.  ``params`` (called ``name``), ``exp_avg`` and ``exp_avg_sq``: the policy's arrays, or the trained rows
+    of a bank's; ``members``: 0, or how many rows."""
+    device, f32 = params.device, torch.float32
     count = rollout.values.numel()
-    wanted = (("policy.params", p, f32, p.numel()), ("optimizer.exp_avg", optimizer.exp_avg, f32, p.numel()),
-              ("optimizer.exp_avg_sq", optimizer.exp_avg_sq, f32, p.numel()), ("rollout.obs", rollout.obs, f32, count * policy.obs_dim),
+    wanted = ((name, params, f32, params.numel()), ("optimizer.exp_avg", exp_avg, f32, params.numel()),
+              ("optimizer.exp_avg_sq", exp_avg_sq, f32, params.numel()), ("rollout.obs", rollout.obs, f32, count * shape.obs_dim),
               ("rollout.actions", rollout.actions, torch.int32, count), ("rollout.logprobs", rollout.logprobs, f32, count),
               ("rollout.values", rollout.values, f32, count), ("advantages", advantages, f32, count), ("returns", returns, f32, count),
               ("indices", indices, torch.int32, None))
     _require_tensors(wanted, device)
-    shape = _lib.MlpPolicyDesc(p.data_ptr(), policy.obs_dim, policy.hidden, policy.num_actions, 0, 0)
-    opt = _lib.PpoOptimizerDesc(p.data_ptr(), optimizer.exp_avg.data_ptr(), optimizer.exp_avg_sq.data_ptr(), optimizer.step)
-    batch = _lib.PpoBatch(rollout.obs.data_ptr(), rollout.actions.data_ptr(), rollout.logprobs.data_ptr(), advantages.data_ptr(),
-                          returns.data_ptr(), rollout.values.data_ptr(), count)
+    head = (_lib.MlpPolicyDesc(params.data_ptr(), shape.obs_dim, shape.hidden, shape.num_actions, 0, 0),
+            _lib.PpoOptimizerDesc(params.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), optimizer.step, members),
+            _lib.PpoBatch(rollout.obs.data_ptr(), rollout.actions.data_ptr(), rollout.logprobs.data_ptr(), advantages.data_ptr(),
+                          returns.data_ptr(), rollout.values.data_ptr(), count))
     cfg = _lib.PpoConfig(clip_coef, ent_coef, vf_coef, max_grad_norm, optimizer.lr, optimizer.betas[0], optimizer.betas[1],
                          optimizer.eps, (_lib.PPO_NORM_ADV if norm_adv else 0) | (_lib.PPO_CLIP_VLOSS if clip_vloss else 0))
-    return _run_update(_lib.lib().mrl_ppo_update, (ctypes.byref(shape), ctypes.byref(opt), ctypes.byref(batch)), indices,
-                       (ctypes.byref(cfg),), optimizer, len(_lib.PPO_STATS), PpoResult, stats, grads)
+    return head, cfg
+
+
+def ppo_update_bank(bank, optimizer, rollout, advantages, returns, indices, clip_coef=0.2, ent_coef=0.01, vf_coef=0.5,
+                    max_grad_norm=0.5, norm_adv=True, clip_vloss=True, stats=True, grads=False, first_member=0):
+    """``ppo_update`` for M members of an ``MlpPolicyBank`` in one call (``mrl_ppo_update`` with ``num_members`` = M): one Adam
+    step per row for every member, in the plain update's 1 + 3 R launches whatever M is.  ``indices`` is (M, R, B) int32, row m
+    the rows of bank row ``first_member + m`` (``member_minibatch_indices``); ``rollout``, ``advantages`` and ``returns`` are
+    everyone's -- the record of a ``rollout_policy_bank`` on N worlds and its ``gae``.  ``optimizer`` is the ``PpoBankOptimizer``
+    made for ``bank``; its ``step`` grows by R.  For every trained member the parameter row, both moment rows, the stats and the
+    grads are bit for bit what ``ppo_update`` leaves for ``bank.policy(k)`` alone with ``indices[m]``; the other rows keep every
+    bit.  Returns ``PpoResult(stats, grads)``: (M, R, 8) and (M, R, P), each None unless asked for."""
+    if not isinstance(bank, MlpPolicyBank) or not isinstance(optimizer, PpoBankOptimizer) or optimizer.bank is not bank:
+        raise ValueError("bank must be an MlpPolicyBank and optimizer the PpoBankOptimizer made for it")
+    p = bank.params
+    if not p.is_cuda:
+        raise ValueError("bank.params must be a contiguous float32 tensor (num_policies, num_params) on a GPU")
+    bank._check_params(p.device.index)
+    if not isinstance(indices, torch.Tensor) or indices.dim() != 3:
+        raise ValueError("indices must be (members, rows, minibatch_size)")
+    members, rows, width = indices.shape
+    first = int(first_member)
+    if members < 1 or first < 0 or first + members > bank.num_policies:
+        raise ValueError(f"indices holds the rows of {members} members from member {first_member}; the bank holds members "
+                         f"0..{bank.num_policies - 1}")
+    for name, moments in (("exp_avg", optimizer.exp_avg), ("exp_avg_sq", optimizer.exp_avg_sq)):
+        if not isinstance(moments, torch.Tensor) or moments.shape != p.shape:
+            raise ValueError(f"optimizer.{name} must have bank.params' shape")
+    trained = slice(first, first + members)
+    head, cfg = _ppo_structs(bank, "bank.params", p[trained], optimizer.exp_avg[trained], optimizer.exp_avg_sq[trained], optimizer,
+                             members, rollout, advantages, returns, indices, clip_coef, ent_coef, vf_coef, max_grad_norm, norm_adv,
+                             clip_vloss)
+    workspace = optimizer.workspace(width, rows, members) if width else None
+    out_stats = torch.empty((members, rows, len(_lib.PPO_STATS)), dtype=torch.float32, device=p.device) if stats else None
+    out_grads = torch.empty((members, rows, bank.num_params), dtype=torch.float32, device=p.device) if grads else None
+    gpu = p.device.index
+    _lib.check(_lib.lib().mrl_ppo_update(*[ctypes.byref(struct) for struct in head], indices.data_ptr(), rows, width, ctypes.byref(cfg),
+                                         workspace.data_ptr() if workspace is not None else None,
+                                         workspace.numel() if workspace is not None else 0, out_stats.data_ptr() if stats else None,
+                                         out_grads.data_ptr() if grads else None, gpu, _stream_ptr(gpu)))
+    optimizer.step += rows
+    return PpoResult(out_stats, out_grads)
 
 
 class _PolicyRollout:
@@ -278,6 +423,24 @@ class _PolicyRollout:
             raise ValueError(f"policy.params must be a contiguous float32 tensor on cuda:{self.gpu_id} (the simulator's device)")
         if p.numel() != int(self._L.mrl_mlp_policy_num_params(policy.obs_dim, policy.hidden, policy.num_actions)):
             raise ValueError("policy.params does not have mrl_mlp_policy_num_params elements")
+        return self._rollout_mlp(policy, p, 0, num_steps, seed, first_step, out, greedy)
+
+    def rollout_policy_bank(self, bank, num_steps, seed=0, first_step=0, out=None, greedy=False):
+        """``rollout_policy`` for the K members of ``bank`` (an ``MlpPolicyBank`` on this GPU) on one batch
+        (``mrl_rollout_policy`` with ``num_members`` = K): this simulator's N = K W worlds are K members of W, member k owns worlds
+        ``[k W, (k + 1) W)`` and acts under ``bank.policy(k)``; still two launches per step.  Returns a ``Rollout`` whose columns
+        ``[k W, (k + 1) W)`` are member k's.  Every cell is bit for bit what ``rollout_policy(bank.policy(k), ...)`` writes for
+        that world on the same simulator state: the draws and the episode numbers are those of world w in the batch of N, not
+        those of a simulator holding the member's W worlds alone."""
+        if not isinstance(bank, MlpPolicyBank):
+            raise ValueError("bank must be an MlpPolicyBank")
+        bank._check_params(self.gpu_id)
+        if bank.num_params != int(self._L.mrl_mlp_policy_num_params(bank.obs_dim, bank.hidden, bank.num_actions)):
+            raise ValueError("bank.params' rows do not have mrl_mlp_policy_num_params elements")
+        return self._rollout_mlp(bank, bank.params, bank.num_policies, num_steps, seed, first_step, out, greedy)
+
+    def _rollout_mlp(self, policy, p, members, num_steps, seed, first_step, out, greedy):
+        """``mrl_rollout_policy`` under checked parameters ``p`` of ``policy``'s shape (a policy's, or with ``members`` a bank's)"""
         t, n, d = int(num_steps), self.num_worlds, policy.obs_dim
         if t < 0:
             raise ValueError("num_steps must not be negative")
@@ -292,7 +455,7 @@ class _PolicyRollout:
                         tensor.dtype != (torch.int32 if name == "actions" else f32) or not tensor.is_contiguous()):
                     raise ValueError(f"out.{name} must be a contiguous {shape} tensor on cuda:{self.gpu_id}")
         desc = _lib.MlpPolicyDesc(p.data_ptr(), d, policy.hidden, policy.num_actions, MlpPolicy._OBS_MODES[policy.observation],
-                                  _lib.POLICY_GREEDY if greedy else 0)
+                                  _lib.POLICY_GREEDY if greedy else 0, members)
         buffers = _lib.RolloutBuffers(*[tensor.data_ptr() for tensor in out], t)
         _lib.check(self._L.mrl_rollout_policy(self._handle, ctypes.byref(desc), ctypes.byref(buffers),
                                               int(seed) & (2 ** 64 - 1), int(first_step) & 0xFFFFFFFF, _stream_ptr(self.gpu_id)))

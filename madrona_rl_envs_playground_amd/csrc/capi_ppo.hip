@@ -93,6 +93,13 @@ int mrl_rollout_policy(mrl_sim *sim, const mrl_mlp_policy *policy, const mrl_rol
         mrl::set_error("mrl_rollout_policy: obs and next_obs must start on a %u-byte boundary", (unsigned)row_align + 1u);
         return MRL_ERR_INVALID;
     }
+    // a bank (num_members != 0): equal shares of the batch, the member in blockIdx.z
+    const uint32_t K = policy->num_members;
+    if (K && (K > 65535u || K > sim->num_worlds || sim->num_worlds % K)) {
+        mrl::set_error("mrl_rollout_policy: a bank of %u members on %u worlds; every member owns the same number of worlds, at least "
+                       "one, so num_worlds must be a multiple of num_members, and num_members at most 65535", K, sim->num_worlds);
+        return MRL_ERR_INVALID;
+    }
     mrl::DeviceGuard on(sim->device);
     return guarded([&] {
         hipStream_t stream = (hipStream_t)hip_stream;
@@ -123,6 +130,7 @@ int mrl_rollout_policy(mrl_sim *sim, const mrl_mlp_policy *policy, const mrl_rol
         args.action_tensor = static_cast<int32_t *>(action.data);
         args.seed = seed;
         args.num_worlds = sim->num_worlds;
+        args.member_worlds = K ? sim->num_worlds / K : 0;
         args.flags = policy->flags;
         for (uint32_t k = 0; k <= T; k++) {
             const bool closing = k == T;
@@ -209,7 +217,9 @@ int mrl_ppo_update(const mrl_mlp_policy *shape, const mrl_ppo_optimizer *opt, co
         return MRL_ERR_INVALID;
     }
     const uint64_t params = mrl_mlp_policy_num_params(shape->obs_dim, shape->hidden, shape->num_actions);
-    const uint64_t need_bytes = mrl::ppo_workspace(params, minibatch_size, num_minibatches).total * sizeof(float);
+    // a bank update (opt->num_members != 0) takes one slice per member
+    const uint64_t need_bytes = mrl::ppo_workspace(params, minibatch_size, num_minibatches).total * sizeof(float) *
+                                (opt->num_members ? opt->num_members : 1u);
     // the observation rows are loaded 16 / 8 bytes at a time, the beam's seven floats one by one
     const uint32_t D = shape->obs_dim;
     const char *rule = D == 4 ? "obs must start on a 16-byte boundary"
@@ -218,6 +228,11 @@ int mrl_ppo_update(const mrl_mlp_policy *shape, const mrl_ppo_optimizer *opt, co
     if (int rc = update_refusal("mrl_ppo_update", "mrl_ppo_workspace_bytes", workspace_bytes, need_bytes, workspace_dev,
                                 reinterpret_cast<uintptr_t>(batch->obs) & (D == 4 ? 15u : D == 6 ? 7u : 3u), rule, hip_stream))
         return rc;
+    if (opt->num_members > 65535u) {
+        mrl::set_error("mrl_ppo_update: %u members; the member travels in the launch grid's third dimension, so at most 65535",
+                       opt->num_members);
+        return MRL_ERR_INVALID;
+    }
     mrl::DeviceGuard on(gpu_id);
     return guarded([&] {
         mrl::launch_ppo_update(*shape, *opt, *batch, indices_dev, num_minibatches, minibatch_size, *cfg,

@@ -209,6 +209,11 @@ int mrl_agent_update(const mrl_wide_policy *policy, const mrl_ppo_optimizer *opt
     if (int rc = update_refusal("mrl_agent_update", "mrl_agent_update_workspace_bytes", workspace_bytes, need_bytes, workspace_dev,
                                 floats & 3u, "float and int32 arrays must start on a 4-byte boundary", hip_stream))
         return rc;
+    if (opt->num_members) {
+        mrl::set_error("mrl_agent_update: opt->num_members is %u; the wide policy has no bank update (mrl_ppo_update takes members), "
+                       "pass 0", opt->num_members);
+        return MRL_ERR_INVALID;
+    }
     if (epochs == 0) return MRL_OK;
     mrl::AgentUpdateArgs args{};
     args.policy = *policy, args.opt = *opt, args.record = *record, args.cfg = *cfg;

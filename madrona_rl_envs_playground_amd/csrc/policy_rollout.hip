@@ -52,11 +52,18 @@ __device__ __forceinline__ void mlp_forward(const float *__restrict__ p, const f
     }
 }
 
-template <int D, int A, int MODE>
+// MEMBERS: a bank of K policies on one batch of N = K W worlds.  Member blockIdx.z owns worlds
+// [z W, (z + 1) W) and its parameters lie z P floats behind a.params: an address that is still the same in every lane, so the
+// weights still arrive through scalar loads.  Everything behind these four lines is the plain body on the world's number in the
+// batch of N.  The MEMBERS = false instance, which every plain rollout launches, reads neither blockIdx.z nor member_worlds.
+template <int D, int A, int MODE, bool MEMBERS>
 __global__ void __launch_bounds__(kActThreads) mrl_policy_act(PolicyActArgs a)
 {
-    const uint32_t w = blockIdx.x * kActThreads + threadIdx.x;
-    if (w >= a.num_worlds) return;
+    const uint32_t local = blockIdx.x * kActThreads + threadIdx.x;
+    if (local >= (MEMBERS ? a.member_worlds : a.num_worlds)) return;
+    const uint32_t w = MEMBERS ? blockIdx.z * a.member_worlds + local : local;
+    const float *__restrict__ params =
+        MEMBERS ? a.params + (size_t)blockIdx.z * (mlp_net_params(D, kH, 1) + mlp_net_params(D, kH, A)) : a.params;
     float x[D];
     if constexpr (MODE == MRL_OBS_BALANCE) {
         // Seat 0's int32 row.  Rows lie 28 bytes apart, so nothing wider than a dword is aligned: every lane reads its own
@@ -83,7 +90,7 @@ __global__ void __launch_bounds__(kActThreads) mrl_policy_act(PolicyActArgs a)
     }
     if (blockIdx.y == 0) {  // critic, and everything that is copied
         float v[1];
-        mlp_forward<D, 1>(a.params, x, v);
+        mlp_forward<D, 1>(params, x, v);
         if (D % 2) {
             float *__restrict__ row = a.obs_row + (size_t)w * D;
 #pragma unroll
@@ -101,7 +108,7 @@ __global__ void __launch_bounds__(kActThreads) mrl_policy_act(PolicyActArgs a)
         return;
     }
     float l[A];
-    mlp_forward<D, A>(a.params + mlp_net_params(D, kH, 1), x, l);
+    mlp_forward<D, A>(params + mlp_net_params(D, kH, 1), x, l);
     int action;
     float logprob;
     categorical_sample<A>(l, policy_hash(a.seed, a.step, w, 0), a.flags & MRL_POLICY_GREEDY, action, logprob);
@@ -112,18 +119,29 @@ __global__ void __launch_bounds__(kActThreads) mrl_policy_act(PolicyActArgs a)
     if constexpr (MODE == MRL_OBS_BALANCE) a.partner_action[w] = (int32_t)scale(policy_hash(a.seed, a.step, w, 1), A);
 }
 
+template <bool MEMBERS>
+static void launch_policy_act_shape(const mrl_mlp_policy &policy, const PolicyActArgs &args, const dim3 &grid, hipStream_t stream)
+{
+    if (policy.obs_mode == MRL_OBS_BALANCE)
+        hipLaunchKernelGGL((mrl_policy_act<7, 4, MRL_OBS_BALANCE, MEMBERS>), grid, dim3(kActThreads), 0, stream, args);
+    else if (policy.obs_mode == MRL_OBS_ACROBOT_GYM)
+        hipLaunchKernelGGL((mrl_policy_act<6, 3, MRL_OBS_ACROBOT_GYM, MEMBERS>), grid, dim3(kActThreads), 0, stream, args);
+    else if (policy.num_actions == 3)
+        hipLaunchKernelGGL((mrl_policy_act<4, 3, MRL_OBS_RAW, MEMBERS>), grid, dim3(kActThreads), 0, stream, args);
+    else
+        hipLaunchKernelGGL((mrl_policy_act<4, 2, MRL_OBS_RAW, MEMBERS>), grid, dim3(kActThreads), 0, stream, args);
+    MRL_HIP(hipGetLastError());
+}
+
 void launch_policy_act(const mrl_mlp_policy &policy, const PolicyActArgs &args, hipStream_t stream)
 {
-    const dim3 grid((args.num_worlds + kActThreads - 1) / kActThreads, args.action_row ? 2 : 1);
-    if (policy.obs_mode == MRL_OBS_BALANCE)
-        hipLaunchKernelGGL((mrl_policy_act<7, 4, MRL_OBS_BALANCE>), grid, dim3(kActThreads), 0, stream, args);
-    else if (policy.obs_mode == MRL_OBS_ACROBOT_GYM)
-        hipLaunchKernelGGL((mrl_policy_act<6, 3, MRL_OBS_ACROBOT_GYM>), grid, dim3(kActThreads), 0, stream, args);
-    else if (policy.num_actions == 3)
-        hipLaunchKernelGGL((mrl_policy_act<4, 3, MRL_OBS_RAW>), grid, dim3(kActThreads), 0, stream, args);
-    else
-        hipLaunchKernelGGL((mrl_policy_act<4, 2, MRL_OBS_RAW>), grid, dim3(kActThreads), 0, stream, args);
-    MRL_HIP(hipGetLastError());
+    const uint32_t nets = args.action_row ? 2 : 1;
+    if (policy.num_members) {  // (validated: num_worlds is num_members times member_worlds)
+        const dim3 grid((args.member_worlds + kActThreads - 1) / kActThreads, nets, policy.num_members);
+        launch_policy_act_shape<true>(policy, args, grid, stream);
+    } else {
+        launch_policy_act_shape<false>(policy, args, dim3((args.num_worlds + kActThreads - 1) / kActThreads, nets), stream);
+    }
 }
 
 // scripts/cartpole_train_torch.py:247-256 with a lane per world: every load and store is one row, coalesced over w.

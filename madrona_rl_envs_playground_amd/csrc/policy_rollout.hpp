@@ -33,9 +33,12 @@ struct PolicyActArgs {
     uint32_t flags;            // MRL_POLICY_GREEDY
     const int32_t *obs_i32;    // the beam only: OBSERVATION[0], (N, 7) int32
     int32_t *partner_action;   // the beam only: ACTION[1], (N, 1), written by every launch that draws
+    uint32_t member_worlds;    // a bank only (policy.num_members != 0): W = N / num_members, the worlds of one member
 };
 
-// one launch; the policy's shape has been validated (obs_dim / num_actions / obs_mode one of the four supported)
+// one launch; the policy's shape has been validated (obs_dim / num_actions / obs_mode one of the four supported).  With
+// policy.num_members = K != 0 the launch is (ceil(W / 64), nets, K): member z acts for worlds [z W, (z + 1) W) under the
+// parameters z P floats behind args.params.
 void launch_policy_act(const mrl_mlp_policy &policy, const PolicyActArgs &args, hipStream_t stream);
 
 void launch_gae(const float *rewards, const float *values, const float *dones, const float *next_value, const float *next_done,

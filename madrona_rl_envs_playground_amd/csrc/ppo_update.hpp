@@ -1,5 +1,6 @@
 // The update phase of PPO on the device (C ABI: mrl_ppo_update, mrl_ppo_workspace_bytes in include/mrl_envs.h).
-// The kernels live in ppo_update.hip; capi_ppo.hip validates the arguments and calls launch_ppo_update.  DESIGN.md section 13.
+// The kernels live in ppo_update_kernels.hpp, compiled into ppo_update.hip (one policy) and ppo_update_bank.hip (the members of a
+// bank); capi_ppo.hip validates the arguments and calls launch_ppo_update.  DESIGN.md sections 13 and 26.
 #pragma once
 
 #include "adam_step.hpp"
@@ -33,9 +34,16 @@ inline PpoWorkspace ppo_workspace(uint64_t num_params, uint32_t minibatch_size, 
     return w;
 }
 
-// K rows enqueued on `stream`; every argument has been validated (capi_ppo.hip, mrl_ppo_update).
+// K rows enqueued on `stream`; every argument has been validated (capi_ppo.hip, mrl_ppo_update).  With opt.num_members = M != 0
+// every row steps M members in the same three launches (blockIdx.z): opt's arrays are the first of M dense rows, indices
+// (M, K, B), stats (M, K, 8), grads (M, K, P), and workspace M slices of ppo_workspace(...).total floats.
 void launch_ppo_update(const mrl_mlp_policy &shape, const mrl_ppo_optimizer &opt, const mrl_ppo_batch &batch,
                        const int32_t *indices, uint32_t num_minibatches, uint32_t minibatch_size, const mrl_ppo_config &cfg,
                        float *workspace, float *stats, float *grads, hipStream_t stream);
+
+// what launch_ppo_update hands a call with opt.num_members != 0 to (ppo_update_bank.hip)
+void launch_ppo_update_members(const mrl_mlp_policy &shape, const mrl_ppo_optimizer &opt, const mrl_ppo_batch &batch,
+                               const int32_t *indices, uint32_t num_minibatches, uint32_t minibatch_size, const mrl_ppo_config &cfg,
+                               float *workspace, float *stats, float *grads, hipStream_t stream);
 
 }  // namespace mrl

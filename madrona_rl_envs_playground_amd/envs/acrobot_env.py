@@ -75,6 +75,13 @@ class AcrobotMadronaTorch(_AcrobotBase):
             raise ValueError(f"this environment observes {self.observation!r}, the policy {policy.observation!r}")
         return self.sim.rollout_policy(policy, num_steps, seed=seed, first_step=first_step, out=out, greedy=greedy)
 
+    def rollout_bank(self, bank, num_steps, seed=0, first_step=0, out=None, greedy=False):
+        """``rollout`` for the K members of ``bank`` (``simulators.MlpPolicyBank``) on this environment's N = K W worlds, member k
+        on worlds ``[k W, (k + 1) W)`` (``sim.rollout_policy_bank``, extension).  Returns a ``Rollout``."""
+        if bank.observation != self.observation:
+            raise ValueError(f"this environment observes {self.observation!r}, the bank {bank.observation!r}")
+        return self.sim.rollout_policy_bank(bank, num_steps, seed=seed, first_step=first_step, out=out, greedy=greedy)
+
 
 class AcrobotMadronaNumpy(_AcrobotBase):
     def step(self, actions):

@@ -68,6 +68,13 @@ class BalanceGym:
             raise ValueError(f"this environment observes 'beam', the policy {policy.observation!r}")
         return self.sim.sim.rollout_policy(policy, num_steps, seed=seed, first_step=first_step, out=out, greedy=greedy)
 
+    def rollout_bank(self, bank, num_steps, seed=0, first_step=0, out=None, greedy=False):
+        """``rollout`` for the K members of ``bank`` (``simulators.MlpPolicyBank``) on this environment's N = K W worlds, member k
+        on worlds ``[k W, (k + 1) W)`` (``sim.rollout_policy_bank``, extension).  Returns a ``Rollout``."""
+        if bank.observation != "beam":
+            raise ValueError(f"this environment observes 'beam', the bank {bank.observation!r}")
+        return self.sim.sim.rollout_policy_bank(bank, num_steps, seed=seed, first_step=first_step, out=out, greedy=greedy)
+
     def episode_totals(self):
         """``BalanceMadronaTorch.episode_totals`` of the inner environment."""
         return self.sim.episode_totals()

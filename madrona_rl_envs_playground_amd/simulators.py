@@ -41,8 +41,9 @@ from ._episode_stats import EpisodeStats, RecordsEpisodeStatistics, totals_of  #
 from ._bank import (BEAM_TIME, BankResample, CNN_RESAMPLE_MODES, CnnResample, CrossPlayResult, _PolicyBank,  # noqa: F401
                     _bank_resample, _bank_rollout_buffers, _bank_workspace, _check_bank_rollout, _cross_play_counted,
                     _cross_play_pairs, _cross_play_result, resample_twin)
-from ._ppo import (MlpAgent, MlpPolicy, PpoOptimizer, PpoResult, Rollout, _AdamState, _PolicyRollout, _aliased, _critic_then_actor,  # noqa: F401
-                   _layer_shapes, _mlp, _run_update, gae, minibatch_indices, ppo_update)
+from ._ppo import (MlpAgent, MlpPolicy, MlpPolicyBank, PpoBankOptimizer, PpoOptimizer, PpoResult, Rollout, _AdamState,  # noqa: F401
+                   _PolicyRollout, _aliased, _critic_then_actor, _layer_shapes, _mlp, _ppo_structs, _run_update, gae,
+                   member_minibatch_indices, minibatch_indices, ppo_update, ppo_update_bank)
 from ._wide import (AgentRecord, WideAgent, WideOptimizer, WidePolicy, WidePolicyBank, _WIDE_TYPES, _cross_play_wide,  # noqa: F401
                     _wide_bank_workspace, _wide_mlp, _wide_seats, agent_act, agent_act_bank, agent_bank_workspace_bytes,
                     agent_credit, agent_update, gae_active, wide_resample)
@@ -71,7 +72,7 @@ class madrona:  # noqa: N801  (mirrors `<module>.madrona.ExecMode`)
 
 class _Simulator(_PolicyRollout, _MappoRollouts):
     """Shared handle management for the six games, and through the two mixins the rollouts under a network: ``rollout_policy``
-    (``_ppo``), ``rollout_cnn``, ``rollout_cnn_bank``, ``rollout_mlpbase`` and ``rollout_mlpbase_bank`` (``_mappo``)."""
+    and ``rollout_policy_bank`` (``_ppo``), ``rollout_cnn``, ``rollout_cnn_bank``, ``rollout_mlpbase`` and ``rollout_mlpbase_bank`` (``_mappo``)."""
 
     _SLOTS = {}
     _game = None  # a game class names its game: what the layers below test in place of the class, so a subclass passes
