@@ -284,9 +284,9 @@ __device__ __forceinline__ uint32_t interact(const StepParams &p, int32_t need, 
 // one-hot (6), idle pot onions/tomatoes, soup onions/tomatoes, remaining time, ready, dish,
 // onion, tomato, urgency (sim.cpp:79-120,151-164; terrain bytes :642-645).  `o` is the object on
 // the cell, `h` what the player standing there holds (kItemNone if nobody).  Straight-line selects.
-__device__ __forceinline__ uint4 cell_tail(const StepParams &p, uint32_t terr, uint32_t o, uint32_t h, uint32_t urgent)
+// `need`: the cooking time of o's recipe (a caller that has looked it up for the pot's tick hands it in)
+__device__ __forceinline__ uint4 cell_tail_need(int32_t need, uint32_t terr, uint32_t o, uint32_t h, uint32_t urgent)
 {
-    const int32_t need = (int32_t)lookup16(p.times_w, recipe_of(o));
     const uint32_t oname = o & 0xFF, on = (o >> 8) & 0xFF, tom = (o >> 16) & 0xFF;
     const int32_t tick = (int8_t)(o >> 24);
     const uint32_t hname = h & 0xFF;
@@ -312,6 +312,10 @@ __device__ __forceinline__ uint4 cell_tail(const StepParams &p, uint32_t terr, u
     t.w = dish | (onion << 8) | (tomato << 16) | ((urgent ? 1u : 0u) << 24);
     return t;
 }
+__device__ __forceinline__ uint4 cell_tail(const StepParams &p, uint32_t terr, uint32_t o, uint32_t h, uint32_t urgent)
+{
+    return cell_tail_need((int32_t)lookup16(p.times_w, recipe_of(o)), terr, o, h, urgent);
+}
 
 // The transition of a whole group at once: lane = (world wl of the group, player q), lane = wl*P + q
 // (sim.cpp:199-438).  `posori` = pos | orientation << 8 and `held` are the lane's own player in
@@ -326,7 +330,10 @@ __device__ __forceinline__ uint4 cell_tail(const StepParams &p, uint32_t terr, u
 //                 in a world and nobody in it moves (sim.cpp:383-426).
 // Inactive lanes (beyond the group's players) run along with harmless values.  Returns the
 // reward of the lane's WORLD (summed over its players) through reward_world.
-template <int kP>
+// kLean (the full-group path of the specialised single step): the same rounds as a counted loop,
+// the count known before the first round -- hipcc turns the `r > 0 && ballot` / break form into some thirty scalar
+// instructions of loop control around one executed round.
+template <int kP, bool kLean = false>
 __device__ __forceinline__ void transition_lanes(const StepParams &p, const uint8_t *s_terrain, uint32_t *obj_w, uint32_t *s_x,
                                                  uint32_t *s_sum, uint32_t *s_blk, uint32_t P, uint32_t lane, bool active, uint32_t wl,
                                                  uint32_t q, uint32_t a, uint32_t &posori, uint32_t &held, int32_t &reward_world)
@@ -355,17 +362,32 @@ __device__ __forceinline__ void transition_lanes(const StepParams &p, const uint
     constexpr uint32_t kRounds = kP == 2 ? 2u : 4u;  // at most four players face one cell
     // one copy of the interaction code for all rounds (rounds after the first are rare and the launch is sensitive to
     // the size of its straight-line code: DESIGN.md 4.1)
+    if constexpr (kLean) {
+        static_assert(kP == 2, "two players: a second round iff some lane has rank 1");
+        const uint32_t rounds = __builtin_amdgcn_ballot_w64(rank != 0u) != 0ull ? 2u : 1u;  // wave-uniform, known before the first round
 #pragma clang loop unroll(disable)
-    for (uint32_t r = 0; r < kRounds; r++) {
-        const bool todo = inter && rank == r;
-        if (r > 0 && __ballot(todo) == 0ull) break;
-        if (todo) {
-            uint32_t there = touches ? *cell : kItemNone;
-            const int32_t need = (int32_t)lookup16(p.times_w, recipe_of(there));
-            held = interact(p, need, value, terr, held, there, mine);
-            if (touches) *cell = there;
+        for (uint32_t r = 0; r < rounds; r++) {
+            if (inter && rank == r) {
+                uint32_t there = touches ? *cell : kItemNone;
+                const int32_t need = (int32_t)lookup16(p.times_w, recipe_of(there));
+                held = interact(p, need, value, terr, held, there, mine);
+                if (touches) *cell = there;
+            }
+            wave_lds_sync();
         }
-        wave_lds_sync();
+    } else {
+#pragma clang loop unroll(disable)
+        for (uint32_t r = 0; r < kRounds; r++) {
+            const bool todo = inter && rank == r;
+            if (r > 0 && __ballot(todo) == 0ull) break;
+            if (todo) {
+                uint32_t there = touches ? *cell : kItemNone;
+                const int32_t need = (int32_t)lookup16(p.times_w, recipe_of(there));
+                held = interact(p, need, value, terr, held, there, mine);
+                if (touches) *cell = there;
+            }
+            wave_lds_sync();
+        }
     }
     // movement proposal; orientation := action unless STAY / INTERACT
     uint32_t prop = pos, pori = ori;
@@ -606,16 +628,73 @@ __device__ __forceinline__ void patch_direct(const StepParams &p, uint32_t *s_ob
     }
 }
 
+// patch_direct<kP, false> for a FULL group of a specialised kernel, with what a full group makes
+// unnecessary taken out of the executed path:
+//   - every table entry is a cell of the group: no `i < ncells`, and a free entry (0) reads cell 0 without a select;
+//   - the pot's tick is straight-line: one unsigned compare for 0 <= tick < need, the ticked word (tick < 255, so +1 never
+//     carries out of the byte) written by every lane, the lanes that are no pot into `dead`, a word of the wave's LDS that
+//     nobody reads -- a select of the address instead of three nested exec-mask regions around one ds_write;
+//   - the cooking time looked up for the tick serves cell_tail as well (it only matters for a soup, whose recipe the tick
+//     does not change);
+//   - the urgency flag does not travel through LDS: `urgent_worlds` is the ballot of the player lanes whose world is in its
+//     last 40 steps, so world l's flag is bit l * P.
+template <int kP>
+__device__ __forceinline__ void patch_direct_full(const StepParams &p, uint32_t *s_obj, uint32_t *dead, const HoldTab &hold, uint8_t *tile,
+                                                  uint32_t P, bool active, uint32_t wl, uint32_t q, uint32_t posori, uint32_t held,
+                                                  unsigned long long urgent_worlds)
+{
+    const uint32_t C = p.C, F = p.F, shift = 5 * P;
+    const uint32_t plane = __umul24(C, F);
+    const uint32_t ori = (posori >> 8) & 0xFFu;
+#pragma unroll
+    for (int k = 0; k < kHoldPerLane; k++) {
+        if (k > 0 && (uint32_t)k * kWave >= p.hold_entries) break;  // wave-uniform
+        const uint32_t e = hold.e[k];
+        const uint32_t i = (e >> 16) & 0x3FFFu;
+        const bool holder = ((e >> 30) & 1u) != 0u, is_pot = (int32_t)e < 0;
+        uint32_t o = s_obj[i];
+        const int32_t need = (int32_t)lookup16(p.times_w, recipe_of(o));
+        const bool ticks = is_pot && (o & 0xFFu) == O_SOUP && (uint32_t)(int32_t)(int8_t)(o >> 24) < (uint32_t)need;
+        o += ticks ? 0x01000000u : 0u;
+        *(is_pot ? s_obj + i : dead) = o;
+        // everything a row needs is worked out by all lanes in straight-line code (selects between the player's and the
+        // holder's values); only the stores sit in exec-mask regions: one for the tails, one for all the player bytes
+        const bool player = k == 0 && active;
+        const uint32_t l = player ? wl : __umulhi(i, p.inv_c);
+        const uint32_t urgent = (uint32_t)(urgent_worlds >> __umul24(l, P)) & 1u;
+        const uint32_t terr = player ? (uint32_t)T_AIR : (is_pot ? (uint32_t)T_POT : (uint32_t)T_COUNTER);
+        const uint4 t = cell_tail_need(need, terr, player ? (uint32_t)kItemNone : o, player ? held : (uint32_t)kItemNone, urgent);
+        uint8_t *row0 = tile + (player ? __umul24(wl, p.block_bytes) + __umul24(posori & 0xFFu, F) : (e & 0xFFFFu));
+        if (player || (holder && (o & 0xFFu) != O_NONE)) {
+#pragma unroll
+            for (uint32_t v = 0; v < (kP > 0 ? (uint32_t)kP : P); v++) lds_store_tail_even(row0 + __umul24(v, plane) + shift, t);
+        }
+        // (the player bytes lie in front of the tail in a row: the order of the two regions' stores does not matter)
+        if (player) {
+#pragma unroll
+            for (uint32_t v = 0; v < (kP > 0 ? (uint32_t)kP : P); v++) {
+                uint8_t *row = row0 + __umul24(v, plane);
+                const uint32_t rel = q == v ? 0u : (q < v ? q + 1u : q);
+                row[rel] = 1;
+                row[P + 4 * rel + ori] = 1;
+            }
+        }
+    }
+}
+
 // kRestore (persistent rollouts, where the tile outlives the step): after the stream-out the patched rows are
 // put back to their static content, so the next step again only touches what is dynamic then; s_prev remembers
 // each world's urgency flag as the tile has it.
-template <int kP, bool kRestore, bool kPlain = false>
+// kLean (a full group of the specialised single step; p.direct, not kRestore): patch_direct_full, and the urgency flags
+// arrive as the ballot `urgent_worlds` (see there) -- s_flags is written only on the way into the urgency pass.
+template <int kP, bool kRestore, bool kPlain = false, bool kLean = false>
 __device__ __forceinline__ void observe_patch(const StepParams &p, const uint8_t *s_terrain, uint32_t *s_obj,
-                                              const uint32_t *s_pl, const uint8_t *s_cur, const uint8_t *s_flags, uint8_t *s_prev,
+                                              const uint32_t *s_pl, const uint8_t *s_cur, uint8_t *s_flags, uint8_t *s_prev,
                                               const uint16_t *s_list, uint32_t ndyn, uint8_t *tile, uint32_t P, uint32_t w0, uint32_t l0,
                                               uint32_t nl, uint32_t lane, const HoldTab &hold, bool active, uint32_t wl, uint32_t q,
-                                              uint32_t posori, uint32_t held)
+                                              uint32_t posori, uint32_t held, uint32_t *dead = nullptr, unsigned long long urgent_worlds = 0ull)
 {
+    static_assert(!(kLean && kRestore), "the lean path is the single step's");
     // worlds l0 .. l0 + nl - 1 of the group (the single step encodes a group in two halves so that the first
     // half's stores are on their way while the second is still being patched); `tile` is the whole group's
     const uint32_t C = p.C, F = p.F, shift = 5 * P;
@@ -624,8 +703,11 @@ __device__ __forceinline__ void observe_patch(const StepParams &p, const uint8_t
 #endif
     const uint32_t plane = __umul24(C, F);  // bytes of one viewer's rows
     // lane = dynamic cell; its 16-byte tail is worked out once and dropped into the rows of all P viewers
-    if (p.direct) patch_direct<kP, false>(p, s_obj, s_flags, hold, tile, P, nl, active, wl, q, posori, held);
-    for (uint32_t j = lane; j < (p.direct ? 0u : ndyn); j += kWave) {
+    if constexpr (kLean)
+        patch_direct_full<kP>(p, s_obj, dead, hold, tile, P, active, wl, q, posori, held, urgent_worlds);
+    else if (p.direct)
+        patch_direct<kP, false>(p, s_obj, s_flags, hold, tile, P, nl, active, wl, q, posori, held);
+    for (uint32_t j = lane; j < ((kLean || p.direct) ? 0u : ndyn); j += kWave) {
         const uint32_t i = s_list[j];
         const uint32_t l = __umulhi(i, p.inv_c), c = i - __umul24(l, C);
         const uint32_t terr = s_terrain[c];
@@ -655,7 +737,17 @@ __device__ __forceinline__ void observe_patch(const StepParams &p, const uint8_t
     }
     // urgency channel (sim.cpp:79-83) of the rows that were not patched: only where a world's flag differs from
     // what the tile holds (a fresh tile holds 0); the flag changes twice per episode
-    {
+    if constexpr (kLean) {
+        if (__builtin_expect(urgent_worlds != 0ull, 0)) {
+            if (active && q == 0) s_flags[wl] = (uint8_t)((urgent_worlds >> lane) & 1ull);
+            wave_lds_sync();
+            const uint32_t nrows = (l0 + nl) * p.rows;
+            for (uint32_t r = l0 * p.rows + lane; r < nrows; r += kWave) {
+                const uint32_t f = s_flags[__umulhi(r, p.inv_rows)];
+                if (f != 0u) tile[__umul24(r, F) + F - 1u] = (uint8_t)f;
+            }
+        }
+    } else {
         const uint32_t mine = lane < nl ? s_flags[l0 + lane] : 0u;
         const uint32_t had = (kRestore && lane < nl) ? s_prev[l0 + lane] : 0u;
         if (__builtin_expect(__ballot(mine != had) != 0ull, 0)) {
@@ -776,6 +868,19 @@ __device__ __forceinline__ void terrain_deliver(const StepParams &p, const TerrP
         if (r.off[k] != 0u && r.off[k] < limit) tile[r.off[k]] = 1;
     }
 }
+// ... of a FULL group: every entry lies inside the tile, and an entry of 0 (no terrain byte, or past the table's end) stores
+// a 0 into byte 0 of the tile, which is zero at this point (the zero fill is in front, the patches come behind) -- a
+// v_min instead of two compares, an AND of their masks and an exec-mask region around each of the stores
+__device__ __forceinline__ void terrain_deliver_full(const StepParams &p, const TerrPos &r, uint8_t *tile)
+{
+#pragma unroll
+    for (int k = 0; k < kTerrPosPerLane; k++) {
+        if ((uint32_t)k * kWave >= p.terr_entries) break;
+        uint32_t one;  // (as asm: hipcc turns min(x, 1) back into a compare, a wait state and a select)
+        asm("v_min_u32 %0, 1, %1" : "=v"(one) : "v"(r.off[k]));
+        tile[r.off[k]] = (uint8_t)one;
+    }
+}
 __device__ __forceinline__ void tile_zero(const StepParams &p, uint32_t lane, uint8_t *tile, uint32_t nw)
 {
     const uint32_t nchunks = (nw * p.block_bytes + 31u) >> 4;  // covers any start misalignment
@@ -815,14 +920,23 @@ __device__ __forceinline__ uint32_t load_action(const StepParams &p, size_t at)
 // `block`: the workgroup's index among those of THIS simulator (blockIdx.x, except under mrl_overcooked_step_many, where
 // one grid covers the workgroups of several simulators)
 // kSparse: only the cell words that differ from what the launch loaded are written back (store_state below)
-template <bool kInit, int kP, bool kPlain = false, bool kSparse = false>
-__device__ __forceinline__ void step_body(const StepParams &p, const uint32_t block)
+// kFull > 0 (mrl_overcooked_step_fixed only): the wave's group is known to hold all kFull = wpw
+// worlds, so every per-lane bound is a constant and the guards that only a ragged or empty group needs are not compiled
+// into this path; such a group takes the kFull = 0 instantiation, today's guarded code, laid out behind it.
+// `at`: the caller has worked out the wave's index in its workgroup and its first world (to choose between the two paths)
+// and hands them in, so that neither is derived twice.
+struct WaveAt {
+    uint32_t wib, w0;
+};
+template <bool kInit, int kP, bool kPlain = false, bool kSparse = false, int kFull = 0>
+__device__ __forceinline__ void step_body(const StepParams &p, const uint32_t block, const WaveAt *at = nullptr)
 {
+    static_assert(kFull == 0 || (!kInit && kP == 2), "the full-group path is the specialised two-player single step's");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & (kWave - 1);
     // wave-uniform values are forced into SGPRs so the address math around them is scalar
-    const uint32_t wib = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    const uint32_t wib = at ? at->wib : (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
 
     STAMP(0);
     STAMP_REALTIME(13);
@@ -854,8 +968,8 @@ __device__ __forceinline__ void step_body(const StepParams &p, const uint32_t bl
     // cache lines of the state arrays and of the observation slab; keep them in one L2).
     const uint32_t per_xcd = p.per_xcd;
     const uint32_t logical_block = (block & 7u) * per_xcd + (block >> 3);
-    const uint32_t w0 = p.share ? logical_block : (logical_block * kWavesPerBlock + wib) * p.wpw;
-    const uint32_t nw = w0 < p.num_worlds ? min(p.wpw, p.num_worlds - w0) : 0u;
+    const uint32_t w0 = at ? at->w0 : (p.share ? logical_block : (logical_block * kWavesPerBlock + wib) * p.wpw);
+    const uint32_t nw = kFull > 0 ? (uint32_t)kFull : (w0 < p.num_worlds ? min(p.wpw, p.num_worlds - w0) : 0u);
 
     // per-wave LDS: the group's state in the same dense order as in HBM
     uint8_t *wbase = smem + kConstBytes + wib * p.lds_wave_stride;
@@ -900,9 +1014,25 @@ __device__ __forceinline__ void step_body(const StepParams &p, const uint32_t bl
         const __amdgpu_buffer_rsrc_t r_pl = __builtin_amdgcn_make_buffer_rsrc(p.players + (size_t)w0 * P, 0, (int)(nplayers * 8u), 0x00020000);
         const auto pl_raw = __builtin_amdgcn_raw_buffer_load_b64(r_pl, (int)(lane * 8u), 0, 0);
         const uint2 pl_reg = make_uint2(pl_raw[0], pl_raw[1]);
-        const size_t a_at = (size_t)(active ? q : 0u) * N + min(w0 + wl, N - 1u);
-        const uint32_t a_raw = load_action(p, a_at);
-        t_loaded = p.timestep[min(w0 + wl, N - 1u)];
+        size_t a_at;
+        uint32_t a_raw;
+        if constexpr (kFull > 0) {
+            // bounds-checked like the state, from the group's first world on: lane (wl, q) reads entry q * N + wl, the range ends
+            // behind the last player's kFull worlds, and so do the clocks' -- no clamp of the world, no select of the player, no
+            // 64-bit address per lane; the lanes beyond the group's players read another entry of the array or a zero
+            const bool wide = p.actions64 != nullptr;
+            const uint32_t sh = wide ? 3u : 2u;
+            const char *a_base = (wide ? reinterpret_cast<const char *>(p.actions64) : reinterpret_cast<const char *>(p.actions)) + ((size_t)w0 << sh);
+            const __amdgpu_buffer_rsrc_t r_act = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(a_base), 0, (int)(((P - 1u) * N + (uint32_t)kFull) << sh), 0x00020000);
+            a_raw = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r_act, (int)((q * N + wl) << sh), 0, 0);
+            a_at = (size_t)q * N + w0 + wl;
+            const __amdgpu_buffer_rsrc_t r_t = __builtin_amdgcn_make_buffer_rsrc(p.timestep + w0, 0, kFull * 4, 0x00020000);
+            t_loaded = __builtin_amdgcn_raw_buffer_load_b32(r_t, (int)(wl * 4u), 0, 0);
+        } else {
+            a_at = (size_t)(active ? q : 0u) * N + min(w0 + wl, N - 1u);
+            a_raw = load_action(p, a_at);
+            t_loaded = p.timestep[min(w0 + wl, N - 1u)];
+        }
         if (p.patch) terrain_request(p, lane, tpos);
         if (p.direct) hold_request(p, lane, hold);  // (the specialised kernels: no scalar load to wait for, see take_hot_args)
         // while the loads are in flight: the cell -> player map starts empty, the tile of the single-pass encode zeroed
@@ -916,14 +1046,23 @@ __device__ __forceinline__ void step_body(const StepParams &p, const uint32_t bl
 #pragma unroll
         for (int k = 0; k < kBatch; k++) {
             const uint32_t i = lane + k * kWave;
-            if (i < ncells) s_obj[i] = cell_reg[k];
+            // (a full group: a round that ends inside the cells or the player records behind them -- which the direct encode
+            // never reads -- is written by all lanes, the ones past the cells with the zeros their loads returned)
+            const bool whole_round = kFull > 0 && (uint32_t)k * kWave < ncells && ((uint32_t)k + 1u) * kWave * 4u <= p.off_x;
+            if (whole_round || i < ncells) s_obj[i] = cell_reg[k];
         }
         for (uint32_t i = lane + kBatch * kWave; i < ncells; i += kWave) s_obj[i] = g_obj[i];
         posori = pl_reg.x & 0xFFFFu;
         held = pl_reg.y;
-        act = (active && a_raw <= A_INTERACT) ? a_raw : (uint32_t)A_STAY;  // outside the enum = outside the contract
+        if constexpr (kFull > 0) {
+            // (the lanes beyond the group's players: their record loaded as zeros, whatever action they read moves nobody --
+            // `active` guards the interaction, the encode and every store)
+            act = a_raw <= A_INTERACT ? a_raw : (uint32_t)A_STAY;
+        } else {
+            act = (active && a_raw <= A_INTERACT) ? a_raw : (uint32_t)A_STAY;  // outside the enum = outside the contract
+        }
         if (p.actions64 && active && (!p.share || wib == 0)) p.action_mirror[a_at] = (int32_t)a_raw;
-        if (!active) {
+        if (kFull == 0 && !active) {
             posori = 0;
             held = kItemNone;
         }
@@ -937,9 +1076,15 @@ __device__ __forceinline__ void step_body(const StepParams &p, const uint32_t bl
         else if (p.whole)
             tile_zero(p, lane, s_tile, nw);
     }
-    if (p.patch) terrain_deliver(p, tpos, s_tile + patch_mis, nw);
+    if constexpr (kFull > 0)
+        terrain_deliver_full(p, tpos, s_tile + patch_mis);
+    else if (p.patch)
+        terrain_deliver(p, tpos, s_tile + patch_mis, nw);
     if (private_consts) {
-        if (lane * 4u < p.C) reinterpret_cast<uint32_t *>(const_cast<uint8_t *>(s_terrain))[lane] = const_word[0];
+        // (a full group of the direct encode: the list of dynamic cells behind the terrain copy is never read, so where it
+        // takes a whole wave's words every lane writes -- the lanes past the terrain the zeros their load returned)
+        const bool all_lanes = kFull > 0 && p.direct && p.off_tail - p.off_terr >= kWave * 4u;
+        if (all_lanes || lane * 4u < p.C) reinterpret_cast<uint32_t *>(const_cast<uint8_t *>(s_terrain))[lane] = const_word[0];
         STAMP(7);
         wave_lds_sync();
     } else {
@@ -958,7 +1103,7 @@ __device__ __forceinline__ void step_body(const StepParams &p, const uint32_t bl
     bool reset_now = kInit;
     if (!kInit) {
         if (!ABLATED(4)) {
-            transition_lanes<kP>(p, s_terrain, s_obj + wl * C, s_x, s_sum, s_blk, P, lane, active, wl, q, act, posori, held, reward_world);
+            transition_lanes<kP, (kFull > 0)>(p, s_terrain, s_obj + wl * C, s_x, s_sum, s_blk, P, lane, active, wl, q, act, posori, held, reward_world);
             if (!p.direct) tick_pots(p, s_pots, s_obj, nw, lane);  // direct: the holder lanes of the encode tick the pots
         }
         // horizon (sim.cpp:485-489)
@@ -966,7 +1111,8 @@ __device__ __forceinline__ void step_body(const StepParams &p, const uint32_t bl
         reset_now = (int64_t)t >= p.horizon;
     }
     // reset (sim.cpp:441-482): rare, and then usually every world of the group at once
-    if (__builtin_expect(__ballot(active && reset_now) != 0ull, 0)) {
+    // (the builtin in the full-group path: __ballot's int predicate costs a select and a compare to get the mask back)
+    if (__builtin_expect((kFull > 0 ? __builtin_amdgcn_ballot_w64(active && reset_now) : __ballot(active && reset_now)) != 0ull, 0)) {
         if (reset_now) {
             t = 0;
             posori = (private_consts ? (p.starts_w >> (8u * (q & 3u))) & 0xFFu : (uint32_t)s_start[active ? q : 0u]) | (A_NORTH << 8);
@@ -985,8 +1131,12 @@ __device__ __forceinline__ void step_body(const StepParams &p, const uint32_t bl
             reinterpret_cast<uint2 *>(s_pl)[lane] = make_uint2(posori, held);
             s_cur[wl * C + (posori & 0xFFu)] = (uint8_t)q;
         }
-        if (q == 0) s_flags[wl] = (p.horizon - (int64_t)t < 40) ? 1 : 0;
+        if (kFull == 0 && q == 0) s_flags[wl] = (p.horizon - (int64_t)t < 40) ? 1 : 0;
     }
+    // a full group: the flags stay in registers -- bit (wl * P + q) for the players of a world in its last 40 steps -- and
+    // the encode takes world l's from bit l * P: no LDS write, hand-off and read between the transition and the patch
+    // (horizon - t < 40 as horizon - 40 < t: the left side is wave-uniform)
+    const unsigned long long urgent_worlds = kFull > 0 ? __builtin_amdgcn_ballot_w64(active && p.horizon - 40 < (int64_t)t) : 0ull;
     wave_lds_sync();
 
     // ---------------- store: LDS -> HBM slab, rewards, flags ----------------
@@ -1039,8 +1189,11 @@ __device__ __forceinline__ void step_body(const StepParams &p, const uint32_t bl
             // patched, measured slower: 8.6 vs 8.25 us.)
             const uint32_t ndyn = p.direct ? 0u : find_dynamic(p, s_obj, s_cur, s_list, 0, nw, lane);
             STAMP(4);
-            observe_patch<kP, false, kPlain>(p, s_terrain, s_obj, s_pl, s_cur, s_flags, nullptr, s_list, ndyn, s_tile + patch_mis, P, w0, 0, nw, lane, hold, active,
-                                     wl, q, posori, held);
+            // (`dead`, the words of a full group's straight-line pot tick that nobody reads: the player records in LDS, which the
+            // direct encode leaves alone -- sixteen words of them, a lane its own of a bank)
+            static_assert(kFull == 0 || kFull >= 4, "sixteen dead words need four worlds' player records");
+            observe_patch<kP, false, kPlain, (kFull > 0)>(p, s_terrain, s_obj, s_pl, s_cur, s_flags, nullptr, s_list, ndyn, s_tile + patch_mis, P, w0, 0, nw, lane,
+                                                          hold, active, wl, q, posori, held, s_pl + (lane & 15u), urgent_worlds);
             STAMP(5);
         } else
             observe_whole<kPlain>(p, s_terrain, s_obj, s_pl, s_cur, s_flags, s_tile, P, w0, nw, lane, true);
@@ -1540,7 +1693,19 @@ __global__ void __launch_bounds__(kBlock) mrl_overcooked_step_fixed(MRL_HOT_ARGS
 {
     StepParams q = fixed_params<kC, kW, kWidth, kPots, kHold>(p);
     take_hot_args<kI64>(q, MRL_HOT_PASS);
+#ifdef MRL_NO_FULL_GROUP  // variant build for measurements: every group through the guarded code
     step_body<false, 2, kPlain, kSparse>(q, blockIdx.x);
+#else
+    // a wave whose group holds all kW worlds -- every wave but a batch's last one or two -- takes the path compiled without the
+    // guards of a ragged group (step_body, kFull); the wave's first world as step_body derives it
+    WaveAt at;
+    at.wib = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    at.w0 = (((blockIdx.x & 7u) * hot_per_xcd + (blockIdx.x >> 3)) * kWavesPerBlock + at.wib) * kW;
+    if (__builtin_expect(at.w0 + kW <= hot_num_worlds, 1))
+        step_body<false, 2, kPlain, kSparse, kW>(q, blockIdx.x, &at);
+    else
+        step_body<false, 2, kPlain, kSparse>(q, blockIdx.x, &at);
+#endif
 }
 
 // ---------------------------------------------------------------------------------------------
