@@ -190,6 +190,24 @@ typedef struct mrl_hanabi_config {
  *   continues with the agent's own hand, which is hidden from the observer (the reference
  *   declares 658 entries whatever the configuration; its wrappers read [:obs_size],
  *   envs/hanabi_env.py:92-104).
+ *   ACTION: only the entry of the agent to move is read, and EVERY int32 there has a defined result, the same in every code
+ *   variant and on every step path; for every move of the table it is the reference's own (sim.cpp:596-792 applies the
+ *   integer without a legality check):
+ *     0..4 discard and 5..9 play that slot, 10..10+K-1 the colour hint, 10+K..10+K+R-1 the rank hint at the partner, whether
+ *     or not ACTION_MASK allows the move (a hint that touches no card still costs its token; a discard at a full pool adds
+ *     a token above the maximum, and the rows then shift as described in csrc/hanabi.hip, followed up to 5 tokens above it);
+ *     any other value -- at or past 10 + K + R, or negative -- is read as uint32 and acts as the in-table rank hint
+ *     10 + K + (u mod R) at the PARTNER, with u = uint32(action) - 10 - K; the remainder is exact over all of uint32.
+ *     This is a DEPARTURE from the reference, whose rank-hint branch (sim.cpp:742-754) takes the same rank u % R but the
+ *     player (actor + 1 + u / R) % 2, i.e. the mover's OWN hand when u / R is odd (actions 20..24 of the full game):
+ *     following it there slowed the full game's step by 0.8 %, so the partner it is, everywhere.
+ *     ACTION_MASK rows 10+K+R..19 stay zero.
+ *   One move is outside the contract: a hint while the pool holds zero tokens.  The pool wraps to 255 as the reference's
+ *   uint8_t does (the reference then writes far past its rows); what that world's rows hold from then on is unspecified,
+ *   but every write stays inside that world's own record and rows, and no other world is affected.
+ *   Slots at or past the hand size cannot occur: the player to move always holds five cards in the two-player game.
+ *   int64 actions: mrl_step_with_actions_i64 is not available for Hanabi (MRL_ERR_INVALID, nothing changes); a caller
+ *   narrows to int32 itself, and the low 32 bits it keeps are the action as above.
  *   GAME uint8 (N, 176): the raw per-world game record (tests only; layout in
  *   csrc/hanabi.hip); RESET_COUNT uint32 (1): worlds that finished in the last completed step (written by
  *   phase 2); SHARD_COUNT uint32 (1): worlds that finished in the last mrl_step_phase1 -- what the ranks of a

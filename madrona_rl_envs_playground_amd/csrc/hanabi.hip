@@ -5,9 +5,15 @@
 // actionSystem :596-792, observationSystem :794-810, checkDone :812-850) and
 // rng.hpp:5-40, including the behaviours listed in oracle/hanabi_oracle.c
 // (plausibility bits test bit <player-loop-index>; only the player to move is
-// re-encoded; hint legality scans all five slots; no legality check).  Actions
-// outside an agent's legal-move mask are outside the contract (the reference
-// then overruns its own encoders); here they are memory-safe but unspecified.
+// re-encoded; hint legality scans all five slots; no legality check).  Every
+// int32 action has a defined result, the same in every code variant
+// (include/mrl_envs.h, ACTION): an in-table move the reference's, whether or not
+// the legal-move mask allows it; a value past the move table acts as the rank hint
+// 10 + K + u % R at the PARTNER, u = uint32(action) - 10 - K.  That is a departure
+// from the reference, which hints the mover's own hand when u / R is odd
+// (sim.cpp:748-754): following it cost the headline step 0.8 %.
+// A hint at zero tokens wraps the pool to 255 as the reference's uint8_t does; what
+// the encoders then write is unspecified but stays inside the world's own rows.
 //
 // Mapping.  A world's step is serial (one deck, one player to move), but its
 // output is 1.5 KB of 0/1 bytes.  So the work is split inside one wave:
@@ -665,7 +671,7 @@ __device__ void apply_action(const HanabiParams &p, uint8_t *rec, uint32_t uid)
     uid -= 2 * kHand;
     // A hint leaves R_LM_MOVE as it was: sim.cpp:696-792 never set lastmove.move, so the last-action section
     // goes on encoding the world's last card move (MV_INVALID after a reset), gated by that move type (:158-290).
-    uint8_t *ph = rec + R_HAND + HAND_BYTES * (actor ^ 1u);  // one partner: target_offset is always 1
+    uint8_t *ph = rec + R_HAND + HAND_BYTES * (actor ^ 1u);  // always the partner, also past the move table (a departure: see the top)
     uint32_t *plaus = plaus_of(ph);
     const uint32_t psize = min((uint32_t)ph[H_SIZE], (uint32_t)kHand);
     rec[R_INFO]--;
@@ -686,7 +692,7 @@ __device__ void apply_action(const HanabiParams &p, uint8_t *rec, uint32_t uid)
             }
         }
     } else {
-        const uint32_t rk = (uid - K) % R;
+        const uint32_t rk = (uid - K) % R;  // exact for every uint32: an action past the table is the rank hint (uid - K) mod R
         rec[R_LM_RANK] = (uint8_t)rk;
         for (uint32_t i = 0; i < R; i++) hint |= 1u << (i * R + rk);
         for (uint32_t i = 0; i < psize; i++) {
@@ -792,7 +798,9 @@ __device__ void apply_action_full(uint8_t *rec, uint32_t uid)
     const uint32_t u = uid - 2 * kHand;
     const bool by_color = u < 5u;
     const uint32_t u_rank = u - 5u;
-    const uint32_t val = by_color ? u : u_rank - ((u_rank * 205u) >> 10) * kRk;  // (uid - K) % R
+    // (uid - K) % R, exact over all of uint32 (__umulhi(x, 0xCCCCCCCD) >> 2 is x / 5 for every x): 0..4, so the shift below and
+    // the bytes packed into rec32[23] stay in range for any action, and all variants agree on what an out-of-table action is
+    const uint32_t val = by_color ? u : u_rank - (__umulhi(u_rank, 0xCCCCCCCDu) >> 2) * kRk;
     const uint32_t hint = by_color ? 0x1Fu << (kRk * val) : 0x108421u << val;     // the 5 cards of a colour / of a rank
     const uint32_t psize = min(hbyte(q, H_SIZE), (uint32_t)kHand);
     uint32_t reveal = 0, newly = 0;
@@ -1020,7 +1028,7 @@ __device__ __forceinline__ MovedFull move_world_full(const HanabiParams &p, uint
     const uint32_t u = uid - 2 * kHand;
     const bool by_color = u < 5u;
     const uint32_t u_rank = u - 5u;
-    const uint32_t val_rank = u_rank - ((u_rank * 205u) >> 10) * kRk;  // (uid - K) % R
+    const uint32_t val_rank = u_rank - (__umulhi(u_rank, 0xCCCCCCCDu) >> 2) * kRk;  // (uid - K) % R, exact over uint32 (see apply_action_full): 0..4
     const uint32_t val = by_color ? u : val_rank;
     const uint32_t hint_color = 0x1Fu << ((kRk * val) & 31u), hint_rank = 0x108421u << (val & 31u);  // the 5 cards of a colour / of a rank
     const uint32_t hint = by_color ? hint_color : hint_rank;

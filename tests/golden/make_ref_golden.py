@@ -13,7 +13,12 @@ layout has one, the others play at random); per step every viewer's observation 
 channels as bytes), reward and done, and the internal state after the last step.  overcooked_ref_limits.npz holds three
 streams side by side: recipe times 127 and 128 (the int8_t tick reaches 127 / wraps past it) and recipe values 300.
 
-    python tests/golden/make_ref_golden.py [kitchens | hanabi NAME...]
+Hanabi, moves the mask forbids (hanabi_ref_illegal_<config>.npz): tests/hanabi_illegal_cases.py:walk -- empty hints,
+discards at a full pool, actions past the move table and negative ones beside legal moves -- with the actions (int32), each
+world's class and what the reference computed per step.  The walk reads the game records, which the reference does not
+export: the oracle plays along to supply them, and the recording stops if the two ever differ.
+
+    python tests/golden/make_ref_golden.py [kitchens | hanabi NAME... | hanabi_illegal [NAME...]]
 """
 import os
 import sys
@@ -72,7 +77,47 @@ def kitchens():
             print(f"    {prefix or 'stream'}: {cov}")
 
 
+ILLEGAL_WORLDS = 40  # x hanabi_illegal_cases.STEPS steps: every class at least 100 times in every configuration (asserted)
+
+
+def hanabi_illegal(names):
+    import hanabi_illegal_cases as ic
+    from oracle.oracle import HanabiOracle
+    for name in names or ic.WALK_CONFIGS:
+        cfg, n = ic.config_of(name), ILLEGAL_WORLDS
+        no, ns = hanabi_spec.observation_size(cfg), hanabi_spec.state_size(cfg)
+        r, orc = ref.RefHanabi(cfg, n), HanabiOracle(cfg, n)
+        first = dict(obs=r.obs[..., :no].copy(), state=r.state[..., :ns].copy(), mask=r.mask.copy(), active=r.active.copy())
+        rec = {k: [] for k in ("actions", "classes", "obs", "state", "mask", "active", "reward", "done")}
+        total = {}
+        for t, before, a, cls in ic.walk(orc, cfg, reference_contract=True):
+            r.step(a)
+            assert np.array_equal(r.mask, orc.mask) and np.array_equal(r.state[..., :ns], orc.state[..., :ns]), f"{name}: oracle != reference at step {t}"
+            rec["actions"].append(a.astype(np.int32))
+            rec["classes"].append(cls.astype(np.int8))
+            rec["obs"].append(r.obs[..., :no].copy())
+            rec["state"].append(r.state[..., :ns].copy())
+            for k in ("mask", "active", "reward", "done"):
+                rec[k].append(getattr(r, k).copy())
+            for k, v in ic.count_classes(cfg, before, a, cls, r.done).items():
+                total[k] = total.get(k, 0) + v
+        assert min(total[k] for k in ("A", "B", "E")) >= 100 and total["E at the mover's own hand"] and total["E at the partner"], total
+        out = os.path.join(HERE, f"hanabi_ref_illegal_{name}.npz")
+        np.savez_compressed(out, actions=np.stack(rec["actions"]), classes=np.stack(rec["classes"]), mask=np.stack(rec["mask"]).astype(np.int8),
+                            active=np.stack(rec["active"]).astype(np.int8), reward=np.stack(rec["reward"]),
+                            done=np.stack(rec["done"]).astype(np.int8), first_mask=first["mask"].astype(np.int8),
+                            first_active=first["active"].astype(np.int8), episodes=np.int64(r.episodes),
+                            **packed("obs", np.stack(rec["obs"])), **packed("state", np.stack(rec["state"])),
+                            **packed("first_obs", first["obs"]), **packed("first_state", first["state"]))
+        print(f"{out}: {n} worlds x {ic.STEPS} steps, {r.episodes} episodes, {os.path.getsize(out) / 1024:.0f} KiB; {total}")
+
+
 def main():
+    if sys.argv[1:2] == ["hanabi_illegal"]:
+        hanabi_illegal(sys.argv[2:])
+        return
+    if not sys.argv[1:]:
+        hanabi_illegal([])
     if sys.argv[1:2] != ["hanabi"]:
         kitchens()
     if sys.argv[1:] == ["kitchens"]:

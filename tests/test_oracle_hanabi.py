@@ -12,6 +12,7 @@ from conftest import load_golden
 from madrona_rl_envs_playground_amd import hanabi_spec
 
 import hanabi_configs
+import hanabi_illegal_cases
 
 CONFIGS = {
     "full": dict(colors=5, ranks=5, players=2, max_information_tokens=8, max_life_tokens=3),
@@ -367,6 +368,37 @@ def test_oracle_reproduces_compiled_reference_fixture(name, oracle_lib):
         for k in ("mask", "active", "reward", "done"):
             assert np.array_equal(getattr(orc, k), z[k][t]), f"{k}, step {t}"
     assert orc.episodes == int(z["episodes"])
+
+
+@pytest.mark.parametrize("name", hanabi_illegal_cases.WALK_CONFIGS)
+def test_oracle_reproduces_compiled_reference_fixture_of_moves_the_mask_forbids(name, oracle_lib):
+    """tests/golden/hanabi_ref_illegal_<cfg>.npz: the compiled reference on hanabi_illegal_cases.walk -- empty hints (A),
+    discards at a full pool (B), actions past the move table and negative ones (E), at least 100 of each and both targets of
+    E -- so that the oracle stays pinned on them where oracle/_ref is not built.  The recorded actions are the walk's own."""
+    ic = hanabi_illegal_cases
+    z = load_golden(f"hanabi_ref_illegal_{name}.npz")
+    cfg = ic.config_of(name)
+    no, ns = hanabi_spec.observation_size(cfg), hanabi_spec.state_size(cfg)
+    steps, _, n = z["actions"].shape
+    assert z["actions"].dtype == np.int32 and steps == ic.STEPS
+    orc = oracle_lib.HanabiOracle(cfg, n)
+    assert np.array_equal(orc.obs[..., :no], z["first_obs"]) and np.array_equal(orc.state[..., :ns], z["first_state"])
+    assert np.array_equal(orc.mask, z["first_mask"]) and np.array_equal(orc.active, z["first_active"])
+    w = np.arange(n)
+    seen = {c: 0 for c in (ic.A, ic.B, ic.E)}
+    targets = set()
+    for t, rec, acts, cls in ic.walk(orc, cfg, reference_contract=True):
+        assert np.array_equal(acts, z["actions"][t]) and np.array_equal(cls, z["classes"][t]), f"the walk's actions, step {t}"
+        assert np.array_equal(orc.obs[..., :no], z["obs"][t]), f"obs, step {t}"
+        assert np.array_equal(orc.state[..., :ns], z["state"][t]), f"state, step {t}"
+        for k in ("mask", "active", "reward", "done"):
+            assert np.array_equal(getattr(orc, k), z[k][t]), f"{k}, step {t}"
+        for c in seen:
+            seen[c] += int((cls == c).sum())
+        mover = rec[:, 83].astype(np.int64)
+        targets |= set(ic.reference_hint(cfg, acts[mover, w])[1][cls == ic.E].tolist())
+    assert orc.episodes == int(z["episodes"])
+    assert min(seen.values()) >= 100 and targets == {0, 1}, (seen, targets)
 
 
 # ---------------------------------------------------------------------------------------------

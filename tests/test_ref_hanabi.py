@@ -18,6 +18,7 @@ from oracle import ref
 from oracle.oracle import HanabiOracle
 
 import hanabi_configs
+import hanabi_illegal_cases
 from hanabi_configs import choose, count_paths, reachable, tokens_after_move  # noqa: F401  (choose: test_gpu_hanabi.py imports it from here)
 
 CONFIGS = {
@@ -95,6 +96,37 @@ def test_oracle_matches_compiled_reference(name, n, steps):
         assert guard_bytes >= 1, "the full configuration's documented one-byte overflow never happened"
     else:
         assert name in CONFIGS or guard_bytes == 0, f"{name}: {guard_bytes} guard bytes written"
+
+
+@pytest.mark.parametrize("name", hanabi_illegal_cases.WALK_CONFIGS)
+def test_oracle_matches_compiled_reference_on_moves_the_mask_forbids(name):
+    """hanabi_illegal_cases.walk -- empty hints (A), discards at a full pool (B) and actions past the move table or negative
+    (E: the reference's rank hint, at the mover's own hand when u / R is odd) side by side with legal moves -- on four times
+    the device tests' worlds: every tensor of both agents after every step, in both reference instances, and the guard bytes,
+    which may hold only the documented overflow of `max + e` tokens.  (The reference exports no game record; its hands and
+    their knowledge are compared through the state rows.)"""
+    ic = hanabi_illegal_cases
+    cfg, n = ic.config_of(name), 4 * ic.WORLDS
+    ob_n, st_n = hanabi_spec.observation_size(cfg), hanabi_spec.state_size(cfg)
+    orc = HanabiOracle(cfg, n)
+    refs = [ref.RefHanabi(cfg, n, fill=0x00, construct=False), ref.RefHanabi(cfg, n, fill=0xA5, construct=True)]
+    _assert_same(name, -1, orc, refs, ob_n, st_n)
+    total, guard_bytes = {}, 0
+    for t, rec, acts, cls in ic.walk(orc, cfg, reference_contract=True):
+        assert np.array_equal(refs[0].mask, refs[1].mask)
+        for r in refs:
+            r.step(acts)
+        _assert_same(name, t, orc, refs, ob_n, st_n)
+        info_after = ic.tokens_after(cfg, rec, acts)
+        assert (info_after <= cfg["max_information_tokens"] + ic.MAX_EXCESS).all() and (info_after >= 0).all()
+        for r in refs:
+            guard_bytes += _check_guards(name, cfg, ob_n, st_n, r, info_after)
+        for k, v in ic.count_classes(cfg, rec, acts, cls, orc.done).items():
+            total[k] = total.get(k, 0) + v
+    print(f"hanabi {name}: {n * ic.STEPS} world-steps with illegal moves compared bit-exact, {guard_bytes} overflow guard bytes; {total}")
+    for k in ("A", "B", "E", "E at the partner", "E at the mover's own hand", "episodes ended"):
+        assert total[k] >= 100, f"{name}: {k} occurred {total[k]} times"
+    assert name != "full" or guard_bytes >= 1
 
 
 def test_episode_index_wraps():
