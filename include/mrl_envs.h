@@ -1170,6 +1170,73 @@ int mrl_mappo_mlp_update(const mrl_mlpbase_policy *policy, const mrl_mappo_optim
                          uint64_t workspace_bytes, float *stats_dev_or_null /* (K, 8) */, float *grads_dev_or_null /* (K, P) */,
                          int gpu_id, void *hip_stream);
 
+/* The RECURRENT MLPBase actor-critic (r_actor_critic.py with use_recurrent_policy, utils/rnn.py with recurrent_N 1): a GRU of width
+ * 64 and a LayerNorm between the base and the head of both nets, through mrl_mlpbase_act, mrl_rollout_mlpbase, mrl_mappo_mlp_update
+ * and the two size queries -- no new entry
+ * point and no changed struct, MRL_ABI_VERSION stays 4.  DESIGN.md section 27.
+ *   Network, per net, with x = the base's output row (the last hidden layer's LayerNorm output), h = the incoming state, m = 0 where
+ *     DONE[world] is set at the time of the act and 1 otherwise (main_player.py:254; multiplying by m at every step equals the
+ *     segment logic of rnn.py:41-69):
+ *         h_in = h * m;  gi = W_ih x + b_ih;  gh = W_hh h_in + b_hh   (192 each, gate order r, z, n)
+ *         r = sigmoid(gi_r + gh_r);  z = sigmoid(gi_z + gh_z);  n = tanh(gi_n + r * gh_n);  h' = (1 - z) * n + z * h_in
+ *         head input = LayerNorm64(h');  new state = h' (before the LayerNorm, as rnn.py:79-80 returns it)
+ *     sigmoid(x) = 1 / (1 + expf(-x)), tanh(x) = tanhf(x), one device function each.  Every 64 x 64 product follows the Linear
+ *     rule above, the LayerNorm the LayerNorm rule; no float atomics; the same inputs give the same bits.
+ *   Flat tensor: per net base.* exactly as above (fc_h included), then rnn.rnn.weight_ih_l0 (192, 64), weight_hh_l0 (192, 64),
+ *     bias_ih_l0 (192), bias_hh_l0 (192), rnn.norm.weight (64), bias (64), then the head: 25 088 floats more per net.
+ *     mrl_mlpbase_policy_num_params(7, 64, layer_N + MRL_MLPBASE_GRU_LAYERS, 4) is 77 537 for layer_N 2 and 68 961 for 1.
+ *   MRL_MLPBASE_RECURRENT is a bit of mrl_mlpbase_policy.flags ONLY, never of the act's `flags` argument.  When it is set the
+ *     `policy` pointer is read as an mrl_mlpbase_gru_policy and a non-NULL `record` pointer as an mrl_mlpbase_gru_record.
+ *     h_actor and h_critic (N, P, 64) are the running states, read and written by the acts.
+ *   Act: behind the base the workgroup of a (tile, net) loads its 32 state rows, applies m, runs the GRU, its LayerNorm and the
+ *     head, and writes h' back.  Seats outside `players` keep every byte of their state rows.  With a record and row % L == 0
+ *     (L = chunk_length) the INCOMING state, before the mask, goes to h0_*[row / L] ((T / L, N, P, 64)).  The closing
+ *     MRL_MLPBASE_VALUE_ONLY act reads the critic's state and writes NOTHING to either state tensor (main_player.py:298 discards
+ *     it: the next rollout's row 0 sees the same observation again).  Without a record only the actor runs and only h_actor
+ *     advances.
+ *   mrl_rollout_mlpbase: for k < T the recurrent act at row k, then the ordinary step; then the closing value-only act.  Two
+ *     rollouts of T with the states carried equal one of 2 T, bit for bit (T a multiple of L).
+ *   Refusals (MRL_ERR_INVALID, nothing changed) beyond mrl_mlpbase_act's: a NULL h_actor or h_critic, or one off a 4-byte boundary;
+ *     with a record chunk_length == 0, num_steps % chunk_length != 0, a NULL h0_actor or h0_critic or one off a 4-byte boundary.
+ *     The banks (mrl_mlpbase_act_bank, mrl_rollout_mlpbase_bank, mrl_mappo_mlp_bank_update) refuse the bit.
+ *   mrl_mappo_mlp_update with the bit in policy->flags: `policy` is read as an mrl_mlpbase_gru_policy (its state pointers are not
+ *     read) and `batch` as an mrl_mappo_mlp_gru_batch.  The unit of a minibatch is a CHUNK: c = (j N + n) P + p, j < T / L, covers
+ *     samples s_i = ((j L + i) N + n) P + p, i < L.  `indices` is (K, Bc) chunk ids and minibatch_size = Bc; every mean of the
+ *     losses runs over the Bc L samples of the row.  Per chunk the forward pass starts from h0_*[j, n, p] and applies m_i = 1 -
+ *     dones[j L + i, n, p] at every step (dones[k] is what the act at row k saw), so on unchanged parameters the recomputed
+ *     log-probs and values are the record's bit for bit.  Launch plan: one launch that writes every row's sample numbers and the
+ *     ValueNorm recurrence up front (with MRL_MAPPO_VALUENORM), then three per row as for mrl_mappo_mlp_update.  The gradient
+ *     kernel takes 32 chunks per tile: a forward sweep that keeps the incoming state of every step in the workgroup's own slice of
+ *     the workspace, then a sweep from i = L - 1 down to 0 that recomputes the step's forward pass, runs the loss head for the
+ *     step's 32 samples and goes back through the head, the LayerNorm, the GRU (dh carried to step i - 1 through z, W_hh and the
+ *     mask) and the base.  A workgroup's partial vector is summed in ONE order: tiles ascending, within a tile the steps
+ *     descending, within a step the samples ascending.  No float atomics, no wait on another workgroup; the same inputs give the
+ *     same bits; a call of K rows gives the bits of K calls of one row; fc_h stays untouched.  1 <= L <=
+ *     MRL_MLPBASE_GRU_MAX_CHUNK = 16.  mrl_mappo_mlp_workspace_bytes(7, 64, layer_N + MRL_MLPBASE_GRU_LAYERS, 4, Bc, K, &bytes)
+ *     sizes the workspace, for any L up to the maximum.
+ *     Refusals beyond mrl_mappo_mlp_update's: a NULL h0_actor, h0_critic or dones, or one off a 4-byte boundary; chunk_length 0
+ *     or above the maximum; num_worlds * num_seats * (T / L) chunks inconsistent with base.size, i.e. base.size not a multiple of
+ *     chunk_length * num_worlds * num_seats; minibatch_size above the batch's number of chunks.  mrl_mappo_mlp_bank_update
+ *     refuses the bit.
+ *   Not built: banks, population training and cross-play of recurrent policies, recurrent_N > 1, use_naive_recurrent_policy. */
+enum { MRL_MLPBASE_RECURRENT = 16 };      /* bit of mrl_mlpbase_policy.flags */
+enum { MRL_MLPBASE_GRU_LAYERS = 0x100 };  /* added to layer_N in the two size queries: the recurrent shape */
+enum { MRL_MLPBASE_GRU_MAX_CHUNK = 16 };  /* the longest chunk mrl_mappo_mlp_update back-propagates through */
+typedef struct mrl_mlpbase_gru_policy {
+    mrl_mlpbase_policy base;    /* base.flags has MRL_MLPBASE_RECURRENT; base.params_dev is the recurrent flat tensor */
+    float *h_actor, *h_critic;  /* (N, P, 64) */
+} mrl_mlpbase_gru_policy;
+typedef struct mrl_mlpbase_gru_record {
+    mrl_mlpbase_record base;
+    float *h0_actor, *h0_critic; /* (T / L, N, P, 64) */
+    uint32_t chunk_length;       /* L */
+} mrl_mlpbase_gru_record;
+typedef struct mrl_mappo_mlp_gru_batch {
+    mrl_mappo_mlp_batch base;                    /* base.obs .. base.advantages as for mrl_mappo_mlp_update; base.size = S = T N P */
+    const float *h0_actor, *h0_critic, *dones;   /* the record's: (T / L, N, P, 64) twice and (T, N, P) */
+    uint32_t chunk_length, num_worlds, num_seats; /* L, N, P */
+} mrl_mappo_mlp_gru_batch;
+
 /* A population of partners on the balance beam: a BANK of K MLPBase policies of one shape and a policy per (world, seat) cell,
  * the counterpart of mrl_cnn_bank and its calls above for the world where cross-play between trained conventions is the thing
  * measured (the reference's --seed_skip and --pop_size).  No reference counterpart as calls.  DESIGN.md section 20.

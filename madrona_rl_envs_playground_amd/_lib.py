@@ -38,6 +38,9 @@ CNN_BANK_MAX_POLICIES = 256  # the rows an mrl_cnn_bank may hold
 CNN_RESAMPLE_ROBIN, CNN_RESAMPLE_RANDOM = 1, 2  # MRL_CNN_RESAMPLE_*
 MLPBASE_VALUE_ONLY = 4  # MRL_MLPBASE_VALUE_ONLY: flag of mrl_mlpbase_act beside POLICY_GREEDY
 MLPBASE_HIDDEN, MLPBASE_OBS, MLPBASE_ACTIONS = 64, 7, 4  # the one shape mrl_mlpbase_act runs (layer_N 1 or 2)
+MLPBASE_RECURRENT = 16  # MRL_MLPBASE_RECURRENT: bit of mrl_mlpbase_policy.flags; the policy is then an mrl_mlpbase_gru_policy
+MLPBASE_GRU_LAYERS = 0x100  # MRL_MLPBASE_GRU_LAYERS: added to layer_N in the size queries for the recurrent shape
+MLPBASE_GRU_MAX_CHUNK = 16  # MRL_MLPBASE_GRU_MAX_CHUNK: the longest chunk mrl_mappo_mlp_update back-propagates through
 MAPPO_VALUENORM, MAPPO_HUBER_LOSS, MAPPO_CLIPPED_VALUE_LOSS, MAPPO_MAX_GRAD_NORM = 1, 2, 4, 8  # MRL_MAPPO_*
 MAPPO_STATS = ("value_loss", "critic_grad_norm", "policy_loss", "dist_entropy", "actor_grad_norm", "ratio", "clipfrac", "reserved")
 PPO_STATS = ("pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac", "total_norm", "loss")  # a stats row
@@ -197,6 +200,30 @@ class WideBankDesc(ctypes.Structure):  # mrl_wide_bank
 
 class MappoMlpBatch(ctypes.Structure):  # mrl_mappo_mlp_batch
     _fields_ = MappoBatch._fields_
+
+
+# The recurrent MLPBase's structs BEGIN WITH the plain ones and travel through the same entry points (``base_ref``).
+class MlpBaseGruPolicyDesc(ctypes.Structure):  # mrl_mlpbase_gru_policy
+    _extends_ = MlpBasePolicyDesc
+    _fields_ = [("base", MlpBasePolicyDesc), ("h_actor", ctypes.c_void_p), ("h_critic", ctypes.c_void_p)]
+
+
+class MlpBaseGruRecordDesc(ctypes.Structure):  # mrl_mlpbase_gru_record
+    _extends_ = MlpBaseRecordDesc
+    _fields_ = [("base", MlpBaseRecordDesc), ("h0_actor", ctypes.c_void_p), ("h0_critic", ctypes.c_void_p), ("chunk_length", ctypes.c_uint32)]
+
+
+class MappoMlpGruBatch(ctypes.Structure):  # mrl_mappo_mlp_gru_batch
+    _extends_ = MappoMlpBatch
+    _fields_ = [("base", MappoMlpBatch), ("h0_actor", ctypes.c_void_p), ("h0_critic", ctypes.c_void_p), ("dones", ctypes.c_void_p),
+                ("chunk_length", ctypes.c_uint32), ("num_worlds", ctypes.c_uint32), ("num_seats", ctypes.c_uint32)]
+
+
+def base_ref(struct):
+    """``ctypes.byref(struct)`` as the entry points' argument types take it: an extended struct (``_extends_``) goes as a pointer
+    to the plain struct it begins with, which is how the library reads it until it has seen the flag"""
+    base = getattr(type(struct), "_extends_", None)
+    return ctypes.byref(struct) if base is None else ctypes.cast(ctypes.pointer(struct), ctypes.POINTER(base))
 
 
 class MrlError(RuntimeError):

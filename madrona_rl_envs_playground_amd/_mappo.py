@@ -13,8 +13,8 @@ import torch
 from . import _lib
 from ._bank import _PolicyBank, _bank_resample, _bank_rollout_buffers, _bank_workspace, _check_bank_rollout
 from ._device import _check_ids, _require_tensors, _seat_mask, _stream_ptr
-from ._mappo_nets import CnnActorCritic, MlpBaseActorCritic
-from ._ppo import Rollout, _AdamState, _aliased, _run_update, gae
+from ._mappo_nets import CnnActorCritic, MlpBaseActorCritic, MlpBaseGruActorCritic
+from ._ppo import Rollout, _AdamState, _aliased, _run_update, gae, minibatch_indices
 
 
 class _FlatPolicy:
@@ -215,6 +215,152 @@ class MlpBaseRecord(_MappoRecord):
         self.obs = z((t + 1, n, p, _lib.MLPBASE_OBS), torch.int32)
 
 
+class MlpBaseGruState:
+    """The running GRU states of a ``MlpBaseGruPolicy`` on a simulator of ``num_worlds`` worlds: ``actor`` and ``critic``, float32
+    (N, P, 64), zero at first; the acts read and write them in place (``mrl_mlpbase_gru_policy``'s ``h_actor`` / ``h_critic``).
+    ``zero_(worlds=None)`` zeroes every row, or the rows of ``worlds`` (indices or a bool mask over N) -- after ``n_reset``, say;
+    episodes that end on their own need nothing: the act masks the state where DONE is set."""
+
+    def __init__(self, num_worlds, device, num_players=2, hidden=_lib.MLPBASE_HIDDEN):
+        shape = (int(num_worlds), int(num_players), int(hidden))
+        self.num_worlds, self.num_players = shape[0], shape[1]
+        self.actor = torch.zeros(shape, dtype=torch.float32, device=torch.device(device))
+        self.critic = torch.zeros_like(self.actor)
+
+    def zero_(self, worlds=None):
+        for h in (self.actor, self.critic):
+            if worlds is None:
+                h.zero_()
+            else:
+                h[worlds] = 0.0
+        return self
+
+    def clone(self):
+        other = MlpBaseGruState(self.num_worlds, self.actor.device, self.num_players, self.actor.shape[2])
+        other.actor.copy_(self.actor)
+        other.critic.copy_(self.critic)
+        return other
+
+
+class MlpBaseGruPolicy(MlpBasePolicy):
+    """The parameters and the running state ``mrl_mlpbase_act`` runs for the RECURRENT actor-critic (``mrl_mlpbase_gru_policy``,
+    ``MRL_MLPBASE_RECURRENT``): ``params`` is the flat tensor of ``parameters_to_vector(MlpBaseGruActorCritic.parameters())`` --
+    per net ``base.*`` as in ``MlpBasePolicy``, then the GRU's four tensors and its LayerNorm, then the head: 77 537 floats for
+    ``layer_N`` 2, 68 961 for 1.  ``module()`` returns a ``MlpBaseGruActorCritic`` over VIEWS of ``params``.
+    ``state(num_worlds)`` makes a zeroed ``MlpBaseGruState`` and BINDS it: ``mlpbase_act``, ``rollout_mlpbase`` and the env's
+    ``act`` / ``rollout``, whose signatures are the plain policy's, run on the bound state ``running`` (``bind(state)`` switches
+    to another one).  EVERY act and rollout of this policy depends on that binding: callers that share one policy -- a trainer
+    and a partner agent, two environments -- must each ``bind`` their own state before each of their calls, or keep a policy
+    object each over the same ``params`` (``MlpBasePolicyAgent`` binds its own state for its call and puts the previous one back).
+    The banks and ``mappo_update_bank`` do not take a recurrent policy."""
+
+    _module_class, _module_name, _shape = MlpBaseGruActorCritic, "an MlpBaseGruActorCritic", ("layer_N",)
+    _desc_flags = _lib.MLPBASE_RECURRENT  # the bit every descriptor of this kind of policy carries, a rollout's included
+
+    def __init__(self, layer_N=2, device="cuda:0"):
+        self.running = None
+        super().__init__(layer_N=layer_N, device=device)
+
+    @property
+    def num_params(self):
+        return int(_lib.lib().mrl_mlpbase_policy_num_params(self.obs_dim, self.hidden, self.layer_N + _lib.MLPBASE_GRU_LAYERS, self.num_actions))
+
+    def state(self, num_worlds):
+        """A zeroed ``MlpBaseGruState`` on the parameters' device, bound as ``running``."""
+        return self.bind(MlpBaseGruState(num_worlds, self.params.device))
+
+    def bind(self, state):
+        if not isinstance(state, MlpBaseGruState):
+            raise ValueError("state must be an MlpBaseGruState")
+        self.running = state
+        return state
+
+    def desc(self):
+        state = self.running
+        if state is None:
+            raise ValueError("a recurrent policy acts on a bound state: call policy.state(num_worlds) or policy.bind(state) first")
+        plain = _lib.MlpBasePolicyDesc(self.params.data_ptr(), self.hidden, self.layer_N, self._desc_flags)
+        return _lib.MlpBaseGruPolicyDesc(plain, state.actor.data_ptr(), state.critic.data_ptr())
+
+    def _act_check(self, worlds, seats, record):
+        """what an act or a rollout of a recurrent policy checks beyond the plain one's: the bound state and the record's kind"""
+        state = self.running
+        if state is None:
+            raise ValueError("a recurrent policy acts on a bound state: call policy.state(num_worlds) or policy.bind(state) first")
+        _require_tensors([("state.actor", state.actor, torch.float32, worlds * seats * self.hidden),
+                          ("state.critic", state.critic, torch.float32, worlds * seats * self.hidden)], self.params.device)
+        if tuple(state.actor.shape) != (worlds, seats, self.hidden) or tuple(state.critic.shape) != (worlds, seats, self.hidden):
+            raise ValueError(f"the bound state must hold ({worlds}, {seats}, {self.hidden}) rows per net")
+        if record is not None and not isinstance(record, MlpBaseGruRecord):
+            raise ValueError("a recurrent policy's record must be an MlpBaseGruRecord")
+
+    # what MappoOptimizer and mappo_update ask of a policy
+    def _mappo_workspace_bytes(self, minibatch_size, num_minibatches, out, members=None):
+        if members is not None:
+            raise ValueError("mappo_update_bank does not take a recurrent policy")
+        return _lib.lib().mrl_mappo_mlp_workspace_bytes(self.obs_dim, self.hidden, self.layer_N + _lib.MLPBASE_GRU_LAYERS, self.num_actions,
+                                                        minibatch_size, num_minibatches, out)
+
+    def _mappo_check(self, record, ring):
+        if not isinstance(record, MlpBaseGruRecord):
+            raise ValueError("record must be an MlpBaseGruRecord")
+        if ring is not None:
+            raise ValueError("an MlpBaseGruPolicy's batch is record.obs: ring must be None")
+
+    def _mappo_batch(self, record, ring, count):
+        """-> ((entry point, None), policy struct, the batch struct's maker, the batch's observations).  ``indices`` are CHUNK ids
+        (``chunk_indices``); the policy struct carries no state: the update starts every chunk from the record's ``h0``."""
+        rows = count + count // max(record.num_steps, 1)
+        cells = record.num_worlds * record.num_players * self.hidden
+        chunks = record.num_steps // record.chunk_length
+        _require_tensors([("record.obs", record.obs, torch.int32, rows * self.obs_dim), ("record.dones", record.dones, torch.float32, count),
+                          ("record.h0_actor", record.h0_actor, torch.float32, chunks * cells),
+                          ("record.h0_critic", record.h0_critic, torch.float32, chunks * cells)], self.params.device)
+        plain = _lib.MlpBasePolicyDesc(self.params.data_ptr(), self.hidden, self.layer_N, _lib.MLPBASE_RECURRENT)
+        shape = _lib.MlpBaseGruPolicyDesc(plain, None, None)
+
+        def batch(*plain_fields):
+            return _lib.MappoMlpGruBatch(_lib.MappoMlpBatch(*plain_fields), record.h0_actor.data_ptr(), record.h0_critic.data_ptr(),
+                                         record.dones.data_ptr(), record.chunk_length, record.num_worlds, record.num_players)
+
+        return (_lib.lib().mrl_mappo_mlp_update, None), shape, batch, record.obs
+
+
+class MlpBaseGruRecord(MlpBaseRecord):
+    """The buffers of a recurrent act or rollout (``mrl_mlpbase_gru_record``): ``MlpBaseRecord``'s and, for chunks of
+    ``chunk_length`` = L steps (the reference's ``data_chunk_length``, default 10; it must divide ``num_steps``), ``h0_actor`` and
+    ``h0_critic`` float32 (T / L, N, P, 64): row j holds the states the act at row j L came in with, before its mask -- where the
+    update's chunk j starts."""
+
+    def __init__(self, num_steps, num_worlds, num_players, device, chunk_length=10, logits=False):
+        self.chunk_length = int(chunk_length)
+        if self.chunk_length < 1 or int(num_steps) % self.chunk_length:
+            raise ValueError(f"chunk_length {chunk_length} must be at least 1 and divide num_steps {num_steps}")
+        super().__init__(num_steps, num_worlds, num_players, device, logits)
+        self.struct = _lib.MlpBaseGruRecordDesc(self.struct, self.h0_actor.data_ptr(), self.h0_critic.data_ptr(), self.chunk_length)
+
+    def _own_buffers(self, z, t, n, p):
+        super()._own_buffers(z, t, n, p)
+        self.h0_actor = z((t // self.chunk_length, n, p, _lib.MLPBASE_HIDDEN))
+        self.h0_critic = z((t // self.chunk_length, n, p, _lib.MLPBASE_HIDDEN))
+
+    @property
+    def num_chunks(self):
+        return self.num_steps // self.chunk_length * self.num_worlds * self.num_players
+
+
+MlpBaseGruPolicy._record_class = MlpBaseGruRecord
+
+
+def chunk_indices(record, num_mini_batch, epochs, generator=None, device="cpu"):
+    """The rows ``mappo_update`` takes for a recurrent policy, (epochs * num_mini_batch, Bc) int32 CHUNK ids on ``device``: every
+    epoch is one permutation of the record's (T / L) N P chunks cut into ``num_mini_batch`` rows, as ``recurrent_generator`` draws
+    it (utils/shared_buffer.py; chunk c = (j N + n) P + p covers rows j L .. j L + L - 1 of world n, seat p)."""
+    if not isinstance(record, MlpBaseGruRecord):
+        raise ValueError("record must be an MlpBaseGruRecord")
+    return minibatch_indices(record.num_chunks, num_mini_batch, epochs, generator, device)
+
+
 class MlpBasePolicyBank(_PolicyBank):
     """K ``MlpBasePolicy`` of one shape in one dense float32 tensor ``params`` (K, num_params) (``mrl_mlpbase_bank``), the
     counterpart of ``CnnPolicyBank`` for the balance beam: row k is exactly what an ``MlpBasePolicy``'s ``params`` is.
@@ -281,6 +427,9 @@ def _call_args(family, sim, policy, players, record):
     if record is not None and (not isinstance(record, family.record) or record.num_worlds != worlds or record.num_players != seats or
                                record.actions.device != p.device):
         raise ValueError(f"record must be {family.record_noun} of {worlds} worlds and {seats} players on cuda:{sim.gpu_id}")
+    own_check = getattr(policy, "_act_check", None)  # a recurrent policy's: its bound state, its kind of record
+    if own_check is not None:
+        own_check(worlds, seats, record)
     return _seat_mask(players, seats), worlds, seats
 
 
@@ -326,7 +475,7 @@ def _act(family, sim, policy, players, record, row, seed, step, greedy, value_on
         scratch = (workspace.data_ptr(), workspace.numel())
     flags = (_lib.POLICY_GREEDY if greedy else 0) | (family.value_only if value_only else 0)
     desc = policy.desc()
-    rc = getattr(sim._L, family.act)(sim._handle, mask, ctypes.byref(desc), ctypes.byref(record.struct) if record is not None else None,
+    rc = getattr(sim._L, family.act)(sim._handle, mask, _lib.base_ref(desc), _lib.base_ref(record.struct) if record is not None else None,
                                      int(row), int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF, flags, *scratch, _stream_ptr(sim.gpu_id))
     if rc:
         _lib.check(rc)
@@ -367,8 +516,9 @@ def _rollout(family, sim, policy, record, obs_ring, players, seed, first_step, g
         raise ValueError(f"{family.rollout[4:]} needs {family.record_noun}")
     ring = _ring_pointer(family, sim, record, obs_ring)
     desc = policy.desc()
-    desc.flags = _lib.POLICY_GREEDY if greedy else 0
-    _lib.check(getattr(sim._L, family.rollout)(sim._handle, mask, ctypes.byref(desc), ctypes.byref(record.struct), *ring,
+    # (a recurrent policy's struct begins with the plain one; the bits a kind of policy always carries are the class's)
+    getattr(desc, "base", desc).flags = getattr(policy, "_desc_flags", 0) | (_lib.POLICY_GREEDY if greedy else 0)
+    _lib.check(getattr(sim._L, family.rollout)(sim._handle, mask, _lib.base_ref(desc), _lib.base_ref(record.struct), *ring,
                                                int(seed) & (2 ** 64 - 1), int(first_step) & 0xFFFFFFFF, _stream_ptr(sim.gpu_id)))
 
 
@@ -510,7 +660,8 @@ class _ActsWithMappoPolicy:
         """``rollout`` and ``rollout_bank`` of either mixin: the buffers, each made when ``None``, then the simulator's ``method``
         -> (record, in a kitchen the ring, under a bank ``ids_record``)"""
         family, device, seats = self._family, self.static_actions.device, getattr(self, self._seats)
-        filled = (family.record._for_rollout(record, num_steps, self.num_envs, seats, device),)
+        record_class = getattr(head[0], "_record_class", family.record)  # (a recurrent policy's record carries the chunks' states)
+        filled = (record_class._for_rollout(record, num_steps, self.num_envs, seats, device),)
         if family.ring:
             if ring is None:
                 ring = torch.empty((int(num_steps) + 1,) + tuple(self.static_world_major_observations.shape), dtype=torch.int8, device=device)
@@ -679,7 +830,10 @@ def mappo_update(policy, optimizer, record, ring, advantages, returns, indices, 
     grads)``: (K, 8) float32, columns ``_lib.MAPPO_STATS``, and (K, P) the unclipped gradients, each None unless asked for.
     For an ``MlpBasePolicy`` (the balance beam; ``mrl_mappo_mlp_update``) ``record`` is an ``MlpBaseRecord``, the batch is its
     ``obs`` and ``ring`` must be ``None``.
-    Not built: active masks, PopArt, recurrent policies, ``update_actor=False``, weight decay."""
+    For an ``MlpBaseGruPolicy`` (the recurrent actor-critic) ``record`` is an ``MlpBaseGruRecord`` and ``indices`` (K, Bc) are CHUNK
+    ids (``chunk_indices``): every mean runs over the Bc L samples of the row's chunks, each chunk's forward pass starts from the
+    record's ``h0`` and applies ``1 - record.dones`` at every step, and the gradient goes back through the chunk's L steps.
+    Not built: active masks, PopArt, ``update_actor=False``, weight decay."""
     if not isinstance(policy, (CnnPolicy, MlpBasePolicy)) or not isinstance(optimizer, MappoOptimizer) or optimizer.policy is not policy:
         raise ValueError("policy must be a CnnPolicy or an MlpBasePolicy and optimizer the MappoOptimizer made for it")
     policy._mappo_check(record, ring)  # the record is the policy's kind, and so is the ring
@@ -702,6 +856,6 @@ def mappo_update(policy, optimizer, record, ring, advantages, returns, indices, 
                        advantages.data_ptr(), count)
     cfg = _mappo_config(optimizer, value_norm, clip_param, entropy_coef, value_loss_coef, max_grad_norm, huber_delta, use_huber_loss,
                         use_clipped_value_loss, use_max_grad_norm)
-    return _run_update(entry, (ctypes.byref(shape), ctypes.byref(opt), ctypes.byref(batch)), indices,
+    return _run_update(entry, (_lib.base_ref(shape), ctypes.byref(opt), _lib.base_ref(batch)), indices,
                        (ctypes.byref(cfg), value_norm.state.data_ptr() if value_norm is not None else None), optimizer,
                        len(_lib.MAPPO_STATS), MappoResult, stats, grads)

@@ -184,3 +184,90 @@ class MlpBaseActorCritic(_ActorCritic):
         for head, head_gain in ((self.actor.act.action_out.linear, 0.01), (self.critic.v_out, 1.0)):
             torch.nn.init.orthogonal_(head.weight, gain=head_gain)
             torch.nn.init.constant_(head.bias, 0.0)
+
+
+class _RnnLayer(torch.nn.Module):
+    """train/MAPPO/utils/rnn.py for ``recurrent_N`` 1 and ``use_orthogonal``: ``rnn`` = one ``nn.GRU`` layer with orthogonal weights
+    and zero biases, ``norm`` = LayerNorm.  ``forward(x, h, mask)`` with x (n, hidden), h (n, hidden) and mask (n) or (n, 1) is one
+    step from ``h * mask`` -> (norm(h'), h'); ``chunk(x, h0, masks)`` with x (L, n, hidden) and masks (L, n) runs L such steps,
+    masking at every step, which equals the segment logic of rnn.py:41-69 -> (norm of every step's h' (L, n, hidden), h_L)."""
+
+    def __init__(self, hidden):
+        super().__init__()
+        self.rnn = torch.nn.GRU(hidden, hidden, num_layers=1)
+        for name, param in self.rnn.named_parameters():
+            if "bias" in name:
+                torch.nn.init.constant_(param, 0.0)
+            else:
+                torch.nn.init.orthogonal_(param)
+        self.norm = torch.nn.LayerNorm(hidden)
+
+    def forward(self, x, h, mask):
+        out, h = self.rnn(x.unsqueeze(0), (h * mask.reshape(-1, 1)).unsqueeze(0).contiguous())
+        return self.norm(out.squeeze(0)), h.squeeze(0)
+
+    def chunk(self, x, h, masks):
+        outs = []
+        for i in range(x.shape[0]):
+            out, h = self.rnn(x[i:i + 1], (h * masks[i].reshape(-1, 1)).unsqueeze(0).contiguous())
+            h = h.squeeze(0)
+            outs.append(out)
+        return self.norm(torch.cat(outs, dim=0)), h
+
+
+class _MlpBaseGruActor(torch.nn.Module):
+    """``R_Actor``'s parameters by name for a vector observation with ``use_recurrent_policy``: ``base...``, ``rnn.rnn.weight_ih_l0``,
+    ``weight_hh_l0``, ``bias_ih_l0``, ``bias_hh_l0``, ``rnn.norm``, ``act.action_out.linear``"""
+
+    def __init__(self, obs_dim, hidden, layer_N, num_actions):
+        super().__init__()
+        self.base = _MlpBase(obs_dim, hidden, layer_N)
+        self.rnn = _RnnLayer(hidden)
+        self.act = _ActLayer(hidden, num_actions)
+
+    def forward(self, obs, h, mask):
+        features, h = self.rnn(self.base(obs), h, mask)
+        return self.act.action_out.linear(features), h
+
+    def chunk(self, obs, h0, masks):
+        """obs (L, n, 7), h0 (n, hidden), masks (L, n) -> (logits (L, n, actions), h_L)"""
+        features, h = self.rnn.chunk(self.base(obs), h0, masks)
+        return self.act.action_out.linear(features), h
+
+
+class _MlpBaseGruCritic(torch.nn.Module):
+    """``R_Critic``'s parameters by name with ``use_recurrent_policy``, without PopArt: ``base...``, ``rnn...``, ``v_out``"""
+
+    def __init__(self, obs_dim, hidden, layer_N):
+        super().__init__()
+        self.base = _MlpBase(obs_dim, hidden, layer_N)
+        self.rnn = _RnnLayer(hidden)
+        self.v_out = torch.nn.Linear(hidden, 1)
+
+    def forward(self, state, h, mask):
+        features, h = self.rnn(self.base(state), h, mask)
+        return self.v_out(features), h
+
+    def chunk(self, state, h0, masks):
+        """state (L, n, 7), h0 (n, hidden), masks (L, n) -> (values (L, n, 1), h_L)"""
+        features, h = self.rnn.chunk(self.base(state), h0, masks)
+        return self.v_out(features), h
+
+
+class MlpBaseGruActorCritic(torch.nn.Module):
+    """MAPPO's RECURRENT MLP actor-critic for the balance beam (r_actor_critic.py with ``use_recurrent_policy``, utils/rnn.py with
+    ``recurrent_N`` 1): ``MlpBaseActorCritic`` with an ``RNNLayer`` -- one GRU layer of width ``hidden`` and a LayerNorm -- between the
+    base and the head of both nets.  ``actor(obs, h, mask)`` / ``critic(obs, h, mask)`` take the (n, 7) observation as floats, the (n,
+    hidden) state and the (n) mask (0 where the episode has just ended) and return (logits or value, new state); ``.chunk`` runs L
+    steps.  The state dicts have the reference's keys (``rnn.rnn.weight_ih_l0`` ... ``rnn.norm.bias``), so ``load_state_dict`` takes a
+    reference checkpoint's two files.  Initialisation is the reference's: the GRU's weights orthogonal and its biases zero
+    (rnn.py:14-21), the rest as ``MlpBaseActorCritic``."""
+
+    def __init__(self, layer_N=2, obs_dim=_lib.MLPBASE_OBS, num_actions=_lib.MLPBASE_ACTIONS, hidden=_lib.MLPBASE_HIDDEN):
+        super().__init__()
+        self.obs_dim, self.num_actions, self.hidden, self.layer_N = int(obs_dim), int(num_actions), int(hidden), int(layer_N)
+        self.actor = _MlpBaseGruActor(self.obs_dim, self.hidden, self.layer_N, self.num_actions)
+        self.critic = _MlpBaseGruCritic(self.obs_dim, self.hidden, self.layer_N)
+        for head, head_gain in ((self.actor.act.action_out.linear, 0.01), (self.critic.v_out, 1.0)):
+            torch.nn.init.orthogonal_(head.weight, gain=head_gain)
+            torch.nn.init.constant_(head.bias, 0.0)

@@ -8,6 +8,7 @@
 #include "cnn_update.hpp"
 #include "mlpbase_policy.hpp"
 #include "mlpbase_bank.hpp"
+#include "mlpbase_gru.hpp"
 #include "mlpbase_update.hpp"
 
 #include <type_traits>
@@ -344,6 +345,7 @@ struct CnnNet {
         return mappo_shape_error(p.width, p.height, p.channels, p.hidden, minibatch_size);
     }
     static uint64_t actor_params(const UpdatePolicy &p) { return cnn_net_params(p.width, p.height, p.channels, kCnnActions); }
+    static uint64_t workspace_floats(const UpdatePolicy &p, uint32_t B, uint32_t K) { return mappo_workspace(actor_params(p), B, K).total; }
     static uint64_t num_params(const UpdatePolicy &p) { return mrl_cnn_policy_num_params(p.width, p.height, p.channels, p.hidden, kCnnActions); }
     template <class... Rest> static void launch_update(const UpdatePolicy &p, Rest &&...rest) { launch_mappo_update(p, rest...); }
 };
@@ -395,8 +397,25 @@ struct MlpBaseNet {
         return mappo_mlp_shape_error(kMlpBaseObs, p.hidden, p.layer_N, kMlpBaseActions, minibatch_size);
     }
     static uint64_t actor_params(const UpdatePolicy &p) { return (uint64_t)mlpbase_net_params(p.layer_N, kMlpBaseActions); }
+    static uint64_t workspace_floats(const UpdatePolicy &p, uint32_t B, uint32_t K) { return mappo_workspace(actor_params(p), B, K).total; }
     static uint64_t num_params(const UpdatePolicy &p) { return mrl_mlpbase_policy_num_params(kMlpBaseObs, p.hidden, p.layer_N, kMlpBaseActions); }
     template <class... Rest> static void launch_update(const UpdatePolicy &p, Rest &&...rest) { launch_mappo_mlp_update(p.layer_N, rest...); }
+};
+
+// The recurrent MLPBase as the update sees it (mrl_mappo_mlp_update with MRL_MLPBASE_RECURRENT): MlpBaseNet's refusals on the
+// structs the extended ones begin with; the rows are chunk ids, the workspace and the launch the recurrent update's.
+struct MlpBaseGruNet : MlpBaseNet {
+    static uint64_t actor_params(const UpdatePolicy &p) { return (uint64_t)gru_net_params(p.layer_N, kMlpBaseActions); }
+    static uint64_t num_params(const UpdatePolicy &p) { return (uint64_t)gru_net_params(p.layer_N, kMlpBaseActions) + gru_net_params(p.layer_N, 1); }
+    static uint64_t workspace_floats(const UpdatePolicy &p, uint32_t Bc, uint32_t K) { return gru_update_workspace(p.layer_N, Bc, K).total; }
+    // `batch` is the first member of the mrl_mappo_mlp_gru_batch that gru_update checked
+    static void launch_update(const UpdatePolicy &p, const mrl_mappo_optimizer &opt, const Batch &batch, const int32_t *indices, uint32_t K,
+                              uint32_t Bc, const mrl_mappo_config &cfg, float *value_norm_state, float *workspace, float *stats, float *grads,
+                              hipStream_t stream, const MappoMembers &)
+    {
+        launch_mappo_gru_update(p.layer_N, opt, reinterpret_cast<const mrl_mappo_mlp_gru_batch &>(batch), indices, K, Bc, cfg, value_norm_state,
+                                workspace, stats, grads, stream);
+    }
 };
 
 // ---- act and rollout, plain and over a bank ----
@@ -485,6 +504,76 @@ static int rollout(const char *what, mrl_sim *sim, uint32_t players, const typen
         [] {});
 }
 
+// ---- the recurrent MLPBase: mrl_mlpbase_act and mrl_rollout_mlpbase with MRL_MLPBASE_RECURRENT in the policy's flags ----
+
+// Everything the recurrent act and rollout check alike: mrl_mlpbase_act's own checks on the base structs (the bit taken out:
+// to every other caller of mlpbase_prepare, the banks included, it stays an unknown policy flag), then the state and h0 arrays.
+static int gru_prepare(mrl_sim *sim, uint32_t players, const mrl_mlpbase_gru_policy *policy, const mrl_mlpbase_gru_record *record,
+                       void *hip_stream, const char *what, MlpBaseGruActArgs *args, mrl_mlpbase_policy *plain)
+{
+    *plain = policy->base;
+    plain->flags &= ~(uint32_t)MRL_MLPBASE_RECURRENT;
+    if (int rc = mlpbase_prepare(sim, players, plain, record ? &record->base : nullptr, hip_stream, what, &args->act)) return rc;
+    if (!policy->h_actor || !policy->h_critic || ((reinterpret_cast<uintptr_t>(policy->h_actor) | reinterpret_cast<uintptr_t>(policy->h_critic)) & 3u))
+        return refusal(what, "a recurrent policy needs h_actor and h_critic, each on a 4-byte boundary");
+    if (record) {
+        if (record->chunk_length == 0 || record->base.num_steps % record->chunk_length != 0)
+            return refusal(what, "a recurrent record needs chunk_length >= 1 that divides num_steps");
+        if (!record->h0_actor || !record->h0_critic ||
+            ((reinterpret_cast<uintptr_t>(record->h0_actor) | reinterpret_cast<uintptr_t>(record->h0_critic)) & 3u))
+            return refusal(what, "a recurrent record needs h0_actor and h0_critic, each on a 4-byte boundary");
+    }
+    args->h[0] = policy->h_actor, args->h[1] = policy->h_critic;
+    return MRL_OK;
+}
+
+// what a recurrent act fills behind the checks: the plain act's rows, seed, step and flags, then the h0 rows and the write-back
+static void gru_fill(MlpBaseGruActArgs &g, const mrl_mlpbase_gru_record *record, uint32_t row, uint64_t seed, uint32_t step, uint32_t flags)
+{
+    const bool value_only = flags & MRL_MLPBASE_VALUE_ONLY;
+    mlpbase_rows(g.act, record ? &record->base : nullptr, row, value_only);
+    g.act.seed = seed, g.act.step = step, g.act.flags = flags;
+    g.write_state = value_only ? 0u : 1u;
+    g.h0_row[0] = g.h0_row[1] = nullptr;
+    if (record && !value_only && row % record->chunk_length == 0) {
+        const size_t at = (size_t)(row / record->chunk_length) * g.act.num_worlds * g.act.P * kMlpBaseHidden;
+        g.h0_row[0] = record->h0_actor + at, g.h0_row[1] = record->h0_critic + at;
+    }
+}
+
+static int gru_act(const char *what, mrl_sim *sim, uint32_t players, const mrl_mlpbase_gru_policy *policy, const mrl_mlpbase_gru_record *record,
+                   uint32_t row, uint64_t seed, uint32_t step, uint32_t flags, void *hip_stream)
+{
+    MlpBaseGruActArgs args{};
+    mrl_mlpbase_policy plain{};
+    if (int rc = gru_prepare(sim, players, policy, record, hip_stream, what, &args, &plain)) return rc;
+    if (int rc = act_row_refusal(what, MlpBaseNet::kValueOnly, flags, plain.flags, record ? &record->base : nullptr, row)) return rc;
+    DeviceGuard on(sim->device);
+    return guarded([&] {
+        gru_fill(args, record, row, seed, step, flags);
+        launch_mlpbase_gru_act(args, (hipStream_t)hip_stream);
+    });
+}
+
+static int gru_rollout(const char *what, mrl_sim *sim, uint32_t players, const mrl_mlpbase_gru_policy *policy, const mrl_mlpbase_gru_record *record,
+                       uint64_t seed, uint32_t first_step, void *hip_stream)
+{
+    MlpBaseGruActArgs args{};
+    mrl_mlpbase_policy plain{};
+    if (int rc = gru_prepare(sim, players, policy, record, hip_stream, what, &args, &plain)) return rc;
+    if (int rc = refusal(what, record ? nullptr : "null record")) return rc;
+    DeviceGuard on(sim->device);
+    return guarded([&] {
+        rollout_loop(
+            sim, record->base.num_steps, (hipStream_t)hip_stream,
+            [&](uint32_t k, bool closing) {
+                gru_fill(args, record, k, seed, first_step + k, plain.flags | (closing ? (uint32_t)MRL_MLPBASE_VALUE_ONLY : 0u));
+                launch_mlpbase_gru_act(args, (hipStream_t)hip_stream);
+            },
+            [] {});
+    });
+}
+
 template <class Net>
 static int rollout_bank(const char *what, mrl_sim *sim, uint32_t players, const typename Net::Bank *bank, int32_t *ids_dev, int32_t *episodes_dev,
                         const mrl_cnn_resample *resample, const typename Net::Record *record, int32_t *ids_record, void *obs_ring_dev,
@@ -561,7 +650,7 @@ static int mappo_update(const char *what, const typename Net::UpdatePolicy *poli
                        minibatch_size, batch->size);
         return MRL_ERR_INVALID;
     }
-    const uint64_t need_bytes = members * mappo_workspace(Net::actor_params(*policy), minibatch_size, num_minibatches).total * sizeof(float);
+    const uint64_t need_bytes = members * Net::workspace_floats(*policy, minibatch_size, num_minibatches) * sizeof(float);
     const void *words[] = {opt->params_dev, opt->exp_avg, opt->exp_avg_sq, Net::kObsWords ? batch->obs : nullptr, batch->actions, batch->logprobs,
                            batch->value_preds, batch->returns, batch->advantages, indices_dev, value_norm_state, stats_dev_or_null,
                            grads_dev_or_null};
@@ -577,6 +666,41 @@ static int mappo_update(const char *what, const typename Net::UpdatePolicy *poli
         Net::launch_update(*policy, *opt, *batch, indices_dev, num_minibatches, minibatch_size, *cfg, value_norm_state,
                            static_cast<float *>(workspace_dev), stats_dev_or_null, grads_dev_or_null, (hipStream_t)hip_stream, launch_members);
     });
+}
+
+// mrl_mappo_mlp_update with MRL_MLPBASE_RECURRENT: what the extended batch adds is checked here, the rest by mappo_update on the
+// structs the extended ones begin with (the policy's state pointers are not read: every chunk starts from the batch's h0)
+static int gru_update(const char *what, const mrl_mlpbase_gru_policy *policy, const mrl_mappo_optimizer *opt, const mrl_mappo_mlp_gru_batch *batch,
+                      const int32_t *indices_dev, uint32_t num_minibatches, uint32_t minibatch_size, const mrl_mappo_config *cfg,
+                      float *value_norm_state, void *workspace_dev, uint64_t workspace_bytes, float *stats_dev_or_null, float *grads_dev_or_null,
+                      int gpu_id, void *hip_stream)
+{
+    if (batch) {
+        const uintptr_t low_bits = reinterpret_cast<uintptr_t>(batch->h0_actor) | reinterpret_cast<uintptr_t>(batch->h0_critic) |
+                                   reinterpret_cast<uintptr_t>(batch->dones);
+        if (!batch->h0_actor || !batch->h0_critic || !batch->dones || (low_bits & 3u))
+            return refusal(what, "a recurrent batch needs h0_actor, h0_critic and dones, each on a 4-byte boundary");
+        if (batch->chunk_length == 0 || batch->chunk_length > kGruMaxChunk) {
+            set_error("%s: chunk_length %u: the update runs chunks of 1 to %u steps", what, batch->chunk_length, kGruMaxChunk);
+            return MRL_ERR_INVALID;
+        }
+        const uint64_t row = (uint64_t)batch->chunk_length * batch->num_worlds * batch->num_seats;
+        if (row == 0 || batch->base.size % row != 0) {
+            set_error("%s: a batch of %u samples is not a whole number of rows of %u-step chunks of %u worlds and %u seats", what,
+                      batch->base.size, batch->chunk_length, batch->num_worlds, batch->num_seats);
+            return MRL_ERR_INVALID;
+        }
+        if (minibatch_size > batch->base.size / batch->chunk_length) {  // (so that Bc L, a row's samples, is at most the batch's size)
+            set_error("%s: minibatch_size %u: a row holds chunk ids, and the batch has %u chunks", what, minibatch_size,
+                      batch->base.size / batch->chunk_length);
+            return MRL_ERR_INVALID;
+        }
+    }
+    mrl_mlpbase_policy plain{};
+    if (policy) plain = policy->base;
+    return mappo_update<MlpBaseGruNet>(what, policy ? &plain : nullptr, opt, batch ? &batch->base : nullptr, indices_dev, num_minibatches,
+                                       minibatch_size, cfg, value_norm_state, workspace_dev, workspace_bytes, stats_dev_or_null,
+                                       grads_dev_or_null, gpu_id, hip_stream);
 }
 
 // mrl_mappo_bank_workspace_bytes and mrl_mappo_mlp_bank_workspace_bytes (`what`): the plain update's workspace, once per member
@@ -610,6 +734,10 @@ uint64_t mrl_cnn_workspace_bytes(uint32_t num_worlds, uint32_t num_players) { re
 
 uint64_t mrl_mlpbase_policy_num_params(uint32_t obs_dim, uint32_t hidden, uint32_t layer_N, uint32_t num_actions)
 {
+    // the recurrent shape: layer_N + MRL_MLPBASE_GRU_LAYERS
+    const uint32_t gru = layer_N - MRL_MLPBASE_GRU_LAYERS;
+    if (obs_dim == mrl::kMlpBaseObs && hidden == mrl::kMlpBaseHidden && gru >= 1 && gru <= mrl::kMlpBaseMaxLayerN && num_actions == mrl::kMlpBaseActions)
+        return (uint64_t)mrl::gru_net_params(gru, num_actions) + mrl::gru_net_params(gru, 1);
     if (obs_dim != mrl::kMlpBaseObs || hidden != mrl::kMlpBaseHidden || layer_N < 1 || layer_N > mrl::kMlpBaseMaxLayerN ||
         num_actions != mrl::kMlpBaseActions)
         return 0;
@@ -644,6 +772,12 @@ int mrl_mappo_workspace_bytes(uint32_t width, uint32_t height, uint32_t channels
 int mrl_mappo_mlp_workspace_bytes(uint32_t obs_dim, uint32_t hidden, uint32_t layer_N, uint32_t num_actions, uint32_t minibatch_size,
                                   uint32_t num_minibatches, uint64_t *out)
 {
+    // the recurrent shape: layer_N + MRL_MLPBASE_GRU_LAYERS
+    const uint32_t gru = layer_N - MRL_MLPBASE_GRU_LAYERS;
+    if (out && gru >= 1 && gru <= mrl::kMlpBaseMaxLayerN && !mappo_mlp_shape_error(obs_dim, hidden, gru, num_actions, minibatch_size)) {
+        *out = mrl::gru_update_workspace(gru, minibatch_size, num_minibatches).total * sizeof(float);
+        return MRL_OK;
+    }
     const char *why = out ? mappo_mlp_shape_error(obs_dim, hidden, layer_N, num_actions, minibatch_size) : "null output pointer";
     if (why) {
         mrl::set_error("mrl_mappo_mlp_workspace_bytes: %s (obs_dim %u, hidden %u, layer_N %u, num_actions %u, minibatch_size %u)", why, obs_dim,
@@ -663,6 +797,9 @@ int mrl_cnn_act(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, co
 int mrl_mlpbase_act(mrl_sim *sim, uint32_t players, const mrl_mlpbase_policy *policy, const mrl_mlpbase_record *record, uint32_t row,
                     uint64_t seed, uint32_t step, uint32_t flags, void *hip_stream)
 {
+    if (policy && (policy->flags & MRL_MLPBASE_RECURRENT))
+        return mrl::gru_act("mrl_mlpbase_act", sim, players, reinterpret_cast<const mrl_mlpbase_gru_policy *>(policy),
+                            reinterpret_cast<const mrl_mlpbase_gru_record *>(record), row, seed, step, flags, hip_stream);
     return mrl::act<MlpBaseNet>("mrl_mlpbase_act", sim, players, policy, record, row, seed, step, flags, nullptr, 0, hip_stream);
 }
 
@@ -691,6 +828,9 @@ int mrl_rollout_cnn(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy
 int mrl_rollout_mlpbase(mrl_sim *sim, uint32_t players, const mrl_mlpbase_policy *policy, const mrl_mlpbase_record *record, uint64_t seed,
                         uint32_t first_step, void *hip_stream)
 {
+    if (policy && (policy->flags & MRL_MLPBASE_RECURRENT))
+        return mrl::gru_rollout("mrl_rollout_mlpbase", sim, players, reinterpret_cast<const mrl_mlpbase_gru_policy *>(policy),
+                                reinterpret_cast<const mrl_mlpbase_gru_record *>(record), seed, first_step, hip_stream);
     return mrl::rollout<MlpBaseNet>("mrl_rollout_mlpbase", sim, players, policy, record, nullptr, seed, first_step, hip_stream);
 }
 
@@ -742,6 +882,10 @@ int mrl_mappo_mlp_update(const mrl_mlpbase_policy *policy, const mrl_mappo_optim
                          uint32_t num_minibatches, uint32_t minibatch_size, const mrl_mappo_config *cfg, float *value_norm_state, void *workspace_dev,
                          uint64_t workspace_bytes, float *stats_dev_or_null, float *grads_dev_or_null, int gpu_id, void *hip_stream)
 {
+    if (policy && (policy->flags & MRL_MLPBASE_RECURRENT))
+        return mrl::gru_update("mrl_mappo_mlp_update", reinterpret_cast<const mrl_mlpbase_gru_policy *>(policy), opt,
+                               reinterpret_cast<const mrl_mappo_mlp_gru_batch *>(batch), indices_dev, num_minibatches, minibatch_size, cfg,
+                               value_norm_state, workspace_dev, workspace_bytes, stats_dev_or_null, grads_dev_or_null, gpu_id, hip_stream);
     return mrl::mappo_update<MlpBaseNet>("mrl_mappo_mlp_update", policy, opt, batch, indices_dev, num_minibatches, minibatch_size, cfg,
                                          value_norm_state, workspace_dev, workspace_bytes, stats_dev_or_null, grads_dev_or_null, gpu_id, hip_stream);
 }
@@ -751,6 +895,8 @@ int mrl_mappo_mlp_bank_update(const mrl_mlpbase_policy *policy, const mrl_mappo_
                               float *value_norm_state, void *workspace_dev, uint64_t workspace_bytes, float *stats_dev_or_null,
                               float *grads_dev_or_null, int gpu_id, void *hip_stream)
 {
+    if (policy && (policy->flags & MRL_MLPBASE_RECURRENT))
+        return mrl::refusal("mrl_mappo_mlp_bank_update", "a bank update does not take a recurrent policy (MRL_MLPBASE_RECURRENT)");
     return mrl::mappo_update<MlpBaseNet>("mrl_mappo_mlp_bank_update", policy, opt, batch, indices_dev, num_minibatches, minibatch_size, cfg,
                                          value_norm_state, workspace_dev, workspace_bytes, stats_dev_or_null, grads_dev_or_null, gpu_id, hip_stream);
 }

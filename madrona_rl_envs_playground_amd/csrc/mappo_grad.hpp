@@ -183,18 +183,27 @@ __device__ __forceinline__ void mappo_stats_tail(const MappoGradCommon &a, uint3
 // parameters and then the critic's `critic` (two clip_grad_norm_ and two Adam steps).  `members` (MappoMembers): every launch
 // serves that many members at once (blockIdx.z), opt, indices, value_norm_state, workspace, stats and grads being the first
 // member's; launch_grad(common arguments, workgroups per net, the members' strides, their count) then launches the MEMBERS instance.
+// What a row's SAMPLES are where its indices are not sample numbers (the recurrent update's rows are chunk ids): the (K, count)
+// sample numbers ValueNorm's recurrence reads (nullptr: the rows' own indices) and the number of samples every mean of a row runs
+// over (0: minibatch_size).
+struct MappoRowSamples {
+    const int32_t *indices;
+    uint32_t count;
+};
+
 template <class Batch, class LaunchGrad>
 inline void mappo_update_rows(uint32_t actor, uint32_t critic, const mrl_mappo_optimizer &opt, const Batch &batch, const int32_t *indices,
                               uint32_t num_minibatches, uint32_t minibatch_size, const mrl_mappo_config &cfg, float *value_norm_state,
                               float *workspace, float *stats, float *grads, hipStream_t stream, const MappoMembers &members,
-                              LaunchGrad launch_grad)
+                              LaunchGrad launch_grad, const MappoRowSamples &samples = MappoRowSamples{nullptr, 0})
 {
+    const uint32_t row_samples = samples.count ? samples.count : minibatch_size;
     const SampleShare share = share_samples(minibatch_size, kMappoTile, kMappoMaxGroups);
     const MappoWorkspace ws = mappo_workspace(actor, minibatch_size, num_minibatches);
     const bool norm = cfg.flags & MRL_MAPPO_VALUENORM, one = members.count == 1;
     const uint64_t member_scratch = one ? 0 : ws.total, member_rows = one ? 0 : num_minibatches;
     if (norm)
-        launch_mappo_value_norm(batch.returns, indices, num_minibatches, minibatch_size, batch.size, cfg, value_norm_state,
+        launch_mappo_value_norm(batch.returns, samples.indices ? samples.indices : indices, num_minibatches, row_samples, batch.size, cfg, value_norm_state,
                                 workspace + ws.row_sums, workspace + ws.row_norm, stream, members.count, member_scratch);
     MappoGradCommon g{};
     g.obs = batch.obs;
@@ -228,7 +237,7 @@ inline void mappo_update_rows(uint32_t actor, uint32_t critic, const mrl_mappo_o
     ad.blocks = (uint32_t)ws.blocks;
     ad.num_params[0] = actor, ad.num_params[1] = critic;
     ad.at[0] = 0, ad.at[1] = actor;
-    MappoBankStatsRow rows{{g.partial_stats, nullptr, share.groups, minibatch_size}, member_scratch / 2, member_rows * kMappoStats};
+    MappoBankStatsRow rows{{g.partial_stats, nullptr, share.groups, row_samples}, member_scratch / 2, member_rows * kMappoStats};
     MappoStatsRow &row = rows.first;
     for (uint32_t k = 0; k < num_minibatches; k++) {
         g.indices = indices + (size_t)k * minibatch_size;

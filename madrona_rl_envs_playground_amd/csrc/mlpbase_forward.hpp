@@ -53,7 +53,9 @@ __device__ __forceinline__ void mlpbase_layer_norm(float *__restrict__ x, float 
 }
 
 // Both the act and the update: from the tile's observation rows as floats in xhat0 (a row past the end: zeros) to the head's
-// outputs in outs (row stride 8).  `net`: the net's first parameter; out_dim 4 (actor) or 1 (critic).
+// outputs in outs (row stride 8).  `net`: the net's first parameter; out_dim 4 (actor) or 1 (critic).  HEAD = false (the recurrent
+// net, mlpbase_gru.hpp, whose GRU lies between the two): the base alone, which ends with y[layer_N] behind a barrier.
+template <bool HEAD = true>
 __device__ __forceinline__ void mlpbase_forward(const float *__restrict__ net, uint32_t layer_N, uint32_t out_dim, float *__restrict__ lds,
                                                 uint32_t wave, uint32_t lane)
 {
@@ -70,6 +72,7 @@ __device__ __forceinline__ void mlpbase_forward(const float *__restrict__ net, u
                            mask + h * kMlpBaseTile, wave, lane);
         in = y, in_ld = kMlpLd, K = kMlpBaseHidden;
     }
+    if constexpr (!HEAD) return;
     const float *__restrict__ head_w = net + mlpbase_head_at(layer_N);
     cnn_fc_layer(in, in_ld, kMlpBaseHidden, head_w, head_w + out_dim * kMlpBaseHidden, out_dim, false, chunk, outs, 8u, wave, lane);
 }

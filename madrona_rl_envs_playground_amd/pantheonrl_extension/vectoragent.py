@@ -155,7 +155,8 @@ class MlpBasePolicyAgent(_DevicePolicyAgent):
     reference's ``CentralizedAgent`` does for the partner seat --, the counterpart of ``CnnPolicyAgent``: ``get_action`` is
     ``mrl_mlpbase_act`` for this agent's seat (``player_num``, set by ``env.add_partner_agent``, or, while that is ``None``, the
     env's ``ego_ind``) on the simulator's own observations, and returns the view ``env.static_actions[seat]``.  ``policy``: a
-    ``simulators.MlpBasePolicy``; ``seed`` seeds the draws, whose step number counts this agent's calls.  ``update`` does nothing.
+    ``simulators.MlpBasePolicy``, or a ``simulators.MlpBaseGruPolicy`` (recurrent), for which the agent keeps its own
+    ``MlpBaseGruState`` in ``state``; ``seed`` seeds the draws, whose step number counts this agent's calls.  ``update`` does nothing.
     Any other env, or one off the GPU, is refused with a ``TypeError`` by the constructor: there is no torch fallback."""
 
     def _check_env(self):
@@ -171,7 +172,20 @@ class MlpBasePolicyAgent(_DevicePolicyAgent):
         return sim
 
     def _act(self, mask):
-        from ..simulators import mlpbase_act
+        from ..simulators import MlpBaseGruPolicy, MlpBaseGruState, mlpbase_act
+        if isinstance(self.policy, MlpBaseGruPolicy):
+            # a recurrent policy: this agent owns the state its seat runs on (``state``, zero at first; the act masks it where an
+            # episode has just ended), binds it for this call alone and puts back what was bound before, so one policy may serve
+            # several agents and a trainer besides: none of them finds another's state bound
+            if getattr(self, "state", None) is None:
+                self.state = MlpBaseGruState(self.envs.num_envs, self.envs.static_actions.device)
+            bound_before = self.policy.running
+            self.policy.bind(self.state)
+            try:
+                mlpbase_act(self._sim, self.policy, mask, seed=self.seed, step=self._draws, greedy=self.greedy)
+            finally:
+                self.policy.running = bound_before
+            return
         mlpbase_act(self._sim, self.policy, mask, seed=self.seed, step=self._draws, greedy=self.greedy)
 
 

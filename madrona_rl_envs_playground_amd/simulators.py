@@ -47,10 +47,12 @@ from ._ppo import (MlpAgent, MlpPolicy, MlpPolicyBank, PpoBankOptimizer, PpoOpti
 from ._wide import (AgentRecord, WideAgent, WideOptimizer, WidePolicy, WidePolicyBank, _WIDE_TYPES, _cross_play_wide,  # noqa: F401
                     _wide_bank_workspace, _wide_mlp, _wide_seats, agent_act, agent_act_bank, agent_bank_workspace_bytes,
                     agent_credit, agent_update, gae_active, wide_resample)
-from ._mappo_nets import (CnnActorCritic, MlpBaseActorCritic, _ActLayer, _ActorCritic, _CategoricalHead, _CnnActor, _CnnBase,  # noqa: F401
-                          _CnnCritic, _CnnLayer, _MlpBase, _MlpBaseActor, _MlpBaseCritic, _MlpLayer)
+from ._mappo_nets import (CnnActorCritic, MlpBaseActorCritic, MlpBaseGruActorCritic, _ActLayer, _ActorCritic, _CategoricalHead, _CnnActor, _CnnBase,  # noqa: F401
+                          _CnnCritic, _CnnLayer, _MlpBase, _MlpBaseActor, _MlpBaseCritic, _MlpBaseGruActor, _MlpBaseGruCritic, _MlpLayer,
+                          _RnnLayer)
 from ._mappo import (ActsWithCnnPolicy, ActsWithMlpBasePolicy, CnnPolicy, CnnPolicyBank, CnnRecord, MappoOptimizer,  # noqa: F401
-                     MappoResult, MlpBasePolicy, MlpBasePolicyBank, MlpBaseRecord, ValueNorm, _ActsWithMappoPolicy, _CNN,
+                     MappoResult, MlpBaseGruPolicy, MlpBaseGruRecord, MlpBaseGruState, MlpBasePolicy, MlpBasePolicyBank, MlpBaseRecord,
+                     ValueNorm, chunk_indices, _ActsWithMappoPolicy, _CNN,
                      _Family, _FlatPolicy, _MLPBASE, _MappoRecord, _MappoRollouts, _act, _act_bank, _bank_call_args,
                      _call_args, _cnn_bank_call_args, _cnn_bank_workspace, _cnn_call_args, _kitchen_cells,
                      _mappo_config, _mlpbase_bank_call_args, _mlpbase_bank_workspace, _mlpbase_call_args, _ring_pointer,

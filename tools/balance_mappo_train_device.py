@@ -7,6 +7,12 @@ of the weights.
 
     python tools/balance_mappo_train_device.py --num-envs 1024 --updates 20
     python tools/balance_mappo_train_device.py --evaluate --json run.json
+    python tools/balance_mappo_train_device.py --recurrent --data-chunk-length 10
+
+``--recurrent``: the reference's ``--use_recurrent_policy`` -- a GRU between the base and the head of both nets
+(``MlpBaseGruPolicy``); the running states are carried from rollout to rollout, the update evaluates chunks of
+``--data-chunk-length`` steps from the states the rollout recorded (``chunk_indices``: a permutation of the chunks per epoch, as
+``recurrent_generator`` draws it) and back-propagates through them.
 
 The defaults are train/config.py's: ``episode_length`` 200 steps per update, ``ppo_epoch`` 15, one minibatch, lr = critic_lr =
 5e-4, ``layer_N`` 2.  ``--evaluate``: greedy episodes in every world, then the histogram of the worlds' returns (an episode is two
@@ -39,6 +45,8 @@ def evaluate(env, policy, seed=0):
     returns rounded to six places."""
     import torch
     env.n_reset(worlds=torch.ones(env.num_envs, dtype=torch.bool, device=env.static_dones.device))
+    if getattr(policy, "running", None) is not None:
+        policy.running.zero_()  # a recurrent policy starts its episodes from zero states
     score = torch.zeros(env.num_envs, dtype=torch.float64, device=env.static_rewards.device)
     playing = torch.ones(env.num_envs, dtype=torch.bool, device=env.static_rewards.device)
     for step in range(EPISODE_STEPS):
@@ -52,38 +60,50 @@ def evaluate(env, policy, seed=0):
 
 def train(num_envs, num_steps, updates, seed, lr=5e-4, critic_lr=5e-4, lr_decay=False, gamma=0.99, gae_lambda=0.95, ppo_epoch=15,
           num_mini_batch=1, clip_param=0.2, entropy_coef=0.01, value_loss_coef=1.0, max_grad_norm=10.0, huber_delta=10.0, layer_N=2,
-          log=None, evaluation=None, final=None, policy=None):
+          log=None, evaluation=None, final=None, policy=None, recurrent=False, data_chunk_length=10):
     """``updates`` iterations of collect, advantages, update with the reference's defaults (train/config.py).  One dict per
     update: the learning rates, the mean of every stat over the update's rows (``train_info``), the episodes finished during the
     update with their mean return, and ``optimizer_step``.  ``evaluation``: a dict that takes ``evaluate``'s histogram under
     "returns" after the last update.  ``final``: a dict that takes the final parameters (a CPU tensor) under "params".  ``policy``: an
     ``MlpBasePolicy`` of ``layer_N`` to train in place from the parameters it holds -- a member of an ``MlpBasePolicyBank``, say --
-    instead of a fresh one initialised under ``seed``."""
+    instead of a fresh one initialised under ``seed``.  ``recurrent``: train an ``MlpBaseGruPolicy`` over chunks of
+    ``data_chunk_length`` steps, which must divide ``num_steps``."""
     import torch
     from madrona_rl_envs_playground_amd import _lib
-    from madrona_rl_envs_playground_amd.simulators import (MappoOptimizer, MlpBaseActorCritic, MlpBasePolicy, ValueNorm, mappo_advantages,
+    from madrona_rl_envs_playground_amd.simulators import (MappoOptimizer, MlpBaseActorCritic, MlpBaseGruActorCritic, MlpBaseGruPolicy,
+                                                             MlpBaseGruRecord, MlpBasePolicy, ValueNorm, chunk_indices, mappo_advantages,
                                                              mappo_update, minibatch_indices)
     env = make_env(num_envs)
     device = torch.device("cuda", 0)
     players = env.n_players
     if policy is None:
         torch.manual_seed(seed)
-        policy = MlpBasePolicy.from_module(MlpBaseActorCritic(layer_N=layer_N), device=device)
-    elif policy.layer_N != layer_N:
-        raise ValueError(f"the policy has layer_N {policy.layer_N}, asked for {layer_N}")
+        if recurrent:
+            policy = MlpBaseGruPolicy.from_module(MlpBaseGruActorCritic(layer_N=layer_N), device=device)
+        else:
+            policy = MlpBasePolicy.from_module(MlpBaseActorCritic(layer_N=layer_N), device=device)
+    elif policy.layer_N != layer_N or isinstance(policy, MlpBaseGruPolicy) != bool(recurrent):
+        raise ValueError(f"the policy has layer_N {policy.layer_N}, asked for {layer_N}; recurrent {bool(recurrent)} needs an "
+                         f"{'MlpBaseGruPolicy' if recurrent else 'MlpBasePolicy'}")
     optimizer = MappoOptimizer(policy, lr=lr, critic_lr=critic_lr)
     value_norm = ValueNorm(device)
     shuffles = torch.Generator(device=device).manual_seed(seed)
     rows = ppo_epoch * num_mini_batch
     host_stats = torch.empty((rows, len(_lib.MAPPO_STATS)), dtype=torch.float32).pin_memory()
     record, history = None, []
+    if recurrent:
+        policy.state(num_envs)
+        record = MlpBaseGruRecord(num_steps, num_envs, players, device, chunk_length=data_chunk_length)
     for update in range(updates):
         if lr_decay:  # utils/util.py:38-43
             optimizer.lr, optimizer.critic_lr = lr - lr * (update / updates), critic_lr - critic_lr * (update / updates)
         env.clear_episode_totals()
         record = env.rollout(policy, num_steps, seed=seed, first_step=update * num_steps, record=record)
         advantages, returns = mappo_advantages(record, value_norm, gamma, gae_lambda)
-        indices = minibatch_indices(num_steps * num_envs * players, num_mini_batch, ppo_epoch, generator=shuffles, device=device)
+        if recurrent:
+            indices = chunk_indices(record, num_mini_batch, ppo_epoch, generator=shuffles, device=device)
+        else:
+            indices = minibatch_indices(num_steps * num_envs * players, num_mini_batch, ppo_epoch, generator=shuffles, device=device)
         result = mappo_update(policy, optimizer, record, None, advantages, returns, indices, value_norm=value_norm, clip_param=clip_param,
                               entropy_coef=entropy_coef, value_loss_coef=value_loss_coef, max_grad_norm=max_grad_norm,
                               huber_delta=huber_delta)
@@ -118,6 +138,8 @@ def parser():
     ap.add_argument("--entropy-coef", type=float, default=DEFAULTS["entropy_coef"])
     ap.add_argument("--layer-N", type=int, default=DEFAULTS["layer_N"], choices=(1, 2))
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--recurrent", action="store_true", help="the recurrent actor-critic (the reference's --use_recurrent_policy)")
+    ap.add_argument("--data-chunk-length", type=int, default=10, help="steps per chunk of the recurrent update (the reference's default)")
     ap.add_argument("--evaluate", action="store_true", help="afterwards one greedy episode in every world; prints {return: worlds}")
     ap.add_argument("--json", help="also write the settings, the per-update entries and the histogram to this file")
     return ap
@@ -128,13 +150,14 @@ def main(argv=None):
     evaluation = {} if args.evaluate else None
     history = train(args.num_envs, args.num_steps, args.updates, args.seed, lr=args.lr, critic_lr=args.critic_lr, ppo_epoch=args.ppo_epoch,
                     num_mini_batch=args.num_mini_batch, entropy_coef=args.entropy_coef, layer_N=args.layer_N, evaluation=evaluation,
-                    log=lambda entry: print(json.dumps(entry), flush=True))
+                    recurrent=args.recurrent, data_chunk_length=args.data_chunk_length, log=lambda entry: print(json.dumps(entry), flush=True))
     if evaluation is not None:
         print(json.dumps({"greedy_returns": {str(k): v for k, v in evaluation["returns"].items()}}), flush=True)
     if args.json:
         from madrona_rl_envs_playground_amd import _lib
         settings = {name: getattr(args, name) for name in ("num_envs", "num_steps", "updates", "ppo_epoch", "num_mini_batch", "lr",
-                                                           "critic_lr", "entropy_coef", "layer_N", "seed")}
+                                                           "critic_lr", "entropy_coef", "layer_N", "seed", "recurrent",
+                                                           "data_chunk_length")}
         out = {"build_hash": _lib.build_hash(), "settings": settings, "updates": history,
                "mean_returns": [entry["mean_return"] for entry in history]}
         if evaluation is not None:
