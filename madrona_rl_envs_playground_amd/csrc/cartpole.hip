@@ -468,8 +468,8 @@ __global__ void __launch_bounds__(kBlock) mrl_cartpole_step_fused(uint32_t n, co
 // same two grid-wide hand-offs per step as mrl_hanabi_rollout (hanabi.hip): the lower workgroups'
 // finished counts of this step (waited for) and everybody's counts of the previous step, through
 // a ring of four epoch-tagged status arrays.  All workgroups must be resident at once: the host
-// launches it cooperatively (the runtime refuses a grid the device cannot hold) and otherwise runs
-// one launch per step; waits are bounded (SCAN_TIMEOUT).
+// launches it cooperatively (the runtime refuses a grid the device cannot hold; mrl::launch_persistent)
+// and otherwise runs one launch per step; waits are bounded (SCAN_TIMEOUT).
 constexpr int kRing = 4;
 constexpr int64_t kPersistentMaxWorlds = 1 << 30;  // (set from the measurement below)
 
@@ -653,26 +653,25 @@ struct CartpoleSim final : mrl::EpisodeSim {
         if (num_steps == 0) return;
         if (persistent_ok && !launch_state.device_mode && !stats) {  // (a cooperative launch cannot be captured; its counters live on the host;
                                                                      // episode statistics are taken behind every step)
-            // cooperative: the runtime checks the grid against what the device can hold at once and
-            // refuses it otherwise -- then, and from then on, one launch per step
+            // cooperative where the runtime has a queue for it: it checks the grid against what the device can hold at
+            // once and refuses it otherwise -- then, and from then on, one launch per step
             uint32_t n = num_worlds, epoch0 = ring_epoch + 1u;
             const uint32_t *base = counter + parity;
             uint32_t *next = counter + (parity ^ 1u);
             mrl::Alarm al = alarm.alarm();
             void *args[] = {&n, &state, &reward, &done, &action, &ring, &epoch0, &num_steps, &first_step, &seed, &base, &next,
                             &reset_count, &al};
-            hipError_t err = hipSuccess;
+            bool launched = false;
             with_variant(variant, [&](auto v) {
-                err = hipLaunchCooperativeKernel(reinterpret_cast<const void *>(&mrl_cartpole_rollout<decltype(v)::value>),
-                                                 dim3(fused_grid), dim3(kBlock), args, 0, stream);
+                launched = mrl::launch_persistent(reinterpret_cast<const void *>(&mrl_cartpole_rollout<decltype(v)::value>), fused_grid,
+                                                  kBlock, args, device, stream);
             });
-            if (err == hipSuccess) {
+            if (launched) {
                 ring_epoch += num_steps;
                 parity ^= 1u;
                 return;
             }
-            (void)hipGetLastError();  // clear it; the per-step path below needs no co-residency
-            persistent_ok = false;
+            persistent_ok = false;  // the per-step path below needs no co-residency
         }
         for (uint32_t k = 0; k < num_steps; k++) {
             if (fused) {

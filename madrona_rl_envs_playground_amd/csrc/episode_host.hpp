@@ -12,6 +12,9 @@
 #include "episode_stats.hpp"
 #include "world_reset.hpp"
 
+#include <atomic>
+#include <map>
+#include <mutex>
 #include <stdexcept>
 
 namespace mrl {
@@ -40,6 +43,41 @@ inline bool grid_resident(const void *kernel, int block_threads, uint32_t grid, 
     // cooperative launch": keep one per CU in hand near the edge; the cooperative launch is the check)
     const int usable = per_cu > 4 ? per_cu - 1 : per_cu;
     return (uint64_t)grid <= (uint64_t)usable * (uint64_t)cus;
+}
+
+// Launches a persistent rollout kernel whose grid grid_resident has passed; false: refused, nothing was enqueued.
+// hipLaunchCooperativeKernel comes first: the runtime checks the grid against the device once more
+// (hipErrorCooperativeLaunchTooLarge is final).  But the runtime sends these launches through one queue of its own, and on a
+// virtualised GPU a process is refused that queue (hipErrorIllegalState) for as long as another process -- the parent that
+// started it, say -- owns one, which says nothing about the grid.  The rollout kernels use none of what that queue is for:
+// their workgroups wait on words in memory, not on the runtime's grid barrier.  So the same grid then goes out as an
+// ordinary launch, here and in every later call of this process.  What the runtime's queue did besides was to run such
+// launches of different streams one after the other; two of them side by side could each hold CUs the other waits for,
+// so an event per device keeps that order.
+inline bool launch_persistent(const void *kernel, uint32_t grid, uint32_t block, void **args, int device, hipStream_t stream)
+{
+    static std::atomic<bool> no_cooperative_queue{false};
+    if (!no_cooperative_queue) {
+        const hipError_t err = hipLaunchCooperativeKernel(kernel, dim3(grid), dim3(block), args, 0, stream);
+        if (err == hipSuccess) return true;
+        (void)hipGetLastError();
+        if (err == hipErrorCooperativeLaunchTooLarge) return false;
+        no_cooperative_queue = true;
+    }
+    static std::mutex mutex;
+    static std::map<int, hipEvent_t> last_launch;
+    std::lock_guard<std::mutex> lock(mutex);
+    hipEvent_t &last = last_launch[device];
+    if (!last)
+        MRL_HIP(hipEventCreateWithFlags(&last, hipEventDisableTiming));
+    else
+        MRL_HIP(hipStreamWaitEvent(stream, last, 0));
+    if (hipLaunchKernel(kernel, dim3(grid), dim3(block), args, 0, stream) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    MRL_HIP(hipEventRecord(last, stream));
+    return true;
 }
 
 struct EpisodeSim : mrl_sim {

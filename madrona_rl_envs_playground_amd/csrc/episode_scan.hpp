@@ -364,7 +364,8 @@ template <typename Reseed> __global__ void reseed_all(uint32_t n, uint32_t world
 // The persistent rollouts (mrl_*_rollout) are a different matter: there every workgroup waits for
 // EVERY other one at each step, which needs the whole grid resident at once.  They are launched
 // with hipLaunchCooperativeKernel, which refuses a grid the device cannot hold, and the host falls
-// back to one launch per step when it does; their waits are bounded and raise the Alarm on expiry.
+// back to one launch per step when it does (episode_host.hpp, launch_persistent: also what happens
+// where the runtime cannot make such a launch at all); their waits are bounded and raise the Alarm on expiry.
 // ---------------------------------------------------------------------------------------------
 // test hook (mrl_debug_set "inject_scan_timeout"): raises the alarm exactly as an expired wait would
 __attribute__((unused)) static __global__ void raise_alarm_kernel(const Alarm alarm) { alarm.raise(); }

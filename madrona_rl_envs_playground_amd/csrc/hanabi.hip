@@ -1984,8 +1984,9 @@ mrl_hanabi_step_fused(uint32_t *hot_records, const int32_t *hot_actions, uint32_
 // can run at most one step ahead of the slowest one (it needs everybody's previous-step count),
 // so a slot is never overwritten while somebody still reads it.  Unlike the single step this
 // kernel NEEDS all its workgroups resident at once (nobody exits before the last step): the host
-// launches it cooperatively (the runtime refuses a grid the device cannot hold at once) and falls
-// back to one launch per step when that fails.  Waits are bounded as everywhere (SCAN_TIMEOUT).
+// launches it cooperatively (the runtime refuses a grid the device cannot hold at once; see
+// mrl::launch_persistent for a runtime without a queue for such launches) and falls back to one
+// launch per step when that fails.  Waits are bounded as everywhere (SCAN_TIMEOUT).
 //
 // Thirteen waves with fixed jobs, coupled by three counters in LDS instead of barriers, so that phase A of step
 // k + 1 runs while the rows of step k are being stored:
@@ -2251,21 +2252,18 @@ struct HanabiSim final : mrl::EpisodeSim {
         a.sample = 1;
         a.sample_seed = seed;
         a.action_out = action;
-        // cooperative: the runtime checks the grid against what the device can hold at once
+        // cooperative where the runtime has a queue for it: it checks the grid against what the device can hold at once
         uint32_t epoch0 = ring_epoch + 1u;
         const uint32_t *base = counter + parity;
         uint32_t *next = counter + (parity ^ 1u);
         mrl::Alarm al = alarm.alarm();
         void *args[] = {&a, &ring, &epoch0, &num_steps, &first_step, &base, &next, &reset_count, &al};
-        hipError_t err = hipSuccess;
+        bool launched = false;
         with_variant(variant, [&](auto v) {
-            err = hipLaunchCooperativeKernel(reinterpret_cast<const void *>(&mrl_hanabi_rollout<decltype(v)::value>), dim3(grid),
-                                             dim3(kRolloutBlock), args, 0, stream);
+            launched = mrl::launch_persistent(reinterpret_cast<const void *>(&mrl_hanabi_rollout<decltype(v)::value>), grid, kRolloutBlock,
+                                              args, device, stream);
         });
-        if (err != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
+        if (!launched) return false;
         ring_epoch += num_steps;
         parity ^= 1u;
         return true;
