@@ -1052,11 +1052,13 @@ int mrl_rollout_cnn_bank(mrl_sim *sim, uint32_t players, const mrl_cnn_bank *ban
  *     section 16) does not fit 160 KiB; B == 0 or S == 0; a
  *     workspace below mrl_mappo_workspace_bytes or off a 16-byte boundary; params, moments, float arrays or indices off a 4-byte
  *     boundary; unknown flag bits; a capturing stream.  K == 0 enqueues nothing.  mrl_mappo_workspace_bytes refuses the same
- *     shapes and a NULL out.  Not built: active masks, PopArt, recurrent networks, update_actor = False, weight decay. */
+ *     shapes and a NULL out.  Not built: active masks, PopArt, update_actor = False, weight decay.  The recurrent network
+ *     (MRL_CNN_RECURRENT in policy->flags) is described behind this call.
+ *   mrl_mappo_policy.flags: MRL_CNN_RECURRENT or 0; other bits are not read. */
 enum { MRL_MAPPO_VALUENORM = 1, MRL_MAPPO_HUBER_LOSS = 2, MRL_MAPPO_CLIPPED_VALUE_LOSS = 4, MRL_MAPPO_MAX_GRAD_NORM = 8 };
 typedef struct mrl_mappo_policy {
     const float *params_dev;     /* as mrl_cnn_policy */
-    uint32_t hidden, flags;      /* flags: not read */
+    uint32_t hidden, flags;      /* flags: MRL_CNN_RECURRENT (below) or 0 */
     uint32_t width, height, channels;
 } mrl_mappo_policy;
 typedef struct mrl_mappo_config {
@@ -1083,6 +1085,71 @@ int mrl_mappo_update(const mrl_mappo_policy *policy, const mrl_mappo_optimizer *
                      const mrl_mappo_config *cfg, float *value_norm_state_dev_or_null /* (3) */, void *workspace_dev,
                      uint64_t workspace_bytes, float *stats_dev_or_null /* (K, 8) */, float *grads_dev_or_null /* (K, P) */,
                      int gpu_id, void *hip_stream);
+
+/* The RECURRENT CNN actor-critic for the kitchens: what the reference runs with --use_recurrent_policy on Overcooked and
+ * Simplecooked (R_Actor / R_Critic put an RNNLayer -- one GRU of width hidden_size and a LayerNorm, train/MAPPO/utils/rnn.py --
+ * between CNNBase and the head).  It travels through mrl_cnn_act, mrl_rollout_cnn, mrl_mappo_update and the two size queries: no
+ * new entry point and no changed struct, MRL_ABI_VERSION stays 4.  DESIGN.md section 28.
+ *   Network, per net: CNNBase as for mrl_cnn_act; with x = its output row, h the incoming state and m = 0 where DONE[world] is
+ *     set at the time of the act and 1 otherwise, the GRU step, its LayerNorm and the state convention are those stated for the
+ *     balance beam's recurrent network below (MRL_MLPBASE_RECURRENT), word for word and by the same device functions; the head
+ *     reads LayerNorm64(h').
+ *   Flat tensor: per net base.* exactly as in mrl_cnn_policy, then rnn.rnn.weight_ih_l0 (192, 64), weight_hh_l0 (192, 64),
+ *     bias_ih_l0 (192), bias_hh_l0 (192), rnn.norm.weight (64), bias (64), then the head: 25 088 floats more per net.
+ *     mrl_cnn_policy_num_params(W, H, F, 64 | MRL_CNN_GRU_HIDDEN, 6) counts it.
+ *   MRL_CNN_RECURRENT is a bit of mrl_cnn_policy.flags and of mrl_mappo_policy.flags ONLY, never of an act's `flags` argument
+ *     (there it is an unknown flag).  With it mrl_cnn_act and mrl_rollout_cnn read `policy` as an mrl_cnn_gru_policy and a non-NULL
+ *     `record` as an mrl_cnn_gru_record; h_actor and h_critic (N, P, 64) are the running states, read and written by the acts.
+ *   Act, one launch: CNNBase into LDS; the tile's 32 state rows, times m; with a record and row % L == 0 (L = chunk_length) the
+ *     INCOMING state, before the mask, goes to h0_*[row / L] ((T / L, N, P, 64)); the GRU and its LayerNorm in an LDS image laid
+ *     over the convolution's dead operands, so that no kitchen mrl_cnn_act admits is refused; the head, the draw and the record
+ *     row as mrl_cnn_act's; h' back to the state.  Seats outside `players` keep every byte of their state rows.  The closing
+ *     MRL_CNN_VALUE_ONLY act reads the critic's state and writes NOTHING to either state tensor or to h0.  Without a record only
+ *     the actor runs and only h_actor advances.
+ *   mrl_rollout_cnn: for k < T the recurrent act on slot k at row k, then the ordinary step; then the closing value-only act.  Two
+ *     rollouts of T with the states carried equal one of 2 T, bit for bit (T a multiple of L).
+ *   mrl_mappo_update with the bit in policy->flags: `batch` is read as an mrl_mappo_gru_batch.  The unit of a minibatch is a CHUNK:
+ *     c = j (N P) + cell, j < T / L, covers samples s_i = (j L + i) N P + cell, i < L.  `indices` is (K, Bc) chunk ids and
+ *     minibatch_size = Bc; every mean of the losses runs over the Bc L samples of the row.  Per chunk the forward pass starts from
+ *     h0_*[c] and applies m_i = 1 - dones[s_i] at every step, so on unchanged parameters the recomputed log-probs and values are
+ *     the record's bit for bit.  Launch plan: one launch that writes every row's sample numbers and the ValueNorm recurrence up
+ *     front (with MRL_MAPPO_VALUENORM), then three per row as for mrl_mappo_update.  The gradient kernel takes 32 chunks per tile
+ *     in three phases that never hold the GRU's arrays together with the activation image or the int8 rows: a forward sweep
+ *     (CNNBase and the GRU per step; x_i and the step's incoming state go to the workgroup's own slice of the workspace), a
+ *     recurrent phase from i = L - 1 down to 0 (GRU, LayerNorm, head, loss head and their backward pass; dL/dx_i replaces x_i in
+ *     the slice) and a convolutional phase (CNNBase again, then mrl_mappo_update's backward path from fc2 down to the
+ *     convolution).  A workgroup's partial vector is summed in ONE order: tiles ascending; within a tile the GRU's and the head's
+ *     terms by steps descending and CNNBase's by steps ascending; within a step the samples ascending.  No float atomics, no wait
+ *     on another workgroup; the same inputs give the same bits; a call of K rows gives the bits of K calls of one row.
+ *     1 <= L <= MRL_CNN_GRU_MAX_CHUNK = 16.  mrl_mappo_workspace_bytes(W, H, F, 64 | MRL_CNN_GRU_HIDDEN, Bc, K, &bytes) sizes the
+ *     workspace, for any L up to the maximum.
+ *   Refusals (MRL_ERR_INVALID, nothing changed) beyond the plain calls': a NULL h_actor or h_critic, or one off a 4-byte boundary;
+ *     with a record chunk_length == 0, num_steps % chunk_length != 0, a NULL h0_actor or h0_critic or one off a 4-byte boundary;
+ *     in the update a NULL h0_actor, h0_critic or dones, or one off a 4-byte boundary, chunk_length 0 or above the maximum,
+ *     base.size not a multiple of chunk_length * num_worlds * num_players, minibatch_size above the batch's number of chunks.
+ *     mrl_cnn_act_bank, mrl_rollout_cnn_bank and mrl_mappo_bank_update refuse the bit.
+ *   Not built: banks, population training and cross-play of recurrent policies, recurrent_N > 1, use_naive_recurrent_policy,
+ *     hidden_size other than 64. */
+enum { MRL_CNN_RECURRENT = 16 };      /* bit of mrl_cnn_policy.flags and mrl_mappo_policy.flags */
+enum { MRL_CNN_GRU_HIDDEN = 0x100 };  /* or-ed into `hidden` in the two size queries: the recurrent shape */
+enum { MRL_CNN_GRU_MAX_CHUNK = 16 };  /* the longest chunk mrl_mappo_update back-propagates through */
+typedef struct mrl_cnn_gru_policy {
+    mrl_cnn_policy base;        /* base.flags has MRL_CNN_RECURRENT; base.params_dev is the recurrent flat tensor */
+    float *h_actor, *h_critic;  /* (N, P, 64) */
+} mrl_cnn_gru_policy;
+typedef struct mrl_cnn_gru_record {
+    mrl_cnn_record base;
+    float *h0_actor, *h0_critic; /* (T / L, N, P, 64) */
+    uint32_t chunk_length;       /* L */
+} mrl_cnn_gru_record;
+typedef struct mrl_mappo_gru_policy {
+    mrl_mappo_policy base;       /* base.flags has MRL_CNN_RECURRENT */
+} mrl_mappo_gru_policy;
+typedef struct mrl_mappo_gru_batch {
+    mrl_mappo_batch base;                          /* as for mrl_mappo_update; base.size = S = T N P */
+    const float *h0_actor, *h0_critic, *dones;     /* the record's: (T / L, N, P, 64) twice and (T, N, P) */
+    uint32_t chunk_length, num_worlds, num_players; /* L, N, P */
+} mrl_mappo_gru_batch;
 
 /* MAPPO's MLP actor-critic for the balance beam on the device: what the reference's trainer runs in torch for `balance`
  * (train/trainer.py, train/env_utils.py:8-26; R_Actor / R_Critic pick MLPBase for a vector observation, train/MAPPO/

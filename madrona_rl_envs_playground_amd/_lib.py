@@ -36,6 +36,9 @@ CNN_VALUE_ONLY = 4  # MRL_CNN_VALUE_ONLY: flag of mrl_cnn_act beside POLICY_GREE
 CNN_HIDDEN, CNN_ACTIONS = 64, 6  # the one shape mrl_cnn_act runs
 CNN_BANK_MAX_POLICIES = 256  # the rows an mrl_cnn_bank may hold
 CNN_RESAMPLE_ROBIN, CNN_RESAMPLE_RANDOM = 1, 2  # MRL_CNN_RESAMPLE_*
+CNN_RECURRENT = 16  # MRL_CNN_RECURRENT: bit of mrl_cnn_policy.flags and mrl_mappo_policy.flags; the structs are then the mrl_*_gru_* ones
+CNN_GRU_HIDDEN = 0x100  # MRL_CNN_GRU_HIDDEN: or-ed into hidden in the size queries for the recurrent shape
+CNN_GRU_MAX_CHUNK = 16  # MRL_CNN_GRU_MAX_CHUNK: the longest chunk mrl_mappo_update back-propagates through
 MLPBASE_VALUE_ONLY = 4  # MRL_MLPBASE_VALUE_ONLY: flag of mrl_mlpbase_act beside POLICY_GREEDY
 MLPBASE_HIDDEN, MLPBASE_OBS, MLPBASE_ACTIONS = 64, 7, 4  # the one shape mrl_mlpbase_act runs (layer_N 1 or 2)
 MLPBASE_RECURRENT = 16  # MRL_MLPBASE_RECURRENT: bit of mrl_mlpbase_policy.flags; the policy is then an mrl_mlpbase_gru_policy
@@ -217,6 +220,28 @@ class MappoMlpGruBatch(ctypes.Structure):  # mrl_mappo_mlp_gru_batch
     _extends_ = MappoMlpBatch
     _fields_ = [("base", MappoMlpBatch), ("h0_actor", ctypes.c_void_p), ("h0_critic", ctypes.c_void_p), ("dones", ctypes.c_void_p),
                 ("chunk_length", ctypes.c_uint32), ("num_worlds", ctypes.c_uint32), ("num_seats", ctypes.c_uint32)]
+
+
+# The recurrent CNN's structs, likewise
+class CnnGruPolicyDesc(ctypes.Structure):  # mrl_cnn_gru_policy
+    _extends_ = CnnPolicyDesc
+    _fields_ = [("base", CnnPolicyDesc), ("h_actor", ctypes.c_void_p), ("h_critic", ctypes.c_void_p)]
+
+
+class CnnGruRecordDesc(ctypes.Structure):  # mrl_cnn_gru_record
+    _extends_ = CnnRecordDesc
+    _fields_ = [("base", CnnRecordDesc), ("h0_actor", ctypes.c_void_p), ("h0_critic", ctypes.c_void_p), ("chunk_length", ctypes.c_uint32)]
+
+
+class MappoGruPolicyDesc(ctypes.Structure):  # mrl_mappo_gru_policy
+    _extends_ = MappoPolicyDesc
+    _fields_ = [("base", MappoPolicyDesc)]
+
+
+class MappoGruBatch(ctypes.Structure):  # mrl_mappo_gru_batch
+    _extends_ = MappoBatch
+    _fields_ = [("base", MappoBatch), ("h0_actor", ctypes.c_void_p), ("h0_critic", ctypes.c_void_p), ("dones", ctypes.c_void_p),
+                ("chunk_length", ctypes.c_uint32), ("num_worlds", ctypes.c_uint32), ("num_players", ctypes.c_uint32)]
 
 
 def base_ref(struct):

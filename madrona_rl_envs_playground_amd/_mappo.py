@@ -13,7 +13,7 @@ import torch
 from . import _lib
 from ._bank import _PolicyBank, _bank_resample, _bank_rollout_buffers, _bank_workspace, _check_bank_rollout
 from ._device import _check_ids, _require_tensors, _seat_mask, _stream_ptr
-from ._mappo_nets import CnnActorCritic, MlpBaseActorCritic, MlpBaseGruActorCritic
+from ._mappo_nets import CnnActorCritic, CnnGruActorCritic, MlpBaseActorCritic, MlpBaseGruActorCritic
 from ._ppo import Rollout, _AdamState, _aliased, _run_update, gae, minibatch_indices
 
 
@@ -291,8 +291,8 @@ class MlpBaseGruPolicy(MlpBasePolicy):
                           ("state.critic", state.critic, torch.float32, worlds * seats * self.hidden)], self.params.device)
         if tuple(state.actor.shape) != (worlds, seats, self.hidden) or tuple(state.critic.shape) != (worlds, seats, self.hidden):
             raise ValueError(f"the bound state must hold ({worlds}, {seats}, {self.hidden}) rows per net")
-        if record is not None and not isinstance(record, MlpBaseGruRecord):
-            raise ValueError("a recurrent policy's record must be an MlpBaseGruRecord")
+        if record is not None and not isinstance(record, self._record_class):
+            raise ValueError(f"a recurrent policy's record must be {'an' if self._record_class is MlpBaseGruRecord else 'a'} {self._record_class.__name__}")
 
     # what MappoOptimizer and mappo_update ask of a policy
     def _mappo_workspace_bytes(self, minibatch_size, num_minibatches, out, members=None):
@@ -350,14 +350,107 @@ class MlpBaseGruRecord(MlpBaseRecord):
 
 
 MlpBaseGruPolicy._record_class = MlpBaseGruRecord
+GruState = MlpBaseGruState  # the running states of either recurrent policy: (N, P, 64) per net
+
+
+class CnnGruPolicy(CnnPolicy):
+    """The parameters and the running state ``mrl_cnn_act`` runs for the RECURRENT CNN actor-critic of the kitchens
+    (``mrl_cnn_gru_policy``, ``MRL_CNN_RECURRENT``): ``params`` is the flat tensor of
+    ``parameters_to_vector(CnnGruActorCritic.parameters())`` -- per net ``base.*`` as in ``CnnPolicy``, then the GRU's four tensors
+    and its LayerNorm, then the head: 25 088 floats more per net.  ``module()`` returns a ``CnnGruActorCritic`` over VIEWS of
+    ``params``.  ``state(num_worlds, num_players=2)`` makes a zeroed ``GruState`` and BINDS it: ``cnn_act``, ``rollout_cnn`` and the
+    env's ``act`` / ``rollout``, whose signatures are the plain policy's, run on the bound state ``running`` (``bind(state)``
+    switches to another one), exactly as for ``MlpBaseGruPolicy``: callers that share one policy must each bind their own state
+    before each of their calls.  The banks and ``mappo_update_bank`` do not take a recurrent policy."""
+
+    _module_class, _module_name = CnnGruActorCritic, "a CnnGruActorCritic"
+    _desc_flags = _lib.CNN_RECURRENT  # the bit every descriptor of this kind of policy carries, a rollout's included
+
+    def __init__(self, width, height, channels, hidden=64, num_actions=6, device="cuda:0"):
+        self.running = None
+        super().__init__(width, height, channels, hidden, num_actions, device)
+
+    @property
+    def num_params(self):
+        return int(_lib.lib().mrl_cnn_policy_num_params(self.width, self.height, self.channels, self.hidden | _lib.CNN_GRU_HIDDEN, self.num_actions))
+
+    def state(self, num_worlds, num_players=2):
+        """A zeroed ``GruState`` of (``num_worlds``, ``num_players``, 64) rows per net on the parameters' device, bound as ``running``."""
+        return self.bind(GruState(num_worlds, self.params.device, num_players, self.hidden))
+
+    def bind(self, state):
+        if not isinstance(state, GruState):
+            raise ValueError("state must be a GruState")
+        self.running = state
+        return state
+
+    def desc(self):
+        state = self.running
+        if state is None:
+            raise ValueError("a recurrent policy acts on a bound state: call policy.state(num_worlds, num_players) or policy.bind(state) first")
+        plain = _lib.CnnPolicyDesc(self.params.data_ptr(), self.hidden, self._desc_flags)
+        return _lib.CnnGruPolicyDesc(plain, state.actor.data_ptr(), state.critic.data_ptr())
+
+    _act_check = MlpBaseGruPolicy._act_check
+
+    # what MappoOptimizer and mappo_update ask of a policy
+    def _mappo_workspace_bytes(self, minibatch_size, num_minibatches, out, members=None):
+        if members is not None:
+            raise ValueError("mappo_update_bank does not take a recurrent policy")
+        return _lib.lib().mrl_mappo_workspace_bytes(self.width, self.height, self.channels, self.hidden | _lib.CNN_GRU_HIDDEN, minibatch_size,
+                                                    num_minibatches, out)
+
+    def _mappo_check(self, record, ring):
+        if not isinstance(record, CnnGruRecord):
+            raise ValueError("record must be a CnnGruRecord")
+
+    def _mappo_batch(self, record, ring, count):
+        """-> ((entry point, None), policy struct, the batch struct's maker, the batch's observations).  ``indices`` are CHUNK ids
+        (``chunk_indices``); the policy struct carries no state: the update starts every chunk from the record's ``h0``."""
+        _, _, _, obs = super()._mappo_batch(record, ring, count)
+        cells = record.num_worlds * record.num_players * self.hidden
+        chunks = record.num_steps // record.chunk_length
+        _require_tensors([("record.dones", record.dones, torch.float32, count), ("record.h0_actor", record.h0_actor, torch.float32, chunks * cells),
+                          ("record.h0_critic", record.h0_critic, torch.float32, chunks * cells)], self.params.device)
+        shape = _lib.MappoGruPolicyDesc(_lib.MappoPolicyDesc(self.params.data_ptr(), self.hidden, _lib.CNN_RECURRENT, self.width, self.height,
+                                                             self.channels))
+
+        def batch(*plain_fields):
+            return _lib.MappoGruBatch(_lib.MappoBatch(*plain_fields), record.h0_actor.data_ptr(), record.h0_critic.data_ptr(),
+                                      record.dones.data_ptr(), record.chunk_length, record.num_worlds, record.num_players)
+
+        return (_lib.lib().mrl_mappo_update, None), shape, batch, obs
+
+
+class CnnGruRecord(CnnRecord):
+    """The buffers of a recurrent act or rollout in a kitchen (``mrl_cnn_gru_record``): ``CnnRecord``'s and, for chunks of
+    ``chunk_length`` = L steps (the reference's ``data_chunk_length``, default 10; it must divide ``num_steps``), ``h0_actor`` and
+    ``h0_critic`` float32 (T / L, N, P, 64): row j holds the states the act at row j L came in with, before its mask -- where the
+    update's chunk j starts."""
+
+    def __init__(self, num_steps, num_worlds, num_players, device, chunk_length=10, logits=False):
+        self.chunk_length = int(chunk_length)
+        if self.chunk_length < 1 or int(num_steps) % self.chunk_length:
+            raise ValueError(f"chunk_length {chunk_length} must be at least 1 and divide num_steps {num_steps}")
+        super().__init__(num_steps, num_worlds, num_players, device, logits)
+        self.struct = _lib.CnnGruRecordDesc(self.struct, self.h0_actor.data_ptr(), self.h0_critic.data_ptr(), self.chunk_length)
+
+    def _own_buffers(self, z, t, n, p):
+        self.h0_actor = z((t // self.chunk_length, n, p, _lib.CNN_HIDDEN))
+        self.h0_critic = z((t // self.chunk_length, n, p, _lib.CNN_HIDDEN))
+
+    num_chunks = MlpBaseGruRecord.num_chunks
+
+
+CnnGruPolicy._record_class = CnnGruRecord
 
 
 def chunk_indices(record, num_mini_batch, epochs, generator=None, device="cpu"):
     """The rows ``mappo_update`` takes for a recurrent policy, (epochs * num_mini_batch, Bc) int32 CHUNK ids on ``device``: every
     epoch is one permutation of the record's (T / L) N P chunks cut into ``num_mini_batch`` rows, as ``recurrent_generator`` draws
     it (utils/shared_buffer.py; chunk c = (j N + n) P + p covers rows j L .. j L + L - 1 of world n, seat p)."""
-    if not isinstance(record, MlpBaseGruRecord):
-        raise ValueError("record must be an MlpBaseGruRecord")
+    if not isinstance(record, (MlpBaseGruRecord, CnnGruRecord)):
+        raise ValueError("record must be an MlpBaseGruRecord or a CnnGruRecord")
     return minibatch_indices(record.num_chunks, num_mini_batch, epochs, generator, device)
 
 
@@ -833,9 +926,11 @@ def mappo_update(policy, optimizer, record, ring, advantages, returns, indices, 
     For an ``MlpBaseGruPolicy`` (the recurrent actor-critic) ``record`` is an ``MlpBaseGruRecord`` and ``indices`` (K, Bc) are CHUNK
     ids (``chunk_indices``): every mean runs over the Bc L samples of the row's chunks, each chunk's forward pass starts from the
     record's ``h0`` and applies ``1 - record.dones`` at every step, and the gradient goes back through the chunk's L steps.
+    For a ``CnnGruPolicy`` (the kitchens' recurrent actor-critic) ``record`` is a ``CnnGruRecord``, ``ring`` its rollout's ring and
+    ``indices`` are chunk ids in the same way.
     Not built: active masks, PopArt, ``update_actor=False``, weight decay."""
     if not isinstance(policy, (CnnPolicy, MlpBasePolicy)) or not isinstance(optimizer, MappoOptimizer) or optimizer.policy is not policy:
-        raise ValueError("policy must be a CnnPolicy or an MlpBasePolicy and optimizer the MappoOptimizer made for it")
+        raise ValueError("policy must be a CnnPolicy or an MlpBasePolicy (plain or recurrent) and optimizer the MappoOptimizer made for it")
     policy._mappo_check(record, ring)  # the record is the policy's kind, and so is the ring
     if value_norm is not None and not isinstance(value_norm, ValueNorm):
         raise ValueError("value_norm must be a ValueNorm or None")

@@ -215,6 +215,71 @@ class _RnnLayer(torch.nn.Module):
         return self.norm(torch.cat(outs, dim=0)), h
 
 
+class _CnnGruActor(torch.nn.Module):
+    """``R_Actor``'s parameters by name for the CNN with ``use_recurrent_policy``: ``base.cnn.cnn.0/3/5``, ``rnn.rnn.*_l0``, ``rnn.norm``,
+    ``act.action_out.linear``"""
+
+    def __init__(self, width, height, channels, hidden, num_actions):
+        super().__init__()
+        self.base = _CnnBase(width, height, channels, hidden)
+        self.rnn = _RnnLayer(hidden)
+        self.act = _ActLayer(hidden, num_actions)
+
+    def forward(self, obs, h, mask):
+        features, h = self.rnn(self.base(obs), h, mask)
+        return self.act.action_out.linear(features), h
+
+    def chunk(self, obs, h0, masks):
+        """obs (L, n, W, H, F), h0 (n, hidden), masks (L, n) -> (logits (L, n, actions), h_L)"""
+        x = self.base(obs.reshape((-1,) + tuple(obs.shape[2:]))).reshape(obs.shape[0], obs.shape[1], -1)
+        features, h = self.rnn.chunk(x, h0, masks)
+        return self.act.action_out.linear(features), h
+
+
+class _CnnGruCritic(torch.nn.Module):
+    """``R_Critic``'s parameters by name for the CNN with ``use_recurrent_policy``, without PopArt: ``base...``, ``rnn...``, ``v_out``"""
+
+    def __init__(self, width, height, channels, hidden):
+        super().__init__()
+        self.base = _CnnBase(width, height, channels, hidden)
+        self.rnn = _RnnLayer(hidden)
+        self.v_out = torch.nn.Linear(hidden, 1)
+
+    def forward(self, state, h, mask):
+        features, h = self.rnn(self.base(state), h, mask)
+        return self.v_out(features), h
+
+    def chunk(self, state, h0, masks):
+        """state (L, n, W, H, F), h0 (n, hidden), masks (L, n) -> (values (L, n, 1), h_L)"""
+        x = self.base(state.reshape((-1,) + tuple(state.shape[2:]))).reshape(state.shape[0], state.shape[1], -1)
+        features, h = self.rnn.chunk(x, h0, masks)
+        return self.v_out(features), h
+
+
+class CnnGruActorCritic(torch.nn.Module):
+    """MAPPO's RECURRENT CNN actor-critic for the two kitchens (r_actor_critic.py with ``use_recurrent_policy``, utils/rnn.py with
+    ``recurrent_N`` 1): ``CnnActorCritic`` with an ``RNNLayer`` -- one GRU layer of width ``hidden`` and a LayerNorm -- between
+    ``CNNBase`` and the head of both nets.  ``actor(obs, h, mask)`` / ``critic(obs, h, mask)`` take the (n, W, H, F) observation as
+    floats, the (n, hidden) state and the (n) mask (0 where the episode has just ended) and return (logits or value, new state);
+    ``.chunk`` runs L steps.  The state dicts have the reference's keys (``base.cnn.cnn.0`` ... ``rnn.rnn.weight_ih_l0`` ...
+    ``rnn.norm.bias``), so ``actor.load_state_dict`` / ``critic.load_state_dict`` take a reference checkpoint trained with
+    ``--use_recurrent_policy``.  Initialisation is the reference's: the GRU's weights orthogonal and its biases zero (rnn.py:14-21),
+    the rest as ``CnnActorCritic``."""
+
+    def __init__(self, width, height, channels, hidden=64, num_actions=6):
+        super().__init__()
+        self.width, self.height, self.channels, self.hidden, self.num_actions = int(width), int(height), int(channels), int(hidden), int(num_actions)
+        self.actor = _CnnGruActor(self.width, self.height, self.channels, self.hidden, self.num_actions)
+        self.critic = _CnnGruCritic(self.width, self.height, self.channels, self.hidden)
+        relu_gain = torch.nn.init.calculate_gain("relu")
+        for net, head, head_gain in ((self.actor, self.actor.act.action_out.linear, 0.01), (self.critic, self.critic.v_out, 1.0)):
+            for i in (0, 3, 5):
+                torch.nn.init.orthogonal_(net.base.cnn.cnn[i].weight, gain=relu_gain)
+                torch.nn.init.constant_(net.base.cnn.cnn[i].bias, 0.0)
+            torch.nn.init.orthogonal_(head.weight, gain=head_gain)
+            torch.nn.init.constant_(head.bias, 0.0)
+
+
 class _MlpBaseGruActor(torch.nn.Module):
     """``R_Actor``'s parameters by name for a vector observation with ``use_recurrent_policy``: ``base...``, ``rnn.rnn.weight_ih_l0``,
     ``weight_hh_l0``, ``bias_ih_l0``, ``bias_hh_l0``, ``rnn.norm``, ``act.action_out.linear``"""

@@ -5,6 +5,7 @@
 #include "capi_internal.hpp"
 #include "cnn_policy.hpp"
 #include "cnn_bank.hpp"
+#include "cnn_gru.hpp"
 #include "cnn_update.hpp"
 #include "mlpbase_policy.hpp"
 #include "mlpbase_bank.hpp"
@@ -418,6 +419,26 @@ struct MlpBaseGruNet : MlpBaseNet {
     }
 };
 
+// The recurrent CNN as the update sees it (mrl_mappo_update with MRL_CNN_RECURRENT): CnnNet's refusals on the structs the extended
+// ones begin with -- the recurrent image admits every kitchen the plain one does (cnn_gru.hpp) --; the rows are chunk ids, the
+// workspace and the launch the recurrent update's.
+struct CnnGruNet : CnnNet {
+    static uint64_t actor_params(const UpdatePolicy &p) { return cnn_gru_net_params(p.width, p.height, p.channels, kCnnActions); }
+    static uint64_t num_params(const UpdatePolicy &p) { return actor_params(p) + cnn_gru_net_params(p.width, p.height, p.channels, 1); }
+    static uint64_t workspace_floats(const UpdatePolicy &p, uint32_t Bc, uint32_t K)
+    {
+        return cnn_gru_update_workspace(p.width, p.height, p.channels, Bc, K).total;
+    }
+    // `batch` is the first member of the mrl_mappo_gru_batch that cnn_gru_update checked
+    static void launch_update(const UpdatePolicy &p, const mrl_mappo_optimizer &opt, const Batch &batch, const int32_t *indices, uint32_t K,
+                              uint32_t Bc, const mrl_mappo_config &cfg, float *value_norm_state, float *workspace, float *stats, float *grads,
+                              hipStream_t stream, const MappoMembers &)
+    {
+        launch_mappo_cnn_gru_update(p, opt, reinterpret_cast<const mrl_mappo_gru_batch &>(batch), indices, K, Bc, cfg, value_norm_state, workspace,
+                                    stats, grads, stream);
+    }
+};
+
 // ---- act and rollout, plain and over a bank ----
 
 // `why`, a check's verdict, refuses the call `what` unless it is nullptr
@@ -574,6 +595,81 @@ static int gru_rollout(const char *what, mrl_sim *sim, uint32_t players, const m
     });
 }
 
+// ---- the recurrent CNN: mrl_cnn_act and mrl_rollout_cnn with MRL_CNN_RECURRENT in the policy's flags ----
+
+// the states of a recurrent policy and the h0 arrays and chunk length of a recurrent record (either network's), or why not
+template <class Policy, class Record>
+static const char *gru_arrays_error(const Policy *policy, const Record *record)
+{
+    if (!policy->h_actor || !policy->h_critic || ((reinterpret_cast<uintptr_t>(policy->h_actor) | reinterpret_cast<uintptr_t>(policy->h_critic)) & 3u))
+        return "a recurrent policy needs h_actor and h_critic, each on a 4-byte boundary";
+    if (!record) return nullptr;
+    if (record->chunk_length == 0 || record->base.num_steps % record->chunk_length != 0)
+        return "a recurrent record needs chunk_length >= 1 that divides num_steps";
+    if (!record->h0_actor || !record->h0_critic ||
+        ((reinterpret_cast<uintptr_t>(record->h0_actor) | reinterpret_cast<uintptr_t>(record->h0_critic)) & 3u))
+        return "a recurrent record needs h0_actor and h0_critic, each on a 4-byte boundary";
+    return nullptr;
+}
+
+// Everything the recurrent act and rollout check alike: mrl_cnn_act's own checks on the base structs (the bit taken out: to every
+// other caller of cnn_prepare, the banks included, it stays an unknown policy flag), then the state and h0 arrays.
+static int cnn_gru_prepare(mrl_sim *sim, uint32_t players, const mrl_cnn_gru_policy *policy, const mrl_cnn_gru_record *record, void *hip_stream,
+                           const char *what, CnnGruActArgs *args, mrl_cnn_policy *plain)
+{
+    *plain = policy->base;
+    plain->flags &= ~(uint32_t)MRL_CNN_RECURRENT;
+    if (int rc = cnn_prepare(sim, players, plain, record ? &record->base : nullptr, hip_stream, what, &args->act)) return rc;
+    if (int rc = refusal(what, gru_arrays_error(policy, record))) return rc;
+    args->h[0] = policy->h_actor, args->h[1] = policy->h_critic;
+    return MRL_OK;
+}
+
+// what a recurrent act fills behind the checks: the plain act's slot, rows, seed, step and flags, then the h0 rows and the write-back
+static void cnn_gru_fill(CnnGruActArgs &g, mrl_sim *sim, const char *what, const int8_t *slot, const mrl_cnn_gru_record *record, uint32_t row,
+                         uint64_t seed, uint32_t step, uint32_t flags)
+{
+    const bool value_only = flags & MRL_CNN_VALUE_ONLY;
+    fill<CnnNet>(g.act, sim, what, slot, record ? &record->base : nullptr, row, seed, step, flags);
+    g.write_state = value_only ? 0u : 1u;
+    g.h0_row[0] = g.h0_row[1] = nullptr;
+    if (record && !value_only && row % record->chunk_length == 0) {
+        const size_t at = (size_t)(row / record->chunk_length) * g.act.num_worlds * g.act.P * kCnnHidden;
+        g.h0_row[0] = record->h0_actor + at, g.h0_row[1] = record->h0_critic + at;
+    }
+}
+
+static int cnn_gru_act(const char *what, mrl_sim *sim, uint32_t players, const mrl_cnn_gru_policy *policy, const mrl_cnn_gru_record *record,
+                       uint32_t row, uint64_t seed, uint32_t step, uint32_t flags, void *workspace_dev, uint64_t workspace_bytes, void *hip_stream)
+{
+    CnnGruActArgs args{};
+    mrl_cnn_policy plain{};
+    if (int rc = cnn_gru_prepare(sim, players, policy, record, hip_stream, what, &args, &plain)) return rc;
+    if (int rc = act_row_refusal(what, CnnNet::kValueOnly, flags, plain.flags, record ? &record->base : nullptr, row)) return rc;
+    if (int rc = refusal(what, CnnNet::workspace_error(args.act, workspace_dev, workspace_bytes))) return rc;
+    DeviceGuard on(sim->device);
+    return guarded([&] {
+        cnn_gru_fill(args, sim, what, nullptr, record, row, seed, step, flags);
+        launch_cnn_gru_act(args, (hipStream_t)hip_stream);
+    });
+}
+
+static int cnn_gru_rollout(const char *what, mrl_sim *sim, uint32_t players, const mrl_cnn_gru_policy *policy, const mrl_cnn_gru_record *record,
+                           void *obs_ring_dev, uint64_t seed, uint32_t first_step, void *hip_stream)
+{
+    CnnGruActArgs args{};
+    mrl_cnn_policy plain{};
+    if (int rc = cnn_gru_prepare(sim, players, policy, record, hip_stream, what, &args, &plain)) return rc;
+    if (int rc = refusal(what, CnnNet::rollout_lacks(record ? &record->base : nullptr, obs_ring_dev))) return rc;
+    return CnnNet::loop(
+        sim, what, record->base.num_steps, obs_ring_dev, hip_stream,
+        [&](uint32_t k, const int8_t *slot, bool closing) {
+            cnn_gru_fill(args, sim, what, slot, record, k, seed, first_step + k, plain.flags | (closing ? (uint32_t)MRL_CNN_VALUE_ONLY : 0u));
+            launch_cnn_gru_act(args, (hipStream_t)hip_stream);
+        },
+        [] {});
+}
+
 template <class Net>
 static int rollout_bank(const char *what, mrl_sim *sim, uint32_t players, const typename Net::Bank *bank, int32_t *ids_dev, int32_t *episodes_dev,
                         const mrl_cnn_resample *resample, const typename Net::Record *record, int32_t *ids_record, void *obs_ring_dev,
@@ -703,6 +799,38 @@ static int gru_update(const char *what, const mrl_mlpbase_gru_policy *policy, co
                                        grads_dev_or_null, gpu_id, hip_stream);
 }
 
+// mrl_mappo_update with MRL_CNN_RECURRENT: what the extended batch adds is checked here (the beam's refusals), the rest by
+// mappo_update on the structs the extended ones begin with
+static int cnn_gru_update(const char *what, const mrl_mappo_policy *policy, const mrl_mappo_optimizer *opt, const mrl_mappo_gru_batch *batch,
+                          const int32_t *indices_dev, uint32_t num_minibatches, uint32_t minibatch_size, const mrl_mappo_config *cfg,
+                          float *value_norm_state, void *workspace_dev, uint64_t workspace_bytes, float *stats_dev_or_null, float *grads_dev_or_null,
+                          int gpu_id, void *hip_stream)
+{
+    if (batch) {
+        const uintptr_t low_bits = reinterpret_cast<uintptr_t>(batch->h0_actor) | reinterpret_cast<uintptr_t>(batch->h0_critic) |
+                                   reinterpret_cast<uintptr_t>(batch->dones);
+        if (!batch->h0_actor || !batch->h0_critic || !batch->dones || (low_bits & 3u))
+            return refusal(what, "a recurrent batch needs h0_actor, h0_critic and dones, each on a 4-byte boundary");
+        if (batch->chunk_length == 0 || batch->chunk_length > kCnnGruMaxChunk) {
+            set_error("%s: chunk_length %u: the update runs chunks of 1 to %u steps", what, batch->chunk_length, kCnnGruMaxChunk);
+            return MRL_ERR_INVALID;
+        }
+        const uint64_t row = (uint64_t)batch->chunk_length * batch->num_worlds * batch->num_players;
+        if (row == 0 || batch->base.size % row != 0) {
+            set_error("%s: a batch of %u samples is not a whole number of rows of %u-step chunks of %u worlds and %u players", what,
+                      batch->base.size, batch->chunk_length, batch->num_worlds, batch->num_players);
+            return MRL_ERR_INVALID;
+        }
+        if (minibatch_size > batch->base.size / batch->chunk_length) {  // (so that Bc L, a row's samples, is at most the batch's size)
+            set_error("%s: minibatch_size %u: a row holds chunk ids, and the batch has %u chunks", what, minibatch_size,
+                      batch->base.size / batch->chunk_length);
+            return MRL_ERR_INVALID;
+        }
+    }
+    return mappo_update<CnnGruNet>(what, policy, opt, batch ? &batch->base : nullptr, indices_dev, num_minibatches, minibatch_size, cfg,
+                                   value_norm_state, workspace_dev, workspace_bytes, stats_dev_or_null, grads_dev_or_null, gpu_id, hip_stream);
+}
+
 // mrl_mappo_bank_workspace_bytes and mrl_mappo_mlp_bank_workspace_bytes (`what`): the plain update's workspace, once per member
 template <class Net>
 static int bank_workspace_bytes(const char *what, uint32_t s0, uint32_t s1, uint32_t s2, uint32_t s3, uint32_t minibatch_size,
@@ -726,8 +854,11 @@ extern "C" {
 
 uint64_t mrl_cnn_policy_num_params(uint32_t width, uint32_t height, uint32_t channels, uint32_t hidden, uint32_t num_actions)
 {
+    // the recurrent shape: hidden | MRL_CNN_GRU_HIDDEN
+    const uint64_t gru = hidden == (mrl::kCnnHidden | MRL_CNN_GRU_HIDDEN) ? 2 * mrl::kGruParams : 0;
+    if (gru) hidden = mrl::kCnnHidden;
     if (hidden != mrl::kCnnHidden || num_actions != mrl::kCnnActions || width < 3 || height < 3 || channels == 0) return 0;
-    return mrl::cnn_net_params(width, height, channels, num_actions) + mrl::cnn_net_params(width, height, channels, 1);
+    return mrl::cnn_net_params(width, height, channels, num_actions) + mrl::cnn_net_params(width, height, channels, 1) + gru;
 }
 
 uint64_t mrl_cnn_workspace_bytes(uint32_t num_worlds, uint32_t num_players) { return mrl::kCnnWorkspaceBytes; }
@@ -758,7 +889,13 @@ uint64_t mrl_mlpbase_bank_workspace_bytes(uint32_t num_worlds, uint32_t num_poli
 int mrl_mappo_workspace_bytes(uint32_t width, uint32_t height, uint32_t channels, uint32_t hidden, uint32_t minibatch_size,
                               uint32_t num_minibatches, uint64_t *out)
 {
-    const char *why = out ? mappo_shape_error(width, height, channels, hidden, minibatch_size) : "null output pointer";
+    // the recurrent shape: hidden | MRL_CNN_GRU_HIDDEN
+    const bool recurrent = hidden == (mrl::kCnnHidden | MRL_CNN_GRU_HIDDEN);
+    const char *why = out ? mappo_shape_error(width, height, channels, recurrent ? mrl::kCnnHidden : hidden, minibatch_size) : "null output pointer";
+    if (!why && recurrent) {
+        *out = mrl::cnn_gru_update_workspace(width, height, channels, minibatch_size, num_minibatches).total * sizeof(float);
+        return MRL_OK;
+    }
     if (why) {
         mrl::set_error("mrl_mappo_workspace_bytes: %s (width %u, height %u, channels %u, hidden %u, minibatch_size %u)", why, width, height,
                        channels, hidden, minibatch_size);
@@ -791,6 +928,10 @@ int mrl_mappo_mlp_workspace_bytes(uint32_t obs_dim, uint32_t hidden, uint32_t la
 int mrl_cnn_act(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, const mrl_cnn_record *record, uint32_t row, uint64_t seed,
                 uint32_t step, uint32_t flags, void *workspace_dev, uint64_t workspace_bytes, void *hip_stream)
 {
+    if (policy && (policy->flags & MRL_CNN_RECURRENT))
+        return mrl::cnn_gru_act("mrl_cnn_act", sim, players, reinterpret_cast<const mrl_cnn_gru_policy *>(policy),
+                                reinterpret_cast<const mrl_cnn_gru_record *>(record), row, seed, step, flags, workspace_dev, workspace_bytes,
+                                hip_stream);
     return mrl::act<CnnNet>("mrl_cnn_act", sim, players, policy, record, row, seed, step, flags, workspace_dev, workspace_bytes, hip_stream);
 }
 
@@ -822,6 +963,9 @@ int mrl_mlpbase_act_bank(mrl_sim *sim, uint32_t players, const mrl_mlpbase_bank 
 int mrl_rollout_cnn(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, const mrl_cnn_record *record, void *obs_ring_dev,
                     uint64_t seed, uint32_t first_step, void *hip_stream)
 {
+    if (policy && (policy->flags & MRL_CNN_RECURRENT))
+        return mrl::cnn_gru_rollout("mrl_rollout_cnn", sim, players, reinterpret_cast<const mrl_cnn_gru_policy *>(policy),
+                                    reinterpret_cast<const mrl_cnn_gru_record *>(record), obs_ring_dev, seed, first_step, hip_stream);
     return mrl::rollout<CnnNet>("mrl_rollout_cnn", sim, players, policy, record, obs_ring_dev, seed, first_step, hip_stream);
 }
 
@@ -866,6 +1010,10 @@ int mrl_mappo_update(const mrl_mappo_policy *policy, const mrl_mappo_optimizer *
                      uint32_t num_minibatches, uint32_t minibatch_size, const mrl_mappo_config *cfg, float *value_norm_state, void *workspace_dev,
                      uint64_t workspace_bytes, float *stats_dev_or_null, float *grads_dev_or_null, int gpu_id, void *hip_stream)
 {
+    if (policy && (policy->flags & MRL_CNN_RECURRENT))
+        return mrl::cnn_gru_update("mrl_mappo_update", policy, opt, reinterpret_cast<const mrl_mappo_gru_batch *>(batch), indices_dev,
+                                   num_minibatches, minibatch_size, cfg, value_norm_state, workspace_dev, workspace_bytes, stats_dev_or_null,
+                                   grads_dev_or_null, gpu_id, hip_stream);
     return mrl::mappo_update<CnnNet>("mrl_mappo_update", policy, opt, batch, indices_dev, num_minibatches, minibatch_size, cfg, value_norm_state,
                                      workspace_dev, workspace_bytes, stats_dev_or_null, grads_dev_or_null, gpu_id, hip_stream);
 }
@@ -874,6 +1022,8 @@ int mrl_mappo_bank_update(const mrl_mappo_policy *policy, const mrl_mappo_bank_o
                           uint32_t num_minibatches, uint32_t minibatch_size, const mrl_mappo_config *cfg, float *value_norm_state, void *workspace_dev,
                           uint64_t workspace_bytes, float *stats_dev_or_null, float *grads_dev_or_null, int gpu_id, void *hip_stream)
 {
+    if (policy && (policy->flags & MRL_CNN_RECURRENT))
+        return mrl::refusal("mrl_mappo_bank_update", "a bank update does not take a recurrent policy (MRL_CNN_RECURRENT)");
     return mrl::mappo_update<CnnNet>("mrl_mappo_bank_update", policy, opt, batch, indices_dev, num_minibatches, minibatch_size, cfg,
                                      value_norm_state, workspace_dev, workspace_bytes, stats_dev_or_null, grads_dev_or_null, gpu_id, hip_stream);
 }

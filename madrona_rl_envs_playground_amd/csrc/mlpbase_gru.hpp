@@ -20,78 +20,38 @@
 // per net.
 #pragma once
 
+#include "gru_step.hpp"
 #include "mappo_loss.hpp"
 #include "mlpbase_forward.hpp"
 #include "mlpbase_policy.hpp"
 
 namespace mrl {
 
-constexpr uint32_t kGruGates = 3 * kMlpBaseHidden;  // 192
-constexpr uint32_t kGruParams = 2 * kGruGates * kMlpBaseHidden + 2 * kGruGates + 2 * kMlpBaseHidden;  // 25 088
-// offsets inside one net, in floats: the GRU block starts where the plain net's head does
+static_assert(kMlpBaseHidden == kGruHidden && kMlpLd == kGruLd && kMlpBaseTile == kGruTile && kMlpBaseThreads == kGruThreads,
+              "gru_step.hpp's functions are written for this net's width, LDS row stride, tile and workgroup");
+// offsets inside one net, in floats: the GRU block (gru_step.hpp) starts where the plain net's head does
 __host__ __device__ constexpr uint32_t gru_wih_at(uint32_t layer_N) { return mlpbase_head_at(layer_N); }
-__host__ __device__ constexpr uint32_t gru_whh_at(uint32_t layer_N) { return gru_wih_at(layer_N) + kGruGates * kMlpBaseHidden; }
-__host__ __device__ constexpr uint32_t gru_bih_at(uint32_t layer_N) { return gru_whh_at(layer_N) + kGruGates * kMlpBaseHidden; }
-__host__ __device__ constexpr uint32_t gru_bhh_at(uint32_t layer_N) { return gru_bih_at(layer_N) + kGruGates; }
-__host__ __device__ constexpr uint32_t gru_norm_at(uint32_t layer_N) { return gru_bhh_at(layer_N) + kGruGates; }
 __host__ __device__ constexpr uint32_t gru_head_at(uint32_t layer_N) { return mlpbase_head_at(layer_N) + kGruParams; }
 __host__ __device__ constexpr uint32_t gru_net_params(uint32_t layer_N, uint32_t out) { return mlpbase_net_params(layer_N, out) + kGruParams; }
 
-// The workgroup's LDS image behind the plain forward image (mlpbase_policy.hpp), in floats, rows 65 apart:
-//   hin          the tile's masked incoming state rows h * m; mlpbase_gru_forward leaves h' there
-//   gate[0..5]   gi_r, gi_z, gi_n, gh_r, gh_z, gh_n as the products leave them; then r, z and n in place of gi_*, gh_n stays
-//   hn           h', then in place its normalised rows
-//   gy           LayerNorm64(h'), the head's input
-//   grstd        1 / sqrt(var + eps) of that LayerNorm per row
-//   cell, keep   per row: the sample's state row (world * P + seat; kGruAbsent for a row the tile lacks) and its mask m
-constexpr uint32_t kGruRows = kMlpBaseTile * kMlpLd;
-constexpr uint32_t kGruHinAt = kMlpFwdFloats, kGruGateAt = kGruHinAt + kGruRows, kGruHnAt = kGruGateAt + 6 * kGruRows, kGruYAt = kGruHnAt + kGruRows,
-                   kGruRstdAt = kGruYAt + kGruRows, kGruCellAt = kGruRstdAt + kMlpBaseTile, kGruKeepAt = kGruCellAt + kMlpBaseTile,
-                   kGruFwdFloats = kGruKeepAt + kMlpBaseTile;
+// The workgroup's LDS image: the plain forward image (mlpbase_policy.hpp), then the GRU's image (gru_step.hpp), in floats
+constexpr uint32_t kGruHinAt = kMlpFwdFloats, kGruGateAt = kGruHinAt + kGruImgGate, kGruHnAt = kGruHinAt + kGruImgHn, kGruYAt = kGruHinAt + kGruImgY,
+                   kGruRstdAt = kGruHinAt + kGruImgRstd, kGruCellAt = kGruHinAt + kGruImgCell, kGruKeepAt = kGruHinAt + kGruImgKeep,
+                   kGruFwdFloats = kGruHinAt + kGruImgFloats;
 static_assert(kGruFwdFloats * 4u <= 160u * 1024u, "the recurrent forward image fits one workgroup's LDS");
-constexpr uint32_t kGruAbsent = 0xFFFFFFFFu;
 
-__device__ __forceinline__ float gru_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
-__device__ __forceinline__ float gru_tanh(float x) { return tanhf(x); }
-
-// The GRU and its LayerNorm for the tile: x = the base's output rows (LDS, rows 65 apart), lds + kGruHinAt = h * m.  Leaves the
-// image described above; thread tid owns elements tid, tid + 256, ... of the 32 x 64 tile in every element-wise pass, so after
-// the call it may read back the h' it wrote to hin without a barrier (there is one anyway: the LayerNorm ends behind it).
+// the GRU and its LayerNorm behind the base: gru_step_forward on this net's image, x = the base's output rows
 __device__ __forceinline__ void mlpbase_gru_forward(const float *__restrict__ net, uint32_t layer_N, const float *__restrict__ x,
                                                     float *__restrict__ lds, uint32_t tid)
 {
-    const uint32_t wave = tid >> 6, lane = tid & 63u;
-    float *chunk = lds + kMlpChunkAt, *hin = lds + kGruHinAt, *gate = lds + kGruGateAt, *hn = lds + kGruHnAt;
-    const float *__restrict__ w_ih = net + gru_wih_at(layer_N), *__restrict__ w_hh = net + gru_whh_at(layer_N);
-    const float *__restrict__ b_ih = net + gru_bih_at(layer_N), *__restrict__ b_hh = net + gru_bhh_at(layer_N);
-#pragma unroll 1
-    for (uint32_t g = 0; g < 3u; g++) {
-        cnn_fc_layer(x, kMlpLd, kMlpBaseHidden, w_ih + g * kMlpBaseHidden * kMlpBaseHidden, b_ih + g * kMlpBaseHidden, kMlpBaseHidden, false, chunk,
-                     gate + g * kGruRows, kMlpLd, wave, lane);
-        cnn_fc_layer(hin, kMlpLd, kMlpBaseHidden, w_hh + g * kMlpBaseHidden * kMlpBaseHidden, b_hh + g * kMlpBaseHidden, kMlpBaseHidden, false,
-                     chunk, gate + (3u + g) * kGruRows, kMlpLd, wave, lane);
-    }
-    for (uint32_t idx = tid; idx < kMlpBaseTile * kMlpBaseHidden; idx += kMlpBaseThreads) {
-        const uint32_t at = (idx >> 6) * kMlpLd + (idx & 63u);
-        const float r = gru_sigmoid(gate[at] + gate[3u * kGruRows + at]);
-        const float z = gru_sigmoid(gate[kGruRows + at] + gate[4u * kGruRows + at]);
-        const float n = gru_tanh(gate[2u * kGruRows + at] + r * gate[5u * kGruRows + at]);
-        const float h = hin[at], next = (1.0f - z) * n + z * h;
-        gate[at] = r, gate[kGruRows + at] = z, gate[2u * kGruRows + at] = n;
-        hin[at] = next, hn[at] = next;
-    }
-    __syncthreads();
-    const float *__restrict__ norm = net + gru_norm_at(layer_N);
-    mlpbase_layer_norm(hn, lds + kGruYAt, kMlpLd, kMlpBaseHidden, norm, norm + kMlpBaseHidden, lds + kGruRstdAt, nullptr, wave, lane);
+    gru_step_forward(net + gru_wih_at(layer_N), x, lds + kMlpChunkAt, lds + kGruHinAt, tid);
 }
 
 // the head of a recurrent net: from gy to outs (row stride 8)
 __device__ __forceinline__ void mlpbase_gru_head(const float *__restrict__ net, uint32_t layer_N, uint32_t out_dim, float *__restrict__ lds,
                                                  uint32_t tid)
 {
-    const float *__restrict__ head_w = net + gru_head_at(layer_N);
-    cnn_fc_layer(lds + kGruYAt, kMlpLd, kMlpBaseHidden, head_w, head_w + out_dim * kMlpBaseHidden, out_dim, false, lds + kMlpChunkAt,
-                 lds + kMlpOutAt, 8u, tid >> 6, tid & 63u);
+    gru_step_head(net + gru_head_at(layer_N), out_dim, lds + kMlpChunkAt, lds + kGruHinAt, lds + kMlpOutAt, tid);
 }
 
 struct MlpBaseGruActArgs {

@@ -39,7 +39,6 @@ static_assert(kMlpBaseHidden == kMappoHidden && kMlpBaseThreads == kMappoThreads
 constexpr uint32_t kGruCarryAt = kGruFwdFloats, kGruDoutAt = kGruCarryAt + kGruRows, kGruSampleAt = kGruDoutAt + kMlpBaseTile * 8,
                    kGruChunkAt = kGruSampleAt + kMlpBaseTile, kGruUpdFloats = kGruChunkAt + kMlpBaseTile;
 static_assert(kGruUpdFloats * 4u <= 160u * 1024u, "the recurrent gradient image fits one workgroup's LDS");
-constexpr uint32_t kGruTileFloats = kMlpBaseTile * kMlpBaseHidden;  // a step's incoming states of a tile in the workspace
 
 extern __shared__ __attribute__((aligned(16))) unsigned char gru_upd_lds_image[];
 
@@ -75,32 +74,6 @@ __device__ __forceinline__ void gru_load_step(const MappoGruGradArgs &a, float *
     lds[kMlpXhat0At + rr * kMlpLd0 + k] = v;
 }
 
-// out[sample][col] = sum over the three gates g of d_g[sample][:] W[g][:][col] (W: three 64 x 64 blocks), a 32-column slab per
-// calling wave (`slab` 0 or 1); with `add`: (that + add[sample][col]) * keep[sample]
-__device__ __forceinline__ void gru_d_in3(const float *d0, const float *d1, const float *d2, const float *__restrict__ w, float *out,
-                                          const float *add, const float *keep, uint32_t slab, uint32_t r, uint32_t half)
-{
-    const uint32_t col = 32u * slab + r;
-    mappo_f32x16 acc;
-#pragma unroll
-    for (int e = 0; e < 16; e++) acc[e] = 0.0f;
-#pragma unroll 1
-    for (uint32_t g = 0; g < 3u; g++) {
-        const float *d = g == 0u ? d0 : (g == 1u ? d1 : d2);
-        const float *__restrict__ wg = w + g * kMlpBaseHidden * kMlpBaseHidden;
-#pragma unroll 4
-        for (uint32_t kk = 0; kk < kMappoHidden / 2u; kk++) {
-            const uint32_t j = 2u * kk + half;
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(d[r * kMlpLd + j], wg[j * kMappoHidden + col], acc, 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 16; e++) {
-        const uint32_t row = tile_row(e, half);
-        out[row * kMlpLd + col] = add ? (acc[e] + add[row * kMlpLd + col]) * keep[row] : acc[e];
-    }
-}
-
 __global__ void __launch_bounds__(kMlpBaseThreads) mrl_mappo_gru_grad(MappoGruGradArgs a)
 {
     const MappoGradCommon &c = a.common;
@@ -110,14 +83,11 @@ __global__ void __launch_bounds__(kMlpBaseThreads) mrl_mappo_gru_grad(MappoGruGr
     float *__restrict__ grads = c.partial_grads + ((size_t)net * c.groups + blockIdx.x) * c.stride;
     float *__restrict__ history = a.history + ((size_t)net * c.groups + blockIdx.x) * L * kGruTileFloats;
     const float *__restrict__ h0 = a.h0[net];
-    const float *__restrict__ head_w = params + gru_head_at(layer_N), *__restrict__ norm_w = params + gru_norm_at(layer_N);
+    const float *__restrict__ head_w = params + gru_head_at(layer_N);
     float *__restrict__ g_head_w = grads + gru_head_at(layer_N), *__restrict__ g_head_b = g_head_w + out_dim * kMlpBaseHidden;
-    float *__restrict__ g_wih = grads + gru_wih_at(layer_N), *__restrict__ g_whh = grads + gru_whh_at(layer_N);
-    float *__restrict__ g_bih = grads + gru_bih_at(layer_N), *__restrict__ g_bhh = grads + gru_bhh_at(layer_N);
-    float *__restrict__ g_norm = grads + gru_norm_at(layer_N);
 
     float *lds = reinterpret_cast<float *>(gru_upd_lds_image);
-    float *hin = lds + kGruHinAt, *gate = lds + kGruGateAt, *hn = lds + kGruHnAt, *keep = lds + kGruKeepAt, *carry = lds + kGruCarryAt;
+    float *hin = lds + kGruHinAt, *gate = lds + kGruGateAt, *keep = lds + kGruKeepAt, *carry = lds + kGruCarryAt;
     float *d_out = lds + kGruDoutAt, *d_gy = gate + 3u * kGruRows, *d_h = gate + 4u * kGruRows;
     uint32_t *sample = reinterpret_cast<uint32_t *>(lds + kGruSampleAt), *chunk = reinterpret_cast<uint32_t *>(lds + kGruChunkAt);
     const float *x = lds + kMlpYAt + layer_N * kMlpBaseTile * kMlpLd;
@@ -131,7 +101,7 @@ __global__ void __launch_bounds__(kMlpBaseThreads) mrl_mappo_gru_grad(MappoGruGr
     for (uint32_t e = tid0; e < kMlpBaseBlock; e += kMlpBaseThreads) grads[kMlpBaseFcHAt + e] = 0.0f;
 
     for (uint64_t base = begin; base < end; base += kMlpBaseTile) {
-        const uint32_t tid = opaque(tid0), lane = tid & 63u, wave = tid >> 6, r = lane & 31u, half = lane >> 5;
+        const uint32_t tid = opaque(tid0), lane = tid & 63u, wave = tid >> 6;
         if (tid < kMlpBaseTile) {
             uint32_t id = kMappoAbsent;
             if (base + tid < end) {
@@ -184,52 +154,9 @@ __global__ void __launch_bounds__(kMlpBaseThreads) mrl_mappo_gru_grad(MappoGruGr
 
             mappo_loss_head<(int)kMlpBaseActions>(c, net, sample, lds + kMlpOutAt, d_out, count, stat, tid);
             __syncthreads();
-            // ---- head: dW_head, db_head and dL/d(gy)
-            mappo_head_backward<false>(head_w, g_head_w, g_head_b, out_dim, d_out, lds + kGruYAt, d_gy, nullptr, kMlpLd, first, tid);
-            __syncthreads();
-            // ---- the GRU's LayerNorm: dh' = rstd (g - mean(g) - xhat mean(g xhat)) + what step i + 1 carried here
-            {
-                const float weight = norm_w[lane];
-                for (uint32_t row = wave; row < kMlpBaseTile; row += 4u) {
-                    const float xh = hn[row * kMlpLd + lane], g = d_gy[row * kMlpLd + lane] * weight;
-                    const float mean_g = wave_sum(g) / (float)kMlpBaseHidden, mean_gx = wave_sum(g * xh) / (float)kMlpBaseHidden;
-                    const float dx = lds[kGruRstdAt + row] * ((g - mean_g) - xh * mean_gx);
-                    d_h[row * kMlpLd + lane] = back ? dx + carry[row * kMlpLd + lane] : dx;
-                }
-                if (wave == 0u)
-                    column_sum(g_norm, first, d_gy, hn, kMlpLd, kMlpLd, lane);
-                else if (wave == 1u)
-                    column_sum(g_norm + kMlpBaseHidden, first, d_gy, nullptr, kMlpLd, 0u, lane);
-            }
-            __syncthreads();  // dh' is complete; d_gy and the normalised rows are dead
-            // ---- the gates, element-wise: gate[0], [1], [2], [5] become a_r, a_z, a_n, a_n r; hn becomes dh' z
-            for (uint32_t idx = tid; idx < kGruTileFloats; idx += kMlpBaseThreads) {
-                const uint32_t at = (idx >> 6) * kMlpLd + (idx & 63u);
-                const float dh = d_h[at], rg = gate[at], zg = gate[kGruRows + at], ng = gate[2u * kGruRows + at], ghn = gate[5u * kGruRows + at];
-                const float a_n = (dh * (1.0f - zg)) * (1.0f - ng * ng);
-                const float a_z = (dh * (hin[at] - ng)) * (zg * (1.0f - zg));
-                const float a_r = (a_n * ghn) * (rg * (1.0f - rg));
-                gate[at] = a_r, gate[kGruRows + at] = a_z, gate[2u * kGruRows + at] = a_n, gate[5u * kGruRows + at] = a_n * rg;
-                hn[at] = dh * zg;
-            }
-            __syncthreads();  // the gate gradients are complete; dh' is dead
-            // ---- dW_ih = dgi^T x, dW_hh = dgh^T h_in, a 32 x 32 block per wave each; the bias sums
-#pragma unroll 1
-            for (uint32_t g = 0; g < 3u; g++) {
-                const float *dgi = gate + g * kGruRows, *dgh = gate + (g == 2u ? 5u : g) * kGruRows;
-                mappo_dw_block(g_wih + g * kMlpBaseHidden * kMlpBaseHidden, dgi, x, kMlpLd, first, wave, r, half);
-                mappo_dw_block(g_whh + g * kMlpBaseHidden * kMlpBaseHidden, dgh, hin, kMlpLd, first, wave, r, half);
-                if (wave == g)
-                    column_sum(g_bih + g * kMlpBaseHidden, first, dgi, nullptr, kMlpLd, 0u, lane);
-                else if (wave == ((g + 1u) & 3u))
-                    column_sum(g_bhh + g * kMlpBaseHidden, first, dgh, nullptr, kMlpLd, 0u, lane);
-            }
-            // ---- dx on waves 0 and 1 (the base's dy); on waves 2 and 3 what step i - 1 receives: (dgh W_hh + dh' z) m_i
-            if (wave < 2u)
-                gru_d_in3(gate, gate + kGruRows, gate + 2u * kGruRows, params + gru_wih_at(layer_N), d_gy, nullptr, nullptr, wave, r, half);
-            else if (i)
-                gru_d_in3(gate, gate + kGruRows, gate + 5u * kGruRows, params + gru_whh_at(layer_N), carry, hn, keep, wave - 2u, r, half);
-            __syncthreads();  // dx and the carry are complete; the gate gradients are dead
+            // ---- back through the head, the LayerNorm and the GRU (gru_step.hpp): dx, the base's dy, arrives in gate[3]
+            gru_step_backward(params + gru_wih_at(layer_N), grads + gru_wih_at(layer_N), head_w, g_head_w, g_head_b, out_dim, d_out, x,
+                              lds + kGruHinAt, carry, back != 0u, i != 0u, first, tid);
             mlpbase_backward(params, grads, layer_N, lds, d_gy, d_h, first, tid);
         }
     }

@@ -104,7 +104,8 @@ class CnnPolicyAgent(_DevicePolicyAgent):
     """A player of either kitchen env (``envs.overcooked_env.OvercookedMadrona`` or the Simplecooked one of
     ``envs.overcooked2_env``) that acts under MAPPO's CNN policy on the device: ``get_action`` is ``mrl_cnn_act`` for this
     agent's seat -- ``player_num``, set by ``env.add_partner_agent``, or, while that is ``None``, the env's ``ego_ind`` -- on the
-    simulator's own observations, and returns the view ``env.static_actions[seat]``.  ``policy``: a ``simulators.CnnPolicy``;
+    simulator's own observations, and returns the view ``env.static_actions[seat]``.  ``policy``: a ``simulators.CnnPolicy``, or a
+    ``simulators.CnnGruPolicy`` (recurrent), for which the agent keeps its own ``GruState`` in ``state``;
     ``seed`` seeds the draws, whose step number counts this agent's calls.  ``update`` does nothing.  Any env other than one of
     those two on the GPU is refused with a ``TypeError`` by the constructor: there is no torch fallback.  ``obs`` and
     ``record`` of ``get_action`` are the ``VectorAgent`` protocol's; the kernel reads the simulator's observations itself and this
@@ -125,8 +126,20 @@ class CnnPolicyAgent(_DevicePolicyAgent):
         return sim
 
     def _act(self, mask):
-        from ..simulators import cnn_act
-        cnn_act(self._sim, self.policy, mask, seed=self.seed, step=self._draws, greedy=self.greedy)
+        from ..simulators import CnnGruPolicy, GruState, cnn_act
+        if not isinstance(self.policy, CnnGruPolicy):
+            cnn_act(self._sim, self.policy, mask, seed=self.seed, step=self._draws, greedy=self.greedy)
+            return
+        # a recurrent policy: this agent owns the state its seat runs on (``state``, zero at first; the act masks it where an episode
+        # has just ended), binds it for this call alone and puts back what was bound before, as ``MlpBasePolicyAgent`` does
+        if getattr(self, "state", None) is None:
+            self.state = GruState(self.envs.num_envs, self.envs.static_actions.device, self.envs.num_players, self.policy.hidden)
+        bound_before = self.policy.running
+        self.policy.bind(self.state)
+        try:
+            cnn_act(self._sim, self.policy, mask, seed=self.seed, step=self._draws, greedy=self.greedy)
+        finally:
+            self.policy.running = bound_before
 
 
 class CnnPopulationAgent(_PopulationSeat, CnnPolicyAgent):

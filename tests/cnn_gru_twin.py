@@ -1,0 +1,222 @@
+"""The float64 twin of MAPPO's RECURRENT CNN actor-critic for the kitchens (``mrl_cnn_act`` and ``mrl_mappo_update`` with
+``MRL_CNN_RECURRENT``), put together from tests/cnn_twin.py (the index map, the draws), tests/mappo_twin.py (the losses, ValueNorm,
+the margins) and tests/mlpbase_gru_twin.py (the chunks): the network of include/mrl_envs.h built from torch's own ``Conv2d`` /
+``Linear`` / ``GRU`` / ``LayerNorm`` (``CnnGruActorCritic``) in float64 -- one act from a state and a mask, the evaluation of chunks
+of L steps with a mask at every step, the losses over the Bc L samples of a row of chunks, the gradient by autograd (through time).  Every function takes ``dtype``: the same computation in float32 on the CPU is torch's own, and its
+distance from the twin is d, the unit of every margin of the device's tests (within ``FACTOR`` x d).  Also the cases' shapes and
+inputs, shared by tests/test_cnn_gru_api.py and tests/test_gpu_cnn_gru.py.  Nothing here touches a GPU."""
+import collections
+import functools
+
+import numpy as np
+import torch
+
+import cnn_twin
+import kitchen_shape_cases
+from madrona_rl_envs_playground_amd import layouts
+from madrona_rl_envs_playground_amd.simulators import CnnGruActorCritic
+from mappo_twin import FACTOR, STATS, Config, huber_loss, mse_loss, value_norm_update  # noqa: F401
+
+A, HIDDEN, GRU = 6, 64, 25088
+W_HH = 3 * HIDDEN * HIDDEN
+# key -> game; the largest custom kitchen tests/kitchen_shape_cases.py lists as admitted is where the GRU image overlays most
+KITCHENS = {"k3x3p1": "overcooked", "cramped_room": "overcooked", "simple/1p": "simplecooked", "k8x5p4": "overcooked"}
+CHUNKS = (1, 2, 10, 16)
+
+
+def layout_params(key, horizon=400):
+    if KITCHENS[key] == "simplecooked":
+        return layouts.get_simplecooked_layout_params(key.partition("/")[0], horizon, max_num_players=1)
+    if key in kitchen_shape_cases.TABLE:
+        return kitchen_shape_cases.layout_params(key, horizon)
+    return layouts.get_base_layout_params(key, horizon)
+
+
+def shape(key):
+    """(W, H, P, F) of a key"""
+    p = layout_params(key)
+    players = int(p["num_players"])
+    return int(p["width"]), int(p["height"]), players, 5 * players + (10 if KITCHENS[key] == "simplecooked" else 16)
+
+
+@functools.lru_cache(maxsize=None)
+def params_of(key, seed=29):
+    """float32 flat parameters of a trained net's scale: He-scaled matrices, a head that spreads the probabilities, the GRU's
+    matrices orthogonal, every bias (the GRU's too) of a tenth, LayerNorm weights away from 1"""
+    w, h, _, f = shape(key)
+    torch.manual_seed(seed)
+    module = CnnGruActorCritic(w, h, f)
+    with torch.no_grad():
+        for name, p in module.named_parameters():
+            if "norm.weight" in name:
+                p.uniform_(0.5, 1.5)
+            elif name.endswith("bias") or "bias_" in name:
+                p.normal_(0.0, 0.1)
+            elif "action_out" in name or "v_out" in name:
+                p.normal_(0.0, 0.3)
+            elif "rnn" not in name:
+                p.normal_(0.0, (2.0 / p[0].numel()) ** 0.5)
+    return torch.nn.utils.parameters_to_vector(module.parameters()).detach().numpy().copy()
+
+
+def module_from(params, key, dtype=torch.float64):
+    w, h, _, f = shape(key)
+    module = CnnGruActorCritic(w, h, f).to(dtype)
+    source = torch.as_tensor(np.asarray(params, np.float64)).to(dtype)
+    at = 0
+    with torch.no_grad():
+        for p in module.parameters():
+            p.copy_(source[at:at + p.numel()].view_as(p))
+            at += p.numel()
+    assert at == source.numel()
+    return module
+
+
+def actor_size(key):
+    w, h, _, f = shape(key)
+    return 32 * f * 9 + 32 + 64 * 32 * (w - 2) * (h - 2) + 64 + 64 * 64 + 64 + GRU + A * HIDDEN + A
+
+
+def whh_slices(key):
+    """where the two nets' weight_hh_l0 lie in the flat tensor"""
+    na = actor_size(key)
+    at = na - (A * HIDDEN + A) - GRU + W_HH
+    return slice(at, at + W_HH), slice(na + at, na + at + W_HH)
+
+
+def observations(key, shape_head, seed):
+    """int8 (*shape_head, H, W, F): a quarter ones, one entry in 16 a count up to 20, one in 64 negative (``cnn_twin``'s mix)"""
+    w, h, _, f = shape(key)
+    rng = np.random.default_rng(seed)
+    size = tuple(shape_head) + (h, w, f)
+    obs = (rng.random(size) < 0.25).astype(np.int8)
+    obs = np.where(rng.random(size) < 1 / 16, rng.integers(0, 21, size), obs)
+    return np.where(rng.random(size) < 1 / 64, rng.integers(-3, 0, size), obs).astype(np.int8)
+
+
+def act_inputs(key, n, states, seed=11):
+    """{"obs" (N, P, H, W, F) int8, "done" (N) int32 with some flags set and some not, "h_actor", "h_critic" (N, P, 64) float32}"""
+    p = shape(key)[2]
+    rng = np.random.default_rng(seed + n)
+    done = (rng.random(n) < 0.3).astype(np.int32)
+    done[:2] = (1, 0)
+    h = [(rng.normal(0.0, 0.5, (n, p, HIDDEN)) if states == "nonzero" else np.zeros((n, p, HIDDEN))).astype(np.float32) for _ in range(2)]
+    return {"obs": observations(key, (n, p), seed + 3 * n), "done": done, "h_actor": h[0], "h_critic": h[1]}
+
+
+def _t(array, dtype):
+    return torch.from_numpy(np.array(array)).to(dtype)
+
+
+def _x(rows, dtype):
+    """rows (..., H, W, F) as the network's (..., W, H, F) floats"""
+    return _t(rows, dtype).transpose(-3, -2)
+
+
+def act(params, key, rows, h_actor, h_critic, mask, u, dtype=torch.float64):
+    """One act: rows (n, H, W, F), states (n, 64), mask (n).  float64 numpy arrays, computed in ``dtype``."""
+    module = module_from(params, key, dtype)
+    with torch.no_grad():
+        x, m = _x(rows, dtype), _t(mask, dtype)
+        logits, ha = module.actor(x, _t(h_actor, dtype), m)
+        values, hc = module.critic(x, _t(h_critic, dtype), m)
+        logp = torch.log_softmax(logits, dim=1)
+    values, logits, logp, ha, hc = (t.double().numpy() for t in (values[:, 0], logits, logp, ha, hc))
+    cdf = np.cumsum(np.exp(logp), axis=1)[:, :-1]
+    actions = (np.asarray(u, np.float64)[:, None] >= cdf).sum(axis=1).astype(np.int32)
+    return {"values": values, "logits": logits, "logp": logp, "cdf": cdf, "actions": actions, "h_actor": ha, "h_critic": hc}
+
+
+ACT_KINDS = ("values", "logp", "logits", "h_actor", "h_critic")
+
+
+def act_margins(params, key, rows, h_actor, h_critic, mask):
+    zero = np.zeros(len(rows))
+    exact = act(params, key, rows, h_actor, h_critic, mask, zero)
+    single = act(params, key, rows, h_actor, h_critic, mask, zero, torch.float32)
+    return {k: float(np.abs(single[k] - exact[k]).max()) for k in ACT_KINDS}
+
+
+# obs (T, N, P, H, W, F) int8; actions, logprobs, values, returns, advantages, dones (T, N, P); h0_* (T / L, N, P, 64)
+Batch = collections.namedtuple("Batch", "obs actions logprobs values returns advantages dones h0_actor h0_critic chunk_length")
+
+
+def evaluate(module, batch, chunk_ids):
+    """(values (L, Bc), logits (L, Bc, 6), where) of the chunks, each from its own h0 with m_i = 1 - dones[j L + i]"""
+    dtype = next(module.parameters()).dtype
+    L = batch.chunk_length
+    _, n_worlds, seats = np.asarray(batch.actions).shape
+    c = np.asarray(chunk_ids).astype(np.int64)
+    j, n, p = c // (n_worlds * seats), (c // seats) % n_worlds, c % seats
+    steps = j[None, :] * L + np.arange(L)[:, None]
+    where = (steps, n[None, :], p[None, :])
+    obs = _x(np.asarray(batch.obs)[where], dtype)
+    masks = 1.0 - _t(np.asarray(batch.dones)[where], dtype)
+    logits, _ = module.actor.chunk(obs, _t(np.asarray(batch.h0_actor)[j, n, p], dtype), masks)
+    values, _ = module.critic.chunk(obs, _t(np.asarray(batch.h0_critic)[j, n, p], dtype), masks)
+    return values[..., 0], logits, where
+
+
+@functools.lru_cache(maxsize=None)
+def update_case(key, L, Bc, rows=1, seed=5):
+    """(params, Batch, chunk ids (rows, Bc) int32) with T = L or 2 L: recorded log-probs and values near the twin's, so that the
+    ratio clips some samples and not others; a fifth of the DONE flags set; h0 non-zero"""
+    _, _, p, _ = shape(key)
+    params = params_of(key)
+    T = 2 * L if L < 10 else L
+    n = -(-Bc // (T // L * p)) + 1
+    rng = np.random.default_rng(seed + 17 * L + Bc)
+    size = (T, n, p)
+    proto = Batch(observations(key, size, seed + L), rng.integers(0, A, size).astype(np.int32), None, None, None, None,
+                  (rng.random(size) < 0.2).astype(np.float32), rng.normal(0, 0.5, (T // L, n, p, HIDDEN)).astype(np.float32),
+                  rng.normal(0, 0.5, (T // L, n, p, HIDDEN)).astype(np.float32), L)
+    chunks = T // L * n * p
+    with torch.no_grad():
+        v, logits, where = evaluate(module_from(params, key), proto, np.arange(chunks))
+        taken = torch.log_softmax(logits, -1).gather(-1, torch.from_numpy(proto.actions[where]).long().unsqueeze(-1)).squeeze(-1).numpy()
+    logp, values = np.zeros(size, np.float32), np.zeros(size, np.float32)
+    logp[where] = taken + rng.normal(0, 0.15, taken.shape)
+    values[where] = v.numpy() + rng.normal(0, 0.15, taken.shape)
+    returns = (values + rng.normal(0, 0.5, size)).astype(np.float32)
+    batch = proto._replace(logprobs=logp, values=values, returns=returns, advantages=rng.normal(0, 1, size).astype(np.float32))
+    ids = np.stack([rng.permutation(chunks)[:Bc] for _ in range(rows)]).astype(np.int32)
+    return params, batch, ids
+
+
+def row(params, key, batch, chunk_ids, cfg, state=(0.0, 0.0, 0.0), dtype=torch.float64):
+    """One minibatch of chunks in ``dtype`` on the CPU, ``mappo_twin.row`` over the Bc L samples of the chunks"""
+    np_dtype = np.float64 if dtype == torch.float64 else np.float32
+    module = module_from(params, key, dtype)
+    v, logits, where = evaluate(module, batch, chunk_ids)
+    take = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a)[where]))  # noqa: E731
+    actions, old_logp, old_v, returns, adv = (take(a) for a in (batch.actions, batch.logprobs, batch.values, batch.returns, batch.advantages))
+    old_logp, old_v, adv = old_logp.to(dtype), old_v.to(dtype), adv.to(dtype)
+    c = cfg.clip_param
+    logp = torch.log_softmax(logits, dim=-1)
+    entropy = -(logp.exp() * logp).sum(dim=-1).mean()
+    taken = logp.gather(-1, actions.long().unsqueeze(-1)).squeeze(-1)
+    ratio = (taken - old_logp).exp()
+    policy_loss = -torch.min(ratio * adv, ratio.clamp(1.0 - c, 1.0 + c) * adv).mean()
+    (policy_loss - entropy * cfg.entropy_coef).backward()
+    new_state, target = np.asarray(state, np_dtype), returns.to(dtype)
+    if cfg.valuenorm:
+        new_state, mean, std = value_norm_update(state, returns.numpy().reshape(-1), cfg, np_dtype)
+        target = (target - float(mean)) / float(std) if dtype == torch.float64 else (target - torch.tensor(mean)) / torch.tensor(std)
+    v_c = old_v + (v - old_v).clamp(-c, c)
+    term = (lambda err: huber_loss(err, cfg.huber_delta)) if cfg.huber else mse_loss
+    plain, clipped = term(target - v), term(target - v_c)
+    value_loss = (torch.max(plain, clipped) if cfg.clipped_value else plain).mean()
+    (value_loss * cfg.value_loss_coef).backward()
+    grad = torch.cat([q.grad.reshape(-1) for q in module.parameters()]).double().numpy()
+    na = actor_size(key)
+    clipped_samples = ((ratio - 1).abs() > c).to(dtype)
+    stats = {"value_loss": value_loss.item(), "policy_loss": policy_loss.item(), "dist_entropy": entropy.item(), "ratio": ratio.mean().item(),
+             "clipfrac": clipped_samples.mean().item(), "actor_grad_norm": float(np.sqrt(np.sum(grad[:na] ** 2))),
+             "critic_grad_norm": float(np.sqrt(np.sum(grad[na:] ** 2)))}
+    return {"grad": grad, "stats": stats, "state": np.asarray(new_state, np.float64), "values": v.detach().double().numpy(),
+            "logp": taken.detach().double().numpy()}
+
+
+draws = cnn_twin.draws
+near_boundary = cnn_twin.near_boundary
+rows_of = cnn_twin.rows_of

@@ -6,10 +6,12 @@ episode totals and the update's stats come back.  The flat parameter tensor is t
 
     python tools/overcooked_train_device.py --layout cramped_room --num-envs 1024 --num-steps 128 --updates 20
     python tools/overcooked_train_device.py --game simplecooked --recipe colab --evaluate
+    python tools/overcooked_train_device.py --recipe colab --recurrent --data-chunk-length 10
 
 ``--game simplecooked`` is the world the reference's trainer binds (train/env_utils.py:3); ``--recipe colab`` sets what its
 notebook overcooked_compiled_colab.ipynb trains (``RECIPES``), and ``--evaluate`` is that notebook's test cell: one greedy episode
-in every world, then the histogram of the worlds' scores.
+in every world, then the histogram of the worlds' scores.  ``--recurrent`` is the reference's ``--use_recurrent_policy`` (a GRU and
+a LayerNorm between the CNN and the head of both nets; minibatches of chunks of ``--data-chunk-length`` steps), on either game.
 
 Importable: ``train(layout, num_envs, num_steps, updates, seed) -> list of per-update dicts``."""
 import argparse
@@ -59,33 +61,45 @@ def evaluate(env, policy, horizon, seed=0):
 
 def train(layout, num_envs, num_steps, updates, seed, lr=5e-4, critic_lr=5e-4, lr_decay=False, gamma=0.99, gae_lambda=0.95, ppo_epoch=15,
           num_mini_batch=1, clip_param=0.2, entropy_coef=0.01, value_loss_coef=1.0, max_grad_norm=10.0, huber_delta=10.0, horizon=400,
-          log=None, game="overcooked", evaluation=None):
+          log=None, game="overcooked", evaluation=None, recurrent=False, data_chunk_length=10, final=None):
     """``updates`` iterations of collect, advantages, update with the reference's defaults (train/config.py).  One dict per
     update: the learning rates, the mean of every stat over the update's rows (``train_info``), the episodes finished during the
     update with their mean return, and ``optimizer_step``.  ``game``: "overcooked" or "simplecooked" (``layout`` is then one of
-    Simplecooked's names).  ``evaluation``: a dict that takes ``evaluate``'s histogram under "scores" after the last update."""
+    Simplecooked's names).  ``evaluation``: a dict that takes ``evaluate``'s histogram under "scores" after the last update.
+    ``recurrent``: the recurrent actor-critic, trained on chunks of ``data_chunk_length`` steps (it must divide ``num_steps``).
+    ``final``: a dict that takes the trained flat tensor (on the host) under "params"."""
     import torch
     from madrona_rl_envs_playground_amd import _lib
-    from madrona_rl_envs_playground_amd.simulators import (CnnActorCritic, CnnPolicy, MappoOptimizer, ValueNorm, mappo_advantages,
-                                                             mappo_update, minibatch_indices)
+    from madrona_rl_envs_playground_amd.simulators import (CnnActorCritic, CnnGruActorCritic, CnnGruPolicy, CnnGruRecord, CnnPolicy,
+                                                             MappoOptimizer, ValueNorm, chunk_indices, mappo_advantages, mappo_update,
+                                                             minibatch_indices)
     env = make_env(game, layout, num_envs, horizon)
     device = torch.device("cuda", 0)
     _, players, height, width, channels = env.static_world_major_observations.shape
     torch.manual_seed(seed)
-    policy = CnnPolicy.from_module(CnnActorCritic(width, height, channels), device=device)
+    record = None
+    if recurrent:
+        policy = CnnGruPolicy.from_module(CnnGruActorCritic(width, height, channels), device=device)
+        policy.state(num_envs, players)
+        record = CnnGruRecord(num_steps, num_envs, players, device, chunk_length=data_chunk_length)
+    else:
+        policy = CnnPolicy.from_module(CnnActorCritic(width, height, channels), device=device)
     optimizer = MappoOptimizer(policy, lr=lr, critic_lr=critic_lr)
     value_norm = ValueNorm(device)
     shuffles = torch.Generator(device=device).manual_seed(seed)
     rows = ppo_epoch * num_mini_batch
     host_stats = torch.empty((rows, len(_lib.MAPPO_STATS)), dtype=torch.float32).pin_memory()
-    record, ring, history = None, None, []
+    ring, history = None, []
     for update in range(updates):
         if lr_decay:  # utils/util.py:38-43
             optimizer.lr, optimizer.critic_lr = lr - lr * (update / updates), critic_lr - critic_lr * (update / updates)
         env.clear_episode_totals()
         record, ring = env.rollout(policy, num_steps, seed=seed, first_step=update * num_steps, record=record, ring=ring)
         advantages, returns = mappo_advantages(record, value_norm, gamma, gae_lambda)
-        indices = minibatch_indices(num_steps * num_envs * players, num_mini_batch, ppo_epoch, generator=shuffles, device=device)
+        if recurrent:
+            indices = chunk_indices(record, num_mini_batch, ppo_epoch, generator=shuffles, device=device)
+        else:
+            indices = minibatch_indices(num_steps * num_envs * players, num_mini_batch, ppo_epoch, generator=shuffles, device=device)
         result = mappo_update(policy, optimizer, record, ring, advantages, returns, indices, value_norm=value_norm, clip_param=clip_param,
                               entropy_coef=entropy_coef, value_loss_coef=value_loss_coef, max_grad_norm=max_grad_norm,
                               huber_delta=huber_delta)
@@ -100,7 +114,11 @@ def train(layout, num_envs, num_steps, updates, seed, lr=5e-4, critic_lr=5e-4, l
         history.append(entry)
         if log:
             log(entry)
+    if final is not None:
+        final["params"] = policy.params.cpu()
     if evaluation is not None:
+        if recurrent:
+            policy.running.zero_()
         evaluation["scores"] = evaluate(env, policy, horizon, seed=seed)
     env.close()
     return history
@@ -126,6 +144,8 @@ def parser():
     ap.add_argument("--lr", type=float)
     ap.add_argument("--critic-lr", type=float)
     ap.add_argument("--entropy-coef", type=float)
+    ap.add_argument("--recurrent", action="store_true", help="the GRU actor-critic (the reference's --use_recurrent_policy)")
+    ap.add_argument("--data-chunk-length", type=int, default=10, help="steps per chunk of a recurrent minibatch; divides --num-steps")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--evaluate", action="store_true", help="afterwards one greedy episode in every world; prints {score: worlds}")
     ap.add_argument("--json", help="also write the settings, the per-update entries and the histogram to this file")
@@ -138,12 +158,12 @@ def main(argv=None):
     evaluation = {} if args.evaluate else None
     history = train(s["layout"], s["num_envs"], s["num_steps"], s["updates"], args.seed, lr=s["lr"], critic_lr=s["critic_lr"],
                     ppo_epoch=s["ppo_epoch"], num_mini_batch=s["num_mini_batch"], entropy_coef=s["entropy_coef"], horizon=s["horizon"],
-                    game=s["game"], evaluation=evaluation, log=lambda entry: print(json.dumps(entry), flush=True))
+                    game=s["game"], evaluation=evaluation, recurrent=args.recurrent, data_chunk_length=args.data_chunk_length, log=lambda entry: print(json.dumps(entry), flush=True))
     if evaluation is not None:
         print(json.dumps({"greedy_scores": {str(k): v for k, v in evaluation["scores"].items()}}), flush=True)
     if args.json:
         from madrona_rl_envs_playground_amd import _lib
-        out = {"build_hash": _lib.build_hash(), "settings": dict(s, seed=args.seed, recipe=args.recipe), "updates": history,
+        out = {"build_hash": _lib.build_hash(), "settings": dict(s, seed=args.seed, recipe=args.recipe, recurrent=args.recurrent, data_chunk_length=args.data_chunk_length), "updates": history,
                "mean_returns": [entry["mean_return"] for entry in history]}
         if evaluation is not None:
             out["greedy_scores"] = {str(k): v for k, v in evaluation["scores"].items()}
