@@ -869,9 +869,20 @@ int mrl_agent_update(const mrl_wide_policy *policy, const mrl_ppo_optimizer *opt
  *     critic's input IS the seat's observation (share_observation_space = observation_space) and no action is masked (Simplecooked's mask is all ones).
  *     params_dev is one flat float32 device array: the actor's eight tensors, then the critic's eight, each in
  *     parameters_to_vector order -- conv weight (32, F, 3, 3) and bias, fc1 weight (64, 32 npos) and bias, fc2 weight and bias, head
- *     weight and bias; mrl_cnn_policy_num_params(W, H, F, hidden, A) floats (0 for hidden != 64 or A != 6 or W, H < 3).  It is read
- *     in place in every call.  hidden must be 64; flags is 0 or MRL_POLICY_GREEDY, which both calls OR into their own flags
+ *     weight and bias; mrl_cnn_policy_num_params(W, H, F, hidden, A) floats (0 for hidden other than 64 and 512, or A != 6 or
+ *     W, H < 3).  It is read in place in every call.  flags is 0 or MRL_POLICY_GREEDY, which both calls OR into their own flags
  *     (mrl_rollout_cnn has no flags argument of its own).
+ *   mrl_cnn_policy.hidden is 64 or 512.  64 is the reference's notebook; 512 is its trainer's default (train/config.py:200, and the
+ *     kitchens' training command in train/torch_to_tfjs.py), where the networks are Conv2d(F, 256, 3 x 3, valid), ReLU, flatten,
+ *     Linear(256 npos, 512), ReLU, Linear(512, 512), ReLU, then Linear(512, 6) or Linear(512, 1), in the same tensor order.
+ *     What 512 runs: mrl_cnn_act and mrl_rollout_cnn, every mode, record and `players` mask, by a kernel of its own
+ *     (mrl_cnn_act_h512) -- the same samples, index map, arithmetic rule, head and record as below; fc1's chain
+ *     runs through the 256 channels in 8 blocks of 32 without setting a partial sum aside, so it is still ONE chain in ascending
+ *     order of torch's index.  Its LDS image is the larger of the 64 image below and 66 688 bytes, so it admits the same kitchens.
+ *     What 512 does not run, each refused with MRL_ERR_INVALID and nothing enqueued: mrl_mappo_update and
+ *     mrl_mappo_workspace_bytes ("hidden must be 64"), the bank calls (mrl_cnn_act_bank, mrl_rollout_cnn_bank,
+ *     mrl_mappo_bank_update: mrl_cnn_bank.hidden must be 64), MRL_CNN_RECURRENT, and the size queries with 512 | MRL_CNN_GRU_HIDDEN
+ *     (0 / refused).  A 512 policy learns through torch autograd on the same flat tensor.  Every other width is refused everywhere.
  *   Samples: (world n, seat p) for every seat whose bit is set in `players` (seats 0..31).  The kernel reads the int8 world-major
  *     block (N, P, H, W, F) where the simulator's most recent step wrote its observations -- its own OBS_WORLD_MAJOR tensor, the
  *     slot of mrl_set_observation_output, or ring slot (k - 1) mod T; where no step has run since that destination was set,
@@ -905,7 +916,7 @@ int mrl_agent_update(const mrl_wide_policy *policy, const mrl_ppo_optimizer *opt
  *     weights (32 rows of 9 F floats, padded to an odd count), 2 bytes per k, and the convolution's output, 32 rows of 32 npos + 1
  *     floats -- must fit 160 KiB.  The five standard two-player layouts do (Overcooked 9 x 5: 154 464 bytes; 5 x 4: 72 032; Simplecooked's rows are shorter); a larger kitchen or
  *     more players than that allows is refused, never computed wrongly.
- *   MRL_ERR_INVALID: a simulator that is neither Overcooked nor Simplecooked; hidden != 64; players == 0 or a bit >= P; a NULL policy, parameter array
+ *   MRL_ERR_INVALID: a simulator that is neither Overcooked nor Simplecooked; hidden other than 64 and 512; players == 0 or a bit >= P; a NULL policy, parameter array
  *     or workspace, or a NULL buffer but logits in a record; row >= T without MRL_CNN_VALUE_ONLY, row != T with it, or it without a
  *     record; workspace_bytes below mrl_cnn_workspace_bytes or a workspace off a 16-byte boundary; a shape beyond the limit; a
  *     capturing stream (row and step travel in kernel arguments, as for the sibling calls); a flag bit other than

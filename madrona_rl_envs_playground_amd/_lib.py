@@ -33,7 +33,8 @@ AGENT_ALL_ROWS, AGENT_VALUE_ONLY = 2, 4  # MRL_AGENT_*: flags of mrl_agent_act b
 WIDE_HIDDEN, WIDE_MAX_ACTIONS = 512, 64  # MRL_WIDE_*
 PPO_NORM_ADV, PPO_CLIP_VLOSS = 1, 2  # MRL_PPO_*
 CNN_VALUE_ONLY = 4  # MRL_CNN_VALUE_ONLY: flag of mrl_cnn_act beside POLICY_GREEDY
-CNN_HIDDEN, CNN_ACTIONS = 64, 6  # the one shape mrl_cnn_act runs
+CNN_HIDDEN, CNN_ACTIONS = 64, 6  # the shape every CNN path runs
+CNN_HIDDEN_WIDE = 512  # the reference trainer's default hidden_size: mrl_cnn_act and mrl_rollout_cnn run it too, nothing else does
 CNN_BANK_MAX_POLICIES = 256  # the rows an mrl_cnn_bank may hold
 CNN_RESAMPLE_ROBIN, CNN_RESAMPLE_RANDOM = 1, 2  # MRL_CNN_RESAMPLE_*
 CNN_RECURRENT = 16  # MRL_CNN_RECURRENT: bit of mrl_cnn_policy.flags and mrl_mappo_policy.flags; the structs are then the mrl_*_gru_* ones

@@ -67,11 +67,18 @@ class CnnPolicy(_FlatPolicy):
 
     def __init__(self, width, height, channels, hidden=64, num_actions=6, device="cuda:0"):
         self.width, self.height, self.channels, self.hidden, self.num_actions = int(width), int(height), int(channels), int(hidden), int(num_actions)
-        self._allocate(device, f"mrl_cnn_act runs hidden = {_lib.CNN_HIDDEN}, num_actions = {_lib.CNN_ACTIONS} and kitchens of at least 3 x 3")
+        self._allocate(device, f"mrl_cnn_act runs hidden = {_lib.CNN_HIDDEN} or {_lib.CNN_HIDDEN_WIDE}, num_actions = {_lib.CNN_ACTIONS} and "
+                               f"kitchens of at least 3 x 3")
 
     @property
     def num_params(self):
         return int(_lib.lib().mrl_cnn_policy_num_params(self.width, self.height, self.channels, self.hidden, self.num_actions))
+
+    def _need_hidden_64(self, what):
+        """``what`` is built on the hidden-64 kernels: the wide policy acts and rolls out, and learns through ``module()``"""
+        if self.hidden != _lib.CNN_HIDDEN:
+            raise ValueError(f"{what}: the device update, the banks and the recurrent policy run hidden = {_lib.CNN_HIDDEN} only; hidden = "
+                             f"{self.hidden} runs cnn_act and rollout_cnn, and learns with torch autograd on policy.module()")
 
     def desc(self):
         return _lib.CnnPolicyDesc(self.params.data_ptr(), self.hidden, 0)
@@ -153,6 +160,7 @@ class CnnPolicyBank(_PolicyBank):
 
     def __init__(self, width, height, channels, num_policies, hidden=64, num_actions=6, device="cuda:0"):
         self.width, self.height, self.channels, self.hidden, self.num_actions = int(width), int(height), int(channels), int(hidden), int(num_actions)
+        CnnPolicy._need_hidden_64(self, "CnnPolicyBank")
         super().__init__(num_policies, device)
 
     def desc(self):
@@ -368,6 +376,8 @@ class CnnGruPolicy(CnnPolicy):
 
     def __init__(self, width, height, channels, hidden=64, num_actions=6, device="cuda:0"):
         self.running = None
+        self.hidden = int(hidden)
+        self._need_hidden_64("CnnGruPolicy")
         super().__init__(width, height, channels, hidden, num_actions, device)
 
     @property
@@ -851,6 +861,8 @@ class MappoOptimizer(_AdamState):
     def __init__(self, policy, lr=5e-4, critic_lr=5e-4, betas=(0.9, 0.999), eps=1e-5):
         if not isinstance(policy, (CnnPolicy, MlpBasePolicy)):
             raise ValueError("policy must be a CnnPolicy or an MlpBasePolicy")
+        if isinstance(policy, CnnPolicy):
+            policy._need_hidden_64("MappoOptimizer")
         super().__init__(policy, betas, eps)
         self.lr, self.critic_lr = float(lr), float(critic_lr)
 
@@ -931,6 +943,8 @@ def mappo_update(policy, optimizer, record, ring, advantages, returns, indices, 
     Not built: active masks, PopArt, ``update_actor=False``, weight decay."""
     if not isinstance(policy, (CnnPolicy, MlpBasePolicy)) or not isinstance(optimizer, MappoOptimizer) or optimizer.policy is not policy:
         raise ValueError("policy must be a CnnPolicy or an MlpBasePolicy (plain or recurrent) and optimizer the MappoOptimizer made for it")
+    if isinstance(policy, CnnPolicy):
+        policy._need_hidden_64("mappo_update")
     policy._mappo_check(record, ring)  # the record is the policy's kind, and so is the ring
     if value_norm is not None and not isinstance(value_norm, ValueNorm):
         raise ValueError("value_norm must be a ValueNorm or None")

@@ -6,6 +6,7 @@
 #include "cnn_policy.hpp"
 #include "cnn_bank.hpp"
 #include "cnn_gru.hpp"
+#include "cnn_h512.hpp"
 #include "cnn_update.hpp"
 #include "mlpbase_policy.hpp"
 #include "mlpbase_bank.hpp"
@@ -117,9 +118,10 @@ static int act_seats(mrl::ActArgs &a, const char *what, mrl_sim *sim, uint32_t p
     return MRL_OK;
 }
 
-// Everything mrl_cnn_act and mrl_rollout_cnn check alike; fills `args` but for the observation pointer, the rows and the step.
-static int cnn_prepare(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, const mrl_cnn_record *record, void *hip_stream,
-                       const char *what, mrl::CnnActArgs *args)
+// Everything mrl_cnn_act and mrl_rollout_cnn check alike, for the kernel of width `hidden` (64: mrl_cnn_act, 512: mrl_cnn_act_h512,
+// whose LDS image is its own); fills `args` but for the observation pointer, the rows and the step.
+static int cnn_prepare_width(uint32_t hidden, mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, const mrl_cnn_record *record,
+                             void *hip_stream, const char *what, mrl::CnnActArgs *args)
 {
     // the two kitchens export the same slab, flags and slot ids (Simplecooked's ExportID is Overcooked's list); the kernels take
     // W, H, F and P at run time, so F = 5P + 10 and P = 1 need nothing of their own
@@ -130,7 +132,7 @@ static int cnn_prepare(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *pol
     }
     const char *sharded = "this simulator is a rank of an exchanged batch (mrl_exchange_create); sharded simulators are out of scope";
     if (int rc = act_scope_refusal(what, sim->exchange.mine ? sharded : nullptr, hip_stream)) return rc;
-    if (!policy || !policy->params_dev || policy->hidden != mrl::kCnnHidden || (policy->flags & ~(uint32_t)MRL_POLICY_GREEDY)) {
+    if (!policy || !policy->params_dev || policy->hidden != hidden || (policy->flags & ~(uint32_t)MRL_POLICY_GREEDY)) {
         mrl::set_error("%s: null policy or parameter array, hidden other than 64, or policy flags other than MRL_POLICY_GREEDY", what);
         return MRL_ERR_INVALID;
     }
@@ -151,9 +153,10 @@ static int cnn_prepare(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *pol
     a = mrl::CnnActArgs{};
     if (int rc = act_seats(a, what, sim, players, P, done, action)) return rc;
     const mrl::CnnLds lds = mrl::cnn_lds(W, H, F);
-    if (lds.total > mrl::kCnnLdsLimit) {
+    const uint32_t image = hidden == mrl::kCnnH512Hidden ? mrl::cnn_h512_lds(W, H, F).total : lds.total;
+    if (image > mrl::kCnnLdsLimit) {
         mrl::set_error("%s: a %u x %u kitchen with %u channels needs an LDS image of %u bytes per workgroup, the limit is %u", what, W, H, F,
-                       lds.total, mrl::kCnnLdsLimit);
+                       image, mrl::kCnnLdsLimit);
         return MRL_ERR_INVALID;
     }
     a.params = policy->params_dev;
@@ -161,6 +164,20 @@ static int cnn_prepare(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *pol
     a.W = W, a.H = H, a.F = F;
     a.lds = lds;
     return MRL_OK;
+}
+
+// the plain act and everything built on it -- the banks, the recurrent act -- run hidden 64 and refuse every other width
+static int cnn_prepare(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, const mrl_cnn_record *record, void *hip_stream,
+                       const char *what, mrl::CnnActArgs *args)
+{
+    return cnn_prepare_width(mrl::kCnnHidden, sim, players, policy, record, hip_stream, what, args);
+}
+
+// mrl_cnn_act and mrl_rollout_cnn with a plain policy of hidden 512
+static int cnn_h512_prepare(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, const mrl_cnn_record *record, void *hip_stream,
+                            const char *what, mrl::CnnActArgs *args)
+{
+    return cnn_prepare_width(mrl::kCnnH512Hidden, sim, players, policy, record, hip_stream, what, args);
 }
 
 // Everything mrl_mlpbase_act and mrl_rollout_mlpbase check alike; fills `args` but for the rows, the seed, the step and the flags.
@@ -349,6 +366,13 @@ struct CnnNet {
     static uint64_t workspace_floats(const UpdatePolicy &p, uint32_t B, uint32_t K) { return mappo_workspace(actor_params(p), B, K).total; }
     static uint64_t num_params(const UpdatePolicy &p) { return mrl_cnn_policy_num_params(p.width, p.height, p.channels, p.hidden, kCnnActions); }
     template <class... Rest> static void launch_update(const UpdatePolicy &p, Rest &&...rest) { launch_mappo_update(p, rest...); }
+};
+
+// The kitchens' CNN at hidden 512 as the act and the rollout see it (cnn_h512.hpp): CnnNet's checks and plumbing, its own kernel
+// and LDS image.  The update and the banks do not run this width and never see this type.
+struct CnnH512Net : CnnNet {
+    static constexpr auto prepare = cnn_h512_prepare;
+    static constexpr auto launch_act = launch_cnn_act_h512;
 };
 
 // The balance beam's MLPBase: it reads the simulator's OBSERVATION tensor in place and copies it into the record (obs_row),
@@ -857,6 +881,9 @@ uint64_t mrl_cnn_policy_num_params(uint32_t width, uint32_t height, uint32_t cha
     // the recurrent shape: hidden | MRL_CNN_GRU_HIDDEN
     const uint64_t gru = hidden == (mrl::kCnnHidden | MRL_CNN_GRU_HIDDEN) ? 2 * mrl::kGruParams : 0;
     if (gru) hidden = mrl::kCnnHidden;
+    // hidden 512: the act and the rollout (cnn_h512.hpp)
+    if (hidden == mrl::kCnnH512Hidden && num_actions == mrl::kCnnActions && width >= 3 && height >= 3 && channels != 0)
+        return mrl::cnn_h512_net_params(width, height, channels, num_actions) + mrl::cnn_h512_net_params(width, height, channels, 1);
     if (hidden != mrl::kCnnHidden || num_actions != mrl::kCnnActions || width < 3 || height < 3 || channels == 0) return 0;
     return mrl::cnn_net_params(width, height, channels, num_actions) + mrl::cnn_net_params(width, height, channels, 1) + gru;
 }
@@ -932,6 +959,9 @@ int mrl_cnn_act(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, co
         return mrl::cnn_gru_act("mrl_cnn_act", sim, players, reinterpret_cast<const mrl_cnn_gru_policy *>(policy),
                                 reinterpret_cast<const mrl_cnn_gru_record *>(record), row, seed, step, flags, workspace_dev, workspace_bytes,
                                 hip_stream);
+    if (policy && policy->hidden == mrl::kCnnH512Hidden)
+        return mrl::act<mrl::CnnH512Net>("mrl_cnn_act", sim, players, policy, record, row, seed, step, flags, workspace_dev, workspace_bytes,
+                                         hip_stream);
     return mrl::act<CnnNet>("mrl_cnn_act", sim, players, policy, record, row, seed, step, flags, workspace_dev, workspace_bytes, hip_stream);
 }
 
@@ -966,6 +996,8 @@ int mrl_rollout_cnn(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy
     if (policy && (policy->flags & MRL_CNN_RECURRENT))
         return mrl::cnn_gru_rollout("mrl_rollout_cnn", sim, players, reinterpret_cast<const mrl_cnn_gru_policy *>(policy),
                                     reinterpret_cast<const mrl_cnn_gru_record *>(record), obs_ring_dev, seed, first_step, hip_stream);
+    if (policy && policy->hidden == mrl::kCnnH512Hidden)
+        return mrl::rollout<mrl::CnnH512Net>("mrl_rollout_cnn", sim, players, policy, record, obs_ring_dev, seed, first_step, hip_stream);
     return mrl::rollout<CnnNet>("mrl_rollout_cnn", sim, players, policy, record, obs_ring_dev, seed, first_step, hip_stream);
 }
 
