@@ -8,7 +8,8 @@
 //   channel loop  the 256 conv channels run as 8 blocks of 32.  A block's conv weights (the plain act's 32 x 9 F floats) go to
 //                 region A beside the rows, cnn_conv_tile writes the block's 32 npos activations to the plain act's image, and
 //                 the image is multiplied straight into fc1: wave w owns the column blocks 4 w .. 4 w + 3 of 32 columns each,
-//                 64 accumulator registers per lane that live across all 8 blocks.  The next block's conv weights are
+//                 64 accumulator registers per lane for the block's own sum and 64 for the running sum of the block sums, which
+//                 live across all 8 blocks.  The next block's conv weights are
 //                 stored to LDS before the products, so a block costs two barriers.
 //   B operands    fc1 (3 to 11 MB a net), fc2 (1 MB) and the head are read from L2 straight into registers: lane (r, half)
 //                 owns column r of its block, i.e. one row of torch's weight, and loads 8 consecutive k of it as two 16-byte
@@ -138,9 +139,19 @@ __global__ void __launch_bounds__(kCnnThreads) mrl_cnn_act_h512(CnnActArgs a)
                 conv_lds[c * l.conv_ld + k] = next[e];
             }
         }
-        h512_products<4>(a_row, kb, w_row, odd, acc);
+        // the block's own sum from 0, then one add per output into the running sum (cnn_h512.hpp says why)
+        f32x16 part[4];
 #pragma unroll
-        for (int j = 0; j < 4; j++) w_row[j] += kb;
+        for (int j = 0; j < 4; j++)
+#pragma unroll
+            for (int e = 0; e < 16; e++) part[j][e] = 0.0f;
+        h512_products<4>(a_row, kb, w_row, odd, part);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+#pragma unroll
+            for (int e = 0; e < 16; e++) acc[j][e] += part[j][e];
+            w_row[j] += kb;
+        }
         __syncthreads();  // the activations are read, the next conv weights in place
     }
 

@@ -3,13 +3,15 @@
 // (C ABI: mrl_cnn_act and mrl_rollout_cnn with mrl_cnn_policy.hidden = 512).  The kernel lives in
 // cnn_h512.hip; capi_mappo.hip validates the arguments.  The index map is cnn_policy.hpp's.
 //
-// THE ORDER OF EVERY SUM.  As in the plain act, every dot product is ONE chain of fused multiply-adds from 0 in ascending order of
+// THE ORDER OF EVERY SUM.  As in the plain act, a dot product is a chain of fused multiply-adds from 0 in ascending order of
 // torch's own flattened weight index, and the bias is added to the finished sum:
 //   convolution   k = f 9 + i 3 + j, an odd K padded with one zero product (cnn_conv_pass);
 //   fc1           the 256 channels run as 8 blocks of 32.  Block b's 32 npos activations are the contiguous range
-//                 [b 32 npos, (b + 1) 32 npos) of torch's index c npos + ow (H - 2) + oh, and the accumulators stay in registers
-//                 from block to block: k runs 0, 1, ..., 256 npos - 1 without a partial sum being set aside;
-//   fc2, head     k = 0 .. 511.
+//                 [b 32 npos, (b + 1) 32 npos) of torch's index c npos + ow (H - 2) + oh.  Each block's sum is its OWN chain from 0
+//                 over that range, and the eight block sums are added in ascending b to a running sum that starts at 0 (both sets
+//                 of accumulators stay in registers).  One chain over all 256 npos products -- 6400 at npos 25 -- drifted to 9 times
+//                 torch float32's own distance from the float64 module there; chains of 32 npos do not;
+//   fc2, head     k = 0 .. 511, one chain.
 // A matrix instruction takes k = 2 kk (lanes 0..31) and 2 kk + 1 (lanes 32..63), in that order.
 #pragma once
 

@@ -20,7 +20,10 @@ from mappo_twin import FACTOR, STATS, Config, huber_loss, mse_loss, value_norm_u
 A, HIDDEN, GRU = 6, 64, 25088
 W_HH = 3 * HIDDEN * HIDDEN
 # key -> game; the largest custom kitchen tests/kitchen_shape_cases.py lists as admitted is where the GRU image overlays most
-KITCHENS = {"k3x3p1": "overcooked", "cramped_room": "overcooked", "simple/1p": "simplecooked", "k8x5p4": "overcooked"}
+KITCHENS = {"k3x3p1": "overcooked", "cramped_room": "overcooked", "simple/1p": "simplecooked", "k8x5p4": "overcooked",
+            # tests/cnn_gru_shape_cases.py: the table's kitchens on either side of the two LDS crossovers, P = 3, npos 12, 13 and 25
+            "forced_coordination": "overcooked", "k15x3p2": "overcooked", "k4x4p3": "overcooked", "k6x5p4": "overcooked",
+            "counter_circuit": "overcooked", "multiplayer_schelling/1p": "overcooked"}
 CHUNKS = (1, 2, 10, 16)
 
 
@@ -39,11 +42,19 @@ def shape(key):
     return int(p["width"]), int(p["height"]), players, 5 * players + (10 if KITCHENS[key] == "simplecooked" else 16)
 
 
+# seed of a kitchen's parameters where the default's critic sits so far above its normalised returns (values near +4) that the
+# reference's one-sided Huber term (``mappo_twin.huber_loss``: e < -delta contributes nothing) gives every sample of ``update_case``
+# a zero loss and the critic no gradient at all, whatever the data's seed (a condition tests/test_cnn_gru_shapes_api.py asserts):
+# replaced here, not excused there
+PARAM_SEEDS = {"k4x4p3": 30}
+
+
 @functools.lru_cache(maxsize=None)
-def params_of(key, seed=29):
+def params_of(key, seed=None):
     """float32 flat parameters of a trained net's scale: He-scaled matrices, a head that spreads the probabilities, the GRU's
     matrices orthogonal, every bias (the GRU's too) of a tenth, LayerNorm weights away from 1"""
     w, h, _, f = shape(key)
+    seed = PARAM_SEEDS.get(key, 29) if seed is None else seed
     torch.manual_seed(seed)
     module = CnnGruActorCritic(w, h, f)
     with torch.no_grad():

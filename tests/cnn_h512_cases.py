@@ -30,9 +30,8 @@ FORWARD = [(key, n, weights, seats) for key in KITCHENS for n in WORLDS for weig
 INTEGER_KEYS = ("cramped_room", "asymmetric_advantages")
 
 @functools.lru_cache(maxsize=None)
-def make_module(key, weights):
+def module_of(w, h, f, weights):
     """the reference's initialisation (head gain 0.01), or ``cnn_twin.make_module``'s "trained" perturbation of it"""
-    w, h, _, f = KITCHENS[key][2]
     torch.manual_seed(twin.MODULE_SEED)
     module = CnnActorCritic(w, h, f, hidden=HIDDEN)
     if weights == "trained":
@@ -43,6 +42,10 @@ def make_module(key, weights):
                 else:
                     p.normal_(0.0, 0.3 if "action_out" in name or "v_out" in name else (2.0 / p[0].numel()) ** 0.5)
     return module
+
+def make_module(key, weights):
+    w, h, _, f = KITCHENS[key][2]
+    return module_of(w, h, f, weights)
 
 @functools.lru_cache(maxsize=None)
 def observations(key, n, seed):
@@ -77,19 +80,22 @@ def reference(key, n, weights):
             "d_logits": float(np.abs(l32 - logits).max())}
 
 @functools.lru_cache(maxsize=None)
-def integer_case(key, n=33, seed=99):
-    """small-integer layers and observations as ``cnn_twin.integer_layers`` builds them at 64, every partial sum below 2^24"""
-    w, h, p, f = KITCHENS[key][2]
+def integer_case_of(w, h, p, f, n=33, seed=99, fc1_one_in=64):
+    """small-integer layers and observations as ``cnn_twin.integer_layers`` builds them at 64, every partial sum below 2^24; one
+    weight of fc1 in ``fc1_one_in`` is nonzero"""
     k2, rng, layers = CHANNELS * (w - 2) * (h - 2), np.random.default_rng(seed), {}
     sparse = lambda shape, lo, hi, one_in: (rng.integers(lo, hi, size=shape) * (rng.uniform(size=shape) < 1.0 / one_in)).astype(np.int64)  # noqa: E731
     for name, out in (("actor", twin.A), ("critic", 1)):
         c, ff, i, j = np.meshgrid(np.arange(CHANNELS), np.arange(f), np.arange(3), np.arange(3), indexing="ij")
         conv = ((c * 131 + ff * 31 + i * 7 + j * 3) % 9 - 4 + rng.integers(-1, 2, size=c.shape)).astype(np.int64)
         o, k = np.meshgrid(np.arange(HIDDEN), np.arange(k2), indexing="ij")
-        fc1 = (((o * 17 + k * 5) % 7 - 3) * (rng.uniform(size=o.shape) < 1.0 / 64)).astype(np.int64)
+        fc1 = (((o * 17 + k * 5) % 7 - 3) * (rng.uniform(size=o.shape) < 1.0 / fc1_one_in)).astype(np.int64)
         bias = lambda size: rng.integers(-3, 4, size=size).astype(np.int64)  # noqa: E731
         layers[name] = [(conv, bias(CHANNELS)), (fc1, bias(HIDDEN)), (sparse((HIDDEN, HIDDEN), -1, 2, 32), bias(HIDDEN)),
                         (sparse((out, HIDDEN), -2, 3, 16), bias(out))]
     size = (n, p, h, w, f)
     obs = (rng.integers(-1, 4, size=size) * (rng.uniform(size=size) < 0.2)).astype(np.int8)
     return layers, obs
+
+def integer_case(key, n=33, seed=99):
+    return integer_case_of(*KITCHENS[key][2], n=n, seed=seed)

@@ -238,9 +238,15 @@ def stat_margins(key):
 
 @pytest.mark.parametrize("case", UPDATE_CASES, ids=lambda c: "-".join(str(x) for x in c))
 def test_gradient_stats_and_step_match_the_twin(hip_lib, case):
+    gradient_stats_and_step_match_the_twin(case, twin_rows(case), stat_margins(case[0]))
+
+
+def gradient_stats_and_step_match_the_twin(case, rows, stat_d):
+    """one row of a case on the device against ``rows``, the twin's and the float32 CPU row; ``stat_d``: d of every scalar stat
+    (also for tests/test_gpu_cnn_gru_shapes.py)"""
     key, L, Bc = case
     params, batch, ids = twin.update_case(*case)
-    exact, single = twin_rows(case)
+    exact, single = rows
     device = Device(key, params, batch)
     stats, grads = device.update(ids)
     after = device.state()
@@ -248,7 +254,7 @@ def test_gradient_stats_and_step_match_the_twin(hip_lib, case):
     ratios = {"grad": distance(grads[0], exact["grad"]) / d_grad}
     for name in twin.STATS:
         if name != "clipfrac":
-            ratios[name] = abs(float(stats[0][STAT(name)]) - exact["stats"][name]) / stat_margins(key)[name]
+            ratios[name] = abs(float(stats[0][STAT(name)]) - exact["stats"][name]) / stat_d[name]
     d_state = np.maximum(np.abs(single["state"] - exact["state"]), np.abs(exact["state"]) * 2.0 ** -24)
     ratios["value_norm"] = float((np.abs(after["value_norm"] - exact["state"]) / d_state).max())
     print(case, "measured / d:", {k: round(float(v), 2) for k, v in ratios.items()}, "d(grad) = %.2e" % d_grad)
