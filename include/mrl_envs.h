@@ -882,7 +882,7 @@ int mrl_agent_update(const mrl_wide_policy *policy, const mrl_ppo_optimizer *opt
  *     What 512 does not run, each refused with MRL_ERR_INVALID and nothing enqueued: mrl_mappo_update and
  *     mrl_mappo_workspace_bytes ("hidden must be 64"), the bank calls (mrl_cnn_act_bank, mrl_rollout_cnn_bank,
  *     mrl_mappo_bank_update: mrl_cnn_bank.hidden must be 64), MRL_CNN_RECURRENT, and the size queries with 512 | MRL_CNN_GRU_HIDDEN
- *     (0 / refused).  A 512 policy learns through torch autograd on the same flat tensor.  Every other width is refused everywhere.
+ *     (0 / refused).  A 512 policy learns through mrl_mappo_update with MRL_MAPPO_H512 (below) or torch autograd on the same flat tensor.  Every other width is refused everywhere.
  *   Samples: (world n, seat p) for every seat whose bit is set in `players` (seats 0..31).  The kernel reads the int8 world-major
  *     block (N, P, H, W, F) where the simulator's most recent step wrote its observations -- its own OBS_WORLD_MAJOR tensor, the
  *     slot of mrl_set_observation_output, or ring slot (k - 1) mod T; where no step has run since that destination was set,
@@ -1065,7 +1065,7 @@ int mrl_rollout_cnn_bank(mrl_sim *sim, uint32_t players, const mrl_cnn_bank *ban
  *     boundary; unknown flag bits; a capturing stream.  K == 0 enqueues nothing.  mrl_mappo_workspace_bytes refuses the same
  *     shapes and a NULL out.  Not built: active masks, PopArt, update_actor = False, weight decay.  The recurrent network
  *     (MRL_CNN_RECURRENT in policy->flags) is described behind this call.
- *   mrl_mappo_policy.flags: MRL_CNN_RECURRENT or 0; other bits are not read. */
+ *   mrl_mappo_policy.flags: MRL_CNN_RECURRENT, MRL_MAPPO_H512 (below) or 0; other bits are not read. */
 enum { MRL_MAPPO_VALUENORM = 1, MRL_MAPPO_HUBER_LOSS = 2, MRL_MAPPO_CLIPPED_VALUE_LOSS = 4, MRL_MAPPO_MAX_GRAD_NORM = 8 };
 typedef struct mrl_mappo_policy {
     const float *params_dev;     /* as mrl_cnn_policy */
@@ -1096,6 +1096,27 @@ int mrl_mappo_update(const mrl_mappo_policy *policy, const mrl_mappo_optimizer *
                      const mrl_mappo_config *cfg, float *value_norm_state_dev_or_null /* (3) */, void *workspace_dev,
                      uint64_t workspace_bytes, float *stats_dev_or_null /* (K, 8) */, float *grads_dev_or_null /* (K, P) */,
                      int gpu_id, void *hip_stream);
+
+/* mrl_mappo_update for a policy of hidden_size 512 (the reference trainer's default; mrl_cnn_act and mrl_rollout_cnn run it),
+ * "mrl_mappo_h512_update" in messages and documents: the same structs, argument list and contract -- losses, gradient rules,
+ * ValueNorm recurrence, clip, Adam, the stats row, the optional gradient rows.  Like the recurrent networks it adds no exported
+ * symbol and travels through the existing calls, MRL_ABI_VERSION stays 4:
+ *     mrl_mappo_update with policy->hidden == 512 and policy->flags == MRL_MAPPO_H512;
+ *     mrl_mappo_workspace_bytes with hidden = 512 | MRL_MAPPO_H512_HIDDEN ("mrl_mappo_h512_workspace_bytes").
+ * Without these bits both calls refuse 512 as they always did.  DESIGN.md section 31.
+ *   A row is processed in slabs of at most 2048 consecutive samples of its index list.  Per slab: the act's forward pass with every
+ *     layer's output stored in the workspace; the loss head; each layer's weight gradient as a matrix product over the slab's
+ *     samples, split into 8 contiguous shares whose sums are added in ascending order; each activation gradient as a matrix
+ *     product over the layer's 512 outputs; the convolution's weight gradient.  The slabs' sums are added in ascending order.  The
+ *     workspace holds one slab and stops growing with B there.  No float atomics, no wait between workgroups: the same inputs
+ *     give the same bits on every run, one call of K rows the bits of K calls of one row.
+ *   MRL_ERR_INVALID, nothing changed: what mrl_mappo_update refuses, with hidden != 512 in place of hidden != 64; any policy
+ *     flag beside MRL_MAPPO_H512 (the recurrent bit included); a kitchen whose LDS image -- the larger of mrl_cnn_act's at 512 and mrl_cnn_act's at 64
+ *     plus 256 bytes -- does not fit 160 KiB (the message names the bytes) or with more than 42 channels; a workspace below
+ *     the size query's; a capturing stream.
+ *   Not built: banks, the recurrent network and cross-play at 512, other widths, bf16, active masks, graph capture. */
+enum { MRL_MAPPO_H512 = 32 };             /* bit of mrl_mappo_policy.flags: mrl_mappo_update runs the layered update of hidden 512 */
+enum { MRL_MAPPO_H512_HIDDEN = 0x1000 };  /* or-ed into `hidden` = 512 in mrl_mappo_workspace_bytes: the layered update's workspace */
 
 /* The RECURRENT CNN actor-critic for the kitchens: what the reference runs with --use_recurrent_policy on Overcooked and
  * Simplecooked (R_Actor / R_Critic put an RNNLayer -- one GRU of width hidden_size and a LayerNorm, train/MAPPO/utils/rnn.py --

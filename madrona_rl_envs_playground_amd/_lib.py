@@ -34,7 +34,9 @@ WIDE_HIDDEN, WIDE_MAX_ACTIONS = 512, 64  # MRL_WIDE_*
 PPO_NORM_ADV, PPO_CLIP_VLOSS = 1, 2  # MRL_PPO_*
 CNN_VALUE_ONLY = 4  # MRL_CNN_VALUE_ONLY: flag of mrl_cnn_act beside POLICY_GREEDY
 CNN_HIDDEN, CNN_ACTIONS = 64, 6  # the shape every CNN path runs
-CNN_HIDDEN_WIDE = 512  # the reference trainer's default hidden_size: mrl_cnn_act and mrl_rollout_cnn run it too, nothing else does
+CNN_HIDDEN_WIDE = 512  # the reference trainer's default hidden_size: mrl_cnn_act, mrl_rollout_cnn and mrl_mappo_h512_update run it
+MAPPO_H512, MAPPO_H512_HIDDEN = 32, 0x1000  # MRL_MAPPO_H512: bit of mrl_mappo_policy.flags; MRL_MAPPO_H512_HIDDEN: or-ed into hidden = 512 in the size query
+H512_SLAB, H512_SHARES = 2048, 8  # kH512Slab, kH512Shares: a slab's samples and the shares of its sum (cnn_h512_update.hpp)
 CNN_BANK_MAX_POLICIES = 256  # the rows an mrl_cnn_bank may hold
 CNN_RESAMPLE_ROBIN, CNN_RESAMPLE_RANDOM = 1, 2  # MRL_CNN_RESAMPLE_*
 CNN_RECURRENT = 16  # MRL_CNN_RECURRENT: bit of mrl_cnn_policy.flags and mrl_mappo_policy.flags; the structs are then the mrl_*_gru_* ones

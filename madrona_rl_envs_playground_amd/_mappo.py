@@ -945,6 +945,14 @@ def mappo_update(policy, optimizer, record, ring, advantages, returns, indices, 
         raise ValueError("policy must be a CnnPolicy or an MlpBasePolicy (plain or recurrent) and optimizer the MappoOptimizer made for it")
     if isinstance(policy, CnnPolicy):
         policy._need_hidden_64("mappo_update")
+    return _mappo_run(0, policy, optimizer, record, ring, advantages, returns, indices, value_norm, clip_param, entropy_coef, value_loss_coef,
+                      max_grad_norm, huber_delta, use_huber_loss, use_clipped_value_loss, use_max_grad_norm, stats, grads)
+
+
+def _mappo_run(layered, policy, optimizer, record, ring, advantages, returns, indices, value_norm, clip_param, entropy_coef, value_loss_coef,
+               max_grad_norm, huber_delta, use_huber_loss, use_clipped_value_loss, use_max_grad_norm, stats, grads):
+    """``mappo_update`` and ``mappo_update_h512`` behind their own checks of the policy and the optimizer; ``layered``: the bit
+    ``mappo_update_h512`` adds to the policy struct's flags (``MRL_MAPPO_H512``), or 0"""
     policy._mappo_check(record, ring)  # the record is the policy's kind, and so is the ring
     if value_norm is not None and not isinstance(value_norm, ValueNorm):
         raise ValueError("value_norm must be a ValueNorm or None")
@@ -960,6 +968,8 @@ def mappo_update(policy, optimizer, record, ring, advantages, returns, indices, 
         wanted.append(("value_norm.state", value_norm.state, f32, 3))
     _require_tensors(wanted, device)
     (entry, _), shape, batch_type, obs = policy._mappo_batch(record, ring, count)  # the policy's own entry point and batch
+    if layered:
+        shape.flags |= layered
     opt = _lib.MappoOptimizerDesc(p.data_ptr(), optimizer.exp_avg.data_ptr(), optimizer.exp_avg_sq.data_ptr(), optimizer.step)
     batch = batch_type(obs.data_ptr(), record.actions.data_ptr(), record.logprobs.data_ptr(), record.values.data_ptr(), returns.data_ptr(),
                        advantages.data_ptr(), count)
@@ -968,3 +978,39 @@ def mappo_update(policy, optimizer, record, ring, advantages, returns, indices, 
     return _run_update(entry, (_lib.base_ref(shape), ctypes.byref(opt), _lib.base_ref(batch)), indices,
                        (ctypes.byref(cfg), value_norm.state.data_ptr() if value_norm is not None else None), optimizer,
                        len(_lib.MAPPO_STATS), MappoResult, stats, grads)
+
+
+class MappoOptimizerH512(_AdamState):
+    """``MappoOptimizer`` for a ``CnnPolicy`` of ``hidden`` 512, the reference trainer's default width: the same state and
+    attributes, and the scratch the layered update (``mrl_mappo_update`` with ``MRL_MAPPO_H512``) asks for (one slab of ``_lib.H512_SLAB`` samples' activations for both
+    nets, whatever the minibatch size beyond that).  It accepts no other policy; ``MappoOptimizer`` accepts no such policy."""
+
+    def __init__(self, policy, lr=5e-4, critic_lr=5e-4, betas=(0.9, 0.999), eps=1e-5):
+        if not isinstance(policy, CnnPolicy) or isinstance(policy, CnnGruPolicy) or policy.hidden != _lib.CNN_HIDDEN_WIDE:
+            raise ValueError(f"MappoOptimizerH512: policy must be a plain CnnPolicy of hidden = {_lib.CNN_HIDDEN_WIDE}; hidden = "
+                             f"{_lib.CNN_HIDDEN} and the recurrent policy learn with MappoOptimizer and mappo_update")
+        super().__init__(policy, betas, eps)
+        self.lr, self.critic_lr = float(lr), float(critic_lr)
+
+    def workspace_bytes(self, minibatch_size, num_minibatches):
+        """``mrl_mappo_workspace_bytes`` with ``512 | MRL_MAPPO_H512_HIDDEN`` for this policy's kitchen."""
+        p, out = self.policy, ctypes.c_uint64(0)
+        _lib.check(_lib.lib().mrl_mappo_workspace_bytes(p.width, p.height, p.channels, p.hidden | _lib.MAPPO_H512_HIDDEN, int(minibatch_size),
+                                                        int(num_minibatches), ctypes.byref(out)))
+        return int(out.value)
+
+
+def mappo_update_h512(policy, optimizer, record, ring, advantages, returns, indices, value_norm=None, clip_param=0.2, entropy_coef=0.01,
+                      value_loss_coef=1.0, max_grad_norm=10.0, huber_delta=10.0, use_huber_loss=True, use_clipped_value_loss=True,
+                      use_max_grad_norm=True, stats=True, grads=False):
+    """``mappo_update`` for a ``CnnPolicy`` of ``hidden`` 512 and its ``MappoOptimizerH512`` (``mrl_mappo_update`` with ``MRL_MAPPO_H512``): the same
+    arguments, losses, ValueNorm, clip, Adam and ``MappoResult``, on the device, enqueued on torch's current stream.  ``record`` and
+    ``ring`` are what ``rollout_cnn`` filled under the policy.  Each row runs in slabs of ``_lib.H512_SLAB`` samples, a launch per
+    layer.  Not built at this width: banks, the recurrent policy, active masks, graph capture."""
+    if (not isinstance(policy, CnnPolicy) or isinstance(policy, CnnGruPolicy) or policy.hidden != _lib.CNN_HIDDEN_WIDE or
+            not isinstance(optimizer, MappoOptimizerH512) or optimizer.policy is not policy):
+        raise ValueError(f"mappo_update_h512: policy must be a plain CnnPolicy of hidden = {_lib.CNN_HIDDEN_WIDE} and optimizer the "
+                         f"MappoOptimizerH512 made for it; every other policy learns with MappoOptimizer and mappo_update")
+    return _mappo_run(_lib.MAPPO_H512, policy, optimizer, record, ring, advantages, returns, indices, value_norm, clip_param,
+                      entropy_coef, value_loss_coef, max_grad_norm, huber_delta, use_huber_loss, use_clipped_value_loss, use_max_grad_norm,
+                      stats, grads)

@@ -7,6 +7,7 @@
 #include "cnn_bank.hpp"
 #include "cnn_gru.hpp"
 #include "cnn_h512.hpp"
+#include "cnn_h512_update.hpp"
 #include "cnn_update.hpp"
 #include "mlpbase_policy.hpp"
 #include "mlpbase_bank.hpp"
@@ -22,6 +23,25 @@ static const char *mappo_shape_error(uint32_t width, uint32_t height, uint32_t c
     if (width < 3 || height < 3 || channels == 0) return "the kitchen must be at least 3 x 3 with at least one channel";
     if ((uint64_t)width * height * channels > 65535u) return "the kitchen's LDS image does not fit one workgroup's 160 KiB";
     if (mrl::cnn_update_lds(width, height, channels).total > mrl::kCnnLdsLimit) return "the kitchen's LDS image does not fit one workgroup's 160 KiB";
+    if (minibatch_size == 0) return "minibatch_size must be positive";
+    return nullptr;
+}
+
+// what mrl_mappo_h512_workspace_bytes and mrl_mappo_h512_update refuse alike: nullptr when the shape can run, else why not (the
+// LDS image named in bytes, as mrl_cnn_act names it)
+static const char *mappo_h512_shape_error(uint32_t width, uint32_t height, uint32_t channels, uint32_t hidden, uint32_t minibatch_size)
+{
+    static thread_local char image[160];
+    if (hidden != mrl::kCnnH512Hidden) return "hidden must be 512";
+    if (width < 3 || height < 3 || channels == 0) return "the kitchen must be at least 3 x 3 with at least one channel";
+    if ((uint64_t)width * height * channels > 65535u || 9u * channels > 128u * mrl::kH512ConvSlabs)
+        return "the kitchen's rows or its 9 F patch columns are beyond what a workgroup holds (65535 bytes, 384 columns)";
+    const uint32_t bytes = mrl::h512_update_lds(width, height, channels);
+    if (bytes > mrl::kCnnLdsLimit) {
+        snprintf(image, sizeof image, "a %u x %u kitchen with %u channels needs an LDS image of %u bytes per workgroup, the limit is %u", width,
+                 height, channels, bytes, mrl::kCnnLdsLimit);
+        return image;
+    }
     if (minibatch_size == 0) return "minibatch_size must be positive";
     return nullptr;
 }
@@ -373,6 +393,26 @@ struct CnnNet {
 struct CnnH512Net : CnnNet {
     static constexpr auto prepare = cnn_h512_prepare;
     static constexpr auto launch_act = launch_cnn_act_h512;
+};
+
+// The kitchens' CNN at hidden 512 as mrl_mappo_h512_update sees it (cnn_h512_update.hpp): mappo_update's refusals with the layered
+// update's own shape check, workspace and launches.  It trains one policy: there are no members.
+struct CnnH512UpdateNet : CnnNet {
+    static constexpr const char *kSizer = "mrl_mappo_h512_workspace_bytes";  // (mrl_mappo_workspace_bytes with 512 | MRL_MAPPO_H512_HIDDEN)
+    static const char *shape_error(const UpdatePolicy &p, uint32_t minibatch_size, char *described, size_t room)
+    {
+        snprintf(described, room, "width %u, height %u, channels %u, hidden %u", p.width, p.height, p.channels, p.hidden);
+        return mappo_h512_shape_error(p.width, p.height, p.channels, p.hidden, minibatch_size);
+    }
+    static uint64_t actor_params(const UpdatePolicy &p) { return cnn_h512_net_params(p.width, p.height, p.channels, kCnnActions); }
+    static uint64_t workspace_floats(const UpdatePolicy &p, uint32_t B, uint32_t K) { return h512_workspace(p.width, p.height, p.channels, B, K).total; }
+    static uint64_t num_params(const UpdatePolicy &p) { return actor_params(p) + cnn_h512_net_params(p.width, p.height, p.channels, 1); }
+    static void launch_update(const UpdatePolicy &p, const mrl_mappo_optimizer &opt, const Batch &batch, const int32_t *indices, uint32_t K,
+                              uint32_t B, const mrl_mappo_config &cfg, float *value_norm_state, float *workspace, float *stats, float *grads,
+                              hipStream_t stream, const MappoMembers &)
+    {
+        launch_mappo_h512_update(p, opt, batch, indices, K, B, cfg, value_norm_state, workspace, stats, grads, stream);
+    }
 };
 
 // The balance beam's MLPBase: it reads the simulator's OBSERVATION tensor in place and copies it into the record (obs_row),
@@ -916,6 +956,18 @@ uint64_t mrl_mlpbase_bank_workspace_bytes(uint32_t num_worlds, uint32_t num_poli
 int mrl_mappo_workspace_bytes(uint32_t width, uint32_t height, uint32_t channels, uint32_t hidden, uint32_t minibatch_size,
                               uint32_t num_minibatches, uint64_t *out)
 {
+    // the layered update's shape: 512 | MRL_MAPPO_H512_HIDDEN ("mrl_mappo_h512_workspace_bytes" in messages)
+    if (hidden & MRL_MAPPO_H512_HIDDEN) {
+        const char *why = out ? mappo_h512_shape_error(width, height, channels, hidden & ~(uint32_t)MRL_MAPPO_H512_HIDDEN, minibatch_size)
+                              : "null output pointer";
+        if (why) {
+            mrl::set_error("mrl_mappo_h512_workspace_bytes: %s (width %u, height %u, channels %u, minibatch_size %u)", why, width, height, channels,
+                           minibatch_size);
+            return MRL_ERR_INVALID;
+        }
+        *out = mrl::h512_workspace(width, height, channels, minibatch_size, num_minibatches).total * sizeof(float);
+        return MRL_OK;
+    }
     // the recurrent shape: hidden | MRL_CNN_GRU_HIDDEN
     const bool recurrent = hidden == (mrl::kCnnHidden | MRL_CNN_GRU_HIDDEN);
     const char *why = out ? mappo_shape_error(width, height, channels, recurrent ? mrl::kCnnHidden : hidden, minibatch_size) : "null output pointer";
@@ -1042,6 +1094,17 @@ int mrl_mappo_update(const mrl_mappo_policy *policy, const mrl_mappo_optimizer *
                      uint32_t num_minibatches, uint32_t minibatch_size, const mrl_mappo_config *cfg, float *value_norm_state, void *workspace_dev,
                      uint64_t workspace_bytes, float *stats_dev_or_null, float *grads_dev_or_null, int gpu_id, void *hip_stream)
 {
+    // the layered update of hidden 512 ("mrl_mappo_h512_update" in messages): the bit taken out, no other flag admitted
+    if (policy && (policy->flags & MRL_MAPPO_H512)) {
+        const char *what = "mrl_mappo_h512_update";
+        mrl_mappo_policy plain = *policy;
+        plain.flags &= ~(uint32_t)MRL_MAPPO_H512;
+        if (plain.flags)
+            return mrl::refusal(what, plain.flags & MRL_CNN_RECURRENT ? "the hidden-512 update does not take a recurrent policy (MRL_CNN_RECURRENT)"
+                                                                      : "the policy's flags must be 0");
+        return mrl::mappo_update<mrl::CnnH512UpdateNet>(what, &plain, opt, batch, indices_dev, num_minibatches, minibatch_size, cfg, value_norm_state,
+                                                        workspace_dev, workspace_bytes, stats_dev_or_null, grads_dev_or_null, gpu_id, hip_stream);
+    }
     if (policy && (policy->flags & MRL_CNN_RECURRENT))
         return mrl::cnn_gru_update("mrl_mappo_update", policy, opt, reinterpret_cast<const mrl_mappo_gru_batch *>(batch), indices_dev,
                                    num_minibatches, minibatch_size, cfg, value_norm_state, workspace_dev, workspace_bytes, stats_dev_or_null,

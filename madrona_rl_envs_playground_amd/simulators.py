@@ -50,13 +50,13 @@ from ._wide import (AgentRecord, WideAgent, WideOptimizer, WidePolicy, WidePolic
 from ._mappo_nets import (CnnActorCritic, CnnGruActorCritic, _CnnGruActor, _CnnGruCritic, MlpBaseActorCritic, MlpBaseGruActorCritic, _ActLayer, _ActorCritic, _CategoricalHead, _CnnActor, _CnnBase,  # noqa: F401
                           _CnnCritic, _CnnLayer, _MlpBase, _MlpBaseActor, _MlpBaseCritic, _MlpBaseGruActor, _MlpBaseGruCritic, _MlpLayer,
                           _RnnLayer)
-from ._mappo import (ActsWithCnnPolicy, ActsWithMlpBasePolicy, CnnGruPolicy, CnnGruRecord, GruState, CnnPolicy, CnnPolicyBank, CnnRecord, MappoOptimizer,  # noqa: F401
+from ._mappo import (ActsWithCnnPolicy, ActsWithMlpBasePolicy, CnnGruPolicy, CnnGruRecord, GruState, CnnPolicy, CnnPolicyBank, CnnRecord, MappoOptimizer, MappoOptimizerH512,  # noqa: F401
                      MappoResult, MlpBaseGruPolicy, MlpBaseGruRecord, MlpBaseGruState, MlpBasePolicy, MlpBasePolicyBank, MlpBaseRecord,
                      ValueNorm, chunk_indices, _ActsWithMappoPolicy, _CNN,
                      _Family, _FlatPolicy, _MLPBASE, _MappoRecord, _MappoRollouts, _act, _act_bank, _bank_call_args,
                      _call_args, _cnn_bank_call_args, _cnn_bank_workspace, _cnn_call_args, _kitchen_cells,
-                     _mappo_config, _mlpbase_bank_call_args, _mlpbase_bank_workspace, _mlpbase_call_args, _ring_pointer,
-                     _rollout, _rollout_bank, cnn_act, cnn_act_bank, cnn_resample, mappo_advantages, mappo_update, mlpbase_act,
+                     _mappo_config, _mappo_run, _mlpbase_bank_call_args, _mlpbase_bank_workspace, _mlpbase_call_args, _ring_pointer,
+                     _rollout, _rollout_bank, cnn_act, cnn_act_bank, cnn_resample, mappo_advantages, mappo_update, mappo_update_h512, mlpbase_act,
                      mlpbase_act_bank, mlpbase_resample)
 from ._population import (MappoBankOptimizer, ValueNormBank, _cross_play_beam, cross_play, mappo_advantages_bank,  # noqa: F401
                           mappo_update_bank, member_samples)

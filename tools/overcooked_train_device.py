@@ -61,18 +61,22 @@ def evaluate(env, policy, horizon, seed=0):
 
 def train(layout, num_envs, num_steps, updates, seed, lr=5e-4, critic_lr=5e-4, lr_decay=False, gamma=0.99, gae_lambda=0.95, ppo_epoch=15,
           num_mini_batch=1, clip_param=0.2, entropy_coef=0.01, value_loss_coef=1.0, max_grad_norm=10.0, huber_delta=10.0, horizon=400,
-          log=None, game="overcooked", evaluation=None, recurrent=False, data_chunk_length=10, final=None):
+          log=None, game="overcooked", evaluation=None, recurrent=False, data_chunk_length=10, final=None, hidden_size=64):
     """``updates`` iterations of collect, advantages, update with the reference's defaults (train/config.py).  One dict per
     update: the learning rates, the mean of every stat over the update's rows (``train_info``), the episodes finished during the
     update with their mean return, and ``optimizer_step``.  ``game``: "overcooked" or "simplecooked" (``layout`` is then one of
     Simplecooked's names).  ``evaluation``: a dict that takes ``evaluate``'s histogram under "scores" after the last update.
     ``recurrent``: the recurrent actor-critic, trained on chunks of ``data_chunk_length`` steps (it must divide ``num_steps``).
-    ``final``: a dict that takes the trained flat tensor (on the host) under "params"."""
+    ``final``: a dict that takes the trained flat tensor (on the host) under "params".  ``hidden_size``: 64, or 512 -- the reference
+    trainer's default width, trained through ``MappoOptimizerH512`` and ``mappo_update_h512`` (feed-forward only)."""
     import torch
     from madrona_rl_envs_playground_amd import _lib
     from madrona_rl_envs_playground_amd.simulators import (CnnActorCritic, CnnGruActorCritic, CnnGruPolicy, CnnGruRecord, CnnPolicy,
-                                                             MappoOptimizer, ValueNorm, chunk_indices, mappo_advantages, mappo_update,
-                                                             minibatch_indices)
+                                                             MappoOptimizer, MappoOptimizerH512, ValueNorm, chunk_indices, mappo_advantages,
+                                                             mappo_update, mappo_update_h512, minibatch_indices)
+    if hidden_size not in (_lib.CNN_HIDDEN, _lib.CNN_HIDDEN_WIDE) or (recurrent and hidden_size != _lib.CNN_HIDDEN):
+        raise ValueError("hidden_size is 64 or 512, and the recurrent actor-critic runs 64 only")
+    wide = hidden_size == _lib.CNN_HIDDEN_WIDE
     env = make_env(game, layout, num_envs, horizon)
     device = torch.device("cuda", 0)
     _, players, height, width, channels = env.static_world_major_observations.shape
@@ -83,8 +87,9 @@ def train(layout, num_envs, num_steps, updates, seed, lr=5e-4, critic_lr=5e-4, l
         policy.state(num_envs, players)
         record = CnnGruRecord(num_steps, num_envs, players, device, chunk_length=data_chunk_length)
     else:
-        policy = CnnPolicy.from_module(CnnActorCritic(width, height, channels), device=device)
-    optimizer = MappoOptimizer(policy, lr=lr, critic_lr=critic_lr)
+        policy = CnnPolicy.from_module(CnnActorCritic(width, height, channels, hidden=hidden_size), device=device)
+    optimizer = (MappoOptimizerH512 if wide else MappoOptimizer)(policy, lr=lr, critic_lr=critic_lr)
+    update_rows = mappo_update_h512 if wide else mappo_update
     value_norm = ValueNorm(device)
     shuffles = torch.Generator(device=device).manual_seed(seed)
     rows = ppo_epoch * num_mini_batch
@@ -100,9 +105,9 @@ def train(layout, num_envs, num_steps, updates, seed, lr=5e-4, critic_lr=5e-4, l
             indices = chunk_indices(record, num_mini_batch, ppo_epoch, generator=shuffles, device=device)
         else:
             indices = minibatch_indices(num_steps * num_envs * players, num_mini_batch, ppo_epoch, generator=shuffles, device=device)
-        result = mappo_update(policy, optimizer, record, ring, advantages, returns, indices, value_norm=value_norm, clip_param=clip_param,
-                              entropy_coef=entropy_coef, value_loss_coef=value_loss_coef, max_grad_norm=max_grad_norm,
-                              huber_delta=huber_delta)
+        result = update_rows(policy, optimizer, record, ring, advantages, returns, indices, value_norm=value_norm, clip_param=clip_param,
+                             entropy_coef=entropy_coef, value_loss_coef=value_loss_coef, max_grad_norm=max_grad_norm,
+                             huber_delta=huber_delta)
         host_stats.copy_(result.stats, non_blocking=True)
         totals = env.episode_totals()  # the update's one host wait; the copy above lies in front of it on the same stream
         episodes = totals["episodes"]
@@ -146,6 +151,8 @@ def parser():
     ap.add_argument("--entropy-coef", type=float)
     ap.add_argument("--recurrent", action="store_true", help="the GRU actor-critic (the reference's --use_recurrent_policy)")
     ap.add_argument("--data-chunk-length", type=int, default=10, help="steps per chunk of a recurrent minibatch; divides --num-steps")
+    ap.add_argument("--hidden-size", type=int, default=64, choices=(64, 512),
+                    help="512: the reference trainer's default width, on the device through mappo_update_h512 (opt-in; not with --recurrent)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--evaluate", action="store_true", help="afterwards one greedy episode in every world; prints {score: worlds}")
     ap.add_argument("--json", help="also write the settings, the per-update entries and the histogram to this file")
@@ -158,12 +165,12 @@ def main(argv=None):
     evaluation = {} if args.evaluate else None
     history = train(s["layout"], s["num_envs"], s["num_steps"], s["updates"], args.seed, lr=s["lr"], critic_lr=s["critic_lr"],
                     ppo_epoch=s["ppo_epoch"], num_mini_batch=s["num_mini_batch"], entropy_coef=s["entropy_coef"], horizon=s["horizon"],
-                    game=s["game"], evaluation=evaluation, recurrent=args.recurrent, data_chunk_length=args.data_chunk_length, log=lambda entry: print(json.dumps(entry), flush=True))
+                    game=s["game"], evaluation=evaluation, recurrent=args.recurrent, data_chunk_length=args.data_chunk_length, hidden_size=args.hidden_size, log=lambda entry: print(json.dumps(entry), flush=True))
     if evaluation is not None:
         print(json.dumps({"greedy_scores": {str(k): v for k, v in evaluation["scores"].items()}}), flush=True)
     if args.json:
         from madrona_rl_envs_playground_amd import _lib
-        out = {"build_hash": _lib.build_hash(), "settings": dict(s, seed=args.seed, recipe=args.recipe, recurrent=args.recurrent, data_chunk_length=args.data_chunk_length), "updates": history,
+        out = {"build_hash": _lib.build_hash(), "settings": dict(s, seed=args.seed, recipe=args.recipe, recurrent=args.recurrent, data_chunk_length=args.data_chunk_length, hidden_size=args.hidden_size), "updates": history,
                "mean_returns": [entry["mean_return"] for entry in history]}
         if evaluation is not None:
             out["greedy_scores"] = {str(k): v for k, v in evaluation["scores"].items()}
