@@ -1269,6 +1269,37 @@ int mrl_mappo_mlp_update(const mrl_mlpbase_policy *policy, const mrl_mappo_optim
                          uint64_t workspace_bytes, float *stats_dev_or_null /* (K, 8) */, float *grads_dev_or_null /* (K, P) */,
                          int gpu_id, void *hip_stream);
 
+/* The MLPBase actor-critic at the reference trainer's default hidden_size 512 (train/config.py:200): act and rollout, through
+ * mrl_mlpbase_act, mrl_rollout_mlpbase and mrl_mlpbase_policy_num_params -- no new entry point and no changed struct,
+ * MRL_ABI_VERSION stays 4.  DESIGN.md section 32.
+ *   MRL_MLPBASE_H512 is a bit of mrl_mlpbase_policy.flags ONLY, never of the act's `flags` argument; with it hidden must be 512.
+ *     Without the bit hidden = 512 stays refused everywhere, and mrl_mlpbase_policy_num_params(7, 512, layer_N, 4) stays 0.
+ *   Network, per net: LayerNorm(7), Linear(7, 512), ReLU, LayerNorm(512), layer_N x [Linear(512, 512), ReLU, LayerNorm(512)], then
+ *     Linear(512, 4) (actor) or Linear(512, 1) (critic); layer_N 1 or 2; eps 1e-5, the biased variance.
+ *   Flat tensor: the plain one with 512 in place of 64, the actor's tensors and then the critic's in parameters_to_vector order,
+ *     base.mlp.fc_h (263 680 floats per net, read by no kernel) included.  mrl_mlpbase_policy_num_params(7, 512 |
+ *     MRL_MLPBASE_H512_HIDDEN, layer_N, 4) floats: 1 594 913 for layer_N 2 (actor 798 226, critic 796 687), 1 067 553 for 1
+ *     (534 546, 533 007); 0 for layer_N outside {1, 2}, obs_dim != 7 or num_actions != 4.
+ *   Arithmetic, float32, every product on v_mfma_f32_32x32x2_f32.  Linear: an output starts from 0 and adds its products with one
+ *     fused multiply-add each in ascending input index -- ONE chain over k = 0 .. 511; fc1: k = 0 .. 6 and one zero product --,
+ *     the bias added to the finished sum.  LayerNorm: a wavefront per row; lane l owns columns l, l + 64, ..., l + 448 (of 7
+ *     columns: column l where l < 7); a sum over the row is the lane's own columns added in ascending order to 0, then the plain
+ *     act's six exchange steps (partners 32, 16, 8, 4, 2, 1 lanes apart); mean = sum / width, var = sum((x - mean)^2) / width,
+ *     xhat = (x - mean) * (1 / sqrtf(var + 1e-5)), y = xhat * weight + bias (a product, then a sum).  A row of variance 0 gives
+ *     xhat = 0 and y = bias.  A sample's result depends on neither its tile-mates, its place in the tile nor the number of worlds
+ *     (a workgroup runs 32 samples of one net, 64 from 4096 samples a call on: the same arithmetic per row).  No float atomics:
+ *     the same inputs give the same bits on every run.
+ *   Everything else is the plain act's, by the same device function (the shared act tail): samples, the `players` mask, the head's
+ *     draw, MRL_POLICY_GREEDY, MRL_MLPBASE_VALUE_ONLY, a record or none (none: the actor alone), optional logits, the observation
+ *     rows copied to record->obs, ACTION, and mrl_rollout_mlpbase's loop.
+ *   MRL_ERR_INVALID, nothing enqueued: the plain act's and rollout's refusals, and the bit with hidden != 512; the bit together
+ *     with MRL_MLPBASE_RECURRENT; the bit in mrl_mlpbase_bank.flags (mrl_mlpbase_act_bank, mrl_rollout_mlpbase_bank) or with
+ *     mrl_mappo_mlp_bank_update; the bit in mrl_mappo_mlp_update.
+ *   Not built: the device update at 512 (a 512 policy learns through torch autograd on the same flat tensor), the banks,
+ *     cross-play and the GRU at 512, widths other than 64 and 512, layer_N above 2, PopArt, graph capture, sharded simulators. */
+enum { MRL_MLPBASE_H512 = 32 };             /* bit of mrl_mlpbase_policy.flags: mrl_mlpbase_act and mrl_rollout_mlpbase run hidden 512 */
+enum { MRL_MLPBASE_H512_HIDDEN = 0x1000 };  /* or-ed into `hidden` = 512 in mrl_mlpbase_policy_num_params: the hidden-512 tensor */
+
 /* The RECURRENT MLPBase actor-critic (r_actor_critic.py with use_recurrent_policy, utils/rnn.py with recurrent_N 1): a GRU of width
  * 64 and a LayerNorm between the base and the head of both nets, through mrl_mlpbase_act, mrl_rollout_mlpbase, mrl_mappo_mlp_update
  * and the two size queries -- no new entry

@@ -189,6 +189,13 @@ class MlpBasePolicy(_FlatPolicy):
     def num_params(self):
         return int(_lib.lib().mrl_mlpbase_policy_num_params(self.obs_dim, self.hidden, self.layer_N, self.num_actions))
 
+    def _need_hidden_64(self, what):
+        """``what`` is built on the hidden-64 kernels: the wide policy acts and rolls out, and learns through ``module()``"""
+        if self.hidden != _lib.MLPBASE_HIDDEN:
+            raise ValueError(f"{what}: the device update, the banks and the recurrent policy run hidden = {_lib.MLPBASE_HIDDEN} only; hidden = "
+                             f"{self.hidden} (MlpBasePolicyH512) runs mlpbase_act, rollout_mlpbase and MlpBasePolicyAgent, and learns with "
+                             f"torch autograd on policy.module()")
+
     def desc(self):
         return _lib.MlpBasePolicyDesc(self.params.data_ptr(), self.hidden, self.layer_N, 0)
 
@@ -211,6 +218,46 @@ class MlpBasePolicy(_FlatPolicy):
         rows = count + count // max(record.num_steps, 1)
         _require_tensors([("record.obs", record.obs, torch.int32, rows * self.obs_dim)], self.params.device)
         return (_lib.lib().mrl_mappo_mlp_update, _lib.lib().mrl_mappo_mlp_bank_update), self.desc(), _lib.MappoMlpBatch, record.obs
+
+
+class MlpBasePolicyH512(MlpBasePolicy):
+    """``MlpBasePolicy`` at the reference trainer's default ``hidden_size`` 512 (``mrl_mlpbase_policy`` with ``MRL_MLPBASE_H512``):
+    ``params`` is the flat tensor of ``parameters_to_vector(MlpBaseActorCritic(hidden=512, layer_N=...).parameters())`` -- 1 594 913
+    floats for ``layer_N`` 2, 1 067 553 for 1, the unused ``fc_h`` included.  ``mlpbase_act``, ``rollout_mlpbase``, the env's ``act``
+    / ``rollout``, ``MlpBaseRecord``, ``mappo_advantages`` and ``MlpBasePolicyAgent`` take it as they take the plain policy.
+    ``module()`` returns an ``MlpBaseActorCritic`` over VIEWS of ``params``, whose ``actor.load_state_dict`` / ``critic.load_state_dict``
+    take a default-width reference checkpoint; ``load_(module)`` copies another module's parameters in.  It LEARNS through torch
+    autograd on ``module()``: ``MappoOptimizer``, ``mappo_update``, ``mappo_update_bank``, ``MlpBasePolicyBank`` and
+    ``MlpBaseGruPolicy`` run hidden 64 only and refuse this width."""
+
+    _module_name = f"an MlpBaseActorCritic of hidden = {_lib.MLPBASE_HIDDEN_WIDE}"
+    _desc_flags = _lib.MLPBASE_H512  # the bit every descriptor of this kind of policy carries, a rollout's included
+
+    def __init__(self, layer_N=2, device="cuda:0"):
+        self.obs_dim, self.num_actions, self.hidden, self.layer_N = _lib.MLPBASE_OBS, _lib.MLPBASE_ACTIONS, _lib.MLPBASE_HIDDEN_WIDE, int(layer_N)
+        self._allocate(device, f"mrl_mlpbase_act runs hidden = {_lib.MLPBASE_HIDDEN_WIDE} with layer_N 1 or 2; got {self.layer_N}")
+
+    @property
+    def num_params(self):
+        return int(_lib.lib().mrl_mlpbase_policy_num_params(self.obs_dim, self.hidden | _lib.MLPBASE_H512_HIDDEN, self.layer_N, self.num_actions))
+
+    @classmethod
+    def from_module(cls, module, device=None):
+        """A policy of ``module``'s ``layer_N`` holding a copy of its parameters (``device``: default its own)."""
+        own = next(module.parameters()).device if isinstance(module, torch.nn.Module) else None
+        return cls(getattr(module, "layer_N", 0), device if device is not None else own).load_(module)
+
+    def load_(self, module):
+        """Copy ``module``'s parameters (an ``MlpBaseActorCritic`` of this shape) into ``params``, in place -> self."""
+        shape = (self.obs_dim, self.num_actions, self.hidden, self.layer_N)
+        if not isinstance(module, MlpBaseActorCritic) or (module.obs_dim, module.num_actions, module.hidden, module.layer_N) != shape:
+            raise ValueError(f"module must be {self._module_name} and layer_N = {self.layer_N}")
+        with torch.no_grad():
+            self.params.copy_(torch.nn.utils.parameters_to_vector(module.parameters()).detach())
+        return self
+
+    def desc(self):
+        return _lib.MlpBasePolicyDesc(self.params.data_ptr(), self.hidden, self.layer_N, self._desc_flags)
 
 
 class MlpBaseRecord(_MappoRecord):
@@ -268,6 +315,12 @@ class MlpBaseGruPolicy(MlpBasePolicy):
     def __init__(self, layer_N=2, device="cuda:0"):
         self.running = None
         super().__init__(layer_N=layer_N, device=device)
+
+    @classmethod
+    def from_module(cls, module, device=None):
+        if isinstance(module, cls._module_class):
+            MlpBasePolicy._need_hidden_64(module, "MlpBaseGruPolicy")
+        return super().from_module(module, device)
 
     @property
     def num_params(self):
@@ -476,6 +529,7 @@ class MlpBasePolicyBank(_PolicyBank):
     def __init__(self, num_policies, layer_N=2, obs_dim=_lib.MLPBASE_OBS, num_actions=_lib.MLPBASE_ACTIONS, hidden=_lib.MLPBASE_HIDDEN,
                  device="cuda:0"):
         self.obs_dim, self.num_actions, self.hidden, self.layer_N = int(obs_dim), int(num_actions), int(hidden), int(layer_N)
+        MlpBasePolicy._need_hidden_64(self, "MlpBasePolicyBank")
         super().__init__(num_policies, device)
 
     def desc(self):
@@ -861,8 +915,7 @@ class MappoOptimizer(_AdamState):
     def __init__(self, policy, lr=5e-4, critic_lr=5e-4, betas=(0.9, 0.999), eps=1e-5):
         if not isinstance(policy, (CnnPolicy, MlpBasePolicy)):
             raise ValueError("policy must be a CnnPolicy or an MlpBasePolicy")
-        if isinstance(policy, CnnPolicy):
-            policy._need_hidden_64("MappoOptimizer")
+        policy._need_hidden_64("MappoOptimizer")
         super().__init__(policy, betas, eps)
         self.lr, self.critic_lr = float(lr), float(critic_lr)
 
@@ -941,6 +994,8 @@ def mappo_update(policy, optimizer, record, ring, advantages, returns, indices, 
     For a ``CnnGruPolicy`` (the kitchens' recurrent actor-critic) ``record`` is a ``CnnGruRecord``, ``ring`` its rollout's ring and
     ``indices`` are chunk ids in the same way.
     Not built: active masks, PopArt, ``update_actor=False``, weight decay."""
+    if isinstance(policy, MlpBasePolicyH512):
+        policy._need_hidden_64("mappo_update")
     if not isinstance(policy, (CnnPolicy, MlpBasePolicy)) or not isinstance(optimizer, MappoOptimizer) or optimizer.policy is not policy:
         raise ValueError("policy must be a CnnPolicy or an MlpBasePolicy (plain or recurrent) and optimizer the MappoOptimizer made for it")
     if isinstance(policy, CnnPolicy):

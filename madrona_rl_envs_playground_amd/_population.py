@@ -11,7 +11,7 @@ import torch
 from . import _lib
 from ._bank import BEAM_TIME, _cross_play_counted, _cross_play_pairs, _cross_play_result
 from ._device import _require_tensors, _stream_ptr
-from ._mappo import (CnnPolicyBank, MappoOptimizer, MappoResult, MlpBasePolicyBank, ValueNorm, _MappoRecord, _mappo_config,
+from ._mappo import (CnnPolicyBank, MappoOptimizer, MappoResult, MlpBasePolicyBank, MlpBasePolicyH512, ValueNorm, _MappoRecord, _mappo_config,
                      cnn_act_bank, mlpbase_act_bank)
 from ._ppo import _AdamState, gae
 from ._wide import WidePolicyBank, _cross_play_wide
@@ -185,6 +185,8 @@ def mappo_update_bank(bank, optimizer, record, ring, advantages, returns, indice
     and ``grads[z]`` are bit for bit what ``mappo_update`` leaves for ``bank.policy(first_member + z)`` with
     ``optimizer.member(...)``, ``value_norms.member(...)`` and ``indices[z]``; no other row of the bank is read or written.
     Returns ``MappoResult(stats, grads)``: (M, R, 8) and (M, R, P), each None unless asked for."""
+    if isinstance(bank, MlpBasePolicyH512):  # no bank holds that width
+        bank._need_hidden_64("mappo_update_bank")
     if (not isinstance(bank, (CnnPolicyBank, MlpBasePolicyBank)) or not isinstance(optimizer, MappoBankOptimizer) or
             optimizer.bank is not bank):
         raise ValueError("bank must be a CnnPolicyBank or an MlpBasePolicyBank and optimizer the MappoBankOptimizer made for it")

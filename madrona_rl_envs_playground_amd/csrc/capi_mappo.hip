@@ -12,6 +12,7 @@
 #include "mlpbase_policy.hpp"
 #include "mlpbase_bank.hpp"
 #include "mlpbase_gru.hpp"
+#include "mlpbase_h512.hpp"
 #include "mlpbase_update.hpp"
 
 #include <type_traits>
@@ -200,9 +201,11 @@ static int cnn_h512_prepare(mrl_sim *sim, uint32_t players, const mrl_cnn_policy
     return cnn_prepare_width(mrl::kCnnH512Hidden, sim, players, policy, record, hip_stream, what, args);
 }
 
-// Everything mrl_mlpbase_act and mrl_rollout_mlpbase check alike; fills `args` but for the rows, the seed, the step and the flags.
-static int mlpbase_prepare(mrl_sim *sim, uint32_t players, const mrl_mlpbase_policy *policy, const mrl_mlpbase_record *record,
-                           void *hip_stream, const char *what, mrl::MlpBaseActArgs *args)
+// Everything mrl_mlpbase_act and mrl_rollout_mlpbase check alike, for the kernel of width `hidden` (64: mrl_mlpbase_act, 512:
+// mrl_mlpbase_act_h512, whose policy arrives with MRL_MLPBASE_H512 taken out); fills `args` but for the rows, the seed, the step
+// and the flags.
+static int mlpbase_prepare_width(uint32_t hidden, mrl_sim *sim, uint32_t players, const mrl_mlpbase_policy *policy,
+                                 const mrl_mlpbase_record *record, void *hip_stream, const char *what, mrl::MlpBaseActArgs *args)
 {
     if (int rc = mrl::need_healthy(sim)) return rc;
     if (sim->game != MRL_GAME_BALANCE) {
@@ -212,7 +215,7 @@ static int mlpbase_prepare(mrl_sim *sim, uint32_t players, const mrl_mlpbase_pol
     const char *prepared = "this simulator has been through mrl_exchange_create or mrl_prepare_graph_capture; sharded and captured "
                            "simulators are out of scope";
     if (int rc = act_scope_refusal(what, sim->exchange.mine || sim->capturable() ? prepared : nullptr, hip_stream)) return rc;
-    if (!policy || !policy->params_dev || policy->hidden != mrl::kMlpBaseHidden || policy->layer_N < 1 ||
+    if (!policy || !policy->params_dev || policy->hidden != hidden || policy->layer_N < 1 ||
         policy->layer_N > mrl::kMlpBaseMaxLayerN || (policy->flags & ~(uint32_t)MRL_POLICY_GREEDY)) {
         mrl::set_error("%s: null policy or parameter array, hidden other than 64, layer_N other than 1 or 2, or policy flags other than "
                        "MRL_POLICY_GREEDY", what);
@@ -246,6 +249,20 @@ static int mlpbase_prepare(mrl_sim *sim, uint32_t players, const mrl_mlpbase_pol
     a.reward = static_cast<const float *>(reward.data);
     a.layer_N = policy->layer_N;
     return MRL_OK;
+}
+
+// the plain act and everything built on it -- the banks, the recurrent act -- run hidden 64 and refuse every other width
+static int mlpbase_prepare(mrl_sim *sim, uint32_t players, const mrl_mlpbase_policy *policy, const mrl_mlpbase_record *record,
+                           void *hip_stream, const char *what, mrl::MlpBaseActArgs *args)
+{
+    return mlpbase_prepare_width(mrl::kMlpBaseHidden, sim, players, policy, record, hip_stream, what, args);
+}
+
+// mrl_mlpbase_act and mrl_rollout_mlpbase with MRL_MLPBASE_H512 (mlpbase_h512_policy has taken the bit out)
+static int mlpbase_h512_prepare(mrl_sim *sim, uint32_t players, const mrl_mlpbase_policy *policy, const mrl_mlpbase_record *record,
+                                void *hip_stream, const char *what, mrl::MlpBaseActArgs *args)
+{
+    return mlpbase_prepare_width(mrl::kMlpH512Hidden, sim, players, policy, record, hip_stream, what, args);
 }
 
 // the rows of `record` an act at `row` writes: record_rows', and the row of observations every act copies
@@ -467,6 +484,13 @@ struct MlpBaseNet {
     template <class... Rest> static void launch_update(const UpdatePolicy &p, Rest &&...rest) { launch_mappo_mlp_update(p.layer_N, rest...); }
 };
 
+// The balance beam's MLPBase at hidden 512 as the act and the rollout see it (mlpbase_h512.hpp): MlpBaseNet's checks and plumbing,
+// its own kernel.  The update and the banks do not run this width and never see this type.
+struct MlpBaseH512Net : MlpBaseNet {
+    static constexpr auto prepare = mlpbase_h512_prepare;
+    static constexpr auto launch_act = launch_mlpbase_act_h512;
+};
+
 // The recurrent MLPBase as the update sees it (mrl_mappo_mlp_update with MRL_MLPBASE_RECURRENT): MlpBaseNet's refusals on the
 // structs the extended ones begin with; the rows are chunk ids, the workspace and the launch the recurrent update's.
 struct MlpBaseGruNet : MlpBaseNet {
@@ -588,6 +612,23 @@ static int rollout(const char *what, mrl_sim *sim, uint32_t players, const typen
         },
         [] {});
 }
+
+// ---- the MLPBase at hidden 512: mrl_mlpbase_act and mrl_rollout_mlpbase with MRL_MLPBASE_H512 in the policy's flags ----
+
+// `policy` carries the bit: what the bit itself demands, then `plain`, the policy without it, for MlpBaseH512Net
+static int mlpbase_h512_policy(const char *what, const mrl_mlpbase_policy *policy, mrl_mlpbase_policy *plain)
+{
+    if (policy->flags & MRL_MLPBASE_RECURRENT) return refusal(what, "MRL_MLPBASE_H512 does not go with MRL_MLPBASE_RECURRENT: the GRU runs hidden 64");
+    if (policy->hidden != kMlpH512Hidden) return refusal(what, "MRL_MLPBASE_H512 needs hidden = 512");
+    *plain = *policy;
+    plain->flags &= ~(uint32_t)MRL_MLPBASE_H512;
+    return MRL_OK;
+}
+
+// what the update and the bank update of the MLPBase say to a policy with the bit
+static constexpr const char *kMlpH512NoUpdate = "MRL_MLPBASE_H512: the device update runs hidden 64; a hidden-512 policy acts and rolls out "
+                                                "on the device (mrl_mlpbase_act, mrl_rollout_mlpbase) and learns through torch autograd on "
+                                                "the same flat tensor";
 
 // ---- the recurrent MLPBase: mrl_mlpbase_act and mrl_rollout_mlpbase with MRL_MLPBASE_RECURRENT in the policy's flags ----
 
@@ -932,6 +973,11 @@ uint64_t mrl_cnn_workspace_bytes(uint32_t num_worlds, uint32_t num_players) { re
 
 uint64_t mrl_mlpbase_policy_num_params(uint32_t obs_dim, uint32_t hidden, uint32_t layer_N, uint32_t num_actions)
 {
+    // hidden 512: 512 | MRL_MLPBASE_H512_HIDDEN (mlpbase_h512.hpp)
+    if (hidden == (mrl::kMlpH512Hidden | MRL_MLPBASE_H512_HIDDEN)) {
+        if (obs_dim != mrl::kMlpBaseObs || layer_N < 1 || layer_N > mrl::kMlpBaseMaxLayerN || num_actions != mrl::kMlpBaseActions) return 0;
+        return (uint64_t)mrl::mlpbase_h512_net_params(layer_N, num_actions) + mrl::mlpbase_h512_net_params(layer_N, 1);
+    }
     // the recurrent shape: layer_N + MRL_MLPBASE_GRU_LAYERS
     const uint32_t gru = layer_N - MRL_MLPBASE_GRU_LAYERS;
     if (obs_dim == mrl::kMlpBaseObs && hidden == mrl::kMlpBaseHidden && gru >= 1 && gru <= mrl::kMlpBaseMaxLayerN && num_actions == mrl::kMlpBaseActions)
@@ -1020,6 +1066,11 @@ int mrl_cnn_act(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy, co
 int mrl_mlpbase_act(mrl_sim *sim, uint32_t players, const mrl_mlpbase_policy *policy, const mrl_mlpbase_record *record, uint32_t row,
                     uint64_t seed, uint32_t step, uint32_t flags, void *hip_stream)
 {
+    if (policy && (policy->flags & MRL_MLPBASE_H512)) {
+        mrl_mlpbase_policy plain{};
+        if (int rc = mrl::mlpbase_h512_policy("mrl_mlpbase_act", policy, &plain)) return rc;
+        return mrl::act<mrl::MlpBaseH512Net>("mrl_mlpbase_act", sim, players, &plain, record, row, seed, step, flags, nullptr, 0, hip_stream);
+    }
     if (policy && (policy->flags & MRL_MLPBASE_RECURRENT))
         return mrl::gru_act("mrl_mlpbase_act", sim, players, reinterpret_cast<const mrl_mlpbase_gru_policy *>(policy),
                             reinterpret_cast<const mrl_mlpbase_gru_record *>(record), row, seed, step, flags, hip_stream);
@@ -1056,6 +1107,11 @@ int mrl_rollout_cnn(mrl_sim *sim, uint32_t players, const mrl_cnn_policy *policy
 int mrl_rollout_mlpbase(mrl_sim *sim, uint32_t players, const mrl_mlpbase_policy *policy, const mrl_mlpbase_record *record, uint64_t seed,
                         uint32_t first_step, void *hip_stream)
 {
+    if (policy && (policy->flags & MRL_MLPBASE_H512)) {
+        mrl_mlpbase_policy plain{};
+        if (int rc = mrl::mlpbase_h512_policy("mrl_rollout_mlpbase", policy, &plain)) return rc;
+        return mrl::rollout<mrl::MlpBaseH512Net>("mrl_rollout_mlpbase", sim, players, &plain, record, nullptr, seed, first_step, hip_stream);
+    }
     if (policy && (policy->flags & MRL_MLPBASE_RECURRENT))
         return mrl::gru_rollout("mrl_rollout_mlpbase", sim, players, reinterpret_cast<const mrl_mlpbase_gru_policy *>(policy),
                                 reinterpret_cast<const mrl_mlpbase_gru_record *>(record), seed, first_step, hip_stream);
@@ -1127,6 +1183,7 @@ int mrl_mappo_mlp_update(const mrl_mlpbase_policy *policy, const mrl_mappo_optim
                          uint32_t num_minibatches, uint32_t minibatch_size, const mrl_mappo_config *cfg, float *value_norm_state, void *workspace_dev,
                          uint64_t workspace_bytes, float *stats_dev_or_null, float *grads_dev_or_null, int gpu_id, void *hip_stream)
 {
+    if (policy && (policy->flags & MRL_MLPBASE_H512)) return mrl::refusal("mrl_mappo_mlp_update", mrl::kMlpH512NoUpdate);
     if (policy && (policy->flags & MRL_MLPBASE_RECURRENT))
         return mrl::gru_update("mrl_mappo_mlp_update", reinterpret_cast<const mrl_mlpbase_gru_policy *>(policy), opt,
                                reinterpret_cast<const mrl_mappo_mlp_gru_batch *>(batch), indices_dev, num_minibatches, minibatch_size, cfg,
@@ -1140,6 +1197,7 @@ int mrl_mappo_mlp_bank_update(const mrl_mlpbase_policy *policy, const mrl_mappo_
                               float *value_norm_state, void *workspace_dev, uint64_t workspace_bytes, float *stats_dev_or_null,
                               float *grads_dev_or_null, int gpu_id, void *hip_stream)
 {
+    if (policy && (policy->flags & MRL_MLPBASE_H512)) return mrl::refusal("mrl_mappo_mlp_bank_update", mrl::kMlpH512NoUpdate);
     if (policy && (policy->flags & MRL_MLPBASE_RECURRENT))
         return mrl::refusal("mrl_mappo_mlp_bank_update", "a bank update does not take a recurrent policy (MRL_MLPBASE_RECURRENT)");
     return mrl::mappo_update<MlpBaseNet>("mrl_mappo_mlp_bank_update", policy, opt, batch, indices_dev, num_minibatches, minibatch_size, cfg,

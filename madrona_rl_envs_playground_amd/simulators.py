@@ -51,7 +51,7 @@ from ._mappo_nets import (CnnActorCritic, CnnGruActorCritic, _CnnGruActor, _CnnG
                           _CnnCritic, _CnnLayer, _MlpBase, _MlpBaseActor, _MlpBaseCritic, _MlpBaseGruActor, _MlpBaseGruCritic, _MlpLayer,
                           _RnnLayer)
 from ._mappo import (ActsWithCnnPolicy, ActsWithMlpBasePolicy, CnnGruPolicy, CnnGruRecord, GruState, CnnPolicy, CnnPolicyBank, CnnRecord, MappoOptimizer, MappoOptimizerH512,  # noqa: F401
-                     MappoResult, MlpBaseGruPolicy, MlpBaseGruRecord, MlpBaseGruState, MlpBasePolicy, MlpBasePolicyBank, MlpBaseRecord,
+                     MappoResult, MlpBaseGruPolicy, MlpBaseGruRecord, MlpBaseGruState, MlpBasePolicy, MlpBasePolicyBank, MlpBasePolicyH512, MlpBaseRecord,
                      ValueNorm, chunk_indices, _ActsWithMappoPolicy, _CNN,
                      _Family, _FlatPolicy, _MLPBASE, _MappoRecord, _MappoRollouts, _act, _act_bank, _bank_call_args,
                      _call_args, _cnn_bank_call_args, _cnn_bank_workspace, _cnn_call_args, _kitchen_cells,

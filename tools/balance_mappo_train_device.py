@@ -8,6 +8,11 @@ of the weights.
     python tools/balance_mappo_train_device.py --num-envs 1024 --updates 20
     python tools/balance_mappo_train_device.py --evaluate --json run.json
     python tools/balance_mappo_train_device.py --recurrent --data-chunk-length 10
+    python tools/balance_mappo_train_device.py --hidden-size 512
+
+``--hidden-size 512``: the reference trainer's default width (``MlpBasePolicyH512``).  The rollout and ``--evaluate`` run on the
+device as at 64; there is no device update at this width, so the learning phase is ``autograd_update``: the same losses in torch
+autograd on ``policy.module()``, whose parameters are the flat tensor the next rollout reads, and two ``torch.optim.Adam``.
 
 ``--recurrent``: the reference's ``--use_recurrent_policy`` -- a GRU between the base and the head of both nets
 (``MlpBaseGruPolicy``); the running states are carried from rollout to rollout, the update evaluates chunks of
@@ -58,21 +63,61 @@ def evaluate(env, policy, seed=0):
     return {round(float(v), 6): int(c) for v, c in zip(values.tolist(), counts.tolist())}
 
 
+def autograd_update(module, actor_opt, critic_opt, value_norm, record, advantages, returns, indices, stats, clip_param, entropy_coef,
+                    value_loss_coef, max_grad_norm, huber_delta):
+    """``mappo_update``'s rows in torch autograd (``R_MAPPO.ppo_update``, train/MAPPO/r_mappo.py:91-164, with ValueNorm, the Huber
+    loss, the clipped value loss and ``max_grad_norm``): per row of ``indices`` both losses, two backward passes, two clips and two
+    Adam steps.  ``stats`` (rows, 8) receives the row's numbers in the order of ``_lib.MAPPO_STATS``; nothing waits."""
+    import torch
+    t = record.num_steps
+    obs, flat = record.obs[:t].view(-1, record.obs.shape[-1]), lambda a: a.reshape(-1)  # noqa: E731
+    actions, old_logp, old_v, adv, ret = flat(record.actions), flat(record.logprobs), flat(record.values[:t]), flat(advantages), flat(returns)
+
+    def huber(err):
+        return torch.where(err.abs() <= huber_delta, err ** 2 / 2, huber_delta * (err.abs() - huber_delta / 2))
+
+    for row, inds in enumerate(indices.long()):
+        x = obs[inds].float()
+        dist = torch.distributions.Categorical(logits=module.actor(x))
+        ratio = (dist.log_prob(actions[inds].long()) - old_logp[inds]).exp()
+        policy_loss = -torch.min(ratio * adv[inds], ratio.clamp(1.0 - clip_param, 1.0 + clip_param) * adv[inds]).mean()
+        entropy = dist.entropy().mean()
+        actor_opt.zero_grad()
+        (policy_loss - entropy * entropy_coef).backward()
+        actor_norm = torch.nn.utils.clip_grad_norm_(module.actor.parameters(), max_grad_norm)
+        actor_opt.step()
+        v, old = module.critic(x).squeeze(1), old_v[inds]
+        value_norm.update(ret[inds])
+        target = value_norm.normalize(ret[inds])
+        value_loss = torch.max(huber(target - v), huber(target - (old + (v - old).clamp(-clip_param, clip_param)))).mean()
+        critic_opt.zero_grad()
+        (value_loss * value_loss_coef).backward()
+        critic_norm = torch.nn.utils.clip_grad_norm_(module.critic.parameters(), max_grad_norm)
+        critic_opt.step()
+        with torch.no_grad():
+            clipfrac = ((ratio - 1.0).abs() > clip_param).float().mean()
+            stats[row] = torch.stack([value_loss, critic_norm, policy_loss, entropy, actor_norm, ratio.mean(), clipfrac, clipfrac * 0])
+
+
 def train(num_envs, num_steps, updates, seed, lr=5e-4, critic_lr=5e-4, lr_decay=False, gamma=0.99, gae_lambda=0.95, ppo_epoch=15,
           num_mini_batch=1, clip_param=0.2, entropy_coef=0.01, value_loss_coef=1.0, max_grad_norm=10.0, huber_delta=10.0, layer_N=2,
-          log=None, evaluation=None, final=None, policy=None, recurrent=False, data_chunk_length=10):
+          log=None, evaluation=None, final=None, policy=None, recurrent=False, data_chunk_length=10, hidden_size=64):
     """``updates`` iterations of collect, advantages, update with the reference's defaults (train/config.py).  One dict per
     update: the learning rates, the mean of every stat over the update's rows (``train_info``), the episodes finished during the
     update with their mean return, and ``optimizer_step``.  ``evaluation``: a dict that takes ``evaluate``'s histogram under
     "returns" after the last update.  ``final``: a dict that takes the final parameters (a CPU tensor) under "params".  ``policy``: an
     ``MlpBasePolicy`` of ``layer_N`` to train in place from the parameters it holds -- a member of an ``MlpBasePolicyBank``, say --
     instead of a fresh one initialised under ``seed``.  ``recurrent``: train an ``MlpBaseGruPolicy`` over chunks of
-    ``data_chunk_length`` steps, which must divide ``num_steps``."""
+    ``data_chunk_length`` steps, which must divide ``num_steps``.  ``hidden_size`` 512: an ``MlpBasePolicyH512``, collected on the
+    device and trained by ``autograd_update`` (``optimizer_step`` then counts its rows)."""
     import torch
     from madrona_rl_envs_playground_amd import _lib
     from madrona_rl_envs_playground_amd.simulators import (MappoOptimizer, MlpBaseActorCritic, MlpBaseGruActorCritic, MlpBaseGruPolicy,
-                                                             MlpBaseGruRecord, MlpBasePolicy, ValueNorm, chunk_indices, mappo_advantages,
-                                                             mappo_update, minibatch_indices)
+                                                             MlpBaseGruRecord, MlpBasePolicy, MlpBasePolicyH512, ValueNorm, chunk_indices,
+                                                             mappo_advantages, mappo_update, minibatch_indices)
+    wide = hidden_size == _lib.MLPBASE_HIDDEN_WIDE
+    if hidden_size not in (_lib.MLPBASE_HIDDEN, _lib.MLPBASE_HIDDEN_WIDE) or (wide and recurrent):
+        raise ValueError("hidden_size is 64 or 512, and the recurrent policy runs 64 only")
     env = make_env(num_envs)
     device = torch.device("cuda", 0)
     players = env.n_players
@@ -80,12 +125,21 @@ def train(num_envs, num_steps, updates, seed, lr=5e-4, critic_lr=5e-4, lr_decay=
         torch.manual_seed(seed)
         if recurrent:
             policy = MlpBaseGruPolicy.from_module(MlpBaseGruActorCritic(layer_N=layer_N), device=device)
+        elif wide:
+            policy = MlpBasePolicyH512.from_module(MlpBaseActorCritic(hidden=hidden_size, layer_N=layer_N), device=device)
         else:
             policy = MlpBasePolicy.from_module(MlpBaseActorCritic(layer_N=layer_N), device=device)
-    elif policy.layer_N != layer_N or isinstance(policy, MlpBaseGruPolicy) != bool(recurrent):
+    elif policy.layer_N != layer_N or isinstance(policy, MlpBaseGruPolicy) != bool(recurrent) or policy.hidden != hidden_size:
         raise ValueError(f"the policy has layer_N {policy.layer_N}, asked for {layer_N}; recurrent {bool(recurrent)} needs an "
                          f"{'MlpBaseGruPolicy' if recurrent else 'MlpBasePolicy'}")
-    optimizer = MappoOptimizer(policy, lr=lr, critic_lr=critic_lr)
+    if wide:
+        module = policy.module()  # (fc_h has no gradient: torch's Adam skips it, as the reference's does)
+        actor_opt = torch.optim.Adam(module.actor.parameters(), lr=lr, eps=1e-5)
+        critic_opt = torch.optim.Adam(module.critic.parameters(), lr=critic_lr, eps=1e-5)
+        optimizer = argparse.Namespace(lr=lr, critic_lr=critic_lr, step=0)
+        wide_stats = torch.zeros((ppo_epoch * num_mini_batch, len(_lib.MAPPO_STATS)), dtype=torch.float32, device=device)
+    else:
+        optimizer = MappoOptimizer(policy, lr=lr, critic_lr=critic_lr)
     value_norm = ValueNorm(device)
     shuffles = torch.Generator(device=device).manual_seed(seed)
     rows = ppo_epoch * num_mini_batch
@@ -104,10 +158,17 @@ def train(num_envs, num_steps, updates, seed, lr=5e-4, critic_lr=5e-4, lr_decay=
             indices = chunk_indices(record, num_mini_batch, ppo_epoch, generator=shuffles, device=device)
         else:
             indices = minibatch_indices(num_steps * num_envs * players, num_mini_batch, ppo_epoch, generator=shuffles, device=device)
-        result = mappo_update(policy, optimizer, record, None, advantages, returns, indices, value_norm=value_norm, clip_param=clip_param,
-                              entropy_coef=entropy_coef, value_loss_coef=value_loss_coef, max_grad_norm=max_grad_norm,
-                              huber_delta=huber_delta)
-        host_stats.copy_(result.stats, non_blocking=True)
+        if wide:
+            actor_opt.param_groups[0]["lr"], critic_opt.param_groups[0]["lr"] = optimizer.lr, optimizer.critic_lr
+            autograd_update(module, actor_opt, critic_opt, value_norm, record, advantages, returns, indices, wide_stats, clip_param,
+                            entropy_coef, value_loss_coef, max_grad_norm, huber_delta)
+            optimizer.step += rows
+            host_stats.copy_(wide_stats, non_blocking=True)
+        else:
+            result = mappo_update(policy, optimizer, record, None, advantages, returns, indices, value_norm=value_norm, clip_param=clip_param,
+                                  entropy_coef=entropy_coef, value_loss_coef=value_loss_coef, max_grad_norm=max_grad_norm,
+                                  huber_delta=huber_delta)
+            host_stats.copy_(result.stats, non_blocking=True)
         totals = env.episode_totals()  # the update's one host wait; the copy above lies in front of it on the same stream
         episodes = totals["episodes"]
         entry = {"update": update, "lr": optimizer.lr, "critic_lr": optimizer.critic_lr, "optimizer_step": optimizer.step,
@@ -137,6 +198,8 @@ def parser():
     ap.add_argument("--critic-lr", type=float, default=DEFAULTS["critic_lr"])
     ap.add_argument("--entropy-coef", type=float, default=DEFAULTS["entropy_coef"])
     ap.add_argument("--layer-N", type=int, default=DEFAULTS["layer_N"], choices=(1, 2))
+    ap.add_argument("--hidden-size", type=int, default=64, choices=(64, 512), help="512: the reference trainer's default width; it "
+                    "collects on the device and learns with torch autograd")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--recurrent", action="store_true", help="the recurrent actor-critic (the reference's --use_recurrent_policy)")
     ap.add_argument("--data-chunk-length", type=int, default=10, help="steps per chunk of the recurrent update (the reference's default)")
@@ -150,14 +213,14 @@ def main(argv=None):
     evaluation = {} if args.evaluate else None
     history = train(args.num_envs, args.num_steps, args.updates, args.seed, lr=args.lr, critic_lr=args.critic_lr, ppo_epoch=args.ppo_epoch,
                     num_mini_batch=args.num_mini_batch, entropy_coef=args.entropy_coef, layer_N=args.layer_N, evaluation=evaluation,
-                    recurrent=args.recurrent, data_chunk_length=args.data_chunk_length, log=lambda entry: print(json.dumps(entry), flush=True))
+                    recurrent=args.recurrent, data_chunk_length=args.data_chunk_length, hidden_size=args.hidden_size, log=lambda entry: print(json.dumps(entry), flush=True))
     if evaluation is not None:
         print(json.dumps({"greedy_returns": {str(k): v for k, v in evaluation["returns"].items()}}), flush=True)
     if args.json:
         from madrona_rl_envs_playground_amd import _lib
         settings = {name: getattr(args, name) for name in ("num_envs", "num_steps", "updates", "ppo_epoch", "num_mini_batch", "lr",
                                                            "critic_lr", "entropy_coef", "layer_N", "seed", "recurrent",
-                                                           "data_chunk_length")}
+                                                           "data_chunk_length", "hidden_size")}
         out = {"build_hash": _lib.build_hash(), "settings": settings, "updates": history,
                "mean_returns": [entry["mean_return"] for entry in history]}
         if evaluation is not None:
