@@ -1294,9 +1294,19 @@ int mrl_mappo_mlp_update(const mrl_mlpbase_policy *policy, const mrl_mappo_optim
  *     rows copied to record->obs, ACTION, and mrl_rollout_mlpbase's loop.
  *   MRL_ERR_INVALID, nothing enqueued: the plain act's and rollout's refusals, and the bit with hidden != 512; the bit together
  *     with MRL_MLPBASE_RECURRENT; the bit in mrl_mlpbase_bank.flags (mrl_mlpbase_act_bank, mrl_rollout_mlpbase_bank) or with
- *     mrl_mappo_mlp_bank_update; the bit in mrl_mappo_mlp_update.
- *   Not built: the device update at 512 (a 512 policy learns through torch autograd on the same flat tensor), the banks,
- *     cross-play and the GRU at 512, widths other than 64 and 512, layer_N above 2, PopArt, graph capture, sharded simulators. */
+ *     mrl_mappo_mlp_bank_update or mrl_mappo_mlp_bank_workspace_bytes.
+ *   The update: mrl_mappo_mlp_update with policy->hidden == 512 and policy->flags == MRL_MLPBASE_H512 exactly runs the LAYERED update
+ *     of this width -- the structs, argument list, losses, ValueNorm recurrence, clip, Adam, stats and grads
+ *     of mrl_mappo_mlp_update; the workspace is mrl_mappo_mlp_workspace_bytes(7, 512 | MRL_MLPBASE_H512_HIDDEN, layer_N, 4, B, K, out),
+ *     which stops growing at one slab of 2048 samples.  A row runs in slabs: the act's forward pass with every layer's row stored, the
+ *     loss head, one backward launch per hidden layer (dy on the matrix cores, LayerNorm backward in LDS), the weight gradients as
+ *     matrix products over the slab in eight shares, and a fold; every sum has one order and no float atomics, so the same inputs
+ *     give the same bits.  The unused fc_h block's gradient is zero and its parameters never change.  MRL_ERR_INVALID, nothing
+ *     changed: what mrl_mappo_mlp_update refuses, with hidden != 512 in place of hidden != 64; any policy flag beside the bit
+ *     (MRL_MLPBASE_RECURRENT included); a workspace smaller than the size query's; a capturing stream.  Without the bit in `hidden`
+ *     the size query refuses 512 as it always did.
+ *   Not built: the banks, cross-play and the GRU at 512, widths other than 64 and 512, layer_N above 2, PopArt, active masks,
+ *     graph capture, sharded simulators. */
 enum { MRL_MLPBASE_H512 = 32 };             /* bit of mrl_mlpbase_policy.flags: mrl_mlpbase_act and mrl_rollout_mlpbase run hidden 512 */
 enum { MRL_MLPBASE_H512_HIDDEN = 0x1000 };  /* or-ed into `hidden` = 512 in mrl_mlpbase_policy_num_params: the hidden-512 tensor */
 

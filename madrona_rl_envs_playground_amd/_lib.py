@@ -46,6 +46,7 @@ MLPBASE_VALUE_ONLY = 4  # MRL_MLPBASE_VALUE_ONLY: flag of mrl_mlpbase_act beside
 MLPBASE_HIDDEN, MLPBASE_OBS, MLPBASE_ACTIONS = 64, 7, 4  # the one shape mrl_mlpbase_act runs (layer_N 1 or 2)
 MLPBASE_HIDDEN_WIDE = 512  # the reference trainer's default hidden_size: mrl_mlpbase_act and mrl_rollout_mlpbase run it with MLPBASE_H512
 MLPBASE_H512, MLPBASE_H512_HIDDEN = 32, 0x1000  # MRL_MLPBASE_H512: bit of mrl_mlpbase_policy.flags; MRL_MLPBASE_H512_HIDDEN: or-ed into hidden = 512 in the size query
+MLPBASE_H512_SLAB = 2048  # kMlpH512Slab: a slab's samples in the hidden-512 MLPBase update (mlpbase_h512_update.hpp); its shares are H512_SHARES
 MLPBASE_RECURRENT = 16  # MRL_MLPBASE_RECURRENT: bit of mrl_mlpbase_policy.flags; the policy is then an mrl_mlpbase_gru_policy
 MLPBASE_GRU_LAYERS = 0x100  # MRL_MLPBASE_GRU_LAYERS: added to layer_N in the size queries for the recurrent shape
 MLPBASE_GRU_MAX_CHUNK = 16  # MRL_MLPBASE_GRU_MAX_CHUNK: the longest chunk mrl_mappo_mlp_update back-propagates through

@@ -194,7 +194,7 @@ class MlpBasePolicy(_FlatPolicy):
         if self.hidden != _lib.MLPBASE_HIDDEN:
             raise ValueError(f"{what}: the device update, the banks and the recurrent policy run hidden = {_lib.MLPBASE_HIDDEN} only; hidden = "
                              f"{self.hidden} (MlpBasePolicyH512) runs mlpbase_act, rollout_mlpbase and MlpBasePolicyAgent, and learns with "
-                             f"torch autograd on policy.module()")
+                             f"torch autograd on policy.module(), or on the device with MappoOptimizerH512 and mappo_update_h512")
 
     def desc(self):
         return _lib.MlpBasePolicyDesc(self.params.data_ptr(), self.hidden, self.layer_N, 0)
@@ -226,9 +226,9 @@ class MlpBasePolicyH512(MlpBasePolicy):
     floats for ``layer_N`` 2, 1 067 553 for 1, the unused ``fc_h`` included.  ``mlpbase_act``, ``rollout_mlpbase``, the env's ``act``
     / ``rollout``, ``MlpBaseRecord``, ``mappo_advantages`` and ``MlpBasePolicyAgent`` take it as they take the plain policy.
     ``module()`` returns an ``MlpBaseActorCritic`` over VIEWS of ``params``, whose ``actor.load_state_dict`` / ``critic.load_state_dict``
-    take a default-width reference checkpoint; ``load_(module)`` copies another module's parameters in.  It LEARNS through torch
-    autograd on ``module()``: ``MappoOptimizer``, ``mappo_update``, ``mappo_update_bank``, ``MlpBasePolicyBank`` and
-    ``MlpBaseGruPolicy`` run hidden 64 only and refuse this width."""
+    take a default-width reference checkpoint; ``load_(module)`` copies another module's parameters in.  It LEARNS on the device
+    with ``MappoOptimizerH512`` and ``mappo_update_h512``, or through torch autograd on ``module()``: ``MappoOptimizer``,
+    ``mappo_update``, ``mappo_update_bank``, ``MlpBasePolicyBank`` and ``MlpBaseGruPolicy`` run hidden 64 only and refuse this width."""
 
     _module_name = f"an MlpBaseActorCritic of hidden = {_lib.MLPBASE_HIDDEN_WIDE}"
     _desc_flags = _lib.MLPBASE_H512  # the bit every descriptor of this kind of policy carries, a rollout's included
@@ -258,6 +258,13 @@ class MlpBasePolicyH512(MlpBasePolicy):
 
     def desc(self):
         return _lib.MlpBasePolicyDesc(self.params.data_ptr(), self.hidden, self.layer_N, self._desc_flags)
+
+    def _mappo_workspace_bytes(self, minibatch_size, num_minibatches, out, members=None):
+        """``mrl_mappo_mlp_workspace_bytes`` with ``512 | MRL_MLPBASE_H512_HIDDEN``; there is no bank update at this width"""
+        if members is not None:
+            self._need_hidden_64("mappo_update_bank")
+        return _lib.lib().mrl_mappo_mlp_workspace_bytes(self.obs_dim, self.hidden | _lib.MLPBASE_H512_HIDDEN, self.layer_N, self.num_actions,
+                                                        minibatch_size, num_minibatches, out)
 
 
 class MlpBaseRecord(_MappoRecord):
@@ -1036,20 +1043,32 @@ def _mappo_run(layered, policy, optimizer, record, ring, advantages, returns, in
 
 
 class MappoOptimizerH512(_AdamState):
-    """``MappoOptimizer`` for a ``CnnPolicy`` of ``hidden`` 512, the reference trainer's default width: the same state and
-    attributes, and the scratch the layered update (``mrl_mappo_update`` with ``MRL_MAPPO_H512``) asks for (one slab of ``_lib.H512_SLAB`` samples' activations for both
+    """``MappoOptimizer`` for a ``CnnPolicy`` of ``hidden`` 512 or an ``MlpBasePolicyH512``, the reference trainer's default width: the
+    same state and attributes, and the scratch the layered update (``mrl_mappo_update`` with ``MRL_MAPPO_H512``, ``mrl_mappo_mlp_update``
+    with ``MRL_MLPBASE_H512``) asks for (one slab of ``_lib.H512_SLAB`` / ``_lib.MLPBASE_H512_SLAB`` samples' activations for both
     nets, whatever the minibatch size beyond that).  It accepts no other policy; ``MappoOptimizer`` accepts no such policy."""
 
+    @staticmethod
+    def _trains(policy):
+        """a policy the layered updates train: a plain ``CnnPolicy`` of hidden 512 or an ``MlpBasePolicyH512``"""
+        if isinstance(policy, MlpBasePolicyH512):
+            return True
+        return isinstance(policy, CnnPolicy) and not isinstance(policy, CnnGruPolicy) and policy.hidden == _lib.CNN_HIDDEN_WIDE
+
     def __init__(self, policy, lr=5e-4, critic_lr=5e-4, betas=(0.9, 0.999), eps=1e-5):
-        if not isinstance(policy, CnnPolicy) or isinstance(policy, CnnGruPolicy) or policy.hidden != _lib.CNN_HIDDEN_WIDE:
-            raise ValueError(f"MappoOptimizerH512: policy must be a plain CnnPolicy of hidden = {_lib.CNN_HIDDEN_WIDE}; hidden = "
-                             f"{_lib.CNN_HIDDEN} and the recurrent policy learn with MappoOptimizer and mappo_update")
+        if not self._trains(policy):
+            raise ValueError(f"MappoOptimizerH512: policy must be a plain CnnPolicy of hidden = {_lib.CNN_HIDDEN_WIDE} or an MlpBasePolicyH512; "
+                             f"hidden = {_lib.CNN_HIDDEN} and the recurrent policies learn with MappoOptimizer and mappo_update")
         super().__init__(policy, betas, eps)
         self.lr, self.critic_lr = float(lr), float(critic_lr)
 
     def workspace_bytes(self, minibatch_size, num_minibatches):
-        """``mrl_mappo_workspace_bytes`` with ``512 | MRL_MAPPO_H512_HIDDEN`` for this policy's kitchen."""
+        """``mrl_mappo_workspace_bytes`` with ``512 | MRL_MAPPO_H512_HIDDEN`` for this policy's kitchen, or
+        ``mrl_mappo_mlp_workspace_bytes`` with ``512 | MRL_MLPBASE_H512_HIDDEN`` for an ``MlpBasePolicyH512``."""
         p, out = self.policy, ctypes.c_uint64(0)
+        if isinstance(p, MlpBasePolicyH512):
+            _lib.check(p._mappo_workspace_bytes(int(minibatch_size), int(num_minibatches), ctypes.byref(out)))
+            return int(out.value)
         _lib.check(_lib.lib().mrl_mappo_workspace_bytes(p.width, p.height, p.channels, p.hidden | _lib.MAPPO_H512_HIDDEN, int(minibatch_size),
                                                         int(num_minibatches), ctypes.byref(out)))
         return int(out.value)
@@ -1061,11 +1080,13 @@ def mappo_update_h512(policy, optimizer, record, ring, advantages, returns, indi
     """``mappo_update`` for a ``CnnPolicy`` of ``hidden`` 512 and its ``MappoOptimizerH512`` (``mrl_mappo_update`` with ``MRL_MAPPO_H512``): the same
     arguments, losses, ValueNorm, clip, Adam and ``MappoResult``, on the device, enqueued on torch's current stream.  ``record`` and
     ``ring`` are what ``rollout_cnn`` filled under the policy.  Each row runs in slabs of ``_lib.H512_SLAB`` samples, a launch per
-    layer.  Not built at this width: banks, the recurrent policy, active masks, graph capture."""
-    if (not isinstance(policy, CnnPolicy) or isinstance(policy, CnnGruPolicy) or policy.hidden != _lib.CNN_HIDDEN_WIDE or
-            not isinstance(optimizer, MappoOptimizerH512) or optimizer.policy is not policy):
-        raise ValueError(f"mappo_update_h512: policy must be a plain CnnPolicy of hidden = {_lib.CNN_HIDDEN_WIDE} and optimizer the "
-                         f"MappoOptimizerH512 made for it; every other policy learns with MappoOptimizer and mappo_update")
-    return _mappo_run(_lib.MAPPO_H512, policy, optimizer, record, ring, advantages, returns, indices, value_norm, clip_param,
+    layer.  For an ``MlpBasePolicyH512`` (the balance beam; ``mrl_mappo_mlp_update`` with ``MRL_MLPBASE_H512``,
+    DESIGN.md section 33) ``record`` is an ``MlpBaseRecord`` the policy's ``rollout_mlpbase`` filled and ``ring`` must be ``None``.
+    Not built at this width: banks, the recurrent policy, active masks, graph capture."""
+    if not MappoOptimizerH512._trains(policy) or not isinstance(optimizer, MappoOptimizerH512) or optimizer.policy is not policy:
+        raise ValueError(f"mappo_update_h512: policy must be a plain CnnPolicy of hidden = {_lib.CNN_HIDDEN_WIDE} or an MlpBasePolicyH512 and "
+                         f"optimizer the MappoOptimizerH512 made for it; every other policy learns with MappoOptimizer and mappo_update")
+    # an MlpBasePolicyH512's descriptor carries its bit already
+    return _mappo_run(0 if isinstance(policy, MlpBasePolicyH512) else _lib.MAPPO_H512, policy, optimizer, record, ring, advantages, returns, indices, value_norm, clip_param,
                       entropy_coef, value_loss_coef, max_grad_norm, huber_delta, use_huber_loss, use_clipped_value_loss, use_max_grad_norm,
                       stats, grads)

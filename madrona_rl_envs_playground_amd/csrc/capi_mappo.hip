@@ -13,6 +13,7 @@
 #include "mlpbase_bank.hpp"
 #include "mlpbase_gru.hpp"
 #include "mlpbase_h512.hpp"
+#include "mlpbase_h512_update.hpp"
 #include "mlpbase_update.hpp"
 
 #include <type_traits>
@@ -51,6 +52,16 @@ static const char *mappo_h512_shape_error(uint32_t width, uint32_t height, uint3
 static const char *mappo_mlp_shape_error(uint32_t obs_dim, uint32_t hidden, uint32_t layer_N, uint32_t num_actions, uint32_t minibatch_size)
 {
     if (hidden != mrl::kMlpBaseHidden) return "hidden must be 64";
+    if (layer_N < 1 || layer_N > mrl::kMlpBaseMaxLayerN) return "layer_N must be 1 or 2";
+    if (obs_dim != mrl::kMlpBaseObs || num_actions != mrl::kMlpBaseActions) return "obs_dim must be 7 and num_actions 4";
+    if (minibatch_size == 0) return "minibatch_size must be positive";
+    return nullptr;
+}
+
+// what mrl_mappo_mlp_workspace_bytes with 512 | MRL_MLPBASE_H512_HIDDEN and mrl_mappo_mlp_update with MRL_MLPBASE_H512 refuse alike
+static const char *mappo_mlp_h512_shape_error(uint32_t obs_dim, uint32_t hidden, uint32_t layer_N, uint32_t num_actions, uint32_t minibatch_size)
+{
+    if (hidden != mrl::kMlpH512Hidden) return "MRL_MLPBASE_H512 needs hidden = 512";
     if (layer_N < 1 || layer_N > mrl::kMlpBaseMaxLayerN) return "layer_N must be 1 or 2";
     if (obs_dim != mrl::kMlpBaseObs || num_actions != mrl::kMlpBaseActions) return "obs_dim must be 7 and num_actions 4";
     if (minibatch_size == 0) return "minibatch_size must be positive";
@@ -491,6 +502,26 @@ struct MlpBaseH512Net : MlpBaseNet {
     static constexpr auto launch_act = launch_mlpbase_act_h512;
 };
 
+// The MLPBase at hidden 512 as mrl_mappo_mlp_update sees it (MRL_MLPBASE_H512 taken out of the flags; mlpbase_h512_update.hpp):
+// mappo_update's refusals with the layered update's own shape check, workspace and launches.  It trains one policy: no members.
+struct MlpBaseH512UpdateNet : MlpBaseNet {
+    static constexpr const char *kSizer = "mrl_mappo_mlp_workspace_bytes with 512 | MRL_MLPBASE_H512_HIDDEN";
+    static const char *shape_error(const UpdatePolicy &p, uint32_t minibatch_size, char *described, size_t room)
+    {
+        snprintf(described, room, "hidden %u, layer_N %u", p.hidden, p.layer_N);
+        return mappo_mlp_h512_shape_error(kMlpBaseObs, p.hidden, p.layer_N, kMlpBaseActions, minibatch_size);
+    }
+    static uint64_t actor_params(const UpdatePolicy &p) { return (uint64_t)mlpbase_h512_net_params(p.layer_N, kMlpBaseActions); }
+    static uint64_t num_params(const UpdatePolicy &p) { return actor_params(p) + mlpbase_h512_net_params(p.layer_N, 1); }
+    static uint64_t workspace_floats(const UpdatePolicy &p, uint32_t B, uint32_t K) { return mlp_h512_workspace(p.layer_N, B, K).total; }
+    static void launch_update(const UpdatePolicy &p, const mrl_mappo_optimizer &opt, const Batch &batch, const int32_t *indices, uint32_t K,
+                              uint32_t B, const mrl_mappo_config &cfg, float *value_norm_state, float *workspace, float *stats, float *grads,
+                              hipStream_t stream, const MappoMembers &)
+    {
+        launch_mappo_mlp_h512_update(p.layer_N, opt, batch, indices, K, B, cfg, value_norm_state, workspace, stats, grads, stream);
+    }
+};
+
 // The recurrent MLPBase as the update sees it (mrl_mappo_mlp_update with MRL_MLPBASE_RECURRENT): MlpBaseNet's refusals on the
 // structs the extended ones begin with; the rows are chunk ids, the workspace and the launch the recurrent update's.
 struct MlpBaseGruNet : MlpBaseNet {
@@ -625,10 +656,9 @@ static int mlpbase_h512_policy(const char *what, const mrl_mlpbase_policy *polic
     return MRL_OK;
 }
 
-// what the update and the bank update of the MLPBase say to a policy with the bit
-static constexpr const char *kMlpH512NoUpdate = "MRL_MLPBASE_H512: the device update runs hidden 64; a hidden-512 policy acts and rolls out "
-                                                "on the device (mrl_mlpbase_act, mrl_rollout_mlpbase) and learns through torch autograd on "
-                                                "the same flat tensor";
+// what the bank update of the MLPBase says to a policy with the bit
+static constexpr const char *kMlpH512NoUpdate = "MRL_MLPBASE_H512: the bank update runs hidden 64; a hidden-512 policy learns alone, through "
+                                                "mrl_mappo_mlp_update with hidden = 512 and this bit as its only flag";
 
 // ---- the recurrent MLPBase: mrl_mlpbase_act and mrl_rollout_mlpbase with MRL_MLPBASE_RECURRENT in the policy's flags ----
 
@@ -1034,6 +1064,18 @@ int mrl_mappo_workspace_bytes(uint32_t width, uint32_t height, uint32_t channels
 int mrl_mappo_mlp_workspace_bytes(uint32_t obs_dim, uint32_t hidden, uint32_t layer_N, uint32_t num_actions, uint32_t minibatch_size,
                                   uint32_t num_minibatches, uint64_t *out)
 {
+    // the layered update's shape: 512 | MRL_MLPBASE_H512_HIDDEN (mlpbase_h512_update.hpp)
+    if (hidden & MRL_MLPBASE_H512_HIDDEN) {
+        const char *why = out ? mappo_mlp_h512_shape_error(obs_dim, hidden & ~(uint32_t)MRL_MLPBASE_H512_HIDDEN, layer_N, num_actions, minibatch_size)
+                              : "null output pointer";
+        if (why) {
+            mrl::set_error("mrl_mappo_mlp_workspace_bytes with MRL_MLPBASE_H512_HIDDEN: %s (obs_dim %u, layer_N %u, num_actions %u, minibatch_size %u)",
+                           why, obs_dim, layer_N, num_actions, minibatch_size);
+            return MRL_ERR_INVALID;
+        }
+        *out = mrl::mlp_h512_workspace(layer_N, minibatch_size, num_minibatches).total * sizeof(float);
+        return MRL_OK;
+    }
     // the recurrent shape: layer_N + MRL_MLPBASE_GRU_LAYERS
     const uint32_t gru = layer_N - MRL_MLPBASE_GRU_LAYERS;
     if (out && gru >= 1 && gru <= mrl::kMlpBaseMaxLayerN && !mappo_mlp_shape_error(obs_dim, hidden, gru, num_actions, minibatch_size)) {
@@ -1183,7 +1225,19 @@ int mrl_mappo_mlp_update(const mrl_mlpbase_policy *policy, const mrl_mappo_optim
                          uint32_t num_minibatches, uint32_t minibatch_size, const mrl_mappo_config *cfg, float *value_norm_state, void *workspace_dev,
                          uint64_t workspace_bytes, float *stats_dev_or_null, float *grads_dev_or_null, int gpu_id, void *hip_stream)
 {
-    if (policy && (policy->flags & MRL_MLPBASE_H512)) return mrl::refusal("mrl_mappo_mlp_update", mrl::kMlpH512NoUpdate);
+    // the layered update of hidden 512: the bit taken out, no other flag admitted; every other refusal and its order are mappo_update's
+    if (policy && (policy->flags & MRL_MLPBASE_H512)) {
+        const char *what = "mrl_mappo_mlp_update";
+        mrl_mlpbase_policy plain = *policy;
+        plain.flags &= ~(uint32_t)MRL_MLPBASE_H512;
+        if (plain.flags)
+            return mrl::refusal(what, plain.flags & MRL_MLPBASE_RECURRENT
+                                          ? "MRL_MLPBASE_H512 does not go with MRL_MLPBASE_RECURRENT: the GRU runs hidden 64"
+                                          : "MRL_MLPBASE_H512 must be the policy's only flag");
+        return mrl::mappo_update<mrl::MlpBaseH512UpdateNet>(what, &plain, opt, batch, indices_dev, num_minibatches, minibatch_size, cfg,
+                                                            value_norm_state, workspace_dev, workspace_bytes, stats_dev_or_null,
+                                                            grads_dev_or_null, gpu_id, hip_stream);
+    }
     if (policy && (policy->flags & MRL_MLPBASE_RECURRENT))
         return mrl::gru_update("mrl_mappo_mlp_update", reinterpret_cast<const mrl_mlpbase_gru_policy *>(policy), opt,
                                reinterpret_cast<const mrl_mappo_mlp_gru_batch *>(batch), indices_dev, num_minibatches, minibatch_size, cfg,
@@ -1214,6 +1268,7 @@ int mrl_mappo_bank_workspace_bytes(uint32_t width, uint32_t height, uint32_t cha
 int mrl_mappo_mlp_bank_workspace_bytes(uint32_t obs_dim, uint32_t hidden, uint32_t layer_N, uint32_t num_actions, uint32_t minibatch_size,
                                        uint32_t num_minibatches, uint32_t num_members, uint64_t *out)
 {
+    if (hidden & MRL_MLPBASE_H512_HIDDEN) return mrl::refusal("mrl_mappo_mlp_bank_workspace_bytes", mrl::kMlpH512NoUpdate);
     return mrl::bank_workspace_bytes<MlpBaseNet>("mrl_mappo_mlp_bank_workspace_bytes", obs_dim, hidden, layer_N, num_actions, minibatch_size,
                                                  num_minibatches, num_members, out);
 }

@@ -211,15 +211,6 @@ __global__ void __launch_bounds__(kMappoThreads) mrl_h512_loss(H512LossArgs g)
 
 // ---------------------------------------------------------------- the weight gradients of the linear layers
 
-struct H512DwArgs {
-    const float *a, *b;  // net 0's A (nrows x lda: dL/d(pre-activation)) and B (nrows x ldb: the layer's input)
-    float *partial;      // (2, kH512Shares, stride)
-    uint64_t a_net, b_net, stride, w_at, bias_at[2];  // floats from net 0's operand to net 1's; where dW and db start in a vector
-    uint32_t lda, ldb, a_cols;  // a_cols: A's valid columns, a multiple of 4
-    uint32_t m[2], n;           // C is m[net] x n; n a multiple of 128
-    uint32_t nrows, share;      // the slab's samples in whole tiles; samples per share
-};
-
 // 32 samples x 128 columns from `src` (rows ld floats apart, `cols` valid columns from col0 on) into registers
 __device__ __forceinline__ void dw_fetch(const float *__restrict__ src, uint32_t ld, uint32_t col0, uint32_t cols, uint32_t tid, f32x4u (&p)[4])
 {
@@ -496,6 +487,13 @@ __global__ void __launch_bounds__(kAdamThreads) mrl_h512_fold(H512FoldArgs g)
 }
 
 }  // namespace
+
+void launch_h512_dw(const H512DwArgs &args, hipStream_t stream)
+{
+    const uint32_t rows = args.m[0] > args.m[1] ? args.m[0] : args.m[1];
+    hipLaunchKernelGGL(mrl_h512_dw, dim3(args.n / 128u, (rows + 127u) / 128u, 2u * kH512Shares), dim3(kCnnThreads), 0, stream, args);
+    MRL_HIP(hipGetLastError());
+}
 
 void launch_mappo_h512_update(const mrl_mappo_policy &policy, const mrl_mappo_optimizer &opt, const mrl_mappo_batch &batch,
                               const int32_t *indices, uint32_t num_minibatches, uint32_t minibatch_size, const mrl_mappo_config &cfg,

@@ -75,6 +75,20 @@ inline uint32_t h512_update_lds(uint32_t W, uint32_t H, uint32_t F)
     return forward > conv ? forward : conv;
 }
 
+// A weight gradient C = A^T B of a linear layer with k = a slab's samples, and db as the same product against ones
+// (mrl_h512_dw in cnn_h512_update.hip): the sum order above.  The hidden-512 MLPBase update (mlpbase_h512_update.hip) launches it
+// for its own layers.
+struct H512DwArgs {
+    const float *a, *b;  // net 0's A (nrows x lda: dL/d(pre-activation)) and B (nrows x ldb: the layer's input)
+    float *partial;      // (2, kH512Shares, stride)
+    uint64_t a_net, b_net, stride, w_at, bias_at[2];  // floats from net 0's operand to net 1's; where dW and db start in a vector
+    uint32_t lda, ldb, a_cols;  // a_cols: A's valid columns, a multiple of 4
+    uint32_t m[2], n;           // C is m[net] x n; n a multiple of 128
+    uint32_t nrows, share;      // the slab's samples in whole tiles; samples per share
+};
+// one launch for both nets and every share; the rows past the slab's samples up to nrows must be zero rows of A and finite in B
+void launch_h512_dw(const H512DwArgs &args, hipStream_t stream);
+
 // K rows enqueued on `stream`; every argument has been validated (capi_mappo.hip, mrl_mappo_h512_update)
 void launch_mappo_h512_update(const mrl_mappo_policy &policy, const mrl_mappo_optimizer &opt, const mrl_mappo_batch &batch,
                               const int32_t *indices, uint32_t num_minibatches, uint32_t minibatch_size, const mrl_mappo_config &cfg,

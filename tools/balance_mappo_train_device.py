@@ -11,8 +11,9 @@ of the weights.
     python tools/balance_mappo_train_device.py --hidden-size 512
 
 ``--hidden-size 512``: the reference trainer's default width (``MlpBasePolicyH512``).  The rollout and ``--evaluate`` run on the
-device as at 64; there is no device update at this width, so the learning phase is ``autograd_update``: the same losses in torch
-autograd on ``policy.module()``, whose parameters are the flat tensor the next rollout reads, and two ``torch.optim.Adam``.
+device as at 64.  The learning phase is ``autograd_update`` -- the same losses in torch autograd on ``policy.module()``, whose
+parameters are the flat tensor the next rollout reads, and two ``torch.optim.Adam`` -- or, with ``--device-update``, the layered
+device update (``MappoOptimizerH512`` and ``mappo_update_h512``; profiles/mlpbase_h512_update_cost.json holds the two paths' cost).
 
 ``--recurrent``: the reference's ``--use_recurrent_policy`` -- a GRU between the base and the head of both nets
 (``MlpBaseGruPolicy``); the running states are carried from rollout to rollout, the update evaluates chunks of
@@ -101,7 +102,8 @@ def autograd_update(module, actor_opt, critic_opt, value_norm, record, advantage
 
 def train(num_envs, num_steps, updates, seed, lr=5e-4, critic_lr=5e-4, lr_decay=False, gamma=0.99, gae_lambda=0.95, ppo_epoch=15,
           num_mini_batch=1, clip_param=0.2, entropy_coef=0.01, value_loss_coef=1.0, max_grad_norm=10.0, huber_delta=10.0, layer_N=2,
-          log=None, evaluation=None, final=None, policy=None, recurrent=False, data_chunk_length=10, hidden_size=64):
+          log=None, evaluation=None, final=None, policy=None, recurrent=False, data_chunk_length=10, hidden_size=64,
+          device_update=False):
     """``updates`` iterations of collect, advantages, update with the reference's defaults (train/config.py).  One dict per
     update: the learning rates, the mean of every stat over the update's rows (``train_info``), the episodes finished during the
     update with their mean return, and ``optimizer_step``.  ``evaluation``: a dict that takes ``evaluate``'s histogram under
@@ -109,14 +111,17 @@ def train(num_envs, num_steps, updates, seed, lr=5e-4, critic_lr=5e-4, lr_decay=
     ``MlpBasePolicy`` of ``layer_N`` to train in place from the parameters it holds -- a member of an ``MlpBasePolicyBank``, say --
     instead of a fresh one initialised under ``seed``.  ``recurrent``: train an ``MlpBaseGruPolicy`` over chunks of
     ``data_chunk_length`` steps, which must divide ``num_steps``.  ``hidden_size`` 512: an ``MlpBasePolicyH512``, collected on the
-    device and trained by ``autograd_update`` (``optimizer_step`` then counts its rows)."""
+    device and trained by ``autograd_update`` (``optimizer_step`` then counts its rows), or with ``device_update`` by
+    ``mappo_update_h512``."""
     import torch
     from madrona_rl_envs_playground_amd import _lib
-    from madrona_rl_envs_playground_amd.simulators import (MappoOptimizer, MlpBaseActorCritic, MlpBaseGruActorCritic, MlpBaseGruPolicy,
+    from madrona_rl_envs_playground_amd.simulators import (MappoOptimizer, MappoOptimizerH512, mappo_update_h512, MlpBaseActorCritic, MlpBaseGruActorCritic, MlpBaseGruPolicy,
                                                              MlpBaseGruRecord, MlpBasePolicy, MlpBasePolicyH512, ValueNorm, chunk_indices,
                                                              mappo_advantages, mappo_update, minibatch_indices)
-    wide = hidden_size == _lib.MLPBASE_HIDDEN_WIDE
-    if hidden_size not in (_lib.MLPBASE_HIDDEN, _lib.MLPBASE_HIDDEN_WIDE) or (wide and recurrent):
+    wide = hidden_size == _lib.MLPBASE_HIDDEN_WIDE and not device_update  # (wide: the autograd path)
+    if device_update and hidden_size != _lib.MLPBASE_HIDDEN_WIDE:
+        raise ValueError("device_update chooses the update of hidden_size 512; 64 always learns on the device")
+    if hidden_size not in (_lib.MLPBASE_HIDDEN, _lib.MLPBASE_HIDDEN_WIDE) or (hidden_size == _lib.MLPBASE_HIDDEN_WIDE and recurrent):
         raise ValueError("hidden_size is 64 or 512, and the recurrent policy runs 64 only")
     env = make_env(num_envs)
     device = torch.device("cuda", 0)
@@ -125,7 +130,7 @@ def train(num_envs, num_steps, updates, seed, lr=5e-4, critic_lr=5e-4, lr_decay=
         torch.manual_seed(seed)
         if recurrent:
             policy = MlpBaseGruPolicy.from_module(MlpBaseGruActorCritic(layer_N=layer_N), device=device)
-        elif wide:
+        elif hidden_size == _lib.MLPBASE_HIDDEN_WIDE:
             policy = MlpBasePolicyH512.from_module(MlpBaseActorCritic(hidden=hidden_size, layer_N=layer_N), device=device)
         else:
             policy = MlpBasePolicy.from_module(MlpBaseActorCritic(layer_N=layer_N), device=device)
@@ -139,7 +144,8 @@ def train(num_envs, num_steps, updates, seed, lr=5e-4, critic_lr=5e-4, lr_decay=
         optimizer = argparse.Namespace(lr=lr, critic_lr=critic_lr, step=0)
         wide_stats = torch.zeros((ppo_epoch * num_mini_batch, len(_lib.MAPPO_STATS)), dtype=torch.float32, device=device)
     else:
-        optimizer = MappoOptimizer(policy, lr=lr, critic_lr=critic_lr)
+        optimizer = (MappoOptimizerH512 if device_update else MappoOptimizer)(policy, lr=lr, critic_lr=critic_lr)
+    run_update = mappo_update_h512 if device_update else mappo_update
     value_norm = ValueNorm(device)
     shuffles = torch.Generator(device=device).manual_seed(seed)
     rows = ppo_epoch * num_mini_batch
@@ -165,7 +171,7 @@ def train(num_envs, num_steps, updates, seed, lr=5e-4, critic_lr=5e-4, lr_decay=
             optimizer.step += rows
             host_stats.copy_(wide_stats, non_blocking=True)
         else:
-            result = mappo_update(policy, optimizer, record, None, advantages, returns, indices, value_norm=value_norm, clip_param=clip_param,
+            result = run_update(policy, optimizer, record, None, advantages, returns, indices, value_norm=value_norm, clip_param=clip_param,
                                   entropy_coef=entropy_coef, value_loss_coef=value_loss_coef, max_grad_norm=max_grad_norm,
                                   huber_delta=huber_delta)
             host_stats.copy_(result.stats, non_blocking=True)
@@ -199,7 +205,8 @@ def parser():
     ap.add_argument("--entropy-coef", type=float, default=DEFAULTS["entropy_coef"])
     ap.add_argument("--layer-N", type=int, default=DEFAULTS["layer_N"], choices=(1, 2))
     ap.add_argument("--hidden-size", type=int, default=64, choices=(64, 512), help="512: the reference trainer's default width; it "
-                    "collects on the device and learns with torch autograd")
+                    "collects on the device and learns with torch autograd, or with --device-update on the device")
+    ap.add_argument("--device-update", action="store_true", help="with --hidden-size 512: learn with mappo_update_h512 instead of torch autograd")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--recurrent", action="store_true", help="the recurrent actor-critic (the reference's --use_recurrent_policy)")
     ap.add_argument("--data-chunk-length", type=int, default=10, help="steps per chunk of the recurrent update (the reference's default)")
@@ -213,14 +220,14 @@ def main(argv=None):
     evaluation = {} if args.evaluate else None
     history = train(args.num_envs, args.num_steps, args.updates, args.seed, lr=args.lr, critic_lr=args.critic_lr, ppo_epoch=args.ppo_epoch,
                     num_mini_batch=args.num_mini_batch, entropy_coef=args.entropy_coef, layer_N=args.layer_N, evaluation=evaluation,
-                    recurrent=args.recurrent, data_chunk_length=args.data_chunk_length, hidden_size=args.hidden_size, log=lambda entry: print(json.dumps(entry), flush=True))
+                    recurrent=args.recurrent, data_chunk_length=args.data_chunk_length, hidden_size=args.hidden_size, device_update=args.device_update, log=lambda entry: print(json.dumps(entry), flush=True))
     if evaluation is not None:
         print(json.dumps({"greedy_returns": {str(k): v for k, v in evaluation["returns"].items()}}), flush=True)
     if args.json:
         from madrona_rl_envs_playground_amd import _lib
         settings = {name: getattr(args, name) for name in ("num_envs", "num_steps", "updates", "ppo_epoch", "num_mini_batch", "lr",
                                                            "critic_lr", "entropy_coef", "layer_N", "seed", "recurrent",
-                                                           "data_chunk_length", "hidden_size")}
+                                                           "data_chunk_length", "hidden_size", "device_update")}
         out = {"build_hash": _lib.build_hash(), "settings": settings, "updates": history,
                "mean_returns": [entry["mean_return"] for entry in history]}
         if evaluation is not None:
